@@ -12,6 +12,10 @@ escape or are absorbed, tallies + 50x50 receiver flux map + receiver hit list ac
 Rays are sharded over the GPUs by stream id (weak scaling: every rank traces `--rays` rays per step); the only
 exchange is ONE all-reduce (RCCL) of the packed tally buffer at the end of the job.
 
+--dump-outputs DIR (single process) writes, after the timed steps, what the last timed step computed as DIR/<name>.npy in
+float64: the per-surface tallies, the receiver's flux map, the segment count and a fixed, seeded sample of the receiver's hit
+list (dump_outputs).  The inputs of a step depend only on the arguments, so two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0: metric/value/unit per BASELINE.json, plus
   roofline      algorithmic HBM bytes of the fast engine (112 B per ray segment) over the time of its
                 kernels for one step, measured with HIP events on the launch stream, against the 8 TB/s HBM peak;
@@ -193,6 +197,34 @@ def sq_counters_for(n):
         return None
 
 
+DUMP_MAX_HITS = 1 << 20    # receiver hits kept by --dump-outputs: 32 MB of float64 (energy + hit point)
+
+
+def dump_outputs(out_dir, tallies, fluxmap, hits, segments, seed=2024):
+    """
+    Write the outputs of one trc_trace_fast call on the NSTTF scene as out_dir/<name>.npy, float64:
+      absorbed, received, hit_count   per surface (trc_scene_get_tallies)
+      receiver_fluxmap                the 50x50 flux map of the receiver
+      segments                        ray segments traced, shape (1,)
+      receiver_hit_energy, receiver_hit_points   the receiver's hit list (absorbed energy; x, y, z as rows), sorted by
+                                      (x, y, z, energy) since the device delivers hits in arrival order; above DUMP_MAX_HITS
+                                      hits a sample of that many, chosen by a generator seeded with `seed`, in sorted order
+    Returns the names written.
+    """
+    import numpy as N
+    os.makedirs(out_dir, exist_ok=True)
+    a, r, h = tallies
+    e, p = N.asarray(hits['e_abs'], dtype=N.float64), N.asarray(hits['points'], dtype=N.float64)
+    order = N.lexsort((e, p[2], p[1], p[0]))
+    if len(order) > DUMP_MAX_HITS:
+        order = order[N.sort(N.random.default_rng(seed).choice(len(order), DUMP_MAX_HITS, replace=False))]
+    arrays = {'absorbed': a, 'received': r, 'hit_count': h, 'receiver_fluxmap': fluxmap, 'segments': [segments],
+              'receiver_hit_energy': e[order], 'receiver_hit_points': p[:, order]}
+    for name, arr in arrays.items():
+        N.save(os.path.join(out_dir, name + '.npy'), N.ascontiguousarray(arr, dtype=N.float64))
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -211,7 +243,10 @@ def main():
                          "a step (distributed.shard), results identical for every number of GPUs")
     ap.add_argument('--kernel', choices=['auto', 'stream', 'megakernel'], default='auto',
                     help='fast-engine form: streaming kernels (default at this size) or the single persistent kernel')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy (single process only)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.cpu_worker:
         print(json.dumps(cpu_worker(int(args.cpu_worker[0]), int(args.cpu_worker[1]), int(args.cpu_worker[2]))), flush=True)
@@ -224,6 +259,8 @@ def main():
     if world != args.gpus:
         log('note: WORLD_SIZE=%d but --gpus %d; using WORLD_SIZE' % (world, args.gpus))
     n = int(args.rays)
+    if args.dump_outputs and world > 1:
+        ap.error('--dump-outputs needs a single process')
 
     cpu = None
     if rank == 0 and world == 1 and args.cpu_rays > 0:
@@ -296,7 +333,16 @@ def main():
     t0 = time.time()
     seg = 0
     kms = 0.0
+    aside = 0.0
     for k in range(args.steps):
+        if args.dump_outputs and k == args.steps - 1:
+            # the last step's own tallies and hits for the dump: those of the steps before are set aside and added back afterwards
+            # (trc_trace_fast has synchronised: the time of the set-aside is no step's, and is left out of the timed region)
+            t1 = time.time()
+            carried = dev.export_tallies()
+            dev.import_tallies(N.zeros_like(carried))
+            dev.lib.trc_scene_clear_hits(dev.handle)
+            aside = time.time() - t1
         st = step(args.warmup + k)
         seg += st.segments
         kms += st.kernel_ms
@@ -304,7 +350,7 @@ def main():
     # the single exchange of the job: sum the tally buffers of all ranks (per-surface energies, counts, flux map)
     reduce_scene_tallies(dev)
     barrier()
-    dt = time.time() - t0
+    dt = time.time() - t0 - aside
 
     if world > 1:
         total_segments = float(all_reduce_sum(N.array([float(seg)]))[0])
@@ -312,6 +358,12 @@ def main():
         dt_max = float(times.max())
     else:
         total_segments, dt_max = float(seg), dt
+
+    if args.dump_outputs:
+        last = dev.export_tallies()
+        names = dump_outputs(args.dump_outputs, dev.get_tallies(), dev.get_fluxmap(218), dev.get_hits(), st.segments)
+        dev.import_tallies(carried + last)
+        log('outputs of the last timed step written to %s: %s' % (args.dump_outputs, ', '.join(names)))
 
     api = None
     if rank == 0:

@@ -2,6 +2,10 @@ import os
 import sys
 
 import pytest
+# torch before any test loads libtracer_amd.so: the library then binds to the HIP runtime torch has already loaded.  Loaded the
+# other way round, the process holds two HIP runtimes, and once a test has initialised torch's the library sees no GPU
+# ("torch in the same process").  Importing torch opens no device.
+import torch  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:

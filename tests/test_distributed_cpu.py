@@ -54,7 +54,9 @@ def _worker(rank, world, port, n_total, q):
     total = dev.buf
     if rank == 0:
         q.put(total)
-    dist.barrier()
+    # (gloo's monitored_barrier stays on the host; dist.barrier() asks torch.cuda for a device, which opens the GPUs of a GPU
+    # machine in every worker)
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
