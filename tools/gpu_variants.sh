@@ -1,7 +1,6 @@
 #!/bin/bash
 # usage: gpu_variants.sh <tag> <lib.so> ...  -- per-kernel rocprofv3 stats of the streaming engine for each library build
 cd /tmp && export TMPDIR=/tmp
-export TRC_FAST_STREAM=1
 while [ $# -gt 1 ]; do
   tag=$1; lib=$2; shift 2
   export TRACER_AMD_LIB=$lib

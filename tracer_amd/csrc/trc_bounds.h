@@ -430,9 +430,8 @@ static inline void trc_accel_build_grid32(const trc_surface_desc *surfs, int n_s
         ext[k] = (double)A.big_root[3 + k] - lo[k];
     }
     // cells per listed surface: 3 measured best on the relief of 105 800 triangles with k_s_bounce_coop (1: 9.4 ms per 1e7 rays,
-    // 2: 9.0, 3: 8.7, 4: 8.9, 6: 9.8, 12: 10.5; with a lane per ray, k_s_bounce<2>, 6: 14.1); TRC_GRID32_DENSITY overrides it
-    double density = 3.0;
-    if (const char *e = std::getenv("TRC_GRID32_DENSITY")) { const double v = std::atof(e); if (v > 0.0) density = v; }
+    // 2: 9.0, 3: 8.7, 4: 8.9, 6: 9.8, 12: 10.5; with a lane per ray, k_s_bounce<2>, 6: 14.1)
+    const double density = 3.0;
     double target = std::fmin(16777216.0, std::fmax(8.0, density * (double)nb));
     for (int attempt = 0; attempt < 16; ++attempt, target *= 0.5) {
         double emax = std::fmax(ext[0], std::fmax(ext[1], ext[2]));

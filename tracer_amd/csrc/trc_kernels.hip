@@ -860,6 +860,33 @@ __global__ __launch_bounds__(THREADS) void k_trace_coop(FastParams P) {
     }
 }
 
+// TRC_SURF_TERMINAL: e_out = e (1 - absorptivity) = 0 exactly, and 0 <= min_energy for every min_energy the API accepts
+static bool surface_ends_every_ray(const trc_surface_desc &sd) {
+    const int ok = sd.optics_kind;
+    const bool plain = ((ok == TRC_OPT_REFLECTIVE || ok == TRC_OPT_ONE_SIDED_REFLECTIVE) && sd.opt[1] == 0.0) ||
+                       ((ok == TRC_OPT_REAL_REFLECTIVE || ok == TRC_OPT_ONE_SIDED_REAL_REFLECTIVE) && sd.opt[3] == 0.0) ||
+                       (ok == TRC_OPT_LAMBERTIAN && sd.opt[2] == 0.0 && sd.opt[4] == 0.0) || ok == TRC_OPT_LAMBERTIAN_SPECULAR;
+    return plain && sd.opt[0] == 1.0;
+}
+
+// Lets `fn` take `lds` bytes of dynamic LDS: beyond 64 KiB a kernel must be allowed them first
+static int kernel_allow_lds(const void *fn, size_t lds) {
+    if (lds <= 64 * 1024) return TRC_OK;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
+    return TRC_OK;
+}
+
+// ... and sets *cap to its workgroups resident at once: the occupancy, at least one and at most `max_bpc` per CU, on `n_cu` CUs
+static int kernel_grid_cap(const void *fn, int threads, size_t lds, int max_bpc, int n_cu, unsigned *cap) {
+    TRC_TRY(kernel_allow_lds(fn, lds));
+    int bpc = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, fn, threads, lds) != hipSuccess || bpc < 1) bpc = 1;
+    if (bpc > max_bpc) bpc = max_bpc;
+    *cap = (unsigned)(n_cu * bpc);
+    return TRC_OK;
+}
+
 #define TRC_STREAM_MIN_RAYS 1048576
 #include "trc_stream.inc"
 
@@ -1386,14 +1413,8 @@ static int scene_upload_surfaces(trc_scene *sc) {
         pack_record(sc->surfs[i], recs.data() + (size_t)i * sc->stride, sc->stride);
         for (int k = 0; k < 8; ++k) opt[(size_t)i * 8 + k] = sc->surfs[i].opt[k];
         flags[i] = sc->surfs[i].flags & 0xFFFF;
-        // e_out = e (1 - absorptivity) = 0 exactly, and 0 <= min_energy for every min_energy the API accepts
-        const trc_surface_desc &sd = sc->surfs[i];
-        const int ok = sd.optics_kind;
-        const bool plain = ((ok == TRC_OPT_REFLECTIVE || ok == TRC_OPT_ONE_SIDED_REFLECTIVE) && sd.opt[1] == 0.0) ||
-                           ((ok == TRC_OPT_REAL_REFLECTIVE || ok == TRC_OPT_ONE_SIDED_REAL_REFLECTIVE) && sd.opt[3] == 0.0) ||
-                           (ok == TRC_OPT_LAMBERTIAN && sd.opt[2] == 0.0 && sd.opt[4] == 0.0) || ok == TRC_OPT_LAMBERTIAN_SPECULAR;
-        if (plain && sd.opt[0] == 1.0) flags[i] |= TRC_SURF_TERMINAL;
-        flags[i] |= trc_shade_class_of(sd) << TRC_SURF_CLS_SHIFT;      // which shading kernel of the streaming engine serves the surface
+        if (surface_ends_every_ray(sc->surfs[i])) flags[i] |= TRC_SURF_TERMINAL;
+        flags[i] |= trc_shade_class_of(sc->surfs[i]) << TRC_SURF_CLS_SHIFT;      // which shading kernel of the streaming engine serves the surface
     }
     HIP_TRY(hipMemcpy(sc->d_recs, recs.data(), recs.size() * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(sc->d_opt, opt.data(), opt.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -2247,6 +2268,7 @@ extern "C" int trc_trace_fast(trc_scene *sc, const trc_rays *in, const trc_sourc
     if ((in == nullptr) == (src == nullptr)) return trc_fail(TRC_ERR_INVALID, "exactly one of `in` and `src` must be given");
     if (n < 0 || reps < 0) return trc_fail(TRC_ERR_INVALID, "n and reps must be >= 0");
     if (sc->splits) return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has ray-splitting optics: use trc_trace_ordered");
+    const StreamKnobs knobs = stream_knobs();
     // Rays that carry the imaginary part of a complex index, materials evaluated at their wavelength or a sampled spectrum are
     // traced by the streaming form (k_s_shade_x); the megakernel knows nothing of them.
     const bool carry = sc->carries || (in && (in->ref_index_im || in->spectra || in->mat));
@@ -2378,31 +2400,23 @@ extern "C" int trc_trace_fast(trc_scene *sc, const trc_rays *in, const trc_sourc
         P.n = n; P.reps = reps; P.flags = flags; P.min_energy = min_energy; P.seed = seed; P.ray_offset = ray_offset;
         P.lx = d_last[0]; P.ly = d_last[1]; P.lz = d_last[2]; P.ldx = d_last[3]; P.ldy = d_last[4]; P.ldz = d_last[5]; P.le = d_last[6];
         P.last_cap = last_cap;
-        P.capture = 0;
-        if (sc->hit_cap > 0)
-            for (int i = 0; i < S; ++i) if (sc->surfs[i].flags & TRC_SURF_CAPTURE_HITS) P.capture = 1;
+        P.capture = captures ? 1 : 0;
 
         const bool accel = sc->has_kd && (flags & TRC_TRACE_ACCEL);
         size_t b_buie = src ? (size_t)TRC_BUIE_STAGED * 8 : 0;
         size_t b_tally = (size_t)(3 * S + 2) * 8;
-        static int threads_env = -1, mode_env = -1;
-        if (threads_env < 0) { const char *ev = getenv("TRC_FAST_THREADS"); threads_env = ev ? atoi(ev) : 0; }
-        if (mode_env < 0) { const char *ev = getenv("TRC_FAST_GENERIC"); mode_env = (ev && atoi(ev)) ? 1 : 0; }
         // preferred: single-precision conservative search with everything it needs in LDS (up to 160 KiB per CU)
-        bool m32 = sc->accel_ok && !mode_env && S <= 65535 &&
+        bool m32 = sc->accel_ok && S <= 65535 &&
                    (!accel || (sc->accel_kd_ok && sc->kd_nodes <= COOP_MAX_NODES && sc->accel.kd_depth <= COOP_MAX_DEPTH));
         int threads = 512;
-        if (threads_env == 256 || threads_env == 512 || threads_env == 768 || threads_env == 1024) threads = threads_env;
         size_t lds = 0;
         if (m32) {
             size_t b_acc = (size_t)6 * S * 4 + (accel ? ((size_t)2 * sc->kd_nodes * 4 + (size_t)sc->kd_nalways * 4 + (size_t)sc->kd_nleaf * 2)
                                                       : (8 + sc->accel.brute_leaf.size() * 2)) +
                            sc->accel.unbounded.size() * 4 + 32;
-            for (;;) {
-                lds = b_buie + b_tally + b_acc + (size_t)(threads / 64) * COOP_WAVE_BYTES(accel ? (sc->accel.kd_depth > 0 ? sc->accel.kd_depth : 1) : 1);
-                if (lds <= 160 * 1024 - 512 || threads == 256) break;
-                threads = threads == 1024 ? 768 : (threads == 768 ? 512 : 256);
-            }
+            const size_t b_wave = COOP_WAVE_BYTES(accel ? (sc->accel.kd_depth > 0 ? sc->accel.kd_depth : 1) : 1);
+            lds = b_buie + b_tally + b_acc + (size_t)(threads / 64) * b_wave;
+            if (lds > 160 * 1024 - 512) { threads = 256; lds = b_buie + b_tally + b_acc + (size_t)(threads / 64) * b_wave; }
             if (lds > 160 * 1024 - 512) m32 = false;
             P.lds_tally = 1;
             P.lds_scene = 0;
@@ -2420,18 +2434,14 @@ extern "C" int trc_trace_fast(trc_scene *sc, const trc_rays *in, const trc_sourc
         }
         // Large calls run the streaming engine (phases as separate kernels connected by HBM queues, trc_stream.inc);
         // small ones the persistent megakernel, which needs one launch and no workspace.  TRC_TRACE_STREAM /
-        // TRC_TRACE_MEGAKERNEL (or TRC_FAST_STREAM=1 / 0) force one or the other.
-        static int stream_env = -2;
-        if (stream_env == -2) { const char *ev = getenv("TRC_FAST_STREAM"); stream_env = ev ? (atoi(ev) ? 1 : 0) : -1; }
-        const bool want_accel = (flags & TRC_TRACE_ACCEL) != 0;
-        int stream_mode = 0;
-        size_t stream_lds = 0;
-        const bool stream_ok = !mode_env && n >= 64 && stream_plan(sc, want_accel, &stream_mode, &stream_lds);
-        const bool force_stream = (flags & TRC_TRACE_STREAM) || stream_env == 1 || carry;
-        const bool force_mega = !carry && ((flags & TRC_TRACE_MEGAKERNEL) || stream_env == 0);
+        // TRC_TRACE_MEGAKERNEL force one or the other.
+        StreamPlan plan = {0, 0, true};
+        const bool stream_ok = n >= 64 && stream_plan(sc, (flags & TRC_TRACE_ACCEL) != 0, knobs, &plan);
+        const bool force_stream = (flags & TRC_TRACE_STREAM) || carry;
+        const bool force_mega = !carry && (flags & TRC_TRACE_MEGAKERNEL);
         // (a scene on the large grid -- a mesh of 1e5 faces -- has nothing but its boxes to search in the megakernel: 2e5 rays on the
         // relief of 105 800 triangles took 570 ms there, 1.3 ms here)
-        const long long stream_from = stream_mode == 3 ? 4096 : TRC_STREAM_MIN_RAYS;
+        const long long stream_from = plan.mode == 3 ? 4096 : TRC_STREAM_MIN_RAYS;
         const bool use_stream = stream_ok && (force_stream || (!force_mega && n >= stream_from));
         if (carry && !use_stream) { st = trc_fail(TRC_ERR_UNSUPPORTED, "no streaming form for this scene: rays that carry complex indices or spectra go through trc_trace_ordered"); break; }
         if (use_stream) {
@@ -2440,7 +2450,7 @@ extern "C" int trc_trace_fast(trc_scene *sc, const trc_rays *in, const trc_sourc
                 if (!sc->stream_eng) { st = trc_fail(TRC_ERR_NOMEM, "out of host memory"); break; }
                 memset(sc->stream_eng, 0, sizeof(StreamEngine));
             }
-            if ((st = stream_trace(sc, P, carry_in, want_accel, src, *sc->stream_eng, &s, &stream_seg, &stream_hits))) {
+            if ((st = stream_trace(sc, P, carry_in, plan, knobs, src, *sc->stream_eng, &s, &stream_seg, &stream_hits))) {
                 // the hits captured by the bounces that completed: wind the buffer back to where the call found it
                 const std::string why = g_last_error;
                 unsigned long long now = 0;
@@ -2459,19 +2469,12 @@ extern "C" int trc_trace_fast(trc_scene *sc, const trc_rays *in, const trc_sourc
         (void)hipStreamSynchronize(ctx->stream);       // (the sums of an earlier streaming call may still be on their way into the buffer)
         if (hipMemcpy(tally_before, sc->d_tally + 3 * S, sizeof(tally_before), hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "counter readback failed"); break; }
         void (*kern)(FastParams) = nullptr;
-        if (m32) kern = threads == 1024 ? k_trace_coop<1024> : (threads == 768 ? k_trace_coop<768> : (threads == 512 ? k_trace_coop<512> : k_trace_coop<256>));
+        if (m32) kern = threads == 512 ? k_trace_coop<512> : k_trace_coop<256>;
         else kern = k_trace_fast<256>;
-        if (lds > 64 * 1024) {
-            hipError_t ae = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (ae != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(ae)); break; }
-        }
-
-        // persistent grid: as many workgroups as are resident at once, never more waves than rays/64
-        int blocks_per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, (const void *)kern, threads, lds) != hipSuccess || blocks_per_cu < 1)
-            blocks_per_cu = 1;
-        if (blocks_per_cu > 8) blocks_per_cu = 8;
-        long long grid = (long long)ctx->n_cu * blocks_per_cu;
+        // persistent grid: as many workgroups as are resident at once (at most 8 per CU), never more waves than rays/64
+        unsigned resident = 0;
+        if ((st = kernel_grid_cap((const void *)kern, threads, lds, 8, ctx->n_cu, &resident))) break;
+        long long grid = resident;
         long long max_grid = (n + threads - 1) / threads;
         if (grid > max_grid) grid = max_grid;
         if (grid < 1) grid = 1;

@@ -2071,39 +2071,51 @@ static int stream_q3_grow(StreamWs &W) {
     return TRC_OK;
 }
 
-static int stream_ws_alloc_queues(StreamWs &W, long long cap, long long want_q3, long long want_room);
-#define STREAM_ACT_STATIC(cap) ((cap) + ((cap) >> 2) + (1ll << 23))      /* entries of an active list that pre-assigned chunks may take */
+#define STREAM_MAX_SLOTS 4
+// Environment knobs of the streaming engine: routes and capacities the tests compare and force.  trc_trace_fast reads them at every
+// call, since the tests switch them within one process.
+struct StreamKnobs {
+    int search;             // TRC_STREAM_SEARCH=1: walk the caller's Kd-tree instead of the grid (when its walk kernel fits)
+    bool fresh;             // TRC_STREAM_FRESH=0: no footprint map
+    bool bounce;            // TRC_STREAM_BOUNCE=0: continued rays through the general path
+    bool first;             // TRC_STREAM_FIRST=1: fresh rays outside the footprint map through k_s_bounce<.., FRESH>
+    bool coop;              // TRC_STREAM_COOP=0: k_s_bounce<2> on the large grid, every lane its own ray
+    int absorb;             // TRC_STREAM_ABSORB=0: no list of terminal hits; =1: the list, finished by k_s_absorb only (-1: not set)
+    bool static_chunks;     // TRC_STREAM_STATIC=0: no pre-assigned chunks
+    bool room_set; long long room;      // TRC_STREAM_ROOM is set, and the room of every list it sets (>= 64; 0: the default)
+    long long q3_entries;   // TRC_STREAM_Q3_ENTRIES: initial capacity of the candidate queue (0: by the batch)
+    int fp_cells;           // TRC_STREAM_FP_CELLS: cells per side of the footprint map (>= 32; 0: by the scene)
+    int slots;              // TRC_STREAM_SLOTS: batches in flight, 1 .. STREAM_MAX_SLOTS (default 2)
+};
 
-static int stream_ws_alloc(StreamWs &W, long long cap, int n_unbounded, long long tally_n) {
-    // candidate pairs per bounce: 4 per ray to start with (NSTTF needs 0.25); a bounce that overflows is run again with
-    // twice the room.  TRC_STREAM_Q3_ENTRIES (tests) sets the initial capacity.
-    long long want_q3 = (4 + (long long)n_unbounded) * cap + (long long)SQ_CHUNK_MAX * 16384;
-    { const char *ev = getenv("TRC_STREAM_Q3_ENTRIES"); if (ev && atoll(ev) > 0) want_q3 = atoll(ev); }
-    long long want_room = cap + (long long)SQ_CHUNK_MAX * 16384;   // room for the invalid tails of every wave's last chunk
-    bool room_env = false;
-    { const char *ev = getenv("TRC_STREAM_ROOM"); if (ev && atoll(ev) >= 64) { want_room = atoll(ev); room_env = true; } }      // tests: lists that overflow
-    if (!(W.cap >= cap && W.q3_cap >= want_q3 && (room_env ? W.room == want_room : W.room >= want_room))) {
-        stream_ws_free(W);
-        TRC_TRY(stream_ws_alloc_queues(W, cap, want_q3, want_room));
-    }
-    if (W.tally_n != tally_n || !W.tally_part) {      // flux maps may have been added since the last call
-        dev_free(W.tally_part);
-        W.tally_part = nullptr;
-        W.tally_n = 0;
-        TRC_TRY(dev_alloc(&W.tally_part, (size_t)TALLY_PARTS * (size_t)tally_n));
-        HIP_TRY(hipMemset(W.tally_part, 0, (size_t)TALLY_PARTS * (size_t)tally_n * sizeof(double)));
-        W.tally_n = tally_n;
-    }
-    return TRC_OK;
+static StreamKnobs stream_knobs() {
+    StreamKnobs K;
+    const char *ev;
+    K.search = (ev = getenv("TRC_STREAM_SEARCH")) ? atoi(ev) : 2;
+    K.fresh = !((ev = getenv("TRC_STREAM_FRESH")) && !atoi(ev));
+    K.bounce = !((ev = getenv("TRC_STREAM_BOUNCE")) && !atoi(ev));
+    K.first = (ev = getenv("TRC_STREAM_FIRST")) && atoi(ev);
+    K.coop = !((ev = getenv("TRC_STREAM_COOP")) && !atoi(ev));
+    K.absorb = (ev = getenv("TRC_STREAM_ABSORB")) ? atoi(ev) : -1;
+    K.static_chunks = !((ev = getenv("TRC_STREAM_STATIC")) && !atoi(ev));
+    K.room_set = (ev = getenv("TRC_STREAM_ROOM")) != nullptr;
+    K.room = K.room_set && atoll(ev) >= 64 ? atoll(ev) : 0;
+    K.q3_entries = (ev = getenv("TRC_STREAM_Q3_ENTRIES")) && atoll(ev) > 0 ? atoll(ev) : 0;
+    K.fp_cells = (ev = getenv("TRC_STREAM_FP_CELLS")) && atoi(ev) >= 32 ? atoi(ev) : 0;
+    K.slots = (ev = getenv("TRC_STREAM_SLOTS")) ? atoi(ev) : 2;
+    if (K.slots < 1 || K.slots > STREAM_MAX_SLOTS) K.slots = 2;
+    return K;
 }
 
-static int stream_ws_alloc_queues(StreamWs &W, long long cap, long long want_q3, long long want_room) {
+#define STREAM_ACT_STATIC(cap) ((cap) + ((cap) >> 2) + (1ll << 23))      /* entries of an active list that pre-assigned chunks may take */
+
+static int stream_ws_alloc_queues(StreamWs &W, long long cap, long long want_q3, long long want_room, const StreamKnobs &K) {
     const size_t cq = (size_t)want_room;   // (= SQ_ROOM)
     W.room = want_room;
     // active lists: pre-assigned chunks for at most STREAM_ACT_STATIC(cap) entries, and behind them every ray of the batch through
     // further reservations, of which every wave may leave one chunk unused -- at most as much again (TRC_STREAM_ROOM: as the
     // other lists).  Whatever the shares of the classes turn out to be, the lists cannot overflow.
-    W.act_room = getenv("TRC_STREAM_ROOM") && atoll(getenv("TRC_STREAM_ROOM")) >= 64 ? want_room
+    W.act_room = K.room ? want_room
                : 2 * STREAM_ACT_STATIC(cap) + cap + (1ll << 20);
     TRC_TRY(dev_alloc(&W.geo, cq));       // slots are handed out in chunks too
     TRC_TRY(dev_alloc(&W.aux, cq));
@@ -2129,13 +2141,34 @@ static int stream_ws_alloc_queues(StreamWs &W, long long cap, long long want_q3,
     return TRC_OK;
 }
 
+static int stream_ws_alloc(StreamWs &W, long long cap, int n_unbounded, long long tally_n, const StreamKnobs &K) {
+    // candidate pairs per bounce: 4 per ray to start with (NSTTF needs 0.25); a bounce that overflows is run again with
+    // twice the room.  TRC_STREAM_Q3_ENTRIES (tests) sets the initial capacity.
+    long long want_q3 = (4 + (long long)n_unbounded) * cap + (long long)SQ_CHUNK_MAX * 16384;
+    if (K.q3_entries) want_q3 = K.q3_entries;
+    long long want_room = cap + (long long)SQ_CHUNK_MAX * 16384;   // room for the invalid tails of every wave's last chunk
+    if (K.room) want_room = K.room;      // tests: lists that overflow
+    if (!(W.cap >= cap && W.q3_cap >= want_q3 && (K.room ? W.room == want_room : W.room >= want_room))) {
+        stream_ws_free(W);
+        TRC_TRY(stream_ws_alloc_queues(W, cap, want_q3, want_room, K));
+    }
+    if (W.tally_n != tally_n || !W.tally_part) {      // flux maps may have been added since the last call
+        dev_free(W.tally_part);
+        W.tally_part = nullptr;
+        W.tally_n = 0;
+        TRC_TRY(dev_alloc(&W.tally_part, (size_t)TALLY_PARTS * (size_t)tally_n));
+        HIP_TRY(hipMemset(W.tally_part, 0, (size_t)TALLY_PARTS * (size_t)tally_n * sizeof(double)));
+        W.tally_n = tally_n;
+    }
+    return TRC_OK;
+}
+
 // Which candidate search the streaming engine would use for this scene -- 0 all boxes, 1 packed Kd-tree, 2 uniform grid (LDS
-// sized), 3 the 32-bit grid of large scenes -- the LDS its walk kernel needs, and whether that kernel can run at all (*walk_ok):
+// sized), 3 the 32-bit grid of large scenes -- the LDS its walk kernel needs, and whether that kernel can run at all (walk_ok):
 // when the tables of the search do not fit LDS the general path (k_s_gen + k_s_walk + k_s_exact) is not available and k_s_bounce
 // searches for every ray from global memory.  false: no streaming form for this scene (the caller uses the megakernel).
-static bool stream_plan(const trc_scene *sc, bool want_accel, int *mode_out, size_t *lds_out, bool *walk_ok_out = nullptr) {
-    int search_env = 2;        // read at every call: tests switch the search within one process
-    { const char *ev = getenv("TRC_STREAM_SEARCH"); if (ev) search_env = atoi(ev); }
+struct StreamPlan { int mode; size_t lds_walk; bool walk_ok; };
+static bool stream_plan(const trc_scene *sc, bool want_accel, const StreamKnobs &K, StreamPlan *out) {
     if (!sc->accel_ok) return false;
     const int S = sc->n_surf;
     auto walk_lds = [&](int mode) {
@@ -2150,7 +2183,7 @@ static bool stream_plan(const trc_scene *sc, bool want_accel, int *mode_out, siz
     if (want_accel) {
         // the uniform grid of trc_bounds.h; TRC_STREAM_SEARCH=1 walks the caller's Kd-tree instead (when its walk kernel fits)
         const bool kd_fits = sc->accel_kd_ok && S <= 65535 && walk_lds(1) <= lds_max;
-        if (search_env == 1 && kd_fits) mode = 1;
+        if (K.search == 1 && kd_fits) mode = 1;
         else if (sc->accel.grid_ok) mode = 2;
         else if (sc->accel.big_ok) mode = 3;       // a scene beyond the LDS-sized structures: the 32-bit grid in global memory
         else if (kd_fits) mode = 1;
@@ -2159,9 +2192,9 @@ static bool stream_plan(const trc_scene *sc, bool want_accel, int *mode_out, siz
     size_t lds = mode == 3 ? 0 : walk_lds(mode);
     const bool walk_ok = mode != 3 && lds <= lds_max;
     if (!walk_ok) lds = 0;
-    *mode_out = mode;
-    *lds_out = lds;
-    if (walk_ok_out) *walk_ok_out = walk_ok;
+    out->mode = mode;
+    out->lds_walk = lds;
+    out->walk_ok = walk_ok;
     return true;
 }
 
@@ -2180,8 +2213,8 @@ struct StreamSlot {
     long long base, nb, n_in;
     unsigned long long n_act;
     int b, cur, attempt;
-    unsigned gb_wide, gb_gen, gb_walk, gb_shade, gb_cull, gb_fresh, gb_bounce;    // grids of the bounce being run
-    unsigned gb_sh[TRC_CLS_COUNT];            // ... of the shading kernels of the classes present (gb_shade: the largest)
+    unsigned gb_wide, gb_gen, gb_walk, gb_cull, gb_fresh, gb_bounce;    // grids of the bounce being run
+    unsigned gb_sh[TRC_CLS_COUNT];            // ... of the shading kernels of the classes present
     unsigned chunk_act_sh[TRC_CLS_COUNT];     // entries of the active list pre-assigned to every wave of each
     long long act_base_sh[TRC_CLS_COUNT];     // ... and where its chunks start
     unsigned gb_part;                         // grid of k_s_partition (0: one shading class, the hit list is walked as it is)
@@ -2193,7 +2226,6 @@ struct StreamSlot {
     bool busy;
 };
 
-#define STREAM_MAX_SLOTS 4
 #define STREAM_SMALL_SURFACES 24    /* scenes up to this many surfaces are searched surface by surface (k_s_bounce<3>) */
 struct StreamEngine {
     StreamSlot slot[STREAM_MAX_SLOTS];
@@ -2227,10 +2259,9 @@ static void stream_fp_key(const trc_source_desc &src, unsigned char *key) {
 
 // Makes (or finds) the footprint map of `src` over the scene.  *use = false when the map does not apply to this source / scene
 // (the general path then generates every ray).  TRC_STREAM_FRESH=0 switches the map off (tests compare the two paths).
-static int stream_fp_prepare(trc_scene *sc, StreamEngine &E, const trc_source_desc *src, FpDev *out, bool *use) {
+static int stream_fp_prepare(trc_scene *sc, StreamEngine &E, const trc_source_desc *src, const StreamKnobs &K, FpDev *out, bool *use) {
     *use = false;
-    { const char *ev = getenv("TRC_STREAM_FRESH"); if (ev && !atoi(ev)) return TRC_OK; }
-    if (!src) return TRC_OK;
+    if (!K.fresh || !src) return TRC_OK;
     unsigned char key[sizeof(E.fp_key)];
     stream_fp_key(*src, key);
     const bool buie = src->kind == TRC_SRC_BUIE_DISK || src->kind == TRC_SRC_BUIE_RECT;
@@ -2238,8 +2269,8 @@ static int stream_fp_prepare(trc_scene *sc, StreamEngine &E, const trc_source_de
     if (!E.fp) { E.fp = new (std::nothrow) trc_fp_host(); if (!E.fp) return trc_fail(TRC_ERR_NOMEM, "out of host memory"); E.fp_valid = false; }
     if (!(E.fp_valid && E.fp_geom_version == sc->geom_version && memcmp(key, E.fp_key, sizeof(key)) == 0 && (!buie || E.fp->P.cdf_end == cdf_end))) {
         int M = sc->n_surf > 4096 ? 1024 : 512;       // (a mesh of small faces: finer cells, fewer faces listed per cell; the mask still fits k_s_cull's LDS)
-        bool forced = false;
-        { const char *ev = getenv("TRC_STREAM_FP_CELLS"); if (ev && atoi(ev) >= 32) { M = atoi(ev); forced = true; } }
+        const bool forced = K.fp_cells > 0;
+        if (forced) M = K.fp_cells;
         if (M > 1024) M = 1024;
         if (sc->n_surf > 4096 && !forced) {
             // A large mesh that fills the source's view: nearly every ray starts over a face, the map culls nothing, and building
@@ -2301,19 +2332,637 @@ static int stream_engine_init(StreamEngine *E, trc_ctx *ctx) {
     return TRC_OK;
 }
 
-// Runs the whole call batch by batch, two batches in flight.  P is fully set up by trc_trace_fast (inputs staged, source uploaded).
-static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, bool want_accel, const trc_source_desc *src_desc, StreamEngine &E, trc_trace_stats *stats, double *seg_out, double *hit_out) {
-    const int src_kind = src_desc ? src_desc->kind : -1;
-    trc_ctx *ctx = sc->ctx;
+// The tables the shading kernels stage in LDS, in bytes: tallies, surface records, optics parameters, and the rest -- flux-map
+// edges and descriptors, surface flags and table offsets (k_s_absorb stages the tallies and the rest)
+struct ShadeBytes { size_t tally, recs, opt, maps; };
+static ShadeBytes shade_table_bytes(const trc_scene *sc) {
+    const size_t S = (size_t)sc->n_surf;
+    return {(3 * S + 2) * 8, S * sc->stride * 8, 8 * S * 8, sc->fm_edges_h.size() * 8 + ((sc->fms_h.size() * sizeof(FluxMapDev) + 7) / 8) * 8 + 2 * S * 4 + 16};
+}
+
+static long long flux_map_bins(const trc_scene *sc) {
+    long long bins = 0;
+    for (auto &m : sc->fms_h) bins += (long long)m.nu * m.nv;
+    return bins;
+}
+
+static bool all_surfaces_flat(const trc_scene *sc) {
+    for (int i = 0; i < sc->n_surf; ++i) if (!trc_gm_is_flat(sc->surfs[i].gm_kind)) return false;
+    return true;
+}
+
+// one kernel instance of a stage: threads per workgroup, dynamic LDS, and the grid cap (the workgroups resident at once)
+struct StreamKernel { const void *fn; int threads; size_t lds; unsigned max_blocks; };
+// ... of a shading kernel: the class it serves (-1: the only shading kernel, every kind) and the tables it stages
+struct StreamShadeK { int cls; const void *fn; unsigned threads, wpb, max_blocks; size_t lds; int lds_tables, lds_fm_bins; };
+
+// The kernels a call runs and the per-call decisions the bounces are planned by
+struct StreamForms {
+    int src_kind;
+    int gridm;                   // k_s_bounce's form of the search: 0 all boxes, 1 LDS-sized grid, 2 large grid, 3 surface by surface
+    bool small_scene;
+    StreamKernel walk;           // the general path: k_s_gen (g_gen), k_s_walk, k_s_exact (g_wide, lds_exact)
+    unsigned g_gen, g_wide;      // (g_wide: k_s_partition too)
+    size_t lds_exact;
+    StreamShadeK shk[TRC_CLS_COUNT];
+    int n_shk;
+    StreamKernel cull, fresh, fresh_one;     // fresh_one: k_s_fresh itself where `fresh` is its two-phase form
+    StreamKernel bounce, first, absorb;      // k_s_bounce for continued rays / for fresh ones, k_s_absorb
+    bool coop;                   // k_s_bounce_coop serves the large grid (it lists terminal hits, never finishes them itself)
+    bool use_fp, use_fused, use_first, use_absorb, absorb_inline;
+    bool multi;                  // more than one shading kernel: k_s_partition parts the hit list by class first
+    double general_share;        // expected share of the fresh rays that k_s_cull leaves to the general path
+    double listed_share;         // ... and lists for k_s_fresh (an estimate for its grid: the covered part of the source)
+};
+
+// the general path: k_s_gen, k_s_walk (the tables of the search in LDS), k_s_exact (the records in LDS when they fit)
+static int stream_form_general(StreamForms &F, StreamParams &SP0, const trc_scene *sc, const StreamPlan &plan) {
+    const int n_cu = sc->ctx->n_cu;
+    const size_t b_recs = (size_t)sc->n_surf * sc->stride * 8;
+    F.lds_exact = b_recs <= 40 * 1024 ? b_recs : 0;
+    SP0.lds_recs = F.lds_exact ? 1 : 0;
+    // (the general path never runs on tables beyond LDS: there SP.search == plan.mode)
+    F.walk = {plan.mode == 2 ? (const void *)k_s_walk<SW_THREADS, true> : (const void *)k_s_walk<SW_THREADS, false>, SW_THREADS, plan.lds_walk, 0u};
+    TRC_TRY(kernel_grid_cap(F.walk.fn, SW_THREADS, F.walk.lds, 2048 / SW_THREADS, n_cu, &F.walk.max_blocks));
+    F.g_wide = (unsigned)(n_cu * 8);     // 256-thread blocks: 4 waves each, <= 16384 waves in all
+    F.g_gen = (unsigned)(n_cu * 8);
+    return TRC_OK;
+}
+
+static int stream_shade_grid(StreamShadeK &K, int n_cu) {
+    TRC_TRY(kernel_grid_cap(K.fn, (int)K.threads, K.lds, 2048 / (int)K.threads, n_cu, &K.max_blocks));
+    if ((unsigned long long)K.max_blocks * K.wpb > SHADE_MAX_WAVES) K.max_blocks = SHADE_MAX_WAVES / K.wpb;
+    return TRC_OK;
+}
+
+// The shading kernels: one per optics class present in the scene (trc_shade.hip), each taking its hits off the bounce's list, or one
+// for every hit (k_s_shade_x) when the rays carry more than the fast engine's record.
+static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene *sc, bool carry) {
+    const int n_cu = sc->ctx->n_cu;
     const int S = sc->n_surf;
-    static long long batch_env = -1;
-    static int slots_env = -1;
-    if (batch_env < 0) { const char *ev = getenv("TRC_STREAM_BATCH"); batch_env = ev ? atoll(ev) : 0; }
-    if (slots_env < 0) { const char *ev = getenv("TRC_STREAM_SLOTS"); slots_env = ev ? atoi(ev) : 2; if (slots_env < 1 || slots_env > STREAM_MAX_SLOTS) slots_env = 2; }
+    const ShadeBytes b = shade_table_bytes(sc);
+    const long long bins = flux_map_bins(sc);
+    // k_s_shade: tallies, records, optics parameters, flux-map tables, flags and table values in LDS -- all of them or none (its LDS
+    // instance knows the address space of every table; see the kernel) -- and the flux-map bins too while a workgroup stays within
+    // half a CU's LDS (two workgroups per CU)
+    const size_t all = b.tally + b.recs + b.opt + b.maps + (size_t)sc->n_extra * 8;
+    const bool shade_lds = all <= 72 * 1024;
+    size_t lds_shade = shade_lds ? all : 8;
+    SP0.P.lds_tally = SP0.lds_tables = SP0.lds_extra = shade_lds ? 1 : 0;
+    SP0.lds_fm_bins = 0;
+    if (bins > 0 && shade_lds && lds_shade + (size_t)bins * 8 + 16 <= 78 * 1024) { SP0.lds_fm_bins = (int)bins; lds_shade += (size_t)bins * 8 + 16; }
+    // scenes of flat surfaces with mirror / diffuse optics only (heliostat fields, plate cavities): the lean instance
+    bool shade_simple = true;
+    for (int i = 0; i < S && shade_simple; ++i)
+        shade_simple = trc_gm_is_flat(sc->surfs[i].gm_kind) && ((TRC_OPT_SIMPLE_MASK >> sc->surfs[i].optics_kind) & 1u);
+    // (instances built for 3 and 4 waves per SIMD -- 168 / 128 registers, 228 / 376 bytes of scratch per lane -- were slower:
+    // 3.09 and 2.70 ms per NSTTF step against 2.54; later, without anything fetched ahead and with the incidence-angle factor out
+    // of line, 192 / 336 bytes and 2.33 / 2.35 ms against 1.99.  The registers are held by the optics code as a whole -- an instance
+    // that only knows Transparent needs none of the spills -- and it does not yield to the obvious: lighter sine / cosine / tangent
+    // kernels for bounded arguments made it worse (their float64 constants live in scalar registers, which then spill into vector
+    // ones))
+    const void *shade_fn = shade_simple ? (shade_lds ? (const void *)k_s_shade<true, 2, true> : (const void *)k_s_shade<true, 2, false>)
+                                        : (shade_lds ? (const void *)k_s_shade<false, 2, true> : (const void *)k_s_shade<false, 2, false>);
+    int n_shk = 0;
+    int term_cls = -1;
+    const bool split = !carry;
+    bool present[TRC_CLS_COUNT] = {false, false, false};
+    if (split) {
+        // a surface that ends every ray (TRC_SURF_TERMINAL) needs no optics when a ray of energy 0 ends in the reference too
+        // (0 <= min_energy): its hits go to a class that is there anyway
+        const bool term_ok = SP0.P.min_energy >= 0.0;
+        bool any_term = false;
+        for (int i = 0; i < S; ++i) {
+            const trc_surface_desc &sd = sc->surfs[i];
+            if (term_ok && surface_ends_every_ray(sd)) any_term = true;
+            else present[trc_shade_class_of(sd)] = true;
+        }
+        if (any_term) {
+            term_cls = present[TRC_CLS_MIRROR] ? TRC_CLS_MIRROR : present[TRC_CLS_DIFFUSE] ? TRC_CLS_DIFFUSE : -1;
+            if (term_cls < 0)          // nothing lean among the others: the terminal surfaces go by their own class
+                for (int i = 0; i < S; ++i) present[trc_shade_class_of(sc->surfs[i])] = true;
+        }
+        const bool all_flat = all_surfaces_flat(sc);
+        for (int c = 0; c < TRC_CLS_GENERAL; ++c) {
+            if (!present[c]) continue;
+            StreamShadeK &K = F.shk[n_shk++];
+            K.cls = c; K.threads = SHC_THREADS; K.wpb = SHC_THREADS / 64;
+            const size_t need = b.tally + b.recs + b.opt + b.maps + (c == TRC_CLS_MIRROR ? 0 : (size_t)sc->n_extra * 8);
+            const bool in_lds = need <= 120 * 1024;       // (one workgroup of sixteen waves per CU)
+            K.lds = in_lds ? need : 16;
+            K.lds_tables = in_lds ? 1 : 0;
+            K.lds_fm_bins = 0;
+            if (bins > 0 && in_lds && K.lds + (size_t)bins * 8 + 16 <= 150 * 1024) { K.lds_fm_bins = (int)bins; K.lds += (size_t)bins * 8 + 16; }
+            K.fn = trc_shade_lean_kernel(c, all_flat, in_lds);
+            TRC_TRY(stream_shade_grid(K, n_cu));
+        }
+    }
+    if (!split || present[TRC_CLS_GENERAL]) {
+        StreamShadeK &K = F.shk[n_shk++];
+        K.cls = split ? TRC_CLS_GENERAL : -1;
+        // 2 waves per SIMD: four workgroups of 256 per CU in two rounds
+        K.fn = shade_fn; K.threads = 256; K.wpb = 4; K.max_blocks = (unsigned)(n_cu * 4); K.lds = lds_shade;
+        K.lds_tables = SP0.lds_tables; K.lds_fm_bins = SP0.lds_fm_bins;
+        if (carry) {            // the same tables (k_s_shade_c's carve-up), sixteen waves per workgroup
+            K.fn = trc_shade_carry_kernel(shade_lds);
+            K.threads = SHC_THREADS; K.wpb = SHC_THREADS / 64;
+            if (K.lds < 16) K.lds = 16;
+            TRC_TRY(stream_shade_grid(K, n_cu));
+        } else
+            TRC_TRY(kernel_allow_lds(K.fn, K.lds));
+    }
+    F.n_shk = n_shk;
+    F.multi = n_shk > 1;
+    SP0.shade_term_cls = term_cls;
+    SP0.chunk_hitbuf = sc->hit_chunk ? sc->hit_chunk : SQ_HIT_CHUNK;
+    return TRC_OK;
+}
+
+// fresh rays of a plane source with a narrow cone: footprint map, k_s_cull + k_s_fresh (trc_footprint.h)
+static int stream_form_fresh(StreamForms &F, StreamParams &SP0, trc_scene *sc, StreamEngine &E, const trc_source_desc *src_desc, const StreamKnobs &K) {
+    F.general_share = 0.0; F.listed_share = 1.0;
+    TRC_TRY(stream_fp_prepare(sc, E, src_desc, K, &SP0.fp, &F.use_fp));
+    if (!F.use_fp) return TRC_OK;
+    const int n_cu = sc->ctx->n_cu;
+    const int S = sc->n_surf;
+    const int src_kind = F.src_kind;
+    const bool buie = src_kind == TRC_SRC_BUIE_DISK || src_kind == TRC_SRC_BUIE_RECT;
+    const bool flat = all_surfaces_flat(sc);
+    const int sf_threads = SF_THREADS(flat);
+    // k_s_fresh: the tables every listed ray reads go to LDS when they all fit (one workgroup per CU)
+    bool fresh_in_lds = false;
+    // the Buie sources go through the two-phase form (k_s_fresh2): a queue of SFQ_CAP (ray, cell) pairs per wave
+    const bool fresh_two = buie;
+    size_t lds_fresh = buie ? ((sizeof(trc_buie_fast) + 15) & ~(size_t)15) : 0;
+    const size_t b_obb = (size_t)S * TRC_OBB_LSTRIDE * 4 + 16, b_recs = (size_t)S * sc->stride * 8;
+    const size_t n_list = E.fp->clist.size();
+    const size_t b_lists = ((((size_t)SP0.fp.P.Mc * SP0.fp.P.Mc + 1) * 2 + 15) & ~(size_t)15) + n_list * 2 + 16;
+    const size_t b_queue = fresh_two ? (size_t)(sf_threads / 64) * 2 * SFQ_CAP * 4 + 16 : 0;
+    if (n_list < 65536 && lds_fresh + b_obb + b_recs + b_lists + b_queue <= 150 * 1024) { fresh_in_lds = true; lds_fresh += b_obb + b_recs + b_lists; }
+    lds_fresh += 32 + b_queue;
+#define SF_PICK(K) (flat ? (fresh_in_lds ? (const void *)k_s_fresh<K, true, true> : (const void *)k_s_fresh<K, true, false>) \
+                         : (fresh_in_lds ? (const void *)k_s_fresh<K, false, true> : (const void *)k_s_fresh<K, false, false>))
+    const void *fresh1_fn = src_kind == TRC_SRC_BUIE_DISK ? SF_PICK(TRC_SRC_BUIE_DISK) : src_kind == TRC_SRC_BUIE_RECT ? SF_PICK(TRC_SRC_BUIE_RECT)
+                          : src_kind == TRC_SRC_PILLBOX_DISK ? SF_PICK(TRC_SRC_PILLBOX_DISK) : SF_PICK(TRC_SRC_PILLBOX_RECT);
+#undef SF_PICK
+#define SF2_PICK(K) (flat ? (fresh_in_lds ? (const void *)k_s_fresh2<K, true, true> : (const void *)k_s_fresh2<K, true, false>) \
+                          : (fresh_in_lds ? (const void *)k_s_fresh2<K, false, true> : (const void *)k_s_fresh2<K, false, false>))
+    const void *fresh_fn = !fresh_two ? fresh1_fn : src_kind == TRC_SRC_BUIE_DISK ? SF2_PICK(TRC_SRC_BUIE_DISK) : SF2_PICK(TRC_SRC_BUIE_RECT);
+#undef SF2_PICK
+    const void *cull_fn = src_kind == TRC_SRC_BUIE_DISK ? (const void *)k_s_cull<TRC_SRC_BUIE_DISK> : src_kind == TRC_SRC_BUIE_RECT ? (const void *)k_s_cull<TRC_SRC_BUIE_RECT>
+                        : src_kind == TRC_SRC_PILLBOX_DISK ? (const void *)k_s_cull<TRC_SRC_PILLBOX_DISK> : (const void *)k_s_cull<TRC_SRC_PILLBOX_RECT>;
+    const size_t lds_cull = (size_t)SP0.fp.P.M * SP0.fp.P.M / 8 + (SC_GEN_CAP + 4) * 4;
+    if (lds_cull > 160 * 1024 - 512 || lds_fresh > 160 * 1024 - 512) { F.use_fp = false; return TRC_OK; }
+    F.fresh = {fresh_fn, sf_threads, lds_fresh, 0u};
+    F.fresh_one = {fresh1_fn, sf_threads, lds_fresh, 0u};
+    F.cull = {cull_fn, SC_THREADS, lds_cull, 0u};
+    TRC_TRY(kernel_grid_cap(fresh_fn, sf_threads, lds_fresh, 2048 / sf_threads, n_cu, &F.fresh.max_blocks));
+    if (fresh1_fn != fresh_fn) TRC_TRY(kernel_allow_lds(fresh1_fn, lds_fresh));
+    TRC_TRY(kernel_grid_cap(cull_fn, SC_THREADS, lds_cull, 2048 / SC_THREADS, n_cu, &F.cull.max_blocks));
+    F.general_share = SP0.fp.P.has_generic ? (1.0 - SP0.fp.P.cdf_end) : 0.0;
+    if (F.general_share < 0.0) F.general_share = 0.0;
+    F.listed_share = E.fp->coverage * (src_kind == TRC_SRC_BUIE_DISK || src_kind == TRC_SRC_PILLBOX_DISK ? 4.0 / TRC_PI : 1.0);
+    if (F.listed_share > 1.0) F.listed_share = 1.0;
+    return TRC_OK;
+}
+
+// Continued rays (bounces >= 1): one kernel per bounce on the grid / all-boxes forms (k_s_bounce); the Kd walk of
+// TRC_STREAM_SEARCH=1 keeps the queues.  Fresh rays outside the footprint map go through k_s_bounce<.., FRESH> instead of the
+// general path in large scenes and in small ones.
+static int stream_form_bounce(StreamForms &F, StreamParams &SP0, const trc_scene *sc, const StreamPlan &plan, const StreamKnobs &K) {
+    const int n_cu = sc->ctx->n_cu;
+    const int S = sc->n_surf;
+    const bool big = !plan.walk_ok;
+    F.use_fused = plan.mode != 1 && (K.bounce || big);
+    F.use_first = big || F.small_scene || (K.first && plan.mode != 1);
+    if (!F.use_fused && !F.use_first) return TRC_OK;
+    const int gridm = F.gridm;
+    const size_t b_grid = plan.mode == 2 ? ((((size_t)sc->accel.grid_off.size() + 2) & ~(size_t)1) * 2 + sc->accel.grid_list.size() * 2 + 8) : 0;
+    const size_t b_all = (size_t)S * 24 + (size_t)S * TRC_OBB_LSTRIDE * 4 + 16 + (size_t)S * sc->stride * 8 + b_grid + (((size_t)S * 4 + 15) & ~(size_t)15);
+    const size_t b_buie = ((sizeof(trc_buie_fast) + 15) & ~(size_t)15);
+    const bool in_lds = gridm != 2 && gridm != 3 && b_all + b_buie <= 150 * 1024;
+    size_t lds_bounce = (in_lds ? b_all : 0) + 16;
+    SP0.bg_occ_words = 0;
+    // the large grid: k_s_bounce_coop, whose lanes share the tests of their wave's rays
+    const bool coop = F.coop = gridm == 2 && K.coop;
+    if (coop) lds_bounce += (size_t)(SB_THREADS / 64) * SBC_WAVE_BYTES;
+    if (gridm == 2 && sc->accel.big_occ.size() * 4 <= (coop ? 80 : 96) * 1024) {      // the occupancy bits of the large grid
+        SP0.bg_occ_words = (int)sc->accel.big_occ.size();
+        lds_bounce += (sc->accel.big_occ.size() * 4 + 15) & ~(size_t)15;
+    }
+    const size_t lds_first = lds_bounce + b_buie;
+#define SB_PICK(FR, FL) (gridm == 3 ? (const void *)k_s_bounce<3, false, FR, FL> : gridm == 2 ? (coop ? (const void *)k_s_bounce_coop<FR, FL> : (const void *)k_s_bounce<2, false, FR, FL>) \
+                       : gridm == 1 ? (in_lds ? (const void *)k_s_bounce<1, true, FR, FL> : (const void *)k_s_bounce<1, false, FR, FL>) \
+                                    : (in_lds ? (const void *)k_s_bounce<0, true, FR, FL> : (const void *)k_s_bounce<0, false, FR, FL>))
+    const bool all_flat = all_surfaces_flat(sc);
+    const void *bounce_fn = all_flat ? SB_PICK(false, true) : SB_PICK(false, false);
+    const void *first_fn = all_flat && gridm == 2 && coop ? (const void *)k_s_bounce_coop<true, true> : SB_PICK(true, false);
+#undef SB_PICK
+    F.bounce = {bounce_fn, SB_THREADS_OF(gridm), lds_bounce, 0u};
+    F.first = {first_fn, SB_THREADS_OF(gridm), lds_first, 0u};
+    TRC_TRY(kernel_grid_cap(bounce_fn, F.bounce.threads, lds_bounce, 2048 / F.bounce.threads, n_cu, &F.bounce.max_blocks));
+    TRC_TRY(kernel_grid_cap(first_fn, F.first.threads, lds_first, 2048 / F.first.threads, n_cu, &F.first.max_blocks));
+    return TRC_OK;
+}
+
+// Hits on surfaces that end every ray (the receiver of a field) are listed apart by k_s_bounce and finished by k_s_absorb -- when
+// the scene has such surfaces and k_s_absorb's tables (those of k_s_shade without records and optics) fit LDS -- or finished inside
+// k_s_bounce when its workgroup has the LDS for the tallies, flux-map tables and bins as well (TRC_STREAM_ABSORB=1: always behind
+// the list, by k_s_absorb).
+static int stream_form_absorb(StreamForms &F, StreamParams &SP0, const trc_scene *sc, bool carry, const StreamKnobs &K) {
+    if (!(F.use_fused && SP0.P.lds_tally && SP0.lds_tables && !carry)) return TRC_OK;
+    bool any = false;
+    for (int i = 0; i < sc->n_surf && !any; ++i) any = surface_ends_every_ray(sc->surfs[i]);
+    const ShadeBytes b = shade_table_bytes(sc);
+    const long long bins = flux_map_bins(sc);
+    const size_t lds_absorb = b.tally + b.maps + (SP0.lds_fm_bins ? (size_t)bins * 8 : 0) + 16;
+    const bool fm_ok = bins == 0 || SP0.lds_fm_bins > 0;       // (bins outside LDS would be scattered global atomics at eight waves per SIMD: not this kernel)
+    F.use_absorb = any && fm_ok && lds_absorb <= 78 * 1024 && sc->tr_off < 0 && SP0.P.min_energy >= 0.0 && K.absorb != 0;      // (0 <= min_energy: the ray ends there in the reference too)
+    if (!F.use_absorb) return TRC_OK;
+    // one workgroup of 16 waves per CU (4096 waves with open chunks of the hit buffer at most)
+    F.absorb = {(const void *)k_s_absorb, SA_THREADS, lds_absorb, (unsigned)sc->ctx->n_cu};
+    TRC_TRY(kernel_allow_lds(F.absorb.fn, lds_absorb));
+    SP0.split_terminal = 1;
+    const size_t extra_lds = lds_absorb + 64;
+    if (K.absorb != 1 && !(F.gridm == 2 && F.coop) && F.bounce.lds + extra_lds <= 158 * 1024) {
+        // (k_s_bounce keeps the grid cap of its LDS without these tables)
+        F.absorb_inline = true;
+        F.bounce.lds += extra_lds;
+        TRC_TRY(kernel_allow_lds(F.bounce.fn, F.bounce.lds));
+        SP0.split_terminal = 2;
+    }
+    return TRC_OK;
+}
+
+// Chooses the kernel of every stage for this call and sets up SP0, the parameters every batch starts from
+static int stream_choose_forms(StreamForms &F, StreamParams &SP0, trc_scene *sc, StreamEngine &E, const StreamPlan &plan, bool carry,
+                               const trc_source_desc *src_desc, const StreamKnobs &K) {
+    const int S = sc->n_surf;
+    memset(&F, 0, sizeof(F));
+    F.src_kind = src_desc ? src_desc->kind : -1;
+    F.gridm = plan.mode == 2 ? 1 : (plan.mode == 3 ? 2 : 0);
+    // a few surfaces: neither grid nor lists, the wave takes the surfaces one by one (k_s_bounce<3>) -- up to four surfaces (a
+    // dish and its receiver), where every lane tests every surface anyway and the form pays: 0.50 against 0.58 ms per bounce of
+    // 1e7 rays.  (Measured on the seven-wall cavity, one batch alone: 1.15 ms per bounce surface by surface against 0.96 ms lane by
+    // lane -- every wave runs all seven exact tests where its lanes needed four or five each.)
+    F.small_scene = S <= STREAM_SMALL_SURFACES && plan.mode != 1 && plan.walk_ok;
+    if (F.small_scene && S <= 4) F.gridm = 3;
+    SP0.search = plan.walk_ok ? plan.mode : 2;
+    SP0.hit_epoch = sc->hit_epoch;
+    TRC_TRY(stream_form_general(F, SP0, sc, plan));
+    TRC_TRY(stream_form_shade(F, SP0, sc, carry));
+    TRC_TRY(stream_form_fresh(F, SP0, sc, E, src_desc, K));
+    TRC_TRY(stream_form_bounce(F, SP0, sc, plan, K));
+    return stream_form_absorb(F, SP0, sc, carry, K);
+}
+
+// workspaces of the slots for batches of `cap` rays: queues, spectra of the rays under way, the class lists of k_s_partition
+static int stream_slots_alloc(StreamEngine &E, int n_slots, long long cap, const trc_scene *sc, const CarryIn &carry_in, const StreamForms &F, const StreamKnobs &K) {
+    for (int k = 0; k < n_slots; ++k) {
+        StreamSlot &Tk = E.slot[k];
+        TRC_TRY(stream_ws_alloc(Tk.W, cap, (int)sc->accel.unbounded.size(), (long long)sc->tally_n, K));
+        const long long want = (carry_in.spec && carry_in.n_spec > 0) ? (long long)carry_in.n_spec * Tk.W.room : 0;
+        if (Tk.spec_len < want) {
+            dev_free(Tk.spec);
+            Tk.spec = nullptr; Tk.spec_len = 0;
+            TRC_TRY(dev_alloc(&Tk.spec, (size_t)want));
+            Tk.spec_len = want;
+        }
+        Tk.spec_on = want > 0;
+        StreamWs &Wk = Tk.W;
+        if (!F.multi) continue;
+        Wk.pl_room = 2 * Wk.room;
+        for (int q = 0; q < F.n_shk; ++q) {
+            const int c = F.shk[q].cls;
+            if (Wk.pl_slot[c]) continue;
+            TRC_TRY(dev_alloc(&Wk.pl_slot[c], (size_t)Wk.pl_room));
+            TRC_TRY(dev_alloc(&Wk.pl_surf[c], (size_t)Wk.pl_room));
+            TRC_TRY(dev_alloc(&Wk.pl_t[c], (size_t)Wk.pl_room));
+        }
+    }
+    return TRC_OK;
+}
+
+// One call: its forms, the parameters every batch starts from, the batch size, and what the batches add up to
+struct StreamCall {
+    const StreamForms &F;
+    const StreamKnobs &K;
+    StreamEngine &E;
+    StreamParams SP0;
+    long long cap;
+    double seg, hits;
+    double cls_hits[TRC_CLS_COUNT];      // hits shaded by the kernel of each class (first STREAM_RATE_BOUNCES bounces)
+    int launches, max_bounces;
+};
+
+// a grid of g workgroups, at least one and at most max_blocks
+static unsigned clamp_grid(long long g, unsigned max_blocks) { return (unsigned)(g < 1 ? 1 : (g > (long long)max_blocks ? (long long)max_blocks : g)); }
+
+// grids and reservation sizes of a slot's next bounce
+static void plan_bounce(const StreamCall &C, StreamSlot &T) {
+    const StreamForms &F = C.F;
+    const StreamEngine &E = C.E;
+    // Grids follow the work of the bounce (every kernel strides over its queue, so a small grid is only slower, never
+    // wrong), with at least SW_ITEMS items per thread: later bounces and small calls do not pay for 2048 workgroups
+    // staging their tables.
+    long long work = T.b == 0 ? T.nb : (long long)T.n_act;
+    auto grid_for = [&](unsigned max_blocks, int threads) { return clamp_grid((work + threads - 1) / threads, max_blocks); };
+    // one pre-assigned chunk per appending wave, for `expected` entries over `waves` waves (+ margin): a multiple of 64, at
+    // least SQ_CHUNK, and never more than the lists have room for
+    auto chunk_for = [&](double expected, unsigned long long waves, unsigned floor = SQ_CHUNK) {
+        double c = 1.1 * expected / (double)(waves ? waves : 1ull) + (floor < SQ_CHUNK ? 48.0 : 128.0);
+        const double most = 0.9 * (double)T.W.room / (double)(waves ? waves : 1ull);
+        if (c > most) c = most;
+        unsigned u = ((unsigned)c + 63u) & ~63u;
+        return u < floor ? floor : u;
+    };
+    const int sf_threads = F.fresh.threads, sb_threads = F.bounce.threads, first_threads = F.first.threads;
+    T.fresh = F.use_fp && T.b == 0;
+    T.fused = F.use_fused && T.b > 0;
+    T.first = F.use_first && T.b == 0 && (!T.fresh || F.general_share > 0.0);
+    T.general = !T.fused && !T.first && (!T.fresh || F.general_share > 0.0);
+    T.gb_bounce = T.fused ? grid_for(F.bounce.max_blocks, sb_threads) : 0u;
+    T.gb_cull = T.fresh ? grid_for(F.cull.max_blocks, SC_THREADS * 8) : 0u;
+    T.SP.chunk_hit = T.SP.chunk_slot = T.SP.chunk_act = T.SP.chunk_first = T.SP.chunk_thit = SQ_CHUNK;
+    double act_expected = -1.0;          // rays expected to go on from this bounce's shading (< 0: unknown, the waves reserve as they go)
+    long long shade_entries = work;      // entries of the hit list the shading kernels walk (used or not)
+    T.gb_first = 0u;
+    T.cull_chunk = SQ_CHUNK;
+    T.cull_gen_chunk = 0;
+    if (T.fresh) {        // one lane per listed ray, a few rays per lane
+        const double listed = F.listed_share * (double)T.nb;
+        T.gb_fresh = clamp_grid(((long long)(1.2 * listed) + 4096 + sf_threads * 2 - 1) / (sf_threads * 2), F.fresh.max_blocks);
+        T.cull_chunk = chunk_for(1.1 * listed, (unsigned long long)T.gb_cull * (SC_THREADS / 64));
+        // general-path rays: rare -> per workgroup through LDS; a source with a strong aureole (CSR 0.3: a third of the rays) ->
+        // chunks per wave like the other lists
+        if (F.general_share * (double)T.nb / (double)T.gb_cull > 0.25 * SC_GEN_CAP)
+            T.cull_gen_chunk = chunk_for(1.1 * F.general_share * (double)T.nb, (unsigned long long)T.gb_cull * (SC_THREADS / 64));
+        // hits of the fresh rays: measured on the batches before (E.fp_hit_rate), every listed ray to start with
+        const double hits = (E.fp_hit_rate > 0.0 ? E.fp_hit_rate : F.listed_share) * (double)T.nb;
+        T.SP.chunk_hit = T.SP.chunk_slot = chunk_for(hits, (unsigned long long)T.gb_fresh * (unsigned long long)(sf_threads / 64));
+        act_expected = hits + 2.0 * F.general_share * (double)T.nb;
+    } else {
+        T.gb_fresh = 0u;
+        if (T.fused) {    // at most the rays that entered the bounce hit, at most those go on
+            const unsigned long long bw = (unsigned long long)T.gb_bounce * (unsigned long long)(sb_threads / 64);
+            const bool known = T.b < STREAM_RATE_BOUNCES && E.rate_term[T.b] >= 0.0;
+            // (the few hits that are left to k_s_shade behind k_s_absorb: short chunks, its list is walked entry by entry)
+            T.SP.chunk_hit = chunk_for((known ? E.rate_other[T.b] : 1.0) * (double)T.n_in, bw, (known && C.SP0.split_terminal) ? 64u : (unsigned)SQ_CHUNK);
+            T.SP.chunk_thit = chunk_for((known ? E.rate_term[T.b] : 1.0) * (double)T.n_in, bw);
+            // the shading kernels only see the hits that k_s_absorb does not take: grids for the entries of their list, used or not
+            // (every workgroup stages 50 KB of tables and flushes its private sums, hits or not)
+            if (known && (long long)bw * (long long)T.SP.chunk_hit < shade_entries) shade_entries = (long long)bw * (long long)T.SP.chunk_hit;
+            act_expected = (known && C.SP0.split_terminal ? E.rate_other[T.b] : 1.0) * (double)T.n_in;
+        }
+    }
+    // behind k_s_cull the general path only sees the rays left to it (the Buie aureole)
+    if (T.fresh) work = (long long)(1.5 * F.general_share * (double)T.nb) + 4096;
+    if (T.first) {
+        T.gb_first = grid_for(F.first.max_blocks, first_threads);
+        T.SP.chunk_first = chunk_for((double)work, (unsigned long long)T.gb_first * (first_threads / 64));      // at most every ray hits
+        if (!T.fresh) act_expected = (double)work;
+    }
+    // the shading kernels of the classes present: grids, and their parts of the active list
+    {
+        const double rays_in0 = T.b == 0 ? (double)T.nb : (double)T.n_in;
+        long long entries_of[TRC_CLS_COUNT] = {shade_entries, shade_entries, shade_entries};
+        T.gb_part = 0u;
+        for (int c = 0; c < TRC_CLS_COUNT; ++c) { T.part_start[c] = 0ull; T.SP.part_chunk[c] = SQ_CHUNK_MAX; T.SP.part_static[c] = 0; }
+        if (F.multi) {
+            T.gb_part = clamp_grid((shade_entries + 256ll * SW_ITEMS - 1) / (256ll * SW_ITEMS), F.g_wide);
+            const unsigned long long pw = (unsigned long long)T.gb_part * 4ull;
+            for (int k = 0; k < F.n_shk; ++k) {
+                const int c = F.shk[k].cls;
+                if (!(C.K.static_chunks && T.b < STREAM_RATE_BOUNCES && E.rate_cls[T.b][c] >= 0.0)) continue;      // share not known yet: the waves reserve as they go
+                double cc = 1.1 * E.rate_cls[T.b][c] * rays_in0 / (double)pw + 128.0;
+                const double most = (double)T.W.room / (double)pw - 64.0;
+                if (cc > most) cc = most;
+                unsigned chunk = ((unsigned)cc + 63u) & ~63u;
+                if (chunk < SQ_CHUNK) chunk = SQ_CHUNK;
+                T.SP.part_chunk[c] = chunk;
+                T.SP.part_static[c] = 1;
+                T.part_start[c] = pw * (unsigned long long)chunk;
+                if ((long long)T.part_start[c] < entries_of[c]) entries_of[c] = (long long)T.part_start[c];
+            }
+        }
+        unsigned long long total_waves = 0;
+        for (int k = 0; k < F.n_shk; ++k) {
+            const long long per = (long long)F.shk[k].threads * SW_ITEMS;
+            const long long shade_entries_k = F.multi ? entries_of[F.shk[k].cls] : shade_entries;
+            T.gb_sh[k] = clamp_grid((shade_entries_k + per - 1) / per, F.shk[k].max_blocks);
+            total_waves += (unsigned long long)T.gb_sh[k] * F.shk[k].wpb;
+        }
+        const double most = (double)(C.K.room_set ? (long long)(0.9 * (double)T.W.act_room) : STREAM_ACT_STATIC(T.W.cap) - 64 * (long long)total_waves) /
+                            (double)(total_waves ? total_waves : 1ull);
+        const double rays_in = T.b == 0 ? (double)T.nb : (double)T.n_in;
+        long long base = 0;
+        for (int k = 0; k < F.n_shk; ++k) {
+            const unsigned long long waves = (unsigned long long)T.gb_sh[k] * F.shk[k].wpb;
+            unsigned chunk = SQ_CHUNK;
+            if (act_expected >= 0.0) {
+                double ex = act_expected;
+                const int c = F.shk[k].cls;
+                if (c >= 0 && T.b < STREAM_RATE_BOUNCES && E.rate_cls[T.b][c] >= 0.0 && E.rate_cls[T.b][c] * rays_in < ex) ex = E.rate_cls[T.b][c] * rays_in;
+                double cc = 1.1 * ex / (double)waves + 128.0;
+                if (cc > most) cc = most;
+                chunk = ((unsigned)cc + 63u) & ~63u;
+                if (chunk < SQ_CHUNK) chunk = SQ_CHUNK;
+            }
+            T.chunk_act_sh[k] = chunk;
+            T.act_base_sh[k] = base;
+            base += (long long)waves * (long long)chunk;
+        }
+        T.SP.chunk_act = T.chunk_act_sh[0];
+    }
+    T.gb_gen = grid_for(F.g_gen, 256 * SW_ITEMS);
+    T.gb_wide = grid_for(F.g_wide, 256 * SW_ITEMS);
+    T.gb_walk = grid_for(F.walk.max_blocks, SW_THREADS * SW_ITEMS);
+    // the largest launches reserve 1024 (walkers) / 512 (candidates) entries per atomic: the counters are single words
+    T.SP.chunk_q1 = work >= (1ll << 22) ? SQ_CHUNK_MAX : SQ_CHUNK;
+    T.SP.chunk_q3 = work >= (1ll << 22) ? 512u : SQ_CHUNK;
+    T.SP.static_first = C.K.static_chunks;
+    T.SP.bounce_no = T.b;
+    T.SP.static_general = C.K.static_chunks && !T.fresh;      // few rays behind k_s_cull: their kernels reserve as they go
+    T.SP.q3_gen_chunk0 = (T.SP.static_general && T.b > 0) ? (long long)T.gb_walk * (SW_THREADS / 64) : -1;
+    T.SP.gen_list = T.fresh ? T.W.gen_list : nullptr;
+    T.SP.slot_base0 = T.fresh ? (long long)T.gb_fresh * (sf_threads / 64) * (long long)T.SP.chunk_slot : 0;
+    T.SP.hit_base0 = T.fresh ? (long long)T.gb_fresh * (sf_threads / 64) * (long long)T.SP.chunk_hit
+                             : (T.fused ? (long long)T.gb_bounce * (sb_threads / 64) * (long long)T.SP.chunk_hit : 0);
+}
+
+static int launch_kernel(const StreamKernel &k, unsigned grid, StreamParams &SP, hipStream_t stream) {
+    void *args[] = {(void *)&SP};
+    HIP_TRY(hipLaunchKernel(k.fn, dim3(grid), dim3(k.threads), args, k.lds, stream));
+    return TRC_OK;
+}
+
+// the kernels of one bounce of a slot's batch, followed by the read-back of its counters
+static int launch_bounce(StreamCall &C, StreamSlot &T) {
+    const StreamForms &F = C.F;
+    StreamParams &SP = T.SP;
+    SP.act_out = T.W.act[T.cur];
+    if (T.fresh) {
+        CullParams CP;
+        CP.F = SP.fp.P; CP.mask = SP.fp.mask; CP.seed = SP.P.seed; CP.rid0 = SP.P.ray_offset + (unsigned long long)T.base; CP.nb = T.nb;
+        CP.fq_ray = T.W.fq_ray; CP.fq_cell = T.W.fq_cell; CP.gen_list = T.W.gen_list; CP.cnt = T.W.cnt;
+        CP.room = T.W.room; CP.chunk = T.cull_chunk; CP.gen_chunk = T.cull_gen_chunk; CP.static_first = SP.static_first;
+        void *cargs[] = {(void *)&CP};
+        HIP_TRY(hipLaunchKernel(F.cull.fn, dim3(T.gb_cull), dim3(F.cull.threads), cargs, F.cull.lds, T.stream));
+        // the two-phase form pays where most listed rays miss (a field of mirrors: two of three); where most of them hit (a dish
+        // under its own source: the first phase rejects nothing) the batches after the first go back to k_s_fresh
+        const bool mostly_hits = C.E.fp_hit_rate > 0.0 && C.E.fp_hit_rate > 0.6 * 1.15 * F.listed_share;
+        TRC_TRY(launch_kernel(mostly_hits ? F.fresh_one : F.fresh, T.gb_fresh, SP, T.stream));
+        C.launches += 2;
+    }
+    if (T.fused) { TRC_TRY(launch_kernel(F.bounce, T.gb_bounce, SP, T.stream)); C.launches += 1; }
+    if (T.first) { TRC_TRY(launch_kernel(F.first, T.gb_first, SP, T.stream)); C.launches += 1; }
+    if (T.general) {
+        const int src_kind = F.src_kind;
+        const unsigned gb_gen = T.gb_gen;
+        if (T.b == 0 && src_kind == TRC_SRC_BUIE_DISK) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_BUIE_DISK>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
+        else if (T.b == 0 && src_kind == TRC_SRC_BUIE_RECT) hipLaunchKernelGGL((k_s_gen<true, TRC_SRC_BUIE_RECT>), dim3(gb_gen), dim3(256), 0, T.stream, SP);
+        else if (T.b == 0 && src_kind == TRC_SRC_PILLBOX_DISK) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_PILLBOX_DISK>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
+        else if (T.b == 0 && src_kind == TRC_SRC_PILLBOX_RECT) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_PILLBOX_RECT>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
+        else if (T.b == 0) hipLaunchKernelGGL(k_s_gen<true>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
+        else hipLaunchKernelGGL(k_s_gen<false>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
+        TRC_TRY(launch_kernel(F.walk, T.gb_walk, SP, T.stream));
+        hipLaunchKernelGGL(k_s_exact, dim3(T.gb_wide), dim3(256), F.lds_exact, T.stream, SP);
+        C.launches += 3;
+    }
+    if (F.multi) { TRC_TRY(launch_kernel({(const void *)k_s_partition, 256, 0, F.g_wide}, T.gb_part, SP, T.stream)); C.launches += 1; }
+    for (int k = 0; k < F.n_shk; ++k) {
+        const StreamShadeK &K = F.shk[k];
+        StreamParams SK = SP;
+        SK.shade_cls = K.cls;
+        if (F.multi) {
+            SK.hl_slot = T.W.pl_slot[K.cls]; SK.hl_surf = T.W.pl_surf[K.cls]; SK.hl_t = T.W.pl_t[K.cls]; SK.hl_room = T.W.pl_room; SK.hl_cn = CN(24 + K.cls);
+        } else {
+            SK.hl_slot = T.W.hit_slot; SK.hl_surf = T.W.hit_surf; SK.hl_t = T.W.hit_t; SK.hl_room = T.W.room; SK.hl_cn = CN(2);
+        }
+        SK.chunk_act = T.chunk_act_sh[k];
+        SK.act_base0 = T.act_base_sh[k];
+        SK.lds_tables = K.lds_tables; SK.lds_extra = K.lds_tables; SK.lds_fm_bins = K.lds_fm_bins;
+        void *args[] = {(void *)&SK};
+        HIP_TRY(hipLaunchKernel(K.fn, dim3(T.gb_sh[k]), dim3(K.threads), args, K.lds, T.stream));
+        C.launches += 1;
+    }
+    if (T.fused && SP.split_terminal == 1) {
+        TRC_TRY(launch_kernel(F.absorb, clamp_grid(((long long)T.n_act + SA_THREADS * 2 - 1) / (SA_THREADS * 2), F.absorb.max_blocks), SP, T.stream));
+        C.launches += 1;
+    }
+    HIP_TRY(hipMemcpyAsync(T.h_cnt, T.W.cnt, CN_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, T.stream));
+    HIP_TRY(hipEventRecord(T.done, T.stream));
+    return TRC_OK;
+}
+
+// plans the slot's next bounce and uploads its counters: everything zero except the length of the active list and, with
+// pre-assigned chunks, where each list starts
+static int upload_counters(const StreamCall &C, StreamSlot &T) {
+    const StreamForms &F = C.F;
+    plan_bounce(C, T);
+    unsigned long long *up = T.h_cnt + CN_WORDS;
+    for (int i = 0; i < CN_WORDS; ++i) up[i] = 0ull;
+    up[CN(5)] = T.n_act;
+    if (T.SP.static_first) {       // the first chunk of every appending wave is pre-assigned: the lists start behind them
+        // (a kernel that is not launched never closes its pre-assigned chunks: it must not be given any)
+        const unsigned long long cull_waves = T.fresh ? (unsigned long long)T.gb_cull * (SC_THREADS / 64) : 0ull;
+        const bool sg = T.SP.static_general != 0 && T.general;
+        if (sg) {
+            up[CN(0)] = (unsigned long long)T.gb_gen * 4ull * T.SP.chunk_q1;                           // Q1 <- k_s_gen
+            up[CN(1)] = ((unsigned long long)T.gb_walk * (unsigned long long)(SW_THREADS / 64) +
+                         (T.SP.q3_gen_chunk0 >= 0 ? (unsigned long long)T.gb_gen * 4ull : 0ull)) * T.SP.chunk_q3;   // Q3 <- k_s_walk (+ k_s_gen<false>)
+        }
+        const unsigned long long first_entries = T.first ? (unsigned long long)T.gb_first * (F.first.threads / 64) * T.SP.chunk_first : 0ull;
+        up[CN(2)] = (unsigned long long)T.SP.hit_base0 + (sg ? (unsigned long long)T.gb_wide * 4ull * SQ_CHUNK : 0ull) + first_entries;   // hit list <- k_s_fresh / k_s_bounce, k_s_exact / k_s_bounce<FRESH>
+        for (int c = 0; c < TRC_CLS_COUNT; ++c) up[CN(24 + c)] = T.part_start[c];                      // class lists <- k_s_partition
+        unsigned long long a = 0;                                                                      // active list <- the shading kernels
+        for (int k = 0; k < F.n_shk; ++k) a += (unsigned long long)T.gb_sh[k] * F.shk[k].wpb * T.chunk_act_sh[k];
+        up[CN(3)] = a;
+        up[CN(8)] = (unsigned long long)T.SP.slot_base0 + ((sg && T.b == 0) ? (unsigned long long)T.gb_gen * 4ull * SQ_CHUNK : 0ull) + first_entries;   // slots <- k_s_fresh, k_s_gen<true> / k_s_bounce<FRESH>
+        up[CN(9)] = cull_waves * (unsigned long long)T.cull_gen_chunk;                                 // general-path list <- k_s_cull
+        up[CN(10)] = cull_waves * (unsigned long long)T.cull_chunk;                                   // footprint list <- k_s_cull
+        if (T.fused && T.SP.split_terminal == 1) up[CN(11)] = (unsigned long long)T.gb_bounce * (unsigned long long)(F.bounce.threads / 64) * T.SP.chunk_thit;   // terminal hits <- k_s_bounce
+    }
+    HIP_TRY(hipMemcpyAsync(T.W.cnt, up, CN_WORDS * sizeof(unsigned long long), hipMemcpyHostToDevice, T.stream));
+    return TRC_OK;
+}
+
+static int start_batch(StreamCall &C, StreamSlot &T, long long base) {
+    const long long n = C.SP0.P.n;
+    T.base = base;
+    T.nb = (n - base < C.cap) ? (n - base) : C.cap;
+    T.n_in = T.nb; T.n_act = 0; T.b = 0; T.cur = 0; T.attempt = 0; T.busy = true;
+    T.SP = C.SP0;
+    T.SP.W = T.W;
+    T.SP.carry.slot_spec = T.spec_on ? T.spec : nullptr;
+    T.SP.base = base;
+    T.SP.nb = T.nb;
+    TRC_TRY(upload_counters(C, T));
+    return launch_bounce(C, T);
+}
+
+// called when the slot's last launch has completed: takes in its counters and launches its next bounce, if any
+static int advance(StreamCall &C, StreamSlot &T) {
+    StreamEngine &E = C.E;
+    const unsigned long long *c = T.h_cnt;
+#ifdef SW_STATS
+    fprintf(stderr, "batch %lld bounce %d: Q1 %llu Q3 %llu hits %llu | walkers %llu wave-iters %llu steps %llu leaf-entries %llu box-tests %llu drains %llu drain-rounds %llu\n",
+            T.base / C.cap, T.b, c[CN(0)], c[CN(1)], c[CN(6)], c[CN(16)], c[CN(17)], c[CN(18)], c[CN(19)], c[CN(20)], c[CN(21)], c[CN(22)]);
+#endif
+    if (c[CN(4)]) {
+        // The candidate queue was too small for this bounce.  Nothing of the bounce has been committed (k_s_exact,
+        // k_s_shade returns at once when the flag is set): double the queue and run the bounce again.
+        if (c[CN(4)] != 1ull || T.attempt >= 6) return trc_fail(TRC_ERR_CAPACITY, "streaming queues overflow (%llu candidate pairs, capacity %lld)", c[CN(1)], T.W.q3_cap);
+        ++T.attempt;
+        TRC_TRY(stream_q3_grow(T.W));
+        T.SP.W = T.W;
+        TRC_TRY(upload_counters(C, T));
+        return launch_bounce(C, T);
+    }
+    T.attempt = 0;
+    C.seg += (double)T.n_in;
+    C.hits += (double)c[CN(6)];
+    if (T.fresh && T.nb > 0) {       // what the next batches can expect (with a margin; a low guess only costs atomics)
+        const double rate = 1.15 * (double)c[CN(6)] / (double)T.nb + 256.0 / (double)T.nb;
+        if (rate > E.fp_hit_rate || E.fp_hit_rate > 2.0 * rate) E.fp_hit_rate = rate;
+    }
+    if (T.fused && T.b < STREAM_RATE_BOUNCES && T.n_in > 0) {       // (without the split CN(12) stays 0: every hit is on the one list)
+        const double nin = (double)T.n_in, pad = 512.0 / nin;
+        const double rt = 1.15 * (double)c[CN(12)] / nin + pad, ro = 1.15 * (double)(c[CN(6)] - c[CN(12)]) / nin + pad;
+        if (E.rate_term[T.b] < 0.0 || rt > E.rate_term[T.b] || E.rate_term[T.b] > 2.0 * rt) E.rate_term[T.b] = rt > 1.0 ? 1.0 : rt;
+        if (E.rate_other[T.b] < 0.0 || ro > E.rate_other[T.b] || E.rate_other[T.b] > 2.0 * ro) E.rate_other[T.b] = ro > 1.0 ? 1.0 : ro;
+    }
+    if (T.b < STREAM_RATE_BOUNCES) {
+        const double rin = T.b == 0 ? (double)T.nb : (double)T.n_in;
+        if (rin > 0.0)
+            for (int cl = 0; cl < TRC_CLS_COUNT; ++cl) {
+                const double r = 1.15 * (double)c[CN(13 + cl)] / rin + 512.0 / rin;
+                double &R = E.rate_cls[T.b][cl];
+                if (R < 0.0 || r > R || R > 2.0 * r) R = r;
+                C.cls_hits[cl] += (double)c[CN(13 + cl)];
+            }
+    }
+    if (T.b + 1 > C.max_bounces) C.max_bounces = T.b + 1;
+    if (c[CN(7)] == 0 || T.b + 1 >= C.SP0.P.reps) { T.busy = false; return TRC_OK; }
+    // next bounce: the rays just shaded are the active list
+    T.n_act = c[CN(3)];                                       // its reserved entries (the tail of the last chunks is invalid)
+    T.n_in = (long long)c[CN(7)];
+    T.SP.act_in = T.W.act[T.cur];
+    T.cur ^= 1;
+    T.b += 1;
+    TRC_TRY(upload_counters(C, T));
+    return launch_bounce(C, T);
+}
+
+// Runs the whole call batch by batch, two batches in flight.  P is fully set up by trc_trace_fast (inputs staged, source uploaded),
+// which has planned the search (stream_plan) and read the knobs.
+static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, const StreamPlan &plan, const StreamKnobs &K, const trc_source_desc *src_desc,
+                        StreamEngine &E, trc_trace_stats *stats, double *seg_out, double *hit_out) {
+    trc_ctx *ctx = sc->ctx;
     // Batches: equal parts, a multiple of the number of slots (so that the slots finish together), at most 2^26 rays each
     // (14 GB of workspace per slot); calls below 2^23 rays are not split.
-    const long long cap_max = batch_env > 0 ? batch_env : (1ll << 26);
-    int n_slots = (P.n >= (1ll << 23)) ? slots_env : 1;
+    const long long cap_max = 1ll << 26;
+    int n_slots = (P.n >= (1ll << 23)) ? K.slots : 1;
     long long n_batches = n_slots * ((P.n + n_slots * cap_max - 1) / (n_slots * cap_max));
     long long cap = (P.n + n_batches - 1) / n_batches;
     cap = (cap + 63) & ~63ll;
@@ -2323,667 +2972,16 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, b
         for (int b = 0; b < STREAM_RATE_BOUNCES; ++b) { E.rate_term[b] = E.rate_other[b] = -1.0; for (int c = 0; c < TRC_CLS_COUNT; ++c) E.rate_cls[b][c] = -1.0; }
         E.rate_geom_version = sc->geom_version;
     }
-    for (int k = 0; k < n_slots; ++k) TRC_TRY(stream_ws_alloc(E.slot[k].W, cap, (int)sc->accel.unbounded.size(), (long long)sc->tally_n));
     // rays that carry more than the fast engine's record -- Im of a complex index, materials at their wavelength, a spectrum -- are
     // shaded by k_s_shade_x; the spectra of the rays under way live in a table of their own beside the ray table
     const bool carry = sc->carries || carry_in.ref_im || carry_in.mat || carry_in.spec;
-    for (int k = 0; k < n_slots; ++k) {
-        StreamSlot &Tk = E.slot[k];
-        const long long want = (carry_in.spec && carry_in.n_spec > 0) ? (long long)carry_in.n_spec * Tk.W.room : 0;
-        if (Tk.spec_len < want) {
-            dev_free(Tk.spec);
-            Tk.spec = nullptr; Tk.spec_len = 0;
-            TRC_TRY(dev_alloc(&Tk.spec, (size_t)want));
-            Tk.spec_len = want;
-        }
-        Tk.spec_on = want > 0;
-    }
-    StreamParams SP0;
-    memset(&SP0, 0, sizeof(SP0));
-    SP0.P = P;
-    SP0.carry = carry_in;
-    int mode = 0;
-    size_t lds_walk = 0;
-    bool walk_ok = true;
-    if (!stream_plan(sc, want_accel, &mode, &lds_walk, &walk_ok)) return trc_fail(TRC_ERR_CAPACITY, "no streaming form for this scene");
-    const bool big = !walk_ok;                                    // tables beyond LDS (or the 32-bit grid): no general path
-    int gridm = mode == 2 ? 1 : (mode == 3 ? 2 : 0);        // k_s_bounce's form of the search
-    // a few surfaces: neither grid nor lists, the wave takes the surfaces one by one (k_s_bounce<3>).  TRC_STREAM_SMALL=0: as before
-    bool small_scene = S <= STREAM_SMALL_SURFACES && mode != 1 && !big;
-    { const char *ev = getenv("TRC_STREAM_SMALL"); if (ev && !atoi(ev)) small_scene = false; }
-    // (measured on the seven-wall cavity, one batch alone: 1.15 ms per bounce surface by surface against 0.96 ms lane by lane -- every
-    // wave runs all seven exact tests where its lanes needed four or five each; TRC_STREAM_SMALL=3 selects the form for experiments)
-    // Up to four surfaces -- a dish and its receiver -- every lane tests every surface anyway and the form pays: 0.50 against 0.58 ms
-    // per bounce of 1e7 rays.
-    if (small_scene && S <= 4) gridm = 3;
-    { const char *ev = getenv("TRC_STREAM_SMALL"); if (small_scene && ev && atoi(ev) == 3) gridm = 3; if (ev && atoi(ev) == 2) gridm = mode == 2 ? 1 : 0; }
-    SP0.search = big ? 2 : mode;
-    SP0.hit_epoch = sc->hit_epoch;
-    const int wthreads = SW_THREADS;
-    const size_t lds_exact = ((size_t)S * sc->stride * 8 <= 40 * 1024) ? (size_t)S * sc->stride * 8 : 0;
-    SP0.lds_recs = lds_exact ? 1 : 0;
-    if (lds_walk > 64 * 1024)
-        {
-        HIP_TRY(hipFuncSetAttribute((const void *)k_s_walk<SW_THREADS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_walk));
-        HIP_TRY(hipFuncSetAttribute((const void *)k_s_walk<SW_THREADS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_walk));
-    }
-    int walk_bpc = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&walk_bpc, (mode == 2 ? (const void *)k_s_walk<SW_THREADS, true> : (const void *)k_s_walk<SW_THREADS, false>), wthreads, lds_walk) != hipSuccess || walk_bpc < 1) walk_bpc = 1;
-    if (walk_bpc > 2048 / SW_THREADS) walk_bpc = 2048 / SW_THREADS;
-    const unsigned g_wide = (unsigned)(ctx->n_cu * 8);     // 256-thread blocks: 4 waves each, <= 16384 waves in all
-    static int gen_bpc_env = -1;
-    if (gen_bpc_env < 0) { const char *ev = getenv("TRC_GEN_BPC"); gen_bpc_env = ev ? atoi(ev) : 8; if (gen_bpc_env < 1 || gen_bpc_env > 8) gen_bpc_env = 8; }
-    const unsigned g_gen = (unsigned)(ctx->n_cu * gen_bpc_env);
-    const unsigned g_walk = (unsigned)(ctx->n_cu * walk_bpc);
-    unsigned g_shade = (unsigned)(ctx->n_cu * 4);        // (set again below, once the instance of k_s_shade is chosen)
-    unsigned shade_wpb = 4;                              // waves per workgroup of k_s_shade
-    // k_s_shade: tallies, records, optics parameters, flux-map tables, flags and table values in LDS -- all of them or none (its LDS
-    // instance knows the address space of every table; see the kernel) -- and the flux-map bins too while a workgroup stays within
-    // half a CU's LDS (two workgroups per CU)
-    size_t lds_shade = 8;
-    bool shade_lds = false;
-    {
-        const size_t b_tally = (size_t)(3 * S + 2) * 8, b_recs = (size_t)S * sc->stride * 8;
-        const size_t b_tables = (size_t)8 * S * 8 + sc->fm_edges_h.size() * 8 + ((sc->fms_h.size() * sizeof(FluxMapDev) + 7) / 8) * 8 + (size_t)2 * S * 4 + 16;
-        const size_t b_extra = (size_t)sc->n_extra * 8;
-        shade_lds = b_tally + b_recs + b_tables + b_extra <= 72 * 1024;
-        if (shade_lds) lds_shade = b_tally + b_recs + b_tables + b_extra;
-        SP0.P.lds_tally = shade_lds ? 1 : 0;
-        SP0.lds_tables = shade_lds ? 1 : 0;
-        SP0.lds_extra = shade_lds ? 1 : 0;
-        long long bins = 0;
-        for (auto &m : sc->fms_h) bins += (long long)m.nu * m.nv;
-        SP0.lds_fm_bins = 0;
-        if (bins > 0 && shade_lds && lds_shade + (size_t)bins * 8 + 16 <= 78 * 1024) { SP0.lds_fm_bins = (int)bins; lds_shade += (size_t)bins * 8 + 16; }
-    }
-    // scenes of flat surfaces with mirror / diffuse optics only (heliostat fields, plate cavities): the lean instance
-    bool shade_simple = true;
-    for (int i = 0; i < S && shade_simple; ++i)
-        shade_simple = trc_gm_is_flat(sc->surfs[i].gm_kind) && ((TRC_OPT_SIMPLE_MASK >> sc->surfs[i].optics_kind) & 1u);
-    { const char *ev = getenv("TRC_STREAM_SHADE_GENERAL"); if (ev && atoi(ev)) shade_simple = false; }
-    // (instances built for 3 and 4 waves per SIMD -- 168 / 128 registers, 228 / 376 bytes of scratch per lane -- were slower:
-    // 3.09 and 2.70 ms per NSTTF step against 2.54; later, without anything fetched ahead and with the incidence-angle factor out
-    // of line, 192 / 336 bytes and 2.33 / 2.35 ms against 1.99.  The registers are held by the optics code as a whole -- an instance
-    // that only knows Transparent needs none of the spills -- and it does not yield to the obvious: lighter sine / cosine / tangent
-    // kernels for bounded arguments made it worse (their float64 constants live in scalar registers, which then spill into vector
-    // ones))
-    const int shade_waves = 2;
-    const void *shade_fn = shade_simple ? (shade_lds ? (const void *)k_s_shade<true, 2, true> : (const void *)k_s_shade<true, 2, false>)
-                                        : (shade_lds ? (const void *)k_s_shade<false, 2, true> : (const void *)k_s_shade<false, 2, false>);
-    shade_wpb = 2u * (unsigned)shade_waves;
-    g_shade = (unsigned)(ctx->n_cu * (shade_waves == 2 ? 4 : 2));      // 2 waves per SIMD: four workgroups of 256 per CU in two rounds, as before
-    if (lds_shade > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(shade_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_shade));
-    // Shading split by optics class (trc_shade.hip): one kernel per class present in the scene, each taking its hits off the
-    // bounce's list.  TRC_STREAM_SHADE_SPLIT=0: k_s_shade alone, for every kind (tests compare the two).
-    struct ShadeK { int cls; const void *fn; unsigned threads, wpb, max_blocks; size_t lds; int lds_tables, lds_fm_bins; };
-    ShadeK shk[TRC_CLS_COUNT];
-    int n_shk = 0;
-    int term_cls = -1;
-    {
-        int split_env = 1;
-        { const char *ev = getenv("TRC_STREAM_SHADE_SPLIT"); if (ev && !atoi(ev)) split_env = 0; }
-        if (carry) split_env = 0;       // one kernel for every hit: k_s_shade_x (below)
-        bool present[TRC_CLS_COUNT] = {false, false, false};
-        bool any_term = false, all_flat = true;
-        for (int i = 0; i < S; ++i) all_flat = all_flat && trc_gm_is_flat(sc->surfs[i].gm_kind);
-        if (split_env) {
-            // a surface that ends every ray (TRC_SURF_TERMINAL, decided when the surfaces were uploaded) needs no optics when a ray of
-            // energy 0 ends in the reference too (0 <= min_energy): its hits go to a class that is there anyway
-            const bool term_ok = P.min_energy >= 0.0;
-            for (int i = 0; i < S; ++i) {
-                const trc_surface_desc &sd = sc->surfs[i];
-                const int ok = sd.optics_kind;
-                const bool plain = ((ok == TRC_OPT_REFLECTIVE || ok == TRC_OPT_ONE_SIDED_REFLECTIVE) && sd.opt[1] == 0.0) ||
-                                   ((ok == TRC_OPT_REAL_REFLECTIVE || ok == TRC_OPT_ONE_SIDED_REAL_REFLECTIVE) && sd.opt[3] == 0.0) ||
-                                   (ok == TRC_OPT_LAMBERTIAN && sd.opt[2] == 0.0 && sd.opt[4] == 0.0) || ok == TRC_OPT_LAMBERTIAN_SPECULAR;
-                const bool term = term_ok && plain && sd.opt[0] == 1.0;      // (as scene_upload_surfaces sets the flag)
-                if (term) any_term = true; else present[trc_shade_class_of(sd)] = true;
-            }
-            if (any_term) {
-                term_cls = present[TRC_CLS_MIRROR] ? TRC_CLS_MIRROR : present[TRC_CLS_DIFFUSE] ? TRC_CLS_DIFFUSE : -1;
-                if (term_cls < 0)          // nothing lean among the others: the terminal surfaces go by their own class
-                    for (int i = 0; i < S; ++i) present[trc_shade_class_of(sc->surfs[i])] = true;
-            }
-            const size_t b_tally = (size_t)(3 * S + 2) * 8, b_recs = (size_t)S * sc->stride * 8;
-            const size_t b_tables = (size_t)8 * S * 8 + sc->fm_edges_h.size() * 8 + ((sc->fms_h.size() * sizeof(FluxMapDev) + 7) / 8) * 8 + (size_t)2 * S * 4 + 16;
-            long long bins = 0;
-            for (auto &m : sc->fms_h) bins += (long long)m.nu * m.nv;
-            for (int c = 0; c < TRC_CLS_GENERAL; ++c) {
-                if (!present[c]) continue;
-                ShadeK &K = shk[n_shk++];
-                K.cls = c; K.threads = SHC_THREADS; K.wpb = SHC_THREADS / 64;
-                const size_t need = b_tally + b_recs + b_tables + (c == TRC_CLS_MIRROR ? 0 : (size_t)sc->n_extra * 8);
-                const bool in_lds = need <= 120 * 1024;       // (one workgroup of sixteen waves per CU)
-                K.lds = in_lds ? need : 16;
-                K.lds_tables = in_lds ? 1 : 0;
-                K.lds_fm_bins = 0;
-                if (bins > 0 && in_lds && K.lds + (size_t)bins * 8 + 16 <= 150 * 1024) { K.lds_fm_bins = (int)bins; K.lds += (size_t)bins * 8 + 16; }
-                K.fn = trc_shade_lean_kernel(c, all_flat, in_lds);
-                if (K.lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(K.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K.lds));
-                {   // an instance of at most 96 registers runs five waves per SIMD: two workgroups of ten waves per CU when the tables fit twice
-                    hipFuncAttributes fa;
-                    static int five_env = -1;
-                    if (five_env < 0) { const char *ev = getenv("TRC_SHADE_FIVE"); five_env = ev ? atoi(ev) : 0; }      // (measured: NSTTF 2.14 against 1.98 ms per step -- off unless asked for)
-                    if (five_env && hipFuncGetAttributes(&fa, K.fn) == hipSuccess && fa.numRegs <= 96 && 2 * (K.lds + 1024) <= 160 * 1024) {
-                        K.threads = 640; K.wpb = 10;
-                    }
-                }
-                int bpc = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, K.fn, (int)K.threads, K.lds) != hipSuccess || bpc < 1) bpc = 1;
-                if (bpc > 2048 / (int)K.threads) bpc = 2048 / (int)K.threads;
-                K.max_blocks = (unsigned)(ctx->n_cu * bpc);
-                if ((unsigned long long)K.max_blocks * K.wpb > SHADE_MAX_WAVES) K.max_blocks = SHADE_MAX_WAVES / K.wpb;
-            }
-        }
-        if (!split_env || present[TRC_CLS_GENERAL]) {
-            ShadeK &K = shk[n_shk++];
-            K.cls = split_env ? TRC_CLS_GENERAL : -1;
-            K.fn = shade_fn; K.threads = 64 * shade_wpb; K.wpb = shade_wpb; K.max_blocks = g_shade; K.lds = lds_shade;
-            K.lds_tables = SP0.lds_tables; K.lds_fm_bins = SP0.lds_fm_bins;
-            if (carry) {            // the same tables (k_s_shade_c's carve-up), sixteen waves per workgroup
-                K.fn = trc_shade_carry_kernel(shade_lds);
-                K.threads = SHC_THREADS; K.wpb = SHC_THREADS / 64;
-                if (K.lds < 16) K.lds = 16;
-                if (K.lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(K.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)K.lds));
-                int bpc = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, K.fn, (int)K.threads, K.lds) != hipSuccess || bpc < 1) bpc = 1;
-                if (bpc > 2048 / (int)K.threads) bpc = 2048 / (int)K.threads;
-                K.max_blocks = (unsigned)(ctx->n_cu * bpc);
-                if ((unsigned long long)K.max_blocks * K.wpb > SHADE_MAX_WAVES) K.max_blocks = SHADE_MAX_WAVES / K.wpb;
-            }
-        }
-    }
-    SP0.shade_term_cls = term_cls;
-    SP0.chunk_hitbuf = sc->hit_chunk ? sc->hit_chunk : SQ_HIT_CHUNK;
-    // more than one shading kernel: the hit list is parted by class first (k_s_partition), every kernel walks its own part
-    const bool multi = n_shk > 1;
-    if (multi)
-        for (int k = 0; k < n_slots; ++k) {
-            StreamWs &Wk = E.slot[k].W;
-            Wk.pl_room = 2 * Wk.room;
-            for (int q = 0; q < n_shk; ++q) {
-                const int c = shk[q].cls;
-                if (Wk.pl_slot[c]) continue;
-                TRC_TRY(dev_alloc(&Wk.pl_slot[c], (size_t)Wk.pl_room));
-                TRC_TRY(dev_alloc(&Wk.pl_surf[c], (size_t)Wk.pl_room));
-                TRC_TRY(dev_alloc(&Wk.pl_t[c], (size_t)Wk.pl_room));
-            }
-        }
-    // fresh rays of a plane source with a narrow cone: footprint map + k_s_fresh (trc_footprint.h)
-    bool use_fp = false;
-    TRC_TRY(stream_fp_prepare(sc, E, src_desc, &SP0.fp, &use_fp));
-    const void *fresh_fn = nullptr, *cull_fn = nullptr;
-    const void *fresh_one_fn = nullptr;     // k_s_fresh itself where fresh_fn is its two-phase form (a batch whose listed rays mostly hit takes it)
-    int sf_threads = 512;
-    size_t lds_fresh = 0, lds_cull = 0;
-    unsigned g_fresh = 0, g_cull = 0;
-    double general_share = 0.0;        // expected share of the fresh rays that k_s_cull leaves to the general path
-    double listed_share = 1.0;         // ... and lists for k_s_fresh (an estimate for its grid: the covered part of the source)
-    if (use_fp) {
-        const bool buie = src_kind == TRC_SRC_BUIE_DISK || src_kind == TRC_SRC_BUIE_RECT;
-        bool flat = true;
-        for (int i = 0; i < S && flat; ++i) flat = trc_gm_is_flat(sc->surfs[i].gm_kind);
-        sf_threads = SF_THREADS(flat);
-        // k_s_fresh: the tables every listed ray reads go to LDS when they all fit (one workgroup per CU)
-        bool fresh_in_lds = false, fresh_two = false;
-        {
-            const size_t budget = 150 * 1024;
-            lds_fresh = buie ? ((sizeof(trc_buie_fast) + 15) & ~(size_t)15) : 0;
-            const size_t b_obb = (size_t)S * TRC_OBB_LSTRIDE * 4 + 16, b_recs = (size_t)S * sc->stride * 8;
-            const size_t n_list = E.fp->clist.size();
-            const size_t b_lists = ((((size_t)SP0.fp.P.Mc * SP0.fp.P.Mc + 1) * 2 + 15) & ~(size_t)15) + n_list * 2 + 16;
-            // the Buie sources go through the two-phase form (k_s_fresh2): a queue of SFQ_CAP (ray, cell) pairs per wave.  TRC_STREAM_FRESH2=0: k_s_fresh
-            fresh_two = buie;
-            { const char *ev = getenv("TRC_STREAM_FRESH2"); if (ev && !atoi(ev)) fresh_two = false; }
-            const size_t b_queue = fresh_two ? (size_t)(sf_threads / 64) * 2 * SFQ_CAP * 4 + 16 : 0;
-            if (n_list < 65536 && lds_fresh + b_obb + b_recs + b_lists + b_queue <= budget) { fresh_in_lds = true; lds_fresh += b_obb + b_recs + b_lists; }
-            lds_fresh += 32 + b_queue;
-        }
-#define SF_PICK(K) (flat ? (fresh_in_lds ? (const void *)k_s_fresh<K, true, true> : (const void *)k_s_fresh<K, true, false>) \
-                         : (fresh_in_lds ? (const void *)k_s_fresh<K, false, true> : (const void *)k_s_fresh<K, false, false>))
-        fresh_fn = src_kind == TRC_SRC_BUIE_DISK ? SF_PICK(TRC_SRC_BUIE_DISK) : src_kind == TRC_SRC_BUIE_RECT ? SF_PICK(TRC_SRC_BUIE_RECT)
-                 : src_kind == TRC_SRC_PILLBOX_DISK ? SF_PICK(TRC_SRC_PILLBOX_DISK) : SF_PICK(TRC_SRC_PILLBOX_RECT);
-#undef SF_PICK
-#define SF2_PICK(K) (flat ? (fresh_in_lds ? (const void *)k_s_fresh2<K, true, true> : (const void *)k_s_fresh2<K, true, false>) \
-                          : (fresh_in_lds ? (const void *)k_s_fresh2<K, false, true> : (const void *)k_s_fresh2<K, false, false>))
-        const void *fresh1_fn = fresh_fn;
-        if (fresh_two) fresh_fn = src_kind == TRC_SRC_BUIE_DISK ? SF2_PICK(TRC_SRC_BUIE_DISK) : SF2_PICK(TRC_SRC_BUIE_RECT);
-#undef SF2_PICK
-        fresh_one_fn = fresh1_fn;
-        cull_fn = src_kind == TRC_SRC_BUIE_DISK ? (const void *)k_s_cull<TRC_SRC_BUIE_DISK> : src_kind == TRC_SRC_BUIE_RECT ? (const void *)k_s_cull<TRC_SRC_BUIE_RECT>
-                : src_kind == TRC_SRC_PILLBOX_DISK ? (const void *)k_s_cull<TRC_SRC_PILLBOX_DISK> : (const void *)k_s_cull<TRC_SRC_PILLBOX_RECT>;
-        lds_cull = (size_t)SP0.fp.P.M * SP0.fp.P.M / 8 + (SC_GEN_CAP + 4) * 4;
-        if (lds_cull > 160 * 1024 - 512 || lds_fresh > 160 * 1024 - 512) use_fp = false;
-        else {
-            if (lds_fresh > 64 * 1024) HIP_TRY(hipFuncSetAttribute(fresh_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fresh));
-            if (lds_fresh > 64 * 1024 && fresh_one_fn != fresh_fn) HIP_TRY(hipFuncSetAttribute(fresh_one_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fresh));
-            if (lds_cull > 64 * 1024) HIP_TRY(hipFuncSetAttribute(cull_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cull));
-            int bpc = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, fresh_fn, sf_threads, lds_fresh) != hipSuccess || bpc < 1) bpc = 1;
-            if (bpc > 2048 / sf_threads) bpc = 2048 / sf_threads;
-            g_fresh = (unsigned)(ctx->n_cu * bpc);
-            bpc = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, cull_fn, SC_THREADS, lds_cull) != hipSuccess || bpc < 1) bpc = 1;
-            if (bpc > 2048 / SC_THREADS) bpc = 2048 / SC_THREADS;
-            g_cull = (unsigned)(ctx->n_cu * bpc);
-            general_share = SP0.fp.P.has_generic ? (1.0 - SP0.fp.P.cdf_end) : 0.0;
-            if (general_share < 0.0) general_share = 0.0;
-            listed_share = E.fp->coverage * (src_kind == TRC_SRC_BUIE_DISK || src_kind == TRC_SRC_PILLBOX_DISK ? 4.0 / TRC_PI : 1.0);
-            if (listed_share > 1.0) listed_share = 1.0;
-        }
-    }
-    // continued rays (bounces >= 1): one kernel per bounce on the grid / all-boxes forms (k_s_bounce); the Kd walk of
-    // TRC_STREAM_SEARCH=1 keeps the queues.  TRC_STREAM_BOUNCE=0 switches it off (tests compare the two paths).
-    bool use_fused = mode != 1;
-    { const char *ev = getenv("TRC_STREAM_BOUNCE"); if (ev && !atoi(ev) && !big) use_fused = false; }
-    // fresh rays outside the footprint map through k_s_bounce<.., FRESH> instead of the general path: always in large scenes,
-    // elsewhere with TRC_STREAM_FIRST=1 (tests compare the two)
-    bool use_first = big || small_scene;
-    { const char *ev = getenv("TRC_STREAM_FIRST"); if (ev && atoi(ev) && mode != 1) use_first = true; }
-    size_t lds_bounce = 0, lds_first = 0;
-    bool coop_on = false;              // k_s_bounce_coop serves the large grid (it lists terminal hits, never finishes them itself)
-    int sb_threads = SB_THREADS;       // threads per workgroup of the k_s_bounce instance for continued rays
-    const int first_threads = SB_THREADS_OF(gridm);      // ... and of the one for fresh rays
-    unsigned g_bounce = 0, g_first = 0;
-    const void *bounce_fn = nullptr, *first_fn = nullptr;
-    if (use_fused || use_first) {
-        const size_t b_grid = mode == 2 ? ((((size_t)sc->accel.grid_off.size() + 2) & ~(size_t)1) * 2 + sc->accel.grid_list.size() * 2 + 8) : 0;
-        const size_t b_all = (size_t)S * 24 + (size_t)S * TRC_OBB_LSTRIDE * 4 + 16 + (size_t)S * sc->stride * 8 + b_grid + (((size_t)S * 4 + 15) & ~(size_t)15);
-        const size_t b_buie = ((sizeof(trc_buie_fast) + 15) & ~(size_t)15);
-        const bool in_lds = gridm != 2 && gridm != 3 && b_all + b_buie <= 150 * 1024;
-        lds_bounce = (in_lds ? b_all : 0) + 16;
-        SP0.bg_occ_words = 0;
-        // the large grid: k_s_bounce_coop, whose lanes share the tests of their wave's rays (TRC_STREAM_COOP=0: k_s_bounce<2>, every
-        // lane its own ray; tests compare the two)
-        bool coop = gridm == 2;
-        { const char *ev = getenv("TRC_STREAM_COOP"); if (ev && !atoi(ev)) coop = false; }
-        coop_on = coop;
-        if (coop) lds_bounce += (size_t)(SB_THREADS / 64) * SBC_WAVE_BYTES;
-        if (gridm == 2 && sc->accel.big_occ.size() * 4 <= (coop ? 80 : 96) * 1024) {      // the occupancy bits of the large grid
-            SP0.bg_occ_words = (int)sc->accel.big_occ.size();
-            lds_bounce += (sc->accel.big_occ.size() * 4 + 15) & ~(size_t)15;
-        }
-        lds_first = lds_bounce + b_buie;
-#define SB_PICK(FR) (gridm == 3 ? (const void *)k_s_bounce<3, false, FR> : gridm == 2 ? (coop ? (const void *)k_s_bounce_coop<FR, false> : (const void *)k_s_bounce<2, false, FR>) \
-                   : gridm == 1 ? (in_lds ? (const void *)k_s_bounce<1, true, FR> : (const void *)k_s_bounce<1, false, FR>) \
-                                : (in_lds ? (const void *)k_s_bounce<0, true, FR> : (const void *)k_s_bounce<0, false, FR>))
-        bounce_fn = SB_PICK(false);
-        first_fn = SB_PICK(true);
-#undef SB_PICK
-        bool all_flat = true;
-        for (int i = 0; i < S && all_flat; ++i) all_flat = trc_gm_is_flat(sc->surfs[i].gm_kind);
-        if (all_flat)
-            bounce_fn = gridm == 3 ? (const void *)k_s_bounce<3, false, false, true> : gridm == 2 ? (coop ? (const void *)k_s_bounce_coop<false, true> : (const void *)k_s_bounce<2, false, false, true>)
-                      : gridm == 1 ? (in_lds ? (const void *)k_s_bounce<1, true, false, true> : (const void *)k_s_bounce<1, false, false, true>)
-                                   : (in_lds ? (const void *)k_s_bounce<0, true, false, true> : (const void *)k_s_bounce<0, false, false, true>);
-        if (all_flat && gridm == 2 && coop) first_fn = (const void *)k_s_bounce_coop<true, true>;
-        if (lds_bounce > 64 * 1024) HIP_TRY(hipFuncSetAttribute(bounce_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bounce));
-        if (lds_first > 64 * 1024) HIP_TRY(hipFuncSetAttribute(first_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_first));
-        int bpc = 0;
-        sb_threads = SB_THREADS_OF(gridm);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, bounce_fn, sb_threads, lds_bounce) != hipSuccess || bpc < 1) bpc = 1;
-        if (bpc > 2048 / sb_threads) bpc = 2048 / sb_threads;
-        g_bounce = (unsigned)(ctx->n_cu * bpc);
-        bpc = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, first_fn, first_threads, lds_first) != hipSuccess || bpc < 1) bpc = 1;
-        if (bpc > 2048 / first_threads) bpc = 2048 / first_threads;
-        g_first = (unsigned)(ctx->n_cu * bpc);
-    }
-    // hits on surfaces that end every ray (the receiver of a field) are listed apart by k_s_bounce and finished by k_s_absorb --
-    // when the scene has such surfaces and k_s_absorb's tables (those of k_s_shade without records and optics) fit LDS
-    bool use_absorb = false;
-    size_t lds_absorb = 0;
-    unsigned g_absorb = 0;
-    if (use_fused && SP0.P.lds_tally && SP0.lds_tables && !carry) {
-        bool any = false;
-        for (int i = 0; i < S && !any; ++i) {
-            const trc_surface_desc &sd = sc->surfs[i];
-            const int ok = sd.optics_kind;
-            const bool plain = ((ok == TRC_OPT_REFLECTIVE || ok == TRC_OPT_ONE_SIDED_REFLECTIVE) && sd.opt[1] == 0.0) ||
-                           ((ok == TRC_OPT_REAL_REFLECTIVE || ok == TRC_OPT_ONE_SIDED_REAL_REFLECTIVE) && sd.opt[3] == 0.0) ||
-                               (ok == TRC_OPT_LAMBERTIAN && sd.opt[2] == 0.0 && sd.opt[4] == 0.0) || ok == TRC_OPT_LAMBERTIAN_SPECULAR;
-            any = plain && sd.opt[0] == 1.0;
-        }
-        long long bins = 0;
-        for (auto &m : sc->fms_h) bins += (long long)m.nu * m.nv;
-        lds_absorb = (size_t)(3 * S + 2) * 8 + sc->fm_edges_h.size() * 8 + ((sc->fms_h.size() * sizeof(FluxMapDev) + 7) / 8) * 8 + (size_t)2 * S * 4 + 16 +
-                     (SP0.lds_fm_bins ? (size_t)bins * 8 : 0) + 16;
-        const bool fm_ok = bins == 0 || SP0.lds_fm_bins > 0;       // (bins outside LDS would be scattered global atomics at eight waves per SIMD: not this kernel)
-        use_absorb = any && fm_ok && lds_absorb <= 78 * 1024 && sc->tr_off < 0 && P.min_energy >= 0.0;      // (0 <= min_energy: the ray ends there in the reference too)
-        { const char *ev = getenv("TRC_STREAM_ABSORB"); if (ev && !atoi(ev)) use_absorb = false; }
-        if (use_absorb) {
-            if (lds_absorb > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)k_s_absorb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_absorb));
-            g_absorb = (unsigned)ctx->n_cu;        // one workgroup of 16 waves per CU (4096 waves with open chunks of the hit buffer at most)
-        }
-    }
-    SP0.split_terminal = use_absorb ? 1 : 0;
-    // ... and finished inside k_s_bounce when its workgroup has the LDS for the tallies, flux-map tables and bins as well
-    // (TRC_STREAM_ABSORB=1: always behind the list, by k_s_absorb)
-    bool absorb_inline = false;
-    if (use_absorb) {
-        const size_t extra_lds = lds_absorb + 64;
-        int want = 1;
-        { const char *ev = getenv("TRC_STREAM_ABSORB"); if (ev && atoi(ev) == 1) want = 0; }
-        if (want && !(gridm == 2 && coop_on) && lds_bounce + extra_lds <= 158 * 1024) {
-            absorb_inline = true;
-            lds_bounce += extra_lds;
-            if (lds_bounce > 64 * 1024) HIP_TRY(hipFuncSetAttribute(bounce_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bounce));
-            SP0.split_terminal = 2;
-        }
-    }
-    double seg = 0, hits = 0;
-    double cls_hits[TRC_CLS_COUNT] = {0.0, 0.0, 0.0};       // hits shaded by the kernel of each class (first STREAM_RATE_BOUNCES bounces)
-    int launches = 0, max_bounces = 0;
-
-    int static_env = 1;            // read at every call: tests switch it within one process
-    { const char *ev = getenv("TRC_STREAM_STATIC"); if (ev && !atoi(ev)) static_env = 0; }
-    // grids and reservation sizes of a slot's next bounce
-    auto plan_bounce = [&](StreamSlot &T) {
-        // Grids follow the work of the bounce (every kernel strides over its queue, so a small grid is only slower, never
-        // wrong), with at least SW_ITEMS items per thread: later bounces and small calls do not pay for 2048 workgroups
-        // staging their tables.
-        long long work = T.b == 0 ? T.nb : (long long)T.n_act;
-        auto grid_for = [&](unsigned max_blocks, int threads) {
-            long long g = (work + threads - 1) / threads;
-            return (unsigned)(g < 1 ? 1 : (g > (long long)max_blocks ? (long long)max_blocks : g));
-        };
-        // one pre-assigned chunk per appending wave, for `expected` entries over `waves` waves (+ margin): a multiple of 64, at
-        // least SQ_CHUNK, and never more than the lists have room for
-        auto chunk_for = [&](double expected, unsigned long long waves, unsigned floor = SQ_CHUNK) {
-            double c = 1.1 * expected / (double)(waves ? waves : 1ull) + (floor < SQ_CHUNK ? 48.0 : 128.0);
-            const double most = 0.9 * (double)T.W.room / (double)(waves ? waves : 1ull);
-            if (c > most) c = most;
-            unsigned u = ((unsigned)c + 63u) & ~63u;
-            return u < floor ? floor : u;
-        };
-        T.fresh = use_fp && T.b == 0;
-        T.fused = use_fused && T.b > 0;
-        T.first = use_first && T.b == 0 && (!T.fresh || general_share > 0.0);
-        T.general = !T.fused && !T.first && (!T.fresh || general_share > 0.0);
-        T.gb_bounce = T.fused ? grid_for(g_bounce, sb_threads) : 0u;
-        T.gb_cull = T.fresh ? grid_for(g_cull, SC_THREADS * 8) : 0u;
-        T.gb_shade = grid_for(g_shade, 64 * (int)shade_wpb * SW_ITEMS);
-        T.SP.chunk_hit = T.SP.chunk_slot = T.SP.chunk_act = T.SP.chunk_first = T.SP.chunk_thit = SQ_CHUNK;
-        double act_expected = -1.0;          // rays expected to go on from this bounce's shading (< 0: unknown, the waves reserve as they go)
-        long long shade_entries = work;      // entries of the hit list the shading kernels walk (used or not)
-        T.gb_first = 0u;
-        T.cull_chunk = SQ_CHUNK;
-        T.cull_gen_chunk = 0;
-        if (T.fresh) {        // one lane per listed ray, a few rays per lane
-            const double listed = listed_share * (double)T.nb;
-            long long g = ((long long)(1.2 * listed) + 4096 + sf_threads * 2 - 1) / (sf_threads * 2);
-            T.gb_fresh = (unsigned)(g < 1 ? 1 : (g > (long long)g_fresh ? (long long)g_fresh : g));
-            T.cull_chunk = chunk_for(1.1 * listed, (unsigned long long)T.gb_cull * (SC_THREADS / 64));
-            // general-path rays: rare -> per workgroup through LDS; a source with a strong aureole (CSR 0.3: a third of the rays) ->
-            // chunks per wave like the other lists
-            if (general_share * (double)T.nb / (double)T.gb_cull > 0.25 * SC_GEN_CAP)
-                T.cull_gen_chunk = chunk_for(1.1 * general_share * (double)T.nb, (unsigned long long)T.gb_cull * (SC_THREADS / 64));
-            // hits of the fresh rays: measured on the batches before (E.fp_hit_rate), every listed ray to start with
-            const double hits = (E.fp_hit_rate > 0.0 ? E.fp_hit_rate : listed_share) * (double)T.nb;
-            T.SP.chunk_hit = T.SP.chunk_slot = chunk_for(hits, (unsigned long long)T.gb_fresh * (unsigned long long)(sf_threads / 64));
-            act_expected = hits + 2.0 * general_share * (double)T.nb;
-        } else {
-            T.gb_fresh = 0u;
-            if (T.fused) {    // at most the rays that entered the bounce hit, at most those go on
-                const unsigned long long bw = (unsigned long long)T.gb_bounce * (unsigned long long)(sb_threads / 64);
-                const bool known = T.b < STREAM_RATE_BOUNCES && E.rate_term[T.b] >= 0.0;
-                // (the few hits that are left to k_s_shade behind k_s_absorb: short chunks, its list is walked entry by entry)
-                T.SP.chunk_hit = chunk_for((known ? E.rate_other[T.b] : 1.0) * (double)T.n_in, bw, (known && SP0.split_terminal) ? 64u : (unsigned)SQ_CHUNK);
-                T.SP.chunk_thit = chunk_for((known ? E.rate_term[T.b] : 1.0) * (double)T.n_in, bw);
-                // the shading kernels only see the hits that k_s_absorb does not take: grids for the entries of their list, used or not
-                // (every workgroup stages 50 KB of tables and flushes its private sums, hits or not)
-                if (known && (long long)bw * (long long)T.SP.chunk_hit < shade_entries) shade_entries = (long long)bw * (long long)T.SP.chunk_hit;
-                act_expected = (known && SP0.split_terminal ? E.rate_other[T.b] : 1.0) * (double)T.n_in;
-            }
-        }
-        // behind k_s_cull the general path only sees the rays left to it (the Buie aureole)
-        if (T.fresh) work = (long long)(1.5 * general_share * (double)T.nb) + 4096;
-        if (T.first) {
-            T.gb_first = grid_for(g_first, first_threads);
-            T.SP.chunk_first = chunk_for((double)work, (unsigned long long)T.gb_first * (first_threads / 64));      // at most every ray hits
-            if (!T.fresh) act_expected = (double)work;
-        }
-        // the shading kernels of the classes present: grids, and their parts of the active list
-        {
-            const double rays_in0 = T.b == 0 ? (double)T.nb : (double)T.n_in;
-            long long entries_of[TRC_CLS_COUNT] = {shade_entries, shade_entries, shade_entries};
-            T.gb_part = 0u;
-            for (int c = 0; c < TRC_CLS_COUNT; ++c) { T.part_start[c] = 0ull; T.SP.part_chunk[c] = SQ_CHUNK_MAX; T.SP.part_static[c] = 0; }
-            if (multi) {
-                long long g = (shade_entries + 256ll * SW_ITEMS - 1) / (256ll * SW_ITEMS);
-                T.gb_part = (unsigned)(g < 1 ? 1 : (g > (long long)g_wide ? (long long)g_wide : g));
-                const unsigned long long pw = (unsigned long long)T.gb_part * 4ull;
-                for (int k = 0; k < n_shk; ++k) {
-                    const int c = shk[k].cls;
-                    if (!(static_env && T.b < STREAM_RATE_BOUNCES && E.rate_cls[T.b][c] >= 0.0)) continue;      // share not known yet: the waves reserve as they go
-                    double cc = 1.1 * E.rate_cls[T.b][c] * rays_in0 / (double)pw + 128.0;
-                    const double most = (double)T.W.room / (double)pw - 64.0;
-                    if (cc > most) cc = most;
-                    unsigned chunk = ((unsigned)cc + 63u) & ~63u;
-                    if (chunk < SQ_CHUNK) chunk = SQ_CHUNK;
-                    T.SP.part_chunk[c] = chunk;
-                    T.SP.part_static[c] = 1;
-                    T.part_start[c] = pw * (unsigned long long)chunk;
-                    if ((long long)T.part_start[c] < entries_of[c]) entries_of[c] = (long long)T.part_start[c];
-                }
-            }
-            unsigned long long total_waves = 0;
-            T.gb_shade = 1u;
-            for (int k = 0; k < n_shk; ++k) {
-                const long long per = (long long)shk[k].threads * SW_ITEMS;
-                const long long shade_entries_k = multi ? entries_of[shk[k].cls] : shade_entries;
-                long long g = (shade_entries_k + per - 1) / per;
-                g = g < 1 ? 1 : (g > (long long)shk[k].max_blocks ? (long long)shk[k].max_blocks : g);
-                T.gb_sh[k] = (unsigned)g;
-                if (T.gb_sh[k] > T.gb_shade) T.gb_shade = T.gb_sh[k];
-                total_waves += (unsigned long long)g * shk[k].wpb;
-            }
-            const double most = (double)(getenv("TRC_STREAM_ROOM") ? (long long)(0.9 * (double)T.W.act_room) : STREAM_ACT_STATIC(T.W.cap) - 64 * (long long)total_waves) /
-                                (double)(total_waves ? total_waves : 1ull);
-            const double rays_in = T.b == 0 ? (double)T.nb : (double)T.n_in;
-            long long base = 0;
-            for (int k = 0; k < n_shk; ++k) {
-                const unsigned long long waves = (unsigned long long)T.gb_sh[k] * shk[k].wpb;
-                unsigned chunk = SQ_CHUNK;
-                if (act_expected >= 0.0) {
-                    double ex = act_expected;
-                    const int c = shk[k].cls;
-                    if (c >= 0 && T.b < STREAM_RATE_BOUNCES && E.rate_cls[T.b][c] >= 0.0 && E.rate_cls[T.b][c] * rays_in < ex) ex = E.rate_cls[T.b][c] * rays_in;
-                    double cc = 1.1 * ex / (double)waves + 128.0;
-                    if (cc > most) cc = most;
-                    chunk = ((unsigned)cc + 63u) & ~63u;
-                    if (chunk < SQ_CHUNK) chunk = SQ_CHUNK;
-                }
-                T.chunk_act_sh[k] = chunk;
-                T.act_base_sh[k] = base;
-                base += (long long)waves * (long long)chunk;
-            }
-            T.SP.chunk_act = T.chunk_act_sh[0];
-        }
-        T.gb_gen = grid_for(g_gen, 256 * SW_ITEMS);
-        T.gb_wide = grid_for(g_wide, 256 * SW_ITEMS);
-        T.gb_walk = grid_for(g_walk, wthreads * SW_ITEMS);
-        // the largest launches reserve 1024 (walkers) / 512 (candidates) entries per atomic: the counters are single words
-        T.SP.chunk_q1 = work >= (1ll << 22) ? SQ_CHUNK_MAX : SQ_CHUNK;
-        T.SP.chunk_q3 = work >= (1ll << 22) ? 512u : SQ_CHUNK;
-        T.SP.static_first = static_env;
-        T.SP.bounce_no = T.b;
-        T.SP.static_general = static_env && !T.fresh;      // few rays behind k_s_cull: their kernels reserve as they go
-        T.SP.q3_gen_chunk0 = (T.SP.static_general && T.b > 0) ? (long long)T.gb_walk * (wthreads / 64) : -1;
-        T.SP.gen_list = T.fresh ? T.W.gen_list : nullptr;
-        T.SP.slot_base0 = T.fresh ? (long long)T.gb_fresh * (sf_threads / 64) * (long long)T.SP.chunk_slot : 0;
-        T.SP.hit_base0 = T.fresh ? (long long)T.gb_fresh * (sf_threads / 64) * (long long)T.SP.chunk_hit
-                                 : (T.fused ? (long long)T.gb_bounce * (sb_threads / 64) * (long long)T.SP.chunk_hit : 0);
-    };
-    // the kernels of one bounce of a slot's batch, followed by the read-back of its counters
-    auto launch_bounce = [&](StreamSlot &T) -> int {
-        StreamParams &SP = T.SP;
-        const unsigned gb_wide = T.gb_wide, gb_gen = T.gb_gen, gb_walk = T.gb_walk, gb_shade = T.gb_shade;
-        SP.act_out = T.W.act[T.cur];
-        if (T.fresh) {
-            CullParams C;
-            C.F = SP.fp.P; C.mask = SP.fp.mask; C.seed = P.seed; C.rid0 = P.ray_offset + (unsigned long long)T.base; C.nb = T.nb;
-            C.fq_ray = T.W.fq_ray; C.fq_cell = T.W.fq_cell; C.gen_list = T.W.gen_list; C.cnt = T.W.cnt;
-            C.room = T.W.room; C.chunk = T.cull_chunk; C.gen_chunk = T.cull_gen_chunk; C.static_first = SP.static_first;
-            void *cargs[] = {(void *)&C};
-            HIP_TRY(hipLaunchKernel(cull_fn, dim3(T.gb_cull), dim3(SC_THREADS), cargs, lds_cull, T.stream));
-            void *args[] = {(void *)&SP};
-            // the two-phase form pays where most listed rays miss (a field of mirrors: two of three); where most of them hit (a dish
-            // under its own source: the first phase rejects nothing) the batches after the first go back to k_s_fresh
-            const bool mostly_hits = E.fp_hit_rate > 0.0 && E.fp_hit_rate > 0.6 * 1.15 * listed_share;
-            HIP_TRY(hipLaunchKernel(mostly_hits ? fresh_one_fn : fresh_fn, dim3(T.gb_fresh), dim3(sf_threads), args, lds_fresh, T.stream));
-            launches += 2;
-        }
-        if (T.fused) {
-            void *args[] = {(void *)&SP};
-            HIP_TRY(hipLaunchKernel(bounce_fn, dim3(T.gb_bounce), dim3(sb_threads), args, lds_bounce, T.stream));
-            launches += 1;
-        }
-        if (T.first) {
-            void *args[] = {(void *)&SP};
-            HIP_TRY(hipLaunchKernel(first_fn, dim3(T.gb_first), dim3(first_threads), args, lds_first, T.stream));
-            launches += 1;
-        }
-        if (T.general) {
-        if (T.b == 0 && src_kind == TRC_SRC_BUIE_DISK) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_BUIE_DISK>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
-        else if (T.b == 0 && src_kind == TRC_SRC_BUIE_RECT) hipLaunchKernelGGL((k_s_gen<true, TRC_SRC_BUIE_RECT>), dim3(gb_gen), dim3(256), 0, T.stream, SP);
-        else if (T.b == 0 && src_kind == TRC_SRC_PILLBOX_DISK) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_PILLBOX_DISK>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
-        else if (T.b == 0 && src_kind == TRC_SRC_PILLBOX_RECT) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_PILLBOX_RECT>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
-        else if (T.b == 0) hipLaunchKernelGGL(k_s_gen<true>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
-        else hipLaunchKernelGGL(k_s_gen<false>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
-        if (SP.search == 2) hipLaunchKernelGGL((k_s_walk<SW_THREADS, true>), dim3(gb_walk), dim3(wthreads), lds_walk, T.stream, SP);
-        else hipLaunchKernelGGL((k_s_walk<SW_THREADS, false>), dim3(gb_walk), dim3(wthreads), lds_walk, T.stream, SP);
-        hipLaunchKernelGGL(k_s_exact, dim3(gb_wide), dim3(256), lds_exact, T.stream, SP);
-        launches += 3;
-        }
-        if (multi) {
-            void *args[] = {(void *)&SP};
-            HIP_TRY(hipLaunchKernel((const void *)k_s_partition, dim3(T.gb_part), dim3(256), args, 0, T.stream));
-            launches += 1;
-        }
-        for (int k = 0; k < n_shk; ++k) {
-            StreamParams SK = SP;
-            SK.shade_cls = shk[k].cls;
-            if (multi) {
-                const int c = shk[k].cls;
-                SK.hl_slot = T.W.pl_slot[c]; SK.hl_surf = T.W.pl_surf[c]; SK.hl_t = T.W.pl_t[c]; SK.hl_room = T.W.pl_room; SK.hl_cn = CN(24 + c);
-            } else {
-                SK.hl_slot = T.W.hit_slot; SK.hl_surf = T.W.hit_surf; SK.hl_t = T.W.hit_t; SK.hl_room = T.W.room; SK.hl_cn = CN(2);
-            }
-            SK.chunk_act = T.chunk_act_sh[k];
-            SK.act_base0 = T.act_base_sh[k];
-            SK.lds_tables = shk[k].lds_tables; SK.lds_extra = shk[k].lds_tables; SK.lds_fm_bins = shk[k].lds_fm_bins;
-            void *args[] = {(void *)&SK};
-            HIP_TRY(hipLaunchKernel(shk[k].fn, dim3(T.gb_sh[k]), dim3(shk[k].threads), args, shk[k].lds, T.stream));
-            launches += 1;
-        }
-        (void)gb_shade;
-        if (T.fused && SP.split_terminal == 1) {
-            void *args[] = {(void *)&SP};
-            long long g = ((long long)T.n_act + SA_THREADS * 2 - 1) / (SA_THREADS * 2);
-            HIP_TRY(hipLaunchKernel((const void *)k_s_absorb, dim3((unsigned)(g < 1 ? 1 : (g > (long long)g_absorb ? (long long)g_absorb : g))), dim3(SA_THREADS), args, lds_absorb, T.stream));
-            launches += 1;
-        }
-        HIP_TRY(hipMemcpyAsync(T.h_cnt, T.W.cnt, CN_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, T.stream));
-        HIP_TRY(hipEventRecord(T.done, T.stream));
-        return TRC_OK;
-    };
-    // counters of a slot for its next launch: everything zero except the length of the active list
-    auto upload_counters = [&](StreamSlot &T) -> int {
-        plan_bounce(T);
-        for (int i = 0; i < CN_WORDS; ++i) T.h_cnt[CN_WORDS + i] = 0ull;
-        T.h_cnt[CN_WORDS + CN(5)] = T.n_act;
-        if (T.SP.static_first) {       // the first chunk of every appending wave is pre-assigned: the lists start behind them
-            // (a kernel that is not launched never closes its pre-assigned chunks: it must not be given any)
-            const unsigned long long fresh_waves = T.fresh ? (unsigned long long)T.gb_fresh * (unsigned long long)(sf_threads / 64) : 0ull;
-            const unsigned long long cull_waves = T.fresh ? (unsigned long long)T.gb_cull * (SC_THREADS / 64) : 0ull;
-            const bool sg = T.SP.static_general != 0 && T.general;
-            if (sg) {
-                T.h_cnt[CN_WORDS + CN(0)] = (unsigned long long)T.gb_gen * 4ull * T.SP.chunk_q1;                           // Q1 <- k_s_gen
-                T.h_cnt[CN_WORDS + CN(1)] = ((unsigned long long)T.gb_walk * (unsigned long long)(wthreads / 64) +
-                                             (T.SP.q3_gen_chunk0 >= 0 ? (unsigned long long)T.gb_gen * 4ull : 0ull)) * T.SP.chunk_q3;   // Q3 <- k_s_walk (+ k_s_gen<false>)
-            }
-            const unsigned long long first_entries = T.first ? (unsigned long long)T.gb_first * (first_threads / 64) * T.SP.chunk_first : 0ull;
-            T.h_cnt[CN_WORDS + CN(2)] = (unsigned long long)T.SP.hit_base0 + (sg ? (unsigned long long)T.gb_wide * 4ull * SQ_CHUNK : 0ull) + first_entries;   // hit list <- k_s_fresh / k_s_bounce, k_s_exact / k_s_bounce<FRESH>
-            for (int c = 0; c < TRC_CLS_COUNT; ++c) T.h_cnt[CN_WORDS + CN(24 + c)] = T.part_start[c];                      // class lists <- k_s_partition
-            {                                                                                                                  // active list <- the shading kernels
-                unsigned long long a = 0;
-                for (int k = 0; k < n_shk; ++k) a += (unsigned long long)T.gb_sh[k] * shk[k].wpb * T.chunk_act_sh[k];
-                T.h_cnt[CN_WORDS + CN(3)] = a;
-            }
-            T.h_cnt[CN_WORDS + CN(8)] = (unsigned long long)T.SP.slot_base0 + ((sg && T.b == 0) ? (unsigned long long)T.gb_gen * 4ull * SQ_CHUNK : 0ull) + first_entries;   // slots <- k_s_fresh, k_s_gen<true> / k_s_bounce<FRESH>
-            T.h_cnt[CN_WORDS + CN(9)] = cull_waves * (unsigned long long)T.cull_gen_chunk;                                 // general-path list <- k_s_cull
-            T.h_cnt[CN_WORDS + CN(10)] = cull_waves * (unsigned long long)T.cull_chunk;                                   // footprint list <- k_s_cull
-            if (T.fused && T.SP.split_terminal == 1) T.h_cnt[CN_WORDS + CN(11)] = (unsigned long long)T.gb_bounce * (unsigned long long)(sb_threads / 64) * T.SP.chunk_thit;   // terminal hits <- k_s_bounce
-            (void)fresh_waves;
-        }
-        HIP_TRY(hipMemcpyAsync(T.W.cnt, T.h_cnt + CN_WORDS, CN_WORDS * sizeof(unsigned long long), hipMemcpyHostToDevice, T.stream));
-        return TRC_OK;
-    };
-    auto start_batch = [&](StreamSlot &T, long long base) -> int {
-        T.base = base;
-        T.nb = (P.n - base < cap) ? (P.n - base) : cap;
-        T.n_in = T.nb; T.n_act = 0; T.b = 0; T.cur = 0; T.attempt = 0; T.busy = true;
-        T.SP = SP0;
-        T.SP.W = T.W;
-        T.SP.carry.slot_spec = T.spec_on ? T.spec : nullptr;
-        T.SP.base = base;
-        T.SP.nb = T.nb;
-        TRC_TRY(upload_counters(T));
-        return launch_bounce(T);
-    };
-    // called when the slot's last launch has completed
-    auto advance = [&](StreamSlot &T) -> int {
-        const unsigned long long *c = T.h_cnt;
-#ifdef SW_STATS
-        fprintf(stderr, "batch %lld bounce %d: Q1 %llu Q3 %llu hits %llu | walkers %llu wave-iters %llu steps %llu leaf-entries %llu box-tests %llu drains %llu drain-rounds %llu\n",
-                T.base / cap, T.b, c[CN(0)], c[CN(1)], c[CN(6)], c[CN(16)], c[CN(17)], c[CN(18)], c[CN(19)], c[CN(20)], c[CN(21)], c[CN(22)]);
-#endif
-        if (c[CN(4)]) {
-            // The candidate queue was too small for this bounce.  Nothing of the bounce has been committed (k_s_exact,
-            // k_s_shade returns at once when the flag is set): double the queue and run the bounce again.
-            if (c[CN(4)] != 1ull || T.attempt >= 6) return trc_fail(TRC_ERR_CAPACITY, "streaming queues overflow (%llu candidate pairs, capacity %lld)", c[CN(1)], T.W.q3_cap);
-            ++T.attempt;
-            TRC_TRY(stream_q3_grow(T.W));
-            T.SP.W = T.W;
-            TRC_TRY(upload_counters(T));
-            return launch_bounce(T);
-        }
-        T.attempt = 0;
-        seg += (double)T.n_in;
-        hits += (double)c[CN(6)];
-        if (T.fresh && T.nb > 0) {       // what the next batches can expect (with a margin; a low guess only costs atomics)
-            const double rate = 1.15 * (double)c[CN(6)] / (double)T.nb + 256.0 / (double)T.nb;
-            if (rate > E.fp_hit_rate || E.fp_hit_rate > 2.0 * rate) E.fp_hit_rate = rate;
-        }
-        if (T.fused && T.b < STREAM_RATE_BOUNCES && T.n_in > 0) {       // (without the split CN(12) stays 0: every hit is on the one list)
-            const double nin = (double)T.n_in, pad = 512.0 / nin;
-            const double rt = 1.15 * (double)c[CN(12)] / nin + pad, ro = 1.15 * (double)(c[CN(6)] - c[CN(12)]) / nin + pad;
-            if (E.rate_term[T.b] < 0.0 || rt > E.rate_term[T.b] || E.rate_term[T.b] > 2.0 * rt) E.rate_term[T.b] = rt > 1.0 ? 1.0 : rt;
-            if (E.rate_other[T.b] < 0.0 || ro > E.rate_other[T.b] || E.rate_other[T.b] > 2.0 * ro) E.rate_other[T.b] = ro > 1.0 ? 1.0 : ro;
-        }
-        if (T.b < STREAM_RATE_BOUNCES) {
-            const double rin = T.b == 0 ? (double)T.nb : (double)T.n_in;
-            if (rin > 0.0)
-                for (int cl = 0; cl < TRC_CLS_COUNT; ++cl) {
-                    const double r = 1.15 * (double)c[CN(13 + cl)] / rin + 512.0 / rin;
-                    double &R = E.rate_cls[T.b][cl];
-                    if (R < 0.0 || r > R || R > 2.0 * r) R = r;
-                    cls_hits[cl] += (double)c[CN(13 + cl)];
-                }
-        }
-        if (T.b + 1 > max_bounces) max_bounces = T.b + 1;
-        if (c[CN(7)] == 0 || T.b + 1 >= P.reps) { T.busy = false; return TRC_OK; }
-        // next bounce: the rays just shaded are the active list
-        T.n_act = c[CN(3)];                                       // its reserved entries (the tail of the last chunks is invalid)
-        T.n_in = (long long)c[CN(7)];
-        T.SP.act_in = T.W.act[T.cur];
-        T.cur ^= 1;
-        T.b += 1;
-        TRC_TRY(upload_counters(T));
-        return launch_bounce(T);
-    };
+    StreamForms F;
+    StreamCall C{F, K, E, StreamParams(), cap, 0.0, 0.0, {0.0, 0.0, 0.0}, 0, 0};
+    memset(&C.SP0, 0, sizeof(C.SP0));
+    C.SP0.P = P;
+    C.SP0.carry = carry_in;
+    TRC_TRY(stream_choose_forms(F, C.SP0, sc, E, plan, carry, src_desc, K));
+    TRC_TRY(stream_slots_alloc(E, n_slots, cap, sc, carry_in, F, K));
 
     for (int k = 0; k < STREAM_MAX_SLOTS; ++k) E.slot[k].busy = false;
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
@@ -2993,7 +2991,7 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, b
     int rc = TRC_OK;
     for (;;) {
         for (int k = 0; k < n_slots && rc == TRC_OK; ++k)
-            if (!E.slot[k].busy && next_base < P.n) { rc = start_batch(E.slot[k], next_base); next_base += cap; }
+            if (!E.slot[k].busy && next_base < P.n) { rc = start_batch(C, E.slot[k], next_base); next_base += cap; }
         if (rc != TRC_OK) break;
         int n_busy = 0;
         for (int k = 0; k < n_slots; ++k) n_busy += E.slot[k].busy ? 1 : 0;
@@ -3002,16 +3000,13 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, b
         int k = -1;
         for (int j = 0; j < n_slots; ++j) {
             const int q = (turn + j) % n_slots;
-            if (E.slot[q].busy && hipEventQuery(E.slot[q].done) == hipSuccess) { k = q; break; }
+            if (!E.slot[q].busy) continue;
+            if (k < 0) k = q;
+            if (hipEventQuery(E.slot[q].done) == hipSuccess) { k = q; break; }
         }
-        if (k < 0)
-            for (int j = 0; j < n_slots; ++j) {
-                const int q = (turn + j) % n_slots;
-                if (E.slot[q].busy) { k = q; break; }
-            }
         hipError_t se = hipEventSynchronize(E.slot[k].done);
         if (se != hipSuccess) { rc = trc_fail(TRC_ERR_DEVICE, "streaming bounce failed: %s", hipGetErrorString(se)); break; }
-        rc = advance(E.slot[k]);
+        rc = advance(C, E.slot[k]);
         if (rc != TRC_OK) break;
         turn = (k + 1) % n_slots;
     }
@@ -3032,7 +3027,7 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, b
     (void)hipEventElapsedTime(&total_ms, ctx->ev0, ctx->ev1);
     for (int k = 0; k < n_slots; ++k)
         hipLaunchKernelGGL(k_s_merge_tallies, dim3((unsigned)((sc->tally_n + 255) / 256)), dim3(256), 0, ctx->stream, sc->d_tally, E.slot[k].W.tally_part, (long long)sc->tally_n);
-    hipLaunchKernelGGL(k_s_add2, dim3(1), dim3(64), 0, ctx->stream, sc->d_tally + 3 * S, seg, hits);
+    hipLaunchKernelGGL(k_s_add2, dim3(1), dim3(64), 0, ctx->stream, sc->d_tally + 3 * sc->n_surf, C.seg, C.hits);
     // (not waited for: whatever reads or resets the tallies synchronises the context's stream first, and the next call's kernels
     // are ordered behind these by ev0)
     stats->kernel_ms = total_ms;
@@ -3052,9 +3047,9 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, b
         }
     }
 #endif
-    stats->launches = launches + 1;
-    stats->bounces = max_bounces;
-    *seg_out = seg;
-    *hit_out = hits;
+    stats->launches = C.launches + 1;
+    stats->bounces = C.max_bounces;
+    *seg_out = C.seg;
+    *hit_out = C.hits;
     return TRC_OK;
 }
