@@ -17,6 +17,8 @@ HDR := $(CSRC)/trc_core.h $(CSRC)/trc_bounds.h $(CSRC)/trc_footprint.h $(CSRC)/t
 
 HOSTCHECK := $(ROOT)tests/hostcheck/libtrc_hostcheck.so
 HOSTCHECK_SRC := $(ROOT)tests/hostcheck/hostcheck.cpp
+SPECCHECK := $(ROOT)tests/hostcheck/libtrc_spectrum_check.so
+SPECCHECK_SRC := $(ROOT)tests/hostcheck/spectrum_check.cpp
 
 all: $(LIB)
 
@@ -48,10 +50,14 @@ $(LIB): $(OBJS)
 	mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared -o $@ $(OBJS)
 
-hostcheck: $(HOSTCHECK)
+hostcheck: $(HOSTCHECK) $(SPECCHECK)
 
 $(HOSTCHECK): $(HOSTCHECK_SRC) $(HDR)
 	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(HOSTCHECK_SRC)
+
+# the source-spectrum sampler of the per-ray core, host-compiled for its tests
+$(SPECCHECK): $(SPECCHECK_SRC) $(HDR)
+	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(SPECCHECK_SRC)
 
 # assembly listings with the registers, scratch and occupancy of every kernel (build/*.s, build/*.resources.txt)
 asm: $(SRCS) $(HDR)
@@ -67,6 +73,6 @@ asm-shade: $(CSRC)/trc_shade.hip $(HDR)
 		-o $(ROOT)build/trc_shade.s $(CSRC)/trc_shade.hip 2> $(ROOT)build/trc_shade.resources.txt
 
 clean:
-	rm -f $(LIB) $(HOSTCHECK)
+	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK)
 
 .PHONY: all hostcheck asm asm-shade clean

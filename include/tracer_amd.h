@@ -208,6 +208,24 @@ typedef struct trc_source_desc {
     double buie[3 * (TRC_BUIE_NELEM + 1) + 6];
 } trc_source_desc;
 
+/*
+ * Spectrum of a source: every source ray gets one wavelength drawn on the device from it (spectral Monte Carlo), a pure
+ * function of (seed, stream id) that leaves the ray's position, direction and energy as they are without a spectrum.
+ * CONSTANT: every ray has `wavelength`.  TABLE: a piecewise-linear spectral density (the inverse CDF of the reference's
+ * ray_trace_utils/sampling.py:35-52, PW_linear_distribution), n points (2..4096) of strictly increasing wavelengths `wl` and
+ * finite, non-negative densities `value` with a positive integral.  The rays start in a medium of index `ref_index`.
+ */
+typedef enum trc_spectrum_kind { TRC_SPECTRUM_NONE = 0, TRC_SPECTRUM_CONSTANT = 1, TRC_SPECTRUM_TABLE = 2 } trc_spectrum_kind;
+#define TRC_SPECTRUM_MAX_POINTS 4096
+typedef struct trc_source_spectrum {
+    int32_t kind;
+    int32_t n;              /* TABLE: points, 2..4096 */
+    double wavelength;      /* CONSTANT */
+    double ref_index;       /* index of the medium the rays start in (1.0 = the value without a spectrum) */
+    const double *wl;       /* TABLE: n strictly increasing wavelengths */
+    const double *value;    /* TABLE: n finite, non-negative spectral densities, linear between points */
+} trc_source_spectrum;
+
 /* ---- Kd-tree (reference: tracer/accel_tree.py) ------------------------------ */
 /*
  * Flattened tree as built on the host with the reference's SAH rules
@@ -369,6 +387,10 @@ int trc_kdtree_traversal(trc_ctx *ctx, const trc_kdtree_desc *kd, int32_t n_surf
 int trc_trace_fast(trc_scene *scene, const trc_rays *in, const trc_source_desc *src, int64_t n,
                    int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset,
                    int32_t flags, trc_rays *last, trc_trace_stats *stats);
+/* The same with the spectrum of `src` (NULL: trc_trace_fast).  A spectrum with a given bundle `in` is TRC_ERR_INVALID. */
+int trc_trace_fast_x(trc_scene *scene, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
+                     int64_t n, int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset,
+                     int32_t flags, trc_rays *last, trc_trace_stats *stats);
 
 /*
  * TracerEngine.ray_tracer(..., tree=True): the ordered engine.  Reproduces the reference's
@@ -379,6 +401,10 @@ int trc_trace_fast(trc_scene *scene, const trc_rays *in, const trc_source_desc *
 int trc_trace_ordered(trc_scene *scene, const trc_rays *in, const trc_source_desc *src, int64_t n,
                       int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset,
                       int32_t flags, trc_result **out, trc_trace_stats *stats);
+/* The same with the spectrum of `src` (NULL: trc_trace_ordered): level 0 carries the drawn wavelengths and ref_index. */
+int trc_trace_ordered_x(trc_scene *scene, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
+                        int64_t n, int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset,
+                        int32_t flags, trc_result **out, trc_trace_stats *stats);
 int trc_result_num_levels(trc_result *res, int32_t *n_levels);
 /* n_total rays recorded at this level, the first n_live of which continued to the next bounce */
 int trc_result_level_size(trc_result *res, int32_t level, int64_t *n_total, int64_t *n_live);
@@ -393,6 +419,9 @@ int trc_result_destroy(trc_result *res);
 /* sources.*_bundle(...) materialised as a bundle (sources.py:175-515) */
 int trc_source_generate(trc_ctx *ctx, const trc_source_desc *src, int64_t n, uint64_t seed,
                         uint64_t ray_offset, trc_rays *out);
+/* The same with a spectrum (NULL: trc_source_generate); out->wavelength and out->ref_index are filled when non-NULL. */
+int trc_source_generate_x(trc_ctx *ctx, const trc_source_desc *src, const trc_source_spectrum *spec, int64_t n, uint64_t seed,
+                          uint64_t ray_offset, trc_rays *out);
 
 /*
  * Start points of the first n rays of a disc / rectangle source (sources.py:175-515) in the source's own plane coordinates

@@ -74,6 +74,17 @@ class SourceDesc(C.Structure):
                 ('energy', C.c_double), ('buie', C.c_double * BUIE_LEN)]
 
 
+# enum trc_spectrum_kind
+SPECTRUM_NONE, SPECTRUM_CONSTANT, SPECTRUM_TABLE = range(3)
+SPECTRUM_MAX_POINTS = 4096
+
+
+class SourceSpectrumDesc(C.Structure):
+    """trc_source_spectrum (built by source_spectrum.SourceSpectrum, which keeps its arrays alive)"""
+    _fields_ = [('kind', C.c_int32), ('n', C.c_int32), ('wavelength', C.c_double), ('ref_index', C.c_double),
+                ('wl', _p_f64), ('value', _p_f64)]
+
+
 class KdTreeDesc(C.Structure):
     _fields_ = [('n_nodes', C.c_int32), ('n_leaf_surfs', C.c_int32), ('n_always', C.c_int32),
                 ('reserved', C.c_int32), ('flag', _p_i32), ('split', _p_f64), ('child', _p_i32),
@@ -124,11 +135,18 @@ SIGNATURES = {
                                  C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(Rays), C.POINTER(TraceStats)]),
     'trc_trace_ordered': (C.c_int, [_vp, C.POINTER(Rays), C.POINTER(SourceDesc), C.c_int64, C.c_int32, C.c_double,
                                     C.c_uint64, C.c_uint64, C.c_int32, _pvp, C.POINTER(TraceStats)]),
+    'trc_trace_fast_x': (C.c_int, [_vp, C.POINTER(Rays), C.POINTER(SourceDesc), C.POINTER(SourceSpectrumDesc), C.c_int64,
+                                   C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(Rays),
+                                   C.POINTER(TraceStats)]),
+    'trc_trace_ordered_x': (C.c_int, [_vp, C.POINTER(Rays), C.POINTER(SourceDesc), C.POINTER(SourceSpectrumDesc), C.c_int64,
+                                      C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_int32, _pvp, C.POINTER(TraceStats)]),
     'trc_result_num_levels': (C.c_int, [_vp, _p_i32]),
     'trc_result_level_size': (C.c_int, [_vp, C.c_int32, _p_i64, _p_i64]),
     'trc_result_level_get': (C.c_int, [_vp, C.c_int32, C.POINTER(Rays), _p_i32]),
     'trc_result_destroy': (C.c_int, [_vp]),
     'trc_source_generate': (C.c_int, [_vp, C.POINTER(SourceDesc), C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(Rays)]),
+    'trc_source_generate_x': (C.c_int, [_vp, C.POINTER(SourceDesc), C.POINTER(SourceSpectrumDesc), C.c_int64, C.c_uint64,
+                                        C.c_uint64, C.POINTER(Rays)]),
     'trc_source_start32': (C.c_int, [_vp, C.POINTER(SourceDesc), C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), _p_f64]),
     'trc_gm_find_intersections': (C.c_int, [_vp, C.POINTER(SurfaceDesc), C.c_int32, _p_f64, C.POINTER(Rays), _p_f64,

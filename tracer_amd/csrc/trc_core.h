@@ -1857,6 +1857,50 @@ TRC_HD void trc_source_ray(const trc_source_desc *src, const double *buie, const
 }
 
 // ---------------------------------------------------------------------------------------------
+// Source spectra: one wavelength per source ray from a piecewise-linear spectral density (the inverse CDF of
+// ray_trace_utils/sampling.py:35-52, PW_linear_distribution.sample).  The table: n >= 2 strictly increasing wavelengths
+// wl[], the density val[] normalised to a unit trapezoid integral, and its running integral cdf[] (cdf[0] = 0, cdf[n-1] = 1
+// exactly; packed on the host in float64, trc_spectrum_pack).  u in [0, 1).
+// ---------------------------------------------------------------------------------------------
+TRC_HD double trc_spectrum_sample(const double *wl, const double *val, const double *cdf, int n, double u) {
+    // interval i: the largest i <= n-2 with cdf[i] <= u.  As cdf[n-1] = 1 > u, cdf[i+1] > u: an interval of zero mass
+    // (zero density at both ends) has cdf[i+1] == cdf[i] and is never chosen.
+    int lo = 0, hi = n - 1;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (cdf[mid] <= u) lo = mid; else hi = mid;
+    }
+    const double x0 = wl[lo], h = wl[lo + 1] - wl[lo];
+    const double p0 = val[lo], s = (val[lo + 1] - val[lo]) / h;
+    const double q = u - cdf[lo];                   // mass to cover inside the interval
+    if (!(q > 0.0)) return x0;
+    double t;
+    if (s == 0.0) t = q / p0;                       // flat: linear map
+    else t = 2.0 * q / (p0 + sqrt(fmax(0.0, p0 * p0 + 2.0 * s * q)));  // positive root of s/2 t^2 + p0 t - q = 0, without
+                                                    // cancellation (the discriminant of a density falling to 0 can round below 0)
+    if (!(t > 0.0)) t = 0.0;
+    if (t > h) t = h;
+    return x0 + t;
+}
+
+// The wavelength of source ray `rid`: event 0, Philox block 0xFFFFFFFF (no source draws from it: positions and directions use
+// block 0, the x_cut redraws blocks 2..4097), the first uniform of the pair.  A pure function of (seed, rid).
+#define TRC_SPECTRUM_BLOCK 0xFFFFFFFFu
+TRC_HD double trc_spectrum_draw(const double *wl, const double *val, const double *cdf, int n, uint64_t seed, uint64_t rid) {
+    double u0, u1;
+    trc_uniform_pair(seed, rid, 0u, TRC_SPECTRUM_BLOCK, &u0, &u1);
+    return trc_spectrum_sample(wl, val, cdf, n, u0);
+}
+
+// Wavelength and index of source ray `rid` from a packed spectrum (the engines' FastParams.spec): spec[0] = n (0: constant),
+// spec[1] = the constant wavelength, spec[2] = ref_index, then wl[n] | val[n] | cdf[n].
+TRC_HD void trc_spectrum_of(const double *spec, uint64_t seed, uint64_t rid, double *wl, double *ref) {
+    const int n = (int)spec[0];
+    *ref = spec[2];
+    *wl = n > 0 ? trc_spectrum_draw(spec + 3, spec + 3 + n, spec + 3 + 2 * n, n, seed, rid) : spec[1];
+}
+
+// ---------------------------------------------------------------------------------------------
 // O8 -- flux-map bin of a coordinate for numpy.histogram edges (right edge of the last bin closed)
 // ---------------------------------------------------------------------------------------------
 TRC_HD int trc_bin_index(const double *edges, int nbins, double x) {

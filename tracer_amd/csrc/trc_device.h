@@ -316,6 +316,8 @@ struct FastParams {
     int lds_scene;    // surfaces (+ Kd arrays) staged in LDS
     int lds_tally;    // tallies privatised in LDS
     int capture;      // some surface captures hits
+    // source spectrum (trc_spectrum_of layout) when the rays of `src` draw wavelengths; read only by the SPEC instances
+    const double *spec;
 };
 
 
@@ -539,7 +541,7 @@ static inline int trc_shade_class_of(const trc_surface_desc &sd) {
 
 // the lean shading kernels (trc_shade.hip): kernel of a class for a scene of flat surfaces only (flat) with its tables in LDS (lds)
 const void *trc_shade_carry_kernel(bool lds);      // k_s_shade_x (trc_shade.hip): every optics kind, with what the rays carry
-const void *trc_shade_lean_kernel(int cls, bool flat, bool lds);
+const void *trc_shade_lean_kernel(int cls, bool flat, bool lds, bool spec = false);
 #ifndef SHC_THREADS
 #define SHC_THREADS 1024
 #endif

@@ -121,6 +121,8 @@ struct trc_scene {
     unsigned long long *d_counters;
     double *d_energy_left;     // = (double *)(d_counters + 5)
     trc_source_desc *d_src_buf; // device copy of the source descriptor of the call in progress (kept between calls)
+    double *d_spec_buf;         // device copy of the packed source spectrum of the call in progress (FastParams.spec), and its room
+    size_t spec_cap;
     trc_source_desc src_host;   // ... and what it holds (src_host_ok): a Monte-Carlo loop hands over the same descriptor every call
     bool src_host_ok;
     unsigned long long cnt_host[8];   // host copy of d_counters as trc_trace_fast left them (cnt_host_ok): the next call does not read
@@ -496,14 +498,16 @@ __device__ __forceinline__ void coop_drain_leaves(const trc_accel_view &A, const
 }
 
 // fresh ray for a lane: from the source descriptor or from the given bundle
-template <int KIND = -1>
+template <int KIND = -1, bool SPEC = false>
 __device__ __forceinline__ void fast_new_ray(const FastParams &P, const double *buie, long long id, double &px, double &py,
                                              double &pz, double &dx, double &dy, double &dz, double &e, double &ref, double &wl,
                                              unsigned long long &rid, const trc_buie_fast *bf = nullptr) {
     rid = P.rid ? P.rid[id] : (P.ray_offset + (unsigned long long)id);
     if (P.src) {
         trc_source_ray_t<KIND>(P.src, buie, buie ? buie + TRC_BUIE_TABLE : nullptr, P.seed, rid, &px, &py, &pz, &dx, &dy, &dz, bf);
-        e = P.src->energy; ref = 1.0; wl = 0.0;
+        e = P.src->energy;
+        if (SPEC) trc_spectrum_of(P.spec, P.seed, rid, &wl, &ref);     // (the megakernel draws at birth: its rays live in registers)
+        else { ref = 1.0; wl = 0.0; }
     } else {
         px = P.x[id]; py = P.y[id]; pz = P.z[id];
         dx = P.dx[id]; dy = P.dy[id]; dz = P.dz[id];
@@ -517,7 +521,7 @@ __device__ __forceinline__ void fast_new_ray(const FastParams &P, const double *
 // staged in LDS when they fit in 64 KiB, read from global memory otherwise.  Used when the single-precision data
 // cannot be built or do not fit (very large scenes), and as a cross-check of the cooperative kernel.
 //   LDS (doubles): [recs S*stride][kd_split nodes][buie 639][tally 3S+2] then int32: [kd_a][kd_b][leaf][always]
-template <int THREADS>
+template <int THREADS, bool SPEC = false>
 __global__ __launch_bounds__(THREADS) void k_trace_fast(FastParams P) {
     extern __shared__ double lds[];
     const DScene &sc = P.sc;
@@ -593,7 +597,7 @@ __global__ __launch_bounds__(THREADS) void k_trace_fast(FastParams P) {
         if (next < end && need) {
             long long id = next + __popcll(need & lt_mask);
             if (!alive && id < end) {
-                fast_new_ray(P, buie, id, px, py, pz, dx, dy, dz, e, ref, wl, rid);
+                fast_new_ray<-1, SPEC>(P, buie, id, px, py, pz, dx, dy, dz, e, ref, wl, rid);
                 bounce = 0;
                 prev = S;
                 alive = true;
@@ -639,7 +643,7 @@ __global__ __launch_bounds__(THREADS) void k_trace_fast(FastParams P) {
 // memory (they are rare); everything the candidate search touches lives in LDS:
 //   doubles [buie 639][tally 3S+2] | float [sbox 6S] | u32 [nodes 2n] | i32 [always][unbounded] | u16 [leaf] |
 //   16-byte aligned per-wave regions of COOP_WAVE_BYTES(depth)
-template <int THREADS>
+template <int THREADS, bool SPEC = false>
 __global__ __launch_bounds__(THREADS) void k_trace_coop(FastParams P) {
     extern __shared__ double lds[];
     const DScene &sc = P.sc;
@@ -728,7 +732,7 @@ __global__ __launch_bounds__(THREADS) void k_trace_coop(FastParams P) {
             if (next < end && need) {
                 long long id = next + __popcll(need & lt_mask);
                 if (!alive && id < end) {
-                    fast_new_ray(P, buie, id, px, py, pz, dx, dy, dz, e, ref, wl, rid);
+                    fast_new_ray<-1, SPEC>(P, buie, id, px, py, pz, dx, dy, dz, e, ref, wl, rid);
                     bounce = 0;
                     prev = S;
                     alive = true;
@@ -1550,7 +1554,7 @@ extern "C" int trc_scene_destroy(trc_scene *sc) {
     dev_free(sc->d_a_sbox); dev_free(sc->d_a_obb); dev_free(sc->d_a_nodes); dev_free(sc->d_a_leaf); dev_free(sc->d_a_unbounded); dev_free(sc->d_a_bleaf);
     dev_free(sc->d_a_goff); dev_free(sc->d_a_glist); dev_free(sc->d_a_gapart); dev_free(sc->d_a_bg_off); dev_free(sc->d_a_bg_occ); dev_free(sc->d_a_bg_ent); dev_free(sc->d_a_bg_apart);
     dev_free(sc->d_kd_split); dev_free(sc->d_tally); dev_free(sc->d_fm_of_surf); dev_free(sc->d_fms);
-    dev_free(sc->d_fm_edges); dev_free(sc->d_counters); dev_free(sc->d_src_buf); dev_free(sc->d_h_surf); dev_free(sc->d_hx);
+    dev_free(sc->d_fm_edges); dev_free(sc->d_counters); dev_free(sc->d_src_buf); dev_free(sc->d_spec_buf); dev_free(sc->d_h_surf); dev_free(sc->d_hx);
     for (int i = 0; i < 8; ++i) dev_free(sc->d_h[i]);
     for (int i = 0; i < 7; ++i) dev_free(sc->d_last[i]);
     delete sc;
@@ -2261,9 +2265,10 @@ static int upload_source(const trc_source_desc *src, trc_source_desc **d_src) {
 // ================================================================================================
 // C-ABI: fast engine
 // ================================================================================================
-extern "C" int trc_trace_fast(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, int64_t n, int32_t reps,
-                              double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags, trc_rays *last,
-                              trc_trace_stats *stats) {
+// d_spec: the packed spectrum of `src` on the device (trc_spectrum_of layout), NULL without one
+static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, const double *d_spec, int64_t n, int32_t reps,
+                           double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags, trc_rays *last,
+                           trc_trace_stats *stats) {
     if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
     if ((in == nullptr) == (src == nullptr)) return trc_fail(TRC_ERR_INVALID, "exactly one of `in` and `src` must be given");
     if (n < 0 || reps < 0) return trc_fail(TRC_ERR_INVALID, "n and reps must be >= 0");
@@ -2397,6 +2402,7 @@ extern "C" int trc_trace_fast(trc_scene *sc, const trc_rays *in, const trc_sourc
         carry_in.hit_x = hit_x; carry_in.hit_x_cap = sc->hx_cap;
         carry_in.ref_im = carry_d[0]; carry_in.mat = carry_d[1]; carry_in.spec_wl = carry_d[2]; carry_in.spec = carry_d[3]; carry_in.n_mat = carry_mat; carry_in.n_spec = carry_W;
         P.src = d_src;
+        P.spec = d_spec;
         P.n = n; P.reps = reps; P.flags = flags; P.min_energy = min_energy; P.seed = seed; P.ray_offset = ray_offset;
         P.lx = d_last[0]; P.ly = d_last[1]; P.lz = d_last[2]; P.ldx = d_last[3]; P.ldy = d_last[4]; P.ldz = d_last[5]; P.le = d_last[6];
         P.last_cap = last_cap;
@@ -2469,8 +2475,13 @@ extern "C" int trc_trace_fast(trc_scene *sc, const trc_rays *in, const trc_sourc
         (void)hipStreamSynchronize(ctx->stream);       // (the sums of an earlier streaming call may still be on their way into the buffer)
         if (hipMemcpy(tally_before, sc->d_tally + 3 * S, sizeof(tally_before), hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "counter readback failed"); break; }
         void (*kern)(FastParams) = nullptr;
-        if (m32) kern = threads == 512 ? k_trace_coop<512> : k_trace_coop<256>;
-        else kern = k_trace_fast<256>;
+        if (P.spec) {       // (a source with a spectrum: the instances that draw the wavelength)
+            if (m32) kern = threads == 512 ? k_trace_coop<512, true> : k_trace_coop<256, true>;
+            else kern = k_trace_fast<256, true>;
+        } else {
+            if (m32) kern = threads == 512 ? k_trace_coop<512> : k_trace_coop<256>;
+            else kern = k_trace_fast<256>;
+        }
         // persistent grid: as many workgroups as are resident at once (at most 8 per CU), never more waves than rays/64
         unsigned resident = 0;
         if ((st = kernel_grid_cap((const void *)kern, threads, lds, 8, ctx->n_cu, &resident))) break;
@@ -2605,6 +2616,156 @@ extern "C" int trc_source_generate(trc_ctx *ctx, const trc_source_desc *src, int
 }
 
 // ================================================================================================
+// source spectra (trc_source_spectrum): one wavelength per source ray, drawn from (seed, stream id)
+// ================================================================================================
+// wl[i], ref[i] of source rays offset + i: CONSTANT writes the constant, TABLE draws (trc_spectrum_draw; tab = wl | val | cdf)
+__global__ __launch_bounds__(256) void k_source_spectrum(const double *tab, int n_tab, int kind, double wl_const, double ref_index,
+                                                         long long n, unsigned long long seed, unsigned long long offset,
+                                                         double *wl, double *ref) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        if (wl) wl[i] = kind == TRC_SPECTRUM_TABLE ? trc_spectrum_draw(tab, tab + n_tab, tab + 2 * n_tab, n_tab, seed, offset + (unsigned long long)i)
+                                                   : wl_const;
+        if (ref) ref[i] = ref_index;
+    }
+}
+
+// A spectrum checked and packed for the device: wl | density normalised to a unit trapezoid integral | its running integral
+// (float64 on the host; the last entry of the CDF is 1 exactly, so every u in [0, 1) finds an interval of positive mass).
+static int spectrum_pack(const trc_source_spectrum *sp, const char *who, std::vector<double> &tab) {
+    tab.clear();
+    if (sp->kind != TRC_SPECTRUM_CONSTANT && sp->kind != TRC_SPECTRUM_TABLE)
+        return trc_fail(TRC_ERR_INVALID, "%s: spectrum kind %d is neither CONSTANT nor TABLE", who, sp->kind);
+    if (!std::isfinite(sp->ref_index) || !(sp->ref_index > 0.0))
+        return trc_fail(TRC_ERR_INVALID, "%s: spectrum ref_index must be finite and positive", who);
+    if (sp->kind == TRC_SPECTRUM_CONSTANT) {
+        if (!std::isfinite(sp->wavelength)) return trc_fail(TRC_ERR_INVALID, "%s: spectrum wavelength is not finite", who);
+        return TRC_OK;
+    }
+    const int n = sp->n;
+    if (n < 2 || n > TRC_SPECTRUM_MAX_POINTS)
+        return trc_fail(TRC_ERR_INVALID, "%s: spectrum table has %d points, 2..%d allowed", who, n, TRC_SPECTRUM_MAX_POINTS);
+    if (!sp->wl || !sp->value) return trc_fail(TRC_ERR_INVALID, "%s: spectrum table without wavelengths or values", who);
+    for (int i = 0; i < n; ++i) {
+        if (!std::isfinite(sp->wl[i])) return trc_fail(TRC_ERR_INVALID, "%s: spectrum wavelength %d is not finite", who, i);
+        if (i > 0 && !(sp->wl[i] > sp->wl[i - 1]))
+            return trc_fail(TRC_ERR_INVALID, "%s: spectrum wavelengths are not strictly increasing (point %d)", who, i);
+        if (!std::isfinite(sp->value[i]) || sp->value[i] < 0.0)
+            return trc_fail(TRC_ERR_INVALID, "%s: spectrum value %d is negative or not finite", who, i);
+    }
+    tab.assign((size_t)3 * n, 0.0);
+    double *w = tab.data(), *v = w + n, *c = v + n;
+    double cum = 0.0;
+    for (int i = 0; i < n; ++i) {
+        w[i] = sp->wl[i];
+        if (i > 0) cum += (sp->wl[i] - sp->wl[i - 1]) * (sp->value[i] + sp->value[i - 1]) / 2.;
+        c[i] = cum;
+    }
+    if (!(cum > 0.0) || !std::isfinite(cum)) return trc_fail(TRC_ERR_INVALID, "%s: spectrum table has a zero (or non-finite) integral", who);
+    for (int i = 0; i < n; ++i) { v[i] = sp->value[i] / cum; c[i] = c[i] / cum; }
+    return TRC_OK;
+}
+
+static bool spectrum_given(const trc_source_spectrum *sp) { return sp && sp->kind != TRC_SPECTRUM_NONE; }
+
+// wl / ref (device columns, either may be NULL) of source rays offset .. offset+n-1 on the context's stream
+static int spectrum_fill(trc_ctx *ctx, const trc_source_spectrum *sp, const std::vector<double> &tab, int64_t n, uint64_t seed,
+                         uint64_t ray_offset, double *wl, double *ref) {
+    if (n == 0 || (!wl && !ref)) return TRC_OK;
+    double *d_tab = nullptr;
+    const int n_tab = sp->kind == TRC_SPECTRUM_TABLE ? sp->n : 0;
+    if (n_tab) {
+        TRC_TRY(dev_alloc(&d_tab, tab.size()));
+        if (hipMemcpy(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { dev_free(d_tab); return trc_fail(TRC_ERR_DEVICE, "spectrum upload failed"); }
+    }
+    long long grid = (n + 255) / 256;
+    if (grid > 8192) grid = 8192;
+    hipLaunchKernelGGL(k_source_spectrum, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const double *)d_tab, n_tab, sp->kind,
+                       sp->wavelength, sp->ref_index, (long long)n, (unsigned long long)seed, (unsigned long long)ray_offset, wl, ref);
+    hipError_t se = hipStreamSynchronize(ctx->stream);
+    dev_free(d_tab);
+    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_source_spectrum failed: %s", hipGetErrorString(se));
+    return TRC_OK;
+}
+
+extern "C" int trc_source_generate_x(trc_ctx *ctx, const trc_source_desc *src, const trc_source_spectrum *spec, int64_t n,
+                                     uint64_t seed, uint64_t ray_offset, trc_rays *out) {
+    if (!spectrum_given(spec)) return trc_source_generate(ctx, src, n, seed, ray_offset, out);
+    if (!ctx || !src || n < 0) return trc_fail(TRC_ERR_INVALID, "trc_source_generate_x: bad arguments");
+    std::vector<double> tab;
+    TRC_TRY(spectrum_pack(spec, "trc_source_generate_x", tab));
+    TRC_TRY(trc_source_generate(ctx, src, n, seed, ray_offset, out));
+    if (n == 0 || (!out->wavelength && !out->ref_index)) return TRC_OK;
+    if (out->on_device) return spectrum_fill(ctx, spec, tab, n, seed, ray_offset, out->wavelength, out->ref_index);
+    double *d[2] = {nullptr, nullptr};
+    double *host[2] = {out->wavelength, out->ref_index};
+    int st = TRC_OK;
+    do {
+        for (int i = 0; i < 2 && st == TRC_OK; ++i) if (host[i]) st = dev_alloc(&d[i], (size_t)n);
+        if (st || (st = spectrum_fill(ctx, spec, tab, n, seed, ray_offset, d[0], d[1]))) break;
+        for (int i = 0; i < 2; ++i)
+            if (host[i] && hipMemcpy(host[i], d[i], (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
+    } while (0);
+    dev_free(d[0]); dev_free(d[1]);
+    return st;
+}
+
+extern "C" int trc_trace_fast(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, int64_t n, int32_t reps,
+                              double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags, trc_rays *last,
+                              trc_trace_stats *stats) {
+    return trace_fast_impl(sc, in, src, nullptr, n, reps, min_energy, seed, ray_offset, flags, last, stats);
+}
+
+static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
+                              const std::vector<double> *spec_tab, int64_t n, int32_t reps, double min_energy, uint64_t seed,
+                              uint64_t ray_offset, int32_t flags, trc_result **out, trc_trace_stats *stats);
+
+// The spectrum travels to the engines as FastParams.spec (trc_spectrum_of layout: n, constant wavelength, index, then the table),
+// kept on the scene between calls.  The SPEC instances of the kernels draw the wavelength where a source ray first needs one.
+extern "C" int trc_trace_fast_x(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
+                                int64_t n, int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags,
+                                trc_rays *last, trc_trace_stats *stats) {
+    if (!spectrum_given(spec)) return trc_trace_fast(sc, in, src, n, reps, min_energy, seed, ray_offset, flags, last, stats);
+    if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
+    if (in) return trc_fail(TRC_ERR_INVALID, "trc_trace_fast_x: a spectrum belongs to a source descriptor, not to a given bundle");
+    if (!src) return trc_fail(TRC_ERR_INVALID, "trc_trace_fast_x: a spectrum needs a source descriptor");
+    std::vector<double> tab;
+    TRC_TRY(spectrum_pack(spec, "trc_trace_fast_x", tab));
+    const int n_tab = spec->kind == TRC_SPECTRUM_TABLE ? spec->n : 0;
+    std::vector<double> packed((size_t)3 + tab.size());
+    packed[0] = (double)n_tab; packed[1] = spec->wavelength; packed[2] = spec->ref_index;
+    std::copy(tab.begin(), tab.end(), packed.begin() + 3);
+    HIP_TRY(hipSetDevice(sc->ctx->device));
+    if (sc->spec_cap < packed.size()) {
+        dev_free(sc->d_spec_buf);
+        sc->spec_cap = 0;
+        TRC_TRY(dev_alloc(&sc->d_spec_buf, (size_t)3 + 3 * TRC_SPECTRUM_MAX_POINTS));     // (room for any table: allocated once)
+        sc->spec_cap = (size_t)3 + 3 * TRC_SPECTRUM_MAX_POINTS;
+    }
+    // (the stream is idle between calls: every call ends with a synchronous read of its counters)
+    HIP_TRY(hipMemcpy(sc->d_spec_buf, packed.data(), packed.size() * 8, hipMemcpyHostToDevice));
+    return trace_fast_impl(sc, nullptr, src, sc->d_spec_buf, n, reps, min_energy, seed, ray_offset, flags, last, stats);
+}
+
+extern "C" int trc_trace_ordered_x(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
+                                   int64_t n, int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags,
+                                   trc_result **out, trc_trace_stats *stats) {
+    if (!spectrum_given(spec)) return trace_ordered_impl(sc, in, src, nullptr, nullptr, n, reps, min_energy, seed, ray_offset, flags, out, stats);
+    if (!sc || !out) return trc_fail(TRC_ERR_INVALID, "trc_trace_ordered_x: bad arguments");
+    *out = nullptr;
+    if (in) return trc_fail(TRC_ERR_INVALID, "trc_trace_ordered_x: a spectrum belongs to a source descriptor, not to a given bundle");
+    if (!src) return trc_fail(TRC_ERR_INVALID, "trc_trace_ordered_x: a spectrum needs a source descriptor");
+    std::vector<double> tab;
+    TRC_TRY(spectrum_pack(spec, "trc_trace_ordered_x", tab));
+    return trace_ordered_impl(sc, nullptr, src, spec, &tab, n, reps, min_energy, seed, ray_offset, flags, out, stats);
+}
+
+extern "C" int trc_trace_ordered(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, int64_t n, int32_t reps,
+                                 double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags, trc_result **out,
+                                 trc_trace_stats *stats) {
+    return trace_ordered_impl(sc, in, src, nullptr, nullptr, n, reps, min_energy, seed, ray_offset, flags, out, stats);
+}
+
+// ================================================================================================
 // C-ABI: ordered engine
 // ================================================================================================
 static void level_free(Level &L) {
@@ -2690,9 +2851,10 @@ extern "C" int trc_result_destroy(trc_result *res) {
     return TRC_OK;
 }
 
-extern "C" int trc_trace_ordered(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, int64_t n, int32_t reps,
-                                 double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags, trc_result **out,
-                                 trc_trace_stats *stats) {
+// spec / spec_tab: the spectrum of `src` and its packed table (spectrum_pack), NULL without one
+static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
+                              const std::vector<double> *spec_tab, int64_t n, int32_t reps, double min_energy, uint64_t seed,
+                              uint64_t ray_offset, int32_t flags, trc_result **out, trc_trace_stats *stats) {
     if (!sc || !out) return trc_fail(TRC_ERR_INVALID, "trc_trace_ordered: bad arguments");
     *out = nullptr;
     if ((in == nullptr) == (src == nullptr)) return trc_fail(TRC_ERR_INVALID, "exactly one of `in` and `src` must be given");
@@ -2748,8 +2910,12 @@ extern "C" int trc_trace_ordered(trc_scene *sc, const trc_rays *in, const trc_so
             hipLaunchKernelGGL(k_source_generate, dim3((unsigned)g0), dim3(256), 0, ctx->stream, d_src, (long long)n,
                                (unsigned long long)seed, (unsigned long long)ray_offset, B0.x, B0.y, B0.z, B0.dx, B0.dy,
                                B0.dz, B0.e, B0.rid);
-            hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)g0), dim3(256), 0, ctx->stream, B0.ref, (long long)n, 1.0);
-            hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)g0), dim3(256), 0, ctx->stream, B0.wl, (long long)n, 0.0);
+            if (spec) {     // level 0 carries the wavelengths the source's spectrum gives its rays, and their index
+                if ((st = spectrum_fill(ctx, spec, *spec_tab, n, seed, ray_offset, B0.wl, B0.ref))) break;
+            } else {
+                hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)g0), dim3(256), 0, ctx->stream, B0.ref, (long long)n, 1.0);
+                hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)g0), dim3(256), 0, ctx->stream, B0.wl, (long long)n, 0.0);
+            }
         } else {
             if ((st = check_rays(in, n, "trc_trace_ordered"))) break;
             if (!in->e) { st = trc_fail(TRC_ERR_INVALID, "ray energies are required"); break; }

@@ -21,7 +21,7 @@
 // FLATN: every surface of the scene is flat (its normal is the z axis of its frame, flat_surface.py:84-91)
 // LDS:   tallies, records, optics parameters, flux-map tables, flags (and the optics tables for the DIFFUSE class) are staged in
 //        LDS -- all of them or none, so that every access has a known address space (see k_s_shade)
-template <int CLS, bool FLATN, bool LDS>
+template <int CLS, bool FLATN, bool LDS, bool SPEC = false>
 __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
     extern __shared__ double lds[];
     const FastParams &P = S.P;
@@ -163,7 +163,11 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
         if (mine) {
             n_hit += 1;
             const int prev = bounce0 == 0 ? Sn : (int)((uint32_t)(g.tail >> 32) & ~SQ_SKIP_SELF);      // the surface the ray left; Sn = the source
-            double e = src_energy, wl = 0.0;
+            double e = src_energy, wl = 0.0, ref0 = 1.0;
+            // a source with a spectrum: the wavelength of a fresh ray is drawn at its first hit (the mirror class does not read it, but
+            // hands it on to the ray's next record)
+            if (SPEC && !aux_in)
+                trc_spectrum_of(P.spec, P.seed, P.ray_offset + (unsigned long long)(S.base + (long long)g.idx), &wl, &ref0);
 #if SHC_PREFETCH == 2
             if (aux_in) { e = ae; wl = aw; }
 #else
@@ -217,7 +221,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
                     go.tail = sray_tail(bounce0 + 1, pw);
                     W.geo[slot] = go;
                     if (aux_in) W.aux[slot].e = e_out;        // (index and wavelength stay as they are: no optics of these classes changes them)
-                    else { SRayAux ao; ao.e = e_out; ao.ref = 1.0; ao.wl = 0.0; ao.pad = 0.0; W.aux[slot] = ao; }
+                    else { SRayAux ao; ao.e = e_out; ao.ref = SPEC ? ref0 : 1.0; ao.wl = SPEC ? wl : 0.0; ao.pad = 0.0; W.aux[slot] = ao; }
                 }
             }
         }
@@ -533,9 +537,11 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
 
 const void *trc_shade_carry_kernel(bool lds) { return lds ? (const void *)k_s_shade_x<true> : (const void *)k_s_shade_x<false>; }
 
-const void *trc_shade_lean_kernel(int cls, bool flat, bool lds) {
-#define SHC_PICK(C) (flat ? (lds ? (const void *)k_s_shade_c<C, true, true> : (const void *)k_s_shade_c<C, true, false>) \
-                          : (lds ? (const void *)k_s_shade_c<C, false, true> : (const void *)k_s_shade_c<C, false, false>))
+const void *trc_shade_lean_kernel(int cls, bool flat, bool lds, bool spec) {
+#define SHC_PICK(C) (spec ? (flat ? (lds ? (const void *)k_s_shade_c<C, true, true, true> : (const void *)k_s_shade_c<C, true, false, true>) \
+                                  : (lds ? (const void *)k_s_shade_c<C, false, true, true> : (const void *)k_s_shade_c<C, false, false, true>)) \
+                          : (flat ? (lds ? (const void *)k_s_shade_c<C, true, true> : (const void *)k_s_shade_c<C, true, false>) \
+                                  : (lds ? (const void *)k_s_shade_c<C, false, true> : (const void *)k_s_shade_c<C, false, false>)))
     if (cls == TRC_CLS_MIRROR) return SHC_PICK(TRC_CLS_MIRROR);
     if (cls == TRC_CLS_DIFFUSE) return SHC_PICK(TRC_CLS_DIFFUSE);
 #undef SHC_PICK

@@ -1700,7 +1700,7 @@ __global__ __launch_bounds__(256) void k_s_partition(StreamParams S) {
 // LDS: tallies, records, optics parameters, flux-map tables, flags and table values are all staged in LDS -- or none of them is (as
 // in k_s_fresh): a pointer that may be either is read with flat loads, and a flat load waits for every load in flight -- the ray
 // records fetched ahead included (81 flat operations, 60 full waits in the instance that chose at run time).
-template <bool SIMPLE, int WAVES, bool LDS>
+template <bool SIMPLE, int WAVES, bool LDS, bool SPEC = false>
 __global__ __launch_bounds__(128 * WAVES, WAVES) void k_s_shade(StreamParams S) {
     extern __shared__ double lds[];
     const FastParams &P = S.P;
@@ -1832,10 +1832,15 @@ __global__ __launch_bounds__(128 * WAVES, WAVES) void k_s_shade(StreamParams S) 
             int bounce = (int)(uint32_t)g.tail;
             int prev = bounce == 0 ? Sn : (int)((uint32_t)(g.tail >> 32) & ~SQ_SKIP_SELF);      // the surface the ray left (transfer matrix); Sn = the source
             double e, ref, wl;
-            if (bounce == 0 && P.src) { e = src_energy; ref = 1.0; wl = 0.0; }
-            else { e = ae; ref = ar; wl = aw; }
             const long long ray_no = S.base + (long long)g.idx;
             unsigned long long rid = P.rid ? P.rid[ray_no] : (P.ray_offset + (unsigned long long)ray_no);
+            if (bounce == 0 && P.src) {
+                e = src_energy;
+                // a source with a spectrum: the wavelength is drawn here, at the ray's first hit (culled rays and misses never draw)
+                if (SPEC) trc_spectrum_of(P.spec, P.seed, rid, &wl, &ref);
+                else { ref = 1.0; wl = 0.0; }
+            }
+            else { e = ae; ref = ar; wl = aw; }
             const double e_in = e;
             bool vol = false;
             if (LDS) alive = fast_shade<true, SIMPLE>(Pl, recs, l_tally, t, s, px, py, pz, dx, dy, dz, e, ref, wl, rid, bounce, prev, &hc, l_fm, true, &vol);
@@ -2421,8 +2426,11 @@ static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene 
     // that only knows Transparent needs none of the spills -- and it does not yield to the obvious: lighter sine / cosine / tangent
     // kernels for bounded arguments made it worse (their float64 constants live in scalar registers, which then spill into vector
     // ones))
-    const void *shade_fn = shade_simple ? (shade_lds ? (const void *)k_s_shade<true, 2, true> : (const void *)k_s_shade<true, 2, false>)
-                                        : (shade_lds ? (const void *)k_s_shade<false, 2, true> : (const void *)k_s_shade<false, 2, false>);
+    const bool spec = SP0.P.spec != nullptr;      // (a source with a spectrum: the instances that draw the wavelength at the first hit)
+    const void *shade_fn = spec ? (shade_simple ? (shade_lds ? (const void *)k_s_shade<true, 2, true, true> : (const void *)k_s_shade<true, 2, false, true>)
+                                                : (shade_lds ? (const void *)k_s_shade<false, 2, true, true> : (const void *)k_s_shade<false, 2, false, true>))
+                                : shade_simple ? (shade_lds ? (const void *)k_s_shade<true, 2, true> : (const void *)k_s_shade<true, 2, false>)
+                                               : (shade_lds ? (const void *)k_s_shade<false, 2, true> : (const void *)k_s_shade<false, 2, false>);
     int n_shk = 0;
     int term_cls = -1;
     const bool split = !carry;
@@ -2453,7 +2461,7 @@ static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene 
             K.lds_tables = in_lds ? 1 : 0;
             K.lds_fm_bins = 0;
             if (bins > 0 && in_lds && K.lds + (size_t)bins * 8 + 16 <= 150 * 1024) { K.lds_fm_bins = (int)bins; K.lds += (size_t)bins * 8 + 16; }
-            K.fn = trc_shade_lean_kernel(c, all_flat, in_lds);
+            K.fn = trc_shade_lean_kernel(c, all_flat, in_lds, spec);
             TRC_TRY(stream_shade_grid(K, n_cu));
         }
     }

@@ -462,14 +462,18 @@ class DeviceScene(object):
 
     # -- tracing --------------------------------------------------------------------------------
     def _bundle_args(self, bundle):
-        """(rays struct or None, source desc or None, n, seed override, offset, keepalive)"""
+        """(rays struct or None, source desc or None, n, seed override, offset, keepalive, source spectrum desc or None)"""
         from .sources import LazySourceBundle
+        mats = getattr(self.compiled, 'materials', [])
         if isinstance(bundle, LazySourceBundle) and bundle.is_pending():
-            desc, n, seed, off = bundle.source_args()
-            return None, desc, n, seed, off, None
+            spec = bundle.source_spectrum()
+            # (surfaces between tabulated materials need m(lambda) of every ray from the host: such a bundle is made first and
+            # traced as a given one, below)
+            if spec is None or not mats:
+                desc, n, seed, off = bundle.source_args()
+                return None, desc, n, seed, off, spec, spec.desc() if spec is not None else None
         cols = bundle.columns_soa()
         n = cols['x'].shape[0]
-        mats = getattr(self.compiled, 'materials', [])
         if mats:
             # the materials' own m(lambda) at every ray's wavelength (children inherit the wavelength): tables, files and analytic
             # models alike, and the device's comparison `index == material_1's` (optics_callables.py:750) stays exact
@@ -480,12 +484,12 @@ class DeviceScene(object):
                                ref_index=cols.get('ref_index'), wavelength=cols.get('wavelength'),
                                ref_index_im=cols.get('ref_index_im'), spec_wl=cols.get('spec_wl'), spectra=cols.get('spectra'),
                                mat=cols.get('mat'))
-        return rays, None, n, None, 0, cols
+        return rays, None, n, None, 0, cols, None
 
     def trace_fast(self, bundle, reps, min_energy, seed, accel=False, keep_last=False, stream=None, last_capacity=None):
         """last_capacity: room for the rays still alive after `reps` interactions (keep_last); None = one per ray.  More rays
         left than that is a TracerAmdError with status ERR_CAPACITY."""
-        rays, src, n, src_seed, off, keep = self._bundle_args(bundle)
+        rays, src, n, src_seed, off, keep, spec = self._bundle_args(bundle)
         if src_seed is not None:
             seed = src_seed
         flags = (_cabi.TRACE_ACCEL if accel else 0) | (_cabi.TRACE_KEEP_LAST if keep_last else 0) | \
@@ -497,26 +501,27 @@ class DeviceScene(object):
             m = n if last_capacity is None else max(1, min(int(last_capacity), n))
             last_cols = [N.empty(m) for _ in range(7)]
             last = _cabi.make_rays(m, *last_cols)
-        _cabi.check(self.lib.trc_trace_fast(self.handle, C.byref(rays) if rays is not None else None,
-                                            C.byref(src) if src is not None else None, n, int(reps), float(min_energy),
-                                            int(seed), int(off), flags, C.byref(last) if last is not None else None,
-                                            C.byref(stats)))
+        _cabi.check(self.lib.trc_trace_fast_x(self.handle, C.byref(rays) if rays is not None else None,
+                                              C.byref(src) if src is not None else None, C.byref(spec) if spec is not None else None,
+                                              n, int(reps), float(min_energy), int(seed), int(off), flags,
+                                              C.byref(last) if last is not None else None, C.byref(stats)))
         if keep_last:
             m = last.n
             last_cols = [c[:m] for c in last_cols]
         return stats, last_cols
 
     def trace_ordered(self, bundle, reps, min_energy, seed, accel=False):
-        rays, src, n, src_seed, off, keep = self._bundle_args(bundle)
+        rays, src, n, src_seed, off, keep, spec = self._bundle_args(bundle)
         if src_seed is not None:
             seed = src_seed
         flags = _cabi.TRACE_ACCEL if accel else 0
         stats = _cabi.TraceStats()
         res = C.c_void_p()
-        _cabi.check(self.lib.trc_trace_ordered(self.handle, C.byref(rays) if rays is not None else None,
-                                               C.byref(src) if src is not None else None, n, int(reps),
-                                               float(min_energy), int(seed), int(off), flags, C.byref(res),
-                                               C.byref(stats)))
+        _cabi.check(self.lib.trc_trace_ordered_x(self.handle, C.byref(rays) if rays is not None else None,
+                                                 C.byref(src) if src is not None else None,
+                                                 C.byref(spec) if spec is not None else None, n, int(reps),
+                                                 float(min_energy), int(seed), int(off), flags, C.byref(res),
+                                                 C.byref(stats)))
         return OrderedResult(self, res), stats
 
 

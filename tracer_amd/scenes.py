@@ -81,9 +81,9 @@ def dish(sigma=2e-3):
     return asm, dish_surf, rec_surf, src
 
 
-def dish_source(n, src, seed=None, ray_offset=0):
+def dish_source(n, src, seed=None, ray_offset=0, spectrum=None):
     return sources.buie_sunshape(n, src['center'], src['direction'], src['radius'], src['CSR'], flux=src['flux'],
-                                 seed=seed, ray_offset=ray_offset)
+                                 seed=seed, ray_offset=ray_offset, spectrum=spectrum)
 
 
 def flat_pair():

@@ -24,18 +24,33 @@ class LazySourceBundle(RayBundle):
     ray_offset + i.  Any column access generates the rays on the device; an engine that receives an
     untouched LazySourceBundle generates them inside its own kernel instead.
     """
-    def __init__(self, desc, n, seed, ray_offset=0, constant_columns=None):
-        RayBundle.__init__(self, **dict((k, None) for k in (constant_columns or {})))
+    def __init__(self, desc, n, seed, ray_offset=0, constant_columns=None, spectrum=None, spectral_columns=('wavelengths', 'ref_index')):
+        """spectrum: a source_spectrum.SourceSpectrum -- every ray gets a wavelength drawn on the device (the columns
+        `spectral_columns` of the materialised bundle); the bundle stays pending."""
+        if spectrum is not None and constant_columns:
+            raise ValueError("a source bundle takes a spectrum or constant columns, not both")
+        spectral_columns = tuple(spectral_columns) if spectrum is not None else ()
+        RayBundle.__init__(self, **dict((k, None) for k in tuple(constant_columns or {}) + spectral_columns))
         object.__setattr__(self, '_src_const', dict(constant_columns or {}))
         object.__setattr__(self, '_src_desc', desc)
         object.__setattr__(self, '_src_n', int(n))
         object.__setattr__(self, '_src_seed', int(seed))
         object.__setattr__(self, '_src_offset', int(ray_offset))
+        object.__setattr__(self, '_src_spectrum', spectrum)
+        object.__setattr__(self, '_src_spec_cols', spectral_columns)
         object.__setattr__(self, '_src_done', False)
 
     def is_pending(self):
-        # bundles carrying extra per-ray columns (wavelength, ref_index) are materialised before tracing
+        # bundles carrying extra per-ray constant columns are materialised before tracing (a spectrum travels with the descriptor)
         return not self._src_done and not self._src_const
+
+    def source_spectrum(self):
+        """the SourceSpectrum the rays' wavelengths are drawn from, or None"""
+        return self._src_spectrum
+
+    def spectral_columns(self):
+        """the columns the spectrum fills when the bundle is materialised ('wavelengths', 'ref_index')"""
+        return self._src_spec_cols
 
     def get_num_rays(self):
         if not self._src_done:
@@ -55,12 +70,20 @@ class LazySourceBundle(RayBundle):
         v = _cabi.pinned_empty((3, n))
         d = _cabi.pinned_empty((3, n))
         e = _cabi.pinned_empty(n)
-        rays = _cabi.make_rays(n, v[0], v[1], v[2], d[0], d[1], d[2], e)
-        _cabi.check(ctx.lib.trc_source_generate(ctx.handle, C.byref(self._src_desc), n, self._src_seed,
-                                                self._src_offset, C.byref(rays)))
+        spec = self._src_spectrum
+        wl = _cabi.pinned_empty(n) if 'wavelengths' in self._src_spec_cols else None
+        ref = _cabi.pinned_empty(n) if 'ref_index' in self._src_spec_cols else None
+        rays = _cabi.make_rays(n, v[0], v[1], v[2], d[0], d[1], d[2], e, ref_index=ref, wavelength=wl)
+        _cabi.check(ctx.lib.trc_source_generate_x(ctx.handle, C.byref(self._src_desc),
+                                                  C.byref(spec.desc()) if spec is not None else None, n, self._src_seed,
+                                                  self._src_offset, C.byref(rays)))
         self._cols['vertices'] = v
         self._cols['directions'] = d
         self._cols['energy'] = e
+        if wl is not None:
+            self._cols['wavelengths'] = wl
+        if ref is not None:
+            self._cols['ref_index'] = ref
         for k, val in self._src_const.items():
             self._cols[k] = N.ones(n) * val
 
@@ -86,10 +109,14 @@ def _fill_source(kind, center, rot_pos, rot_dir, params, energy, buie=None):
     return s
 
 
-def _new_bundle(desc, num_rays, seed, ray_offset, constant_columns=None):
+def _new_bundle(desc, num_rays, seed, ray_offset, constant_columns=None, spectrum=None, spectral_columns=('wavelengths', 'ref_index')):
     if seed is None:
         seed = rng.next_seed()
-    return LazySourceBundle(desc, int(num_rays), seed, ray_offset, constant_columns)
+    if spectrum is not None:
+        from .source_spectrum import SourceSpectrum
+        if not isinstance(spectrum, SourceSpectrum):
+            raise TypeError("spectrum must be a SourceSpectrum, got %r" % (type(spectrum).__name__,))
+    return LazySourceBundle(desc, int(num_rays), seed, ray_offset, constant_columns, spectrum, spectral_columns)
 
 
 def _tilt_cos(rays_direction, direction):
@@ -99,7 +126,7 @@ def _tilt_cos(rays_direction, direction):
 
 
 def disk_bundle(num_rays, center, direction, radius, ang_range, flux=None, radius_in=0., angular_span=[0., 2. * N.pi],
-                x_cut=None, procs=1, rays_direction=None, seed=None, ray_offset=0):
+                x_cut=None, procs=1, rays_direction=None, seed=None, ray_offset=0, spectrum=None):
     """
     Pillbox/Lambertian-cone rays leaving an annular disc.  center: 3x1 column, direction: 3-vector
     normal of the disc; energies flux*area/N*cos(tilt), or 1/N/procs without flux.  x_cut keeps the part of the disc
@@ -119,21 +146,21 @@ def disk_bundle(num_rays, center, direction, radius, ang_range, flux=None, radiu
     desc = _fill_source(_cabi.SRC_PILLBOX_DISK, center, rot, rot,
                         [radius, radius_in, angular_span[0], angular_span[1], ang_range,
                          0. if x_cut is None else 1., 0. if x_cut is None else float(x_cut)], energy)
-    return _new_bundle(desc, num_rays, seed, ray_offset)
+    return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum)
 
 
-def rect_bundle(num_rays, center, direction, x, y, ang_range, flux=None, procs=1, seed=None, ray_offset=0):
+def rect_bundle(num_rays, center, direction, x, y, ang_range, flux=None, procs=1, seed=None, ray_offset=0, spectrum=None):
     """Pillbox rays leaving an x by y rectangle normal to `direction` (sources.py:241-264)."""
     direction = N.asarray(direction)
     swap = bool((direction == N.array([0, 0, -1])).all())
     energy = x * y / num_rays * flux if flux is not None else 1. / float(num_rays) / procs
     rot = rotation_to_z(direction)
     desc = _fill_source(_cabi.SRC_PILLBOX_RECT, center, rot, rot, [x, y, ang_range, 1. if swap else 0.], energy)
-    return _new_bundle(desc, num_rays, seed, ray_offset)
+    return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum)
 
 
 def oblique_solar_rect_bundle(num_rays, center, source_direction, rays_direction, x, y, ang_range, flux=None, procs=1,
-                              wavelength=None, ref_index=None, seed=None, ray_offset=0):
+                              wavelength=None, ref_index=None, seed=None, ray_offset=0, spectrum=None):
     """Pillbox rays about `rays_direction` leaving an x by y rectangle normal to `source_direction`
     (sources.py:268-302); optional constant wavelength / ref_index columns."""
     source_direction = N.asarray(source_direction, dtype=float)
@@ -146,15 +173,22 @@ def oblique_solar_rect_bundle(num_rays, center, source_direction, rays_direction
         energy = 1. / float(num_rays) / procs
     desc = _fill_source(_cabi.SRC_PILLBOX_RECT, center, rotation_to_z(source_direction), rotation_to_z(rays_direction),
                         [x, y, ang_range, 1. if swap else 0.], energy)
-    const = {}
     if wavelength is not None:
-        const['wavelengths'] = wavelength
+        # a monochromatic spectrum: the bundle stays pending, its materialised columns are the constants
+        if spectrum is not None:
+            raise ValueError("oblique_solar_rect_bundle: give a wavelength or a spectrum, not both")
+        from .source_spectrum import SourceSpectrum
+        spectrum = SourceSpectrum.monochromatic(wavelength, 1. if ref_index is None else ref_index)
+        cols = ('wavelengths',) if ref_index is None else ('wavelengths', 'ref_index')
+        return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum, spectral_columns=cols)
     if ref_index is not None:
-        const['ref_index'] = ref_index
-    return _new_bundle(desc, num_rays, seed, ray_offset, const)
+        if spectrum is not None:
+            raise ValueError("oblique_solar_rect_bundle: the spectrum carries the index of the rays' medium (ref_index=)")
+        return _new_bundle(desc, num_rays, seed, ray_offset, {'ref_index': ref_index})
+    return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum)
 
 
-def triangular_bundle(num_rays, A, B, C, direction=None, ang_range=N.pi / 2., flux=None, procs=1, seed=None, ray_offset=0):
+def triangular_bundle(num_rays, A, B, C, direction=None, ang_range=N.pi / 2., flux=None, procs=1, seed=None, ray_offset=0, spectrum=None):
     """Pillbox rays leaving the triangle ABC (uniform point picking), about `direction` (default: the triangle
     normal AB x AC) -- sources.py:544-597."""
     A, B, C = [N.ravel(N.asarray(q, dtype=float)) for q in (A, B, C)]
@@ -176,11 +210,11 @@ def triangular_bundle(num_rays, A, B, C, direction=None, ang_range=N.pi / 2., fl
     rot_pos[:, 0] = AB
     rot_pos[:, 1] = AC
     desc = _fill_source(_cabi.SRC_PILLBOX_TRIANGLE, A, rot_pos, rotation_to_z(direction), [ang_range], energy)
-    return _new_bundle(desc, num_rays, seed, ray_offset)
+    return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum)
 
 
 def vf_cylinder_bundle(num_rays, rc, lc, center, direction, flux=None, rays_in=True, angular_span=[0., 2. * N.pi],
-                       ang_range=N.pi / 2., seed=None, ray_offset=0):
+                       ang_range=N.pi / 2., seed=None, ray_offset=0, spectrum=None):
     """
     Lambertian emitter on the wall of a cylinder of radius rc and length lc centred on `center` with its axis along
     `direction`, firing towards the axis (rays_in) or away from it (sources.py:716-769; the view-factor workload of
@@ -194,11 +228,11 @@ def vf_cylinder_bundle(num_rays, rc, lc, center, direction, flux=None, rays_in=T
     rot = rotation_to_z(direction)
     desc = _fill_source(_cabi.SRC_VF_CYLINDER, center, rot, rot,
                         [rc, lc, angular_span[0], angular_span[1], ang_range, 1. if rays_in else -1.], energy)
-    return _new_bundle(desc, num_rays, seed, ray_offset)
+    return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum)
 
 
 def vf_frustum_bundle(num_rays, r0, r1, depth, center, direction, flux=None, rays_in=True, angular_span=[0., 2. * N.pi],
-                      angular_range=N.pi / 2., seed=None, ray_offset=0):
+                      angular_range=N.pi / 2., seed=None, ray_offset=0, spectrum=None):
     """
     Lambertian emitter on the wall of a frustum: radius r0 at the base centred on `center`, r1 at `depth` along
     `direction` (sources.py:644-714).  r0 == r1 is a cylinder and must use vf_cylinder_bundle (the reference divides
@@ -215,7 +249,7 @@ def vf_frustum_bundle(num_rays, r0, r1, depth, center, direction, flux=None, ray
     rot = rotation_to_z(direction)
     desc = _fill_source(_cabi.SRC_VF_FRUSTUM, center, rot, rot,
                         [r0, r1, depth, angular_span[0], angular_span[1], angular_range, 1. if rays_in else -1.], energy)
-    return _new_bundle(desc, num_rays, seed, ray_offset)
+    return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum)
 
 
 def Lambertian_directions(num_rays, ang_range, normals=None):
@@ -266,7 +300,7 @@ def edge_rays_bundle(num_rays, center, direction, radius, ang_range, flux=None, 
     return rayb
 
 
-def trapezoid_bundle(num_rays, A, B, C, direction=None, ang_range=N.pi / 2., flux=None, procs=1, seed=None, ray_offset=0):
+def trapezoid_bundle(num_rays, A, B, C, direction=None, ang_range=N.pi / 2., flux=None, procs=1, seed=None, ray_offset=0, spectrum=None):
     """
     Isosceles trapezoid ABCD (AB the first base, C the third vertex, D by symmetry) as two triangular bundles sharing the
     rays in proportion to their areas (sources.py:599-642).
@@ -283,8 +317,9 @@ def trapezoid_bundle(num_rays, A, B, C, direction=None, ang_range=N.pi / 2., flu
     area_ABC = N.sqrt(s1 * (s1 - l1) * (s1 - l2) * (s1 - l4))      # Heron
     area_ACD = N.sqrt(s2 * (s2 - l2) * (s2 - l3) * (s2 - l5))
     n_ABC = int(area_ABC / (area_ABC + area_ACD) * num_rays)
-    first = triangular_bundle(n_ABC, A, B, C, direction, ang_range, flux, seed=seed, ray_offset=ray_offset)
-    second = triangular_bundle(num_rays - n_ABC, A, C, D, direction, ang_range, flux, seed=seed, ray_offset=ray_offset + n_ABC)
+    first = triangular_bundle(n_ABC, A, B, C, direction, ang_range, flux, seed=seed, ray_offset=ray_offset, spectrum=spectrum)
+    second = triangular_bundle(num_rays - n_ABC, A, C, D, direction, ang_range, flux, seed=seed, ray_offset=ray_offset + n_ABC,
+                               spectrum=spectrum)
     rayb = concatenate_rays([first, second])
     if flux is None:
         rayb.set_energy(N.ones(num_rays) / float(num_rays) / procs)
@@ -306,10 +341,10 @@ def regular_square_bundle(num_rays, center, direction, width):
 
 
 def solar_disk_bundle(num_rays, center, direction, radius, ang_range, flux=None, radius_in=0., angular_span=[0., 2. * N.pi],
-                      procs=1, seed=None, ray_offset=0):
+                      procs=1, seed=None, ray_offset=0, spectrum=None):
     """Older name of disk_bundle still used by scene scripts."""
     return disk_bundle(num_rays, center, direction, radius, ang_range, flux, radius_in, angular_span, None, procs,
-                       None, seed, ray_offset)
+                       None, seed, ray_offset, spectrum)
 
 
 _buie_tables = {}
@@ -359,7 +394,7 @@ def _buie_table(CSR, pre_process_CSR=True):
 
 
 def buie_sunshape(num_rays, center, direction, radius, CSR, flux=None, pre_process_CSR=True, rays_direction=None,
-                  seed=None, ray_offset=0):
+                  seed=None, ray_offset=0, spectrum=None):
     """
     Disc source with the Buie sunshape (sources.py:412-464): start points uniform on a disc of
     `radius` normal to `direction`, directions about `rays_direction` (default `direction`).
@@ -370,11 +405,11 @@ def buie_sunshape(num_rays, center, direction, radius, CSR, flux=None, pre_proce
     energy = flux * (N.pi * radius ** 2.) / num_rays * _tilt_cos(rays_direction, direction)
     desc = _fill_source(_cabi.SRC_BUIE_DISK, center, rotation_to_z(direction), rotation_to_z(rays_direction),
                         [radius], energy, buie_table(CSR, pre_process_CSR))
-    return _new_bundle(desc, num_rays, seed, ray_offset)
+    return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum)
 
 
 def rect_buie_sunshape(num_rays, center, direction, width, height, CSR, flux=None, pre_process_CSR=True,
-                       rays_direction=None, seed=None, ray_offset=0):
+                       rays_direction=None, seed=None, ray_offset=0, spectrum=None):
     """Rectangular source with the Buie sunshape (sources.py:466-515)."""
     direction = N.asarray(direction, dtype=float)
     if rays_direction is None:
@@ -382,7 +417,7 @@ def rect_buie_sunshape(num_rays, center, direction, width, height, CSR, flux=Non
     energy = flux * (width * height) / num_rays * _tilt_cos(rays_direction, direction)
     desc = _fill_source(_cabi.SRC_BUIE_RECT, center, rotation_to_z(direction), rotation_to_z(rays_direction),
                         [width, height], energy, buie_table(CSR, pre_process_CSR))
-    return _new_bundle(desc, num_rays, seed, ray_offset)
+    return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum)
 
 
 def single_ray_source(position, direction, flux=None):

@@ -353,6 +353,10 @@ class TracerEngine(object):
     def _trace_ordered(self, dev, bundle, reps, min_energy, seed, accel, tree):
         has_ref = bundle._has_column('ref_index') if not _pending(bundle) else False
         has_wl = bundle._has_column('wavelengths') if not _pending(bundle) else False
+        if _pending(bundle) and bundle.source_spectrum() is not None:
+            # (a source with a spectrum: level 0 carries the wavelengths drawn on the device, and the index the spectrum gives)
+            has_ref = 'ref_index' in bundle.spectral_columns()
+            has_wl = 'wavelengths' in bundle.spectral_columns()
         n_spec = bundle.get_spectra().shape[0] if (not _pending(bundle) and bundle.is_polychromatic()) else 0
         cplx = bool(dev.compiled.materials) or (not _pending(bundle) and bundle.has_complex_index())
         if n_spec:
