@@ -29,6 +29,7 @@
 #include <unordered_map>
 #include <deque>
 #include <utility>
+#include <memory>
 
 #include "trc_core.h"
 #include "trc_bounds.h"
@@ -66,107 +67,6 @@ static int trc_fail(int code, const char *fmt, ...) {
 
 extern "C" const char *trc_last_error(void) { return g_last_error.c_str(); }
 extern "C" int trc_abi_version(void) { return TRC_ABI_VERSION; }
-
-// ================================================================================================
-// host-side objects
-// ================================================================================================
-struct trc_ctx {
-    int device;
-    hipStream_t stream;
-    hipEvent_t ev0, ev1;
-    int n_cu;
-};
-
-struct trc_scene {
-    trc_ctx *ctx;
-    int32_t n_surf, stride, n_extra;
-    std::vector<trc_surface_desc> surfs;
-    std::vector<double> extra_h;
-    bool splits;  // some optics can emit two rays per hit
-    bool carries; // some optics read what only rays of the ordered engine carry (complex indices, spectra)
-    // device buffers
-    double *d_recs, *d_opt, *d_extra;
-    int32_t *d_sflags;
-    int32_t *d_kd_a, *d_kd_b, *d_kd_leaf, *d_kd_always;
-    double *d_kd_split;
-    int32_t kd_nodes, kd_nleaf, kd_nalways;
-    double kd_bounds[6];
-    bool has_kd;
-    trc_accel_host accel;
-    bool accel_ok, accel_kd_ok;
-    float *d_a_sbox;
-    float *d_a_obb;
-    uint64_t geom_version;     // bumped whenever the surfaces are (re)uploaded: tables derived from their poses are stale
-    uint32_t *d_a_nodes;
-    uint16_t *d_a_leaf;
-    int32_t *d_a_unbounded;
-    uint16_t *d_a_bleaf;
-    uint16_t *d_a_goff, *d_a_glist;
-    uint32_t *d_a_bg_off, *d_a_bg_occ;
-    float *d_a_bg_ent;
-    int32_t *d_a_bg_apart;
-    int32_t *d_a_gapart;
-    struct StreamEngine *stream_eng;   // slots of the streaming fast engine (trc_stream.inc), allocated on first use
-    struct OrdScratch *ord_scratch;    // scratch of the ordered engine's bounce loop, kept between calls
-    double *d_tally;
-    int64_t tally_n;
-    bool transfer_on;          // keep the transfer matrix (trc_scene_enable_transfer)
-    int64_t tr_off;
-    std::vector<FluxMapDev> fms_h;
-    std::vector<double> fm_edges_h;
-    std::vector<int32_t> fm_of_surf_h;
-    int32_t *d_fm_of_surf;
-    FluxMapDev *d_fms;
-    double *d_fm_edges;
-    unsigned long long *d_counters;
-    double *d_energy_left;     // = (double *)(d_counters + 5)
-    trc_source_desc *d_src_buf; // device copy of the source descriptor of the call in progress (kept between calls)
-    double *d_spec_buf;         // device copy of the packed source spectrum of the call in progress (FastParams.spec), and its room
-    size_t spec_cap;
-    trc_source_desc src_host;   // ... and what it holds (src_host_ok): a Monte-Carlo loop hands over the same descriptor every call
-    bool src_host_ok;
-    unsigned long long cnt_host[8];   // host copy of d_counters as trc_trace_fast left them (cnt_host_ok): the next call does not read
-    bool cnt_host_ok;                 // them back before it starts.  Every other writer of d_counters updates or drops the copy.
-    double *d_last[7];                // device side of trc_trace_fast's `last` bundle, kept between calls (seven hipMalloc / hipFree per
-    int64_t d_last_cap;               // call were a millisecond of a Monte-Carlo loop's 1e6-ray calls)
-    int64_t hit_dirty_to;             // entries [0, hit_dirty_to) of the hit buffer may have been written since it was last emptied: emptying
-                                      // 2e8 entries for the 6e6 a trace used was 0.9 GB of memset, twice per call of the public entry point
-    int64_t hit_cap;      // entries allocated: the capacity asked for + TRC_HIT_SLACK
-    int64_t hit_cap_user;
-    uint32_t hit_epoch;   // bumped whenever the cursor is reset: chunks left open by earlier launches are stale
-    uint32_t hit_chunk;   // entries a wave of the streaming engine's shading kernels reserves per atomic (set with the capacity)
-    int32_t *d_h_surf;
-    double *d_h[8];
-    double *d_hx;         // polychromatic hits: hx_cols more columns of the hit buffer (column k at d_hx + k * hx_cap): per hit the W sample
-    int hx_cols;          // wavelengths, the W samples of the spectrum that arrived and the W that left (k_s_shade_x)
-    int64_t hx_cap;
-};
-
-// what rays of the ordered engine carry beyond the nine columns: rows of one matrix `pay` (row r of ray i at pay[r * n + i]):
-// [Im of the refractive index] [Re, Im of each material at the ray's wavelength] [wavelengths of the spectrum] [spectrum]
-struct PayLayout {
-    int has_im = 0, n_mat = 0, W = 0;
-    __host__ __device__ int rows() const { return has_im + 2 * n_mat + 2 * W; }
-    __host__ __device__ int r_mat() const { return has_im; }
-    __host__ __device__ int r_wl() const { return has_im + 2 * n_mat; }
-    __host__ __device__ int r_spec() const { return has_im + 2 * n_mat + W; }
-};
-
-struct Level {
-    int64_t n_total, n_live;
-    double *x, *y, *z, *dx, *dy, *dz, *e, *ref, *wl;
-    uint64_t *rid;
-    int64_t *parent;
-    int32_t *surf;
-    double *pay;
-    char *slab;       // the one allocation the columns above are carved from
-};
-
-struct trc_result {
-    trc_ctx *ctx;
-    std::vector<Level> levels;
-    PayLayout lay;
-};
 
 // Device memory.  A freed block of up to POOL_BLOCK_MAX bytes is kept for the next request of its size class instead of going back
 // to the driver: scripts build an engine per run, and an ordered trace of 1e5 rays spent 3 of its 10 ms in hipMalloc / hipFree (a
@@ -325,6 +225,185 @@ static void dev_free(T *&p) {
     if (p) pool_free((void *)p);
     p = nullptr;
 }
+
+// Owner of one block of dev_alloc: freed when it is reset, replaced or goes out of scope.  Kernel parameter structs take get().
+template <class T>
+class DevBuf {
+    T *p_ = nullptr;
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    int alloc(size_t n) { reset(); return dev_alloc(&p_, n); }
+    void reset() { dev_free(p_); }
+    T *get() const { return p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+};
+
+// a new block of n elements for `b`, and the n elements of host `src` copied into it (nothing is copied for n == 0 or no src);
+// a failed copy reports `fail` when given
+template <class T>
+static int dev_upload(DevBuf<T> &b, const T *src, size_t n, const char *fail = nullptr) {
+    TRC_TRY(b.alloc(n));
+    if (n == 0 || !src) return TRC_OK;
+    if (fail) {
+        if (hipMemcpy(b.get(), src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "%s", fail);
+    } else HIP_TRY(hipMemcpy(b.get(), src, n * sizeof(T), hipMemcpyHostToDevice));
+    return TRC_OK;
+}
+
+// n elements of device `src` to host `dst`
+template <class T>
+static int dev_download(T *dst, const T *src, size_t n) {
+    if (hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
+    return TRC_OK;
+}
+
+// ================================================================================================
+// host-side objects
+// ================================================================================================
+struct trc_ctx {
+    int device;
+    hipStream_t stream;
+    hipEvent_t ev0, ev1;
+    int n_cu;
+};
+
+struct trc_scene {
+    trc_ctx *ctx;
+    int32_t n_surf, stride, n_extra;
+    std::vector<trc_surface_desc> surfs;
+    std::vector<double> extra_h;
+    bool splits;  // some optics can emit two rays per hit
+    bool carries; // some optics read what only rays of the ordered engine carry (complex indices, spectra)
+    // device buffers
+    DevBuf<double> d_recs, d_opt, d_extra;
+    DevBuf<int32_t> d_sflags;
+    DevBuf<int32_t> d_kd_a, d_kd_b, d_kd_leaf, d_kd_always;
+    DevBuf<double> d_kd_split;
+    int32_t kd_nodes, kd_nleaf, kd_nalways;
+    double kd_bounds[6];
+    bool has_kd;
+    trc_accel_host accel;
+    bool accel_ok, accel_kd_ok;
+    DevBuf<float> d_a_sbox;
+    DevBuf<float> d_a_obb;
+    uint64_t geom_version;     // bumped whenever the surfaces are (re)uploaded: tables derived from their poses are stale
+    DevBuf<uint32_t> d_a_nodes;
+    DevBuf<uint16_t> d_a_leaf;
+    DevBuf<int32_t> d_a_unbounded;
+    DevBuf<uint16_t> d_a_bleaf;
+    DevBuf<uint16_t> d_a_goff, d_a_glist;
+    DevBuf<uint32_t> d_a_bg_off, d_a_bg_occ;
+    DevBuf<float> d_a_bg_ent;
+    DevBuf<int32_t> d_a_bg_apart;
+    DevBuf<int32_t> d_a_gapart;
+    struct StreamEngine *stream_eng;   // slots of the streaming fast engine (trc_stream.inc), allocated on first use
+    std::unique_ptr<struct OrdScratch> ord_scratch;    // scratch of the ordered engine's bounce loop, kept between calls
+    DevBuf<double> d_tally;
+    int64_t tally_n;
+    bool transfer_on;          // keep the transfer matrix (trc_scene_enable_transfer)
+    int64_t tr_off;
+    std::vector<FluxMapDev> fms_h;
+    std::vector<double> fm_edges_h;
+    std::vector<int32_t> fm_of_surf_h;
+    DevBuf<int32_t> d_fm_of_surf;
+    DevBuf<FluxMapDev> d_fms;
+    DevBuf<double> d_fm_edges;
+    DevBuf<unsigned long long> d_counters;
+    double *d_energy_left;     // = (double *)(d_counters + 5)
+    DevBuf<trc_source_desc> d_src_buf; // device copy of the source descriptor of the call in progress (kept between calls)
+    DevBuf<double> d_spec_buf;         // device copy of the packed source spectrum of the call in progress (FastParams.spec), and its room
+    size_t spec_cap;
+    trc_source_desc src_host;   // ... and what it holds (src_host_ok): a Monte-Carlo loop hands over the same descriptor every call
+    bool src_host_ok;
+    unsigned long long cnt_host[8];   // host copy of d_counters as trc_trace_fast left them (cnt_host_ok): the next call does not read
+    bool cnt_host_ok;                 // them back before it starts.  Every other writer of d_counters updates or drops the copy.
+    DevBuf<double> d_last[7];         // device side of trc_trace_fast's `last` bundle, kept between calls (seven hipMalloc / hipFree per
+    int64_t d_last_cap;               // call were a millisecond of a Monte-Carlo loop's 1e6-ray calls)
+    int64_t hit_dirty_to;             // entries [0, hit_dirty_to) of the hit buffer may have been written since it was last emptied: emptying
+                                      // 2e8 entries for the 6e6 a trace used was 0.9 GB of memset, twice per call of the public entry point
+    int64_t hit_cap;      // entries allocated: the capacity asked for + TRC_HIT_SLACK
+    int64_t hit_cap_user;
+    uint32_t hit_epoch;   // bumped whenever the cursor is reset: chunks left open by earlier launches are stale
+    uint32_t hit_chunk;   // entries a wave of the streaming engine's shading kernels reserves per atomic (set with the capacity)
+    DevBuf<int32_t> d_h_surf;
+    DevBuf<double> d_h[8];
+    DevBuf<double> d_hx;  // polychromatic hits: hx_cols more columns of the hit buffer (column k at d_hx + k * hx_cap): per hit the W sample
+    int hx_cols;          // wavelengths, the W samples of the spectrum that arrived and the W that left (k_s_shade_x)
+    int64_t hx_cap;
+};
+
+// what rays of the ordered engine carry beyond the nine columns: rows of one matrix `pay` (row r of ray i at pay[r * n + i]):
+// [Im of the refractive index] [Re, Im of each material at the ray's wavelength] [wavelengths of the spectrum] [spectrum]
+struct PayLayout {
+    int has_im = 0, n_mat = 0, W = 0;
+    __host__ __device__ int rows() const { return has_im + 2 * n_mat + 2 * W; }
+    __host__ __device__ int r_mat() const { return has_im; }
+    __host__ __device__ int r_wl() const { return has_im + 2 * n_mat; }
+    __host__ __device__ int r_spec() const { return has_im + 2 * n_mat + W; }
+};
+
+struct Level {
+    int64_t n_total, n_live;
+    double *x, *y, *z, *dx, *dy, *dz, *e, *ref, *wl;
+    uint64_t *rid;
+    int64_t *parent;
+    int32_t *surf;
+    double *pay;
+    DevBuf<char> slab;    // the one allocation the columns above are carved from
+};
+
+// Scratch of the bounce loop: allocated for the first (usually the largest) bounce and kept; a bounce that needs more -- refractive
+// surfaces can double a level -- gets a new set.
+#define ORD_SCRATCH_KEEP ((size_t)1 << 26)
+struct OrdScratch {
+    DevBuf<double> o[9];
+    DevBuf<uint64_t> orid;
+    DevBuf<double> opay;
+    DevBuf<uint32_t> key, ckey, cslot, skey, sslot;
+    DevBuf<unsigned> blk_cnt, blk_cul;
+    DevBuf<unsigned long long> blk_off, totals;
+    DevBuf<char> sort_tmp;
+    size_t cap_slots = 0, sort_bytes = 0;
+    int cap_pay = 0;
+    int ensure(size_t slots, int n_pay) {
+        if (slots <= cap_slots && n_pay <= cap_pay) return TRC_OK;
+        if (slots < cap_slots) slots = cap_slots;
+        *this = OrdScratch();
+        cap_pay = n_pay;
+        for (int i = 0; i < 9; ++i) TRC_TRY(o[i].alloc(slots));
+        TRC_TRY(orid.alloc(slots));
+        if (n_pay > 0) TRC_TRY(opay.alloc(slots * (size_t)n_pay));
+        TRC_TRY(key.alloc(slots));
+        TRC_TRY(ckey.alloc(slots)); TRC_TRY(cslot.alloc(slots));      // the occupied slots: at most all of them
+        TRC_TRY(skey.alloc(slots)); TRC_TRY(sslot.alloc(slots));
+        const size_t nblk = (slots + 255) / 256;
+        TRC_TRY(blk_cnt.alloc(nblk)); TRC_TRY(blk_cul.alloc(nblk)); TRC_TRY(blk_off.alloc(nblk));
+        TRC_TRY(totals.alloc(2));
+        cap_slots = slots;
+        return TRC_OK;
+    }
+    int ensure_sort(size_t bytes) {
+        if (bytes <= sort_bytes && sort_tmp) return TRC_OK;
+        sort_bytes = 0;
+        TRC_TRY(sort_tmp.alloc(bytes));
+        sort_bytes = bytes;
+        return TRC_OK;
+    }
+};
+
+struct trc_result {
+    trc_ctx *ctx;
+    std::vector<Level> levels;
+    PayLayout lay;
+};
 
 // ------------------------------------------------------------------------------------------------
 // Wave-cooperative fast path (k_trace_coop).  Same candidates, same exact float64 tests and the same winner as
@@ -1420,51 +1499,35 @@ static int scene_upload_surfaces(trc_scene *sc) {
         if (surface_ends_every_ray(sc->surfs[i])) flags[i] |= TRC_SURF_TERMINAL;
         flags[i] |= trc_shade_class_of(sc->surfs[i]) << TRC_SURF_CLS_SHIFT;      // which shading kernel of the streaming engine serves the surface
     }
-    HIP_TRY(hipMemcpy(sc->d_recs, recs.data(), recs.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(sc->d_opt, opt.data(), opt.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(sc->d_sflags, flags.data(), flags.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(sc->d_recs.get(), recs.data(), recs.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(sc->d_opt.get(), opt.data(), opt.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(sc->d_sflags.get(), flags.data(), flags.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     // conservative single-precision boxes of the bounded surfaces (fast engine)
     trc_accel_build_surfaces(sc->surfs.data(), sc->n_surf, sc->accel);
     sc->geom_version += 1;
-    dev_free(sc->d_a_sbox); dev_free(sc->d_a_obb); dev_free(sc->d_a_unbounded); dev_free(sc->d_a_bleaf);
-    TRC_TRY(dev_alloc(&sc->d_a_obb, sc->accel.obb.size()));
-    HIP_TRY(hipMemcpy(sc->d_a_obb, sc->accel.obb.data(), sc->accel.obb.size() * sizeof(float), hipMemcpyHostToDevice));
-    TRC_TRY(dev_alloc(&sc->d_a_bleaf, sc->accel.brute_leaf.size()));
-    if (!sc->accel.brute_leaf.empty())
-        HIP_TRY(hipMemcpy(sc->d_a_bleaf, sc->accel.brute_leaf.data(), sc->accel.brute_leaf.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    TRC_TRY(dev_alloc(&sc->d_a_sbox, sc->accel.sbox.size()));
-    TRC_TRY(dev_alloc(&sc->d_a_unbounded, sc->accel.unbounded.size()));
-    HIP_TRY(hipMemcpy(sc->d_a_sbox, sc->accel.sbox.data(), sc->accel.sbox.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (!sc->accel.unbounded.empty())
-        HIP_TRY(hipMemcpy(sc->d_a_unbounded, sc->accel.unbounded.data(), sc->accel.unbounded.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    TRC_TRY(dev_upload(sc->d_a_obb, sc->accel.obb.data(), sc->accel.obb.size()));
+    TRC_TRY(dev_upload(sc->d_a_bleaf, sc->accel.brute_leaf.data(), sc->accel.brute_leaf.size()));
+    TRC_TRY(dev_upload(sc->d_a_sbox, sc->accel.sbox.data(), sc->accel.sbox.size()));
+    TRC_TRY(dev_upload(sc->d_a_unbounded, sc->accel.unbounded.data(), sc->accel.unbounded.size()));
     trc_accel_build_grid(sc->accel, sc->n_surf);
     { const char *ev = getenv("TRC_GRID_FORCE32"); if (ev && atoi(ev)) sc->accel.grid_ok = false; }      // (measurements: the large grid for a scene the LDS-sized one holds)
-    dev_free(sc->d_a_goff); dev_free(sc->d_a_glist); dev_free(sc->d_a_gapart);
-    sc->d_a_goff = nullptr; sc->d_a_glist = nullptr; sc->d_a_gapart = nullptr;
+    sc->d_a_goff.reset(); sc->d_a_glist.reset(); sc->d_a_gapart.reset();
     if (sc->accel.grid_ok) {
-        TRC_TRY(dev_alloc(&sc->d_a_gapart, sc->accel.grid_apart.size()));
-        if (!sc->accel.grid_apart.empty())
-            HIP_TRY(hipMemcpy(sc->d_a_gapart, sc->accel.grid_apart.data(), sc->accel.grid_apart.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        TRC_TRY(dev_alloc(&sc->d_a_goff, sc->accel.grid_off.size()));
-        TRC_TRY(dev_alloc(&sc->d_a_glist, sc->accel.grid_list.size()));
-        HIP_TRY(hipMemcpy(sc->d_a_goff, sc->accel.grid_off.data(), sc->accel.grid_off.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(sc->d_a_glist, sc->accel.grid_list.data(), sc->accel.grid_list.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        TRC_TRY(dev_upload(sc->d_a_gapart, sc->accel.grid_apart.data(), sc->accel.grid_apart.size()));
+        TRC_TRY(dev_upload(sc->d_a_goff, sc->accel.grid_off.data(), sc->accel.grid_off.size()));
+        TRC_TRY(dev_upload(sc->d_a_glist, sc->accel.grid_list.data(), sc->accel.grid_list.size()));
     }
-    dev_free(sc->d_a_bg_off); dev_free(sc->d_a_bg_occ); dev_free(sc->d_a_bg_ent); dev_free(sc->d_a_bg_apart);
-    sc->d_a_bg_off = nullptr; sc->d_a_bg_occ = nullptr; sc->d_a_bg_ent = nullptr; sc->d_a_bg_apart = nullptr;
+    sc->d_a_bg_off.reset(); sc->d_a_bg_occ.reset(); sc->d_a_bg_ent.reset(); sc->d_a_bg_apart.reset();
     if (!sc->accel.grid_ok) {      // a scene the LDS-sized grid cannot hold: the 32-bit grid in global memory
         trc_accel_build_grid32(sc->surfs.data(), sc->n_surf, sc->accel);
         if (sc->accel.big_ok) {
-            TRC_TRY(dev_alloc(&sc->d_a_bg_off, sc->accel.big_off.size()));
-            TRC_TRY(dev_alloc(&sc->d_a_bg_ent, sc->accel.big_ent.size()));
-            TRC_TRY(dev_alloc(&sc->d_a_bg_occ, sc->accel.big_occ.size()));
-            HIP_TRY(hipMemcpy(sc->d_a_bg_off, sc->accel.big_off.data(), sc->accel.big_off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(sc->d_a_bg_ent, sc->accel.big_ent.data(), sc->accel.big_ent.size() * sizeof(float), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(sc->d_a_bg_occ, sc->accel.big_occ.data(), sc->accel.big_occ.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            TRC_TRY(dev_upload(sc->d_a_bg_off, sc->accel.big_off.data(), sc->accel.big_off.size()));
+            TRC_TRY(dev_upload(sc->d_a_bg_ent, sc->accel.big_ent.data(), sc->accel.big_ent.size()));
+            TRC_TRY(dev_upload(sc->d_a_bg_occ, sc->accel.big_occ.data(), sc->accel.big_occ.size()));
             std::vector<float>().swap(sc->accel.big_ent);       // (the host keeps the list itself, not its 48-byte entries)
-            TRC_TRY(dev_alloc(&sc->d_a_bg_apart, sc->accel.big_apart.size() + 1));
+            TRC_TRY(sc->d_a_bg_apart.alloc(sc->accel.big_apart.size() + 1));
             if (!sc->accel.big_apart.empty())
-                HIP_TRY(hipMemcpy(sc->d_a_bg_apart, sc->accel.big_apart.data(), sc->accel.big_apart.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy(sc->d_a_bg_apart.get(), sc->accel.big_apart.data(), sc->accel.big_apart.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         }
     }
     sc->accel_ok = true;
@@ -1473,14 +1536,13 @@ static int scene_upload_surfaces(trc_scene *sc) {
 }
 
 static int scene_alloc_tally(trc_scene *sc) {
-    dev_free(sc->d_tally);
     int64_t n = 3 * (int64_t)sc->n_surf + 2;
     for (auto &m : sc->fms_h) { m.bins = n; n += (int64_t)m.nu * m.nv; }
     sc->tr_off = -1;
     if (sc->transfer_on) { sc->tr_off = n; n += ((int64_t)sc->n_surf + 1) * sc->n_surf; }
     sc->tally_n = n;
-    TRC_TRY(dev_alloc(&sc->d_tally, (size_t)n));
-    HIP_TRY(hipMemset(sc->d_tally, 0, (size_t)n * sizeof(double)));
+    TRC_TRY(sc->d_tally.alloc((size_t)n));
+    HIP_TRY(hipMemset(sc->d_tally.get(), 0, (size_t)n * sizeof(double)));
     return TRC_OK;
 }
 
@@ -1500,13 +1562,12 @@ extern "C" int trc_scene_create(trc_ctx *ctx, int32_t n_surf, const trc_surface_
         if (surfs[i].optics_kind == TRC_OPT_REFRACTIVE_MATERIAL && surfs[i].opt[0] == 0.0) splits = true;
         if (surfs[i].optics_kind == TRC_OPT_REFRACTIVE_MATERIAL || surfs[i].optics_kind == TRC_OPT_LAMBERTIAN_POLYCHROMATIC) carries = true;
     }
-    trc_scene *sc = new (std::nothrow) trc_scene();
+    std::unique_ptr<trc_scene> sc(new (std::nothrow) trc_scene());
     if (!sc) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
     sc->ctx = ctx;
     sc->src_host_ok = false;
     sc->cnt_host_ok = false;
     sc->hit_dirty_to = 0;
-    for (int i = 0; i < 7; ++i) sc->d_last[i] = nullptr;
     sc->d_last_cap = 0;
     memset(sc->cnt_host, 0, sizeof(sc->cnt_host));
     sc->n_surf = n_surf;
@@ -1520,43 +1581,29 @@ extern "C" int trc_scene_create(trc_ctx *ctx, int32_t n_surf, const trc_surface_
     sc->has_kd = false;
     sc->hit_cap = 0;
     sc->fm_of_surf_h.assign(n_surf, -1);
-    int st = TRC_OK;
-    do {
-        if ((st = dev_alloc(&sc->d_recs, (size_t)n_surf * sc->stride))) break;
-        if ((st = dev_alloc(&sc->d_opt, (size_t)n_surf * 8))) break;
-        if ((st = dev_alloc(&sc->d_sflags, (size_t)n_surf))) break;
-        if ((st = dev_alloc(&sc->d_extra, (size_t)n_extra))) break;
-        if ((st = dev_alloc(&sc->d_fm_of_surf, (size_t)n_surf))) break;
-        if ((st = dev_alloc(&sc->d_counters, 8))) break;
-        sc->d_energy_left = (double *)(sc->d_counters + 5);      // same 64-byte block as the counters: one read-back gets both
-        if ((st = scene_upload_surfaces(sc))) break;
-        if (n_extra > 0 && hipMemcpy(sc->d_extra, sc->extra_h.data(), (size_t)n_extra * sizeof(double),
-                                     hipMemcpyHostToDevice) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "extra upload failed"); break; }
-        if (hipMemcpy(sc->d_fm_of_surf, sc->fm_of_surf_h.data(), (size_t)n_surf * sizeof(int32_t),
-                      hipMemcpyHostToDevice) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "upload failed"); break; }
-        if (hipMemset(sc->d_counters, 0, 8 * sizeof(unsigned long long)) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memset failed"); break; }
-        if ((st = scene_alloc_tally(sc))) break;
-    } while (0);
-    if (st != TRC_OK) { trc_scene_destroy(sc); return st; }
-    *out = sc;
+    TRC_TRY(sc->d_recs.alloc((size_t)n_surf * sc->stride));
+    TRC_TRY(sc->d_opt.alloc((size_t)n_surf * 8));
+    TRC_TRY(sc->d_sflags.alloc((size_t)n_surf));
+    TRC_TRY(sc->d_extra.alloc((size_t)n_extra));
+    TRC_TRY(sc->d_fm_of_surf.alloc((size_t)n_surf));
+    TRC_TRY(sc->d_counters.alloc(8));
+    sc->d_energy_left = (double *)(sc->d_counters.get() + 5);      // same 64-byte block as the counters: one read-back gets both
+    TRC_TRY(scene_upload_surfaces(sc.get()));
+    if (n_extra > 0 && hipMemcpy(sc->d_extra.get(), sc->extra_h.data(), (size_t)n_extra * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return trc_fail(TRC_ERR_DEVICE, "extra upload failed");
+    if (hipMemcpy(sc->d_fm_of_surf.get(), sc->fm_of_surf_h.data(), (size_t)n_surf * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
+        return trc_fail(TRC_ERR_DEVICE, "upload failed");
+    if (hipMemset(sc->d_counters.get(), 0, 8 * sizeof(unsigned long long)) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memset failed");
+    TRC_TRY(scene_alloc_tally(sc.get()));
+    *out = sc.release();
     return TRC_OK;
 }
 
-static void scene_free_ord_scratch(trc_scene *sc);
 extern "C" int trc_scene_destroy(trc_scene *sc) {
     if (!sc) return TRC_OK;
     (void)hipSetDevice(sc->ctx->device);
     (void)hipStreamSynchronize(sc->ctx->stream);
     scene_free_stream_ws(sc);
-    scene_free_ord_scratch(sc);
-    dev_free(sc->d_recs); dev_free(sc->d_opt); dev_free(sc->d_extra); dev_free(sc->d_sflags);
-    dev_free(sc->d_kd_a); dev_free(sc->d_kd_b); dev_free(sc->d_kd_leaf); dev_free(sc->d_kd_always);
-    dev_free(sc->d_a_sbox); dev_free(sc->d_a_obb); dev_free(sc->d_a_nodes); dev_free(sc->d_a_leaf); dev_free(sc->d_a_unbounded); dev_free(sc->d_a_bleaf);
-    dev_free(sc->d_a_goff); dev_free(sc->d_a_glist); dev_free(sc->d_a_gapart); dev_free(sc->d_a_bg_off); dev_free(sc->d_a_bg_occ); dev_free(sc->d_a_bg_ent); dev_free(sc->d_a_bg_apart);
-    dev_free(sc->d_kd_split); dev_free(sc->d_tally); dev_free(sc->d_fm_of_surf); dev_free(sc->d_fms);
-    dev_free(sc->d_fm_edges); dev_free(sc->d_counters); dev_free(sc->d_src_buf); dev_free(sc->d_spec_buf); dev_free(sc->d_h_surf); dev_free(sc->d_hx);
-    for (int i = 0; i < 8; ++i) dev_free(sc->d_h[i]);
-    for (int i = 0; i < 7; ++i) dev_free(sc->d_last[i]);
     delete sc;
     return TRC_OK;
 }
@@ -1574,7 +1621,7 @@ extern "C" int trc_scene_set_kdtree(trc_scene *sc, const trc_kdtree_desc *kd) {
     if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
     HIP_TRY(hipSetDevice(sc->ctx->device));
     HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    dev_free(sc->d_kd_a); dev_free(sc->d_kd_b); dev_free(sc->d_kd_leaf); dev_free(sc->d_kd_always); dev_free(sc->d_kd_split);
+    sc->d_kd_a.reset(); sc->d_kd_b.reset(); sc->d_kd_leaf.reset(); sc->d_kd_always.reset(); sc->d_kd_split.reset();
     sc->has_kd = false;
     sc->accel_kd_ok = false;
     if (!kd) return TRC_OK;
@@ -1607,27 +1654,19 @@ extern "C" int trc_scene_set_kdtree(trc_scene *sc, const trc_kdtree_desc *kd) {
     if (max_depth > TRC_KD_STACK) return trc_fail(TRC_ERR_UNSUPPORTED, "Kd-tree depth %d exceeds the traversal stack (%d)", max_depth, TRC_KD_STACK);
     for (int k = 0; k < kd->n_always; ++k)
         if (kd->always_relevant[k] < 0 || kd->always_relevant[k] >= sc->n_surf) return trc_fail(TRC_ERR_INVALID, "always_relevant out of range");
-    TRC_TRY(dev_alloc(&sc->d_kd_a, (size_t)kd->n_nodes));
-    TRC_TRY(dev_alloc(&sc->d_kd_b, (size_t)kd->n_nodes));
-    TRC_TRY(dev_alloc(&sc->d_kd_split, (size_t)kd->n_nodes));
-    TRC_TRY(dev_alloc(&sc->d_kd_leaf, (size_t)kd->n_leaf_surfs));
-    TRC_TRY(dev_alloc(&sc->d_kd_always, (size_t)kd->n_always));
-    HIP_TRY(hipMemcpy(sc->d_kd_a, a.data(), a.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(sc->d_kd_b, b.data(), b.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(sc->d_kd_split, kd->split, (size_t)kd->n_nodes * 8, hipMemcpyHostToDevice));
-    if (kd->n_leaf_surfs) HIP_TRY(hipMemcpy(sc->d_kd_leaf, kd->leaf_surfs, (size_t)kd->n_leaf_surfs * 4, hipMemcpyHostToDevice));
-    if (kd->n_always) HIP_TRY(hipMemcpy(sc->d_kd_always, kd->always_relevant, (size_t)kd->n_always * 4, hipMemcpyHostToDevice));
+    TRC_TRY(dev_upload(sc->d_kd_a, a.data(), a.size()));
+    TRC_TRY(dev_upload(sc->d_kd_b, b.data(), b.size()));
+    TRC_TRY(dev_upload(sc->d_kd_split, kd->split, (size_t)kd->n_nodes));
+    TRC_TRY(dev_upload(sc->d_kd_leaf, kd->leaf_surfs, (size_t)kd->n_leaf_surfs));
+    TRC_TRY(dev_upload(sc->d_kd_always, kd->always_relevant, (size_t)kd->n_always));
     sc->kd_nodes = kd->n_nodes; sc->kd_nleaf = kd->n_leaf_surfs; sc->kd_nalways = kd->n_always;
     memcpy(sc->kd_bounds, kd->bounds, sizeof(sc->kd_bounds));
     sc->has_kd = true;
-    dev_free(sc->d_a_nodes); dev_free(sc->d_a_leaf);
+    sc->d_a_nodes.reset(); sc->d_a_leaf.reset();
     sc->accel_kd_ok = false;
     if (sc->accel_ok && trc_accel_build_kd(kd, sc->accel)) {
-        TRC_TRY(dev_alloc(&sc->d_a_nodes, sc->accel.nodes.size()));
-        TRC_TRY(dev_alloc(&sc->d_a_leaf, sc->accel.leaf_surfs.size()));
-        HIP_TRY(hipMemcpy(sc->d_a_nodes, sc->accel.nodes.data(), sc->accel.nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        if (!sc->accel.leaf_surfs.empty())
-            HIP_TRY(hipMemcpy(sc->d_a_leaf, sc->accel.leaf_surfs.data(), sc->accel.leaf_surfs.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        TRC_TRY(dev_upload(sc->d_a_nodes, sc->accel.nodes.data(), sc->accel.nodes.size()));
+        TRC_TRY(dev_upload(sc->d_a_leaf, sc->accel.leaf_surfs.data(), sc->accel.leaf_surfs.size()));
         sc->accel_kd_ok = true;
     }
     return TRC_OK;
@@ -1653,12 +1692,9 @@ extern "C" int trc_scene_set_fluxmap(trc_scene *sc, int32_t surf, int32_t nu, in
     sc->fm_of_surf_h[surf] = (int32_t)sc->fms_h.size();
     sc->fms_h.push_back(m);
     TRC_TRY(scene_alloc_tally(sc));  // resets the tallies
-    dev_free(sc->d_fms); dev_free(sc->d_fm_edges);
-    TRC_TRY(dev_alloc(&sc->d_fms, sc->fms_h.size()));
-    TRC_TRY(dev_alloc(&sc->d_fm_edges, sc->fm_edges_h.size()));
-    HIP_TRY(hipMemcpy(sc->d_fms, sc->fms_h.data(), sc->fms_h.size() * sizeof(FluxMapDev), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(sc->d_fm_edges, sc->fm_edges_h.data(), sc->fm_edges_h.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(sc->d_fm_of_surf, sc->fm_of_surf_h.data(), (size_t)sc->n_surf * sizeof(int32_t), hipMemcpyHostToDevice));
+    TRC_TRY(dev_upload(sc->d_fms, sc->fms_h.data(), sc->fms_h.size()));
+    TRC_TRY(dev_upload(sc->d_fm_edges, sc->fm_edges_h.data(), sc->fm_edges_h.size()));
+    HIP_TRY(hipMemcpy(sc->d_fm_of_surf.get(), sc->fm_of_surf_h.data(), (size_t)sc->n_surf * sizeof(int32_t), hipMemcpyHostToDevice));
     return TRC_OK;
 }
 
@@ -1669,18 +1705,18 @@ extern "C" int trc_scene_set_hit_capacity(trc_scene *sc, int64_t capacity) {
     HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
     // the same capacity again (an engine sizes the buffer before every trace): the buffer is kept and emptied -- freeing and
     // allocating 15 GB per call was a tenth of a second at 1e8 rays
-    if (capacity > 0 && capacity == sc->hit_cap_user && sc->d_h_surf) {
-        HIP_TRY(hipMemset(sc->d_counters, 0, 2 * sizeof(unsigned long long)));      // cursor and dropped count start over
+    if (capacity > 0 && capacity == sc->hit_cap_user && sc->d_h_surf.get()) {
+        HIP_TRY(hipMemset(sc->d_counters.get(), 0, 2 * sizeof(unsigned long long)));      // cursor and dropped count start over
         sc->cnt_host[0] = sc->cnt_host[1] = 0ull;
         return scene_reset_hit_buffer(sc);
     }
-    dev_free(sc->d_h_surf);
-    for (int i = 0; i < 8; ++i) dev_free(sc->d_h[i]);
-    dev_free(sc->d_hx); sc->hx_cols = 0; sc->hx_cap = 0;      // (made again by the next call that brings spectra)
+    sc->d_h_surf.reset();
+    for (auto &col : sc->d_h) col.reset();
+    sc->d_hx.reset(); sc->hx_cols = 0; sc->hx_cap = 0;      // (made again by the next call that brings spectra)
     sc->hit_cap = 0;
     sc->hit_cap_user = 0;
     sc->hit_epoch += 1;
-    HIP_TRY(hipMemset(sc->d_counters, 0, 2 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(sc->d_counters.get(), 0, 2 * sizeof(unsigned long long)));
     sc->cnt_host[0] = sc->cnt_host[1] = 0ull;
     if (capacity == 0) return TRC_OK;
     // The streaming engine appends in chunks that stay open between launches: room for what they can leave unused.  The chunk
@@ -1692,9 +1728,9 @@ extern "C" int trc_scene_set_hit_capacity(trc_scene *sc, int64_t capacity) {
     sc->hit_chunk = (uint32_t)chunk;
     const int64_t slack = TRC_HIT_HOLDERS * chunk + 64;
     const int64_t alloc = capacity + slack;
-    TRC_TRY(dev_alloc(&sc->d_h_surf, (size_t)alloc));
-    for (int i = 0; i < 8; ++i) TRC_TRY(dev_alloc(&sc->d_h[i], (size_t)alloc));
-    HIP_TRY(hipMemset(sc->d_h_surf, 0xFF, (size_t)alloc * sizeof(int32_t)));     // surface -1: entry not written
+    TRC_TRY(sc->d_h_surf.alloc((size_t)alloc));
+    for (auto &col : sc->d_h) TRC_TRY(col.alloc((size_t)alloc));
+    HIP_TRY(hipMemset(sc->d_h_surf.get(), 0xFF, (size_t)alloc * sizeof(int32_t)));     // surface -1: entry not written
     sc->hit_dirty_to = 0;
     sc->hit_cap = alloc;
     sc->hit_cap_user = capacity;
@@ -1706,30 +1742,28 @@ extern "C" int trc_scene_set_hit_capacity(trc_scene *sc, int64_t capacity) {
 // read at last.  Grows by half at least; the chunk size stays (chunks left open by earlier launches go on being filled).
 extern "C" int trc_scene_reserve_hits(trc_scene *sc, int64_t capacity) {
     if (!sc || capacity < 0) return trc_fail(TRC_ERR_INVALID, "bad arguments");
-    if (!sc->d_h_surf || sc->hit_cap_user == 0) return trc_scene_set_hit_capacity(sc, capacity);
+    if (!sc->d_h_surf.get() || sc->hit_cap_user == 0) return trc_scene_set_hit_capacity(sc, capacity);
     if (capacity <= sc->hit_cap_user) return TRC_OK;
     HIP_TRY(hipSetDevice(sc->ctx->device));
     HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
     if (capacity < sc->hit_cap_user + sc->hit_cap_user / 2) capacity = sc->hit_cap_user + sc->hit_cap_user / 2;
     unsigned long long c[2];
-    HIP_TRY(hipMemcpy(c, sc->d_counters, sizeof(c), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c, sc->d_counters.get(), sizeof(c), hipMemcpyDeviceToHost));
     const int64_t used = (int64_t)c[0] < sc->hit_cap ? (int64_t)c[0] : sc->hit_cap;
     const int64_t alloc = capacity + (sc->hit_cap - sc->hit_cap_user);
-    int32_t *n_surf = nullptr;
-    double *n_col[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int st = dev_alloc(&n_surf, (size_t)alloc);
-    for (int i = 0; i < 8 && st == TRC_OK; ++i) st = dev_alloc(&n_col[i], (size_t)alloc);
-    if (st != TRC_OK) { dev_free(n_surf); for (int i = 0; i < 8; ++i) dev_free(n_col[i]); return st; }
-    HIP_TRY(hipMemset(n_surf, 0xFF, (size_t)alloc * sizeof(int32_t)));
+    // the new columns join the scene once they hold its hits
+    DevBuf<int32_t> n_surf;
+    DevBuf<double> n_col[8];
+    TRC_TRY(n_surf.alloc((size_t)alloc));
+    for (auto &col : n_col) TRC_TRY(col.alloc((size_t)alloc));
+    HIP_TRY(hipMemset(n_surf.get(), 0xFF, (size_t)alloc * sizeof(int32_t)));
     if (used > 0) {
-        HIP_TRY(hipMemcpy(n_surf, sc->d_h_surf, (size_t)used * sizeof(int32_t), hipMemcpyDeviceToDevice));
-        for (int i = 0; i < 8; ++i) HIP_TRY(hipMemcpy(n_col[i], sc->d_h[i], (size_t)used * sizeof(double), hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(n_surf.get(), sc->d_h_surf.get(), (size_t)used * sizeof(int32_t), hipMemcpyDeviceToDevice));
+        for (int i = 0; i < 8; ++i) HIP_TRY(hipMemcpy(n_col[i].get(), sc->d_h[i].get(), (size_t)used * sizeof(double), hipMemcpyDeviceToDevice));
     }
-    dev_free(sc->d_h_surf);
-    for (int i = 0; i < 8; ++i) dev_free(sc->d_h[i]);
-    dev_free(sc->d_hx); sc->hx_cols = 0; sc->hx_cap = 0;      // (a buffer that grows keeps its hits, not their spectra: the host reads those before)
-    sc->d_h_surf = n_surf;
-    for (int i = 0; i < 8; ++i) sc->d_h[i] = n_col[i];
+    sc->d_h_surf = std::move(n_surf);
+    for (int i = 0; i < 8; ++i) sc->d_h[i] = std::move(n_col[i]);
+    sc->d_hx.reset(); sc->hx_cols = 0; sc->hx_cap = 0;      // (a buffer that grows keeps its hits, not their spectra: the host reads those before)
     sc->hit_dirty_to = used;
     sc->hit_cap = alloc;
     sc->hit_cap_user = capacity;
@@ -1745,7 +1779,7 @@ extern "C" int trc_scene_hits_reserved(trc_scene *sc, int64_t *reserved, int64_t
             HIP_TRY(hipSetDevice(sc->ctx->device));
             HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
             unsigned long long c = 0;
-            HIP_TRY(hipMemcpy(&c, sc->d_counters, sizeof(c), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(&c, sc->d_counters.get(), sizeof(c), hipMemcpyDeviceToHost));
             *reserved = (int64_t)c;
         }
     }
@@ -1820,7 +1854,7 @@ extern "C" int trc_host_free(void *p) {
 static int scene_reset_hit_buffer(trc_scene *sc) {
     sc->hit_epoch += 1;
     const int64_t upto = sc->hit_dirty_to < sc->hit_cap ? sc->hit_dirty_to : sc->hit_cap;
-    if (upto > 0) HIP_TRY(hipMemset(sc->d_h_surf, 0xFF, (size_t)upto * sizeof(int32_t)));
+    if (upto > 0) HIP_TRY(hipMemset(sc->d_h_surf.get(), 0xFF, (size_t)upto * sizeof(int32_t)));
     sc->hit_dirty_to = 0;
     return TRC_OK;
 }
@@ -1829,7 +1863,7 @@ extern "C" int trc_scene_clear_hits(trc_scene *sc) {
     if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
     HIP_TRY(hipSetDevice(sc->ctx->device));
     HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    HIP_TRY(hipMemset(sc->d_counters, 0, 2 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(sc->d_counters.get(), 0, 2 * sizeof(unsigned long long)));
     sc->cnt_host[0] = sc->cnt_host[1] = 0ull;
     return scene_reset_hit_buffer(sc);
 }
@@ -1838,8 +1872,8 @@ extern "C" int trc_scene_reset_tallies(trc_scene *sc) {
     if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
     HIP_TRY(hipSetDevice(sc->ctx->device));
     HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    HIP_TRY(hipMemset(sc->d_tally, 0, (size_t)sc->tally_n * sizeof(double)));
-    HIP_TRY(hipMemset(sc->d_counters, 0, 8 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(sc->d_tally.get(), 0, (size_t)sc->tally_n * sizeof(double)));
+    HIP_TRY(hipMemset(sc->d_counters.get(), 0, 8 * sizeof(unsigned long long)));
     HIP_TRY(hipMemset(sc->d_energy_left, 0, sizeof(double)));
     memset(sc->cnt_host, 0, sizeof(sc->cnt_host));
     return scene_reset_hit_buffer(sc);
@@ -1851,7 +1885,7 @@ extern "C" int trc_scene_get_tallies(trc_scene *sc, double *absorbed, double *re
     HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
     const int S = sc->n_surf;
     std::vector<double> t((size_t)3 * S);
-    HIP_TRY(hipMemcpy(t.data(), sc->d_tally, t.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(t.data(), sc->d_tally.get(), t.size() * sizeof(double), hipMemcpyDeviceToHost));
     for (int i = 0; i < S; ++i) {
         if (absorbed) absorbed[i] = t[i];
         if (received) received[i] = t[S + i];
@@ -1867,7 +1901,7 @@ extern "C" int trc_scene_get_fluxmap(trc_scene *sc, int32_t surf, double *out) {
     HIP_TRY(hipSetDevice(sc->ctx->device));
     HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
     const FluxMapDev &m = sc->fms_h[fm];
-    HIP_TRY(hipMemcpy(out, sc->d_tally + m.bins, (size_t)m.nu * m.nv * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, sc->d_tally.get() + m.bins, (size_t)m.nu * m.nv * sizeof(double), hipMemcpyDeviceToHost));
     return TRC_OK;
 }
 
@@ -1932,12 +1966,12 @@ __global__ __launch_bounds__(256) void k_hits_gather(HitPack H, const uint32_t *
 static int scene_get_hits(trc_scene *sc, int64_t *n, int32_t *surf, double *e_abs, double *e_in, double *px,
                           double *py, double *pz, double *dx, double *dy, double *dz, int32_t n_x, double *x_out) {
     if (!sc || !n) return trc_fail(TRC_ERR_INVALID, "bad arguments");
-    if (n_x < 0 || (n_x > 0 && (!x_out || n_x != sc->hx_cols || !sc->d_hx)))
+    if (n_x < 0 || (n_x > 0 && (!x_out || n_x != sc->hx_cols || !sc->d_hx.get())))
         return trc_fail(TRC_ERR_INVALID, "trc_scene_get_hits_x: the hit buffer holds %d spectral columns, %d asked for", sc ? sc->hx_cols : 0, n_x);
     HIP_TRY(hipSetDevice(sc->ctx->device));
     HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
     unsigned long long c[2];
-    HIP_TRY(hipMemcpy(c, sc->d_counters, sizeof(c), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c, sc->d_counters.get(), sizeof(c), hipMemcpyDeviceToHost));
     int64_t reserved = (int64_t)c[0];
     if (reserved > sc->hit_cap) reserved = sc->hit_cap;
     *n = 0;
@@ -1947,77 +1981,78 @@ static int scene_get_hits(trc_scene *sc, int64_t *n, int32_t *surf, double *e_ab
     // gets the written ones, in buffer order (one capturing surface) or surface by surface (several).  They are packed on the device (copying the whole range and picking on the
     // host was 0.11 s for the 6.5e6 receiver hits of an NSTTF step).
     double *dst[8] = {e_abs, e_in, px, py, pz, dx, dy, dz};
-    uint32_t *d_flag = nullptr, *d_off = nullptr;
-    uint32_t *d_key[2] = {nullptr, nullptr}, *d_ent[2] = {nullptr, nullptr};
-    char *d_tmp = nullptr;
+    DevBuf<uint32_t> d_flag, d_off, d_key[2], d_ent[2];
+    DevBuf<char> d_tmp;
+    DevBuf<int32_t> o_surf;
+    DevBuf<double> o_col[8], o_x;
+    // declared after the temporaries, so it runs before they are freed: nothing queued on the stream may still use them
+    struct StreamWait { hipStream_t s; ~StreamWait() { (void)hipStreamSynchronize(s); } } wait_before_free{sc->ctx->stream};
+    TRC_TRY(d_flag.alloc((size_t)reserved));
+    TRC_TRY(d_off.alloc((size_t)reserved));
+    const unsigned nblk = (unsigned)((reserved + 255) / 256);
+    hipLaunchKernelGGL(k_hits_flag, dim3(nblk), dim3(256), 0, sc->ctx->stream, sc->d_h_surf.get(), (long long)reserved, d_flag.get());
+    size_t tmp_bytes = 0;
+    if (rocprim::exclusive_scan(nullptr, tmp_bytes, d_flag.get(), d_off.get(), 0u, (size_t)reserved, rocprim::plus<uint32_t>(), sc->ctx->stream) != hipSuccess)
+        return trc_fail(TRC_ERR_DEVICE, "exclusive_scan (size query) failed");
+    TRC_TRY(d_tmp.alloc(tmp_bytes ? tmp_bytes : 1));
+    if (rocprim::exclusive_scan(d_tmp.get(), tmp_bytes, d_flag.get(), d_off.get(), 0u, (size_t)reserved, rocprim::plus<uint32_t>(), sc->ctx->stream) != hipSuccess)
+        return trc_fail(TRC_ERR_DEVICE, "exclusive_scan failed");
+    uint32_t last_off = 0, last_flag = 0;
+    if (hipMemcpyAsync(&last_off, d_off.get() + (reserved - 1), 4, hipMemcpyDeviceToHost, sc->ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(&last_flag, d_flag.get() + (reserved - 1), 4, hipMemcpyDeviceToHost, sc->ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(sc->ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "hit count readback failed");
+    const int64_t cnt = (int64_t)last_off + (int64_t)last_flag;
+    *n = cnt;
+    if (cnt == 0 || (!surf && !e_abs && !e_in && !px && !py && !pz && !dx && !dy && !dz)) return TRC_OK;
     HitPack H;
     memset(&H, 0, sizeof(H));
-    int st = TRC_OK;
-    do {
-        if ((st = dev_alloc(&d_flag, (size_t)reserved)) || (st = dev_alloc(&d_off, (size_t)reserved))) break;
-        const unsigned nblk = (unsigned)((reserved + 255) / 256);
-        hipLaunchKernelGGL(k_hits_flag, dim3(nblk), dim3(256), 0, sc->ctx->stream, sc->d_h_surf, (long long)reserved, d_flag);
-        size_t tmp_bytes = 0;
-        if (rocprim::exclusive_scan(nullptr, tmp_bytes, d_flag, d_off, 0u, (size_t)reserved, rocprim::plus<uint32_t>(), sc->ctx->stream) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "exclusive_scan (size query) failed"); break; }
-        if ((st = dev_alloc(&d_tmp, tmp_bytes ? tmp_bytes : 1))) break;
-        if (rocprim::exclusive_scan(d_tmp, tmp_bytes, d_flag, d_off, 0u, (size_t)reserved, rocprim::plus<uint32_t>(), sc->ctx->stream) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "exclusive_scan failed"); break; }
-        uint32_t last_off = 0, last_flag = 0;
-        if (hipMemcpyAsync(&last_off, d_off + (reserved - 1), 4, hipMemcpyDeviceToHost, sc->ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(&last_flag, d_flag + (reserved - 1), 4, hipMemcpyDeviceToHost, sc->ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(sc->ctx->stream) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "hit count readback failed"); break; }
-        const int64_t cnt = (int64_t)last_off + (int64_t)last_flag;
-        *n = cnt;
-        if (cnt == 0 || (!surf && !e_abs && !e_in && !px && !py && !pz && !dx && !dy && !dz)) break;
-        H.surf = sc->d_h_surf;
-        H.sflags = sc->d_sflags;
-        if ((st = dev_alloc(&H.o_surf, (size_t)cnt))) break;
-        for (int k = 0; k < 8 && st == TRC_OK; ++k) {
-            H.col[k] = sc->d_h[k];
-            H.want[k] = dst[k] ? 1 : 0;
-            if (dst[k]) st = dev_alloc(&H.o_col[k], (size_t)cnt);
-        }
-        if (st) break;
-        if (n_x > 0) {
-            H.x = sc->d_hx; H.n_x = n_x; H.x_cap = sc->hx_cap; H.o_cnt = cnt;
-            if ((st = dev_alloc(&H.o_x, (size_t)cnt * (size_t)n_x))) break;
-        }
-        int n_capture = 0;
-        for (int i = 0; i < sc->n_surf; ++i) if (sc->surfs[i].flags & TRC_SURF_CAPTURE_HITS) ++n_capture;
-        if (n_capture <= 1) {
-            hipLaunchKernelGGL(k_hits_pack, dim3(nblk), dim3(256), 0, sc->ctx->stream, H, (const uint32_t *)d_off, (long long)reserved);
-        } else {
-            // Several capturing surfaces: the caller wants each one's hits together (accountants), and regrouping eight columns
-            // on the host cost 60 ms per 1e6 hits.  A stable radix sort of (surface, entry) pairs over the bits a surface index
-            // needs, then one gather: surface by surface, buffer order inside a surface, unwritten entries behind all of them.
-            if ((st = dev_alloc(&d_key[0], (size_t)reserved)) || (st = dev_alloc(&d_key[1], (size_t)reserved)) ||
-                (st = dev_alloc(&d_ent[0], (size_t)reserved)) || (st = dev_alloc(&d_ent[1], (size_t)reserved))) break;
-            hipLaunchKernelGGL(k_hits_keys, dim3(nblk), dim3(256), 0, sc->ctx->stream, sc->d_h_surf, (long long)reserved, (uint32_t)sc->n_surf,
-                               d_key[0], d_ent[0]);
-            unsigned bits = 1;
-            while ((1u << bits) <= (unsigned)sc->n_surf) ++bits;
-            size_t sort_bytes = 0;
-            if (rocprim::radix_sort_pairs(nullptr, sort_bytes, d_key[0], d_key[1], d_ent[0], d_ent[1], (size_t)reserved, 0, bits, sc->ctx->stream) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "radix_sort_pairs (size query) failed"); break; }
-            dev_free(d_tmp);
-            if ((st = dev_alloc(&d_tmp, sort_bytes ? sort_bytes : 1))) break;
-            if (rocprim::radix_sort_pairs(d_tmp, sort_bytes, d_key[0], d_key[1], d_ent[0], d_ent[1], (size_t)reserved, 0, bits, sc->ctx->stream) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "radix_sort_pairs failed"); break; }
-            hipLaunchKernelGGL(k_hits_gather, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, sc->ctx->stream, H, (const uint32_t *)d_ent[1], (long long)cnt);
-        }
-        // one copy per column, all behind the packing on the context's stream (page-locked destinations -- trc_host_alloc -- take
-        // them at the rate of the link), one wait
-        if (surf && hipMemcpyAsync(surf, H.o_surf, (size_t)cnt * 4, hipMemcpyDeviceToHost, sc->ctx->stream) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        for (int k = 0; k < 8; ++k)
-            if (dst[k] && hipMemcpyAsync(dst[k], H.o_col[k], (size_t)cnt * 8, hipMemcpyDeviceToHost, sc->ctx->stream) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        if (n_x > 0 && hipMemcpyAsync(x_out, H.o_x, (size_t)cnt * (size_t)n_x * 8, hipMemcpyDeviceToHost, sc->ctx->stream) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        if (st == TRC_OK && hipStreamSynchronize(sc->ctx->stream) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "fetching the hits failed"); break; }
-    } while (0);
-    (void)hipStreamSynchronize(sc->ctx->stream);
-    dev_free(d_flag); dev_free(d_off);
-    dev_free(d_key[0]); dev_free(d_key[1]); dev_free(d_ent[0]); dev_free(d_ent[1]);
-    dev_free(d_tmp);
-    dev_free(H.o_surf);
-    dev_free(H.o_x);
-    for (int k = 0; k < 8; ++k) dev_free(H.o_col[k]);
-    return st;
+    H.surf = sc->d_h_surf.get();
+    H.sflags = sc->d_sflags.get();
+    TRC_TRY(o_surf.alloc((size_t)cnt));
+    H.o_surf = o_surf.get();
+    for (int k = 0; k < 8; ++k) {
+        H.col[k] = sc->d_h[k].get();
+        H.want[k] = dst[k] ? 1 : 0;
+        if (dst[k]) { TRC_TRY(o_col[k].alloc((size_t)cnt)); H.o_col[k] = o_col[k].get(); }
+    }
+    if (n_x > 0) {
+        H.x = sc->d_hx.get(); H.n_x = n_x; H.x_cap = sc->hx_cap; H.o_cnt = cnt;
+        TRC_TRY(o_x.alloc((size_t)cnt * (size_t)n_x));
+        H.o_x = o_x.get();
+    }
+    int n_capture = 0;
+    for (int i = 0; i < sc->n_surf; ++i) if (sc->surfs[i].flags & TRC_SURF_CAPTURE_HITS) ++n_capture;
+    if (n_capture <= 1) {
+        hipLaunchKernelGGL(k_hits_pack, dim3(nblk), dim3(256), 0, sc->ctx->stream, H, (const uint32_t *)d_off.get(), (long long)reserved);
+    } else {
+        // Several capturing surfaces: the caller wants each one's hits together (accountants), and regrouping eight columns
+        // on the host cost 60 ms per 1e6 hits.  A stable radix sort of (surface, entry) pairs over the bits a surface index
+        // needs, then one gather: surface by surface, buffer order inside a surface, unwritten entries behind all of them.
+        TRC_TRY(d_key[0].alloc((size_t)reserved));
+        TRC_TRY(d_key[1].alloc((size_t)reserved));
+        TRC_TRY(d_ent[0].alloc((size_t)reserved));
+        TRC_TRY(d_ent[1].alloc((size_t)reserved));
+        uint32_t *key0 = d_key[0].get(), *key1 = d_key[1].get(), *ent0 = d_ent[0].get(), *ent1 = d_ent[1].get();
+        hipLaunchKernelGGL(k_hits_keys, dim3(nblk), dim3(256), 0, sc->ctx->stream, sc->d_h_surf.get(), (long long)reserved, (uint32_t)sc->n_surf,
+                           key0, ent0);
+        unsigned bits = 1;
+        while ((1u << bits) <= (unsigned)sc->n_surf) ++bits;
+        size_t sort_bytes = 0;
+        if (rocprim::radix_sort_pairs(nullptr, sort_bytes, key0, key1, ent0, ent1, (size_t)reserved, 0, bits, sc->ctx->stream) != hipSuccess)
+            return trc_fail(TRC_ERR_DEVICE, "radix_sort_pairs (size query) failed");
+        TRC_TRY(d_tmp.alloc(sort_bytes ? sort_bytes : 1));
+        if (rocprim::radix_sort_pairs(d_tmp.get(), sort_bytes, key0, key1, ent0, ent1, (size_t)reserved, 0, bits, sc->ctx->stream) != hipSuccess)
+            return trc_fail(TRC_ERR_DEVICE, "radix_sort_pairs failed");
+        hipLaunchKernelGGL(k_hits_gather, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, sc->ctx->stream, H, (const uint32_t *)ent1, (long long)cnt);
+    }
+    // one copy per column, all behind the packing on the context's stream (page-locked destinations -- trc_host_alloc -- take
+    // them at the rate of the link), one wait
+    if (surf && hipMemcpyAsync(surf, H.o_surf, (size_t)cnt * 4, hipMemcpyDeviceToHost, sc->ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
+    for (int k = 0; k < 8; ++k)
+        if (dst[k] && hipMemcpyAsync(dst[k], H.o_col[k], (size_t)cnt * 8, hipMemcpyDeviceToHost, sc->ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
+    if (n_x > 0 && hipMemcpyAsync(x_out, H.o_x, (size_t)cnt * (size_t)n_x * 8, hipMemcpyDeviceToHost, sc->ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
+    if (hipStreamSynchronize(sc->ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "fetching the hits failed");
+    return TRC_OK;
 }
 
 extern "C" int trc_scene_get_hits(trc_scene *sc, int64_t *n, int32_t *surf, double *e_abs, double *e_in, double *px,
@@ -2032,7 +2067,7 @@ extern "C" int trc_scene_get_hits_x(trc_scene *sc, int64_t *n, int32_t *surf, do
 
 extern "C" int trc_scene_hit_spectral_columns(trc_scene *sc, int32_t *n_x) {
     if (!sc || !n_x) return trc_fail(TRC_ERR_INVALID, "bad arguments");
-    *n_x = sc->d_hx ? sc->hx_cols : 0;
+    *n_x = sc->d_hx.get() ? sc->hx_cols : 0;
     return TRC_OK;
 }
 
@@ -2081,7 +2116,7 @@ extern "C" int trc_scene_bin_hits(trc_scene *sc, int32_t n_bins, const int32_t *
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     unsigned long long c[2];
-    HIP_TRY(hipMemcpy(c, sc->d_counters, sizeof(c), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c, sc->d_counters.get(), sizeof(c), hipMemcpyDeviceToHost));
     long long reserved = (long long)c[0];
     if (reserved > sc->hit_cap) reserved = sc->hit_cap;
     for (int i = 0; i < n_bins; ++i) out[i] = 0.0;
@@ -2102,8 +2137,8 @@ extern "C" int trc_scene_bin_hits(trc_scene *sc, int32_t n_bins, const int32_t *
         if (e == hipSuccess) e = hipMemcpyAsync(d_mode, mode + b0, (size_t)nb * 4, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, (size_t)nb * 8, ctx->stream);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_bin_hits, dim3(grid), dim3(256), 0, ctx->stream, reserved, sc->d_h_surf, sc->d_h[0], sc->d_h[2], sc->d_h[3],
-                               sc->d_h[4], nb, d_lo, d_hi, d_rng, d_mode, d_out);
+            hipLaunchKernelGGL(k_bin_hits, dim3(grid), dim3(256), 0, ctx->stream, reserved, sc->d_h_surf.get(), sc->d_h[0].get(), sc->d_h[2].get(), sc->d_h[3].get(),
+                               sc->d_h[4].get(), nb, d_lo, d_hi, d_rng, d_mode, d_out);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(out + b0, d_out, (size_t)nb * 8, hipMemcpyDeviceToHost, ctx->stream);
@@ -2124,7 +2159,7 @@ extern "C" int trc_scene_enable_transfer(trc_scene *sc, int32_t on) {
     if ((on != 0) == sc->transfer_on) return TRC_OK;
     sc->transfer_on = on != 0;
     TRC_TRY(scene_alloc_tally(sc));      // resets the tallies; flux-map bins keep their offsets (the matrix comes last)
-    if (!sc->fms_h.empty()) HIP_TRY(hipMemcpy(sc->d_fms, sc->fms_h.data(), sc->fms_h.size() * sizeof(FluxMapDev), hipMemcpyHostToDevice));
+    if (!sc->fms_h.empty()) HIP_TRY(hipMemcpy(sc->d_fms.get(), sc->fms_h.data(), sc->fms_h.size() * sizeof(FluxMapDev), hipMemcpyHostToDevice));
     return TRC_OK;
 }
 
@@ -2133,7 +2168,7 @@ extern "C" int trc_scene_get_transfer(trc_scene *sc, double *out) {
     if (!sc->transfer_on) return trc_fail(TRC_ERR_INVALID, "the transfer matrix is not enabled (trc_scene_enable_transfer)");
     HIP_TRY(hipSetDevice(sc->ctx->device));
     HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    HIP_TRY(hipMemcpy(out, sc->d_tally + sc->tr_off, (size_t)(sc->n_surf + 1) * sc->n_surf * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, sc->d_tally.get() + sc->tr_off, (size_t)(sc->n_surf + 1) * sc->n_surf * sizeof(double), hipMemcpyDeviceToHost));
     return TRC_OK;
 }
 
@@ -2147,7 +2182,7 @@ extern "C" int trc_scene_export_tallies(trc_scene *sc, double *dst, int32_t on_d
     if (!sc || !dst) return trc_fail(TRC_ERR_INVALID, "bad arguments");
     HIP_TRY(hipSetDevice(sc->ctx->device));
     HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    HIP_TRY(hipMemcpy(dst, sc->d_tally, (size_t)sc->tally_n * sizeof(double),
+    HIP_TRY(hipMemcpy(dst, sc->d_tally.get(), (size_t)sc->tally_n * sizeof(double),
                       on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
     return TRC_OK;
 }
@@ -2156,7 +2191,7 @@ extern "C" int trc_scene_import_tallies(trc_scene *sc, const double *src, int32_
     if (!sc || !src) return trc_fail(TRC_ERR_INVALID, "bad arguments");
     HIP_TRY(hipSetDevice(sc->ctx->device));
     HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    HIP_TRY(hipMemcpy(sc->d_tally, src, (size_t)sc->tally_n * sizeof(double),
+    HIP_TRY(hipMemcpy(sc->d_tally.get(), src, (size_t)sc->tally_n * sizeof(double),
                       on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     return TRC_OK;
 }
@@ -2164,23 +2199,23 @@ extern "C" int trc_scene_import_tallies(trc_scene *sc, const double *src, int32_
 static DScene make_dscene(trc_scene *sc) {
     DScene d;
     memset(&d, 0, sizeof(d));
-    d.recs = sc->d_recs; d.opt = sc->d_opt; d.sflags = sc->d_sflags; d.extra = sc->d_extra;
+    d.recs = sc->d_recs.get(); d.opt = sc->d_opt.get(); d.sflags = sc->d_sflags.get(); d.extra = sc->d_extra.get();
     d.stride = sc->stride; d.n_surf = sc->n_surf; d.n_extra = sc->n_extra; d.has_kd = sc->has_kd ? 1 : 0;
-    d.kd_a = sc->d_kd_a; d.kd_b = sc->d_kd_b; d.kd_leaf = sc->d_kd_leaf; d.kd_always = sc->d_kd_always;
-    d.kd_split = sc->d_kd_split;
+    d.kd_a = sc->d_kd_a.get(); d.kd_b = sc->d_kd_b.get(); d.kd_leaf = sc->d_kd_leaf.get(); d.kd_always = sc->d_kd_always.get();
+    d.kd_split = sc->d_kd_split.get();
     d.kd_nodes = sc->kd_nodes; d.kd_nleaf = sc->kd_nleaf; d.kd_nalways = sc->kd_nalways;
     for (int i = 0; i < 3; ++i) { d.kd_bmin[i] = sc->kd_bounds[i]; d.kd_bmax[i] = sc->kd_bounds[3 + i]; }
-    d.a_sbox = sc->d_a_sbox; d.a_obb = sc->d_a_obb; d.a_nodes = sc->d_a_nodes; d.a_leaf = sc->d_a_leaf; d.a_unbounded = sc->d_a_unbounded;
+    d.a_sbox = sc->d_a_sbox.get(); d.a_obb = sc->d_a_obb.get(); d.a_nodes = sc->d_a_nodes.get(); d.a_leaf = sc->d_a_leaf.get(); d.a_unbounded = sc->d_a_unbounded.get();
     d.a_n_unbounded = (int32_t)sc->accel.unbounded.size(); d.a_kd_depth = sc->accel.kd_depth;
-    d.a_bleaf = sc->d_a_bleaf; d.a_n_bleaf = (int32_t)sc->accel.brute_leaf.size();
+    d.a_bleaf = sc->d_a_bleaf.get(); d.a_n_bleaf = (int32_t)sc->accel.brute_leaf.size();
     d.a_bnodes[0] = sc->accel.brute_nodes[0]; d.a_bnodes[1] = sc->accel.brute_nodes[1];
     for (int i = 0; i < 6; ++i) d.a_broot[i] = sc->accel.brute_root[i];
     d.a_ok = sc->accel_ok ? 1 : 0; d.a_kd_ok = sc->accel_kd_ok ? 1 : 0;
     for (int i = 0; i < 6; ++i) d.a_root[i] = sc->accel.root[i];
     d.a_delta = sc->accel.delta;
-    d.a_goff = sc->d_a_goff; d.a_glist = sc->d_a_glist; d.a_gapart = sc->d_a_gapart;
-    d.a_bg_off = sc->d_a_bg_off; d.a_bg_occ = sc->d_a_bg_occ; d.a_bg_ent = sc->d_a_bg_ent; d.a_bg_ok = sc->accel.big_ok ? 1 : 0;
-    d.a_bg_apart = sc->d_a_bg_apart; d.a_bg_napart = sc->accel.big_ok ? (int32_t)sc->accel.big_apart.size() : 0;
+    d.a_goff = sc->d_a_goff.get(); d.a_glist = sc->d_a_glist.get(); d.a_gapart = sc->d_a_gapart.get();
+    d.a_bg_off = sc->d_a_bg_off.get(); d.a_bg_occ = sc->d_a_bg_occ.get(); d.a_bg_ent = sc->d_a_bg_ent.get(); d.a_bg_ok = sc->accel.big_ok ? 1 : 0;
+    d.a_bg_apart = sc->d_a_bg_apart.get(); d.a_bg_napart = sc->accel.big_ok ? (int32_t)sc->accel.big_apart.size() : 0;
     for (int i = 0; i < 3; ++i) {
         d.a_bg_dim[i] = sc->accel.big_ok ? sc->accel.big_dim[i] : 1;
         d.a_bg_lo[i] = sc->accel.big_lo[i]; d.a_bg_cs[i] = sc->accel.big_cs[i]; d.a_bg_inv[i] = sc->accel.big_inv[i];
@@ -2196,31 +2231,27 @@ static DScene make_dscene(trc_scene *sc) {
         d.a_glo[i] = sc->accel.grid_lo[i]; d.a_gcs[i] = sc->accel.grid_cs[i]; d.a_ginv[i] = sc->accel.grid_inv[i];
     }
     for (int i = 0; i < 3; ++i) { d.a_cen[i] = sc->accel.cen[i]; d.a_slo[i] = sc->accel.slo[i]; d.a_shi[i] = sc->accel.shi[i]; }
-    d.tally = sc->d_tally;
-    d.fm_of_surf = sc->d_fm_of_surf; d.fms = sc->d_fms; d.fm_edges = sc->d_fm_edges;
+    d.tally = sc->d_tally.get();
+    d.fm_of_surf = sc->d_fm_of_surf.get(); d.fms = sc->d_fms.get(); d.fm_edges = sc->d_fm_edges.get();
     d.tr_off = sc->tr_off;
     d.n_fm = (int32_t)sc->fms_h.size(); d.n_fm_edges = (int32_t)sc->fm_edges_h.size();
-    d.counters = sc->d_counters; d.energy_left = sc->d_energy_left;
-    d.hit_cap = sc->hit_cap; d.h_surf = sc->d_h_surf;
-    d.h_eabs = sc->d_h[0]; d.h_ein = sc->d_h[1]; d.h_px = sc->d_h[2]; d.h_py = sc->d_h[3]; d.h_pz = sc->d_h[4];
-    d.h_dx = sc->d_h[5]; d.h_dy = sc->d_h[6]; d.h_dz = sc->d_h[7];
+    d.counters = sc->d_counters.get(); d.energy_left = sc->d_energy_left;
+    d.hit_cap = sc->hit_cap; d.h_surf = sc->d_h_surf.get();
+    d.h_eabs = sc->d_h[0].get(); d.h_ein = sc->d_h[1].get(); d.h_px = sc->d_h[2].get(); d.h_py = sc->d_h[3].get(); d.h_pz = sc->d_h[4].get();
+    d.h_dx = sc->d_h[5].get(); d.h_dy = sc->d_h[6].get(); d.h_dz = sc->d_h[7].get();
     return d;
 }
 
 // ================================================================================================
 // ray staging helpers
 // ================================================================================================
+// the columns of a bundle as the kernels read them: the caller's own when they are on the device, else copies held in `own`
 struct DevRays {
     double *x = nullptr, *y = nullptr, *z = nullptr, *dx = nullptr, *dy = nullptr, *dz = nullptr, *e = nullptr;
     double *ref = nullptr, *wl = nullptr;
     uint64_t *rid = nullptr;
-    bool owned[10] = {false, false, false, false, false, false, false, false, false, false};
-    void release() {
-        double **p[9] = {&x, &y, &z, &dx, &dy, &dz, &e, &ref, &wl};
-        for (int i = 0; i < 9; ++i) { if (owned[i] && *p[i]) pool_free(*p[i]); *p[i] = nullptr; }
-        if (owned[9] && rid) pool_free(rid);
-        rid = nullptr;
-    }
+    DevBuf<double> own[9];
+    DevBuf<uint64_t> own_rid;
 };
 
 static int check_rays(const trc_rays *r, int64_t n, const char *who) {
@@ -2239,27 +2270,23 @@ static int stage_rays(const trc_rays *r, int64_t n, bool need_energy, DevRays *d
     for (int i = 0; i < 9; ++i) {
         if (!src[i]) continue;
         if (r->on_device) { *dst[i] = (double *)src[i]; continue; }
-        TRC_TRY(dev_alloc(dst[i], (size_t)n));
-        d->owned[i] = true;
-        HIP_TRY(hipMemcpy(*dst[i], src[i], (size_t)n * 8, hipMemcpyHostToDevice));
+        TRC_TRY(dev_upload(d->own[i], src[i], (size_t)n));
+        *dst[i] = d->own[i].get();
     }
     if (r->rid) {
         if (r->on_device) d->rid = r->rid;
         else {
-            TRC_TRY(dev_alloc(&d->rid, (size_t)n));
-            d->owned[9] = true;
-            HIP_TRY(hipMemcpy(d->rid, r->rid, (size_t)n * 8, hipMemcpyHostToDevice));
+            TRC_TRY(dev_upload(d->own_rid, r->rid, (size_t)n));
+            d->rid = d->own_rid.get();
         }
     }
     return TRC_OK;
 }
 
-static int upload_source(const trc_source_desc *src, trc_source_desc **d_src) {
+static int upload_source(const trc_source_desc *src, DevBuf<trc_source_desc> &d_src) {
     if (src->kind < TRC_SRC_PILLBOX_DISK || src->kind > TRC_SRC_VF_FRUSTUM)
         return trc_fail(TRC_ERR_UNSUPPORTED, "source kind %d is not in the native table", src->kind);
-    TRC_TRY(dev_alloc(d_src, 1));
-    HIP_TRY(hipMemcpy(*d_src, src, sizeof(trc_source_desc), hipMemcpyHostToDevice));
-    return TRC_OK;
+    return dev_upload(d_src, src, 1);
 }
 
 // ================================================================================================
@@ -2297,73 +2324,70 @@ static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_d
     // TRC_TRACE_ACCEL without a Kd-tree: the streaming form searches its own grid; the megakernel tests every box
     trc_ctx *ctx = sc->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    DevRays dr;
-    trc_source_desc *d_src = nullptr;
-    double *d_last[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int st = TRC_OK;
     trc_trace_stats s;
     memset(&s, 0, sizeof(s));
-    double tally_before[2] = {0, 0};
-    unsigned long long cnt_before[4] = {0, 0, 0, 0};
-    double eleft_before = 0;
-    double stream_seg = 0, stream_hits = 0;
-    bool stream_counts_known = false;
-    const int S = sc->n_surf;
-    double *carry_d[4] = {nullptr, nullptr, nullptr, nullptr};      // Im of the index, materials, sample wavelengths, spectra
-    bool carry_owned[4] = {false, false, false, false};
-    do {
+    // the call's work; the stats it gathered are handed back whatever its outcome
+    const int st = [&]() -> int {
+        DevRays dr;
+        trc_source_desc *d_src = nullptr;
+        double *d_last[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        double tally_before[2] = {0, 0};
+        unsigned long long cnt_before[4] = {0, 0, 0, 0};
+        double eleft_before = 0;
+        double stream_seg = 0, stream_hits = 0;
+        bool stream_counts_known = false;
+        const int S = sc->n_surf;
+        double *carry_d[4] = {nullptr, nullptr, nullptr, nullptr};      // Im of the index, materials, sample wavelengths, spectra
+        DevBuf<double> carry_own[4];                                    // ... copied here unless the caller's are on the device
         if (in) {
-            if ((st = check_rays(in, n, "trc_trace_fast")) || (st = stage_rays(in, n, true, &dr))) break;
+            TRC_TRY(check_rays(in, n, "trc_trace_fast"));
+            TRC_TRY(stage_rays(in, n, true, &dr));
             if (carry) {        // the carried columns: rows of the bundle's own length in->n apart on the host, n apart here
-                struct { const double *src; int rows; double **dst; } blk[4] = {{in->ref_index_im, 1, &carry_d[0]}, {in->mat, 2 * carry_mat, &carry_d[1]},
-                                                                                 {carry_W ? in->spec_wl : nullptr, carry_W, &carry_d[2]},
-                                                                                 {carry_W ? in->spectra : nullptr, carry_W, &carry_d[3]}};
-                for (int b = 0; b < 4 && st == TRC_OK; ++b) {
+                struct { const double *src; int rows; } blk[4] = {{in->ref_index_im, 1}, {in->mat, 2 * carry_mat}, {carry_W ? in->spec_wl : nullptr, carry_W},
+                                                                  {carry_W ? in->spectra : nullptr, carry_W}};
+                for (int b = 0; b < 4; ++b) {
                     if (!blk[b].src || blk[b].rows <= 0) continue;
-                    if (in->on_device && in->n == n) { *blk[b].dst = (double *)blk[b].src; continue; }
-                    if ((st = dev_alloc(blk[b].dst, (size_t)blk[b].rows * (size_t)n))) break;
-                    carry_owned[b] = true;
-                    if (hipMemcpy2D(*blk[b].dst, (size_t)n * 8, blk[b].src, (size_t)in->n * 8, (size_t)n * 8, (size_t)blk[b].rows,
+                    if (in->on_device && in->n == n) { carry_d[b] = (double *)blk[b].src; continue; }
+                    TRC_TRY(carry_own[b].alloc((size_t)blk[b].rows * (size_t)n));
+                    carry_d[b] = carry_own[b].get();
+                    if (hipMemcpy2D(carry_d[b], (size_t)n * 8, blk[b].src, (size_t)in->n * 8, (size_t)n * 8, (size_t)blk[b].rows,
                                     in->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) != hipSuccess)
-                        st = trc_fail(TRC_ERR_DEVICE, "upload of the carried columns failed");
+                        return trc_fail(TRC_ERR_DEVICE, "upload of the carried columns failed");
                 }
-                if (st) break;
             }
         }
         else {
             // the scene keeps a device buffer for the descriptor of the call in progress (hipMalloc / hipFree per call
             // cost more than the upload)
-            if (src->kind < TRC_SRC_PILLBOX_DISK || src->kind > TRC_SRC_VF_FRUSTUM) { st = trc_fail(TRC_ERR_UNSUPPORTED, "source kind %d is not in the native table", src->kind); break; }
-            if (!sc->d_src_buf) { if ((st = dev_alloc(&sc->d_src_buf, 1))) break; sc->src_host_ok = false; }
+            if (src->kind < TRC_SRC_PILLBOX_DISK || src->kind > TRC_SRC_VF_FRUSTUM) return trc_fail(TRC_ERR_UNSUPPORTED, "source kind %d is not in the native table", src->kind);
+            if (!sc->d_src_buf) { TRC_TRY(sc->d_src_buf.alloc(1)); sc->src_host_ok = false; }
             if (!(sc->src_host_ok && memcmp(&sc->src_host, src, sizeof(trc_source_desc)) == 0)) {
                 sc->src_host_ok = false;
-                if (hipMemcpy(sc->d_src_buf, src, sizeof(trc_source_desc), hipMemcpyHostToDevice) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "source upload failed"); break; }
+                if (hipMemcpy(sc->d_src_buf.get(), src, sizeof(trc_source_desc), hipMemcpyHostToDevice) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "source upload failed");
                 memcpy(&sc->src_host, src, sizeof(trc_source_desc));
                 sc->src_host_ok = true;
             }
-            d_src = sc->d_src_buf;
+            d_src = sc->d_src_buf.get();
         }
         int64_t last_cap = 0;
         if (flags & TRC_TRACE_KEEP_LAST) {
-            if (!last || !last->x || !last->y || !last->z || !last->dx || !last->dy || !last->dz || !last->e || last->on_device) {
-                st = trc_fail(TRC_ERR_INVALID, "TRC_TRACE_KEEP_LAST needs a host `last` bundle with x..e"); break;
-            }
+            if (!last || !last->x || !last->y || !last->z || !last->dx || !last->dy || !last->dz || !last->e || last->on_device)
+                return trc_fail(TRC_ERR_INVALID, "TRC_TRACE_KEEP_LAST needs a host `last` bundle with x..e");
             last_cap = last->n;
             if (sc->d_last_cap < last_cap) {
-                for (int i = 0; i < 7; ++i) dev_free(sc->d_last[i]);
+                for (auto &col : sc->d_last) col.reset();
                 sc->d_last_cap = 0;
-                for (int i = 0; i < 7 && st == TRC_OK; ++i) st = dev_alloc(&sc->d_last[i], (size_t)last_cap);
-                if (st) { for (int i = 0; i < 7; ++i) dev_free(sc->d_last[i]); break; }
+                for (auto &col : sc->d_last)
+                    if (int e = col.alloc((size_t)last_cap)) { for (auto &c : sc->d_last) c.reset(); return e; }
                 sc->d_last_cap = last_cap;
             }
-            for (int i = 0; i < 7; ++i) d_last[i] = sc->d_last[i];
+            for (int i = 0; i < 7; ++i) d_last[i] = sc->d_last[i].get();
         }
         // counters and the energy left live in one 64-byte block: one read before, one after
         unsigned long long blk_before[8];
         if (sc->cnt_host_ok) memcpy(blk_before, sc->cnt_host, sizeof(blk_before));
-        else if (hipMemcpy(blk_before, sc->d_counters, sizeof(blk_before), hipMemcpyDeviceToHost) != hipSuccess) {
-            st = trc_fail(TRC_ERR_DEVICE, "counter readback failed"); break;
-        }
+        else if (hipMemcpy(blk_before, sc->d_counters.get(), sizeof(blk_before), hipMemcpyDeviceToHost) != hipSuccess)
+            return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
         sc->cnt_host_ok = false;          // (until this call has read them back at its end)
         const int64_t dirty_before = sc->hit_dirty_to;
         sc->hit_dirty_to = sc->hit_cap;   // (... and then says how far the hit buffer was used)
@@ -2372,7 +2396,7 @@ static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_d
         // the `last` cursor restarts for every call
         if (blk_before[2] != 0ull) {
             unsigned long long zero = 0;
-            if (hipMemcpy(sc->d_counters + 2, &zero, sizeof(zero), hipMemcpyHostToDevice) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
+            if (hipMemcpy(sc->d_counters.get() + 2, &zero, sizeof(zero), hipMemcpyHostToDevice) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
         }
 
         FastParams P;
@@ -2389,14 +2413,14 @@ static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_d
         if (carry_W > 0 && captures) {
             const int cols = 3 * carry_W;
             if (sc->d_hx && (sc->hx_cols != cols || sc->hx_cap != sc->hit_cap)) {
-                if (cnt_before[0] != 0ull) { st = trc_fail(TRC_ERR_INVALID, "the hit buffer holds hits with spectra of another sample count: read or clear them first"); break; }
-                dev_free(sc->d_hx); sc->hx_cols = 0; sc->hx_cap = 0;
+                if (cnt_before[0] != 0ull) return trc_fail(TRC_ERR_INVALID, "the hit buffer holds hits with spectra of another sample count: read or clear them first");
+                sc->d_hx.reset(); sc->hx_cols = 0; sc->hx_cap = 0;
             }
             if (!sc->d_hx) {
-                if ((st = dev_alloc(&sc->d_hx, (size_t)cols * (size_t)sc->hit_cap))) break;
+                TRC_TRY(sc->d_hx.alloc((size_t)cols * (size_t)sc->hit_cap));
                 sc->hx_cols = cols; sc->hx_cap = sc->hit_cap;
             }
-            hit_x = sc->d_hx;
+            hit_x = sc->d_hx.get();
         }
         CarryIn carry_in;
         carry_in.hit_x = hit_x; carry_in.hit_x_cap = sc->hx_cap;
@@ -2449,31 +2473,30 @@ static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_d
         // relief of 105 800 triangles took 570 ms there, 1.3 ms here)
         const long long stream_from = plan.mode == 3 ? 4096 : TRC_STREAM_MIN_RAYS;
         const bool use_stream = stream_ok && (force_stream || (!force_mega && n >= stream_from));
-        if (carry && !use_stream) { st = trc_fail(TRC_ERR_UNSUPPORTED, "no streaming form for this scene: rays that carry complex indices or spectra go through trc_trace_ordered"); break; }
+        if (carry && !use_stream) return trc_fail(TRC_ERR_UNSUPPORTED, "no streaming form for this scene: rays that carry complex indices or spectra go through trc_trace_ordered");
         if (use_stream) {
             if (!sc->stream_eng) {
-                sc->stream_eng = new (std::nothrow) StreamEngine();
-                if (!sc->stream_eng) { st = trc_fail(TRC_ERR_NOMEM, "out of host memory"); break; }
-                memset(sc->stream_eng, 0, sizeof(StreamEngine));
+                sc->stream_eng = new (std::nothrow) StreamEngine();      // (value-initialised: all zero)
+                if (!sc->stream_eng) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
             }
-            if ((st = stream_trace(sc, P, carry_in, plan, knobs, src, *sc->stream_eng, &s, &stream_seg, &stream_hits))) {
+            if (int e = stream_trace(sc, P, carry_in, plan, knobs, src, *sc->stream_eng, &s, &stream_seg, &stream_hits)) {
                 // the hits captured by the bounces that completed: wind the buffer back to where the call found it
                 const std::string why = g_last_error;
                 unsigned long long now = 0;
                 (void)hipDeviceSynchronize();
-                if (sc->hit_cap > 0 && hipMemcpy(&now, sc->d_counters, sizeof(now), hipMemcpyDeviceToHost) == hipSuccess && now > cnt_before[0]) {
+                if (sc->hit_cap > 0 && hipMemcpy(&now, sc->d_counters.get(), sizeof(now), hipMemcpyDeviceToHost) == hipSuccess && now > cnt_before[0]) {
                     const unsigned long long end = now < (unsigned long long)sc->hit_cap ? now : (unsigned long long)sc->hit_cap;
-                    if (end > cnt_before[0]) (void)hipMemset(sc->d_h_surf + cnt_before[0], 0xFF, (size_t)(end - cnt_before[0]) * sizeof(int32_t));
-                    (void)hipMemcpy(sc->d_counters, &cnt_before[0], sizeof(unsigned long long), hipMemcpyHostToDevice);
+                    if (end > cnt_before[0]) (void)hipMemset(sc->d_h_surf.get() + cnt_before[0], 0xFF, (size_t)(end - cnt_before[0]) * sizeof(int32_t));
+                    (void)hipMemcpy(sc->d_counters.get(), &cnt_before[0], sizeof(unsigned long long), hipMemcpyHostToDevice);
                 }
                 sc->hit_epoch += 1;
                 g_last_error = why;
-                break;
+                return e;
             }
             stream_counts_known = true;
         } else {
         (void)hipStreamSynchronize(ctx->stream);       // (the sums of an earlier streaming call may still be on their way into the buffer)
-        if (hipMemcpy(tally_before, sc->d_tally + 3 * S, sizeof(tally_before), hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "counter readback failed"); break; }
+        if (hipMemcpy(tally_before, sc->d_tally.get() + 3 * S, sizeof(tally_before), hipMemcpyDeviceToHost) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
         void (*kern)(FastParams) = nullptr;
         if (P.spec) {       // (a source with a spectrum: the instances that draw the wavelength)
             if (m32) kern = threads == 512 ? k_trace_coop<512, true> : k_trace_coop<256, true>;
@@ -2484,19 +2507,19 @@ static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_d
         }
         // persistent grid: as many workgroups as are resident at once (at most 8 per CU), never more waves than rays/64
         unsigned resident = 0;
-        if ((st = kernel_grid_cap((const void *)kern, threads, lds, 8, ctx->n_cu, &resident))) break;
+        TRC_TRY(kernel_grid_cap((const void *)kern, threads, lds, 8, ctx->n_cu, &resident));
         long long grid = resident;
         long long max_grid = (n + threads - 1) / threads;
         if (grid > max_grid) grid = max_grid;
         if (grid < 1) grid = 1;
         if (n > 0) {
-            if (hipEventRecord(ctx->ev0, ctx->stream) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "event record failed"); break; }
+            if (hipEventRecord(ctx->ev0, ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "event record failed");
             hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), lds, ctx->stream, P);
             hipError_t le = hipGetLastError();
-            if (le != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "k_trace_fast launch failed: %s", hipGetErrorString(le)); break; }
-            if (hipEventRecord(ctx->ev1, ctx->stream) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "event record failed"); break; }
+            if (le != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_trace_fast launch failed: %s", hipGetErrorString(le));
+            if (hipEventRecord(ctx->ev1, ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "event record failed");
             hipError_t se = hipStreamSynchronize(ctx->stream);
-            if (se != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "k_trace_fast failed: %s", hipGetErrorString(se)); break; }
+            if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_trace_fast failed: %s", hipGetErrorString(se));
             float ms = 0;
             (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
             s.kernel_ms = ms;
@@ -2505,9 +2528,8 @@ static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_d
         }
         unsigned long long blk_after[8], cnt_after[4];
         double eleft_after;
-        if (hipMemcpy(blk_after, sc->d_counters, sizeof(blk_after), hipMemcpyDeviceToHost) != hipSuccess) {
-            st = trc_fail(TRC_ERR_DEVICE, "counter readback failed"); break;
-        }
+        if (hipMemcpy(blk_after, sc->d_counters.get(), sizeof(blk_after), hipMemcpyDeviceToHost) != hipSuccess)
+            return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
         for (int i = 0; i < 4; ++i) cnt_after[i] = blk_after[i];
         memcpy(&eleft_after, &blk_after[5], sizeof(double));
         memcpy(sc->cnt_host, blk_after, sizeof(blk_after));
@@ -2521,9 +2543,8 @@ static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_d
             s.hits = (int64_t)(stream_hits + 0.5);
         } else {
             double tally_after[2];
-            if (hipMemcpy(tally_after, sc->d_tally + 3 * S, sizeof(tally_after), hipMemcpyDeviceToHost) != hipSuccess) {
-                st = trc_fail(TRC_ERR_DEVICE, "counter readback failed"); break;
-            }
+            if (hipMemcpy(tally_after, sc->d_tally.get() + 3 * S, sizeof(tally_after), hipMemcpyDeviceToHost) != hipSuccess)
+                return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
             s.segments = (int64_t)(tally_after[0] - tally_before[0] + 0.5);
             s.hits = (int64_t)(tally_after[1] - tally_before[1] + 0.5);
         }
@@ -2533,15 +2554,13 @@ static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_d
         s.bounces = reps;
         if (flags & TRC_TRACE_KEEP_LAST) {
             int64_t m = (int64_t)cnt_after[2];
-            if (m > last_cap) { st = trc_fail(TRC_ERR_CAPACITY, "%lld rays left but `last` holds %lld", (long long)m, (long long)last_cap); break; }
+            if (m > last_cap) return trc_fail(TRC_ERR_CAPACITY, "%lld rays left but `last` holds %lld", (long long)m, (long long)last_cap);
             double *dst[7] = {last->x, last->y, last->z, last->dx, last->dy, last->dz, last->e};
-            for (int i = 0; i < 7 && m > 0; ++i)
-                if (hipMemcpy(dst[i], d_last[i], (size_t)m * 8, hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
+            for (int i = 0; i < 7 && m > 0; ++i) TRC_TRY(dev_download(dst[i], d_last[i], (size_t)m));
             last->n = m;
         }
-    } while (0);
-    dr.release();
-    for (int b = 0; b < 4; ++b) if (carry_owned[b]) pool_free(carry_d[b]);
+        return TRC_OK;
+    }();
     if (stats) *stats = s;
     return st;
 }
@@ -2559,21 +2578,17 @@ extern "C" int trc_source_start32(trc_ctx *ctx, const trc_source_desc *src, int6
     if (!trc_fp_source(*src, F, &half, &theta_c, &why)) return trc_fail(TRC_ERR_UNSUPPORTED, "no footprint map for this source: %s", why);
     if (eps) *eps = TRC_FP_EPS_REL * half;
     if (n == 0) return TRC_OK;
-    float *d[2] = {nullptr, nullptr};
-    int st = TRC_OK;
-    do {
-        if ((st = dev_alloc(&d[0], (size_t)n)) || (st = dev_alloc(&d[1], (size_t)n))) break;
-        long long grid = (n + 255) / 256;
-        if (grid > 8192) grid = 8192;
-        hipLaunchKernelGGL(k_source_start32, dim3((unsigned)grid), dim3(256), 0, ctx->stream, F, (long long)n, (unsigned long long)seed,
-                           (unsigned long long)ray_offset, d[0], d[1]);
-        hipError_t se = hipStreamSynchronize(ctx->stream);
-        if (se != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "k_source_start32 failed: %s", hipGetErrorString(se)); break; }
-        if (hipMemcpy(lx, d[0], (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(ly, d[1], (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
-            st = trc_fail(TRC_ERR_DEVICE, "memcpy failed");
-    } while (0);
-    dev_free(d[0]); dev_free(d[1]);
-    return st;
+    DevBuf<float> d[2];
+    TRC_TRY(d[0].alloc((size_t)n));
+    TRC_TRY(d[1].alloc((size_t)n));
+    long long grid = (n + 255) / 256;
+    if (grid > 8192) grid = 8192;
+    hipLaunchKernelGGL(k_source_start32, dim3((unsigned)grid), dim3(256), 0, ctx->stream, F, (long long)n, (unsigned long long)seed,
+                       (unsigned long long)ray_offset, d[0].get(), d[1].get());
+    hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_source_start32 failed: %s", hipGetErrorString(se));
+    TRC_TRY(dev_download(lx, d[0].get(), (size_t)n));
+    return dev_download(ly, d[1].get(), (size_t)n);
 }
 
 extern "C" int trc_source_generate(trc_ctx *ctx, const trc_source_desc *src, int64_t n, uint64_t seed,
@@ -2583,36 +2598,32 @@ extern "C" int trc_source_generate(trc_ctx *ctx, const trc_source_desc *src, int
     if (!out->e) return trc_fail(TRC_ERR_INVALID, "trc_source_generate: energy column required");
     HIP_TRY(hipSetDevice(ctx->device));
     if (n == 0) return TRC_OK;
-    trc_source_desc *d_src = nullptr;
-    double *d[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint64_t *d_rid = nullptr;
-    int st = TRC_OK;
-    do {
-        if ((st = upload_source(src, &d_src))) break;
-        double *host[7] = {out->x, out->y, out->z, out->dx, out->dy, out->dz, out->e};
-        if (out->on_device) { for (int i = 0; i < 7; ++i) d[i] = host[i]; d_rid = out->rid; }
-        else {
-            for (int i = 0; i < 7 && st == TRC_OK; ++i) st = dev_alloc(&d[i], (size_t)n);
-            if (st == TRC_OK && out->rid) st = dev_alloc(&d_rid, (size_t)n);
-            if (st) break;
-        }
-        long long grid = (n + 255) / 256;
-        if (grid > 8192) grid = 8192;
-        hipLaunchKernelGGL(k_source_generate, dim3((unsigned)grid), dim3(256), 0, ctx->stream, d_src, (long long)n,
-                           (unsigned long long)seed, (unsigned long long)ray_offset, d[0], d[1], d[2], d[3], d[4], d[5],
-                           d[6], d_rid);
-        hipError_t se = hipStreamSynchronize(ctx->stream);
-        if (se != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "k_source_generate failed: %s", hipGetErrorString(se)); break; }
-        if (!out->on_device) {
-            for (int i = 0; i < 7; ++i)
-                if (hipMemcpy(host[i], d[i], (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-            if (st == TRC_OK && out->rid && hipMemcpy(out->rid, d_rid, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess)
-                st = trc_fail(TRC_ERR_DEVICE, "memcpy failed");
-        }
-    } while (0);
-    dev_free(d_src);
-    if (!out->on_device) { for (int i = 0; i < 7; ++i) dev_free(d[i]); dev_free(d_rid); }
-    return st;
+    DevBuf<trc_source_desc> d_src;
+    TRC_TRY(upload_source(src, d_src));
+    // the kernel writes the caller's columns when they are on the device, else copies held in `own`
+    double *host[7] = {out->x, out->y, out->z, out->dx, out->dy, out->dz, out->e};
+    double *d[7];
+    uint64_t *d_rid = out->rid;
+    DevBuf<double> own[7];
+    DevBuf<uint64_t> own_rid;
+    for (int i = 0; i < 7; ++i) d[i] = host[i];
+    if (!out->on_device) {
+        for (int i = 0; i < 7; ++i) { TRC_TRY(own[i].alloc((size_t)n)); d[i] = own[i].get(); }
+        if (out->rid) TRC_TRY(own_rid.alloc((size_t)n));
+        d_rid = own_rid.get();
+    }
+    long long grid = (n + 255) / 256;
+    if (grid > 8192) grid = 8192;
+    hipLaunchKernelGGL(k_source_generate, dim3((unsigned)grid), dim3(256), 0, ctx->stream, d_src.get(), (long long)n,
+                       (unsigned long long)seed, (unsigned long long)ray_offset, d[0], d[1], d[2], d[3], d[4], d[5],
+                       d[6], d_rid);
+    hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_source_generate failed: %s", hipGetErrorString(se));
+    if (!out->on_device) {
+        for (int i = 0; i < 7; ++i) TRC_TRY(dev_download(host[i], d[i], (size_t)n));
+        if (out->rid) TRC_TRY(dev_download(out->rid, d_rid, (size_t)n));
+    }
+    return TRC_OK;
 }
 
 // ================================================================================================
@@ -2671,18 +2682,14 @@ static bool spectrum_given(const trc_source_spectrum *sp) { return sp && sp->kin
 static int spectrum_fill(trc_ctx *ctx, const trc_source_spectrum *sp, const std::vector<double> &tab, int64_t n, uint64_t seed,
                          uint64_t ray_offset, double *wl, double *ref) {
     if (n == 0 || (!wl && !ref)) return TRC_OK;
-    double *d_tab = nullptr;
+    DevBuf<double> d_tab;
     const int n_tab = sp->kind == TRC_SPECTRUM_TABLE ? sp->n : 0;
-    if (n_tab) {
-        TRC_TRY(dev_alloc(&d_tab, tab.size()));
-        if (hipMemcpy(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { dev_free(d_tab); return trc_fail(TRC_ERR_DEVICE, "spectrum upload failed"); }
-    }
+    if (n_tab) TRC_TRY(dev_upload(d_tab, tab.data(), tab.size(), "spectrum upload failed"));
     long long grid = (n + 255) / 256;
     if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(k_source_spectrum, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const double *)d_tab, n_tab, sp->kind,
+    hipLaunchKernelGGL(k_source_spectrum, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const double *)d_tab.get(), n_tab, sp->kind,
                        sp->wavelength, sp->ref_index, (long long)n, (unsigned long long)seed, (unsigned long long)ray_offset, wl, ref);
     hipError_t se = hipStreamSynchronize(ctx->stream);
-    dev_free(d_tab);
     if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_source_spectrum failed: %s", hipGetErrorString(se));
     return TRC_OK;
 }
@@ -2696,17 +2703,12 @@ extern "C" int trc_source_generate_x(trc_ctx *ctx, const trc_source_desc *src, c
     TRC_TRY(trc_source_generate(ctx, src, n, seed, ray_offset, out));
     if (n == 0 || (!out->wavelength && !out->ref_index)) return TRC_OK;
     if (out->on_device) return spectrum_fill(ctx, spec, tab, n, seed, ray_offset, out->wavelength, out->ref_index);
-    double *d[2] = {nullptr, nullptr};
+    DevBuf<double> d[2];
     double *host[2] = {out->wavelength, out->ref_index};
-    int st = TRC_OK;
-    do {
-        for (int i = 0; i < 2 && st == TRC_OK; ++i) if (host[i]) st = dev_alloc(&d[i], (size_t)n);
-        if (st || (st = spectrum_fill(ctx, spec, tab, n, seed, ray_offset, d[0], d[1]))) break;
-        for (int i = 0; i < 2; ++i)
-            if (host[i] && hipMemcpy(host[i], d[i], (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-    } while (0);
-    dev_free(d[0]); dev_free(d[1]);
-    return st;
+    for (int i = 0; i < 2; ++i) if (host[i]) TRC_TRY(d[i].alloc((size_t)n));
+    TRC_TRY(spectrum_fill(ctx, spec, tab, n, seed, ray_offset, d[0].get(), d[1].get()));
+    for (int i = 0; i < 2; ++i) if (host[i]) TRC_TRY(dev_download(host[i], d[i].get(), (size_t)n));
+    return TRC_OK;
 }
 
 extern "C" int trc_trace_fast(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, int64_t n, int32_t reps,
@@ -2736,14 +2738,13 @@ extern "C" int trc_trace_fast_x(trc_scene *sc, const trc_rays *in, const trc_sou
     std::copy(tab.begin(), tab.end(), packed.begin() + 3);
     HIP_TRY(hipSetDevice(sc->ctx->device));
     if (sc->spec_cap < packed.size()) {
-        dev_free(sc->d_spec_buf);
         sc->spec_cap = 0;
-        TRC_TRY(dev_alloc(&sc->d_spec_buf, (size_t)3 + 3 * TRC_SPECTRUM_MAX_POINTS));     // (room for any table: allocated once)
+        TRC_TRY(sc->d_spec_buf.alloc((size_t)3 + 3 * TRC_SPECTRUM_MAX_POINTS));     // (room for any table: allocated once)
         sc->spec_cap = (size_t)3 + 3 * TRC_SPECTRUM_MAX_POINTS;
     }
     // (the stream is idle between calls: every call ends with a synchronous read of its counters)
-    HIP_TRY(hipMemcpy(sc->d_spec_buf, packed.data(), packed.size() * 8, hipMemcpyHostToDevice));
-    return trace_fast_impl(sc, nullptr, src, sc->d_spec_buf, n, reps, min_energy, seed, ray_offset, flags, last, stats);
+    HIP_TRY(hipMemcpy(sc->d_spec_buf.get(), packed.data(), packed.size() * 8, hipMemcpyHostToDevice));
+    return trace_fast_impl(sc, nullptr, src, sc->d_spec_buf.get(), n, reps, min_energy, seed, ray_offset, flags, last, stats);
 }
 
 extern "C" int trc_trace_ordered_x(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
@@ -2768,85 +2769,26 @@ extern "C" int trc_trace_ordered(trc_scene *sc, const trc_rays *in, const trc_so
 // ================================================================================================
 // C-ABI: ordered engine
 // ================================================================================================
-static void level_free(Level &L) {
-    dev_free(L.slab);
-    L.x = L.y = L.z = L.dx = L.dy = L.dz = L.e = L.ref = L.wl = L.pay = nullptr;
-    L.rid = nullptr; L.parent = nullptr; L.surf = nullptr;
-}
-
 // One allocation per level (a trace of five levels used to cost 65 hipMalloc / hipFree pairs, 2 ms of a 1e5-ray call): eleven
 // 8-byte columns and the surface column, each starting on a 256-byte boundary, then the carried rows (n apart, as the kernels index them).
 static int level_alloc(Level &L, int64_t n, int n_pay) {
-    memset(&L, 0, sizeof(L));
     L.n_total = n; L.n_live = n;
     const size_t m = ((size_t)(n > 0 ? n : 1) + 31) & ~(size_t)31;
     const size_t bytes = m * (11 * 8 + 4) + (n_pay > 0 ? (size_t)n * n_pay * 8 : 0);
-    TRC_TRY(dev_alloc(&L.slab, bytes));
+    TRC_TRY(L.slab.alloc(bytes));
+    char *slab = L.slab.get();
     double **p[9] = {&L.x, &L.y, &L.z, &L.dx, &L.dy, &L.dz, &L.e, &L.ref, &L.wl};
-    for (int i = 0; i < 9; ++i) *p[i] = (double *)(L.slab + (size_t)i * m * 8);
-    L.rid = (uint64_t *)(L.slab + 9 * m * 8);
-    L.parent = (int64_t *)(L.slab + 10 * m * 8);
-    L.surf = (int32_t *)(L.slab + 11 * m * 8);
-    if (n_pay > 0) L.pay = (double *)(L.slab + 11 * m * 8 + m * 4);
+    for (int i = 0; i < 9; ++i) *p[i] = (double *)(slab + (size_t)i * m * 8);
+    L.rid = (uint64_t *)(slab + 9 * m * 8);
+    L.parent = (int64_t *)(slab + 10 * m * 8);
+    L.surf = (int32_t *)(slab + 11 * m * 8);
+    L.pay = n_pay > 0 ? (double *)(slab + 11 * m * 8 + m * 4) : nullptr;
     return TRC_OK;
-}
-
-// Scratch of the bounce loop: allocated for the first (usually the largest) bounce and kept; a bounce that needs more -- refractive
-// surfaces can double a level -- gets a new set.
-#define ORD_SCRATCH_KEEP ((size_t)1 << 26)
-struct OrdScratch {
-    double *o[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint64_t *orid = nullptr;
-    double *opay = nullptr;
-    uint32_t *key = nullptr, *ckey = nullptr, *cslot = nullptr, *skey = nullptr, *sslot = nullptr;
-    unsigned *blk_cnt = nullptr, *blk_cul = nullptr;
-    unsigned long long *blk_off = nullptr, *totals = nullptr;
-    char *sort_tmp = nullptr;
-    size_t cap_slots = 0, sort_bytes = 0;
-    int cap_pay = 0;
-    void release() {
-        for (int i = 0; i < 9; ++i) dev_free(o[i]);
-        dev_free(opay);
-        dev_free(orid); dev_free(key); dev_free(ckey); dev_free(cslot); dev_free(skey); dev_free(sslot);
-        dev_free(blk_cnt); dev_free(blk_cul); dev_free(blk_off); dev_free(totals);
-        dev_free(sort_tmp);
-        cap_slots = 0; sort_bytes = 0; cap_pay = 0;
-    }
-    int ensure(size_t slots, int n_pay) {
-        if (slots <= cap_slots && n_pay <= cap_pay) return TRC_OK;
-        if (slots < cap_slots) slots = cap_slots;
-        release();
-        cap_pay = n_pay;
-        for (int i = 0; i < 9; ++i) TRC_TRY(dev_alloc(&o[i], slots));
-        TRC_TRY(dev_alloc(&orid, slots));
-        if (n_pay > 0) TRC_TRY(dev_alloc(&opay, slots * (size_t)n_pay));
-        TRC_TRY(dev_alloc(&key, slots));
-        TRC_TRY(dev_alloc(&ckey, slots)); TRC_TRY(dev_alloc(&cslot, slots));      // the occupied slots: at most all of them
-        TRC_TRY(dev_alloc(&skey, slots)); TRC_TRY(dev_alloc(&sslot, slots));
-        const size_t nblk = (slots + 255) / 256;
-        TRC_TRY(dev_alloc(&blk_cnt, nblk)); TRC_TRY(dev_alloc(&blk_cul, nblk)); TRC_TRY(dev_alloc(&blk_off, nblk));
-        TRC_TRY(dev_alloc(&totals, 2));
-        cap_slots = slots;
-        return TRC_OK;
-    }
-    int ensure_sort(size_t bytes) {
-        if (bytes <= sort_bytes && sort_tmp) return TRC_OK;
-        dev_free(sort_tmp);
-        sort_bytes = 0;
-        TRC_TRY(dev_alloc(&sort_tmp, bytes));
-        sort_bytes = bytes;
-        return TRC_OK;
-    }
-};
-
-static void scene_free_ord_scratch(trc_scene *sc) {
-    if (sc->ord_scratch) { sc->ord_scratch->release(); delete sc->ord_scratch; sc->ord_scratch = nullptr; }
 }
 
 extern "C" int trc_result_destroy(trc_result *res) {
     if (!res) return TRC_OK;
     (void)hipSetDevice(res->ctx->device);
-    for (auto &L : res->levels) level_free(L);
     delete res;
     return TRC_OK;
 }
@@ -2885,7 +2827,7 @@ static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_sourc
         if (lay.W < 0 || lay.W > 4096 || lay.n_mat < 0 || lay.n_mat > 64) return trc_fail(TRC_ERR_INVALID, "trc_trace_ordered: n_spec or n_mat out of range");
     }
     const int n_pay = lay.rows();
-    trc_result *res = new (std::nothrow) trc_result();
+    std::unique_ptr<trc_result> res(new (std::nothrow) trc_result());
     if (!res) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
     res->ctx = ctx;
     res->lay = lay;
@@ -2893,32 +2835,32 @@ static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_sourc
     memset(&s, 0, sizeof(s));
     // the scratch of the bounce loop stays with the scene (an ordered trace of 1e7 rays allocated and freed 3 GB in twenty blocks
     // beyond the pool's sizes per call: 30 of its 45 ms)
-    if (!sc->ord_scratch) { sc->ord_scratch = new (std::nothrow) OrdScratch(); if (!sc->ord_scratch) return trc_fail(TRC_ERR_NOMEM, "out of host memory"); }
+    if (!sc->ord_scratch) { sc->ord_scratch.reset(new (std::nothrow) OrdScratch()); if (!sc->ord_scratch) return trc_fail(TRC_ERR_NOMEM, "out of host memory"); }
     OrdScratch &sx = *sc->ord_scratch;
-    trc_source_desc *d_src = nullptr;
-    int st = TRC_OK;
-    float total_ms = 0;
-    do {
+    // the call's work; the stats it gathered are handed back whatever its outcome
+    const int st = [&]() -> int {
+        DevBuf<trc_source_desc> d_src;
+        float total_ms = 0;
         // ---- level 0: the source bundle ----
         Level L0;
-        if ((st = level_alloc(L0, n, n_pay))) { level_free(L0); break; }
-        res->levels.push_back(L0);
+        TRC_TRY(level_alloc(L0, n, n_pay));
+        res->levels.push_back(std::move(L0));
         Level &B0 = res->levels.back();
         long long g0 = (n + 255) / 256; if (g0 > 8192) g0 = 8192; if (g0 < 1) g0 = 1;
         if (src) {
-            if ((st = upload_source(src, &d_src))) break;
-            hipLaunchKernelGGL(k_source_generate, dim3((unsigned)g0), dim3(256), 0, ctx->stream, d_src, (long long)n,
+            TRC_TRY(upload_source(src, d_src));
+            hipLaunchKernelGGL(k_source_generate, dim3((unsigned)g0), dim3(256), 0, ctx->stream, d_src.get(), (long long)n,
                                (unsigned long long)seed, (unsigned long long)ray_offset, B0.x, B0.y, B0.z, B0.dx, B0.dy,
                                B0.dz, B0.e, B0.rid);
             if (spec) {     // level 0 carries the wavelengths the source's spectrum gives its rays, and their index
-                if ((st = spectrum_fill(ctx, spec, *spec_tab, n, seed, ray_offset, B0.wl, B0.ref))) break;
+                TRC_TRY(spectrum_fill(ctx, spec, *spec_tab, n, seed, ray_offset, B0.wl, B0.ref));
             } else {
                 hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)g0), dim3(256), 0, ctx->stream, B0.ref, (long long)n, 1.0);
                 hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)g0), dim3(256), 0, ctx->stream, B0.wl, (long long)n, 0.0);
             }
         } else {
-            if ((st = check_rays(in, n, "trc_trace_ordered"))) break;
-            if (!in->e) { st = trc_fail(TRC_ERR_INVALID, "ray energies are required"); break; }
+            TRC_TRY(check_rays(in, n, "trc_trace_ordered"));
+            if (!in->e) return trc_fail(TRC_ERR_INVALID, "ray energies are required");
             hipMemcpyKind kind = in->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
             const double *hs[7] = {in->x, in->y, in->z, in->dx, in->dy, in->dz, in->e};
             double *ds[7] = {B0.x, B0.y, B0.z, B0.dx, B0.dy, B0.dz, B0.e};
@@ -2941,20 +2883,20 @@ static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_sourc
                     if (b.rows > 0 && hipMemcpy2D(B0.pay + (size_t)b.r0 * n, (size_t)n * 8, b.src, (size_t)in->n * 8, (size_t)n * 8, (size_t)b.rows, kind) != hipSuccess)
                         bad = true;
             }
-            if (bad) { st = trc_fail(TRC_ERR_DEVICE, "bundle upload failed"); break; }
+            if (bad) return trc_fail(TRC_ERR_DEVICE, "bundle upload failed");
         }
         if (n > 0) {
             (void)hipMemsetAsync(B0.parent, 0, (size_t)n * 8, ctx->stream);
             (void)hipMemsetAsync(B0.surf, 0xFF, (size_t)n * 4, ctx->stream);
         }
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "level 0 setup failed"); break; }
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "level 0 setup failed");
 
         // ---- bounce loop ----
         int64_t n_cur = n;
         for (int it = 0; it < reps && n_cur > 0; ++it) {
-            const Level cur = res->levels.back();
+            const Level &cur = res->levels.back();
             const int64_t slots = 2 * n_cur;
-            if ((st = sx.ensure((size_t)slots, n_pay))) break;
+            TRC_TRY(sx.ensure((size_t)slots, n_pay));
             const long long nblk = (slots + 255) / 256;
 
             OrdParams P;
@@ -2963,9 +2905,9 @@ static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_sourc
             P.x = cur.x; P.y = cur.y; P.z = cur.z; P.dx = cur.dx; P.dy = cur.dy; P.dz = cur.dz; P.e = cur.e;
             P.ref = cur.ref; P.wl = cur.wl; P.rid = cur.rid;
             P.n = n_cur; P.event = it + 1; P.flags = flags; P.min_energy = min_energy; P.seed = seed;
-            P.ox = sx.o[0]; P.oy = sx.o[1]; P.oz = sx.o[2]; P.odx = sx.o[3]; P.ody = sx.o[4]; P.odz = sx.o[5];
-            P.oe = sx.o[6]; P.oref = sx.o[7]; P.owl = sx.o[8]; P.orid = sx.orid; P.key = sx.key;
-            P.pay = cur.pay; P.pay_stride = cur.n_total; P.opay = sx.opay; P.lay = lay;
+            P.ox = sx.o[0].get(); P.oy = sx.o[1].get(); P.oz = sx.o[2].get(); P.odx = sx.o[3].get(); P.ody = sx.o[4].get(); P.odz = sx.o[5].get();
+            P.oe = sx.o[6].get(); P.oref = sx.o[7].get(); P.owl = sx.o[8].get(); P.orid = sx.orid.get(); P.key = sx.key.get();
+            P.pay = cur.pay; P.pay_stride = cur.n_total; P.opay = sx.opay.get(); P.lay = lay;
 
             (void)hipEventRecord(ctx->ev0, ctx->stream);
             {
@@ -2976,15 +2918,15 @@ static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_sourc
                 else if (fast) hipLaunchKernelGGL(k_ord_bounce<1>, dim3((unsigned)((n_cur + 255) / 256)), dim3(256), 0, ctx->stream, P);
                 else hipLaunchKernelGGL(k_ord_bounce<0>, dim3((unsigned)((n_cur + 255) / 256)), dim3(256), 0, ctx->stream, P);
             }
-            hipLaunchKernelGGL(k_compact_count, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, sx.key, (long long)slots,
-                               sx.blk_cnt, sx.blk_cul);
-            hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, ctx->stream, sx.blk_cnt, sx.blk_cul, nblk, sx.blk_off,
-                               sx.totals);
+            hipLaunchKernelGGL(k_compact_count, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, sx.key.get(), (long long)slots,
+                               sx.blk_cnt.get(), sx.blk_cul.get());
+            hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, ctx->stream, sx.blk_cnt.get(), sx.blk_cul.get(), nblk, sx.blk_off.get(),
+                               sx.totals.get());
             (void)hipEventRecord(ctx->ev1, ctx->stream);
             unsigned long long totals[2];
-            hipError_t ce = hipMemcpyAsync(totals, sx.totals, sizeof(totals), hipMemcpyDeviceToHost, ctx->stream);
+            hipError_t ce = hipMemcpyAsync(totals, sx.totals.get(), sizeof(totals), hipMemcpyDeviceToHost, ctx->stream);
             hipError_t se = hipStreamSynchronize(ctx->stream);
-            if (ce != hipSuccess || se != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "bounce %d failed: %s", it, hipGetErrorString(se != hipSuccess ? se : ce)); break; }
+            if (ce != hipSuccess || se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "bounce %d failed: %s", it, hipGetErrorString(se != hipSuccess ? se : ce));
             float ms = 0; (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); total_ms += ms;
             s.launches += 3;
             s.segments += n_cur;
@@ -2992,35 +2934,35 @@ static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_sourc
             const int64_t m = (int64_t)totals[0], n_culled = (int64_t)totals[1];
             // hits = rays that produced at least one child: count child-0 slots == slots < n_cur occupied; cheap bound: m minus second children
             if (m == 0) { n_cur = 0; break; }   // "Ray bundle depleted": nothing recorded (tracer_engine.py:271, :277)
-            hipLaunchKernelGGL(k_compact_scatter, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, sx.key, (long long)slots,
-                               sx.blk_off, sx.ckey, sx.cslot);
+            hipLaunchKernelGGL(k_compact_scatter, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, sx.key.get(), (long long)slots,
+                               sx.blk_off.get(), sx.ckey.get(), sx.cslot.get());
             // stable sort by (culled, surface, block); slot order (= parent order) is kept inside a key
             size_t tmp_bytes = 0;
-            hipError_t re = rocprim::radix_sort_pairs(nullptr, tmp_bytes, sx.ckey, sx.skey, sx.cslot, sx.sslot, (size_t)m, 0, 31, ctx->stream);
-            if (re != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "radix_sort_pairs(size query) failed: %s", hipGetErrorString(re)); break; }
-            if ((st = sx.ensure_sort(tmp_bytes))) break;
-            re = rocprim::radix_sort_pairs(sx.sort_tmp, tmp_bytes, sx.ckey, sx.skey, sx.cslot, sx.sslot, (size_t)m, 0, 31, ctx->stream);
-            if (re != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "radix_sort_pairs failed: %s", hipGetErrorString(re)); break; }
-            Level Ln;
-            if ((st = level_alloc(Ln, m, n_pay))) { level_free(Ln); break; }
-            Ln.n_live = m - n_culled;
-            res->levels.push_back(Ln);
+            hipError_t re = rocprim::radix_sort_pairs(nullptr, tmp_bytes, sx.ckey.get(), sx.skey.get(), sx.cslot.get(), sx.sslot.get(), (size_t)m, 0, 31, ctx->stream);
+            if (re != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "radix_sort_pairs(size query) failed: %s", hipGetErrorString(re));
+            TRC_TRY(sx.ensure_sort(tmp_bytes));
+            re = rocprim::radix_sort_pairs(sx.sort_tmp.get(), tmp_bytes, sx.ckey.get(), sx.skey.get(), sx.cslot.get(), sx.sslot.get(), (size_t)m, 0, 31, ctx->stream);
+            if (re != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "radix_sort_pairs failed: %s", hipGetErrorString(re));
+            Level next;
+            TRC_TRY(level_alloc(next, m, n_pay));
+            next.n_live = m - n_culled;
+            res->levels.push_back(std::move(next));
+            const Level &Ln = res->levels.back();
             GatherParams G;
-            G.ox = sx.o[0]; G.oy = sx.o[1]; G.oz = sx.o[2]; G.odx = sx.o[3]; G.ody = sx.o[4]; G.odz = sx.o[5];
-            G.oe = sx.o[6]; G.oref = sx.o[7]; G.owl = sx.o[8]; G.orid = sx.orid; G.skey = sx.skey; G.sslot = sx.sslot;
+            G.ox = sx.o[0].get(); G.oy = sx.o[1].get(); G.oz = sx.o[2].get(); G.odx = sx.o[3].get(); G.ody = sx.o[4].get(); G.odz = sx.o[5].get();
+            G.oe = sx.o[6].get(); G.oref = sx.o[7].get(); G.owl = sx.o[8].get(); G.orid = sx.orid.get(); G.skey = sx.skey.get(); G.sslot = sx.sslot.get();
             G.m = m; G.n_parent = n_cur;
             G.x = Ln.x; G.y = Ln.y; G.z = Ln.z; G.dx = Ln.dx; G.dy = Ln.dy; G.dz = Ln.dz; G.e = Ln.e; G.ref = Ln.ref;
             G.wl = Ln.wl; G.rid = Ln.rid; G.parent = Ln.parent; G.surf = Ln.surf;
-            G.recs = sc->d_recs; G.stride = sc->stride;
-            G.opay = sx.opay; G.pay = Ln.pay; G.n_pay = n_pay;
+            G.recs = sc->d_recs.get(); G.stride = sc->stride;
+            G.opay = sx.opay.get(); G.pay = Ln.pay; G.n_pay = n_pay;
             hipLaunchKernelGGL(k_ord_gather, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, G);
             se = hipStreamSynchronize(ctx->stream);
-            if (se != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "ordering of bounce %d failed: %s", it, hipGetErrorString(se)); break; }
+            if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "ordering of bounce %d failed: %s", it, hipGetErrorString(se));
             s.launches += 3;
             s.hits += m;
             n_cur = Ln.n_live;
         }
-        if (st) break;
         s.rays_left = n_cur;
         s.kernel_ms = total_ms;
         if (n_cur > 0) {
@@ -3030,12 +2972,12 @@ static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_sourc
             if (hipMemcpy(eh.data(), LL.e, (size_t)n_cur * 8, hipMemcpyDeviceToHost) == hipSuccess)
                 for (double v : eh) s.energy_left += v;
         }
-    } while (0);
-    if (sx.cap_slots > ORD_SCRATCH_KEEP) sx.release();      // (beyond 2^26 slots -- 10 GB -- the scratch goes back after the call)
-    dev_free(d_src);
+        return TRC_OK;
+    }();
+    if (sx.cap_slots > ORD_SCRATCH_KEEP) sx = OrdScratch();      // (beyond 2^26 slots -- 10 GB -- the scratch goes back after the call)
     if (stats) *stats = s;
-    if (st != TRC_OK) { trc_result_destroy(res); return st; }
-    *out = res;
+    if (st != TRC_OK) return st;
+    *out = res.release();
     return TRC_OK;
 }
 
@@ -3166,76 +3108,59 @@ extern "C" int trc_kdtree_traversal(trc_ctx *ctx, const trc_kdtree_desc *kd, int
     for (int i = 0; i < kd->n_always; ++i)
         if (kd->always_relevant[i] < 0 || kd->always_relevant[i] >= n_surf) return trc_fail(TRC_ERR_INVALID, "always-relevant surface out of range");
     HIP_TRY(hipSetDevice(ctx->device));
-    int32_t *d_i32[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    double *d_split = nullptr, *d_r[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint8_t *d_rel = nullptr;
-    int *d_flags = nullptr;
-    int st = TRC_OK;
+    DevBuf<int32_t> d_i32[5];
+    DevBuf<double> d_split, d_r[6];
+    DevBuf<uint8_t> d_rel;
+    DevBuf<int> d_flags;
     int any = 0;
-    do {
-        const int32_t *hs[5] = {kd->flag, kd->child, kd->leaf_off, kd->leaf_cnt, kd->leaf_surfs};
-        const size_t cnt[5] = {(size_t)kd->n_nodes, (size_t)kd->n_nodes, (size_t)kd->n_nodes, (size_t)kd->n_nodes, (size_t)std::max(kd->n_leaf_surfs, 1)};
-        for (int i = 0; i < 5 && st == TRC_OK; ++i) {
-            if ((st = dev_alloc(&d_i32[i], cnt[i]))) break;
-            if (hs[i] && (i < 4 || kd->n_leaf_surfs > 0) && hipMemcpy(d_i32[i], hs[i], cnt[i] * 4, hipMemcpyHostToDevice) != hipSuccess) st = trc_fail(TRC_ERR_DEVICE, "memcpy failed");
-        }
-        if (st) break;
-        if ((st = dev_alloc(&d_split, (size_t)kd->n_nodes))) break;
-        if (hipMemcpy(d_split, kd->split, (size_t)kd->n_nodes * 8, hipMemcpyHostToDevice) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        if ((st = dev_alloc(&d_flags, 2))) break;
-        (void)hipMemset(d_flags, 0, 8);
-        const size_t nn = (size_t)std::max<int64_t>(n, 1);
-        if ((st = dev_alloc(&d_rel, (size_t)n_surf * nn))) break;
-        (void)hipMemset(d_rel, 0, (size_t)n_surf * nn);
-        for (int i = 0; i < kd->n_always; ++i) (void)hipMemset(d_rel + (size_t)kd->always_relevant[i] * nn, 1, nn);        // :236
-        if (n > 0) {
-            const double *src[6] = {rays->x, rays->y, rays->z, rays->dx, rays->dy, rays->dz};
-            for (int i = 0; i < 6 && st == TRC_OK; ++i) {
-                if ((st = dev_alloc(&d_r[i], (size_t)n))) break;
-                if (hipMemcpy(d_r[i], src[i], (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) st = trc_fail(TRC_ERR_DEVICE, "memcpy failed");
-            }
-            if (st) break;
-            KdTravParams P;
-            P.flag = d_i32[0]; P.child = d_i32[1]; P.leaf_off = d_i32[2]; P.leaf_cnt = d_i32[3]; P.leaf_surfs = d_i32[4]; P.split = d_split;
-            for (int i = 0; i < 3; ++i) { P.lo[i] = kd->bounds[i]; P.hi[i] = kd->bounds[3 + i]; }
-            P.x = d_r[0]; P.y = d_r[1]; P.z = d_r[2]; P.dx = d_r[3]; P.dy = d_r[4]; P.dz = d_r[5];
-            P.n = n; P.rel = d_rel; P.flags = d_flags;
-            hipLaunchKernelGGL(k_kd_traversal, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, P);
-            hipError_t se = hipStreamSynchronize(ctx->stream);
-            if (se != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "k_kd_traversal failed: %s", hipGetErrorString(se)); break; }
-            int fl[2] = {0, 0};
-            if (hipMemcpy(fl, d_flags, 8, hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-            if (fl[1]) { st = trc_fail(TRC_ERR_CAPACITY, "a ray had more than %d pending nodes: the tree is deeper than the traversal's stack", KD_TRAV_STACK); break; }
-            any = fl[0];
-            if (hipMemcpy(relevancy, d_rel, (size_t)n_surf * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        }
-        // `if inters.any() or self.always_relevant.any()` (:238): any() of the array of surface indices -- a non-zero index
-        for (int i = 0; i < kd->n_always; ++i) if (kd->always_relevant[i] != 0) any = 1;
-    } while (0);
-    for (int i = 0; i < 5; ++i) dev_free(d_i32[i]);
-    for (int i = 0; i < 6; ++i) dev_free(d_r[i]);
-    dev_free(d_split); dev_free(d_rel); dev_free(d_flags);
-    if (st == TRC_OK && any_inter) *any_inter = any;
-    return st;
+    const int32_t *hs[5] = {kd->flag, kd->child, kd->leaf_off, kd->leaf_cnt, kd->leaf_surfs};
+    const size_t cnt[5] = {(size_t)kd->n_nodes, (size_t)kd->n_nodes, (size_t)kd->n_nodes, (size_t)kd->n_nodes, (size_t)kd->n_leaf_surfs};
+    for (int i = 0; i < 5; ++i) TRC_TRY(dev_upload(d_i32[i], hs[i], cnt[i], "memcpy failed"));
+    TRC_TRY(dev_upload(d_split, kd->split, (size_t)kd->n_nodes, "memcpy failed"));
+    TRC_TRY(d_flags.alloc(2));
+    (void)hipMemset(d_flags.get(), 0, 8);
+    const size_t nn = (size_t)std::max<int64_t>(n, 1);
+    TRC_TRY(d_rel.alloc((size_t)n_surf * nn));
+    (void)hipMemset(d_rel.get(), 0, (size_t)n_surf * nn);
+    for (int i = 0; i < kd->n_always; ++i) (void)hipMemset(d_rel.get() + (size_t)kd->always_relevant[i] * nn, 1, nn);        // :236
+    if (n > 0) {
+        const double *src[6] = {rays->x, rays->y, rays->z, rays->dx, rays->dy, rays->dz};
+        for (int i = 0; i < 6; ++i) TRC_TRY(dev_upload(d_r[i], src[i], (size_t)n, "memcpy failed"));
+        KdTravParams P;
+        P.flag = d_i32[0].get(); P.child = d_i32[1].get(); P.leaf_off = d_i32[2].get(); P.leaf_cnt = d_i32[3].get(); P.leaf_surfs = d_i32[4].get();
+        P.split = d_split.get();
+        for (int i = 0; i < 3; ++i) { P.lo[i] = kd->bounds[i]; P.hi[i] = kd->bounds[3 + i]; }
+        P.x = d_r[0].get(); P.y = d_r[1].get(); P.z = d_r[2].get(); P.dx = d_r[3].get(); P.dy = d_r[4].get(); P.dz = d_r[5].get();
+        P.n = n; P.rel = d_rel.get(); P.flags = d_flags.get();
+        hipLaunchKernelGGL(k_kd_traversal, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, P);
+        hipError_t se = hipStreamSynchronize(ctx->stream);
+        if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_kd_traversal failed: %s", hipGetErrorString(se));
+        int fl[2] = {0, 0};
+        TRC_TRY(dev_download(fl, d_flags.get(), 2));
+        if (fl[1]) return trc_fail(TRC_ERR_CAPACITY, "a ray had more than %d pending nodes: the tree is deeper than the traversal's stack", KD_TRAV_STACK);
+        any = fl[0];
+        TRC_TRY(dev_download(relevancy, d_rel.get(), (size_t)n_surf * (size_t)n));
+    }
+    // `if inters.any() or self.always_relevant.any()` (:238): any() of the array of surface indices -- a non-zero index
+    for (int i = 0; i < kd->n_always; ++i) if (kd->always_relevant[i] != 0) any = 1;
+    if (any_inter) *any_inter = any;
+    return TRC_OK;
 }
 
 // ================================================================================================
 // C-ABI: per-surface protocol
 // ================================================================================================
-static int upload_record(const trc_surface_desc *surf, int32_t n_extra, const double *extra, double **d_rec, double **d_opt,
-                         double **d_extra) {
+// one surface on the device: its record, its optics parameters (unless d_opt is NULL) and its extra values
+static int upload_record(const trc_surface_desc *surf, int32_t n_extra, const double *extra, DevBuf<double> &d_rec, DevBuf<double> *d_opt,
+                         DevBuf<double> &d_extra) {
     TRC_TRY(validate_surface(*surf, 0, n_extra));
     int stride = TRC_REC_HDR + 16;
     std::vector<double> rec(stride);
     pack_record(*surf, rec.data(), stride);
-    TRC_TRY(dev_alloc(d_rec, (size_t)stride));
-    HIP_TRY(hipMemcpy(*d_rec, rec.data(), stride * sizeof(double), hipMemcpyHostToDevice));
-    if (d_opt) {
-        TRC_TRY(dev_alloc(d_opt, 8));
-        HIP_TRY(hipMemcpy(*d_opt, surf->opt, 8 * sizeof(double), hipMemcpyHostToDevice));
-    }
-    TRC_TRY(dev_alloc(d_extra, (size_t)(n_extra > 0 ? n_extra : 1)));
-    if (n_extra > 0 && extra) HIP_TRY(hipMemcpy(*d_extra, extra, (size_t)n_extra * sizeof(double), hipMemcpyHostToDevice));
+    TRC_TRY(dev_upload(d_rec, rec.data(), (size_t)stride));
+    if (d_opt) TRC_TRY(dev_upload(*d_opt, surf->opt, 8));
+    TRC_TRY(d_extra.alloc((size_t)(n_extra > 0 ? n_extra : 1)));
+    if (n_extra > 0 && extra) HIP_TRY(hipMemcpy(d_extra.get(), extra, (size_t)n_extra * sizeof(double), hipMemcpyHostToDevice));
     return TRC_OK;
 }
 
@@ -3247,31 +3172,23 @@ extern "C" int trc_gm_find_intersections(trc_ctx *ctx, const trc_surface_desc *s
     TRC_TRY(check_rays(rays, n, "trc_gm_find_intersections"));
     HIP_TRY(hipSetDevice(ctx->device));
     if (n == 0) return TRC_OK;
-    double *d_rec = nullptr, *d_extra = nullptr, *d_t = nullptr, *d_h[3] = {nullptr, nullptr, nullptr};
+    DevBuf<double> d_rec, d_extra, d_t, d_h[3];
     DevRays dr;
-    int st = TRC_OK;
-    do {
-        if ((st = upload_record(surf, n_extra, extra, &d_rec, nullptr, &d_extra))) break;
-        if ((st = stage_rays(rays, n, false, &dr))) break;
-        if ((st = dev_alloc(&d_t, (size_t)n))) break;
-        const bool want_h = hx && hy && hz;
-        if (want_h) for (int i = 0; i < 3 && st == TRC_OK; ++i) st = dev_alloc(&d_h[i], (size_t)n);
-        if (st) break;
-        hipLaunchKernelGGL(k_gm_intersect, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_rec, d_extra,
-                           (long long)n, dr.x, dr.y, dr.z, dr.dx, dr.dy, dr.dz, d_t, d_h[0], d_h[1], d_h[2]);
-        hipError_t se = hipStreamSynchronize(ctx->stream);
-        if (se != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "k_gm_intersect failed: %s", hipGetErrorString(se)); break; }
-        if (hipMemcpy(t_out, d_t, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        if (want_h) {
-            double *dst[3] = {hx, hy, hz};
-            for (int i = 0; i < 3; ++i)
-                if (hipMemcpy(dst[i], d_h[i], (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        }
-    } while (0);
-    dr.release();
-    dev_free(d_rec); dev_free(d_extra); dev_free(d_t);
-    for (int i = 0; i < 3; ++i) dev_free(d_h[i]);
-    return st;
+    TRC_TRY(upload_record(surf, n_extra, extra, d_rec, nullptr, d_extra));
+    TRC_TRY(stage_rays(rays, n, false, &dr));
+    TRC_TRY(d_t.alloc((size_t)n));
+    const bool want_h = hx && hy && hz;
+    if (want_h) for (auto &col : d_h) TRC_TRY(col.alloc((size_t)n));
+    hipLaunchKernelGGL(k_gm_intersect, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_rec.get(), d_extra.get(),
+                       (long long)n, dr.x, dr.y, dr.z, dr.dx, dr.dy, dr.dz, d_t.get(), d_h[0].get(), d_h[1].get(), d_h[2].get());
+    hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_gm_intersect failed: %s", hipGetErrorString(se));
+    TRC_TRY(dev_download(t_out, d_t.get(), (size_t)n));
+    if (want_h) {
+        double *dst[3] = {hx, hy, hz};
+        for (int i = 0; i < 3; ++i) TRC_TRY(dev_download(dst[i], d_h[i].get(), (size_t)n));
+    }
+    return TRC_OK;
 }
 
 extern "C" int trc_gm_get_normals(trc_ctx *ctx, const trc_surface_desc *surf, int64_t n, const double *hx, const double *hy,
@@ -3281,30 +3198,22 @@ extern "C" int trc_gm_get_normals(trc_ctx *ctx, const trc_surface_desc *surf, in
     if (n == 0) return TRC_OK;
     if (!hx || !hy || !hz || !dx || !dy || !dz || !nx || !ny || !nz) return trc_fail(TRC_ERR_INVALID, "trc_gm_get_normals: NULL array");
     HIP_TRY(hipSetDevice(ctx->device));
-    double *d_rec = nullptr, *d_extra = nullptr, *d[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    DevBuf<double> d_rec, d_extra, d[9];
     const double *src[6] = {hx, hy, hz, dx, dy, dz};
-    int st = TRC_OK;
-    do {
-        trc_surface_desc tmp = *surf;
-        tmp.optics_kind = TRC_OPT_TRANSPARENT;   // normals do not depend on the optics
-        if (tmp.gm_kind == TRC_GM_RECT_PERFORATED) { tmp.gm_kind = TRC_GM_RECT; }
-        if ((st = upload_record(&tmp, 0, nullptr, &d_rec, nullptr, &d_extra))) break;
-        for (int i = 0; i < 9 && st == TRC_OK; ++i) st = dev_alloc(&d[i], (size_t)n);
-        if (st) break;
-        for (int i = 0; i < 6; ++i)
-            if (hipMemcpy(d[i], src[i], (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        if (st) break;
-        hipLaunchKernelGGL(k_gm_normals, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_rec, (long long)n, d[0],
-                           d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8]);
-        hipError_t se = hipStreamSynchronize(ctx->stream);
-        if (se != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "k_gm_normals failed: %s", hipGetErrorString(se)); break; }
-        double *dst[3] = {nx, ny, nz};
-        for (int i = 0; i < 3; ++i)
-            if (hipMemcpy(dst[i], d[6 + i], (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-    } while (0);
-    dev_free(d_rec); dev_free(d_extra);
-    for (int i = 0; i < 9; ++i) dev_free(d[i]);
-    return st;
+    trc_surface_desc tmp = *surf;
+    tmp.optics_kind = TRC_OPT_TRANSPARENT;   // normals do not depend on the optics
+    if (tmp.gm_kind == TRC_GM_RECT_PERFORATED) { tmp.gm_kind = TRC_GM_RECT; }
+    TRC_TRY(upload_record(&tmp, 0, nullptr, d_rec, nullptr, d_extra));
+    for (auto &col : d) TRC_TRY(col.alloc((size_t)n));
+    for (int i = 0; i < 6; ++i)
+        if (hipMemcpy(d[i].get(), src[i], (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
+    hipLaunchKernelGGL(k_gm_normals, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_rec.get(), (long long)n, d[0].get(),
+                       d[1].get(), d[2].get(), d[3].get(), d[4].get(), d[5].get(), d[6].get(), d[7].get(), d[8].get());
+    hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_gm_normals failed: %s", hipGetErrorString(se));
+    double *dst[3] = {nx, ny, nz};
+    for (int i = 0; i < 3; ++i) TRC_TRY(dev_download(dst[i], d[6 + i].get(), (size_t)n));
+    return TRC_OK;
 }
 
 __global__ __launch_bounds__(256) void k_fresnel_attenuating(long long n, double n1, const double *m_re, const double *m_im,
@@ -3319,25 +3228,18 @@ extern "C" int trc_optics_fresnel_attenuating(trc_ctx *ctx, int64_t n, double n1
         return trc_fail(TRC_ERR_INVALID, "trc_optics_fresnel_attenuating: bad arguments");
     if (n == 0) return TRC_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    double *d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    DevBuf<double> d[6];
     const double *src[3] = {m_re, m_im, theta1};
     double *dst[3] = {r_p, r_s, theta2};
-    int st = TRC_OK;
-    do {
-        for (int i = 0; i < 6 && st == TRC_OK; ++i) st = dev_alloc(&d[i], (size_t)n);
-        if (st) break;
-        for (int i = 0; i < 3; ++i)
-            if (hipMemcpy(d[i], src[i], (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        if (st) break;
-        hipLaunchKernelGGL(k_fresnel_attenuating, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (long long)n, n1,
-                           d[0], d[1], d[2], d[3], d[4], d[5]);
-        hipError_t se = hipStreamSynchronize(ctx->stream);
-        if (se != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "k_fresnel_attenuating failed: %s", hipGetErrorString(se)); break; }
-        for (int i = 0; i < 3; ++i)
-            if (hipMemcpy(dst[i], d[3 + i], (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-    } while (0);
-    for (int i = 0; i < 6; ++i) dev_free(d[i]);
-    return st;
+    for (auto &col : d) TRC_TRY(col.alloc((size_t)n));
+    for (int i = 0; i < 3; ++i)
+        if (hipMemcpy(d[i].get(), src[i], (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
+    hipLaunchKernelGGL(k_fresnel_attenuating, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (long long)n, n1,
+                       d[0].get(), d[1].get(), d[2].get(), d[3].get(), d[4].get(), d[5].get());
+    hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_fresnel_attenuating failed: %s", hipGetErrorString(se));
+    for (int i = 0; i < 3; ++i) TRC_TRY(dev_download(dst[i], d[3 + i].get(), (size_t)n));
+    return TRC_OK;
 }
 
 extern "C" int trc_optics_apply(trc_ctx *ctx, const trc_surface_desc *surf, int32_t n_extra, const double *extra,
@@ -3353,13 +3255,13 @@ extern "C" int trc_optics_apply(trc_ctx *ctx, const trc_surface_desc *surf, int3
     if (!out->x || !out->y || !out->z || !out->dx || !out->dy || !out->dz || !out->e || !out->parent)
         return trc_fail(TRC_ERR_INVALID, "trc_optics_apply: output needs x..e and parent");
     HIP_TRY(hipSetDevice(ctx->device));
-    double *d_rec = nullptr, *d_opt = nullptr, *d_extra = nullptr;
-    double *d_in[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // dx dy dz e ref wl nx ny nz
-    uint64_t *d_rid = nullptr;
-    double *d_path = nullptr;
-    double *d_out[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    int32_t *d_blk = nullptr;
-    double *d_shift = nullptr;
+    DevBuf<double> d_rec, d_opt, d_extra;
+    DevBuf<double> d_in[9];      // dx dy dz e ref wl nx ny nz
+    DevBuf<uint64_t> d_rid;
+    DevBuf<double> d_path;
+    DevBuf<double> d_out[5];
+    DevBuf<int32_t> d_blk;
+    DevBuf<double> d_shift;
     // complex indices, material rows, spectra
     const int W = (in->spectra && in->spec_wl) ? in->n_spec : 0;
     const int n_mat = in->mat ? (int)in->n_mat : 0;
@@ -3370,106 +3272,86 @@ extern "C" int trc_optics_apply(trc_ctx *ctx, const trc_surface_desc *surf, int3
         return trc_fail(TRC_ERR_INVALID, "refraction between tabulated materials: the bundle needs wavelengths and the materials' indices at them (trc_rays.mat), the output ref_index_im");
     if (W > 0 && out->spectra && out->n_spec != W) return trc_fail(TRC_ERR_INVALID, "trc_optics_apply: the output's n_spec differs from the input's");
     const int64_t out_cap = out->n;
-    double *d_im = nullptr, *d_mat = nullptr, *d_swl = nullptr, *d_spec = nullptr, *d_oim = nullptr, *d_ospec = nullptr;
-    int st = TRC_OK;
-    do {
-        if ((st = upload_record(surf, n_extra, extra, &d_rec, &d_opt, &d_extra))) break;
-        if (in->ref_index_im) {
-            if ((st = dev_alloc(&d_im, (size_t)n))) break;
-            if (hipMemcpy(d_im, in->ref_index_im, (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
+    DevBuf<double> d_im, d_mat, d_swl, d_spec, d_oim, d_ospec;
+    TRC_TRY(upload_record(surf, n_extra, extra, d_rec, &d_opt, d_extra));
+    if (in->ref_index_im) TRC_TRY(dev_upload(d_im, in->ref_index_im, (size_t)n, "memcpy failed"));
+    struct { const double *src; int rows; DevBuf<double> &dst; } blk2[3] = {{in->mat, 2 * n_mat, d_mat}, {in->spec_wl, W, d_swl}, {in->spectra, W, d_spec}};
+    for (auto &b : blk2) {
+        if (b.rows <= 0) continue;
+        TRC_TRY(b.dst.alloc((size_t)n * b.rows));
+        if (hipMemcpy2D(b.dst.get(), (size_t)n * 8, b.src, (size_t)in->n * 8, (size_t)n * 8, (size_t)b.rows, hipMemcpyHostToDevice) != hipSuccess)
+            return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
+    }
+    if (out->ref_index_im) TRC_TRY(d_oim.alloc((size_t)(2 * n)));
+    if (W > 0 && out->spectra) TRC_TRY(d_ospec.alloc((size_t)(2 * n) * W));
+    const double *src[9] = {in->dx, in->dy, in->dz, in->e, in->ref_index, in->wavelength, nx, ny, nz};
+    for (int i = 0; i < 9; ++i)
+        if (src[i]) TRC_TRY(dev_upload(d_in[i], src[i], (size_t)n, "memcpy failed"));
+    if (in->x && in->y && in->z) {      // path lengths for the attenuating optics (Absorbant.attenuate, :874-877)
+        std::vector<double> path((size_t)n);
+        for (int64_t i = 0; i < n; ++i) {
+            double ax = hx[i] - in->x[i], ay = hy[i] - in->y[i], az = hz[i] - in->z[i];
+            path[(size_t)i] = std::sqrt(ax * ax + ay * ay + az * az);
         }
-        {
-            struct { const double *src; int rows; double **dst; } blk2[3] = {{in->mat, 2 * n_mat, &d_mat}, {in->spec_wl, W, &d_swl}, {in->spectra, W, &d_spec}};
-            for (auto &b : blk2) {
-                if (b.rows <= 0) continue;
-                if ((st = dev_alloc(b.dst, (size_t)n * b.rows))) break;
-                if (hipMemcpy2D(*b.dst, (size_t)n * 8, b.src, (size_t)in->n * 8, (size_t)n * 8, (size_t)b.rows, hipMemcpyHostToDevice) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-            }
-            if (st) break;
+        TRC_TRY(dev_upload(d_path, path.data(), (size_t)n, "memcpy failed"));
+    }
+    if (in->rid) TRC_TRY(dev_upload(d_rid, in->rid, (size_t)n, "memcpy failed"));
+    for (auto &col : d_out) TRC_TRY(col.alloc((size_t)(2 * n)));
+    TRC_TRY(d_blk.alloc((size_t)(2 * n)));
+    TRC_TRY(d_shift.alloc((size_t)(2 * n)));
+    OpticsParams P;
+    memset(&P, 0, sizeof(P));
+    P.rec = d_rec.get(); P.opt = d_opt.get(); P.extra = d_extra.get(); P.n = n;
+    P.dx = d_in[0].get(); P.dy = d_in[1].get(); P.dz = d_in[2].get(); P.e = d_in[3].get(); P.ref = d_in[4].get(); P.wl = d_in[5].get();
+    P.rid = d_rid.get(); P.ray_offset = 0;
+    P.nx = d_in[6].get(); P.ny = d_in[7].get(); P.nz = d_in[8].get(); P.path = d_path.get();
+    P.seed = seed; P.event = bounce;
+    P.odx = d_out[0].get(); P.ody = d_out[1].get(); P.odz = d_out[2].get(); P.oe = d_out[3].get(); P.oref = d_out[4].get();
+    P.oblk = d_blk.get(); P.oshift = d_shift.get();
+    P.ref_im = d_im.get(); P.mat = d_mat.get(); P.spec_wl = d_swl.get(); P.spec = d_spec.get(); P.n_mat = n_mat; P.W = W;
+    P.o_im = d_oim.get(); P.o_spec = d_ospec.get();
+    hipLaunchKernelGGL(k_optics_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, P);
+    hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_optics_apply failed: %s", hipGetErrorString(se));
+    std::vector<double> h[5];
+    std::vector<int32_t> blk((size_t)(2 * n));
+    for (int i = 0; i < 5; ++i) {
+        h[i].resize((size_t)(2 * n));
+        TRC_TRY(dev_download(h[i].data(), d_out[i].get(), (size_t)(2 * n)));
+    }
+    TRC_TRY(dev_download(blk.data(), d_blk.get(), (size_t)(2 * n)));
+    std::vector<double> h_shift((size_t)(2 * n));
+    TRC_TRY(dev_download(h_shift.data(), d_shift.get(), (size_t)(2 * n)));
+    std::vector<double> h_im, h_spec;
+    if (d_oim) {
+        h_im.resize((size_t)(2 * n));
+        TRC_TRY(dev_download(h_im.data(), d_oim.get(), (size_t)(2 * n)));
+    }
+    if (d_ospec) {
+        h_spec.resize((size_t)(2 * n) * W);
+        TRC_TRY(dev_download(h_spec.data(), d_ospec.get(), h_spec.size()));
+    }
+    // reflected block first, then refracted block, each in selector order (optics_callables.py:852-857)
+    int64_t m = 0;
+    for (int b = 0; b < 2; ++b)
+        for (int64_t slot = 0; slot < 2 * n; ++slot) {
+            if (blk[(size_t)slot] != b) continue;
+            int64_t i = slot < n ? slot : slot - n;
+            const double sh = h_shift[(size_t)slot];        // (0 but for a periodic boundary: the ray goes on one period along the normal)
+            out->x[m] = hx[i] + sh * nx[i]; out->y[m] = hy[i] + sh * ny[i]; out->z[m] = hz[i] + sh * nz[i];
+            out->dx[m] = h[0][(size_t)slot]; out->dy[m] = h[1][(size_t)slot]; out->dz[m] = h[2][(size_t)slot];
+            out->e[m] = h[3][(size_t)slot];
+            if (out->ref_index) out->ref_index[m] = h[4][(size_t)slot];
+            if (out->wavelength) out->wavelength[m] = in->wavelength ? in->wavelength[i] : 0.0;
+            if (out->ref_index_im) out->ref_index_im[m] = h_im[(size_t)slot];
+            if (d_ospec)
+                for (int w = 0; w < W; ++w) {
+                    out->spectra[(size_t)w * out_cap + m] = h_spec[(size_t)w * 2 * n + slot];
+                    if (out->spec_wl) out->spec_wl[(size_t)w * out_cap + m] = in->spec_wl[(size_t)w * in->n + i];
+                }
+            out->parent[m] = i;
+            ++m;
         }
-        if (out->ref_index_im && (st = dev_alloc(&d_oim, (size_t)(2 * n)))) break;
-        if (W > 0 && out->spectra && (st = dev_alloc(&d_ospec, (size_t)(2 * n) * W))) break;
-        const double *src[9] = {in->dx, in->dy, in->dz, in->e, in->ref_index, in->wavelength, nx, ny, nz};
-        for (int i = 0; i < 9; ++i) {
-            if (!src[i]) continue;
-            if ((st = dev_alloc(&d_in[i], (size_t)n))) break;
-            if (hipMemcpy(d_in[i], src[i], (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        }
-        if (st) break;
-        if (in->x && in->y && in->z) {      // path lengths for the attenuating optics (Absorbant.attenuate, :874-877)
-            std::vector<double> path((size_t)n);
-            for (int64_t i = 0; i < n; ++i) {
-                double ax = hx[i] - in->x[i], ay = hy[i] - in->y[i], az = hz[i] - in->z[i];
-                path[(size_t)i] = std::sqrt(ax * ax + ay * ay + az * az);
-            }
-            if ((st = dev_alloc(&d_path, (size_t)n))) break;
-            if (hipMemcpy(d_path, path.data(), (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        }
-        if (in->rid) {
-            if ((st = dev_alloc(&d_rid, (size_t)n))) break;
-            if (hipMemcpy(d_rid, in->rid, (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        }
-        for (int i = 0; i < 5 && st == TRC_OK; ++i) st = dev_alloc(&d_out[i], (size_t)(2 * n));
-        if (st == TRC_OK) st = dev_alloc(&d_blk, (size_t)(2 * n));
-        if (st == TRC_OK) st = dev_alloc(&d_shift, (size_t)(2 * n));
-        if (st) break;
-        OpticsParams P;
-        memset(&P, 0, sizeof(P));
-        P.rec = d_rec; P.opt = d_opt; P.extra = d_extra; P.n = n;
-        P.dx = d_in[0]; P.dy = d_in[1]; P.dz = d_in[2]; P.e = d_in[3]; P.ref = d_in[4]; P.wl = d_in[5];
-        P.rid = d_rid; P.ray_offset = 0;
-        P.nx = d_in[6]; P.ny = d_in[7]; P.nz = d_in[8]; P.path = d_path;
-        P.seed = seed; P.event = bounce;
-        P.odx = d_out[0]; P.ody = d_out[1]; P.odz = d_out[2]; P.oe = d_out[3]; P.oref = d_out[4]; P.oblk = d_blk; P.oshift = d_shift;
-        P.ref_im = d_im; P.mat = d_mat; P.spec_wl = d_swl; P.spec = d_spec; P.n_mat = n_mat; P.W = W; P.o_im = d_oim; P.o_spec = d_ospec;
-        hipLaunchKernelGGL(k_optics_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, P);
-        hipError_t se = hipStreamSynchronize(ctx->stream);
-        if (se != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "k_optics_apply failed: %s", hipGetErrorString(se)); break; }
-        std::vector<double> h[5];
-        std::vector<int32_t> blk((size_t)(2 * n));
-        for (int i = 0; i < 5; ++i) {
-            h[i].resize((size_t)(2 * n));
-            if (hipMemcpy(h[i].data(), d_out[i], (size_t)(2 * n) * 8, hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        }
-        if (st) break;
-        if (hipMemcpy(blk.data(), d_blk, (size_t)(2 * n) * 4, hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        std::vector<double> h_shift((size_t)(2 * n));
-        if (hipMemcpy(h_shift.data(), d_shift, (size_t)(2 * n) * 8, hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        std::vector<double> h_im, h_spec;
-        if (d_oim) {
-            h_im.resize((size_t)(2 * n));
-            if (hipMemcpy(h_im.data(), d_oim, (size_t)(2 * n) * 8, hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        }
-        if (d_ospec) {
-            h_spec.resize((size_t)(2 * n) * W);
-            if (hipMemcpy(h_spec.data(), d_ospec, h_spec.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) { st = trc_fail(TRC_ERR_DEVICE, "memcpy failed"); break; }
-        }
-        // reflected block first, then refracted block, each in selector order (optics_callables.py:852-857)
-        int64_t m = 0;
-        for (int b = 0; b < 2; ++b)
-            for (int64_t slot = 0; slot < 2 * n; ++slot) {
-                if (blk[(size_t)slot] != b) continue;
-                int64_t i = slot < n ? slot : slot - n;
-                const double sh = h_shift[(size_t)slot];        // (0 but for a periodic boundary: the ray goes on one period along the normal)
-                out->x[m] = hx[i] + sh * nx[i]; out->y[m] = hy[i] + sh * ny[i]; out->z[m] = hz[i] + sh * nz[i];
-                out->dx[m] = h[0][(size_t)slot]; out->dy[m] = h[1][(size_t)slot]; out->dz[m] = h[2][(size_t)slot];
-                out->e[m] = h[3][(size_t)slot];
-                if (out->ref_index) out->ref_index[m] = h[4][(size_t)slot];
-                if (out->wavelength) out->wavelength[m] = in->wavelength ? in->wavelength[i] : 0.0;
-                if (out->ref_index_im) out->ref_index_im[m] = h_im[(size_t)slot];
-                if (d_ospec)
-                    for (int w = 0; w < W; ++w) {
-                        out->spectra[(size_t)w * out_cap + m] = h_spec[(size_t)w * 2 * n + slot];
-                        if (out->spec_wl) out->spec_wl[(size_t)w * out_cap + m] = in->spec_wl[(size_t)w * in->n + i];
-                    }
-                out->parent[m] = i;
-                ++m;
-            }
-        out->n = m;
-    } while (0);
-    dev_free(d_rec); dev_free(d_opt); dev_free(d_extra); dev_free(d_rid); dev_free(d_blk); dev_free(d_shift); dev_free(d_path);
-    dev_free(d_im); dev_free(d_mat); dev_free(d_swl); dev_free(d_spec); dev_free(d_oim); dev_free(d_ospec);
-    for (int i = 0; i < 9; ++i) dev_free(d_in[i]);
-    for (int i = 0; i < 5; ++i) dev_free(d_out[i]);
-    return st;
+    out->n = m;
+    return TRC_OK;
 }

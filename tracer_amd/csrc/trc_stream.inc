@@ -2208,7 +2208,7 @@ static bool stream_plan(const trc_scene *sc, bool want_accel, const StreamKnobs 
 // (exact tests, tie pass, shading).
 struct StreamSlot {
     StreamWs W;
-    double *spec;                 // spectra of the rays under way (CarryIn.slot_spec), spec_len doubles; spec_on: this call brings spectra
+    DevBuf<double> spec;          // spectra of the rays under way (CarryIn.slot_spec), spec_len doubles; spec_on: this call brings spectra
     long long spec_len;
     bool spec_on;
     hipStream_t stream;
@@ -2248,8 +2248,8 @@ struct StreamEngine {
     double rate_term[STREAM_RATE_BOUNCES], rate_other[STREAM_RATE_BOUNCES];
     double rate_cls[STREAM_RATE_BOUNCES][TRC_CLS_COUNT];   // hits per ray entering bounce b that each shading class took (< 0: not yet)
     uint64_t rate_geom_version;
-    uint32_t *d_fp_mask, *d_fp_coff;
-    uint32_t *d_fp_clist;
+    DevBuf<uint32_t> d_fp_mask, d_fp_coff;
+    DevBuf<uint32_t> d_fp_clist;
 };
 
 // the part of a source descriptor the footprint map depends on (the Buie table enters through p[] / the CSR only via cdf_end,
@@ -2291,19 +2291,16 @@ static int stream_fp_prepare(trc_scene *sc, StreamEngine &E, const trc_source_de
         E.fp_geom_version = sc->geom_version;
         E.fp_valid = true;
         E.fp_hit_rate = 0.0;
-        dev_free(E.d_fp_mask); dev_free(E.d_fp_coff); dev_free(E.d_fp_clist);
+        E.d_fp_mask.reset(); E.d_fp_coff.reset(); E.d_fp_clist.reset();
         if (E.fp->ok) {
-            TRC_TRY(dev_alloc(&E.d_fp_mask, E.fp->mask.size()));
-            TRC_TRY(dev_alloc(&E.d_fp_coff, E.fp->coff.size()));
-            TRC_TRY(dev_alloc(&E.d_fp_clist, E.fp->clist.size()));
-            HIP_TRY(hipMemcpy(E.d_fp_mask, E.fp->mask.data(), E.fp->mask.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(E.d_fp_coff, E.fp->coff.data(), E.fp->coff.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(E.d_fp_clist, E.fp->clist.data(), E.fp->clist.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            TRC_TRY(dev_upload(E.d_fp_mask, E.fp->mask.data(), E.fp->mask.size()));
+            TRC_TRY(dev_upload(E.d_fp_coff, E.fp->coff.data(), E.fp->coff.size()));
+            TRC_TRY(dev_upload(E.d_fp_clist, E.fp->clist.data(), E.fp->clist.size()));
         }
     }
     if (!E.fp->ok) return TRC_OK;
     out->P = E.fp->P;
-    out->mask = E.d_fp_mask; out->coff = E.d_fp_coff; out->clist = E.d_fp_clist;
+    out->mask = E.d_fp_mask.get(); out->coff = E.d_fp_coff.get(); out->clist = E.d_fp_clist.get();
     out->n_list = (long long)E.fp->clist.size();
     *use = true;
     return TRC_OK;
@@ -2313,12 +2310,10 @@ static void stream_engine_free(StreamEngine *E) {
     if (!E) return;
     for (int k = 0; k < STREAM_MAX_SLOTS; ++k) {
         stream_ws_free(E->slot[k].W);
-        dev_free(E->slot[k].spec);
         if (E->slot[k].h_cnt) (void)hipHostFree(E->slot[k].h_cnt);
         if (E->slot[k].done) (void)hipEventDestroy(E->slot[k].done);
         if (k >= 1 && E->slot[k].stream) (void)hipStreamDestroy(E->slot[k].stream);
     }
-    dev_free(E->d_fp_mask); dev_free(E->d_fp_coff); dev_free(E->d_fp_clist);
     delete E->fp;
     delete E;
 }
@@ -2631,9 +2626,8 @@ static int stream_slots_alloc(StreamEngine &E, int n_slots, long long cap, const
         TRC_TRY(stream_ws_alloc(Tk.W, cap, (int)sc->accel.unbounded.size(), (long long)sc->tally_n, K));
         const long long want = (carry_in.spec && carry_in.n_spec > 0) ? (long long)carry_in.n_spec * Tk.W.room : 0;
         if (Tk.spec_len < want) {
-            dev_free(Tk.spec);
-            Tk.spec = nullptr; Tk.spec_len = 0;
-            TRC_TRY(dev_alloc(&Tk.spec, (size_t)want));
+            Tk.spec_len = 0;
+            TRC_TRY(Tk.spec.alloc((size_t)want));
             Tk.spec_len = want;
         }
         Tk.spec_on = want > 0;
@@ -2902,7 +2896,7 @@ static int start_batch(StreamCall &C, StreamSlot &T, long long base) {
     T.n_in = T.nb; T.n_act = 0; T.b = 0; T.cur = 0; T.attempt = 0; T.busy = true;
     T.SP = C.SP0;
     T.SP.W = T.W;
-    T.SP.carry.slot_spec = T.spec_on ? T.spec : nullptr;
+    T.SP.carry.slot_spec = T.spec_on ? T.spec.get() : nullptr;
     T.SP.base = base;
     T.SP.nb = T.nb;
     TRC_TRY(upload_counters(C, T));
@@ -3034,8 +3028,8 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, c
     float total_ms = 0;
     (void)hipEventElapsedTime(&total_ms, ctx->ev0, ctx->ev1);
     for (int k = 0; k < n_slots; ++k)
-        hipLaunchKernelGGL(k_s_merge_tallies, dim3((unsigned)((sc->tally_n + 255) / 256)), dim3(256), 0, ctx->stream, sc->d_tally, E.slot[k].W.tally_part, (long long)sc->tally_n);
-    hipLaunchKernelGGL(k_s_add2, dim3(1), dim3(64), 0, ctx->stream, sc->d_tally + 3 * sc->n_surf, C.seg, C.hits);
+        hipLaunchKernelGGL(k_s_merge_tallies, dim3((unsigned)((sc->tally_n + 255) / 256)), dim3(256), 0, ctx->stream, sc->d_tally.get(), E.slot[k].W.tally_part, (long long)sc->tally_n);
+    hipLaunchKernelGGL(k_s_add2, dim3(1), dim3(64), 0, ctx->stream, sc->d_tally.get() + 3 * sc->n_surf, C.seg, C.hits);
     // (not waited for: whatever reads or resets the tallies synchronises the context's stream first, and the next call's kernels
     // are ordered behind these by ev0)
     stats->kernel_ms = total_ms;
