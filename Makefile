@@ -19,6 +19,8 @@ HOSTCHECK := $(ROOT)tests/hostcheck/libtrc_hostcheck.so
 HOSTCHECK_SRC := $(ROOT)tests/hostcheck/hostcheck.cpp
 SPECCHECK := $(ROOT)tests/hostcheck/libtrc_spectrum_check.so
 SPECCHECK_SRC := $(ROOT)tests/hostcheck/spectrum_check.cpp
+SUNCHECK := $(ROOT)tests/hostcheck/libtrc_sunshape_check.so
+SUNCHECK_SRC := $(ROOT)tests/hostcheck/sunshape_check.cpp
 
 all: $(LIB)
 
@@ -50,7 +52,7 @@ $(LIB): $(OBJS)
 	mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared -o $@ $(OBJS)
 
-hostcheck: $(HOSTCHECK) $(SPECCHECK)
+hostcheck: $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK)
 
 $(HOSTCHECK): $(HOSTCHECK_SRC) $(HDR)
 	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(HOSTCHECK_SRC)
@@ -58,6 +60,10 @@ $(HOSTCHECK): $(HOSTCHECK_SRC) $(HDR)
 # the source-spectrum sampler of the per-ray core, host-compiled for its tests
 $(SPECCHECK): $(SPECCHECK_SRC) $(HDR)
 	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(SPECCHECK_SRC)
+
+# the tabulated-sunshape sampler and sources of the per-ray core, host-compiled for their tests
+$(SUNCHECK): $(SUNCHECK_SRC) $(HDR)
+	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(SUNCHECK_SRC)
 
 # assembly listings with the registers, scratch and occupancy of every kernel (build/*.s, build/*.resources.txt)
 asm: $(SRCS) $(HDR)
@@ -73,6 +79,6 @@ asm-shade: $(CSRC)/trc_shade.hip $(HDR)
 		-o $(ROOT)build/trc_shade.s $(CSRC)/trc_shade.hip 2> $(ROOT)build/trc_shade.resources.txt
 
 clean:
-	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK)
+	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK)
 
 .PHONY: all hostcheck asm asm-shade clean

@@ -184,8 +184,14 @@ typedef enum trc_source_kind {
     TRC_SRC_PILLBOX_TRIANGLE = 4, /* triangular_bundle sources.py:544-597  center = A, rot_pos columns 0,1 = AB, AC ; p: ang_range */
     TRC_SRC_VF_CYLINDER = 5,   /* vf_cylinder_bundle sources.py:716-769  Lambertian emitter on a cylinder wall
                                   p: rc,lc,span0,span1,ang_range,sign(+1 rays_in / -1) */
-    TRC_SRC_VF_FRUSTUM = 6     /* vf_frustum_bundle sources.py:644-714  Lambertian emitter on a frustum wall
+    TRC_SRC_VF_FRUSTUM = 6,    /* vf_frustum_bundle sources.py:644-714  Lambertian emitter on a frustum wall
                                   p: r0,r1,depth,span0,span1,ang_range,sign */
+    /* tabulated sunshapes (sunshape_to_ray_directions sources.py:386-410): start points as the Buie kinds, polar angle from the
+       table `table` names (trc_sunshape_create); p[5..7] are written by the library (TRC_SUNSHAPE_P_*).  (Numbered after
+       the last kind rather than by a literal: the oracle's kind table, which the header's literals are checked against, has no
+       model of them.) */
+    TRC_SRC_SUNSHAPE_DISK = TRC_SRC_VF_FRUSTUM + 1,  /* tabulated_sunshape sources.py:386-410, :412-464  p: radius ; table */
+    TRC_SRC_SUNSHAPE_RECT = TRC_SRC_VF_FRUSTUM + 2   /* rect_tabulated_sunshape sources.py:386-410, :466-515  p: width,height ; table */
 } trc_source_kind;
 
 #define TRC_BUIE_NELEM 210  /* sources.py:338 */
@@ -199,7 +205,7 @@ typedef enum trc_source_kind {
  */
 typedef struct trc_source_desc {
     int32_t kind;
-    int32_t reserved;
+    int32_t table;      /* TRC_SRC_SUNSHAPE_*: the id of a live trc_sunshape (trc_sunshape_id); 0 for every other kind */
     double center[3];
     double rot_pos[9];  /* row-major local->global for start points */
     double rot_dir[9];  /* row-major local->global for directions   */
@@ -207,6 +213,23 @@ typedef struct trc_source_desc {
     double energy;      /* energy carried by each ray */
     double buie[3 * (TRC_BUIE_NELEM + 1) + 6];
 } trc_source_desc;
+
+/*
+ * Tabulated sunshape (sunshape_to_ray_directions, sources.py:386-410): n points (2..4096) of strictly increasing polar angles
+ * angle[0] >= 0, angle[n-1] < pi/2, and finite, non-negative intensities with a positive mass.  The polar angle has the density
+ * that interpolates g_i = I_i cos(theta_i) sin(theta_i) linearly between the points.  The library packs theta | g | cdf (g
+ * normalised to a unit trapezoid integral, cdf its running integral, ending at exactly 1) and uploads it once.  It also picks the
+ * core angle theta_c = the smallest point beyond which at most 1 % of the mass lies, and u_c = cdf there: rays with a polar
+ * uniform u < u_c have theta <= theta_c.  For a descriptor of kind TRC_SRC_SUNSHAPE_* the library writes theta_c, u_c and n
+ * into p[TRC_SUNSHAPE_P_THETA_C..TRC_SUNSHAPE_P_N] and the table's device address into buie[0] of its own copy; the caller's
+ * values of those entries are ignored.  A descriptor that names an unknown or destroyed table is TRC_ERR_INVALID.
+ */
+typedef struct trc_sunshape trc_sunshape;
+#define TRC_SUNSHAPE_MAX_POINTS 4096
+#define TRC_SUNSHAPE_CORE_TAIL 0.01    /* the share of the mass beyond theta_c at most */
+#define TRC_SUNSHAPE_P_THETA_C 5
+#define TRC_SUNSHAPE_P_U_C 6
+#define TRC_SUNSHAPE_P_N 7
 
 /*
  * Spectrum of a source: every source ray gets one wavelength drawn on the device from it (spectral Monte Carlo), a pure
@@ -422,6 +445,16 @@ int trc_source_generate(trc_ctx *ctx, const trc_source_desc *src, int64_t n, uin
 /* The same with a spectrum (NULL: trc_source_generate); out->wavelength and out->ref_index are filled when non-NULL. */
 int trc_source_generate_x(trc_ctx *ctx, const trc_source_desc *src, const trc_source_spectrum *spec, int64_t n, uint64_t seed,
                           uint64_t ray_offset, trc_rays *out);
+
+/*
+ * Tabulated sunshape tables (see trc_sunshape above).  create: checks and packs the table, uploads it to the context's GPU and
+ * gives it an id (never reused) for trc_source_desc.table.  get: the packed table (3n doubles: theta | g | cdf), theta_c and u_c
+ * (any pointer may be NULL).  destroy: frees it; descriptors that name it fail from then on.
+ */
+int trc_sunshape_create(trc_ctx *ctx, int32_t n, const double *angle, const double *intensity, trc_sunshape **out);
+int trc_sunshape_id(trc_sunshape *table, int32_t *id);
+int trc_sunshape_get(trc_sunshape *table, int32_t *n, double *packed, double *theta_c, double *u_c);
+int trc_sunshape_destroy(trc_sunshape *table);
 
 /*
  * Start points of the first n rays of a disc / rectangle source (sources.py:175-515) in the source's own plane coordinates

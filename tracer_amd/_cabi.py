@@ -47,6 +47,10 @@ LEVEL_VOLUME = 0x40000000        # TRC_LEVEL_VOLUME: bit of a level's surf[] ent
 
 # enum trc_source_kind
 SRC_PILLBOX_DISK, SRC_PILLBOX_RECT, SRC_BUIE_DISK, SRC_BUIE_RECT, SRC_PILLBOX_TRIANGLE, SRC_VF_CYLINDER, SRC_VF_FRUSTUM = range(7)
+SRC_SUNSHAPE_DISK, SRC_SUNSHAPE_RECT = 7, 8       # tabulated sunshapes: the descriptor's `table` names a trc_sunshape
+SUNSHAPE_MAX_POINTS = 4096
+SUNSHAPE_CORE_TAIL = 0.01
+SUNSHAPE_P_THETA_C, SUNSHAPE_P_U_C, SUNSHAPE_P_N = 5, 6, 7
 
 _p_f64 = C.POINTER(C.c_double)
 _p_i64 = C.POINTER(C.c_int64)
@@ -69,7 +73,7 @@ class Rays(C.Structure):
 
 
 class SourceDesc(C.Structure):
-    _fields_ = [('kind', C.c_int32), ('reserved', C.c_int32), ('center', C.c_double * 3),
+    _fields_ = [('kind', C.c_int32), ('table', C.c_int32), ('center', C.c_double * 3),
                 ('rot_pos', C.c_double * 9), ('rot_dir', C.c_double * 9), ('p', C.c_double * 8),
                 ('energy', C.c_double), ('buie', C.c_double * BUIE_LEN)]
 
@@ -147,6 +151,10 @@ SIGNATURES = {
     'trc_source_generate': (C.c_int, [_vp, C.POINTER(SourceDesc), C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(Rays)]),
     'trc_source_generate_x': (C.c_int, [_vp, C.POINTER(SourceDesc), C.POINTER(SourceSpectrumDesc), C.c_int64, C.c_uint64,
                                         C.c_uint64, C.POINTER(Rays)]),
+    'trc_sunshape_create': (C.c_int, [_vp, C.c_int32, _p_f64, _p_f64, _pvp]),
+    'trc_sunshape_id': (C.c_int, [_vp, _p_i32]),
+    'trc_sunshape_get': (C.c_int, [_vp, _p_i32, _p_f64, _p_f64, _p_f64]),
+    'trc_sunshape_destroy': (C.c_int, [_vp]),
     'trc_source_start32': (C.c_int, [_vp, C.POINTER(SourceDesc), C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), _p_f64]),
     'trc_gm_find_intersections': (C.c_int, [_vp, C.POINTER(SurfaceDesc), C.c_int32, _p_f64, C.POINTER(Rays), _p_f64,

@@ -1744,11 +1744,46 @@ TRC_HD double trc_buie_theta_fast(const trc_buie_fast *F, double Rv) {
     return trc_pow_pos((Rv - 1.0) * F->aur[0] + Rv * F->aur[1], F->aur[2]);
 }
 
+// Tabulated sunshape (sunshape_to_ray_directions, sources.py:386-410): the polar angle of uniform u from the packed table of
+// a trc_sunshape (theta | g | cdf, n points; trc_sunshape_create).  The reference's density interpolates g linearly between the
+// points: a piecewise-linear density over theta, inverted by the sampler of the source spectra (every engine calls this).
+TRC_HD double trc_spectrum_sample(const double *wl, const double *val, const double *cdf, int n, double u);
+TRC_HD double trc_sunshape_theta(const double *tab, int n, double u) { return trc_spectrum_sample(tab, tab + n, tab + 2 * n, n, u); }
+// Host: packs a checked table (n >= 2 strictly increasing angles, finite non-negative intensities) into tab[3n] = theta | g | cdf
+// and picks the core.  The reference's table (sources.py:389-393): g_i = I_i cos(theta_i) sin(theta_i), trapezoid integrals over
+// the intervals.  Here g is normalised to a unit integral and cdf ends at exactly 1 (the reference's may end a little below 1,
+// and its draws beyond CDF[-1] then keep theta = 0), so that every u in [0, 1) finds an interval of positive mass.  The core
+// angle theta_c: the smallest point beyond which at most TRC_SUNSHAPE_CORE_TAIL of the mass lies; u_c = cdf there.  A ray with
+// u < u_c falls in an interval that ends at or below theta_c.  Returns false for a table without mass.
+static inline bool trc_sunshape_pack(int n, const double *angle, const double *intensity, double *tab, double *theta_c, double *u_c) {
+    double *th = tab, *g = tab + n, *c = tab + 2 * n;
+    double cum = 0.0;
+    for (int i = 0; i < n; ++i) {
+        th[i] = angle[i];
+        g[i] = intensity[i] * cos(angle[i]) * sin(angle[i]);
+        if (i > 0) cum += 0.5 * (g[i - 1] + g[i]) * (th[i] - th[i - 1]);
+        c[i] = cum;
+    }
+    if (!(cum > 0.0) || !(cum < TRC_INF)) return false;
+    for (int i = 0; i < n; ++i) { g[i] /= cum; c[i] /= cum; }
+    c[n - 1] = 1.0;
+    int k = 1;
+    while (k < n - 1 && !(1.0 - c[k] <= TRC_SUNSHAPE_CORE_TAIL)) ++k;
+    *theta_c = th[k]; *u_c = c[k];
+    return true;
+}
+
+// the table a resolved sunshape descriptor points to (its device address in buie[0], TRC_SUNSHAPE_P_N points)
+TRC_HD const double *trc_sunshape_table(const trc_source_desc *src) {
+    return (const double *)(uintptr_t)__builtin_bit_cast(uint64_t, src->buie[0]);
+}
+
 // buie: the table of the descriptor (or its LDS copy); aur: trc_buie_aureole_consts of it, or null; bf: the
 // trc_buie_fast form of the table when the caller has staged one (then buie and aur are not read).
 // KIND >= 0 promises src->kind == KIND (the streaming engine compiles the Buie disc on its own: 158 instead of 237
-// VGPRs); KIND < 0 reads the kind from the descriptor.
-template <int KIND>
+// VGPRs); KIND < 0 reads the kind from the descriptor.  SUN: an instance for any kind that knows the tabulated sunshapes too
+// (the instances without it are those that existed before them, unchanged; the host never hands them a sunshape).
+template <int KIND, bool SUN = false>
 TRC_HD void trc_source_ray_t(const trc_source_desc *src, const double *buie, const double *aur, uint64_t seed, uint64_t rid,
                              double *px, double *py, double *pz, double *dx, double *dy, double *dz,
                              const trc_buie_fast *bf = nullptr) {
@@ -1757,7 +1792,22 @@ TRC_HD void trc_source_ray_t(const trc_source_desc *src, const double *buie, con
     double lx, ly, lz = 0.0, ax, ay, az;
     const double *p = src->p;
     const int kind = KIND >= 0 ? KIND : src->kind;
-    switch (kind) {
+    constexpr bool SUNC = KIND == TRC_SRC_SUNSHAPE_DISK || KIND == TRC_SRC_SUNSHAPE_RECT || (KIND < 0 && SUN);
+    const bool sun = SUNC && (kind == TRC_SRC_SUNSHAPE_DISK || kind == TRC_SRC_SUNSHAPE_RECT);
+    if (sun) {                          // draws: xv1, phiv, R_theta, xi as the Buie sources (sources.py:386-410, :431-434, :485-486)
+        if (kind == TRC_SRC_SUNSHAPE_DISK) {
+            double r = p[0] * sqrt(u0), sph, cph;
+            trc_sincos_2pi(u1, &sph, &cph);
+            lx = r * cph; ly = r * sph;
+        } else {
+            lx = p[0] * (u0 - 0.5); ly = p[1] * (u1 - 0.5);
+        }
+        double th = trc_sunshape_theta(trc_sunshape_table(src), (int)p[TRC_SUNSHAPE_P_N], u2);
+        double st, ct, sxi, cxi;
+        trc_sincos(th, &st, &ct);       // (a table may reach pi/2)
+        trc_sincos_2pi(u3, &sxi, &cxi);
+        ax = cxi * st; ay = sxi * st; az = ct;
+    } else switch (kind) {
     case TRC_SRC_VF_CYLINDER:           // draws: zs, phi_s, dir phi, dir R (sources.py:737-746)
     case TRC_SRC_VF_FRUSTUM: {          // draws: dir phi, dir R, R, phi_s (sources.py:670-685)
         double phi, slope, sign, fx, fy, fz;
@@ -1826,7 +1876,7 @@ TRC_HD void trc_source_ray_t(const trc_source_desc *src, const double *buie, con
         trc_pillbox_dir_u(u2, u3, p[0], &ax, &ay, &az);
         break;
     }
-    default: {                          // TRC_SRC_BUIE_RECT (sources.py:485-486)
+    default: {                          // TRC_SRC_BUIE_RECT (sources.py:485-486; the sunshape kinds are handled above)
         lx = p[0] * (u0 - 0.5); ly = p[1] * (u1 - 0.5);
         double th = bf ? trc_buie_theta_fast(bf, u2) : trc_buie_theta(buie, aur, u2);
         double st, ct, sxi, cxi;
@@ -1837,7 +1887,7 @@ TRC_HD void trc_source_ray_t(const trc_source_desc *src, const double *buie, con
     }
     }
     const double *rp = src->rot_pos, *rd = src->rot_dir;
-    if (kind >= TRC_SRC_VF_CYLINDER) {      // wall emitters have a third local coordinate
+    if (!sun && kind >= TRC_SRC_VF_CYLINDER) {      // wall emitters (VF_CYLINDER, VF_FRUSTUM) have a third local coordinate
         *px = rp[0] * lx + rp[1] * ly + rp[2] * lz + src->center[0];
         *py = rp[3] * lx + rp[4] * ly + rp[5] * lz + src->center[1];
         *pz = rp[6] * lx + rp[7] * ly + rp[8] * lz + src->center[2];
@@ -1853,7 +1903,7 @@ TRC_HD void trc_source_ray_t(const trc_source_desc *src, const double *buie, con
 
 TRC_HD void trc_source_ray(const trc_source_desc *src, const double *buie, const double *aur, uint64_t seed, uint64_t rid,
                            double *px, double *py, double *pz, double *dx, double *dy, double *dz) {
-    trc_source_ray_t<-1>(src, buie, aur, seed, rid, px, py, pz, dx, dy, dz);
+    trc_source_ray_t<-1, true>(src, buie, aur, seed, rid, px, py, pz, dx, dy, dz);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -29,9 +29,9 @@
 #define TRC_FP_EPS_REL 1e-4       /* eps = TRC_FP_EPS_REL * half: float32 start points are good to ~1e-6 * half */
 
 struct trc_fp_params {
-    int32_t kind;                 // source kind (trc_source_kind)
+    int32_t kind;                 // source kind (trc_source_kind; the Buie kind of the same start shape for a tabulated sunshape)
     int32_t M, Mc;                // mask cells / list cells per side; M = Mc << TRC_FP_SHIFT, a multiple of 32
-    int32_t has_generic;          // Buie: rays with u2 >= cdf_end (aureole) take the general path
+    int32_t has_generic;          // Buie: rays with u2 >= cdf_end (aureole) take the general path; tabulated sunshape: u2 >= u_c
     float half, inv_cell;         // the map covers [-half, half]^2; inv_cell = M / (2 half)
     float p[6];                   // start-point mapping in float32, per kind (trc_fp_position32)
     double cdf_end;
@@ -58,7 +58,9 @@ TRC_HD void trc_fp_sincos_rev32(float rev, float *sn, float *cs) {        // sin
 template <int KIND>
 TRC_HD void trc_fp_position32_t(const trc_fp_params &F, const uint32_t o[4], float *lx, float *ly) {
     const float s = 1.0f / 4294967296.0f;
-    const int kind = KIND >= 0 ? KIND : F.kind;
+    // (the tabulated sunshapes start their rays as the Buie sources: their maps carry the Buie kind, trc_fp_source)
+    const int kind = KIND == TRC_SRC_SUNSHAPE_DISK ? TRC_SRC_BUIE_DISK : KIND == TRC_SRC_SUNSHAPE_RECT ? TRC_SRC_BUIE_RECT
+                   : KIND >= 0 ? KIND : F.kind;
     float sn, cs;
     if (kind == TRC_SRC_BUIE_DISK) {            // r = R sqrt(u0), phi = 2 pi u1
         const float u0 = ((float)o[0] + 0.5f) * s, u1 = ((float)o[1] + 0.5f) * s;
@@ -170,6 +172,17 @@ static inline bool trc_fp_source(const trc_source_desc &src, trc_fp_params &P, d
         P.p[0] = (float)p[0]; P.p[1] = (float)p[1];
         break;
     }
+    case TRC_SRC_SUNSHAPE_DISK:
+    case TRC_SRC_SUNSHAPE_RECT:
+        // the core cone theta_c (p[] of a resolved descriptor): a ray with u2 < u_c falls in an interval of the table that ends
+        // at or below theta_c, and the sampler clamps to the interval -- its angle is x0 + h, at most one ulp above theta_c.
+        // That ulp moves a ray by depth * 2.2e-16 * theta_c, far inside the margin's 1e-9 (half + depth) term (trc_fp_build).
+        // The rays of the tail (u2 >= u_c) take the general path.
+        if (src.kind == TRC_SRC_SUNSHAPE_DISK) { half = p[0]; P.p[0] = (float)p[0]; P.kind = TRC_SRC_BUIE_DISK; }
+        else { half = 0.5 * std::fmax(std::fabs(p[0]), std::fabs(p[1])); P.p[0] = (float)p[0]; P.p[1] = (float)p[1]; P.kind = TRC_SRC_BUIE_RECT; }
+        theta_c = p[TRC_SUNSHAPE_P_THETA_C];
+        P.has_generic = 1; P.cdf_end = p[TRC_SUNSHAPE_P_U_C];
+        break;
     case TRC_SRC_PILLBOX_DISK:
         if (p[5] != 0.0) { *why = "disc source with x_cut (positions are redrawn)"; return false; }
         half = std::fmax(std::fabs(p[0]), std::fabs(p[1])); theta_c = p[4];

@@ -576,14 +576,14 @@ __device__ __forceinline__ void coop_drain_leaves(const trc_accel_view &A, const
     WAVE_SYNC();
 }
 
-// fresh ray for a lane: from the source descriptor or from the given bundle
-template <int KIND = -1, bool SPEC = false>
+// fresh ray for a lane: from the source descriptor or from the given bundle (SUN: trc_source_ray_t's)
+template <int KIND = -1, bool SPEC = false, bool SUN = false>
 __device__ __forceinline__ void fast_new_ray(const FastParams &P, const double *buie, long long id, double &px, double &py,
                                              double &pz, double &dx, double &dy, double &dz, double &e, double &ref, double &wl,
                                              unsigned long long &rid, const trc_buie_fast *bf = nullptr) {
     rid = P.rid ? P.rid[id] : (P.ray_offset + (unsigned long long)id);
     if (P.src) {
-        trc_source_ray_t<KIND>(P.src, buie, buie ? buie + TRC_BUIE_TABLE : nullptr, P.seed, rid, &px, &py, &pz, &dx, &dy, &dz, bf);
+        trc_source_ray_t<KIND, SUN>(P.src, buie, buie ? buie + TRC_BUIE_TABLE : nullptr, P.seed, rid, &px, &py, &pz, &dx, &dy, &dz, bf);
         e = P.src->energy;
         if (SPEC) trc_spectrum_of(P.spec, P.seed, rid, &wl, &ref);     // (the megakernel draws at birth: its rays live in registers)
         else { ref = 1.0; wl = 0.0; }
@@ -600,7 +600,7 @@ __device__ __forceinline__ void fast_new_ray(const FastParams &P, const double *
 // staged in LDS when they fit in 64 KiB, read from global memory otherwise.  Used when the single-precision data
 // cannot be built or do not fit (very large scenes), and as a cross-check of the cooperative kernel.
 //   LDS (doubles): [recs S*stride][kd_split nodes][buie 639][tally 3S+2] then int32: [kd_a][kd_b][leaf][always]
-template <int THREADS, bool SPEC = false>
+template <int THREADS, bool SPEC = false, bool SUN = false>
 __global__ __launch_bounds__(THREADS) void k_trace_fast(FastParams P) {
     extern __shared__ double lds[];
     const DScene &sc = P.sc;
@@ -676,7 +676,7 @@ __global__ __launch_bounds__(THREADS) void k_trace_fast(FastParams P) {
         if (next < end && need) {
             long long id = next + __popcll(need & lt_mask);
             if (!alive && id < end) {
-                fast_new_ray<-1, SPEC>(P, buie, id, px, py, pz, dx, dy, dz, e, ref, wl, rid);
+                fast_new_ray<-1, SPEC, SUN>(P, buie, id, px, py, pz, dx, dy, dz, e, ref, wl, rid);
                 bounce = 0;
                 prev = S;
                 alive = true;
@@ -722,7 +722,7 @@ __global__ __launch_bounds__(THREADS) void k_trace_fast(FastParams P) {
 // memory (they are rare); everything the candidate search touches lives in LDS:
 //   doubles [buie 639][tally 3S+2] | float [sbox 6S] | u32 [nodes 2n] | i32 [always][unbounded] | u16 [leaf] |
 //   16-byte aligned per-wave regions of COOP_WAVE_BYTES(depth)
-template <int THREADS, bool SPEC = false>
+template <int THREADS, bool SPEC = false, bool SUN = false>
 __global__ __launch_bounds__(THREADS) void k_trace_coop(FastParams P) {
     extern __shared__ double lds[];
     const DScene &sc = P.sc;
@@ -811,7 +811,7 @@ __global__ __launch_bounds__(THREADS) void k_trace_coop(FastParams P) {
             if (next < end && need) {
                 long long id = next + __popcll(need & lt_mask);
                 if (!alive && id < end) {
-                    fast_new_ray<-1, SPEC>(P, buie, id, px, py, pz, dx, dy, dz, e, ref, wl, rid);
+                    fast_new_ray<-1, SPEC, SUN>(P, buie, id, px, py, pz, dx, dy, dz, e, ref, wl, rid);
                     bounce = 0;
                     prev = S;
                     alive = true;
@@ -2283,8 +2283,109 @@ static int stage_rays(const trc_rays *r, int64_t n, bool need_energy, DevRays *d
     return TRC_OK;
 }
 
+// ================================================================================================
+// tabulated sunshapes (trc_sunshape): tables packed and uploaded once, named by descriptors through their id
+// ================================================================================================
+struct trc_sunshape {
+    int device;                     // the GPU of the context it was made on
+    int32_t id, n;
+    std::vector<double> tab;        // theta | g | cdf (trc_sunshape_theta layout)
+    double theta_c, u_c;
+    DevBuf<double> d_tab;
+};
+
+// every live table by id; ids count up and are never reused, so that a descriptor (and the footprint map cached from it) always
+// means the same table
+static std::mutex g_sun_mu;
+static std::unordered_map<int32_t, trc_sunshape *> g_sun;
+static int32_t g_sun_next = 1;
+
+// checks a table (trc_sunshape_create's errors) and packs it (trc_sunshape_pack)
+static int sunshape_pack(int32_t n, const double *angle, const double *intensity, std::vector<double> &tab, double *theta_c, double *u_c) {
+    if (n < 2 || n > TRC_SUNSHAPE_MAX_POINTS)
+        return trc_fail(TRC_ERR_INVALID, "trc_sunshape_create: the table has %d points, 2..%d allowed", n, TRC_SUNSHAPE_MAX_POINTS);
+    if (!angle || !intensity) return trc_fail(TRC_ERR_INVALID, "trc_sunshape_create: angles or intensities missing");
+    for (int i = 0; i < n; ++i) {
+        if (!std::isfinite(angle[i])) return trc_fail(TRC_ERR_INVALID, "trc_sunshape_create: angle %d is not finite", i);
+        if (i > 0 && !(angle[i] > angle[i - 1]))
+            return trc_fail(TRC_ERR_INVALID, "trc_sunshape_create: angles are not strictly increasing (point %d)", i);
+        if (!std::isfinite(intensity[i]) || intensity[i] < 0.0)
+            return trc_fail(TRC_ERR_INVALID, "trc_sunshape_create: intensity %d is negative or not finite", i);
+    }
+    if (!(angle[0] >= 0.0) || !(angle[n - 1] < TRC_PI / 2.0))
+        return trc_fail(TRC_ERR_INVALID, "trc_sunshape_create: angles must lie in [0, pi/2)");
+    tab.assign((size_t)3 * n, 0.0);
+    if (!trc_sunshape_pack(n, angle, intensity, tab.data(), theta_c, u_c))
+        return trc_fail(TRC_ERR_INVALID, "trc_sunshape_create: the table has no mass");
+    return TRC_OK;
+}
+
+extern "C" int trc_sunshape_create(trc_ctx *ctx, int32_t n, const double *angle, const double *intensity, trc_sunshape **out) {
+    if (!ctx || !out) return trc_fail(TRC_ERR_INVALID, "trc_sunshape_create: bad arguments");
+    *out = nullptr;
+    std::unique_ptr<trc_sunshape> t(new (std::nothrow) trc_sunshape());
+    if (!t) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
+    TRC_TRY(sunshape_pack(n, angle, intensity, t->tab, &t->theta_c, &t->u_c));
+    t->device = ctx->device; t->n = n;
+    HIP_TRY(hipSetDevice(ctx->device));
+    TRC_TRY(dev_upload(t->d_tab, t->tab.data(), t->tab.size(), "sunshape upload failed"));
+    std::lock_guard<std::mutex> lk(g_sun_mu);
+    if (g_sun_next == INT32_MAX) return trc_fail(TRC_ERR_CAPACITY, "trc_sunshape_create: table ids exhausted");
+    t->id = g_sun_next++;
+    g_sun[t->id] = t.get();
+    *out = t.release();
+    return TRC_OK;
+}
+
+extern "C" int trc_sunshape_id(trc_sunshape *t, int32_t *id) {
+    if (!t || !id) return trc_fail(TRC_ERR_INVALID, "trc_sunshape_id: bad arguments");
+    *id = t->id;
+    return TRC_OK;
+}
+
+extern "C" int trc_sunshape_get(trc_sunshape *t, int32_t *n, double *packed, double *theta_c, double *u_c) {
+    if (!t) return trc_fail(TRC_ERR_INVALID, "trc_sunshape_get: table is NULL");
+    if (n) *n = t->n;
+    if (packed) memcpy(packed, t->tab.data(), t->tab.size() * sizeof(double));
+    if (theta_c) *theta_c = t->theta_c;
+    if (u_c) *u_c = t->u_c;
+    return TRC_OK;
+}
+
+extern "C" int trc_sunshape_destroy(trc_sunshape *t) {
+    if (!t) return TRC_OK;
+    {
+        std::lock_guard<std::mutex> lk(g_sun_mu);
+        g_sun.erase(t->id);
+    }
+    HIP_TRY(hipSetDevice(t->device));
+    delete t;
+    return TRC_OK;
+}
+
+static bool source_is_sunshape(int kind) { return kind == TRC_SRC_SUNSHAPE_DISK || kind == TRC_SRC_SUNSHAPE_RECT; }
+
+// A sunshape descriptor as the kernels read it: `tmp` = *src with theta_c, u_c, n in p[] and the table's device address in
+// buie[0]; `src` then points to it.  Other kinds are left as they are.  A host-side lookup: no device traffic.
+static int source_resolve(trc_ctx *ctx, const trc_source_desc *&src, trc_source_desc &tmp, const char *who) {
+    if (!src || !source_is_sunshape(src->kind)) return TRC_OK;
+    std::lock_guard<std::mutex> lk(g_sun_mu);
+    auto it = g_sun.find(src->table);
+    if (it == g_sun.end()) return trc_fail(TRC_ERR_INVALID, "%s: the source names sunshape table %d, which does not exist (destroyed?)", who, src->table);
+    const trc_sunshape *t = it->second;
+    if (ctx && t->device != ctx->device) return trc_fail(TRC_ERR_INVALID, "%s: sunshape table %d lives on another device", who, src->table);
+    tmp = *src;
+    tmp.p[TRC_SUNSHAPE_P_THETA_C] = t->theta_c;
+    tmp.p[TRC_SUNSHAPE_P_U_C] = t->u_c;
+    tmp.p[TRC_SUNSHAPE_P_N] = (double)t->n;
+    memset(tmp.buie, 0, sizeof(tmp.buie));
+    tmp.buie[0] = __builtin_bit_cast(double, (uint64_t)(uintptr_t)t->d_tab.get());
+    src = &tmp;
+    return TRC_OK;
+}
+
 static int upload_source(const trc_source_desc *src, DevBuf<trc_source_desc> &d_src) {
-    if (src->kind < TRC_SRC_PILLBOX_DISK || src->kind > TRC_SRC_VF_FRUSTUM)
+    if (src->kind < TRC_SRC_PILLBOX_DISK || src->kind > TRC_SRC_SUNSHAPE_RECT)
         return trc_fail(TRC_ERR_UNSUPPORTED, "source kind %d is not in the native table", src->kind);
     return dev_upload(d_src, src, 1);
 }
@@ -2299,6 +2400,8 @@ static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_d
     if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
     if ((in == nullptr) == (src == nullptr)) return trc_fail(TRC_ERR_INVALID, "exactly one of `in` and `src` must be given");
     if (n < 0 || reps < 0) return trc_fail(TRC_ERR_INVALID, "n and reps must be >= 0");
+    trc_source_desc src_res;
+    TRC_TRY(source_resolve(sc->ctx, src, src_res, "trc_trace_fast"));
     if (sc->splits) return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has ray-splitting optics: use trc_trace_ordered");
     const StreamKnobs knobs = stream_knobs();
     // Rays that carry the imaginary part of a complex index, materials evaluated at their wavelength or a sampled spectrum are
@@ -2359,7 +2462,7 @@ static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_d
         else {
             // the scene keeps a device buffer for the descriptor of the call in progress (hipMalloc / hipFree per call
             // cost more than the upload)
-            if (src->kind < TRC_SRC_PILLBOX_DISK || src->kind > TRC_SRC_VF_FRUSTUM) return trc_fail(TRC_ERR_UNSUPPORTED, "source kind %d is not in the native table", src->kind);
+            if (src->kind < TRC_SRC_PILLBOX_DISK || src->kind > TRC_SRC_SUNSHAPE_RECT) return trc_fail(TRC_ERR_UNSUPPORTED, "source kind %d is not in the native table", src->kind);
             if (!sc->d_src_buf) { TRC_TRY(sc->d_src_buf.alloc(1)); sc->src_host_ok = false; }
             if (!(sc->src_host_ok && memcmp(&sc->src_host, src, sizeof(trc_source_desc)) == 0)) {
                 sc->src_host_ok = false;
@@ -2498,7 +2601,14 @@ static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_d
         (void)hipStreamSynchronize(ctx->stream);       // (the sums of an earlier streaming call may still be on their way into the buffer)
         if (hipMemcpy(tally_before, sc->d_tally.get() + 3 * S, sizeof(tally_before), hipMemcpyDeviceToHost) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
         void (*kern)(FastParams) = nullptr;
-        if (P.spec) {       // (a source with a spectrum: the instances that draw the wavelength)
+        const bool sun = d_src && source_is_sunshape(src->kind);     // (a tabulated sunshape: the instances that know it)
+        if (sun && P.spec) {
+            if (m32) kern = threads == 512 ? k_trace_coop<512, true, true> : k_trace_coop<256, true, true>;
+            else kern = k_trace_fast<256, true, true>;
+        } else if (sun) {
+            if (m32) kern = threads == 512 ? k_trace_coop<512, false, true> : k_trace_coop<256, false, true>;
+            else kern = k_trace_fast<256, false, true>;
+        } else if (P.spec) {       // (a source with a spectrum: the instances that draw the wavelength)
             if (m32) kern = threads == 512 ? k_trace_coop<512, true> : k_trace_coop<256, true>;
             else kern = k_trace_fast<256, true>;
         } else {
@@ -2571,6 +2681,8 @@ static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_d
 extern "C" int trc_source_start32(trc_ctx *ctx, const trc_source_desc *src, int64_t n, uint64_t seed, uint64_t ray_offset,
                                   float *lx, float *ly, double *eps) {
     if (!ctx || !src || n < 0 || !lx || !ly) return trc_fail(TRC_ERR_INVALID, "trc_source_start32: bad arguments");
+    trc_source_desc src_res;
+    TRC_TRY(source_resolve(ctx, src, src_res, "trc_source_start32"));
     HIP_TRY(hipSetDevice(ctx->device));
     trc_fp_params F;
     double half = 0.0, theta_c = 0.0;
@@ -2594,6 +2706,8 @@ extern "C" int trc_source_start32(trc_ctx *ctx, const trc_source_desc *src, int6
 extern "C" int trc_source_generate(trc_ctx *ctx, const trc_source_desc *src, int64_t n, uint64_t seed,
                                    uint64_t ray_offset, trc_rays *out) {
     if (!ctx || !src || n < 0) return trc_fail(TRC_ERR_INVALID, "trc_source_generate: bad arguments");
+    trc_source_desc src_res;
+    TRC_TRY(source_resolve(ctx, src, src_res, "trc_source_generate"));
     TRC_TRY(check_rays(out, n, "trc_source_generate"));
     if (!out->e) return trc_fail(TRC_ERR_INVALID, "trc_source_generate: energy column required");
     HIP_TRY(hipSetDevice(ctx->device));
@@ -2801,6 +2915,8 @@ static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_sourc
     *out = nullptr;
     if ((in == nullptr) == (src == nullptr)) return trc_fail(TRC_ERR_INVALID, "exactly one of `in` and `src` must be given");
     if (n < 0 || reps < 0) return trc_fail(TRC_ERR_INVALID, "n and reps must be >= 0");
+    trc_source_desc src_res;
+    TRC_TRY(source_resolve(sc->ctx, src, src_res, "trc_trace_ordered"));
     if (2 * n >= (int64_t)0xFFFFFFFFll) return trc_fail(TRC_ERR_UNSUPPORTED, "ordered engine handles fewer than 2^31 rays per call");
     if ((flags & TRC_TRACE_ACCEL) && !sc->has_kd) return trc_fail(TRC_ERR_INVALID, "TRC_TRACE_ACCEL without a Kd-tree on the scene");
     if (sc->n_surf >= (1 << 28)) return trc_fail(TRC_ERR_UNSUPPORTED, "too many surfaces for the ordering key");

@@ -832,7 +832,8 @@ __device__ unsigned long long g_sb_stats[32];        /* [0, 16): fresh rays, [16
 #else
 #define SB_COUNT(K, V) ((void)0)
 #endif
-template <int GRIDM, bool LDS, bool FRESH, bool FLAT = false>
+// SUN: a FRESH instance for the tabulated sunshapes (trc_source_ray_t)
+template <int GRIDM, bool LDS, bool FRESH, bool FLAT = false, bool SUN = false>
 __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams S) {
     constexpr int THREADS = SB_THREADS_OF(GRIDM);
     extern __shared__ double lds[];
@@ -985,7 +986,7 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
         if (valid) {
             if (FRESH) {
                 unsigned long long rid;
-                fast_new_ray<-1>(P, nullptr, S.base + ri, px, py, pz, dx, dy, dz, e0, ref0, wl0, rid, buie_src ? l_bf : nullptr);
+                fast_new_ray<-1, false, SUN>(P, nullptr, S.base + ri, px, py, pz, dx, dy, dz, e0, ref0, wl0, rid, buie_src ? l_bf : nullptr);
             } else {
                 const SRayGeo g = W.geo[slot];
                 px = g.px; py = g.py; pz = g.pz; dx = g.dx; dy = g.dy; dz = g.dz;
@@ -1290,7 +1291,7 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
 #endif
 #define SBC_PAIRS 256           /* (ray, surface) pairs that can wait for their exact test, per wave */
 #define SBC_WAVE_BYTES (2 * SBC_CELLS * 64 * 4 + 64 * 4 + SBC_PAIRS * 4 + 64 * 8 + 64 * 4)
-template <bool FRESH, bool FLAT>
+template <bool FRESH, bool FLAT, bool SUN = false>
 __global__ __launch_bounds__(SB_THREADS) void k_s_bounce_coop(StreamParams S) {
     constexpr int THREADS = SB_THREADS;
     extern __shared__ double lds[];
@@ -1370,7 +1371,7 @@ __global__ __launch_bounds__(SB_THREADS) void k_s_bounce_coop(StreamParams S) {
         if (valid) {
             if (FRESH) {
                 unsigned long long rid;
-                fast_new_ray<-1>(P, nullptr, S.base + ri, px, py, pz, dx, dy, dz, e0, ref0, wl0, rid, buie_src ? l_bf : nullptr);
+                fast_new_ray<-1, false, SUN>(P, nullptr, S.base + ri, px, py, pz, dx, dy, dz, e0, ref0, wl0, rid, buie_src ? l_bf : nullptr);
             } else {
                 const SRayGeo g = W.geo[slot];
                 px = g.px; py = g.py; pz = g.pz; dx = g.dx; dy = g.dy; dz = g.dz;
@@ -2282,7 +2283,7 @@ static int stream_fp_prepare(trc_scene *sc, StreamEngine &E, const trc_source_de
             // it at full resolution takes seconds (1e5 faces: 2.5 s).  A coarse map first (1/16 of the work): covered more than
             // 80 % -> no map for this scene and source, every fresh ray is searched on the grid (k_s_bounce<.., FRESH>).
             trc_fp_build(sc->surfs.data(), sc->n_surf, sc->accel, *src, *E.fp, 256);
-            const bool disc = src->kind == TRC_SRC_BUIE_DISK || src->kind == TRC_SRC_PILLBOX_DISK;      // (the mask is a square around the disc)
+            const bool disc = src->kind == TRC_SRC_BUIE_DISK || src->kind == TRC_SRC_PILLBOX_DISK || src->kind == TRC_SRC_SUNSHAPE_DISK;      // (the mask is a square around the disc)
             if (E.fp->ok && E.fp->coverage * (disc ? 4.0 / TRC_PI : 1.0) > 0.8) E.fp->ok = false;
             else trc_fp_build(sc->surfs.data(), sc->n_surf, sc->accel, *src, *E.fp, M);
         } else
@@ -2505,7 +2506,9 @@ static int stream_form_fresh(StreamForms &F, StreamParams &SP0, trc_scene *sc, S
     lds_fresh += 32 + b_queue;
 #define SF_PICK(K) (flat ? (fresh_in_lds ? (const void *)k_s_fresh<K, true, true> : (const void *)k_s_fresh<K, true, false>) \
                          : (fresh_in_lds ? (const void *)k_s_fresh<K, false, true> : (const void *)k_s_fresh<K, false, false>))
+    // (the tabulated sunshapes: the general <kind, flat, lds> form, their table read from global memory, where it stays in L2)
     const void *fresh1_fn = src_kind == TRC_SRC_BUIE_DISK ? SF_PICK(TRC_SRC_BUIE_DISK) : src_kind == TRC_SRC_BUIE_RECT ? SF_PICK(TRC_SRC_BUIE_RECT)
+                          : src_kind == TRC_SRC_SUNSHAPE_DISK ? SF_PICK(TRC_SRC_SUNSHAPE_DISK) : src_kind == TRC_SRC_SUNSHAPE_RECT ? SF_PICK(TRC_SRC_SUNSHAPE_RECT)
                           : src_kind == TRC_SRC_PILLBOX_DISK ? SF_PICK(TRC_SRC_PILLBOX_DISK) : SF_PICK(TRC_SRC_PILLBOX_RECT);
 #undef SF_PICK
 #define SF2_PICK(K) (flat ? (fresh_in_lds ? (const void *)k_s_fresh2<K, true, true> : (const void *)k_s_fresh2<K, true, false>) \
@@ -2513,6 +2516,8 @@ static int stream_form_fresh(StreamForms &F, StreamParams &SP0, trc_scene *sc, S
     const void *fresh_fn = !fresh_two ? fresh1_fn : src_kind == TRC_SRC_BUIE_DISK ? SF2_PICK(TRC_SRC_BUIE_DISK) : SF2_PICK(TRC_SRC_BUIE_RECT);
 #undef SF2_PICK
     const void *cull_fn = src_kind == TRC_SRC_BUIE_DISK ? (const void *)k_s_cull<TRC_SRC_BUIE_DISK> : src_kind == TRC_SRC_BUIE_RECT ? (const void *)k_s_cull<TRC_SRC_BUIE_RECT>
+                        : src_kind == TRC_SRC_SUNSHAPE_DISK ? (const void *)k_s_cull<TRC_SRC_SUNSHAPE_DISK>
+                        : src_kind == TRC_SRC_SUNSHAPE_RECT ? (const void *)k_s_cull<TRC_SRC_SUNSHAPE_RECT>
                         : src_kind == TRC_SRC_PILLBOX_DISK ? (const void *)k_s_cull<TRC_SRC_PILLBOX_DISK> : (const void *)k_s_cull<TRC_SRC_PILLBOX_RECT>;
     const size_t lds_cull = (size_t)SP0.fp.P.M * SP0.fp.P.M / 8 + (SC_GEN_CAP + 4) * 4;
     if (lds_cull > 160 * 1024 - 512 || lds_fresh > 160 * 1024 - 512) { F.use_fp = false; return TRC_OK; }
@@ -2524,7 +2529,7 @@ static int stream_form_fresh(StreamForms &F, StreamParams &SP0, trc_scene *sc, S
     TRC_TRY(kernel_grid_cap(cull_fn, SC_THREADS, lds_cull, 2048 / SC_THREADS, n_cu, &F.cull.max_blocks));
     F.general_share = SP0.fp.P.has_generic ? (1.0 - SP0.fp.P.cdf_end) : 0.0;
     if (F.general_share < 0.0) F.general_share = 0.0;
-    F.listed_share = E.fp->coverage * (src_kind == TRC_SRC_BUIE_DISK || src_kind == TRC_SRC_PILLBOX_DISK ? 4.0 / TRC_PI : 1.0);
+    F.listed_share = E.fp->coverage * (src_kind == TRC_SRC_BUIE_DISK || src_kind == TRC_SRC_PILLBOX_DISK || src_kind == TRC_SRC_SUNSHAPE_DISK ? 4.0 / TRC_PI : 1.0);
     if (F.listed_share > 1.0) F.listed_share = 1.0;
     return TRC_OK;
 }
@@ -2554,12 +2559,15 @@ static int stream_form_bounce(StreamForms &F, StreamParams &SP0, const trc_scene
         lds_bounce += (sc->accel.big_occ.size() * 4 + 15) & ~(size_t)15;
     }
     const size_t lds_first = lds_bounce + b_buie;
-#define SB_PICK(FR, FL) (gridm == 3 ? (const void *)k_s_bounce<3, false, FR, FL> : gridm == 2 ? (coop ? (const void *)k_s_bounce_coop<FR, FL> : (const void *)k_s_bounce<2, false, FR, FL>) \
-                       : gridm == 1 ? (in_lds ? (const void *)k_s_bounce<1, true, FR, FL> : (const void *)k_s_bounce<1, false, FR, FL>) \
-                                    : (in_lds ? (const void *)k_s_bounce<0, true, FR, FL> : (const void *)k_s_bounce<0, false, FR, FL>))
+#define SB_PICK(FR, FL, SN) (gridm == 3 ? (const void *)k_s_bounce<3, false, FR, FL, SN> : gridm == 2 ? (coop ? (const void *)k_s_bounce_coop<FR, FL, SN> : (const void *)k_s_bounce<2, false, FR, FL, SN>) \
+                           : gridm == 1 ? (in_lds ? (const void *)k_s_bounce<1, true, FR, FL, SN> : (const void *)k_s_bounce<1, false, FR, FL, SN>) \
+                                        : (in_lds ? (const void *)k_s_bounce<0, true, FR, FL, SN> : (const void *)k_s_bounce<0, false, FR, FL, SN>))
     const bool all_flat = all_surfaces_flat(sc);
-    const void *bounce_fn = all_flat ? SB_PICK(false, true) : SB_PICK(false, false);
-    const void *first_fn = all_flat && gridm == 2 && coop ? (const void *)k_s_bounce_coop<true, true> : SB_PICK(true, false);
+    const void *bounce_fn = all_flat ? SB_PICK(false, true, false) : SB_PICK(false, false, false);
+    // (fresh rays of a tabulated sunshape: the instances that know it)
+    const bool sun = F.src_kind == TRC_SRC_SUNSHAPE_DISK || F.src_kind == TRC_SRC_SUNSHAPE_RECT;
+    const void *first_fn = sun ? (all_flat && gridm == 2 && coop ? (const void *)k_s_bounce_coop<true, true, true> : SB_PICK(true, false, true))
+                               : (all_flat && gridm == 2 && coop ? (const void *)k_s_bounce_coop<true, true> : SB_PICK(true, false, false));
 #undef SB_PICK
     F.bounce = {bounce_fn, SB_THREADS_OF(gridm), lds_bounce, 0u};
     F.first = {first_fn, SB_THREADS_OF(gridm), lds_first, 0u};
@@ -2825,6 +2833,8 @@ static int launch_bounce(StreamCall &C, StreamSlot &T) {
         else if (T.b == 0 && src_kind == TRC_SRC_BUIE_RECT) hipLaunchKernelGGL((k_s_gen<true, TRC_SRC_BUIE_RECT>), dim3(gb_gen), dim3(256), 0, T.stream, SP);
         else if (T.b == 0 && src_kind == TRC_SRC_PILLBOX_DISK) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_PILLBOX_DISK>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
         else if (T.b == 0 && src_kind == TRC_SRC_PILLBOX_RECT) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_PILLBOX_RECT>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
+        else if (T.b == 0 && src_kind == TRC_SRC_SUNSHAPE_DISK) hipLaunchKernelGGL((k_s_gen<true, TRC_SRC_SUNSHAPE_DISK>), dim3(gb_gen), dim3(256), 0, T.stream, SP);
+        else if (T.b == 0 && src_kind == TRC_SRC_SUNSHAPE_RECT) hipLaunchKernelGGL((k_s_gen<true, TRC_SRC_SUNSHAPE_RECT>), dim3(gb_gen), dim3(256), 0, T.stream, SP);
         else if (T.b == 0) hipLaunchKernelGGL(k_s_gen<true>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
         else hipLaunchKernelGGL(k_s_gen<false>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
         TRC_TRY(launch_kernel(F.walk, T.gb_walk, SP, T.stream));

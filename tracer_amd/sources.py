@@ -24,9 +24,11 @@ class LazySourceBundle(RayBundle):
     ray_offset + i.  Any column access generates the rays on the device; an engine that receives an
     untouched LazySourceBundle generates them inside its own kernel instead.
     """
-    def __init__(self, desc, n, seed, ray_offset=0, constant_columns=None, spectrum=None, spectral_columns=('wavelengths', 'ref_index')):
+    def __init__(self, desc, n, seed, ray_offset=0, constant_columns=None, spectrum=None, spectral_columns=('wavelengths', 'ref_index'),
+                 table=None):
         """spectrum: a source_spectrum.SourceSpectrum -- every ray gets a wavelength drawn on the device (the columns
-        `spectral_columns` of the materialised bundle); the bundle stays pending."""
+        `spectral_columns` of the materialised bundle); the bundle stays pending.  table: the SunshapeTable a tabulated
+        sunshape's descriptor names (made on the device when the rays are first needed, kept alive with the bundle)."""
         if spectrum is not None and constant_columns:
             raise ValueError("a source bundle takes a spectrum or constant columns, not both")
         spectral_columns = tuple(spectral_columns) if spectrum is not None else ()
@@ -38,6 +40,7 @@ class LazySourceBundle(RayBundle):
         object.__setattr__(self, '_src_offset', int(ray_offset))
         object.__setattr__(self, '_src_spectrum', spectrum)
         object.__setattr__(self, '_src_spec_cols', spectral_columns)
+        object.__setattr__(self, '_src_table', table)
         object.__setattr__(self, '_src_done', False)
 
     def is_pending(self):
@@ -57,8 +60,13 @@ class LazySourceBundle(RayBundle):
             return self._src_n
         return RayBundle.get_num_rays(self)
 
+    def _bound_desc(self):
+        if self._src_table is not None:
+            self._src_desc.table = self._src_table.table_id()
+        return self._src_desc
+
     def source_args(self):
-        return self._src_desc, self._src_n, self._src_seed, self._src_offset
+        return self._bound_desc(), self._src_n, self._src_seed, self._src_offset
 
     def _materialize(self):
         if self._src_done:
@@ -74,7 +82,7 @@ class LazySourceBundle(RayBundle):
         wl = _cabi.pinned_empty(n) if 'wavelengths' in self._src_spec_cols else None
         ref = _cabi.pinned_empty(n) if 'ref_index' in self._src_spec_cols else None
         rays = _cabi.make_rays(n, v[0], v[1], v[2], d[0], d[1], d[2], e, ref_index=ref, wavelength=wl)
-        _cabi.check(ctx.lib.trc_source_generate_x(ctx.handle, C.byref(self._src_desc),
+        _cabi.check(ctx.lib.trc_source_generate_x(ctx.handle, C.byref(self._bound_desc()),
                                                   C.byref(spec.desc()) if spec is not None else None, n, self._src_seed,
                                                   self._src_offset, C.byref(rays)))
         self._cols['vertices'] = v
@@ -109,14 +117,15 @@ def _fill_source(kind, center, rot_pos, rot_dir, params, energy, buie=None):
     return s
 
 
-def _new_bundle(desc, num_rays, seed, ray_offset, constant_columns=None, spectrum=None, spectral_columns=('wavelengths', 'ref_index')):
+def _new_bundle(desc, num_rays, seed, ray_offset, constant_columns=None, spectrum=None, spectral_columns=('wavelengths', 'ref_index'),
+                table=None):
     if seed is None:
         seed = rng.next_seed()
     if spectrum is not None:
         from .source_spectrum import SourceSpectrum
         if not isinstance(spectrum, SourceSpectrum):
             raise TypeError("spectrum must be a SourceSpectrum, got %r" % (type(spectrum).__name__,))
-    return LazySourceBundle(desc, int(num_rays), seed, ray_offset, constant_columns, spectrum, spectral_columns)
+    return LazySourceBundle(desc, int(num_rays), seed, ray_offset, constant_columns, spectrum, spectral_columns, table)
 
 
 def _tilt_cos(rays_direction, direction):
@@ -418,6 +427,151 @@ def rect_buie_sunshape(num_rays, center, direction, width, height, CSR, flux=Non
     desc = _fill_source(_cabi.SRC_BUIE_RECT, center, rotation_to_z(direction), rotation_to_z(rays_direction),
                         [width, height], energy, buie_table(CSR, pre_process_CSR))
     return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum)
+
+
+def sunshape_to_ray_directions(angles, norm_intensity, num_rays):
+    """
+    Directions about +z drawn from a tabulated sunshape on the host (sources.py:386-410), with numpy's global generator and
+    in the reference's order (all polar uniforms, then all azimuths), so that under the same numpy.random.seed it returns the
+    reference's (3, num_rays) array.  The polar angle has the density that interpolates g = I cos(theta) sin(theta) linearly
+    between the points.  As in the reference, draws at or beyond the last entry of its CDF (which can round below 1) keep
+    theta = 0; the device sources (tabulated_sunshape) use a CDF that ends at exactly 1.
+    """
+    angles = N.asarray(angles, dtype=float)
+    norm_intensity = N.asarray(norm_intensity, dtype=float)
+    num_rays = int(num_rays)
+    thetas = N.zeros(num_rays)
+    R_thetas = N.random.uniform(size=num_rays)
+    g = norm_intensity * N.cos(angles) * N.sin(angles)
+    integ = 0.5 * (g[:-1] + g[1:]) * (angles[1:] - angles[:-1])
+    total = N.sum(integ)
+    CDF = N.add.accumulate(N.hstack(([0.], integ / total)))
+    for i in range(len(CDF) - 1):
+        sl = N.logical_and(R_thetas >= CDF[i], R_thetas < CDF[i + 1])
+        if not N.any(sl):
+            continue
+        A, B = g[i], g[i + 1]
+        if A == B:
+            thetas[sl] = angles[i] + total * (R_thetas[sl] - CDF[i]) / A
+        else:
+            Cq = 2. * total * (R_thetas[sl] - CDF[i]) * (angles[i + 1] - angles[i])
+            thetas[sl] = -(-A * angles[i + 1] + B * angles[i] + N.sqrt(((angles[i] - angles[i + 1]) * A) ** 2. + Cq * (B - A))) / (A - B)
+    phis = N.random.uniform(high=2. * N.pi, size=num_rays)
+    sin_th = N.sin(thetas)
+    return N.vstack((N.cos(phis) * sin_th, N.sin(phis) * sin_th, N.cos(thetas)))
+
+
+def check_sunshape_table(angles, norm_intensity):
+    """The table of a tabulated sunshape as two float64 arrays; ValueError unless it has 2..4096 points, finite angles
+    strictly increasing in [0, pi/2), finite non-negative intensities and a positive mass (the checks of trc_sunshape_create)."""
+    a = N.ascontiguousarray(N.ravel(N.asarray(angles, dtype=float)))
+    I = N.ascontiguousarray(N.ravel(N.asarray(norm_intensity, dtype=float)))
+    if a.shape != I.shape:
+        raise ValueError("sunshape table: %d angles but %d intensities" % (a.size, I.size))
+    if not 2 <= a.size <= _cabi.SUNSHAPE_MAX_POINTS:
+        raise ValueError("sunshape table: 2..%d points, got %d" % (_cabi.SUNSHAPE_MAX_POINTS, a.size))
+    if not N.all(N.isfinite(a)) or not N.all(a[1:] > a[:-1]):
+        raise ValueError("sunshape table: the angles must be finite and strictly increasing")
+    if not (a[0] >= 0. and a[-1] < N.pi / 2.):
+        raise ValueError("sunshape table: the angles must lie in [0, pi/2)")
+    if not N.all(N.isfinite(I)) or N.any(I < 0.):
+        raise ValueError("sunshape table: the intensities must be finite and non-negative")
+    g = I * N.cos(a) * N.sin(a)
+    mass = N.sum(0.5 * (g[:-1] + g[1:]) * (a[1:] - a[:-1]))
+    if not (mass > 0. and N.isfinite(mass)):
+        raise ValueError("sunshape table: the table has no mass")
+    return a, I
+
+
+class SunshapeTable(object):
+    """
+    A checked tabulated sunshape.  Its packed table (include/tracer_amd.h, trc_sunshape) is made on the device on first use
+    and freed with the object; sunshape_table() hands out one object per content, so that a Monte-Carlo loop that makes a bundle
+    per batch uploads the table once.
+    """
+    def __init__(self, angles, norm_intensity):
+        self.angles, self.intensity = check_sunshape_table(angles, norm_intensity)
+        self._handle = None
+        self._lib = None
+        self._id = 0
+
+    def table_id(self):
+        """the id a descriptor names the device table by (trc_sunshape_create on the current device on first call)"""
+        if self._handle is None:
+            ctx = _cabi.get_context()
+            h = C.c_void_p()
+            _cabi.check(ctx.lib.trc_sunshape_create(ctx.handle, self.angles.size, _cabi.ptr(self.angles),
+                                                    _cabi.ptr(self.intensity), C.byref(h)))
+            i = C.c_int32()
+            _cabi.check(ctx.lib.trc_sunshape_id(h, C.byref(i)))
+            self._handle, self._lib, self._id = h, ctx.lib, int(i.value)
+        return self._id
+
+    def packed(self):
+        """(theta, g, cdf, theta_c, u_c) of the device table, as the library packed them"""
+        self.table_id()
+        n = self.angles.size
+        tab = N.empty(3 * n)
+        tc, uc = C.c_double(), C.c_double()
+        _cabi.check(self._lib.trc_sunshape_get(self._handle, None, _cabi.ptr(tab), C.byref(tc), C.byref(uc)))
+        return tab[:n], tab[n:2 * n], tab[2 * n:], tc.value, uc.value
+
+    def destroy(self):
+        if self._handle is not None:
+            h, lib = self._handle, self._lib
+            self._handle = self._lib = None
+            lib.trc_sunshape_destroy(h)
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+_sunshape_tables = {}
+
+
+def sunshape_table(angles, norm_intensity):
+    """the SunshapeTable of this content (cached like buie_table)"""
+    a, I = check_sunshape_table(angles, norm_intensity)
+    key = (a.tobytes(), I.tobytes())
+    t = _sunshape_tables.get(key)
+    if t is None:
+        if len(_sunshape_tables) > 64:
+            _sunshape_tables.clear()        # (bundles still hold theirs)
+        t = _sunshape_tables[key] = SunshapeTable(a, I)
+    return t
+
+
+def tabulated_sunshape(num_rays, center, direction, radius, angles, norm_intensity, flux=None, rays_direction=None, seed=None,
+                       ray_offset=0, spectrum=None):
+    """
+    Disc source with a tabulated sunshape (sources.py:386-410): start points and energies as buie_sunshape, polar angles drawn
+    on the device from the table (angles in rad, intensities per unit solid angle), azimuths uniform.  Draws of ray i (event 0,
+    block 0): u0, u1 the position, u2 the polar angle, u3 the azimuth -- the Buie source's, so that the Buie CSR-0 nodes as a
+    table give buie_sunshape(CSR=0)'s rays.
+    """
+    table = sunshape_table(angles, norm_intensity)
+    direction = N.asarray(direction, dtype=float)
+    if rays_direction is None:
+        rays_direction = direction
+    energy = flux * (N.pi * radius ** 2.) / num_rays * _tilt_cos(rays_direction, direction)
+    desc = _fill_source(_cabi.SRC_SUNSHAPE_DISK, center, rotation_to_z(direction), rotation_to_z(rays_direction), [radius], energy)
+    return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum, table=table)
+
+
+def rect_tabulated_sunshape(num_rays, center, direction, width, height, angles, norm_intensity, flux=None, rays_direction=None,
+                            seed=None, ray_offset=0, spectrum=None):
+    """Rectangular source with a tabulated sunshape: start points and energies as rect_buie_sunshape (sources.py:466-515)."""
+    table = sunshape_table(angles, norm_intensity)
+    direction = N.asarray(direction, dtype=float)
+    if rays_direction is None:
+        rays_direction = direction
+    energy = flux * (width * height) / num_rays * _tilt_cos(rays_direction, direction)
+    desc = _fill_source(_cabi.SRC_SUNSHAPE_RECT, center, rotation_to_z(direction), rotation_to_z(rays_direction),
+                        [width, height], energy)
+    return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum, table=table)
 
 
 def single_ray_source(position, direction, flux=None):
