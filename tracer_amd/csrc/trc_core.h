@@ -88,6 +88,16 @@ TRC_HD int trc_gm_nparams(int kind) {
 //   counter = (rid_lo, rid_hi, event, block)   key = (seed_lo, seed_hi)
 //   event 0 = source generation; event k>=1 = the k-th surface interaction of the ray.
 // ---------------------------------------------------------------------------------------------
+// a ^ b ^ c: on gfx950 one v_bitop3_b32 (truth table 0x96) where the compiler emits two v_xor_b32 for Philox's chains
+// (tools/ubench/bitop3.hip: the same rate as one v_xor_b32); elsewhere, and on the host, the plain expression
+TRC_HD uint32_t trc_xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+    return a ^ b ^ c;
+#endif
+}
+
 TRC_HD void trc_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                               uint32_t k1, uint32_t out[4]) {
     const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
@@ -95,9 +105,9 @@ TRC_HD void trc_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3
     for (int r = 0; r < 10; ++r) {
         uint64_t p0 = (uint64_t)M0 * c0;
         uint64_t p1 = (uint64_t)M1 * c2;
-        uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+        uint32_t n0 = trc_xor3((uint32_t)(p1 >> 32), c1, k0);
         uint32_t n1 = (uint32_t)p1;
-        uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        uint32_t n2 = trc_xor3((uint32_t)(p0 >> 32), c3, k1);
         uint32_t n3 = (uint32_t)p0;
         c0 = n0; c1 = n1; c2 = n2; c3 = n3;
         k0 += W0; k1 += W1;
