@@ -328,7 +328,8 @@ int trc_scene_set_hit_capacity(trc_scene *scene, int64_t capacity);
 int trc_scene_clear_hits(trc_scene *scene);
 /* A hit buffer of at least `capacity` hits that keeps what it holds (set_hit_capacity starts an empty one): the accountants of
    the reference accumulate over calls until they are reset (optics_callables.py:1577-1643), so a script that traces again
-   before it has read the hits of its last call leaves them on the device and reads them all at once later. */
+   before it has read the hits of its last call leaves them on the device and reads them all at once later.  Their spectral
+   columns (trc_scene_get_hits_x) are kept too. */
 int trc_scene_reserve_hits(trc_scene *scene, int64_t capacity);
 /* entries of the hit buffer reserved so far -- written hits and the unused parts of the chunks the streaming engine keeps
    open -- and the capacity last asked for.  Either pointer may be NULL. */
@@ -351,7 +352,9 @@ int trc_scene_get_hits(trc_scene *scene, int64_t *n, int32_t *surf, double *e_ab
                        double *px, double *py, double *pz, double *dx, double *dy, double *dz);
 /* The same with the spectra of polychromatic hits (trc_trace_fast on a bundle with spectra, k_s_shade_x): n_x = 3 W more columns per
    hit, x[k * n + i] for hit i -- k in [0, W): sample wavelengths, [W, 2W): the spectrum that arrived, [2W, 3W): the spectrum that
-   left (optics_callables.py:1825-1848 takes their difference).  trc_scene_hit_spectral_columns: the n_x the buffer holds (0: none). */
+   left (optics_callables.py:1825-1848 takes their difference).  trc_scene_hit_spectral_columns: the n_x the buffer holds (0: none).
+   All hits in the buffer have the same n_x: a trc_trace_fast call whose captured hits would have another one than those the
+   buffer holds fails with TRC_ERR_INVALID before it starts (read or clear them first). */
 int trc_scene_get_hits_x(trc_scene *scene, int64_t *n, int32_t *surf, double *e_abs, double *e_in, double *px, double *py,
                          double *pz, double *dx, double *dy, double *dz, int32_t n_x, double *x);
 int trc_scene_hit_spectral_columns(trc_scene *scene, int32_t *n_x);

@@ -318,6 +318,139 @@ def test_polychromatic_bundle_on_the_fast_path(ctx):
     assert len(e5) > 1.9 * h[0] and s5.shape[1] == len(e5) and N.allclose(s5[:, :h[0]][:, k3], s4[:, k4], rtol=1e-9, atol=1e-6)
 
 
+def _poly_rays(n, seed=8, W=9, spectra=True):
+    """the rays of the polychromatic tests above, from z = 1 down; spectra=False: the same rays without their spectra"""
+    from tracer_amd.ray_bundle import RayBundle
+    rng = N.random.RandomState(seed)
+    v = N.vstack((rng.uniform(-1, 1, n), rng.uniform(-1, 1, n), N.full(n, 1.)))
+    d = N.vstack((rng.uniform(-0.4, 0.4, n), rng.uniform(-0.4, 0.4, n), -N.ones(n)))
+    d /= N.sqrt(N.sum(d ** 2, axis=0))
+    swl = N.sort(rng.uniform(0.3e-6, 2.5e-6, size=(W, n)), axis=0)
+    spec = rng.uniform(0.5, 2., size=(W, n)) * 1e6
+    e = N.trapezoid(spec, swl, axis=0)
+    if not spectra:
+        return RayBundle(vertices=v, directions=d, energy=e)
+    return RayBundle(vertices=v, directions=d, energy=e, spectra=spec, wavelengths=swl)
+
+
+def _receiver_box(log=False):
+    """_poly_scene with a plain diffuse receiver for a floor: rays with and without spectra both trace it.  log: the floor also
+    keeps, call by call, what the fast engine delivers of each hit -- hit point, absorbed energy and, when it has them, its spectra"""
+    from tracer_amd import optics_callables as opt
+    from tracer_amd.assembly import Assembly
+    from tracer_amd.object import AssembledObject
+    from tracer_amd.surface import Surface
+    from tracer_amd.flat_surface import RectPlateGM
+    from tracer_amd.spatial_geometry import translate, rotx
+    from tracer_amd.deferred import settle_marks
+
+    class HitLog(opt.Accountant):
+        def feed(self, hit):
+            e = hit['e_abs'] if 'e_abs' in hit else hit['e_in'] - hit['e_out']
+            sp = N.vstack((hit['wavelengths'], hit['spectra_in'], hit['spectra_out'])) if 'spectra_in' in hit else None
+            self._data.append((N.array(hit['points']), N.array(e), sp))
+
+        def chunks(self):
+            settle_marks(self)
+            return self._data
+
+    floor_opt = opt.LambertianReceiver(0.6)
+    if log:
+        floor_opt.accountants.append(HitLog())
+    floor = AssembledObject(surfs=[Surface(RectPlateGM(4., 4.), floor_opt)], transform=translate(0., 0., 0.))
+    roof = AssembledObject(surfs=[Surface(RectPlateGM(4., 4.), opt.Reflective(0.1))], transform=N.dot(translate(0., 0., 1.5), rotx(N.pi)))
+    side = AssembledObject(surfs=[Surface(RectPlateGM(4., 1.5), opt.Lambertian(0.3))], transform=N.dot(translate(0., 2., 0.75), rotx(N.pi / 2.)))
+    return Assembly(objects=[floor, roof, side]), (floor_opt.accountants[-1] if log else None)
+
+
+def _same_hits(a, b):
+    for k in ('surf', 'e_abs', 'e_in', 'points', 'directions'):
+        assert (a[k] is None and b[k] is None) or N.array_equal(a[k], b[k]), k
+    assert ('spectra' in a) == ('spectra' in b)
+    if 'spectra' in a:
+        for x, y in zip(a['spectra'], b['spectra']):
+            assert N.array_equal(x, y)
+
+
+def test_reserve_hits_keeps_the_spectra_of_pending_hits(ctx):
+    """
+    Hits of polychromatic rays wait in a small hit buffer; growing it (trc_scene_reserve_hits) keeps them with their spectra:
+    read after the growth they are what they were before it, entry by entry.
+    """
+    from tracer_amd.scene import compile_scene, DeviceScene
+    n = 5000
+    dev = DeviceScene(compile_scene(_poly_scene()[0]), ctx)
+    try:
+        dev.set_hit_capacity(4 * n)
+        dev.trace_fast(_poly_rays(n), 6, 1e-9, 33, stream=True)
+        before = dev.get_hits()
+        assert len(before['surf']) > n and before['spectra'][0].shape == (9, len(before['surf']))
+        dev.reserve_hits(40 * n)
+        assert dev.hit_capacity == 40 * n
+        _same_hits(dev.get_hits(), before)
+    finally:
+        dev.close()
+
+
+def test_hits_of_another_spectral_shape_are_refused_at_the_c_abi(ctx):
+    """
+    All hits waiting in the buffer have the same spectral columns.  A fast call whose hits would have other ones -- a plain
+    bundle behind hits with spectra, or the reverse -- fails with TRC_ERR_INVALID before it starts: the waiting hits, their
+    spectra and the tallies are as they were.
+    """
+    from tracer_amd import _cabi
+    from tracer_amd.scene import compile_scene, DeviceScene
+    n = 5000
+    dev = DeviceScene(compile_scene(_receiver_box()[0]), ctx)
+    try:
+        for first, second in ((True, False), (False, True)):
+            dev.set_hit_capacity(8 * n)
+            dev.lib.trc_scene_clear_hits(dev.handle)
+            dev.trace_fast(_poly_rays(n, spectra=first), 6, 1e-9, 33, stream=True)
+            held, tallies = dev.get_hits(), dev.get_tallies()
+            assert len(held['surf']) > n // 2 and ('spectra' in held) == first
+            with pytest.raises(_cabi.TracerAmdError) as err:
+                dev.trace_fast(_poly_rays(n, seed=9, spectra=second), 6, 1e-9, 34, stream=True)
+            assert err.value.status == _cabi.ERR_INVALID and 'spectral columns' in str(err.value)
+            _same_hits(dev.get_hits(), held)
+            for x, y in zip(dev.get_tallies(), tallies):
+                assert N.array_equal(x, y)
+    finally:
+        dev.close()
+
+
+@pytest.mark.parametrize('n2', [500, 20000])
+def test_hits_of_another_spectral_shape_are_delivered_first(ctx, n2):
+    """
+    A call with spectra, then a plain one, without a read in between: what an accountant of the capturing surface holds then is
+    what it holds when each call is read on its own -- chunk by chunk, hit by hit, spectra included.  The second call is small
+    (500 rays: the buffer had room for its hits) or large (20000: the buffer would have had to grow).
+    """
+    from tracer_amd.tracer_engine import TracerEngine
+
+    def run(read_between):
+        asm, log = _receiver_box(log=True)
+        eng = TracerEngine(asm)
+        eng.ray_tracer(_poly_rays(20000), reps=6, min_energy=1e-9, tree=False, seed=33)
+        assert eng.stats['engine'] == 'fast'
+        if read_between:
+            log.chunks()
+        eng.ray_tracer(_poly_rays(n2, seed=9, spectra=False), reps=6, min_energy=1e-9, tree=False, seed=34)
+        assert eng.stats['engine'] == 'fast'
+        return log.chunks()
+
+    got, ref = run(False), run(True)
+    assert len(got) == len(ref) == 2
+    assert ref[0][2] is not None and ref[1][2] is None
+    for (p, e, sp), (pr, er, spr) in zip(got, ref):
+        o, orr = N.lexsort((e, p[1], p[0])), N.lexsort((er, pr[1], pr[0]))
+        assert len(e) == len(er) > 0
+        assert N.array_equal(p[:, o], pr[:, orr]) and N.array_equal(e[o], er[orr])
+        assert (sp is None) == (spr is None)
+        if sp is not None:
+            assert N.array_equal(sp[:, o], spr[:, orr])
+
+
 def test_polychromatic_wall_without_spectra_is_an_error(ctx):
     from tracer_amd.tracer_engine import TracerEngine
     from tracer_amd._cabi import TracerAmdError

@@ -200,8 +200,34 @@ __device__ __forceinline__ unsigned long long chunk_append(unsigned long long *c
 #define TRC_HIT_HOLDERS (4ll * SHADE_MAX_WAVES)   /* waves that can hold an open chunk of the hit buffer: SHADE_MAX_WAVES per slot (the shading
                                                     kernels of a slot run one after another, wave w of each continues the chunk wave w of the
                                                     one before left open), four slots at most */
+// The open chunk of the hit buffer a wave of a shading kernel carries to the next launch, in two words of its state `st`: the
+// chunk's base, and epoch << 32 | used << 1 | open.  A chunk left open under another epoch (the buffer was emptied or wound back
+// since) is stale.  Each kernel calls these under its own gate: capturing, and the wave is one that keeps its chunk.
+__device__ __forceinline__ void hit_chunk_resume(WaveChunk &hc, const unsigned long long *st, unsigned epoch) {
+    const unsigned long long w = st[1];
+    if ((unsigned)(w >> 32) == epoch && (w & 1ull)) { hc.base = st[0]; hc.used = (unsigned)(w >> 1) & 0x7FFFFFFFu; hc.open = 1; }
+}
+__device__ __forceinline__ void hit_chunk_suspend(const WaveChunk &hc, unsigned long long *st, unsigned epoch) {
+    st[0] = hc.base;
+    st[1] = ((unsigned long long)epoch << 32) | ((unsigned long long)hc.used << 1) | (hc.open ? 1ull : 0ull);
+}
+
 #define TRC_SURF_TERMINAL 0x10000   /* device copy of the surface flags only: every ray that lands here ends here -- the optics absorb all of
                                        it whatever the angle (absorptivity 1, no incidence-angle factor): no direction needs to be drawn */
+
+// a captured hit on surface s (flags fl) into entry `slot` of the hit buffer, or counted as dropped beyond its end.  A lean capture
+// (TRC_SURF_CAPTURE_LEAN) writes neither the incident energy (column 1) nor the direction (columns 5-7).
+__device__ __forceinline__ void hit_store(const DScene &sc, unsigned long long slot, int s, int fl, double e_in, double e_abs, double hx,
+                                          double hy, double hz, double dx, double dy, double dz) {
+    if ((long long)slot < sc.hit_cap) {
+        sc.h_surf[slot] = s;
+        sc.h_eabs[slot] = e_abs;
+        sc.h_px[slot] = hx; sc.h_py[slot] = hy; sc.h_pz[slot] = hz;
+        if (!(fl & TRC_SURF_CAPTURE_LEAN)) { sc.h_ein[slot] = e_in; sc.h_dx[slot] = dx; sc.h_dy[slot] = dy; sc.h_dz[slot] = dz; }
+    } else {
+        atomicAdd(&sc.counters[1], 1ull);
+    }
+}
 
 // per-hit bookkeeping shared by both engines: tallies, flux map, hit capture
 template <bool LDS_TALLY>
@@ -249,14 +275,7 @@ __device__ __forceinline__ void record_hit(const DScene &sc, double *lds_tally, 
         unsigned long long slot = chunk_append(&sc.counters[0], *hc, want, nullptr, 0);
         if (slot_out) *slot_out = (want && (long long)slot < sc.hit_cap) ? slot : ~0ull;
         if (want) {
-            if ((long long)slot < sc.hit_cap) {
-                sc.h_surf[slot] = s;
-                sc.h_eabs[slot] = e_abs;
-                sc.h_px[slot] = hx; sc.h_py[slot] = hy; sc.h_pz[slot] = hz;
-                if (!(fl & TRC_SURF_CAPTURE_LEAN)) { sc.h_ein[slot] = e_in; sc.h_dx[slot] = dx; sc.h_dy[slot] = dy; sc.h_dz[slot] = dz; }
-            } else {
-                atomicAdd(&sc.counters[1], 1ull);
-            }
+            hit_store(sc, slot, s, fl, e_in, e_abs, hx, hy, hz, dx, dy, dz);
         }
     } else if (capture_enabled) {
         // wave-aggregated append: one atomic per wave per iteration
@@ -270,14 +289,7 @@ __device__ __forceinline__ void record_hit(const DScene &sc, double *lds_tally, 
             base = __shfl(base, leader, 64);
             if (want) {
                 unsigned long long slot = base + __popcll(mask & ((1ull << lane_id()) - 1ull));
-                if ((long long)slot < sc.hit_cap) {
-                    sc.h_surf[slot] = s;
-                    sc.h_eabs[slot] = e_abs;
-                    sc.h_px[slot] = hx; sc.h_py[slot] = hy; sc.h_pz[slot] = hz;
-                    if (!(fl & TRC_SURF_CAPTURE_LEAN)) { sc.h_ein[slot] = e_in; sc.h_dx[slot] = dx; sc.h_dy[slot] = dy; sc.h_dz[slot] = dz; }
-                } else {
-                    atomicAdd(&sc.counters[1], 1ull);
-                }
+                hit_store(sc, slot, s, fl, e_in, e_abs, hx, hy, hz, dx, dy, dz);
             }
         }
     }

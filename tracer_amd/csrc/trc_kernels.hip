@@ -275,6 +275,82 @@ struct trc_ctx {
     int n_cu;
 };
 
+// The fast engine's hit buffer, where the hits on capturing surfaces wait until a script reads them: eight columns (absorbed and
+// incident energy, hit point, direction) and the surface of every entry, -1 for an entry not written.  Hits of polychromatic rays
+// bring 3 W spectral columns more: per hit the W sample wavelengths, the W samples of the spectrum that arrived and the W that left
+// (k_s_shade_x).  All pending hits have the same spectral shape, and spectral columns, when there are any, have the `cap` rows of
+// the others.  The cursor (entries reserved so far) and the count of dropped hits are words 0 and 1 of the scene's counter block:
+// the methods that need the cursor are handed it.
+struct HitBuffer {
+    DevBuf<int32_t> surf;
+    DevBuf<double> col[8];
+    DevBuf<double> x;        // x_cols spectral columns, column k at x + k * cap
+    int x_cols = 0;
+    int64_t cap = 0;         // entries allocated: the capacity asked for + room for what the streaming engine's open chunks leave unused
+    int64_t cap_user = 0;    // the capacity asked for
+    uint32_t epoch = 0;      // bumped whenever the cursor is reset or wound back: chunks left open by earlier launches are stale
+    uint32_t chunk = 0;      // entries a wave of the streaming engine's shading kernels reserves per atomic (set with the capacity)
+    int64_t dirty_to = 0;    // entries [0, dirty_to) may have been written since the buffer was last emptied: emptying 2e8 entries
+                             // for the 6e6 a trace used was 0.9 GB of memset, twice per call of the public entry point
+
+    // surface -1 (not written) over n entries from s: the only writer of that mark on the host
+    static hipError_t unwrite(int32_t *s, int64_t n) { return n > 0 ? hipMemset(s, 0xFF, (size_t)n * sizeof(int32_t)) : hipSuccess; }
+    int64_t used(unsigned long long cursor) const { return cursor < (unsigned long long)cap ? (int64_t)cursor : cap; }
+    unsigned chunk_size() const { return chunk ? chunk : SQ_HIT_CHUNK; }
+    int set_capacity(int64_t capacity);
+    int allocate(int64_t capacity, int64_t slack, int64_t keep);
+    // room for at least `capacity` hits, half as much again at least, keeping entries [0, cursor); the chunk size stays (chunks
+    // left open by earlier launches go on being filled)
+    int grow(int64_t capacity, unsigned long long cursor) {
+        return allocate(capacity > cap_user + cap_user / 2 ? capacity : cap_user + cap_user / 2, cap - cap_user, used(cursor));
+    }
+    // forget the captured hits (the caller zeroes the cursor): every entry unwritten, open chunks stale
+    int reset() {
+        epoch += 1;
+        HIP_TRY(unwrite(surf.get(), dirty_to < cap ? dirty_to : cap));
+        dirty_to = 0;
+        return TRC_OK;
+    }
+    // a fast call may write any entry until it says how far it got: what begin_call returns goes to end_call with the cursor then
+    int64_t begin_call() { const int64_t before = dirty_to; dirty_to = cap; return before; }
+    void end_call(int64_t before, unsigned long long cursor) {      // (every entry written lies below the cursor: chunks are reserved by advancing it)
+        const int64_t cur = used(cursor);
+        dirty_to = cur > before ? cur : before;
+    }
+    // the call that found the cursor at `cursor` failed part way: the hits its completed bounces captured are unwritten again, the
+    // cursor (d_cursor) goes back and the chunks they left open are stale
+    void rollback(unsigned long long *d_cursor, unsigned long long cursor) {
+        unsigned long long now = 0;
+        (void)hipDeviceSynchronize();
+        if (cap > 0 && hipMemcpy(&now, d_cursor, sizeof(now), hipMemcpyDeviceToHost) == hipSuccess && now > cursor) {
+            const int64_t end = used(now);
+            if (end > (int64_t)cursor) (void)unwrite(surf.get() + cursor, end - (int64_t)cursor);
+            (void)hipMemcpy(d_cursor, &cursor, sizeof(cursor), hipMemcpyHostToDevice);
+        }
+        epoch += 1;
+    }
+    // the spectral columns for a call whose hits carry `cols` of them (0: none), made or dropped as the call needs: a call whose
+    // hits would differ in shape from those the buffer holds (cursor > 0) is refused
+    int spectra_for(int cols, unsigned long long cursor, double **out) {
+        *out = nullptr;
+        if (cols != x_cols) {
+            if (cursor != 0)
+                return trc_fail(TRC_ERR_INVALID, "the hit buffer holds hits with %d spectral columns, this call's would have %d: read or clear them first", x_cols, cols);
+            x.reset(); x_cols = 0;
+            if (cols > 0) { TRC_TRY(x.alloc((size_t)cols * (size_t)cap)); x_cols = cols; }
+        }
+        *out = x.get();
+        return TRC_OK;
+    }
+    void fill(DScene &d) const {
+        d.hit_cap = cap; d.h_surf = surf.get();
+        d.h_eabs = col[0].get(); d.h_ein = col[1].get(); d.h_px = col[2].get(); d.h_py = col[3].get(); d.h_pz = col[4].get();
+        d.h_dx = col[5].get(); d.h_dy = col[6].get(); d.h_dz = col[7].get();
+    }
+    int read(hipStream_t stream, const std::vector<trc_surface_desc> &surfs, const int32_t *d_sflags, unsigned long long cursor,
+             int64_t *n, int32_t *surf_out, double *const dst[8], int32_t n_x, double *x_out) const;
+};
+
 struct trc_scene {
     trc_ctx *ctx;
     int32_t n_surf, stride, n_extra;
@@ -327,17 +403,7 @@ struct trc_scene {
     bool cnt_host_ok;                 // them back before it starts.  Every other writer of d_counters updates or drops the copy.
     DevBuf<double> d_last[7];         // device side of trc_trace_fast's `last` bundle, kept between calls (seven hipMalloc / hipFree per
     int64_t d_last_cap;               // call were a millisecond of a Monte-Carlo loop's 1e6-ray calls)
-    int64_t hit_dirty_to;             // entries [0, hit_dirty_to) of the hit buffer may have been written since it was last emptied: emptying
-                                      // 2e8 entries for the 6e6 a trace used was 0.9 GB of memset, twice per call of the public entry point
-    int64_t hit_cap;      // entries allocated: the capacity asked for + TRC_HIT_SLACK
-    int64_t hit_cap_user;
-    uint32_t hit_epoch;   // bumped whenever the cursor is reset: chunks left open by earlier launches are stale
-    uint32_t hit_chunk;   // entries a wave of the streaming engine's shading kernels reserves per atomic (set with the capacity)
-    DevBuf<int32_t> d_h_surf;
-    DevBuf<double> d_h[8];
-    DevBuf<double> d_hx;  // polychromatic hits: hx_cols more columns of the hit buffer (column k at d_hx + k * hx_cap): per hit the W sample
-    int hx_cols;          // wavelengths, the W samples of the spectrum that arrived and the W that left (k_s_shade_x)
-    int64_t hx_cap;
+    HitBuffer hits;
 };
 
 // what rays of the ordered engine carry beyond the nine columns: rows of one matrix `pay` (row r of ray i at pay[r * n + i]):
@@ -1567,7 +1633,6 @@ extern "C" int trc_scene_create(trc_ctx *ctx, int32_t n_surf, const trc_surface_
     sc->ctx = ctx;
     sc->src_host_ok = false;
     sc->cnt_host_ok = false;
-    sc->hit_dirty_to = 0;
     sc->d_last_cap = 0;
     memset(sc->cnt_host, 0, sizeof(sc->cnt_host));
     sc->n_surf = n_surf;
@@ -1579,7 +1644,6 @@ extern "C" int trc_scene_create(trc_ctx *ctx, int32_t n_surf, const trc_surface_
     sc->splits = splits;
     sc->carries = carries;
     sc->has_kd = false;
-    sc->hit_cap = 0;
     sc->fm_of_surf_h.assign(n_surf, -1);
     TRC_TRY(sc->d_recs.alloc((size_t)n_surf * sc->stride));
     TRC_TRY(sc->d_opt.alloc((size_t)n_surf * 8));
@@ -1698,92 +1762,88 @@ extern "C" int trc_scene_set_fluxmap(trc_scene *sc, int32_t surf, int32_t nu, in
     return TRC_OK;
 }
 
-static int scene_reset_hit_buffer(trc_scene *sc);
+// the cursor of the hit buffer (word 0 of the counter block) once the context's stream has finished
+static int scene_hit_cursor(trc_scene *sc, unsigned long long *cursor) {
+    HIP_TRY(hipSetDevice(sc->ctx->device));
+    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
+    HIP_TRY(hipMemcpy(cursor, sc->d_counters.get(), sizeof(*cursor), hipMemcpyDeviceToHost));
+    return TRC_OK;
+}
+
 extern "C" int trc_scene_set_hit_capacity(trc_scene *sc, int64_t capacity) {
     if (!sc || capacity < 0) return trc_fail(TRC_ERR_INVALID, "bad arguments");
     HIP_TRY(hipSetDevice(sc->ctx->device));
     HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
+    HIP_TRY(hipMemset(sc->d_counters.get(), 0, 2 * sizeof(unsigned long long)));      // cursor and dropped count start over
+    sc->cnt_host[0] = sc->cnt_host[1] = 0ull;
+    return sc->hits.set_capacity(capacity);
+}
+
+int HitBuffer::set_capacity(int64_t capacity) {
     // the same capacity again (an engine sizes the buffer before every trace): the buffer is kept and emptied -- freeing and
     // allocating 15 GB per call was a tenth of a second at 1e8 rays
-    if (capacity > 0 && capacity == sc->hit_cap_user && sc->d_h_surf.get()) {
-        HIP_TRY(hipMemset(sc->d_counters.get(), 0, 2 * sizeof(unsigned long long)));      // cursor and dropped count start over
-        sc->cnt_host[0] = sc->cnt_host[1] = 0ull;
-        return scene_reset_hit_buffer(sc);
-    }
-    sc->d_h_surf.reset();
-    for (auto &col : sc->d_h) col.reset();
-    sc->d_hx.reset(); sc->hx_cols = 0; sc->hx_cap = 0;      // (made again by the next call that brings spectra)
-    sc->hit_cap = 0;
-    sc->hit_cap_user = 0;
-    sc->hit_epoch += 1;
-    HIP_TRY(hipMemset(sc->d_counters.get(), 0, 2 * sizeof(unsigned long long)));
-    sc->cnt_host[0] = sc->cnt_host[1] = 0ull;
+    if (capacity > 0 && capacity == cap_user) return reset();
+    const uint32_t e = epoch + 1;
+    *this = HitBuffer();      // (spectral columns are made again by the next call that brings spectra)
+    epoch = e;
     if (capacity == 0) return TRC_OK;
     // The streaming engine appends in chunks that stay open between launches: room for what they can leave unused.  The chunk
     // follows the buffer -- 1024 entries per atomic for the buffers of full-size runs (the cursor is one word), less for modest
     // ones -- and the slack is what every wave that can hold an open chunk may leave unused of one: a call whose hits fit the
     // capacity asked for never drops one, whatever its size.
-    int64_t chunk = 64;          // (never below a wave's worth: one append of a wave must fit a fresh chunk)
-    while (chunk < SQ_HIT_CHUNK && 2048 * (chunk * 2) <= capacity) chunk *= 2;
-    sc->hit_chunk = (uint32_t)chunk;
-    const int64_t slack = TRC_HIT_HOLDERS * chunk + 64;
+    int64_t ch = 64;          // (never below a wave's worth: one append of a wave must fit a fresh chunk)
+    while (ch < SQ_HIT_CHUNK && 2048 * (ch * 2) <= capacity) ch *= 2;
+    chunk = (uint32_t)ch;
+    return allocate(capacity, TRC_HIT_HOLDERS * ch + 64, 0);
+}
+
+// Columns for `capacity` hits + `slack`, holding entries [0, keep) of the present ones, spectral ones included.
+int HitBuffer::allocate(int64_t capacity, int64_t slack, int64_t keep) {
     const int64_t alloc = capacity + slack;
-    TRC_TRY(sc->d_h_surf.alloc((size_t)alloc));
-    for (auto &col : sc->d_h) TRC_TRY(col.alloc((size_t)alloc));
-    HIP_TRY(hipMemset(sc->d_h_surf.get(), 0xFF, (size_t)alloc * sizeof(int32_t)));     // surface -1: entry not written
-    sc->hit_dirty_to = 0;
-    sc->hit_cap = alloc;
-    sc->hit_cap_user = capacity;
+    // the new columns join the buffer once they hold its hits
+    DevBuf<int32_t> n_surf;
+    DevBuf<double> n_col[8], n_x;
+    TRC_TRY(n_surf.alloc((size_t)alloc));
+    for (auto &c : n_col) TRC_TRY(c.alloc((size_t)alloc));
+    if (x_cols > 0) TRC_TRY(n_x.alloc((size_t)x_cols * (size_t)alloc));
+    HIP_TRY(unwrite(n_surf.get(), alloc));
+    if (keep > 0) {
+        HIP_TRY(hipMemcpy(n_surf.get(), surf.get(), (size_t)keep * sizeof(int32_t), hipMemcpyDeviceToDevice));
+        for (int i = 0; i < 8; ++i) HIP_TRY(hipMemcpy(n_col[i].get(), col[i].get(), (size_t)keep * sizeof(double), hipMemcpyDeviceToDevice));
+        if (x_cols > 0)
+            HIP_TRY(hipMemcpy2D(n_x.get(), (size_t)alloc * sizeof(double), x.get(), (size_t)cap * sizeof(double), (size_t)keep * sizeof(double),
+                                (size_t)x_cols, hipMemcpyDeviceToDevice));
+    }
+    surf = std::move(n_surf);
+    for (int i = 0; i < 8; ++i) col[i] = std::move(n_col[i]);
+    x = std::move(n_x);
+    dirty_to = keep;
+    cap = alloc;
+    cap_user = capacity;
     return TRC_OK;
 }
 
 // A buffer of at least `capacity` hits that keeps what it holds: the accountants of a script that traces again before it has
 // read the hits of its last call (optics_callables.py:1577-1643 accumulate over calls) are served from the device when they are
-// read at last.  Grows by half at least; the chunk size stays (chunks left open by earlier launches go on being filled).
+// read at last.
 extern "C" int trc_scene_reserve_hits(trc_scene *sc, int64_t capacity) {
     if (!sc || capacity < 0) return trc_fail(TRC_ERR_INVALID, "bad arguments");
-    if (!sc->d_h_surf.get() || sc->hit_cap_user == 0) return trc_scene_set_hit_capacity(sc, capacity);
-    if (capacity <= sc->hit_cap_user) return TRC_OK;
-    HIP_TRY(hipSetDevice(sc->ctx->device));
-    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    if (capacity < sc->hit_cap_user + sc->hit_cap_user / 2) capacity = sc->hit_cap_user + sc->hit_cap_user / 2;
-    unsigned long long c[2];
-    HIP_TRY(hipMemcpy(c, sc->d_counters.get(), sizeof(c), hipMemcpyDeviceToHost));
-    const int64_t used = (int64_t)c[0] < sc->hit_cap ? (int64_t)c[0] : sc->hit_cap;
-    const int64_t alloc = capacity + (sc->hit_cap - sc->hit_cap_user);
-    // the new columns join the scene once they hold its hits
-    DevBuf<int32_t> n_surf;
-    DevBuf<double> n_col[8];
-    TRC_TRY(n_surf.alloc((size_t)alloc));
-    for (auto &col : n_col) TRC_TRY(col.alloc((size_t)alloc));
-    HIP_TRY(hipMemset(n_surf.get(), 0xFF, (size_t)alloc * sizeof(int32_t)));
-    if (used > 0) {
-        HIP_TRY(hipMemcpy(n_surf.get(), sc->d_h_surf.get(), (size_t)used * sizeof(int32_t), hipMemcpyDeviceToDevice));
-        for (int i = 0; i < 8; ++i) HIP_TRY(hipMemcpy(n_col[i].get(), sc->d_h[i].get(), (size_t)used * sizeof(double), hipMemcpyDeviceToDevice));
-    }
-    sc->d_h_surf = std::move(n_surf);
-    for (int i = 0; i < 8; ++i) sc->d_h[i] = std::move(n_col[i]);
-    sc->d_hx.reset(); sc->hx_cols = 0; sc->hx_cap = 0;      // (a buffer that grows keeps its hits, not their spectra: the host reads those before)
-    sc->hit_dirty_to = used;
-    sc->hit_cap = alloc;
-    sc->hit_cap_user = capacity;
-    return TRC_OK;
+    if (sc->hits.cap_user == 0) return trc_scene_set_hit_capacity(sc, capacity);
+    if (capacity <= sc->hits.cap_user) return TRC_OK;
+    unsigned long long cursor;
+    TRC_TRY(scene_hit_cursor(sc, &cursor));
+    return sc->hits.grow(capacity, cursor);
 }
 
 // entries of the hit buffer reserved so far (written ones and the unused parts of chunks still open) and its capacity
 extern "C" int trc_scene_hits_reserved(trc_scene *sc, int64_t *reserved, int64_t *capacity) {
     if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
     if (reserved) {
-        if (sc->cnt_host_ok) *reserved = (int64_t)sc->cnt_host[0];
-        else {
-            HIP_TRY(hipSetDevice(sc->ctx->device));
-            HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-            unsigned long long c = 0;
-            HIP_TRY(hipMemcpy(&c, sc->d_counters.get(), sizeof(c), hipMemcpyDeviceToHost));
-            *reserved = (int64_t)c;
-        }
+        unsigned long long c = sc->cnt_host[0];
+        if (!sc->cnt_host_ok) TRC_TRY(scene_hit_cursor(sc, &c));
+        *reserved = (int64_t)c;
     }
-    if (capacity) *capacity = sc->hit_cap_user;
+    if (capacity) *capacity = sc->hits.cap_user;
     return TRC_OK;
 }
 
@@ -1850,22 +1910,9 @@ extern "C" int trc_host_free(void *p) {
     return TRC_OK;
 }
 
-// forget the captured hits: cursor to zero, every entry unwritten, open chunks of the streaming engine stale
-static int scene_reset_hit_buffer(trc_scene *sc) {
-    sc->hit_epoch += 1;
-    const int64_t upto = sc->hit_dirty_to < sc->hit_cap ? sc->hit_dirty_to : sc->hit_cap;
-    if (upto > 0) HIP_TRY(hipMemset(sc->d_h_surf.get(), 0xFF, (size_t)upto * sizeof(int32_t)));
-    sc->hit_dirty_to = 0;
-    return TRC_OK;
-}
-
 extern "C" int trc_scene_clear_hits(trc_scene *sc) {
     if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
-    HIP_TRY(hipSetDevice(sc->ctx->device));
-    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    HIP_TRY(hipMemset(sc->d_counters.get(), 0, 2 * sizeof(unsigned long long)));
-    sc->cnt_host[0] = sc->cnt_host[1] = 0ull;
-    return scene_reset_hit_buffer(sc);
+    return trc_scene_set_hit_capacity(sc, sc->hits.cap_user);       // (the same capacity: the buffer is kept and emptied)
 }
 
 extern "C" int trc_scene_reset_tallies(trc_scene *sc) {
@@ -1876,7 +1923,7 @@ extern "C" int trc_scene_reset_tallies(trc_scene *sc) {
     HIP_TRY(hipMemset(sc->d_counters.get(), 0, 8 * sizeof(unsigned long long)));
     HIP_TRY(hipMemset(sc->d_energy_left, 0, sizeof(double)));
     memset(sc->cnt_host, 0, sizeof(sc->cnt_host));
-    return scene_reset_hit_buffer(sc);
+    return sc->hits.reset();
 }
 
 extern "C" int trc_scene_get_tallies(trc_scene *sc, double *absorbed, double *received, int64_t *hits) {
@@ -1966,64 +2013,67 @@ __global__ __launch_bounds__(256) void k_hits_gather(HitPack H, const uint32_t *
 static int scene_get_hits(trc_scene *sc, int64_t *n, int32_t *surf, double *e_abs, double *e_in, double *px,
                           double *py, double *pz, double *dx, double *dy, double *dz, int32_t n_x, double *x_out) {
     if (!sc || !n) return trc_fail(TRC_ERR_INVALID, "bad arguments");
-    if (n_x < 0 || (n_x > 0 && (!x_out || n_x != sc->hx_cols || !sc->d_hx.get())))
-        return trc_fail(TRC_ERR_INVALID, "trc_scene_get_hits_x: the hit buffer holds %d spectral columns, %d asked for", sc ? sc->hx_cols : 0, n_x);
-    HIP_TRY(hipSetDevice(sc->ctx->device));
-    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    unsigned long long c[2];
-    HIP_TRY(hipMemcpy(c, sc->d_counters.get(), sizeof(c), hipMemcpyDeviceToHost));
-    int64_t reserved = (int64_t)c[0];
-    if (reserved > sc->hit_cap) reserved = sc->hit_cap;
+    if (n_x < 0 || (n_x > 0 && (!x_out || n_x != sc->hits.x_cols)))
+        return trc_fail(TRC_ERR_INVALID, "trc_scene_get_hits_x: the hit buffer holds %d spectral columns, %d asked for", sc->hits.x_cols, n_x);
+    unsigned long long cursor;
+    TRC_TRY(scene_hit_cursor(sc, &cursor));
+    double *const dst[8] = {e_abs, e_in, px, py, pz, dx, dy, dz};
+    return sc->hits.read(sc->ctx->stream, sc->surfs, sc->d_sflags.get(), cursor, n, surf, dst, n_x, x_out);
+}
+
+// the written entries of [0, cursor): n of them, and the columns whose destinations are given
+int HitBuffer::read(hipStream_t stream, const std::vector<trc_surface_desc> &surfs, const int32_t *d_sflags, unsigned long long cursor,
+                    int64_t *n, int32_t *surf_out, double *const dst[8], int32_t n_x, double *x_out) const {
+    const int64_t reserved = used(cursor);
     *n = 0;
     if (reserved == 0) return TRC_OK;
     if (reserved >= (1ll << 32)) return trc_fail(TRC_ERR_CAPACITY, "more than 2^32 entries in the hit buffer");
     // The reserved range holds unwritten entries (surface -1) where the streaming engine's chunks are still open: the caller
     // gets the written ones, in buffer order (one capturing surface) or surface by surface (several).  They are packed on the device (copying the whole range and picking on the
     // host was 0.11 s for the 6.5e6 receiver hits of an NSTTF step).
-    double *dst[8] = {e_abs, e_in, px, py, pz, dx, dy, dz};
     DevBuf<uint32_t> d_flag, d_off, d_key[2], d_ent[2];
     DevBuf<char> d_tmp;
     DevBuf<int32_t> o_surf;
     DevBuf<double> o_col[8], o_x;
     // declared after the temporaries, so it runs before they are freed: nothing queued on the stream may still use them
-    struct StreamWait { hipStream_t s; ~StreamWait() { (void)hipStreamSynchronize(s); } } wait_before_free{sc->ctx->stream};
+    struct StreamWait { hipStream_t s; ~StreamWait() { (void)hipStreamSynchronize(s); } } wait_before_free{stream};
     TRC_TRY(d_flag.alloc((size_t)reserved));
     TRC_TRY(d_off.alloc((size_t)reserved));
     const unsigned nblk = (unsigned)((reserved + 255) / 256);
-    hipLaunchKernelGGL(k_hits_flag, dim3(nblk), dim3(256), 0, sc->ctx->stream, sc->d_h_surf.get(), (long long)reserved, d_flag.get());
+    hipLaunchKernelGGL(k_hits_flag, dim3(nblk), dim3(256), 0, stream, surf.get(), (long long)reserved, d_flag.get());
     size_t tmp_bytes = 0;
-    if (rocprim::exclusive_scan(nullptr, tmp_bytes, d_flag.get(), d_off.get(), 0u, (size_t)reserved, rocprim::plus<uint32_t>(), sc->ctx->stream) != hipSuccess)
+    if (rocprim::exclusive_scan(nullptr, tmp_bytes, d_flag.get(), d_off.get(), 0u, (size_t)reserved, rocprim::plus<uint32_t>(), stream) != hipSuccess)
         return trc_fail(TRC_ERR_DEVICE, "exclusive_scan (size query) failed");
     TRC_TRY(d_tmp.alloc(tmp_bytes ? tmp_bytes : 1));
-    if (rocprim::exclusive_scan(d_tmp.get(), tmp_bytes, d_flag.get(), d_off.get(), 0u, (size_t)reserved, rocprim::plus<uint32_t>(), sc->ctx->stream) != hipSuccess)
+    if (rocprim::exclusive_scan(d_tmp.get(), tmp_bytes, d_flag.get(), d_off.get(), 0u, (size_t)reserved, rocprim::plus<uint32_t>(), stream) != hipSuccess)
         return trc_fail(TRC_ERR_DEVICE, "exclusive_scan failed");
     uint32_t last_off = 0, last_flag = 0;
-    if (hipMemcpyAsync(&last_off, d_off.get() + (reserved - 1), 4, hipMemcpyDeviceToHost, sc->ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(&last_flag, d_flag.get() + (reserved - 1), 4, hipMemcpyDeviceToHost, sc->ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(sc->ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "hit count readback failed");
+    if (hipMemcpyAsync(&last_off, d_off.get() + (reserved - 1), 4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipMemcpyAsync(&last_flag, d_flag.get() + (reserved - 1), 4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "hit count readback failed");
     const int64_t cnt = (int64_t)last_off + (int64_t)last_flag;
     *n = cnt;
-    if (cnt == 0 || (!surf && !e_abs && !e_in && !px && !py && !pz && !dx && !dy && !dz)) return TRC_OK;
+    if (cnt == 0 || (!surf_out && !dst[0] && !dst[1] && !dst[2] && !dst[3] && !dst[4] && !dst[5] && !dst[6] && !dst[7])) return TRC_OK;
     HitPack H;
     memset(&H, 0, sizeof(H));
-    H.surf = sc->d_h_surf.get();
-    H.sflags = sc->d_sflags.get();
+    H.surf = surf.get();
+    H.sflags = d_sflags;
     TRC_TRY(o_surf.alloc((size_t)cnt));
     H.o_surf = o_surf.get();
     for (int k = 0; k < 8; ++k) {
-        H.col[k] = sc->d_h[k].get();
+        H.col[k] = col[k].get();
         H.want[k] = dst[k] ? 1 : 0;
         if (dst[k]) { TRC_TRY(o_col[k].alloc((size_t)cnt)); H.o_col[k] = o_col[k].get(); }
     }
     if (n_x > 0) {
-        H.x = sc->d_hx.get(); H.n_x = n_x; H.x_cap = sc->hx_cap; H.o_cnt = cnt;
+        H.x = x.get(); H.n_x = n_x; H.x_cap = cap; H.o_cnt = cnt;
         TRC_TRY(o_x.alloc((size_t)cnt * (size_t)n_x));
         H.o_x = o_x.get();
     }
     int n_capture = 0;
-    for (int i = 0; i < sc->n_surf; ++i) if (sc->surfs[i].flags & TRC_SURF_CAPTURE_HITS) ++n_capture;
+    for (const trc_surface_desc &d : surfs) if (d.flags & TRC_SURF_CAPTURE_HITS) ++n_capture;
     if (n_capture <= 1) {
-        hipLaunchKernelGGL(k_hits_pack, dim3(nblk), dim3(256), 0, sc->ctx->stream, H, (const uint32_t *)d_off.get(), (long long)reserved);
+        hipLaunchKernelGGL(k_hits_pack, dim3(nblk), dim3(256), 0, stream, H, (const uint32_t *)d_off.get(), (long long)reserved);
     } else {
         // Several capturing surfaces: the caller wants each one's hits together (accountants), and regrouping eight columns
         // on the host cost 60 ms per 1e6 hits.  A stable radix sort of (surface, entry) pairs over the bits a surface index
@@ -2033,25 +2083,25 @@ static int scene_get_hits(trc_scene *sc, int64_t *n, int32_t *surf, double *e_ab
         TRC_TRY(d_ent[0].alloc((size_t)reserved));
         TRC_TRY(d_ent[1].alloc((size_t)reserved));
         uint32_t *key0 = d_key[0].get(), *key1 = d_key[1].get(), *ent0 = d_ent[0].get(), *ent1 = d_ent[1].get();
-        hipLaunchKernelGGL(k_hits_keys, dim3(nblk), dim3(256), 0, sc->ctx->stream, sc->d_h_surf.get(), (long long)reserved, (uint32_t)sc->n_surf,
+        hipLaunchKernelGGL(k_hits_keys, dim3(nblk), dim3(256), 0, stream, surf.get(), (long long)reserved, (uint32_t)surfs.size(),
                            key0, ent0);
         unsigned bits = 1;
-        while ((1u << bits) <= (unsigned)sc->n_surf) ++bits;
+        while ((1u << bits) <= (unsigned)surfs.size()) ++bits;
         size_t sort_bytes = 0;
-        if (rocprim::radix_sort_pairs(nullptr, sort_bytes, key0, key1, ent0, ent1, (size_t)reserved, 0, bits, sc->ctx->stream) != hipSuccess)
+        if (rocprim::radix_sort_pairs(nullptr, sort_bytes, key0, key1, ent0, ent1, (size_t)reserved, 0, bits, stream) != hipSuccess)
             return trc_fail(TRC_ERR_DEVICE, "radix_sort_pairs (size query) failed");
         TRC_TRY(d_tmp.alloc(sort_bytes ? sort_bytes : 1));
-        if (rocprim::radix_sort_pairs(d_tmp.get(), sort_bytes, key0, key1, ent0, ent1, (size_t)reserved, 0, bits, sc->ctx->stream) != hipSuccess)
+        if (rocprim::radix_sort_pairs(d_tmp.get(), sort_bytes, key0, key1, ent0, ent1, (size_t)reserved, 0, bits, stream) != hipSuccess)
             return trc_fail(TRC_ERR_DEVICE, "radix_sort_pairs failed");
-        hipLaunchKernelGGL(k_hits_gather, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, sc->ctx->stream, H, (const uint32_t *)ent1, (long long)cnt);
+        hipLaunchKernelGGL(k_hits_gather, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, H, (const uint32_t *)ent1, (long long)cnt);
     }
     // one copy per column, all behind the packing on the context's stream (page-locked destinations -- trc_host_alloc -- take
     // them at the rate of the link), one wait
-    if (surf && hipMemcpyAsync(surf, H.o_surf, (size_t)cnt * 4, hipMemcpyDeviceToHost, sc->ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
+    if (surf_out && hipMemcpyAsync(surf_out, H.o_surf, (size_t)cnt * 4, hipMemcpyDeviceToHost, stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
     for (int k = 0; k < 8; ++k)
-        if (dst[k] && hipMemcpyAsync(dst[k], H.o_col[k], (size_t)cnt * 8, hipMemcpyDeviceToHost, sc->ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
-    if (n_x > 0 && hipMemcpyAsync(x_out, H.o_x, (size_t)cnt * (size_t)n_x * 8, hipMemcpyDeviceToHost, sc->ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
-    if (hipStreamSynchronize(sc->ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "fetching the hits failed");
+        if (dst[k] && hipMemcpyAsync(dst[k], H.o_col[k], (size_t)cnt * 8, hipMemcpyDeviceToHost, stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
+    if (n_x > 0 && hipMemcpyAsync(x_out, H.o_x, (size_t)cnt * (size_t)n_x * 8, hipMemcpyDeviceToHost, stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
+    if (hipStreamSynchronize(stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "fetching the hits failed");
     return TRC_OK;
 }
 
@@ -2067,7 +2117,7 @@ extern "C" int trc_scene_get_hits_x(trc_scene *sc, int64_t *n, int32_t *surf, do
 
 extern "C" int trc_scene_hit_spectral_columns(trc_scene *sc, int32_t *n_x) {
     if (!sc || !n_x) return trc_fail(TRC_ERR_INVALID, "bad arguments");
-    *n_x = sc->d_hx.get() ? sc->hx_cols : 0;
+    *n_x = sc->hits.x_cols;
     return TRC_OK;
 }
 
@@ -2113,12 +2163,10 @@ extern "C" int trc_scene_bin_hits(trc_scene *sc, int32_t n_bins, const int32_t *
     if (!sc || n_bins < 0 || (n_bins > 0 && (!surf_lo || !surf_hi || !ranges6 || !mode || !out))) return trc_fail(TRC_ERR_INVALID, "bad arguments");
     if (n_bins == 0) return TRC_OK;
     trc_ctx *ctx = sc->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    unsigned long long c[2];
-    HIP_TRY(hipMemcpy(c, sc->d_counters.get(), sizeof(c), hipMemcpyDeviceToHost));
-    long long reserved = (long long)c[0];
-    if (reserved > sc->hit_cap) reserved = sc->hit_cap;
+    unsigned long long cursor;
+    TRC_TRY(scene_hit_cursor(sc, &cursor));
+    const HitBuffer &hb = sc->hits;
+    const long long reserved = hb.used(cursor);
     for (int i = 0; i < n_bins; ++i) out[i] = 0.0;
     if (reserved == 0) return TRC_OK;
     const size_t per_bin = 2 * sizeof(int32_t) + 6 * sizeof(double) + sizeof(int32_t) + sizeof(double);
@@ -2137,8 +2185,8 @@ extern "C" int trc_scene_bin_hits(trc_scene *sc, int32_t n_bins, const int32_t *
         if (e == hipSuccess) e = hipMemcpyAsync(d_mode, mode + b0, (size_t)nb * 4, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, (size_t)nb * 8, ctx->stream);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_bin_hits, dim3(grid), dim3(256), 0, ctx->stream, reserved, sc->d_h_surf.get(), sc->d_h[0].get(), sc->d_h[2].get(), sc->d_h[3].get(),
-                               sc->d_h[4].get(), nb, d_lo, d_hi, d_rng, d_mode, d_out);
+            hipLaunchKernelGGL(k_bin_hits, dim3(grid), dim3(256), 0, ctx->stream, reserved, hb.surf.get(), hb.col[0].get(), hb.col[2].get(), hb.col[3].get(),
+                               hb.col[4].get(), nb, d_lo, d_hi, d_rng, d_mode, d_out);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(out + b0, d_out, (size_t)nb * 8, hipMemcpyDeviceToHost, ctx->stream);
@@ -2236,9 +2284,7 @@ static DScene make_dscene(trc_scene *sc) {
     d.tr_off = sc->tr_off;
     d.n_fm = (int32_t)sc->fms_h.size(); d.n_fm_edges = (int32_t)sc->fm_edges_h.size();
     d.counters = sc->d_counters.get(); d.energy_left = sc->d_energy_left;
-    d.hit_cap = sc->hit_cap; d.h_surf = sc->d_h_surf.get();
-    d.h_eabs = sc->d_h[0].get(); d.h_ein = sc->d_h[1].get(); d.h_px = sc->d_h[2].get(); d.h_py = sc->d_h[3].get(); d.h_pz = sc->d_h[4].get();
-    d.h_dx = sc->d_h[5].get(); d.h_dy = sc->d_h[6].get(); d.h_dz = sc->d_h[7].get();
+    sc->hits.fill(d);
     return d;
 }
 
@@ -2492,9 +2538,15 @@ static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_d
         else if (hipMemcpy(blk_before, sc->d_counters.get(), sizeof(blk_before), hipMemcpyDeviceToHost) != hipSuccess)
             return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
         sc->cnt_host_ok = false;          // (until this call has read them back at its end)
-        const int64_t dirty_before = sc->hit_dirty_to;
-        sc->hit_dirty_to = sc->hit_cap;   // (... and then says how far the hit buffer was used)
         for (int i = 0; i < 4; ++i) cnt_before[i] = blk_before[i];
+        // polychromatic hits: the captured ones keep their sample wavelengths and their spectrum before and after (3 W columns beside
+        // the hit buffer); a call whose hits would not have the shape of those the buffer holds is refused before anything is written
+        double *hit_x = nullptr;
+        bool captures = false;
+        if (sc->hits.cap > 0)
+            for (int i = 0; i < S && !captures; ++i) captures = (sc->surfs[i].flags & TRC_SURF_CAPTURE_HITS) != 0;
+        if (captures) TRC_TRY(sc->hits.spectra_for(3 * carry_W, cnt_before[0], &hit_x));
+        const int64_t dirty_before = sc->hits.begin_call();      // (... and then says how far the hit buffer was used)
         memcpy(&eleft_before, &blk_before[5], sizeof(double));
         // the `last` cursor restarts for every call
         if (blk_before[2] != 0ull) {
@@ -2507,26 +2559,8 @@ static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_d
         P.sc = make_dscene(sc);
         P.x = dr.x; P.y = dr.y; P.z = dr.z; P.dx = dr.dx; P.dy = dr.dy; P.dz = dr.dz; P.e = dr.e;
         P.ref = dr.ref; P.wl = dr.wl; P.rid = dr.rid;
-        // polychromatic hits: the captured ones keep their sample wavelengths and their spectrum before and after (3 W columns beside
-        // the hit buffer, made when the first call with spectra finds a buffer to capture into)
-        double *hit_x = nullptr;
-        bool captures = false;
-        if (sc->hit_cap > 0)
-            for (int i = 0; i < S && !captures; ++i) captures = (sc->surfs[i].flags & TRC_SURF_CAPTURE_HITS) != 0;
-        if (carry_W > 0 && captures) {
-            const int cols = 3 * carry_W;
-            if (sc->d_hx && (sc->hx_cols != cols || sc->hx_cap != sc->hit_cap)) {
-                if (cnt_before[0] != 0ull) return trc_fail(TRC_ERR_INVALID, "the hit buffer holds hits with spectra of another sample count: read or clear them first");
-                sc->d_hx.reset(); sc->hx_cols = 0; sc->hx_cap = 0;
-            }
-            if (!sc->d_hx) {
-                TRC_TRY(sc->d_hx.alloc((size_t)cols * (size_t)sc->hit_cap));
-                sc->hx_cols = cols; sc->hx_cap = sc->hit_cap;
-            }
-            hit_x = sc->d_hx.get();
-        }
         CarryIn carry_in;
-        carry_in.hit_x = hit_x; carry_in.hit_x_cap = sc->hx_cap;
+        carry_in.hit_x = hit_x; carry_in.hit_x_cap = hit_x ? sc->hits.cap : 0;
         carry_in.ref_im = carry_d[0]; carry_in.mat = carry_d[1]; carry_in.spec_wl = carry_d[2]; carry_in.spec = carry_d[3]; carry_in.n_mat = carry_mat; carry_in.n_spec = carry_W;
         P.src = d_src;
         P.spec = d_spec;
@@ -2583,17 +2617,7 @@ static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_d
                 if (!sc->stream_eng) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
             }
             if (int e = stream_trace(sc, P, carry_in, plan, knobs, src, *sc->stream_eng, &s, &stream_seg, &stream_hits)) {
-                // the hits captured by the bounces that completed: wind the buffer back to where the call found it
-                const std::string why = g_last_error;
-                unsigned long long now = 0;
-                (void)hipDeviceSynchronize();
-                if (sc->hit_cap > 0 && hipMemcpy(&now, sc->d_counters.get(), sizeof(now), hipMemcpyDeviceToHost) == hipSuccess && now > cnt_before[0]) {
-                    const unsigned long long end = now < (unsigned long long)sc->hit_cap ? now : (unsigned long long)sc->hit_cap;
-                    if (end > cnt_before[0]) (void)hipMemset(sc->d_h_surf.get() + cnt_before[0], 0xFF, (size_t)(end - cnt_before[0]) * sizeof(int32_t));
-                    (void)hipMemcpy(sc->d_counters.get(), &cnt_before[0], sizeof(unsigned long long), hipMemcpyHostToDevice);
-                }
-                sc->hit_epoch += 1;
-                g_last_error = why;
+                sc->hits.rollback(sc->d_counters.get(), cnt_before[0]);     // (the hits captured by the bounces that completed)
                 return e;
             }
             stream_counts_known = true;
@@ -2644,10 +2668,7 @@ static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_d
         memcpy(&eleft_after, &blk_after[5], sizeof(double));
         memcpy(sc->cnt_host, blk_after, sizeof(blk_after));
         sc->cnt_host_ok = true;
-        {       // every entry written lies below the cursor: chunks are reserved by advancing it
-            const int64_t cur = (int64_t)(blk_after[0] < (unsigned long long)sc->hit_cap ? blk_after[0] : (unsigned long long)sc->hit_cap);
-            sc->hit_dirty_to = cur > dirty_before ? cur : dirty_before;
-        }
+        sc->hits.end_call(dirty_before, blk_after[0]);
         if (stream_counts_known) {              // the streaming form counted on the host
             s.segments = (int64_t)(stream_seg + 0.5);
             s.hits = (int64_t)(stream_hits + 0.5);

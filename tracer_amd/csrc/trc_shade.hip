@@ -71,11 +71,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
     WaveChunk ca = S.static_first ? chunk_init_static_at(S.chunk_act, (unsigned long long)S.act_base0 + (unsigned long long)wave_g * S.chunk_act) : chunk_init(S.chunk_act);
     // this wave's open chunk of the scene's hit buffer, carried over from earlier launches (see k_s_shade)
     WaveChunk hc = chunk_init(S.chunk_hitbuf);
-    unsigned long long *hstate = W.hit_state;
-    if (P.capture && wave_g < SHADE_MAX_WAVES) {
-        const unsigned long long st = hstate[2 * wave_g + 1];
-        if ((unsigned)(st >> 32) == S.hit_epoch && (st & 1ull)) { hc.base = hstate[2 * wave_g]; hc.used = (unsigned)(st >> 1) & 0x7FFFFFFFu; hc.open = 1; }
-    }
+    if (P.capture && wave_g < SHADE_MAX_WAVES) hit_chunk_resume(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
     unsigned n_hit = 0, n_alive = 0;
     const int bounce0 = S.bounce_no;          // every ray of a launch is at the same bounce
     const bool aux_in = !P.src || bounce0 > 0;     // fresh rays of a source carry (energy, 1, 0): nothing was written for them
@@ -252,10 +248,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
         if (alive) { if ((long long)q < W.act_room) S.act_out[q] = slot; else W.cnt[CN(4)] = 2ull; n_alive += 1; }
     }
     chunk_close(ca, S.act_out, W.act_room);
-    if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) {
-        hstate[2 * wave_g] = hc.base;
-        hstate[2 * wave_g + 1] = ((unsigned long long)S.hit_epoch << 32) | ((unsigned long long)hc.used << 1) | (hc.open ? 1ull : 0ull);
-    }
+    if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
     // real (unpadded) counts of this bounce: hits and rays that go on -- one pair of atomics per workgroup
     {
         const double h = wave_sum((double)n_hit), a = wave_sum((double)n_alive);
@@ -337,11 +330,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
     const unsigned wave_g = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     WaveChunk ca = S.static_first ? chunk_init_static_at(S.chunk_act, (unsigned long long)S.act_base0 + (unsigned long long)wave_g * S.chunk_act) : chunk_init(S.chunk_act);
     WaveChunk hc = chunk_init(S.chunk_hitbuf);
-    unsigned long long *hstate = W.hit_state;
-    if (P.capture && wave_g < SHADE_MAX_WAVES) {
-        const unsigned long long st = hstate[2 * wave_g + 1];
-        if ((unsigned)(st >> 32) == S.hit_epoch && (st & 1ull)) { hc.base = hstate[2 * wave_g]; hc.used = (unsigned)(st >> 1) & 0x7FFFFFFFu; hc.open = 1; }
-    }
+    if (P.capture && wave_g < SHADE_MAX_WAVES) hit_chunk_resume(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
     unsigned n_hit = 0, n_alive = 0;
     const int bounce0 = S.bounce_no;
     const bool aux_in = !P.src || bounce0 > 0;
@@ -507,10 +496,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
         if (alive) { if ((long long)q < W.act_room) S.act_out[q] = slot; else W.cnt[CN(4)] = 2ull; n_alive += 1; }
     }
     chunk_close(ca, S.act_out, W.act_room);
-    if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) {
-        hstate[2 * wave_g] = hc.base;
-        hstate[2 * wave_g + 1] = ((unsigned long long)S.hit_epoch << 32) | ((unsigned long long)hc.used << 1) | (hc.open ? 1ull : 0ull);
-    }
+    if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
     {
         const double h = wave_sum((double)n_hit), a = wave_sum((double)n_alive);
         double *spare = l_tally + (LDS ? 3 * Sn : 0);

@@ -931,10 +931,7 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
     }
     const unsigned wave_a = (unsigned)(((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     WaveChunk hc = chunk_init(S.chunk_hitbuf);          // this wave's open chunk of the scene's hit buffer (see k_s_shade)
-    if (absorb_here && P.capture && wave_a < SHADE_MAX_WAVES) {
-        const unsigned long long st = W.hit_state[2 * wave_a + 1];
-        if ((unsigned)(st >> 32) == S.hit_epoch && (st & 1ull)) { hc.base = W.hit_state[2 * wave_a]; hc.used = (unsigned)(st >> 1) & 0x7FFFFFFFu; hc.open = 1; }
-    }
+    if (absorb_here && P.capture && wave_a < SHADE_MAX_WAVES) hit_chunk_resume(hc, W.hit_state + 2 * wave_a, S.hit_epoch);
     unsigned n_term = 0;
     const bool buie_src = FRESH && P.src && (P.src->kind == TRC_SRC_BUIE_DISK || P.src->kind == TRC_SRC_BUIE_RECT);
     if (FRESH) {
@@ -1245,10 +1242,7 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
     chunk_close(ch, W.hit_slot, SQ_ROOM(W));
     if (split && !absorb_here) chunk_close(ct, t_slot, SQ_ROOM(W));
     if (absorb_here) {
-        if (P.capture && wave_a < SHADE_MAX_WAVES && lane_id() == 0) {
-            W.hit_state[2 * wave_a] = hc.base;
-            W.hit_state[2 * wave_a + 1] = ((unsigned long long)S.hit_epoch << 32) | ((unsigned long long)hc.used << 1) | (hc.open ? 1ull : 0ull);
-        }
+        if (P.capture && wave_a < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_a, S.hit_epoch);
         const double h = wave_sum((double)n_term);
         if (lane_id() == 0) atomicAdd(&a_tally[3 * Sn], h);
         __syncthreads();
@@ -1753,11 +1747,7 @@ __global__ __launch_bounds__(128 * WAVES, WAVES) void k_s_shade(StreamParams S) 
     // in the chunks open when the buffer is read (they keep the surface index -1 the buffer is cleared with)
     const unsigned wave_g = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     WaveChunk hc = chunk_init(S.chunk_hitbuf);
-    unsigned long long *hstate = W.hit_state;
-    if (P.capture && wave_g < SHADE_MAX_WAVES) {
-        const unsigned long long st = hstate[2 * wave_g + 1];
-        if ((unsigned)(st >> 32) == S.hit_epoch && (st & 1ull)) { hc.base = hstate[2 * wave_g]; hc.used = (unsigned)(st >> 1) & 0x7FFFFFFFu; hc.open = 1; }
-    }
+    if (P.capture && wave_g < SHADE_MAX_WAVES) hit_chunk_resume(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
     unsigned n_hit = 0, n_alive = 0;
     // Two loads stand in front of every hit -- its entry of the hit list, then the ray record the entry points to -- and at 2 waves
     // per SIMD nothing hides them.  Both are fetched ahead, in two stages: while hit i is worked on, the record of hit i + 1 (whose
@@ -1894,10 +1884,7 @@ __global__ __launch_bounds__(128 * WAVES, WAVES) void k_s_shade(StreamParams S) 
         if (alive) { if ((long long)q < W.act_room) S.act_out[q] = slot; else W.cnt[CN(4)] = 2ull; n_alive += 1; }
     }
     chunk_close(ca, S.act_out, W.act_room);
-    if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) {
-        hstate[2 * wave_g] = hc.base;
-        hstate[2 * wave_g + 1] = ((unsigned long long)S.hit_epoch << 32) | ((unsigned long long)hc.used << 1) | (hc.open ? 1ull : 0ull);
-    }
+    if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
     // real (unpadded) counts of this bounce: hits and rays that go on -- one pair of atomics per workgroup (through the two
     // spare words at the end of the LDS tallies), not per wave: they all land on the same two words at the end of the kernel
     {
@@ -1973,11 +1960,7 @@ __global__ __launch_bounds__(SA_THREADS, 2) void k_s_absorb(StreamParams S) {
     // this wave's open chunk of the scene's hit buffer: the second half of the state array (k_s_shade's waves own the first)
     const unsigned wave_g = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     WaveChunk hc = chunk_init(S.chunk_hitbuf);
-    unsigned long long *state = W.hit_state;
-    if (P.capture && wave_g < SHADE_MAX_WAVES) {
-        const unsigned long long st = state[2 * wave_g + 1];
-        if ((unsigned)(st >> 32) == S.hit_epoch && (st & 1ull)) { hc.base = state[2 * wave_g]; hc.used = (unsigned)(st >> 1) & 0x7FFFFFFFu; hc.open = 1; }
-    }
+    if (P.capture && wave_g < SHADE_MAX_WAVES) hit_chunk_resume(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
     unsigned n_hit = 0;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < padded; i += (long long)gridDim.x * blockDim.x) {
         const uint32_t slot = i < nh ? t_slot[i] : SQ_INVALID;
@@ -2014,10 +1997,7 @@ __global__ __launch_bounds__(SA_THREADS, 2) void k_s_absorb(StreamParams S) {
         if (has_hit) record_hit<true>(L, l_tally, s, e, e, hx, hy, hz, dx, dy, dz, P.capture != 0, prev, &hc, l_fm, false, true);
         if (P.capture) chunk_rebroadcast(hc, __ffsll((long long)hit_lanes) - 1);
     }
-    if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) {
-        state[2 * wave_g] = hc.base;
-        state[2 * wave_g + 1] = ((unsigned long long)S.hit_epoch << 32) | ((unsigned long long)hc.used << 1) | (hc.open ? 1ull : 0ull);
-    }
+    if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
     {
         const double h = wave_sum((double)n_hit);
         if (lane_id() == 0) atomicAdd(&l_tally[3 * Sn], h);
@@ -2478,7 +2458,7 @@ static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene 
     F.n_shk = n_shk;
     F.multi = n_shk > 1;
     SP0.shade_term_cls = term_cls;
-    SP0.chunk_hitbuf = sc->hit_chunk ? sc->hit_chunk : SQ_HIT_CHUNK;
+    SP0.chunk_hitbuf = sc->hits.chunk_size();
     return TRC_OK;
 }
 
@@ -2619,7 +2599,7 @@ static int stream_choose_forms(StreamForms &F, StreamParams &SP0, trc_scene *sc,
     F.small_scene = S <= STREAM_SMALL_SURFACES && plan.mode != 1 && plan.walk_ok;
     if (F.small_scene && S <= 4) F.gridm = 3;
     SP0.search = plan.walk_ok ? plan.mode : 2;
-    SP0.hit_epoch = sc->hit_epoch;
+    SP0.hit_epoch = sc->hits.epoch;
     TRC_TRY(stream_form_general(F, SP0, sc, plan));
     TRC_TRY(stream_form_shade(F, SP0, sc, carry));
     TRC_TRY(stream_form_fresh(F, SP0, sc, E, src_desc, K));
@@ -3025,12 +3005,10 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, c
     // drain both streams whatever happened, then close the timed region on the context's stream
     for (int k = 0; k < n_slots; ++k) (void)hipStreamSynchronize(E.slot[k].stream);
     if (rc != TRC_OK) {
-        // what the bounces that did complete have added to the private tallies and to the open chunks of the hit buffer must
-        // not reach the scene with a later call: the caller (trc_trace_fast) winds the hit buffer back
-        for (int k = 0; k < n_slots; ++k) {
+        // what the bounces that did complete have added to the private tallies must not reach the scene with a later call; the
+        // caller (trc_trace_fast) winds the hit buffer back, which leaves the chunks they opened in it stale
+        for (int k = 0; k < n_slots; ++k)
             if (E.slot[k].W.tally_part) (void)hipMemset(E.slot[k].W.tally_part, 0, (size_t)TALLY_PARTS * (size_t)E.slot[k].W.tally_n * sizeof(double));
-            if (E.slot[k].W.hit_state) (void)hipMemset(E.slot[k].W.hit_state, 0, 2 * SHADE_MAX_WAVES * sizeof(unsigned long long));
-        }
         return rc;
     }
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));

@@ -344,6 +344,12 @@ class DeviceScene(object):
         _cabi.check(self.lib.trc_scene_hits_reserved(self.handle, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def hit_spectral_columns(self):
+        """spectral columns per hit the hit buffer holds: 3 W after hits of polychromatic rays, else 0"""
+        nx = C.c_int32(0)
+        _cabi.check(self.lib.trc_scene_hit_spectral_columns(self.handle, C.byref(nx)))
+        return nx.value
+
     def reserve_hits(self, capacity):
         """room for `capacity` hits in all, keeping the hits the buffer holds"""
         _cabi.check(self.lib.trc_scene_reserve_hits(self.handle, int(capacity)))
@@ -387,9 +393,7 @@ class DeviceScene(object):
         directions = None if lean else _cabi.pinned_empty((3, k))
         cols = [e_abs, None if lean else e_in, points[0], points[1], points[2]] + ([None] * 3 if lean else [directions[0], directions[1], directions[2]])   # rows: no copy afterwards
         # hits of polychromatic rays bring 3 W more columns: sample wavelengths, the spectrum that arrived, the one that left
-        nx = C.c_int32(0)
-        _cabi.check(self.lib.trc_scene_hit_spectral_columns(self.handle, C.byref(nx)))
-        nx = nx.value
+        nx = self.hit_spectral_columns()
         x = _cabi.pinned_empty((nx, k)) if (nx and k) else None
         if k and x is not None:
             _cabi.check(self.lib.trc_scene_get_hits_x(self.handle, C.byref(n), surf.ctypes.data_as(C.POINTER(C.c_int32)),

@@ -291,8 +291,9 @@ class TracerEngine(object):
             accs = [a for opt in dev.compiled.capturing_optics for a in opt.accountants]
             pend = dev.pending_hits
             keep = bool(feed and hit_capacity is None and pend is not None and pend.wanted() and accs and all(pend.holds_mark(a) for a in accs))
-            if keep and not _pending(bundle) and bundle.is_polychromatic():
-                keep = False        # (the spectra of captured hits live beside the buffer as it is: hits waiting there are delivered first)
+            if keep and ((not _pending(bundle) and bundle.is_polychromatic()) or dev.hit_spectral_columns()):
+                keep = False        # (all hits in the buffer have the same spectral columns: hits waiting there with spectra, or
+                                    # before a call that brings spectra, are delivered first)
             used = 0
             if keep:
                 used = dev.hits_reserved()[0]
