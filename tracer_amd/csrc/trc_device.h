@@ -551,6 +551,69 @@ static inline int trc_shade_class_of(const trc_surface_desc &sd) {
     return TRC_CLS_GENERAL;
 }
 
+// ================================================================================================
+// hit bookkeeping of the streaming kernels that finish hits (k_s_shade, k_s_shade_c, k_s_shade_x, k_s_absorb, k_s_bounce)
+// ================================================================================================
+// the next index of a loop over the threads of a workgroup of THREADS threads (0: blockDim.x, read where the loop steps)
+template <int THREADS>
+__device__ __forceinline__ int wg_next(int i) {
+    if constexpr (THREADS > 0) return i + THREADS;
+    else return i + blockDim.x;
+}
+
+// the nearest of a ray's linked candidates (general path: from `k`, its last one, through q3n); on equal t the lowest surface index
+// (tracer_engine.py:58-63).  t and s come in as the best so far (TRC_INF and 0x7FFFFFFF: none).
+__device__ __forceinline__ void nearest_linked(const SCand *q3n, uint32_t k, double &t, int &s) {
+    while (k != SQ_INVALID) {
+        const SCand c = q3n[k];
+        if (c.t < t || (c.t == t && (int)c.surf < s)) { t = c.t; s = (int)c.surf; }
+        k = c.next;
+    }
+}
+
+// leaving the flat surface `rec` from (hx, hy, hz) along (ox, oy, oz), the ray cannot meet it again when its own plane test is certain
+// to give t < 1e-7 (flat_surface.py:39-51: t = -((p - c).n) / (d.n), the hit point p is on the plane up to rounding): SQ_SKIP_SELF
+__device__ __forceinline__ bool leaves_flat(const double *rec, double hx, double hy, double hz, double ox, double oy, double oz) {
+    if (!trc_gm_is_flat(trc_rec_gm_kind(rec))) return false;
+    const double dtn = ox * rec[2] + oy * rec[5] + oz * rec[8];
+    const double vt = rec[2] * (hx - rec[9]) + rec[5] * (hy - rec[10]) + rec[8] * (hz - rec[11]);
+    const double scale = 1.0 + fabs(hx) + fabs(hy) + fabs(hz) + fabs(rec[9]) + fabs(rec[10]) + fabs(rec[11]);
+    return fabs(dtn) > 1e-6 && fabs(vt) + 1e-12 * scale < 5e-8 * fabs(dtn);
+}
+
+// The real (unpadded) counts of a kernel that finishes hits, one atomic per counter word and workgroup -- they all land on the same
+// words at the end of the kernel: every wave adds its hits and its rays that go on into the two spare words `spare` in LDS, then
+// thread 0 adds the hits to c_hit and c_hit2 and the rays to c_alive (null: the kernel keeps no ray alive).  IF_ANY: only counts
+// that are not 0.
+template <bool IF_ANY>
+__device__ __forceinline__ void flush_counts(double *spare, unsigned n_hit, unsigned n_alive, unsigned long long *c_hit,
+                                             unsigned long long *c_hit2, unsigned long long *c_alive) {
+    const double h = wave_sum((double)n_hit), a = wave_sum((double)n_alive);
+    if (lane_id() == 0) { atomicAdd(&spare[0], h); if (c_alive) atomicAdd(&spare[1], a); }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (!IF_ANY || spare[0] > 0.0) { atomicAdd(c_hit, (unsigned long long)(spare[0] + 0.5)); atomicAdd(c_hit2, (unsigned long long)(spare[0] + 0.5)); }
+        if (c_alive && (!IF_ANY || spare[1] > 0.0)) atomicAdd(c_alive, (unsigned long long)(spare[1] + 0.5));
+    }
+}
+
+// adds what the workgroup summed in LDS to its copy of the tally buffer, each word that is not 0: the n_sums per-surface sums, then
+// the private copy of the flux-map bins (fm_bins of them at l_fm, null: none), which follow the 3S+2 sums in the tally buffer
+template <int THREADS = 0>
+__device__ __forceinline__ void flush_sums(double *tally, const double *l_sums, int n_sums, const double *l_fm, int fm_bins, int n_surf) {
+    for (int i = threadIdx.x; i < n_sums; i = wg_next<THREADS>(i)) {
+        const double v = l_sums[i];
+        if (v != 0.0) atomicAdd(&tally[i], v);
+    }
+    if (l_fm) {
+        double *gt = tally + 3 * n_surf + 2;
+        for (int i = threadIdx.x; i < fm_bins; i = wg_next<THREADS>(i)) {
+            const double v = l_fm[i];
+            if (v != 0.0) atomicAdd(&gt[i], v);
+        }
+    }
+}
+
 // the lean shading kernels (trc_shade.hip): kernel of a class for a scene of flat surfaces only (flat) with its tables in LDS (lds)
 const void *trc_shade_carry_kernel(bool lds);      // k_s_shade_x (trc_shade.hip): every optics kind, with what the rays carry
 const void *trc_shade_lean_kernel(int cls, bool flat, bool lds, bool spec = false);

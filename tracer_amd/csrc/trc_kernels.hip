@@ -774,10 +774,7 @@ __global__ __launch_bounds__(THREADS) void k_trace_fast(FastParams P) {
     if (P.lds_tally) {
         if (lane == 0) { atomicAdd(&l_tally[3 * S], nseg); atomicAdd(&l_tally[3 * S + 1], nhit); }
         __syncthreads();
-        for (int i = tid; i < 3 * S + 2; i += THREADS) {
-            double v = l_tally[i];
-            if (v != 0.0) atomicAdd(&sc.tally[i], v);
-        }
+        flush_sums<THREADS>(sc.tally, l_tally, 3 * S + 2, nullptr, 0, S);
     } else if (lane == 0) {
         atomicAdd(&sc.tally[3 * S], nseg);
         atomicAdd(&sc.tally[3 * S + 1], nhit);
@@ -1003,10 +1000,7 @@ __global__ __launch_bounds__(THREADS) void k_trace_coop(FastParams P) {
     nhit = wave_sum(nhit);
     if (lane == 0) { atomicAdd(&l_tally[3 * S], nseg); atomicAdd(&l_tally[3 * S + 1], nhit); }
     __syncthreads();
-    for (int i = tid; i < 3 * S + 2; i += THREADS) {
-        double v = l_tally[i];
-        if (v != 0.0) atomicAdd(&sc.tally[i], v);
-    }
+    flush_sums<THREADS>(sc.tally, l_tally, 3 * S + 2, nullptr, 0, S);
 }
 
 // TRC_SURF_TERMINAL: e_out = e (1 - absorptivity) = 0 exactly, and 0 <= min_energy for every min_energy the API accepts

@@ -76,73 +76,22 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
     const int bounce0 = S.bounce_no;          // every ray of a launch is at the same bounce
     const bool aux_in = !P.src || bounce0 > 0;     // fresh rays of a source carry (energy, 1, 0): nothing was written for them
     const long long stride = (long long)gridDim.x * blockDim.x;
-#if SHC_PREFETCH == 2
-    // Two loads stand in front of every hit -- its entry of the list, then the ray record the entry points to.  Both are fetched
-    // ahead, in two stages (as in k_s_shade): while hit i is worked on, the record of hit i + 1 (whose entry arrived an iteration
-    // ago) and the entry of hit i + 2 are on their way.  22 registers.
-    uint32_t slot_a = SQ_INVALID, hs_a = SQ_INVALID, slot_n = SQ_INVALID, hs_n = SQ_INVALID;
-    double t_a = TRC_INF, t_n = TRC_INF, ae_n = 0.0, aw_n = 0.0;
-    SRayGeo g_n;
-    g_n.px = g_n.py = g_n.pz = g_n.dx = g_n.dy = 0.0; g_n.dz = 1.0; g_n.head = SQ_INVALID; g_n.idx = 0u; g_n.tail = 0ull;
-    {
-        const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-        if (i0 < nh) { slot_n = S.hl_slot[i0]; hs_n = S.hl_surf[i0]; t_n = S.hl_t[i0]; }
-        if (i0 + stride < nh) { slot_a = S.hl_slot[i0 + stride]; hs_a = S.hl_surf[i0 + stride]; t_a = S.hl_t[i0 + stride]; }
-        if (slot_n != SQ_INVALID) {
-            g_n = W.geo[slot_n];
-            if (aux_in) { ae_n = W.aux[slot_n].e; if (CLS != TRC_CLS_MIRROR) aw_n = W.aux[slot_n].wl; }
-        }
-    }
-#elif defined(SHC_PREFETCH)
-    // the entry of the next iteration is on its way while this one is worked on
-    uint32_t slot_n = SQ_INVALID, hs_n = SQ_INVALID;
-    double t_n = TRC_INF;
-    { const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x; if (i0 < nh) { slot_n = S.hl_slot[i0]; hs_n = S.hl_surf[i0]; t_n = S.hl_t[i0]; } }
-#endif
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < padded; i += stride) {
         uint32_t slot = SQ_INVALID, hs = SQ_INVALID;
         double t = TRC_INF;
         SRayGeo g;
         g.px = g.py = g.pz = g.dx = g.dy = 0.0; g.dz = 1.0; g.head = SQ_INVALID; g.idx = 0u; g.tail = 0ull;
         bool have = false;
-        double ae = 0.0, aw = 0.0;
-#if SHC_PREFETCH == 2
-        slot = slot_n; hs = hs_n; t = t_n; g = g_n; ae = ae_n; aw = aw_n;
-        have = slot != SQ_INVALID;
-        // (everything fetched for this hit is made to arrive here, before the loads for the next ones are issued: see k_s_shade)
-        asm volatile("" : "+v"(slot), "+v"(hs), "+v"(t), "+v"(slot_a), "+v"(hs_a), "+v"(t_a));
-        asm volatile("" : "+v"(g.px), "+v"(g.py), "+v"(g.pz), "+v"(g.dx), "+v"(g.dy), "+v"(g.dz), "+v"(g.head), "+v"(g.idx), "+v"(g.tail));
-        asm volatile("" : "+v"(ae), "+v"(aw));
-        slot_n = slot_a; hs_n = hs_a; t_n = t_a;
-        if (slot_n != SQ_INVALID) {
-            g_n = W.geo[slot_n];
-            if (aux_in) { ae_n = W.aux[slot_n].e; if (CLS != TRC_CLS_MIRROR) aw_n = W.aux[slot_n].wl; }
-        }
-        slot_a = SQ_INVALID; hs_a = SQ_INVALID; t_a = TRC_INF;
-        if (i + 2 * stride < nh) { slot_a = S.hl_slot[i + 2 * stride]; hs_a = S.hl_surf[i + 2 * stride]; t_a = S.hl_t[i + 2 * stride]; }
-#elif defined(SHC_PREFETCH)
-        slot = slot_n; hs = hs_n; t = t_n;
-        asm volatile("" : "+v"(slot), "+v"(hs), "+v"(t));
-        slot_n = SQ_INVALID; hs_n = SQ_INVALID; t_n = TRC_INF;
-        if (i + stride < nh) { slot_n = S.hl_slot[i + stride]; hs_n = S.hl_surf[i + stride]; t_n = S.hl_t[i + stride]; }
-#else
         if (i < nh) { slot = S.hl_slot[i]; hs = S.hl_surf[i]; t = S.hl_t[i]; }
-#endif
         bool mine = false;
         int s = 0, fl = 0;
         if (slot != SQ_INVALID) {
-            if (hs == SQ_INVALID) {
-                // general path: the nearest of the ray's linked hits; on equal t the lowest surface index (tracer_engine.py:58-63)
-                if (!have) g = W.geo[slot];
+            if (hs == SQ_INVALID) {         // general path
+                g = W.geo[slot];
                 have = true;
                 t = TRC_INF;
-                int sb = 0x7FFFFFFF;
-                for (uint32_t k = g.head; k != SQ_INVALID;) {
-                    const SCand c = W.q3n[k];
-                    if (c.t < t || (c.t == t && (int)c.surf < sb)) { t = c.t; sb = (int)c.surf; }
-                    k = c.next;
-                }
-                s = sb;
+                s = 0x7FFFFFFF;
+                nearest_linked(W.q3n, g.head, t, s);
             } else s = (int)hs;
             if ((unsigned)s < (unsigned)Sn) {
                 fl = L.sflags[s];
@@ -164,12 +113,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
             // hands it on to the ray's next record)
             if (SPEC && !aux_in)
                 trc_spectrum_of(P.spec, P.seed, P.ray_offset + (unsigned long long)(S.base + (long long)g.idx), &wl, &ref0);
-#if SHC_PREFETCH == 2
-            if (aux_in) { e = ae; wl = aw; }
-#else
             if (aux_in) { e = W.aux[slot].e; if (CLS != TRC_CLS_MIRROR) wl = W.aux[slot].wl; }
-            (void)ae; (void)aw;
-#endif
             const double *rec = L.recs + (size_t)s * sc.stride;
             const double hx = g.px + t * g.dx, hy = g.py + t * g.dy, hz = g.pz + t * g.dz;
             double ox = g.dx, oy = g.dy, oz = g.dz, e_out = 0.0;
@@ -205,15 +149,8 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
                     go.px = hx; go.py = hy; go.pz = hz; go.dx = ox; go.dy = oy; go.dz = oz;
                     go.head = SQ_INVALID;          // ready for the next bounce's search
                     go.idx = g.idx;
-                    // leaving a flat surface the ray cannot meet it again when its own plane test is certain to give t < 1e-7
-                    // (flat_surface.py:39-51: t = -((p - c).n) / (d.n), the hit point p is on the plane up to rounding)
                     uint32_t pw = (uint32_t)s;
-                    if (trc_gm_is_flat(trc_rec_gm_kind(rec))) {
-                        const double dtn = ox * rec[2] + oy * rec[5] + oz * rec[8];
-                        const double vt = rec[2] * (hx - rec[9]) + rec[5] * (hy - rec[10]) + rec[8] * (hz - rec[11]);
-                        const double scale = 1.0 + fabs(hx) + fabs(hy) + fabs(hz) + fabs(rec[9]) + fabs(rec[10]) + fabs(rec[11]);
-                        if (fabs(dtn) > 1e-6 && fabs(vt) + 1e-12 * scale < 5e-8 * fabs(dtn)) pw |= SQ_SKIP_SELF;
-                    }
+                    if (leaves_flat(rec, hx, hy, hz, ox, oy, oz)) pw |= SQ_SKIP_SELF;
                     go.tail = sray_tail(bounce0 + 1, pw);
                     W.geo[slot] = go;
                     if (aux_in) W.aux[slot].e = e_out;        // (index and wavelength stay as they are: no optics of these classes changes them)
@@ -238,9 +175,6 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
                 if (in) ts = -1;
                 todo &= ~m;
             }
-#ifdef SHC_DIAG_NO_TALLY        /* diagnostic builds only: what the scattered sums beyond LDS cost */
-            if (LDS)
-#endif
             if (ts >= 0) { atomicAdd(&tl[ts], tea); atomicAdd(&tl[Sn + ts], tei); atomicAdd(&tl[2 * Sn + ts], 1.0); }
         }
         if (P.capture) chunk_rebroadcast(hc, __ffsll((long long)my_lanes) - 1);   // hc was advanced by the lanes with a hit only
@@ -249,29 +183,8 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
     }
     chunk_close(ca, S.act_out, W.act_room);
     if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
-    // real (unpadded) counts of this bounce: hits and rays that go on -- one pair of atomics per workgroup
-    {
-        const double h = wave_sum((double)n_hit), a = wave_sum((double)n_alive);
-        double *spare = l_tally + (LDS ? 3 * Sn : 0);
-        if (lane_id() == 0) { atomicAdd(&spare[0], h); atomicAdd(&spare[1], a); }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            if (spare[0] > 0.0) { atomicAdd(&W.cnt[CN(6)], (unsigned long long)(spare[0] + 0.5)); atomicAdd(&W.cnt[CN(13 + CLS)], (unsigned long long)(spare[0] + 0.5)); }
-            if (spare[1] > 0.0) atomicAdd(&W.cnt[CN(7)], (unsigned long long)(spare[1] + 0.5));
-        }
-    }
-    if (LDS)
-        for (int i = threadIdx.x; i < 3 * Sn; i += blockDim.x) {
-            const double v = l_tally[i];
-            if (v != 0.0) atomicAdd(&L.tally[i], v);
-        }
-    if (l_fm) {
-        double *gt = L.tally + 3 * Sn + 2;
-        for (int i = threadIdx.x; i < S.lds_fm_bins; i += blockDim.x) {
-            const double v = l_fm[i];
-            if (v != 0.0) atomicAdd(&gt[i], v);
-        }
-    }
+    flush_counts<true>(l_tally + (LDS ? 3 * Sn : 0), n_hit, n_alive, &W.cnt[CN(6)], &W.cnt[CN(13 + CLS)], &W.cnt[CN(7)]);
+    flush_sums(L.tally, l_tally, LDS ? 3 * Sn : 0, l_fm, S.lds_fm_bins, Sn);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -347,15 +260,10 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
         int s = 0;
         if (slot != SQ_INVALID) {
             g = W.geo[slot];
-            if (hs == SQ_INVALID) {         // general path: the nearest of the ray's linked hits; on equal t the lowest surface index
+            if (hs == SQ_INVALID) {         // general path
                 t = TRC_INF;
-                int sb = 0x7FFFFFFF;
-                for (uint32_t k = g.head; k != SQ_INVALID;) {
-                    const SCand c = W.q3n[k];
-                    if (c.t < t || (c.t == t && (int)c.surf < sb)) { t = c.t; sb = (int)c.surf; }
-                    k = c.next;
-                }
-                s = sb;
+                s = 0x7FFFFFFF;
+                nearest_linked(W.q3n, g.head, t, s);
             } else s = (int)hs;
             mine = (unsigned)s < (unsigned)Sn;
         }
@@ -455,12 +363,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
                     go.head = SQ_INVALID;
                     go.idx = g.idx;
                     uint32_t pw = volume ? (uint32_t)prev : (uint32_t)s;        // the surface the ray leaves (a volume event: still the one before)
-                    if (!volume && out[0].shift == 0.0 && trc_gm_is_flat(trc_rec_gm_kind(rec))) {
-                        const double dtn = ox * rec[2] + oy * rec[5] + oz * rec[8];
-                        const double vt = rec[2] * (hx - rec[9]) + rec[5] * (hy - rec[10]) + rec[8] * (hz - rec[11]);
-                        const double scale = 1.0 + fabs(hx) + fabs(hy) + fabs(hz) + fabs(rec[9]) + fabs(rec[10]) + fabs(rec[11]);
-                        if (fabs(dtn) > 1e-6 && fabs(vt) + 1e-12 * scale < 5e-8 * fabs(dtn)) pw |= SQ_SKIP_SELF;
-                    }
+                    if (!volume && out[0].shift == 0.0 && leaves_flat(rec, hx, hy, hz, ox, oy, oz)) pw |= SQ_SKIP_SELF;
                     go.tail = sray_tail(bounce0 + 1, pw);
                     W.geo[slot] = go;
                     SRayAux ao;
@@ -497,28 +400,8 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
     }
     chunk_close(ca, S.act_out, W.act_room);
     if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
-    {
-        const double h = wave_sum((double)n_hit), a = wave_sum((double)n_alive);
-        double *spare = l_tally + (LDS ? 3 * Sn : 0);
-        if (lane_id() == 0) { atomicAdd(&spare[0], h); atomicAdd(&spare[1], a); }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            if (spare[0] > 0.0) { atomicAdd(&W.cnt[CN(6)], (unsigned long long)(spare[0] + 0.5)); atomicAdd(&W.cnt[CN(13 + TRC_CLS_GENERAL)], (unsigned long long)(spare[0] + 0.5)); }
-            if (spare[1] > 0.0) atomicAdd(&W.cnt[CN(7)], (unsigned long long)(spare[1] + 0.5));
-        }
-    }
-    if (LDS)
-        for (int i = threadIdx.x; i < 3 * Sn; i += blockDim.x) {
-            const double v = l_tally[i];
-            if (v != 0.0) atomicAdd(&L.tally[i], v);
-        }
-    if (l_fm) {
-        double *gt = L.tally + 3 * Sn + 2;
-        for (int i = threadIdx.x; i < S.lds_fm_bins; i += blockDim.x) {
-            const double v = l_fm[i];
-            if (v != 0.0) atomicAdd(&gt[i], v);
-        }
-    }
+    flush_counts<true>(l_tally + (LDS ? 3 * Sn : 0), n_hit, n_alive, &W.cnt[CN(6)], &W.cnt[CN(13 + TRC_CLS_GENERAL)], &W.cnt[CN(7)]);
+    flush_sums(L.tally, l_tally, LDS ? 3 * Sn : 0, l_fm, S.lds_fm_bins, Sn);
 }
 
 const void *trc_shade_carry_kernel(bool lds) { return lds ? (const void *)k_s_shade_x<true> : (const void *)k_s_shade_x<false>; }

@@ -1250,17 +1250,7 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
             const unsigned long long hh = (unsigned long long)(a_tally[3 * Sn] + 0.5);
             if (hh) { atomicAdd(&W.cnt[CN(6)], hh); atomicAdd(&W.cnt[CN(12)], hh); }
         }
-        for (int i = tid; i < 3 * Sn; i += THREADS) {
-            const double v = a_tally[i];
-            if (v != 0.0) atomicAdd(&La.tally[i], v);
-        }
-        if (a_fm) {
-            double *gt = La.tally + 3 * Sn + 2;
-            for (int i = tid; i < S.lds_fm_bins; i += THREADS) {
-                const double v = a_fm[i];
-                if (v != 0.0) atomicAdd(&gt[i], v);
-            }
-        }
+        flush_sums<THREADS>(La.tally, a_tally, 3 * Sn, a_fm, S.lds_fm_bins, Sn);
     }
 }
 
@@ -1659,11 +1649,7 @@ __global__ __launch_bounds__(256) void k_s_partition(StreamParams S) {
                 if (hs[u] == SQ_INVALID) {
                     double tt = TRC_INF;
                     int sb = 0x7FFFFFFF;
-                    for (uint32_t k = W.geo[slot[u]].head; k != SQ_INVALID;) {
-                        const SCand c = W.q3n[k];
-                        if (c.t < tt || (c.t == tt && (int)c.surf < sb)) { tt = c.t; sb = (int)c.surf; }
-                        k = c.next;
-                    }
+                    nearest_linked(W.q3n, W.geo[slot[u]].head, tt, sb);
                     hs[u] = (uint32_t)sb; t[u] = tt;
                 }
                 if (hs[u] < (uint32_t)Sn) {
@@ -1799,12 +1785,7 @@ __global__ __launch_bounds__(128 * WAVES, WAVES) void k_s_shade(StreamParams S) 
         int s = 0x7FFFFFFF;
         if (has_hit) {
             if (hs != SQ_INVALID) { t = ht; s = (int)hs; }
-            else
-                for (uint32_t k = g.head; k != SQ_INVALID;) {
-                    const SCand c = W.q3n[k];
-                    if (c.t < t || (c.t == t && (int)c.surf < s)) { t = c.t; s = (int)c.surf; }
-                    k = c.next;
-                }
+            else nearest_linked(W.q3n, g.head, t, s);
             // the hits on surfaces of the other optics classes are taken by their own kernels (trc_shade.hip)
             if ((unsigned)s < (unsigned)Sn) {
                 const int fl = Pl.sc.sflags[s];
@@ -1842,18 +1823,9 @@ __global__ __launch_bounds__(128 * WAVES, WAVES) void k_s_shade(StreamParams S) 
                 go.px = px; go.py = py; go.pz = pz; go.dx = dx; go.dy = dy; go.dz = dz;
                 go.head = SQ_INVALID;          // ready for the next bounce's search
                 go.idx = g.idx;
-                // leaving a flat surface the ray cannot meet it again when its own plane test is certain to give t < 1e-7
-                // (flat_surface.py:39-51: t = -((p - c).n) / (d.n), the hit point p is on the plane up to rounding)
+                // (a ray scattered in the medium before its first surface still has the source behind it: prev == Sn)
                 uint32_t pw = (uint32_t)prev;
-                if (prev < Sn) {          // (a ray scattered in the medium before its first surface still has the source behind it)
-                    const double *rc = recs + (size_t)prev * sc.stride;
-                    if (trc_gm_is_flat(trc_rec_gm_kind(rc))) {
-                        const double dtn = dx * rc[2] + dy * rc[5] + dz * rc[8];
-                        const double vt = rc[2] * (px - rc[9]) + rc[5] * (py - rc[10]) + rc[8] * (pz - rc[11]);
-                        const double scale = 1.0 + fabs(px) + fabs(py) + fabs(pz) + fabs(rc[9]) + fabs(rc[10]) + fabs(rc[11]);
-                        if (fabs(dtn) > 1e-6 && fabs(vt) + 1e-12 * scale < 5e-8 * fabs(dtn)) pw |= SQ_SKIP_SELF;
-                    }
-                }
+                if (prev < Sn && leaves_flat(recs + (size_t)prev * sc.stride, px, py, pz, dx, dy, dz)) pw |= SQ_SKIP_SELF;
                 go.tail = sray_tail(bounce, pw);
                 W.geo[slot] = go;
                 SRayAux ao;
@@ -1998,27 +1970,9 @@ __global__ __launch_bounds__(SA_THREADS, 2) void k_s_absorb(StreamParams S) {
         if (P.capture) chunk_rebroadcast(hc, __ffsll((long long)hit_lanes) - 1);
     }
     if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
-    {
-        const double h = wave_sum((double)n_hit);
-        if (lane_id() == 0) atomicAdd(&l_tally[3 * Sn], h);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long h = (unsigned long long)(l_tally[3 * Sn] + 0.5);
-        atomicAdd(&W.cnt[CN(6)], h);
-        atomicAdd(&W.cnt[CN(12)], h);      // (the host sizes the two lists of the batches to come by their shares)
-    }
-    for (int i = threadIdx.x; i < 3 * Sn; i += blockDim.x) {
-        const double v = l_tally[i];
-        if (v != 0.0) atomicAdd(&L.tally[i], v);
-    }
-    if (l_fm) {
-        double *gt = L.tally + 3 * Sn + 2;
-        for (int i = threadIdx.x; i < S.lds_fm_bins; i += blockDim.x) {
-            const double v = l_fm[i];
-            if (v != 0.0) atomicAdd(&gt[i], v);
-        }
-    }
+    // (CN(12): the host sizes the two lists of the batches to come by their shares)
+    flush_counts<false>(l_tally + 3 * Sn, n_hit, 0u, &W.cnt[CN(6)], &W.cnt[CN(12)], nullptr);
+    flush_sums(L.tally, l_tally, 3 * Sn, l_fm, S.lds_fm_bins, Sn);
 }
 
 // adds the private copies of one slot into the scene's tally buffer and clears them
