@@ -886,3 +886,120 @@ def test_trapezoid_bundle():
     upper = N.sum(v[1] > 1.)
     assert abs(upper / float(n) - 2.5 / 6.) < 0.015        # the strip 1 < y < 2 holds 2.5 of the 6 area units
     assert (N.arccos(N.clip(d[2], -1., 1.)) <= 0.3 + 1e-9).all()
+
+
+def _dish_device(ctx, capacity):
+    from tracer_amd import scenes
+    from tracer_amd.scene import DeviceScene, compile_scene
+    asm, _, _, src = scenes.dish()
+    dev = DeviceScene(compile_scene(asm), ctx)
+    dev.set_hit_capacity(capacity)
+    return dev, src
+
+
+def _fast_call(dev, src, n, seed, reps, stream):
+    """one trc_trace_fast of n source rays: (rays_left, hits_dropped, energy_left, hits in the buffer afterwards, entries of the
+    buffer reserved afterwards)"""
+    from tracer_amd import scenes
+    st, _ = dev.trace_fast(scenes.dish_source(n, src, seed=seed), reps, 1e-10, seed, stream=stream)
+    return st.rays_left, st.hits_dropped, st.energy_left, len(dev.get_hits()['surf']), dev.hits_reserved()[0]
+
+
+def test_counter_mirror_follows_every_writer_of_the_counter_block():
+    """
+    trc_trace_fast takes the counts a call starts from (hit cursor, hits dropped, rays left, energy left) from the host's copy
+    of the scene's counter block, not from the device.  Everything else that writes the block -- trc_scene_set_hit_capacity,
+    trc_scene_clear_hits, trc_scene_reserve_hits, trc_scene_reset_tallies -- or reads through the copy
+    (trc_scene_hits_reserved) is interleaved with traces here: after each, the call's rays_left, hits_dropped, energy_left and
+    the hits it added to the buffer equal those of the same call (same seed, same engine form) on a scene made for it alone.
+    Counts are compared exactly; so are the entries the call reserved in the hit buffer (trc_scene_hits_reserved, read through
+    the copy) in the megakernel form, where a wave reserves exactly the entries it writes -- the streaming form reserves chunks
+    whose unused tails depend on the order of the waves.
+    energy_left is compared to rel=1e-12 throughout, never exactly: both forms add each surviving ray's energy to one float64
+    with an atomic, so the last bits of the sum depend on the order the rays arrive in and two runs of the same call need not
+    agree in them (nor would two runs that happened to agree say anything about a third); and after the scene's first call the
+    figure is (A + s) - A, A the energy left by earlier calls, which is s only to an ulp of A + s.  Both are below 1e-14 of s
+    here (a few thousand addends of about 5 each; A at most 1.5e5 against s of 2e4).
+    """
+    from tracer_amd import _cabi
+    ctx = _cabi.get_context(0)
+    n = 4000
+    seen = dict(left=0, dropped=0, hits=0)
+
+    def check(dev, src, capacity, seed, reps, stream, what, n=n):
+        held, reserved = len(dev.get_hits()['surf']), dev.hits_reserved()[0]
+        got = _fast_call(dev, src, n, seed, reps, stream)
+        ref, _ = _dish_device(ctx, capacity)
+        left, dropped, energy, hits, ref_reserved = want = _fast_call(ref, src, n, seed, reps, stream)
+        ref.close()
+        assert got[0] == left and got[1] == dropped and got[3] - held == hits, (what, got, held, want)
+        assert got[2] == pytest.approx(energy, rel=1e-12), (what, got, want)
+        if stream:
+            assert got[4] - reserved >= hits, (what, got, reserved, want)
+        else:
+            assert got[4] - reserved == ref_reserved, (what, got, reserved, want)
+        seen['left'] += left; seen['dropped'] += dropped; seen['hits'] += hits
+
+    for stream in (None, True):             # the megakernel (a call of this size by default) and the streaming form
+        dev, src = _dish_device(ctx, 8 * n)
+        check(dev, src, 8 * n, 1, 2, stream, 'first call')
+        check(dev, src, 8 * n, 2, 1, stream, 'after hits_reserved, hits of the first call still held')
+        dev.reserve_hits(16 * n)
+        check(dev, src, 16 * n, 3, 2, stream, 'after reserve_hits (the buffer grew and kept its hits)')
+        _cabi.check(dev.lib.trc_scene_clear_hits(dev.handle))
+        assert dev.hits_reserved() == (0, 16 * n)
+        check(dev, src, 16 * n, 4, 2, stream, 'after clear_hits')
+        check(dev, src, 16 * n, 5, 1, stream, 'straight after another call')
+        dev.reset_tallies()
+        assert dev.hits_reserved() == (0, 16 * n)
+        check(dev, src, 16 * n, 6, 1, stream, 'after reset_tallies')
+        check(dev, src, 16 * n, 7, 2, stream, 'after reset_tallies and a call')
+        if stream is None:
+            # A buffer too small: hits are dropped, and the count of dropped hits starts over with the capacity.  The buffer has
+            # room for 1.3e6 hits beyond the capacity asked for (what the streaming form's open chunks may leave unused), so
+            # these two calls, and they alone, are large: 1.5e6 rays, 1.4e6 hits.  Megakernel form only: how many hits of the
+            # streaming form land beyond the end depends on the unused tails of its chunks, and differs from run to run.
+            dev.set_hit_capacity(100)
+            check(dev, src, 100, 8, 2, False, 'after set_hit_capacity (too small)', n=1500000)
+            _cabi.check(dev.lib.trc_scene_clear_hits(dev.handle))
+            check(dev, src, 100, 9, 2, False, 'after clear_hits of the full buffer', n=1500000)
+        dev.close()
+    assert seen['left'] > 1000 and seen['dropped'] > 100 and seen['hits'] > 1000         # (the calls did count something)
+
+
+def test_failed_fast_call_still_reports_its_stats():
+    """
+    A call that fails after its rays were traced -- TRC_TRACE_KEEP_LAST with a `last` bundle too small for the rays left,
+    TRC_ERR_CAPACITY -- still fills trc_trace_stats with what it did, and the scene goes on counting from there: the next
+    call's stats equal those of the same call on a fresh scene.
+    """
+    import ctypes as C
+    from tracer_amd import _cabi, scenes
+    ctx = _cabi.get_context(0)
+    n = 4000
+
+    def call(dev, src, seed, last_cap):
+        desc, m, seed, off = scenes.dish_source(n, src, seed=seed).source_args()
+        cols = [N.empty(last_cap) for _ in range(7)]
+        last = _cabi.make_rays(last_cap, *cols)
+        stats = _cabi.TraceStats()
+        st = dev.lib.trc_trace_fast_x(dev.handle, None, C.byref(desc), None, m, 1, 1e-10, int(seed), int(off), _cabi.TRACE_KEEP_LAST,
+                                      C.byref(last), C.byref(stats))
+        return st, stats
+
+    ref, src = _dish_device(ctx, 8 * n)
+    st, good = call(ref, src, 11, n)
+    assert st == 0 and good.rays_left > 1000 and good.segments >= n and good.hits > 1000
+    ref.close()
+    dev, src = _dish_device(ctx, 8 * n)
+    st, bad = call(dev, src, 11, 8)
+    assert st == _cabi.ERR_CAPACITY
+    assert (bad.segments, bad.hits, bad.rays_left, bad.hits_dropped, bad.bounces) == (good.segments, good.hits, good.rays_left, good.hits_dropped, good.bounces)
+    assert bad.energy_left == pytest.approx(good.energy_left, rel=1e-12)
+    held = len(dev.get_hits()['surf'])          # (the hits the failed call captured stay in the buffer)
+    again = _fast_call(dev, src, n, 12, 1, None)
+    dev.close()
+    ref, src = _dish_device(ctx, 8 * n)
+    want = _fast_call(ref, src, n, 12, 1, None)
+    ref.close()
+    assert again[:2] == want[:2] and again[3] - held == want[3] and again[2] == pytest.approx(want[2], rel=1e-12), (again, held, want)

@@ -12,24 +12,24 @@
 //
 // No CPU fallback lives here: without a GPU every entry point fails with TRC_ERR_DEVICE.
 
-#include <cstring>
-#include <cstdlib>
-#include <hip/hip_runtime.h>
-#include <rocprim/rocprim.hpp>
-
+#include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
-#include <vector>
-#include <new>
-#include <map>
-#include <mutex>
-#include <unordered_map>
 #include <deque>
-#include <utility>
+#include <map>
 #include <memory>
+#include <mutex>
+#include <new>
+#include <string>
+#include <unordered_map>
+#include <utility>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+#include <rocprim/rocprim.hpp>      // (wants <cstring> before it)
 
 #include "trc_core.h"
 #include "trc_bounds.h"
@@ -351,13 +351,87 @@ struct HitBuffer {
              int64_t *n, int32_t *surf_out, double *const dst[8], int32_t n_x, double *x_out) const;
 };
 
+// The scene's counter block: eight 64-bit words the fast engine's kernels count into (DScene.counters, DScene.energy_left),
+// CNT_ENERGY_LEFT holding the bits of a double.  A call reads all 64 bytes back once, when it ends, and the host keeps that copy
+// (the mirror): the next call knows where its counts start without a read before it runs.  Every write to the block from the host
+// is a method here and leaves the mirror in step; only HitBuffer::rollback winds the hit cursor back through device(), after a
+// failed call, when the mirror is stale anyway.
+enum CounterWord { CNT_HIT_CURSOR = 0, CNT_DROPPED = 1, CNT_LAST_CURSOR = 2, CNT_RAYS_LEFT = 3, CNT_ENERGY_LEFT = 5, CNT_WORDS = 8 };
+
+struct CounterValues { unsigned long long hit_cursor, dropped, last_cursor, rays_left; double energy_left; };
+
+class CounterBlock {
+    DevBuf<unsigned long long> d_;
+    unsigned long long mirror_[CNT_WORDS] = {};
+    bool mirror_ok_ = false;      // false from a call's snapshot() until its read_back(): the kernels are counting
+
+    CounterValues values() const {
+        CounterValues v = {mirror_[CNT_HIT_CURSOR], mirror_[CNT_DROPPED], mirror_[CNT_LAST_CURSOR], mirror_[CNT_RAYS_LEFT], 0.0};
+        memcpy(&v.energy_left, &mirror_[CNT_ENERGY_LEFT], sizeof(double));
+        return v;
+    }
+    int fetch() {
+        if (hipMemcpy(mirror_, d_.get(), sizeof(mirror_), hipMemcpyDeviceToHost) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
+        return TRC_OK;
+    }
+    // words [first, first + n) to zero, here and on the device (the context's stream is idle)
+    int clear(int first, int n) {
+        HIP_TRY(hipMemset(d_.get() + first, 0, (size_t)n * sizeof(unsigned long long)));
+        memset(mirror_ + first, 0, (size_t)n * sizeof(unsigned long long));
+        return TRC_OK;
+    }
+public:
+    int alloc() { TRC_TRY(d_.alloc(CNT_WORDS)); return zero(); }
+    unsigned long long *device() const { return d_.get(); }
+    // the block as a call finds it (read from the device only when the mirror is stale); the mirror is stale from here on
+    int snapshot(CounterValues *v) {
+        if (!mirror_ok_) TRC_TRY(fetch());
+        mirror_ok_ = false;
+        *v = values();
+        return TRC_OK;
+    }
+    // ... and as the call left it: the one read-back of a call
+    int read_back(CounterValues *v) {
+        TRC_TRY(fetch());
+        mirror_ok_ = true;
+        *v = values();
+        return TRC_OK;
+    }
+    int zero() { return clear(0, CNT_WORDS); }
+    int restart_hits() { return clear(CNT_HIT_CURSOR, 2); }     // cursor and dropped count start over
+    // the `last` cursor restarts for every call: written only where the snapshot found it moved
+    int restart_last(const CounterValues &before) {
+        const unsigned long long zero = 0;
+        if (before.last_cursor == 0ull) return TRC_OK;
+        if (hipMemcpy(d_.get() + CNT_LAST_CURSOR, &zero, sizeof(zero), hipMemcpyHostToDevice) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
+        mirror_[CNT_LAST_CURSOR] = 0ull;
+        return TRC_OK;
+    }
+    bool stale() const { return !mirror_ok_; }
+    // entries of the hit buffer reserved so far: the mirror's when it is valid; when it is stale() the caller has waited for the
+    // context's stream and word 0 is read from the device
+    int hit_cursor(unsigned long long *cursor) const {
+        if (mirror_ok_) { *cursor = mirror_[CNT_HIT_CURSOR]; return TRC_OK; }
+        HIP_TRY(hipMemcpy(cursor, d_.get() + CNT_HIT_CURSOR, sizeof(*cursor), hipMemcpyDeviceToHost));
+        return TRC_OK;
+    }
+};
+
+// what the scene's optics read that rays carry beyond the nine columns: the highest material row named by a surface between
+// tabulated materials (-1: none) and whether some wall is polychromatic.  Found once: optics do not change after creation.
+struct CarryNeeds {
+    int max_mat = -1;
+    bool poly = false;
+    bool any() const { return max_mat >= 0 || poly; }
+};
+
 struct trc_scene {
     trc_ctx *ctx;
     int32_t n_surf, stride, n_extra;
     std::vector<trc_surface_desc> surfs;
     std::vector<double> extra_h;
     bool splits;  // some optics can emit two rays per hit
-    bool carries; // some optics read what only rays of the ordered engine carry (complex indices, spectra)
+    CarryNeeds needs;   // needs.any(): some optics read what only rays of a given bundle carry (complex indices, spectra)
     // device buffers
     DevBuf<double> d_recs, d_opt, d_extra;
     DevBuf<int32_t> d_sflags;
@@ -392,15 +466,12 @@ struct trc_scene {
     DevBuf<int32_t> d_fm_of_surf;
     DevBuf<FluxMapDev> d_fms;
     DevBuf<double> d_fm_edges;
-    DevBuf<unsigned long long> d_counters;
-    double *d_energy_left;     // = (double *)(d_counters + 5)
+    CounterBlock counters;
     DevBuf<trc_source_desc> d_src_buf; // device copy of the source descriptor of the call in progress (kept between calls)
     DevBuf<double> d_spec_buf;         // device copy of the packed source spectrum of the call in progress (FastParams.spec), and its room
     size_t spec_cap;
     trc_source_desc src_host;   // ... and what it holds (src_host_ok): a Monte-Carlo loop hands over the same descriptor every call
     bool src_host_ok;
-    unsigned long long cnt_host[8];   // host copy of d_counters as trc_trace_fast left them (cnt_host_ok): the next call does not read
-    bool cnt_host_ok;                 // them back before it starts.  Every other writer of d_counters updates or drops the copy.
     DevBuf<double> d_last[7];         // device side of trc_trace_fast's `last` bundle, kept between calls (seven hipMalloc / hipFree per
     int64_t d_last_cap;               // call were a millisecond of a Monte-Carlo loop's 1e6-ray calls)
     HitBuffer hits;
@@ -490,6 +561,10 @@ struct trc_result {
 #define COOP_MAX_DEPTH 24
 #define COOP_FIXED_BYTES (COOP_E * 8 + 64 * 8 + COOP_E * 4 + 64 * 4 + 64 * 4 + 64 * 4 + COOP_LEAFCAP * 64 * 2)
 #define COOP_WAVE_BYTES(DEPTH) ((size_t)(DEPTH) * 64 * 4 + COOP_FIXED_BYTES)
+// dynamic LDS a workgroup may ask for: of the CU's 160 KiB once allowed them (kernel_allow_lds; 512 bytes stay with the kernels'
+// static LDS), and what any kernel gets unasked (k_trace_fast keeps to it)
+static const size_t LDS_MAX_ALLOWED = 160 * 1024 - 512;
+static const size_t LDS_MAX_PLAIN = 64 * 1024;
 
 struct CoopLds {
     double *exq_t;                // [COOP_E]
@@ -1014,7 +1089,7 @@ static bool surface_ends_every_ray(const trc_surface_desc &sd) {
 
 // Lets `fn` take `lds` bytes of dynamic LDS: beyond 64 KiB a kernel must be allowed them first
 static int kernel_allow_lds(const void *fn, size_t lds) {
-    if (lds <= 64 * 1024) return TRC_OK;
+    if (lds <= LDS_MAX_PLAIN) return TRC_OK;
     const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
     return TRC_OK;
@@ -1613,22 +1688,22 @@ extern "C" int trc_scene_create(trc_ctx *ctx, int32_t n_surf, const trc_surface_
     *out = nullptr;
     HIP_TRY(hipSetDevice(ctx->device));
     int max_np = 0;
-    bool splits = false, carries = false;
+    bool splits = false;
+    CarryNeeds needs;
     for (int i = 0; i < n_surf; ++i) {
         TRC_TRY(validate_surface(surfs[i], i, n_extra));
         int np = trc_gm_nparams(surfs[i].gm_kind);
         if (np > max_np) max_np = np;
         if (surfs[i].optics_kind == TRC_OPT_REFRACTIVE_HOMOGENOUS && surfs[i].opt[2] == 0.0) splits = true;
         if (surfs[i].optics_kind == TRC_OPT_REFRACTIVE_MATERIAL && surfs[i].opt[0] == 0.0) splits = true;
-        if (surfs[i].optics_kind == TRC_OPT_REFRACTIVE_MATERIAL || surfs[i].optics_kind == TRC_OPT_LAMBERTIAN_POLYCHROMATIC) carries = true;
+        if (surfs[i].optics_kind == TRC_OPT_REFRACTIVE_MATERIAL) needs.max_mat = std::max(needs.max_mat, std::max((int)surfs[i].opt[4], (int)surfs[i].opt[5]));
+        if (surfs[i].optics_kind == TRC_OPT_LAMBERTIAN_POLYCHROMATIC) needs.poly = true;
     }
     std::unique_ptr<trc_scene> sc(new (std::nothrow) trc_scene());
     if (!sc) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
     sc->ctx = ctx;
     sc->src_host_ok = false;
-    sc->cnt_host_ok = false;
     sc->d_last_cap = 0;
-    memset(sc->cnt_host, 0, sizeof(sc->cnt_host));
     sc->n_surf = n_surf;
     sc->stride = TRC_REC_HDR + max_np;
     if ((sc->stride & 1) == 0) sc->stride += 1;  // odd number of doubles: spreads records over LDS banks
@@ -1636,7 +1711,7 @@ extern "C" int trc_scene_create(trc_ctx *ctx, int32_t n_surf, const trc_surface_
     sc->surfs.assign(surfs, surfs + n_surf);
     if (n_extra > 0 && extra) sc->extra_h.assign(extra, extra + n_extra);
     sc->splits = splits;
-    sc->carries = carries;
+    sc->needs = needs;
     sc->has_kd = false;
     sc->fm_of_surf_h.assign(n_surf, -1);
     TRC_TRY(sc->d_recs.alloc((size_t)n_surf * sc->stride));
@@ -1644,14 +1719,12 @@ extern "C" int trc_scene_create(trc_ctx *ctx, int32_t n_surf, const trc_surface_
     TRC_TRY(sc->d_sflags.alloc((size_t)n_surf));
     TRC_TRY(sc->d_extra.alloc((size_t)n_extra));
     TRC_TRY(sc->d_fm_of_surf.alloc((size_t)n_surf));
-    TRC_TRY(sc->d_counters.alloc(8));
-    sc->d_energy_left = (double *)(sc->d_counters.get() + 5);      // same 64-byte block as the counters: one read-back gets both
+    TRC_TRY(sc->counters.alloc());
     TRC_TRY(scene_upload_surfaces(sc.get()));
     if (n_extra > 0 && hipMemcpy(sc->d_extra.get(), sc->extra_h.data(), (size_t)n_extra * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
         return trc_fail(TRC_ERR_DEVICE, "extra upload failed");
     if (hipMemcpy(sc->d_fm_of_surf.get(), sc->fm_of_surf_h.data(), (size_t)n_surf * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
         return trc_fail(TRC_ERR_DEVICE, "upload failed");
-    if (hipMemset(sc->d_counters.get(), 0, 8 * sizeof(unsigned long long)) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memset failed");
     TRC_TRY(scene_alloc_tally(sc.get()));
     *out = sc.release();
     return TRC_OK;
@@ -1756,20 +1829,18 @@ extern "C" int trc_scene_set_fluxmap(trc_scene *sc, int32_t surf, int32_t nu, in
     return TRC_OK;
 }
 
-// the cursor of the hit buffer (word 0 of the counter block) once the context's stream has finished
+// the cursor of the hit buffer once the context's stream has finished, for what goes on to work on the buffer
 static int scene_hit_cursor(trc_scene *sc, unsigned long long *cursor) {
     HIP_TRY(hipSetDevice(sc->ctx->device));
     HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    HIP_TRY(hipMemcpy(cursor, sc->d_counters.get(), sizeof(*cursor), hipMemcpyDeviceToHost));
-    return TRC_OK;
+    return sc->counters.hit_cursor(cursor);
 }
 
 extern "C" int trc_scene_set_hit_capacity(trc_scene *sc, int64_t capacity) {
     if (!sc || capacity < 0) return trc_fail(TRC_ERR_INVALID, "bad arguments");
     HIP_TRY(hipSetDevice(sc->ctx->device));
     HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    HIP_TRY(hipMemset(sc->d_counters.get(), 0, 2 * sizeof(unsigned long long)));      // cursor and dropped count start over
-    sc->cnt_host[0] = sc->cnt_host[1] = 0ull;
+    TRC_TRY(sc->counters.restart_hits());
     return sc->hits.set_capacity(capacity);
 }
 
@@ -1833,8 +1904,8 @@ extern "C" int trc_scene_reserve_hits(trc_scene *sc, int64_t capacity) {
 extern "C" int trc_scene_hits_reserved(trc_scene *sc, int64_t *reserved, int64_t *capacity) {
     if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
     if (reserved) {
-        unsigned long long c = sc->cnt_host[0];
-        if (!sc->cnt_host_ok) TRC_TRY(scene_hit_cursor(sc, &c));
+        unsigned long long c;
+        TRC_TRY(sc->counters.stale() ? scene_hit_cursor(sc, &c) : sc->counters.hit_cursor(&c));      // (no wait while the mirror is valid)
         *reserved = (int64_t)c;
     }
     if (capacity) *capacity = sc->hits.cap_user;
@@ -1914,9 +1985,7 @@ extern "C" int trc_scene_reset_tallies(trc_scene *sc) {
     HIP_TRY(hipSetDevice(sc->ctx->device));
     HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
     HIP_TRY(hipMemset(sc->d_tally.get(), 0, (size_t)sc->tally_n * sizeof(double)));
-    HIP_TRY(hipMemset(sc->d_counters.get(), 0, 8 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(sc->d_energy_left, 0, sizeof(double)));
-    memset(sc->cnt_host, 0, sizeof(sc->cnt_host));
+    TRC_TRY(sc->counters.zero());
     return sc->hits.reset();
 }
 
@@ -2277,7 +2346,7 @@ static DScene make_dscene(trc_scene *sc) {
     d.fm_of_surf = sc->d_fm_of_surf.get(); d.fms = sc->d_fms.get(); d.fm_edges = sc->d_fm_edges.get();
     d.tr_off = sc->tr_off;
     d.n_fm = (int32_t)sc->fms_h.size(); d.n_fm_edges = (int32_t)sc->fm_edges_h.size();
-    d.counters = sc->d_counters.get(); d.energy_left = sc->d_energy_left;
+    d.counters = sc->counters.device(); d.energy_left = (double *)(d.counters + CNT_ENERGY_LEFT);      // one 64-byte block: one read-back gets both
     sc->hits.fill(d);
     return d;
 }
@@ -2424,270 +2493,15 @@ static int source_resolve(trc_ctx *ctx, const trc_source_desc *&src, trc_source_
     return TRC_OK;
 }
 
-static int upload_source(const trc_source_desc *src, DevBuf<trc_source_desc> &d_src) {
+static int source_kind_check(const trc_source_desc *src) {
     if (src->kind < TRC_SRC_PILLBOX_DISK || src->kind > TRC_SRC_SUNSHAPE_RECT)
         return trc_fail(TRC_ERR_UNSUPPORTED, "source kind %d is not in the native table", src->kind);
-    return dev_upload(d_src, src, 1);
+    return TRC_OK;
 }
 
-// ================================================================================================
-// C-ABI: fast engine
-// ================================================================================================
-// d_spec: the packed spectrum of `src` on the device (trc_spectrum_of layout), NULL without one
-static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, const double *d_spec, int64_t n, int32_t reps,
-                           double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags, trc_rays *last,
-                           trc_trace_stats *stats) {
-    if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
-    if ((in == nullptr) == (src == nullptr)) return trc_fail(TRC_ERR_INVALID, "exactly one of `in` and `src` must be given");
-    if (n < 0 || reps < 0) return trc_fail(TRC_ERR_INVALID, "n and reps must be >= 0");
-    trc_source_desc src_res;
-    TRC_TRY(source_resolve(sc->ctx, src, src_res, "trc_trace_fast"));
-    if (sc->splits) return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has ray-splitting optics: use trc_trace_ordered");
-    const StreamKnobs knobs = stream_knobs();
-    // Rays that carry the imaginary part of a complex index, materials evaluated at their wavelength or a sampled spectrum are
-    // traced by the streaming form (k_s_shade_x); the megakernel knows nothing of them.
-    const bool carry = sc->carries || (in && (in->ref_index_im || in->spectra || in->mat));
-    const int carry_W = (in && in->spectra && in->spec_wl) ? in->n_spec : 0;
-    const int carry_mat = (in && in->mat) ? (int)in->n_mat : 0;
-    if (carry) {
-        if (!in) return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has optics that read what only the rays of a given bundle carry (materials, spectra)");
-        if (carry_W < 0 || carry_W > 4096 || carry_mat < 0 || carry_mat > 64) return trc_fail(TRC_ERR_INVALID, "trc_trace_fast: n_spec or n_mat out of range");
-        int max_mat = -1;
-        bool poly = false;
-        for (const trc_surface_desc &sd : sc->surfs) {
-            if (sd.optics_kind == TRC_OPT_REFRACTIVE_MATERIAL) max_mat = std::max(max_mat, std::max((int)sd.opt[4], (int)sd.opt[5]));
-            if (sd.optics_kind == TRC_OPT_LAMBERTIAN_POLYCHROMATIC) poly = true;
-        }
-        if (max_mat >= 0 && (!in->wavelength || carry_mat <= max_mat))
-            return trc_fail(TRC_ERR_INVALID, "trc_trace_fast: surfaces between materials need the rays' wavelengths and the materials evaluated at them (trc_rays.mat)");
-        if (poly && carry_W < 2) return trc_fail(TRC_ERR_INVALID, "trc_trace_fast: a polychromatic wall needs rays with spectra of at least two samples");
-        if ((flags & TRC_TRACE_MEGAKERNEL) || n < 64)
-            return trc_fail(TRC_ERR_UNSUPPORTED, "complex refractive indices and spectra travel with the streaming form of the fast engine (64 rays or more) and with trc_trace_ordered");
-    }
-    // TRC_TRACE_ACCEL without a Kd-tree: the streaming form searches its own grid; the megakernel tests every box
-    trc_ctx *ctx = sc->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    trc_trace_stats s;
-    memset(&s, 0, sizeof(s));
-    // the call's work; the stats it gathered are handed back whatever its outcome
-    const int st = [&]() -> int {
-        DevRays dr;
-        trc_source_desc *d_src = nullptr;
-        double *d_last[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        double tally_before[2] = {0, 0};
-        unsigned long long cnt_before[4] = {0, 0, 0, 0};
-        double eleft_before = 0;
-        double stream_seg = 0, stream_hits = 0;
-        bool stream_counts_known = false;
-        const int S = sc->n_surf;
-        double *carry_d[4] = {nullptr, nullptr, nullptr, nullptr};      // Im of the index, materials, sample wavelengths, spectra
-        DevBuf<double> carry_own[4];                                    // ... copied here unless the caller's are on the device
-        if (in) {
-            TRC_TRY(check_rays(in, n, "trc_trace_fast"));
-            TRC_TRY(stage_rays(in, n, true, &dr));
-            if (carry) {        // the carried columns: rows of the bundle's own length in->n apart on the host, n apart here
-                struct { const double *src; int rows; } blk[4] = {{in->ref_index_im, 1}, {in->mat, 2 * carry_mat}, {carry_W ? in->spec_wl : nullptr, carry_W},
-                                                                  {carry_W ? in->spectra : nullptr, carry_W}};
-                for (int b = 0; b < 4; ++b) {
-                    if (!blk[b].src || blk[b].rows <= 0) continue;
-                    if (in->on_device && in->n == n) { carry_d[b] = (double *)blk[b].src; continue; }
-                    TRC_TRY(carry_own[b].alloc((size_t)blk[b].rows * (size_t)n));
-                    carry_d[b] = carry_own[b].get();
-                    if (hipMemcpy2D(carry_d[b], (size_t)n * 8, blk[b].src, (size_t)in->n * 8, (size_t)n * 8, (size_t)blk[b].rows,
-                                    in->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) != hipSuccess)
-                        return trc_fail(TRC_ERR_DEVICE, "upload of the carried columns failed");
-                }
-            }
-        }
-        else {
-            // the scene keeps a device buffer for the descriptor of the call in progress (hipMalloc / hipFree per call
-            // cost more than the upload)
-            if (src->kind < TRC_SRC_PILLBOX_DISK || src->kind > TRC_SRC_SUNSHAPE_RECT) return trc_fail(TRC_ERR_UNSUPPORTED, "source kind %d is not in the native table", src->kind);
-            if (!sc->d_src_buf) { TRC_TRY(sc->d_src_buf.alloc(1)); sc->src_host_ok = false; }
-            if (!(sc->src_host_ok && memcmp(&sc->src_host, src, sizeof(trc_source_desc)) == 0)) {
-                sc->src_host_ok = false;
-                if (hipMemcpy(sc->d_src_buf.get(), src, sizeof(trc_source_desc), hipMemcpyHostToDevice) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "source upload failed");
-                memcpy(&sc->src_host, src, sizeof(trc_source_desc));
-                sc->src_host_ok = true;
-            }
-            d_src = sc->d_src_buf.get();
-        }
-        int64_t last_cap = 0;
-        if (flags & TRC_TRACE_KEEP_LAST) {
-            if (!last || !last->x || !last->y || !last->z || !last->dx || !last->dy || !last->dz || !last->e || last->on_device)
-                return trc_fail(TRC_ERR_INVALID, "TRC_TRACE_KEEP_LAST needs a host `last` bundle with x..e");
-            last_cap = last->n;
-            if (sc->d_last_cap < last_cap) {
-                for (auto &col : sc->d_last) col.reset();
-                sc->d_last_cap = 0;
-                for (auto &col : sc->d_last)
-                    if (int e = col.alloc((size_t)last_cap)) { for (auto &c : sc->d_last) c.reset(); return e; }
-                sc->d_last_cap = last_cap;
-            }
-            for (int i = 0; i < 7; ++i) d_last[i] = sc->d_last[i].get();
-        }
-        // counters and the energy left live in one 64-byte block: one read before, one after
-        unsigned long long blk_before[8];
-        if (sc->cnt_host_ok) memcpy(blk_before, sc->cnt_host, sizeof(blk_before));
-        else if (hipMemcpy(blk_before, sc->d_counters.get(), sizeof(blk_before), hipMemcpyDeviceToHost) != hipSuccess)
-            return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
-        sc->cnt_host_ok = false;          // (until this call has read them back at its end)
-        for (int i = 0; i < 4; ++i) cnt_before[i] = blk_before[i];
-        // polychromatic hits: the captured ones keep their sample wavelengths and their spectrum before and after (3 W columns beside
-        // the hit buffer); a call whose hits would not have the shape of those the buffer holds is refused before anything is written
-        double *hit_x = nullptr;
-        bool captures = false;
-        if (sc->hits.cap > 0)
-            for (int i = 0; i < S && !captures; ++i) captures = (sc->surfs[i].flags & TRC_SURF_CAPTURE_HITS) != 0;
-        if (captures) TRC_TRY(sc->hits.spectra_for(3 * carry_W, cnt_before[0], &hit_x));
-        const int64_t dirty_before = sc->hits.begin_call();      // (... and then says how far the hit buffer was used)
-        memcpy(&eleft_before, &blk_before[5], sizeof(double));
-        // the `last` cursor restarts for every call
-        if (blk_before[2] != 0ull) {
-            unsigned long long zero = 0;
-            if (hipMemcpy(sc->d_counters.get() + 2, &zero, sizeof(zero), hipMemcpyHostToDevice) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
-        }
-
-        FastParams P;
-        memset(&P, 0, sizeof(P));
-        P.sc = make_dscene(sc);
-        P.x = dr.x; P.y = dr.y; P.z = dr.z; P.dx = dr.dx; P.dy = dr.dy; P.dz = dr.dz; P.e = dr.e;
-        P.ref = dr.ref; P.wl = dr.wl; P.rid = dr.rid;
-        CarryIn carry_in;
-        carry_in.hit_x = hit_x; carry_in.hit_x_cap = hit_x ? sc->hits.cap : 0;
-        carry_in.ref_im = carry_d[0]; carry_in.mat = carry_d[1]; carry_in.spec_wl = carry_d[2]; carry_in.spec = carry_d[3]; carry_in.n_mat = carry_mat; carry_in.n_spec = carry_W;
-        P.src = d_src;
-        P.spec = d_spec;
-        P.n = n; P.reps = reps; P.flags = flags; P.min_energy = min_energy; P.seed = seed; P.ray_offset = ray_offset;
-        P.lx = d_last[0]; P.ly = d_last[1]; P.lz = d_last[2]; P.ldx = d_last[3]; P.ldy = d_last[4]; P.ldz = d_last[5]; P.le = d_last[6];
-        P.last_cap = last_cap;
-        P.capture = captures ? 1 : 0;
-
-        const bool accel = sc->has_kd && (flags & TRC_TRACE_ACCEL);
-        size_t b_buie = src ? (size_t)TRC_BUIE_STAGED * 8 : 0;
-        size_t b_tally = (size_t)(3 * S + 2) * 8;
-        // preferred: single-precision conservative search with everything it needs in LDS (up to 160 KiB per CU)
-        bool m32 = sc->accel_ok && S <= 65535 &&
-                   (!accel || (sc->accel_kd_ok && sc->kd_nodes <= COOP_MAX_NODES && sc->accel.kd_depth <= COOP_MAX_DEPTH));
-        int threads = 512;
-        size_t lds = 0;
-        if (m32) {
-            size_t b_acc = (size_t)6 * S * 4 + (accel ? ((size_t)2 * sc->kd_nodes * 4 + (size_t)sc->kd_nalways * 4 + (size_t)sc->kd_nleaf * 2)
-                                                      : (8 + sc->accel.brute_leaf.size() * 2)) +
-                           sc->accel.unbounded.size() * 4 + 32;
-            const size_t b_wave = COOP_WAVE_BYTES(accel ? (sc->accel.kd_depth > 0 ? sc->accel.kd_depth : 1) : 1);
-            lds = b_buie + b_tally + b_acc + (size_t)(threads / 64) * b_wave;
-            if (lds > 160 * 1024 - 512) { threads = 256; lds = b_buie + b_tally + b_acc + (size_t)(threads / 64) * b_wave; }
-            if (lds > 160 * 1024 - 512) m32 = false;
-            P.lds_tally = 1;
-            P.lds_scene = 0;
-        }
-        if (!m32) {
-            threads = 256;
-            size_t b_scene = (size_t)S * sc->stride * 8;
-            if (sc->has_kd) b_scene += (size_t)sc->kd_nodes * 8 + ((size_t)sc->kd_nodes * 2 + sc->kd_nleaf + sc->kd_nalways) * 4 + 8;
-            const size_t LDS_MAX = 64 * 1024;
-            lds = b_buie;
-            P.lds_tally = (lds + b_tally <= LDS_MAX) ? 1 : 0;
-            if (P.lds_tally) lds += b_tally;
-            P.lds_scene = (lds + b_scene <= LDS_MAX) ? 1 : 0;
-            if (P.lds_scene) lds += b_scene;
-        }
-        // Large calls run the streaming engine (phases as separate kernels connected by HBM queues, trc_stream.inc);
-        // small ones the persistent megakernel, which needs one launch and no workspace.  TRC_TRACE_STREAM /
-        // TRC_TRACE_MEGAKERNEL force one or the other.
-        StreamPlan plan = {0, 0, true};
-        const bool stream_ok = n >= 64 && stream_plan(sc, (flags & TRC_TRACE_ACCEL) != 0, knobs, &plan);
-        const bool force_stream = (flags & TRC_TRACE_STREAM) || carry;
-        const bool force_mega = !carry && (flags & TRC_TRACE_MEGAKERNEL);
-        // (a scene on the large grid -- a mesh of 1e5 faces -- has nothing but its boxes to search in the megakernel: 2e5 rays on the
-        // relief of 105 800 triangles took 570 ms there, 1.3 ms here)
-        const long long stream_from = plan.mode == 3 ? 4096 : TRC_STREAM_MIN_RAYS;
-        const bool use_stream = stream_ok && (force_stream || (!force_mega && n >= stream_from));
-        if (carry && !use_stream) return trc_fail(TRC_ERR_UNSUPPORTED, "no streaming form for this scene: rays that carry complex indices or spectra go through trc_trace_ordered");
-        if (use_stream) {
-            if (!sc->stream_eng) {
-                sc->stream_eng = new (std::nothrow) StreamEngine();      // (value-initialised: all zero)
-                if (!sc->stream_eng) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
-            }
-            if (int e = stream_trace(sc, P, carry_in, plan, knobs, src, *sc->stream_eng, &s, &stream_seg, &stream_hits)) {
-                sc->hits.rollback(sc->d_counters.get(), cnt_before[0]);     // (the hits captured by the bounces that completed)
-                return e;
-            }
-            stream_counts_known = true;
-        } else {
-        (void)hipStreamSynchronize(ctx->stream);       // (the sums of an earlier streaming call may still be on their way into the buffer)
-        if (hipMemcpy(tally_before, sc->d_tally.get() + 3 * S, sizeof(tally_before), hipMemcpyDeviceToHost) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
-        void (*kern)(FastParams) = nullptr;
-        const bool sun = d_src && source_is_sunshape(src->kind);     // (a tabulated sunshape: the instances that know it)
-        if (sun && P.spec) {
-            if (m32) kern = threads == 512 ? k_trace_coop<512, true, true> : k_trace_coop<256, true, true>;
-            else kern = k_trace_fast<256, true, true>;
-        } else if (sun) {
-            if (m32) kern = threads == 512 ? k_trace_coop<512, false, true> : k_trace_coop<256, false, true>;
-            else kern = k_trace_fast<256, false, true>;
-        } else if (P.spec) {       // (a source with a spectrum: the instances that draw the wavelength)
-            if (m32) kern = threads == 512 ? k_trace_coop<512, true> : k_trace_coop<256, true>;
-            else kern = k_trace_fast<256, true>;
-        } else {
-            if (m32) kern = threads == 512 ? k_trace_coop<512> : k_trace_coop<256>;
-            else kern = k_trace_fast<256>;
-        }
-        // persistent grid: as many workgroups as are resident at once (at most 8 per CU), never more waves than rays/64
-        unsigned resident = 0;
-        TRC_TRY(kernel_grid_cap((const void *)kern, threads, lds, 8, ctx->n_cu, &resident));
-        long long grid = resident;
-        long long max_grid = (n + threads - 1) / threads;
-        if (grid > max_grid) grid = max_grid;
-        if (grid < 1) grid = 1;
-        if (n > 0) {
-            if (hipEventRecord(ctx->ev0, ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "event record failed");
-            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), lds, ctx->stream, P);
-            hipError_t le = hipGetLastError();
-            if (le != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_trace_fast launch failed: %s", hipGetErrorString(le));
-            if (hipEventRecord(ctx->ev1, ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "event record failed");
-            hipError_t se = hipStreamSynchronize(ctx->stream);
-            if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_trace_fast failed: %s", hipGetErrorString(se));
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-            s.kernel_ms = ms;
-            s.launches = 1;
-        }
-        }
-        unsigned long long blk_after[8], cnt_after[4];
-        double eleft_after;
-        if (hipMemcpy(blk_after, sc->d_counters.get(), sizeof(blk_after), hipMemcpyDeviceToHost) != hipSuccess)
-            return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
-        for (int i = 0; i < 4; ++i) cnt_after[i] = blk_after[i];
-        memcpy(&eleft_after, &blk_after[5], sizeof(double));
-        memcpy(sc->cnt_host, blk_after, sizeof(blk_after));
-        sc->cnt_host_ok = true;
-        sc->hits.end_call(dirty_before, blk_after[0]);
-        if (stream_counts_known) {              // the streaming form counted on the host
-            s.segments = (int64_t)(stream_seg + 0.5);
-            s.hits = (int64_t)(stream_hits + 0.5);
-        } else {
-            double tally_after[2];
-            if (hipMemcpy(tally_after, sc->d_tally.get() + 3 * S, sizeof(tally_after), hipMemcpyDeviceToHost) != hipSuccess)
-                return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
-            s.segments = (int64_t)(tally_after[0] - tally_before[0] + 0.5);
-            s.hits = (int64_t)(tally_after[1] - tally_before[1] + 0.5);
-        }
-        s.rays_left = (int64_t)(cnt_after[3] - cnt_before[3]);
-        s.hits_dropped = (int64_t)(cnt_after[1] - cnt_before[1]);
-        s.energy_left = eleft_after - eleft_before;
-        s.bounces = reps;
-        if (flags & TRC_TRACE_KEEP_LAST) {
-            int64_t m = (int64_t)cnt_after[2];
-            if (m > last_cap) return trc_fail(TRC_ERR_CAPACITY, "%lld rays left but `last` holds %lld", (long long)m, (long long)last_cap);
-            double *dst[7] = {last->x, last->y, last->z, last->dx, last->dy, last->dz, last->e};
-            for (int i = 0; i < 7 && m > 0; ++i) TRC_TRY(dev_download(dst[i], d_last[i], (size_t)m));
-            last->n = m;
-        }
-        return TRC_OK;
-    }();
-    if (stats) *stats = s;
-    return st;
+static int upload_source(const trc_source_desc *src, DevBuf<trc_source_desc> &d_src) {
+    TRC_TRY(source_kind_check(src));
+    return dev_upload(d_src, src, 1);
 }
 
 // ================================================================================================
@@ -2840,32 +2654,33 @@ extern "C" int trc_source_generate_x(trc_ctx *ctx, const trc_source_desc *src, c
     return TRC_OK;
 }
 
-extern "C" int trc_trace_fast(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, int64_t n, int32_t reps,
-                              double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags, trc_rays *last,
-                              trc_trace_stats *stats) {
-    return trace_fast_impl(sc, in, src, nullptr, n, reps, min_energy, seed, ray_offset, flags, last, stats);
+// ================================================================================================
+// what a call brings: the source's spectrum, the columns rays carry beyond the nine (both engines)
+// ================================================================================================
+// The spectrum of a source descriptor as the engines take it: checked, its table packed (spectrum_pack).  desc NULL: none.
+struct SourceSpectrum {
+    const trc_source_spectrum *desc = nullptr;
+    std::vector<double> tab;
+};
+
+// ... made by the _x entry points (`who`) from their arguments; a spectrum belongs to a source descriptor
+static int source_spectrum_make(const trc_source_spectrum *spec, const trc_rays *in, const trc_source_desc *src, const char *who, SourceSpectrum *out) {
+    if (!spectrum_given(spec)) return TRC_OK;
+    if (in) return trc_fail(TRC_ERR_INVALID, "%s: a spectrum belongs to a source descriptor, not to a given bundle", who);
+    if (!src) return trc_fail(TRC_ERR_INVALID, "%s: a spectrum needs a source descriptor", who);
+    TRC_TRY(spectrum_pack(spec, who, out->tab));
+    out->desc = spec;
+    return TRC_OK;
 }
 
-static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
-                              const std::vector<double> *spec_tab, int64_t n, int32_t reps, double min_energy, uint64_t seed,
-                              uint64_t ray_offset, int32_t flags, trc_result **out, trc_trace_stats *stats);
-
-// The spectrum travels to the engines as FastParams.spec (trc_spectrum_of layout: n, constant wavelength, index, then the table),
-// kept on the scene between calls.  The SPEC instances of the kernels draw the wavelength where a source ray first needs one.
-extern "C" int trc_trace_fast_x(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
-                                int64_t n, int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags,
-                                trc_rays *last, trc_trace_stats *stats) {
-    if (!spectrum_given(spec)) return trc_trace_fast(sc, in, src, n, reps, min_energy, seed, ray_offset, flags, last, stats);
-    if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
-    if (in) return trc_fail(TRC_ERR_INVALID, "trc_trace_fast_x: a spectrum belongs to a source descriptor, not to a given bundle");
-    if (!src) return trc_fail(TRC_ERR_INVALID, "trc_trace_fast_x: a spectrum needs a source descriptor");
-    std::vector<double> tab;
-    TRC_TRY(spectrum_pack(spec, "trc_trace_fast_x", tab));
-    const int n_tab = spec->kind == TRC_SPECTRUM_TABLE ? spec->n : 0;
-    std::vector<double> packed((size_t)3 + tab.size());
-    packed[0] = (double)n_tab; packed[1] = spec->wavelength; packed[2] = spec->ref_index;
-    std::copy(tab.begin(), tab.end(), packed.begin() + 3);
-    HIP_TRY(hipSetDevice(sc->ctx->device));
+// The spectrum travels to the fast engine as FastParams.spec (trc_spectrum_of layout: n, constant wavelength, index, then the
+// table), in a buffer kept on the scene between calls.  The SPEC instances of the kernels draw the wavelength where a source ray
+// first needs one.
+static int scene_stage_spectrum(trc_scene *sc, const SourceSpectrum &sp, const double **d_spec) {
+    const int n_tab = sp.desc->kind == TRC_SPECTRUM_TABLE ? sp.desc->n : 0;
+    std::vector<double> packed((size_t)3 + sp.tab.size());
+    packed[0] = (double)n_tab; packed[1] = sp.desc->wavelength; packed[2] = sp.desc->ref_index;
+    std::copy(sp.tab.begin(), sp.tab.end(), packed.begin() + 3);
     if (sc->spec_cap < packed.size()) {
         sc->spec_cap = 0;
         TRC_TRY(sc->d_spec_buf.alloc((size_t)3 + 3 * TRC_SPECTRUM_MAX_POINTS));     // (room for any table: allocated once)
@@ -2873,30 +2688,342 @@ extern "C" int trc_trace_fast_x(trc_scene *sc, const trc_rays *in, const trc_sou
     }
     // (the stream is idle between calls: every call ends with a synchronous read of its counters)
     HIP_TRY(hipMemcpy(sc->d_spec_buf.get(), packed.data(), packed.size() * 8, hipMemcpyHostToDevice));
-    return trace_fast_impl(sc, nullptr, src, sc->d_spec_buf.get(), n, reps, min_energy, seed, ray_offset, flags, last, stats);
+    *d_spec = sc->d_spec_buf.get();
+    return TRC_OK;
 }
 
-extern "C" int trc_trace_ordered_x(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
-                                   int64_t n, int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags,
-                                   trc_result **out, trc_trace_stats *stats) {
-    if (!spectrum_given(spec)) return trace_ordered_impl(sc, in, src, nullptr, nullptr, n, reps, min_energy, seed, ray_offset, flags, out, stats);
-    if (!sc || !out) return trc_fail(TRC_ERR_INVALID, "trc_trace_ordered_x: bad arguments");
-    *out = nullptr;
-    if (in) return trc_fail(TRC_ERR_INVALID, "trc_trace_ordered_x: a spectrum belongs to a source descriptor, not to a given bundle");
-    if (!src) return trc_fail(TRC_ERR_INVALID, "trc_trace_ordered_x: a spectrum needs a source descriptor");
-    std::vector<double> tab;
-    TRC_TRY(spectrum_pack(spec, "trc_trace_ordered_x", tab));
-    return trace_ordered_impl(sc, nullptr, src, spec, &tab, n, reps, min_energy, seed, ray_offset, flags, out, stats);
+// The device copy of the source descriptor of the call in progress, kept on the scene with what it holds: a Monte-Carlo loop hands
+// over the same descriptor every call (hipMalloc / hipFree per call cost more than the upload).
+static int scene_stage_source(trc_scene *sc, const trc_source_desc *src, const trc_source_desc **d_src) {
+    TRC_TRY(source_kind_check(src));
+    if (!sc->d_src_buf) { TRC_TRY(sc->d_src_buf.alloc(1)); sc->src_host_ok = false; }
+    if (!(sc->src_host_ok && memcmp(&sc->src_host, src, sizeof(trc_source_desc)) == 0)) {
+        sc->src_host_ok = false;
+        if (hipMemcpy(sc->d_src_buf.get(), src, sizeof(trc_source_desc), hipMemcpyHostToDevice) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "source upload failed");
+        memcpy(&sc->src_host, src, sizeof(trc_source_desc));
+        sc->src_host_ok = true;
+    }
+    *d_src = sc->d_src_buf.get();
+    return TRC_OK;
 }
 
-extern "C" int trc_trace_ordered(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, int64_t n, int32_t reps,
-                                 double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags, trc_result **out,
-                                 trc_trace_stats *stats) {
-    return trace_ordered_impl(sc, in, src, nullptr, nullptr, n, reps, min_energy, seed, ray_offset, flags, out, stats);
+// What the bundle `in` (NULL: a source descriptor, whose rays carry nothing) brings beyond the nine columns, against what the
+// scene's optics read: lay->n_mat and lay->W.  has_im is the ordered engine's to set.
+static int check_carried(const CarryNeeds &needs, const trc_rays *in, const char *who, PayLayout *lay) {
+    lay->n_mat = (in && in->mat) ? (int)in->n_mat : 0;
+    lay->W = (in && in->spectra && in->spec_wl) ? in->n_spec : 0;
+    if (lay->W < 0 || lay->W > 4096 || lay->n_mat < 0 || lay->n_mat > 64) return trc_fail(TRC_ERR_INVALID, "%s: n_spec or n_mat out of range", who);
+    if (needs.max_mat >= 0 && (!in || !in->wavelength || lay->n_mat <= needs.max_mat))
+        return trc_fail(TRC_ERR_INVALID, "%s: the scene refracts between tabulated materials: the bundle needs wavelengths and the %d materials' indices at them (trc_rays.mat)",
+                        who, needs.max_mat + 1);
+    if (needs.poly && lay->W < 2)
+        return trc_fail(TRC_ERR_INVALID, "%s: a polychromatic wall needs rays with spectra of at least two samples (trc_rays.spectra, spec_wl)", who);
+    return TRC_OK;
+}
+
+// the carried columns of a bundle in the order of PayLayout's rows: Im of the index, materials, sample wavelengths, spectra
+struct CarriedBlock { const double *src; int rows; };
+static void carried_blocks(const trc_rays *in, const PayLayout &lay, CarriedBlock blk[4]) {
+    blk[0] = {in->ref_index_im, 1};
+    blk[1] = {in->mat, 2 * lay.n_mat};
+    blk[2] = {lay.W ? in->spec_wl : nullptr, lay.W};
+    blk[3] = {lay.W ? in->spectra : nullptr, lay.W};
+}
+
+// `rows` rows of a carried column to the device block `dst`: in->n apart where they come from, n apart there
+static int stage_carried(double *dst, const double *src, int rows, int64_t n, const trc_rays *in) {
+    if (rows <= 0 || n <= 0) return TRC_OK;
+    if (hipMemcpy2D(dst, (size_t)n * 8, src, (size_t)in->n * 8, (size_t)n * 8, (size_t)rows,
+                    in->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) != hipSuccess)
+        return trc_fail(TRC_ERR_DEVICE, "upload of the carried columns failed");
+    return TRC_OK;
 }
 
 // ================================================================================================
-// C-ABI: ordered engine
+// fast engine
+// ================================================================================================
+// One call: its arguments, and what its steps hand one another
+struct FastCall {
+    // the arguments of trc_trace_fast_x (src as source_resolve left it)
+    trc_scene *sc; const trc_rays *in; const trc_source_desc *src; const SourceSpectrum *spec;
+    int64_t n; int32_t reps; double min_energy; uint64_t seed, ray_offset; int32_t flags; trc_rays *last;
+    // fast_check_args: the knobs, whether the rays carry more than the megakernel knows, and what
+    trc_source_desc src_res;
+    StreamKnobs knobs;
+    bool carry;
+    PayLayout lay;
+    // fast_stage_inputs: the bundle and its carried columns (the caller's own when they are on the device, else copies held
+    // here), or the source descriptor and its spectrum
+    DevRays dr;
+    double *carry_d[4];
+    DevBuf<double> carry_own[4];
+    const trc_source_desc *d_src;
+    const double *d_spec;
+    // fast_stage_last
+    double *d_last[7];
+    int64_t last_cap;
+    // fast_begin
+    CounterValues before;
+    int64_t dirty_before;
+    bool captures;
+    double *hit_x;
+    // segments and hits: counted on the host by the streaming form, else the difference of the tallies from tally_before
+    bool stream_counts_known;
+    double stream_seg, stream_hits, tally_before[2];
+    trc_trace_stats s;
+};
+
+static int fast_check_args(FastCall &C) {
+    trc_scene *sc = C.sc;
+    if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
+    if ((C.in == nullptr) == (C.src == nullptr)) return trc_fail(TRC_ERR_INVALID, "exactly one of `in` and `src` must be given");
+    if (C.n < 0 || C.reps < 0) return trc_fail(TRC_ERR_INVALID, "n and reps must be >= 0");
+    TRC_TRY(source_resolve(sc->ctx, C.src, C.src_res, "trc_trace_fast"));
+    if (sc->splits) return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has ray-splitting optics: use trc_trace_ordered");
+    C.knobs = stream_knobs();
+    // Rays that carry the imaginary part of a complex index, materials evaluated at their wavelength or a sampled spectrum are
+    // traced by the streaming form (k_s_shade_x); the megakernel knows nothing of them.
+    C.carry = sc->needs.any() || (C.in && (C.in->ref_index_im || C.in->spectra || C.in->mat));
+    if (C.carry && !C.in) return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has optics that read what only the rays of a given bundle carry (materials, spectra)");
+    TRC_TRY(check_carried(sc->needs, C.in, "trc_trace_fast", &C.lay));
+    if (C.carry && ((C.flags & TRC_TRACE_MEGAKERNEL) || C.n < 64))
+        return trc_fail(TRC_ERR_UNSUPPORTED, "complex refractive indices and spectra travel with the streaming form of the fast engine (64 rays or more) and with trc_trace_ordered");
+    return TRC_OK;
+}
+
+static int fast_stage_inputs(FastCall &C) {
+    if (!C.in) {
+        if (C.spec->desc) TRC_TRY(scene_stage_spectrum(C.sc, *C.spec, &C.d_spec));
+        return scene_stage_source(C.sc, C.src, &C.d_src);
+    }
+    TRC_TRY(check_rays(C.in, C.n, "trc_trace_fast"));
+    TRC_TRY(stage_rays(C.in, C.n, true, &C.dr));
+    if (!C.carry) return TRC_OK;
+    CarriedBlock blk[4];
+    carried_blocks(C.in, C.lay, blk);
+    for (int b = 0; b < 4; ++b) {
+        if (!blk[b].src || blk[b].rows <= 0) continue;
+        if (C.in->on_device && C.in->n == C.n) { C.carry_d[b] = (double *)blk[b].src; continue; }
+        TRC_TRY(C.carry_own[b].alloc((size_t)blk[b].rows * (size_t)C.n));
+        C.carry_d[b] = C.carry_own[b].get();
+        TRC_TRY(stage_carried(C.carry_d[b], blk[b].src, blk[b].rows, C.n, C.in));
+    }
+    return TRC_OK;
+}
+
+// the device side of the `last` bundle, kept on the scene between calls
+static int fast_stage_last(FastCall &C) {
+    trc_scene *sc = C.sc;
+    const trc_rays *last = C.last;
+    if (!(C.flags & TRC_TRACE_KEEP_LAST)) return TRC_OK;
+    if (!last || !last->x || !last->y || !last->z || !last->dx || !last->dy || !last->dz || !last->e || last->on_device)
+        return trc_fail(TRC_ERR_INVALID, "TRC_TRACE_KEEP_LAST needs a host `last` bundle with x..e");
+    C.last_cap = last->n;
+    if (sc->d_last_cap < C.last_cap) {
+        for (auto &col : sc->d_last) col.reset();
+        sc->d_last_cap = 0;
+        for (auto &col : sc->d_last)
+            if (int e = col.alloc((size_t)C.last_cap)) { for (auto &c : sc->d_last) c.reset(); return e; }
+        sc->d_last_cap = C.last_cap;
+    }
+    for (int i = 0; i < 7; ++i) C.d_last[i] = sc->d_last[i].get();
+    return TRC_OK;
+}
+
+// Where the call's counts start, and the hit buffer made ready.  Polychromatic hits: the captured ones keep their sample
+// wavelengths and their spectrum before and after (3 W columns beside the hit buffer); a call whose hits would not have the shape
+// of those the buffer holds is refused before anything is written.
+static int fast_begin(FastCall &C) {
+    trc_scene *sc = C.sc;
+    TRC_TRY(sc->counters.snapshot(&C.before));
+    if (sc->hits.cap > 0)
+        for (int i = 0; i < sc->n_surf && !C.captures; ++i) C.captures = (sc->surfs[i].flags & TRC_SURF_CAPTURE_HITS) != 0;
+    if (C.captures) TRC_TRY(sc->hits.spectra_for(3 * C.lay.W, C.before.hit_cursor, &C.hit_x));
+    C.dirty_before = sc->hits.begin_call();      // (fast_finish says how far the hit buffer was used)
+    return sc->counters.restart_last(C.before);
+}
+
+// The megakernel's LDS budget.  Preferred (m32): k_trace_coop, the single-precision conservative search with everything it needs
+// in LDS, 512 threads or 256; else k_trace_fast with the tallies and the scene in LDS as far as they fit.
+struct MegaPlan {
+    bool m32;
+    int threads;
+    size_t lds;
+    int lds_tally, lds_scene;
+};
+static MegaPlan mega_plan(const FastCall &C) {
+    const trc_scene *sc = C.sc;
+    const int S = sc->n_surf;
+    const bool accel = sc->has_kd && (C.flags & TRC_TRACE_ACCEL);       // (without a Kd-tree the megakernel tests every box)
+    const size_t b_buie = C.src ? (size_t)TRC_BUIE_STAGED * 8 : 0;
+    const size_t b_tally = (size_t)(3 * S + 2) * 8;
+    MegaPlan M = {false, 256, 0, 0, 0};
+    if (sc->accel_ok && S <= 65535 && (!accel || (sc->accel_kd_ok && sc->kd_nodes <= COOP_MAX_NODES && sc->accel.kd_depth <= COOP_MAX_DEPTH))) {
+        const size_t b_acc = (size_t)6 * S * 4 + (accel ? ((size_t)2 * sc->kd_nodes * 4 + (size_t)sc->kd_nalways * 4 + (size_t)sc->kd_nleaf * 2)
+                                                        : (8 + sc->accel.brute_leaf.size() * 2)) +
+                             sc->accel.unbounded.size() * 4 + 32;
+        const size_t b_wave = COOP_WAVE_BYTES(accel ? (sc->accel.kd_depth > 0 ? sc->accel.kd_depth : 1) : 1);
+        for (int threads = 512; threads >= 256 && !M.m32; threads /= 2) {
+            const size_t lds = b_buie + b_tally + b_acc + (size_t)(threads / 64) * b_wave;
+            if (lds <= LDS_MAX_ALLOWED) M = {true, threads, lds, 1, 0};
+        }
+    }
+    if (!M.m32) {
+        size_t b_scene = (size_t)S * sc->stride * 8;
+        if (sc->has_kd) b_scene += (size_t)sc->kd_nodes * 8 + ((size_t)sc->kd_nodes * 2 + sc->kd_nleaf + sc->kd_nalways) * 4 + 8;
+        M.lds = b_buie;
+        M.lds_tally = (M.lds + b_tally <= LDS_MAX_PLAIN) ? 1 : 0;
+        if (M.lds_tally) M.lds += b_tally;
+        M.lds_scene = (M.lds + b_scene <= LDS_MAX_PLAIN) ? 1 : 0;
+        if (M.lds_scene) M.lds += b_scene;
+    }
+    return M;
+}
+
+static void fast_params(const FastCall &C, const MegaPlan &M, FastParams *P, CarryIn *carry_in) {
+    memset(P, 0, sizeof(*P));
+    P->sc = make_dscene(C.sc);
+    P->x = C.dr.x; P->y = C.dr.y; P->z = C.dr.z; P->dx = C.dr.dx; P->dy = C.dr.dy; P->dz = C.dr.dz; P->e = C.dr.e;
+    P->ref = C.dr.ref; P->wl = C.dr.wl; P->rid = C.dr.rid;
+    P->src = C.d_src;
+    P->spec = C.d_spec;
+    P->n = C.n; P->reps = C.reps; P->flags = C.flags; P->min_energy = C.min_energy; P->seed = C.seed; P->ray_offset = C.ray_offset;
+    P->lx = C.d_last[0]; P->ly = C.d_last[1]; P->lz = C.d_last[2]; P->ldx = C.d_last[3]; P->ldy = C.d_last[4]; P->ldz = C.d_last[5]; P->le = C.d_last[6];
+    P->last_cap = C.last_cap;
+    P->capture = C.captures ? 1 : 0;
+    P->lds_tally = M.lds_tally; P->lds_scene = M.lds_scene;
+    memset(carry_in, 0, sizeof(*carry_in));
+    carry_in->hit_x = C.hit_x; carry_in->hit_x_cap = C.hit_x ? C.sc->hits.cap : 0;
+    carry_in->ref_im = C.carry_d[0]; carry_in->mat = C.carry_d[1]; carry_in->spec_wl = C.carry_d[2]; carry_in->spec = C.carry_d[3];
+    carry_in->n_mat = C.lay.n_mat; carry_in->n_spec = C.lay.W;
+}
+
+// Large calls run the streaming engine (phases as separate kernels connected by HBM queues, trc_stream.inc); small ones the
+// persistent megakernel, which needs one launch and no workspace.  TRC_TRACE_STREAM / TRC_TRACE_MEGAKERNEL force one or the other.
+static int fast_choose_engine(const FastCall &C, StreamPlan *plan, bool *use_stream) {
+    *plan = {0, 0, true};
+    const bool stream_ok = C.n >= 64 && stream_plan(C.sc, (C.flags & TRC_TRACE_ACCEL) != 0, C.knobs, plan);
+    const bool force_stream = (C.flags & TRC_TRACE_STREAM) || C.carry;
+    const bool force_mega = !C.carry && (C.flags & TRC_TRACE_MEGAKERNEL);
+    // (a scene on the large grid -- a mesh of 1e5 faces -- has nothing but its boxes to search in the megakernel: 2e5 rays on the
+    // relief of 105 800 triangles took 570 ms there, 1.3 ms here)
+    const long long stream_from = plan->mode == 3 ? 4096 : TRC_STREAM_MIN_RAYS;
+    *use_stream = stream_ok && (force_stream || (!force_mega && C.n >= stream_from));
+    if (C.carry && !*use_stream) return trc_fail(TRC_ERR_UNSUPPORTED, "no streaming form for this scene: rays that carry complex indices or spectra go through trc_trace_ordered");
+    return TRC_OK;
+}
+
+// the megakernel's instances for a source with a spectrum (SPEC: they draw the wavelength) and a tabulated sunshape (SUN)
+struct MegaKernels { void (*coop512)(FastParams), (*coop256)(FastParams), (*fast256)(FastParams); };
+template <bool SPEC, bool SUN>
+static MegaKernels mega_kernels_of() { return {k_trace_coop<512, SPEC, SUN>, k_trace_coop<256, SPEC, SUN>, k_trace_fast<256, SPEC, SUN>}; }
+static MegaKernels mega_kernels(bool spec, bool sun) {
+    if (spec) return sun ? mega_kernels_of<true, true>() : mega_kernels_of<true, false>();
+    return sun ? mega_kernels_of<false, true>() : mega_kernels_of<false, false>();
+}
+
+static int mega_launch(FastCall &C, const MegaPlan &M, const FastParams &P) {
+    trc_scene *sc = C.sc;
+    trc_ctx *ctx = sc->ctx;
+    (void)hipStreamSynchronize(ctx->stream);       // (the sums of an earlier streaming call may still be on their way into the buffer)
+    if (hipMemcpy(C.tally_before, sc->d_tally.get() + 3 * sc->n_surf, sizeof(C.tally_before), hipMemcpyDeviceToHost) != hipSuccess)
+        return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
+    const MegaKernels K = mega_kernels(P.spec != nullptr, C.d_src && source_is_sunshape(C.src->kind));
+    void (*kern)(FastParams) = !M.m32 ? K.fast256 : (M.threads == 512 ? K.coop512 : K.coop256);
+    // persistent grid: as many workgroups as are resident at once (at most 8 per CU), never more waves than rays/64
+    unsigned resident = 0;
+    TRC_TRY(kernel_grid_cap((const void *)kern, M.threads, M.lds, 8, ctx->n_cu, &resident));
+    long long grid = resident;
+    const long long max_grid = (C.n + M.threads - 1) / M.threads;
+    if (grid > max_grid) grid = max_grid;
+    if (grid < 1) grid = 1;
+    if (C.n == 0) return TRC_OK;
+    if (hipEventRecord(ctx->ev0, ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "event record failed");
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(M.threads), M.lds, ctx->stream, P);
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_trace_fast launch failed: %s", hipGetErrorString(le));
+    if (hipEventRecord(ctx->ev1, ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "event record failed");
+    hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_trace_fast failed: %s", hipGetErrorString(se));
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+    C.s.kernel_ms = ms;
+    C.s.launches = 1;
+    return TRC_OK;
+}
+
+// the counters read back (one 64-byte copy), the stats of the call, the rays left
+static int fast_finish(FastCall &C) {
+    trc_scene *sc = C.sc;
+    trc_trace_stats &s = C.s;
+    CounterValues after = {};
+    TRC_TRY(sc->counters.read_back(&after));
+    sc->hits.end_call(C.dirty_before, after.hit_cursor);
+    if (C.stream_counts_known) {
+        s.segments = (int64_t)(C.stream_seg + 0.5);
+        s.hits = (int64_t)(C.stream_hits + 0.5);
+    } else {
+        double tally_after[2];
+        if (hipMemcpy(tally_after, sc->d_tally.get() + 3 * sc->n_surf, sizeof(tally_after), hipMemcpyDeviceToHost) != hipSuccess)
+            return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
+        s.segments = (int64_t)(tally_after[0] - C.tally_before[0] + 0.5);
+        s.hits = (int64_t)(tally_after[1] - C.tally_before[1] + 0.5);
+    }
+    s.rays_left = (int64_t)(after.rays_left - C.before.rays_left);
+    s.hits_dropped = (int64_t)(after.dropped - C.before.dropped);
+    s.energy_left = after.energy_left - C.before.energy_left;
+    s.bounces = C.reps;
+    if (C.flags & TRC_TRACE_KEEP_LAST) {
+        trc_rays *last = C.last;
+        const int64_t m = (int64_t)after.last_cursor;
+        if (m > C.last_cap) return trc_fail(TRC_ERR_CAPACITY, "%lld rays left but `last` holds %lld", (long long)m, (long long)C.last_cap);
+        double *dst[7] = {last->x, last->y, last->z, last->dx, last->dy, last->dz, last->e};
+        for (int i = 0; i < 7 && m > 0; ++i) TRC_TRY(dev_download(dst[i], C.d_last[i], (size_t)m));
+        last->n = m;
+    }
+    return TRC_OK;
+}
+
+// the steps of a call after its arguments have passed, in order
+static int fast_steps(FastCall &C) {
+    trc_scene *sc = C.sc;
+    TRC_TRY(fast_stage_inputs(C));
+    TRC_TRY(fast_stage_last(C));
+    TRC_TRY(fast_begin(C));
+    const MegaPlan M = mega_plan(C);
+    FastParams P;
+    CarryIn carry_in;
+    fast_params(C, M, &P, &carry_in);
+    StreamPlan plan;
+    bool use_stream = false;
+    TRC_TRY(fast_choose_engine(C, &plan, &use_stream));
+    if (use_stream) {
+        if (!sc->stream_eng) {
+            sc->stream_eng = new (std::nothrow) StreamEngine();      // (value-initialised: all zero)
+            if (!sc->stream_eng) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
+        }
+        if (int e = stream_trace(sc, P, carry_in, plan, C.knobs, C.src, *sc->stream_eng, &C.s, &C.stream_seg, &C.stream_hits)) {
+            sc->hits.rollback(sc->counters.device() + CNT_HIT_CURSOR, C.before.hit_cursor);     // (the hits captured by the bounces that completed)
+            return e;
+        }
+        C.stream_counts_known = true;
+    } else TRC_TRY(mega_launch(C, M, P));
+    return fast_finish(C);
+}
+
+static int trace_fast_impl(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, const SourceSpectrum &spec, int64_t n, int32_t reps,
+                           double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags, trc_rays *last,
+                           trc_trace_stats *stats) {
+    FastCall C = {sc, in, src, &spec, n, reps, min_energy, seed, ray_offset, flags, last};      // (the rest: zero, empty)
+    TRC_TRY(fast_check_args(C));
+    HIP_TRY(hipSetDevice(sc->ctx->device));
+    const int st = fast_steps(C);
+    if (stats) *stats = C.s;        // what the call gathered is handed back whatever its outcome
+    return st;
+}
+
+// ================================================================================================
+// ordered engine
 // ================================================================================================
 // One allocation per level (a trace of five levels used to cost 65 hipMalloc / hipFree pairs, 2 ms of a 1e5-ray call): eleven
 // 8-byte columns and the surface column, each starting on a 256-byte boundary, then the carried rows (n apart, as the kernels index them).
@@ -2922,10 +3049,172 @@ extern "C" int trc_result_destroy(trc_result *res) {
     return TRC_OK;
 }
 
-// spec / spec_tab: the spectrum of `src` and its packed table (spectrum_pack), NULL without one
-static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
-                              const std::vector<double> *spec_tab, int64_t n, int32_t reps, double min_energy, uint64_t seed,
-                              uint64_t ray_offset, int32_t flags, trc_result **out, trc_trace_stats *stats) {
+// One call: what its steps share
+struct OrdCall {
+    trc_scene *sc; trc_result *res; PayLayout lay; int32_t flags; double min_energy; uint64_t seed;
+    trc_trace_stats s;
+    float total_ms;
+};
+
+static void fill_f64(hipStream_t stream, long long grid, double *col, int64_t n, double v) {
+    hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)grid), dim3(256), 0, stream, col, (long long)n, v);
+}
+
+// Level 0: the source bundle, generated from `src` or copied from `in` into a slab that the result owns (it outlives the call)
+static int ordered_level0(OrdCall &C, const trc_rays *in, const trc_source_desc *src, const SourceSpectrum &spec, int64_t n, uint64_t ray_offset) {
+    trc_ctx *ctx = C.sc->ctx;
+    const PayLayout &lay = C.lay;
+    Level L0;
+    TRC_TRY(level_alloc(L0, n, lay.rows()));
+    C.res->levels.push_back(std::move(L0));
+    Level &B0 = C.res->levels.back();
+    long long g0 = (n + 255) / 256; if (g0 > 8192) g0 = 8192; if (g0 < 1) g0 = 1;
+    DevBuf<trc_source_desc> d_src;
+    if (src) {
+        TRC_TRY(upload_source(src, d_src));
+        hipLaunchKernelGGL(k_source_generate, dim3((unsigned)g0), dim3(256), 0, ctx->stream, d_src.get(), (long long)n,
+                           (unsigned long long)C.seed, (unsigned long long)ray_offset, B0.x, B0.y, B0.z, B0.dx, B0.dy, B0.dz, B0.e, B0.rid);
+        if (spec.desc) {     // level 0 carries the wavelengths the source's spectrum gives its rays, and their index
+            TRC_TRY(spectrum_fill(ctx, spec.desc, spec.tab, n, C.seed, ray_offset, B0.wl, B0.ref));
+        } else { fill_f64(ctx->stream, g0, B0.ref, n, 1.0); fill_f64(ctx->stream, g0, B0.wl, n, 0.0); }
+    } else {
+        TRC_TRY(check_rays(in, n, "trc_trace_ordered"));
+        if (!in->e) return trc_fail(TRC_ERR_INVALID, "ray energies are required");
+        const hipMemcpyKind kind = in->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+        struct { const void *src; void *dst; } col[10] = {{in->x, B0.x}, {in->y, B0.y}, {in->z, B0.z}, {in->dx, B0.dx}, {in->dy, B0.dy}, {in->dz, B0.dz}, {in->e, B0.e},
+                                                          {in->ref_index, B0.ref}, {in->wavelength, B0.wl}, {in->rid, B0.rid}};
+        for (auto &c : col)
+            if (c.src && n > 0 && hipMemcpy(c.dst, c.src, (size_t)n * 8, kind) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "bundle upload failed");
+        if (!in->ref_index) fill_f64(ctx->stream, g0, B0.ref, n, 1.0);
+        if (!in->wavelength) fill_f64(ctx->stream, g0, B0.wl, n, 0.0);
+        if (!in->rid) hipLaunchKernelGGL(k_fill_rid, dim3((unsigned)g0), dim3(256), 0, ctx->stream, B0.rid, (long long)n, (unsigned long long)ray_offset);
+        if (lay.rows() > 0 && n > 0) {
+            CarriedBlock blk[4];
+            carried_blocks(in, lay, blk);
+            const int row[4] = {0, lay.r_mat(), lay.r_wl(), lay.r_spec()};
+            for (int b = 0; b < 4; ++b)
+                if (blk[b].src) TRC_TRY(stage_carried(B0.pay + (size_t)row[b] * n, blk[b].src, blk[b].rows, n, in));
+            if (lay.has_im && !in->ref_index_im && hipMemset(B0.pay, 0, (size_t)n * 8) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "bundle upload failed");
+        }
+    }
+    if (n > 0) {
+        (void)hipMemsetAsync(B0.parent, 0, (size_t)n * 8, ctx->stream);
+        (void)hipMemsetAsync(B0.surf, 0xFF, (size_t)n * 4, ctx->stream);
+    }
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "level 0 setup failed");
+    return TRC_OK;
+}
+
+// the search of k_ord_bounce: 2 the large grid (the scene stands on it and the caller brought no tree), 1 the single-precision
+// conservative search, 0 the generic one
+static int ordered_search_mode(const trc_scene *sc, int32_t flags) {
+    const bool use_kd = sc->has_kd && (flags & TRC_TRACE_ACCEL);
+    if (sc->accel_ok && sc->accel.big_ok && !use_kd) return 2;
+    return (sc->accel_ok && sc->n_surf <= 65535 && (!use_kd || (sc->accel_kd_ok && sc->accel.kd_depth + 2 <= ORD_STACK_DEPTH))) ? 1 : 0;
+}
+
+// Bounce `it` of the n_cur live rays of the last level into the 2 n_cur slots of the scratch: *m of them occupied (the rays of
+// the next level), *n_culled of those below the energy threshold
+static int ordered_bounce(OrdCall &C, int it, int64_t n_cur, int64_t *m, int64_t *n_culled) {
+    trc_scene *sc = C.sc;
+    trc_ctx *ctx = sc->ctx;
+    OrdScratch &sx = *sc->ord_scratch;
+    const Level &cur = C.res->levels.back();
+    const int64_t slots = 2 * n_cur;
+    TRC_TRY(sx.ensure((size_t)slots, C.lay.rows()));
+    const long long nblk = (slots + 255) / 256;
+
+    OrdParams P;
+    memset(&P, 0, sizeof(P));
+    P.sc = make_dscene(sc);
+    P.x = cur.x; P.y = cur.y; P.z = cur.z; P.dx = cur.dx; P.dy = cur.dy; P.dz = cur.dz; P.e = cur.e;
+    P.ref = cur.ref; P.wl = cur.wl; P.rid = cur.rid;
+    P.n = n_cur; P.event = it + 1; P.flags = C.flags; P.min_energy = C.min_energy; P.seed = C.seed;
+    P.ox = sx.o[0].get(); P.oy = sx.o[1].get(); P.oz = sx.o[2].get(); P.odx = sx.o[3].get(); P.ody = sx.o[4].get(); P.odz = sx.o[5].get();
+    P.oe = sx.o[6].get(); P.oref = sx.o[7].get(); P.owl = sx.o[8].get(); P.orid = sx.orid.get(); P.key = sx.key.get();
+    P.pay = cur.pay; P.pay_stride = cur.n_total; P.opay = sx.opay.get(); P.lay = C.lay;
+
+    (void)hipEventRecord(ctx->ev0, ctx->stream);
+    const int mode = ordered_search_mode(sc, C.flags);
+    void (*kern)(OrdParams) = mode == 2 ? k_ord_bounce<2> : (mode == 1 ? k_ord_bounce<1> : k_ord_bounce<0>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((n_cur + 255) / 256)), dim3(256), 0, ctx->stream, P);
+    hipLaunchKernelGGL(k_compact_count, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, sx.key.get(), (long long)slots,
+                       sx.blk_cnt.get(), sx.blk_cul.get());
+    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, ctx->stream, sx.blk_cnt.get(), sx.blk_cul.get(), nblk, sx.blk_off.get(),
+                       sx.totals.get());
+    (void)hipEventRecord(ctx->ev1, ctx->stream);
+    unsigned long long totals[2];
+    hipError_t ce = hipMemcpyAsync(totals, sx.totals.get(), sizeof(totals), hipMemcpyDeviceToHost, ctx->stream);
+    hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (ce != hipSuccess || se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "bounce %d failed: %s", it, hipGetErrorString(se != hipSuccess ? se : ce));
+    float ms = 0; (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); C.total_ms += ms;
+    C.s.launches += 3;
+    C.s.segments += n_cur;
+    C.s.bounces = it + 1;
+    *m = (int64_t)totals[0]; *n_culled = (int64_t)totals[1];
+    return TRC_OK;
+}
+
+// The next level from the m occupied slots of bounce `it`: compacted in slot order, sorted, gathered into a slab of its own
+static int ordered_next_level(OrdCall &C, int it, int64_t n_cur, int64_t m, int64_t n_culled) {
+    trc_scene *sc = C.sc;
+    trc_ctx *ctx = sc->ctx;
+    OrdScratch &sx = *sc->ord_scratch;
+    const int64_t slots = 2 * n_cur;
+    hipLaunchKernelGGL(k_compact_scatter, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, ctx->stream, sx.key.get(), (long long)slots,
+                       sx.blk_off.get(), sx.ckey.get(), sx.cslot.get());
+    // stable sort by (culled, surface, block); slot order (= parent order) is kept inside a key
+    size_t tmp_bytes = 0;
+    hipError_t re = rocprim::radix_sort_pairs(nullptr, tmp_bytes, sx.ckey.get(), sx.skey.get(), sx.cslot.get(), sx.sslot.get(), (size_t)m, 0, 31, ctx->stream);
+    if (re != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "radix_sort_pairs(size query) failed: %s", hipGetErrorString(re));
+    TRC_TRY(sx.ensure_sort(tmp_bytes));
+    re = rocprim::radix_sort_pairs(sx.sort_tmp.get(), tmp_bytes, sx.ckey.get(), sx.skey.get(), sx.cslot.get(), sx.sslot.get(), (size_t)m, 0, 31, ctx->stream);
+    if (re != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "radix_sort_pairs failed: %s", hipGetErrorString(re));
+    Level next;
+    TRC_TRY(level_alloc(next, m, C.lay.rows()));
+    next.n_live = m - n_culled;
+    C.res->levels.push_back(std::move(next));
+    const Level &Ln = C.res->levels.back();
+    GatherParams G;
+    G.ox = sx.o[0].get(); G.oy = sx.o[1].get(); G.oz = sx.o[2].get(); G.odx = sx.o[3].get(); G.ody = sx.o[4].get(); G.odz = sx.o[5].get();
+    G.oe = sx.o[6].get(); G.oref = sx.o[7].get(); G.owl = sx.o[8].get(); G.orid = sx.orid.get(); G.skey = sx.skey.get(); G.sslot = sx.sslot.get();
+    G.m = m; G.n_parent = n_cur;
+    G.x = Ln.x; G.y = Ln.y; G.z = Ln.z; G.dx = Ln.dx; G.dy = Ln.dy; G.dz = Ln.dz; G.e = Ln.e; G.ref = Ln.ref;
+    G.wl = Ln.wl; G.rid = Ln.rid; G.parent = Ln.parent; G.surf = Ln.surf;
+    G.recs = sc->d_recs.get(); G.stride = sc->stride;
+    G.opay = sx.opay.get(); G.pay = Ln.pay; G.n_pay = C.lay.rows();
+    hipLaunchKernelGGL(k_ord_gather, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, G);
+    const hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "ordering of bounce %d failed: %s", it, hipGetErrorString(se));
+    C.s.launches += 3;
+    C.s.hits += m;
+    return TRC_OK;
+}
+
+// level 0, then a level per bounce until none is left or the bundle is depleted
+static int ordered_steps(OrdCall &C, const trc_rays *in, const trc_source_desc *src, const SourceSpectrum &spec, int64_t n, int32_t reps, uint64_t ray_offset) {
+    TRC_TRY(ordered_level0(C, in, src, spec, n, ray_offset));
+    int64_t n_cur = n;
+    for (int it = 0; it < reps && n_cur > 0; ++it) {
+        int64_t m = 0, n_culled = 0;
+        TRC_TRY(ordered_bounce(C, it, n_cur, &m, &n_culled));
+        if (m == 0) { n_cur = 0; break; }   // "Ray bundle depleted": nothing recorded (tracer_engine.py:271, :277)
+        TRC_TRY(ordered_next_level(C, it, n_cur, m, n_culled));
+        n_cur = m - n_culled;
+    }
+    C.s.rays_left = n_cur;
+    C.s.kernel_ms = C.total_ms;
+    if (n_cur > 0) {
+        // energy of the live part of the last level
+        std::vector<double> eh((size_t)n_cur);
+        if (hipMemcpy(eh.data(), C.res->levels.back().e, (size_t)n_cur * 8, hipMemcpyDeviceToHost) == hipSuccess)
+            for (double v : eh) C.s.energy_left += v;
+    }
+    return TRC_OK;
+}
+
+static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, const SourceSpectrum &spec, int64_t n, int32_t reps,
+                              double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags, trc_result **out, trc_trace_stats *stats) {
     if (!sc || !out) return trc_fail(TRC_ERR_INVALID, "trc_trace_ordered: bad arguments");
     *out = nullptr;
     if ((in == nullptr) == (src == nullptr)) return trc_fail(TRC_ERR_INVALID, "exactly one of `in` and `src` must be given");
@@ -2935,181 +3224,58 @@ static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_sourc
     if (2 * n >= (int64_t)0xFFFFFFFFll) return trc_fail(TRC_ERR_UNSUPPORTED, "ordered engine handles fewer than 2^31 rays per call");
     if ((flags & TRC_TRACE_ACCEL) && !sc->has_kd) return trc_fail(TRC_ERR_INVALID, "TRC_TRACE_ACCEL without a Kd-tree on the scene");
     if (sc->n_surf >= (1 << 28)) return trc_fail(TRC_ERR_UNSUPPORTED, "too many surfaces for the ordering key");
-    trc_ctx *ctx = sc->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    // what the rays carry beyond the nine columns (complex indices, material rows, spectra)
+    HIP_TRY(hipSetDevice(sc->ctx->device));
+    // what the rays carry beyond the nine columns (complex indices, material rows, spectra); rays between materials carry Im of the
+    // index whether the bundle brought it or not
     PayLayout lay;
-    {
-        int max_mat = -1;
-        bool poly = false;
-        for (const auto &sd : sc->surfs) {
-            if (sd.optics_kind == TRC_OPT_REFRACTIVE_MATERIAL) max_mat = std::max(max_mat, std::max((int)sd.opt[4], (int)sd.opt[5]));
-            if (sd.optics_kind == TRC_OPT_LAMBERTIAN_POLYCHROMATIC) poly = true;
-        }
-        if (in) {
-            lay.has_im = (in->ref_index_im != nullptr || max_mat >= 0) ? 1 : 0;
-            lay.n_mat = in->mat ? (int)in->n_mat : 0;
-            lay.W = (in->spectra && in->spec_wl) ? in->n_spec : 0;
-        }
-        if (max_mat >= 0 && (!in || !in->wavelength || lay.n_mat <= max_mat))
-            return trc_fail(TRC_ERR_INVALID, "the scene refracts between tabulated materials: the bundle needs wavelengths and the %d materials' indices at them (trc_rays.mat)", max_mat + 1);
-        if (poly && lay.W < 2)
-            return trc_fail(TRC_ERR_INVALID, "the scene has polychromatic optics: the bundle needs spectra (trc_rays.spectra, spec_wl)");
-        if (lay.W < 0 || lay.W > 4096 || lay.n_mat < 0 || lay.n_mat > 64) return trc_fail(TRC_ERR_INVALID, "trc_trace_ordered: n_spec or n_mat out of range");
-    }
-    const int n_pay = lay.rows();
+    TRC_TRY(check_carried(sc->needs, in, "trc_trace_ordered", &lay));
+    lay.has_im = ((in && in->ref_index_im) || sc->needs.max_mat >= 0) ? 1 : 0;
     std::unique_ptr<trc_result> res(new (std::nothrow) trc_result());
     if (!res) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
-    res->ctx = ctx;
+    res->ctx = sc->ctx;
     res->lay = lay;
-    trc_trace_stats s;
-    memset(&s, 0, sizeof(s));
     // the scratch of the bounce loop stays with the scene (an ordered trace of 1e7 rays allocated and freed 3 GB in twenty blocks
     // beyond the pool's sizes per call: 30 of its 45 ms)
     if (!sc->ord_scratch) { sc->ord_scratch.reset(new (std::nothrow) OrdScratch()); if (!sc->ord_scratch) return trc_fail(TRC_ERR_NOMEM, "out of host memory"); }
-    OrdScratch &sx = *sc->ord_scratch;
-    // the call's work; the stats it gathered are handed back whatever its outcome
-    const int st = [&]() -> int {
-        DevBuf<trc_source_desc> d_src;
-        float total_ms = 0;
-        // ---- level 0: the source bundle ----
-        Level L0;
-        TRC_TRY(level_alloc(L0, n, n_pay));
-        res->levels.push_back(std::move(L0));
-        Level &B0 = res->levels.back();
-        long long g0 = (n + 255) / 256; if (g0 > 8192) g0 = 8192; if (g0 < 1) g0 = 1;
-        if (src) {
-            TRC_TRY(upload_source(src, d_src));
-            hipLaunchKernelGGL(k_source_generate, dim3((unsigned)g0), dim3(256), 0, ctx->stream, d_src.get(), (long long)n,
-                               (unsigned long long)seed, (unsigned long long)ray_offset, B0.x, B0.y, B0.z, B0.dx, B0.dy,
-                               B0.dz, B0.e, B0.rid);
-            if (spec) {     // level 0 carries the wavelengths the source's spectrum gives its rays, and their index
-                TRC_TRY(spectrum_fill(ctx, spec, *spec_tab, n, seed, ray_offset, B0.wl, B0.ref));
-            } else {
-                hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)g0), dim3(256), 0, ctx->stream, B0.ref, (long long)n, 1.0);
-                hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)g0), dim3(256), 0, ctx->stream, B0.wl, (long long)n, 0.0);
-            }
-        } else {
-            TRC_TRY(check_rays(in, n, "trc_trace_ordered"));
-            if (!in->e) return trc_fail(TRC_ERR_INVALID, "ray energies are required");
-            hipMemcpyKind kind = in->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-            const double *hs[7] = {in->x, in->y, in->z, in->dx, in->dy, in->dz, in->e};
-            double *ds[7] = {B0.x, B0.y, B0.z, B0.dx, B0.dy, B0.dz, B0.e};
-            bool bad = false;
-            for (int i = 0; i < 7 && n > 0; ++i) if (hipMemcpy(ds[i], hs[i], (size_t)n * 8, kind) != hipSuccess) bad = true;
-            if (in->ref_index) { if (n > 0 && hipMemcpy(B0.ref, in->ref_index, (size_t)n * 8, kind) != hipSuccess) bad = true; }
-            else hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)g0), dim3(256), 0, ctx->stream, B0.ref, (long long)n, 1.0);
-            if (in->wavelength) { if (n > 0 && hipMemcpy(B0.wl, in->wavelength, (size_t)n * 8, kind) != hipSuccess) bad = true; }
-            else hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)g0), dim3(256), 0, ctx->stream, B0.wl, (long long)n, 0.0);
-            if (in->rid) { if (n > 0 && hipMemcpy(B0.rid, in->rid, (size_t)n * 8, kind) != hipSuccess) bad = true; }
-            else hipLaunchKernelGGL(k_fill_rid, dim3((unsigned)g0), dim3(256), 0, ctx->stream, B0.rid, (long long)n, (unsigned long long)ray_offset);
-            if (n_pay > 0 && n > 0) {       // rows of the caller's 2-D columns are in->n apart, ours n
-                if (lay.has_im) {
-                    if (in->ref_index_im) { if (hipMemcpy(B0.pay, in->ref_index_im, (size_t)n * 8, kind) != hipSuccess) bad = true; }
-                    else if (hipMemset(B0.pay, 0, (size_t)n * 8) != hipSuccess) bad = true;
-                }
-                struct { const double *src; int rows, r0; } blk[3] = {{in->mat, 2 * lay.n_mat, lay.r_mat()}, {in->spec_wl, lay.W, lay.r_wl()},
-                                                                      {in->spectra, lay.W, lay.r_spec()}};
-                for (auto &b : blk)
-                    if (b.rows > 0 && hipMemcpy2D(B0.pay + (size_t)b.r0 * n, (size_t)n * 8, b.src, (size_t)in->n * 8, (size_t)n * 8, (size_t)b.rows, kind) != hipSuccess)
-                        bad = true;
-            }
-            if (bad) return trc_fail(TRC_ERR_DEVICE, "bundle upload failed");
-        }
-        if (n > 0) {
-            (void)hipMemsetAsync(B0.parent, 0, (size_t)n * 8, ctx->stream);
-            (void)hipMemsetAsync(B0.surf, 0xFF, (size_t)n * 4, ctx->stream);
-        }
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "level 0 setup failed");
-
-        // ---- bounce loop ----
-        int64_t n_cur = n;
-        for (int it = 0; it < reps && n_cur > 0; ++it) {
-            const Level &cur = res->levels.back();
-            const int64_t slots = 2 * n_cur;
-            TRC_TRY(sx.ensure((size_t)slots, n_pay));
-            const long long nblk = (slots + 255) / 256;
-
-            OrdParams P;
-            memset(&P, 0, sizeof(P));
-            P.sc = make_dscene(sc);
-            P.x = cur.x; P.y = cur.y; P.z = cur.z; P.dx = cur.dx; P.dy = cur.dy; P.dz = cur.dz; P.e = cur.e;
-            P.ref = cur.ref; P.wl = cur.wl; P.rid = cur.rid;
-            P.n = n_cur; P.event = it + 1; P.flags = flags; P.min_energy = min_energy; P.seed = seed;
-            P.ox = sx.o[0].get(); P.oy = sx.o[1].get(); P.oz = sx.o[2].get(); P.odx = sx.o[3].get(); P.ody = sx.o[4].get(); P.odz = sx.o[5].get();
-            P.oe = sx.o[6].get(); P.oref = sx.o[7].get(); P.owl = sx.o[8].get(); P.orid = sx.orid.get(); P.key = sx.key.get();
-            P.pay = cur.pay; P.pay_stride = cur.n_total; P.opay = sx.opay.get(); P.lay = lay;
-
-            (void)hipEventRecord(ctx->ev0, ctx->stream);
-            {
-                const bool use_kd = sc->has_kd && (flags & TRC_TRACE_ACCEL);
-                const bool fast = sc->accel_ok && sc->n_surf <= 65535 && (!use_kd || (sc->accel_kd_ok && sc->accel.kd_depth + 2 <= ORD_STACK_DEPTH));
-                const bool big = sc->accel_ok && sc->accel.big_ok && !use_kd;      // the scene stands on the large grid (and the caller brought no tree)
-                if (big) hipLaunchKernelGGL(k_ord_bounce<2>, dim3((unsigned)((n_cur + 255) / 256)), dim3(256), 0, ctx->stream, P);
-                else if (fast) hipLaunchKernelGGL(k_ord_bounce<1>, dim3((unsigned)((n_cur + 255) / 256)), dim3(256), 0, ctx->stream, P);
-                else hipLaunchKernelGGL(k_ord_bounce<0>, dim3((unsigned)((n_cur + 255) / 256)), dim3(256), 0, ctx->stream, P);
-            }
-            hipLaunchKernelGGL(k_compact_count, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, sx.key.get(), (long long)slots,
-                               sx.blk_cnt.get(), sx.blk_cul.get());
-            hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, ctx->stream, sx.blk_cnt.get(), sx.blk_cul.get(), nblk, sx.blk_off.get(),
-                               sx.totals.get());
-            (void)hipEventRecord(ctx->ev1, ctx->stream);
-            unsigned long long totals[2];
-            hipError_t ce = hipMemcpyAsync(totals, sx.totals.get(), sizeof(totals), hipMemcpyDeviceToHost, ctx->stream);
-            hipError_t se = hipStreamSynchronize(ctx->stream);
-            if (ce != hipSuccess || se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "bounce %d failed: %s", it, hipGetErrorString(se != hipSuccess ? se : ce));
-            float ms = 0; (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); total_ms += ms;
-            s.launches += 3;
-            s.segments += n_cur;
-            s.bounces = it + 1;
-            const int64_t m = (int64_t)totals[0], n_culled = (int64_t)totals[1];
-            // hits = rays that produced at least one child: count child-0 slots == slots < n_cur occupied; cheap bound: m minus second children
-            if (m == 0) { n_cur = 0; break; }   // "Ray bundle depleted": nothing recorded (tracer_engine.py:271, :277)
-            hipLaunchKernelGGL(k_compact_scatter, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, sx.key.get(), (long long)slots,
-                               sx.blk_off.get(), sx.ckey.get(), sx.cslot.get());
-            // stable sort by (culled, surface, block); slot order (= parent order) is kept inside a key
-            size_t tmp_bytes = 0;
-            hipError_t re = rocprim::radix_sort_pairs(nullptr, tmp_bytes, sx.ckey.get(), sx.skey.get(), sx.cslot.get(), sx.sslot.get(), (size_t)m, 0, 31, ctx->stream);
-            if (re != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "radix_sort_pairs(size query) failed: %s", hipGetErrorString(re));
-            TRC_TRY(sx.ensure_sort(tmp_bytes));
-            re = rocprim::radix_sort_pairs(sx.sort_tmp.get(), tmp_bytes, sx.ckey.get(), sx.skey.get(), sx.cslot.get(), sx.sslot.get(), (size_t)m, 0, 31, ctx->stream);
-            if (re != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "radix_sort_pairs failed: %s", hipGetErrorString(re));
-            Level next;
-            TRC_TRY(level_alloc(next, m, n_pay));
-            next.n_live = m - n_culled;
-            res->levels.push_back(std::move(next));
-            const Level &Ln = res->levels.back();
-            GatherParams G;
-            G.ox = sx.o[0].get(); G.oy = sx.o[1].get(); G.oz = sx.o[2].get(); G.odx = sx.o[3].get(); G.ody = sx.o[4].get(); G.odz = sx.o[5].get();
-            G.oe = sx.o[6].get(); G.oref = sx.o[7].get(); G.owl = sx.o[8].get(); G.orid = sx.orid.get(); G.skey = sx.skey.get(); G.sslot = sx.sslot.get();
-            G.m = m; G.n_parent = n_cur;
-            G.x = Ln.x; G.y = Ln.y; G.z = Ln.z; G.dx = Ln.dx; G.dy = Ln.dy; G.dz = Ln.dz; G.e = Ln.e; G.ref = Ln.ref;
-            G.wl = Ln.wl; G.rid = Ln.rid; G.parent = Ln.parent; G.surf = Ln.surf;
-            G.recs = sc->d_recs.get(); G.stride = sc->stride;
-            G.opay = sx.opay.get(); G.pay = Ln.pay; G.n_pay = n_pay;
-            hipLaunchKernelGGL(k_ord_gather, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, G);
-            se = hipStreamSynchronize(ctx->stream);
-            if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "ordering of bounce %d failed: %s", it, hipGetErrorString(se));
-            s.launches += 3;
-            s.hits += m;
-            n_cur = Ln.n_live;
-        }
-        s.rays_left = n_cur;
-        s.kernel_ms = total_ms;
-        if (n_cur > 0) {
-            // energy of the live part of the last level
-            const Level &LL = res->levels.back();
-            std::vector<double> eh((size_t)n_cur);
-            if (hipMemcpy(eh.data(), LL.e, (size_t)n_cur * 8, hipMemcpyDeviceToHost) == hipSuccess)
-                for (double v : eh) s.energy_left += v;
-        }
-        return TRC_OK;
-    }();
-    if (sx.cap_slots > ORD_SCRATCH_KEEP) sx = OrdScratch();      // (beyond 2^26 slots -- 10 GB -- the scratch goes back after the call)
-    if (stats) *stats = s;
+    OrdCall C = {sc, res.get(), lay, flags, min_energy, seed};      // (stats and time: zero)
+    const int st = ordered_steps(C, in, src, spec, n, reps, ray_offset);
+    if (sc->ord_scratch->cap_slots > ORD_SCRATCH_KEEP) *sc->ord_scratch = OrdScratch();      // (beyond 2^26 slots -- 10 GB -- the scratch goes back after the call)
+    if (stats) *stats = C.s;        // what the call gathered is handed back whatever its outcome
     if (st != TRC_OK) return st;
     *out = res.release();
     return TRC_OK;
+}
+
+// ================================================================================================
+// C-ABI: the trace entry points
+// ================================================================================================
+extern "C" int trc_trace_fast_x(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
+                                int64_t n, int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags,
+                                trc_rays *last, trc_trace_stats *stats) {
+    SourceSpectrum sp;
+    TRC_TRY(source_spectrum_make(spec, in, src, "trc_trace_fast_x", &sp));
+    return trace_fast_impl(sc, in, src, sp, n, reps, min_energy, seed, ray_offset, flags, last, stats);
+}
+
+extern "C" int trc_trace_fast(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, int64_t n, int32_t reps,
+                              double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags, trc_rays *last,
+                              trc_trace_stats *stats) {
+    return trc_trace_fast_x(sc, in, src, nullptr, n, reps, min_energy, seed, ray_offset, flags, last, stats);
+}
+
+extern "C" int trc_trace_ordered_x(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
+                                   int64_t n, int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags,
+                                   trc_result **out, trc_trace_stats *stats) {
+    if (out) *out = nullptr;
+    SourceSpectrum sp;
+    TRC_TRY(source_spectrum_make(spec, in, src, "trc_trace_ordered_x", &sp));
+    return trace_ordered_impl(sc, in, src, sp, n, reps, min_energy, seed, ray_offset, flags, out, stats);
+}
+
+extern "C" int trc_trace_ordered(trc_scene *sc, const trc_rays *in, const trc_source_desc *src, int64_t n, int32_t reps,
+                                 double min_energy, uint64_t seed, uint64_t ray_offset, int32_t flags, trc_result **out,
+                                 trc_trace_stats *stats) {
+    return trc_trace_ordered_x(sc, in, src, nullptr, n, reps, min_energy, seed, ray_offset, flags, out, stats);
 }
 
 extern "C" int trc_result_num_levels(trc_result *res, int32_t *n_levels) {

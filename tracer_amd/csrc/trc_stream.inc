@@ -2118,7 +2118,7 @@ static bool stream_plan(const trc_scene *sc, bool want_accel, const StreamKnobs 
                        : (mode == 1 ? ((size_t)2 * sc->kd_nodes * 4 + (size_t)sc->kd_nleaf * 2) : (8 + sc->accel.brute_leaf.size() * 2))) + 32;
         return shared + (size_t)(SW_THREADS / 64) * SW_WAVE_BYTES(depth);
     };
-    const size_t lds_max = 160 * 1024 - 512;
+    const size_t lds_max = LDS_MAX_ALLOWED;
     int mode = 0;
     if (want_accel) {
         // the uniform grid of trc_bounds.h; TRC_STREAM_SEARCH=1 walks the caller's Kd-tree instead (when its walk kernel fits)
@@ -2454,7 +2454,7 @@ static int stream_form_fresh(StreamForms &F, StreamParams &SP0, trc_scene *sc, S
                         : src_kind == TRC_SRC_SUNSHAPE_RECT ? (const void *)k_s_cull<TRC_SRC_SUNSHAPE_RECT>
                         : src_kind == TRC_SRC_PILLBOX_DISK ? (const void *)k_s_cull<TRC_SRC_PILLBOX_DISK> : (const void *)k_s_cull<TRC_SRC_PILLBOX_RECT>;
     const size_t lds_cull = (size_t)SP0.fp.P.M * SP0.fp.P.M / 8 + (SC_GEN_CAP + 4) * 4;
-    if (lds_cull > 160 * 1024 - 512 || lds_fresh > 160 * 1024 - 512) { F.use_fp = false; return TRC_OK; }
+    if (lds_cull > LDS_MAX_ALLOWED || lds_fresh > LDS_MAX_ALLOWED) { F.use_fp = false; return TRC_OK; }
     F.fresh = {fresh_fn, sf_threads, lds_fresh, 0u};
     F.fresh_one = {fresh1_fn, sf_threads, lds_fresh, 0u};
     F.cull = {cull_fn, SC_THREADS, lds_cull, 0u};
@@ -2920,7 +2920,7 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, c
     }
     // rays that carry more than the fast engine's record -- Im of a complex index, materials at their wavelength, a spectrum -- are
     // shaded by k_s_shade_x; the spectra of the rays under way live in a table of their own beside the ray table
-    const bool carry = sc->carries || carry_in.ref_im || carry_in.mat || carry_in.spec;
+    const bool carry = sc->needs.any() || carry_in.ref_im || carry_in.mat || carry_in.spec;
     StreamForms F;
     StreamCall C{F, K, E, StreamParams(), cap, 0.0, 0.0, {0.0, 0.0, 0.0}, 0, 0};
     memset(&C.SP0, 0, sizeof(C.SP0));
