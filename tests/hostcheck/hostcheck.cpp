@@ -438,4 +438,10 @@ int hc_hg_theta(double g, long n, const double *Rv, double *theta) {
     return 0;
 }
 
+// flux-map bin of every x[i] on edges[nbins + 1] (trc_bin_index, O8), -1: outside the map
+int hc_bin_index(const double *edges, int nbins, const double *x, long n, int *out) {
+    for (long i = 0; i < n; ++i) out[i] = trc_bin_index(edges, nbins, x[i]);
+    return 0;
+}
+
 }  // extern "C"

@@ -624,3 +624,41 @@ def test_core_henyey_greenstein_vs_reference(hc):
         th = N.empty_like(R)
         hc.hc_hg_theta(C.c_double(float(gv)), C.c_long(len(R)), _p(R), _p(th))
         assert N.allclose(th, g['hg%d_theta' % k], rtol=0., atol=1e-12), gv
+
+
+def test_core_bin_index_vs_numpy(hc):
+    """
+    trc_bin_index (trc_core.h, O8) -- the binary search behind every flux-map bin, on the device and here -- against numpy's rule
+    for explicit edges: bins are half open, the right edge of the last one is closed, values outside and nan fall in no bin.  The
+    reference is searchsorted(edges, x, 'right') - 1 with those two rules applied, and the bin counts are compared with one
+    numpy.histogram call per edge set as well.  Uniform, geometric, one, two and 1 000 003 bins, negative and mixed-sign edges; x is every
+    edge, its two neighbours in float64, +-inf, nan and 1e5 random values.  Equality is exact.
+    """
+    rng = N.random.RandomState(8)
+    sets = {'uniform': N.linspace(-1.5, 2.5, 51),
+            'geometric': 1e-3 * 1.37 ** N.arange(40),
+            'one bin': N.array([0.25, 0.75]),
+            'two bins': N.array([-1., 0.5, 3.]),
+            '1000003 bins': N.linspace(-7., 11., 1000004),
+            'negative': -N.geomspace(5e3, 2e-4, 34),
+            'mixed signs': N.r_[-N.geomspace(40., 1e-3, 12), 0., N.geomspace(2e-3, 90., 17)]}
+    for name, edges in sets.items():
+        edges = N.ascontiguousarray(edges, dtype=float)
+        nb = len(edges) - 1
+        assert (N.diff(edges) > 0).all(), name
+        span = edges[-1] - edges[0]
+        x = N.r_[edges, N.nextafter(edges, -N.inf), N.nextafter(edges, N.inf), N.inf, -N.inf, N.nan,
+                 rng.uniform(edges[0] - 0.1 * span, edges[-1] + 0.1 * span, 100000)]
+        got = N.empty(len(x), dtype=N.int32)
+        hc.hc_bin_index(_p(edges), C.c_int(nb), _p(x), C.c_long(len(x)), _p(got, C.c_int))
+        want = N.searchsorted(edges, x, 'right') - 1
+        want[x == edges[-1]] = nb - 1                                       # the last bin is closed on the right
+        want[~((x >= edges[0]) & (x <= edges[-1]))] = -1                    # outside (nan included): no bin
+        bad = N.nonzero(got != want)[0]
+        assert len(bad) == 0, (name, x[bad[:5]], got[bad[:5]], want[bad[:5]])
+        # the edges themselves: edge i opens bin i, the last one closes bin nb - 1; one ulp outside the map is outside
+        assert N.array_equal(got[:nb + 1], N.r_[N.arange(nb), nb - 1]), name
+        assert got[nb + 1] == -1 and got[3 * nb + 2] == -1, name
+        counts = N.histogram(x[N.isfinite(x)], bins=edges)[0]
+        assert N.array_equal(N.bincount(got[got >= 0], minlength=nb), counts), name
+        assert (got >= 0).sum() > 0.5 * len(x) and (got < 0).sum() > 1000, name
