@@ -413,6 +413,71 @@ def test_list_overflows_are_reported_and_leave_no_trace(ctx):
         dev.close()
 
 
+def test_workspace_is_made_again_when_a_call_needs_more(ctx):
+    """
+    A slot's workspace is kept between calls and made again when a call needs more: a larger batch drops the queues, the class
+    lists and the private tally copies; another flux map changes the length of the tally buffer, so the private copies alone are
+    made again; a smaller batch reuses what is there.  One scene of the mixed-class cavity (mirror, diffuse and general surfaces:
+    k_s_partition and the class lists run) goes through these steps, and after every call its tallies, flux maps and captured
+    hits are those of a fresh scene traced with the same bundle and seed.  The scene is closed and made again at the end.
+    (65 536 and 262 144 rays are one batch each, in one slot whatever TRC_STREAM_SLOTS says: a call is split from 2^23 rays on.
+    The streams, events and pinned blocks of all four slots are made by the first call and go with the scene.)
+    """
+    import fluxmap_scene as fs
+    from tracer_amd.scene import compile_scene, DeviceScene
+    asm, objs, T = fs.cavity()
+    cs = compile_scene(asm)
+    edges = fs.map_edges('small')
+    small, large, seed = 65536, 262144, 11
+    capacity = 2 * large + 65536        # (1.1 captured hits per ray in this cavity)
+
+    def scene(maps):
+        dev = DeviceScene(cs, ctx)
+        for s in maps:
+            dev.set_fluxmap(s, *edges[s])
+        dev.set_hit_capacity(capacity)
+        return dev
+
+    def call(dev, n, maps):
+        st, _ = dev.trace_fast(fs.source(n, T, seed), 12, 1e-10, seed, accel=True, stream=True)
+        assert st.hits_dropped == 0
+        a, r, h = dev.get_tallies()
+        cap = dev.get_hits()
+        out = dict(a=a, r=r, h=h, seg=st.segments, hits=st.hits, fm=[dev.get_fluxmap(s) for s in maps],
+                   cap_n=N.bincount(cap['surf'], minlength=cs.n_surf), cap_e=N.bincount(cap['surf'], weights=cap['e_abs'], minlength=cs.n_surf))
+        dev.reset_tallies()             # (empties the hit buffer too)
+        return out
+
+    refs = {}
+
+    def check(got, n, maps, what):
+        if (n, maps) not in refs:
+            ref_dev = scene(maps)
+            refs[(n, maps)] = call(ref_dev, n, maps)
+            ref_dev.close()
+        ref = refs[(n, maps)]
+        assert N.array_equal(got['h'], ref['h']) and (got['seg'], got['hits']) == (ref['seg'], ref['hits']), what
+        assert ref['h'][[0, 1, 2, 3, 5]].min() > 0, what            # every shading class took hits
+        assert N.allclose(got['a'], ref['a'], rtol=1e-9, atol=1e-12) and N.allclose(got['r'], ref['r'], rtol=1e-9, atol=1e-12), what
+        for s, x, y in zip(maps, got['fm'], ref['fm']):
+            assert y.sum() > 0. and N.allclose(x, y, rtol=1e-9, atol=1e-12), (what, s)
+        assert N.array_equal(got['cap_n'], ref['cap_n']) and ref['cap_n'].sum() > 0, what
+        assert N.allclose(got['cap_e'], ref['cap_e'], rtol=1e-9, atol=1e-12), what
+
+    dev = scene((0,))
+    check(call(dev, small, (0,)), small, (0,), 'first call')
+    check(call(dev, large, (0,)), large, (0,), 'larger batch: queues and class lists made again')
+    with env(TRC_STREAM_SLOTS=4):
+        check(call(dev, large, (0,)), large, (0,), 'four slots asked for')
+    dev.set_fluxmap(2, *edges[2])
+    check(call(dev, large, (0, 2)), large, (0, 2), 'second flux map: private tally copies made again')
+    check(call(dev, small, (0, 2)), small, (0, 2), 'smaller batch: the larger workspace reused')
+    dev.close()
+    dev = scene((0, 2))
+    check(call(dev, small, (0, 2)), small, (0, 2), 'scene made again')
+    dev.close()
+
+
 def test_full_size_routes_agree(ctx):
     """
     configs[2] / configs[3] at their real size: 1e8 NSTTF source rays (two batches of 5e7 in flight) and the per-GPU share of

@@ -391,7 +391,7 @@ __device__ __forceinline__ bool fast_shade(const FastParams &P, const double *re
 // One ray of the table, split by use: what the search reads and updates is exactly one 64-byte sector, the rest
 // (needed by shading only) another 32 bytes.  A structure-of-arrays table costs one sector per *field* on the gathers
 // by slot of k_s_exact / k_s_shade (8x the useful bytes).
-// Slots are handed out densely, in the order in which rays turn out to have a candidate (a chunked counter, CN(8)): of the
+// Slots are handed out densely, in the order in which rays turn out to have a candidate (a chunked counter, CN(CW_SLOTS)): of the
 // 1e8 source rays of an NSTTF step 6.5e6 ever need a record, and a table indexed by ray number spread those over 6.4 GB --
 // every access of the later bounces a DRAM page of its own.  The ray's number in its batch travels in the record (idx).
 #define SQ_SKIP_SELF 0x80000000u    /* tail, high word: the ray cannot meet the (flat) surface it left again -- its exact test would
@@ -424,6 +424,29 @@ struct __attribute__((aligned(32))) SRayAux {
 // counters live 128 bytes apart: atomics on words of one cache line serialise in the same L2 bank
 #define CN(k) ((k) << 4)
 #define CN_WORDS (32 << 4)
+// the words of a slot's counter block (StreamWs::cnt[CN(word)]): lengths are entries reserved, unused tails of chunks included
+enum StreamCounter {
+    CW_Q1 = 0,            // walker queue
+    CW_Q3 = 1,            // candidate queue
+    CW_HIT_LIST = 2,      // hit list
+    CW_ACT_OUT = 3,       // next active list
+    CW_OVERFLOW = 4,      // overflow flag: 0 or a StreamOverflow
+    CW_ACT_IN = 5,        // entries of the active list coming in
+    CW_HITS = 6,          // hits (real count)
+    CW_ALIVE = 7,         // rays going on (real count)
+    CW_SLOTS = 8,         // slots of the ray table handed out
+    CW_GEN_LIST = 9,      // general-path list of k_s_cull
+    CW_FP_LIST = 10,      // footprint list of k_s_cull
+    CW_TERM_LIST = 11,    // hits on terminal surfaces (k_s_bounce -> k_s_absorb)
+    CW_TERM_HITS = 12,    // ... and their real count
+    CW_CLS_HITS = 13,     // + class: hits shaded per class (TRC_CLS_COUNT words)
+    CW_STATS = 16,        // first of the seven words of SW_STATS
+    CW_CLS_LIST = 24      // + class: entries of the class lists of k_s_partition (TRC_CLS_COUNT words)
+};
+enum StreamOverflow : unsigned long long {
+    CW_OVF_RETRY = 1,     // the candidate queue was too small: nothing of the bounce is committed, the host doubles it and runs the bounce again
+    CW_OVF_FAIL = 2       // a list overflowed: the call fails
+};
 
 struct StreamWs {
     long long cap;      // rays per batch
@@ -452,11 +475,7 @@ struct StreamWs {
     uint32_t *pl_slot[3], *pl_surf[3];
     double *pl_t[3];
     long long pl_room;
-    unsigned long long *cnt;   // CN(k): [0] Q1, [1] Q3, [2] hit list, [3] next active list, [4] overflow flag, [5] entries of the
-                               // active list coming in, [6] hits and [7] rays going on (real counts), [8] slots of the ray table
-                               // handed out, [9] general-path list and [10] footprint list of k_s_cull, [11] hits on terminal surfaces
-                               // (k_s_bounce -> k_s_absorb) and [12] their real count; [13..15] hits shaded per class; [16..22] SW_STATS;
-                               // [24..26] entries of the class lists of k_s_partition
+    unsigned long long *cnt;   // CN_WORDS counters, word k at cnt[CN(k)]: see StreamCounter
 };
 
 // the footprint map of the call's source on the device (trc_footprint.h)
@@ -476,7 +495,7 @@ struct StreamParams {
     unsigned hit_epoch;  // generation of the scene's hit buffer: open chunks of an older one are stale
     unsigned chunk_q1, chunk_q3;   // entries reserved per atomic in the walker / candidate queues of this launch
     long long q3_gen_chunk0;   // >= 0: k_s_gen<false> takes pre-assigned first chunks of Q3 from this chunk number on (behind k_s_walk's)
-    const uint32_t *gen_list;  // k_s_gen<true>: the rays to generate (numbers in the batch, CN(9) entries), null = all nb rays
+    const uint32_t *gen_list;  // k_s_gen<true>: the rays to generate (numbers in the batch, CN(CW_GEN_LIST) entries), null = all nb rays
     // A single counter word sustains ~88 returning atomics per microsecond, and the waves of a kernel run out of their chunks at
     // about the same time: 8192 waves fetching a second chunk are 0.1 ms.  So every list that a bounce fills gets ONE pre-assigned
     // chunk per appending wave, sized by the host for what the wave is expected to append (+ margin); the atomic is the rare path.
@@ -497,7 +516,7 @@ struct StreamParams {
                          // too -- an interpolation is a binary search, every step a dependent load
     int bounce_no;       // the bounce this launch belongs to (every ray of a launch is at the same bounce)
     int bg_occ_words;    // k_s_bounce<2>: the occupancy bits of the large grid staged in LDS (this many words), 0 = read from global memory
-    int split_terminal;  // k_s_bounce lists the hits on surfaces that end every ray (TRC_SURF_TERMINAL) apart, for k_s_absorb: CN(11),
+    int split_terminal;  // k_s_bounce lists the hits on surfaces that end every ray (TRC_SURF_TERMINAL) apart, for k_s_absorb: CN(CW_TERM_LIST),
                          // entries in the arrays of the walker queue, which is idle in a bounce that k_s_bounce serves
     unsigned chunk_thit; // ... one pre-assigned chunk per wave of k_s_bounce
     int search;          // candidate search: 0 all boxes (one leaf), 1 packed Kd-tree, 2 uniform grid
@@ -509,7 +528,7 @@ struct StreamParams {
     long long act_base0;       // first entry of the pre-assigned chunks of the active list that belong to this launch (the shading
                                // kernels of a bounce append to one list; wave w starts at act_base0 + w * chunk_act)
     unsigned chunk_hitbuf;     // entries of the scene's hit buffer a wave reserves per atomic (<= SQ_HIT_CHUNK; small buffers: less)
-    // the list a shading kernel walks: the bounce's hit list (counter CN(2)), or its class's part of it (k_s_partition, CN(24 + class))
+    // the list a shading kernel walks: the bounce's hit list (counter CN(CW_HIT_LIST)), or its class's part of it (k_s_partition, CN(CW_CLS_LIST + class))
     const uint32_t *hl_slot, *hl_surf;
     const double *hl_t;
     long long hl_room;

@@ -265,6 +265,26 @@ static int dev_download(T *dst, const T *src, size_t n) {
     return TRC_OK;
 }
 
+// Owner of a HIP handle that FREE releases -- a stream, an event, a pinned host block -- in the style of DevBuf.  own() takes a
+// handle this object made and releases with FREE; borrow() takes somebody else's, which is only forgotten.
+template <class H, auto FREE>
+class HipHandle {
+    H h_ = nullptr;
+    bool owned_ = false;
+public:
+    HipHandle() = default;
+    HipHandle(const HipHandle &) = delete;
+    HipHandle &operator=(const HipHandle &) = delete;
+    ~HipHandle() { reset(); }
+    void reset() { if (h_ && owned_) (void)FREE(h_); h_ = nullptr; owned_ = false; }
+    void own(H h) { reset(); h_ = h; owned_ = true; }
+    void borrow(H h) { reset(); h_ = h; }
+    H get() const { return h_; }
+};
+using StreamHandle = HipHandle<hipStream_t, hipStreamDestroy>;
+using EventHandle = HipHandle<hipEvent_t, hipEventDestroy>;
+using PinnedWords = HipHandle<unsigned long long *, hipHostFree>;
+
 // ================================================================================================
 // host-side objects
 // ================================================================================================
@@ -454,7 +474,7 @@ struct trc_scene {
     DevBuf<float> d_a_bg_ent;
     DevBuf<int32_t> d_a_bg_apart;
     DevBuf<int32_t> d_a_gapart;
-    struct StreamEngine *stream_eng;   // slots of the streaming fast engine (trc_stream.inc), allocated on first use
+    std::unique_ptr<struct StreamEngine> stream_eng;   // slots of the streaming fast engine (trc_stream.inc), allocated on first use
     std::unique_ptr<struct OrdScratch> ord_scratch;    // scratch of the ordered engine's bounce loop, kept between calls
     DevBuf<double> d_tally;
     int64_t tally_n;
@@ -1108,10 +1128,6 @@ static int kernel_grid_cap(const void *fn, int threads, size_t lds, int max_bpc,
 #define TRC_STREAM_MIN_RAYS 1048576
 #include "trc_stream.inc"
 
-static void scene_free_stream_ws(trc_scene *sc) {
-    if (sc->stream_eng) { stream_engine_free(sc->stream_eng); sc->stream_eng = nullptr; }
-}
-
 // ================================================================================================
 // source generation as a bundle (sources.*_bundle)
 // ================================================================================================
@@ -1734,7 +1750,6 @@ extern "C" int trc_scene_destroy(trc_scene *sc) {
     if (!sc) return TRC_OK;
     (void)hipSetDevice(sc->ctx->device);
     (void)hipStreamSynchronize(sc->ctx->stream);
-    scene_free_stream_ws(sc);
     delete sc;
     return TRC_OK;
 }
@@ -2233,9 +2248,9 @@ extern "C" int trc_scene_bin_hits(trc_scene *sc, int32_t n_bins, const int32_t *
     for (int i = 0; i < n_bins; ++i) out[i] = 0.0;
     if (reserved == 0) return TRC_OK;
     const size_t per_bin = 2 * sizeof(int32_t) + 6 * sizeof(double) + sizeof(int32_t) + sizeof(double);
-    char *d_buf = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_buf, (size_t)BIN_TILE * per_bin));
-    double *d_rng = (double *)d_buf, *d_out = d_rng + 6 * BIN_TILE;
+    DevBuf<char> d_buf;
+    TRC_TRY(d_buf.alloc((size_t)BIN_TILE * per_bin));
+    double *d_rng = (double *)d_buf.get(), *d_out = d_rng + 6 * BIN_TILE;
     int32_t *d_lo = (int32_t *)(d_out + BIN_TILE), *d_hi = d_lo + BIN_TILE, *d_mode = d_hi + BIN_TILE;
     int st = TRC_OK;
     unsigned grid = (unsigned)((reserved + 255) / 256);
@@ -2256,7 +2271,6 @@ extern "C" int trc_scene_bin_hits(trc_scene *sc, int32_t n_bins, const int32_t *
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) st = trc_fail(TRC_ERR_DEVICE, "trc_scene_bin_hits: %s", hipGetErrorString(e));
     }
-    (void)hipFree(d_buf);
     return st;
 }
 
@@ -2999,7 +3013,7 @@ static int fast_steps(FastCall &C) {
     TRC_TRY(fast_choose_engine(C, &plan, &use_stream));
     if (use_stream) {
         if (!sc->stream_eng) {
-            sc->stream_eng = new (std::nothrow) StreamEngine();      // (value-initialised: all zero)
+            sc->stream_eng.reset(new (std::nothrow) StreamEngine());
             if (!sc->stream_eng) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
         }
         if (int e = stream_trace(sc, P, carry_in, plan, C.knobs, C.src, *sc->stream_eng, &C.s, &C.stream_seg, &C.stream_hits)) {

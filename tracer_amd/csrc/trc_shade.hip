@@ -28,7 +28,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
     const DScene &sc = P.sc;
     const StreamWs &W = S.W;
     const int Sn = sc.n_surf;
-    if (W.cnt[CN(4)]) return;
+    if (W.cnt[CN(CW_OVERFLOW)]) return;
     constexpr unsigned KINDS = CLS == TRC_CLS_MIRROR ? TRC_CLS_MIRROR_KINDS : TRC_CLS_DIFFUSE_KINDS;
     DScene L = sc;
     // (one of TALLY_PARTS copies of the tally buffer per workgroup, also where the tables are beyond LDS and the sums are added per
@@ -178,12 +178,12 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
             if (ts >= 0) { atomicAdd(&tl[ts], tea); atomicAdd(&tl[Sn + ts], tei); atomicAdd(&tl[2 * Sn + ts], 1.0); }
         }
         if (P.capture) chunk_rebroadcast(hc, __ffsll((long long)my_lanes) - 1);   // hc was advanced by the lanes with a hit only
-        const unsigned long long q = chunk_append(&W.cnt[CN(3)], ca, alive, S.act_out, W.act_room);
-        if (alive) { if ((long long)q < W.act_room) S.act_out[q] = slot; else W.cnt[CN(4)] = 2ull; n_alive += 1; }
+        const unsigned long long q = chunk_append(&W.cnt[CN(CW_ACT_OUT)], ca, alive, S.act_out, W.act_room);
+        if (alive) { if ((long long)q < W.act_room) S.act_out[q] = slot; else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL; n_alive += 1; }
     }
     chunk_close(ca, S.act_out, W.act_room);
     if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
-    flush_counts<true>(l_tally + (LDS ? 3 * Sn : 0), n_hit, n_alive, &W.cnt[CN(6)], &W.cnt[CN(13 + CLS)], &W.cnt[CN(7)]);
+    flush_counts<true>(l_tally + (LDS ? 3 * Sn : 0), n_hit, n_alive, &W.cnt[CN(CW_HITS)], &W.cnt[CN(CW_CLS_HITS + CLS)], &W.cnt[CN(CW_ALIVE)]);
     flush_sums(L.tally, l_tally, LDS ? 3 * Sn : 0, l_fm, S.lds_fm_bins, Sn);
 }
 
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
     const DScene &sc = P.sc;
     const StreamWs &W = S.W;
     const int Sn = sc.n_surf;
-    if (W.cnt[CN(4)]) return;
+    if (W.cnt[CN(CW_OVERFLOW)]) return;
     DScene L = sc;
     L.tally = W.tally_part + (size_t)(blockIdx.x % TALLY_PARTS) * (size_t)W.tally_n;
     double *l_tally = lds;
@@ -395,12 +395,12 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
             if (ts >= 0) { atomicAdd(&tl[ts], tea); atomicAdd(&tl[Sn + ts], tei); atomicAdd(&tl[2 * Sn + ts], 1.0); }
         }
         if (P.capture) chunk_rebroadcast(hc, __ffsll((long long)my_lanes) - 1);
-        const unsigned long long q = chunk_append(&W.cnt[CN(3)], ca, alive, S.act_out, W.act_room);
-        if (alive) { if ((long long)q < W.act_room) S.act_out[q] = slot; else W.cnt[CN(4)] = 2ull; n_alive += 1; }
+        const unsigned long long q = chunk_append(&W.cnt[CN(CW_ACT_OUT)], ca, alive, S.act_out, W.act_room);
+        if (alive) { if ((long long)q < W.act_room) S.act_out[q] = slot; else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL; n_alive += 1; }
     }
     chunk_close(ca, S.act_out, W.act_room);
     if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
-    flush_counts<true>(l_tally + (LDS ? 3 * Sn : 0), n_hit, n_alive, &W.cnt[CN(6)], &W.cnt[CN(13 + TRC_CLS_GENERAL)], &W.cnt[CN(7)]);
+    flush_counts<true>(l_tally + (LDS ? 3 * Sn : 0), n_hit, n_alive, &W.cnt[CN(CW_HITS)], &W.cnt[CN(CW_CLS_HITS + TRC_CLS_GENERAL)], &W.cnt[CN(CW_ALIVE)]);
     flush_sums(L.tally, l_tally, LDS ? 3 * Sn : 0, l_fm, S.lds_fm_bins, Sn);
 }
 

@@ -35,7 +35,7 @@ __device__ __forceinline__ void s_gen_body(const StreamParams &S, trc_buie_fast 
     const trc_accel_view A = stream_accel_global(sc, S.search);
     // FRESH: the rays of the batch, or those k_s_fresh left to this path (their numbers in gen_list); else the active list
     const uint32_t *list = FRESH ? S.gen_list : S.act_in;
-    long long count = FRESH ? (list ? (long long)W.cnt[CN(9)] : S.nb) : (long long)W.cnt[CN(5)];
+    long long count = FRESH ? (list ? (long long)W.cnt[CN(CW_GEN_LIST)] : S.nb) : (long long)W.cnt[CN(CW_ACT_IN)];
     if (list && count > (FRESH ? SQ_ROOM(W) : W.act_room)) count = FRESH ? SQ_ROOM(W) : W.act_room;
     const long long padded = (count + 63) & ~63ll;
     const unsigned long long wave_g = ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -81,10 +81,10 @@ __device__ __forceinline__ void s_gen_body(const StreamParams &S, trc_buie_fast 
         }
         cand = valid && (cand || A.n_unbounded > 0);
         if (FRESH) {                    // a ray with a candidate takes the next slot of the table
-            const unsigned long long sl = chunk_append(&W.cnt[CN(8)], cs, cand, nullptr, 0);
+            const unsigned long long sl = chunk_append(&W.cnt[CN(CW_SLOTS)], cs, cand, nullptr, 0);
             if (cand) {
                 if ((long long)sl < SQ_ROOM(W)) slot = (uint32_t)sl;
-                else { W.cnt[CN(4)] = 2ull; cand = false; }
+                else { W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL; cand = false; }
             }
         }
         if (cand) {
@@ -104,20 +104,20 @@ __device__ __forceinline__ void s_gen_body(const StreamParams &S, trc_buie_fast 
         }
         // rays that enter the root box go to the walker queue Q1
         const bool towalk = cand && walking;
-        unsigned long long q = chunk_append(&W.cnt[CN(0)], c1, towalk, W.q1_slot, SQ_ROOM(W));
+        unsigned long long q = chunk_append(&W.cnt[CN(CW_Q1)], c1, towalk, W.q1_slot, SQ_ROOM(W));
         if (towalk) {
             if ((long long)q < SQ_ROOM(W)) {
                 W.q1_slot[q] = slot;
                 W.q1_a[q] = make_float4(r.ox, r.oy, r.oz, r.ix);
                 W.q1_b[q] = make_float4(r.iy, r.iz, tmin, tmax);
-            } else W.cnt[CN(4)] = 2ull;
+            } else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
         }
         // surfaces without bounds (infinite planes, cylinders ...): every ray is a candidate
         for (int k = 0; k < A.n_unbounded; ++k) {
-            unsigned long long q3 = chunk_append(&W.cnt[CN(1)], c3, cand, W.q3_slot, W.q3_cap);
+            unsigned long long q3 = chunk_append(&W.cnt[CN(CW_Q3)], c3, cand, W.q3_slot, W.q3_cap);
             if (cand) {
                 if ((long long)q3 < W.q3_cap) { W.q3_slot[q3] = slot; W.q3_surf[q3] = (uint32_t)A.unbounded[k]; }
-                else W.cnt[CN(4)] = 1ull;
+                else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_RETRY;
             }
         }
         // always-relevant surfaces whose box the ray crosses: straight to the exact queue
@@ -128,10 +128,10 @@ __device__ __forceinline__ void s_gen_body(const StreamParams &S, trc_buie_fast 
                 want = !(b[3] == TRC_INF && b[0] == -TRC_INF) && trc_box_hit32(b, r);
             }
             if (want) want = trc_obb_hit32(sc.a_obb + (size_t)TRC_OBB_STRIDE * (size_t)A.always[k], r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
-            unsigned long long q3 = chunk_append(&W.cnt[CN(1)], c3, want, W.q3_slot, W.q3_cap);
+            unsigned long long q3 = chunk_append(&W.cnt[CN(CW_Q3)], c3, want, W.q3_slot, W.q3_cap);
             if (want) {
                 if ((long long)q3 < W.q3_cap) { W.q3_slot[q3] = slot; W.q3_surf[q3] = (uint32_t)A.always[k]; }
-                else W.cnt[CN(4)] = 1ull;
+                else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_RETRY;
             }
         }
     }
@@ -214,21 +214,21 @@ __global__ __launch_bounds__(SC_THREADS) void k_s_cull(CullParams C) {
         const bool bit = ((l_mask[((uint32_t)iy * (uint32_t)F.M + (uint32_t)ix) >> 5] >> (ix & 31)) & 1u) != 0u;
         const bool generic = valid && trc_fp_generic(F, o);
         if (C.gen_chunk) {
-            const unsigned long long qg = chunk_append(&C.cnt[CN(9)], cg, generic, C.gen_list, C.room);
-            if (generic) { if ((long long)qg < C.room) C.gen_list[qg] = (uint32_t)i; else C.cnt[CN(4)] = 2ull; }
+            const unsigned long long qg = chunk_append(&C.cnt[CN(CW_GEN_LIST)], cg, generic, C.gen_list, C.room);
+            if (generic) { if ((long long)qg < C.room) C.gen_list[qg] = (uint32_t)i; else C.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL; }
         } else if (generic) {
             const uint32_t at = atomicAdd(&l_gen_n[0], 1u);
             if (at < SC_GEN_CAP) l_gen[at] = (uint32_t)i;
             else {      // the workgroup's list is full (the source is not what the host took it for): one entry, one atomic
-                const unsigned long long qg = atomicAdd(&C.cnt[CN(9)], 1ull);
-                if ((long long)qg < C.room) C.gen_list[qg] = (uint32_t)i; else C.cnt[CN(4)] = 2ull;
+                const unsigned long long qg = atomicAdd(&C.cnt[CN(CW_GEN_LIST)], 1ull);
+                if ((long long)qg < C.room) C.gen_list[qg] = (uint32_t)i; else C.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
             }
         }
         const bool pass = valid && !generic && bit;
-        const unsigned long long q = chunk_append(&C.cnt[CN(10)], cf, pass, C.fq_ray, C.room);
+        const unsigned long long q = chunk_append(&C.cnt[CN(CW_FP_LIST)], cf, pass, C.fq_ray, C.room);
         if (pass) {
             if ((long long)q < C.room) { C.fq_ray[q] = (uint32_t)i; C.fq_cell[q] = ((uint32_t)iy << 16) | (uint32_t)ix; }
-            else C.cnt[CN(4)] = 2ull;
+            else C.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
         }
     }
     if (C.gen_chunk) chunk_close(cg, C.gen_list, C.room);
@@ -238,9 +238,9 @@ __global__ __launch_bounds__(SC_THREADS) void k_s_cull(CullParams C) {
         uint32_t n = l_gen_n[0];
         if (n > SC_GEN_CAP) n = SC_GEN_CAP;
         if (threadIdx.x == 0 && n) {
-            const unsigned long long b = atomicAdd(&C.cnt[CN(9)], (unsigned long long)n);
+            const unsigned long long b = atomicAdd(&C.cnt[CN(CW_GEN_LIST)], (unsigned long long)n);
             l_gen_n[1] = (uint32_t)b;           // the list holds fewer than 2^32 entries (room <= 2^26 + slack)
-            if ((long long)(b + n) > C.room) { C.cnt[CN(4)] = 2ull; l_gen_n[0] = 0u; }
+            if ((long long)(b + n) > C.room) { C.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL; l_gen_n[0] = 0u; }
         }
         __syncthreads();
         n = l_gen_n[0] > SC_GEN_CAP ? SC_GEN_CAP : l_gen_n[0];
@@ -305,8 +305,8 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh(StreamParams S) {
     __syncthreads();
     if (BUIE) trc_buie_fast_fill(P.src->buie, l_bf, 1, (int)threadIdx.x, (int)blockDim.x);
     __syncthreads();
-    if (W.cnt[CN(4)]) return;
-    long long count = (long long)W.cnt[CN(10)];
+    if (W.cnt[CN(CW_OVERFLOW)]) return;
+    long long count = (long long)W.cnt[CN(CW_FP_LIST)];
     if (count > SQ_ROOM(W)) count = SQ_ROOM(W);
     const long long padded = (count + 63) & ~63ll;
     const unsigned long long wave_g = ((unsigned long long)blockIdx.x * THREADS + threadIdx.x) >> 6;
@@ -363,8 +363,8 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh(StreamParams S) {
             }
         }
         const bool hit = active && tb < TRC_INF;
-        const unsigned long long sl = chunk_append(&W.cnt[CN(8)], cs, hit, nullptr, 0);
-        const unsigned long long qh = chunk_append(&W.cnt[CN(2)], ch, hit, W.hit_slot, SQ_ROOM(W));
+        const unsigned long long sl = chunk_append(&W.cnt[CN(CW_SLOTS)], cs, hit, nullptr, 0);
+        const unsigned long long qh = chunk_append(&W.cnt[CN(CW_HIT_LIST)], ch, hit, W.hit_slot, SQ_ROOM(W));
         if (hit) {
             if ((long long)sl < SQ_ROOM(W) && (long long)qh < SQ_ROOM(W)) {
                 SRayGeo g;
@@ -376,7 +376,7 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh(StreamParams S) {
                 W.hit_slot[qh] = (uint32_t)sl;
                 W.hit_surf[qh] = (uint32_t)sb;
                 W.hit_t[qh] = tb;
-            } else W.cnt[CN(4)] = 2ull;
+            } else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
         }
     }
     chunk_close(ch, W.hit_slot, SQ_ROOM(W));
@@ -431,8 +431,8 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh2(StreamParams S) {
     __syncthreads();
     trc_buie_fast_fill(P.src->buie, l_bf, 1, (int)threadIdx.x, (int)blockDim.x);
     __syncthreads();
-    if (W.cnt[CN(4)]) return;
-    long long count = (long long)W.cnt[CN(10)];
+    if (W.cnt[CN(CW_OVERFLOW)]) return;
+    long long count = (long long)W.cnt[CN(CW_FP_LIST)];
     if (count > SQ_ROOM(W)) count = SQ_ROOM(W);
     const long long padded = (count + 63) & ~63ll;
     const unsigned lane = lane_id();
@@ -488,8 +488,8 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh2(StreamParams S) {
             }
         }
         const bool hit = active && tb < TRC_INF;
-        const unsigned long long sl = chunk_append(&W.cnt[CN(8)], cs, hit, nullptr, 0);
-        const unsigned long long qhit = chunk_append(&W.cnt[CN(2)], ch, hit, W.hit_slot, SQ_ROOM(W));
+        const unsigned long long sl = chunk_append(&W.cnt[CN(CW_SLOTS)], cs, hit, nullptr, 0);
+        const unsigned long long qhit = chunk_append(&W.cnt[CN(CW_HIT_LIST)], ch, hit, W.hit_slot, SQ_ROOM(W));
         if (hit) {
             if ((long long)sl < SQ_ROOM(W) && (long long)qhit < SQ_ROOM(W)) {
                 SRayGeo g;
@@ -501,7 +501,7 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh2(StreamParams S) {
                 W.hit_slot[qhit] = (uint32_t)sl;
                 W.hit_surf[qhit] = (uint32_t)sb;
                 W.hit_t[qhit] = tb;
-            } else W.cnt[CN(4)] = 2ull;
+            } else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
         }
         qh += take;
     };
@@ -595,7 +595,7 @@ __device__ __forceinline__ void sw_drain(const trc_accel_view &A, const float *o
     const unsigned total = __shfl(incl, 63, 64);
     if (total == 0) return;
 #ifdef SW_STATS
-    if (lane == 0) { atomicAdd(&W.cnt[CN(21)], 1ull); atomicAdd(&W.cnt[CN(22)], (unsigned long long)((total + 63) / 64)); }
+    if (lane == 0) { atomicAdd(&W.cnt[CN(CW_STATS + 5)], 1ull); atomicAdd(&W.cnt[CN(CW_STATS + 6)], (unsigned long long)((total + 63) / 64)); }
 #endif
     L.pre[lane] = incl;
     WAVE_SYNC();
@@ -639,10 +639,10 @@ __device__ __forceinline__ void sw_drain(const trc_accel_view &A, const float *o
                 // the surface's own (oriented) box: for a plate the plate itself +- delta -- three of four rays that cross the
                 // axis-aligned box of a tilted mirror miss the mirror
                 if (want) want = trc_obb_hit32(obb + (size_t)TRC_OBB_STRIDE * sidx, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
-                unsigned long long q3 = chunk_append(&W.cnt[CN(1)], c3, want, W.q3_slot, W.q3_cap);
+                unsigned long long q3 = chunk_append(&W.cnt[CN(CW_Q3)], c3, want, W.q3_slot, W.q3_cap);
                 if (want) {
                     if ((long long)q3 < W.q3_cap) { W.q3_slot[q3] = oslot; W.q3_surf[q3] = sidx; }
-                    else W.cnt[CN(4)] = 1ull;
+                    else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_RETRY;
                 }
                 hits &= hits - 1u;
             }
@@ -704,8 +704,8 @@ __global__ __launch_bounds__(THREADS) void k_s_walk(StreamParams S) {
         A.sbox = l_sbox; A.nodes = l_nodes; A.leaf_surfs = l_leaf;
     }
     __syncthreads();
-    if (W.cnt[CN(4)] == 2ull) return;       // a list overflowed upstream: the host gives the call up, nothing below may run on its leftovers
-    long long nq = (long long)W.cnt[CN(0)];
+    if (W.cnt[CN(CW_OVERFLOW)] == CW_OVF_FAIL) return;       // a list overflowed upstream: the host gives the call up, nothing below may run on its leftovers
+    long long nq = (long long)W.cnt[CN(CW_Q1)];
     if (nq > SQ_ROOM(W)) nq = SQ_ROOM(W);   // never read beyond the allocation, whatever the counter says
     const long long n_waves = (long long)gridDim.x * (THREADS >> 6);
     const long long wave = (long long)blockIdx.x * (THREADS >> 6) + (tid >> 6);
@@ -729,7 +729,7 @@ __global__ __launch_bounds__(THREADS) void k_s_walk(StreamParams S) {
         int sp = 0;
         unsigned cnt = 0;
 #ifdef SW_STATS
-        if (walk) atomicAdd(&W.cnt[CN(16)], 1ull);
+        if (walk) atomicAdd(&W.cnt[CN(CW_STATS)], 1ull);
 #endif
         if (GRID) {
             // uniform grid: list the non-empty cells of the DDA between tmin and tmax
@@ -741,8 +741,8 @@ __global__ __launch_bounds__(THREADS) void k_s_walk(StreamParams S) {
                 for (int rep = 0; rep < 4 && walk && cnt < SW_LEAFCAP; ++rep) {
                     const int cell = trc_dda_cell(G, dd);
 #ifdef SW_STATS
-                    atomicAdd(&W.cnt[CN(18)], 1ull);
-                    if (goff[cell + 1] != goff[cell]) { atomicAdd(&W.cnt[CN(19)], 1ull); atomicAdd(&W.cnt[CN(20)], (unsigned long long)(goff[cell + 1] - goff[cell])); }
+                    atomicAdd(&W.cnt[CN(CW_STATS + 2)], 1ull);
+                    if (goff[cell + 1] != goff[cell]) { atomicAdd(&W.cnt[CN(CW_STATS + 3)], 1ull); atomicAdd(&W.cnt[CN(CW_STATS + 4)], (unsigned long long)(goff[cell + 1] - goff[cell])); }
 #endif
                     if (goff[cell + 1] != goff[cell]) { L.lst[cnt * 64 + lane] = (SW_LIST_T)cell; ++cnt; }
                     walk = trc_dda_next(G, r, tmax, &dd);
@@ -755,14 +755,14 @@ __global__ __launch_bounds__(THREADS) void k_s_walk(StreamParams S) {
         }
         while (!GRID && __ballot(walk)) {
 #ifdef SW_STATS
-            if (lane == 0) atomicAdd(&W.cnt[CN(17)], 1ull);
+            if (lane == 0) atomicAdd(&W.cnt[CN(CW_STATS + 1)], 1ull);
 #endif
 #pragma unroll 1
             for (int rep = 0; rep < 4 && walk && cnt < SW_LEAFCAP; ++rep) {
                 uint32_t w0 = A.nodes[2 * node], w1 = A.nodes[2 * node + 1];
 #ifdef SW_STATS
-                atomicAdd(&W.cnt[CN(18)], 1ull);
-                if ((w1 & 3u) == 3u && (w1 >> 2) != 0u) { atomicAdd(&W.cnt[CN(19)], 1ull); atomicAdd(&W.cnt[CN(20)], (unsigned long long)(w1 >> 2)); }
+                atomicAdd(&W.cnt[CN(CW_STATS + 2)], 1ull);
+                if ((w1 & 3u) == 3u && (w1 >> 2) != 0u) { atomicAdd(&W.cnt[CN(CW_STATS + 3)], 1ull); atomicAdd(&W.cnt[CN(CW_STATS + 4)], (unsigned long long)(w1 >> 2)); }
 #endif
                 if ((w1 & 3u) != 3u) {
                     bool push;
@@ -940,10 +940,10 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
         if (buie_src) trc_buie_fast_fill(P.src->buie, l_bf, 1, tid, THREADS);
     }
     __syncthreads();
-    if (W.cnt[CN(4)]) return;
+    if (W.cnt[CN(CW_OVERFLOW)]) return;
     // the rays: the active list (slots), or fresh rays by number -- all of the batch or those k_s_cull left to this path
     const uint32_t *list = FRESH ? S.gen_list : S.act_in;
-    long long count = FRESH ? (list ? (long long)W.cnt[CN(9)] : S.nb) : (long long)W.cnt[CN(5)];
+    long long count = FRESH ? (list ? (long long)W.cnt[CN(CW_GEN_LIST)] : S.nb) : (long long)W.cnt[CN(CW_ACT_IN)];
     if (list && count > (FRESH ? SQ_ROOM(W) : W.act_room)) count = FRESH ? SQ_ROOM(W) : W.act_room;
     const long long padded = (count + 63) & ~63ll;
     const unsigned long long wave_g = ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -1181,7 +1181,7 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
 #undef SB_TEST
         const bool hit = valid && tb < TRC_INF;
         if (FRESH) {            // a fresh ray that hits takes the next slot of the table
-            const unsigned long long sl = chunk_append(&W.cnt[CN(8)], cs, hit, nullptr, 0);
+            const unsigned long long sl = chunk_append(&W.cnt[CN(CW_SLOTS)], cs, hit, nullptr, 0);
             if (hit) {
                 if ((long long)sl < SQ_ROOM(W)) {
                     slot = (uint32_t)sl;
@@ -1196,7 +1196,7 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
                         a.e = e0; a.ref = ref0; a.wl = wl0; a.pad = 0.0;
                         W.aux[slot] = a;
                     }
-                } else W.cnt[CN(4)] = 2ull;
+                } else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
             }
         }
         bool listed = hit && slot != SQ_INVALID;
@@ -1226,17 +1226,17 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
             if (term) listed = false;
         } else if (split) {
             const bool term = listed && (sflags[sb] & TRC_SURF_TERMINAL) != 0;
-            const unsigned long long q2 = chunk_append(&W.cnt[CN(11)], ct, term, t_slot, SQ_ROOM(W));
+            const unsigned long long q2 = chunk_append(&W.cnt[CN(CW_TERM_LIST)], ct, term, t_slot, SQ_ROOM(W));
             if (term) {
                 if ((long long)q2 < SQ_ROOM(W)) { t_slot[q2] = slot; t_surf[q2] = (uint32_t)sb; t_t[q2] = tb; }
-                else W.cnt[CN(4)] = 2ull;
+                else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
                 listed = false;
             }
         }
-        const unsigned long long q = chunk_append(&W.cnt[CN(2)], ch, listed, W.hit_slot, SQ_ROOM(W));
+        const unsigned long long q = chunk_append(&W.cnt[CN(CW_HIT_LIST)], ch, listed, W.hit_slot, SQ_ROOM(W));
         if (listed) {
             if ((long long)q < SQ_ROOM(W)) { W.hit_slot[q] = slot; W.hit_surf[q] = (uint32_t)sb; W.hit_t[q] = tb; }
-            else W.cnt[CN(4)] = 2ull;
+            else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
         }
     }
     chunk_close(ch, W.hit_slot, SQ_ROOM(W));
@@ -1248,7 +1248,7 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
         __syncthreads();
         if (tid == 0) {
             const unsigned long long hh = (unsigned long long)(a_tally[3 * Sn] + 0.5);
-            if (hh) { atomicAdd(&W.cnt[CN(6)], hh); atomicAdd(&W.cnt[CN(12)], hh); }
+            if (hh) { atomicAdd(&W.cnt[CN(CW_HITS)], hh); atomicAdd(&W.cnt[CN(CW_TERM_HITS)], hh); }
         }
         flush_sums<THREADS>(La.tally, a_tally, 3 * Sn, a_fm, S.lds_fm_bins, Sn);
     }
@@ -1324,9 +1324,9 @@ __global__ __launch_bounds__(SB_THREADS) void k_s_bounce_coop(StreamParams S) {
         if (buie_src) trc_buie_fast_fill(P.src->buie, l_bf, 1, tid, THREADS);
     }
     __syncthreads();
-    if (W.cnt[CN(4)]) return;
+    if (W.cnt[CN(CW_OVERFLOW)]) return;
     const uint32_t *list = FRESH ? S.gen_list : S.act_in;
-    long long count = FRESH ? (list ? (long long)W.cnt[CN(9)] : S.nb) : (long long)W.cnt[CN(5)];
+    long long count = FRESH ? (list ? (long long)W.cnt[CN(CW_GEN_LIST)] : S.nb) : (long long)W.cnt[CN(CW_ACT_IN)];
     if (list && count > (FRESH ? SQ_ROOM(W) : W.act_room)) count = FRESH ? SQ_ROOM(W) : W.act_room;
     const long long padded = (count + 63) & ~63ll;
     const unsigned long long wave_g = ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -1519,7 +1519,7 @@ __global__ __launch_bounds__(SB_THREADS) void k_s_bounce_coop(StreamParams S) {
         }
         const bool hit = valid && sb != 0x7FFFFFFF && tb < TRC_INF;
         if (FRESH) {            // a fresh ray that hits takes the next slot of the table
-            const unsigned long long sl = chunk_append(&W.cnt[CN(8)], cs, hit, nullptr, 0);
+            const unsigned long long sl = chunk_append(&W.cnt[CN(CW_SLOTS)], cs, hit, nullptr, 0);
             if (hit) {
                 if ((long long)sl < SQ_ROOM(W)) {
                     slot = (uint32_t)sl;
@@ -1534,23 +1534,23 @@ __global__ __launch_bounds__(SB_THREADS) void k_s_bounce_coop(StreamParams S) {
                         a.e = e0; a.ref = ref0; a.wl = wl0; a.pad = 0.0;
                         W.aux[slot] = a;
                     }
-                } else W.cnt[CN(4)] = 2ull;
+                } else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
             }
         }
         bool listed = hit && slot != SQ_INVALID;
         if (split) {
             const bool term = listed && (sflags[sb] & TRC_SURF_TERMINAL) != 0;
-            const unsigned long long q2 = chunk_append(&W.cnt[CN(11)], ct, term, t_slot, SQ_ROOM(W));
+            const unsigned long long q2 = chunk_append(&W.cnt[CN(CW_TERM_LIST)], ct, term, t_slot, SQ_ROOM(W));
             if (term) {
                 if ((long long)q2 < SQ_ROOM(W)) { t_slot[q2] = slot; t_surf[q2] = (uint32_t)sb; t_t[q2] = tb; }
-                else W.cnt[CN(4)] = 2ull;
+                else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
                 listed = false;
             }
         }
-        const unsigned long long q = chunk_append(&W.cnt[CN(2)], ch, listed, W.hit_slot, SQ_ROOM(W));
+        const unsigned long long q = chunk_append(&W.cnt[CN(CW_HIT_LIST)], ch, listed, W.hit_slot, SQ_ROOM(W));
         if (listed) {
             if ((long long)q < SQ_ROOM(W)) { W.hit_slot[q] = slot; W.hit_surf[q] = (uint32_t)sb; W.hit_t[q] = tb; }
-            else W.cnt[CN(4)] = 2ull;
+            else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
         }
     }
     chunk_close(ch, W.hit_slot, SQ_ROOM(W));
@@ -1569,8 +1569,8 @@ __global__ __launch_bounds__(256) void k_s_exact(StreamParams S) {
         __syncthreads();
         recs = lds;
     }
-    if (W.cnt[CN(4)]) return;       // the candidate queue overflowed in k_s_walk: nothing of this bounce is committed, the host retries
-    long long n3 = (long long)W.cnt[CN(1)];
+    if (W.cnt[CN(CW_OVERFLOW)]) return;       // the candidate queue overflowed in k_s_walk: nothing of this bounce is committed, the host retries
+    long long n3 = (long long)W.cnt[CN(CW_Q3)];
     if (n3 > W.q3_cap) n3 = W.q3_cap;
     const long long padded = (n3 + 63) & ~63ll;
     WaveChunk ch = S.static_general ? chunk_init_static_at(SQ_CHUNK, (unsigned long long)S.hit_base0 + (((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * SQ_CHUNK) : chunk_init();
@@ -1604,10 +1604,10 @@ __global__ __launch_bounds__(256) void k_s_exact(StreamParams S) {
         if (t0 < TRC_INF) { SCand c; c.t = t0; c.surf = sidx0; c.next = prev0; W.q3n[i0] = c; }
         if (t1 < TRC_INF) { SCand c; c.t = t1; c.surf = sidx1; c.next = prev1; W.q3n[i1] = c; }
         const bool first0 = t0 < TRC_INF && prev0 == SQ_INVALID, first1 = t1 < TRC_INF && prev1 == SQ_INVALID;
-        unsigned long long q = chunk_append(&W.cnt[CN(2)], ch, first0, W.hit_slot, SQ_ROOM(W));
-        if (first0) { if ((long long)q < SQ_ROOM(W)) { W.hit_slot[q] = slot0; W.hit_surf[q] = SQ_INVALID; } else W.cnt[CN(4)] = 2ull; }
-        q = chunk_append(&W.cnt[CN(2)], ch, first1, W.hit_slot, SQ_ROOM(W));
-        if (first1) { if ((long long)q < SQ_ROOM(W)) { W.hit_slot[q] = slot1; W.hit_surf[q] = SQ_INVALID; } else W.cnt[CN(4)] = 2ull; }
+        unsigned long long q = chunk_append(&W.cnt[CN(CW_HIT_LIST)], ch, first0, W.hit_slot, SQ_ROOM(W));
+        if (first0) { if ((long long)q < SQ_ROOM(W)) { W.hit_slot[q] = slot0; W.hit_surf[q] = SQ_INVALID; } else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL; }
+        q = chunk_append(&W.cnt[CN(CW_HIT_LIST)], ch, first1, W.hit_slot, SQ_ROOM(W));
+        if (first1) { if ((long long)q < SQ_ROOM(W)) { W.hit_slot[q] = slot1; W.hit_surf[q] = SQ_INVALID; } else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL; }
     }
     chunk_close(ch, W.hit_slot, SQ_ROOM(W));
 }
@@ -1621,8 +1621,8 @@ __global__ __launch_bounds__(256) void k_s_partition(StreamParams S) {
     const DScene &sc = S.P.sc;
     const StreamWs &W = S.W;
     const int Sn = sc.n_surf;
-    if (W.cnt[CN(4)]) return;
-    long long nh = (long long)W.cnt[CN(2)];
+    if (W.cnt[CN(CW_OVERFLOW)]) return;
+    long long nh = (long long)W.cnt[CN(CW_HIT_LIST)];
     if (nh > SQ_ROOM(W)) nh = SQ_ROOM(W);
     const long long padded = (nh + 63) & ~63ll;
     const unsigned long long wave_g = ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -1664,10 +1664,10 @@ __global__ __launch_bounds__(256) void k_s_partition(StreamParams S) {
 #pragma unroll
             for (int c = 0; c < TRC_CLS_COUNT; ++c) {
                 if (!W.pl_slot[c]) continue;
-                const unsigned long long q = chunk_append(&W.cnt[CN(24 + c)], pc[c], cls[u] == c, W.pl_slot[c], W.pl_room);
+                const unsigned long long q = chunk_append(&W.cnt[CN(CW_CLS_LIST + c)], pc[c], cls[u] == c, W.pl_slot[c], W.pl_room);
                 if (cls[u] == c) {
                     if ((long long)q < W.pl_room) { W.pl_slot[c][q] = slot[u]; W.pl_surf[c][q] = hs[u]; W.pl_t[c][q] = t[u]; }
-                    else W.cnt[CN(4)] = 2ull;
+                    else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
                 }
             }
         }
@@ -1688,7 +1688,7 @@ __global__ __launch_bounds__(128 * WAVES, WAVES) void k_s_shade(StreamParams S) 
     const DScene &sc = P.sc;
     const StreamWs &W = S.W;
     const int Sn = sc.n_surf;
-    if (W.cnt[CN(4)]) return;
+    if (W.cnt[CN(CW_OVERFLOW)]) return;
     // LDS: tallies | surface records | optics parameters | flux-map tables and capture flags.  Everything a hit looks up by
     // surface index is read from LDS: from global memory each of them is a dependent round trip (the flux-map bin search
     // alone was twelve of them per hit).
@@ -1852,8 +1852,8 @@ __global__ __launch_bounds__(128 * WAVES, WAVES) void k_s_shade(StreamParams S) 
             if (ts >= 0) { atomicAdd(&l_tally[ts], tea); atomicAdd(&l_tally[Sn + ts], tei); atomicAdd(&l_tally[2 * Sn + ts], 1.0); }
         }
         if (hit_lanes && P.capture) chunk_rebroadcast(hc, __ffsll((long long)hit_lanes) - 1);   // hc was advanced by the lanes with a hit only
-        unsigned long long q = chunk_append(&W.cnt[CN(3)], ca, alive, S.act_out, W.act_room);
-        if (alive) { if ((long long)q < W.act_room) S.act_out[q] = slot; else W.cnt[CN(4)] = 2ull; n_alive += 1; }
+        unsigned long long q = chunk_append(&W.cnt[CN(CW_ACT_OUT)], ca, alive, S.act_out, W.act_room);
+        if (alive) { if ((long long)q < W.act_room) S.act_out[q] = slot; else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL; n_alive += 1; }
     }
     chunk_close(ca, S.act_out, W.act_room);
     if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
@@ -1864,16 +1864,16 @@ __global__ __launch_bounds__(128 * WAVES, WAVES) void k_s_shade(StreamParams S) 
         if (LDS) {
             if (lane_id() == 0) { atomicAdd(&l_tally[3 * Sn], h); atomicAdd(&l_tally[3 * Sn + 1], a); }
         } else if (lane_id() == 0) {
-            atomicAdd(&W.cnt[CN(6)], (unsigned long long)(h + 0.5)); atomicAdd(&W.cnt[CN(7)], (unsigned long long)(a + 0.5));
-            atomicAdd(&W.cnt[CN(13 + TRC_CLS_GENERAL)], (unsigned long long)(h + 0.5));
+            atomicAdd(&W.cnt[CN(CW_HITS)], (unsigned long long)(h + 0.5)); atomicAdd(&W.cnt[CN(CW_ALIVE)], (unsigned long long)(a + 0.5));
+            atomicAdd(&W.cnt[CN(CW_CLS_HITS + TRC_CLS_GENERAL)], (unsigned long long)(h + 0.5));
         }
     }
     if (LDS) {
         __syncthreads();
         if (threadIdx.x == 0) {
-            atomicAdd(&W.cnt[CN(6)], (unsigned long long)(l_tally[3 * Sn] + 0.5));
-            atomicAdd(&W.cnt[CN(7)], (unsigned long long)(l_tally[3 * Sn + 1] + 0.5));
-            atomicAdd(&W.cnt[CN(13 + TRC_CLS_GENERAL)], (unsigned long long)(l_tally[3 * Sn] + 0.5));
+            atomicAdd(&W.cnt[CN(CW_HITS)], (unsigned long long)(l_tally[3 * Sn] + 0.5));
+            atomicAdd(&W.cnt[CN(CW_ALIVE)], (unsigned long long)(l_tally[3 * Sn + 1] + 0.5));
+            atomicAdd(&W.cnt[CN(CW_CLS_HITS + TRC_CLS_GENERAL)], (unsigned long long)(l_tally[3 * Sn] + 0.5));
         }
         for (int i = threadIdx.x; i < 3 * Sn; i += blockDim.x) {
             double v = l_tally[i];
@@ -1901,7 +1901,7 @@ __global__ __launch_bounds__(SA_THREADS, 2) void k_s_absorb(StreamParams S) {
     const DScene &sc = P.sc;
     const StreamWs &W = S.W;
     const int Sn = sc.n_surf;
-    if (W.cnt[CN(4)]) return;
+    if (W.cnt[CN(CW_OVERFLOW)]) return;
     DScene L = sc;
     L.tally = W.tally_part + (size_t)(blockIdx.x % TALLY_PARTS) * (size_t)W.tally_n;
     double *l_tally = lds;
@@ -1926,7 +1926,7 @@ __global__ __launch_bounds__(SA_THREADS, 2) void k_s_absorb(StreamParams S) {
     const uint32_t *t_slot = W.q1_slot;
     const uint32_t *t_surf = (const uint32_t *)W.q1_a;
     const double *t_t = (const double *)W.q1_b;
-    long long nh = (long long)W.cnt[CN(11)];
+    long long nh = (long long)W.cnt[CN(CW_TERM_LIST)];
     if (nh > SQ_ROOM(W)) nh = SQ_ROOM(W);
     const long long padded = (nh + 63) & ~63ll;
     // this wave's open chunk of the scene's hit buffer: the second half of the state array (k_s_shade's waves own the first)
@@ -1970,8 +1970,8 @@ __global__ __launch_bounds__(SA_THREADS, 2) void k_s_absorb(StreamParams S) {
         if (P.capture) chunk_rebroadcast(hc, __ffsll((long long)hit_lanes) - 1);
     }
     if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
-    // (CN(12): the host sizes the two lists of the batches to come by their shares)
-    flush_counts<false>(l_tally + 3 * Sn, n_hit, 0u, &W.cnt[CN(6)], &W.cnt[CN(12)], nullptr);
+    // (CN(CW_TERM_HITS): the host sizes the two lists of the batches to come by their shares)
+    flush_counts<false>(l_tally + 3 * Sn, n_hit, 0u, &W.cnt[CN(CW_HITS)], &W.cnt[CN(CW_TERM_HITS)], nullptr);
     flush_sums(L.tally, l_tally, 3 * Sn, l_fm, S.lds_fm_bins, Sn);
 }
 
@@ -1989,27 +1989,41 @@ __global__ void k_s_add2(double *p, double a, double b) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-static void stream_ws_free(StreamWs &W) {
-    for (int c = 0; c < 3; ++c) { dev_free(W.pl_slot[c]); dev_free(W.pl_surf[c]); dev_free(W.pl_t[c]); }
-    dev_free(W.geo); dev_free(W.aux);
-    dev_free(W.q1_slot); dev_free(W.q1_a); dev_free(W.q1_b); dev_free(W.q3_slot); dev_free(W.q3_surf); dev_free(W.q3n);
-    dev_free(W.hit_slot); dev_free(W.hit_surf); dev_free(W.hit_t); dev_free(W.gen_list); dev_free(W.fq_ray); dev_free(W.fq_cell); dev_free(W.act[0]); dev_free(W.act[1]); dev_free(W.cnt); dev_free(W.hit_state); dev_free(W.tally_part);
-    memset(&W, 0, sizeof(W));      // no dangling pointers: a failed re-allocation is followed by another free
-}
+// Owner of a slot's workspace: every array StreamWs points to, and the sizes, which describe only what is allocated.  The kernels
+// get view().
+struct StreamBuffers {
+    long long cap = 0, room = 0, q3_cap = 0, act_room = 0, pl_room = 0, tally_n = 0;      // (as in StreamWs)
+    DevBuf<SRayGeo> geo;
+    DevBuf<SRayAux> aux;
+    DevBuf<float4> q1_a, q1_b;
+    DevBuf<SCand> q3n;
+    DevBuf<uint32_t> q1_slot, q3_slot, q3_surf, hit_slot, hit_surf, gen_list, fq_ray, fq_cell, act[2], pl_slot[TRC_CLS_COUNT], pl_surf[TRC_CLS_COUNT];
+    DevBuf<double> hit_t, tally_part, pl_t[TRC_CLS_COUNT];
+    DevBuf<unsigned long long> hit_state, cnt;
 
-// doubles the candidate queue (contents are not kept: the bounce is run again)
-static int stream_q3_grow(StreamWs &W) {
-    const long long want = 2 * W.q3_cap;
-    if (want >= (1ll << 31)) return trc_fail(TRC_ERR_CAPACITY, "candidate queue cannot grow beyond 2^31 entries (ray records link candidates by 32-bit index)");
-    dev_free(W.q3_slot); dev_free(W.q3_surf); dev_free(W.q3n);
-    W.q3_slot = nullptr; W.q3_surf = nullptr; W.q3n = nullptr;
-    W.q3_cap = 0;
-    TRC_TRY(dev_alloc(&W.q3_slot, (size_t)want));
-    TRC_TRY(dev_alloc(&W.q3_surf, (size_t)want));
-    TRC_TRY(dev_alloc(&W.q3n, (size_t)want));
-    W.q3_cap = want;
-    return TRC_OK;
-}
+    StreamWs view() const {
+        StreamWs W;
+        W.cap = cap; W.room = room; W.q3_cap = q3_cap; W.act_room = act_room; W.pl_room = pl_room; W.tally_n = tally_n;
+        W.geo = geo.get(); W.aux = aux.get(); W.q1_slot = q1_slot.get(); W.q1_a = q1_a.get(); W.q1_b = q1_b.get();
+        W.q3_slot = q3_slot.get(); W.q3_surf = q3_surf.get(); W.q3n = q3n.get();
+        W.hit_slot = hit_slot.get(); W.hit_surf = hit_surf.get(); W.hit_t = hit_t.get();
+        W.gen_list = gen_list.get(); W.fq_ray = fq_ray.get(); W.fq_cell = fq_cell.get(); W.act[0] = act[0].get(); W.act[1] = act[1].get();
+        W.tally_part = tally_part.get(); W.hit_state = hit_state.get(); W.cnt = cnt.get();
+        for (int c = 0; c < TRC_CLS_COUNT; ++c) { W.pl_slot[c] = pl_slot[c].get(); W.pl_surf[c] = pl_surf[c].get(); W.pl_t[c] = pl_t[c].get(); }
+        return W;
+    }
+    // doubles the candidate queue (contents are not kept: the bounce is run again)
+    int grow_q3() {
+        const long long want = 2 * q3_cap;
+        if (want >= (1ll << 31)) return trc_fail(TRC_ERR_CAPACITY, "candidate queue cannot grow beyond 2^31 entries (ray records link candidates by 32-bit index)");
+        q3_cap = 0;
+        TRC_TRY(q3_slot.alloc((size_t)want));
+        TRC_TRY(q3_surf.alloc((size_t)want));
+        TRC_TRY(q3n.alloc((size_t)want));
+        q3_cap = want;
+        return TRC_OK;
+    }
+};
 
 #define STREAM_MAX_SLOTS 4
 // Environment knobs of the streaming engine: routes and capacities the tests compare and force.  trc_trace_fast reads them at every
@@ -2049,39 +2063,38 @@ static StreamKnobs stream_knobs() {
 
 #define STREAM_ACT_STATIC(cap) ((cap) + ((cap) >> 2) + (1ll << 23))      /* entries of an active list that pre-assigned chunks may take */
 
-static int stream_ws_alloc_queues(StreamWs &W, long long cap, long long want_q3, long long want_room, const StreamKnobs &K) {
+// the queues and lists of a workspace that has none, for batches of `cap` rays
+static int stream_ws_alloc_queues(StreamBuffers &W, long long cap, long long want_q3, long long want_room, const StreamKnobs &K) {
     const size_t cq = (size_t)want_room;   // (= SQ_ROOM)
-    W.room = want_room;
     // active lists: pre-assigned chunks for at most STREAM_ACT_STATIC(cap) entries, and behind them every ray of the batch through
     // further reservations, of which every wave may leave one chunk unused -- at most as much again (TRC_STREAM_ROOM: as the
     // other lists).  Whatever the shares of the classes turn out to be, the lists cannot overflow.
-    W.act_room = K.room ? want_room
-               : 2 * STREAM_ACT_STATIC(cap) + cap + (1ll << 20);
-    TRC_TRY(dev_alloc(&W.geo, cq));       // slots are handed out in chunks too
-    TRC_TRY(dev_alloc(&W.aux, cq));
-    TRC_TRY(dev_alloc(&W.q1_slot, cq));
-    TRC_TRY(dev_alloc(&W.q1_a, cq));
-    TRC_TRY(dev_alloc(&W.q1_b, cq));
-    W.q3_cap = want_q3;
-    TRC_TRY(dev_alloc(&W.q3_slot, (size_t)W.q3_cap));
-    TRC_TRY(dev_alloc(&W.q3_surf, (size_t)W.q3_cap));
-    TRC_TRY(dev_alloc(&W.q3n, (size_t)W.q3_cap));
-    TRC_TRY(dev_alloc(&W.hit_slot, cq));
-    TRC_TRY(dev_alloc(&W.hit_surf, cq));
-    TRC_TRY(dev_alloc(&W.hit_t, cq));
-    TRC_TRY(dev_alloc(&W.gen_list, cq));
-    TRC_TRY(dev_alloc(&W.fq_ray, cq));
-    TRC_TRY(dev_alloc(&W.fq_cell, cq));
-    TRC_TRY(dev_alloc(&W.act[0], (size_t)W.act_room));
-    TRC_TRY(dev_alloc(&W.act[1], (size_t)W.act_room));
-    TRC_TRY(dev_alloc(&W.cnt, CN_WORDS));
-    TRC_TRY(dev_alloc(&W.hit_state, 2 * SHADE_MAX_WAVES));        // (wave w of every shading kernel of the slot continues the chunk wave w left open)
-    HIP_TRY(hipMemset(W.hit_state, 0, 2 * SHADE_MAX_WAVES * sizeof(unsigned long long)));
-    W.cap = cap;
+    const long long act_room = K.room ? want_room
+                             : 2 * STREAM_ACT_STATIC(cap) + cap + (1ll << 20);
+    TRC_TRY(W.geo.alloc(cq));       // slots are handed out in chunks too
+    TRC_TRY(W.aux.alloc(cq));
+    TRC_TRY(W.q1_slot.alloc(cq));
+    TRC_TRY(W.q1_a.alloc(cq));
+    TRC_TRY(W.q1_b.alloc(cq));
+    TRC_TRY(W.q3_slot.alloc((size_t)want_q3));
+    TRC_TRY(W.q3_surf.alloc((size_t)want_q3));
+    TRC_TRY(W.q3n.alloc((size_t)want_q3));
+    TRC_TRY(W.hit_slot.alloc(cq));
+    TRC_TRY(W.hit_surf.alloc(cq));
+    TRC_TRY(W.hit_t.alloc(cq));
+    TRC_TRY(W.gen_list.alloc(cq));
+    TRC_TRY(W.fq_ray.alloc(cq));
+    TRC_TRY(W.fq_cell.alloc(cq));
+    TRC_TRY(W.act[0].alloc((size_t)act_room));
+    TRC_TRY(W.act[1].alloc((size_t)act_room));
+    TRC_TRY(W.cnt.alloc(CN_WORDS));
+    TRC_TRY(W.hit_state.alloc(2 * SHADE_MAX_WAVES));        // (wave w of every shading kernel of the slot continues the chunk wave w left open)
+    HIP_TRY(hipMemset(W.hit_state.get(), 0, 2 * SHADE_MAX_WAVES * sizeof(unsigned long long)));
+    W.cap = cap; W.room = want_room; W.q3_cap = want_q3; W.act_room = act_room;      // (last: a workspace half made claims nothing)
     return TRC_OK;
 }
 
-static int stream_ws_alloc(StreamWs &W, long long cap, int n_unbounded, long long tally_n, const StreamKnobs &K) {
+static int stream_ws_alloc(StreamBuffers &W, long long cap, int n_unbounded, long long tally_n, const StreamKnobs &K) {
     // candidate pairs per bounce: 4 per ray to start with (NSTTF needs 0.25); a bounce that overflows is run again with
     // twice the room.  TRC_STREAM_Q3_ENTRIES (tests) sets the initial capacity.
     long long want_q3 = (4 + (long long)n_unbounded) * cap + (long long)SQ_CHUNK_MAX * 16384;
@@ -2089,15 +2102,13 @@ static int stream_ws_alloc(StreamWs &W, long long cap, int n_unbounded, long lon
     long long want_room = cap + (long long)SQ_CHUNK_MAX * 16384;   // room for the invalid tails of every wave's last chunk
     if (K.room) want_room = K.room;      // tests: lists that overflow
     if (!(W.cap >= cap && W.q3_cap >= want_q3 && (K.room ? W.room == want_room : W.room >= want_room))) {
-        stream_ws_free(W);
+        W = StreamBuffers();      // the class lists and the private tallies go with the queues
         TRC_TRY(stream_ws_alloc_queues(W, cap, want_q3, want_room, K));
     }
     if (W.tally_n != tally_n || !W.tally_part) {      // flux maps may have been added since the last call
-        dev_free(W.tally_part);
-        W.tally_part = nullptr;
         W.tally_n = 0;
-        TRC_TRY(dev_alloc(&W.tally_part, (size_t)TALLY_PARTS * (size_t)tally_n));
-        HIP_TRY(hipMemset(W.tally_part, 0, (size_t)TALLY_PARTS * (size_t)tally_n * sizeof(double)));
+        TRC_TRY(W.tally_part.alloc((size_t)TALLY_PARTS * (size_t)tally_n));
+        HIP_TRY(hipMemset(W.tally_part.get(), 0, (size_t)TALLY_PARTS * (size_t)tally_n * sizeof(double)));
         W.tally_n = tally_n;
     }
     return TRC_OK;
@@ -2142,49 +2153,53 @@ static bool stream_plan(const trc_scene *sc, bool want_accel, const StreamKnobs 
 // arithmetic-bound kernels of one batch (generation, walk) share the device with the access-bound ones of the other
 // (exact tests, tie pass, shading).
 struct StreamSlot {
-    StreamWs W;
+    StreamBuffers W;
     DevBuf<double> spec;          // spectra of the rays under way (CarryIn.slot_spec), spec_len doubles; spec_on: this call brings spectra
-    long long spec_len;
-    bool spec_on;
-    hipStream_t stream;
-    hipEvent_t done;
-    unsigned long long *h_cnt;    // pinned: CN_WORDS counters read back, then CN_WORDS counters to upload
-    StreamParams SP;
-    long long base, nb, n_in;
-    unsigned long long n_act;
-    int b, cur, attempt;
-    unsigned gb_wide, gb_gen, gb_walk, gb_cull, gb_fresh, gb_bounce;    // grids of the bounce being run
-    unsigned gb_sh[TRC_CLS_COUNT];            // ... of the shading kernels of the classes present
-    unsigned chunk_act_sh[TRC_CLS_COUNT];     // entries of the active list pre-assigned to every wave of each
-    long long act_base_sh[TRC_CLS_COUNT];     // ... and where its chunks start
-    unsigned gb_part;                         // grid of k_s_partition (0: one shading class, the hit list is walked as it is)
-    unsigned long long part_start[TRC_CLS_COUNT];   // entries of each class list that are pre-assigned to the waves of k_s_partition
-    unsigned cull_chunk;      // entries of the footprint list pre-assigned to every wave of k_s_cull
-    unsigned cull_gen_chunk;  // ... and of the general-path list (0: collected per workgroup, see CullParams)
-    bool fresh, general, fused, first;     // first: k_s_bounce<.., FRESH> takes the fresh rays outside the footprint map
-    unsigned gb_first;      // this bounce: k_s_fresh generates the rays / the general path (gen, walk, exact) runs / k_s_bounce searches
-    bool busy;
+    long long spec_len = 0;
+    bool spec_on = false;
+    StreamHandle stream;          // slot 0 borrows the context's stream, which is not this slot's to destroy; the others own theirs
+    EventHandle done;
+    PinnedWords h_cnt;            // pinned: CN_WORDS counters read back, then CN_WORDS counters to upload
+    StreamParams SP;              // (assigned by start_batch)
+    long long base = 0, nb = 0, n_in = 0;
+    unsigned long long n_act = 0;
+    int b = 0, cur = 0, attempt = 0;
+    unsigned gb_wide = 0, gb_gen = 0, gb_walk = 0, gb_cull = 0, gb_fresh = 0, gb_bounce = 0;    // grids of the bounce being run
+    unsigned gb_sh[TRC_CLS_COUNT] = {};            // ... of the shading kernels of the classes present
+    unsigned chunk_act_sh[TRC_CLS_COUNT] = {};     // entries of the active list pre-assigned to every wave of each
+    long long act_base_sh[TRC_CLS_COUNT] = {};     // ... and where its chunks start
+    unsigned gb_part = 0;                          // grid of k_s_partition (0: one shading class, the hit list is walked as it is)
+    unsigned long long part_start[TRC_CLS_COUNT] = {};   // entries of each class list that are pre-assigned to the waves of k_s_partition
+    unsigned cull_chunk = 0;      // entries of the footprint list pre-assigned to every wave of k_s_cull
+    unsigned cull_gen_chunk = 0;  // ... and of the general-path list (0: collected per workgroup, see CullParams)
+    bool fresh = false, general = false, fused = false, first = false;     // first: k_s_bounce<.., FRESH> takes the fresh rays outside the footprint map
+    unsigned gb_first = 0;  // this bounce: k_s_fresh generates the rays / the general path (gen, walk, exact) runs / k_s_bounce searches
+    bool busy = false;
 };
 
 #define STREAM_SMALL_SURFACES 24    /* scenes up to this many surfaces are searched surface by surface (k_s_bounce<3>) */
 struct StreamEngine {
     StreamSlot slot[STREAM_MAX_SLOTS];
-    bool ready;
+    bool ready = false;        // the slots have their streams, events and pinned blocks
     // footprint map of the last source traced on this scene (trc_footprint.h): rebuilt when the source or the poses change
-    trc_fp_host *fp;
-    unsigned char fp_key[sizeof(int32_t) + (3 + 9 + 9 + 8) * sizeof(double)];
-    uint64_t fp_geom_version;
-    bool fp_valid;
-    double fp_hit_rate;        // hits per fresh ray measured on the batches traced with this map (0: not yet), + margin: sizes the chunks
+    std::unique_ptr<trc_fp_host> fp;
+    unsigned char fp_key[sizeof(int32_t) + (3 + 9 + 9 + 8) * sizeof(double)] = {};
+    uint64_t fp_geom_version = 0;
+    bool fp_valid = false;
+    double fp_hit_rate = 0.0;  // hits per fresh ray measured on the batches traced with this map (0: not yet), + margin: sizes the chunks
     // k_s_bounce's two lists: hits per ray entering bounce b on surfaces that end the ray / on the others, measured on the batches
     // before (+ margin; < 0: not yet -- every ray may hit).  A list sized for every ray but filled by 3 % of them costs k_s_shade
     // 0.1 ms of walking over invalid entries.
 #define STREAM_RATE_BOUNCES 8
     double rate_term[STREAM_RATE_BOUNCES], rate_other[STREAM_RATE_BOUNCES];
     double rate_cls[STREAM_RATE_BOUNCES][TRC_CLS_COUNT];   // hits per ray entering bounce b that each shading class took (< 0: not yet)
-    uint64_t rate_geom_version;
+    uint64_t rate_geom_version = 0;      // the pose the rates were measured on
     DevBuf<uint32_t> d_fp_mask, d_fp_coff;
     DevBuf<uint32_t> d_fp_clist;
+
+    void forget_rates() {      // not measured yet
+        for (int b = 0; b < STREAM_RATE_BOUNCES; ++b) { rate_term[b] = rate_other[b] = -1.0; for (int c = 0; c < TRC_CLS_COUNT; ++c) rate_cls[b][c] = -1.0; }
+    }
 };
 
 // the part of a source descriptor the footprint map depends on (the Buie table enters through p[] / the CSR only via cdf_end,
@@ -2206,7 +2221,7 @@ static int stream_fp_prepare(trc_scene *sc, StreamEngine &E, const trc_source_de
     stream_fp_key(*src, key);
     const bool buie = src->kind == TRC_SRC_BUIE_DISK || src->kind == TRC_SRC_BUIE_RECT;
     const double cdf_end = buie ? src->buie[2 * (TRC_BUIE_NELEM + 1) + TRC_BUIE_NELEM] : 0.0;
-    if (!E.fp) { E.fp = new (std::nothrow) trc_fp_host(); if (!E.fp) return trc_fail(TRC_ERR_NOMEM, "out of host memory"); E.fp_valid = false; }
+    if (!E.fp) { E.fp.reset(new (std::nothrow) trc_fp_host()); if (!E.fp) return trc_fail(TRC_ERR_NOMEM, "out of host memory"); E.fp_valid = false; }
     if (!(E.fp_valid && E.fp_geom_version == sc->geom_version && memcmp(key, E.fp_key, sizeof(key)) == 0 && (!buie || E.fp->P.cdf_end == cdf_end))) {
         int M = sc->n_surf > 4096 ? 1024 : 512;       // (a mesh of small faces: finer cells, fewer faces listed per cell; the mask still fits k_s_cull's LDS)
         const bool forced = K.fp_cells > 0;
@@ -2241,27 +2256,21 @@ static int stream_fp_prepare(trc_scene *sc, StreamEngine &E, const trc_source_de
     return TRC_OK;
 }
 
-static void stream_engine_free(StreamEngine *E) {
-    if (!E) return;
-    for (int k = 0; k < STREAM_MAX_SLOTS; ++k) {
-        stream_ws_free(E->slot[k].W);
-        if (E->slot[k].h_cnt) (void)hipHostFree(E->slot[k].h_cnt);
-        if (E->slot[k].done) (void)hipEventDestroy(E->slot[k].done);
-        if (k >= 1 && E->slot[k].stream) (void)hipStreamDestroy(E->slot[k].stream);
-    }
-    delete E->fp;
-    delete E;
-}
-
+// streams, events and pinned counter blocks of the slots, made once
 static int stream_engine_init(StreamEngine *E, trc_ctx *ctx) {
-    if (!E->ready) { for (int b = 0; b < STREAM_RATE_BOUNCES; ++b) { E->rate_term[b] = E->rate_other[b] = -1.0; for (int c = 0; c < TRC_CLS_COUNT; ++c) E->rate_cls[b][c] = -1.0; } E->rate_geom_version = 0; }
     if (E->ready) return TRC_OK;
+    E->forget_rates();
     for (int k = 0; k < STREAM_MAX_SLOTS; ++k) {
         StreamSlot &T = E->slot[k];
-        if (k == 0) T.stream = ctx->stream;
-        else HIP_TRY(hipStreamCreateWithFlags(&T.stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&T.done, hipEventDisableTiming));
-        HIP_TRY(hipHostMalloc((void **)&T.h_cnt, 2 * CN_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
+        hipStream_t st;
+        hipEvent_t ev;
+        unsigned long long *h;
+        if (k == 0) T.stream.borrow(ctx->stream);
+        else { HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); T.stream.own(st); }
+        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        T.done.own(ev);
+        HIP_TRY(hipHostMalloc((void **)&h, 2 * CN_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
+        T.h_cnt.own(h);
     }
     E->ready = true;
     return TRC_OK;
@@ -2573,15 +2582,15 @@ static int stream_slots_alloc(StreamEngine &E, int n_slots, long long cap, const
             Tk.spec_len = want;
         }
         Tk.spec_on = want > 0;
-        StreamWs &Wk = Tk.W;
+        StreamBuffers &Wk = Tk.W;
         if (!F.multi) continue;
         Wk.pl_room = 2 * Wk.room;
         for (int q = 0; q < F.n_shk; ++q) {
             const int c = F.shk[q].cls;
-            if (Wk.pl_slot[c]) continue;
-            TRC_TRY(dev_alloc(&Wk.pl_slot[c], (size_t)Wk.pl_room));
-            TRC_TRY(dev_alloc(&Wk.pl_surf[c], (size_t)Wk.pl_room));
-            TRC_TRY(dev_alloc(&Wk.pl_t[c], (size_t)Wk.pl_room));
+            if (Wk.pl_t[c]) continue;      // (the last of the three made: a list half made is made again)
+            TRC_TRY(Wk.pl_slot[c].alloc((size_t)Wk.pl_room));
+            TRC_TRY(Wk.pl_surf[c].alloc((size_t)Wk.pl_room));
+            TRC_TRY(Wk.pl_t[c].alloc((size_t)Wk.pl_room));
         }
     }
     return TRC_OK;
@@ -2728,7 +2737,7 @@ static void plan_bounce(const StreamCall &C, StreamSlot &T) {
     T.SP.bounce_no = T.b;
     T.SP.static_general = C.K.static_chunks && !T.fresh;      // few rays behind k_s_cull: their kernels reserve as they go
     T.SP.q3_gen_chunk0 = (T.SP.static_general && T.b > 0) ? (long long)T.gb_walk * (SW_THREADS / 64) : -1;
-    T.SP.gen_list = T.fresh ? T.W.gen_list : nullptr;
+    T.SP.gen_list = T.fresh ? T.SP.W.gen_list : nullptr;
     T.SP.slot_base0 = T.fresh ? (long long)T.gb_fresh * (sf_threads / 64) * (long long)T.SP.chunk_slot : 0;
     T.SP.hit_base0 = T.fresh ? (long long)T.gb_fresh * (sf_threads / 64) * (long long)T.SP.chunk_hit
                              : (T.fused ? (long long)T.gb_bounce * (sb_threads / 64) * (long long)T.SP.chunk_hit : 0);
@@ -2744,60 +2753,60 @@ static int launch_kernel(const StreamKernel &k, unsigned grid, StreamParams &SP,
 static int launch_bounce(StreamCall &C, StreamSlot &T) {
     const StreamForms &F = C.F;
     StreamParams &SP = T.SP;
-    SP.act_out = T.W.act[T.cur];
+    SP.act_out = SP.W.act[T.cur];
     if (T.fresh) {
         CullParams CP;
         CP.F = SP.fp.P; CP.mask = SP.fp.mask; CP.seed = SP.P.seed; CP.rid0 = SP.P.ray_offset + (unsigned long long)T.base; CP.nb = T.nb;
-        CP.fq_ray = T.W.fq_ray; CP.fq_cell = T.W.fq_cell; CP.gen_list = T.W.gen_list; CP.cnt = T.W.cnt;
-        CP.room = T.W.room; CP.chunk = T.cull_chunk; CP.gen_chunk = T.cull_gen_chunk; CP.static_first = SP.static_first;
+        CP.fq_ray = SP.W.fq_ray; CP.fq_cell = SP.W.fq_cell; CP.gen_list = SP.W.gen_list; CP.cnt = SP.W.cnt;
+        CP.room = SP.W.room; CP.chunk = T.cull_chunk; CP.gen_chunk = T.cull_gen_chunk; CP.static_first = SP.static_first;
         void *cargs[] = {(void *)&CP};
-        HIP_TRY(hipLaunchKernel(F.cull.fn, dim3(T.gb_cull), dim3(F.cull.threads), cargs, F.cull.lds, T.stream));
+        HIP_TRY(hipLaunchKernel(F.cull.fn, dim3(T.gb_cull), dim3(F.cull.threads), cargs, F.cull.lds, T.stream.get()));
         // the two-phase form pays where most listed rays miss (a field of mirrors: two of three); where most of them hit (a dish
         // under its own source: the first phase rejects nothing) the batches after the first go back to k_s_fresh
         const bool mostly_hits = C.E.fp_hit_rate > 0.0 && C.E.fp_hit_rate > 0.6 * 1.15 * F.listed_share;
-        TRC_TRY(launch_kernel(mostly_hits ? F.fresh_one : F.fresh, T.gb_fresh, SP, T.stream));
+        TRC_TRY(launch_kernel(mostly_hits ? F.fresh_one : F.fresh, T.gb_fresh, SP, T.stream.get()));
         C.launches += 2;
     }
-    if (T.fused) { TRC_TRY(launch_kernel(F.bounce, T.gb_bounce, SP, T.stream)); C.launches += 1; }
-    if (T.first) { TRC_TRY(launch_kernel(F.first, T.gb_first, SP, T.stream)); C.launches += 1; }
+    if (T.fused) { TRC_TRY(launch_kernel(F.bounce, T.gb_bounce, SP, T.stream.get())); C.launches += 1; }
+    if (T.first) { TRC_TRY(launch_kernel(F.first, T.gb_first, SP, T.stream.get())); C.launches += 1; }
     if (T.general) {
         const int src_kind = F.src_kind;
         const unsigned gb_gen = T.gb_gen;
-        if (T.b == 0 && src_kind == TRC_SRC_BUIE_DISK) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_BUIE_DISK>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
-        else if (T.b == 0 && src_kind == TRC_SRC_BUIE_RECT) hipLaunchKernelGGL((k_s_gen<true, TRC_SRC_BUIE_RECT>), dim3(gb_gen), dim3(256), 0, T.stream, SP);
-        else if (T.b == 0 && src_kind == TRC_SRC_PILLBOX_DISK) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_PILLBOX_DISK>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
-        else if (T.b == 0 && src_kind == TRC_SRC_PILLBOX_RECT) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_PILLBOX_RECT>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
-        else if (T.b == 0 && src_kind == TRC_SRC_SUNSHAPE_DISK) hipLaunchKernelGGL((k_s_gen<true, TRC_SRC_SUNSHAPE_DISK>), dim3(gb_gen), dim3(256), 0, T.stream, SP);
-        else if (T.b == 0 && src_kind == TRC_SRC_SUNSHAPE_RECT) hipLaunchKernelGGL((k_s_gen<true, TRC_SRC_SUNSHAPE_RECT>), dim3(gb_gen), dim3(256), 0, T.stream, SP);
-        else if (T.b == 0) hipLaunchKernelGGL(k_s_gen<true>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
-        else hipLaunchKernelGGL(k_s_gen<false>, dim3(gb_gen), dim3(256), 0, T.stream, SP);
-        TRC_TRY(launch_kernel(F.walk, T.gb_walk, SP, T.stream));
-        hipLaunchKernelGGL(k_s_exact, dim3(T.gb_wide), dim3(256), F.lds_exact, T.stream, SP);
+        if (T.b == 0 && src_kind == TRC_SRC_BUIE_DISK) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_BUIE_DISK>, dim3(gb_gen), dim3(256), 0, T.stream.get(), SP);
+        else if (T.b == 0 && src_kind == TRC_SRC_BUIE_RECT) hipLaunchKernelGGL((k_s_gen<true, TRC_SRC_BUIE_RECT>), dim3(gb_gen), dim3(256), 0, T.stream.get(), SP);
+        else if (T.b == 0 && src_kind == TRC_SRC_PILLBOX_DISK) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_PILLBOX_DISK>, dim3(gb_gen), dim3(256), 0, T.stream.get(), SP);
+        else if (T.b == 0 && src_kind == TRC_SRC_PILLBOX_RECT) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_PILLBOX_RECT>, dim3(gb_gen), dim3(256), 0, T.stream.get(), SP);
+        else if (T.b == 0 && src_kind == TRC_SRC_SUNSHAPE_DISK) hipLaunchKernelGGL((k_s_gen<true, TRC_SRC_SUNSHAPE_DISK>), dim3(gb_gen), dim3(256), 0, T.stream.get(), SP);
+        else if (T.b == 0 && src_kind == TRC_SRC_SUNSHAPE_RECT) hipLaunchKernelGGL((k_s_gen<true, TRC_SRC_SUNSHAPE_RECT>), dim3(gb_gen), dim3(256), 0, T.stream.get(), SP);
+        else if (T.b == 0) hipLaunchKernelGGL(k_s_gen<true>, dim3(gb_gen), dim3(256), 0, T.stream.get(), SP);
+        else hipLaunchKernelGGL(k_s_gen<false>, dim3(gb_gen), dim3(256), 0, T.stream.get(), SP);
+        TRC_TRY(launch_kernel(F.walk, T.gb_walk, SP, T.stream.get()));
+        hipLaunchKernelGGL(k_s_exact, dim3(T.gb_wide), dim3(256), F.lds_exact, T.stream.get(), SP);
         C.launches += 3;
     }
-    if (F.multi) { TRC_TRY(launch_kernel({(const void *)k_s_partition, 256, 0, F.g_wide}, T.gb_part, SP, T.stream)); C.launches += 1; }
+    if (F.multi) { TRC_TRY(launch_kernel({(const void *)k_s_partition, 256, 0, F.g_wide}, T.gb_part, SP, T.stream.get())); C.launches += 1; }
     for (int k = 0; k < F.n_shk; ++k) {
         const StreamShadeK &K = F.shk[k];
         StreamParams SK = SP;
         SK.shade_cls = K.cls;
         if (F.multi) {
-            SK.hl_slot = T.W.pl_slot[K.cls]; SK.hl_surf = T.W.pl_surf[K.cls]; SK.hl_t = T.W.pl_t[K.cls]; SK.hl_room = T.W.pl_room; SK.hl_cn = CN(24 + K.cls);
+            SK.hl_slot = SP.W.pl_slot[K.cls]; SK.hl_surf = SP.W.pl_surf[K.cls]; SK.hl_t = SP.W.pl_t[K.cls]; SK.hl_room = SP.W.pl_room; SK.hl_cn = CN(CW_CLS_LIST + K.cls);
         } else {
-            SK.hl_slot = T.W.hit_slot; SK.hl_surf = T.W.hit_surf; SK.hl_t = T.W.hit_t; SK.hl_room = T.W.room; SK.hl_cn = CN(2);
+            SK.hl_slot = SP.W.hit_slot; SK.hl_surf = SP.W.hit_surf; SK.hl_t = SP.W.hit_t; SK.hl_room = SP.W.room; SK.hl_cn = CN(CW_HIT_LIST);
         }
         SK.chunk_act = T.chunk_act_sh[k];
         SK.act_base0 = T.act_base_sh[k];
         SK.lds_tables = K.lds_tables; SK.lds_extra = K.lds_tables; SK.lds_fm_bins = K.lds_fm_bins;
         void *args[] = {(void *)&SK};
-        HIP_TRY(hipLaunchKernel(K.fn, dim3(T.gb_sh[k]), dim3(K.threads), args, K.lds, T.stream));
+        HIP_TRY(hipLaunchKernel(K.fn, dim3(T.gb_sh[k]), dim3(K.threads), args, K.lds, T.stream.get()));
         C.launches += 1;
     }
     if (T.fused && SP.split_terminal == 1) {
-        TRC_TRY(launch_kernel(F.absorb, clamp_grid(((long long)T.n_act + SA_THREADS * 2 - 1) / (SA_THREADS * 2), F.absorb.max_blocks), SP, T.stream));
+        TRC_TRY(launch_kernel(F.absorb, clamp_grid(((long long)T.n_act + SA_THREADS * 2 - 1) / (SA_THREADS * 2), F.absorb.max_blocks), SP, T.stream.get()));
         C.launches += 1;
     }
-    HIP_TRY(hipMemcpyAsync(T.h_cnt, T.W.cnt, CN_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, T.stream));
-    HIP_TRY(hipEventRecord(T.done, T.stream));
+    HIP_TRY(hipMemcpyAsync(T.h_cnt.get(), SP.W.cnt, CN_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, T.stream.get()));
+    HIP_TRY(hipEventRecord(T.done.get(), T.stream.get()));
     return TRC_OK;
 }
 
@@ -2806,30 +2815,30 @@ static int launch_bounce(StreamCall &C, StreamSlot &T) {
 static int upload_counters(const StreamCall &C, StreamSlot &T) {
     const StreamForms &F = C.F;
     plan_bounce(C, T);
-    unsigned long long *up = T.h_cnt + CN_WORDS;
+    unsigned long long *up = T.h_cnt.get() + CN_WORDS;
     for (int i = 0; i < CN_WORDS; ++i) up[i] = 0ull;
-    up[CN(5)] = T.n_act;
+    up[CN(CW_ACT_IN)] = T.n_act;
     if (T.SP.static_first) {       // the first chunk of every appending wave is pre-assigned: the lists start behind them
         // (a kernel that is not launched never closes its pre-assigned chunks: it must not be given any)
         const unsigned long long cull_waves = T.fresh ? (unsigned long long)T.gb_cull * (SC_THREADS / 64) : 0ull;
         const bool sg = T.SP.static_general != 0 && T.general;
         if (sg) {
-            up[CN(0)] = (unsigned long long)T.gb_gen * 4ull * T.SP.chunk_q1;                           // Q1 <- k_s_gen
-            up[CN(1)] = ((unsigned long long)T.gb_walk * (unsigned long long)(SW_THREADS / 64) +
+            up[CN(CW_Q1)] = (unsigned long long)T.gb_gen * 4ull * T.SP.chunk_q1;                           // Q1 <- k_s_gen
+            up[CN(CW_Q3)] = ((unsigned long long)T.gb_walk * (unsigned long long)(SW_THREADS / 64) +
                          (T.SP.q3_gen_chunk0 >= 0 ? (unsigned long long)T.gb_gen * 4ull : 0ull)) * T.SP.chunk_q3;   // Q3 <- k_s_walk (+ k_s_gen<false>)
         }
         const unsigned long long first_entries = T.first ? (unsigned long long)T.gb_first * (F.first.threads / 64) * T.SP.chunk_first : 0ull;
-        up[CN(2)] = (unsigned long long)T.SP.hit_base0 + (sg ? (unsigned long long)T.gb_wide * 4ull * SQ_CHUNK : 0ull) + first_entries;   // hit list <- k_s_fresh / k_s_bounce, k_s_exact / k_s_bounce<FRESH>
-        for (int c = 0; c < TRC_CLS_COUNT; ++c) up[CN(24 + c)] = T.part_start[c];                      // class lists <- k_s_partition
+        up[CN(CW_HIT_LIST)] = (unsigned long long)T.SP.hit_base0 + (sg ? (unsigned long long)T.gb_wide * 4ull * SQ_CHUNK : 0ull) + first_entries;   // hit list <- k_s_fresh / k_s_bounce, k_s_exact / k_s_bounce<FRESH>
+        for (int c = 0; c < TRC_CLS_COUNT; ++c) up[CN(CW_CLS_LIST + c)] = T.part_start[c];                      // class lists <- k_s_partition
         unsigned long long a = 0;                                                                      // active list <- the shading kernels
         for (int k = 0; k < F.n_shk; ++k) a += (unsigned long long)T.gb_sh[k] * F.shk[k].wpb * T.chunk_act_sh[k];
-        up[CN(3)] = a;
-        up[CN(8)] = (unsigned long long)T.SP.slot_base0 + ((sg && T.b == 0) ? (unsigned long long)T.gb_gen * 4ull * SQ_CHUNK : 0ull) + first_entries;   // slots <- k_s_fresh, k_s_gen<true> / k_s_bounce<FRESH>
-        up[CN(9)] = cull_waves * (unsigned long long)T.cull_gen_chunk;                                 // general-path list <- k_s_cull
-        up[CN(10)] = cull_waves * (unsigned long long)T.cull_chunk;                                   // footprint list <- k_s_cull
-        if (T.fused && T.SP.split_terminal == 1) up[CN(11)] = (unsigned long long)T.gb_bounce * (unsigned long long)(F.bounce.threads / 64) * T.SP.chunk_thit;   // terminal hits <- k_s_bounce
+        up[CN(CW_ACT_OUT)] = a;
+        up[CN(CW_SLOTS)] = (unsigned long long)T.SP.slot_base0 + ((sg && T.b == 0) ? (unsigned long long)T.gb_gen * 4ull * SQ_CHUNK : 0ull) + first_entries;   // slots <- k_s_fresh, k_s_gen<true> / k_s_bounce<FRESH>
+        up[CN(CW_GEN_LIST)] = cull_waves * (unsigned long long)T.cull_gen_chunk;                                 // general-path list <- k_s_cull
+        up[CN(CW_FP_LIST)] = cull_waves * (unsigned long long)T.cull_chunk;                                   // footprint list <- k_s_cull
+        if (T.fused && T.SP.split_terminal == 1) up[CN(CW_TERM_LIST)] = (unsigned long long)T.gb_bounce * (unsigned long long)(F.bounce.threads / 64) * T.SP.chunk_thit;   // terminal hits <- k_s_bounce
     }
-    HIP_TRY(hipMemcpyAsync(T.W.cnt, up, CN_WORDS * sizeof(unsigned long long), hipMemcpyHostToDevice, T.stream));
+    HIP_TRY(hipMemcpyAsync(T.SP.W.cnt, up, CN_WORDS * sizeof(unsigned long long), hipMemcpyHostToDevice, T.stream.get()));
     return TRC_OK;
 }
 
@@ -2839,7 +2848,7 @@ static int start_batch(StreamCall &C, StreamSlot &T, long long base) {
     T.nb = (n - base < C.cap) ? (n - base) : C.cap;
     T.n_in = T.nb; T.n_act = 0; T.b = 0; T.cur = 0; T.attempt = 0; T.busy = true;
     T.SP = C.SP0;
-    T.SP.W = T.W;
+    T.SP.W = T.W.view();
     T.SP.carry.slot_spec = T.spec_on ? T.spec.get() : nullptr;
     T.SP.base = base;
     T.SP.nb = T.nb;
@@ -2850,31 +2859,31 @@ static int start_batch(StreamCall &C, StreamSlot &T, long long base) {
 // called when the slot's last launch has completed: takes in its counters and launches its next bounce, if any
 static int advance(StreamCall &C, StreamSlot &T) {
     StreamEngine &E = C.E;
-    const unsigned long long *c = T.h_cnt;
+    const unsigned long long *c = T.h_cnt.get();
 #ifdef SW_STATS
     fprintf(stderr, "batch %lld bounce %d: Q1 %llu Q3 %llu hits %llu | walkers %llu wave-iters %llu steps %llu leaf-entries %llu box-tests %llu drains %llu drain-rounds %llu\n",
-            T.base / C.cap, T.b, c[CN(0)], c[CN(1)], c[CN(6)], c[CN(16)], c[CN(17)], c[CN(18)], c[CN(19)], c[CN(20)], c[CN(21)], c[CN(22)]);
+            T.base / C.cap, T.b, c[CN(CW_Q1)], c[CN(CW_Q3)], c[CN(CW_HITS)], c[CN(CW_STATS)], c[CN(CW_STATS + 1)], c[CN(CW_STATS + 2)], c[CN(CW_STATS + 3)], c[CN(CW_STATS + 4)], c[CN(CW_STATS + 5)], c[CN(CW_STATS + 6)]);
 #endif
-    if (c[CN(4)]) {
+    if (c[CN(CW_OVERFLOW)]) {
         // The candidate queue was too small for this bounce.  Nothing of the bounce has been committed (k_s_exact,
         // k_s_shade returns at once when the flag is set): double the queue and run the bounce again.
-        if (c[CN(4)] != 1ull || T.attempt >= 6) return trc_fail(TRC_ERR_CAPACITY, "streaming queues overflow (%llu candidate pairs, capacity %lld)", c[CN(1)], T.W.q3_cap);
+        if (c[CN(CW_OVERFLOW)] != CW_OVF_RETRY || T.attempt >= 6) return trc_fail(TRC_ERR_CAPACITY, "streaming queues overflow (%llu candidate pairs, capacity %lld)", c[CN(CW_Q3)], T.W.q3_cap);
         ++T.attempt;
-        TRC_TRY(stream_q3_grow(T.W));
-        T.SP.W = T.W;
+        TRC_TRY(T.W.grow_q3());
+        T.SP.W = T.W.view();
         TRC_TRY(upload_counters(C, T));
         return launch_bounce(C, T);
     }
     T.attempt = 0;
     C.seg += (double)T.n_in;
-    C.hits += (double)c[CN(6)];
+    C.hits += (double)c[CN(CW_HITS)];
     if (T.fresh && T.nb > 0) {       // what the next batches can expect (with a margin; a low guess only costs atomics)
-        const double rate = 1.15 * (double)c[CN(6)] / (double)T.nb + 256.0 / (double)T.nb;
+        const double rate = 1.15 * (double)c[CN(CW_HITS)] / (double)T.nb + 256.0 / (double)T.nb;
         if (rate > E.fp_hit_rate || E.fp_hit_rate > 2.0 * rate) E.fp_hit_rate = rate;
     }
-    if (T.fused && T.b < STREAM_RATE_BOUNCES && T.n_in > 0) {       // (without the split CN(12) stays 0: every hit is on the one list)
+    if (T.fused && T.b < STREAM_RATE_BOUNCES && T.n_in > 0) {       // (without the split CN(CW_TERM_HITS) stays 0: every hit is on the one list)
         const double nin = (double)T.n_in, pad = 512.0 / nin;
-        const double rt = 1.15 * (double)c[CN(12)] / nin + pad, ro = 1.15 * (double)(c[CN(6)] - c[CN(12)]) / nin + pad;
+        const double rt = 1.15 * (double)c[CN(CW_TERM_HITS)] / nin + pad, ro = 1.15 * (double)(c[CN(CW_HITS)] - c[CN(CW_TERM_HITS)]) / nin + pad;
         if (E.rate_term[T.b] < 0.0 || rt > E.rate_term[T.b] || E.rate_term[T.b] > 2.0 * rt) E.rate_term[T.b] = rt > 1.0 ? 1.0 : rt;
         if (E.rate_other[T.b] < 0.0 || ro > E.rate_other[T.b] || E.rate_other[T.b] > 2.0 * ro) E.rate_other[T.b] = ro > 1.0 ? 1.0 : ro;
     }
@@ -2882,18 +2891,18 @@ static int advance(StreamCall &C, StreamSlot &T) {
         const double rin = T.b == 0 ? (double)T.nb : (double)T.n_in;
         if (rin > 0.0)
             for (int cl = 0; cl < TRC_CLS_COUNT; ++cl) {
-                const double r = 1.15 * (double)c[CN(13 + cl)] / rin + 512.0 / rin;
+                const double r = 1.15 * (double)c[CN(CW_CLS_HITS + cl)] / rin + 512.0 / rin;
                 double &R = E.rate_cls[T.b][cl];
                 if (R < 0.0 || r > R || R > 2.0 * r) R = r;
-                C.cls_hits[cl] += (double)c[CN(13 + cl)];
+                C.cls_hits[cl] += (double)c[CN(CW_CLS_HITS + cl)];
             }
     }
     if (T.b + 1 > C.max_bounces) C.max_bounces = T.b + 1;
-    if (c[CN(7)] == 0 || T.b + 1 >= C.SP0.P.reps) { T.busy = false; return TRC_OK; }
+    if (c[CN(CW_ALIVE)] == 0 || T.b + 1 >= C.SP0.P.reps) { T.busy = false; return TRC_OK; }
     // next bounce: the rays just shaded are the active list
-    T.n_act = c[CN(3)];                                       // its reserved entries (the tail of the last chunks is invalid)
-    T.n_in = (long long)c[CN(7)];
-    T.SP.act_in = T.W.act[T.cur];
+    T.n_act = c[CN(CW_ACT_OUT)];                                       // its reserved entries (the tail of the last chunks is invalid)
+    T.n_in = (long long)c[CN(CW_ALIVE)];
+    T.SP.act_in = T.SP.W.act[T.cur];
     T.cur ^= 1;
     T.b += 1;
     TRC_TRY(upload_counters(C, T));
@@ -2915,7 +2924,7 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, c
     if (cap < 64) cap = 64;
     TRC_TRY(stream_engine_init(&E, ctx));
     if (E.rate_geom_version != sc->geom_version) {       // another pose of the scene: measured again
-        for (int b = 0; b < STREAM_RATE_BOUNCES; ++b) { E.rate_term[b] = E.rate_other[b] = -1.0; for (int c = 0; c < TRC_CLS_COUNT; ++c) E.rate_cls[b][c] = -1.0; }
+        E.forget_rates();
         E.rate_geom_version = sc->geom_version;
     }
     // rays that carry more than the fast engine's record -- Im of a complex index, materials at their wavelength, a spectrum -- are
@@ -2931,7 +2940,7 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, c
 
     for (int k = 0; k < STREAM_MAX_SLOTS; ++k) E.slot[k].busy = false;
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    for (int k = 1; k < n_slots; ++k) HIP_TRY(hipStreamWaitEvent(E.slot[k].stream, ctx->ev0, 0));   // inputs were staged on the context's stream
+    for (int k = 1; k < n_slots; ++k) HIP_TRY(hipStreamWaitEvent(E.slot[k].stream.get(), ctx->ev0, 0));   // inputs were staged on the context's stream
     long long next_base = 0;
     int turn = 0;
     int rc = TRC_OK;
@@ -2948,21 +2957,21 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, c
             const int q = (turn + j) % n_slots;
             if (!E.slot[q].busy) continue;
             if (k < 0) k = q;
-            if (hipEventQuery(E.slot[q].done) == hipSuccess) { k = q; break; }
+            if (hipEventQuery(E.slot[q].done.get()) == hipSuccess) { k = q; break; }
         }
-        hipError_t se = hipEventSynchronize(E.slot[k].done);
+        hipError_t se = hipEventSynchronize(E.slot[k].done.get());
         if (se != hipSuccess) { rc = trc_fail(TRC_ERR_DEVICE, "streaming bounce failed: %s", hipGetErrorString(se)); break; }
         rc = advance(C, E.slot[k]);
         if (rc != TRC_OK) break;
         turn = (k + 1) % n_slots;
     }
     // drain both streams whatever happened, then close the timed region on the context's stream
-    for (int k = 0; k < n_slots; ++k) (void)hipStreamSynchronize(E.slot[k].stream);
+    for (int k = 0; k < n_slots; ++k) (void)hipStreamSynchronize(E.slot[k].stream.get());
     if (rc != TRC_OK) {
         // what the bounces that did complete have added to the private tallies must not reach the scene with a later call; the
         // caller (trc_trace_fast) winds the hit buffer back, which leaves the chunks they opened in it stale
         for (int k = 0; k < n_slots; ++k)
-            if (E.slot[k].W.tally_part) (void)hipMemset(E.slot[k].W.tally_part, 0, (size_t)TALLY_PARTS * (size_t)E.slot[k].W.tally_n * sizeof(double));
+            if (E.slot[k].W.tally_part) (void)hipMemset(E.slot[k].W.tally_part.get(), 0, (size_t)TALLY_PARTS * (size_t)E.slot[k].W.tally_n * sizeof(double));
         return rc;
     }
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
@@ -2970,7 +2979,7 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, c
     float total_ms = 0;
     (void)hipEventElapsedTime(&total_ms, ctx->ev0, ctx->ev1);
     for (int k = 0; k < n_slots; ++k)
-        hipLaunchKernelGGL(k_s_merge_tallies, dim3((unsigned)((sc->tally_n + 255) / 256)), dim3(256), 0, ctx->stream, sc->d_tally.get(), E.slot[k].W.tally_part, (long long)sc->tally_n);
+        hipLaunchKernelGGL(k_s_merge_tallies, dim3((unsigned)((sc->tally_n + 255) / 256)), dim3(256), 0, ctx->stream, sc->d_tally.get(), E.slot[k].W.tally_part.get(), (long long)sc->tally_n);
     hipLaunchKernelGGL(k_s_add2, dim3(1), dim3(64), 0, ctx->stream, sc->d_tally.get() + 3 * sc->n_surf, C.seg, C.hits);
     // (not waited for: whatever reads or resets the tallies synchronises the context's stream first, and the next call's kernels
     // are ordered behind these by ev0)
