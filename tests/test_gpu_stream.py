@@ -189,6 +189,76 @@ def test_fresh_and_bounce_kernels_on_mixed_scenes_and_sources(ctx):
                 _same(ref, _trace(ctx, cs, bundle, reps=12, accel=False), ('all boxes', flat_only, k))
 
 
+def test_listed_rays_in_partial_waves(ctx):
+    """
+    The search of a footprint-listed ray is one body for k_s_fresh (its loop) and k_s_fresh2 (its second phase, fed from a queue per
+    wave).  Ray counts around the wave size -- 1, 63, 65, 129, 1000 -- leave it inactive lanes, second phases of fewer than 64
+    entries and a queue to drain at the end: a Buie disc source (k_s_fresh2) and a pillbox rectangle (k_s_fresh) on the flat-only
+    and the mixed scene, default route against the megakernel over 4 bounces.
+    """
+    from tracer_amd import sources
+    from tracer_amd.scene import compile_scene
+    direction = N.r_[0.25, -0.15, -1.] / N.linalg.norm([0.25, -0.15, -1.])
+    center = N.c_[-30. * direction]
+    srcs = [lambda n, s: sources.buie_sunshape(n, center, direction, 9., 0.05, flux=1., seed=s),
+            lambda n, s: sources.rect_bundle(n, center, direction, 16., 14., 0.01, flux=1., seed=s)]
+    for flat_only in (True, False):
+        cs = compile_scene(_mixed_scene(3 + flat_only, flat_only=flat_only))
+        for k, make in enumerate(srcs):
+            hits = 0
+            for n in (1, 63, 65, 129, 1000):
+                bundle = lambda: make(n, 60 + k)
+                ref = _trace(ctx, cs, bundle, reps=4)
+                _same(ref, _trace(ctx, cs, bundle, reps=4, stream=False), ('megakernel', flat_only, k, n))
+                hits += ref['hits']
+            assert hits > 0, (flat_only, k)
+
+
+def _record_stride(cs):
+    """doubles per surface record of a compiled scene: 14 of header, the geometry parameters of the widest kind, made odd
+    (trc_scene_create); counted from the descriptors, trailing zeros left out -- never more than the library's own"""
+    n_par = max(len(N.trim_zeros(N.array(list(cs.descs[i].gm)), 'b')) for i in range(cs.n_surf))
+    return (14 + n_par) | 1
+
+
+def test_listed_rays_with_tables_in_global_memory(ctx):
+    """
+    k_s_fresh and k_s_fresh2 stage records, oriented boxes and lists in LDS when they fit 150 KiB, and read them from global
+    memory otherwise (their LDS = false instances, 32-bit lists).  A field of identical plates, as many that records (8 * stride
+    bytes each) and oriented boxes (4 * TRC_OBB_LSTRIDE = 80 bytes each in their LDS form) alone exceed the limit, under a pillbox
+    rectangle and a Buie disc: default route against the general path and the megakernel.
+    """
+    from tracer_amd import sources
+    from tracer_amd import optics_callables as opt
+    from tracer_amd.assembly import Assembly
+    from tracer_amd.object import AssembledObject
+    from tracer_amd.surface import Surface
+    from tracer_amd.flat_surface import RectPlateGM
+    from tracer_amd.scene import compile_scene
+    from tracer_amd.spatial_geometry import translate
+    OBB_LSTRIDE = 20
+    plate = lambda x, y: AssembledObject(surfs=[Surface(RectPlateGM(1., 1.), opt.Reflective(0.1))], transform=translate(x, y, 0.))
+    stride = _record_stride(compile_scene(Assembly(objects=[plate(0., 0.)])))
+    n_plates = 150 * 1024 // (8 * stride + 4 * OBB_LSTRIDE) + 1
+    side = int(N.ceil(N.sqrt(n_plates)))
+    pitch = 1.5
+    xy = [((k % side - 0.5 * (side - 1)) * pitch, (k // side - 0.5 * (side - 1)) * pitch) for k in range(n_plates)]
+    cs = compile_scene(Assembly(objects=[plate(x, y) for x, y in xy]))
+    assert cs.n_surf == n_plates and _record_stride(cs) == stride
+    assert n_plates * (8 * stride + 4 * OBB_LSTRIDE) > 150 * 1024
+    direction = N.r_[0.1, -0.05, -1.] / N.linalg.norm([0.1, -0.05, -1.])
+    center = N.c_[-30. * direction]
+    extent = side * pitch
+    n = 200000
+    srcs = [lambda: sources.rect_bundle(n, center, direction, extent, extent, 0.01, flux=1., seed=71),
+            lambda: sources.buie_sunshape(n, center, direction, 0.5 * extent, 0.05, flux=1., seed=72)]
+    for k, bundle in enumerate(srcs):
+        ref = _trace(ctx, cs, bundle, reps=3)
+        assert ref['hits'] > 0.02 * n, k
+        _same(ref, _trace(ctx, cs, bundle, reps=3, TRC_STREAM_FRESH=0), ('fresh rays on the general path', k))
+        _same(ref, _trace(ctx, cs, bundle, reps=3, stream=False), ('megakernel', k))
+
+
 def test_terminal_surfaces_are_finished_by_k_s_absorb(ctx):
     """
     Surfaces that end every ray (absorptivity 1: the receivers) among mirrors and partly absorbing walls.  k_s_bounce lists the hits on

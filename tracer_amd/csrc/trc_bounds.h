@@ -105,6 +105,64 @@ static inline float trc_f32_up(double x) { float f = (float)x; return ((double)f
 // For a flat surface the box is the plate itself +- delta: a ray that passes this test nearly always passes the exact one.
 #define TRC_BG_ENT 12      /* floats per entry of the large grid's lists */
 #define TRC_OBB_STRIDE 20   /* [A0 A1 A2 c0 | A3 A4 A5 c1 | A6 A7 A8 c2 | lo0 lo1 lo2 hi0 | hi1 hi2 - -]; A = R^T */
+#ifndef TRC_OBB_LSTRIDE
+#define TRC_OBB_LSTRIDE 20      /* floats between the oriented boxes of two surfaces in their LDS copies.  At 20, the stride of the global
+                                   table, eight lanes on different surfaces share a bank group and the counters show bank conflicts worth
+                                   a quarter of k_s_fresh's time -- but 21 (every lane its own bank, 32-bit reads instead of 128-bit ones)
+                                   measured the same on all three configurations: the conflicts hide behind the arithmetic */
+#endif
+
+// The LDS image of the tables a search kernel of the streaming engine reads (k_s_fresh, k_s_fresh2, k_s_bounce, k_s_bounce_coop):
+// ONE description, read by the kernels, which carve their pointers from it (stage_search_tables, trc_device.h), and by the host,
+// which sizes the launches from it and decides whether a scene's tables fit LDS (stream_form_fresh, stream_form_bounce).  The
+// parts follow one another in the order of the fields below; a part that is absent takes no room.
+#define SFQ_CAP 128             /* entries of a wave's queue between the two phases of k_s_fresh2 (a power of two, >= 2 x 64) */
+#ifndef SBC_CELLS
+#define SBC_CELLS 4             /* cells with faces a lane of k_s_bounce_coop collects per stage */
+#endif
+#define SBC_PAIRS 256           /* (ray, surface) pairs that can wait for their exact test, per wave of k_s_bounce_coop */
+#define SBC_WAVE_BYTES (2 * SBC_CELLS * 64 * 4 + 64 * 4 + SBC_PAIRS * 4 + 64 * 8 + 64 * 4)
+#define TRC_LDS_SLACK 16        /* bytes the fits-in-LDS decisions allow on top of what each of the oriented boxes, the footprint lists
+                                   and the queues takes (half of it for the small grid, and 4 more when its cell count is odd): the
+                                   margins of the hand-made sums this description replaced, kept so that no scene changes sides of a
+                                   limit */
+struct trc_lds_parts {
+    int n_surf, stride;         // surfaces, doubles per surface record
+    int buie_bytes;             // the Buie table (sizeof(trc_buie_fast)), 0: none
+    int occ_words;              // occupancy words of the large grid, 0: none
+    bool tables;                // surface records and oriented boxes (TRC_OBB_LSTRIDE floats apart)
+    bool sbox, flags;           // per surface: axis-aligned box (6 floats), flags (one word)
+    int fp_offs, fp_list;       // footprint map: cell offsets (0: none) and list entries, 16 bits each
+    int grid_cells, grid_list;  // small grid: cells (0: none; one offset more) and list entries, 16 bits each
+    int queue_waves;            // k_s_fresh2: waves with a queue of SFQ_CAP (ray, cell) pairs each
+    int coop_waves;             // k_s_bounce_coop: waves with a block of SBC_WAVE_BYTES each
+};
+struct trc_lds_layout {
+    size_t buie, occ, recs, obb, sbox, flags, fp_off, fp_list, grid_off, grid_list, queues, coop;      // byte offset of every part
+    size_t end;                 // bytes in all
+    size_t slack;               // what a fits-in-LDS decision adds to `end` (TRC_LDS_SLACK)
+};
+TRC_HD size_t trc_lds_round16(size_t b) { return (b + 15) & ~(size_t)15; }
+TRC_HD trc_lds_layout trc_search_lds_layout(const trc_lds_parts &p) {
+    trc_lds_layout L;
+    const size_t S = (size_t)p.n_surf;
+    size_t cur = 0, slack = 0;
+    L.buie = cur; cur += trc_lds_round16((size_t)p.buie_bytes);
+    L.occ = cur; cur += trc_lds_round16((size_t)p.occ_words * 4);
+    L.recs = cur; if (p.tables) cur += S * (size_t)p.stride * 8;
+    L.obb = cur; if (p.tables) { cur += trc_lds_round16(S * TRC_OBB_LSTRIDE * 4); slack += TRC_LDS_SLACK; }
+    L.sbox = cur; if (p.sbox) cur += S * 6 * 4;
+    L.flags = cur; if (p.flags) cur += trc_lds_round16(S * 4);
+    L.fp_off = cur; if (p.fp_offs) cur += trc_lds_round16((size_t)p.fp_offs * 2);
+    L.fp_list = cur; if (p.fp_offs) { cur += (size_t)p.fp_list * 2; slack += TRC_LDS_SLACK; }
+    L.grid_off = cur; if (p.grid_cells) cur += (((size_t)p.grid_cells + 2) & ~(size_t)1) * 2;
+    L.grid_list = cur; if (p.grid_cells) { cur += (size_t)p.grid_list * 2; slack += TRC_LDS_SLACK / 2 + ((p.grid_cells & 1) ? 4 : 0); }      // (odd: the old sum's rounding)
+    if (p.queue_waves) { cur = trc_lds_round16(cur); slack += TRC_LDS_SLACK; }
+    L.queues = cur; cur += (size_t)p.queue_waves * (2 * SFQ_CAP * 4);
+    L.coop = cur; cur += (size_t)p.coop_waves * SBC_WAVE_BYTES;
+    L.end = cur; L.slack = slack;
+    return L;
+}
 
 struct trc_accel_host {
     std::vector<float> sbox;          // 6 per surface

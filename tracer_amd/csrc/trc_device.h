@@ -730,4 +730,136 @@ __device__ __forceinline__ void trc_nearest_grid32(const DScene &sc, double px, 
 // capacity of the ray table and of the lists of slots / ray numbers: rays per batch + room for the unused tails of the chunks
 #define SQ_ROOM(W) ((W).room)
 
+// ================================================================================================
+// shared pieces of the streaming kernels that find a ray's first or next surface (k_s_fresh, k_s_fresh2, k_s_bounce)
+// ================================================================================================
+// Copies the parts of the search tables' LDS image that `p` names (trc_search_lds_layout, trc_bounds.h) from global memory, in the
+// order of the image; every thread of the workgroup calls it, the caller's next barrier makes the copies visible.  The footprint
+// lists are 32-bit in global memory and 16-bit here.
+template <int THREADS>
+__device__ __forceinline__ void stage_search_tables(char *lds, const trc_lds_layout &L, const trc_lds_parts &p, const DScene &sc, const FpDev &fp,
+                                                    int tid) {
+    const int Sn = p.n_surf;
+    if (p.occ_words > 0) {
+        uint32_t *l_occ = (uint32_t *)(lds + L.occ);
+        for (int i = tid; i < p.occ_words; i += THREADS) l_occ[i] = sc.a_bg_occ[i];
+    }
+    if (p.tables) {
+        double *lr = (double *)(lds + L.recs);
+        for (int i = tid; i < Sn * p.stride; i += THREADS) lr[i] = sc.recs[i];
+        float *lb = (float *)(lds + L.obb);
+        for (int i = tid; i < Sn * TRC_OBB_STRIDE; i += THREADS) lb[(i / TRC_OBB_STRIDE) * TRC_OBB_LSTRIDE + i % TRC_OBB_STRIDE] = sc.a_obb[i];
+    }
+    if (p.sbox) {
+        float *ls = (float *)(lds + L.sbox);
+        for (int i = tid; i < Sn * 6; i += THREADS) ls[i] = sc.a_sbox[i];
+    }
+    if (p.flags) {
+        int32_t *lf = (int32_t *)(lds + L.flags);
+        for (int i = tid; i < Sn; i += THREADS) lf[i] = sc.sflags[i];
+    }
+    if (p.fp_offs) {
+        uint16_t *lo = (uint16_t *)(lds + L.fp_off), *ll = (uint16_t *)(lds + L.fp_list);
+        for (int i = tid; i < p.fp_offs; i += THREADS) lo[i] = (uint16_t)fp.coff[i];
+        for (int i = tid; i < p.fp_list; i += THREADS) ll[i] = (uint16_t)fp.clist[i];
+    }
+    if (p.grid_cells) {
+        uint16_t *l_goff = (uint16_t *)(lds + L.grid_off), *l_list = (uint16_t *)(lds + L.grid_list);
+        for (int i = tid; i < p.grid_cells + 1; i += THREADS) l_goff[i] = sc.a_goff[i];
+        for (int i = tid; i < p.grid_list; i += THREADS) l_list[i] = sc.a_glist[i];
+    }
+}
+
+// The two passes of the Buie table's LDS form (trc_buie_fast_fill) with the barrier behind each: every thread of the workgroup
+// reaches both barriers, whatever `want` says (the source is a Buie one and the kernel samples it).
+__device__ __forceinline__ void buie_tables_fill(const trc_source_desc *src, trc_buie_fast *l_bf, int tid, int nth, bool want) {
+    if (want) trc_buie_fast_fill(src->buie, l_bf, 0, tid, nth);
+    __syncthreads();
+    if (want) trc_buie_fast_fill(src->buie, l_bf, 1, tid, nth);
+    __syncthreads();
+}
+
+// A fresh ray takes `slot` of the ray table: no candidate linked, bounce 0, left no surface.  Rays of a source descriptor all
+// carry (energy, 1, 0), written at their first hit; given rays bring their own (the second form).
+__device__ __forceinline__ void store_fresh_ray(const StreamWs &W, unsigned long long slot, uint32_t ri, double px, double py, double pz,
+                                                double dx, double dy, double dz) {
+    SRayGeo g;
+    g.px = px; g.py = py; g.pz = pz; g.dx = dx; g.dy = dy; g.dz = dz;
+    g.head = SQ_INVALID;
+    g.idx = ri;
+    g.tail = sray_tail(0, 0u);
+    W.geo[slot] = g;
+}
+__device__ __forceinline__ void store_fresh_ray(const StreamWs &W, unsigned long long slot, uint32_t ri, double px, double py, double pz,
+                                                double dx, double dy, double dz, double e, double ref, double wl) {
+    store_fresh_ray(W, slot, ri, px, py, pz, dx, dy, dz);
+    SRayAux a;
+    a.e = e; a.ref = ref; a.wl = wl; a.pad = 0.0;
+    W.aux[slot] = a;
+}
+
+// entry q of the hit list: the ray in `slot` hits surface `surf` at distance t
+__device__ __forceinline__ void store_hit(const StreamWs &W, unsigned long long q, uint32_t slot, int surf, double t) {
+    W.hit_slot[q] = slot; W.hit_surf[q] = (uint32_t)surf; W.hit_t[q] = t;
+}
+// One listed fresh ray per lane (k_s_fresh's loop body, k_s_fresh2's second phase): ray `ri` of the batch, whose start point lies in
+// mask cell `cell` of the footprint map, or an inactive lane.  The float64 ray exactly as k_s_gen makes it (trc_source_ray_t, same
+// stream), the surfaces listed for its cell, their oriented boxes in float32, 32 at a time, then the exact float64 tests of those
+// that pass -- each lane pops its own -- with the reference's tie rule: nearest, lowest surface index on equal t.  A ray that hits
+// takes the next slot of the ray table (cs) and goes to the hit list (ch) with its surface and distance.  Called by the whole wave.
+// LDS: records, boxes and lists are the LDS copies (16-bit lists), else the global tables (32-bit lists).
+template <bool LDS> using fp_list_t = typename std::conditional<LDS, uint16_t, uint32_t>::type;
+template <int KIND, bool FLAT, bool LDS>
+__device__ __forceinline__ void listed_ray_search(const StreamParams &S, const trc_buie_fast *l_bf, const double *recs, const float *obb,
+                                                  const fp_list_t<LDS> *l_coff, const fp_list_t<LDS> *clist, WaveChunk &cs, WaveChunk &ch,
+                                                  bool active, uint32_t ri, uint32_t cell) {
+    const FastParams &P = S.P;
+    const DScene &sc = P.sc;
+    const StreamWs &W = S.W;
+    const trc_fp_params &F = S.fp.P;
+    double px = 0, py = 0, pz = 0, dx = 0, dy = 0, dz = 1;
+    double tb = TRC_INF;
+    int sb = 0x7FFFFFFF;
+    if (active) {
+        const unsigned long long rid = P.ray_offset + (unsigned long long)(S.base + ri);
+        trc_source_ray_t<KIND>(P.src, nullptr, nullptr, P.seed, rid, &px, &py, &pz, &dx, &dy, &dz, l_bf);
+    }
+    // float32 copy for the box tests, taken after an advance that no surface is nearer than, relative to the scene centre
+    const float ox = (float)(px + F.t_adv * dx - sc.a_cen[0]), oy = (float)(py + F.t_adv * dy - sc.a_cen[1]), oz = (float)(pz + F.t_adv * dz - sc.a_cen[2]);
+    const float ex = (float)dx, ey = (float)dy, ez = (float)dz;
+    uint32_t k0 = 0, k1 = 0;
+    if (active) {
+        const uint32_t c = ((cell >> 16) >> TRC_FP_SHIFT) * (uint32_t)F.Mc + ((cell & 0xFFFFu) >> TRC_FP_SHIFT);
+        if (LDS) { k0 = l_coff[c]; k1 = l_coff[c + 1]; }
+        else { k0 = S.fp.coff[c]; k1 = S.fp.coff[c + 1]; }
+    }
+    for (uint32_t kb = k0; __ballot(kb < k1); kb += 32) {
+        unsigned hits = 0;
+        for (uint32_t k = kb; k < kb + 32 && k < k1; ++k) {
+            const uint32_t sidx = clist[k];
+            if (trc_obb_hit32(obb + (size_t)(LDS ? TRC_OBB_LSTRIDE : TRC_OBB_STRIDE) * sidx, ox, oy, oz, ex, ey, ez)) hits |= 1u << (k - kb);
+        }
+        while (__ballot(hits != 0)) {
+            if (hits != 0) {
+                const int sidx = (int)clist[kb + (uint32_t)__ffs((int)hits) - 1u];
+                const double *rec = recs + (size_t)sidx * sc.stride;
+                double t = FLAT ? trc_intersect_flat(trc_rec_gm_kind(rec), rec, sc.extra, px, py, pz, dx, dy, dz)
+                                : trc_intersect(rec, sc.extra, px, py, pz, dx, dy, dz);
+                if (!(t > 0.0) || !(t < TRC_INF)) t = TRC_INF;      // t == 0 is not a hit (tracer_engine.py:58)
+                if (t < tb || (t == tb && t < TRC_INF && sidx < sb)) { tb = t; sb = sidx; }      // tracer_engine.py:58-63
+                hits &= hits - 1u;
+            }
+        }
+    }
+    const bool hit = active && tb < TRC_INF;
+    const unsigned long long sl = chunk_append(&W.cnt[CN(CW_SLOTS)], cs, hit, nullptr, 0);
+    const unsigned long long qh = chunk_append(&W.cnt[CN(CW_HIT_LIST)], ch, hit, W.hit_slot, SQ_ROOM(W));
+    if (hit) {
+        if ((long long)sl < SQ_ROOM(W) && (long long)qh < SQ_ROOM(W)) {
+            store_fresh_ray(W, sl, ri, px, py, pz, dx, dy, dz);
+            store_hit(W, qh, (uint32_t)sl, sb, tb);
+        } else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
+    }
+}
+
 #endif

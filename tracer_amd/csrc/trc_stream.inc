@@ -18,6 +18,12 @@
 //              t (the reference's tie rule); normal, optics, tallies (LDS-privatised), flux map, hit capture; the continued ray is
 //              written back to the table and appended to the next bounce's active list
 //
+// What k_s_fresh, k_s_fresh2 and k_s_bounce share is written once, in trc_device.h: the LDS image of their tables
+// (trc_search_lds_layout, trc_bounds.h: the kernels carve their pointers from it, the host sizes the launches and decides "fits in
+// LDS" from the same function) and its staging (stage_search_tables), the search of a listed fresh ray (listed_ray_search), the
+// Buie table's fill (buie_tables_fill), a fresh ray's record and a hit-list entry (store_fresh_ray, store_hit).  k_s_gen and
+// k_s_bounce_coop keep their own copies: through the helpers their instances changed registers or scratch.
+//
 // Results are those of the other engines ray for ray: the same per-ray functions of trc_core.h, the same Philox
 // streams (stream id = ray_offset + index in the call), the same candidates, the same tie rule.
 
@@ -254,20 +260,24 @@ __global__ __launch_bounds__(SC_THREADS) void k_s_cull(CullParams C) {
 // the rate of its arithmetic, its dependent float64 chains want waves to switch to) -- 512 (2 per SIMD) with the quadric code in;
 // every table then exists once per CU
 #define SF_THREADS(FLAT) ((FLAT) ? 1024 : 768)
-#ifndef TRC_OBB_LSTRIDE
-#define TRC_OBB_LSTRIDE 20      /* floats between the oriented boxes of two surfaces in their LDS copies.  At 20, the stride of the global
-                                   table, eight lanes on different surfaces share a bank group and the counters show bank conflicts worth
-                                   a quarter of k_s_fresh's time -- but 21 (every lane its own bank, 32-bit reads instead of 128-bit ones)
-                                   measured the same on all three configurations: the conflicts hide behind the arithmetic */
-#endif
 #ifndef SB_FLAT_WALK
 #define SB_FLAT_WALK 0          /* 1: the grid that fits LDS is walked like the large one, one cell or one candidate per lane and turn */
 #endif
-#define SFQ_CAP 128             /* entries of a wave's queue between the two phases of k_s_fresh2 (a power of two, >= 2 x 64) */
 
 // FLAT: every surface of the scene is a flat kind (a heliostat field, a mesh): the instance carries no quadric code.
 // LDS: the tables a listed ray reads (surface records, oriented boxes, cell lists) are staged in LDS -- all of them or none, so
 // that the compiler knows the address space of every access (a pointer that may be either is read with flat loads).
+// the footprint-listed kernels' LDS image: [the Buie table] [records | oriented boxes | cell offsets | lists (lds)] [queues]
+TRC_HD trc_lds_parts fresh_lds_parts(int n_surf, int stride, const trc_fp_params &F, long long n_list, bool buie, bool lds, int queue_waves) {
+    trc_lds_parts p = {};
+    p.n_surf = n_surf; p.stride = stride;
+    p.buie_bytes = buie ? (int)sizeof(trc_buie_fast) : 0;
+    p.tables = lds;
+    if (lds) { p.fp_offs = F.Mc * F.Mc + 1; p.fp_list = (int)n_list; }
+    p.queue_waves = queue_waves;
+    return p;
+}
+
 template <int KIND, bool FLAT, bool LDS>
 __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh(StreamParams S) {
     constexpr int THREADS = SF_THREADS(FLAT);
@@ -275,36 +285,20 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh(StreamParams S) {
     const FastParams &P = S.P;
     const DScene &sc = P.sc;
     const StreamWs &W = S.W;
-    const trc_fp_params &F = S.fp.P;
     constexpr bool BUIE = KIND == TRC_SRC_BUIE_DISK || KIND == TRC_SRC_BUIE_RECT;
-    const int Sn = sc.n_surf;
-    char *cur = (char *)lds;
-    trc_buie_fast *l_bf = nullptr;
-    if (BUIE) { l_bf = (trc_buie_fast *)cur; cur += (sizeof(trc_buie_fast) + 15) & ~(size_t)15; }
+    const trc_lds_parts parts = fresh_lds_parts(sc.n_surf, sc.stride, S.fp.P, S.fp.n_list, BUIE, LDS, 0);
+    const trc_lds_layout L = trc_search_lds_layout(parts);
+    trc_buie_fast *l_bf = BUIE ? (trc_buie_fast *)((char *)lds + L.buie) : nullptr;
     const double *recs = sc.recs;
     const float *obb = sc.a_obb;
-    typedef typename std::conditional<LDS, uint16_t, uint32_t>::type list_t;
-    const list_t *l_coff = nullptr, *clist = nullptr;
-    if (!LDS) clist = (const list_t *)S.fp.clist;
+    typedef fp_list_t<LDS> list_t;
+    const list_t *l_coff = nullptr, *clist = (const list_t *)S.fp.clist;
+    stage_search_tables<THREADS>((char *)lds, L, parts, sc, S.fp, (int)threadIdx.x);
     if (LDS) {
-        double *lr = (double *)cur; cur += (size_t)Sn * sc.stride * 8;
-        for (int i = threadIdx.x; i < Sn * sc.stride; i += THREADS) lr[i] = sc.recs[i];
-        recs = lr;
-        float *lb = (float *)cur; cur += (((size_t)Sn * TRC_OBB_LSTRIDE * 4) + 15) & ~(size_t)15;
-        for (int i = threadIdx.x; i < Sn * TRC_OBB_STRIDE; i += THREADS) lb[(i / TRC_OBB_STRIDE) * TRC_OBB_LSTRIDE + i % TRC_OBB_STRIDE] = sc.a_obb[i];
-        obb = lb;
-        const int nc = F.Mc * F.Mc + 1;
-        uint16_t *lo = (uint16_t *)cur; cur += ((size_t)nc * 2 + 15) & ~(size_t)15;
-        for (int i = threadIdx.x; i < nc; i += THREADS) lo[i] = (uint16_t)S.fp.coff[i];
-        uint16_t *ll = (uint16_t *)cur;
-        const int nl = (int)S.fp.n_list;
-        for (int i = threadIdx.x; i < nl; i += THREADS) ll[i] = (uint16_t)S.fp.clist[i];
-        l_coff = (const list_t *)lo; clist = (const list_t *)ll;
+        recs = (const double *)((char *)lds + L.recs); obb = (const float *)((char *)lds + L.obb);
+        l_coff = (const list_t *)((char *)lds + L.fp_off); clist = (const list_t *)((char *)lds + L.fp_list);
     }
-    if (BUIE) trc_buie_fast_fill(P.src->buie, l_bf, 0, (int)threadIdx.x, (int)blockDim.x);
-    __syncthreads();
-    if (BUIE) trc_buie_fast_fill(P.src->buie, l_bf, 1, (int)threadIdx.x, (int)blockDim.x);
-    __syncthreads();
+    buie_tables_fill(P.src, l_bf, (int)threadIdx.x, (int)blockDim.x, BUIE);
     if (W.cnt[CN(CW_OVERFLOW)]) return;
     long long count = (long long)W.cnt[CN(CW_FP_LIST)];
     if (count > SQ_ROOM(W)) count = SQ_ROOM(W);
@@ -327,57 +321,7 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh(StreamParams S) {
         }
         const bool active = ri != SQ_INVALID;
         if (!__ballot(active)) continue;
-        double px = 0, py = 0, pz = 0, dx = 0, dy = 0, dz = 1;
-        double tb = TRC_INF;
-        int sb = 0x7FFFFFFF;
-        if (active) {
-            const unsigned long long rid = P.ray_offset + (unsigned long long)(S.base + ri);
-            trc_source_ray_t<KIND>(P.src, nullptr, nullptr, P.seed, rid, &px, &py, &pz, &dx, &dy, &dz, l_bf);
-        }
-        // float32 copy for the box tests, taken after an advance that no surface is nearer than, relative to the scene centre
-        const float ox = (float)(px + F.t_adv * dx - sc.a_cen[0]), oy = (float)(py + F.t_adv * dy - sc.a_cen[1]), oz = (float)(pz + F.t_adv * dz - sc.a_cen[2]);
-        const float ex = (float)dx, ey = (float)dy, ez = (float)dz;
-        uint32_t k0 = 0, k1 = 0;
-        if (active) {
-            const uint32_t c = ((cell >> 16) >> TRC_FP_SHIFT) * (uint32_t)F.Mc + ((cell & 0xFFFFu) >> TRC_FP_SHIFT);
-            if (LDS) { k0 = l_coff[c]; k1 = l_coff[c + 1]; }
-            else { k0 = S.fp.coff[c]; k1 = S.fp.coff[c + 1]; }
-        }
-        for (uint32_t kb = k0; __ballot(kb < k1); kb += 32) {
-            // oriented boxes of up to 32 listed surfaces, then the exact tests of those that pass -- each lane pops its own
-            unsigned hits = 0;
-            for (uint32_t k = kb; k < kb + 32 && k < k1; ++k) {
-                const uint32_t sidx = clist[k];
-                if (trc_obb_hit32(obb + (size_t)(LDS ? TRC_OBB_LSTRIDE : TRC_OBB_STRIDE) * sidx, ox, oy, oz, ex, ey, ez)) hits |= 1u << (k - kb);
-            }
-            while (__ballot(hits != 0)) {
-                if (hits != 0) {
-                    const int sidx = (int)clist[kb + (uint32_t)__ffs((int)hits) - 1u];
-                    const double *rec = recs + (size_t)sidx * sc.stride;
-                    double t = FLAT ? trc_intersect_flat(trc_rec_gm_kind(rec), rec, sc.extra, px, py, pz, dx, dy, dz)
-                                    : trc_intersect(rec, sc.extra, px, py, pz, dx, dy, dz);
-                    if (!(t > 0.0) || !(t < TRC_INF)) t = TRC_INF;      // t == 0 is not a hit (tracer_engine.py:58)
-                    if (t < tb || (t == tb && t < TRC_INF && sidx < sb)) { tb = t; sb = sidx; }      // tracer_engine.py:58-63
-                    hits &= hits - 1u;
-                }
-            }
-        }
-        const bool hit = active && tb < TRC_INF;
-        const unsigned long long sl = chunk_append(&W.cnt[CN(CW_SLOTS)], cs, hit, nullptr, 0);
-        const unsigned long long qh = chunk_append(&W.cnt[CN(CW_HIT_LIST)], ch, hit, W.hit_slot, SQ_ROOM(W));
-        if (hit) {
-            if ((long long)sl < SQ_ROOM(W) && (long long)qh < SQ_ROOM(W)) {
-                SRayGeo g;
-                g.px = px; g.py = py; g.pz = pz; g.dx = dx; g.dy = dy; g.dz = dz;
-                g.head = SQ_INVALID;
-                g.idx = ri;
-                g.tail = sray_tail(0, 0u);
-                W.geo[sl] = g;
-                W.hit_slot[qh] = (uint32_t)sl;
-                W.hit_surf[qh] = (uint32_t)sb;
-                W.hit_t[qh] = tb;
-            } else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
-        }
+        listed_ray_search<KIND, FLAT, LDS>(S, l_bf, recs, obb, l_coff, clist, cs, ch, active, ri, cell);
     }
     chunk_close(ch, W.hit_slot, SQ_ROOM(W));
 }
@@ -400,37 +344,22 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh2(StreamParams S) {
     const StreamWs &W = S.W;
     const trc_fp_params &F = S.fp.P;
     static_assert(KIND == TRC_SRC_BUIE_DISK || KIND == TRC_SRC_BUIE_RECT, "the two-phase form samples the Buie direction in float32");
-    const int Sn = sc.n_surf;
-    char *cur = (char *)lds;
-    trc_buie_fast *l_bf = (trc_buie_fast *)cur; cur += (sizeof(trc_buie_fast) + 15) & ~(size_t)15;
+    const trc_lds_parts parts = fresh_lds_parts(sc.n_surf, sc.stride, S.fp.P, S.fp.n_list, true, LDS, THREADS / 64);
+    const trc_lds_layout L = trc_search_lds_layout(parts);
+    trc_buie_fast *l_bf = (trc_buie_fast *)((char *)lds + L.buie);
     const double *recs = sc.recs;
     const float *obb = sc.a_obb;
-    typedef typename std::conditional<LDS, uint16_t, uint32_t>::type list_t;
-    const list_t *l_coff = nullptr, *clist = nullptr;
-    if (!LDS) clist = (const list_t *)S.fp.clist;
+    typedef fp_list_t<LDS> list_t;
+    const list_t *l_coff = nullptr, *clist = (const list_t *)S.fp.clist;
+    stage_search_tables<THREADS>((char *)lds, L, parts, sc, S.fp, (int)threadIdx.x);
     if (LDS) {
-        double *lr = (double *)cur; cur += (size_t)Sn * sc.stride * 8;
-        for (int i = threadIdx.x; i < Sn * sc.stride; i += THREADS) lr[i] = sc.recs[i];
-        recs = lr;
-        float *lb = (float *)cur; cur += (((size_t)Sn * TRC_OBB_LSTRIDE * 4) + 15) & ~(size_t)15;
-        for (int i = threadIdx.x; i < Sn * TRC_OBB_STRIDE; i += THREADS) lb[(i / TRC_OBB_STRIDE) * TRC_OBB_LSTRIDE + i % TRC_OBB_STRIDE] = sc.a_obb[i];
-        obb = lb;
-        const int nc = F.Mc * F.Mc + 1;
-        uint16_t *lo = (uint16_t *)cur; cur += ((size_t)nc * 2 + 15) & ~(size_t)15;
-        for (int i = threadIdx.x; i < nc; i += THREADS) lo[i] = (uint16_t)S.fp.coff[i];
-        uint16_t *ll = (uint16_t *)cur;
-        const int nl = (int)S.fp.n_list;
-        for (int i = threadIdx.x; i < nl; i += THREADS) ll[i] = (uint16_t)S.fp.clist[i];
-        cur = (char *)(((uintptr_t)(ll + nl) + 15) & ~(uintptr_t)15);
-        l_coff = (const list_t *)lo; clist = (const list_t *)ll;
+        recs = (const double *)((char *)lds + L.recs); obb = (const float *)((char *)lds + L.obb);
+        l_coff = (const list_t *)((char *)lds + L.fp_off); clist = (const list_t *)((char *)lds + L.fp_list);
     }
     // the queue of this wave: SFQ_CAP ray numbers, then their cells
-    uint32_t *q_ray = (uint32_t *)cur + (size_t)(threadIdx.x >> 6) * (2 * SFQ_CAP);
+    uint32_t *q_ray = (uint32_t *)((char *)lds + L.queues) + (size_t)(threadIdx.x >> 6) * (2 * SFQ_CAP);
     uint32_t *q_cell = q_ray + SFQ_CAP;
-    trc_buie_fast_fill(P.src->buie, l_bf, 0, (int)threadIdx.x, (int)blockDim.x);
-    __syncthreads();
-    trc_buie_fast_fill(P.src->buie, l_bf, 1, (int)threadIdx.x, (int)blockDim.x);
-    __syncthreads();
+    buie_tables_fill(P.src, l_bf, (int)threadIdx.x, (int)blockDim.x, true);
     if (W.cnt[CN(CW_OVERFLOW)]) return;
     long long count = (long long)W.cnt[CN(CW_FP_LIST)];
     if (count > SQ_ROOM(W)) count = SQ_ROOM(W);
@@ -454,55 +383,7 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh2(StreamParams S) {
         const bool active = lane < take;
         uint32_t ri = 0, cell = 0;
         if (active) { ri = q_ray[(qh + lane) & (SFQ_CAP - 1)]; cell = q_cell[(qh + lane) & (SFQ_CAP - 1)]; }
-        double px = 0, py = 0, pz = 0, dx = 0, dy = 0, dz = 1;
-        double tb = TRC_INF;
-        int sb = 0x7FFFFFFF;
-        if (active) {
-            const unsigned long long rid = P.ray_offset + (unsigned long long)(S.base + ri);
-            trc_source_ray_t<KIND>(P.src, nullptr, nullptr, P.seed, rid, &px, &py, &pz, &dx, &dy, &dz, l_bf);
-        }
-        const float ox = (float)(px + F.t_adv * dx - sc.a_cen[0]), oy = (float)(py + F.t_adv * dy - sc.a_cen[1]), oz = (float)(pz + F.t_adv * dz - sc.a_cen[2]);
-        const float ex = (float)dx, ey = (float)dy, ez = (float)dz;
-        uint32_t k0 = 0, k1 = 0;
-        if (active) {
-            const uint32_t c = ((cell >> 16) >> TRC_FP_SHIFT) * (uint32_t)F.Mc + ((cell & 0xFFFFu) >> TRC_FP_SHIFT);
-            if (LDS) { k0 = l_coff[c]; k1 = l_coff[c + 1]; }
-            else { k0 = S.fp.coff[c]; k1 = S.fp.coff[c + 1]; }
-        }
-        for (uint32_t kb = k0; __ballot(kb < k1); kb += 32) {
-            unsigned hits = 0;
-            for (uint32_t k = kb; k < kb + 32 && k < k1; ++k) {
-                const uint32_t sidx = clist[k];
-                if (trc_obb_hit32(obb + (size_t)(LDS ? TRC_OBB_LSTRIDE : TRC_OBB_STRIDE) * sidx, ox, oy, oz, ex, ey, ez)) hits |= 1u << (k - kb);
-            }
-            while (__ballot(hits != 0)) {
-                if (hits != 0) {
-                    const int sidx = (int)clist[kb + (uint32_t)__ffs((int)hits) - 1u];
-                    const double *rec = recs + (size_t)sidx * sc.stride;
-                    double t = FLAT ? trc_intersect_flat(trc_rec_gm_kind(rec), rec, sc.extra, px, py, pz, dx, dy, dz)
-                                    : trc_intersect(rec, sc.extra, px, py, pz, dx, dy, dz);
-                    if (!(t > 0.0) || !(t < TRC_INF)) t = TRC_INF;      // t == 0 is not a hit (tracer_engine.py:58)
-                    if (t < tb || (t == tb && t < TRC_INF && sidx < sb)) { tb = t; sb = sidx; }      // tracer_engine.py:58-63
-                    hits &= hits - 1u;
-                }
-            }
-        }
-        const bool hit = active && tb < TRC_INF;
-        const unsigned long long sl = chunk_append(&W.cnt[CN(CW_SLOTS)], cs, hit, nullptr, 0);
-        const unsigned long long qhit = chunk_append(&W.cnt[CN(CW_HIT_LIST)], ch, hit, W.hit_slot, SQ_ROOM(W));
-        if (hit) {
-            if ((long long)sl < SQ_ROOM(W) && (long long)qhit < SQ_ROOM(W)) {
-                SRayGeo g;
-                g.px = px; g.py = py; g.pz = pz; g.dx = dx; g.dy = dy; g.dz = dz;
-                g.head = SQ_INVALID;
-                g.idx = ri;
-                g.tail = sray_tail(0, 0u);
-                W.geo[sl] = g;
-                W.hit_slot[qhit] = (uint32_t)sl;
-                W.hit_surf[qhit] = (uint32_t)sb;
-                W.hit_t[qhit] = tb;
-            } else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
-        }
+        listed_ray_search<KIND, FLAT, LDS>(S, l_bf, recs, obb, l_coff, clist, cs, ch, active, ri, cell);
         qh += take;
     };
     uint32_t ri_n = SQ_INVALID, cell_n = 0;
@@ -826,6 +707,20 @@ __global__ __launch_bounds__(THREADS) void k_s_walk(StreamParams S) {
 // structures do not fit the LDS of the walk kernel (meshes of 1e5 faces), or everywhere with TRC_STREAM_FIRST=1.  A ray that hits
 // takes the next slot of the table.
 // FLAT: every surface of the scene is of a flat kind: no quadric code in the exact test (as in k_s_fresh).
+// the LDS image of k_s_bounce / k_s_bounce_coop: [the Buie table (fresh)] [occupancy bits] [records | oriented boxes | boxes | flags |
+// small grid (lds)] [the waves' blocks (coop)]
+TRC_HD trc_lds_parts bounce_lds_parts(int n_surf, int stride, bool fresh, bool lds, bool flags, int grid_cells, int grid_list, int occ_words,
+                                      int coop_waves) {
+    trc_lds_parts p = {};
+    p.n_surf = n_surf; p.stride = stride;
+    p.buie_bytes = fresh ? (int)sizeof(trc_buie_fast) : 0;
+    p.occ_words = occ_words;
+    p.tables = p.sbox = lds;
+    p.flags = flags;
+    if (grid_cells) { p.grid_cells = grid_cells; p.grid_list = grid_list; }
+    p.coop_waves = coop_waves;
+    return p;
+}
 #ifdef SB_STATS      /* diagnostic builds only: what the lanes of k_s_bounce spend their turns on (printed at the end of a call) */
 __device__ unsigned long long g_sb_stats[32];        /* [0, 16): fresh rays, [16, 32): continued rays */
 #define SB_COUNT(K, V) atomicAdd(&g_sb_stats[(FRESH ? 0 : 16) + (K)], (unsigned long long)(V))
@@ -870,41 +765,33 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
         G.csx = sc.a_bg_cs[0]; G.csy = sc.a_bg_cs[1]; G.csz = sc.a_bg_cs[2];
         G.ivx = sc.a_bg_inv[0]; G.ivy = sc.a_bg_inv[1]; G.ivz = sc.a_bg_inv[2];
     }
-    // dynamic LDS: [the Buie tables (FRESH)] [records | oriented boxes | boxes | grid (LDS)]
+    // dynamic LDS: [the Buie tables (FRESH)] [occupancy bits (large grid)] [records | oriented boxes | boxes | flags | grid (LDS)]
     char *cur = (char *)lds;
     trc_buie_fast *l_bf = nullptr;
-    if (FRESH) { l_bf = (trc_buie_fast *)cur; cur += (sizeof(trc_buie_fast) + 15) & ~(size_t)15; }
-    // the large grid: one bit per cell that lists anything, in LDS when the host found room for it -- most cells of a ray's way
-    // are empty, and a step through one then reads nothing from memory
     const uint32_t *occ = sc.a_bg_occ;
-    if (GRIDM == 2 && S.bg_occ_words > 0) {
-        uint32_t *l_occ = (uint32_t *)cur; cur += (((size_t)S.bg_occ_words * 4) + 15) & ~(size_t)15;
-        for (int i = tid; i < S.bg_occ_words; i += THREADS) l_occ[i] = sc.a_bg_occ[i];
-        occ = l_occ;
-    }
-    if (LDS) {
-        double *lr = (double *)cur; cur += (size_t)Sn * sc.stride * 8;
-        for (int i = tid; i < Sn * sc.stride; i += THREADS) lr[i] = sc.recs[i];
-        recs = lr;
-        float *lb = (float *)cur; cur += (((size_t)Sn * TRC_OBB_LSTRIDE * 4) + 15) & ~(size_t)15;
-        for (int i = tid; i < Sn * TRC_OBB_STRIDE; i += THREADS) lb[(i / TRC_OBB_STRIDE) * TRC_OBB_LSTRIDE + i % TRC_OBB_STRIDE] = sc.a_obb[i];
-        obb = lb;
-        float *ls = (float *)cur; cur += (size_t)Sn * 6 * 4;
-        for (int i = tid; i < Sn * 6; i += THREADS) ls[i] = sc.a_sbox[i];
-        A.sbox = ls;
-        if (!FRESH) {
-            int32_t *lf = (int32_t *)cur; cur += (((size_t)Sn * 4) + 15) & ~(size_t)15;
-            for (int i = tid; i < Sn; i += THREADS) lf[i] = sc.sflags[i];
-            sflags = lf;
+    if constexpr (GRIDM == 2) {
+        // (the large grid has no tables in LDS: its two parts are carved here, in the layout's order -- through the layout the
+        // instances of this form changed their scratch)
+        if (FRESH) { l_bf = (trc_buie_fast *)cur; cur += (sizeof(trc_buie_fast) + 15) & ~(size_t)15; }
+        // one bit per cell that lists anything, in LDS when the host found room for it -- most cells of a ray's way are empty, and
+        // a step through one then reads nothing from memory
+        if (S.bg_occ_words > 0) {
+            uint32_t *l_occ = (uint32_t *)cur; cur += (((size_t)S.bg_occ_words * 4) + 15) & ~(size_t)15;
+            for (int i = tid; i < S.bg_occ_words; i += THREADS) l_occ[i] = sc.a_bg_occ[i];
+            occ = l_occ;
         }
-        if (GRIDM == 1) {
-            uint16_t *l_goff = (uint16_t *)cur;
-            for (int i = tid; i < sc.a_g_ncell + 1; i += THREADS) l_goff[i] = sc.a_goff[i];
-            uint16_t *l_list = l_goff + ((sc.a_g_ncell + 2) & ~1);
-            for (int i = tid; i < sc.a_g_nlist; i += THREADS) l_list[i] = sc.a_glist[i];
-            G.off = (decltype(G.off))l_goff; G.list = (decltype(G.list))l_list;
-            cur = (char *)(l_list + sc.a_g_nlist);
+    } else {
+        const trc_lds_parts parts = bounce_lds_parts(Sn, sc.stride, FRESH, LDS, LDS && !FRESH, (LDS && GRIDM == 1) ? sc.a_g_ncell : 0, sc.a_g_nlist, 0, 0);
+        const trc_lds_layout L = trc_search_lds_layout(parts);
+        if (FRESH) l_bf = (trc_buie_fast *)(cur + L.buie);
+        stage_search_tables<THREADS>(cur, L, parts, sc, S.fp, tid);
+        if (LDS) {
+            recs = (const double *)(cur + L.recs); obb = (const float *)(cur + L.obb);
+            A.sbox = (const float *)(cur + L.sbox);
+            if (!FRESH) sflags = (const int32_t *)(cur + L.flags);
+            if (GRIDM == 1) { G.off = (decltype(G.off))(cur + L.grid_off); G.list = (decltype(G.list))(cur + L.grid_list); }
         }
+        cur += L.end;
     }
     // split_terminal == 2: the hits on surfaces that end every ray are finished HERE (what k_s_absorb does behind a list: hit point,
     // tallies, flux-map bin, hit capture) -- the list entry, its re-read, the second read of the ray record and a launch less per
@@ -934,12 +821,8 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
     if (absorb_here && P.capture && wave_a < SHADE_MAX_WAVES) hit_chunk_resume(hc, W.hit_state + 2 * wave_a, S.hit_epoch);
     unsigned n_term = 0;
     const bool buie_src = FRESH && P.src && (P.src->kind == TRC_SRC_BUIE_DISK || P.src->kind == TRC_SRC_BUIE_RECT);
-    if (FRESH) {
-        if (buie_src) trc_buie_fast_fill(P.src->buie, l_bf, 0, tid, THREADS);
-        __syncthreads();
-        if (buie_src) trc_buie_fast_fill(P.src->buie, l_bf, 1, tid, THREADS);
-    }
-    __syncthreads();
+    if (FRESH) buie_tables_fill(P.src, l_bf, tid, THREADS, buie_src);
+    else __syncthreads();
     if (W.cnt[CN(CW_OVERFLOW)]) return;
     // the rays: the active list (slots), or fresh rays by number -- all of the batch or those k_s_cull left to this path
     const uint32_t *list = FRESH ? S.gen_list : S.act_in;
@@ -1185,17 +1068,8 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
             if (hit) {
                 if ((long long)sl < SQ_ROOM(W)) {
                     slot = (uint32_t)sl;
-                    SRayGeo g;
-                    g.px = px; g.py = py; g.pz = pz; g.dx = dx; g.dy = dy; g.dz = dz;
-                    g.head = SQ_INVALID;
-                    g.idx = ri;
-                    g.tail = sray_tail(0, 0u);
-                    W.geo[slot] = g;
-                    if (!P.src) {      // rays of a source descriptor all carry (energy, 1, 0); given rays their own
-                        SRayAux a;
-                        a.e = e0; a.ref = ref0; a.wl = wl0; a.pad = 0.0;
-                        W.aux[slot] = a;
-                    }
+                    if (P.src) store_fresh_ray(W, slot, ri, px, py, pz, dx, dy, dz);
+                    else store_fresh_ray(W, slot, ri, px, py, pz, dx, dy, dz, e0, ref0, wl0);
                 } else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
             }
         }
@@ -1270,11 +1144,7 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
 //            that gave that distance, the lowest surface index: the reference's tie rule (tracer_engine.py:58-63);
 // and a ray stops walking at the first cell that starts behind its nearest hit so far.  Same candidates (a superset is tested
 // exactly where a ray's walk runs a stage ahead of its exact tests), same exact test, same results as k_s_bounce<2>.
-#ifndef SBC_CELLS
-#define SBC_CELLS 4             /* cells with faces a lane collects per stage */
-#endif
-#define SBC_PAIRS 256           /* (ray, surface) pairs that can wait for their exact test, per wave */
-#define SBC_WAVE_BYTES (2 * SBC_CELLS * 64 * 4 + 64 * 4 + SBC_PAIRS * 4 + 64 * 8 + 64 * 4)
+// (SBC_CELLS, SBC_PAIRS and SBC_WAVE_BYTES, the wave's block of LDS, stand with the LDS layout in trc_bounds.h)
 template <bool FRESH, bool FLAT, bool SUN = false>
 __global__ __launch_bounds__(SB_THREADS) void k_s_bounce_coop(StreamParams S) {
     constexpr int THREADS = SB_THREADS;
@@ -2425,6 +2295,11 @@ static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene 
     return TRC_OK;
 }
 
+// Dynamic LDS of a search kernel from its image (trc_search_lds_layout): what a fits-in-LDS decision compares with its limit, and what
+// a launch asks for -- 16 bytes more, so that it is never 0 and a block the kernel puts behind the image can start on 16 bytes
+static size_t lds_need(const trc_lds_layout &L) { return L.end + L.slack; }
+static size_t lds_request(const trc_lds_layout &L) { return lds_need(L) + 16; }
+
 // fresh rays of a plane source with a narrow cone: footprint map, k_s_cull + k_s_fresh (trc_footprint.h)
 static int stream_form_fresh(StreamForms &F, StreamParams &SP0, trc_scene *sc, StreamEngine &E, const trc_source_desc *src_desc, const StreamKnobs &K) {
     F.general_share = 0.0; F.listed_share = 1.0;
@@ -2440,13 +2315,11 @@ static int stream_form_fresh(StreamForms &F, StreamParams &SP0, trc_scene *sc, S
     bool fresh_in_lds = false;
     // the Buie sources go through the two-phase form (k_s_fresh2): a queue of SFQ_CAP (ray, cell) pairs per wave
     const bool fresh_two = buie;
-    size_t lds_fresh = buie ? ((sizeof(trc_buie_fast) + 15) & ~(size_t)15) : 0;
-    const size_t b_obb = (size_t)S * TRC_OBB_LSTRIDE * 4 + 16, b_recs = (size_t)S * sc->stride * 8;
+    // (the kernels' own description of their LDS image; the lists are 16-bit there)
     const size_t n_list = E.fp->clist.size();
-    const size_t b_lists = ((((size_t)SP0.fp.P.Mc * SP0.fp.P.Mc + 1) * 2 + 15) & ~(size_t)15) + n_list * 2 + 16;
-    const size_t b_queue = fresh_two ? (size_t)(sf_threads / 64) * 2 * SFQ_CAP * 4 + 16 : 0;
-    if (n_list < 65536 && lds_fresh + b_obb + b_recs + b_lists + b_queue <= 150 * 1024) { fresh_in_lds = true; lds_fresh += b_obb + b_recs + b_lists; }
-    lds_fresh += 32 + b_queue;
+    const int queue_waves = fresh_two ? sf_threads / 64 : 0;
+    if (n_list < 65536) fresh_in_lds = lds_need(trc_search_lds_layout(fresh_lds_parts(S, sc->stride, SP0.fp.P, (long long)n_list, buie, true, queue_waves))) <= 150 * 1024;
+    const size_t lds_fresh = lds_request(trc_search_lds_layout(fresh_lds_parts(S, sc->stride, SP0.fp.P, (long long)n_list, buie, fresh_in_lds, queue_waves)));
 #define SF_PICK(K) (flat ? (fresh_in_lds ? (const void *)k_s_fresh<K, true, true> : (const void *)k_s_fresh<K, true, false>) \
                          : (fresh_in_lds ? (const void *)k_s_fresh<K, false, true> : (const void *)k_s_fresh<K, false, false>))
     // (the tabulated sunshapes: the general <kind, flat, lds> form, their table read from global memory, where it stays in L2)
@@ -2488,20 +2361,17 @@ static int stream_form_bounce(StreamForms &F, StreamParams &SP0, const trc_scene
     F.use_first = big || F.small_scene || (K.first && plan.mode != 1);
     if (!F.use_fused && !F.use_first) return TRC_OK;
     const int gridm = F.gridm;
-    const size_t b_grid = plan.mode == 2 ? ((((size_t)sc->accel.grid_off.size() + 2) & ~(size_t)1) * 2 + sc->accel.grid_list.size() * 2 + 8) : 0;
-    const size_t b_all = (size_t)S * 24 + (size_t)S * TRC_OBB_LSTRIDE * 4 + 16 + (size_t)S * sc->stride * 8 + b_grid + (((size_t)S * 4 + 15) & ~(size_t)15);
-    const size_t b_buie = ((sizeof(trc_buie_fast) + 15) & ~(size_t)15);
-    const bool in_lds = gridm != 2 && gridm != 3 && b_all + b_buie <= 150 * 1024;
-    size_t lds_bounce = (in_lds ? b_all : 0) + 16;
+    // One decision for the instance of the continued rays and that of the fresh ones: the tables go to LDS when an image with the
+    // parts of both (the Buie table of the one, the flags of the other) fits; the fresh instance is sized by that image
+    const int g_cells = plan.mode == 2 ? (int)sc->accel.grid_off.size() - 1 : 0, g_list = (int)sc->accel.grid_list.size();
+    const bool in_lds = gridm != 2 && gridm != 3 && lds_need(trc_search_lds_layout(bounce_lds_parts(S, sc->stride, true, true, true, g_cells, g_list, 0, 0))) <= 150 * 1024;
     SP0.bg_occ_words = 0;
     // the large grid: k_s_bounce_coop, whose lanes share the tests of their wave's rays
     const bool coop = F.coop = gridm == 2 && K.coop;
-    if (coop) lds_bounce += (size_t)(SB_THREADS / 64) * SBC_WAVE_BYTES;
-    if (gridm == 2 && sc->accel.big_occ.size() * 4 <= (coop ? 80 : 96) * 1024) {      // the occupancy bits of the large grid
-        SP0.bg_occ_words = (int)sc->accel.big_occ.size();
-        lds_bounce += (sc->accel.big_occ.size() * 4 + 15) & ~(size_t)15;
-    }
-    const size_t lds_first = lds_bounce + b_buie;
+    if (gridm == 2 && sc->accel.big_occ.size() * 4 <= (coop ? 80 : 96) * 1024) SP0.bg_occ_words = (int)sc->accel.big_occ.size();      // the occupancy bits of the large grid
+    const int coop_waves = coop ? SB_THREADS / 64 : 0;
+    const size_t lds_bounce = lds_request(trc_search_lds_layout(bounce_lds_parts(S, sc->stride, false, in_lds, in_lds, in_lds ? g_cells : 0, g_list, SP0.bg_occ_words, coop_waves)));
+    const size_t lds_first = lds_request(trc_search_lds_layout(bounce_lds_parts(S, sc->stride, true, in_lds, in_lds, in_lds ? g_cells : 0, g_list, SP0.bg_occ_words, coop_waves)));
 #define SB_PICK(FR, FL, SN) (gridm == 3 ? (const void *)k_s_bounce<3, false, FR, FL, SN> : gridm == 2 ? (coop ? (const void *)k_s_bounce_coop<FR, FL, SN> : (const void *)k_s_bounce<2, false, FR, FL, SN>) \
                            : gridm == 1 ? (in_lds ? (const void *)k_s_bounce<1, true, FR, FL, SN> : (const void *)k_s_bounce<1, false, FR, FL, SN>) \
                                         : (in_lds ? (const void *)k_s_bounce<0, true, FR, FL, SN> : (const void *)k_s_bounce<0, false, FR, FL, SN>))
