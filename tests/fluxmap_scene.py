@@ -117,17 +117,27 @@ def host_maps(hits, frames, edges):
     return out
 
 
-def hits_of_levels(levels):
+def hits_of_levels(levels, keep=None):
     """the hit list of a recorded trace (the levels of the ordered engine's tree or of oracle.engine, one ray out per hit): a ray
-    of level k + 1 starts where its parent of level k landed, on `surf`, and what the parent lost there was absorbed"""
-    surf, e_abs, pts = [], [], []
+    of level k + 1 starts where its parent of level k landed, on `surf`, and what the parent lost there was absorbed.  Levels
+    that carry directions (oracle.engine's) give the incident energy and direction of every hit as well: what a full capture holds.
+    keep: level -> mask of its rays that stand for a hit (default: all of them)."""
+    surf, e_abs, pts, e_in, dirs = [], [], [], [], []
+    with_dirs = all('directions' in L for L in levels[:-1])       # (the ordered engine's level 0 is given as energies alone: no directions then)
     for prev, L in zip(levels[:-1], levels[1:]):
-        par = N.asarray(L['parents'])
+        m = N.ones(len(L['parents']), dtype=bool) if keep is None else keep(L)
+        par = N.asarray(L['parents'])[m]
         assert len(N.unique(par)) == len(par)           # (no optics of this scene sends two rays on)
-        surf.append(N.asarray(L['surf']))
-        e_abs.append(N.asarray(prev['energy'])[par] - N.asarray(L['energy']))
-        pts.append(N.asarray(L['vertices']))
-    return dict(surf=N.concatenate(surf), e_abs=N.concatenate(e_abs), points=N.hstack(pts))
+        surf.append(N.asarray(L['surf'])[m])
+        e_in.append(N.asarray(prev['energy'])[par])
+        e_abs.append(e_in[-1] - N.asarray(L['energy'])[m])
+        pts.append(N.asarray(L['vertices'])[:, m])
+        if with_dirs:
+            dirs.append(N.asarray(prev['directions'])[:, par])
+    out = dict(surf=N.concatenate(surf), e_abs=N.concatenate(e_abs), points=N.hstack(pts), e_in=N.concatenate(e_in))
+    if with_dirs:
+        out['directions'] = N.hstack(dirs)
+    return out
 
 
 def check_inputs(ref, edges, min_filled=0.10):

@@ -373,10 +373,12 @@ def test_engines_vs_oracle_monte_carlo(ctx):
     assert N.array_equal(h2, ref['hits']) and N.allclose(a2, ref['absorbed'], rtol=1e-9, atol=1e-9) and N.allclose(r2, ref['received'], rtol=1e-9, atol=1e-9)
     assert st2.segments == ref['segments'] and st2.rays_left == st.rays_left and st2.hits == st.hits
     if st.rays_left:
-        mine = N.vstack(last)[:, N.lexsort(N.round(N.vstack(last[:3]), 6))]
         theirs = N.vstack((ref['last_vertices'], ref['last_directions'], ref['last_energy'][None, :]))
         theirs = theirs[:, N.lexsort(N.round(ref['last_vertices'], 6))]
-        assert N.allclose(mine, theirs, rtol=1e-8, atol=1e-7)
+        for form, left in (('megakernel', last), ('stream', last2)):
+            mine = N.vstack(left)[:, N.lexsort(N.round(N.vstack(left[:3]), 6))]
+            assert mine.shape == theirs.shape, form
+            assert N.allclose(mine, theirs, rtol=1e-8, atol=1e-7), form
 
 
 def test_kd_accel_equals_brute_and_reference(ctx):
