@@ -539,6 +539,23 @@ struct StreamParams {
     CarryIn carry;      // (last: see CarryIn)
 };
 
+// The kernel's argument block read again where it stands in the kernel-argument segment.  What a kernel reads from its by-value
+// argument the compiler loads once, at the top, and keeps -- in scalar registers, and beyond ~100 of them in lanes of a vector
+// register, every use then a v_readlane_b32: a vector instruction.  Read through this pointer the values are fetched by scalar
+// loads where they are used, from the scalar cache, and are dead at the end of the loop body; k_s_bounce and k_s_fresh2
+// call it at the top of every turn of their loops.
+// It holds for a kernel whose ONLY explicit argument is one ARGS by value: the explicit arguments start at offset 0 of the segment.
+// The effect (not the result) rests on the compiler not seeing through the empty asm, so that it cannot tell that the address is
+// the same in every turn; a compiler that does would load the arguments once again, as before.  Figures: profiles/lean_args.txt
+// (hipcc of ROCm 7.2).
+template <class ARGS>
+__device__ __forceinline__ const ARGS *kernel_args_again() {
+    static_assert(std::is_trivially_copyable<ARGS>::value, "the block is read as the bytes the launch copied into the segment");
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return (const ARGS *)p;
+}
+
 // optics classes of the shading stage.  MIRROR and DIFFUSE are served by lean kernels (trc_shade.hip: <= 128 registers, four
 // waves per SIMD and more); everything else -- refraction, media, conductors, incidence-angle modifiers -- by k_s_shade.
 #define TRC_CLS_MIRROR 0       /* Transparent, Reflective, OneSidedReflective, RealReflective, OneSidedRealReflective (no IAM) */

@@ -336,9 +336,12 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh(StreamParams S) {
 // rays that pass wait in a queue of the wave in LDS; whenever 64 of them have come together the wave runs phase 2 with every
 // lane busy: the float64 ray, boxes and exact tests exactly as k_s_fresh does them.
 template <int KIND, bool FLAT, bool LDS>
-__global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh2(StreamParams S) {
+__global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh2(StreamParams S0) {
     constexpr int THREADS = SF_THREADS(FLAT);
     extern __shared__ double lds[];
+    // (one explicit argument: kernel_args_again.  The instances with their tables in LDS read it again in every turn of the loop;
+    // those with the tables in global memory came out with more vector registers that way and keep the by-value block)
+    const StreamParams &S = S0;
     const FastParams &P = S.P;
     const DScene &sc = P.sc;
     const StreamWs &W = S.W;
@@ -379,7 +382,7 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh2(StreamParams S) {
     const float t_adv = (float)F.t_adv;
     unsigned qh = 0, qt = 0;            // the queue holds entries qh .. qt - 1 (mod SFQ_CAP); the same in every lane
     // phase 2 on up to 64 entries of the queue: what k_s_fresh does for a listed ray
-    auto phase2 = [&](unsigned take) {
+    auto phase2 = [&](const StreamParams &S, unsigned take) {
         const bool active = lane < take;
         uint32_t ri = 0, cell = 0;
         if (active) { ri = q_ray[(qh + lane) & (SFQ_CAP - 1)]; cell = q_cell[(qh + lane) & (SFQ_CAP - 1)]; }
@@ -392,6 +395,13 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh2(StreamParams S) {
         if (i0 < count) { ri_n = W.fq_ray[i0]; cell_n = W.fq_cell[i0]; }
     }
     for (long long i = (long long)blockIdx.x * THREADS + threadIdx.x; i < padded; i += (long long)gridDim.x * THREADS) {
+        // the arguments of this turn: none of them lives across the loop in a scalar register
+        const StreamParams *again = &S0;
+        if constexpr (LDS) again = kernel_args_again<StreamParams>();
+        const StreamParams &S = *again;
+        const FastParams &P = S.P;
+        const StreamWs &W = S.W;
+        const trc_fp_params &F = S.fp.P;
         const uint32_t ri = ri_n, cell = cell_n;
         {
             const long long i1 = i + (long long)gridDim.x * THREADS;
@@ -436,10 +446,12 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh2(StreamParams S) {
             qt += (unsigned)__popcll(m);
         }
         WAVE_SYNC();
-        if (qt - qh >= 64u) { phase2(64u); WAVE_SYNC(); }
+        if (qt - qh >= 64u) { phase2(S, 64u); WAVE_SYNC(); }
     }
-    while (qt != qh) { const unsigned take = qt - qh < 64u ? qt - qh : 64u; phase2(take); }
-    chunk_close(ch, W.hit_slot, SQ_ROOM(W));
+    const StreamParams *last = &S0;
+    if constexpr (LDS) last = kernel_args_again<StreamParams>();
+    while (qt != qh) { const unsigned take = qt - qh < 64u ? qt - qh : 64u; phase2(*last, take); }
+    chunk_close(ch, last->W.hit_slot, SQ_ROOM(last->W));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -729,41 +741,47 @@ __device__ unsigned long long g_sb_stats[32];        /* [0, 16): fresh rays, [16
 #endif
 // SUN: a FRESH instance for the tabulated sunshapes (trc_source_ray_t)
 template <int GRIDM, bool LDS, bool FRESH, bool FLAT = false, bool SUN = false>
-__global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams S) {
+__global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams S0) {
     constexpr int THREADS = SB_THREADS_OF(GRIDM);
     extern __shared__ double lds[];
     constexpr bool GRID = GRIDM == 1 || GRIDM == 2;
     typedef typename std::conditional<GRIDM == 2, trc_grid_view32, trc_grid_view>::type grid_t;
+    // (one explicit argument: kernel_args_again.  AGAIN: the instance reads its arguments again in every turn of its loop and builds
+    // its views of them there -- the continued rays on the LDS-sized grid and on all boxes.  The FRESH instances, the large grid, the
+    // surface-by-surface form and the all-boxes instance with quadrics and its tables in global memory came out with more vector
+    // registers or scratch that way: they keep the views made here from the by-value block, as before)
+    constexpr bool AGAIN = !FRESH && (GRIDM == 1 || (GRIDM == 0 && (LDS || FLAT)));
+    const StreamParams &S = S0;
     const FastParams &P = S.P;
     const DScene &sc = S.P.sc;
     const StreamWs &W = S.W;
     const int Sn = sc.n_surf;
     const int tid = threadIdx.x;
-    trc_accel_view A = stream_accel_global(sc, GRIDM == 1 ? 2 : 0);
+    trc_accel_view A0 = stream_accel_global(sc, GRIDM == 1 ? 2 : 0);
     if (GRIDM == 2) {           // the large grid and the few surfaces set apart from it
 #pragma unroll
-        for (int i = 0; i < 6; ++i) A.root[i] = sc.a_bg_root[i];
-        A.always = sc.a_bg_apart;
-        A.n_always = sc.a_bg_napart;
+        for (int i = 0; i < 6; ++i) A0.root[i] = sc.a_bg_root[i];
+        A0.always = sc.a_bg_apart;
+        A0.n_always = sc.a_bg_napart;
     }
-    const double *recs = sc.recs;
-    const float *obb = sc.a_obb;
+    const double *recs0 = sc.recs;
+    const float *obb0 = sc.a_obb;
     const int32_t *sflags = sc.sflags;
-    grid_t G;
-    memset(&G, 0, sizeof(G));
+    grid_t G0;
+    memset(&G0, 0, sizeof(G0));
     if (GRIDM == 1) {
-        G.off = (decltype(G.off))sc.a_goff; G.list = (decltype(G.list))sc.a_glist;
-        G.nx = sc.a_gdim[0]; G.ny = sc.a_gdim[1]; G.nz = sc.a_gdim[2];
-        G.lox = sc.a_glo[0]; G.loy = sc.a_glo[1]; G.loz = sc.a_glo[2];
-        G.csx = sc.a_gcs[0]; G.csy = sc.a_gcs[1]; G.csz = sc.a_gcs[2];
-        G.ivx = sc.a_ginv[0]; G.ivy = sc.a_ginv[1]; G.ivz = sc.a_ginv[2];
+        G0.off = (decltype(G0.off))sc.a_goff; G0.list = (decltype(G0.list))sc.a_glist;
+        G0.nx = sc.a_gdim[0]; G0.ny = sc.a_gdim[1]; G0.nz = sc.a_gdim[2];
+        G0.lox = sc.a_glo[0]; G0.loy = sc.a_glo[1]; G0.loz = sc.a_glo[2];
+        G0.csx = sc.a_gcs[0]; G0.csy = sc.a_gcs[1]; G0.csz = sc.a_gcs[2];
+        G0.ivx = sc.a_ginv[0]; G0.ivy = sc.a_ginv[1]; G0.ivz = sc.a_ginv[2];
     }
     if (GRIDM == 2) {
-        G.off = (decltype(G.off))sc.a_bg_off; G.list = nullptr;       // (the lists: sc.a_bg_ent)
-        G.nx = sc.a_bg_dim[0]; G.ny = sc.a_bg_dim[1]; G.nz = sc.a_bg_dim[2];
-        G.lox = sc.a_bg_lo[0]; G.loy = sc.a_bg_lo[1]; G.loz = sc.a_bg_lo[2];
-        G.csx = sc.a_bg_cs[0]; G.csy = sc.a_bg_cs[1]; G.csz = sc.a_bg_cs[2];
-        G.ivx = sc.a_bg_inv[0]; G.ivy = sc.a_bg_inv[1]; G.ivz = sc.a_bg_inv[2];
+        G0.off = (decltype(G0.off))sc.a_bg_off; G0.list = nullptr;       // (the lists: sc.a_bg_ent)
+        G0.nx = sc.a_bg_dim[0]; G0.ny = sc.a_bg_dim[1]; G0.nz = sc.a_bg_dim[2];
+        G0.lox = sc.a_bg_lo[0]; G0.loy = sc.a_bg_lo[1]; G0.loz = sc.a_bg_lo[2];
+        G0.csx = sc.a_bg_cs[0]; G0.csy = sc.a_bg_cs[1]; G0.csz = sc.a_bg_cs[2];
+        G0.ivx = sc.a_bg_inv[0]; G0.ivy = sc.a_bg_inv[1]; G0.ivz = sc.a_bg_inv[2];
     }
     // dynamic LDS: [the Buie tables (FRESH)] [occupancy bits (large grid)] [records | oriented boxes | boxes | flags | grid (LDS)]
     char *cur = (char *)lds;
@@ -786,10 +804,10 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
         if (FRESH) l_bf = (trc_buie_fast *)(cur + L.buie);
         stage_search_tables<THREADS>(cur, L, parts, sc, S.fp, tid);
         if (LDS) {
-            recs = (const double *)(cur + L.recs); obb = (const float *)(cur + L.obb);
-            A.sbox = (const float *)(cur + L.sbox);
+            recs0 = (const double *)(cur + L.recs); obb0 = (const float *)(cur + L.obb);
+            A0.sbox = (const float *)(cur + L.sbox);
             if (!FRESH) sflags = (const int32_t *)(cur + L.flags);
-            if (GRIDM == 1) { G.off = (decltype(G.off))(cur + L.grid_off); G.list = (decltype(G.list))(cur + L.grid_list); }
+            if (GRIDM == 1) { G0.off = (decltype(G0.off))(cur + L.grid_off); G0.list = (decltype(G0.list))(cur + L.grid_list); }
         }
         cur += L.end;
     }
@@ -797,11 +815,11 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
     // tallies, flux-map bin, hit capture) -- the list entry, its re-read, the second read of the ray record and a launch less per
     // bounce.  Tallies, flux-map tables and bins of the workgroup in LDS behind the tables of the search.
     const bool absorb_here = !FRESH && S.split_terminal == 2;
-    DScene La = sc;
+    DScene La0 = sc;      // (the workgroup's view for the hits it finishes: its copy of the tally buffer, the tables in LDS)
     double *a_tally = nullptr, *a_fm = nullptr;
     if (absorb_here) {
         cur = (char *)(((uintptr_t)cur + 15) & ~(uintptr_t)15);
-        La.tally = W.tally_part + (size_t)(blockIdx.x % TALLY_PARTS) * (size_t)W.tally_n;
+        La0.tally = W.tally_part + (size_t)(blockIdx.x % TALLY_PARTS) * (size_t)W.tally_n;
         a_tally = (double *)cur; cur += (size_t)(3 * Sn + 2) * 8;
         for (int i = tid; i < 3 * Sn + 2; i += THREADS) a_tally[i] = 0.0;
         double *l_edges = (double *)cur; cur += (size_t)sc.n_fm_edges * 8;
@@ -810,7 +828,7 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
         for (int i = tid; i < sc.n_fm; i += THREADS) l_fms[i] = sc.fms[i];
         int32_t *l_fm_of = (int32_t *)cur; cur += (((size_t)Sn * 4) + 7) & ~(size_t)7;
         for (int i = tid; i < Sn; i += THREADS) l_fm_of[i] = sc.fm_of_surf ? sc.fm_of_surf[i] : -1;
-        La.fm_edges = l_edges; La.fms = l_fms; La.fm_of_surf = l_fm_of; La.sflags = sflags;
+        La0.fm_edges = l_edges; La0.fms = l_fms; La0.fm_of_surf = l_fm_of; La0.sflags = sflags;
         if (S.lds_fm_bins > 0) {
             a_fm = (double *)cur; cur += (size_t)S.lds_fm_bins * 8;
             for (int i = tid; i < S.lds_fm_bins; i += THREADS) a_fm[i] = 0.0;
@@ -837,15 +855,46 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
     // hits on surfaces that end every ray go to a list of their own (k_s_absorb: no optics to sample, a quarter of the registers)
     const bool split = !FRESH && S.split_terminal;
     WaveChunk ct = (split && S.static_first) ? chunk_init_static(S.chunk_thit, wave_g) : chunk_init(S.chunk_thit);
-    uint32_t *const t_slot = W.q1_slot;
-    uint32_t *const t_surf = (uint32_t *)W.q1_a;
-    double *const t_t = (double *)W.q1_b;
     // the entry of the active list for the next iteration is fetched while this one is worked on: the list entry and the ray record
     // behind it are two round trips in a row otherwise
     const long long bstride = (long long)gridDim.x * blockDim.x;
     uint32_t slot_next = SQ_INVALID;
     if (!FRESH) { const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x; if (i0 < count) slot_next = S.act_in[i0]; }
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < padded; i += bstride) {
+        // the arguments of this turn and the views made of them (AGAIN: read again, none of them lives across the loop)
+        const StreamParams *again = &S0;
+        if constexpr (AGAIN) again = kernel_args_again<StreamParams>();
+        const StreamParams &S = *again;
+        const FastParams &P = S.P;
+        const DScene &sc = S.P.sc;
+        const StreamWs &W = S.W;
+        const uint32_t *list = FRESH ? S.gen_list : S.act_in;
+        // (AGAIN: what does not come from the workgroup's LDS is taken from the arguments of this turn; else the views made above)
+        trc_accel_view A_t;
+        grid_t G_t;
+        DScene La_t;
+        if constexpr (AGAIN) {
+            A_t = stream_accel_global(sc, GRIDM == 1 ? 2 : 0);
+            if (LDS) A_t.sbox = A0.sbox;
+            memset(&G_t, 0, sizeof(G_t));
+            if (GRIDM == 1) {
+                G_t.off = LDS ? G0.off : (decltype(G_t.off))sc.a_goff; G_t.list = LDS ? G0.list : (decltype(G_t.list))sc.a_glist;
+                G_t.nx = sc.a_gdim[0]; G_t.ny = sc.a_gdim[1]; G_t.nz = sc.a_gdim[2];
+                G_t.lox = sc.a_glo[0]; G_t.loy = sc.a_glo[1]; G_t.loz = sc.a_glo[2];
+                G_t.csx = sc.a_gcs[0]; G_t.csy = sc.a_gcs[1]; G_t.csz = sc.a_gcs[2];
+                G_t.ivx = sc.a_ginv[0]; G_t.ivy = sc.a_ginv[1]; G_t.ivz = sc.a_ginv[2];
+            }
+            La_t = sc;
+            La_t.tally = La0.tally; La_t.fm_edges = La0.fm_edges; La_t.fms = La0.fms; La_t.fm_of_surf = La0.fm_of_surf; La_t.sflags = La0.sflags;
+        }
+        const trc_accel_view &A = AGAIN ? A_t : A0;
+        const grid_t &G = AGAIN ? G_t : G0;
+        const DScene &La = AGAIN ? La_t : La0;
+        const double *recs = (AGAIN && !LDS) ? sc.recs : recs0;
+        const float *obb = (AGAIN && !LDS) ? sc.a_obb : obb0;
+        uint32_t *const t_slot = W.q1_slot;
+        uint32_t *const t_surf = (uint32_t *)W.q1_a;
+        double *const t_t = (double *)W.q1_b;
         uint32_t slot = SQ_INVALID, ri = SQ_INVALID;
         if (FRESH) { if (i < count) ri = list ? list[i] : (uint32_t)i; }
         else {
@@ -1114,7 +1163,7 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
         }
     }
     chunk_close(ch, W.hit_slot, SQ_ROOM(W));
-    if (split && !absorb_here) chunk_close(ct, t_slot, SQ_ROOM(W));
+    if (split && !absorb_here) chunk_close(ct, W.q1_slot, SQ_ROOM(W));
     if (absorb_here) {
         if (P.capture && wave_a < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_a, S.hit_epoch);
         const double h = wave_sum((double)n_term);
@@ -1124,7 +1173,7 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
             const unsigned long long hh = (unsigned long long)(a_tally[3 * Sn] + 0.5);
             if (hh) { atomicAdd(&W.cnt[CN(CW_HITS)], hh); atomicAdd(&W.cnt[CN(CW_TERM_HITS)], hh); }
         }
-        flush_sums<THREADS>(La.tally, a_tally, 3 * Sn, a_fm, S.lds_fm_bins, Sn);
+        flush_sums<THREADS>(La0.tally, a_tally, 3 * Sn, a_fm, S.lds_fm_bins, Sn);
     }
 }
 
