@@ -75,6 +75,40 @@ def cavity(mirror_turn=0.):
     return Assembly(objects=objs), objs, T
 
 
+def plates(general=False):
+    """
+    (assembly, T): the cavity's box alone, five surfaces -- an ODD count, two maps of different bin counts (PLATES_EDGES) and a
+    non-empty optics table: the scene in which every rounding of the shading kernels' LDS image shows (the surface -> map table of
+    five words ends off 8 bytes, and the optics table and the bins lie behind it).
+
+      0  floor     LambertianReceiver(1.)       ends every ray; map of 3 x 4
+      1  wall +x   Lambertian_directional_axisymmetric_piecewise: a diffuse wall driven by a table of absorptance over angle
+      2  wall -x   ReflectiveReceiver(0.3)      mirror class; map of 5 x 2
+      3  wall +y   LambertianSpecular(0.3, 0.5) diffuse class
+      4  wall -y   Reflective(0.2), or with `general` Reflective_IAM(0.2, 0.2): the general class, which brings k_s_shade in
+    """
+    from tracer_amd.assembly import Assembly
+    from tracer_amd.object import AssembledObject
+    from tracer_amd.surface import Surface
+    from tracer_amd.flat_surface import RectPlateGM
+    from tracer_amd import optics_callables as opt
+    from tracer_amd.spatial_geometry import translate, rotx, roty, rotz
+    T = N.dot(translate(-2.3, 6.1, 1.7), N.dot(rotx(-0.6), N.dot(roty(0.5), rotz(0.8))))
+    half = N.pi / 2.
+    th = N.linspace(0., half, 7)
+    parts = [(RectPlateGM(4., 4.), opt.LambertianReceiver(1.), N.eye(4)),
+             (RectPlateGM(3., 4.), opt.Lambertian_directional_axisymmetric_piecewise(th, 0.2 + 0.4 * N.cos(th)), N.dot(translate(2., 0., 1.5), roty(half))),
+             (RectPlateGM(3., 4.), opt.ReflectiveReceiver(0.3), N.dot(translate(-2., 0., 1.5), roty(half))),
+             (RectPlateGM(4., 3.), opt.LambertianSpecular(0.3, 0.5), N.dot(translate(0., 2., 1.5), rotx(half))),
+             (RectPlateGM(4., 3.), opt.Reflective_IAM(0.2, 0.2) if general else opt.Reflective(0.2), N.dot(translate(0., -2., 1.5), rotx(half)))]
+    objs = [AssembledObject(surfs=[Surface(gm, o)], transform=N.dot(T, tr)) for gm, o, tr in parts]
+    return Assembly(objects=objs), T
+
+
+PLATES_EDGES = {0: (nonuniform(-2., 2., 3), N.linspace(-2., 2., 5)),          # 3 x 4
+                2: (N.linspace(-1.5, 1.5, 6), N.linspace(-2., 2., 3))}        # 5 x 2
+
+
 def mirror_pose(turn):
     from tracer_amd.spatial_geometry import translate, rotx, roty
     return N.dot(translate(0.9, -0.8, 1.2), N.dot(rotx(0.5 + turn), roty(-0.6)))

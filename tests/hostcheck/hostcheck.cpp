@@ -444,4 +444,24 @@ int hc_bin_index(const double *edges, int nbins, const double *x, long n, int *o
     return 0;
 }
 
+// The LDS image of the kernels that finish hits as the library describes it (trc_shade_lds_layout): for each of n rows (image,
+// tables staged or not, surfaces, doubles per record, flux-map edges, bytes of the map descriptors, doubles of optics tables, bins in
+// LDS) the byte offsets of the nine parts, `end`, `slack`, and the limits of the image's decisions without and with bins; and what
+// the host decides for a scene with the row's bins in all (trc_shade_lds_choose, the shading images only): tables in LDS, bins in
+// LDS, the bytes the launch asks for
+int hc_shade_lds_layout(long n, const int *rows, unsigned long long *out) {
+    for (long i = 0; i < n; ++i) {
+        const int *r = rows + 8 * i;
+        const trc_shade_layout L = trc_shade_lds_layout(trc_shade_lds_parts(r[0], r[1] != 0, r[2], r[3], r[4], r[5], r[6], r[7]));
+        bool in_lds = false;
+        int bins_in = 0;
+        size_t request = 0;
+        if (r[0] != TRC_IMG_ABSORB && r[0] != TRC_IMG_INLINE) request = trc_shade_lds_choose(r[0], r[2], r[3], r[4], r[5], r[6], r[7], &in_lds, &bins_in);
+        const size_t v[16] = {L.tally, L.recs, L.opt, L.fm_edges, L.fms, L.fm_of, L.flags, L.extra, L.bins, L.end, L.slack,
+                              trc_shade_lds_limit(r[0], false), trc_shade_lds_limit(r[0], true), (size_t)in_lds, (size_t)bins_in, request};
+        for (int k = 0; k < 16; ++k) out[16 * i + k] = (unsigned long long)v[k];
+    }
+    return 0;
+}
+
 }  // extern "C"

@@ -317,3 +317,61 @@ def test_maps_of_the_spectral_paths(ctx, cavity, kind, regime):
     assert st.segments > 1.5 * n
     _check(dev, ref, edges, (kind, regime))
     dev.close()
+
+
+# -- five plates: the LDS image of every kernel that finishes hits, where its rounding shows -----------------------------------------
+# form: (general class present, the rays carry spectra, environment knobs) -> the kernel whose image the form is there for
+PLATES_FORMS = {'inline': (False, False, {}),                                  # k_s_bounce finishes the floor's hits itself
+                'absorb-list': (False, False, {'TRC_STREAM_ABSORB': 1}),       # k_s_absorb
+                'lean': (False, False, {'TRC_STREAM_ABSORB': 0}),              # k_s_shade_c of both classes, the floor's hits too
+                'general': (True, False, {'TRC_STREAM_ABSORB': 0}),            # ... and k_s_shade
+                'carried': (False, True, {})}                                  # k_s_shade_x
+
+
+@pytest.fixture(scope='module')
+def plates(ctx):
+    """per scene (without / with the general class): compiled scene, frames, the 20 000 rays, and the megakernel's tallies of them"""
+    from tracer_amd.scene import compile_scene
+    out = {}
+    for general in (False, True):
+        asm, T = fs.plates(general)
+        cs = compile_scene(asm)
+        assert cs.n_surf == 5 and len(cs.extra) > 0
+        rays = _given(fs.source(20000, T, 51))
+        mega = _device(ctx, cs, fs.PLATES_EDGES, _capacity(20000))
+        st, _ = mega.trace_fast(rays, 3, EMIN, 51, accel=True, stream=False)
+        out[general] = (cs, [N.array(s._temp_frame) for s in cs.surfaces], rays, [N.array(x) for x in mega.get_tallies()])
+        mega.close()
+    return out
+
+
+@pytest.mark.parametrize('form', sorted(PLATES_FORMS))
+def test_five_plates_two_maps_and_an_optics_table(ctx, plates, form):
+    """An odd surface count, two maps of different bin counts, a table-driven diffuse wall and a floor that ends every ray; 20 000
+    rays, 3 bounces, through every kernel that stages the image (PLATES_FORMS): the device maps against the host histogram of the
+    captured hits, the tallies against the megakernel's of the same rays (no optics of the scene reads a wavelength: rays that
+    carry spectra lose the same shares)."""
+    from tracer_amd.ray_bundle import RayBundle
+    general, carried, knobs = PLATES_FORMS[form]
+    cs, frames, rays, (a0, r0, h0) = plates[general]
+    bundle = rays
+    if carried:
+        n, W = 20000, 3
+        rng = N.random.RandomState(8)
+        swl = N.sort(rng.uniform(0.3e-6, 2.5e-6, size=(W, n)), axis=0)
+        spec = rng.uniform(0.5, 2., size=(W, n))
+        spec *= N.asarray(rays.get_energy()) / N.trapezoid(spec, swl, axis=0)
+        bundle = RayBundle(vertices=N.array(rays.get_vertices()), directions=N.array(rays.get_directions()),
+                           energy=N.trapezoid(spec, swl, axis=0), spectra=spec, wavelengths=swl)
+    dev = _device(ctx, cs, fs.PLATES_EDGES, _capacity(20000))
+    with env(**knobs):
+        st, _ = dev.trace_fast(bundle, 3, EMIN, 51, accel=True, stream=True)
+    assert st.hits_dropped == 0
+    ref = _captured(dev, frames, fs.PLATES_EDGES)
+    fs.check_inputs(ref, fs.PLATES_EDGES)
+    _check(dev, ref, fs.PLATES_EDGES, ('plates', form))
+    a, r, h = dev.get_tallies()
+    print('plates %s: hits %s, absorbed %s' % (form, h, a))
+    assert h0.sum() > 20000 and (h0 > 500).all()
+    assert N.array_equal(h, h0) and N.allclose(a, a0, rtol=1e-9, atol=0.) and N.allclose(r, r0, rtol=1e-9, atol=0.)
+    dev.close()

@@ -4,10 +4,16 @@ a device from the oracle and the restated sums of stream_form_shade alone (shade
 the instances it is there for, with its byte sum on the intended side of the limit; its rays hit every optics kind of its classes,
 its curved surfaces, its captured surfaces inside and outside the map; some rays are culled on the way and some survive; and no
 ray is near a tie -- two surfaces at nearly the same distance, an energy nearly at min_energy -- so that the device tests exclude
-no ray at all.  This says nothing about the library: which instances ran on a device is recorded in profiles/shade_instances.txt.
+no ray at all.  Which instances ran on a device is recorded in profiles/shade_instances.txt.
+
+The sums themselves are held to the library: trc_shade_lds_layout (csrc/trc_bounds.h), the one description of the LDS image the
+kernels carve from and the host sizes launches by, exported by the host-compiled check library, must give the restated sums of
+shade_cases.py to the byte -- for the cases, and for random scenes on both sides of every limit.
 """
+import ctypes as C
 import os
 import subprocess
+import types
 
 import numpy as N
 import pytest
@@ -19,7 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope='module')
 def hostcheck():
-    subprocess.check_call(['make', '-s', '-C', ROOT, 'hostcheck'])          # (the wavelength sampler of the SPEC cases)
+    subprocess.check_call(['make', '-s', '-C', ROOT, 'hostcheck'])          # (the wavelength sampler of the SPEC cases, the LDS layout)
+    return C.CDLL(os.path.join(ROOT, 'tests', 'hostcheck', 'libtrc_hostcheck.so'))
 
 
 @pytest.mark.parametrize('name', sorted(sc.CASES))
@@ -87,3 +94,167 @@ def test_cases_cover_every_instance_that_can_be_selected():
     targets = set(t for v in sc.CASES.values() for t in v[5])
     assert len(sc.ALL_INSTANCES) == 26 and targets == set(sc.ALL_INSTANCES)
     assert set(sc.GIVEN) <= set(sc.CASES) and all(not sc.CASES[n][3] and not sc.CASES[n][4] for n in sc.GIVEN)
+
+
+# -- the library's description of the LDS image against the restated sums ----------------------------------------------------------
+# enum trc_shade_img (csrc/trc_bounds.h)
+IMG_SHADE, IMG_SHADE_X, IMG_LEAN, IMG_LEAN_MIRROR, IMG_ABSORB, IMG_INLINE = range(6)
+PARTS = ('tally', 'recs', 'opt', 'fm_edges', 'fms', 'fm_of', 'flags', 'extra', 'bins')
+END, SLACK, LIMIT, LIMIT_BINS, IN_LDS, BINS_IN, REQUEST = 9, 10, 11, 12, 13, 14, 15
+# what a launch of each image asks for when nothing is staged: the count words (k_s_shade keeps one)
+BARE = {IMG_SHADE: 8, IMG_SHADE_X: 16, IMG_LEAN: 16, IMG_LEAN_MIRROR: 16}
+INLINE_MARGIN = 64          # stream_form_absorb, as it was: `extra_lds = lds_absorb + 64`
+LIMIT_ABSORB, LIMIT_INLINE = 78 * sc.KiB, 158 * sc.KiB         # ... `lds_absorb <= 78 * 1024`, `F.bounce.lds + extra_lds <= 158 * 1024`
+
+
+def lds_layout(hc, rows):
+    """trc_shade_lds_layout of rows (image, tables staged, surfaces, record stride, map edges, descriptor bytes, table doubles, bins in
+    LDS): (n, 16) -- the offsets of PARTS, end, slack, the two limits of the image, and what the host's own decision
+    (trc_shade_lds_choose, the code stream_form_shade calls) makes of a scene with that many bins: tables in LDS, bins in LDS, the bytes
+    its launch asks for"""
+    rows = N.ascontiguousarray(rows, dtype=N.int32).reshape(-1, 8)
+    out = N.zeros((len(rows), 16), dtype=N.uint64)
+    hc.hc_shade_lds_layout.argtypes = [C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]
+    assert hc.hc_shade_lds_layout(len(rows), rows.ctypes.data_as(C.POINTER(C.c_int)), out.ctypes.data_as(C.POINTER(C.c_ulonglong))) == 0
+    return out.astype(N.int64)
+
+
+def check_images(hc, S, stride, n_edges, n_maps, n_extra, bins, old):
+    """
+    The library's images of scenes (arrays, one entry per scene) against the sums `old` = (tallies, records, optics parameters, maps)
+    of shade_cases.table_bytes.  Returns per image the old sum without bins, for the caller to count the scenes near each limit.
+    """
+    n = len(S)
+    fms = n_maps * sc.SIZEOF_FLUXMAPDEV
+    t, r, o, m = [N.asarray(a, dtype=N.int64) for a in old]
+    rows = lambda img, lds, b: N.stack([N.full(n, img), N.full(n, 1) * lds, S, stride, n_edges, fms, n_extra, b], axis=1)
+    sums = {}
+    for img in (IMG_SHADE, IMG_SHADE_X, IMG_LEAN, IMG_LEAN_MIRROR):
+        # stream_form_shade as predict() restates it: tables by `need`, bins by `need + bins * 8 + 16`
+        need = t + r + o + m + (0 if img == IMG_LEAN_MIRROR else n_extra * 8)
+        limit, limit_bins = (sc.LIMIT_LEAN, sc.LIMIT_LEAN_BINS) if img in (IMG_LEAN, IMG_LEAN_MIRROR) else (sc.LIMIT_SHADE, sc.LIMIT_SHADE_BINS)
+        in_lds = need <= limit
+        bins_in = (bins > 0) & in_lds & (need + bins * 8 + 16 <= limit_bins)
+        request = N.where(in_lds, need + N.where(bins_in, bins * 8 + 16, 0), BARE[img])
+        # the library: its image with everything staged, without and with the bins, and the decision the host makes of the scene
+        L0 = lds_layout(hc, rows(img, 1, 0 * bins))
+        L1 = lds_layout(hc, rows(img, 1, bins))
+        assert (L0[:, LIMIT] == limit).all() and (L0[:, LIMIT_BINS] == limit_bins).all()
+        assert N.array_equal(L0[:, END] + L0[:, SLACK], need)
+        assert N.array_equal(L1[:, END] + L1[:, SLACK], need + N.where(bins > 0, bins * 8 + 16, 0))
+        lib_in, lib_bins = L1[:, IN_LDS] == 1, L1[:, BINS_IN] > 0
+        assert N.array_equal(lib_in, in_lds) and N.array_equal(lib_bins, bins_in) and N.array_equal(L1[:, BINS_IN], N.where(bins_in, bins, 0))
+        assert N.array_equal(L1[:, REQUEST], request)
+        L = lds_layout(hc, rows(img, lib_in.astype(int), N.where(lib_bins, bins, 0)))
+        assert N.array_equal(L[:, END] + L[:, SLACK], request)
+        check_parts(L, img, lib_in, S, stride, n_edges, fms, n_extra, N.where(lib_bins, bins, 0), request)
+        sums[img] = (need, need + bins * 8 + 16, bins > 0)
+    # stream_form_absorb, as it was: `b.tally + b.maps + (lds_fm_bins ? bins * 8 : 0) + 16`, with the bins k_s_shade took or none
+    for b_in in (bins, 0 * bins):
+        old_absorb = t + m + b_in * 8 + 16
+        La = lds_layout(hc, rows(IMG_ABSORB, 1, b_in))
+        Li = lds_layout(hc, rows(IMG_INLINE, 1, b_in))
+        assert N.array_equal(La[:, END] + La[:, SLACK], old_absorb) and (La[:, LIMIT_BINS] == LIMIT_ABSORB).all()
+        assert N.array_equal(Li[:, END] + Li[:, SLACK], old_absorb + INLINE_MARGIN) and (Li[:, LIMIT_BINS] == LIMIT_INLINE).all()
+        check_parts(La, IMG_ABSORB, N.ones(n, bool), S, stride, n_edges, fms, n_extra, b_in, old_absorb)
+        # (the inline image starts on the next 16 bytes behind the search image, inside what the launch asks for the two)
+        check_parts(Li, IMG_INLINE, N.ones(n, bool), S, stride, n_edges, fms, n_extra, b_in, old_absorb + INLINE_MARGIN - 15)
+    sums[IMG_ABSORB] = (t + m + bins * 8 + 16, None, None)
+    return sums
+
+
+def check_parts(L, img, in_lds, S, stride, n_edges, fms, n_extra, bins_in, request):
+    """every part behind the one before with room for what the kernel writes there, doubles on 8 bytes, the end inside the request"""
+    terminal = img in (IMG_ABSORB, IMG_INLINE)
+    has = in_lds.astype(N.int64)
+    size = {'tally': (3 * S * has + (1 if img == IMG_SHADE else 2) * (1 - has) + 2 * has) * 8,
+            'recs': 0 if terminal else S * stride * 8 * has, 'opt': 0 if terminal else S * 64 * has,
+            'fm_edges': n_edges * 8 * has, 'fms': fms * has, 'fm_of': S * 4 * has, 'flags': 0 if img == IMG_INLINE else S * 4 * has,
+            'extra': 0 if terminal or img == IMG_LEAN_MIRROR else n_extra * 8 * has, 'bins': bins_in * 8}
+    assert (L[:, 0] == 0).all()
+    for k, name in enumerate(PARTS):
+        nxt = L[:, k + 1] if k + 1 < len(PARTS) else L[:, END]
+        assert (L[:, k] + size[name] <= nxt).all(), name
+        assert (L[:, k] % (4 if name == 'flags' else 8) == 0).all(), name
+    assert (L[:, END] <= request).all()
+
+
+def test_library_layout_gives_the_cases_their_restated_sums(hostcheck):
+    """all 20 cases: predict()'s sum, limit and decisions per instance are those of the library's image of the instance"""
+    for name in sorted(sc.CASES):
+        c = sc.case(name)
+        S = c.cs.n_surf
+        n_edges = sum(len(u) + len(v) for u, v in c.edges.values())
+        bins = sum((len(u) - 1) * (len(v) - 1) for u, v in c.edges.values())
+        one = lambda x: N.array([x], dtype=N.int64)
+        check_images(hostcheck, one(S), one(sc.record_stride(c.cs)), one(n_edges), one(len(c.edges)), one(len(c.cs.extra)), one(bins),
+                     [one(x) for x in sc.table_bytes(c.cs, c.edges)])
+        for inst, (total, limit, in_lds, bins_in) in c.instances.items():
+            img = IMG_SHADE_X if inst.startswith('k_s_shade_x') else IMG_SHADE if inst.startswith('k_s_shade<') else \
+                IMG_LEAN_MIRROR if inst.startswith('k_s_shade_c<0') else IMG_LEAN
+            row = [img, 1, S, sc.record_stride(c.cs), n_edges, len(c.edges) * sc.SIZEOF_FLUXMAPDEV, len(c.cs.extra)]
+            L0, L1 = lds_layout(hostcheck, [row + [0], row + [bins]])
+            assert L0[END] + L0[SLACK] == total and L0[LIMIT] == limit
+            assert (L1[IN_LDS] == 1) == in_lds and (L1[BINS_IN] > 0) == bins_in         # (the host's own decision)
+
+
+def test_library_layout_gives_random_scenes_their_restated_sums(hostcheck, monkeypatch):
+    """
+    1e5 seeded scenes -- 1..3000 surfaces, both record strides of the cases, 0..4 maps of differing edge counts, 0..4000 doubles of
+    optics tables -- half of them drawn freely, half with the surface count solved so that one of the sums lands within 2 KiB of one
+    of its limits: the library's image against shade_cases.table_bytes, to the byte, with the same decisions on both sides of each
+    limit.  (table_bytes as it stands; only its record stride is handed in, where it would walk 3000 descriptors per scene.)
+    """
+    monkeypatch.setattr(sc, 'record_stride', lambda cs: cs.stride)
+    rng = N.random.RandomState(20260)
+    n = 100000
+    targets = [(IMG_SHADE, False), (IMG_SHADE, True), (IMG_LEAN, False), (IMG_LEAN, True), (IMG_ABSORB, False)]
+    limit_of = {(IMG_SHADE, False): sc.LIMIT_SHADE, (IMG_SHADE, True): sc.LIMIT_SHADE_BINS, (IMG_LEAN, False): sc.LIMIT_LEAN,
+                (IMG_LEAN, True): sc.LIMIT_LEAN_BINS, (IMG_ABSORB, False): LIMIT_ABSORB}
+    S, stride, n_edges, n_maps, n_extra, bins, old = [N.zeros(n, dtype=N.int64) for _ in range(6)] + [N.zeros((4, n), dtype=N.int64)]
+    for i in range(n):
+        stride[i] = (17, 21)[rng.randint(2)]
+        img, with_bins = targets[rng.randint(len(targets))]
+        # (a scene aimed at a limit of the bins has a map; at the lean kernels' one, maps of the 30 KiB between their two limits)
+        n_maps[i] = rng.randint(1 if (i % 2 and with_bins) else 0, 5)
+        big = i % 2 and with_bins and img == IMG_LEAN
+        shape = [(rng.randint(30, 80), rng.randint(30, 80)) if big else (rng.randint(1, 40), rng.randint(1, 40)) for _ in range(n_maps[i])]        # (nu, nv)
+        n_extra[i] = rng.randint(4001)
+        n_edges[i] = sum(nu + nv + 2 for nu, nv in shape)
+        bins[i] = sum(nu * nv for nu, nv in shape)
+        S[i] = rng.randint(1, 3001)
+        if i % 2:           # the surface count that puts the target's sum at its limit + d, |d| <= 2 KiB
+            d = rng.randint(-2 * sc.KiB, 2 * sc.KiB + 1)
+            fixed = 2 * 8 + n_edges[i] * 8 + n_maps[i] * sc.SIZEOF_FLUXMAPDEV + 16
+            per = 3 * 8 + 2 * 4
+            if img != IMG_ABSORB:
+                fixed += n_extra[i] * 8
+                per += stride[i] * 8 + 8 * 8
+            if with_bins or img == IMG_ABSORB:
+                fixed += bins[i] * 8 + 16
+            S[i] = min(max((limit_of[(img, with_bins)] + d - fixed) // per, 1), 3000)
+        cs = types.SimpleNamespace(n_surf=int(S[i]), stride=int(stride[i]))
+        edges = dict((k, (range(nu + 1), range(nv + 1))) for k, (nu, nv) in enumerate(shape))
+        old[:, i] = sc.table_bytes(cs, edges)
+    assert (S % 2 == 1).sum() > n // 4 and (S % 2 == 0).sum() > n // 4
+    sums = check_images(hostcheck, S, stride, n_edges, n_maps, n_extra, bins, old)
+    # scenes within 2 KiB of every limit, on both sides
+    near = lambda x, limit, ok: (((x > limit - 2 * sc.KiB) & (x <= limit) & ok).sum(), ((x > limit) & (x <= limit + 2 * sc.KiB) & ok).sum())
+    every = N.ones(n, bool)
+    counts = {'72 KiB': near(sums[IMG_SHADE][0], sc.LIMIT_SHADE, every),
+              '78 KiB, bins': near(sums[IMG_SHADE][1], sc.LIMIT_SHADE_BINS, sums[IMG_SHADE][2] & (sums[IMG_SHADE][0] <= sc.LIMIT_SHADE)),
+              '120 KiB': near(sums[IMG_LEAN][0], sc.LIMIT_LEAN, every),
+              '150 KiB, bins': near(sums[IMG_LEAN][1], sc.LIMIT_LEAN_BINS, sums[IMG_LEAN][2] & (sums[IMG_LEAN][0] <= sc.LIMIT_LEAN)),
+              '78 KiB, k_s_absorb': near(sums[IMG_ABSORB][0], LIMIT_ABSORB, every)}
+    # 158 KiB: k_s_bounce's own request (any, a multiple of 16) + the inline image, with requests drawn to put the total within 2 KiB of
+    # the limit.  The image's bytes were compared above, so this holds the library's limit for it and no more: the addition and the
+    # comparison themselves are host text of stream_form_absorb that no host-compiled code reaches (the device tests of the terminal
+    # surfaces do)
+    d = rng.randint(-2 * sc.KiB, 2 * sc.KiB + 1, size=n)
+    inline_old = sums[IMG_ABSORB][0] + INLINE_MARGIN
+    bounce = N.maximum((LIMIT_INLINE + d - inline_old) // 16 * 16, 16)
+    Li = lds_layout(hostcheck, N.stack([N.full(n, IMG_INLINE), N.ones(n, int), S, stride, n_edges, n_maps * sc.SIZEOF_FLUXMAPDEV, n_extra, bins], axis=1))
+    assert N.array_equal(bounce + Li[:, END] + Li[:, SLACK] <= Li[:, LIMIT_BINS], bounce + inline_old <= LIMIT_INLINE)
+    counts['158 KiB, inline'] = near(bounce + inline_old, LIMIT_INLINE, every)
+    print(counts)
+    assert all(lo >= 100 and hi >= 100 for lo, hi in counts.values()), counts

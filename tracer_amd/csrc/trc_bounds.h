@@ -164,6 +164,104 @@ TRC_HD trc_lds_layout trc_search_lds_layout(const trc_lds_parts &p) {
     return L;
 }
 
+// The LDS image of a kernel of the streaming engine that finishes hits, as the HOST sees it: it sizes the launches and decides "fits in
+// LDS" from this description alone (stream_form_shade, stream_form_absorb, through trc_shade_lds_choose), and
+// tests/test_shade_cases_host.py holds it to the hand-made sums it replaced.  The kernels do NOT read it: each carves its image in its
+// own text (each says why at its carving), and that text is kept in agreement with the order, sizes and rounding written here BY HAND
+// -- whoever changes a carving changes trc_shade_lds_layout with it; the device tests of the maps and of the shading instances are
+// what notices a kernel that carves more than this sums.  The parts follow one another in the order of the layout's fields; a part
+// that is absent takes no room.
+enum trc_shade_img {
+    TRC_IMG_SHADE,              // k_s_shade: every part
+    TRC_IMG_SHADE_X,            // k_s_shade_x: every part
+    TRC_IMG_LEAN,               // k_s_shade_c<DIFFUSE>: every part
+    TRC_IMG_LEAN_MIRROR,        // k_s_shade_c<MIRROR>: no optics tables (no mirror reads one)
+    TRC_IMG_ABSORB,             // k_s_absorb: no records, optics parameters or optics tables
+    TRC_IMG_INLINE              // k_s_bounce where it finishes the terminal hits itself: k_s_absorb's, behind its search image
+};
+#define TRC_LDS_SHADE_SLACK 16      /* bytes a decision allows beside the flux-map tables, and again beside the bins ... */
+#define TRC_LDS_INLINE_SLACK 64     /* ... and for an image that starts behind another one: the margins of the hand-made sums this
+                                       description replaced, kept so that no scene changes sides of a limit (as TRC_LDS_SLACK) */
+struct trc_shade_parts {
+    int n_surf, stride;         // surfaces, doubles per surface record
+    int n_fm_edges, fms_bytes;  // flux maps: edges of all maps (doubles), bytes of the descriptors (n_fm * sizeof(FluxMapDev))
+    int n_extra, fm_bins;       // doubles of the optics tables; bins of all flux maps
+    int counts;                 // words behind the per-surface sums: the workgroup's hits and rays that go on
+    bool tally;                 // the three sums per surface
+    bool recs;                  // surface records and optics parameters (8 doubles per surface)
+    bool maps;                  // flux-map edges, descriptors, surface -> map
+    bool flags;                 // the surface flags behind surface -> map, the two rounded to 8 bytes together.  Without them
+                                // surface -> map is rounded on its own
+    bool extra;                 // the optics tables
+    bool bins;                  // a private copy of the flux-map bins (fm_bins may be 0: the part is there, and its margin)
+};
+struct trc_shade_layout {
+    size_t tally, recs, opt, fm_edges, fms, fm_of, flags, extra, bins;     // byte offset of every part
+    size_t end;                 // bytes in all
+    size_t slack;               // what a fits-in-LDS decision and a launch add to `end`
+};
+// The parts of a kernel's image.  lds: the scene's tables are staged (all of them or none: every access then has a known address
+// space, see k_s_shade); fm_bins: the flux-map bins privatised in LDS, 0: none.  Without tables the two count words remain -- the lean
+// kernels and k_s_shade_x add their counts through them; k_s_shade adds them per wave then and keeps one word that nobody reads.
+// k_s_absorb and k_s_bounce run with their tables in LDS only, and always have a bins part (empty when the scene has no map).
+TRC_HD trc_shade_parts trc_shade_lds_parts(int img, bool lds, int n_surf, int stride, int n_fm_edges, int fms_bytes, int n_extra, int fm_bins) {
+    trc_shade_parts p = {};
+    const bool terminal = img == TRC_IMG_ABSORB || img == TRC_IMG_INLINE;
+    p.n_surf = n_surf; p.stride = stride; p.n_fm_edges = n_fm_edges; p.fms_bytes = fms_bytes; p.n_extra = n_extra; p.fm_bins = fm_bins;
+    p.counts = (img == TRC_IMG_SHADE && !lds) ? 1 : 2;
+    p.tally = p.maps = lds;
+    p.recs = lds && !terminal;
+    p.flags = lds && img != TRC_IMG_INLINE;     // (k_s_bounce reads the flags of its search image)
+    p.extra = lds && !terminal && img != TRC_IMG_LEAN_MIRROR;
+    p.bins = terminal || fm_bins > 0;
+    return p;
+}
+TRC_HD trc_shade_layout trc_shade_lds_layout(const trc_shade_parts &p) {
+    trc_shade_layout L;
+    const size_t S = (size_t)p.n_surf;
+    size_t cur = 0, slack = 0;
+    L.tally = cur; cur += ((p.tally ? 3 * S : 0) + (size_t)p.counts) * 8;
+    L.recs = cur; if (p.recs) cur += S * (size_t)p.stride * 8;
+    L.opt = cur; if (p.recs) cur += S * 8 * 8;
+    L.fm_edges = cur; if (p.maps) cur += (size_t)p.n_fm_edges * 8;
+    L.fms = cur; if (p.maps) cur += (((size_t)p.fms_bytes + 7) / 8) * 8;
+    L.fm_of = cur; if (p.maps) cur += S * 4;
+    L.flags = cur; if (p.maps && p.flags) cur += S * 4;
+    if (p.maps) {
+        const size_t r = (cur + 7) & ~(size_t)7;
+        // flags read from elsewhere take no room here, but the old sum counted them all the same: what of their S * 4 bytes the
+        // rounding of surface -> map does not use up stays in the sum as a margin, beside the one for the start behind another image
+        const size_t borrowed = p.flags ? 0 : cur + S * 4 - r;
+        slack += TRC_LDS_SHADE_SLACK + (p.flags ? 0 : TRC_LDS_INLINE_SLACK) + borrowed;
+        cur = r;
+    }
+    L.extra = cur; if (p.extra) cur += (size_t)p.n_extra * 8;
+    L.bins = cur; if (p.bins) { cur += (size_t)p.fm_bins * 8; slack += TRC_LDS_SHADE_SLACK; }
+    L.end = cur; L.slack = slack;
+    return L;
+}
+// the bytes up to which an image's tables go to LDS, and (bins) up to which the flux-map bins go with them
+TRC_HD size_t trc_shade_lds_limit(int img, bool bins) {
+    switch (img) {
+    case TRC_IMG_SHADE: case TRC_IMG_SHADE_X: return (size_t)(bins ? 78 : 72) * 1024;       // two workgroups per CU
+    case TRC_IMG_LEAN: case TRC_IMG_LEAN_MIRROR: return (size_t)(bins ? 150 : 120) * 1024;  // one workgroup of sixteen waves per CU
+    case TRC_IMG_ABSORB: return (size_t)78 * 1024;
+    default: return (size_t)158 * 1024;          // TRC_IMG_INLINE: with the search image in front
+    }
+}
+// Tables and bins of a shading kernel (not TRC_IMG_ABSORB / TRC_IMG_INLINE, which follow k_s_shade's choice): the tables go to LDS when
+// the image fits the kernel's limit, all `bins` flux-map bins with them when the image still fits the limit set for that (bins are
+// never in LDS without the tables).  Returns the dynamic LDS of the launch: end + slack of the image chosen.
+TRC_HD size_t trc_shade_lds_choose(int img, int n_surf, int stride, int n_fm_edges, int fms_bytes, int n_extra, long long bins, bool *in_lds,
+                                   int *lds_fm_bins) {
+    trc_shade_layout L = trc_shade_lds_layout(trc_shade_lds_parts(img, true, n_surf, stride, n_fm_edges, fms_bytes, n_extra, 0));
+    *in_lds = L.end + L.slack <= trc_shade_lds_limit(img, false);
+    L = trc_shade_lds_layout(trc_shade_lds_parts(img, true, n_surf, stride, n_fm_edges, fms_bytes, n_extra, (int)bins));
+    *lds_fm_bins = (bins > 0 && *in_lds && L.end + L.slack <= trc_shade_lds_limit(img, true)) ? (int)bins : 0;
+    L = trc_shade_lds_layout(trc_shade_lds_parts(img, *in_lds, n_surf, stride, n_fm_edges, fms_bytes, n_extra, *lds_fm_bins));
+    return L.end + L.slack;
+}
+
 struct trc_accel_host {
     std::vector<float> sbox;          // 6 per surface
     std::vector<float> obb;           // TRC_OBB_STRIDE per surface (unbounded: a box nothing misses)

@@ -16,6 +16,7 @@ struct FluxMapDev {
     int64_t bins;              // offset into the tally buffer
     double proj[12];           // global -> local (rows 0..2 of round(inv(frame), 9), surface.py:125)
 };
+static_assert(sizeof(FluxMapDev) == 136, "tests/shade_cases.py (SIZEOF_FLUXMAPDEV) restates this size in the sums of the LDS images");
 
 // device view of a scene, passed by value to kernels
 struct DScene {
@@ -648,6 +649,26 @@ __device__ __forceinline__ void flush_sums(double *tally, const double *l_sums, 
             if (v != 0.0) atomicAdd(&gt[i], v);
         }
     }
+}
+
+// The three sums of a surface (absorbed, incident, hits) for the hit of every lane (ts: its surface, < 0: none): 64 lanes adding to one
+// word take 64 turns, in LDS and in global memory alike.  While at least `share` lanes are on the surface of the first lane still to
+// be served, they are summed in registers and added once, for ROUNDS surfaces at most; the other lanes add for themselves.
+// share == 0: no lanes to share with (a field of hundreds of mirrors), every lane adds for itself.
+template <int ROUNDS>
+__device__ __forceinline__ void tally_by_wave(double *tl, int Sn, int ts, double tea, double tei, int share) {
+    unsigned long long todo = share > 0 ? __ballot(ts >= 0) : 0ull;
+    for (int round = 0; round < ROUNDS && todo; ++round) {
+        const int s0 = __shfl(ts, __ffsll((long long)todo) - 1, 64);
+        const bool in = ts == s0;
+        const unsigned long long m = __ballot(in);
+        if (__popcll(m) < share) break;
+        const double a = wave_sum(in ? tea : 0.0), b = wave_sum(in ? tei : 0.0);
+        if (lane_id() == 0) { atomicAdd(&tl[s0], a); atomicAdd(&tl[Sn + s0], b); atomicAdd(&tl[2 * Sn + s0], (double)__popcll(m)); }
+        if (in) ts = -1;
+        todo &= ~m;
+    }
+    if (ts >= 0) { atomicAdd(&tl[ts], tea); atomicAdd(&tl[Sn + ts], tei); atomicAdd(&tl[2 * Sn + ts], 1.0); }
 }
 
 // the lean shading kernels (trc_shade.hip): kernel of a class for a scene of flat surfaces only (flat) with its tables in LDS (lds)

@@ -1295,24 +1295,9 @@ __global__ __launch_bounds__(256) void k_ord_bounce(OrdParams P) {
             if (c == 0) k0 = k; else k1 = k;
         }
     }
-    {
-        // The three sums per surface: global float64 atomics on one word are served one after the other, and a bounce whose rays
-        // all land on the receiver of a field put 640 000 x 3 of them on three words -- 7.8 ms for a bounce of 6e5 rays.  The
-        // lanes of a wave that share the surface of the first lane still to be served are summed in registers and added once.
-        const int S = sc.n_surf;
-        unsigned long long todo = __ballot(ts >= 0);
-        for (int round = 0; round < 8 && todo; ++round) {
-            const int s0 = __shfl(ts, __ffsll((long long)todo) - 1, 64);
-            const bool in = ts == s0;
-            const unsigned long long m = __ballot(in);
-            if (__popcll(m) < 4) break;
-            const double a = wave_sum(in ? tea : 0.0), b = wave_sum(in ? tei : 0.0);
-            if (lane_id() == 0) { atomicAdd(&sc.tally[s0], a); atomicAdd(&sc.tally[S + s0], b); atomicAdd(&sc.tally[2 * S + s0], (double)__popcll(m)); }
-            if (in) ts = -1;
-            todo &= ~m;
-        }
-        if (ts >= 0) { atomicAdd(&sc.tally[ts], tea); atomicAdd(&sc.tally[S + ts], tei); atomicAdd(&sc.tally[2 * S + ts], 1.0); }
-    }
+    // The three sums per surface: global float64 atomics on one word are served one after the other, and a bounce whose rays all land
+    // on the receiver of a field put 640 000 x 3 of them on three words -- 7.8 ms for a bounce of 6e5 rays: per wave (tally_by_wave)
+    tally_by_wave<8>(sc.tally, sc.n_surf, ts, tea, tei, 4);
     if (live) {
         P.key[i] = k0;
         P.key[P.n + i] = k1;

@@ -30,6 +30,8 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
     const int Sn = sc.n_surf;
     if (W.cnt[CN(CW_OVERFLOW)]) return;
     constexpr unsigned KINDS = CLS == TRC_CLS_MIRROR ? TRC_CLS_MIRROR_KINDS : TRC_CLS_DIFFUSE_KINDS;
+    // (the image of TRC_IMG_LEAN / TRC_IMG_LEAN_MIRROR, trc_shade_lds_layout in trc_bounds.h, by which the host sizes the launch: carved here
+    // in its order -- through a shared staging routine most instances spilled more scalar registers, profiles/shade_layout.txt)
     DScene L = sc;
     // (one of TALLY_PARTS copies of the tally buffer per workgroup, also where the tables are beyond LDS and the sums are added per
     // hit: a single copy -- 2.4 MB for a mesh of 1e5 faces, against 38 MB -- measured slower, 33.8 against 26.9 ms per 1e7 rays)
@@ -163,6 +165,8 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
             // and added once while at least 8 of them do (see k_s_shade); the others add for themselves.  In LDS, or -- a scene whose
             // tables do not fit it: a mesh -- in the workgroup's copy of the tally buffer in global memory, where 64 lanes on one
             // word are served one after the other (the lid over the mesh of 1e5 faces: 10 ms per 5e6 hits on it).
+            // (tally_by_wave, trc_device.h, in this kernel's own text: with the helper the dish configuration of the bench measured
+            // slower, profiles/shade_layout.txt)
             double *tl = LDS ? l_tally : L.tally;
             unsigned long long todo = (!LDS || Sn <= 64) ? __ballot(ts >= 0) : 0ull;
             for (int round = 0; round < 6 && todo; ++round) {
@@ -207,7 +211,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
     const StreamWs &W = S.W;
     const int Sn = sc.n_surf;
     if (W.cnt[CN(CW_OVERFLOW)]) return;
-    DScene L = sc;
+    DScene L = sc;          // (the image of TRC_IMG_SHADE_X, carved here in its order: see k_s_shade_c)
     L.tally = W.tally_part + (size_t)(blockIdx.x % TALLY_PARTS) * (size_t)W.tally_n;
     double *l_tally = lds;
     double *cur = lds + (LDS ? 3 * Sn + 2 : 2);
@@ -379,21 +383,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
                 }
             }
         }
-        {   // the three sums per surface, per wave where lanes share a surface (see k_s_shade_c)
-            double *tl = LDS ? l_tally : L.tally;
-            unsigned long long todo = (!LDS || Sn <= 64) ? __ballot(ts >= 0) : 0ull;
-            for (int round = 0; round < 6 && todo; ++round) {
-                const int s0 = __shfl(ts, __ffsll((long long)todo) - 1, 64);
-                const bool in = ts == s0;
-                const unsigned long long m = __ballot(in);
-                if (__popcll(m) < 8) break;
-                const double a = wave_sum(in ? tea : 0.0), b = wave_sum(in ? tei : 0.0);
-                if (lane_id() == 0) { atomicAdd(&tl[s0], a); atomicAdd(&tl[Sn + s0], b); atomicAdd(&tl[2 * Sn + s0], (double)__popcll(m)); }
-                if (in) ts = -1;
-                todo &= ~m;
-            }
-            if (ts >= 0) { atomicAdd(&tl[ts], tea); atomicAdd(&tl[Sn + ts], tei); atomicAdd(&tl[2 * Sn + ts], 1.0); }
-        }
+        tally_by_wave<6>(LDS ? l_tally : L.tally, Sn, ts, tea, tei, (!LDS || Sn <= 64) ? 8 : 0);     // (the loop of k_s_shade_c)
         if (P.capture) chunk_rebroadcast(hc, __ffsll((long long)my_lanes) - 1);
         const unsigned long long q = chunk_append(&W.cnt[CN(CW_ACT_OUT)], ca, alive, S.act_out, W.act_room);
         if (alive) { if ((long long)q < W.act_room) S.act_out[q] = slot; else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL; n_alive += 1; }

@@ -818,6 +818,8 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
     DScene La0 = sc;      // (the workgroup's view for the hits it finishes: its copy of the tally buffer, the tables in LDS)
     double *a_tally = nullptr, *a_fm = nullptr;
     if (absorb_here) {
+        // (the image of TRC_IMG_INLINE, trc_shade_lds_layout in trc_bounds.h, by which the host sizes it: carved here in its order, on the
+        // next 16 bytes behind the search image -- through a shared staging routine two instances spilled more scalar registers)
         cur = (char *)(((uintptr_t)cur + 15) & ~(uintptr_t)15);
         La0.tally = W.tally_part + (size_t)(blockIdx.x % TALLY_PARTS) * (size_t)W.tally_n;
         a_tally = (double *)cur; cur += (size_t)(3 * Sn + 2) * 8;
@@ -1611,6 +1613,8 @@ __global__ __launch_bounds__(128 * WAVES, WAVES) void k_s_shade(StreamParams S) 
     // LDS: tallies | surface records | optics parameters | flux-map tables and capture flags.  Everything a hit looks up by
     // surface index is read from LDS: from global memory each of them is a dependent round trip (the flux-map bin search
     // alone was twelve of them per hit).
+    // (the image of TRC_IMG_SHADE, trc_shade_lds_layout in trc_bounds.h, by which the host sizes the launch: carved here in its order --
+    // this kernel sits at its register limit, and through a shared staging routine five of its instances spilled more scalar registers)
     FastParams Pl = S.P;
     Pl.sc.tally = W.tally_part + (size_t)(blockIdx.x % TALLY_PARTS) * (size_t)W.tally_n;
     double *l_tally = lds;
@@ -1756,7 +1760,8 @@ __global__ __launch_bounds__(128 * WAVES, WAVES) void k_s_shade(StreamParams S) 
             // The three sums per surface.  64 lanes adding to one word of LDS take 64 turns, and scenes of few surfaces (a dish
             // and its receiver, a cavity of seven walls) put most lanes of a wave on the same ones: while at least 8 lanes share
             // the surface of the first lane still to be served, they are summed in registers and added once; the others add for
-            // themselves.
+            // themselves.  (tally_by_wave, trc_device.h, in this kernel's own text: through the helper two instances spilled more scalar
+            // registers)
             unsigned long long todo = Sn <= 64 ? __ballot(ts >= 0) : 0ull;       // (a field of hundreds of mirrors: no lanes to share with)
             for (int round = 0; round < 6 && todo; ++round) {
                 const int s0 = __shfl(ts, __ffsll((long long)todo) - 1, 64);
@@ -1776,35 +1781,17 @@ __global__ __launch_bounds__(128 * WAVES, WAVES) void k_s_shade(StreamParams S) 
     }
     chunk_close(ca, S.act_out, W.act_room);
     if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
-    // real (unpadded) counts of this bounce: hits and rays that go on -- one pair of atomics per workgroup (through the two
-    // spare words at the end of the LDS tallies), not per wave: they all land on the same two words at the end of the kernel
-    {
-        double h = wave_sum((double)n_hit), a = wave_sum((double)n_alive);
-        if (LDS) {
-            if (lane_id() == 0) { atomicAdd(&l_tally[3 * Sn], h); atomicAdd(&l_tally[3 * Sn + 1], a); }
-        } else if (lane_id() == 0) {
+    // real (unpadded) counts of this bounce: hits and rays that go on -- one pair of atomics per workgroup where the tallies are in
+    // LDS (flush_counts), per wave otherwise: its image has one word there that nobody reads.  (The bins are flushed with the tallies:
+    // they are in LDS only when the tables are -- trc_shade_lds_choose -- so the instances without have none to flush.)
+    if (LDS) {
+        flush_counts<false>(l_tally + 3 * Sn, n_hit, n_alive, &W.cnt[CN(CW_HITS)], &W.cnt[CN(CW_CLS_HITS + TRC_CLS_GENERAL)], &W.cnt[CN(CW_ALIVE)]);
+        flush_sums(Pl.sc.tally, l_tally, 3 * Sn, l_fm, S.lds_fm_bins, Sn);
+    } else {
+        const double h = wave_sum((double)n_hit), a = wave_sum((double)n_alive);
+        if (lane_id() == 0) {
             atomicAdd(&W.cnt[CN(CW_HITS)], (unsigned long long)(h + 0.5)); atomicAdd(&W.cnt[CN(CW_ALIVE)], (unsigned long long)(a + 0.5));
             atomicAdd(&W.cnt[CN(CW_CLS_HITS + TRC_CLS_GENERAL)], (unsigned long long)(h + 0.5));
-        }
-    }
-    if (LDS) {
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            atomicAdd(&W.cnt[CN(CW_HITS)], (unsigned long long)(l_tally[3 * Sn] + 0.5));
-            atomicAdd(&W.cnt[CN(CW_ALIVE)], (unsigned long long)(l_tally[3 * Sn + 1] + 0.5));
-            atomicAdd(&W.cnt[CN(CW_CLS_HITS + TRC_CLS_GENERAL)], (unsigned long long)(l_tally[3 * Sn] + 0.5));
-        }
-        for (int i = threadIdx.x; i < 3 * Sn; i += blockDim.x) {
-            double v = l_tally[i];
-            if (v != 0.0) atomicAdd(&Pl.sc.tally[i], v);
-        }
-    }
-    if (l_fm) {
-        if (!LDS) __syncthreads();
-        double *g = Pl.sc.tally + 3 * Sn + 2;
-        for (int i = threadIdx.x; i < S.lds_fm_bins; i += blockDim.x) {
-            double v = l_fm[i];
-            if (v != 0.0) atomicAdd(&g[i], v);
         }
     }
 }
@@ -1821,6 +1808,8 @@ __global__ __launch_bounds__(SA_THREADS, 2) void k_s_absorb(StreamParams S) {
     const StreamWs &W = S.W;
     const int Sn = sc.n_surf;
     if (W.cnt[CN(CW_OVERFLOW)]) return;
+    // (the image of TRC_IMG_ABSORB, trc_shade_lds_layout in trc_bounds.h, by which the host sizes the launch: carved here in its order --
+    // through a shared staging routine the kernel took six more scalar registers, one wave per SIMD of its eight)
     DScene L = sc;
     L.tally = W.tally_part + (size_t)(blockIdx.x % TALLY_PARTS) * (size_t)W.tally_n;
     double *l_tally = lds;
@@ -2195,12 +2184,15 @@ static int stream_engine_init(StreamEngine *E, trc_ctx *ctx) {
     return TRC_OK;
 }
 
-// The tables the shading kernels stage in LDS, in bytes: tallies, surface records, optics parameters, and the rest -- flux-map
-// edges and descriptors, surface flags and table offsets (k_s_absorb stages the tallies and the rest)
-struct ShadeBytes { size_t tally, recs, opt, maps; };
-static ShadeBytes shade_table_bytes(const trc_scene *sc) {
-    const size_t S = (size_t)sc->n_surf;
-    return {(3 * S + 2) * 8, S * sc->stride * 8, 8 * S * 8, sc->fm_edges_h.size() * 8 + ((sc->fms_h.size() * sizeof(FluxMapDev) + 7) / 8) * 8 + 2 * S * 4 + 16};
+// The LDS image of a kernel that finishes hits (trc_shade_lds_layout, trc_bounds.h) for a scene, and its bytes: what a fits-in-LDS
+// decision compares with trc_shade_lds_limit and what a launch asks for
+static trc_shade_parts shade_lds_parts(const trc_scene *sc, int img, bool lds, long long fm_bins) {
+    return trc_shade_lds_parts(img, lds, sc->n_surf, sc->stride, (int)sc->fm_edges_h.size(), (int)(sc->fms_h.size() * sizeof(FluxMapDev)), sc->n_extra, (int)fm_bins);
+}
+static size_t shade_lds_need(const trc_shade_parts &p) { const trc_shade_layout L = trc_shade_lds_layout(p); return L.end + L.slack; }
+static size_t shade_lds_choose(const trc_scene *sc, int img, long long bins, bool *in_lds, int *lds_fm_bins) {
+    return trc_shade_lds_choose(img, sc->n_surf, sc->stride, (int)sc->fm_edges_h.size(), (int)(sc->fms_h.size() * sizeof(FluxMapDev)), sc->n_extra, bins,
+                                in_lds, lds_fm_bins);
 }
 
 static long long flux_map_bins(const trc_scene *sc) {
@@ -2263,17 +2255,13 @@ static int stream_shade_grid(StreamShadeK &K, int n_cu) {
 static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene *sc, bool carry) {
     const int n_cu = sc->ctx->n_cu;
     const int S = sc->n_surf;
-    const ShadeBytes b = shade_table_bytes(sc);
     const long long bins = flux_map_bins(sc);
-    // k_s_shade: tallies, records, optics parameters, flux-map tables, flags and table values in LDS -- all of them or none (its LDS
-    // instance knows the address space of every table; see the kernel) -- and the flux-map bins too while a workgroup stays within
-    // half a CU's LDS (two workgroups per CU)
-    const size_t all = b.tally + b.recs + b.opt + b.maps + (size_t)sc->n_extra * 8;
-    const bool shade_lds = all <= 72 * 1024;
-    size_t lds_shade = shade_lds ? all : 8;
+    // k_s_shade, or k_s_shade_x for rays that carry more (the same image): tallies, records, optics parameters, flux-map tables, flags
+    // and table values in LDS -- all of them or none (its LDS instance knows the address space of every table; see the kernel) -- and
+    // the flux-map bins too while a workgroup stays within half a CU's LDS (two workgroups per CU)
+    bool shade_lds;
+    const size_t lds_shade = shade_lds_choose(sc, carry ? TRC_IMG_SHADE_X : TRC_IMG_SHADE, bins, &shade_lds, &SP0.lds_fm_bins);
     SP0.P.lds_tally = SP0.lds_tables = SP0.lds_extra = shade_lds ? 1 : 0;
-    SP0.lds_fm_bins = 0;
-    if (bins > 0 && shade_lds && lds_shade + (size_t)bins * 8 + 16 <= 78 * 1024) { SP0.lds_fm_bins = (int)bins; lds_shade += (size_t)bins * 8 + 16; }
     // scenes of flat surfaces with mirror / diffuse optics only (heliostat fields, plate cavities): the lean instance
     bool shade_simple = true;
     for (int i = 0; i < S && shade_simple; ++i)
@@ -2313,12 +2301,9 @@ static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene 
             if (!present[c]) continue;
             StreamShadeK &K = F.shk[n_shk++];
             K.cls = c; K.threads = SHC_THREADS; K.wpb = SHC_THREADS / 64;
-            const size_t need = b.tally + b.recs + b.opt + b.maps + (c == TRC_CLS_MIRROR ? 0 : (size_t)sc->n_extra * 8);
-            const bool in_lds = need <= 120 * 1024;       // (one workgroup of sixteen waves per CU)
-            K.lds = in_lds ? need : 16;
+            bool in_lds;
+            K.lds = shade_lds_choose(sc, c == TRC_CLS_MIRROR ? TRC_IMG_LEAN_MIRROR : TRC_IMG_LEAN, bins, &in_lds, &K.lds_fm_bins);
             K.lds_tables = in_lds ? 1 : 0;
-            K.lds_fm_bins = 0;
-            if (bins > 0 && in_lds && K.lds + (size_t)bins * 8 + 16 <= 150 * 1024) { K.lds_fm_bins = (int)bins; K.lds += (size_t)bins * 8 + 16; }
             K.fn = trc_shade_lean_kernel(c, all_flat, in_lds, spec);
             TRC_TRY(stream_shade_grid(K, n_cu));
         }
@@ -2329,10 +2314,9 @@ static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene 
         // 2 waves per SIMD: four workgroups of 256 per CU in two rounds
         K.fn = shade_fn; K.threads = 256; K.wpb = 4; K.max_blocks = (unsigned)(n_cu * 4); K.lds = lds_shade;
         K.lds_tables = SP0.lds_tables; K.lds_fm_bins = SP0.lds_fm_bins;
-        if (carry) {            // the same tables (k_s_shade_c's carve-up), sixteen waves per workgroup
+        if (carry) {            // sixteen waves per workgroup
             K.fn = trc_shade_carry_kernel(shade_lds);
             K.threads = SHC_THREADS; K.wpb = SHC_THREADS / 64;
-            if (K.lds < 16) K.lds = 16;
             TRC_TRY(stream_shade_grid(K, n_cu));
         } else
             TRC_TRY(kernel_allow_lds(K.fn, K.lds));
@@ -2446,18 +2430,17 @@ static int stream_form_absorb(StreamForms &F, StreamParams &SP0, const trc_scene
     if (!(F.use_fused && SP0.P.lds_tally && SP0.lds_tables && !carry)) return TRC_OK;
     bool any = false;
     for (int i = 0; i < sc->n_surf && !any; ++i) any = surface_ends_every_ray(sc->surfs[i]);
-    const ShadeBytes b = shade_table_bytes(sc);
     const long long bins = flux_map_bins(sc);
-    const size_t lds_absorb = b.tally + b.maps + (SP0.lds_fm_bins ? (size_t)bins * 8 : 0) + 16;
+    const size_t lds_absorb = shade_lds_need(shade_lds_parts(sc, TRC_IMG_ABSORB, true, SP0.lds_fm_bins));
     const bool fm_ok = bins == 0 || SP0.lds_fm_bins > 0;       // (bins outside LDS would be scattered global atomics at eight waves per SIMD: not this kernel)
-    F.use_absorb = any && fm_ok && lds_absorb <= 78 * 1024 && sc->tr_off < 0 && SP0.P.min_energy >= 0.0 && K.absorb != 0;      // (0 <= min_energy: the ray ends there in the reference too)
+    F.use_absorb = any && fm_ok && lds_absorb <= trc_shade_lds_limit(TRC_IMG_ABSORB, true) && sc->tr_off < 0 && SP0.P.min_energy >= 0.0 && K.absorb != 0;      // (0 <= min_energy: the ray ends there in the reference too)
     if (!F.use_absorb) return TRC_OK;
     // one workgroup of 16 waves per CU (4096 waves with open chunks of the hit buffer at most)
     F.absorb = {(const void *)k_s_absorb, SA_THREADS, lds_absorb, (unsigned)sc->ctx->n_cu};
     TRC_TRY(kernel_allow_lds(F.absorb.fn, lds_absorb));
     SP0.split_terminal = 1;
-    const size_t extra_lds = lds_absorb + 64;
-    if (K.absorb != 1 && !(F.gridm == 2 && F.coop) && F.bounce.lds + extra_lds <= 158 * 1024) {
+    const size_t extra_lds = shade_lds_need(shade_lds_parts(sc, TRC_IMG_INLINE, true, SP0.lds_fm_bins));
+    if (K.absorb != 1 && !(F.gridm == 2 && F.coop) && F.bounce.lds + extra_lds <= trc_shade_lds_limit(TRC_IMG_INLINE, true)) {
         // (k_s_bounce keeps the grid cap of its LDS without these tables)
         F.absorb_inline = true;
         F.bounce.lds += extra_lds;
