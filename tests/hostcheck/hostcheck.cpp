@@ -464,4 +464,72 @@ int hc_shade_lds_layout(long n, const int *rows, unsigned long long *out) {
     return 0;
 }
 
+// The LDS image of the search kernels as the library describes it (trc_search_lds_layout): for each of n rows of 13 numbers -- the
+// fields of trc_lds_parts in their order -- the byte offsets of the twelve parts, `end` and `slack`
+int hc_search_lds_layout(long n, const int *rows, unsigned long long *out) {
+    for (long i = 0; i < n; ++i) {
+        const int *r = rows + 13 * i;
+        trc_lds_parts p = {};
+        p.n_surf = r[0]; p.stride = r[1]; p.buie_bytes = r[2]; p.occ_words = r[3]; p.tables = r[4] != 0; p.sbox = r[5] != 0; p.flags = r[6] != 0;
+        p.fp_offs = r[7]; p.fp_list = r[8]; p.grid_cells = r[9]; p.grid_list = r[10]; p.queue_waves = r[11]; p.coop_waves = r[12];
+        const trc_lds_layout L = trc_search_lds_layout(p);
+        const size_t v[14] = {L.buie, L.occ, L.recs, L.obb, L.sbox, L.flags, L.fp_off, L.fp_list, L.grid_off, L.grid_list, L.queues, L.coop, L.end, L.slack};
+        for (int k = 0; k < 14; ++k) out[14 * i + k] = (unsigned long long)v[k];
+    }
+    return 0;
+}
+
+// What the streaming engine's choice of search kernels reads off a scene and a source (stream_plan, stream_form_fresh,
+// stream_form_bounce): the search structures as trc_scene_create builds them and the footprint map of `src` (null: none) at M cells.
+// out[0] small grid ok, [1] its cells, [2] its list entries, [3] large grid ok, [4] its occupancy words, [5] entries of the list of all
+// boxes, [6] unbounded surfaces, [7] footprint map ok, [8] Mc, [9] its list entries, [10] coverage, [11] has_generic, [12] cdf_end,
+// [13] sizeof(trc_buie_fast)
+int hc_search_sizes(int n_surf, const trc_surface_desc *surfs, const trc_source_desc *src, int M, double *out) {
+    trc_accel_host H;
+    trc_accel_build_surfaces(surfs, n_surf, H);
+    trc_accel_build_grid(H, n_surf);
+    out[0] = H.grid_ok ? 1.0 : 0.0;
+    out[1] = H.grid_ok ? (double)H.grid_off.size() - 1.0 : 0.0;
+    out[2] = H.grid_ok ? (double)H.grid_list.size() : 0.0;
+    trc_accel_build_grid32(surfs, n_surf, H);
+    out[3] = H.big_ok ? 1.0 : 0.0;
+    out[4] = (double)H.big_occ.size();
+    out[5] = (double)H.brute_leaf.size();
+    out[6] = (double)H.unbounded.size();
+    for (int k = 7; k < 13; ++k) out[k] = 0.0;
+    out[13] = (double)sizeof(trc_buie_fast);
+    if (src) {
+        trc_fp_host F;
+        trc_fp_build(surfs, n_surf, H, *src, F, M);
+        if (F.ok) {
+            out[7] = 1.0; out[8] = (double)F.P.Mc; out[9] = (double)F.clist.size(); out[10] = F.coverage;
+            out[11] = (double)F.P.has_generic; out[12] = F.P.cdf_end;
+        }
+    }
+    return 0;
+}
+
+// Per ray of a source, what k_s_cull decides: bit[i] = its start point lies in a set cell of the footprint map, generic[i] = it takes the
+// general path (trc_fp_generic).  Returns 0, or -3 when the map does not apply.
+int hc_footprint_bits(int n_surf, const trc_surface_desc *surfs, const trc_source_desc *src, long n, uint64_t seed, uint64_t offset, int M,
+                      unsigned char *bit, unsigned char *generic) {
+    trc_accel_host H;
+    trc_accel_build_surfaces(surfs, n_surf, H);
+    trc_fp_host F;
+    trc_fp_build(surfs, n_surf, H, *src, F, M);
+    if (!F.ok) return -3;
+    for (long i = 0; i < n; ++i) {
+        const uint64_t rid = offset + (uint64_t)i;
+        uint32_t o[4];
+        trc_philox4x32_10((uint32_t)rid, (uint32_t)(rid >> 32), 0, 0, (uint32_t)seed, (uint32_t)(seed >> 32), o);
+        float lx, ly;
+        trc_fp_position32(F.P, o, &lx, &ly);
+        int32_t ix, iy;
+        trc_fp_cell(F.P, lx, ly, &ix, &iy);
+        bit[i] = (F.mask[((size_t)iy * F.P.M + ix) >> 5] >> (ix & 31)) & 1u;
+        generic[i] = trc_fp_generic(F.P, o) ? 1 : 0;
+    }
+    return 0;
+}
+
 }  // extern "C"

@@ -53,6 +53,8 @@ CLS_MIRROR, CLS_DIFFUSE, CLS_GENERAL = 0, 1, 2
 
 MAP_TILE, FULL_WALL = 0, 4          # places among the room's own surfaces (behind the fillers): the mapped tile, the wall captured in full
 MAP_EDGES = (fs.nonuniform(-0.7, 0.9, 13), N.linspace(-0.9, 0.6, 10))           # 12 x 9 of a tile of +-0.9: clipped on three sides
+TWIN_AT, TWIN_SIZE = (1.2, -1.3, 1.9), (1.35, 1.35)           # room(ends=True): the twin and the receiver, in the room's own coordinates
+TERMINAL_AT, TERMINAL_SIZE = (-1.3, 1.25, 1.8), (1.3, 1.3)
 
 
 def _kinds():
@@ -150,7 +152,7 @@ def _tables():
     return th, wl, grid
 
 
-def room(kind, n_fill=0, table_len=12):
+def room(kind, n_fill=0, table_len=12, ends=False):
     """
     (assembly, T): a box of 4 x 4 x 3 open at the top -- a floor of four tiles with gaps between them, four walls -- with flat pieces
     hanging inside, turned by a general rotation T and moved off the origin, so that no frame is axis aligned.
@@ -167,6 +169,9 @@ def room(kind, n_fill=0, table_len=12):
     n_fill    filler plates in a grid under the floor, mirrors and Lambertian plates in turn, in front of the room's own surfaces in
               the table (the room's surfaces then sit at offsets of hundreds of records)
     table_len points of the Reflective_spectral disc's table (2 doubles each in n_extra)
+    ends      (search_cases.py) three plates more, behind the room's own surfaces in the table: a twin -- two plates of one frame and one
+              size, a partial mirror and, at the higher index, an absorber: every hit on them is an exact tie -- and a receiver that
+              ends every ray
     """
     from tracer_amd.assembly import Assembly
     from tracer_amd.object import AssembledObject
@@ -227,6 +232,10 @@ def room(kind, n_fill=0, table_len=12):
                    N.dot(translate(0.9, 0.8, 1.7), rotx(0.2)))]
     if kind in ('carry', 'carry-mat'):
         parts += [(RectPlateGM(1.3, 1.3), opt.PeriodicBoundary(-0.35), N.dot(translate(-1.1, -0.3, 1.9), roty(0.25)))]
+    if ends:
+        twin = N.dot(translate(*TWIN_AT), N.dot(rotx(-0.45), roty(-0.35)))
+        parts += [(RectPlateGM(*TWIN_SIZE), opt.Reflective(0.3), twin), (RectPlateGM(*TWIN_SIZE), opt.Lambertian(1.), twin),
+                  (RectPlateGM(*TERMINAL_SIZE), opt.LambertianReceiver(1.), N.dot(translate(*TERMINAL_AT), N.dot(rotx(0.4), roty(0.3))))]
     fill = []
     side = int(N.ceil(N.sqrt(n_fill))) if n_fill else 0
     for k in range(n_fill):
@@ -429,12 +438,22 @@ def hit_list(levels, c):
     return hits
 
 
-def near_ties(name):
+def identical_surfaces(scene):
+    """surfaces of an oracle scene table whose geometry descriptor (kind, frame, parameters) is that of a surface of lower index: a
+    ray meets the two at exactly the same distance, and the reference gives the hit to the lower index"""
+    same = lambda a, b: a['kind'] == b['kind'] and N.array_equal(a['frame'], b['frame']) and N.array_equal(a['gm'], b['gm'])
+    return [k for k in range(len(scene)) if any(same(scene[k], scene[j]) for j in range(k))]
+
+
+def near_ties(name, given=None, identical_as_one=False):
     """(smallest relative gap between a ray's nearest and second-nearest intersection, smallest relative distance of an outgoing
-    energy from min_energy) over every bounce of the reference: what decides whether a ray could end elsewhere on a device"""
+    energy from min_energy) over every bounce of the reference: what decides whether a ray could end elsewhere on a device.
+    given: (compiled scene, reference, min_energy) instead of those of the case `name` (search_cases.py); identical_as_one: a pair of
+    surfaces with identical descriptors counts as one surface -- their tie is exact and decided by index, not a near tie"""
     from oracle import engine, geometry
-    c, o = case(name), reference(name)
-    scene = engine.scene_from_compiled(c.cs)
+    cs, o, min_energy = (case(name).cs, reference(name), case(name).min_energy) if given is None else given
+    scene = engine.scene_from_compiled(cs)
+    skip = identical_surfaces(scene) if identical_as_one else []
     gap = N.inf
     for L in o['levels'][:-1] if len(o['levels']) > REPS else o['levels']:
         n = L['n_live']
@@ -442,7 +461,9 @@ def near_ties(name):
             continue
         v, d = L['vertices'][:, :n], L['directions'][:, :n]
         first, second = N.full(n, N.inf), N.full(n, N.inf)
-        for s in scene:
+        for k, s in enumerate(scene):
+            if k in skip:
+                continue
             t = geometry.intersect(s['kind'], s['frame'], s['gm'], s['extra'], v, d)
             t[t == 0.] = N.inf
             second = N.minimum(second, N.maximum(first, t))
@@ -451,4 +472,4 @@ def near_ties(name):
         if both.any():
             gap = min(gap, ((second[both] - first[both]) / second[both]).min())
     e = N.concatenate([L['energy'] for L in o['levels'][1:]])
-    return gap, N.abs(e / c.min_energy - 1.).min()
+    return gap, N.abs(e / min_energy - 1.).min()

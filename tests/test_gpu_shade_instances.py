@@ -54,13 +54,21 @@ def _by_point(points):
     return N.lexsort((points[2], points[1], points[0]))
 
 
-def _check(ctx, c, o, given, stream, what, **knobs):
+def _check(ctx, c, o, given, stream, what, accel=True, kd=None, scene_knobs=None, warm_up=False, **knobs):
+    """accel, kd: trace_fast's accel, a Kd-tree set on the scene; scene_knobs: knobs around the scene's creation (the library reads them
+    there); warm_up: the call is made twice on the scene -- tallies, hits and maps reset in between -- and checked the second time"""
     from tracer_amd.scene import DeviceScene
-    dev = DeviceScene(c.cs, ctx)
+    with env(**(scene_knobs or {})):
+        dev = DeviceScene(c.cs, ctx)
+    if kd is not None:
+        dev.set_kdtree(kd)
     dev.set_fluxmap(c.map_surf, *c.edges[c.map_surf])
     dev.set_hit_capacity(8 * sc.N_RAYS + 65536)
     with env(**knobs):
-        st, last = dev.trace_fast(c.bundle(given), sc.REPS, c.min_energy, sc.SEED, accel=True, keep_last=True, stream=stream)
+        if warm_up:
+            dev.trace_fast(c.bundle(given), sc.REPS, c.min_energy, sc.SEED, accel=accel, keep_last=True, stream=stream)
+            dev.reset_tallies()
+        st, last = dev.trace_fast(c.bundle(given), sc.REPS, c.min_energy, sc.SEED, accel=accel, keep_last=True, stream=stream)
     a, r, h = dev.get_tallies()
     hits = dev.get_hits()
     nx = dev.hit_spectral_columns()
