@@ -22,6 +22,10 @@ SPECCHECK_SRC := $(ROOT)tests/hostcheck/spectrum_check.cpp
 SUNCHECK := $(ROOT)tests/hostcheck/libtrc_sunshape_check.so
 SUNCHECK_SRC := $(ROOT)tests/hostcheck/sunshape_check.cpp
 
+UMASKCHECK := $(ROOT)tests/umaskcheck/libtrc_umask_check.so
+UMASKCHECK_EXE := $(ROOT)tests/umaskcheck/umask_check
+UMASKCHECK_SRC := $(ROOT)tests/umaskcheck/umask_check.cpp
+
 all: $(LIB)
 
 # -ffp-contract=off: a*b+c is rounded twice, as NumPy rounds it in the reference.  Fused, the same formula rounds differently in
@@ -65,6 +69,17 @@ $(SPECCHECK): $(SPECCHECK_SRC) $(HDR)
 $(SUNCHECK): $(SUNCHECK_SRC) $(HDR)
 	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(SUNCHECK_SRC)
 
+# the footprint map's mask over the uniforms against brute force, host-compiled: a library for its test, and the same as a program
+# (umaskcheck-exe; SAN="-fsanitize=address,undefined" builds it for a sanitizer run)
+umaskcheck: $(UMASKCHECK)
+umaskcheck-exe: $(UMASKCHECK_EXE)
+
+$(UMASKCHECK): $(UMASKCHECK_SRC) $(HDR)
+	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(UMASKCHECK_SRC)
+
+$(UMASKCHECK_EXE): $(UMASKCHECK_SRC) $(HDR)
+	$(CXX) -O2 -g -std=c++17 $(FPFLAGS) $(SAN) -DUMASK_CHECK_MAIN -o $@ $(UMASKCHECK_SRC)
+
 # assembly listings with the registers, scratch and occupancy of every kernel (build/*.s, build/*.resources.txt)
 asm: $(SRCS) $(HDR)
 	mkdir -p $(ROOT)build
@@ -81,4 +96,4 @@ asm-shade: $(CSRC)/trc_shade.hip $(HDR)
 clean:
 	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK)
 
-.PHONY: all hostcheck asm asm-shade clean
+.PHONY: all hostcheck umaskcheck umaskcheck-exe asm asm-shade clean

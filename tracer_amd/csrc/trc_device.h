@@ -466,7 +466,7 @@ struct StreamWs {
     uint32_t *hit_surf;        // resolved it itself (k_s_fresh, k_s_bounce) -- the surface and the distance; SQ_INVALID in hit_surf:
     double *hit_t;             // k_s_shade picks the nearest of the ray's linked candidates (general path, k_s_exact)
     uint32_t *gen_list;        // fresh rays that k_s_cull leaves to the general path (ray numbers in the batch)
-    uint32_t *fq_ray, *fq_cell;   // fresh rays that start inside a footprint: ray number, mask cell (k_s_cull -> k_s_fresh)
+    uint32_t *fq_ray, *fq_cell;   // fresh rays that start inside a footprint: ray number, mask cell (k_s_cull -> k_s_fresh; k_s_ucull writes no cell)
     uint32_t *act[2];
     double *tally_part;        // TALLY_PARTS private copies of the scene's tally buffer (merged at the end of the call)
     long long tally_n;

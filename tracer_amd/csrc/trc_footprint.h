@@ -14,16 +14,28 @@
 // (lx, ly) over [-half, half]^2:
 //   mask   M x M bits: some footprint (+ cell half-diagonal + eps) overlaps the cell          (k_s_fresh stage A, in LDS)
 //   lists  (M/4) x (M/4) cells: the surfaces whose footprint overlaps the cell, ascending    (stage B, candidate tests)
+//   umask  Mu x Mv bits over the source's two position uniforms: some footprint (+ a radius covering the cell's region) overlaps the
+//          region of the start shape that the rays with these top bits of their uniforms start in -- an annular sector of a
+//          disc (r = R sqrt(u): cells of equal area), a small rectangle of a rectangle                        (k_s_ucull, in LDS)
+// The Cartesian mask wants the ray's float32 start point; the mask over the uniforms wants nothing but the Philox block: the top
+// log2 Mu and log2 Mv bits of the two words are its index (trc_fp_ucell), and the step from the bits to the cell is exact, so
+// it carries no eps.  Mu Mv is the largest power of two within M M, split Mu : Mv as 1 : 4, 1 : 1 or 4 : 1, whichever sets the
+// fewest bits for the scene and source; ucoverage, the share of its bits set, is the share of the source's rays it lists (for
+// discs as for rectangles: every cell holds the same share of the rays).  k_s_ucull lists the ray alone; its consumer
+// k_s_fresh2 finds the list cell from the float32 start point it makes anyway.  k_s_cull, on the Cartesian mask, hands the cell
+// to the consumers that do not (k_s_fresh).
 // eps covers the float32 evaluation of the start point in stage A (trc_fp_position32; checked on the device against
 // the float64 position by tests/test_gpu_parity.py).  Conservative by construction: a set bit or a listed surface
 // only costs time.  tests/test_hostcheck.py checks on the CPU that every ray of the source that hits a surface
-// (brute force, float64) has its bit set and that surface listed and passing the oriented-box test.
+// (brute force, float64) has its bit set and that surface listed and passing the oriented-box test; tests/test_umask_host.py the
+// same of the mask over the uniforms, with the list cell taken from the float32 start point.
 //
 // Plain C++ for the host part; the lookups are TRC_HD and shared with the kernels.
 #ifndef TRC_FOOTPRINT_H
 #define TRC_FOOTPRINT_H
 
 #include "trc_core.h"
+#include <cmath>
 
 #define TRC_FP_SHIFT 2            /* a list cell is 4 x 4 mask cells */
 #define TRC_FP_EPS_REL 1e-4       /* eps = TRC_FP_EPS_REL * half: float32 start points are good to ~1e-6 * half */
@@ -96,6 +108,35 @@ TRC_HD bool trc_fp_generic(const trc_fp_params &F, const uint32_t o[4]) {
     return F.has_generic && !(((double)o[2] + 0.5) * (1.0 / 4294967296.0) < F.cdf_end);
 }
 
+// ---- the mask over the uniforms (umask) ----
+// Bit (a, b) of the Mu x Mv mask stands for the rays whose first position uniform has a in its top log2 Mu bits and whose
+// second has b in its top log2 Mv bits (o[0], o[1] for the Buie and sunshape kinds, o[2], o[3] for the pillbox kinds).  Bit
+// a + Mu b of the mask, words of 32: the word index is b followed by the top log2 Mu - 5 bits of the first uniform, the bit
+// its next five -- one alignbit behind a shift, and one bit-field extract.  64 <= Mu, 2 <= Mv (trc_fp_build sees to it).
+TRC_HD int trc_fp_first_uniform(int kind) { return (kind == TRC_SRC_PILLBOX_DISK || kind == TRC_SRC_PILLBOX_RECT) ? 2 : 0; }
+TRC_HD void trc_fp_ucell(uint32_t ua, uint32_t ub, int lu, int lv, uint32_t *word, uint32_t *bit) {
+    const uint32_t b = ub >> (32 - lv);
+#if defined(__HIP_DEVICE_COMPILE__)
+    *word = __builtin_amdgcn_alignbit(b, ua, (uint32_t)(37 - lu));
+#else
+    *word = (uint32_t)((((uint64_t)b << 32) | (uint64_t)ua) >> (37 - lu));
+#endif
+    *bit = (ua >> (32 - lu)) & 31u;
+}
+
+// trc_fp_generic as one unsigned compare: ((double)o2 + 0.5) 2^-32 < cdf_end holds exactly when o2 < ceil(cdf_end 2^32 - 0.5)
+// (the scaling is exact, and so is the subtraction wherever its result is not below 0).  *on = false: no ray takes the general
+// path (no aureole, or a threshold of 2^32 and more); otherwise a ray does when !(o[2] < threshold).
+static inline uint32_t trc_fp_generic_threshold(const trc_fp_params &F, bool *on) {
+    *on = false;
+    if (!F.has_generic) return 0u;
+    const double t = std::ceil(F.cdf_end * 4294967296.0 - 0.5);
+    if (t >= 4294967296.0) return 0u;
+    *on = true;
+    return t > 0.0 ? (uint32_t)t : 0u;          // (a cdf_end that is no number compares false with everything: every ray)
+}
+TRC_HD bool trc_fp_generic_u(bool on, uint32_t threshold, uint32_t o2) { return on && !(o2 < threshold); }
+
 // ---- host side: construction (plain C++, parsed by both passes of hipcc like trc_bounds.h) ----
 #include <algorithm>
 #include <cmath>
@@ -109,6 +150,9 @@ struct trc_fp_host {
     std::vector<uint32_t> coff;       // Mc * Mc + 1
     std::vector<uint32_t> clist;
     double coverage;                  // fraction of mask cells set
+    std::vector<uint32_t> umask;      // Mu * Mv / 32 words, bit (b * Mu + a): the mask over the uniforms (trc_fp_ucell)
+    int Mu, Mv;                       // powers of two, Mu >= 64, Mu * Mv <= M * M
+    double ucoverage;                 // fraction of umask bits set = the share of the source's rays it lists
     const char *why;                  // when !ok
 };
 
@@ -202,14 +246,130 @@ static inline bool trc_fp_source(const trc_source_desc &src, trc_fp_params &P, d
     return true;
 }
 
+// The region of the start shape that the rays of umask cell (a, b) cover, as a point and a radius that covers the region from
+// it.  Discs: the annular sector r0 <= r <= r1, |phi - phi_m| <= dphi / 2 (r = R sqrt(u): cells of equal area; a = 0 reaches
+// the centre); from the point (r_m, phi_m) its farthest point is a corner (the distance grows with the angle and is convex
+// in r).  Rectangles: a small rectangle, its centre and half diagonal.  src_p: the float64 parameters of the descriptor.
+static inline void trc_fp_uregion(int kind, const double *p, int Mu, int Mv, int a, int b, double *cx, double *cy, double *rad) {
+    const double ua0 = (double)a / Mu, ua1 = (double)(a + 1) / Mu, ub0 = (double)b / Mv, ub1 = (double)(b + 1) / Mv;
+    if (kind == TRC_SRC_BUIE_DISK || kind == TRC_SRC_PILLBOX_DISK) {
+        double r0, r1, f0, f1;
+        if (kind == TRC_SRC_BUIE_DISK) {
+            r0 = p[0] * std::sqrt(ua0); r1 = p[0] * std::sqrt(ua1);
+            f0 = TRC_TWO_PI * ub0; f1 = TRC_TWO_PI * ub1;
+        } else {
+            const double i2 = p[1] * p[1], d2 = p[0] * p[0] - p[1] * p[1];
+            r0 = std::sqrt(std::fmax(0.0, i2 + ua0 * d2)); r1 = std::sqrt(std::fmax(0.0, i2 + ua1 * d2));
+            f0 = p[2] + (p[3] - p[2]) * ub0; f1 = p[2] + (p[3] - p[2]) * ub1;
+        }
+        if (r1 < r0) std::swap(r0, r1);
+        const double rm = 0.5 * (r0 + r1), fm = 0.5 * (f0 + f1), hw = 0.5 * std::fabs(f1 - f0);
+        *cx = rm * std::cos(fm); *cy = rm * std::sin(fm);
+        if (hw >= 0.5 * TRC_PI) { *rad = rm + r1; return; }          // (a sector wider than half a turn: the whole disc about the point)
+        const double ch = std::cos(hw);
+        const double d0 = std::sqrt(std::fmax(0.0, rm * rm + r0 * r0 - 2.0 * rm * r0 * ch)), d1 = std::sqrt(std::fmax(0.0, rm * rm + r1 * r1 - 2.0 * rm * r1 * ch));
+        *rad = std::fmax(d0, d1) * (1.0 + 1e-12) + 1e-12 * r1;
+    } else {
+        double x0, x1, y0, y1;
+        if (kind == TRC_SRC_BUIE_RECT) { x0 = p[0] * (ua0 - 0.5); x1 = p[0] * (ua1 - 0.5); y0 = p[1] * (ub0 - 0.5); y1 = p[1] * (ub1 - 0.5); }
+        else {      // TRC_SRC_PILLBOX_RECT: xs from the first uniform, ys from the second, swapped when the source says so; (lx, ly) = (ys, xs)
+            const double xa = -p[0] / 2.0 + p[0] * ua0, xb = -p[0] / 2.0 + p[0] * ua1, ya = -p[1] / 2.0 + p[1] * ub0, yb = -p[1] / 2.0 + p[1] * ub1;
+            if (p[3] != 0.0) { x0 = xa; x1 = xb; y0 = ya; y1 = yb; }
+            else { x0 = ya; x1 = yb; y0 = xa; y1 = xb; }
+        }
+        *cx = 0.5 * (x0 + x1); *cy = 0.5 * (y0 + y1);
+        *rad = 0.5 * std::hypot(x1 - x0, y1 - y0) * (1.0 + 1e-12);
+    }
+}
+
+// one footprint: the hull of a surface's projected box and the margin its rays can start from it (without the float32 eps)
+struct trc_fp_print { std::vector<double> hx, hy; double margin; };
+
+// umask of Mu x Mv bits from the footprints: the test of the Cartesian mask on every cell's region.  A bounding circle of the
+// footprint bounds the rings (a) and, where it does not hold the centre, the sectors (b) that have to be looked at.
+static inline size_t trc_fp_build_umask(int kind, const double *p, const std::vector<trc_fp_print> &prints, int Mu, int Mv, std::vector<uint32_t> &um) {
+    um.assign((size_t)Mu * Mv / 32, 0u);
+    const bool disc = kind == TRC_SRC_BUIE_DISK || kind == TRC_SRC_PILLBOX_DISK;
+    // rings: the squared radius is linear in the first uniform, q(u) = q0 + u dq
+    const double q0 = kind == TRC_SRC_PILLBOX_DISK ? p[1] * p[1] : 0.0, dq = kind == TRC_SRC_PILLBOX_DISK ? p[0] * p[0] - p[1] * p[1] : p[0] * p[0];
+    for (const trc_fp_print &f : prints) {
+        const size_t n = f.hx.size();
+        if (n == 0) continue;
+        double bx0 = INFINITY, bx1 = -INFINITY, by0 = INFINITY, by1 = -INFINITY;
+        for (size_t k = 0; k < n; ++k) { bx0 = std::fmin(bx0, f.hx[k]); bx1 = std::fmax(bx1, f.hx[k]); by0 = std::fmin(by0, f.hy[k]); by1 = std::fmax(by1, f.hy[k]); }
+        const double ccx = 0.5 * (bx0 + bx1), ccy = 0.5 * (by0 + by1);
+        double cr = 0.0;
+        for (size_t k = 0; k < n; ++k) cr = std::fmax(cr, std::hypot(f.hx[k] - ccx, f.hy[k] - ccy));
+        cr += f.margin;
+        int a0 = 0, a1 = Mu - 1, b0 = 0, nb = Mv;       // sectors b0, b0 + 1, ... (nb of them, wrapping)
+        if (disc && dq != 0.0) {
+            const double dc = std::hypot(ccx, ccy);
+            const double lo = std::fmax(0.0, dc - cr), hi = dc + cr;
+            double ul = (lo * lo - q0) / dq, uh = (hi * hi - q0) / dq;
+            if (ul > uh) std::swap(ul, uh);
+            const double fa0 = std::floor(ul * Mu) - 1.0, fa1 = std::floor(uh * Mu) + 1.0;
+            if (fa1 < 0.0 || fa0 > Mu - 1) continue;
+            a0 = fa0 < 0.0 ? 0 : (int)fa0; a1 = fa1 > Mu - 1 ? Mu - 1 : (int)fa1;
+            const double span = kind == TRC_SRC_PILLBOX_DISK ? p[3] - p[2] : TRC_TWO_PI, f0 = kind == TRC_SRC_PILLBOX_DISK ? p[2] : 0.0;
+            if (dc > cr * 1.0001 && std::fabs(span) > 0.0 && std::fabs(span) <= TRC_TWO_PI * (1.0 + 1e-9)) {
+                // the circle is seen from the centre under the angles fc +- fw; in units of sectors, from the source's first angle
+                const double fc = std::atan2(ccy, ccx), fw = std::asin(cr / dc);
+                double t0 = (fc - fw - f0) / span, t1 = (fc + fw - f0) / span;
+                if (t0 > t1) std::swap(t0, t1);
+                const double turn = TRC_TWO_PI / std::fabs(span);           // the same direction again, in units of the span (>= 1)
+                if (std::fabs(turn - 1.0) < 1e-9) {      // a whole disc: sectors wrap
+                    const double s0 = std::floor(t0 * Mv) - 1.0, s1 = std::floor(t1 * Mv) + 1.0;
+                    if (s1 - s0 + 1.0 < Mv) { nb = (int)(s1 - s0 + 1.0); b0 = (int)(((long long)s0 % Mv + Mv) % Mv); }
+                }
+                // (a part of a turn: the angles repeat with a period that is no whole number of sectors; every sector is looked at)
+            }
+        } else if (!disc) {
+            // rectangles: which uniform runs along lx
+            const bool first_is_x = kind == TRC_SRC_BUIE_RECT || p[3] != 0.0;
+            const double wa = p[0], wb = p[1];          // extent along the first / second uniform
+            const double alo = first_is_x ? bx0 : by0, ahi = first_is_x ? bx1 : by1, blo = first_is_x ? by0 : bx0, bhi = first_is_x ? by1 : bx1;
+            auto range = [&](double lo, double hi, double w, int m, int *i0, int *i1) {
+                if (!(std::fabs(w) > 0.0)) { *i0 = 0; *i1 = m - 1; return true; }
+                double u0 = (lo - f.margin) / w + 0.5, u1 = (hi + f.margin) / w + 0.5;
+                if (u0 > u1) std::swap(u0, u1);
+                const double s0 = std::floor(u0 * m) - 1.0, s1 = std::floor(u1 * m) + 1.0;
+                if (s1 < 0.0 || s0 > m - 1) return false;
+                *i0 = s0 < 0.0 ? 0 : (int)s0; *i1 = s1 > m - 1 ? m - 1 : (int)s1;
+                return true;
+            };
+            int b1;
+            if (!range(alo, ahi, wa, Mu, &a0, &a1) || !range(blo, bhi, wb, Mv, &b0, &b1)) continue;
+            nb = b1 - b0 + 1;
+        }
+        for (int kb = 0; kb < nb; ++kb) {
+            const int b = (b0 + kb) % Mv;
+            for (int a = a0; a <= a1; ++a) {
+                const size_t bit = (size_t)b * Mu + a;
+                if ((um[bit >> 5] >> (bit & 31)) & 1u) continue;
+                double cx, cy, rad;
+                trc_fp_uregion(kind, p, Mu, Mv, a, b, &cx, &cy, &rad);
+                const double dx = cx - ccx, dy = cy - ccy, reach = cr + rad;
+                if (dx * dx + dy * dy > reach * reach) continue;
+                if (trc_fp_dist_poly(f.hx, f.hy, cx, cy) <= f.margin + rad) um[bit >> 5] |= 1u << (bit & 31);
+            }
+        }
+    }
+    size_t bits = 0;
+    for (uint32_t wd : um) bits += (size_t)__builtin_popcount(wd);
+    return bits;
+}
+
 // A: trc_accel_build_surfaces of the same surfaces.  M: mask cells per side (a multiple of 32 << TRC_FP_SHIFT is not needed,
-// a multiple of 32 is).
+// a multiple of 32 is).  with_umask: also the mask over the uniforms (umask, Mu, Mv, ucoverage) -- the largest power-of-two
+// budget of bits within M * M, in the split (Mu = m / 2, m, 2 m by Mv = 2 m, m, m / 2) that sets the fewest bits for this scene
+// and source.  Without it umask stays empty and ucoverage 1.
 static inline void trc_fp_build(const trc_surface_desc *surfs, int n_surf, const trc_accel_host &A, const trc_source_desc &src,
-                                trc_fp_host &F, int M = 512) {
+                                trc_fp_host &F, int M = 512, bool with_umask = true) {
     F.ok = false;
     F.why = "";
     F.mask.clear(); F.coff.clear(); F.clist.clear();
     F.coverage = 1.0;
+    F.umask.clear(); F.Mu = F.Mv = 0; F.ucoverage = 1.0;
     memset(&F.P, 0, sizeof(F.P));
     if (!A.unbounded.empty()) { F.why = "the scene has unbounded surfaces"; return; }
     if (!A.any_bounded) { F.why = "no bounded surface"; return; }
@@ -238,6 +398,7 @@ static inline void trc_fp_build(const trc_surface_desc *surfs, int n_surf, const
     std::vector<std::vector<uint32_t>> lists((size_t)Mc * Mc);
     double depth_min = INFINITY;
     std::vector<double> hx, hy;
+    std::vector<trc_fp_print> prints;
     for (int s = 0; s < n_surf; ++s) {
         double l[3], h[3];
         bool global_axes;
@@ -258,6 +419,9 @@ static inline void trc_fp_build(const trc_surface_desc *surfs, int n_surf, const
         // |h| = |depth * wn| <= depth_max |wn| for the corners in front; corners behind (depth < 0) are not reached
         const double margin = depth_max * std::fabs(wn) * K + eps + 1e-9 * (half + depth_max);
         trc_fp_hull(pts, hx, hy);
+        // (the mask over the uniforms needs no eps: the kernel's step from the bits to the cell is exact, and the 1e-9 term covers
+        // the float64 rounding of the start point)
+        if (with_umask) prints.push_back({hx, hy, depth_max * std::fabs(wn) * K + 1e-9 * (half + depth_max)});
         double bx0 = INFINITY, bx1 = -INFINITY, by0 = INFINITY, by1 = -INFINITY;
         for (size_t k = 0; k < hx.size(); ++k) { bx0 = std::fmin(bx0, hx[k]); bx1 = std::fmax(bx1, hx[k]); by0 = std::fmin(by0, hy[k]); by1 = std::fmax(by1, hy[k]); }
         auto range = [&](double lo, double hi, double c, int n, int *i0, int *i1) {
@@ -297,6 +461,19 @@ static inline void trc_fp_build(const trc_surface_desc *surfs, int n_surf, const
     const double t_min = depth_min / (1.0 + a / std::fabs(wn));
     const double slack = 4.0 * (double)A.delta + 1e-6 * std::fabs(t_min);
     P.t_adv = (std::isfinite(t_min) && t_min - slack > 0.0) ? t_min - slack : 0.0;
+    if (with_umask) {
+        int m = 32;
+        while (2 * m <= M) m *= 2;
+        std::vector<uint32_t> um;
+        size_t best = 0;
+        for (int k = 0; k < 3; ++k) {
+            const int Mu = k == 0 ? m / 2 : (k == 1 ? m : 2 * m), Mv = k == 0 ? 2 * m : (k == 1 ? m : m / 2);
+            if (Mu < 64) continue;
+            const size_t set = trc_fp_build_umask(P.kind, src.p, prints, Mu, Mv, um);
+            if (F.umask.empty() || set < best) { best = set; F.umask.swap(um); F.Mu = Mu; F.Mv = Mv; }
+        }
+        F.ucoverage = (double)best / ((double)F.Mu * F.Mv);
+    }
     F.ok = true;
 }
 #endif  // TRC_FOOTPRINT_H

@@ -168,6 +168,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 //              -> k_s_walk -> k_s_exact); the others are listed (ray number, mask cell) for k_s_fresh.  A lean kernel of its own:
 //              a handful of arguments, ~40 registers, 8 waves per SIMD -- inside one kernel with the rest the round keys of
 //              Philox lived in spilled scalar registers and the whole ran at 2 waves per SIMD;
+//   k_s_ucull  the same decision without a start point, for the Buie sources in front of k_s_fresh2: the footprint mask tabulated
+//              over the two position uniforms (umask, trc_footprint.h), indexed by the top bits of o[0] and o[1] -- a shift, an
+//              alignbit and a bit-field extract, one LDS read, the bit test -- and the aureole by one unsigned compare of o[2]
+//              with a threshold of the host's (trc_fp_generic_threshold).  No conversion, square root, sine, cosine, cell or
+//              float64 compare: 72 vector instructions per ray instead of 104, 40 of them Philox (NSTTF: 0.159 -> 0.122 ms per 5e7
+//              rays).  It lists the ray number alone (fq_cell is neither computed nor written); k_s_fresh2 derives the list cell
+//              in its phase 1.  The mask in uniform space lists 2.7 % more NSTTF rays than the Cartesian one (19.6 % / 19.1 %);
+//              lists, chunks and grids behind it are sized by its own share (ucoverage).  Both forms are one body
+//              (s_cull_body<KIND, UM>); profiles/umask.txt says which instance uses which;
 //   k_s_fresh  one lane per listed ray, every lane busy: the float64 ray exactly as k_s_gen makes it (trc_source_ray_t, same
 //              stream), the surfaces listed for its cell, their oriented boxes in float32, the exact float64 test of those that
 //              pass (the reference's tie rule: nearest, lowest surface index on equal t).  A ray that hits takes the next slot
@@ -188,17 +197,23 @@ struct CullParams {
                                         // collected in LDS and appended with one atomic (they are rare: 4e-4 of the NSTTF rays; one
                                         // chunk per wave would leave k_s_gen a list of a few rays per 64 entries)
     int static_first;
+    // the mask as the instance takes it: its words, and for the form over the uniforms (UM) its dimensions Mu = 1 << lu,
+    // Mv = 1 << lv and trc_fp_generic as a compare of o[2] (trc_fp_generic_threshold)
+    int mask_words;
+    int lu, lv;
+    int gen_on;
+    uint32_t gen_thr;
 };
 #define SC_GEN_CAP 1024                 /* general-path rays a workgroup collects before it appends them */
 
-template <int KIND>
-__global__ __launch_bounds__(SC_THREADS) void k_s_cull(CullParams C) {
+template <int KIND, bool UM>
+__device__ __forceinline__ void s_cull_body(const CullParams &C) {
     extern __shared__ double lds[];
     uint32_t *l_mask = (uint32_t *)lds;
     const trc_fp_params &F = C.F;
-    uint32_t *l_gen = l_mask + F.M * F.M / 32;         // [SC_GEN_CAP] rays | count | base of the flush
+    uint32_t *l_gen = l_mask + C.mask_words;           // [SC_GEN_CAP] rays | count | base of the flush
     uint32_t *l_gen_n = l_gen + SC_GEN_CAP;
-    for (int i = threadIdx.x; i < F.M * F.M / 32; i += SC_THREADS) l_mask[i] = C.mask[i];
+    for (int i = threadIdx.x; i < C.mask_words; i += SC_THREADS) l_mask[i] = C.mask[i];
     if (threadIdx.x == 0) { l_gen_n[0] = 0u; l_gen_n[1] = 0u; }
     __syncthreads();
     const unsigned lane = lane_id();
@@ -213,12 +228,21 @@ __global__ __launch_bounds__(SC_THREADS) void k_s_cull(CullParams C) {
         const unsigned long long rid = C.rid0 + (unsigned long long)i;
         uint32_t o[4];
         trc_philox4x32_10((uint32_t)rid, (uint32_t)(rid >> 32), 0u, 0u, (uint32_t)C.seed, (uint32_t)(C.seed >> 32), o);   // = trc_uniform_quad's block
-        float lx, ly;
-        trc_fp_position32_t<KIND>(F, o, &lx, &ly);
-        int32_t ix, iy;
-        trc_fp_cell(F, lx, ly, &ix, &iy);
-        const bool bit = ((l_mask[((uint32_t)iy * (uint32_t)F.M + (uint32_t)ix) >> 5] >> (ix & 31)) & 1u) != 0u;
-        const bool generic = valid && trc_fp_generic(F, o);
+        int32_t ix = 0, iy = 0;
+        bool bit, generic;
+        if constexpr (UM) {         // the position uniforms' top bits are the mask index: no start point
+            constexpr int U = KIND == TRC_SRC_PILLBOX_DISK || KIND == TRC_SRC_PILLBOX_RECT ? 2 : 0;
+            uint32_t word, b;
+            trc_fp_ucell(o[U], o[U + 1], C.lu, C.lv, &word, &b);
+            bit = ((l_mask[word] >> b) & 1u) != 0u;
+            generic = valid && trc_fp_generic_u(C.gen_on != 0, C.gen_thr, o[2]);
+        } else {
+            float lx, ly;
+            trc_fp_position32_t<KIND>(F, o, &lx, &ly);
+            trc_fp_cell(F, lx, ly, &ix, &iy);
+            bit = ((l_mask[((uint32_t)iy * (uint32_t)F.M + (uint32_t)ix) >> 5] >> (ix & 31)) & 1u) != 0u;
+            generic = valid && trc_fp_generic(F, o);
+        }
         if (C.gen_chunk) {
             const unsigned long long qg = chunk_append(&C.cnt[CN(CW_GEN_LIST)], cg, generic, C.gen_list, C.room);
             if (generic) { if ((long long)qg < C.room) C.gen_list[qg] = (uint32_t)i; else C.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL; }
@@ -233,8 +257,10 @@ __global__ __launch_bounds__(SC_THREADS) void k_s_cull(CullParams C) {
         const bool pass = valid && !generic && bit;
         const unsigned long long q = chunk_append(&C.cnt[CN(CW_FP_LIST)], cf, pass, C.fq_ray, C.room);
         if (pass) {
-            if ((long long)q < C.room) { C.fq_ray[q] = (uint32_t)i; C.fq_cell[q] = ((uint32_t)iy << 16) | (uint32_t)ix; }
-            else C.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
+            if ((long long)q < C.room) {
+                C.fq_ray[q] = (uint32_t)i;
+                if constexpr (!UM) C.fq_cell[q] = ((uint32_t)iy << 16) | (uint32_t)ix;
+            } else C.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL;
         }
     }
     if (C.gen_chunk) chunk_close(cg, C.gen_list, C.room);
@@ -254,6 +280,11 @@ __global__ __launch_bounds__(SC_THREADS) void k_s_cull(CullParams C) {
         for (uint32_t k = threadIdx.x; k < n; k += SC_THREADS) C.gen_list[(size_t)b + k] = l_gen[k];
     }
 }
+// the form on the Cartesian mask, which hands k_s_fresh the cell / the form on the mask over the uniforms, in front of k_s_fresh2
+template <int KIND>
+__global__ __launch_bounds__(SC_THREADS) void k_s_cull(CullParams C) { s_cull_body<KIND, false>(C); }
+template <int KIND>
+__global__ __launch_bounds__(SC_THREADS) void k_s_ucull(CullParams C) { s_cull_body<KIND, true>(C); }
 
 // one workgroup per CU: 1024 threads (4 waves per SIMD) for a scene of flat surfaces -- 128 registers with 18 of the instance's 160
 // in scratch, and still a quarter faster than 3 waves per SIMD without (NSTTF: 0.33 -> 0.25 ms per batch: the kernel issues at half
@@ -335,6 +366,7 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh(StreamParams S) {
 // delta >= 1e-3 m (1e-2 on the NSTTF field) on every side, so a ray that hits a surface passes its box in this form too.  The
 // rays that pass wait in a queue of the wave in LDS; whenever 64 of them have come together the wave runs phase 2 with every
 // lane busy: the float64 ray, boxes and exact tests exactly as k_s_fresh does them.
+#define SF2_DERIVES_CELL(FLAT, LDS) ((FLAT) || (LDS))
 template <int KIND, bool FLAT, bool LDS>
 __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh2(StreamParams S0) {
     constexpr int THREADS = SF_THREADS(FLAT);
@@ -389,10 +421,14 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh2(StreamParams S0) 
         listed_ray_search<KIND, FLAT, LDS>(S, l_bf, recs, obb, l_coff, clist, cs, ch, active, ri, cell);
         qh += take;
     };
+    // DERIVE: the instance finds a listed ray's mask cell itself, from the float32 start point of phase 1 (the cell k_s_cull packs:
+    // the same functions on the same bits), and takes the list of k_s_ucull, which carries no cells.  The instances with the quadric
+    // code in and their tables in global memory came out with 7 to 9 more vector registers that way: they are handed the cell.
+    constexpr bool DERIVE = SF2_DERIVES_CELL(FLAT, LDS);
     uint32_t ri_n = SQ_INVALID, cell_n = 0;
     {
         const long long i0 = (long long)blockIdx.x * THREADS + threadIdx.x;
-        if (i0 < count) { ri_n = W.fq_ray[i0]; cell_n = W.fq_cell[i0]; }
+        if (i0 < count) { ri_n = W.fq_ray[i0]; if constexpr (!DERIVE) cell_n = W.fq_cell[i0]; }
     }
     for (long long i = (long long)blockIdx.x * THREADS + threadIdx.x; i < padded; i += (long long)gridDim.x * THREADS) {
         // the arguments of this turn: none of them lives across the loop in a scalar register
@@ -402,11 +438,12 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh2(StreamParams S0) 
         const FastParams &P = S.P;
         const StreamWs &W = S.W;
         const trc_fp_params &F = S.fp.P;
-        const uint32_t ri = ri_n, cell = cell_n;
+        const uint32_t ri = ri_n;
+        uint32_t cell = cell_n;
         {
             const long long i1 = i + (long long)gridDim.x * THREADS;
             ri_n = SQ_INVALID; cell_n = 0;
-            if (i1 < count) { ri_n = W.fq_ray[i1]; cell_n = W.fq_cell[i1]; }
+            if (i1 < count) { ri_n = W.fq_ray[i1]; if constexpr (!DERIVE) cell_n = W.fq_cell[i1]; }
         }
         const bool active = ri != SQ_INVALID;
         if (!__ballot(active)) continue;
@@ -418,6 +455,11 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh2(StreamParams S0) 
             trc_philox4x32_10((uint32_t)rid, (uint32_t)(rid >> 32), 0u, 0u, (uint32_t)P.seed, (uint32_t)(P.seed >> 32), o);
             float lx, ly;
             trc_fp_position32_t<KIND>(F, o, &lx, &ly);
+            if constexpr (DERIVE) {
+                int32_t ix, iy;
+                trc_fp_cell(F, lx, ly, &ix, &iy);
+                cell = ((uint32_t)iy << 16) | (uint32_t)ix;
+            }
             const double u2 = ((double)o[2] + 0.5) * (1.0 / 4294967296.0);
             const float th = (float)trc_buie_theta_fast(l_bf, u2);
             float sxi, cxi;
@@ -1947,6 +1989,7 @@ struct StreamKnobs {
     bool room_set; long long room;      // TRC_STREAM_ROOM is set, and the room of every list it sets (>= 64; 0: the default)
     long long q3_entries;   // TRC_STREAM_Q3_ENTRIES: initial capacity of the candidate queue (0: by the batch)
     int fp_cells;           // TRC_STREAM_FP_CELLS: cells per side of the footprint map (>= 32; 0: by the scene)
+    bool umask;             // TRC_STREAM_UMASK=0: k_s_cull on the Cartesian mask for every source (the form that packs the cell)
     int slots;              // TRC_STREAM_SLOTS: batches in flight, 1 .. STREAM_MAX_SLOTS (default 2)
 };
 
@@ -1964,6 +2007,7 @@ static StreamKnobs stream_knobs() {
     K.room = K.room_set && atoll(ev) >= 64 ? atoll(ev) : 0;
     K.q3_entries = (ev = getenv("TRC_STREAM_Q3_ENTRIES")) && atoll(ev) > 0 ? atoll(ev) : 0;
     K.fp_cells = (ev = getenv("TRC_STREAM_FP_CELLS")) && atoi(ev) >= 32 ? atoi(ev) : 0;
+    K.umask = !((ev = getenv("TRC_STREAM_UMASK")) && !atoi(ev));
     K.slots = (ev = getenv("TRC_STREAM_SLOTS")) ? atoi(ev) : 2;
     if (K.slots < 1 || K.slots > STREAM_MAX_SLOTS) K.slots = 2;
     return K;
@@ -2080,6 +2124,8 @@ struct StreamSlot {
     unsigned long long part_start[TRC_CLS_COUNT] = {};   // entries of each class list that are pre-assigned to the waves of k_s_partition
     unsigned cull_chunk = 0;      // entries of the footprint list pre-assigned to every wave of k_s_cull
     unsigned cull_gen_chunk = 0;  // ... and of the general-path list (0: collected per workgroup, see CullParams)
+    bool fresh_one = false;       // this batch's listed rays go to k_s_fresh although the source has the two-phase form
+    bool umask = false;           // this batch's k_s_cull reads the mask over the uniforms, and k_s_fresh2 takes its list
     bool fresh = false, general = false, fused = false, first = false;     // first: k_s_bounce<.., FRESH> takes the fresh rays outside the footprint map
     unsigned gb_first = 0;  // this bounce: k_s_fresh generates the rays / the general path (gen, walk, exact) runs / k_s_bounce searches
     bool busy = false;
@@ -2102,7 +2148,7 @@ struct StreamEngine {
     double rate_term[STREAM_RATE_BOUNCES], rate_other[STREAM_RATE_BOUNCES];
     double rate_cls[STREAM_RATE_BOUNCES][TRC_CLS_COUNT];   // hits per ray entering bounce b that each shading class took (< 0: not yet)
     uint64_t rate_geom_version = 0;      // the pose the rates were measured on
-    DevBuf<uint32_t> d_fp_mask, d_fp_coff;
+    DevBuf<uint32_t> d_fp_mask, d_fp_coff, d_fp_umask;     // (d_fp_umask: empty where the source's kernels do not use the mask over the uniforms)
     DevBuf<uint32_t> d_fp_clist;
 
     void forget_rates() {      // not measured yet
@@ -2133,23 +2179,25 @@ static int stream_fp_prepare(trc_scene *sc, StreamEngine &E, const trc_source_de
     if (!(E.fp_valid && E.fp_geom_version == sc->geom_version && memcmp(key, E.fp_key, sizeof(key)) == 0 && (!buie || E.fp->P.cdf_end == cdf_end))) {
         int M = sc->n_surf > 4096 ? 1024 : 512;       // (a mesh of small faces: finer cells, fewer faces listed per cell; the mask still fits k_s_cull's LDS)
         const bool forced = K.fp_cells > 0;
+        const bool um = buie;      // the mask over the uniforms: for the sources whose listed rays go to k_s_fresh2 (stream_form_fresh)
         if (forced) M = K.fp_cells;
         if (M > 1024) M = 1024;
         if (sc->n_surf > 4096 && !forced) {
             // A large mesh that fills the source's view: nearly every ray starts over a face, the map culls nothing, and building
             // it at full resolution takes seconds (1e5 faces: 2.5 s).  A coarse map first (1/16 of the work): covered more than
             // 80 % -> no map for this scene and source, every fresh ray is searched on the grid (k_s_bounce<.., FRESH>).
-            trc_fp_build(sc->surfs.data(), sc->n_surf, sc->accel, *src, *E.fp, 256);
+            trc_fp_build(sc->surfs.data(), sc->n_surf, sc->accel, *src, *E.fp, 256, false);
             const bool disc = src->kind == TRC_SRC_BUIE_DISK || src->kind == TRC_SRC_PILLBOX_DISK || src->kind == TRC_SRC_SUNSHAPE_DISK;      // (the mask is a square around the disc)
             if (E.fp->ok && E.fp->coverage * (disc ? 4.0 / TRC_PI : 1.0) > 0.8) E.fp->ok = false;
-            else trc_fp_build(sc->surfs.data(), sc->n_surf, sc->accel, *src, *E.fp, M);
+            else trc_fp_build(sc->surfs.data(), sc->n_surf, sc->accel, *src, *E.fp, M, um);
         } else
-        trc_fp_build(sc->surfs.data(), sc->n_surf, sc->accel, *src, *E.fp, M);
+        trc_fp_build(sc->surfs.data(), sc->n_surf, sc->accel, *src, *E.fp, M, um);
         memcpy(E.fp_key, key, sizeof(key));
         E.fp_geom_version = sc->geom_version;
         E.fp_valid = true;
         E.fp_hit_rate = 0.0;
-        E.d_fp_mask.reset(); E.d_fp_coff.reset(); E.d_fp_clist.reset();
+        E.d_fp_mask.reset(); E.d_fp_coff.reset(); E.d_fp_clist.reset(); E.d_fp_umask.reset();
+        if (E.fp->ok && !E.fp->umask.empty()) TRC_TRY(dev_upload(E.d_fp_umask, E.fp->umask.data(), E.fp->umask.size()));
         if (E.fp->ok) {
             TRC_TRY(dev_upload(E.d_fp_mask, E.fp->mask.data(), E.fp->mask.size()));
             TRC_TRY(dev_upload(E.d_fp_coff, E.fp->coff.data(), E.fp->coff.size()));
@@ -2222,6 +2270,9 @@ struct StreamForms {
     StreamShadeK shk[TRC_CLS_COUNT];
     int n_shk;
     StreamKernel cull, fresh, fresh_one;     // fresh_one: k_s_fresh itself where `fresh` is its two-phase form
+    StreamKernel cull_u;         // k_s_cull on the mask over the uniforms, in front of k_s_fresh2 (fn null: this source has none)
+    CullParams cull_up;          // ... what it takes that the other form does not: the mask, its words and dimensions, the generic compare
+    double ulisted_share;        // ... and the share of the fresh rays it lists
     StreamKernel bounce, first, absorb;      // k_s_bounce for continued rays / for fresh ones, k_s_absorb
     bool coop;                   // k_s_bounce_coop serves the large grid (it lists terminal hits, never finishes them itself)
     bool use_fp, use_fused, use_first, use_absorb, absorb_inline;
@@ -2370,6 +2421,25 @@ static int stream_form_fresh(StreamForms &F, StreamParams &SP0, trc_scene *sc, S
                         : src_kind == TRC_SRC_PILLBOX_DISK ? (const void *)k_s_cull<TRC_SRC_PILLBOX_DISK> : (const void *)k_s_cull<TRC_SRC_PILLBOX_RECT>;
     const size_t lds_cull = (size_t)SP0.fp.P.M * SP0.fp.P.M / 8 + (SC_GEN_CAP + 4) * 4;
     if (lds_cull > LDS_MAX_ALLOWED || lds_fresh > LDS_MAX_ALLOWED) { F.use_fp = false; return TRC_OK; }
+    // The mask over the uniforms, for the listed rays that k_s_fresh2 takes: it finds its list cell itself.  k_s_fresh (the
+    // pillbox kinds, the tabulated sunshapes, a Buie source whose listed rays mostly hit) and the instances of k_s_fresh2 that
+    // do not derive the cell (SF2_DERIVES_CELL) are handed it by the other form.
+    F.cull_u = {nullptr, SC_THREADS, 0, 0u};
+    F.ulisted_share = 1.0;
+    memset(&F.cull_up, 0, sizeof(F.cull_up));
+    if (fresh_two && SF2_DERIVES_CELL(flat, fresh_in_lds) && K.umask && E.d_fp_umask.get()) {
+        F.cull_u.fn = src_kind == TRC_SRC_BUIE_DISK ? (const void *)k_s_ucull<TRC_SRC_BUIE_DISK> : (const void *)k_s_ucull<TRC_SRC_BUIE_RECT>;
+        F.cull_u.lds = E.fp->umask.size() * 4 + (SC_GEN_CAP + 4) * 4;      // (at most what the Cartesian mask takes: Mu Mv <= M M)
+        CullParams &U = F.cull_up;
+        U.mask = E.d_fp_umask.get(); U.mask_words = (int)E.fp->umask.size();
+        for (U.lu = 0; (1 << U.lu) < E.fp->Mu; ++U.lu) {}
+        for (U.lv = 0; (1 << U.lv) < E.fp->Mv; ++U.lv) {}
+        bool on;
+        U.gen_thr = trc_fp_generic_threshold(SP0.fp.P, &on);
+        U.gen_on = on ? 1 : 0;
+        F.ulisted_share = E.fp->ucoverage > 1.0 ? 1.0 : E.fp->ucoverage;
+        TRC_TRY(kernel_grid_cap(F.cull_u.fn, SC_THREADS, F.cull_u.lds, 2048 / SC_THREADS, n_cu, &F.cull_u.max_blocks));
+    }
     F.fresh = {fresh_fn, sf_threads, lds_fresh, 0u};
     F.fresh_one = {fresh1_fn, sf_threads, lds_fresh, 0u};
     F.cull = {cull_fn, SC_THREADS, lds_cull, 0u};
@@ -2544,8 +2614,17 @@ static void plan_bounce(const StreamCall &C, StreamSlot &T) {
     T.gb_first = 0u;
     T.cull_chunk = SQ_CHUNK;
     T.cull_gen_chunk = 0;
+    T.umask = false;
     if (T.fresh) {        // one lane per listed ray, a few rays per lane
-        const double listed = F.listed_share * (double)T.nb;
+        // the two-phase form pays where most listed rays miss (a field of mirrors: two of three); where most of them hit (a dish
+        // under its own source: the first phase rejects nothing) the batches after the first go back to k_s_fresh, which is
+        // handed its cells by k_s_cull on the Cartesian mask
+        const bool mostly_hits = E.fp_hit_rate > 0.0 && E.fp_hit_rate > 0.6 * 1.15 * F.listed_share;
+        T.umask = F.cull_u.fn != nullptr && !mostly_hits;
+        T.fresh_one = mostly_hits;
+        if (T.umask) T.gb_cull = grid_for(F.cull_u.max_blocks, SC_THREADS * 8);
+        // (the mask over the uniforms lists somewhat more rays than the Cartesian one: its lists and grids are sized by its own share)
+        const double listed = (T.umask ? F.ulisted_share : F.listed_share) * (double)T.nb;
         T.gb_fresh = clamp_grid(((long long)(1.2 * listed) + 4096 + sf_threads * 2 - 1) / (sf_threads * 2), F.fresh.max_blocks);
         T.cull_chunk = chunk_for(1.1 * listed, (unsigned long long)T.gb_cull * (SC_THREADS / 64));
         // general-path rays: rare -> per workgroup through LDS; a source with a strong aureole (CSR 0.3: a third of the rays) ->
@@ -2553,7 +2632,7 @@ static void plan_bounce(const StreamCall &C, StreamSlot &T) {
         if (F.general_share * (double)T.nb / (double)T.gb_cull > 0.25 * SC_GEN_CAP)
             T.cull_gen_chunk = chunk_for(1.1 * F.general_share * (double)T.nb, (unsigned long long)T.gb_cull * (SC_THREADS / 64));
         // hits of the fresh rays: measured on the batches before (E.fp_hit_rate), every listed ray to start with
-        const double hits = (E.fp_hit_rate > 0.0 ? E.fp_hit_rate : F.listed_share) * (double)T.nb;
+        const double hits = (E.fp_hit_rate > 0.0 ? E.fp_hit_rate : (T.umask ? F.ulisted_share : F.listed_share)) * (double)T.nb;
         T.SP.chunk_hit = T.SP.chunk_slot = chunk_for(hits, (unsigned long long)T.gb_fresh * (unsigned long long)(sf_threads / 64));
         act_expected = hits + 2.0 * F.general_share * (double)T.nb;
     } else {
@@ -2661,12 +2740,16 @@ static int launch_bounce(StreamCall &C, StreamSlot &T) {
         CP.F = SP.fp.P; CP.mask = SP.fp.mask; CP.seed = SP.P.seed; CP.rid0 = SP.P.ray_offset + (unsigned long long)T.base; CP.nb = T.nb;
         CP.fq_ray = SP.W.fq_ray; CP.fq_cell = SP.W.fq_cell; CP.gen_list = SP.W.gen_list; CP.cnt = SP.W.cnt;
         CP.room = SP.W.room; CP.chunk = T.cull_chunk; CP.gen_chunk = T.cull_gen_chunk; CP.static_first = SP.static_first;
+        CP.mask_words = SP.fp.P.M * SP.fp.P.M / 32; CP.lu = CP.lv = 0; CP.gen_on = 0; CP.gen_thr = 0u;
+        if (T.umask) {
+            const CullParams &U = F.cull_up;
+            CP.mask = U.mask; CP.mask_words = U.mask_words; CP.lu = U.lu; CP.lv = U.lv; CP.gen_on = U.gen_on; CP.gen_thr = U.gen_thr;
+        }
+        const StreamKernel &cull = T.umask ? F.cull_u : F.cull;
         void *cargs[] = {(void *)&CP};
-        HIP_TRY(hipLaunchKernel(F.cull.fn, dim3(T.gb_cull), dim3(F.cull.threads), cargs, F.cull.lds, T.stream.get()));
-        // the two-phase form pays where most listed rays miss (a field of mirrors: two of three); where most of them hit (a dish
-        // under its own source: the first phase rejects nothing) the batches after the first go back to k_s_fresh
-        const bool mostly_hits = C.E.fp_hit_rate > 0.0 && C.E.fp_hit_rate > 0.6 * 1.15 * F.listed_share;
-        TRC_TRY(launch_kernel(mostly_hits ? F.fresh_one : F.fresh, T.gb_fresh, SP, T.stream.get()));
+        HIP_TRY(hipLaunchKernel(cull.fn, dim3(T.gb_cull), dim3(cull.threads), cargs, cull.lds, T.stream.get()));
+        // (plan_bounce chose between the two-phase form and k_s_fresh, and with it k_s_cull's form)
+        TRC_TRY(launch_kernel(T.fresh_one ? F.fresh_one : F.fresh, T.gb_fresh, SP, T.stream.get()));
         C.launches += 2;
     }
     if (T.fused) { TRC_TRY(launch_kernel(F.bounce, T.gb_bounce, SP, T.stream.get())); C.launches += 1; }
@@ -2763,6 +2846,7 @@ static int advance(StreamCall &C, StreamSlot &T) {
     StreamEngine &E = C.E;
     const unsigned long long *c = T.h_cnt.get();
 #ifdef SW_STATS
+    if (T.fresh) fprintf(stderr, "batch %lld: footprint list %llu entries of %lld rays (%s)\n", T.base / C.cap, c[CN(CW_FP_LIST)], T.nb, T.umask ? "umask" : "Cartesian mask");
     fprintf(stderr, "batch %lld bounce %d: Q1 %llu Q3 %llu hits %llu | walkers %llu wave-iters %llu steps %llu leaf-entries %llu box-tests %llu drains %llu drain-rounds %llu\n",
             T.base / C.cap, T.b, c[CN(CW_Q1)], c[CN(CW_Q3)], c[CN(CW_HITS)], c[CN(CW_STATS)], c[CN(CW_STATS + 1)], c[CN(CW_STATS + 2)], c[CN(CW_STATS + 3)], c[CN(CW_STATS + 4)], c[CN(CW_STATS + 5)], c[CN(CW_STATS + 6)]);
 #endif
