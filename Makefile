@@ -21,6 +21,8 @@ SPECCHECK := $(ROOT)tests/hostcheck/libtrc_spectrum_check.so
 SPECCHECK_SRC := $(ROOT)tests/hostcheck/spectrum_check.cpp
 SUNCHECK := $(ROOT)tests/hostcheck/libtrc_sunshape_check.so
 SUNCHECK_SRC := $(ROOT)tests/hostcheck/sunshape_check.cpp
+FMCHECK := $(ROOT)tests/hostcheck/libtrc_fluxmap_check.so
+FMCHECK_SRC := $(ROOT)tests/hostcheck/fluxmap_check.cpp
 
 UMASKCHECK := $(ROOT)tests/umaskcheck/libtrc_umask_check.so
 UMASKCHECK_EXE := $(ROOT)tests/umaskcheck/umask_check
@@ -56,7 +58,7 @@ $(LIB): $(OBJS)
 	mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared -o $@ $(OBJS)
 
-hostcheck: $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK)
+hostcheck: $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK)
 
 $(HOSTCHECK): $(HOSTCHECK_SRC) $(HDR)
 	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(HOSTCHECK_SRC)
@@ -68,6 +70,10 @@ $(SPECCHECK): $(SPECCHECK_SRC) $(HDR)
 # the tabulated-sunshape sampler and sources of the per-ray core, host-compiled for their tests
 $(SUNCHECK): $(SUNCHECK_SRC) $(HDR)
 	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(SUNCHECK_SRC)
+
+# the flux-map charts and bin index of the per-ray core, host-compiled for their tests
+$(FMCHECK): $(FMCHECK_SRC) $(HDR)
+	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(FMCHECK_SRC)
 
 # the footprint map's mask over the uniforms against brute force, host-compiled: a library for its test, and the same as a program
 # (umaskcheck-exe; SAN="-fsanitize=address,undefined" builds it for a sanitizer run)
@@ -94,6 +100,6 @@ asm-shade: $(CSRC)/trc_shade.hip $(HDR)
 		-o $(ROOT)build/trc_shade.s $(CSRC)/trc_shade.hip 2> $(ROOT)build/trc_shade.resources.txt
 
 clean:
-	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK)
+	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK)
 
 .PHONY: all hostcheck umaskcheck umaskcheck-exe asm asm-shade clean

@@ -321,6 +321,18 @@ int trc_scene_set_kdtree(trc_scene *scene, const trc_kdtree_desc *kd);
    round(inv(frame), 9) as in Surface.global_to_local (surface.py:114-126).  Resets the tallies. */
 int trc_scene_set_fluxmap(trc_scene *scene, int32_t surf, int32_t nu, int32_t nv,
                           const double *u_edges, const double *v_edges, const double *proj12);
+/* The same in the coordinates of the receiver's shape (chart), as the reference's get_fluxmap of that shape bins them from the
+   local point (xl, yl, zl), with phi = arctan2(yl, xl), 2 pi added where it is negative:
+     TRC_FM_XY (0)        u = xl, v = yl                       RectPlateGM (flat_surface.py:237-251); trc_scene_set_fluxmap is this chart
+     TRC_FM_CYLINDER (1)  u = zl, v = phi                      FiniteCylinder over its ang_range (cylinder.py:139-159)
+     TRC_FM_POLAR (2)     u = sqrt(xl^2 + yl^2), v = phi       ParabolicDishGM (paraboloid.py:151-172); RoundPlateGM, whose
+                                                               arctan2(x, y) (flat_surface.py:524-545) takes proj12 with rows 0 and 1 exchanged
+     TRC_FM_SPHERE (3)    u = arccos(zl / |(xl, yl, zl)|), v = phi   SphericalGM (sphere_surface.py:100-115)
+   Cones and frusta, which have no get_fluxmap there, are served by CYLINDER or POLAR with edges of the caller's.  An unknown chart
+   is TRC_ERR_INVALID; a surface has one flux map, whichever of the two calls set it. */
+typedef enum trc_fluxmap_chart { TRC_FM_XY = 0, TRC_FM_CYLINDER = 1, TRC_FM_POLAR = 2, TRC_FM_SPHERE = 3 } trc_fluxmap_chart;
+int trc_scene_set_fluxmap_chart(trc_scene *scene, int32_t surf, int32_t chart, int32_t nu, int32_t nv,
+                                const double *u_edges, const double *v_edges, const double *proj12);
 /* capacity (in hits) of the hit buffer that backs the Location/Direction/
    Absorption accountants (optics_callables.py:1597-1771) in the fast engine */
 int trc_scene_set_hit_capacity(trc_scene *scene, int64_t capacity);

@@ -45,6 +45,10 @@ LEVEL_VOLUME = 0x40000000        # TRC_LEVEL_VOLUME: bit of a level's surf[] ent
  OPT_FRESNEL_CONDUCTOR, OPT_SEMI_LAMBERTIAN, OPT_REFRACTIVE_SCATTERING, OPT_REFRACTIVE_MATERIAL,
  OPT_LAMBERTIAN_POLYCHROMATIC, OPT_PERIODIC_BOUNDARY) = range(17)
 
+# enum trc_fluxmap_chart: the coordinates a flux map bins in (trc_scene_set_fluxmap_chart)
+FM_XY, FM_CYLINDER, FM_POLAR, FM_SPHERE = range(4)
+FM_CHARTS = {'xy': FM_XY, 'cylinder': FM_CYLINDER, 'polar': FM_POLAR, 'sphere': FM_SPHERE}
+
 # enum trc_source_kind
 SRC_PILLBOX_DISK, SRC_PILLBOX_RECT, SRC_BUIE_DISK, SRC_BUIE_RECT, SRC_PILLBOX_TRIANGLE, SRC_VF_CYLINDER, SRC_VF_FRUSTUM = range(7)
 SRC_SUNSHAPE_DISK, SRC_SUNSHAPE_RECT = 7, 8       # tabulated sunshapes: the descriptor's `table` names a trc_sunshape
@@ -117,6 +121,7 @@ SIGNATURES = {
     'trc_scene_update_frames': (C.c_int, [_vp, C.c_int32, _p_f64]),
     'trc_scene_set_kdtree': (C.c_int, [_vp, C.POINTER(KdTreeDesc)]),
     'trc_scene_set_fluxmap': (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _p_f64, _p_f64, _p_f64]),
+    'trc_scene_set_fluxmap_chart': (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p_f64, _p_f64, _p_f64]),
     'trc_scene_set_hit_capacity': (C.c_int, [_vp, C.c_int64]),
     'trc_scene_clear_hits': (C.c_int, [_vp]),
     'trc_scene_reserve_hits': (C.c_int, [_vp, C.c_int64]),

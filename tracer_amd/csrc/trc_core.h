@@ -1973,4 +1973,29 @@ TRC_HD int trc_bin_index(const double *edges, int nbins, double x) {
     return lo;
 }
 
+// The coordinates a flux map bins a hit in: the chart of the receiver's shape, as the reference's get_fluxmap of that shape takes
+// them from the local point (xl, yl, zl) = proj (rows 0..2 of round(inv(frame), 9), surface.py:125) applied to the global hit point.
+//   TRC_FM_XY        (xl, yl)                 RectPlateGM, flat_surface.py:237-251
+//   TRC_FM_CYLINDER  (zl, phi)                FiniteCylinder, cylinder.py:139-159
+//   TRC_FM_POLAR     (sqrt(xl^2 + yl^2), phi) ParabolicDishGM, paraboloid.py:151-172; RoundPlateGM, flat_surface.py:524-545, whose
+//                                             arctan2(x, y) the host serves by handing over proj with rows 0 and 1 exchanged
+//   TRC_FM_SPHERE    (theta, phi)             SphericalGM, sphere_surface.py:100-115 -- theta from the point's own radius, not the
+//                                             surface's: the two differ by rounding, and this one is never NaN on the sphere
+// phi = atan2(yl, xl), and 2.*pi added where it is negative (angs[angs<0.] += 2.*N.pi: -0.0 stays).  Products and sums in the written
+// order (the build does not contract them), so that NumPy rounds the same formulas the same way.  A NaN coordinate is outside every
+// map (trc_bin_index).
+#define TRC_FM_CHARTS 4     /* charts of trc_fluxmap_chart (tracer_amd.h) */
+TRC_HD void trc_fluxmap_uv(int chart, const double *proj, double hx, double hy, double hz, double *u, double *v) {
+    const double xl = proj[0] * hx + proj[1] * hy + proj[2] * hz + proj[3];
+    const double yl = proj[4] * hx + proj[5] * hy + proj[6] * hz + proj[7];
+    if (chart == TRC_FM_XY) { *u = xl; *v = yl; return; }
+    const double zl = proj[8] * hx + proj[9] * hy + proj[10] * hz + proj[11];
+    double phi = atan2(yl, xl);
+    if (phi < 0.0) phi += TRC_TWO_PI;
+    *v = phi;
+    if (chart == TRC_FM_CYLINDER) *u = zl;
+    else if (chart == TRC_FM_POLAR) *u = sqrt(xl * xl + yl * yl);
+    else *u = acos(zl / sqrt((xl * xl + yl * yl) + zl * zl));
+}
+
 #endif  // TRC_CORE_H

@@ -11,10 +11,10 @@
 #include "trc_footprint.h"
 
 struct FluxMapDev {
-    int32_t surf, nu, nv, pad;
+    int32_t surf, nu, nv, chart;   // chart: the coordinates the map bins in (TRC_FM_*, trc_core.h)
     int64_t edges_u, edges_v;  // offsets into fm_edges
     int64_t bins;              // offset into the tally buffer
-    double proj[12];           // global -> local (rows 0..2 of round(inv(frame), 9), surface.py:125)
+    double proj[12];           // global -> local (rows 0..2 of round(inv(frame), 9), surface.py:125; row 2 is read by the charts other than XY)
 };
 static_assert(sizeof(FluxMapDev) == 136, "tests/shade_cases.py (SIZEOF_FLUXMAPDEV) restates this size in the sums of the LDS images");
 
@@ -231,7 +231,10 @@ __device__ __forceinline__ void hit_store(const DScene &sc, unsigned long long s
 }
 
 // per-hit bookkeeping shared by both engines: tallies, flux map, hit capture
-template <bool LDS_TALLY>
+// CHART: the instance knows the flux-map charts other than XY (trc_fluxmap_uv: a float64 atan2, an acos and a square root).  Compiled
+// apart, as SPEC and SUN are: the host picks the CHART instances of a kernel only for a scene that holds such a map, and the others
+// are the code they were.
+template <bool LDS_TALLY, bool CHART = false>
 __device__ __forceinline__ void record_hit(const DScene &sc, double *lds_tally, int s, double e_in,
                                            double e_abs, double hx, double hy, double hz, double dx,
                                            double dy, double dz, bool capture_enabled, int prev, WaveChunk *hc = nullptr,
@@ -257,8 +260,12 @@ __device__ __forceinline__ void record_hit(const DScene &sc, double *lds_tally, 
     int fm = (!volume && sc.fm_of_surf) ? sc.fm_of_surf[s] : -1;
     if (fm >= 0) {
         const FluxMapDev &m = sc.fms[fm];
-        double u = m.proj[0] * hx + m.proj[1] * hy + m.proj[2] * hz + m.proj[3];
-        double v = m.proj[4] * hx + m.proj[5] * hy + m.proj[6] * hz + m.proj[7];
+        double u, v;
+        if constexpr (CHART) trc_fluxmap_uv(m.chart, m.proj, hx, hy, hz, &u, &v);
+        else {
+            u = m.proj[0] * hx + m.proj[1] * hy + m.proj[2] * hz + m.proj[3];
+            v = m.proj[4] * hx + m.proj[5] * hy + m.proj[6] * hz + m.proj[7];
+        }
         int iu = trc_bin_index(sc.fm_edges + m.edges_u, m.nu, u);
         int iv = trc_bin_index(sc.fm_edges + m.edges_v, m.nv, v);
         if (iu >= 0 && iv >= 0) {
@@ -342,7 +349,7 @@ struct FastParams {
 
 // shading + bookkeeping of one hit, shared by the two fast kernels.  Returns false when the ray stops here.
 // SIMPLE promises a flat geometry kind and an optics kind of TRC_OPT_SIMPLE_MASK on every surface: the compiler drops the rest.
-template <bool LDS_TALLY, bool SIMPLE = false>
+template <bool LDS_TALLY, bool SIMPLE = false, bool CHART = false>
 __device__ __forceinline__ bool fast_shade(const FastParams &P, const double *recs, double *l_tally, double t, int s, double &px,
                                            double &py, double &pz, double &dx, double &dy, double &dz, double &e, double &ref,
                                            double wl, unsigned long long rid, int &bounce, int &prev, WaveChunk *hc = nullptr,
@@ -367,7 +374,7 @@ __device__ __forceinline__ bool fast_shade(const FastParams &P, const double *re
     if (was_volume) *was_volume = volume;
     if (volume) { hx -= out[0].back * dx; hy -= out[0].back * dy; hz -= out[0].back * dz; }
     double e_abs = e - out[0].e;
-    record_hit<LDS_TALLY>(sc, l_tally, s, e, e_abs, hx, hy, hz, dx, dy, dz, P.capture != 0, prev, hc, lds_fm, volume, tallied);
+    record_hit<LDS_TALLY, CHART>(sc, l_tally, s, e, e_abs, hx, hy, hz, dx, dy, dz, P.capture != 0, prev, hc, lds_fm, volume, tallied);
     if (!volume) prev = s;
     px = hx + out[0].shift * nx; py = hy + out[0].shift * ny; pz = hz + out[0].shift * nz;      // (PeriodicBoundary: one period along the normal)
     dx = out[0].dx; dy = out[0].dy; dz = out[0].dz;
@@ -672,8 +679,9 @@ __device__ __forceinline__ void tally_by_wave(double *tl, int Sn, int ts, double
 }
 
 // the lean shading kernels (trc_shade.hip): kernel of a class for a scene of flat surfaces only (flat) with its tables in LDS (lds)
-const void *trc_shade_carry_kernel(bool lds);      // k_s_shade_x (trc_shade.hip): every optics kind, with what the rays carry
-const void *trc_shade_lean_kernel(int cls, bool flat, bool lds, bool spec = false);
+// chart: the instance that knows every flux-map chart (record_hit<.., CHART>) -- of the lean kernels the ones for any geometry only
+const void *trc_shade_carry_kernel(bool lds, bool chart = false);      // k_s_shade_x (trc_shade.hip): every optics kind, with what the rays carry
+const void *trc_shade_lean_kernel(int cls, bool flat, bool lds, bool spec = false, bool chart = false);
 #ifndef SHC_THREADS
 #define SHC_THREADS 1024
 #endif

@@ -761,7 +761,7 @@ __device__ __forceinline__ void fast_new_ray(const FastParams &P, const double *
 // staged in LDS when they fit in 64 KiB, read from global memory otherwise.  Used when the single-precision data
 // cannot be built or do not fit (very large scenes), and as a cross-check of the cooperative kernel.
 //   LDS (doubles): [recs S*stride][kd_split nodes][buie 639][tally 3S+2] then int32: [kd_a][kd_b][leaf][always]
-template <int THREADS, bool SPEC = false, bool SUN = false>
+template <int THREADS, bool SPEC = false, bool SUN = false, bool CHART = false>
 __global__ __launch_bounds__(THREADS) void k_trace_fast(FastParams P) {
     extern __shared__ double lds[];
     const DScene &sc = P.sc;
@@ -859,8 +859,8 @@ __global__ __launch_bounds__(THREADS) void k_trace_fast(FastParams P) {
         }
         if (s < 0) { alive = false; continue; }
         nhit += 1.0;
-        if (P.lds_tally) alive = fast_shade<true>(P, recs, l_tally, t, s, px, py, pz, dx, dy, dz, e, ref, wl, rid, bounce, prev);
-        else alive = fast_shade<false>(P, recs, l_tally, t, s, px, py, pz, dx, dy, dz, e, ref, wl, rid, bounce, prev);
+        if (P.lds_tally) alive = fast_shade<true, false, CHART>(P, recs, l_tally, t, s, px, py, pz, dx, dy, dz, e, ref, wl, rid, bounce, prev);
+        else alive = fast_shade<false, false, CHART>(P, recs, l_tally, t, s, px, py, pz, dx, dy, dz, e, ref, wl, rid, bounce, prev);
     }
 
     // ---- flush ----
@@ -880,7 +880,7 @@ __global__ __launch_bounds__(THREADS) void k_trace_fast(FastParams P) {
 // memory (they are rare); everything the candidate search touches lives in LDS:
 //   doubles [buie 639][tally 3S+2] | float [sbox 6S] | u32 [nodes 2n] | i32 [always][unbounded] | u16 [leaf] |
 //   16-byte aligned per-wave regions of COOP_WAVE_BYTES(depth)
-template <int THREADS, bool SPEC = false, bool SUN = false>
+template <int THREADS, bool SPEC = false, bool SUN = false, bool CHART = false>
 __global__ __launch_bounds__(THREADS) void k_trace_coop(FastParams P) {
     extern __shared__ double lds[];
     const DScene &sc = P.sc;
@@ -1084,7 +1084,7 @@ __global__ __launch_bounds__(THREADS) void k_trace_coop(FastParams P) {
             if (s < 0) alive = false;
             else {
                 nhit += 1.0;
-                alive = fast_shade<true>(P, recs, l_tally, t, s, px, py, pz, dx, dy, dz, e, ref, wl, rid, bounce, prev);
+                alive = fast_shade<true, false, CHART>(P, recs, l_tally, t, s, px, py, pz, dx, dy, dz, e, ref, wl, rid, bounce, prev);
             }
         }
         WAVE_SYNC();
@@ -1105,6 +1105,12 @@ static bool surface_ends_every_ray(const trc_surface_desc &sd) {
                        ((ok == TRC_OPT_REAL_REFLECTIVE || ok == TRC_OPT_ONE_SIDED_REAL_REFLECTIVE) && sd.opt[3] == 0.0) ||
                        (ok == TRC_OPT_LAMBERTIAN && sd.opt[2] == 0.0 && sd.opt[4] == 0.0) || ok == TRC_OPT_LAMBERTIAN_SPECULAR;
     return plain && sd.opt[0] == 1.0;
+}
+
+// Some flux map of the scene bins in another chart than XY: the call runs the CHART instances of the kernels that finish hits
+static bool scene_has_chart_map(const trc_scene *sc) {
+    for (auto &m : sc->fms_h) if (m.chart != TRC_FM_XY) return true;
+    return false;
 }
 
 // Lets `fn` take `lds` bytes of dynamic LDS: beyond 64 KiB a kernel must be allowed them first
@@ -1206,7 +1212,8 @@ struct LdsStack32 {
 // float64 tests -- the same nearest hit, the same tie rule (trc_nearest_accel32; tests/hostcheck pins it against brute force) --
 // with its stack in LDS; otherwise the float64 walk of the caller's tree / brute force, with a stack in private memory.
 // MODE 2: the scene stands on the large grid (a mesh): trc_nearest_grid32.
-template <int MODE>
+// CHART: the flux maps may bin in the charts other than XY (trc_fluxmap_uv)
+template <int MODE, bool CHART = false>
 __global__ __launch_bounds__(256) void k_ord_bounce(OrdParams P) {
     constexpr bool FAST = MODE == 1;
     __shared__ uint32_t s_na[FAST ? ORD_STACK_DEPTH * 256 : 1];
@@ -1266,8 +1273,12 @@ __global__ __launch_bounds__(256) void k_ord_bounce(OrdParams P) {
         int fm = (!volume && sc.fm_of_surf) ? sc.fm_of_surf[s] : -1;
         if (fm >= 0) {
             const FluxMapDev &m = sc.fms[fm];
-            double u = m.proj[0] * hx + m.proj[1] * hy + m.proj[2] * hz + m.proj[3];
-            double v = m.proj[4] * hx + m.proj[5] * hy + m.proj[6] * hz + m.proj[7];
+            double u, v;
+            if constexpr (CHART) trc_fluxmap_uv(m.chart, m.proj, hx, hy, hz, &u, &v);
+            else {
+                u = m.proj[0] * hx + m.proj[1] * hy + m.proj[2] * hz + m.proj[3];
+                v = m.proj[4] * hx + m.proj[5] * hy + m.proj[6] * hz + m.proj[7];
+            }
             int iu = trc_bin_index(sc.fm_edges + m.edges_u, m.nu, u);
             int iv = trc_bin_index(sc.fm_edges + m.edges_v, m.nv, v);
             if (iu >= 0 && iv >= 0) atomicAdd(&sc.tally[m.bins + (int64_t)iu * m.nv + iv], e - e_out);
@@ -1805,15 +1816,21 @@ extern "C" int trc_scene_set_kdtree(trc_scene *sc, const trc_kdtree_desc *kd) {
 
 extern "C" int trc_scene_set_fluxmap(trc_scene *sc, int32_t surf, int32_t nu, int32_t nv, const double *u_edges,
                                            const double *v_edges, const double *proj12) {
+    return trc_scene_set_fluxmap_chart(sc, surf, TRC_FM_XY, nu, nv, u_edges, v_edges, proj12);
+}
+
+extern "C" int trc_scene_set_fluxmap_chart(trc_scene *sc, int32_t surf, int32_t chart, int32_t nu, int32_t nv, const double *u_edges,
+                                                 const double *v_edges, const double *proj12) {
     if (!sc || surf < 0 || surf >= sc->n_surf || nu <= 0 || nv <= 0 || !u_edges || !v_edges || !proj12)
-        return trc_fail(TRC_ERR_INVALID, "trc_scene_set_fluxmap: bad arguments");
+        return trc_fail(TRC_ERR_INVALID, "trc_scene_set_fluxmap_chart: bad arguments");
+    if (chart < 0 || chart >= TRC_FM_CHARTS) return trc_fail(TRC_ERR_INVALID, "trc_scene_set_fluxmap_chart: unknown chart %d", chart);
     HIP_TRY(hipSetDevice(sc->ctx->device));
     HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
     for (int i = 0; i < nu; ++i) if (!(u_edges[i + 1] > u_edges[i])) return trc_fail(TRC_ERR_INVALID, "u edges must increase");
     for (int i = 0; i < nv; ++i) if (!(v_edges[i + 1] > v_edges[i])) return trc_fail(TRC_ERR_INVALID, "v edges must increase");
     if (sc->fm_of_surf_h[surf] >= 0) return trc_fail(TRC_ERR_INVALID, "surface %d already has a flux map", surf);
     FluxMapDev m;
-    m.surf = surf; m.nu = nu; m.nv = nv; m.pad = 0;
+    m.surf = surf; m.nu = nu; m.nv = nv; m.chart = chart;
     m.edges_u = (int64_t)sc->fm_edges_h.size();
     sc->fm_edges_h.insert(sc->fm_edges_h.end(), u_edges, u_edges + nu + 1);
     m.edges_v = (int64_t)sc->fm_edges_h.size();
@@ -2912,14 +2929,17 @@ static int fast_choose_engine(const FastCall &C, StreamPlan *plan, bool *use_str
     return TRC_OK;
 }
 
-// the megakernel's instances for a source with a spectrum (SPEC: they draw the wavelength) and a tabulated sunshape (SUN)
+// the megakernel's instances for a source with a spectrum (SPEC: they draw the wavelength), a tabulated sunshape (SUN) and a scene
+// with a flux map in another chart than XY (CHART)
 struct MegaKernels { void (*coop512)(FastParams), (*coop256)(FastParams), (*fast256)(FastParams); };
-template <bool SPEC, bool SUN>
-static MegaKernels mega_kernels_of() { return {k_trace_coop<512, SPEC, SUN>, k_trace_coop<256, SPEC, SUN>, k_trace_fast<256, SPEC, SUN>}; }
-static MegaKernels mega_kernels(bool spec, bool sun) {
-    if (spec) return sun ? mega_kernels_of<true, true>() : mega_kernels_of<true, false>();
-    return sun ? mega_kernels_of<false, true>() : mega_kernels_of<false, false>();
+template <bool SPEC, bool SUN, bool CHART>
+static MegaKernels mega_kernels_of() { return {k_trace_coop<512, SPEC, SUN, CHART>, k_trace_coop<256, SPEC, SUN, CHART>, k_trace_fast<256, SPEC, SUN, CHART>}; }
+template <bool CHART>
+static MegaKernels mega_kernels_for(bool spec, bool sun) {
+    if (spec) return sun ? mega_kernels_of<true, true, CHART>() : mega_kernels_of<true, false, CHART>();
+    return sun ? mega_kernels_of<false, true, CHART>() : mega_kernels_of<false, false, CHART>();
 }
+static MegaKernels mega_kernels(bool spec, bool sun, bool chart) { return chart ? mega_kernels_for<true>(spec, sun) : mega_kernels_for<false>(spec, sun); }
 
 static int mega_launch(FastCall &C, const MegaPlan &M, const FastParams &P) {
     trc_scene *sc = C.sc;
@@ -2927,7 +2947,7 @@ static int mega_launch(FastCall &C, const MegaPlan &M, const FastParams &P) {
     (void)hipStreamSynchronize(ctx->stream);       // (the sums of an earlier streaming call may still be on their way into the buffer)
     if (hipMemcpy(C.tally_before, sc->d_tally.get() + 3 * sc->n_surf, sizeof(C.tally_before), hipMemcpyDeviceToHost) != hipSuccess)
         return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
-    const MegaKernels K = mega_kernels(P.spec != nullptr, C.d_src && source_is_sunshape(C.src->kind));
+    const MegaKernels K = mega_kernels(P.spec != nullptr, C.d_src && source_is_sunshape(C.src->kind), scene_has_chart_map(sc));
     void (*kern)(FastParams) = !M.m32 ? K.fast256 : (M.threads == 512 ? K.coop512 : K.coop256);
     // persistent grid: as many workgroups as are resident at once (at most 8 per CU), never more waves than rays/64
     unsigned resident = 0;
@@ -3136,6 +3156,7 @@ static int ordered_bounce(OrdCall &C, int it, int64_t n_cur, int64_t *m, int64_t
     (void)hipEventRecord(ctx->ev0, ctx->stream);
     const int mode = ordered_search_mode(sc, C.flags);
     void (*kern)(OrdParams) = mode == 2 ? k_ord_bounce<2> : (mode == 1 ? k_ord_bounce<1> : k_ord_bounce<0>);
+    if (scene_has_chart_map(sc)) kern = mode == 2 ? k_ord_bounce<2, true> : (mode == 1 ? k_ord_bounce<1, true> : k_ord_bounce<0, true>);
     hipLaunchKernelGGL(kern, dim3((unsigned)((n_cur + 255) / 256)), dim3(256), 0, ctx->stream, P);
     hipLaunchKernelGGL(k_compact_count, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, sx.key.get(), (long long)slots,
                        sx.blk_cnt.get(), sx.blk_cul.get());

@@ -21,7 +21,8 @@
 // FLATN: every surface of the scene is flat (its normal is the z axis of its frame, flat_surface.py:84-91)
 // LDS:   tallies, records, optics parameters, flux-map tables, flags (and the optics tables for the DIFFUSE class) are staged in
 //        LDS -- all of them or none, so that every access has a known address space (see k_s_shade)
-template <int CLS, bool FLATN, bool LDS, bool SPEC = false>
+// CHART: the flux maps may bin in the charts other than XY (record_hit, trc_device.h)
+template <int CLS, bool FLATN, bool LDS, bool SPEC = false, bool CHART = false>
 __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
     extern __shared__ double lds[];
     const FastParams &P = S.P;
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
                 ox = out[0].dx; oy = out[0].dy; oz = out[0].dz; e_out = out[0].e;
             }
             const double e_abs = e - e_out;
-            record_hit<LDS>(L, l_tally, s, e, e_abs, hx, hy, hz, g.dx, g.dy, g.dz, P.capture != 0, prev, &hc, l_fm, false, true);
+            record_hit<LDS, CHART>(L, l_tally, s, e, e_abs, hx, hy, hz, g.dx, g.dy, g.dz, P.capture != 0, prev, &hc, l_fm, false, true);
             ts = s; tea = e_abs; tei = e;        // (the three sums of the surface: below, per wave)
             if (e_out > P.min_energy) {                               // tracer_engine.py:242
                 if (bounce0 + 1 >= P.reps) {                          // still alive after the last iteration
@@ -203,7 +204,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
 //                         first interaction.  Scaled per sample by 1 - absorptance(theta, lambda_w) at a polychromatic wall, as a
 //                         whole by the optics' factor elsewhere -- what k_ord_bounce does for the ordered engine.
 // Given bundles only (a source descriptor makes rays of energy, index 1 and no wavelength).
-template <bool LDS>
+template <bool LDS, bool CHART = false>
 __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
     extern __shared__ double lds[];
     const FastParams &P = S.P;
@@ -335,7 +336,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
             const double e_out = out[0].e;
             const double e_abs = e - e_out;
             unsigned long long hslot = ~0ull;
-            record_hit<LDS>(L, l_tally, s, e, e_abs, hx, hy, hz, g.dx, g.dy, g.dz, P.capture != 0, prev, &hc, l_fm, volume, true, &hslot);
+            record_hit<LDS, CHART>(L, l_tally, s, e, e_abs, hx, hy, hz, g.dx, g.dy, g.dz, P.capture != 0, prev, &hc, l_fm, volume, true, &hslot);
             if (!volume) { ts = s; tea = e_abs; tei = e; }
             if (nW && C.hit_x && hslot != ~0ull) {        // a captured hit of a polychromatic ray: wavelengths, spectrum in, spectrum out
                 const double *tab = L.extra + trc_rec_extra_off(rec);
@@ -394,9 +395,19 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
     flush_sums(L.tally, l_tally, LDS ? 3 * Sn : 0, l_fm, S.lds_fm_bins, Sn);
 }
 
-const void *trc_shade_carry_kernel(bool lds) { return lds ? (const void *)k_s_shade_x<true> : (const void *)k_s_shade_x<false>; }
+const void *trc_shade_carry_kernel(bool lds, bool chart) {
+    if (chart) return lds ? (const void *)k_s_shade_x<true, true> : (const void *)k_s_shade_x<false, true>;
+    return lds ? (const void *)k_s_shade_x<true> : (const void *)k_s_shade_x<false>;
+}
 
-const void *trc_shade_lean_kernel(int cls, bool flat, bool lds, bool spec) {
+const void *trc_shade_lean_kernel(int cls, bool flat, bool lds, bool spec, bool chart) {
+    // a scene with a flux map in another chart than XY: the instances for any geometry (such a map lies on a cylinder, a dish or a
+    // sphere more often than on a round plate), which serve flat surfaces with the same arithmetic
+#define SHC_PICK_CHART(C) (spec ? (lds ? (const void *)k_s_shade_c<C, false, true, true, true> : (const void *)k_s_shade_c<C, false, false, true, true>) \
+                                : (lds ? (const void *)k_s_shade_c<C, false, true, false, true> : (const void *)k_s_shade_c<C, false, false, false, true>))
+    if (chart && cls == TRC_CLS_MIRROR) return SHC_PICK_CHART(TRC_CLS_MIRROR);
+    if (chart && cls == TRC_CLS_DIFFUSE) return SHC_PICK_CHART(TRC_CLS_DIFFUSE);
+#undef SHC_PICK_CHART
 #define SHC_PICK(C) (spec ? (flat ? (lds ? (const void *)k_s_shade_c<C, true, true, true> : (const void *)k_s_shade_c<C, true, false, true>) \
                                   : (lds ? (const void *)k_s_shade_c<C, false, true, true> : (const void *)k_s_shade_c<C, false, false, true>)) \
                           : (flat ? (lds ? (const void *)k_s_shade_c<C, true, true> : (const void *)k_s_shade_c<C, true, false>) \

@@ -1644,7 +1644,8 @@ __global__ __launch_bounds__(256) void k_s_partition(StreamParams S) {
 // LDS: tallies, records, optics parameters, flux-map tables, flags and table values are all staged in LDS -- or none of them is (as
 // in k_s_fresh): a pointer that may be either is read with flat loads, and a flat load waits for every load in flight -- the ray
 // records fetched ahead included (81 flat operations, 60 full waits in the instance that chose at run time).
-template <bool SIMPLE, int WAVES, bool LDS, bool SPEC = false>
+// CHART: the flux maps may bin in the charts other than XY (record_hit, trc_device.h)
+template <bool SIMPLE, int WAVES, bool LDS, bool SPEC = false, bool CHART = false>
 __global__ __launch_bounds__(128 * WAVES, WAVES) void k_s_shade(StreamParams S) {
     extern __shared__ double lds[];
     const FastParams &P = S.P;
@@ -1780,8 +1781,8 @@ __global__ __launch_bounds__(128 * WAVES, WAVES) void k_s_shade(StreamParams S) 
             else { e = ae; ref = ar; wl = aw; }
             const double e_in = e;
             bool vol = false;
-            if (LDS) alive = fast_shade<true, SIMPLE>(Pl, recs, l_tally, t, s, px, py, pz, dx, dy, dz, e, ref, wl, rid, bounce, prev, &hc, l_fm, true, &vol);
-            else alive = fast_shade<false, SIMPLE>(Pl, recs, l_tally, t, s, px, py, pz, dx, dy, dz, e, ref, wl, rid, bounce, prev, &hc, l_fm);
+            if (LDS) alive = fast_shade<true, SIMPLE, CHART>(Pl, recs, l_tally, t, s, px, py, pz, dx, dy, dz, e, ref, wl, rid, bounce, prev, &hc, l_fm, true, &vol);
+            else alive = fast_shade<false, SIMPLE, CHART>(Pl, recs, l_tally, t, s, px, py, pz, dx, dy, dz, e, ref, wl, rid, bounce, prev, &hc, l_fm);
             if (LDS && !vol) { ts = s; tea = e_in - e; tei = e_in; }      // (a volume event tallies nothing)
             if (alive) {
                 SRayGeo go;
@@ -2324,7 +2325,14 @@ static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene 
     // kernels for bounded arguments made it worse (their float64 constants live in scalar registers, which then spill into vector
     // ones))
     const bool spec = SP0.P.spec != nullptr;      // (a source with a spectrum: the instances that draw the wavelength at the first hit)
-    const void *shade_fn = spec ? (shade_simple ? (shade_lds ? (const void *)k_s_shade<true, 2, true, true> : (const void *)k_s_shade<true, 2, false, true>)
+    // A flux map in another chart than XY: the instances that know the charts -- of k_s_shade and of the lean kernels the ones for
+    // any geometry and any optics, which serve flat mirrors and walls with the same arithmetic.  Hits on surfaces that end every ray
+    // go to the shading kernels in such a scene (stream_form_absorb): k_s_absorb and k_s_bounce have no such instance.
+    const bool chart = scene_has_chart_map(sc);
+    if (chart) shade_simple = false;
+    const void *shade_fn = chart ? (spec ? (shade_lds ? (const void *)k_s_shade<false, 2, true, true, true> : (const void *)k_s_shade<false, 2, false, true, true>)
+                                         : (shade_lds ? (const void *)k_s_shade<false, 2, true, false, true> : (const void *)k_s_shade<false, 2, false, false, true>))
+                         : spec ? (shade_simple ? (shade_lds ? (const void *)k_s_shade<true, 2, true, true> : (const void *)k_s_shade<true, 2, false, true>)
                                                 : (shade_lds ? (const void *)k_s_shade<false, 2, true, true> : (const void *)k_s_shade<false, 2, false, true>))
                                 : shade_simple ? (shade_lds ? (const void *)k_s_shade<true, 2, true> : (const void *)k_s_shade<true, 2, false>)
                                                : (shade_lds ? (const void *)k_s_shade<false, 2, true> : (const void *)k_s_shade<false, 2, false>);
@@ -2347,7 +2355,7 @@ static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene 
             if (term_cls < 0)          // nothing lean among the others: the terminal surfaces go by their own class
                 for (int i = 0; i < S; ++i) present[trc_shade_class_of(sc->surfs[i])] = true;
         }
-        const bool all_flat = all_surfaces_flat(sc);
+        const bool all_flat = !chart && all_surfaces_flat(sc);
         for (int c = 0; c < TRC_CLS_GENERAL; ++c) {
             if (!present[c]) continue;
             StreamShadeK &K = F.shk[n_shk++];
@@ -2355,7 +2363,7 @@ static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene 
             bool in_lds;
             K.lds = shade_lds_choose(sc, c == TRC_CLS_MIRROR ? TRC_IMG_LEAN_MIRROR : TRC_IMG_LEAN, bins, &in_lds, &K.lds_fm_bins);
             K.lds_tables = in_lds ? 1 : 0;
-            K.fn = trc_shade_lean_kernel(c, all_flat, in_lds, spec);
+            K.fn = trc_shade_lean_kernel(c, all_flat, in_lds, spec, chart);
             TRC_TRY(stream_shade_grid(K, n_cu));
         }
     }
@@ -2366,7 +2374,7 @@ static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene 
         K.fn = shade_fn; K.threads = 256; K.wpb = 4; K.max_blocks = (unsigned)(n_cu * 4); K.lds = lds_shade;
         K.lds_tables = SP0.lds_tables; K.lds_fm_bins = SP0.lds_fm_bins;
         if (carry) {            // sixteen waves per workgroup
-            K.fn = trc_shade_carry_kernel(shade_lds);
+            K.fn = trc_shade_carry_kernel(shade_lds, chart);
             K.threads = SHC_THREADS; K.wpb = SHC_THREADS / 64;
             TRC_TRY(stream_shade_grid(K, n_cu));
         } else
@@ -2502,8 +2510,9 @@ static int stream_form_absorb(StreamForms &F, StreamParams &SP0, const trc_scene
     for (int i = 0; i < sc->n_surf && !any; ++i) any = surface_ends_every_ray(sc->surfs[i]);
     const long long bins = flux_map_bins(sc);
     const size_t lds_absorb = shade_lds_need(shade_lds_parts(sc, TRC_IMG_ABSORB, true, SP0.lds_fm_bins));
-    const bool fm_ok = bins == 0 || SP0.lds_fm_bins > 0;       // (bins outside LDS would be scattered global atomics at eight waves per SIMD: not this kernel)
-    F.use_absorb = any && fm_ok && lds_absorb <= trc_shade_lds_limit(TRC_IMG_ABSORB, true) && sc->tr_off < 0 && SP0.P.min_energy >= 0.0 && K.absorb != 0;      // (0 <= min_energy: the ray ends there in the reference too)
+    const bool fm_ok = bins == 0 || SP0.lds_fm_bins > 0;       // (bins outside LDS would be scattered global atomics at eight waves per SIMD: not this kernel;
+                                                                // nor a map in another chart than XY: k_s_absorb and k_s_bounce bin in x, y only)
+    F.use_absorb = any && fm_ok && !scene_has_chart_map(sc) && lds_absorb <= trc_shade_lds_limit(TRC_IMG_ABSORB, true) && sc->tr_off < 0 && SP0.P.min_energy >= 0.0 && K.absorb != 0;      // (0 <= min_energy: the ray ends there in the reference too)
     if (!F.use_absorb) return TRC_OK;
     // one workgroup of 16 waves per CU (4096 waves with open chunks of the hit buffer at most)
     F.absorb = {(const void *)k_s_absorb, SA_THREADS, lds_absorb, (unsigned)sc->ctx->n_cu};

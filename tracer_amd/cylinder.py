@@ -5,6 +5,7 @@ Constructors as in the reference's tracer/cylinder.py (:12-18, :59-68, :161-168)
 import numpy as N
 from . import _cabi
 from .quadric import QuadricGM
+from .flat_surface import _grid_flux
 
 
 class InfiniteCylinder(QuadricGM):
@@ -26,15 +27,19 @@ class FiniteCylinder(InfiniteCylinder):
     def _native(self):
         return _cabi.GM_CYL_FINITE, [self._R, self._half_h, self._ang_range[0], self._ang_range[1]], []
 
-    def get_fluxmap(self, eners, local_coords, resolution):
-        """Energy per area on a (z, azimuth) grid of the wall."""
+    def fluxmap_grid(self, resolution):
+        """(chart, swap_xy, u_edges, v_edges, areas): the grid of get_fluxmap -- height by azimuth over ang_range
+        (cylinder.py:139-159) -- for a flux map binned on the device (TracerEngine.set_surface_fluxmap)."""
         zs = N.linspace(-self._half_h, self._half_h, resolution + 1)
         angs = N.linspace(self._ang_range[0], self._ang_range[1], resolution + 1)
+        areas = N.diff(zs)[:, None] * (self._R * N.diff(angs))[None, :]
+        return 'cylinder', False, zs, angs, areas
+
+    def get_fluxmap(self, eners, local_coords, resolution):
+        """Energy per area on a (z, azimuth) grid of the wall."""
         az = N.arctan2(local_coords[1], local_coords[0])
         az[az < 0.] += 2. * N.pi
-        h = N.histogram2d(local_coords[2], az, bins=[zs, angs], weights=eners)[0]
-        areas = N.diff(zs)[:, None] * (self._R * N.diff(angs))[None, :]
-        return N.hstack(h / areas)
+        return _grid_flux(self.fluxmap_grid(resolution), local_coords[2], az, eners)
 
 
 class RectCutCylinder(FiniteCylinder):

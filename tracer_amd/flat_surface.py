@@ -22,10 +22,12 @@ class FiniteFlatGM(FlatGeometryManager):
         FlatGeometryManager.__init__(self)
 
 
-def _histogram_flux(xs, ys, coords_x, coords_y, eners):
-    """Energy per unit area on a rectilinear grid (flat_surface.py:237-251)."""
-    h = N.histogram2d(coords_x, coords_y, bins=[xs, ys], weights=eners)[0]
-    areas = N.abs(N.diff(xs))[:, None] * N.abs(N.diff(ys))[None, :]
+def _grid_flux(grid, us, vs, eners):
+    """Energy per unit area on a grid (chart, swap_xy, u_edges, v_edges, areas) of a fluxmap_grid(): histogram2d of the chart
+    coordinates us, vs over its edges, divided by its bin areas, the rows side by side as the reference returns them
+    (flat_surface.py:244-251)."""
+    _, _, u_edges, v_edges, areas = grid
+    h = N.histogram2d(us, vs, bins=[u_edges, v_edges], weights=eners)[0]
     return N.hstack(h / areas)
 
 
@@ -52,10 +54,17 @@ class RectPlateGM(FiniteFlatGM):
         x, y = N.broadcast_arrays(xs[:, None], ys)
         return x, y, N.zeros_like(x)
 
-    def get_fluxmap(self, eners, local_coords, resolution):
+    def fluxmap_grid(self, resolution):
+        """(chart, swap_xy, u_edges, v_edges, areas): the grid of get_fluxmap -- resolution x resolution bins of the local x, y
+        over the plate (flat_surface.py:237-251) -- for a flux map binned on the device (TracerEngine.set_surface_fluxmap)."""
         xs = N.linspace(-self._half_dims[0, 0], self._half_dims[0, 0], resolution + 1)
         ys = N.linspace(-self._half_dims[1, 0], self._half_dims[1, 0], resolution + 1)
-        return _histogram_flux(xs, ys, local_coords[0], local_coords[1], eners)
+        areas = N.abs(N.diff(xs))[:, None] * N.abs(N.diff(ys))[None, :]
+        return 'xy', False, xs, ys, areas
+
+    def get_fluxmap(self, eners, local_coords, resolution):
+        # (the plate's own grid, for the children too: the plates with holes have no single grid, and keep this map)
+        return _grid_flux(RectPlateGM.fluxmap_grid(self, resolution), local_coords[0], local_coords[1], eners)
 
 
 class ExtrudedRectPlateGM(RectPlateGM):
@@ -65,6 +74,9 @@ class ExtrudedRectPlateGM(RectPlateGM):
         self.extr_center = extr_center
         self.extr_half_dims = N.c_[[extr_width, extr_height]] / 2.
         assert ((extr_center + self.extr_half_dims) < self._half_dims).all()
+
+    def fluxmap_grid(self, resolution):
+        raise NotImplementedError("ExtrudedRectPlateGM: the reference's flux map has four regions (flat_surface.py:321-364); no single grid")
 
     def _native(self):
         c = N.ravel(self.extr_center)
@@ -117,17 +129,21 @@ class RoundPlateGM(FiniteFlatGM):
         y = N.outer(rs, N.sin(angs))
         return x, y, N.zeros_like(x)
 
-    def get_fluxmap(self, eners, local_coords, resolution):
-        """Polar-bin flux map (flat_surface.py:524-545; note the reference's arctan2(x, y) order)."""
+    def fluxmap_grid(self, resolution):
+        """(chart, swap_xy, u_edges, v_edges, areas): the grid of get_fluxmap -- radius by the azimuth arctan2(x, y), which is the
+        polar chart with x and y exchanged (flat_surface.py:524-545) -- for a flux map binned on the device."""
         if resolution is None:
             resolution = 40
+        rs, angs = self._polar_grid(resolution)
+        areas = N.diff(rs)[:, None] * ((rs[1:] + rs[:-1]) / 2.)[:, None] * N.abs(N.diff(angs))[None, :]
+        return 'polar', True, rs, angs, areas
+
+    def get_fluxmap(self, eners, local_coords, resolution):
+        """Polar-bin flux map (flat_surface.py:524-545; note the reference's arctan2(x, y) order)."""
         rads = N.sqrt(N.sum(local_coords[:2] ** 2, axis=0))
         azim = N.arctan2(local_coords[0], local_coords[1])
         azim[azim < 0.] += 2. * N.pi
-        rs, angs = self._polar_grid(resolution)
-        h = N.histogram2d(rads, azim, bins=[rs, angs], weights=eners)[0]
-        areas = N.diff(rs)[:, None] * ((rs[1:] + rs[:-1]) / 2.)[:, None] * N.abs(N.diff(angs))[None, :]
-        return N.hstack(h / areas)
+        return _grid_flux(RoundPlateGM.fluxmap_grid(self, resolution), rads, azim, eners)      # (the disc's own grid, for the cut disc too)
 
 
 class StraightCutRoundPlateGM(RoundPlateGM):
@@ -135,6 +151,9 @@ class StraightCutRoundPlateGM(RoundPlateGM):
     def __init__(self, Re, x_cut=None):
         RoundPlateGM.__init__(self, Re)
         self.x_cut = x_cut
+
+    def fluxmap_grid(self, resolution):
+        raise NotImplementedError("StraightCutRoundPlateGM: the reference's flux map has several regions (flat_surface.py:605-680); no single grid")
 
     def _native(self):
         return _cabi.GM_ROUND_CUT, [self._Re, -1. if self._Ri is None else self._Ri,

@@ -6,6 +6,7 @@ tracer/paraboloid.py (:11-28, :71-87, :174-190, :225-255, :328-342, :386-403).
 import numpy as N
 from . import _cabi
 from .quadric import QuadricGM
+from .flat_surface import _grid_flux
 from .spatial_geometry import roty, rotz
 
 
@@ -41,17 +42,21 @@ class ParabolicDishGM(Paraboloid):
         y = N.outer(rs, N.sin(angs))
         return x, y, self.a * x ** 2 + self.b * y ** 2
 
+    def fluxmap_grid(self, resolution):
+        """(chart, swap_xy, u_edges, v_edges, areas): the grid of get_fluxmap -- radius by azimuth, the areas those of the
+        paraboloid's surface (paraboloid.py:151-172) -- for a flux map binned on the device."""
+        r = N.r_[0:self._R * (1. + 1. / resolution):self._R / resolution]
+        ang = N.r_[0:2. * N.pi * (1 + 1. / resolution):2 * N.pi / resolution][:resolution + 1]
+        grow = (4. * self.a ** 2 * r ** 2 + 1.) ** 1.5
+        areas = (grow[1:] - grow[:-1])[:, None] * (ang[1:] - ang[:-1])[None, :]
+        return 'polar', False, r, ang, areas
+
     def get_fluxmap(self, eners, local_coords, resolution):
         """Polar-bin flux map with paraboloid surface areas (paraboloid.py:151-172)."""
         rads = N.sqrt(N.sum(local_coords[:2] ** 2., axis=0))
         angs = N.arctan2(local_coords[1], local_coords[0])
         angs[angs < 0.] += 2. * N.pi
-        r = N.r_[0:self._R * (1. + 1. / resolution):self._R / resolution]
-        ang = N.r_[0:2. * N.pi * (1 + 1. / resolution):2 * N.pi / resolution][:resolution + 1]
-        h = N.histogram2d(rads, angs, bins=[r, ang], weights=eners)[0]
-        grow = (4. * self.a ** 2 * r ** 2 + 1.) ** 1.5
-        areas = (grow[1:] - grow[:-1])[:, None] * (ang[1:] - ang[:-1])[None, :]
-        return N.hstack(h / areas)
+        return _grid_flux(self.fluxmap_grid(resolution), rads, angs, eners)
 
 
 class HexagonalParabolicDishGM(Paraboloid):

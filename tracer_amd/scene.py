@@ -305,18 +305,24 @@ class DeviceScene(object):
         _cabi.check(self.lib.trc_scene_set_kdtree(self.handle, C.byref(d)))
 
     # -- tallies ----------------------------------------------------------------------------------
-    def set_fluxmap(self, surf_index, u_edges, v_edges, proj=None):
+    def set_fluxmap(self, surf_index, u_edges, v_edges, proj=None, chart='xy'):
         """
         Accumulate absorbed energy of surface `surf_index` on the grid u_edges x v_edges of its local
         x, y.  proj defaults to round(inv(frame), 9) (Surface.global_to_local, surface.py:125).
+        chart: the coordinates (u, v) of a hit -- 'xy' (x, y), 'cylinder' (z, azimuth), 'polar' (radius, azimuth),
+        'sphere' (polar angle, azimuth), azimuth = arctan2(y, x) in [0, 2 pi] -- or its number (_cabi.FM_*).
         """
         u = _cabi.f64(u_edges)
         v = _cabi.f64(v_edges)
         if proj is None:
             proj = N.round(N.linalg.inv(self.compiled.surfaces[surf_index]._temp_frame), decimals=9)
         p = _cabi.f64(N.asarray(proj)[:3].ravel())
-        _cabi.check(self.lib.trc_scene_set_fluxmap(self.handle, surf_index, len(u) - 1, len(v) - 1, _cabi.ptr(u),
-                                                   _cabi.ptr(v), _cabi.ptr(p)))
+        if isinstance(chart, str):
+            if chart not in _cabi.FM_CHARTS:
+                raise ValueError("unknown flux-map chart %r (one of %s)" % (chart, sorted(_cabi.FM_CHARTS)))
+            chart = _cabi.FM_CHARTS[chart]
+        _cabi.check(self.lib.trc_scene_set_fluxmap_chart(self.handle, surf_index, int(chart), len(u) - 1, len(v) - 1, _cabi.ptr(u),
+                                                         _cabi.ptr(v), _cabi.ptr(p)))
         self.fluxmaps[surf_index] = (len(u) - 1, len(v) - 1)
 
     def get_fluxmap(self, surf_index):

@@ -6,6 +6,7 @@ BoundaryPlane / BoundarySphere / BoundaryCylinder given in the surface's own fra
 import numpy as N
 from . import _cabi
 from .quadric import QuadricGM
+from .flat_surface import _grid_flux
 
 
 class SphericalGM(QuadricGM):
@@ -24,16 +25,20 @@ class SphericalGM(QuadricGM):
     def _native(self):
         return _cabi.GM_SPHERE, [self._rad], []
 
-    def get_fluxmap(self, eners, local_coords, resolution):
-        """Energy per area on a (polar angle, azimuth) grid of resolution x 2*resolution bins (sphere_surface.py:100-115)."""
+    def fluxmap_grid(self, resolution):
+        """(chart, swap_xy, u_edges, v_edges, areas): the grid of get_fluxmap -- resolution bins of the polar angle by
+        2 * resolution of the azimuth (sphere_surface.py:100-115) -- for a flux map binned on the device."""
         ths_bin = N.linspace(0., N.pi, resolution + 1)
         phis_bin = N.linspace(0., 2. * N.pi, resolution * 2 + 1)
+        areas = self._rad ** 2. * N.diff(phis_bin)[None, :] * (N.cos(ths_bin[:-1]) - N.cos(ths_bin[1:]))[:, None]
+        return 'sphere', False, ths_bin, phis_bin, areas
+
+    def get_fluxmap(self, eners, local_coords, resolution):
+        """Energy per area on a (polar angle, azimuth) grid of resolution x 2*resolution bins (sphere_surface.py:100-115)."""
         ths = N.arccos(local_coords[2] / self._rad)
         phis = N.arctan2(local_coords[1], local_coords[0])
         phis[phis < 0.] += 2. * N.pi
-        h = N.histogram2d(ths, phis, bins=[ths_bin, phis_bin], weights=eners)[0]
-        areas = self._rad ** 2. * N.diff(phis_bin)[None, :] * (N.cos(ths_bin[:-1]) - N.cos(ths_bin[1:]))[:, None]
-        return N.hstack(h / areas)
+        return _grid_flux(self.fluxmap_grid(resolution), ths, phis, eners)
 
 
 class HemisphereGM(SphericalGM):

@@ -25,6 +25,7 @@ import weakref
 import numpy as N
 
 from . import rng
+from . import _cabi
 from .accel_tree import KdTree
 from .ray_bundle import RayBundle, concatenate_rays
 from .scene import compile_scene, DeviceScene, NotNativeError, feed_accountants, PendingHits
@@ -41,7 +42,8 @@ class TracerEngine(object):
         self._dev_sig = None
         self._dev_static_sig = None
         self._dev_frames = None
-        self._fluxmap_requests = {}
+        self._fluxmap_requests = {}     # surface index -> (u edges, v edges, chart, swap_xy)
+        self._fluxmap_areas = {}        # ... -> bin areas of a map set from the surface's geometry (set_surface_fluxmap)
         self._transfer = False
         self._transfer_host = None      # contribution of ordered-engine runs (from the tree's parents)
         self._kd_on_device = None
@@ -93,8 +95,11 @@ class TracerEngine(object):
                 self._dev.close()
             self._dev = DeviceScene(compiled)
             self._dev_static_sig = compiled.signature_without_frames()
-            for si, (u, v) in self._fluxmap_requests.items():
-                self._dev.set_fluxmap(si, u, v)
+            for si, (u, v, chart, swap_xy) in self._fluxmap_requests.items():
+                proj = None
+                if swap_xy:     # the chart's x and y exchanged: RoundPlateGM's arctan2(x, y) (flat_surface.py:528)
+                    proj = N.round(N.linalg.inv(compiled.surfaces[si]._temp_frame), decimals=9)[[1, 0, 2, 3]]
+                self._dev.set_fluxmap(si, u, v, proj=proj, chart=chart)
             if self._transfer:
                 self._dev.enable_transfer(True)
         self._dev_sig = sig
@@ -108,17 +113,49 @@ class TracerEngine(object):
         new = compiled.frames12()
         return all(N.array_equal(self._dev_frames[si], new[si]) for si in self._fluxmap_requests)
 
-    def set_fluxmap(self, surface, u_edges, v_edges):
+    def set_fluxmap(self, surface, u_edges, v_edges, chart='xy', swap_xy=False):
         """
         Ask the device to bin the energy absorbed by `surface` (a Surface of the assembly, or its
         index) on u_edges x v_edges of its local x, y -- the on-device form of the caller-side
         numpy.histogram2d of the reference's examples.  Read it back with get_fluxmap().
+
+        chart: the coordinates the edges are in -- 'xy' (x, y), 'cylinder' (z, azimuth), 'polar' (radius, azimuth) or 'sphere'
+        (polar angle, azimuth) of the surface's local frame, the azimuth arctan2(y, x) in [0, 2 pi] as the reference's
+        get_fluxmap of those shapes takes it.  swap_xy: the local x and y exchanged first (RoundPlateGM's arctan2(x, y)).
         """
+        if chart not in _cabi.FM_CHARTS:
+            raise ValueError("unknown flux-map chart %r (one of %s)" % (chart, sorted(_cabi.FM_CHARTS)))
         si = surface if isinstance(surface, int) else self._asm.get_surfaces().index(surface)
-        self._fluxmap_requests[si] = (N.asarray(u_edges, dtype=float), N.asarray(v_edges, dtype=float))
+        self._fluxmap_requests[si] = (N.asarray(u_edges, dtype=float), N.asarray(v_edges, dtype=float), chart, bool(swap_xy))
+        self._fluxmap_areas.pop(si, None)
         if self._dev is not None:
             self._dev.close()
             self._dev = None
+
+    def set_surface_fluxmap(self, surface, resolution=None):
+        """
+        The flux map of the surface's own shape on the device: chart, edges and bin areas of its geometry manager's
+        get_fluxmap(.., resolution) (fluxmap_grid).  Read it with get_surface_flux().  A geometry without such a grid
+        raises NotImplementedError.
+        """
+        surfs = self._asm.get_surfaces()
+        si = surface if isinstance(surface, int) else surfs.index(surface)
+        grid = getattr(surfs[si].get_geometry_manager(), 'fluxmap_grid', None)
+        if grid is None:
+            raise NotImplementedError("%s has no flux-map grid" % type(surfs[si].get_geometry_manager()).__name__)
+        chart, swap_xy, u_edges, v_edges, areas = grid(resolution)
+        self.set_fluxmap(si, u_edges, v_edges, chart=chart, swap_xy=swap_xy)
+        self._fluxmap_areas[si] = N.asarray(areas, dtype=float)
+
+    def get_surface_flux(self, surface):
+        """energy per area of the bins of a map set by set_surface_fluxmap: the array the geometry's get_fluxmap returns"""
+        si = surface if isinstance(surface, int) else self._asm.get_surfaces().index(surface)
+        if si not in self._fluxmap_areas:
+            raise ValueError("surface %d has no flux map set by set_surface_fluxmap (a map set by set_fluxmap has no bin areas: "
+                             "read it with get_fluxmap)" % si)
+        if self._dev is None:
+            raise ValueError("no trace since the flux map of surface %d was set: there is nothing to read yet" % si)
+        return N.hstack(self._dev.get_fluxmap(si) / self._fluxmap_areas[si])
 
     def get_fluxmap(self, surface):
         si = surface if isinstance(surface, int) else self._asm.get_surfaces().index(surface)
