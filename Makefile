@@ -86,6 +86,16 @@ $(UMASKCHECK): $(UMASKCHECK_SRC) $(HDR)
 $(UMASKCHECK_EXE): $(UMASKCHECK_SRC) $(HDR)
 	$(CXX) -O2 -g -std=c++17 $(FPFLAGS) $(SAN) -DUMASK_CHECK_MAIN -o $@ $(UMASKCHECK_SRC)
 
+# the room of a streaming call whose optics split rays (trc_split_room_need, trc_split_grow: trc_bounds.h) on a grid of inputs: a
+# program of its own, built with the sanitizers and run by tests/test_split_cases_host.py
+SPLITCHECK_EXE := $(ROOT)tests/splitcheck/split_check
+SPLITCHECK_SRC := $(ROOT)tests/splitcheck/split_check.cpp
+SPLIT_SAN ?= -fsanitize=address,undefined -fno-sanitize-recover=undefined
+splitcheck: $(SPLITCHECK_EXE)
+
+$(SPLITCHECK_EXE): $(SPLITCHECK_SRC) $(HDR)
+	$(CXX) -O1 -g -std=c++17 $(FPFLAGS) $(SPLIT_SAN) -o $@ $(SPLITCHECK_SRC)
+
 # assembly listings with the registers, scratch and occupancy of every kernel (build/*.s, build/*.resources.txt)
 asm: $(SRCS) $(HDR)
 	mkdir -p $(ROOT)build
@@ -102,4 +112,4 @@ asm-shade: $(CSRC)/trc_shade.hip $(HDR)
 clean:
 	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK)
 
-.PHONY: all hostcheck umaskcheck umaskcheck-exe asm asm-shade clean
+.PHONY: all hostcheck umaskcheck umaskcheck-exe splitcheck asm asm-shade clean

@@ -421,11 +421,19 @@ int trc_kdtree_traversal(trc_ctx *ctx, const trc_kdtree_desc *kd, int32_t n_surf
  * A given bundle may carry what Refractive / RefractiveAbsorbant and the polychromatic wall read (ref_index_im, mat, spec_wl +
  * spectra): such calls, and calls on scenes with those optics, run the streaming form (64 rays or more; TRC_ERR_UNSUPPORTED with
  * TRC_TRACE_MEGAKERNEL or fewer rays: use trc_trace_ordered).  Captured hits keep their spectra (trc_scene_get_hits_x); `last` does not.
+ * Optics that send two rays on from a hit (RefractiveHomogenous and its family, Refractive / RefractiveAbsorbant with single_ray off)
+ * run the streaming form too, under the same conditions, from a given bundle or a source descriptor: the hit is recorded once
+ * (tallies, flux map, transfer matrix, hit buffer), with what neither ray takes along as the absorbed energy -- of a polychromatic
+ * hit the spectrum that left is the sum of the two rays' -- and the second ray's stream id is the ordered engine's.  Such a call
+ * can leave more than n rays (`last`) and capture more than n hits per bounce: more rays left than `last` holds is
+ * TRC_ERR_CAPACITY with stats->rays_left set, hits beyond the buffer are counted in stats->hits_dropped, as ever.  Its ray table
+ * never recycles a slot and grows between bounces (TRC_ERR_NOMEM when it cannot; TRC_ERR_CAPACITY beyond 2^32 slots).
  */
 int trc_trace_fast(trc_scene *scene, const trc_rays *in, const trc_source_desc *src, int64_t n,
                    int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset,
                    int32_t flags, trc_rays *last, trc_trace_stats *stats);
-/* The same with the spectrum of `src` (NULL: trc_trace_fast).  A spectrum with a given bundle `in` is TRC_ERR_INVALID. */
+/* The same with the spectrum of `src` (NULL: trc_trace_fast).  A spectrum with a given bundle `in` is TRC_ERR_INVALID; a spectrum
+   on a scene whose optics send two rays on from a hit is TRC_ERR_UNSUPPORTED (use trc_trace_ordered_x). */
 int trc_trace_fast_x(trc_scene *scene, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
                      int64_t n, int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset,
                      int32_t flags, trc_rays *last, trc_trace_stats *stats);

@@ -752,4 +752,42 @@ static inline bool trc_accel_build_kd(const trc_kdtree_desc *kd, trc_accel_host 
     return true;
 }
 
+// ---- the room of a streaming call whose optics split rays (k_s_shade_x<.., SPLIT>) --------------------------------------------
+// Such a call never recycles a slot of the ray table: a hit that sends two rays on keeps its slot for the first and takes a new
+// one for the second.  What one bounce can ask of a workspace, from what the host knows before it launches the bounce:
+//   slots          slots of the ray table handed out so far (bounce 0: what the search stage can hand out, its unused chunk
+//                  tails included)
+//   live           rays that enter the bounce: at most as many hits, as many new slots and twice as many rays that go on
+//   search_tails   entries the appending waves of the search stage can leave unused in a list (waves x chunk, summed over
+//                  the kernels that append to one list)
+//   shade_waves    waves of the shading kernel; every wave can leave one chunk of slots (slot_chunk entries) and one chunk of the
+//                  active list (act_chunk entries) unused
+// room: entries of the ray table, of the tables beside it and of every list of the search stage; act_room: of the active lists.
+// The sums saturate at 2^64 - 1 instead of wrapping (a need beyond the 32-bit slot numbers is refused by the caller).
+typedef unsigned long long trc_u64;
+static inline trc_u64 trc_sat_add(trc_u64 a, trc_u64 b) { return a > ~0ull - b ? ~0ull : a + b; }
+static inline trc_u64 trc_sat_mul(trc_u64 a, trc_u64 b) { return (a != 0 && b > ~0ull / a) ? ~0ull : a * b; }
+struct trc_split_room { trc_u64 room, act_room; };
+static inline trc_split_room trc_split_room_need(trc_u64 slots, trc_u64 live, trc_u64 search_tails, trc_u64 shade_waves, trc_u64 slot_chunk,
+                                                 trc_u64 act_chunk) {
+    trc_split_room r;
+    const trc_u64 table = trc_sat_add(trc_sat_add(slots, live), trc_sat_mul(shade_waves, slot_chunk));
+    const trc_u64 lists = trc_sat_add(live, search_tails);
+    r.room = table > lists ? table : lists;
+    r.act_room = trc_sat_add(trc_sat_mul(2ull, live), trc_sat_mul(shade_waves, act_chunk));
+    return r;
+}
+// `slots` for bounce 0, where nothing has been handed out yet: the search stage gives every ray of the batch that hits a slot
+// (at most nb) and can leave `search_slot_tails` entries of its waves' chunks unused; the shading kernel of the same bounce then
+// takes its slots behind those.
+static inline trc_u64 trc_split_slots_bounce0(trc_u64 nb, trc_u64 search_slot_tails) { return trc_sat_add(nb, search_slot_tails); }
+// The doubling rule: the size a table of `have` entries grows to for a need of `need` -- `have` itself while it is enough, else
+// the first of 2 have, 4 have, ... (from 64 entries) that reaches the need; 2^64 - 1 where doubling would wrap.
+static inline trc_u64 trc_split_grow(trc_u64 have, trc_u64 need) {
+    if (need <= have) return have;
+    trc_u64 r = have < 64ull ? 64ull : have;
+    while (r < need) r = r > ~0ull / 2ull ? ~0ull : 2ull * r;
+    return r;
+}
+
 #endif  // TRC_BOUNDS_H

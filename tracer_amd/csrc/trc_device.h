@@ -316,6 +316,10 @@ struct CarryIn {
     double *slot_spec;      // the slot's table of spectra under way: sample w of the ray in slot s at slot_spec[w * room + s] (null: none)
     double *hit_x;          // 3 n_spec columns beside the hit buffer, hit_x_cap entries each (null: no spectra per captured hit):
     long long hit_x_cap;    // sample wavelengths, spectrum that arrived, spectrum that left
+    // a scene whose optics split rays (k_s_shade_x<.., SPLIT>): the Philox stream of the ray in every slot of the ray table, which
+    // is no function of SRayGeo.idx once a hit has sent two rays on (trc_child_rid); null for every other call.  Last, for the
+    // reason given above.
+    unsigned long long *slot_rid;
 };
 
 struct FastParams {
@@ -680,7 +684,8 @@ __device__ __forceinline__ void tally_by_wave(double *tl, int Sn, int ts, double
 
 // the lean shading kernels (trc_shade.hip): kernel of a class for a scene of flat surfaces only (flat) with its tables in LDS (lds)
 // chart: the instance that knows every flux-map chart (record_hit<.., CHART>) -- of the lean kernels the ones for any geometry only
-const void *trc_shade_carry_kernel(bool lds, bool chart = false);      // k_s_shade_x (trc_shade.hip): every optics kind, with what the rays carry
+const void *trc_shade_carry_kernel(bool lds, bool chart = false, bool split = false);      // k_s_shade_x (trc_shade.hip): every optics kind, with what the rays carry;
+                                                                                            // split: its form for scenes whose optics send two rays on from a hit
 const void *trc_shade_lean_kernel(int cls, bool flat, bool lds, bool spec = false, bool chart = false);
 #ifndef SHC_THREADS
 #define SHC_THREADS 1024

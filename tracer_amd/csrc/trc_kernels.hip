@@ -2795,7 +2795,11 @@ static int fast_check_args(FastCall &C) {
     if ((C.in == nullptr) == (C.src == nullptr)) return trc_fail(TRC_ERR_INVALID, "exactly one of `in` and `src` must be given");
     if (C.n < 0 || C.reps < 0) return trc_fail(TRC_ERR_INVALID, "n and reps must be >= 0");
     TRC_TRY(source_resolve(sc->ctx, C.src, C.src_res, "trc_trace_fast"));
-    if (sc->splits) return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has ray-splitting optics: use trc_trace_ordered");
+    // Optics that send two rays on from a hit are traced by the streaming form alone (k_s_shade_x<.., SPLIT>), as rays that carry
+    // more are: not by the megakernel, not in calls too small for that form, and not under a source with a spectrum (k_s_shade_x
+    // has no instance that draws wavelengths).
+    if (sc->splits && ((C.flags & TRC_TRACE_MEGAKERNEL) || C.n < 64 || C.spec->desc))
+        return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has ray-splitting optics, which the fast engine traces in its streaming form only (64 rays or more, no source spectrum): use trc_trace_ordered");
     C.knobs = stream_knobs();
     // Rays that carry the imaginary part of a complex index, materials evaluated at their wavelength or a sampled spectrum are
     // traced by the streaming form (k_s_shade_x); the megakernel knows nothing of them.
@@ -2919,13 +2923,15 @@ static void fast_params(const FastCall &C, const MegaPlan &M, FastParams *P, Car
 static int fast_choose_engine(const FastCall &C, StreamPlan *plan, bool *use_stream) {
     *plan = {0, 0, true};
     const bool stream_ok = C.n >= 64 && stream_plan(C.sc, (C.flags & TRC_TRACE_ACCEL) != 0, C.knobs, plan);
-    const bool force_stream = (C.flags & TRC_TRACE_STREAM) || C.carry;
-    const bool force_mega = !C.carry && (C.flags & TRC_TRACE_MEGAKERNEL);
+    // (rays that carry more, and optics that send two rays on from a hit, are the streaming form's alone: k_s_shade_x)
+    const bool stream_only = C.carry || C.sc->splits;
+    const bool force_stream = (C.flags & TRC_TRACE_STREAM) || stream_only;
+    const bool force_mega = !stream_only && (C.flags & TRC_TRACE_MEGAKERNEL);
     // (a scene on the large grid -- a mesh of 1e5 faces -- has nothing but its boxes to search in the megakernel: 2e5 rays on the
     // relief of 105 800 triangles took 570 ms there, 1.3 ms here)
     const long long stream_from = plan->mode == 3 ? 4096 : TRC_STREAM_MIN_RAYS;
     *use_stream = stream_ok && (force_stream || (!force_mega && C.n >= stream_from));
-    if (C.carry && !*use_stream) return trc_fail(TRC_ERR_UNSUPPORTED, "no streaming form for this scene: rays that carry complex indices or spectra go through trc_trace_ordered");
+    if (stream_only && !*use_stream) return trc_fail(TRC_ERR_UNSUPPORTED, "no streaming form for this scene: rays that carry complex indices or spectra, and ray-splitting optics, go through trc_trace_ordered");
     return TRC_OK;
 }
 

@@ -204,7 +204,15 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
 //                         first interaction.  Scaled per sample by 1 - absorptance(theta, lambda_w) at a polychromatic wall, as a
 //                         whole by the optics' factor elsewhere -- what k_ord_bounce does for the ordered engine.
 // Given bundles only (a source descriptor makes rays of energy, index 1 and no wavelength).
-template <bool LDS, bool CHART = false>
+// SPLIT: the scene has optics that send two rays on from a hit (RefractiveHomogenous(single_ray=False) and its family,
+//        optics_callables.py:600-724, :726-858): the reflected and the refracted ray of the reference's deterministic Fresnel mode.
+//        The hit is recorded once, with what neither ray takes along as the absorbed energy (k_ord_bounce); each ray is culled,
+//        counted or kept on its own.  The first goes back into the hit's slot, the second takes a new slot of the ray table
+//        (CN(CW_SLOTS): slots are never recycled in such a call, the host grows the table between bounces), and both are appended to
+//        the next active list.  The second ray's Philox stream is trc_child_rid(parent's, event) as in the ordered engine, so the
+//        stream of the ray in a slot is kept in CarryIn.slot_rid: read from the second bounce on, written for every ray that goes on.
+//        What a ray carries (Im of its index, its spectrum) goes with both.  Given bundles and source descriptors (without spectrum).
+template <bool LDS, bool CHART = false, bool SPLIT = false>
 __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
     extern __shared__ double lds[];
     const FastParams &P = S.P;
@@ -249,6 +257,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
     WaveChunk ca = S.static_first ? chunk_init_static_at(S.chunk_act, (unsigned long long)S.act_base0 + (unsigned long long)wave_g * S.chunk_act) : chunk_init(S.chunk_act);
     WaveChunk hc = chunk_init(S.chunk_hitbuf);
     if (P.capture && wave_g < SHADE_MAX_WAVES) hit_chunk_resume(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
+    WaveChunk cs = chunk_init(S.chunk_slot);        // (SPLIT) slots of the ray table for the second ray of a hit
     unsigned n_hit = 0, n_alive = 0;
     const int bounce0 = S.bounce_no;
     const bool aux_in = !P.src || bounce0 > 0;
@@ -275,6 +284,8 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
         const unsigned long long my_lanes = __ballot(mine);
         if (!my_lanes) continue;
         bool alive = false;
+        bool alive1 = false;            // (SPLIT) the hit's second ray goes on, from slot1
+        uint32_t slot1 = SQ_INVALID;
         int ts = -1;
         double tea = 0.0, tei = 0.0;
         if (mine) {
@@ -299,7 +310,8 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
             if (nW && !first) { X.spec = C.slot_spec + slot; spec_stride = W.room; }
             trc_ray_out out[2];
             double out_im[2], poly_th;
-            const unsigned long long rid = P.rid ? P.rid[ray] : (P.ray_offset + (unsigned long long)ray);
+            unsigned long long rid = P.rid ? P.rid[ray] : (P.ray_offset + (unsigned long long)ray);
+            if (SPLIT && !first) rid = C.slot_rid[slot];
             // (sample wavelengths and spectrum have different strides once the spectrum lives in the slot table: the polychromatic
             // wall reads both, so its integral is taken here with the two strides, the optics get the wavelengths' stride)
             int n_out;
@@ -330,11 +342,11 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
                 n_out = trc_shade_x(trc_rec_opt_kind(rec), L.opt + (size_t)s * 8, L.extra, trc_rec_extra_off(rec), trc_rec_extra_len(rec),
                                     rec[2], rec[5], rec[8], g.dx, g.dy, g.dz, e, ref, wl, path, nx, ny, nz, P.seed, rid, (uint32_t)(bounce0 + 1),
                                     X, out, out_im, &poly_th);
-            (void)n_out;        // (scenes whose optics split rays go to the ordered engine)
+            const bool two = SPLIT && n_out == 2;       // (the other instances serve scenes none of whose optics sends two rays on)
             const bool volume = out[0].back > 0.0;          // scattered in the medium before the surface (see fast_shade)
             if (volume) { hx -= out[0].back * g.dx; hy -= out[0].back * g.dy; hz -= out[0].back * g.dz; }
             const double e_out = out[0].e;
-            const double e_abs = e - e_out;
+            const double e_abs = SPLIT ? e - (two ? out[0].e + out[1].e : out[0].e) : e - e_out;
             unsigned long long hslot = ~0ull;
             record_hit<LDS, CHART>(L, l_tally, s, e, e_abs, hx, hy, hz, g.dx, g.dy, g.dz, P.capture != 0, prev, &hc, l_fm, volume, true, &hslot);
             if (!volume) { ts = s; tea = e_abs; tei = e; }
@@ -342,10 +354,46 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
                 const double *tab = L.extra + trc_rec_extra_off(rec);
                 for (int w = 0; w < nW; ++w) {
                     const double xw = X.wl[(long long)w * P.n], yin = X.spec[(long long)w * spec_stride];
-                    const double f = poly_th >= 0.0 ? 1.0 - trc_poly_absorptance(tab, poly_th, xw) : out[0].sf;
+                    const double f = poly_th >= 0.0 ? 1.0 - trc_poly_absorptance(tab, poly_th, xw) : (two ? out[0].sf + out[1].sf : out[0].sf);
                     C.hit_x[(long long)w * C.hit_x_cap + (long long)hslot] = xw;
                     C.hit_x[(long long)(nW + w) * C.hit_x_cap + (long long)hslot] = yin;
                     C.hit_x[(long long)(2 * nW + w) * C.hit_x_cap + (long long)hslot] = yin * f;
+                }
+            }
+            if constexpr (SPLIT) {
+                // the second ray, before the first goes back into the hit's slot (whose spectrum row it reads)
+                const bool on1 = two && out[1].e > P.min_energy;
+                if (on1 && bounce0 + 1 >= P.reps) {
+                    atomicAdd(&sc.counters[3], 1ull);
+                    atomicAdd(sc.energy_left, out[1].e);
+                    if (P.flags & TRC_TRACE_KEEP_LAST) {
+                        const unsigned long long q = atomicAdd(&sc.counters[2], 1ull);
+                        if ((long long)q < P.last_cap) {
+                            P.lx[q] = hx + out[1].shift * nx; P.ly[q] = hy + out[1].shift * ny; P.lz[q] = hz + out[1].shift * nz;
+                            P.ldx[q] = out[1].dx; P.ldy[q] = out[1].dy; P.ldz[q] = out[1].dz; P.le[q] = out[1].e;
+                        }
+                    }
+                }
+                alive1 = on1 && bounce0 + 1 < P.reps;
+                // (the lanes with a hit are all here: cs is handed to the others behind the region, as the hit buffer's chunk is)
+                const unsigned long long sl = chunk_append(&W.cnt[CN(CW_SLOTS)], cs, alive1, nullptr, 0);
+                if (alive1 && (long long)sl >= W.room) { W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL; alive1 = false; }
+                if (alive1) {
+                    slot1 = (uint32_t)sl;
+                    SRayGeo go;
+                    go.px = hx + out[1].shift * nx; go.py = hy + out[1].shift * ny; go.pz = hz + out[1].shift * nz;
+                    go.dx = out[1].dx; go.dy = out[1].dy; go.dz = out[1].dz;
+                    go.head = SQ_INVALID;
+                    go.idx = g.idx;             // (still the place of the bundle's columns: materials, sample wavelengths)
+                    uint32_t pw = volume ? (uint32_t)prev : (uint32_t)s;
+                    if (!volume && out[1].shift == 0.0 && leaves_flat(rec, hx, hy, hz, out[1].dx, out[1].dy, out[1].dz)) pw |= SQ_SKIP_SELF;
+                    go.tail = sray_tail(bounce0 + 1, pw);
+                    W.geo[slot1] = go;
+                    SRayAux ao;
+                    ao.e = out[1].e; ao.ref = out[1].ref; ao.wl = wl; ao.pad = out_im[1];
+                    W.aux[slot1] = ao;
+                    C.slot_rid[slot1] = trc_child_rid(rid, (uint32_t)(bounce0 + 1));
+                    for (int w = 0; w < nW; ++w) C.slot_spec[(long long)w * W.room + slot1] = X.spec[(long long)w * spec_stride] * out[1].sf;
                 }
             }
             const double ox = out[0].dx, oy = out[0].dy, oz = out[0].dz;
@@ -374,6 +422,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
                     SRayAux ao;
                     ao.e = e_out; ao.ref = out[0].ref; ao.wl = wl; ao.pad = out_im[0];
                     W.aux[slot] = ao;
+                    if (SPLIT) C.slot_rid[slot] = rid;          // (the first ray keeps the parent's stream)
                     if (nW) {       // the spectrum goes on with the ray (RayBundle.inherit, ray_bundle.py:117-143), the optics' changes applied
                         const double *tab = L.extra + trc_rec_extra_off(rec);
                         for (int w = 0; w < nW; ++w) {
@@ -386,8 +435,13 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
         }
         tally_by_wave<6>(LDS ? l_tally : L.tally, Sn, ts, tea, tei, (!LDS || Sn <= 64) ? 8 : 0);     // (the loop of k_s_shade_c)
         if (P.capture) chunk_rebroadcast(hc, __ffsll((long long)my_lanes) - 1);
+        if (SPLIT) chunk_rebroadcast(cs, __ffsll((long long)my_lanes) - 1);
         const unsigned long long q = chunk_append(&W.cnt[CN(CW_ACT_OUT)], ca, alive, S.act_out, W.act_room);
         if (alive) { if ((long long)q < W.act_room) S.act_out[q] = slot; else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL; n_alive += 1; }
+        if constexpr (SPLIT) {      // (a wave whose 64 lanes all split appends 128 entries in this turn: a round of its own, so that each fits a chunk)
+            const unsigned long long q1 = chunk_append(&W.cnt[CN(CW_ACT_OUT)], ca, alive1, S.act_out, W.act_room);
+            if (alive1) { if ((long long)q1 < W.act_room) S.act_out[q1] = slot1; else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL; n_alive += 1; }
+        }
     }
     chunk_close(ca, S.act_out, W.act_room);
     if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
@@ -395,7 +449,11 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
     flush_sums(L.tally, l_tally, LDS ? 3 * Sn : 0, l_fm, S.lds_fm_bins, Sn);
 }
 
-const void *trc_shade_carry_kernel(bool lds, bool chart) {
+const void *trc_shade_carry_kernel(bool lds, bool chart, bool split) {
+    if (split) {
+        if (chart) return lds ? (const void *)k_s_shade_x<true, true, true> : (const void *)k_s_shade_x<false, true, true>;
+        return lds ? (const void *)k_s_shade_x<true, false, true> : (const void *)k_s_shade_x<false, false, true>;
+    }
     if (chart) return lds ? (const void *)k_s_shade_x<true, true> : (const void *)k_s_shade_x<false, true>;
     return lds ? (const void *)k_s_shade_x<true> : (const void *)k_s_shade_x<false>;
 }

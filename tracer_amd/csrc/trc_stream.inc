@@ -2110,6 +2110,12 @@ struct StreamSlot {
     DevBuf<double> spec;          // spectra of the rays under way (CarryIn.slot_spec), spec_len doubles; spec_on: this call brings spectra
     long long spec_len = 0;
     bool spec_on = false;
+    // a call whose optics split rays (k_s_shade_x<.., SPLIT>): the Philox stream of the ray in every slot (CarryIn.slot_rid, rid_len
+    // entries), the slots handed out by the bounces done, and the slots a wave of the shading kernel reserves per atomic
+    DevBuf<unsigned long long> rid;
+    long long rid_len = 0;
+    unsigned long long slots_used = 0;
+    unsigned chunk_slot_sh = SQ_CHUNK;
     StreamHandle stream;          // slot 0 borrows the context's stream, which is not this slot's to destroy; the others own theirs
     EventHandle done;
     PinnedWords h_cnt;            // pinned: CN_WORDS counters read back, then CN_WORDS counters to upload
@@ -2304,7 +2310,8 @@ static int stream_shade_grid(StreamShadeK &K, int n_cu) {
 
 // The shading kernels: one per optics class present in the scene (trc_shade.hip), each taking its hits off the bounce's list, or one
 // for every hit (k_s_shade_x) when the rays carry more than the fast engine's record.
-static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene *sc, bool carry) {
+// (split: some optics of the scene send two rays on from a hit -- a carry call served by k_s_shade_x<.., SPLIT>)
+static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene *sc, bool carry, bool split_rays) {
     const int n_cu = sc->ctx->n_cu;
     const int S = sc->n_surf;
     const long long bins = flux_map_bins(sc);
@@ -2374,7 +2381,7 @@ static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene 
         K.fn = shade_fn; K.threads = 256; K.wpb = 4; K.max_blocks = (unsigned)(n_cu * 4); K.lds = lds_shade;
         K.lds_tables = SP0.lds_tables; K.lds_fm_bins = SP0.lds_fm_bins;
         if (carry) {            // sixteen waves per workgroup
-            K.fn = trc_shade_carry_kernel(shade_lds, chart);
+            K.fn = trc_shade_carry_kernel(shade_lds, chart, split_rays);
             K.threads = SHC_THREADS; K.wpb = SHC_THREADS / 64;
             TRC_TRY(stream_shade_grid(K, n_cu));
         } else
@@ -2530,7 +2537,7 @@ static int stream_form_absorb(StreamForms &F, StreamParams &SP0, const trc_scene
 }
 
 // Chooses the kernel of every stage for this call and sets up SP0, the parameters every batch starts from
-static int stream_choose_forms(StreamForms &F, StreamParams &SP0, trc_scene *sc, StreamEngine &E, const StreamPlan &plan, bool carry,
+static int stream_choose_forms(StreamForms &F, StreamParams &SP0, trc_scene *sc, StreamEngine &E, const StreamPlan &plan, bool carry, bool split_rays,
                                const trc_source_desc *src_desc, const StreamKnobs &K) {
     const int S = sc->n_surf;
     memset(&F, 0, sizeof(F));
@@ -2545,14 +2552,15 @@ static int stream_choose_forms(StreamForms &F, StreamParams &SP0, trc_scene *sc,
     SP0.search = plan.walk_ok ? plan.mode : 2;
     SP0.hit_epoch = sc->hits.epoch;
     TRC_TRY(stream_form_general(F, SP0, sc, plan));
-    TRC_TRY(stream_form_shade(F, SP0, sc, carry));
+    TRC_TRY(stream_form_shade(F, SP0, sc, carry, split_rays));
     TRC_TRY(stream_form_fresh(F, SP0, sc, E, src_desc, K));
     TRC_TRY(stream_form_bounce(F, SP0, sc, plan, K));
     return stream_form_absorb(F, SP0, sc, carry, K);
 }
 
 // workspaces of the slots for batches of `cap` rays: queues, spectra of the rays under way, the class lists of k_s_partition
-static int stream_slots_alloc(StreamEngine &E, int n_slots, long long cap, const trc_scene *sc, const CarryIn &carry_in, const StreamForms &F, const StreamKnobs &K) {
+static int stream_slots_alloc(StreamEngine &E, int n_slots, long long cap, const trc_scene *sc, const CarryIn &carry_in, const StreamForms &F, const StreamKnobs &K,
+                              bool split_rays) {
     for (int k = 0; k < n_slots; ++k) {
         StreamSlot &Tk = E.slot[k];
         TRC_TRY(stream_ws_alloc(Tk.W, cap, (int)sc->accel.unbounded.size(), (long long)sc->tally_n, K));
@@ -2563,6 +2571,11 @@ static int stream_slots_alloc(StreamEngine &E, int n_slots, long long cap, const
             Tk.spec_len = want;
         }
         Tk.spec_on = want > 0;
+        if (split_rays && Tk.rid_len < Tk.W.room) {
+            Tk.rid_len = 0;
+            TRC_TRY(Tk.rid.alloc((size_t)Tk.W.room));
+            Tk.rid_len = Tk.W.room;
+        }
         StreamBuffers &Wk = Tk.W;
         if (!F.multi) continue;
         Wk.pl_room = 2 * Wk.room;
@@ -2587,6 +2600,7 @@ struct StreamCall {
     double seg, hits;
     double cls_hits[TRC_CLS_COUNT];      // hits shaded by the kernel of each class (first STREAM_RATE_BOUNCES bounces)
     int launches, max_bounces;
+    bool split_rays;                     // the scene's optics can send two rays on from a hit (k_s_shade_x<.., SPLIT>)
 };
 
 // a grid of g workgroups, at least one and at most max_blocks
@@ -2706,6 +2720,7 @@ static void plan_bounce(const StreamCall &C, StreamSlot &T) {
                 double ex = act_expected;
                 const int c = F.shk[k].cls;
                 if (c >= 0 && T.b < STREAM_RATE_BOUNCES && E.rate_cls[T.b][c] >= 0.0 && E.rate_cls[T.b][c] * rays_in < ex) ex = E.rate_cls[T.b][c] * rays_in;
+                if (C.split_rays) ex *= 2.0;        // (two entries per hit)
                 double cc = 1.1 * ex / (double)waves + 128.0;
                 if (cc > most) cc = most;
                 chunk = ((unsigned)cc + 63u) & ~63u;
@@ -2716,6 +2731,13 @@ static void plan_bounce(const StreamCall &C, StreamSlot &T) {
             base += (long long)waves * (long long)chunk;
         }
         T.SP.chunk_act = T.chunk_act_sh[0];
+        // the second rays' slots: at most one per ray that enters the bounce, in chunks that leave little of the ray table unused
+        T.chunk_slot_sh = SQ_CHUNK;
+        if (C.split_rays && total_waves) {
+            double cc = 1.1 * rays_in / (double)total_waves + 64.0;
+            if (cc > (double)SQ_CHUNK_MAX) cc = (double)SQ_CHUNK_MAX;
+            T.chunk_slot_sh = ((unsigned)cc + 63u) & ~63u;
+        }
     }
     T.gb_gen = grid_for(F.g_gen, 256 * SW_ITEMS);
     T.gb_wide = grid_for(F.g_wide, 256 * SW_ITEMS);
@@ -2790,6 +2812,7 @@ static int launch_bounce(StreamCall &C, StreamSlot &T) {
         }
         SK.chunk_act = T.chunk_act_sh[k];
         SK.act_base0 = T.act_base_sh[k];
+        if (C.split_rays) SK.chunk_slot = T.chunk_slot_sh;
         SK.lds_tables = K.lds_tables; SK.lds_extra = K.lds_tables; SK.lds_fm_bins = K.lds_fm_bins;
         void *args[] = {(void *)&SK};
         HIP_TRY(hipLaunchKernel(K.fn, dim3(T.gb_sh[k]), dim3(K.threads), args, K.lds, T.stream.get()));
@@ -2832,8 +2855,110 @@ static int upload_counters(const StreamCall &C, StreamSlot &T) {
         up[CN(CW_FP_LIST)] = cull_waves * (unsigned long long)T.cull_chunk;                                   // footprint list <- k_s_cull
         if (T.fused && T.SP.split_terminal == 1) up[CN(CW_TERM_LIST)] = (unsigned long long)T.gb_bounce * (unsigned long long)(F.bounce.threads / 64) * T.SP.chunk_thit;   // terminal hits <- k_s_bounce
     }
+    // (slots are never recycled where rays split: the shading kernel goes on from the slots handed out so far)
+    if (C.split_rays && T.b > 0) up[CN(CW_SLOTS)] = T.slots_used;
     HIP_TRY(hipMemcpyAsync(T.SP.W.cnt, up, CN_WORDS * sizeof(unsigned long long), hipMemcpyHostToDevice, T.stream.get()));
     return TRC_OK;
+}
+
+// ---- a call whose optics split rays: a ray table that grows --------------------------------------------------------------------
+// Larger tables for a slot between two bounces: ray table, the tables beside it (streams, spectra) and every list of `room` entries,
+// new_room entries each; the two active lists, new_act entries each.  What is live at that point is copied -- the records and
+// streams of the slots handed out, their spectra (sample-major, `room` apart: one strided copy), the active list coming in --
+// everything else of that size is scratch between bounces.  The slot's stream is idle (its last bounce has been read back).
+static int split_grow(StreamSlot &T, long long new_room, long long new_act, int n_spec) {
+    StreamBuffers &W = T.W;
+    hipStream_t st = T.stream.get();
+    const size_t live = (size_t)T.slots_used;
+    auto fail = [&](int e) { T.W = StreamBuffers(); T.spec_len = 0; T.rid_len = 0; return e; };       // (a workspace half grown claims nothing)
+    if (new_room > W.room) {
+        DevBuf<SRayGeo> geo;
+        DevBuf<SRayAux> aux;
+        DevBuf<unsigned long long> rid;
+        DevBuf<double> spec;
+        if (int e = geo.alloc((size_t)new_room)) return fail(e);
+        if (int e = aux.alloc((size_t)new_room)) return fail(e);
+        if (int e = rid.alloc((size_t)new_room)) return fail(e);
+        if (T.spec_on) if (int e = spec.alloc((size_t)n_spec * (size_t)new_room)) return fail(e);
+        hipError_t he = hipSuccess;
+        if (live) {
+            he = hipMemcpyAsync(geo.get(), W.geo.get(), live * sizeof(SRayGeo), hipMemcpyDeviceToDevice, st);
+            if (he == hipSuccess) he = hipMemcpyAsync(aux.get(), W.aux.get(), live * sizeof(SRayAux), hipMemcpyDeviceToDevice, st);
+            if (he == hipSuccess) he = hipMemcpyAsync(rid.get(), T.rid.get(), live * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st);
+            if (he == hipSuccess && T.spec_on)
+                he = hipMemcpy2DAsync(spec.get(), (size_t)new_room * 8, T.spec.get(), (size_t)W.room * 8, live * 8, (size_t)n_spec, hipMemcpyDeviceToDevice, st);
+        }
+        if (he == hipSuccess) he = hipStreamSynchronize(st);       // (the old tables go back to the pool below)
+        if (he != hipSuccess) { (void)fail(TRC_ERR_DEVICE); return trc_fail(TRC_ERR_DEVICE, "copy into the grown ray table failed: %s", hipGetErrorString(he)); }
+        W.geo = std::move(geo); W.aux = std::move(aux); T.rid = std::move(rid); T.rid_len = new_room;
+        if (T.spec_on) { T.spec = std::move(spec); T.spec_len = (long long)n_spec * new_room; }
+        const size_t cq = (size_t)new_room;
+        int e = W.q1_slot.alloc(cq);
+        if (!e) e = W.q1_a.alloc(cq);
+        if (!e) e = W.q1_b.alloc(cq);
+        if (!e) e = W.hit_slot.alloc(cq);
+        if (!e) e = W.hit_surf.alloc(cq);
+        if (!e) e = W.hit_t.alloc(cq);
+        if (!e) e = W.gen_list.alloc(cq);
+        if (!e) e = W.fq_ray.alloc(cq);
+        if (!e) e = W.fq_cell.alloc(cq);
+        if (e) return fail(e);
+        // (the class lists of k_s_partition follow `room`: a later call that parts its hit list makes them again)
+        for (int c = 0; c < TRC_CLS_COUNT; ++c) { W.pl_slot[c].reset(); W.pl_surf[c].reset(); W.pl_t[c].reset(); }
+        W.pl_room = 0;
+        W.room = new_room;
+    }
+    if (new_act > W.act_room) {
+        const int in = T.cur ^ 1;           // (the list coming in, once a bounce has been shaded)
+        DevBuf<uint32_t> a0, a1;
+        if (int e = a0.alloc((size_t)new_act)) return fail(e);
+        if (int e = a1.alloc((size_t)new_act)) return fail(e);
+        if (T.b > 0 && T.n_act) {
+            hipError_t he = hipMemcpyAsync((in == 0 ? a0 : a1).get(), W.act[in].get(), (size_t)T.n_act * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
+            if (he == hipSuccess) he = hipStreamSynchronize(st);
+            if (he != hipSuccess) { (void)fail(TRC_ERR_DEVICE); return trc_fail(TRC_ERR_DEVICE, "copy into the grown active list failed: %s", hipGetErrorString(he)); }
+        }
+        W.act[0] = std::move(a0); W.act[1] = std::move(a1);
+        W.act_room = new_act;
+    }
+    return TRC_OK;
+}
+
+// Before the search kernel of a bounce of such a call: what the bounce as planned can ask of the ray table and of the lists
+// (trc_split_room_need, trc_bounds.h) against what the slot has; when short, tables of at least twice the size (trc_split_grow).
+// Larger tables allow larger chunks, so the bounce is planned again behind every growth.
+static int split_ensure_room(const StreamCall &C, StreamSlot &T) {
+    const StreamForms &F = C.F;
+    for (int round = 0; round < 8; ++round) {
+        plan_bounce(C, T);
+        const unsigned long long live = T.b == 0 ? (unsigned long long)T.nb : (unsigned long long)T.n_in;
+        const unsigned long long w_fresh = T.fresh ? (unsigned long long)T.gb_fresh * (unsigned long long)(F.fresh.threads / 64) : 0ull;
+        const unsigned long long w_fused = T.fused ? (unsigned long long)T.gb_bounce * (unsigned long long)(F.bounce.threads / 64) : 0ull;
+        const unsigned long long w_first = T.first ? (unsigned long long)T.gb_first * (unsigned long long)(F.first.threads / 64) : 0ull;
+        const unsigned long long w_cull = T.fresh ? (unsigned long long)T.gb_cull * (SC_THREADS / 64) : 0ull;
+        const unsigned long long w_gen = T.general ? (unsigned long long)T.gb_gen * 4ull : 0ull, w_exact = T.general ? (unsigned long long)T.gb_wide * 4ull : 0ull;
+        // the lists of `room` entries, each with the unused tails of the waves that append to it: hit list, walker queue, k_s_cull's two
+        const unsigned long long t_hit = w_fresh * T.SP.chunk_hit + w_fused * T.SP.chunk_hit + w_first * T.SP.chunk_first + w_exact * SQ_CHUNK;
+        const unsigned long long t_q1 = w_gen * T.SP.chunk_q1;
+        const unsigned long long t_cull = w_cull * ((unsigned long long)T.cull_chunk + T.cull_gen_chunk + SC_GEN_CAP);
+        unsigned long long tails = t_hit > t_q1 ? t_hit : t_q1;
+        if (t_cull > tails) tails = t_cull;
+        // bounce 0: the search stage hands out the slots, at most one per ray and a chunk per wave unused
+        const unsigned long long slots = T.b > 0 ? T.slots_used
+                                                 : trc_split_slots_bounce0((unsigned long long)T.nb, w_fresh * T.SP.chunk_slot + w_gen * SQ_CHUNK + w_first * T.SP.chunk_first);
+        const unsigned long long w_shade = (unsigned long long)T.gb_sh[0] * F.shk[0].wpb;
+        const trc_split_room need = trc_split_room_need(slots, live, tails, w_shade, T.chunk_slot_sh, T.chunk_act_sh[0]);
+        if ((long long)need.room <= T.W.room && (long long)need.act_room <= T.W.act_room && need.room < (1ull << 62) && need.act_room < (1ull << 62)) return TRC_OK;
+        const unsigned long long new_room = trc_split_grow((unsigned long long)T.W.room, need.room), new_act = trc_split_grow((unsigned long long)T.W.act_room, need.act_room);
+        if (new_room >= (unsigned long long)SQ_INVALID || new_act >= (1ull << 40))
+            return trc_fail(TRC_ERR_CAPACITY, "the ray table of a call that splits rays cannot grow beyond 2^32 slots (%llu needed): slots are not recycled", need.room);
+        TRC_TRY(split_grow(T, (long long)new_room, (long long)new_act, C.SP0.carry.n_spec));
+        T.SP.W = T.W.view();
+        T.SP.carry.slot_spec = T.spec_on ? T.spec.get() : nullptr;
+        T.SP.carry.slot_rid = T.rid.get();
+        if (T.b > 0) T.SP.act_in = T.SP.W.act[T.cur ^ 1];
+    }
+    return trc_fail(TRC_ERR_CAPACITY, "the room of a call that splits rays did not settle (%lld slots, %lld active entries)", T.W.room, T.W.act_room);
 }
 
 static int start_batch(StreamCall &C, StreamSlot &T, long long base) {
@@ -2841,11 +2966,14 @@ static int start_batch(StreamCall &C, StreamSlot &T, long long base) {
     T.base = base;
     T.nb = (n - base < C.cap) ? (n - base) : C.cap;
     T.n_in = T.nb; T.n_act = 0; T.b = 0; T.cur = 0; T.attempt = 0; T.busy = true;
+    T.slots_used = 0;
     T.SP = C.SP0;
     T.SP.W = T.W.view();
     T.SP.carry.slot_spec = T.spec_on ? T.spec.get() : nullptr;
+    T.SP.carry.slot_rid = C.split_rays ? T.rid.get() : nullptr;
     T.SP.base = base;
     T.SP.nb = T.nb;
+    if (C.split_rays) TRC_TRY(split_ensure_room(C, T));
     TRC_TRY(upload_counters(C, T));
     return launch_bounce(C, T);
 }
@@ -2870,6 +2998,7 @@ static int advance(StreamCall &C, StreamSlot &T) {
         return launch_bounce(C, T);
     }
     T.attempt = 0;
+    if (C.split_rays) T.slots_used = c[CN(CW_SLOTS)];       // (reserved: the unused tails of the waves' chunks stay unused)
     C.seg += (double)T.n_in;
     C.hits += (double)c[CN(CW_HITS)];
     if (T.fresh && T.nb > 0) {       // what the next batches can expect (with a margin; a low guess only costs atomics)
@@ -2900,6 +3029,7 @@ static int advance(StreamCall &C, StreamSlot &T) {
     T.SP.act_in = T.SP.W.act[T.cur];
     T.cur ^= 1;
     T.b += 1;
+    if (C.split_rays) TRC_TRY(split_ensure_room(C, T));
     TRC_TRY(upload_counters(C, T));
     return launch_bounce(C, T);
 }
@@ -2924,14 +3054,16 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, c
     }
     // rays that carry more than the fast engine's record -- Im of a complex index, materials at their wavelength, a spectrum -- are
     // shaded by k_s_shade_x; the spectra of the rays under way live in a table of their own beside the ray table
-    const bool carry = sc->needs.any() || carry_in.ref_im || carry_in.mat || carry_in.spec;
+    // ... and so are all hits of a scene whose optics send two rays on from a hit, by its SPLIT form
+    const bool split_rays = sc->splits;
+    const bool carry = sc->needs.any() || carry_in.ref_im || carry_in.mat || carry_in.spec || split_rays;
     StreamForms F;
-    StreamCall C{F, K, E, StreamParams(), cap, 0.0, 0.0, {0.0, 0.0, 0.0}, 0, 0};
+    StreamCall C{F, K, E, StreamParams(), cap, 0.0, 0.0, {0.0, 0.0, 0.0}, 0, 0, split_rays};
     memset(&C.SP0, 0, sizeof(C.SP0));
     C.SP0.P = P;
     C.SP0.carry = carry_in;
-    TRC_TRY(stream_choose_forms(F, C.SP0, sc, E, plan, carry, src_desc, K));
-    TRC_TRY(stream_slots_alloc(E, n_slots, cap, sc, carry_in, F, K));
+    TRC_TRY(stream_choose_forms(F, C.SP0, sc, E, plan, carry, split_rays, src_desc, K));
+    TRC_TRY(stream_slots_alloc(E, n_slots, cap, sc, carry_in, F, K, split_rays));
 
     for (int k = 0; k < STREAM_MAX_SLOTS; ++k) E.slot[k].busy = false;
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));

@@ -115,6 +115,8 @@ class PendingLevels(Delivery):
                     wavelengths=bundle.get_wavelengths() if has_wl else None,
                     spectra=N.asarray(bundle.get_spectra()) if n_spec else None)
         prev_surf = None
+        dev = getattr(self.engine, '_dev', None)
+        splits = dev is not None and bool(dev.compiled.splits)       # some optics send two rays on from a hit
         for lv in range(1, lv_src.nlev):
             L = lv_src.level(lv)
             # accountants: hits of a surface in the order the reference selects them (ascending parent).  Only the hits on
@@ -133,6 +135,24 @@ class PendingLevels(Delivery):
                     whole = False
                     so, po = L['surf'][order], par[order]
                 sel = slice(None) if whole else order
+                if splits:
+                    key = so.astype(N.int64) * (1 << 40) + po
+                if splits and len(key) > 1 and (key[1:] == key[:-1]).any():
+                    # A hit that sent two rays on (single_ray=False) is one hit: the reference's accountants see its point once
+                    # (LocationAccountant, optics_callables.py:1610-1611) and one incident energy (:1699-1701), and what it
+                    # absorbed is that less what both rays take along.  Fed ray by ray, such a hit was counted twice.
+                    first = N.r_[True, key[1:] != key[:-1]]
+                    starts = N.nonzero(first)[0]
+                    idx = N.arange(len(par)) if whole else order
+                    e_out = N.add.reduceat(L['energy'][idx], starts)
+                    one = idx[starts]
+                    feed_accountants(surfaces, so[starts], prev['energy'][po[starts]], e_out, L['vertices'][:, one], prev['directions'][:, po[starts]],
+                                     None if prev['wavelengths'] is None else prev['wavelengths'][po[starts]],
+                                     spectra=None if not n_spec else (prev['spectra'][:, po[starts]], N.add.reduceat(L['spectra'][:, idx], starts, axis=1),
+                                                                      L['wavelengths'][:, one]),
+                                     only=holders)
+                    order = order[:0]
+            if len(order):
                 # (copies, not views, of what the recorded bundle of the tree holds: a script may edit engine.tree in place)
                 feed_accountants(surfaces, so, prev['energy'][po], L['energy'].copy() if whole else L['energy'][order],
                                  L['vertices'].copy() if whole else L['vertices'][:, order], prev['directions'][:, po],
@@ -144,10 +164,16 @@ class PendingLevels(Delivery):
                 left = N.full(len(prev['energy']), ns) if prev_surf is None else prev_surf
                 if self.engine._transfer_host is None:
                     self.engine._transfer_host = N.zeros((ns + 1, ns))
-                if vol is None:
+                # (a segment is counted once: of the two rays a splitting hit sends on, the first stands for the segment that
+                # landed there -- added once per ray of this level, such a hit carried its energy twice)
+                once = None
+                if splits and len(par):
+                    once = N.zeros(len(par), dtype=bool)
+                    once[N.unique(par, return_index=True)[1]] = True
+                if vol is None and once is None:
                     N.add.at(self.engine._transfer_host, (left[par], L['surf']), prev['energy'][par])
                 else:               # (a volume event lands nowhere, and the ray goes on from where it had left)
-                    keep = ~vol
+                    keep = (once if vol is None else (~vol if once is None else (~vol & once)))
                     N.add.at(self.engine._transfer_host, (left[par][keep], L['surf'][keep]), prev['energy'][par][keep])
             prev_surf = L['surf'] if vol is None or not self.transfer else N.where(vol, (N.full(len(prev['energy']), self.n_surf) if prev_surf is None else prev_surf)[par], L['surf'])
             prev = dict(energy=L['energy'], directions=L['directions'], wavelengths=L.get('wavelengths') if has_wl else None,

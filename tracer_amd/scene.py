@@ -496,9 +496,10 @@ class DeviceScene(object):
                                mat=cols.get('mat'))
         return rays, None, n, None, 0, cols, None
 
-    def trace_fast(self, bundle, reps, min_energy, seed, accel=False, keep_last=False, stream=None, last_capacity=None):
+    def trace_fast(self, bundle, reps, min_energy, seed, accel=False, keep_last=False, stream=None, last_capacity=None, short_last_ok=False):
         """last_capacity: room for the rays still alive after `reps` interactions (keep_last); None = one per ray.  More rays
-        left than that is a TracerAmdError with status ERR_CAPACITY."""
+        left than that is a TracerAmdError with status ERR_CAPACITY -- or, with short_last_ok, the return value (stats, None):
+        stats.rays_left then says how many there were (a scene whose optics split rays can leave more rays than it was given)."""
         rays, src, n, src_seed, off, keep, spec = self._bundle_args(bundle)
         if src_seed is not None:
             seed = src_seed
@@ -508,13 +509,17 @@ class DeviceScene(object):
         last = None
         last_cols = None
         if keep_last:
-            m = n if last_capacity is None else max(1, min(int(last_capacity), n))
+            # (at most one ray left per ray given, unless the optics split rays)
+            m = n if last_capacity is None else max(1, int(last_capacity) if self.compiled.splits else min(int(last_capacity), n))
             last_cols = [N.empty(m) for _ in range(7)]
             last = _cabi.make_rays(m, *last_cols)
-        _cabi.check(self.lib.trc_trace_fast_x(self.handle, C.byref(rays) if rays is not None else None,
-                                              C.byref(src) if src is not None else None, C.byref(spec) if spec is not None else None,
-                                              n, int(reps), float(min_energy), int(seed), int(off), flags,
-                                              C.byref(last) if last is not None else None, C.byref(stats)))
+        status = self.lib.trc_trace_fast_x(self.handle, C.byref(rays) if rays is not None else None,
+                                           C.byref(src) if src is not None else None, C.byref(spec) if spec is not None else None,
+                                           n, int(reps), float(min_energy), int(seed), int(off), flags,
+                                           C.byref(last) if last is not None else None, C.byref(stats))
+        if status == _cabi.ERR_CAPACITY and short_last_ok and keep_last and stats.rays_left > m:
+            return stats, None
+        _cabi.check(status)
         if keep_last:
             m = last.n
             last_cols = [c[:m] for c in last_cols]

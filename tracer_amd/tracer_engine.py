@@ -209,6 +209,7 @@ class TracerEngine(object):
     TUNE_MIN_RAYS = 1 << 21  # calls from which the two forms of the fast engine are compared on a scene (fast_kernel='auto')
     TUNE_MAX_SURFACES = 512  # ... and the scene size up to which the megakernel is worth a try
     SLOW_STREAM = 1.5e6      # segments per ms of kernel time below which the streaming form counts as slow
+    SPLIT_ON_FAST = True     # engine='auto' sends scenes whose optics split rays to the fast engine (tree=False): measured, DESIGN.md 14.11
     HITS_RESIDENT_MAX = 1 << 30     # entries up to which unread hits of successive calls are kept in the device's buffer (68 B each)
     LEVELS_RESIDENT_MAX = 16 << 30  # bytes of unread ray-tree levels of earlier calls that may stay on the device
 
@@ -260,7 +261,12 @@ class TracerEngine(object):
             carries = dev.compiled.carries or (not _pending(bundle) and (bundle.is_polychromatic() or bundle.has_complex_index()))
             if carries:
                 carries = _pending(bundle) or bundle.get_num_rays() < 64
-            engine = 'ordered' if (tree or dev.compiled.splits or carries) else 'fast'
+            # Optics that send two rays on from a hit (single_ray=False) are traced by the streaming form too (k_s_shade_x<.., SPLIT>,
+            # DESIGN.md section 14.11): 64 rays or more, no source spectrum.  The ray tree, smaller calls and sources with a
+            # spectrum stay with the ordered engine.
+            splits = dev.compiled.splits and not (self.SPLIT_ON_FAST and bundle.get_num_rays() >= 64 and
+                                                  not (_pending(bundle) and bundle.source_spectrum() is not None))
+            engine = 'ordered' if (tree or splits or carries) else 'fast'
         if accel and Kd_Tree is None and (engine == 'fast' or (engine == 'ordered' and (dev.n_surf > self.KD_BUILD_MAX or (
                 dev.n_surf <= 65535 and bundle.get_num_rays() * dev.n_surf <= self.KD_WORTH_IT)))):
             # The fast engine does not walk the reference's Kd-tree: large calls search the library's own uniform grid over the same
@@ -312,6 +318,7 @@ class TracerEngine(object):
     def _trace_fast(self, dev, bundle, reps, min_energy, seed, accel, hit_capacity, fast_kernel='auto', feed=True, last_capacity=None):
         n = bundle.get_num_rays()
         capture = any(dev.compiled.capture)
+        split = bool(dev.compiled.splits)       # optics that send two rays on from a hit: the streaming form alone (k_s_shade_x<.., SPLIT>)
         accs = []
         pend = None
         if capture:
@@ -331,6 +338,8 @@ class TracerEngine(object):
             if keep and ((not _pending(bundle) and bundle.is_polychromatic()) or dev.hit_spectral_columns()):
                 keep = False        # (all hits in the buffer have the same spectral columns: hits waiting there with spectra, or
                                     # before a call that brings spectra, are delivered first)
+            if keep and split:
+                keep = False        # (a call whose hits do not fit is made again on an empty buffer: see below)
             used = 0
             if keep:
                 used = dev.hits_reserved()[0]
@@ -347,6 +356,8 @@ class TracerEngine(object):
                 dev.lib.trc_scene_clear_hits(dev.handle)
         t0 = time.time()
         stream = {'auto': None, 'stream': True, 'megakernel': False}[fast_kernel]
+        if stream is None and split:
+            stream = True       # (fast_kernel='megakernel' is refused by the library, which names trc_trace_ordered)
         if stream is None and accel and dev.n_surf > self.KD_BUILD_MAX:
             stream = True       # the streaming form has the grid for large scenes; the megakernel would test every box
         # Large calls go to the streaming form.  On a scene where it turns out slow -- every segment a hit on overlapping curved
@@ -363,7 +374,44 @@ class TracerEngine(object):
         # of host arrays per call for a result that is empty in most scenes.  More rays left than room is an error of the
         # call (status ERR_CAPACITY), raised after the trace: tallies and flux maps of the scene then hold it, the accountants do not.
         cap = last_capacity if last_capacity is not None else (n if n <= (1 << 24) else (1 << 22))
-        stats, last = dev.trace_fast(bundle, reps, min_energy, seed, accel=accel, keep_last=True, stream=stream, last_capacity=cap)
+        if split and last_capacity is None and n <= (1 << 24):
+            cap = 2 * n + 1024      # (two rays may leave a hit: room as for the hits; beyond it the call is made again, below)
+        over_capacity = 0
+        if not split:
+            stats, last = dev.trace_fast(bundle, reps, min_energy, seed, accel=accel, keep_last=True, stream=stream, last_capacity=cap)
+        else:
+            # A scene that splits rays can capture more hits than the default room of two per ray, and leave more rays than it was
+            # given; the ordered engine has neither limit, and nothing grows in the middle of a call.  So before a call that
+            # captures the packed tally buffer (tallies, flux maps, transfer matrix) is kept aside, and a call that dropped hits
+            # or had no room for its last rays is undone -- hit buffer emptied, tallies put back -- and made once more, with the
+            # same seed, with room for every hit it counted (captured or not: an upper bound; the library adds what the buffer's
+            # open chunks can leave unused) and every ray it left.  A scene that captures nothing pays for no snapshot: there
+            # only the last rays can lack room, the tallies of such a call are complete, and they are put back behind the
+            # second call.  Room the caller set (hit_capacity, last_capacity) is taken literally.
+            saved = dev.export_tallies() if capture else None
+            literal = capture and hit_capacity is not None
+            hits_before = dev.get_tallies()[2] if literal else None
+            stats, last = dev.trace_fast(bundle, reps, min_energy, seed, accel=accel, keep_last=True, stream=stream, last_capacity=cap,
+                                         short_last_ok=last_capacity is None)
+            if (stats.hits_dropped and capture and hit_capacity is None) or last is None:
+                if capture:
+                    if stats.hits_dropped and hit_capacity is None:
+                        dev.set_hit_capacity(int(stats.hits))
+                    dev.lib.trc_scene_clear_hits(dev.handle)
+                    dev.import_tallies(saved)
+                else:
+                    done = dev.export_tallies()
+                if last is None:
+                    cap = int(stats.rays_left)
+                stats, last = dev.trace_fast(bundle, reps, min_energy, seed, accel=accel, keep_last=True, stream=stream, last_capacity=cap)
+                if not capture:
+                    dev.import_tallies(done)
+            if literal and not stats.hits_dropped:
+                # The library leaves room beside a buffer for the unused ends of its chunks, which holds a small call's hits
+                # whatever capacity was asked for, and such a scene captures a multiple of its rays: the hits this call made
+                # on capturing surfaces (the hit tallies before and after) are held against the capacity here.
+                made = (dev.get_tallies()[2] - hits_before)[N.asarray(dev.compiled.capture, dtype=bool)].sum()
+                over_capacity = int(made) - int(hit_capacity)
         wall = time.time() - t0
         self._set_stats(stats, wall, 'fast')
         self.stats['form'] = 'stream' if stats.launches > 1 else 'megakernel'
@@ -372,7 +420,10 @@ class TracerEngine(object):
         if stats.hits_dropped:
             raise RuntimeError("%d hits were not captured: the hit buffer holds %d; pass hit_capacity=..."
                                % (stats.hits_dropped, dev.hit_capacity))
-        if capture and n > 0:
+        if over_capacity > 0:
+            dev.lib.trc_scene_clear_hits(dev.handle)
+            raise RuntimeError("%d hits were not captured: the hit buffer holds %d; pass hit_capacity=..." % (over_capacity, int(hit_capacity)))
+        if capture and n > 0 and not split:      # (a split call's room is found by the call itself)
             rate = max(dev.hits_reserved()[0] - used, 0) / float(n)
             dev.capture_rate = rate if dev.capture_rate is None else max(dev.capture_rate, rate)
         if capture and feed and accs:
