@@ -54,25 +54,31 @@ def _by_point(points):
     return N.lexsort((points[2], points[1], points[0]))
 
 
-def _check(ctx, c, o, given, stream, what, accel=True, kd=None, scene_knobs=None, warm_up=False, **knobs):
+def _check(ctx, c, o, given, stream, what, accel=True, kd=None, scene_knobs=None, warm_up=False, chart=None, reps=None, **knobs):
     """accel, kd: trace_fast's accel, a Kd-tree set on the scene; scene_knobs: knobs around the scene's creation (the library reads them
-    there); warm_up: the call is made twice on the scene -- tallies, hits and maps reset in between -- and checked the second time"""
+    there); warm_up: the call is made twice on the scene -- tallies, hits and maps reset in between -- and checked the second time;
+    chart: (surface, chart, u edges, v edges) of a second flux map, in another chart than XY, held to the host histogram of the oracle's
+    hits in that chart (fluxmap_chart_scene.host_maps; the case then has `frames`); reps: interactions, if not shade_cases.REPS"""
     from tracer_amd.scene import DeviceScene
+    reps = sc.REPS if reps is None else reps
     with env(**(scene_knobs or {})):
         dev = DeviceScene(c.cs, ctx)
     if kd is not None:
         dev.set_kdtree(kd)
     dev.set_fluxmap(c.map_surf, *c.edges[c.map_surf])
+    if chart is not None:
+        dev.set_fluxmap(chart[0], chart[2], chart[3], chart=chart[1])
     dev.set_hit_capacity(8 * sc.N_RAYS + 65536)
     with env(**knobs):
         if warm_up:
-            dev.trace_fast(c.bundle(given), sc.REPS, c.min_energy, sc.SEED, accel=accel, keep_last=True, stream=stream)
+            dev.trace_fast(c.bundle(given), reps, c.min_energy, sc.SEED, accel=accel, keep_last=True, stream=stream)
             dev.reset_tallies()
-        st, last = dev.trace_fast(c.bundle(given), sc.REPS, c.min_energy, sc.SEED, accel=accel, keep_last=True, stream=stream)
+        st, last = dev.trace_fast(c.bundle(given), reps, c.min_energy, sc.SEED, accel=accel, keep_last=True, stream=stream)
     a, r, h = dev.get_tallies()
     hits = dev.get_hits()
     nx = dev.hit_spectral_columns()
     fm = dev.get_fluxmap(c.map_surf)
+    fm_chart = dev.get_fluxmap(chart[0]) if chart is not None else None
     dev.close()
     assert st.hits_dropped == 0, what
     # tallies and statistics
@@ -118,6 +124,13 @@ def _check(ctx, c, o, given, stream, what, accel=True, kd=None, scene_knobs=None
     assert fm.shape == Hm.shape and n_hits == h[c.map_surf]
     assert N.allclose(fm, Hm, rtol=1e-9, atol=tol), (what, N.abs(fm - Hm).max(), Hm.max())
     assert N.isclose(a[c.map_surf] - fm.sum(), e_out, rtol=1e-9, atol=tol), (what, a[c.map_surf] - fm.sum(), e_out)
+    if chart is not None:           # the map in another chart, at the same tolerances
+        import fluxmap_chart_scene as fc
+        Hc, e_out, n_out, n_hits, n_edge = fc.host_maps(o['hit_list'], c.frames, {chart[0]: (chart[1], False, chart[2], chart[3])})[chart[0]]
+        tol = 1e-9 * Hc.max()
+        assert fm_chart.shape == Hc.shape and n_hits == h[chart[0]] and n_edge == 0 and Hc.max() > 0., what
+        assert N.allclose(fm_chart, Hc, rtol=1e-9, atol=tol), (what, N.abs(fm_chart - Hc).max(), Hc.max())
+        assert N.isclose(a[chart[0]] - fm_chart.sum(), e_out, rtol=1e-9, atol=tol), (what, a[chart[0]] - fm_chart.sum(), e_out)
 
 
 def _ids(name):
