@@ -58,7 +58,14 @@ $(LIB): $(OBJS)
 	mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared -o $@ $(OBJS)
 
-hostcheck: $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK)
+MATCHECK := $(ROOT)tests/hostcheck/libtrc_material_check.so
+MATCHECK_SRC := $(ROOT)tests/hostcheck/material_check.cpp
+
+hostcheck: $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK)
+
+# the tabulated materials' lookup of the per-ray core, host-compiled for its tests
+$(MATCHECK): $(MATCHECK_SRC) $(HDR)
+	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(MATCHECK_SRC)
 
 $(HOSTCHECK): $(HOSTCHECK_SRC) $(HDR)
 	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(HOSTCHECK_SRC)
@@ -110,6 +117,6 @@ asm-shade: $(CSRC)/trc_shade.hip $(HDR)
 		-o $(ROOT)build/trc_shade.s $(CSRC)/trc_shade.hip 2> $(ROOT)build/trc_shade.resources.txt
 
 clean:
-	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK)
+	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK)
 
 .PHONY: all hostcheck umaskcheck umaskcheck-exe splitcheck asm asm-shade clean

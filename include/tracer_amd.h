@@ -110,8 +110,9 @@ typedef enum trc_optics_kind {
                                            (Absorbant.attenuate :874-889 with k = Im m, optics.py:205-212).  Rays carry a complex index
                                            (trc_rays.ref_index_im), a wavelength, and the materials' indices at it (trc_rays.mat).
                                            opt: single_ray, sigma(<0:none), attenuate(0|1), scaling, k0, k1 (rows of trc_rays.mat of
-                                           material_1, material_2).  Ordered engine, per-surface protocol and (one ray per hit) the
-                                           streaming form of the fast engine. */
+                                           material_1, material_2).  Ordered engine, per-surface protocol and the streaming form of
+                                           the fast engine.  k0, k1 are also the materials' numbers in trc_scene_set_materials:
+                                           with tables there, the engines evaluate m(lambda) per ray and no trc_rays.mat is needed. */
     TRC_OPT_LAMBERTIAN_POLYCHROMATIC = 15, /* Lambertian_directional_axisymmetric_piecewise_Polychromatic :393-425: every ray carries a
                                            spectrum (trc_rays.spectra over trc_rays.spec_wl); each sample is scaled by 1 - absorptance(theta_in,
                                            lambda_w), the ray energy is the trapezoid integral of the result.  extra as
@@ -171,7 +172,8 @@ typedef struct trc_rays {
     double *spectra;            /* n_spec x n: spectral power, same layout; its trapezoid integral over spec_wl is the ray energy */
     int64_t n_mat;              /* TRC_OPT_REFRACTIVE_MATERIAL: number of materials, and                                          */
     double *mat;                /* 2 n_mat x n: Re m_k(lambda_i) at mat[2k * n + i], Im at mat[(2k + 1) * n + i] -- material k's own
-                                   m() evaluated by the caller at the wavelength of ray i (children inherit the wavelength)     */
+                                   m() evaluated by the caller at the wavelength of ray i (children inherit the wavelength).
+                                   NULL on a scene with trc_scene_set_materials tables: evaluated on the device instead      */
 } trc_rays;
 
 /* ---- sources (reference: tracer/sources.py) -------------------------------- */
@@ -370,6 +372,16 @@ int trc_scene_get_hits(trc_scene *scene, int64_t *n, int32_t *surf, double *e_ab
 int trc_scene_get_hits_x(trc_scene *scene, int64_t *n, int32_t *surf, double *e_abs, double *e_in, double *px, double *py,
                          double *pz, double *dx, double *dy, double *dz, int32_t n_x, double *x);
 int trc_scene_hit_spectral_columns(trc_scene *scene, int32_t *n_x);
+/* The tabulated materials of the scene's TRC_OPT_REFRACTIVE_MATERIAL optics on the device: material k (the row numbers k0, k1 of
+   those optics) has n_points[k] points, 2..4096, and packed holds wl[n] | re[n] | im[n] of material 0, then of material 1, ...:
+   wavelengths strictly increasing, every value finite, at most 64 materials (anything else: TRC_ERR_INVALID).  Replaces the tables
+   set before; n_mat = 0 removes them.  Between the points m(lambda) is linear in Re and Im, outside them the end values, with
+   the bits numpy.interp gives.  While the scene has a table for every material its optics name, a trace call whose bundle brings
+   no trc_rays.mat evaluates the materials per ray on the device (see trc_trace_fast); a bundle that brings mat is traced by its
+   rows as before.  trc_scene_eval_materials: those values for n wavelengths, laid out like trc_rays.mat
+   (out[2k * n + i], out[(2k + 1) * n + i] = Re, Im of m_k(wl[i])); host arrays. */
+int trc_scene_set_materials(trc_scene *scene, int32_t n_mat, const int32_t *n_points, const double *packed);
+int trc_scene_eval_materials(trc_scene *scene, int64_t n, const double *wl, double *out /* 2 n_mat x n */);
 /* View-factor allocation (emissive_losses/view_factors_3D.py:239-356 and :598-674, `alloc_VF`): the absorbed energy of
    the captured hits collected per element on the device instead of fetching every hit and looping over the elements on
    the host.  Element j takes the hits of the surfaces surf_lo[j]..surf_hi[j] whose global azimuth atan2(y,x) (brought
@@ -428,12 +440,17 @@ int trc_kdtree_traversal(trc_ctx *ctx, const trc_kdtree_desc *kd, int32_t n_surf
  * can leave more than n rays (`last`) and capture more than n hits per bounce: more rays left than `last` holds is
  * TRC_ERR_CAPACITY with stats->rays_left set, hits beyond the buffer are counted in stats->hits_dropped, as ever.  Its ray table
  * never recycles a slot and grows between bounces (TRC_ERR_NOMEM when it cannot; TRC_ERR_CAPACITY beyond 2^32 slots).
+ * Tabulated materials on the device (trc_scene_set_materials, a table for every material the optics name, no flux map in a chart
+ * other than XY): a given bundle then needs `wavelength` only, not `mat`; and a source descriptor lights such a scene when it has
+ * a spectrum (trc_trace_fast_x), ray-splitting optics included -- each ray draws its wavelength at its first hit and starts in the
+ * spectrum's ref_index.  A descriptor without a spectrum is TRC_ERR_INVALID there.  The same holds for trc_trace_ordered(_x).
  */
 int trc_trace_fast(trc_scene *scene, const trc_rays *in, const trc_source_desc *src, int64_t n,
                    int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset,
                    int32_t flags, trc_rays *last, trc_trace_stats *stats);
 /* The same with the spectrum of `src` (NULL: trc_trace_fast).  A spectrum with a given bundle `in` is TRC_ERR_INVALID; a spectrum
-   on a scene whose optics send two rays on from a hit is TRC_ERR_UNSUPPORTED (use trc_trace_ordered_x). */
+   on a scene whose optics send two rays on from a hit is TRC_ERR_UNSUPPORTED (use trc_trace_ordered_x) unless the scene's
+   tabulated materials are on the device (above). */
 int trc_trace_fast_x(trc_scene *scene, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
                      int64_t n, int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset,
                      int32_t flags, trc_rays *last, trc_trace_stats *stats);

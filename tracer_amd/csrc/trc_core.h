@@ -1128,6 +1128,57 @@ TRC_HD double trc_interp_xy(const double *xs, const double *ys, int n, double x)
     return slope * (x - xs[lo]) + ys[lo];
 }
 
+// The scene's tabulated materials (Refractive / RefractiveAbsorbant) evaluated per ray: m(lambda) of material k from a packed table
+//   tab[0] = n_mat, tab[1 + 2k] = where material k starts (in doubles from tab), tab[2 + 2k] = its points n; there: n | wl[n] | re[n] | im[n]
+// with 2 <= n <= TRC_MATERIAL_MAX_POINTS finite points, wl strictly increasing (checked where the table is made).  The result has
+// the bits numpy.interp gives (compiled_base.c, arr_interp, the form without precomputed slopes and the one with them round
+// alike): the optics compare a ray's index with material_1's for equality (trc_shade_material), and the index a host-made bundle
+// brings is TabulatedMaterial.m() of its wavelengths.  NaN in, NaN out; the end values outside the table; the node's value on a
+// node; inside, slope * (x - xp[j]) + fp[j] in that order, each operation rounded on its own (the build does not contract).
+// k outside the table's materials: NaN.
+// The interval is found by binary search over the whole table, 12 steps at 4096 points, before anything else is looked at: the
+// ends need no loads of their own (below the first node the search ends on interval 0 with x <= xp[0], at or above the last on
+// interval n-2 with x >= xp[n-1]; a NaN compares false everywhere and ends on interval 0), so a lookup is a chain of
+// 1 + steps + 1 dependent loads.  trc_material_index2 walks two materials' tables in one loop, for the two sides of a surface.
+#define TRC_MATERIAL_MAX_POINTS 4096
+#define TRC_MATERIAL_MAX 64
+struct trc_material_cursor { const double *xp; int n, lo, hi; };    // xp[lo] <= x < xp[hi] while x is inside the table
+TRC_HD trc_material_cursor trc_material_open(const double *tab, int k) {
+    trc_material_cursor c;
+    c.xp = tab; c.n = 0; c.lo = c.hi = 0;
+    if (k >= 0 && k < (int)tab[0]) { c.xp = tab + (long long)tab[1 + 2 * k] + 1; c.n = (int)tab[2 + 2 * k]; c.hi = c.n - 1; }
+    return c;
+}
+TRC_HD void trc_material_step(trc_material_cursor &c, double x) {
+    if (c.hi - c.lo > 1) {
+        const int mid = (c.lo + c.hi) >> 1;
+        if (c.xp[mid] <= x) c.lo = mid; else c.hi = mid;
+    }
+}
+TRC_HD void trc_material_close(const trc_material_cursor &c, double x, double *re, double *im) {
+    if (c.n == 0) { *re = NAN; *im = NAN; return; }
+    if (x != x) { *re = x; *im = x; return; }
+    const double *fr = c.xp + c.n, *fi = fr + c.n;
+    const int j = c.lo;
+    const double x0 = c.xp[j], x1 = c.xp[j + 1];
+    if (x <= x0) { *re = fr[j]; *im = fi[j]; return; }              // on node j, or below the table (j = 0)
+    if (x >= x1) { *re = fr[j + 1]; *im = fi[j + 1]; return; }      // the last node, or above the table (j = n - 2)
+    const double h = x1 - x0, d = x - x0;
+    *re = ((fr[j + 1] - fr[j]) / h) * d + fr[j];
+    *im = ((fi[j + 1] - fi[j]) / h) * d + fi[j];
+}
+TRC_HD void trc_material_index(const double *tab, int k, double wl, double *re, double *im) {
+    trc_material_cursor c = trc_material_open(tab, k);
+    while (c.hi - c.lo > 1) trc_material_step(c, wl);
+    trc_material_close(c, wl, re, im);
+}
+TRC_HD void trc_material_index2(const double *tab, int k0, int k1, double wl, double *re0, double *im0, double *re1, double *im1) {
+    trc_material_cursor a = trc_material_open(tab, k0), b = trc_material_open(tab, k1);
+    while (a.hi - a.lo > 1 || b.hi - b.lo > 1) { trc_material_step(a, wl); trc_material_step(b, wl); }
+    trc_material_close(a, wl, re0, im0);
+    trc_material_close(b, wl, re1, im1);
+}
+
 // RegularGridInterpolator (linear) on a (theta, lambda) grid, arguments clamped to the grid
 // tab: n_theta, n_lambda, theta[n_theta], lambda[n_lambda], value[n_theta][n_lambda]
 TRC_HD int trc_grid_cell(const double *xs, int n, double x, double *w) {
@@ -1627,6 +1678,26 @@ TRC_HD int trc_shade_x(int opt_kind, const double *opt, const double *extra, int
     }
     return trc_shade(opt_kind, opt, extra, extra_off, extra_len, ux, uy, uz, dx, dy, dz, e, ref, wl, path, nx, ny, nz, seed, rid,
                      event, out);
+}
+
+// trc_shade_x on a scene whose materials' tables are on the device (trc_scene_set_materials): a surface between tabulated materials
+// takes both indices from `mat_tab` at the ray's wavelength (trc_material_index2) and reads no rows of X.mat.  Both lookups stand
+// in front of the optics' own branches (which medium the ray is in, refracted or not, one ray or two), so the lanes of a wave,
+// which hit different materials at different wavelengths, walk their tables together.
+TRC_HD int trc_shade_xt(int opt_kind, const double *opt, const double *extra, int extra_off, int extra_len,
+                        double ux, double uy, double uz, double dx, double dy, double dz, double e, double ref,
+                        double wl, double path, double nx, double ny, double nz, uint64_t seed, uint64_t rid,
+                        uint32_t event, const trc_ray_ext &X, const double *mat_tab, trc_ray_out out[2], double out_im[2], double *poly_th) {
+    if (opt_kind == TRC_OPT_REFRACTIVE_MATERIAL) {
+        *poly_th = -1.0;
+        out_im[0] = out_im[1] = X.ref_im;
+        out[0].blk = 0; out[1].blk = 1; out[0].back = out[1].back = 0.0; out[0].sf = out[1].sf = 1.0; out[0].shift = out[1].shift = 0.0;
+        trc_cplx m0, m1;
+        trc_material_index2(mat_tab, (int)opt[4], (int)opt[5], wl, &m0.re, &m0.im, &m1.re, &m1.im);
+        return trc_shade_material(opt, m0, m1, dx, dy, dz, e, ref, X.ref_im, wl, path, nx, ny, nz, seed, rid, event, out, out_im);
+    }
+    return trc_shade_x(opt_kind, opt, extra, extra_off, extra_len, ux, uy, uz, dx, dy, dz, e, ref, wl, path, nx, ny, nz, seed, rid,
+                       event, X, out, out_im, poly_th);
 }
 
 // ---------------------------------------------------------------------------------------------

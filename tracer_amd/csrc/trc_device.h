@@ -320,6 +320,9 @@ struct CarryIn {
     // is no function of SRayGeo.idx once a hit has sent two rays on (trc_child_rid); null for every other call.  Last, for the
     // reason given above.
     unsigned long long *slot_rid;
+    // the scene's tabulated materials (trc_material_index's packed table, trc_scene_set_materials) for a call that brings no rows
+    // of them: read by the MAT instances of k_s_shade_x alone, null for every other call.  The very last word, for the same reason.
+    const double *mat_tab;
 };
 
 struct FastParams {
@@ -684,7 +687,7 @@ __device__ __forceinline__ void tally_by_wave(double *tl, int Sn, int ts, double
 
 // the lean shading kernels (trc_shade.hip): kernel of a class for a scene of flat surfaces only (flat) with its tables in LDS (lds)
 // chart: the instance that knows every flux-map chart (record_hit<.., CHART>) -- of the lean kernels the ones for any geometry only
-const void *trc_shade_carry_kernel(bool lds, bool chart = false, bool split = false);      // k_s_shade_x (trc_shade.hip): every optics kind, with what the rays carry;
+const void *trc_shade_carry_kernel(bool lds, bool chart = false, bool split = false, bool mat = false);      // k_s_shade_x (trc_shade.hip): every optics kind, with what the rays carry;
                                                                                             // split: its form for scenes whose optics send two rays on from a hit
 const void *trc_shade_lean_kernel(int cls, bool flat, bool lds, bool spec = false, bool chart = false);
 #ifndef SHC_THREADS

@@ -452,6 +452,11 @@ struct trc_scene {
     std::vector<double> extra_h;
     bool splits;  // some optics can emit two rays per hit
     CarryNeeds needs;   // needs.any(): some optics read what only rays of a given bundle carry (complex indices, spectra)
+    // the tabulated materials of the scene's optics on the device (trc_scene_set_materials; trc_material_index's packed table, in
+    // global memory: part of no LDS image), mat_tab_n of them (0: none).  A call that brings no trc_rays.mat reads them.
+    DevBuf<double> d_mat_tab;
+    int32_t mat_tab_n = 0;
+    bool mat_tab_serves() const { return needs.max_mat >= 0 && mat_tab_n > needs.max_mat; }
     // device buffers
     DevBuf<double> d_recs, d_opt, d_extra;
     DevBuf<int32_t> d_sflags;
@@ -1192,6 +1197,7 @@ struct OrdParams {
     long long pay_stride;
     double *opay;           // the children's, rows 2n apart
     PayLayout lay;
+    const double *mat_tab;  // the scene's tabulated materials (trc_material_index's table): read by the MAT instances alone; last
 };
 
 // pending far children of the single-precision Kd walk (trc_nearest_accel32), in LDS: entry sp of thread t at [sp * 256 + t].
@@ -1213,7 +1219,9 @@ struct LdsStack32 {
 // with its stack in LDS; otherwise the float64 walk of the caller's tree / brute force, with a stack in private memory.
 // MODE 2: the scene stands on the large grid (a mesh): trc_nearest_grid32.
 // CHART: the flux maps may bin in the charts other than XY (trc_fluxmap_uv)
-template <int MODE, bool CHART = false>
+// MAT: the scene's tabulated materials are on the device (P.mat_tab) and the rays bring no rows of them (P.lay.n_mat == 0): a hit
+//      between materials evaluates both at the ray's wavelength (trc_shade_xt)
+template <int MODE, bool CHART = false, bool MAT = false>
 __global__ __launch_bounds__(256) void k_ord_bounce(OrdParams P) {
     constexpr bool FAST = MODE == 1;
     __shared__ uint32_t s_na[FAST ? ORD_STACK_DEPTH * 256 : 1];
@@ -1263,7 +1271,13 @@ __global__ __launch_bounds__(256) void k_ord_bounce(OrdParams P) {
             X.spec = P.pay + (size_t)P.lay.r_spec() * P.pay_stride + i;
         }
         double out_im[2], poly_th;
-        int n_out = trc_shade_x(trc_rec_opt_kind(rec), sc.opt + (size_t)s * 8, sc.extra, trc_rec_extra_off(rec),
+        int n_out;
+        if constexpr (MAT)
+            n_out = trc_shade_xt(trc_rec_opt_kind(rec), sc.opt + (size_t)s * 8, sc.extra, trc_rec_extra_off(rec),
+                                 trc_rec_extra_len(rec), rec[2], rec[5], rec[8], dx, dy, dz, e, ref, wl, path, nx, ny,
+                                 nz, P.seed, rid, (uint32_t)P.event, X, P.mat_tab, out, out_im, &poly_th);
+        else
+            n_out = trc_shade_x(trc_rec_opt_kind(rec), sc.opt + (size_t)s * 8, sc.extra, trc_rec_extra_off(rec),
                                 trc_rec_extra_len(rec), rec[2], rec[5], rec[8], dx, dy, dz, e, ref, wl, path, nx, ny,
                                 nz, P.seed, rid, (uint32_t)P.event, X, out, out_im, &poly_th);
         double e_out = out[0].e + (n_out > 1 ? out[1].e : 0.0);
@@ -2201,6 +2215,68 @@ extern "C" int trc_scene_hit_spectral_columns(trc_scene *sc, int32_t *n_x) {
     return TRC_OK;
 }
 
+// ---- the scene's tabulated materials on the device ----------------------------------------------------------------------------
+// m_k(wl[i]) of every material of the table: Re at out[2k * n + i], Im at out[(2k + 1) * n + i] (the layout of trc_rays.mat)
+__global__ __launch_bounds__(256) void k_material_eval(const double *tab, int n_mat, const double *wl, long long n, double *out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double x = wl[i];
+    for (int k = 0; k < n_mat; ++k) {
+        double re, im;
+        trc_material_index(tab, k, x, &re, &im);
+        out[(long long)(2 * k) * n + i] = re;
+        out[(long long)(2 * k + 1) * n + i] = im;
+    }
+}
+
+extern "C" int trc_scene_set_materials(trc_scene *sc, int32_t n_mat, const int32_t *n_points, const double *packed) {
+    if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
+    if (n_mat < 0 || n_mat > TRC_MATERIAL_MAX) return trc_fail(TRC_ERR_INVALID, "trc_scene_set_materials: between 0 and %d materials", TRC_MATERIAL_MAX);
+    HIP_TRY(hipSetDevice(sc->ctx->device));
+    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
+    if (n_mat == 0) { sc->mat_tab_n = 0; sc->d_mat_tab.reset(); return TRC_OK; }
+    if (!n_points || !packed) return trc_fail(TRC_ERR_INVALID, "trc_scene_set_materials: n_points and packed are required");
+    // the caller's wl[n] | re[n] | im[n] per material, one after the other -> trc_material_index's table
+    std::vector<double> tab((size_t)1 + 2 * n_mat);
+    tab[0] = (double)n_mat;
+    const double *p = packed;
+    for (int k = 0; k < n_mat; ++k) {
+        const int n = n_points[k];
+        if (n < 2 || n > TRC_MATERIAL_MAX_POINTS) return trc_fail(TRC_ERR_INVALID, "material %d: a table has 2 to %d points (%d given)", k, TRC_MATERIAL_MAX_POINTS, n);
+        for (int j = 0; j < 3 * n; ++j)
+            if (!std::isfinite(p[j])) return trc_fail(TRC_ERR_INVALID, "material %d: the table holds a value that is not finite", k);
+        for (int j = 1; j < n; ++j)
+            if (!(p[j] > p[j - 1])) return trc_fail(TRC_ERR_INVALID, "material %d: wavelengths must increase strictly", k);
+        tab[1 + 2 * k] = (double)tab.size();
+        tab[2 + 2 * k] = (double)n;
+        tab.push_back((double)n);
+        tab.insert(tab.end(), p, p + 3 * n);
+        p += 3 * n;
+    }
+    sc->mat_tab_n = 0;
+    TRC_TRY(sc->d_mat_tab.alloc(tab.size()));
+    HIP_TRY(hipMemcpy(sc->d_mat_tab.get(), tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    sc->mat_tab_n = n_mat;
+    return TRC_OK;
+}
+
+extern "C" int trc_scene_eval_materials(trc_scene *sc, int64_t n, const double *wl, double *out) {
+    if (!sc || n < 0 || (n > 0 && (!wl || !out))) return trc_fail(TRC_ERR_INVALID, "trc_scene_eval_materials: bad arguments");
+    if (sc->mat_tab_n <= 0) return trc_fail(TRC_ERR_INVALID, "trc_scene_eval_materials: the scene has no material tables (trc_scene_set_materials)");
+    if (n == 0) return TRC_OK;
+    HIP_TRY(hipSetDevice(sc->ctx->device));
+    DevBuf<double> d_wl, d_out;
+    TRC_TRY(d_wl.alloc((size_t)n));
+    TRC_TRY(d_out.alloc((size_t)n * 2 * (size_t)sc->mat_tab_n));
+    HIP_TRY(hipMemcpy(d_wl.get(), wl, (size_t)n * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_material_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sc->ctx->stream, (const double *)sc->d_mat_tab.get(),
+                       (int)sc->mat_tab_n, (const double *)d_wl.get(), (long long)n, d_out.get());
+    const hipError_t se = hipStreamSynchronize(sc->ctx->stream);
+    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_material_eval failed: %s", hipGetErrorString(se));
+    HIP_TRY(hipMemcpy(out, d_out.get(), (size_t)n * 2 * (size_t)sc->mat_tab_n * 8, hipMemcpyDeviceToHost));
+    return TRC_OK;
+}
+
 #define BIN_TILE 256
 __global__ __launch_bounds__(256) void k_bin_hits(long long n_hits, const int32_t *h_surf, const double *h_e, const double *hx,
                                                   const double *hy, const double *hz, int n_bins, const int32_t *surf_lo,
@@ -2723,13 +2799,28 @@ static int scene_stage_source(trc_scene *sc, const trc_source_desc *src, const t
     return TRC_OK;
 }
 
-// What the bundle `in` (NULL: a source descriptor, whose rays carry nothing) brings beyond the nine columns, against what the
-// scene's optics read: lay->n_mat and lay->W.  has_im is the ordered engine's to set.
-static int check_carried(const CarryNeeds &needs, const trc_rays *in, const char *who, PayLayout *lay) {
+// The scene's tabulated materials are evaluated on the device for this call: it has a table for every material its optics name
+// (trc_scene_set_materials), the bundle brings no rows of its own (trc_rays.mat: those are traced as they are), and no flux map
+// bins in a chart other than XY (there is no CHART x MAT kernel instance)
+static bool scene_mat_route(const trc_scene *sc, const trc_rays *in) {
+    return sc->mat_tab_serves() && !(in && in->mat) && !scene_has_chart_map(sc);
+}
+
+// What the bundle `in` (NULL: a source descriptor, whose rays carry nothing but what its spectrum gives them: has_spec) brings
+// beyond the nine columns, against what the scene's optics read: lay->n_mat and lay->W.  has_im is the ordered engine's to set.
+// *mat_dev: scene_mat_route -- the materials' indices come from the scene's tables, lay->n_mat is 0.
+static int check_carried(const trc_scene *sc, const trc_rays *in, bool has_spec, const char *who, PayLayout *lay, bool *mat_dev) {
+    const CarryNeeds &needs = sc->needs;
     lay->n_mat = (in && in->mat) ? (int)in->n_mat : 0;
     lay->W = (in && in->spectra && in->spec_wl) ? in->n_spec : 0;
+    *mat_dev = scene_mat_route(sc, in);
     if (lay->W < 0 || lay->W > 4096 || lay->n_mat < 0 || lay->n_mat > 64) return trc_fail(TRC_ERR_INVALID, "%s: n_spec or n_mat out of range", who);
-    if (needs.max_mat >= 0 && (!in || !in->wavelength || lay->n_mat <= needs.max_mat))
+    if (needs.max_mat >= 0 && *mat_dev) {
+        if (in && !in->wavelength)
+            return trc_fail(TRC_ERR_INVALID, "%s: the scene refracts between tabulated materials: the bundle needs wavelengths", who);
+        if (!in && !has_spec)       // (rays of wavelength 0 would index nothing sensible)
+            return trc_fail(TRC_ERR_INVALID, "%s: the scene refracts between tabulated materials: a source descriptor needs a source spectrum, which gives its rays their wavelengths", who);
+    } else if (needs.max_mat >= 0 && (!in || !in->wavelength || lay->n_mat <= needs.max_mat))
         return trc_fail(TRC_ERR_INVALID, "%s: the scene refracts between tabulated materials: the bundle needs wavelengths and the %d materials' indices at them (trc_rays.mat)",
                         who, needs.max_mat + 1);
     if (needs.poly && lay->W < 2)
@@ -2767,6 +2858,7 @@ struct FastCall {
     trc_source_desc src_res;
     StreamKnobs knobs;
     bool carry;
+    bool mat_dev;       // the materials' indices come from the scene's tables (scene_mat_route)
     PayLayout lay;
     // fast_stage_inputs: the bundle and its carried columns (the caller's own when they are on the device, else copies held
     // here), or the source descriptor and its spectrum
@@ -2796,16 +2888,17 @@ static int fast_check_args(FastCall &C) {
     if (C.n < 0 || C.reps < 0) return trc_fail(TRC_ERR_INVALID, "n and reps must be >= 0");
     TRC_TRY(source_resolve(sc->ctx, C.src, C.src_res, "trc_trace_fast"));
     // Optics that send two rays on from a hit are traced by the streaming form alone (k_s_shade_x<.., SPLIT>), as rays that carry
-    // more are: not by the megakernel, not in calls too small for that form, and not under a source with a spectrum (k_s_shade_x
-    // has no instance that draws wavelengths).
-    if (sc->splits && ((C.flags & TRC_TRACE_MEGAKERNEL) || C.n < 64 || C.spec->desc))
+    // more are: not by the megakernel, not in calls too small for that form, and not under a source with a spectrum -- unless the
+    // scene's materials are on the device: the MAT instances of k_s_shade_x are the ones that draw wavelengths.
+    const bool mat_dev = scene_mat_route(sc, C.in);
+    if (sc->splits && ((C.flags & TRC_TRACE_MEGAKERNEL) || C.n < 64 || (C.spec->desc && !mat_dev)))
         return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has ray-splitting optics, which the fast engine traces in its streaming form only (64 rays or more, no source spectrum): use trc_trace_ordered");
     C.knobs = stream_knobs();
     // Rays that carry the imaginary part of a complex index, materials evaluated at their wavelength or a sampled spectrum are
     // traced by the streaming form (k_s_shade_x); the megakernel knows nothing of them.
     C.carry = sc->needs.any() || (C.in && (C.in->ref_index_im || C.in->spectra || C.in->mat));
-    if (C.carry && !C.in) return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has optics that read what only the rays of a given bundle carry (materials, spectra)");
-    TRC_TRY(check_carried(sc->needs, C.in, "trc_trace_fast", &C.lay));
+    if (C.carry && !C.in && !mat_dev) return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has optics that read what only the rays of a given bundle carry (materials, spectra)");
+    TRC_TRY(check_carried(sc, C.in, C.spec->desc != nullptr, "trc_trace_fast", &C.lay, &C.mat_dev));
     if (C.carry && ((C.flags & TRC_TRACE_MEGAKERNEL) || C.n < 64))
         return trc_fail(TRC_ERR_UNSUPPORTED, "complex refractive indices and spectra travel with the streaming form of the fast engine (64 rays or more) and with trc_trace_ordered");
     return TRC_OK;
@@ -2916,6 +3009,7 @@ static void fast_params(const FastCall &C, const MegaPlan &M, FastParams *P, Car
     carry_in->hit_x = C.hit_x; carry_in->hit_x_cap = C.hit_x ? C.sc->hits.cap : 0;
     carry_in->ref_im = C.carry_d[0]; carry_in->mat = C.carry_d[1]; carry_in->spec_wl = C.carry_d[2]; carry_in->spec = C.carry_d[3];
     carry_in->n_mat = C.lay.n_mat; carry_in->n_spec = C.lay.W;
+    carry_in->mat_tab = C.mat_dev ? C.sc->d_mat_tab.get() : nullptr;
 }
 
 // Large calls run the streaming engine (phases as separate kernels connected by HBM queues, trc_stream.inc); small ones the
@@ -3079,6 +3173,7 @@ struct OrdCall {
     trc_scene *sc; trc_result *res; PayLayout lay; int32_t flags; double min_energy; uint64_t seed;
     trc_trace_stats s;
     float total_ms;
+    const double *mat_tab;      // the scene's material tables when the rays bring no rows of them (scene_mat_route), else null
 };
 
 static void fill_f64(hipStream_t stream, long long grid, double *col, int64_t n, double v) {
@@ -3102,6 +3197,8 @@ static int ordered_level0(OrdCall &C, const trc_rays *in, const trc_source_desc 
         if (spec.desc) {     // level 0 carries the wavelengths the source's spectrum gives its rays, and their index
             TRC_TRY(spectrum_fill(ctx, spec.desc, spec.tab, n, C.seed, ray_offset, B0.wl, B0.ref));
         } else { fill_f64(ctx->stream, g0, B0.ref, n, 1.0); fill_f64(ctx->stream, g0, B0.wl, n, 0.0); }
+        // (a scene between materials whose tables are on the device: the source's rays start with a real index)
+        if (lay.has_im && n > 0 && hipMemsetAsync(B0.pay, 0, (size_t)n * 8, ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "level 0 setup failed");
     } else {
         TRC_TRY(check_rays(in, n, "trc_trace_ordered"));
         if (!in->e) return trc_fail(TRC_ERR_INVALID, "ray energies are required");
@@ -3158,11 +3255,13 @@ static int ordered_bounce(OrdCall &C, int it, int64_t n_cur, int64_t *m, int64_t
     P.ox = sx.o[0].get(); P.oy = sx.o[1].get(); P.oz = sx.o[2].get(); P.odx = sx.o[3].get(); P.ody = sx.o[4].get(); P.odz = sx.o[5].get();
     P.oe = sx.o[6].get(); P.oref = sx.o[7].get(); P.owl = sx.o[8].get(); P.orid = sx.orid.get(); P.key = sx.key.get();
     P.pay = cur.pay; P.pay_stride = cur.n_total; P.opay = sx.opay.get(); P.lay = C.lay;
+    P.mat_tab = C.mat_tab;
 
     (void)hipEventRecord(ctx->ev0, ctx->stream);
     const int mode = ordered_search_mode(sc, C.flags);
     void (*kern)(OrdParams) = mode == 2 ? k_ord_bounce<2> : (mode == 1 ? k_ord_bounce<1> : k_ord_bounce<0>);
     if (scene_has_chart_map(sc)) kern = mode == 2 ? k_ord_bounce<2, true> : (mode == 1 ? k_ord_bounce<1, true> : k_ord_bounce<0, true>);
+    else if (C.mat_tab) kern = mode == 2 ? k_ord_bounce<2, false, true> : (mode == 1 ? k_ord_bounce<1, false, true> : k_ord_bounce<0, false, true>);
     hipLaunchKernelGGL(kern, dim3((unsigned)((n_cur + 255) / 256)), dim3(256), 0, ctx->stream, P);
     hipLaunchKernelGGL(k_compact_count, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, sx.key.get(), (long long)slots,
                        sx.blk_cnt.get(), sx.blk_cul.get());
@@ -3254,7 +3353,8 @@ static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_sourc
     // what the rays carry beyond the nine columns (complex indices, material rows, spectra); rays between materials carry Im of the
     // index whether the bundle brought it or not
     PayLayout lay;
-    TRC_TRY(check_carried(sc->needs, in, "trc_trace_ordered", &lay));
+    bool mat_dev = false;
+    TRC_TRY(check_carried(sc, in, spec.desc != nullptr, "trc_trace_ordered", &lay, &mat_dev));
     lay.has_im = ((in && in->ref_index_im) || sc->needs.max_mat >= 0) ? 1 : 0;
     std::unique_ptr<trc_result> res(new (std::nothrow) trc_result());
     if (!res) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
@@ -3264,6 +3364,7 @@ static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_sourc
     // beyond the pool's sizes per call: 30 of its 45 ms)
     if (!sc->ord_scratch) { sc->ord_scratch.reset(new (std::nothrow) OrdScratch()); if (!sc->ord_scratch) return trc_fail(TRC_ERR_NOMEM, "out of host memory"); }
     OrdCall C = {sc, res.get(), lay, flags, min_energy, seed};      // (stats and time: zero)
+    C.mat_tab = mat_dev ? sc->d_mat_tab.get() : nullptr;
     const int st = ordered_steps(C, in, src, spec, n, reps, ray_offset);
     if (sc->ord_scratch->cap_slots > ORD_SCRATCH_KEEP) *sc->ord_scratch = OrdScratch();      // (beyond 2^26 slots -- 10 GB -- the scratch goes back after the call)
     if (stats) *stats = C.s;        // what the call gathered is handed back whatever its outcome

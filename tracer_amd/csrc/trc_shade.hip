@@ -212,7 +212,11 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
 //        the next active list.  The second ray's Philox stream is trc_child_rid(parent's, event) as in the ordered engine, so the
 //        stream of the ray in a slot is kept in CarryIn.slot_rid: read from the second bounce on, written for every ray that goes on.
 //        What a ray carries (Im of its index, its spectrum) goes with both.  Given bundles and source descriptors (without spectrum).
-template <bool LDS, bool CHART = false, bool SPLIT = false>
+// MAT:   the scene's tabulated materials are on the device (CarryIn.mat_tab, trc_scene_set_materials) and the call brings no rows of
+//        them: a hit between materials evaluates both at the ray's wavelength (trc_shade_xt), and the ray of a source descriptor
+//        draws its wavelength from the source's spectrum at its first hit, with the spectrum's index and no imaginary part -- as
+//        the lean SPEC kernels do (k_s_shade_c).  The children of a SPLIT hit inherit the wavelength like every other ray.
+template <bool LDS, bool CHART = false, bool SPLIT = false, bool MAT = false>
 __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
     extern __shared__ double lds[];
     const FastParams &P = S.P;
@@ -302,8 +306,8 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
             trc_normal(rec, hx, hy, hz, g.dx, g.dy, g.dz, &nx, &ny, &nz);
             const double path = sqrt((hx - g.px) * (hx - g.px) + (hy - g.py) * (hy - g.py) + (hz - g.pz) * (hz - g.pz));
             trc_ray_ext X;
-            X.ref_im = ref_im; X.W = nW; X.n_mat = C.mat ? C.n_mat : 0; X.stride = P.n;
-            X.mat = C.mat ? C.mat + ray : nullptr;
+            X.ref_im = ref_im; X.W = nW; X.n_mat = (!MAT && C.mat) ? C.n_mat : 0; X.stride = P.n;
+            X.mat = (!MAT && C.mat) ? C.mat + ray : nullptr;
             X.wl = nW ? C.spec_wl + ray : nullptr;
             X.spec = nW ? C.spec + ray : nullptr;
             long long spec_stride = P.n;                                 // ... of the spectrum as it reaches this hit
@@ -312,6 +316,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
             double out_im[2], poly_th;
             unsigned long long rid = P.rid ? P.rid[ray] : (P.ray_offset + (unsigned long long)ray);
             if (SPLIT && !first) rid = C.slot_rid[slot];
+            if (MAT && !aux_in) trc_spectrum_of(P.spec, P.seed, rid, &wl, &ref);     // (culled rays and misses never draw)
             // (sample wavelengths and spectrum have different strides once the spectrum lives in the slot table: the polychromatic
             // wall reads both, so its integral is taken here with the two strides, the optics get the wavelengths' stride)
             int n_out;
@@ -338,7 +343,11 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
                 out[0].e = en;
                 poly_th = th;
                 n_out = 1;
-            } else
+            } else if constexpr (MAT)
+                n_out = trc_shade_xt(trc_rec_opt_kind(rec), L.opt + (size_t)s * 8, L.extra, trc_rec_extra_off(rec), trc_rec_extra_len(rec),
+                                     rec[2], rec[5], rec[8], g.dx, g.dy, g.dz, e, ref, wl, path, nx, ny, nz, P.seed, rid, (uint32_t)(bounce0 + 1),
+                                     X, C.mat_tab, out, out_im, &poly_th);
+            else
                 n_out = trc_shade_x(trc_rec_opt_kind(rec), L.opt + (size_t)s * 8, L.extra, trc_rec_extra_off(rec), trc_rec_extra_len(rec),
                                     rec[2], rec[5], rec[8], g.dx, g.dy, g.dz, e, ref, wl, path, nx, ny, nz, P.seed, rid, (uint32_t)(bounce0 + 1),
                                     X, out, out_im, &poly_th);
@@ -449,7 +458,12 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
     flush_sums(L.tally, l_tally, LDS ? 3 * Sn : 0, l_fm, S.lds_fm_bins, Sn);
 }
 
-const void *trc_shade_carry_kernel(bool lds, bool chart, bool split) {
+const void *trc_shade_carry_kernel(bool lds, bool chart, bool split, bool mat) {
+    if (mat) {      // (no CHART x MAT instance: stream_form_shade never asks for one)
+        if (chart) return nullptr;
+        if (split) return lds ? (const void *)k_s_shade_x<true, false, true, true> : (const void *)k_s_shade_x<false, false, true, true>;
+        return lds ? (const void *)k_s_shade_x<true, false, false, true> : (const void *)k_s_shade_x<false, false, false, true>;
+    }
     if (split) {
         if (chart) return lds ? (const void *)k_s_shade_x<true, true, true> : (const void *)k_s_shade_x<false, true, true>;
         return lds ? (const void *)k_s_shade_x<true, false, true> : (const void *)k_s_shade_x<false, false, true>;

@@ -2381,7 +2381,9 @@ static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene 
         K.fn = shade_fn; K.threads = 256; K.wpb = 4; K.max_blocks = (unsigned)(n_cu * 4); K.lds = lds_shade;
         K.lds_tables = SP0.lds_tables; K.lds_fm_bins = SP0.lds_fm_bins;
         if (carry) {            // sixteen waves per workgroup
-            K.fn = trc_shade_carry_kernel(shade_lds, chart, split_rays);
+            // (CarryIn.mat_tab: the materials' tables are on the device and the call brings no rows -- the MAT instances)
+            K.fn = trc_shade_carry_kernel(shade_lds, chart, split_rays, SP0.carry.mat_tab != nullptr);
+            if (!K.fn) return trc_fail(TRC_ERR_UNSUPPORTED, "no shading kernel for device material tables beside a chart flux map");
             K.threads = SHC_THREADS; K.wpb = SHC_THREADS / 64;
             TRC_TRY(stream_shade_grid(K, n_cu));
         } else

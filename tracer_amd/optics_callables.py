@@ -314,14 +314,36 @@ class Lambertian_directional_axisymmetric_piecewise_spectral(NativeOptics):
 
 class TabulatedMaterial(object):
     """Complex refractive index m = n + i k tabulated over wavelength, linear in between (what the reference's
-    ray_trace_utils.optical_constants materials do with interp1d)."""
-    def __init__(self, wavelengths, n, k):
+    ray_trace_utils.optical_constants materials do with interp1d).
+    device=True: the table may go to the device with the scene (Refractive / RefractiveAbsorbant: when every material of a scene
+    is such a one, the engines evaluate m(lambda) per ray there, trc_material_index, with the bits m() gives here, and a source with
+    a spectrum can light the scene without its rays ever being made on the host).  The table then has 2 to 4096 finite points
+    of strictly increasing wavelength (ValueError otherwise).  The default, False, keeps the host's evaluation per ray."""
+    DEVICE_MAX_POINTS = 4096
+
+    def __init__(self, wavelengths, n, k, device=False):
         self.wavelengths = N.asarray(wavelengths, dtype=float)
         self.n = N.asarray(n, dtype=float)
         self.k = N.asarray(k, dtype=float)
+        self.device = bool(device)
+        if self.device:
+            self.device_table()
 
     def m(self, lambdas):
         return N.interp(lambdas, self.wavelengths, self.n) + 1j * N.interp(lambdas, self.wavelengths, self.k)
+
+    def device_table(self):
+        """(wavelengths, n, k) as contiguous float64 arrays, checked against what the device's lookup takes"""
+        wl, n, k = (N.ascontiguousarray(a, dtype=float) for a in (self.wavelengths, self.n, self.k))
+        if wl.ndim != 1 or n.shape != wl.shape or k.shape != wl.shape:
+            raise ValueError("a device material table needs wavelengths, n and k of one length")
+        if not 2 <= len(wl) <= self.DEVICE_MAX_POINTS:
+            raise ValueError("a device material table has 2 to %d points (%d given)" % (self.DEVICE_MAX_POINTS, len(wl)))
+        if not (N.isfinite(wl).all() and N.isfinite(n).all() and N.isfinite(k).all()):
+            raise ValueError("a device material table holds finite values only")
+        if not (N.diff(wl) > 0.).all():
+            raise ValueError("the wavelengths of a device material table must increase strictly")
+        return wl, n, k
 
     def table(self):
         return self.wavelengths, self.n, self.k
@@ -446,7 +468,10 @@ class Refractive(NativeOptics):
     other enters material_1 (:750-751).  Snell's law on the real parts, the real part of the complex Fresnel reflectance as the
     reference computes it (:838-840); single_ray / sigma as RefractiveHomogenous.
     The materials are evaluated by their own m() once per ray (the wavelength does not change along a path) and travel with the
-    rays (trc_rays.mat): ordered engine and per-surface protocol.
+    rays (trc_rays.mat): ordered engine, streaming form of the fast engine and per-surface protocol.
+    When every material of the scene is a TabulatedMaterial(..., device=True) their tables go to the device with the scene
+    instead, and the ordered and the fast engine evaluate m(lambda) at each hit (same bits as m()): a bundle then brings
+    wavelengths only, and a source with a spectrum (SourceSpectrum) is traced without being made on the host first.
     """
     _attenuate = False
     _scaling = 1.

@@ -37,6 +37,16 @@ def material_rows(materials, wavelengths):
     return out
 
 
+def pack_material_tables(materials):
+    """(points per material as int32, wl | n | k of material 0, of material 1, ... as one float64 array) -- what
+    trc_scene_set_materials takes -- when every one of `materials` is a TabulatedMaterial(device=True); else None (and None for no
+    materials): the materials' m(lambda) are then evaluated on the host for every ray (material_rows)."""
+    if not materials or len(materials) > 64 or not all(getattr(m, 'device', False) and hasattr(m, 'device_table') for m in materials):
+        return None
+    tabs = [m.device_table() for m in materials]
+    return N.array([len(t[0]) for t in tabs], dtype=N.int32), N.concatenate([N.concatenate(t) for t in tabs])
+
+
 class NotNativeError(NotImplementedError):
     """The scene holds a geometry/optics plug-in that only exists in Python."""
 
@@ -111,6 +121,7 @@ class CompiledScene(object):
         self.extra = _cabi.f64(self._extra)
         del self._extra, self._seen
         self.n_surf = n
+        self.material_tables = pack_material_tables(self.materials)
 
     def _optics_row(self, i, opt, no_tables=False):
         """(kind, parameters, surface flags[, table]) of an optics manager, and what it means for the scene as a whole"""
@@ -163,6 +174,8 @@ class CompiledScene(object):
         if at < self.n_surf:
             out.append(rows_bytes(at, self.n_surf))
         out.append(self.extra.tobytes())
+        if self.material_tables is not None:        # (the tables go to the device with the scene: an edited one is a new scene)
+            out.append(('materials', self.material_tables[0].tobytes(), self.material_tables[1].tobytes()))
         return tuple(out)
 
     def signature(self):
@@ -205,6 +218,7 @@ class TableScene(object):
         self.splits = False
         self.carries = False
         self.materials = []
+        self.material_tables = None
         self.capture = [False] * n
         self.optics, self.capturing_optics = [], []
         for i in range(n):
@@ -254,6 +268,34 @@ class DeviceScene(object):
         self.pending_hits = None    # PendingHits: what the hit buffer holds for accountants that have not read it yet
         self._has_scattering = None
         self.capture_rate = None    # largest share of captured hits per ray of a fast trace seen on the scene in its present poses
+        self._chart_maps = set()    # surfaces whose flux map bins in another chart than XY
+        self.has_material_tables = False
+        self._n_materials = 0
+        if getattr(compiled, 'material_tables', None) is not None:
+            self.set_materials(*compiled.material_tables)
+
+    def set_materials(self, n_points, packed):
+        """The tabulated materials of the scene's Refractive optics on the device (trc_scene_set_materials): points per material
+        and wl | n | k of each, one after the other; replaces the tables set before, no materials removes them."""
+        n_points = N.ascontiguousarray(n_points, dtype=N.int32)
+        packed = _cabi.f64(packed)
+        _cabi.check(self.lib.trc_scene_set_materials(self.handle, len(n_points), n_points.ctypes.data_as(C.POINTER(C.c_int32)) if len(n_points) else None,
+                                                     _cabi.ptr(packed) if len(n_points) else None))
+        self.has_material_tables = len(n_points) > 0
+        self._n_materials = len(n_points)
+
+    def materials_on_device(self):
+        """the engines evaluate the scene's materials per ray themselves: tables on the device, and no flux map in a chart other
+        than XY (which has no kernel instance beside them: such a scene keeps the host's rows)"""
+        return self.has_material_tables and not self._chart_maps
+
+    def material_rows(self, wavelengths):
+        """trc_rays.mat as the device evaluates it (trc_scene_eval_materials): (2K, n), rows 2k, 2k+1 = Re, Im of material k at
+        `wavelengths` -- bit for bit what material_rows(compiled.materials, wavelengths) gives on the host"""
+        wl = _cabi.f64(N.ravel(wavelengths))
+        out = N.empty((2 * self._n_materials, len(wl)))
+        _cabi.check(self.lib.trc_scene_eval_materials(self.handle, len(wl), _cabi.ptr(wl) if len(wl) else None, _cabi.ptr(out) if len(wl) else None))
+        return out
 
     def close(self):
         if self.handle is not None and self.handle.value:
@@ -324,6 +366,10 @@ class DeviceScene(object):
         _cabi.check(self.lib.trc_scene_set_fluxmap_chart(self.handle, surf_index, int(chart), len(u) - 1, len(v) - 1, _cabi.ptr(u),
                                                          _cabi.ptr(v), _cabi.ptr(p)))
         self.fluxmaps[surf_index] = (len(u) - 1, len(v) - 1)
+        if int(chart) != _cabi.FM_XY:
+            self._chart_maps.add(surf_index)
+        else:
+            self._chart_maps.discard(surf_index)
 
     def get_fluxmap(self, surf_index):
         nu, nv = self.fluxmaps[surf_index]
@@ -478,13 +524,16 @@ class DeviceScene(object):
         if isinstance(bundle, LazySourceBundle) and bundle.is_pending():
             spec = bundle.source_spectrum()
             # (surfaces between tabulated materials need m(lambda) of every ray from the host: such a bundle is made first and
-            # traced as a given one, below)
-            if spec is None or not mats:
+            # traced as a given one, below -- unless the materials' tables are on the device, which evaluates them itself)
+            if spec is None or not mats or self.materials_on_device():
                 desc, n, seed, off = bundle.source_args()
                 return None, desc, n, seed, off, spec, spec.desc() if spec is not None else None
         cols = bundle.columns_soa()
         n = cols['x'].shape[0]
-        if mats:
+        if mats and self.materials_on_device():
+            if 'wavelength' not in cols:
+                raise ValueError("the scene refracts between materials: the bundle needs a `wavelengths` column")
+        elif mats:
             # the materials' own m(lambda) at every ray's wavelength (children inherit the wavelength): tables, files and analytic
             # models alike, and the device's comparison `index == material_1's` (optics_callables.py:750) stays exact
             if 'wavelength' not in cols:

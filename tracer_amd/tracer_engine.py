@@ -259,13 +259,17 @@ class TracerEngine(object):
             # captured hit of a polychromatic ray keeps its sample wavelengths and its spectrum before and after the surface (what
             # PolychromaticAccountant collects).
             carries = dev.compiled.carries or (not _pending(bundle) and (bundle.is_polychromatic() or bundle.has_complex_index()))
+            # A source with a spectrum stays pending on a scene whose materials' tables are on the device (TabulatedMaterial(...,
+            # device=True)): the kernels evaluate m(lambda) per ray and draw the wavelengths themselves.
+            dev_mats = getattr(dev.compiled, 'material_tables', None) is not None and _pending(bundle) and \
+                bundle.source_spectrum() is not None and dev.materials_on_device()
             if carries:
-                carries = _pending(bundle) or bundle.get_num_rays() < 64
+                carries = (_pending(bundle) and not dev_mats) or bundle.get_num_rays() < 64
             # Optics that send two rays on from a hit (single_ray=False) are traced by the streaming form too (k_s_shade_x<.., SPLIT>,
             # DESIGN.md section 14.11): 64 rays or more, no source spectrum.  The ray tree, smaller calls and sources with a
             # spectrum stay with the ordered engine.
             splits = dev.compiled.splits and not (self.SPLIT_ON_FAST and bundle.get_num_rays() >= 64 and
-                                                  not (_pending(bundle) and bundle.source_spectrum() is not None))
+                                                  not (_pending(bundle) and bundle.source_spectrum() is not None and not dev_mats))
             engine = 'ordered' if (tree or splits or carries) else 'fast'
         if accel and Kd_Tree is None and (engine == 'fast' or (engine == 'ordered' and (dev.n_surf > self.KD_BUILD_MAX or (
                 dev.n_surf <= 65535 and bundle.get_num_rays() * dev.n_surf <= self.KD_WORTH_IT)))):
