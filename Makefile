@@ -9,11 +9,10 @@ LIB := $(ROOT)tracer_amd/lib/libtracer_amd.so
 CSRC := $(ROOT)tracer_amd/csrc
 # two translation units: the engines and the C-ABI (trc_kernels.hip, which includes trc_stream.inc), and the class-split shading
 # kernels of the streaming engine (trc_shade.hip).  `make -j2` compiles them side by side.
-SRC := $(CSRC)/trc_kernels.hip
 SRCS := $(CSRC)/trc_kernels.hip $(CSRC)/trc_shade.hip
 OBJDIR := $(ROOT)build/obj
 OBJS := $(OBJDIR)/trc_kernels.o $(OBJDIR)/trc_shade.o
-HDR := $(CSRC)/trc_core.h $(CSRC)/trc_bounds.h $(CSRC)/trc_footprint.h $(CSRC)/trc_device.h $(CSRC)/trc_stream.inc $(ROOT)include/tracer_amd.h
+HDR := $(CSRC)/trc_core.h $(CSRC)/trc_bounds.h $(CSRC)/trc_footprint.h $(CSRC)/trc_forms.h $(CSRC)/trc_device.h $(CSRC)/trc_stream.inc $(ROOT)include/tracer_amd.h
 
 HOSTCHECK := $(ROOT)tests/hostcheck/libtrc_hostcheck.so
 HOSTCHECK_SRC := $(ROOT)tests/hostcheck/hostcheck.cpp

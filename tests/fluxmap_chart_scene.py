@@ -29,7 +29,7 @@ SEAM = (FLOOR, CYLINDER, SPHERE)          # full-azimuth maps: their first and l
 CLASS_OF = {FLOOR: 'terminal', WALL: 'diffuse', CYLINDER: 'general', SPHERE: 'mirror', DISH: 'diffuse', FRUSTUM: 'mirror'}
 EDGE_EPS = 1e-12                          # no hit may lie within this share of a map's span from one of its edges
 
-# Bins of the floor's map per storage regime of the streaming engine (stream_form_shade, trc_stream.inc: a shading kernel keeps the
+# Bins of the floor's map per storage regime of the streaming engine (trc_stream_form_shade, trc_stream.inc: a shading kernel keeps the
 # bins in LDS while they and its tables fit 78 KiB (k_s_shade) / 150 KiB (the lean kernels)).  The other five maps hold
 # 14 * 19 + 7 * 12 + 6 * 12 + 5 * 8 + 6 * 9 = 516 bins.
 #   lds      13 x 16:   (208 + 516) * 8   =   5 792 bytes: every kernel keeps the bins in LDS

@@ -23,7 +23,7 @@ CLIPPED = (1, 5)          # maps that cover only a part of what their surface se
 FLOOR = 0
 MOVING = 6
 
-# Bins of the floor's map per storage regime of the streaming engine (stream_form_shade / stream_form_absorb in trc_stream.inc); the
+# Bins of the floor's map per storage regime of the streaming engine (trc_stream_form_shade / trc_stream_form_absorb in trc_stream.inc); the
 # other four maps hold 204 + 266 + 336 + 48 = 854 bins in every regime.  The tables every shading kernel stages besides the bins --
 # tallies (3 S + 2) * 8 = 184, surface records S * stride * 8, optics 8 * S * 8 = 448, edges, map descriptors and flags -- come to
 # less than 8 KiB for these seven surfaces (records of at most 31 doubles: 1.7 KiB; the edges of the five maps: 4.9 KiB with the

@@ -10,6 +10,7 @@
 #include "../../tracer_amd/csrc/trc_core.h"
 #include "../../tracer_amd/csrc/trc_bounds.h"
 #include "../../tracer_amd/csrc/trc_footprint.h"
+#include "../../tracer_amd/csrc/trc_forms.h"
 
 static void pack_record(const trc_surface_desc &s, double *rec, int stride) {
     for (int i = 0; i < stride; ++i) rec[i] = 0.0;
@@ -479,8 +480,8 @@ int hc_search_lds_layout(long n, const int *rows, unsigned long long *out) {
     return 0;
 }
 
-// What the streaming engine's choice of search kernels reads off a scene and a source (stream_plan, stream_form_fresh,
-// stream_form_bounce): the search structures as trc_scene_create builds them and the footprint map of `src` (null: none) at M cells.
+// What the streaming engine's choice of search kernels reads off a scene and a source (stream_plan, trc_stream_form_fresh,
+// trc_stream_form_bounce): the search structures as trc_scene_create builds them and the footprint map of `src` (null: none) at M cells.
 // out[0] small grid ok, [1] its cells, [2] its list entries, [3] large grid ok, [4] its occupancy words, [5] entries of the list of all
 // boxes, [6] unbounded surfaces, [7] footprint map ok, [8] Mc, [9] its list entries, [10] coverage, [11] has_generic, [12] cdf_end,
 // [13] sizeof(trc_buie_fast)
@@ -530,6 +531,148 @@ int hc_footprint_bits(int n_surf, const trc_surface_desc *surfs, const trc_sourc
         generic[i] = trc_fp_generic(F.P, o) ? 1 : 0;
     }
     return 0;
+}
+
+// ---- the choice of kernel instances (tracer_amd/csrc/trc_forms.h) -------------------------------------------------------------------
+// A fact block is HC_FACTS doubles, in the order of search_cases.FACT_KEYS: the scene, the call, the footprint map, the knobs.
+enum { HC_FACTS = 53, HC_STAGE = 8, HC_SHADE = 11 };
+
+static trc_facts hc_facts_of(const double *v) {
+    trc_facts f = {};
+    trc_scene_facts &s = f.scene;
+    int k = 0;
+    auto I = [&]() { return (int)v[k++]; };
+    auto B = [&]() { return v[k++] != 0.0; };
+    s.n_surf = I(); s.stride = I(); s.accel_ok = B(); s.accel_kd_ok = B(); s.has_kd = B();
+    s.kd_nodes = I(); s.kd_nleaf = I(); s.kd_nalways = I(); s.kd_depth = I();
+    s.grid_ok = B(); s.big_ok = B(); s.grid_cells = I(); s.grid_list = I(); s.brute_list = I(); s.n_unbounded = I(); s.big_occ_words = I();
+    s.n_fm_edges = I(); s.fms_bytes = I(); s.n_extra = I(); s.fm_bins = (long long)v[k++];
+    s.chart = B(); s.transfer = B(); s.splits = B();
+    s.walked = true; s.all_flat = B(); s.simple = B(); s.cls_moving = (unsigned)I(); s.cls_all = (unsigned)I(); s.any_term = B();
+    trc_call_facts &c = f.call;
+    c.n = (long long)v[k++]; c.flags = I(); c.src_kind = I(); c.spec = B(); c.carry = B(); c.mat_dev = B(); c.term_ok = B();
+    trc_fp_facts &p = f.fp;
+    p.use = B(); p.n_list = (long long)v[k++]; p.M = I(); p.Mc = I(); p.has_generic = B(); p.cdf_end = v[k++]; p.coverage = v[k++];
+    p.ucoverage = v[k++]; p.umask_words = I(); p.Mu = I(); p.Mv = I();
+    StreamKnobs &K = f.knobs;
+    K.search = I(); K.fresh = B(); K.bounce = B(); K.first = B(); K.coop = B(); K.absorb = I(); K.umask = B();
+    return f;
+}
+
+static double *hc_put_id(double *o, const trc_kernel_id &id) {
+    *o++ = id.family;
+    for (int k = 0; k < 5; ++k) *o++ = id.a[k];
+    return o;
+}
+static double *hc_put_stage(double *o, const trc_stage &s) {
+    o = hc_put_id(o, s.id);
+    *o++ = s.threads; *o++ = (double)s.lds;
+    return o;
+}
+
+// Every decision of trc_forms.h for n fact blocks: per block HC_DECISIONS doubles in the order of search_cases.DECISION_KEYS -- the
+// engine of a fast call, the megakernel's plan, the ordered engine's choice, the streaming plan and, where the scene has a streaming
+// form and its shading stage an instance (out[..] `decided`), the streaming forms with the stages in the order gen0, gen, walk, exact,
+// cull, cull_u, fresh, fresh_one, bounce, first, absorb (id, threads, LDS bytes each) and the three shading stages (+ class, tables
+// in LDS, bins in LDS).  Returns the doubles per block.
+int hc_forms_decide(long n, const double *facts, double *out) {
+    const int per = 3 + 11 + 7 + 5 + 26 + 11 * HC_STAGE + 3 * HC_SHADE;
+    for (long i = 0; i < n; ++i) {
+        trc_facts f = hc_facts_of(facts + (size_t)HC_FACTS * i);
+        double *o = out + (size_t)per * i;
+        for (int k = 0; k < per; ++k) o[k] = 0.0;
+        const trc_engine_choice E = trc_fast_choose_engine(f.scene, f.call, f.knobs);
+        *o++ = E.use_stream; *o++ = E.refused; *o++ = E.plan.mode;
+        const MegaPlan M = mega_plan(f.scene, f.call);
+        *o++ = M.m32; *o++ = M.threads; *o++ = (double)M.lds; *o++ = M.lds_tally; *o++ = M.lds_scene;
+        o = hc_put_id(o, M.id);
+        const trc_ord_choice O = trc_ordered_choose(f.scene, f.call.flags, f.call.mat_dev);
+        *o++ = O.mode;
+        o = hc_put_id(o, O.id);
+        StreamPlan plan = {0, 0, true};
+        const bool ok = stream_plan(f.scene, (f.call.flags & TRC_TRACE_ACCEL) != 0, f.knobs, &plan);
+        trc_stream_forms F;
+        f.call.carry = f.call.carry || f.scene.splits;      // (stream_trace: the calls on a scene whose optics split rays carry too)
+        const bool decided = ok && trc_stream_decide(f, plan, &F);
+        *o++ = ok; *o++ = plan.mode; *o++ = (double)plan.lds_walk; *o++ = plan.walk_ok; *o++ = decided;
+        if (!decided) continue;
+        const double flags[26] = {(double)F.src_kind, (double)F.gridm, (double)F.small_scene, (double)F.n_shk, (double)F.multi, (double)F.cull_lu, (double)F.cull_lv,
+                                  F.ulisted_share, (double)F.coop, (double)F.use_fp, (double)F.use_fused, (double)F.use_first, (double)F.use_absorb,
+                                  (double)F.absorb_inline, (double)F.lds_inline, F.general_share, F.listed_share, (double)F.search, (double)F.lds_recs,
+                                  (double)F.lds_tally, (double)F.lds_tables, (double)F.lds_extra, (double)F.lds_fm_bins, (double)F.bg_occ_words,
+                                  (double)F.shade_term_cls, (double)F.split_terminal};
+        for (int k = 0; k < 26; ++k) *o++ = flags[k];
+        const trc_stage *st[11] = {&F.gen0, &F.gen, &F.walk, &F.exact, &F.cull, &F.cull_u, &F.fresh, &F.fresh_one, &F.bounce, &F.first, &F.absorb};
+        for (int k = 0; k < 11; ++k) o = hc_put_stage(o, *st[k]);
+        for (int k = 0; k < TRC_CLS_COUNT; ++k) {
+            const trc_shade_stage &s = F.shk[k];
+            o = hc_put_stage(o, {s.id, s.threads, s.lds});
+            *o++ = s.cls; *o++ = s.lds_tables; *o++ = s.lds_fm_bins;
+        }
+    }
+    return per;
+}
+
+// the scene and footprint parts of a fact block (the rest is left as it is) for a scene built as hc_search_sizes builds it: the search
+// structures as trc_scene_create makes them, the Kd-tree `kd` (null: none) as trc_scene_set_kdtree packs it, the footprint map of
+// `src` (null: none) at M cells as stream_fp_prepare makes it.  force32: TRC_GRID_FORCE32 is set when the scene is made.
+int hc_scene_facts(int n_surf, const trc_surface_desc *surfs, const trc_kdtree_desc *kd, const trc_source_desc *src, int M, int force32, double *v) {
+    trc_accel_host H;
+    H.kd_depth = 0;
+    trc_accel_build_surfaces(surfs, n_surf, H);
+    trc_accel_build_grid(H, n_surf);
+    if (force32) H.grid_ok = false;
+    if (!H.grid_ok) trc_accel_build_grid32(surfs, n_surf, H);       // (the large grid: of the scenes the LDS-sized one cannot hold)
+    trc_scene_facts s = {};
+    s.accel_ok = true;
+    if (kd) { s.has_kd = true; s.kd_nodes = kd->n_nodes; s.kd_nleaf = kd->n_leaf_surfs; s.kd_nalways = kd->n_always; s.accel_kd_ok = trc_accel_build_kd(kd, H); }
+    trc_scene_facts_fill(surfs, n_surf, H, true, &s);
+    int max_np = 0;
+    for (int i = 0; i < n_surf; ++i) { int np = trc_gm_nparams(surfs[i].gm_kind); if (np > max_np) max_np = np; }
+    s.stride = (TRC_REC_HDR + max_np) | 1;
+    const double sv[16] = {(double)s.n_surf, (double)s.stride, (double)s.accel_ok, (double)s.accel_kd_ok, (double)s.has_kd, (double)s.kd_nodes, (double)s.kd_nleaf,
+                           (double)s.kd_nalways, (double)s.kd_depth, (double)s.grid_ok, (double)s.big_ok, (double)s.grid_cells, (double)s.grid_list,
+                           (double)s.brute_list, (double)s.n_unbounded, (double)s.big_occ_words};
+    for (int k = 0; k < 16; ++k) v[k] = sv[k];
+    v[23] = s.all_flat; v[24] = s.simple; v[25] = s.cls_moving; v[26] = s.cls_all; v[27] = s.any_term;
+    for (int k = 35; k < 46; ++k) v[k] = 0.0;
+    if (src) {
+        trc_fp_host F;
+        trc_fp_build(surfs, n_surf, H, *src, F, M, trc_src_kind_is_buie(src->kind));
+        if (F.ok) {
+            v[35] = 1.0; v[36] = (double)F.clist.size(); v[37] = F.P.M; v[38] = F.P.Mc; v[39] = F.P.has_generic != 0; v[40] = F.P.cdf_end;
+            v[41] = F.coverage; v[42] = F.ucoverage; v[43] = (double)F.umask.size(); v[44] = F.Mu; v[45] = F.Mv;
+        }
+    }
+    return 0;
+}
+
+int hc_kernel_name(const int *id, char *buf, int len) {
+    return trc_kernel_name(trc_kid(id[0], id[1], id[2], id[3], id[4], id[5]), buf, (size_t)len);
+}
+
+// every id the header can produce: its families over their argument ranges (an integer argument over `ints`, the n_ints values the
+// caller thinks possible; a bool over 0, 1) under trc_kernel_id_valid.  Six ints per id into out[6 * cap]; returns how many there are.
+int hc_kernel_ids(const int *ints, int n_ints, int *out, int cap) {
+    int n = 0;
+    for (int family = 1; family < TRC_K_FAMILIES; ++family) {
+        const char *args;
+        trc_kernel_family_name(family, &args);
+        const int n_args = (int)strlen(args);
+        int range[5], idx[5] = {0, 0, 0, 0, 0};
+        long total = 1;
+        for (int k = 0; k < 5; ++k) { range[k] = k >= n_args ? 1 : (args[k] == 'b' ? 2 : n_ints); total *= range[k]; }
+        for (long t = 0; t < total; ++t) {
+            long r = t;
+            for (int k = 0; k < 5; ++k) { idx[k] = (int)(r % range[k]); r /= range[k]; }
+            trc_kernel_id id = trc_kid(family);
+            for (int k = 0; k < n_args; ++k) id.a[k] = args[k] == 'b' ? idx[k] : ints[idx[k]];
+            if (!trc_kernel_id_valid(id)) continue;
+            if (n < cap) { out[6 * n] = family; for (int k = 0; k < 5; ++k) out[6 * n + 1 + k] = id.a[k]; }
+            ++n;
+        }
+    }
+    return n;
 }
 
 }  // extern "C"

@@ -4,8 +4,12 @@ Calls that select every instance and every search branch of the persistent megak
 
 The megakernel is three kernels, k_trace_coop<512 | 256, SPEC, SUN, CHART> and k_trace_fast<256, SPEC, SUN, CHART>
 (csrc/trc_kernels.hip): 24 compiled instances.  mega_plan picks the kernel and k_trace_fast's staging form from byte sums over the
-scene, the Kd-tree set on it and the source; mega_kernels picks SPEC, SUN and CHART from the source and the scene's flux maps.
-plan() restates the first, instance() the second, partition() the slice of the ray range every wave takes.
+scene, the Kd-tree set on it and the source; its id takes SPEC, SUN and CHART from the source and the scene's flux maps.
+plan() restates the first, instance() the second, partition() the slice of the ray range every wave takes; engine() and ordered()
+restate the choice between the engines and k_ord_bounce's search.  They take a fact block (search_cases.FACT_KEYS), and decide()
+puts them together with the restatements of search_cases.py and shade_cases.py.  What holds them to the library: the decisions of
+csrc/trc_forms.h itself, exported by the check library (search_cases.library_decide), must equal decide() field by field -- for every
+case, and for 1e5 random fact blocks across every threshold (test_mega_cases_host.py).
 
 The scenes are the rooms of search_cases.py -- general rotation, a twin whose exact tie the reference gives to the lower index, a
 receiver that ends every ray, a lean and a full capture, a flux map -- with filler counts taken from plan(), Kd-trees over them that
@@ -26,7 +30,7 @@ import shade_cases as sc
 
 N_RAYS, REPS, SEED, E_MIN_SHARE = sc.N_RAYS, sc.REPS, sc.SEED, sc.E_MIN_SHARE
 KiB = 1024
-COOP_LEAFCAP = 16               # csrc/trc_kernels.hip: leaves listed per lane between two drains
+COOP_LEAFCAP = 16               # csrc/trc_forms.h: leaves listed per lane between two drains
 COOP_E = 128                    # ... exact-test queue entries per wave
 COOP_MAX_NODES = 16384          # ... mega_plan: `sc->kd_nodes <= COOP_MAX_NODES` (14 bits of a stack entry)
 COOP_MAX_DEPTH = 24             # ... mega_plan: `sc->accel.kd_depth <= COOP_MAX_DEPTH`
@@ -34,7 +38,7 @@ COOP_FIXED_BYTES = COOP_E * 8 + 64 * 8 + COOP_E * 4 + 64 * 4 + 64 * 4 + 64 * 4 +
 LDS_MAX_ALLOWED = 160 * KiB - 512           # ... mega_plan: `lds <= LDS_MAX_ALLOWED`
 LDS_MAX_PLAIN = 64 * KiB        # ... mega_plan: `M.lds + b_tally <= LDS_MAX_PLAIN`, `M.lds + b_scene <= LDS_MAX_PLAIN`
 TRC_KD_STACK = 32               # csrc/trc_core.h; trc_scene_set_kdtree: `max_depth > TRC_KD_STACK` is refused
-ORD_STACK_DEPTH = 24            # csrc/trc_kernels.hip, ordered_search_mode: `kd_depth + 2 <= ORD_STACK_DEPTH`
+ORD_STACK_DEPTH = 24            # csrc/trc_forms.h, trc_ordered_choose: `kd_depth + 2 <= ORD_STACK_DEPTH`
 TRC_BUIE_NELEM = 210            # include/tracer_amd.h
 TRC_BUIE_STAGED = 3 * (TRC_BUIE_NELEM + 1) + 6 + 3          # csrc/trc_core.h: TRC_BUIE_TABLE + 3
 MAX_SURFACES = 65535            # mega_plan: `S <= 65535`
@@ -46,22 +50,23 @@ def coop_wave_bytes(depth):
     return depth * 64 * 4 + COOP_FIXED_BYTES
 
 
-# -- mega_plan, mega_kernels and the wave partition restated -----------------------------------------------------------------------
-def plan(n_surf, stride, brute_list, unbounded, kd, accel, src):
+# -- mega_plan, its instance and the wave partition restated -----------------------------------------------------------------------
+def plan(f):
     """
-    mega_plan: kd: the flattened tree set on the scene (None: no tree); accel: trace_fast's accel; src: a source descriptor travels with
-    the call (its Buie table is staged whatever the source kind).  Returns dict(kernel 'coop512' | 'coop256' | 'fast256', threads,
-    lds_tally, lds_scene, lds: the dynamic LDS asked for, and the sums behind every decision).
+    mega_plan (csrc/trc_forms.h) restated for a fact block (search_cases.FACT_KEYS): the tree set on the scene, trace_fast's accel
+    (flags), whether a source descriptor travels with the call (src_kind >= 0: its Buie table is staged whatever the source kind).
+    Returns dict(kernel 'coop512' | 'coop256' | 'fast256', threads, lds_tally, lds_scene, lds: the dynamic LDS asked for, and the sums
+    behind every decision).
     """
-    Sn = n_surf
-    use_kd = kd is not None and accel
-    nodes, nleaf, nalways = (len(kd['flag']), len(kd['leaf_surfs']), len(kd['always_relevant'])) if kd is not None else (0, 0, 0)
-    depth = S.kd_depth(kd) if kd is not None else 0
+    Sn = f['n_surf']
+    has_kd = bool(f['has_kd'])
+    use_kd = has_kd and bool(f['flags'] & S.TRACE_ACCEL)
+    nodes, nleaf, nalways, depth = f['kd_nodes'], f['kd_nleaf'], f['kd_nalways'], f['kd_depth']
     p = dict(n_surf=Sn, use_kd=use_kd, nodes=nodes, nleaf=nleaf, nalways=nalways, depth=depth)
-    p['b_buie'] = b_buie = TRC_BUIE_STAGED * 8 if src else 0
+    p['b_buie'] = b_buie = TRC_BUIE_STAGED * 8 if f['src_kind'] >= 0 else 0
     p['b_tally'] = b_tally = (3 * Sn + 2) * 8
-    p['coop_ok'] = Sn <= MAX_SURFACES and (not use_kd or (nodes <= COOP_MAX_NODES and depth <= COOP_MAX_DEPTH))
-    p['b_acc'] = 6 * Sn * 4 + ((2 * nodes * 4 + nalways * 4 + nleaf * 2) if use_kd else (8 + brute_list * 2)) + unbounded * 4 + 32
+    p['coop_ok'] = bool(f['accel_ok']) and Sn <= MAX_SURFACES and (not use_kd or (bool(f['accel_kd_ok']) and nodes <= COOP_MAX_NODES and depth <= COOP_MAX_DEPTH))
+    p['b_acc'] = 6 * Sn * 4 + ((2 * nodes * 4 + nalways * 4 + nleaf * 2) if use_kd else (8 + f['brute_list'] * 2)) + f['n_unbounded'] * 4 + 32
     p['b_wave'] = coop_wave_bytes((depth if depth > 0 else 1) if use_kd else 1)
     p['lds512'], p['lds256'] = [b_buie + b_tally + p['b_acc'] + (t // 64) * p['b_wave'] for t in (512, 256)]
     p['threads'] = 256
@@ -70,7 +75,7 @@ def plan(n_surf, stride, brute_list, unbounded, kd, accel, src):
     elif p['coop_ok'] and p['lds256'] <= LDS_MAX_ALLOWED:
         p.update(kernel='coop256', lds=p['lds256'], lds_tally=1, lds_scene=0)
     else:
-        p['b_scene'] = b_scene = Sn * stride * 8 + ((nodes * 8 + (nodes * 2 + nleaf + nalways) * 4 + 8) if kd is not None else 0)
+        p['b_scene'] = b_scene = Sn * f['stride'] * 8 + ((nodes * 8 + (nodes * 2 + nleaf + nalways) * 4 + 8) if has_kd else 0)
         lds = b_buie
         p['need_tally'] = lds + b_tally
         p['lds_tally'] = int(p['need_tally'] <= LDS_MAX_PLAIN)
@@ -82,6 +87,51 @@ def plan(n_surf, stride, brute_list, unbounded, kd, accel, src):
     return p
 
 
+STREAM_MIN_RAYS, STREAM_MIN_RAYS_BIG, STREAM_FEWEST_RAYS = 1048576, 4096, 64         # csrc/trc_forms.h
+
+
+def engine(f, forms):
+    """trc_fast_choose_engine restated, from the streaming plan of search_cases.forms(f): dict(use_stream, refused, engine_mode)"""
+    stream_ok = f['n'] >= STREAM_FEWEST_RAYS and bool(forms['plan_ok'])
+    mode = forms['mode'] if stream_ok else 0
+    only = bool(f['carry'] or f['splits'])
+    force_stream = bool(f['flags'] & S.TRACE_STREAM) or only
+    force_mega = not only and bool(f['flags'] & S.TRACE_MEGAKERNEL)
+    use = stream_ok and (force_stream or (not force_mega and f['n'] >= (STREAM_MIN_RAYS_BIG if mode == 3 else STREAM_MIN_RAYS)))
+    return dict(use_stream=int(use), refused=int(only and not use), engine_mode=mode)
+
+
+def ordered(f):
+    """trc_ordered_choose restated: (mode of the search, instance of k_ord_bounce)"""
+    use_kd = bool(f['has_kd']) and bool(f['flags'] & S.TRACE_ACCEL)
+    mode = 0
+    if f['accel_ok'] and f['big_ok'] and not use_kd:
+        mode = 2
+    elif f['accel_ok'] and f['n_surf'] <= MAX_SURFACES and (not use_kd or (f['accel_kd_ok'] and f['kd_depth'] + 2 <= ORD_STACK_DEPTH)):
+        mode = 1
+    return mode, 'k_ord_bounce<%d, %s, %s>' % (mode, _t(f['chart']), _t(f['mat_dev'] and not f['chart']))
+
+
+def decide(f):
+    """every decision of csrc/trc_forms.h restated for a fact block, in the shape of search_cases.library_decide: plan() / instance(),
+    engine(), ordered() here, search_cases.forms(), shade_cases.shade_forms() and absorb_forms()"""
+    d = S.forms(f)
+    out = engine(f, d)
+    p = plan(f)
+    out.update(m32=int(p['kernel'] != 'fast256'), mega_threads=p['threads'], mega_lds=p['lds'], mega_lds_tally=p['lds_tally'], mega_lds_scene=p['lds_scene'],
+               mega=instance(p['kernel'], f['spec'], f['src_kind'] in (7, 8), f['chart']))
+    out['ord_mode'], out['ord'] = ordered(f)
+    out.update(plan_ok=d['plan_ok'], mode=d.get('mode', 0), lds_walk=d.get('lds_walk', 0), walk_ok=d.get('walk_ok', 1), decided=0)
+    sh = sc.shade_forms(f) if d['plan_ok'] else None
+    if sh is None:
+        return out
+    d.update(sh)
+    d.update(sc.absorb_forms(f, d))
+    out.update((k, d[k]) for k in S.FORM_KEYS + S.STAGES + ('shk',))
+    out['decided'] = 1
+    return out
+
+
 def _t(x):
     return 'true' if x else 'false'
 
@@ -90,7 +140,7 @@ KERNEL = {'coop512': 'k_trace_coop<512, %s, %s, %s>', 'coop256': 'k_trace_coop<2
 
 
 def instance(kernel, spec, sun, chart):
-    """mega_kernels: the instance as a kernel trace names it"""
+    """the id of mega_plan: the instance as a kernel trace names it"""
     return KERNEL[kernel] % (_t(spec), _t(sun), _t(chart))
 
 
@@ -123,7 +173,7 @@ ROOM_STRIDE = 21                                # (14 + the polygon's 6 paramete
 def _room_plan(n_surf):
     """plan() of a room traced from a descriptor source without a tree, every surface bounded (brute_list = S): what decides the filler
     counts; test_mega_cases_host.py repeats the sums with the sizes the library reads off the scene"""
-    return plan(n_surf, ROOM_STRIDE, n_surf, 0, None, True, True)
+    return plan(S.blank_facts(n_surf=n_surf, stride=ROOM_STRIDE, brute_list=n_surf, flags=S.TRACE_ACCEL, src_kind=S.SRC_KIND['buie']))
 
 
 def fill_for(what, kind='curved'):
@@ -551,11 +601,21 @@ class Case(_Case):
         v, d, e, rid = rays_of(self)
         return RayBundle(vertices=v.copy(), directions=d.copy(), energy=e.copy())
 
-    def plan(self):
+    def facts(self):
+        """the fact block of the call: the scene with its maps and the case's tree as the library gathers them (search_cases.scene_facts),
+        a call of n rays that leaves the engine to the library"""
         s = scene(self.scene)
-        q = s.sizes(None)
         kd = tree(self)
-        return plan(s.cs.n_surf, s.stride, q['brute_list'], q['unbounded'], kd.flat() if kd is not None else None, self.accel, not self.given)
+        edges = dict(s.edges)
+        if self.chart:
+            edges[self.chart_map[0]] = CHART_EDGES
+        f = S.scene_facts(s.cs, kd.flat() if kd is not None else None, None, edges, chart=self.chart)
+        f.update(n=self.n, flags=S.TRACE_ACCEL if self.accel else 0, src_kind=-1 if self.given else S.SRC_KIND[self.src], spec=int(self.spec),
+                 term_ok=int(self.min_energy >= 0.))
+        return f
+
+    def plan(self):
+        return plan(self.facts())
 
 
 def _case(name, scn, src, kernel, staging=(1, 0), spec=False, chart=False, given=False, n=N_RAYS, reps=REPS, accel=True, kd=None, branches=()):
@@ -745,18 +805,7 @@ def near_ties_of(s, o, min_energy, reps):
 
 
 # -- walking a flat tree on the host -------------------------------------------------------------------------------------------------
-def kd_desc(f):
-    """the flattened tree as the check library takes it (the arrays stay with `f`)"""
-    from tracer_amd import _cabi
-    kd = _cabi.KdTreeDesc()
-    kd.n_nodes, kd.n_leaf_surfs, kd.n_always = len(f['flag']), len(f['leaf_surfs']), len(f['always_relevant'])
-    i32 = C.POINTER(C.c_int32)
-    for k in ('flag', 'child', 'leaf_off', 'leaf_cnt', 'leaf_surfs', 'always_relevant'):
-        setattr(kd, k, f[k].ctypes.data_as(i32))
-    kd.split = S._ptr(f['split'])
-    for k in range(6):
-        kd.bounds[k] = f['bounds'][k]
-    return kd
+kd_desc = S.kd_desc
 
 
 def leaves_crossed(f, v, d):

@@ -10,10 +10,13 @@ driver (csrc/trc_stream.inc) picks its search kernels per call from 79 template 
   k_s_bounce<GRIDM, LDS, FRESH, FLAT, SUN>  continued rays, and fresh rays outside the map; k_s_bounce_coop<FRESH, FLAT, SUN> on the large grid
   k_s_gen<FRESH, KIND>, k_s_gen_src<KIND>, k_s_walk<256, GRID>, k_s_exact      the general path
 
-predict() restates that choice -- stream_plan, stream_choose_forms, stream_form_fresh, stream_form_bounce, plan_bounce /
-launch_bounce -- from the sizes the host-compiled check library reads off the scene and the source (hc_search_sizes: the search
-structures as trc_scene_create builds them, the footprint map), and lds_layout() restates trc_search_lds_layout (csrc/trc_bounds.h)
-with fresh_lds_parts / bounce_lds_parts to the byte.
+forms() restates that choice -- stream_plan and the search stages of trc_stream_decide (csrc/trc_forms.h) -- for a fact block: the
+plain numbers the choice reads, which facts() takes for a call from the host-compiled check library (hc_scene_facts: the search
+structures as trc_scene_create builds them, the footprint map).  predict() adds the per-bounce choice of plan_bounce / launch_bounce,
+and lds_layout() restates trc_search_lds_layout (csrc/trc_bounds.h) with fresh_lds_parts / bounce_lds_parts to the byte.  What holds
+the restatement to the library: the check library exports the header's own decisions (library_decide) and names (kernel_name,
+library_ids), and test_search_cases_host.py / test_mega_cases_host.py compare them with forms() field by field -- for every call,
+for 1e5 random fact blocks across every threshold, and ALL_INSTANCES with the ids the header can produce.
 
 The scenes are shade_cases.room() -- general rotation, fillers in front of the room's own surfaces -- and a wedge of four surfaces,
 each with a receiver that ends every ray and a twin: two plates of one frame and one size, a partial mirror at the lower index and
@@ -34,15 +37,15 @@ import shade_cases as sc
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_RAYS, REPS, SEED, E_MIN_SHARE = sc.N_RAYS, sc.REPS, sc.SEED, sc.E_MIN_SHARE
 KiB = 1024
-LIMIT_LDS = 150 * KiB               # stream_form_fresh, stream_form_bounce: `lds_need(...) <= 150 * 1024`
-LIMIT_LIST = 65536                  # stream_form_fresh: `n_list < 65536`
-LIMIT_RECS = 40 * KiB               # stream_form_general: `b_recs <= 40 * 1024`
-LDS_MAX_ALLOWED = 160 * KiB - 512   # csrc/trc_kernels.hip
-SMALL_SURFACES, TINY_SURFACES = 24, 4           # STREAM_SMALL_SURFACES; stream_choose_forms: `F.small_scene && S <= 4`
+LIMIT_LDS = 150 * KiB               # trc_stream_form_fresh, trc_stream_form_bounce: `lds_need(...) <= 150 * 1024`
+LIMIT_LIST = 65536                  # trc_stream_form_fresh: `n_list < 65536`
+LIMIT_RECS = 40 * KiB               # trc_stream_form_general: `b_recs <= 40 * 1024`
+LDS_MAX_ALLOWED = 160 * KiB - 512   # csrc/trc_forms.h
+SMALL_SURFACES, TINY_SURFACES = 24, 4           # STREAM_SMALL_SURFACES; trc_stream_decide: STREAM_TINY_SURFACES
 FP_CELLS = 512                      # stream_fp_prepare: M of a scene of at most 4096 surfaces
 SFQ_CAP, SBC_CELLS, SBC_PAIRS, LDS_SLACK, OBB_LSTRIDE = 128, 4, 256, 16, 20         # csrc/trc_bounds.h
 SBC_WAVE_BYTES = 2 * SBC_CELLS * 64 * 4 + 64 * 4 + SBC_PAIRS * 4 + 64 * 8 + 64 * 4
-SB_THREADS, SW_THREADS, SW_LEAFCAP = 1024, 256, 16                                  # csrc/trc_stream.inc
+SB_THREADS, SW_THREADS, SW_LEAFCAP = 1024, 256, 16                                  # csrc/trc_forms.h
 SRC_KIND = {'disk': 0, 'rect': 1, 'buie': 2, 'rbuie': 3, 'sun': 7, 'rsun': 8}      # trc_source_kind of the sources below
 CSR = 0.3
 PILLBOX_CONE = 0.02                 # half angle of the pillbox sources, rad
@@ -124,6 +127,122 @@ def hostcheck():
     hs.hs_sunshape_pack.argtypes = [C.c_int, _p, _p, _p, _p, _p]
     hs.hs_sunshape_rays.argtypes = [C.c_void_p, _p, C.c_int, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_long] + [_p] * 6
     return hc, hs
+
+
+# -- the library's choice of kernel instances (csrc/trc_forms.h), through the check library -----------------------------------------
+# A fact block: what the choice reads -- of the scene, of the call, of the footprint map, of the knobs -- in the order hostcheck.cpp
+# takes it (hc_facts_of).  forms() here, shade_cases.shade_forms() / absorb_forms() and mega_cases.plan() / engine() / ordered() restate
+# the choice from such a block; library_decide() is what the header itself makes of it, and test_*_cases_host.py hold the two together.
+FACT_KEYS = ('n_surf', 'stride', 'accel_ok', 'accel_kd_ok', 'has_kd', 'kd_nodes', 'kd_nleaf', 'kd_nalways', 'kd_depth', 'grid_ok', 'big_ok',
+             'grid_cells', 'grid_list', 'brute_list', 'n_unbounded', 'big_occ_words', 'n_fm_edges', 'fms_bytes', 'n_extra', 'fm_bins', 'chart',
+             'transfer', 'splits', 'all_flat', 'simple', 'cls_moving', 'cls_all', 'any_term',
+             'n', 'flags', 'src_kind', 'spec', 'carry', 'mat_dev', 'term_ok',
+             'fp_use', 'fp_n_list', 'fp_M', 'fp_Mc', 'fp_has_generic', 'fp_cdf_end', 'fp_coverage', 'fp_ucoverage', 'fp_umask_words', 'fp_Mu', 'fp_Mv',
+             'k_search', 'k_fresh', 'k_bounce', 'k_first', 'k_coop', 'k_absorb', 'k_umask')
+TRACE_ACCEL, TRACE_STREAM, TRACE_MEGAKERNEL = 1, 4, 8          # include/tracer_amd.h
+ENGINE_KEYS = ('use_stream', 'refused', 'engine_mode')
+MEGA_KEYS = ('m32', 'mega_threads', 'mega_lds', 'mega_lds_tally', 'mega_lds_scene')
+PLAN_KEYS = ('plan_ok', 'mode', 'lds_walk', 'walk_ok', 'decided')
+FORM_KEYS = ('src_kind', 'gridm', 'small_scene', 'n_shk', 'multi', 'cull_lu', 'cull_lv', 'ulisted_share', 'coop', 'use_fp', 'use_fused', 'use_first',
+             'use_absorb', 'absorb_inline', 'lds_inline', 'general_share', 'listed_share', 'search', 'lds_recs', 'lds_tally', 'lds_tables', 'lds_extra',
+             'lds_fm_bins', 'bg_occ_words', 'shade_term_cls', 'split_terminal')
+STAGES = ('gen0', 'gen', 'walk', 'exact', 'cull', 'cull_u', 'fresh', 'fresh_one', 'bounce', 'first', 'absorb')
+NO_STAGE = (None, 0, 0)             # (kernel name, threads, bytes of dynamic LDS) of a stage the call does not have
+FLOAT_KEYS = ('ulisted_share', 'general_share', 'listed_share')
+
+
+def blank_facts(**kw):
+    """a fact block of a scene with its boxes built, no tree, no grid, no map, given rays and the knobs unset"""
+    f = dict((k, 0) for k in FACT_KEYS)
+    f.update(accel_ok=1, src_kind=-1, term_ok=1, k_search=2, k_fresh=1, k_bounce=1, k_coop=1, k_absorb=-1, k_umask=1)
+    f.update(kw)
+    return f
+
+
+def kd_desc(f):
+    """the flattened tree as the check library takes it (the arrays stay with `f`)"""
+    from tracer_amd import _cabi
+    kd = _cabi.KdTreeDesc()
+    kd.n_nodes, kd.n_leaf_surfs, kd.n_always = len(f['flag']), len(f['leaf_surfs']), len(f['always_relevant'])
+    i32 = C.POINTER(C.c_int32)
+    for k in ('flag', 'child', 'leaf_off', 'leaf_cnt', 'leaf_surfs', 'always_relevant'):
+        setattr(kd, k, f[k].ctypes.data_as(i32))
+    kd.split = _ptr(f['split'])
+    for k in range(6):
+        kd.bounds[k] = f['bounds'][k]
+    return kd
+
+
+def scene_facts(cs, kd=None, desc=None, edges=None, chart=False, force32=False):
+    """the fact block of a compiled scene as the library gathers it (hc_scene_facts: trc_scene_facts_fill on the structures of
+    trc_scene_create, the tree `kd` flattened, the footprint map of the descriptor `desc`), with the flux maps `edges` = {surface: (u
+    edges, v edges)}; the call and the knobs are left blank"""
+    f = blank_facts()
+    v = N.array([float(f[k]) for k in FACT_KEYS])
+    hc = hostcheck()[0]
+    d = resolved(desc) if desc is not None else None
+    assert hc.hc_scene_facts(cs.n_surf, cs.descs, C.byref(kd_desc(kd)) if kd is not None else None, C.byref(d) if d is not None else None,
+                             FP_CELLS, int(force32), _ptr(v)) == 0
+    f = dict((k, (float(x) if k.startswith('fp_c') or k == 'fp_ucoverage' else int(x))) for k, x in zip(FACT_KEYS, v))
+    edges = edges or {}
+    f.update(n_fm_edges=sum(len(u) + len(w) for u, w in edges.values()), fms_bytes=len(edges) * sc.SIZEOF_FLUXMAPDEV, n_extra=len(cs.extra),
+             fm_bins=sum((len(u) - 1) * (len(w) - 1) for u, w in edges.values()), chart=int(chart))
+    return f
+
+
+_NAMES = {}
+
+
+def kernel_name(ident):
+    """trc_kernel_name of (family, five arguments); None: no kernel"""
+    ident = tuple(int(x) for x in ident)
+    if ident not in _NAMES:
+        buf = C.create_string_buffer(96)
+        n = hostcheck()[0].hc_kernel_name((C.c_int * 6)(*ident), buf, 96)
+        assert 0 <= n < 96
+        _NAMES[ident] = buf.value.decode() or None
+    return _NAMES[ident]
+
+
+def library_decide(blocks):
+    """every decision of trc_forms.h for the fact blocks: per block a dict of ENGINE_KEYS, MEGA_KEYS + 'mega', 'ord_mode', 'ord', PLAN_KEYS and,
+    where 'decided', FORM_KEYS, the STAGES as (kernel name, threads, LDS bytes) and 'shk': per shading kernel (name, threads, LDS bytes,
+    class, tables in LDS, bins in LDS)"""
+    hc = hostcheck()[0]
+    rows = N.ascontiguousarray([[float(b[k]) for k in FACT_KEYS] for b in blocks])
+    per = 3 + 11 + 7 + 5 + len(FORM_KEYS) + 8 * len(STAGES) + 3 * 11
+    out = N.zeros((len(rows), per))
+    assert hc.hc_forms_decide(C.c_long(len(rows)), _ptr(rows), _ptr(out)) == per
+    res = []
+    for r in out:
+        it = iter(r)
+        take = lambda n: [next(it) for _ in range(n)]
+        num = lambda keys: dict((k, (v if k in FLOAT_KEYS else int(v))) for k, v in zip(keys, take(len(keys))))
+        d = num(ENGINE_KEYS)
+        d.update(num(MEGA_KEYS))
+        d['mega'] = kernel_name(take(6))
+        d.update(num(('ord_mode',)))
+        d['ord'] = kernel_name(take(6))
+        d.update(num(PLAN_KEYS))
+        if d['decided']:
+            d.update(num(FORM_KEYS))
+            for st in STAGES:
+                d[st] = (kernel_name(take(6)),) + tuple(int(x) for x in take(2))
+            shk = [(kernel_name(take(6)),) + tuple(int(x) for x in take(5)) for _ in range(3)]
+            d['shk'] = shk[:d['n_shk']]
+            assert all(x == (None, 0, 0, 0, 0, 0) for x in shk[d['n_shk']:])
+        res.append(d)
+    return res
+
+
+def library_ids(ints=(-1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 128, 256, 512, 1024)):
+    """the names of every kernel id trc_forms.h can produce (trc_kernel_id_valid), integer arguments tried over `ints`"""
+    hc = hostcheck()[0]
+    cap = 4096
+    out = (C.c_int * (6 * cap))()
+    n = hc.hc_kernel_ids((C.c_int * len(ints))(*ints), len(ints), out, cap)
+    assert 0 < n <= cap
+    return [kernel_name(out[6 * i:6 * i + 6]) for i in range(n)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -290,6 +409,11 @@ class Scene(object):
         return dict((k, (float(v) if k in ('coverage', 'cdf_end') else int(v))) for k, v in zip(keys, out))
 
     @functools.lru_cache(maxsize=None)
+    def facts(self, src, kd=False, force32=False):
+        """scene_facts of the scene with its flux map, the source (None: no source) and its Kd-tree (kd): nobody changes it"""
+        return scene_facts(self.cs, self.kdtree().flat() if kd else None, self.desc(src) if src else None, self.edges, force32=force32)
+
+    @functools.lru_cache(maxsize=None)
     def kdtree(self):
         from tracer_amd.accel_tree import KdTree
         builder, kind, n_fill = SCENES[self.name]
@@ -442,83 +566,129 @@ FAMILIES = ('k_s_cull', 'k_s_fresh', 'k_s_fresh2', 'k_s_bounce', 'k_s_bounce_coo
 
 
 # -- the choice of kernels restated ---------------------------------------------------------------------------------------------------
-def forms(call):
-    """
-    stream_plan, stream_choose_forms, stream_form_fresh and stream_form_bounce restated for a call: a dict of the decisions (mode,
-    walk_ok, small_scene, gridm, use_fp, fresh_two, fresh_in_lds, use_fused, use_first, in_lds, coop, sun, general_share, listed_share,
-    lds_recs) with the byte sums behind the two fits-in-LDS decisions (need_fresh, need_bounce) and the kernel names
-    """
+def facts(call):
+    """the fact block of a call: the scene and the footprint map as the library gathers them (scene_facts), the call and the knobs as the test makes it (the streaming engine forced: a call of N_RAYS rays)"""
     s = scene(call.scene)
     env, senv = dict(call.env), dict(call.scene_env)
-    S, stride = s.cs.n_surf, s.stride
     src = None if call.given else call.src
-    q = s.sizes(src)
-    K = dict(search=int(env.get('TRC_STREAM_SEARCH', 2)), fresh=int(env.get('TRC_STREAM_FRESH', 1)) != 0, bounce=int(env.get('TRC_STREAM_BOUNCE', 1)) != 0,
-             first=int(env.get('TRC_STREAM_FIRST', 0)) != 0, coop=int(env.get('TRC_STREAM_COOP', 1)) != 0)
-    grid_ok = q['grid_ok'] and not int(senv.get('TRC_GRID_FORCE32', 0))          # trc_scene_create
-    assert q['unbounded'] == 0
-    f = {}
+    f = dict(s.facts(src, call.kd, bool(int(senv.get('TRC_GRID_FORCE32', 0)))))
+    f.update(n=N_RAYS, flags=TRACE_STREAM | (TRACE_ACCEL if call.accel else 0), src_kind=SRC_KIND[call.src] if src else -1,
+             term_ok=int(s.min_energy(call.src) >= 0.))
+    f.update(k_search=int(env.get('TRC_STREAM_SEARCH', 2)), k_fresh=int(int(env.get('TRC_STREAM_FRESH', 1)) != 0),
+             k_bounce=int(int(env.get('TRC_STREAM_BOUNCE', 1)) != 0), k_first=int(int(env.get('TRC_STREAM_FIRST', 0)) != 0),
+             k_coop=int(int(env.get('TRC_STREAM_COOP', 1)) != 0), k_absorb=int(env.get('TRC_STREAM_ABSORB', -1)),
+             k_umask=int(int(env.get('TRC_STREAM_UMASK', 1)) != 0))
+    if not f['k_fresh']:            # stream_fp_prepare: TRC_STREAM_FRESH=0 makes no map
+        f.update((k, 0) for k in FACT_KEYS if k.startswith('fp_'))
+    return f
+
+
+BUIE_BYTES = 9472                   # sizeof(trc_buie_fast) (csrc/trc_core.h); hc_search_sizes reports it, test_search_cases_host.py compares
+SC_THREADS, SC_GEN_CAP = 512, 1024  # csrc/trc_forms.h: k_s_cull's threads, the general-path rays its workgroup collects
+OCC_COOP, OCC_LANES = 80 * KiB, 96 * KiB        # ... the occupancy bits of the large grid in LDS, beside k_s_bounce_coop's blocks / in k_s_bounce<2>
+
+
+def forms(f):
+    """
+    stream_plan and the search stages of trc_stream_decide (csrc/trc_forms.h: general, fresh, bounce) restated for a fact block: a dict
+    of the decisions -- PLAN_KEYS without 'decided', the FORM_KEYS they set, the STAGES but 'absorb' as (kernel name, threads, LDS bytes)
+    -- with the byte sums behind the two fits-in-LDS decisions (need_fresh, need_bounce) and what predict() reads beside them (grid,
+    kind, fresh_two, fresh_in_lds, in_lds, sun).  Only 'plan_ok' where the scene has no streaming form.
+    """
+    S, stride = f['n_surf'], f['stride']
+    d = {}
     # stream_plan
-    waves = (SW_THREADS // 64)
+    waves = SW_THREADS // 64
 
     def walk_lds(mode):
         depth = 1
         if mode == 1:
-            kd = s.kdtree().flat()
-            shared = 6 * S * 4 + 2 * len(kd['flag']) * 4 + len(kd['leaf_surfs']) * 2 + 32
-            depth = max(kd_depth(kd), 1)
+            shared = 6 * S * 4 + 2 * f['kd_nodes'] * 4 + f['kd_nleaf'] * 2 + 32
+            depth = max(f['kd_depth'], 1)
         elif mode == 2:
-            shared = 6 * S * 4 + (q['grid_cells'] + 1 + 2 + q['grid_list']) * 2 + 32
+            shared = 6 * S * 4 + (f['grid_cells'] + 1 + 2 + f['grid_list']) * 2 + 32
         else:
-            shared = 6 * S * 4 + 8 + q['brute_list'] * 2 + 32
+            shared = 6 * S * 4 + 8 + f['brute_list'] * 2 + 32
         return shared + waves * (depth * 64 * 4 + SW_LEAFCAP * 64 * 2 + 64 * 4)
     mode = 0
-    if call.accel:
-        kd_fits = call.kd and S <= 65535 and walk_lds(1) <= LDS_MAX_ALLOWED
-        mode = 1 if K['search'] == 1 and kd_fits else 2 if grid_ok else 3 if q['big_ok'] else 1 if kd_fits else 0
-    f['mode'] = mode
-    f['walk_ok'] = walk_ok = mode != 3 and walk_lds(mode) <= LDS_MAX_ALLOWED
-    # stream_choose_forms
+    if f['accel_ok'] and f['flags'] & TRACE_ACCEL:
+        kd_fits = f['accel_kd_ok'] and S <= 65535 and walk_lds(1) <= LDS_MAX_ALLOWED
+        mode = 1 if f['k_search'] == 1 and kd_fits else 2 if f['grid_ok'] else 3 if f['big_ok'] else 1 if kd_fits else 0
+    d['plan_ok'] = int(bool(f['accel_ok']) and not (mode == 0 and S > 65535))
+    if not d['plan_ok']:
+        return d
+    d['mode'] = mode
+    walk_ok = mode != 3 and walk_lds(mode) <= LDS_MAX_ALLOWED
+    d['walk_ok'] = int(walk_ok)
+    d['lds_walk'] = walk_lds(mode) if walk_ok else 0
+    # trc_stream_decide
     gridm = 1 if mode == 2 else 2 if mode == 3 else 0
-    f['small_scene'] = small = S <= SMALL_SURFACES and mode != 1 and walk_ok
+    small = S <= SMALL_SURFACES and mode != 1 and walk_ok
+    d['small_scene'] = int(small)
     if small and S <= TINY_SURFACES:
         gridm = 3
-    f['gridm'] = gridm
-    f['lds_recs'] = S * stride * 8 <= LIMIT_RECS            # stream_form_general
-    f['grid'] = mode == 2                                   # ... k_s_walk<256, GRID>
-    # stream_form_fresh (stream_fp_prepare: a map for a descriptor source unless TRC_STREAM_FRESH=0)
-    kind = SRC_KIND[call.src] if src else -1
-    f['kind'] = kind
-    f['use_fp'] = use_fp = bool(src) and K['fresh'] and q['fp_ok'] == 1
-    f['general_share'], f['listed_share'] = 0., 1.
-    if use_fp:
+    d['gridm'] = gridm
+    d['search'] = mode if walk_ok else 2
+    # the general path
+    kind = d['src_kind'] = d['kind'] = f['src_kind']
+    recs = S * stride * 8
+    d['lds_recs'] = int(0 < recs <= LIMIT_RECS)
+    d['grid'] = mode == 2                                   # ... k_s_walk<256, GRID>
+    d['gen0'] = ({2: 'k_s_gen_src<2>', 3: 'k_s_gen<true, 3>', 0: 'k_s_gen_src<0>', 1: 'k_s_gen_src<1>', 7: 'k_s_gen<true, 7>',
+                  8: 'k_s_gen<true, 8>'}.get(kind, 'k_s_gen<true, -1>'), 256, 0)
+    d['gen'] = ('k_s_gen<false, -1>', 256, 0)
+    d['walk'] = ('k_s_walk<256, %s>' % _t(d['grid']), SW_THREADS, d['lds_walk'])
+    d['exact'] = ('k_s_exact', 256, recs if d['lds_recs'] else 0)
+    # the footprint route
+    flat = bool(f['all_flat'])
+    d['use_fp'] = int(bool(f['fp_use']))
+    d['general_share'], d['listed_share'], d['ulisted_share'] = 0., 1., 0.
+    d['cull_lu'] = d['cull_lv'] = 0
+    d['cull'] = d['cull_u'] = d['fresh'] = d['fresh_one'] = NO_STAGE
+    if d['use_fp']:
         buie = kind in (2, 3)
-        f['fresh_two'] = buie
-        qw = ((1024 if s.flat else 768) // 64) if buie else 0          # SF_THREADS(flat) / 64
-        bb = q['buie_bytes'] if buie else 0
-        f['need_fresh'] = lds_need(fresh_lds_parts(S, stride, q['Mc'], q['n_list'], bb, True, qw))
-        f['fresh_in_lds'] = q['n_list'] < LIMIT_LIST and f['need_fresh'] <= LIMIT_LDS
-        request = lds_need(fresh_lds_parts(S, stride, q['Mc'], q['n_list'], bb, f['fresh_in_lds'], qw)) + 16
-        assert request <= LDS_MAX_ALLOWED and FP_CELLS * FP_CELLS // 8 + (1024 + 4) * 4 <= LDS_MAX_ALLOWED
-        f['general_share'] = max(1. - q['cdf_end'], 0.) if q['has_generic'] else 0.
-        f['listed_share'] = min(q['coverage'] * (4. / N.pi if kind in (0, 2, 7) else 1.), 1.)
-        args = (kind, _t(s.flat), _t(f['fresh_in_lds']))
-        f['cull'] = 'k_s_cull<%d>' % kind
-        f['fresh_one'] = 'k_s_fresh<%d, %s, %s>' % args
-        f['fresh'] = 'k_s_fresh2<%d, %s, %s>' % args if buie else f['fresh_one']
-    # stream_form_bounce
+        threads = 1024 if flat else 768                     # SF_THREADS(flat)
+        qw = threads // 64 if buie else 0
+        bb = BUIE_BYTES if buie else 0
+        d['need_fresh'] = lds_need(fresh_lds_parts(S, stride, f['fp_Mc'], f['fp_n_list'], bb, True, qw))
+        in_lds = f['fp_n_list'] < LIMIT_LIST and d['need_fresh'] <= LIMIT_LDS
+        request = lds_need(fresh_lds_parts(S, stride, f['fp_Mc'], f['fp_n_list'], bb, in_lds, qw)) + 16
+        lds_cull = f['fp_M'] * f['fp_M'] // 8 + (SC_GEN_CAP + 4) * 4
+        if lds_cull > LDS_MAX_ALLOWED or request > LDS_MAX_ALLOWED:
+            d['use_fp'] = 0
+        else:
+            d['fresh_two'], d['fresh_in_lds'] = buie, in_lds
+            d['general_share'] = max(1. - f['fp_cdf_end'], 0.) if f['fp_has_generic'] else 0.
+            d['listed_share'] = min(f['fp_coverage'] * (4. / N.pi if kind in (0, 2, 7) else 1.), 1.)
+            d['ulisted_share'] = 1.
+            args = (kind, _t(flat), _t(in_lds))
+            d['cull'] = ('k_s_cull<%d>' % kind, SC_THREADS, lds_cull)
+            d['fresh_one'] = ('k_s_fresh<%d, %s, %s>' % args, threads, request)
+            d['fresh'] = ('k_s_fresh2<%d, %s, %s>' % args, threads, request) if buie else d['fresh_one']
+            if buie and (flat or in_lds) and f['k_umask'] and f['fp_umask_words'] > 0:      # SF2_DERIVES_CELL
+                d['cull_u'] = ('k_s_ucull<%d>' % kind, SC_THREADS, f['fp_umask_words'] * 4 + (SC_GEN_CAP + 4) * 4)
+                d['cull_lu'], d['cull_lv'] = [max(int(m) - 1, 0).bit_length() for m in (f['fp_Mu'], f['fp_Mv'])]
+                d['ulisted_share'] = min(f['fp_ucoverage'], 1.)
+    # k_s_bounce
     big = not walk_ok
-    f['use_fused'] = mode != 1 and (K['bounce'] or big)
-    f['use_first'] = big or small or (K['first'] and mode != 1)
-    if f['use_fused'] or f['use_first']:
-        g_cells = q['grid_cells'] if mode == 2 else 0
-        f['need_bounce'] = lds_need(bounce_lds_parts(S, stride, q['buie_bytes'], True, True, g_cells, q['grid_list'], 0, 0))
-        f['in_lds'] = in_lds = gridm not in (2, 3) and f['need_bounce'] <= LIMIT_LDS
-        f['coop'] = coop = gridm == 2 and K['coop']
-        f['sun'] = sun = kind in (7, 8)
-        f['bounce'] = _coop(False, s.flat, False) if coop else _bounce(gridm, in_lds, False, s.flat, False)
-        f['first'] = _coop(True, s.flat, sun) if coop else _bounce(gridm, in_lds, True, False, sun)
-    return f
+    d['use_fused'] = int(mode != 1 and bool(f['k_bounce'] or big))
+    d['use_first'] = int(big or small or bool(f['k_first'] and mode != 1))
+    d['coop'], d['bg_occ_words'] = 0, 0
+    d['bounce'] = d['first'] = NO_STAGE
+    if d['use_fused'] or d['use_first']:
+        g_cells = f['grid_cells'] if mode == 2 else 0
+        d['need_bounce'] = lds_need(bounce_lds_parts(S, stride, BUIE_BYTES, True, True, g_cells, f['grid_list'], 0, 0))
+        d['in_lds'] = in_lds = gridm not in (2, 3) and d['need_bounce'] <= LIMIT_LDS
+        coop = gridm == 2 and bool(f['k_coop'])
+        d['coop'] = int(coop)
+        if gridm == 2 and f['big_occ_words'] * 4 <= (OCC_COOP if coop else OCC_LANES):
+            d['bg_occ_words'] = f['big_occ_words']
+        d['sun'] = sun = kind in (7, 8)
+        request = lambda bb: lds_need(bounce_lds_parts(S, stride, bb, in_lds, in_lds, g_cells if in_lds else 0, f['grid_list'], d['bg_occ_words'],
+                                                       SB_THREADS // 64 if coop else 0)) + 16
+        d['bounce'] = (_coop(False, flat, False) if coop else _bounce(gridm, in_lds, False, flat, False), SB_THREADS, request(0))
+        d['first'] = (_coop(True, flat, sun) if coop else _bounce(gridm, in_lds, True, False, sun), SB_THREADS, request(BUIE_BYTES))
+    return d
 
 
 
@@ -535,7 +705,7 @@ def kd_depth(kd):
 def predict(call):
     """{search-stage kernel as a kernel trace names it: launches} of a call (a second call: of the two), from forms(), the per-bounce
     choice of plan_bounce / launch_bounce, and the reference's rays alive at every bounce"""
-    f = forms(call)
+    f = forms(facts(call))
     o = reference(call)
     # bounces run: b = 0, then one more while rays are alive and b + 1 < reps (advance)
     n_bounces = 1
@@ -544,8 +714,6 @@ def predict(call):
             break
         n_bounces += 1
     out = collections.Counter()
-    gen0 = {2: 'k_s_gen_src<2>', 3: 'k_s_gen<true, 3>', 0: 'k_s_gen_src<0>', 1: 'k_s_gen_src<1>', 7: 'k_s_gen<true, 7>', 8: 'k_s_gen<true, 8>',
-            -1: 'k_s_gen<true, -1>'}[f['kind']]
     hit_rate = 0.
     for turn in range(2 if call.second else 1):
         for b in range(n_bounces):
@@ -555,16 +723,15 @@ def predict(call):
             general = not fused and not first and (not fresh or f['general_share'] > 0.)
             if fresh:
                 mostly_hits = hit_rate > 0. and hit_rate > 0.6 * 1.15 * f['listed_share']
-                out[f['cull']] += 1
-                out[f['fresh_one'] if mostly_hits else f['fresh']] += 1
+                out[f['cull'][0]] += 1
+                out[(f['fresh_one'] if mostly_hits else f['fresh'])[0]] += 1
             if fused:
-                out[f['bounce']] += 1
+                out[f['bounce'][0]] += 1
             if first:
-                out[f['first']] += 1
+                out[f['first'][0]] += 1
             if general:
-                out[gen0 if b == 0 else 'k_s_gen<false, -1>'] += 1
-                out['k_s_walk<256, %s>' % _t(f['grid'])] += 1
-                out['k_s_exact'] += 1
+                for stage in ('gen0' if b == 0 else 'gen', 'walk', 'exact'):
+                    out[f[stage][0]] += 1
         if f['use_fp']:         # advance: what the next call on the scene expects of the listed rays
             hit_rate = 1.15 * len(o['levels'][1]['surf']) / float(N_RAYS) + 256. / N_RAYS
     return dict(out)

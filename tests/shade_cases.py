@@ -2,7 +2,7 @@
 Scenes that select every shading kernel instance of the streaming engine, and their host reference (test_shade_cases_host.py for what
 can be said without a device, test_gpu_shade_instances.py on one).
 
-stream_form_shade (csrc/trc_stream.inc) picks, per launch, one of
+trc_stream_form_shade (csrc/trc_forms.h) picks, per launch, one of
 
   k_s_shade_c<CLS, FLATN, LDS, SPEC>   CLS 0 mirror / 1 diffuse: the lean kernels of a scene traced without carried columns
   k_s_shade<SIMPLE, 2, LDS, SPEC>      the general class of such a scene
@@ -18,6 +18,11 @@ intended side of its limit:
   k_s_shade         72 KiB, n_extra counted: a long Reflective_spectral table crosses it with the lean kernels still in LDS; its SIMPLE
                     instances admit no optics table (no kind of TRC_OPT_SIMPLE_MASK has one), so fillers again
   k_s_shade_x       72 KiB, the table again
+
+predict() keeps the sums as they were first written; shade_forms() / absorb_forms() restate the shading and terminal stages of
+trc_stream_decide (csrc/trc_forms.h) for a fact block (search_cases.FACT_KEYS), and test_shade_cases_host.py holds both to the
+header's own decisions, which the check library exports (search_cases.library_decide): field by field for every case, the instance
+names included.  The cases spell an instance without the CHART / SPLIT / MAT arguments added since (short_name).
 
 Every case has one flux map (on a Lambertian floor tile, lean capture) and a second capturing surface (a mirror wall, full capture);
 no surface absorbs everything, so that every hit goes through a shading kernel and none through k_s_absorb / k_s_bounce's finish.
@@ -36,7 +41,7 @@ SEED = 20251
 E_MIN_SHARE = 0.1137        # min_energy as a share of a source ray's energy (no product of the room's reflectances): culls from the second hit on, leaves survivors
 
 KiB = 1024
-LIMIT_LEAN, LIMIT_LEAN_BINS = 120 * KiB, 150 * KiB          # stream_form_shade: `need <= 120 * 1024`, `K.lds + bins * 8 + 16 <= 150 * 1024`
+LIMIT_LEAN, LIMIT_LEAN_BINS = 120 * KiB, 150 * KiB          # trc_stream_form_shade: `need <= 120 * 1024`, `K.lds + bins * 8 + 16 <= 150 * 1024`
 LIMIT_SHADE, LIMIT_SHADE_BINS = 72 * KiB, 78 * KiB          # ... `all <= 72 * 1024`, `lds_shade + bins * 8 + 16 <= 78 * 1024`
 
 # trc_gm_nparams (csrc/trc_core.h) of the geometry kinds the room uses, by _cabi.GM_* name
@@ -48,7 +53,7 @@ FLAT_KINDS = ('GM_FLAT_INF', 'GM_RECT', 'GM_RECT_EXTRUDED', 'GM_RECT_PERFORATED'
 MIRROR_KINDS = ('OPT_TRANSPARENT', 'OPT_REFLECTIVE', 'OPT_ONE_SIDED_REFLECTIVE', 'OPT_REAL_REFLECTIVE', 'OPT_ONE_SIDED_REAL_REFLECTIVE')
 DIFFUSE_KINDS = ('OPT_LAMBERTIAN', 'OPT_LAMBERTIAN_SPECULAR', 'OPT_SEMI_LAMBERTIAN', 'OPT_REFLECTIVE_SPECTRAL', 'OPT_LAMBERTIAN_DIRECTIONAL',
                  'OPT_LAMBERTIAN_DIRECTIONAL_SPECTRAL', 'OPT_FRESNEL_CONDUCTOR')
-SIMPLE_KINDS = MIRROR_KINDS + ('OPT_LAMBERTIAN', 'OPT_LAMBERTIAN_SPECULAR')        # TRC_OPT_SIMPLE_MASK (csrc/trc_device.h)
+SIMPLE_KINDS = MIRROR_KINDS + ('OPT_LAMBERTIAN', 'OPT_LAMBERTIAN_SPECULAR')        # TRC_OPT_SIMPLE_MASK (csrc/trc_forms.h)
 CLS_MIRROR, CLS_DIFFUSE, CLS_GENERAL = 0, 1, 2
 
 MAP_TILE, FULL_WALL = 0, 4          # places among the room's own surfaces (behind the fillers): the mapped tile, the wall captured in full
@@ -67,7 +72,7 @@ def _names(prefix):
     return dict((getattr(K, k), k) for k in dir(K) if k.startswith(prefix) and isinstance(getattr(K, k), int))
 
 
-# -- the sums of stream_form_shade ------------------------------------------------------------------------------------------------
+# -- the sums of trc_stream_form_shade ------------------------------------------------------------------------------------------------
 def record_stride(cs):
     """doubles per surface record (trc_scene_create): TRC_REC_HDR + the parameters of the widest geometry kind, made odd"""
     gm = _names('GM_')
@@ -75,7 +80,7 @@ def record_stride(cs):
 
 
 def shade_class_of(desc):
-    """trc_shade_class_of (csrc/trc_device.h)"""
+    """trc_shade_class_of (csrc/trc_forms.h)"""
     K = _kinds()
     ok, o = desc.optics_kind, list(desc.opt)
     name = _names('OPT_').get(ok)
@@ -89,7 +94,7 @@ def shade_class_of(desc):
 
 
 def ends_every_ray(desc):
-    """surface_ends_every_ray (csrc/trc_kernels.hip)"""
+    """surface_ends_every_ray (csrc/trc_forms.h)"""
     K = _kinds()
     ok, o = desc.optics_kind, list(desc.opt)
     plain = (ok in (K.OPT_REFLECTIVE, K.OPT_ONE_SIDED_REFLECTIVE) and o[1] == 0.) or \
@@ -108,7 +113,7 @@ def table_bytes(cs, edges):
 
 
 def predict(cs, edges, spec, carry):
-    """stream_form_shade restated: {kernel instance as a kernel trace names it: (bytes summed, limit, tables in LDS, bins in LDS)} of the
+    """trc_stream_form_shade restated: {kernel instance as a kernel trace names it: (bytes summed, limit, tables in LDS, bins in LDS)} of the
     shading kernels a streaming call on the scene launches"""
     gm, opt = _names('GM_'), _names('OPT_')
     S = cs.n_surf
@@ -136,6 +141,87 @@ def predict(cs, edges, spec, carry):
     if CLS_GENERAL in present:
         out['k_s_shade<%s, 2, %s, %s>' % (t(simple), t(shade_lds), t(spec))] = (all_, LIMIT_SHADE, shade_lds, shade_bins)
     return out
+
+
+# -- the shading stage of trc_stream_decide (csrc/trc_forms.h) restated for a fact block (search_cases.FACT_KEYS) ----------------------
+IMG_SHADE, IMG_SHADE_X, IMG_LEAN, IMG_LEAN_MIRROR = range(4)            # enum trc_shade_img (csrc/trc_bounds.h)
+BARE = {IMG_SHADE: 8, IMG_SHADE_X: 16, IMG_LEAN: 16, IMG_LEAN_MIRROR: 16}         # a launch with nothing staged: the count words (k_s_shade keeps one)
+LIMIT_ABSORB, LIMIT_INLINE, INLINE_MARGIN = 78 * KiB, 158 * KiB, 64     # k_s_absorb's tables; k_s_bounce's LDS with them behind its own, and the margin between
+SHC_THREADS, SH_THREADS, SA_THREADS = 1024, 256, 1024                   # k_s_shade_c / k_s_shade_x, k_s_shade, k_s_absorb
+
+
+def fact_bytes(f):
+    """table_bytes of a fact block: (tallies, records, optics parameters, maps and flags) in bytes"""
+    S = f['n_surf']
+    return (3 * S + 2) * 8, S * f['stride'] * 8, 8 * S * 8, f['n_fm_edges'] * 8 + ((f['fms_bytes'] + 7) // 8) * 8 + 2 * S * 4 + 16
+
+
+def lds_choose(f, img):
+    """trc_shade_lds_choose: (tables in LDS, bins in LDS, bytes the launch asks for) of an image of the scene's tables"""
+    need = sum(fact_bytes(f)) + (0 if img == IMG_LEAN_MIRROR else f['n_extra'] * 8)
+    limit, limit_bins = (LIMIT_LEAN, LIMIT_LEAN_BINS) if img in (IMG_LEAN, IMG_LEAN_MIRROR) else (LIMIT_SHADE, LIMIT_SHADE_BINS)
+    bins = f['fm_bins']
+    in_lds = need <= limit
+    bins_in = bins > 0 and in_lds and need + bins * 8 + 16 <= limit_bins
+    return in_lds, bins if bins_in else 0, (need + (bins * 8 + 16 if bins_in else 0)) if in_lds else BARE[img]
+
+
+def shade_forms(f):
+    """
+    trc_stream_form_shade restated: dict(shk: per shading kernel of the call (kernel name with every template argument, threads, LDS
+    bytes, class or -1, tables in LDS, bins in LDS), n_shk, multi, lds_tally, lds_tables, lds_extra, lds_fm_bins, shade_term_cls); None:
+    no instance.  `carry` as the streaming engine takes it: with the calls on a scene whose optics split rays.
+    """
+    t = lambda x: 'true' if x else 'false'
+    carry, spec, chart = bool(f['carry'] or f['splits']), bool(f['spec']), bool(f['chart'])
+    in_lds, bins_in, request = lds_choose(f, IMG_SHADE_X if carry else IMG_SHADE)
+    d = dict(lds_tally=int(in_lds), lds_tables=int(in_lds), lds_extra=int(in_lds), lds_fm_bins=bins_in, shade_term_cls=-1)
+    shk = []
+    if carry:
+        if f['mat_dev'] and chart:
+            return None
+        shk.append(('k_s_shade_x<%s, %s, %s, %s>' % (t(in_lds), t(chart), t(f['splits']), t(f['mat_dev'])), SHC_THREADS, request, -1, int(in_lds), bins_in))
+    else:
+        present = f['cls_moving'] if f['term_ok'] else f['cls_all']
+        if f['term_ok'] and f['any_term']:
+            d['shade_term_cls'] = CLS_MIRROR if present & 1 else CLS_DIFFUSE if present & 2 else -1
+            if d['shade_term_cls'] < 0:
+                present = f['cls_all']
+        for c, img in ((CLS_MIRROR, IMG_LEAN_MIRROR), (CLS_DIFFUSE, IMG_LEAN)):
+            if present >> c & 1:
+                l, b, r = lds_choose(f, img)
+                shk.append(('k_s_shade_c<%d, %s, %s, %s, %s>' % (c, t(f['all_flat'] and not chart), t(l), t(spec), t(chart)), SHC_THREADS, r, c, int(l), b))
+        if present >> CLS_GENERAL & 1:
+            shk.append(('k_s_shade<%s, 2, %s, %s, %s>' % (t(f['simple'] and not chart), t(in_lds), t(spec), t(chart)), SH_THREADS, request, CLS_GENERAL,
+                        int(in_lds), bins_in))
+    d.update(shk=shk, n_shk=len(shk), multi=int(len(shk) > 1))
+    return d
+
+
+def absorb_forms(f, d):
+    """trc_stream_form_absorb restated, from the decisions `d` made so far (search_cases.forms, shade_forms): dict(use_absorb,
+    absorb_inline, lds_inline, split_terminal, absorb, bounce)"""
+    out = dict(use_absorb=0, absorb_inline=0, lds_inline=0, split_terminal=0, absorb=(None, 0, 0), bounce=d['bounce'])
+    if not (d['use_fused'] and d['lds_tables'] and not (f['carry'] or f['splits'])):
+        return out
+    t, r, o, m = fact_bytes(f)
+    lds_absorb = t + m + d['lds_fm_bins'] * 8 + 16
+    fm_ok = f['fm_bins'] == 0 or d['lds_fm_bins'] > 0
+    if not (f['any_term'] and fm_ok and not f['chart'] and lds_absorb <= LIMIT_ABSORB and not f['transfer'] and f['term_ok'] and f['k_absorb'] != 0):
+        return out
+    out.update(use_absorb=1, split_terminal=1, absorb=('k_s_absorb', SA_THREADS, lds_absorb))
+    extra = lds_absorb + INLINE_MARGIN
+    if f['k_absorb'] != 1 and not (d['gridm'] == 2 and d['coop']) and d['bounce'][2] + extra <= LIMIT_INLINE:
+        out.update(absorb_inline=1, lds_inline=extra, split_terminal=2, bounce=d['bounce'][:2] + (d['bounce'][2] + extra,))
+    return out
+
+
+def short_name(inst):
+    """a shading instance as the cases spell it: without the CHART argument of k_s_shade / k_s_shade_c and the CHART, SPLIT, MAT arguments of
+    k_s_shade_x, which every case holds at false (the 'carry-mat' rooms, whose materials are on the device: MAT true)"""
+    head, args = inst[:-1].split('<')
+    args = args.split(', ')
+    return '%s<%s>' % (head, ', '.join(args[:1] if head == 'k_s_shade_x' else args[:4]))
 
 
 ALL_INSTANCES = ['k_s_shade_c<%d, %s, %s, %s>' % (c, f, l, s) for c in (0, 1) for f in ('true', 'false') for l in ('true', 'false')
@@ -296,7 +382,7 @@ CURVED_GM = ('GM_SPHERE', 'GM_CYL_FINITE', 'GM_PARAB_DISH')
 
 
 class Case(object):
-    """a case built: compiled scene, frames, maps, source, and what stream_form_shade is predicted to pick for it"""
+    """a case built: compiled scene, frames, maps, source, and what trc_stream_form_shade is predicted to pick for it"""
     def __init__(self, name):
         from tracer_amd.scene import compile_scene
         self.name = name

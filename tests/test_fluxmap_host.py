@@ -38,7 +38,7 @@ def test_host_histograms_of_the_cavity_meet_the_conditions_on_the_inputs(regime)
 
 def test_regime_bins_against_the_byte_limits_of_the_streaming_engine():
     """The arithmetic of fluxmap_scene.FLOOR_BINS, so that a change of the maps there cannot move a case out of its regime unnoticed:
-    bins * 8 + 16 plus the tables against the 78 KiB and 150 KiB of stream_form_shade, restated here.  This says nothing about the
+    bins * 8 + 16 plus the tables against the 78 KiB and 150 KiB of trc_stream_form_shade, restated here.  This says nothing about the
     library: that the regimes are reached on the device is asserted there (test_gpu_fluxmap.py, from the launches the library
     reports).  The tables: below 8 KiB for seven surfaces (fluxmap_scene.py); the scene has no optics or geometry tables (n_extra = 0)."""
     from tracer_amd.scene import compile_scene

@@ -142,7 +142,7 @@ def test_maps_equal_the_host_histogram_of_the_hits(ctx, cavity, form, regime, gi
 def test_k_s_absorb_runs_in_the_small_regime_only(ctx, cavity):
     """What the library reports of the regimes: its launches.  With TRC_STREAM_ABSORB=1 the terminal hits are listed and k_s_absorb
     is launched to finish them, one launch more per bounce than with TRC_STREAM_ABSORB=0 -- as long as the bins are in LDS for
-    every kernel.  In the middle regime the knob changes nothing: k_s_absorb is switched off there (fm_ok, stream_form_absorb)."""
+    every kernel.  In the middle regime the knob changes nothing: k_s_absorb is switched off there (fm_ok, trc_stream_form_absorb)."""
     cs, T, frames = cavity
     n, seed = 200000, 11
     launches = {}

@@ -1,6 +1,6 @@
 """
 GPU tests of the persistent megakernel (k_trace_coop<512 | 256, SPEC, SUN, CHART>, k_trace_fast<256, SPEC, SUN, CHART>: 24 compiled
-kernels, one picked per call by mega_plan and mega_kernels), run with -m gpu on the MI355X box.
+kernels, one picked per call by mega_plan), run with -m gpu on the MI355X box.
 
 Every case of mega_cases.py -- a scene, a source or given rays, a Kd-tree or none, a chart map or none;
 test_mega_cases_host.py checks the selection, the branch the case is there for and the conditions on the inputs without a device --

@@ -1,6 +1,6 @@
 """
 GPU tests of the search kernel instances of the streaming engine (k_s_cull, k_s_fresh, k_s_fresh2, k_s_bounce, k_s_bounce_coop, k_s_walk,
-k_s_gen, k_s_gen_src, k_s_exact: 79 compiled kernels, picked per call by stream_plan and the stream_form_* functions), run with -m gpu
+k_s_gen, k_s_gen_src, k_s_exact: 79 compiled kernels, picked per call by stream_plan and the trc_stream_form_* functions), run with -m gpu
 on the MI355X box.
 
 Every call of search_cases.py -- a scene, a source or its rays given, accel, a Kd-tree, knobs, a first or a second call;

@@ -1,6 +1,6 @@
 """
 GPU tests of the shading kernel instances of the streaming engine (k_s_shade_c, k_s_shade, k_s_shade_x: 26 compiled kernels, one
-picked per launch by stream_form_shade), run with -m gpu on the MI355X box.
+picked per launch by trc_stream_form_shade), run with -m gpu on the MI355X box.
 
 Every case of shade_cases.py -- the smallest scene that selects its target instances; test_shade_cases_host.py checks the selection
 and the conditions on the inputs without a device -- is traced by the streaming form and compared with oracle.engine on the same

@@ -351,3 +351,125 @@ def test_tree_agrees_with_brute_force(name):
         assert N.array_equal(sb, hit), (name, 'oracle', N.nonzero(sb != hit)[0][:10])
         total += len(sb)
     assert total >= c.n
+
+
+# -- the library's choice of kernels (csrc/trc_forms.h) against the restated one ----------------------------------------------------
+def same_decisions(blocks):
+    """every decision of the header for the fact blocks equals M.decide's: field by field, LDS byte sums and kernel names included"""
+    for f, lib in zip(blocks, S.library_decide(blocks)):
+        mine = M.decide(f)
+        assert mine == lib, (sorted((k, mine.get(k), lib.get(k)) for k in set(mine) | set(lib) if mine.get(k) != lib.get(k)), f)
+
+
+def test_header_decides_every_case_as_restated():
+    """all cases, none left out: plan() and instance() are mega_plan of the library's own facts; and the target is the header's name"""
+    blocks = [c.facts() for c in M.CASES]
+    same_decisions(blocks)
+    for c, d in zip(M.CASES, S.library_decide(blocks)):
+        assert d['mega'] == c.target and not d['use_stream'], c.name
+    for depth, chart, kernel in M.ORDERED:          # the ordered engine under the row's chains: the instance of test_gpu_mega_instances
+        f = dict(M.CASE['row/chain25'].facts(), kd_depth=depth, chart=int(chart))
+        assert S.library_decide([f])[0]['ord'] == kernel[:-1] + ', false>' == M.ordered(f)[1]
+
+
+def test_header_names_every_instance():
+    """the ids the header can produce in the megakernel's families, over their argument ranges, are ALL_INSTANCES; k_ord_bounce's nine"""
+    names = S.library_ids()
+    assert len(names) == len(set(names))
+    assert sorted(n for n in names if n.split('<')[0] in M.FAMILIES) == sorted(M.ALL_INSTANCES)
+    assert sorted(n for n in names if n.startswith('k_ord_bounce<')) == sorted(
+        'k_ord_bounce<%d, %s, %s>' % (m, M._t(c), M._t(t)) for m in (0, 1, 2) for c, t in ((0, 0), (1, 0), (0, 1)))
+
+
+# every threshold of the choice: (name, the fact that is moved across it, its range, the decision that flips there, facts held fixed)
+_STREAM, _BIG = dict(flags=S.TRACE_ACCEL | S.TRACE_STREAM, n=5000), dict(grid_ok=0, big_ok=1)
+THRESHOLDS = [
+    ('fewest rays of a streaming call', 'n', (1, 200), 'use_stream', dict(flags=S.TRACE_STREAM)),
+    ('TRC_STREAM_MIN_RAYS', 'n', (64, 1 << 21), 'use_stream', dict(flags=S.TRACE_ACCEL, grid_ok=1)),
+    ('4096 rays on the large grid', 'n', (64, 1 << 21), 'use_stream', dict(_BIG, flags=S.TRACE_ACCEL)),
+    ('65535 surfaces, all boxes', 'n_surf', (60000, 70000), 'plan_ok', dict(flags=0)),
+    ('65535 surfaces, k_ord_bounce', 'n_surf', (60000, 70000), 'ord_mode', dict(flags=0)),
+    ('STREAM_SMALL_SURFACES', 'n_surf', (5, 60), 'small_scene', dict(_STREAM, grid_ok=1)),
+    ('four surfaces', 'n_surf', (1, 24), 'gridm', dict(_STREAM, grid_ok=1)),
+    ('40 KiB of records', 'n_surf', (1, 2000), 'lds_recs', dict(_STREAM, grid_ok=1)),
+    ('LDS_MAX_ALLOWED, k_s_walk on the grid', 'grid_list', (0, 100000), 'walk_ok', dict(_STREAM, grid_ok=1)),
+    ('LDS_MAX_ALLOWED, k_s_walk on all boxes', 'brute_list', (0, 100000), 'walk_ok', dict(_STREAM, flags=S.TRACE_STREAM)),
+    ('LDS_MAX_ALLOWED, k_s_walk on the tree', 'kd_nleaf', (0, 100000), 'mode', dict(_STREAM, has_kd=1, accel_kd_ok=1, k_search=1, grid_ok=1)),
+    ('150 KiB, k_s_bounce', 'grid_list', (0, 60000), 'bounce', dict(_STREAM, grid_ok=1, n_surf=30, grid_cells=500)),
+    ('150 KiB, k_s_fresh', 'fp_n_list', (0, 65000), 'fresh', dict(_STREAM, grid_ok=1, n_surf=30, src_kind=2, fp_use=1, fp_M=512, fp_Mc=128, fp_coverage=.5)),
+    ('65536 list entries, k_s_fresh', 'fp_n_list', (60000, 70000), 'fresh', dict(_STREAM, grid_ok=1, n_surf=5, src_kind=0, fp_use=1, fp_M=128, fp_Mc=32, fp_coverage=.5)),
+    ('LDS_MAX_ALLOWED, k_s_cull', 'fp_M', (32, 2048), 'use_fp', dict(_STREAM, grid_ok=1, n_surf=5, src_kind=0, fp_use=1, fp_Mc=8, fp_coverage=.5)),
+    ('80 KiB of occupancy bits', 'big_occ_words', (1, 40000), lambda d: d.get('bg_occ_words', 0) > 0, dict(_STREAM, accel_ok=1, **_BIG)),
+    ('96 KiB of occupancy bits', 'big_occ_words', (1, 40000), lambda d: d.get('bg_occ_words', 0) > 0, dict(_STREAM, accel_ok=1, k_coop=0, **_BIG)),
+    ('LDS_MAX_ALLOWED, k_trace_coop<512>', 'brute_list', (0, 100000), 'mega_threads', dict(flags=0)),
+    ('LDS_MAX_ALLOWED, k_trace_coop<256>', 'brute_list', (40000, 100000), 'm32', dict(flags=0)),
+    ('COOP_MAX_NODES', 'kd_nodes', (1, 20000), 'm32', dict(flags=S.TRACE_ACCEL, has_kd=1, accel_kd_ok=1, n_surf=2, kd_depth=1)),
+    ('COOP_MAX_DEPTH', 'kd_depth', (1, 40), 'm32', dict(flags=S.TRACE_ACCEL, has_kd=1, accel_kd_ok=1, kd_nodes=31)),
+    ('ORD_STACK_DEPTH', 'kd_depth', (1, 40), 'ord_mode', dict(flags=S.TRACE_ACCEL, has_kd=1, accel_kd_ok=1, kd_nodes=31)),
+    ('LDS_MAX_PLAIN, tallies of k_trace_fast', 'n_surf', (1, 5000), 'mega_lds_tally', dict(flags=0, accel_ok=0)),
+    ('LDS_MAX_PLAIN, scene of k_trace_fast', 'n_surf', (1, 5000), 'mega_lds_scene', dict(flags=0, accel_ok=0)),
+    ('72 KiB, k_s_shade', 'n_extra', (0, 20000), 'lds_tables', dict(_STREAM, grid_ok=1, cls_moving=4, cls_all=4)),
+    ('72 KiB, k_s_shade_x', 'n_extra', (0, 20000), 'lds_tables', dict(_STREAM, grid_ok=1, carry=1, cls_all=4)),
+    ('78 KiB with bins, k_s_shade', 'fm_bins', (1, 20000), 'lds_fm_bins', dict(_STREAM, grid_ok=1, cls_moving=4, cls_all=4, n_fm_edges=40, fms_bytes=136)),
+    ('120 KiB, lean kernels', 'n_extra', (0, 30000), 'shk', dict(_STREAM, grid_ok=1, cls_moving=2, cls_all=2)),
+    ('150 KiB with bins, lean kernels', 'fm_bins', (1, 30000), 'shk', dict(_STREAM, grid_ok=1, cls_moving=1, cls_all=1, n_fm_edges=40, fms_bytes=136)),
+    ('158 KiB, terminal hits inside k_s_bounce', 'grid_list', (0, 60000), 'absorb_inline',
+     dict(_STREAM, accel_ok=1, grid_ok=1, grid_cells=500, n_surf=30, stride=15, n_extra=0, cls_moving=1, cls_all=1, any_term=1, n_fm_edges=40, fms_bytes=136,
+          fm_bins=8000, carry=0, splits=0, chart=0, transfer=0, term_ok=1, k_absorb=-1, k_bounce=1, k_search=2)),
+]
+# Two limits of the header are not in the list because no fact block is decided by them: S <= 65535 of mega_plan (the tallies of
+# 65536 surfaces alone are 1.5 MB, beyond LDS_MAX_ALLOWED) and k_s_absorb's 78 KiB (its image is part of k_s_shade's, which has passed
+# 72 KiB, or 78 KiB with the bins, before).  The free blocks of the sweep agree on them all the same.
+
+
+def random_block(rng):
+    """a fact block drawn freely: scenes of 1..3000 surfaces (now and then beyond 65535) on either grid, on a tree or on their boxes,
+    with and without maps, terminal surfaces and a source with its footprint map; every flag and knob of a call"""
+    b, r = lambda p=.5: int(rng.rand() < p), rng.randint
+    n_surf = r(1, 40) if b(.3) else r(65000, 66000) if b(.03) else r(1, 3001)
+    has_kd, maps, src = b(), r(0, 3), (-1, 0, 1, 2, 3, 7, 8)[r(7)]
+    cls_all = r(1, 8)
+    f = S.blank_facts(n_surf=n_surf, stride=(15, 17, 21)[r(3)], accel_ok=b(.95), has_kd=has_kd, accel_kd_ok=has_kd and b(.9),
+                      kd_nodes=has_kd * (2 * r(1, 9000) + 1), kd_nleaf=has_kd * r(0, 90000), kd_nalways=has_kd * r(0, 50), kd_depth=has_kd * r(1, 33),
+                      grid_ok=b(.6), big_ok=b(.7), grid_cells=r(1, 4000), grid_list=r(0, 60000), brute_list=r(0, n_surf + 1), n_unbounded=b(.1) * r(1, 4),
+                      big_occ_words=r(0, 40000), n_fm_edges=maps * r(4, 80), fms_bytes=maps * sc.SIZEOF_FLUXMAPDEV, n_extra=b() * r(1, 12000),
+                      fm_bins=maps * r(1, 4000), chart=maps and b(.2), transfer=b(.1), splits=b(.1), all_flat=b(), cls_all=cls_all,
+                      cls_moving=cls_all & r(0, 8), any_term=b(),
+                      n=(r(1, 200), r(3000, 6000), r(1000000, 1100000), r(1, 1 << 22))[r(4)], flags=r(0, 16) & ~2, src_kind=src, spec=src >= 0 and b(.3),
+                      carry=b(.15), mat_dev=b(.1), term_ok=b(.9),
+                      k_search=(1, 2)[b(.8)], k_fresh=b(.9), k_bounce=b(.8), k_first=b(.3), k_coop=b(.7), k_absorb=(-1, 0, 1)[r(3)], k_umask=b(.8))
+    f['simple'] = f['all_flat'] and b()
+    if src >= 0 and b(.8):
+        Mc = (32, 64, 128, 256)[r(4)]
+        f.update(fp_use=1, fp_n_list=r(0, 70000), fp_M=4 * Mc, fp_Mc=Mc, fp_has_generic=b(), fp_cdf_end=rng.rand() * 1.1, fp_coverage=rng.rand(),
+                 fp_ucoverage=rng.rand() * 1.1, fp_umask_words=b(.8) * r(64, 8193), fp_Mu=1 << r(6, 11), fp_Mv=1 << r(0, 11))
+    return dict((k, (v if isinstance(v, float) else int(v))) for k, v in f.items())
+
+
+def test_header_decides_random_calls_as_restated():
+    """
+    1e5 seeded fact blocks: three quarters drawn freely (random_block), a quarter in pairs one step apart across one of THRESHOLDS --
+    a random block with the threshold's fixed facts, the moved fact found by bisection of the restated decision -- so that every
+    threshold named in csrc/trc_forms.h is straddled at least 100 times; the header's decisions equal the restated ones for all of them
+    """
+    rng = N.random.RandomState(20262)
+    blocks, crossed = [], dict((t[0], 0) for t in THRESHOLDS)
+    while len(blocks) < 75000:
+        blocks.append(random_block(rng))
+    while len(blocks) < 100000:
+        name, key, (lo, hi), what, fixed = THRESHOLDS[rng.randint(len(THRESHOLDS))]
+        f = dict(random_block(rng), **fixed)
+        at = lambda v: what(M.decide(dict(f, **{key: v}))) if callable(what) else M.decide(dict(f, **{key: v})).get(what)
+        first = at(lo)
+        if at(hi) == first:         # (this block does not reach the threshold: its other facts decide)
+            blocks += [dict(f, **{key: lo}), dict(f, **{key: hi})]
+            continue
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if at(mid) == first else (lo, mid)
+        blocks += [dict(f, **{key: lo}), dict(f, **{key: hi})]
+        crossed[name] += 1
+    print(crossed)
+    assert all(n >= 100 for n in crossed.values()), crossed
+    for k in range(0, len(blocks), 10000):
+        same_decisions(blocks[k:k + 10000])

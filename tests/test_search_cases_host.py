@@ -68,7 +68,7 @@ def conditions(call):
 @pytest.mark.parametrize('name', [c.name for c in S.CALLS])
 def test_call_selects_its_instances_and_exercises_them(name):
     call = S.CALL[name]
-    s, f, p = S.scene(call.scene), S.forms(call), S.predict(call)
+    s, f, p = S.scene(call.scene), S.forms(S.facts(call)), S.predict(call)
     # the prediction: the call's targets among what the host would launch
     for inst in call.targets:
         assert inst in p, (inst, sorted(p))
@@ -95,7 +95,7 @@ def test_call_selects_its_instances_and_exercises_them(name):
         assert f['in_lds'] == (f['gridm'] in (0, 1) and not full) and (f['need_bounce'] > S.LIMIT_LDS) == full
         assert f['coop'] == (bool(forced) and dict(call.env).get('TRC_STREAM_COOP', 1) != 0)
     if call.second:         # the inequality of launch_bounce holds after the first call: the second one is k_s_fresh's
-        assert p[f['fresh']] == 1 and p[f['fresh_one']] == 1 and f['fresh'] != f['fresh_one']
+        assert p[f['fresh'][0]] == 1 and p[f['fresh_one'][0]] == 1 and f['fresh'] != f['fresh_one']
     # the per-ray conditions
     c = conditions(call)
     gm = sc._names('GM_')
@@ -181,9 +181,9 @@ def test_library_layout_is_the_restated_one_for_every_call():
     """the images behind every decision and every launch of the calls: with the tables and without"""
     parts = []
     for call in S.CALLS:
-        s, f = S.scene(call.scene), S.forms(call)
+        s, f = S.scene(call.scene), S.forms(S.facts(call))
         S_, q = s.cs.n_surf, s.sizes(None if call.given else call.src)
-        assert q['buie_bytes'] > 0
+        assert q['buie_bytes'] == S.BUIE_BYTES
         if f['use_fp']:
             qw = ((1024 if s.flat else 768) // 64) if f['fresh_two'] else 0
             bb = q['buie_bytes'] if f['fresh_two'] else 0
@@ -260,3 +260,25 @@ def test_large_grid_agrees_with_brute_force(key):
         assert not (sb == s.twin[1]).any()
         total += int((sb == s.twin[0]).sum())
     assert total >= 130
+
+
+# -- the library's choice of kernels (csrc/trc_forms.h) against the restated one ----------------------------------------------------
+def test_header_decides_every_call_as_restated():
+    """all calls, none left out: every decision of the header for the call's facts -- the plan, the forms, each stage's kernel by name,
+    threads and LDS bytes -- is the restated one (mega_cases.decide: forms() here, with the shading and terminal stages of
+    shade_cases); and predict()'s kernels are the header's names"""
+    import mega_cases as M
+    blocks = [S.facts(call) for call in S.CALLS]
+    lib = S.library_decide(blocks)
+    for call, f, d in zip(S.CALLS, blocks, lib):
+        mine = M.decide(f)
+        assert mine == d, (call.name, sorted((k, mine.get(k), d.get(k)) for k in set(mine) | set(d) if mine.get(k) != d.get(k)))
+        assert d['use_stream'] and d['decided'], call.name
+        launched = set(d[st][0] for st in S.STAGES if d[st][0]) - set([d['absorb'][0]])
+        assert set(S.predict(call)) <= launched and set(call.targets) <= launched, (call.name, sorted(launched))
+
+
+def test_header_names_every_instance():
+    """the ids the header can produce in the search families, over their argument ranges, are ALL_INSTANCES"""
+    names = S.library_ids()
+    assert sorted(n for n in names if n.split('<')[0] in S.FAMILIES) == sorted(S.ALL_INSTANCES)

@@ -1,6 +1,6 @@
 """
 What the tests of the shading kernel instances (test_gpu_shade_instances.py) take for granted about their cases, checked without
-a device from the oracle and the restated sums of stream_form_shade alone (shade_cases.py): every case is predicted to select
+a device from the oracle and the restated sums of trc_stream_form_shade alone (shade_cases.py): every case is predicted to select
 the instances it is there for, with its byte sum on the intended side of the limit; its rays hit every optics kind of its classes,
 its curved surfaces, its captured surfaces inside and outside the map; some rays are culled on the way and some survive; and no
 ray is near a tie -- two surfaces at nearly the same distance, an energy nearly at min_energy -- so that the device tests exclude
@@ -34,7 +34,7 @@ def test_case_selects_its_instances_and_exercises_them(hostcheck, name):
     c = sc.case(name)
     o = sc.reference(name)
     opt, gm = sc._names('OPT_'), sc._names('GM_')
-    # the prediction: the case's targets among what stream_form_shade would launch, each on its side of its limit
+    # the prediction: the case's targets among what trc_stream_form_shade would launch, each on its side of its limit
     for inst in c.targets:
         assert inst in c.instances, (inst, sorted(c.instances))
         total, limit, in_lds, bins_in_lds = c.instances[inst]
@@ -103,14 +103,14 @@ PARTS = ('tally', 'recs', 'opt', 'fm_edges', 'fms', 'fm_of', 'flags', 'extra', '
 END, SLACK, LIMIT, LIMIT_BINS, IN_LDS, BINS_IN, REQUEST = 9, 10, 11, 12, 13, 14, 15
 # what a launch of each image asks for when nothing is staged: the count words (k_s_shade keeps one)
 BARE = {IMG_SHADE: 8, IMG_SHADE_X: 16, IMG_LEAN: 16, IMG_LEAN_MIRROR: 16}
-INLINE_MARGIN = 64          # stream_form_absorb, as it was: `extra_lds = lds_absorb + 64`
+INLINE_MARGIN = 64          # trc_stream_form_absorb, as it was: `extra_lds = lds_absorb + 64`
 LIMIT_ABSORB, LIMIT_INLINE = 78 * sc.KiB, 158 * sc.KiB         # ... `lds_absorb <= 78 * 1024`, `F.bounce.lds + extra_lds <= 158 * 1024`
 
 
 def lds_layout(hc, rows):
     """trc_shade_lds_layout of rows (image, tables staged, surfaces, record stride, map edges, descriptor bytes, table doubles, bins in
     LDS): (n, 16) -- the offsets of PARTS, end, slack, the two limits of the image, and what the host's own decision
-    (trc_shade_lds_choose, the code stream_form_shade calls) makes of a scene with that many bins: tables in LDS, bins in LDS, the bytes
+    (trc_shade_lds_choose, the code trc_stream_form_shade calls) makes of a scene with that many bins: tables in LDS, bins in LDS, the bytes
     its launch asks for"""
     rows = N.ascontiguousarray(rows, dtype=N.int32).reshape(-1, 8)
     out = N.zeros((len(rows), 16), dtype=N.uint64)
@@ -130,7 +130,7 @@ def check_images(hc, S, stride, n_edges, n_maps, n_extra, bins, old):
     rows = lambda img, lds, b: N.stack([N.full(n, img), N.full(n, 1) * lds, S, stride, n_edges, fms, n_extra, b], axis=1)
     sums = {}
     for img in (IMG_SHADE, IMG_SHADE_X, IMG_LEAN, IMG_LEAN_MIRROR):
-        # stream_form_shade as predict() restates it: tables by `need`, bins by `need + bins * 8 + 16`
+        # trc_stream_form_shade as predict() restates it: tables by `need`, bins by `need + bins * 8 + 16`
         need = t + r + o + m + (0 if img == IMG_LEAN_MIRROR else n_extra * 8)
         limit, limit_bins = (sc.LIMIT_LEAN, sc.LIMIT_LEAN_BINS) if img in (IMG_LEAN, IMG_LEAN_MIRROR) else (sc.LIMIT_SHADE, sc.LIMIT_SHADE_BINS)
         in_lds = need <= limit
@@ -149,7 +149,7 @@ def check_images(hc, S, stride, n_edges, n_maps, n_extra, bins, old):
         assert N.array_equal(L[:, END] + L[:, SLACK], request)
         check_parts(L, img, lib_in, S, stride, n_edges, fms, n_extra, N.where(lib_bins, bins, 0), request)
         sums[img] = (need, need + bins * 8 + 16, bins > 0)
-    # stream_form_absorb, as it was: `b.tally + b.maps + (lds_fm_bins ? bins * 8 : 0) + 16`, with the bins k_s_shade took or none
+    # trc_stream_form_absorb, as it was: `b.tally + b.maps + (lds_fm_bins ? bins * 8 : 0) + 16`, with the bins k_s_shade took or none
     for b_in in (bins, 0 * bins):
         old_absorb = t + m + b_in * 8 + 16
         La = lds_layout(hc, rows(IMG_ABSORB, 1, b_in))
@@ -248,7 +248,7 @@ def test_library_layout_gives_random_scenes_their_restated_sums(hostcheck, monke
               '78 KiB, k_s_absorb': near(sums[IMG_ABSORB][0], LIMIT_ABSORB, every)}
     # 158 KiB: k_s_bounce's own request (any, a multiple of 16) + the inline image, with requests drawn to put the total within 2 KiB of
     # the limit.  The image's bytes were compared above, so this holds the library's limit for it and no more: the addition and the
-    # comparison themselves are host text of stream_form_absorb that no host-compiled code reaches (the device tests of the terminal
+    # comparison themselves are host text of trc_stream_form_absorb that no host-compiled code reaches (the device tests of the terminal
     # surfaces do)
     d = rng.randint(-2 * sc.KiB, 2 * sc.KiB + 1, size=n)
     inline_old = sums[IMG_ABSORB][0] + INLINE_MARGIN
@@ -258,3 +258,57 @@ def test_library_layout_gives_random_scenes_their_restated_sums(hostcheck, monke
     counts['158 KiB, inline'] = near(bounce + inline_old, LIMIT_INLINE, every)
     print(counts)
     assert all(lo >= 100 and hi >= 100 for lo, hi in counts.values()), counts
+
+
+# -- the library's choice of kernels (csrc/trc_forms.h) against the restated one ----------------------------------------------------
+SHADE_FAMILIES = ('k_s_shade', 'k_s_shade_c', 'k_s_shade_x')
+
+
+def case_facts(c, given=False):
+    """the fact block of a case's streaming call: the scene with its map as the library gathers it, the case's source or (carry, given)
+    its bundle; 'carry-mat': the materials' tables are on the device"""
+    import search_cases as S
+    f = S.scene_facts(c.cs, None, None, c.edges)
+    src = -1 if (c.carry or given) else c.source().source_args()[0].kind
+    f.update(n=sc.N_RAYS, flags=S.TRACE_ACCEL | S.TRACE_STREAM, src_kind=src, spec=int(c.spec and src >= 0), carry=int(c.carry),
+             mat_dev=int(c.kind == 'carry-mat'), term_ok=1)
+    return f
+
+
+def test_header_decides_every_case_as_restated(hostcheck):
+    """all 20 cases, none left out: every decision of the header for the case's facts is the restated one (mega_cases.decide, whose
+    shading stage is shade_forms()), and its shading kernels are predict()'s, with predict()'s tables and bins in LDS"""
+    import mega_cases as M
+    import search_cases as S
+    for name in sorted(sc.CASES):
+        c = sc.case(name)
+        for given in ((False, True) if name in sc.GIVEN else (False,)):
+            f = case_facts(c, given)
+            mine, lib = M.decide(f), S.library_decide([f])[0]
+            assert mine == lib, (name, sorted((k, mine.get(k), lib.get(k)) for k in set(mine) | set(lib) if mine.get(k) != lib.get(k)))
+            assert lib['use_stream'] and lib['decided']
+            shk = dict((sc.short_name(k[0]), k) for k in lib['shk'])
+            assert set(shk) == set(c.instances), (name, sorted(shk))
+            for inst, (total, limit, in_lds, bins_in) in c.instances.items():
+                assert shk[inst][4] == int(in_lds) and (shk[inst][5] > 0) == bins_in
+
+
+def test_header_names_every_instance(hostcheck):
+    """the ids the header can produce in the shading families with the CHART, SPLIT and MAT arguments off -- what the cases hold them at --
+    are ALL_INSTANCES as the cases spell them; with those arguments, the kernels of the built library by name"""
+    import search_cases as S
+    names = [n for n in S.library_ids() if n.split('<')[0] in SHADE_FAMILIES]
+    off = [n for n in names if n.endswith(', false>') and not (n.startswith('k_s_shade_x') and n != 'k_s_shade_x<%s, false, false, false>' % n[12:-22])]
+    assert sorted(sc.short_name(n) for n in off) == sorted(sc.ALL_INSTANCES)
+    lib = os.path.join(ROOT, 'tracer_amd', 'lib', 'libtracer_amd.so')
+    import re
+    import shutil
+    if not os.path.exists(lib) or shutil.which('nm') is None:
+        pytest.skip('no built library, or no nm')
+    squeeze = lambda x: re.sub(r'\s+', '', x)
+    held = set()
+    for line in subprocess.check_output(['nm', '-C', lib]).decode().splitlines():
+        m = re.search(r'\b(k_s_shade(_c|_x)?)(<[^>]*>)\(StreamParams\)', line)
+        if m and '__device_stub__' not in line:
+            held.add(squeeze(m.group(1) + m.group(3)))
+    assert held == set(squeeze(n) for n in names), sorted(held ^ set(squeeze(n) for n in names))

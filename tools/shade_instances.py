@@ -1,4 +1,4 @@
-"""One line per shading kernel instance of the streaming engine (the 26 of stream_form_shade) from a rocprofv3 --kernel-trace --stats
+"""One line per shading kernel instance of the streaming engine (the 26 of trc_stream_form_shade) from a rocprofv3 --kernel-trace --stats
 output directory of tests/test_gpu_shade_instances.py: its calls in the trace, and the cases of tests/shade_cases.py whose restated
 sums predict it.  The trace is of the whole file, so the cases are the prediction's, not read from the trace: what ties them to
 the calls is the count -- every streaming call launches each of its shading kernels once per repetition (shade_cases.REPS), and the

@@ -114,7 +114,7 @@ static inline float trc_f32_up(double x) { float f = (float)x; return ((double)f
 
 // The LDS image of the tables a search kernel of the streaming engine reads (k_s_fresh, k_s_fresh2, k_s_bounce, k_s_bounce_coop):
 // ONE description, read by the kernels, which carve their pointers from it (stage_search_tables, trc_device.h), and by the host,
-// which sizes the launches from it and decides whether a scene's tables fit LDS (stream_form_fresh, stream_form_bounce).  The
+// which sizes the launches from it and decides whether a scene's tables fit LDS (trc_stream_form_fresh, trc_stream_form_bounce).  The
 // parts follow one another in the order of the fields below; a part that is absent takes no room.
 #define SFQ_CAP 128             /* entries of a wave's queue between the two phases of k_s_fresh2 (a power of two, >= 2 x 64) */
 #ifndef SBC_CELLS
@@ -165,7 +165,7 @@ TRC_HD trc_lds_layout trc_search_lds_layout(const trc_lds_parts &p) {
 }
 
 // The LDS image of a kernel of the streaming engine that finishes hits, as the HOST sees it: it sizes the launches and decides "fits in
-// LDS" from this description alone (stream_form_shade, stream_form_absorb, through trc_shade_lds_choose), and
+// LDS" from this description alone (trc_stream_form_shade, trc_stream_form_absorb, through trc_shade_lds_choose), and
 // tests/test_shade_cases_host.py holds it to the hand-made sums it replaced.  The kernels do NOT read it: each carves its image in its
 // own text (each says why at its carving), and that text is kept in agreement with the order, sizes and rounding written here BY HAND
 // -- whoever changes a carving changes trc_shade_lds_layout with it; the device tests of the maps and of the shading instances are

@@ -9,6 +9,7 @@
 #include "trc_core.h"
 #include "trc_bounds.h"
 #include "trc_footprint.h"
+#include "trc_forms.h"
 
 struct FluxMapDev {
     int32_t surf, nu, nv, chart;   // chart: the coordinates the map bins in (TRC_FM_*, trc_core.h)
@@ -348,12 +349,6 @@ struct FastParams {
 };
 
 
-// optics kinds of the "mirrors and diffuse walls" family: what a heliostat field, a dish or a cavity of opaque walls is made of.
-// A scene of flat surfaces with only these gets an instance of k_s_shade that carries nothing else (SIMPLE below).
-#define TRC_OPT_SIMPLE_MASK ((1u << TRC_OPT_TRANSPARENT) | (1u << TRC_OPT_REFLECTIVE) | (1u << TRC_OPT_ONE_SIDED_REFLECTIVE) | \
-                             (1u << TRC_OPT_REAL_REFLECTIVE) | (1u << TRC_OPT_ONE_SIDED_REAL_REFLECTIVE) | (1u << TRC_OPT_LAMBERTIAN) | \
-                             (1u << TRC_OPT_LAMBERTIAN_SPECULAR))
-
 // shading + bookkeeping of one hit, shared by the two fast kernels.  Returns false when the ray stops here.
 // SIMPLE promises a flat geometry kind and an optics kind of TRC_OPT_SIMPLE_MASK on every surface: the compiler drops the rest.
 template <bool LDS_TALLY, bool SIMPLE = false, bool CHART = false>
@@ -572,36 +567,10 @@ __device__ __forceinline__ const ARGS *kernel_args_again() {
 }
 
 // optics classes of the shading stage.  MIRROR and DIFFUSE are served by lean kernels (trc_shade.hip: <= 128 registers, four
-// waves per SIMD and more); everything else -- refraction, media, conductors, incidence-angle modifiers -- by k_s_shade.
-#define TRC_CLS_MIRROR 0       /* Transparent, Reflective, OneSidedReflective, RealReflective, OneSidedRealReflective (no IAM) */
-#define TRC_CLS_DIFFUSE 1      /* Lambertian (no IAM, no absorbing medium), LambertianSpecular, SemiLambertian, Reflective_spectral, the
-                                  Lambertian_directional_axisymmetric_piecewise family */
-#define TRC_CLS_GENERAL 2
-#define TRC_CLS_COUNT 3
+// waves per SIMD and more); everything else -- refraction, media, conductors, incidence-angle modifiers -- by k_s_shade
+// (TRC_CLS_*, trc_shade_class_of: trc_forms.h).
 #define TRC_SURF_CLS_SHIFT 17  /* device copy of the surface flags only: bits 17-18 = class */
 #define TRC_SURF_CLS_MASK 0x3
-#define TRC_CLS_MIRROR_KINDS ((1u << TRC_OPT_TRANSPARENT) | (1u << TRC_OPT_REFLECTIVE) | (1u << TRC_OPT_ONE_SIDED_REFLECTIVE) | \
-                              (1u << TRC_OPT_REAL_REFLECTIVE) | (1u << TRC_OPT_ONE_SIDED_REAL_REFLECTIVE))
-#define TRC_CLS_DIFFUSE_KINDS ((1u << TRC_OPT_LAMBERTIAN) | (1u << TRC_OPT_LAMBERTIAN_SPECULAR) | (1u << TRC_OPT_SEMI_LAMBERTIAN) | \
-                               (1u << TRC_OPT_REFLECTIVE_SPECTRAL) | (1u << TRC_OPT_LAMBERTIAN_DIRECTIONAL) |                     \
-                               (1u << TRC_OPT_LAMBERTIAN_DIRECTIONAL_SPECTRAL) | (1u << TRC_OPT_FRESNEL_CONDUCTOR))
-
-// class of a surface from its optics kind and parameters (host side, when the flags are uploaded)
-static inline int trc_shade_class_of(const trc_surface_desc &sd) {
-    const int ok = sd.optics_kind;
-    if (ok < 0 || ok >= 32) return TRC_CLS_GENERAL;
-    if ((TRC_CLS_MIRROR_KINDS >> ok) & 1u) {
-        const bool iam = ((ok == TRC_OPT_REFLECTIVE || ok == TRC_OPT_ONE_SIDED_REFLECTIVE) && sd.opt[1] != 0.0) ||
-                         ((ok == TRC_OPT_REAL_REFLECTIVE || ok == TRC_OPT_ONE_SIDED_REAL_REFLECTIVE) && sd.opt[3] != 0.0);
-        return iam ? TRC_CLS_GENERAL : TRC_CLS_MIRROR;
-    }
-    if ((TRC_CLS_DIFFUSE_KINDS >> ok) & 1u) {
-        if (ok == TRC_OPT_LAMBERTIAN && (sd.opt[2] != 0.0 || sd.opt[4] != 0.0)) return TRC_CLS_GENERAL;      // absorbing medium / IAM
-        return TRC_CLS_DIFFUSE;
-    }
-    return TRC_CLS_GENERAL;
-}
-
 // ================================================================================================
 // hit bookkeeping of the streaming kernels that finish hits (k_s_shade, k_s_shade_c, k_s_shade_x, k_s_absorb, k_s_bounce)
 // ================================================================================================
@@ -690,9 +659,6 @@ __device__ __forceinline__ void tally_by_wave(double *tl, int Sn, int ts, double
 const void *trc_shade_carry_kernel(bool lds, bool chart = false, bool split = false, bool mat = false);      // k_s_shade_x (trc_shade.hip): every optics kind, with what the rays carry;
                                                                                             // split: its form for scenes whose optics send two rays on from a hit
 const void *trc_shade_lean_kernel(int cls, bool flat, bool lds, bool spec = false, bool chart = false);
-#ifndef SHC_THREADS
-#define SHC_THREADS 1024
-#endif
 
 __device__ __forceinline__ trc_accel_view stream_accel_global(const DScene &sc, int mode) {
     const bool kd32 = mode == 1;

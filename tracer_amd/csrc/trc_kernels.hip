@@ -580,17 +580,7 @@ struct trc_result {
 //   exact    survivors are queued; all lanes drain that queue with trc_intersect (float64) and combine per ray
 //            with LDS atomics: minimal t, then the lowest surface index among equal t (tracer_engine.py:58-63).
 // ------------------------------------------------------------------------------------------------
-#define COOP_LEAFCAP 16      // leaves listed per lane between two drains
-#define COOP_E 128           // exact-test queue entries per wave
-#define COOP_MAX_NODES 16384 // stack entries are 4 bytes: node (14 bits) | axis code (2 bits) | interval end (16 bits)
-#define COOP_MAX_DEPTH 24
-#define COOP_FIXED_BYTES (COOP_E * 8 + 64 * 8 + COOP_E * 4 + 64 * 4 + 64 * 4 + 64 * 4 + COOP_LEAFCAP * 64 * 2)
-#define COOP_WAVE_BYTES(DEPTH) ((size_t)(DEPTH) * 64 * 4 + COOP_FIXED_BYTES)
-// dynamic LDS a workgroup may ask for: of the CU's 160 KiB once allowed them (kernel_allow_lds; 512 bytes stay with the kernels'
-// static LDS), and what any kernel gets unasked (k_trace_fast keeps to it)
-static const size_t LDS_MAX_ALLOWED = 160 * 1024 - 512;
-static const size_t LDS_MAX_PLAIN = 64 * 1024;
-
+// (COOP_LEAFCAP, COOP_E, COOP_WAVE_BYTES and the limits of the packed stack: trc_forms.h, where mega_plan sizes the launch)
 struct CoopLds {
     double *exq_t;                // [COOP_E]
     unsigned long long *best_t;   // [64]
@@ -1103,19 +1093,25 @@ __global__ __launch_bounds__(THREADS) void k_trace_coop(FastParams P) {
     flush_sums<THREADS>(sc.tally, l_tally, 3 * S + 2, nullptr, 0, S);
 }
 
-// TRC_SURF_TERMINAL: e_out = e (1 - absorptivity) = 0 exactly, and 0 <= min_energy for every min_energy the API accepts
-static bool surface_ends_every_ray(const trc_surface_desc &sd) {
-    const int ok = sd.optics_kind;
-    const bool plain = ((ok == TRC_OPT_REFLECTIVE || ok == TRC_OPT_ONE_SIDED_REFLECTIVE) && sd.opt[1] == 0.0) ||
-                       ((ok == TRC_OPT_REAL_REFLECTIVE || ok == TRC_OPT_ONE_SIDED_REAL_REFLECTIVE) && sd.opt[3] == 0.0) ||
-                       (ok == TRC_OPT_LAMBERTIAN && sd.opt[2] == 0.0 && sd.opt[4] == 0.0) || ok == TRC_OPT_LAMBERTIAN_SPECULAR;
-    return plain && sd.opt[0] == 1.0;
-}
-
 // Some flux map of the scene bins in another chart than XY: the call runs the CHART instances of the kernels that finish hits
 static bool scene_has_chart_map(const trc_scene *sc) {
     for (auto &m : sc->fms_h) if (m.chart != TRC_FM_XY) return true;
     return false;
+}
+
+// What the decisions of trc_forms.h read of the scene.  walk: with the pass over the surfaces, which the streaming engine alone needs.
+static trc_scene_facts scene_facts(const trc_scene *sc, bool walk) {
+    trc_scene_facts s = {};
+    trc_scene_facts_fill(sc->surfs.data(), sc->n_surf, sc->accel, walk, &s);
+    s.stride = sc->stride;
+    s.accel_ok = sc->accel_ok; s.accel_kd_ok = sc->accel_kd_ok; s.has_kd = sc->has_kd;
+    s.kd_nodes = sc->kd_nodes; s.kd_nleaf = sc->kd_nleaf; s.kd_nalways = sc->kd_nalways;
+    s.n_fm_edges = (int)sc->fm_edges_h.size(); s.fms_bytes = (int)(sc->fms_h.size() * sizeof(FluxMapDev)); s.n_extra = sc->n_extra;
+    for (auto &m : sc->fms_h) s.fm_bins += (long long)m.nu * m.nv;
+    s.chart = scene_has_chart_map(sc);
+    s.transfer = sc->tr_off >= 0;
+    s.splits = sc->splits;
+    return s;
 }
 
 // Lets `fn` take `lds` bytes of dynamic LDS: beyond 64 KiB a kernel must be allowed them first
@@ -1136,7 +1132,6 @@ static int kernel_grid_cap(const void *fn, int threads, size_t lds, int max_bpc,
     return TRC_OK;
 }
 
-#define TRC_STREAM_MIN_RAYS 1048576
 #include "trc_stream.inc"
 
 // ================================================================================================
@@ -1202,8 +1197,8 @@ struct OrdParams {
 
 // pending far children of the single-precision Kd walk (trc_nearest_accel32), in LDS: entry sp of thread t at [sp * 256 + t].
 // (In private memory the two stacks of this kernel were 576 bytes of scratch per lane -- 300 MB per dispatch, more than the
-// runtime keeps, so every launch allocated and freed it: 7.4 ms per bounce, whatever the number of rays.)
-#define ORD_STACK_DEPTH 24
+// runtime keeps, so every launch allocated and freed it: 7.4 ms per bounce, whatever the number of rays.)  ORD_STACK_DEPTH entries
+// each (trc_forms.h).
 struct LdsStack32 {
     uint32_t *na;
     float *tmax;
@@ -2854,9 +2849,10 @@ struct FastCall {
     // the arguments of trc_trace_fast_x (src as source_resolve left it)
     trc_scene *sc; const trc_rays *in; const trc_source_desc *src; const SourceSpectrum *spec;
     int64_t n; int32_t reps; double min_energy; uint64_t seed, ray_offset; int32_t flags; trc_rays *last;
-    // fast_check_args: the knobs, whether the rays carry more than the megakernel knows, and what
+    // fast_check_args: the knobs (facts.knobs), whether the rays carry more than the megakernel knows, and what; fast_facts: the rest
+    // of what the choice of kernels reads (trc_forms.h)
     trc_source_desc src_res;
-    StreamKnobs knobs;
+    trc_facts facts;
     bool carry;
     bool mat_dev;       // the materials' indices come from the scene's tables (scene_mat_route)
     PayLayout lay;
@@ -2893,7 +2889,7 @@ static int fast_check_args(FastCall &C) {
     const bool mat_dev = scene_mat_route(sc, C.in);
     if (sc->splits && ((C.flags & TRC_TRACE_MEGAKERNEL) || C.n < 64 || (C.spec->desc && !mat_dev)))
         return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has ray-splitting optics, which the fast engine traces in its streaming form only (64 rays or more, no source spectrum): use trc_trace_ordered");
-    C.knobs = stream_knobs();
+    C.facts.knobs = stream_knobs();
     // Rays that carry the imaginary part of a complex index, materials evaluated at their wavelength or a sampled spectrum are
     // traced by the streaming form (k_s_shade_x); the megakernel knows nothing of them.
     C.carry = sc->needs.any() || (C.in && (C.in->ref_index_im || C.in->spectra || C.in->mat));
@@ -2956,43 +2952,6 @@ static int fast_begin(FastCall &C) {
     return sc->counters.restart_last(C.before);
 }
 
-// The megakernel's LDS budget.  Preferred (m32): k_trace_coop, the single-precision conservative search with everything it needs
-// in LDS, 512 threads or 256; else k_trace_fast with the tallies and the scene in LDS as far as they fit.
-struct MegaPlan {
-    bool m32;
-    int threads;
-    size_t lds;
-    int lds_tally, lds_scene;
-};
-static MegaPlan mega_plan(const FastCall &C) {
-    const trc_scene *sc = C.sc;
-    const int S = sc->n_surf;
-    const bool accel = sc->has_kd && (C.flags & TRC_TRACE_ACCEL);       // (without a Kd-tree the megakernel tests every box)
-    const size_t b_buie = C.src ? (size_t)TRC_BUIE_STAGED * 8 : 0;
-    const size_t b_tally = (size_t)(3 * S + 2) * 8;
-    MegaPlan M = {false, 256, 0, 0, 0};
-    if (sc->accel_ok && S <= 65535 && (!accel || (sc->accel_kd_ok && sc->kd_nodes <= COOP_MAX_NODES && sc->accel.kd_depth <= COOP_MAX_DEPTH))) {
-        const size_t b_acc = (size_t)6 * S * 4 + (accel ? ((size_t)2 * sc->kd_nodes * 4 + (size_t)sc->kd_nalways * 4 + (size_t)sc->kd_nleaf * 2)
-                                                        : (8 + sc->accel.brute_leaf.size() * 2)) +
-                             sc->accel.unbounded.size() * 4 + 32;
-        const size_t b_wave = COOP_WAVE_BYTES(accel ? (sc->accel.kd_depth > 0 ? sc->accel.kd_depth : 1) : 1);
-        for (int threads = 512; threads >= 256 && !M.m32; threads /= 2) {
-            const size_t lds = b_buie + b_tally + b_acc + (size_t)(threads / 64) * b_wave;
-            if (lds <= LDS_MAX_ALLOWED) M = {true, threads, lds, 1, 0};
-        }
-    }
-    if (!M.m32) {
-        size_t b_scene = (size_t)S * sc->stride * 8;
-        if (sc->has_kd) b_scene += (size_t)sc->kd_nodes * 8 + ((size_t)sc->kd_nodes * 2 + sc->kd_nleaf + sc->kd_nalways) * 4 + 8;
-        M.lds = b_buie;
-        M.lds_tally = (M.lds + b_tally <= LDS_MAX_PLAIN) ? 1 : 0;
-        if (M.lds_tally) M.lds += b_tally;
-        M.lds_scene = (M.lds + b_scene <= LDS_MAX_PLAIN) ? 1 : 0;
-        if (M.lds_scene) M.lds += b_scene;
-    }
-    return M;
-}
-
 static void fast_params(const FastCall &C, const MegaPlan &M, FastParams *P, CarryIn *carry_in) {
     memset(P, 0, sizeof(*P));
     P->sc = make_dscene(C.sc);
@@ -3012,34 +2971,32 @@ static void fast_params(const FastCall &C, const MegaPlan &M, FastParams *P, Car
     carry_in->mat_tab = C.mat_dev ? C.sc->d_mat_tab.get() : nullptr;
 }
 
-// Large calls run the streaming engine (phases as separate kernels connected by HBM queues, trc_stream.inc); small ones the
-// persistent megakernel, which needs one launch and no workspace.  TRC_TRACE_STREAM / TRC_TRACE_MEGAKERNEL force one or the other.
-static int fast_choose_engine(const FastCall &C, StreamPlan *plan, bool *use_stream) {
-    *plan = {0, 0, true};
-    const bool stream_ok = C.n >= 64 && stream_plan(C.sc, (C.flags & TRC_TRACE_ACCEL) != 0, C.knobs, plan);
-    // (rays that carry more, and optics that send two rays on from a hit, are the streaming form's alone: k_s_shade_x)
-    const bool stream_only = C.carry || C.sc->splits;
-    const bool force_stream = (C.flags & TRC_TRACE_STREAM) || stream_only;
-    const bool force_mega = !stream_only && (C.flags & TRC_TRACE_MEGAKERNEL);
-    // (a scene on the large grid -- a mesh of 1e5 faces -- has nothing but its boxes to search in the megakernel: 2e5 rays on the
-    // relief of 105 800 triangles took 570 ms there, 1.3 ms here)
-    const long long stream_from = plan->mode == 3 ? 4096 : TRC_STREAM_MIN_RAYS;
-    *use_stream = stream_ok && (force_stream || (!force_mega && C.n >= stream_from));
-    if (stream_only && !*use_stream) return trc_fail(TRC_ERR_UNSUPPORTED, "no streaming form for this scene: rays that carry complex indices or spectra, and ray-splitting optics, go through trc_trace_ordered");
-    return TRC_OK;
+// the facts of the call for the decisions of trc_forms.h (the scene's without the pass over its surfaces; the knobs are there already)
+static void fast_facts(FastCall &C) {
+    C.facts.scene = scene_facts(C.sc, false);
+    C.facts.call = {C.n, C.flags, C.src ? C.src->kind : -1, C.d_spec != nullptr, C.carry, C.mat_dev && C.sc->d_mat_tab.get(), C.min_energy >= 0.0};
 }
 
-// the megakernel's instances for a source with a spectrum (SPEC: they draw the wavelength), a tabulated sunshape (SUN) and a scene
-// with a flux map in another chart than XY (CHART)
-struct MegaKernels { void (*coop512)(FastParams), (*coop256)(FastParams), (*fast256)(FastParams); };
+// the megakernel's instance of an id (mega_plan, trc_forms.h); null: the library has none
 template <bool SPEC, bool SUN, bool CHART>
-static MegaKernels mega_kernels_of() { return {k_trace_coop<512, SPEC, SUN, CHART>, k_trace_coop<256, SPEC, SUN, CHART>, k_trace_fast<256, SPEC, SUN, CHART>}; }
-template <bool CHART>
-static MegaKernels mega_kernels_for(bool spec, bool sun) {
-    if (spec) return sun ? mega_kernels_of<true, true, CHART>() : mega_kernels_of<true, false, CHART>();
-    return sun ? mega_kernels_of<false, true, CHART>() : mega_kernels_of<false, false, CHART>();
+static const void *mega_kernel_of(int family, int threads) {
+    if (family == TRC_K_TRACE_FAST) return threads == 256 ? (const void *)k_trace_fast<256, SPEC, SUN, CHART> : nullptr;
+    return threads == 512 ? (const void *)k_trace_coop<512, SPEC, SUN, CHART> : threads == 256 ? (const void *)k_trace_coop<256, SPEC, SUN, CHART> : nullptr;
 }
-static MegaKernels mega_kernels(bool spec, bool sun, bool chart) { return chart ? mega_kernels_for<true>(spec, sun) : mega_kernels_for<false>(spec, sun); }
+static const void *mega_kernel_fn(const trc_kernel_id &id) {
+    if (id.family != TRC_K_TRACE_COOP && id.family != TRC_K_TRACE_FAST) return nullptr;
+    switch (4 * id.a[1] + 2 * id.a[2] + id.a[3]) {        // SPEC, SUN, CHART
+    case 0: return mega_kernel_of<false, false, false>(id.family, id.a[0]);
+    case 1: return mega_kernel_of<false, false, true>(id.family, id.a[0]);
+    case 2: return mega_kernel_of<false, true, false>(id.family, id.a[0]);
+    case 3: return mega_kernel_of<false, true, true>(id.family, id.a[0]);
+    case 4: return mega_kernel_of<true, false, false>(id.family, id.a[0]);
+    case 5: return mega_kernel_of<true, false, true>(id.family, id.a[0]);
+    case 6: return mega_kernel_of<true, true, false>(id.family, id.a[0]);
+    case 7: return mega_kernel_of<true, true, true>(id.family, id.a[0]);
+    default: return nullptr;
+    }
+}
 
 static int mega_launch(FastCall &C, const MegaPlan &M, const FastParams &P) {
     trc_scene *sc = C.sc;
@@ -3047,8 +3004,8 @@ static int mega_launch(FastCall &C, const MegaPlan &M, const FastParams &P) {
     (void)hipStreamSynchronize(ctx->stream);       // (the sums of an earlier streaming call may still be on their way into the buffer)
     if (hipMemcpy(C.tally_before, sc->d_tally.get() + 3 * sc->n_surf, sizeof(C.tally_before), hipMemcpyDeviceToHost) != hipSuccess)
         return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
-    const MegaKernels K = mega_kernels(P.spec != nullptr, C.d_src && source_is_sunshape(C.src->kind), scene_has_chart_map(sc));
-    void (*kern)(FastParams) = !M.m32 ? K.fast256 : (M.threads == 512 ? K.coop512 : K.coop256);
+    void (*kern)(FastParams) = (void (*)(FastParams))mega_kernel_fn(M.id);
+    if (!kern) return trc_fail(TRC_ERR_UNSUPPORTED, "the library holds no megakernel instance for this call");
     // persistent grid: as many workgroups as are resident at once (at most 8 per CU), never more waves than rays/64
     unsigned resident = 0;
     TRC_TRY(kernel_grid_cap((const void *)kern, M.threads, M.lds, 8, ctx->n_cu, &resident));
@@ -3109,19 +3066,19 @@ static int fast_steps(FastCall &C) {
     TRC_TRY(fast_stage_inputs(C));
     TRC_TRY(fast_stage_last(C));
     TRC_TRY(fast_begin(C));
-    const MegaPlan M = mega_plan(C);
+    fast_facts(C);
+    const MegaPlan M = mega_plan(C.facts.scene, C.facts.call);
     FastParams P;
     CarryIn carry_in;
     fast_params(C, M, &P, &carry_in);
-    StreamPlan plan;
-    bool use_stream = false;
-    TRC_TRY(fast_choose_engine(C, &plan, &use_stream));
-    if (use_stream) {
+    const trc_engine_choice engine = trc_fast_choose_engine(C.facts.scene, C.facts.call, C.facts.knobs);
+    if (engine.refused) return trc_fail(TRC_ERR_UNSUPPORTED, "no streaming form for this scene: rays that carry complex indices or spectra, and ray-splitting optics, go through trc_trace_ordered");
+    if (engine.use_stream) {
         if (!sc->stream_eng) {
             sc->stream_eng.reset(new (std::nothrow) StreamEngine());
             if (!sc->stream_eng) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
         }
-        if (int e = stream_trace(sc, P, carry_in, plan, C.knobs, C.src, *sc->stream_eng, &C.s, &C.stream_seg, &C.stream_hits)) {
+        if (int e = stream_trace(sc, P, carry_in, engine.plan, C.facts, C.src, *sc->stream_eng, &C.s, &C.stream_seg, &C.stream_hits)) {
             sc->hits.rollback(sc->counters.device() + CNT_HIT_CURSOR, C.before.hit_cursor);     // (the hits captured by the bounces that completed)
             return e;
         }
@@ -3227,12 +3184,15 @@ static int ordered_level0(OrdCall &C, const trc_rays *in, const trc_source_desc 
     return TRC_OK;
 }
 
-// the search of k_ord_bounce: 2 the large grid (the scene stands on it and the caller brought no tree), 1 the single-precision
-// conservative search, 0 the generic one
-static int ordered_search_mode(const trc_scene *sc, int32_t flags) {
-    const bool use_kd = sc->has_kd && (flags & TRC_TRACE_ACCEL);
-    if (sc->accel_ok && sc->accel.big_ok && !use_kd) return 2;
-    return (sc->accel_ok && sc->n_surf <= 65535 && (!use_kd || (sc->accel_kd_ok && sc->accel.kd_depth + 2 <= ORD_STACK_DEPTH))) ? 1 : 0;
+// k_ord_bounce's instance of an id (trc_ordered_choose, trc_forms.h); null: the library has none
+template <bool CHART, bool MAT>
+static const void *ord_kernel_of(int mode) {
+    return mode == 2 ? (const void *)k_ord_bounce<2, CHART, MAT> : mode == 1 ? (const void *)k_ord_bounce<1, CHART, MAT>
+         : mode == 0 ? (const void *)k_ord_bounce<0, CHART, MAT> : nullptr;
+}
+static const void *ord_kernel_fn(const trc_kernel_id &id) {
+    if (id.family != TRC_K_ORD_BOUNCE || (id.a[1] && id.a[2])) return nullptr;
+    return id.a[1] ? ord_kernel_of<true, false>(id.a[0]) : id.a[2] ? ord_kernel_of<false, true>(id.a[0]) : ord_kernel_of<false, false>(id.a[0]);
 }
 
 // Bounce `it` of the n_cur live rays of the last level into the 2 n_cur slots of the scratch: *m of them occupied (the rays of
@@ -3257,11 +3217,9 @@ static int ordered_bounce(OrdCall &C, int it, int64_t n_cur, int64_t *m, int64_t
     P.pay = cur.pay; P.pay_stride = cur.n_total; P.opay = sx.opay.get(); P.lay = C.lay;
     P.mat_tab = C.mat_tab;
 
+    void (*kern)(OrdParams) = (void (*)(OrdParams))ord_kernel_fn(trc_ordered_choose(scene_facts(sc, false), C.flags, C.mat_tab != nullptr).id);
+    if (!kern) return trc_fail(TRC_ERR_UNSUPPORTED, "the library holds no k_ord_bounce instance for this call");
     (void)hipEventRecord(ctx->ev0, ctx->stream);
-    const int mode = ordered_search_mode(sc, C.flags);
-    void (*kern)(OrdParams) = mode == 2 ? k_ord_bounce<2> : (mode == 1 ? k_ord_bounce<1> : k_ord_bounce<0>);
-    if (scene_has_chart_map(sc)) kern = mode == 2 ? k_ord_bounce<2, true> : (mode == 1 ? k_ord_bounce<1, true> : k_ord_bounce<0, true>);
-    else if (C.mat_tab) kern = mode == 2 ? k_ord_bounce<2, false, true> : (mode == 1 ? k_ord_bounce<1, false, true> : k_ord_bounce<0, false, true>);
     hipLaunchKernelGGL(kern, dim3((unsigned)((n_cur + 255) / 256)), dim3(256), 0, ctx->stream, P);
     hipLaunchKernelGGL(k_compact_count, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, sx.key.get(), (long long)slots,
                        sx.blk_cnt.get(), sx.blk_cul.get());

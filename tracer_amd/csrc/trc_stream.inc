@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 //              pass (the reference's tie rule: nearest, lowest surface index on equal t).  A ray that hits takes the next slot
 //              of the ray table and goes straight to the hit list of k_s_shade, surface and distance with it.
 // No ray record, walker or candidate entry is written for a ray that hits nothing.
-#define SC_THREADS 512
+// (SC_THREADS, SC_GEN_CAP, SF_THREADS and the other launch shapes: trc_forms.h, where the host sizes the launches)
 struct CullParams {
     trc_fp_params F;
     const uint32_t *mask;
@@ -204,7 +204,6 @@ struct CullParams {
     int gen_on;
     uint32_t gen_thr;
 };
-#define SC_GEN_CAP 1024                 /* general-path rays a workgroup collects before it appends them */
 
 template <int KIND, bool UM>
 __device__ __forceinline__ void s_cull_body(const CullParams &C) {
@@ -286,11 +285,6 @@ __global__ __launch_bounds__(SC_THREADS) void k_s_cull(CullParams C) { s_cull_bo
 template <int KIND>
 __global__ __launch_bounds__(SC_THREADS) void k_s_ucull(CullParams C) { s_cull_body<KIND, true>(C); }
 
-// one workgroup per CU: 1024 threads (4 waves per SIMD) for a scene of flat surfaces -- 128 registers with 18 of the instance's 160
-// in scratch, and still a quarter faster than 3 waves per SIMD without (NSTTF: 0.33 -> 0.25 ms per batch: the kernel issues at half
-// the rate of its arithmetic, its dependent float64 chains want waves to switch to) -- 512 (2 per SIMD) with the quadric code in;
-// every table then exists once per CU
-#define SF_THREADS(FLAT) ((FLAT) ? 1024 : 768)
 #ifndef SB_FLAT_WALK
 #define SB_FLAT_WALK 0          /* 1: the grid that fits LDS is walked like the large one, one cell or one candidate per lane and turn */
 #endif
@@ -298,16 +292,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_s_ucull(CullParams C) { s_cull_b
 // FLAT: every surface of the scene is a flat kind (a heliostat field, a mesh): the instance carries no quadric code.
 // LDS: the tables a listed ray reads (surface records, oriented boxes, cell lists) are staged in LDS -- all of them or none, so
 // that the compiler knows the address space of every access (a pointer that may be either is read with flat loads).
-// the footprint-listed kernels' LDS image: [the Buie table] [records | oriented boxes | cell offsets | lists (lds)] [queues]
-TRC_HD trc_lds_parts fresh_lds_parts(int n_surf, int stride, const trc_fp_params &F, long long n_list, bool buie, bool lds, int queue_waves) {
-    trc_lds_parts p = {};
-    p.n_surf = n_surf; p.stride = stride;
-    p.buie_bytes = buie ? (int)sizeof(trc_buie_fast) : 0;
-    p.tables = lds;
-    if (lds) { p.fp_offs = F.Mc * F.Mc + 1; p.fp_list = (int)n_list; }
-    p.queue_waves = queue_waves;
-    return p;
-}
+// (their LDS image: fresh_lds_parts, trc_forms.h)
 
 template <int KIND, bool FLAT, bool LDS>
 __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh(StreamParams S) {
@@ -366,7 +351,6 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh(StreamParams S) {
 // delta >= 1e-3 m (1e-2 on the NSTTF field) on every side, so a ray that hits a surface passes its box in this form too.  The
 // rays that pass wait in a queue of the wave in LDS; whenever 64 of them have come together the wave runs phase 2 with every
 // lane busy: the float64 ray, boxes and exact tests exactly as k_s_fresh does them.
-#define SF2_DERIVES_CELL(FLAT, LDS) ((FLAT) || (LDS))
 template <int KIND, bool FLAT, bool LDS>
 __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh2(StreamParams S0) {
     constexpr int THREADS = SF_THREADS(FLAT);
@@ -498,19 +482,10 @@ __global__ __launch_bounds__(SF_THREADS(FLAT)) void k_s_fresh2(StreamParams S0) 
 
 // ---------------------------------------------------------------------------------------------------------------
 // walk + balanced box tests, single precision only
-#ifndef SW_LEAFCAP
-#define SW_LEAFCAP 16
-#endif
-#ifndef SW_LIST_T
-#define SW_LIST_T uint16_t
-#endif
+// (SW_THREADS, SW_LEAFCAP, SW_LIST_T, SW_WAVE_BYTES: trc_forms.h)
 #ifndef SW_ITEMS
 #define SW_ITEMS 4
 #endif
-#ifndef SW_THREADS
-#define SW_THREADS 256
-#endif
-#define SW_WAVE_BYTES(DEPTH) ((size_t)(DEPTH) * 64 * 4 + SW_LEAFCAP * 64 * sizeof(SW_LIST_T) + 64 * 4)
 
 struct WalkLds {
     uint32_t *stack;   // [depth][64]
@@ -744,11 +719,6 @@ __global__ __launch_bounds__(THREADS) void k_s_walk(StreamParams S) {
 // first cell that starts behind the best hit: a surface is listed in every cell its box overlaps, the cell of a nearer hit
 // has been visited.
 
-#define SB_THREADS 1024          /* one workgroup per CU, 4 waves per SIMD: every table exists once per CU.  The instances with the quadric
-                                    code in need ~166 registers and keep 18 of them in scratch at 128 (dish + receiver: 19.7 -> 18.3 ms per
-                                    1e8 rays against 768 threads; the seven-wall cavity: unchanged); the flat instance needs 121 */
-#define SB_THREADS_OF(GRIDM) (SB_THREADS)       /* (768 and 512 threads on the large grid, no scratch then: 16.3 and 21.2 ms against 14.2 per 1e7 rays on the relief) */
-
 // GRIDM: 0 every bounded surface (accel = False), 1 the grid that fits LDS, 2 the 32-bit grid of large scenes (global memory),
 // 3 scenes of a few surfaces (a dish and its receiver, a cavity of seven walls), surface by surface: the wave goes through the
 // surfaces together, every lane whose ray passes the surface's boxes runs the exact test of that ONE surface.  Its record is
@@ -761,20 +731,7 @@ __global__ __launch_bounds__(THREADS) void k_s_walk(StreamParams S) {
 // structures do not fit the LDS of the walk kernel (meshes of 1e5 faces), or everywhere with TRC_STREAM_FIRST=1.  A ray that hits
 // takes the next slot of the table.
 // FLAT: every surface of the scene is of a flat kind: no quadric code in the exact test (as in k_s_fresh).
-// the LDS image of k_s_bounce / k_s_bounce_coop: [the Buie table (fresh)] [occupancy bits] [records | oriented boxes | boxes | flags |
-// small grid (lds)] [the waves' blocks (coop)]
-TRC_HD trc_lds_parts bounce_lds_parts(int n_surf, int stride, bool fresh, bool lds, bool flags, int grid_cells, int grid_list, int occ_words,
-                                      int coop_waves) {
-    trc_lds_parts p = {};
-    p.n_surf = n_surf; p.stride = stride;
-    p.buie_bytes = fresh ? (int)sizeof(trc_buie_fast) : 0;
-    p.occ_words = occ_words;
-    p.tables = p.sbox = lds;
-    p.flags = flags;
-    if (grid_cells) { p.grid_cells = grid_cells; p.grid_list = grid_list; }
-    p.coop_waves = coop_waves;
-    return p;
-}
+// (SB_THREADS, and the LDS image of k_s_bounce / k_s_bounce_coop, bounce_lds_parts: trc_forms.h)
 #ifdef SB_STATS      /* diagnostic builds only: what the lanes of k_s_bounce spend their turns on (printed at the end of a call) */
 __device__ unsigned long long g_sb_stats[32];        /* [0, 16): fresh rays, [16, 32): continued rays */
 #define SB_COUNT(K, V) atomicAdd(&g_sb_stats[(FRESH ? 0 : 16) + (K)], (unsigned long long)(V))
@@ -1843,7 +1800,6 @@ __global__ __launch_bounds__(128 * WAVES, WAVES) void k_s_shade(StreamParams S) 
 // nothing goes on: hit point, tallies, flux-map bin, hit capture.  A quarter of k_s_shade's registers, so eight waves per SIMD hide
 // the two loads in front of every hit; k_s_shade at two could not (0.20 -> ms of an NSTTF batch's second bounce).
 // LDS: tallies | flux-map edges, descriptors, surface -> map, flags | flux-map bins -- as k_s_shade with lds_tally, lds_tables.
-#define SA_THREADS 1024
 __global__ __launch_bounds__(SA_THREADS, 2) void k_s_absorb(StreamParams S) {
     extern __shared__ double lds[];
     const FastParams &P = S.P;
@@ -1977,23 +1933,7 @@ struct StreamBuffers {
 };
 
 #define STREAM_MAX_SLOTS 4
-// Environment knobs of the streaming engine: routes and capacities the tests compare and force.  trc_trace_fast reads them at every
-// call, since the tests switch them within one process.
-struct StreamKnobs {
-    int search;             // TRC_STREAM_SEARCH=1: walk the caller's Kd-tree instead of the grid (when its walk kernel fits)
-    bool fresh;             // TRC_STREAM_FRESH=0: no footprint map
-    bool bounce;            // TRC_STREAM_BOUNCE=0: continued rays through the general path
-    bool first;             // TRC_STREAM_FIRST=1: fresh rays outside the footprint map through k_s_bounce<.., FRESH>
-    bool coop;              // TRC_STREAM_COOP=0: k_s_bounce<2> on the large grid, every lane its own ray
-    int absorb;             // TRC_STREAM_ABSORB=0: no list of terminal hits; =1: the list, finished by k_s_absorb only (-1: not set)
-    bool static_chunks;     // TRC_STREAM_STATIC=0: no pre-assigned chunks
-    bool room_set; long long room;      // TRC_STREAM_ROOM is set, and the room of every list it sets (>= 64; 0: the default)
-    long long q3_entries;   // TRC_STREAM_Q3_ENTRIES: initial capacity of the candidate queue (0: by the batch)
-    int fp_cells;           // TRC_STREAM_FP_CELLS: cells per side of the footprint map (>= 32; 0: by the scene)
-    bool umask;             // TRC_STREAM_UMASK=0: k_s_cull on the Cartesian mask for every source (the form that packs the cell)
-    int slots;              // TRC_STREAM_SLOTS: batches in flight, 1 .. STREAM_MAX_SLOTS (default 2)
-};
-
+// the environment knobs of the streaming engine (StreamKnobs, trc_forms.h), read at every call
 static StreamKnobs stream_knobs() {
     StreamKnobs K;
     const char *ev;
@@ -2067,41 +2007,6 @@ static int stream_ws_alloc(StreamBuffers &W, long long cap, int n_unbounded, lon
     return TRC_OK;
 }
 
-// Which candidate search the streaming engine would use for this scene -- 0 all boxes, 1 packed Kd-tree, 2 uniform grid (LDS
-// sized), 3 the 32-bit grid of large scenes -- the LDS its walk kernel needs, and whether that kernel can run at all (walk_ok):
-// when the tables of the search do not fit LDS the general path (k_s_gen + k_s_walk + k_s_exact) is not available and k_s_bounce
-// searches for every ray from global memory.  false: no streaming form for this scene (the caller uses the megakernel).
-struct StreamPlan { int mode; size_t lds_walk; bool walk_ok; };
-static bool stream_plan(const trc_scene *sc, bool want_accel, const StreamKnobs &K, StreamPlan *out) {
-    if (!sc->accel_ok) return false;
-    const int S = sc->n_surf;
-    auto walk_lds = [&](int mode) {
-        const int depth = mode == 1 ? (sc->accel.kd_depth > 0 ? sc->accel.kd_depth : 1) : 1;
-        const size_t shared = (size_t)6 * S * 4 +
-            (mode == 2 ? (sc->accel.grid_off.size() + 2 + sc->accel.grid_list.size()) * 2
-                       : (mode == 1 ? ((size_t)2 * sc->kd_nodes * 4 + (size_t)sc->kd_nleaf * 2) : (8 + sc->accel.brute_leaf.size() * 2))) + 32;
-        return shared + (size_t)(SW_THREADS / 64) * SW_WAVE_BYTES(depth);
-    };
-    const size_t lds_max = LDS_MAX_ALLOWED;
-    int mode = 0;
-    if (want_accel) {
-        // the uniform grid of trc_bounds.h; TRC_STREAM_SEARCH=1 walks the caller's Kd-tree instead (when its walk kernel fits)
-        const bool kd_fits = sc->accel_kd_ok && S <= 65535 && walk_lds(1) <= lds_max;
-        if (K.search == 1 && kd_fits) mode = 1;
-        else if (sc->accel.grid_ok) mode = 2;
-        else if (sc->accel.big_ok) mode = 3;       // a scene beyond the LDS-sized structures: the 32-bit grid in global memory
-        else if (kd_fits) mode = 1;
-    }
-    if (mode == 0 && S > 65535) return false;      // (the list of all boxes holds 16-bit numbers)
-    size_t lds = mode == 3 ? 0 : walk_lds(mode);
-    const bool walk_ok = mode != 3 && lds <= lds_max;
-    if (!walk_ok) lds = 0;
-    out->mode = mode;
-    out->lds_walk = lds;
-    out->walk_ok = walk_ok;
-    return true;
-}
-
 // One batch in flight: its workspace, its stream and where it is in its bounces.  Two of them alternate, so that the
 // arithmetic-bound kernels of one batch (generation, walk) share the device with the access-bound ones of the other
 // (exact tests, tie pass, shading).
@@ -2138,7 +2043,6 @@ struct StreamSlot {
     bool busy = false;
 };
 
-#define STREAM_SMALL_SURFACES 24    /* scenes up to this many surfaces are searched surface by surface (k_s_bounce<3>) */
 struct StreamEngine {
     StreamSlot slot[STREAM_MAX_SLOTS];
     bool ready = false;        // the slots have their streams, events and pinned blocks
@@ -2186,7 +2090,7 @@ static int stream_fp_prepare(trc_scene *sc, StreamEngine &E, const trc_source_de
     if (!(E.fp_valid && E.fp_geom_version == sc->geom_version && memcmp(key, E.fp_key, sizeof(key)) == 0 && (!buie || E.fp->P.cdf_end == cdf_end))) {
         int M = sc->n_surf > 4096 ? 1024 : 512;       // (a mesh of small faces: finer cells, fewer faces listed per cell; the mask still fits k_s_cull's LDS)
         const bool forced = K.fp_cells > 0;
-        const bool um = buie;      // the mask over the uniforms: for the sources whose listed rays go to k_s_fresh2 (stream_form_fresh)
+        const bool um = buie;      // the mask over the uniforms: for the sources whose listed rays go to k_s_fresh2 (trc_stream_form_fresh)
         if (forced) M = K.fp_cells;
         if (M > 1024) M = 1024;
         if (sc->n_surf > 4096 && !forced) {
@@ -2239,325 +2143,187 @@ static int stream_engine_init(StreamEngine *E, trc_ctx *ctx) {
     return TRC_OK;
 }
 
-// The LDS image of a kernel that finishes hits (trc_shade_lds_layout, trc_bounds.h) for a scene, and its bytes: what a fits-in-LDS
-// decision compares with trc_shade_lds_limit and what a launch asks for
-static trc_shade_parts shade_lds_parts(const trc_scene *sc, int img, bool lds, long long fm_bins) {
-    return trc_shade_lds_parts(img, lds, sc->n_surf, sc->stride, (int)sc->fm_edges_h.size(), (int)(sc->fms_h.size() * sizeof(FluxMapDev)), sc->n_extra, (int)fm_bins);
+// A kernel id (trc_forms.h) -> the instance the library holds for it, null: none.  One place per family, which reads nothing but the
+// id; the ids a place answers with a pointer are those of trc_kernel_id_valid, and the kernels compiled are exactly these.
+// ... the families whose first argument is the source kind: k_s_cull, k_s_ucull, k_s_fresh, k_s_fresh2
+template <int KIND, bool FLAT, bool LDS>
+static const void *fresh_kernel_of(int family) {
+    if (family == TRC_K_FRESH) return (const void *)k_s_fresh<KIND, FLAT, LDS>;
+    if constexpr (KIND == TRC_SRC_BUIE_DISK || KIND == TRC_SRC_BUIE_RECT) if (family == TRC_K_FRESH2) return (const void *)k_s_fresh2<KIND, FLAT, LDS>;
+    return nullptr;
 }
-static size_t shade_lds_need(const trc_shade_parts &p) { const trc_shade_layout L = trc_shade_lds_layout(p); return L.end + L.slack; }
-static size_t shade_lds_choose(const trc_scene *sc, int img, long long bins, bool *in_lds, int *lds_fm_bins) {
-    return trc_shade_lds_choose(img, sc->n_surf, sc->stride, (int)sc->fm_edges_h.size(), (int)(sc->fms_h.size() * sizeof(FluxMapDev)), sc->n_extra, bins,
-                                in_lds, lds_fm_bins);
+template <int KIND>
+static const void *source_kernel_of(const trc_kernel_id &id) {
+    if (id.family == TRC_K_CULL) return (const void *)k_s_cull<KIND>;
+    if constexpr (KIND == TRC_SRC_BUIE_DISK || KIND == TRC_SRC_BUIE_RECT) if (id.family == TRC_K_UCULL) return (const void *)k_s_ucull<KIND>;
+    const bool flat = id.a[1] != 0, lds = id.a[2] != 0;
+    return flat ? (lds ? fresh_kernel_of<KIND, true, true>(id.family) : fresh_kernel_of<KIND, true, false>(id.family))
+                : (lds ? fresh_kernel_of<KIND, false, true>(id.family) : fresh_kernel_of<KIND, false, false>(id.family));
+}
+static const void *source_kernel_fn(const trc_kernel_id &id) {
+    switch (id.a[0]) {
+    case TRC_SRC_PILLBOX_DISK: return source_kernel_of<TRC_SRC_PILLBOX_DISK>(id);
+    case TRC_SRC_PILLBOX_RECT: return source_kernel_of<TRC_SRC_PILLBOX_RECT>(id);
+    case TRC_SRC_BUIE_DISK: return source_kernel_of<TRC_SRC_BUIE_DISK>(id);
+    case TRC_SRC_BUIE_RECT: return source_kernel_of<TRC_SRC_BUIE_RECT>(id);
+    case TRC_SRC_SUNSHAPE_DISK: return source_kernel_of<TRC_SRC_SUNSHAPE_DISK>(id);
+    case TRC_SRC_SUNSHAPE_RECT: return source_kernel_of<TRC_SRC_SUNSHAPE_RECT>(id);
+    default: return nullptr;
+    }
+}
+// ... k_s_gen, k_s_gen_src
+static const void *gen_kernel_fn(const trc_kernel_id &id) {
+    const int kind = id.family == TRC_K_GEN ? id.a[1] : id.a[0];
+    if (id.family == TRC_K_GEN_SRC)
+        return kind == TRC_SRC_BUIE_DISK ? (const void *)k_s_gen_src<TRC_SRC_BUIE_DISK> : kind == TRC_SRC_PILLBOX_DISK ? (const void *)k_s_gen_src<TRC_SRC_PILLBOX_DISK>
+             : kind == TRC_SRC_PILLBOX_RECT ? (const void *)k_s_gen_src<TRC_SRC_PILLBOX_RECT> : nullptr;
+    if (!id.a[0]) return kind == -1 ? (const void *)k_s_gen<false> : nullptr;
+    return kind == -1 ? (const void *)k_s_gen<true> : kind == TRC_SRC_BUIE_RECT ? (const void *)k_s_gen<true, TRC_SRC_BUIE_RECT>
+         : kind == TRC_SRC_SUNSHAPE_DISK ? (const void *)k_s_gen<true, TRC_SRC_SUNSHAPE_DISK>
+         : kind == TRC_SRC_SUNSHAPE_RECT ? (const void *)k_s_gen<true, TRC_SRC_SUNSHAPE_RECT> : nullptr;
+}
+// ... k_s_bounce, k_s_bounce_coop
+template <bool FRESH, bool FLAT, bool SUN>
+static const void *bounce_kernel_of(const trc_kernel_id &id) {
+    if (id.family == TRC_K_BOUNCE_COOP) return (const void *)k_s_bounce_coop<FRESH, FLAT, SUN>;
+    if constexpr (FRESH && FLAT) return nullptr;        // (k_s_bounce takes fresh rays in its instance for any geometry)
+    else {
+        const bool lds = id.a[1] != 0;
+        switch (id.a[0]) {
+        case 0: return lds ? (const void *)k_s_bounce<0, true, FRESH, FLAT, SUN> : (const void *)k_s_bounce<0, false, FRESH, FLAT, SUN>;
+        case 1: return lds ? (const void *)k_s_bounce<1, true, FRESH, FLAT, SUN> : (const void *)k_s_bounce<1, false, FRESH, FLAT, SUN>;
+        case 2: return lds ? nullptr : (const void *)k_s_bounce<2, false, FRESH, FLAT, SUN>;
+        case 3: return lds ? nullptr : (const void *)k_s_bounce<3, false, FRESH, FLAT, SUN>;
+        default: return nullptr;
+        }
+    }
+}
+static const void *bounce_kernel_fn(const trc_kernel_id &id) {
+    const int *a = id.family == TRC_K_BOUNCE ? id.a + 2 : id.a;       // FRESH, FLAT, SUN
+    const bool fresh = a[0] != 0, flat = a[1] != 0, sun = a[2] != 0;
+    if (!fresh) return sun ? nullptr : flat ? bounce_kernel_of<false, true, false>(id) : bounce_kernel_of<false, false, false>(id);
+    if (flat) return sun ? bounce_kernel_of<true, true, true>(id) : bounce_kernel_of<true, true, false>(id);
+    return sun ? bounce_kernel_of<true, false, true>(id) : bounce_kernel_of<true, false, false>(id);
+}
+// ... k_s_shade
+template <bool LDS, bool SPEC>
+static const void *shade_kernel_of(bool simple, bool chart) {
+    if (chart) return simple ? nullptr : (const void *)k_s_shade<false, 2, LDS, SPEC, true>;
+    return simple ? (const void *)k_s_shade<true, 2, LDS, SPEC> : (const void *)k_s_shade<false, 2, LDS, SPEC>;
+}
+static const void *shade_kernel_fn(const trc_kernel_id &id) {
+    const bool simple = id.a[0] != 0, lds = id.a[2] != 0, spec = id.a[3] != 0, chart = id.a[4] != 0;
+    if (id.a[1] != 2) return nullptr;
+    return lds ? (spec ? shade_kernel_of<true, true>(simple, chart) : shade_kernel_of<true, false>(simple, chart))
+               : (spec ? shade_kernel_of<false, true>(simple, chart) : shade_kernel_of<false, false>(simple, chart));
+}
+// ... and every family of the streaming engine (the lean and carry kernels: trc_shade.hip)
+static const void *stream_kernel_fn(const trc_kernel_id &id) {
+    switch (id.family) {
+    case TRC_K_CULL: case TRC_K_UCULL: case TRC_K_FRESH: case TRC_K_FRESH2: return source_kernel_fn(id);
+    case TRC_K_GEN: case TRC_K_GEN_SRC: return gen_kernel_fn(id);
+    case TRC_K_BOUNCE: case TRC_K_BOUNCE_COOP: return bounce_kernel_fn(id);
+    case TRC_K_WALK: return id.a[0] != SW_THREADS ? nullptr : id.a[1] ? (const void *)k_s_walk<SW_THREADS, true> : (const void *)k_s_walk<SW_THREADS, false>;
+    case TRC_K_EXACT: return (const void *)k_s_exact;
+    case TRC_K_ABSORB: return (const void *)k_s_absorb;
+    case TRC_K_SHADE: return shade_kernel_fn(id);
+    case TRC_K_SHADE_C: return trc_shade_lean_kernel(id.a[0], id.a[1] != 0, id.a[2] != 0, id.a[3] != 0, id.a[4] != 0);
+    case TRC_K_SHADE_X: return trc_shade_carry_kernel(id.a[0] != 0, id.a[1] != 0, id.a[2] != 0, id.a[3] != 0);
+    default: return nullptr;
+    }
 }
 
-static long long flux_map_bins(const trc_scene *sc) {
-    long long bins = 0;
-    for (auto &m : sc->fms_h) bins += (long long)m.nu * m.nv;
-    return bins;
-}
-
-static bool all_surfaces_flat(const trc_scene *sc) {
-    for (int i = 0; i < sc->n_surf; ++i) if (!trc_gm_is_flat(sc->surfs[i].gm_kind)) return false;
-    return true;
-}
-
-// one kernel instance of a stage: threads per workgroup, dynamic LDS, and the grid cap (the workgroups resident at once)
+// one kernel instance of a stage as the batches launch it: the function of its id, threads per workgroup, dynamic LDS, and the grid
+// cap (the workgroups resident at once)
 struct StreamKernel { const void *fn; int threads; size_t lds; unsigned max_blocks; };
 // ... of a shading kernel: the class it serves (-1: the only shading kernel, every kind) and the tables it stages
 struct StreamShadeK { int cls; const void *fn; unsigned threads, wpb, max_blocks; size_t lds; int lds_tables, lds_fm_bins; };
 
-// The kernels a call runs and the per-call decisions the bounces are planned by
+// The kernels a call runs: the decisions (D, trc_forms.h) and, stage by stage, the instance they name made ready to launch
 struct StreamForms {
-    int src_kind;
-    int gridm;                   // k_s_bounce's form of the search: 0 all boxes, 1 LDS-sized grid, 2 large grid, 3 surface by surface
-    bool small_scene;
-    StreamKernel walk;           // the general path: k_s_gen (g_gen), k_s_walk, k_s_exact (g_wide, lds_exact)
+    trc_stream_forms D;
+    StreamKernel gen0, gen, walk, exact;     // the general path (grids: g_gen, walk.max_blocks, g_wide)
     unsigned g_gen, g_wide;      // (g_wide: k_s_partition too)
-    size_t lds_exact;
     StreamShadeK shk[TRC_CLS_COUNT];
-    int n_shk;
-    StreamKernel cull, fresh, fresh_one;     // fresh_one: k_s_fresh itself where `fresh` is its two-phase form
-    StreamKernel cull_u;         // k_s_cull on the mask over the uniforms, in front of k_s_fresh2 (fn null: this source has none)
-    CullParams cull_up;          // ... what it takes that the other form does not: the mask, its words and dimensions, the generic compare
-    double ulisted_share;        // ... and the share of the fresh rays it lists
-    StreamKernel bounce, first, absorb;      // k_s_bounce for continued rays / for fresh ones, k_s_absorb
-    bool coop;                   // k_s_bounce_coop serves the large grid (it lists terminal hits, never finishes them itself)
-    bool use_fp, use_fused, use_first, use_absorb, absorb_inline;
-    bool multi;                  // more than one shading kernel: k_s_partition parts the hit list by class first
-    double general_share;        // expected share of the fresh rays that k_s_cull leaves to the general path
-    double listed_share;         // ... and lists for k_s_fresh (an estimate for its grid: the covered part of the source)
+    StreamKernel cull, fresh, fresh_one, cull_u;
+    CullParams cull_up;          // what k_s_ucull takes that k_s_cull does not: the mask, its words and dimensions, the generic compare
+    StreamKernel bounce, first, absorb;
 };
 
-// the general path: k_s_gen, k_s_walk (the tables of the search in LDS), k_s_exact (the records in LDS when they fit)
-static int stream_form_general(StreamForms &F, StreamParams &SP0, const trc_scene *sc, const StreamPlan &plan) {
+// A stage made ready: the function of its id (a missing one is an error), its grid cap at `lds_cap` bytes (cap) and the leave to take
+// its dynamic LDS.  A stage the call does not have (TRC_K_NONE) stays empty.
+static int stream_stage(StreamKernel &k, const trc_stage &s, int n_cu, bool cap, size_t lds_cap) {
+    k = {nullptr, s.threads, s.lds, 0u};
+    if (s.id.family == TRC_K_NONE) return TRC_OK;
+    k.fn = stream_kernel_fn(s.id);
+    if (!k.fn) {
+        char name[96];
+        trc_kernel_name(s.id, name, sizeof(name));
+        return trc_fail(TRC_ERR_UNSUPPORTED, "the library holds no kernel %s", name);
+    }
+    if (cap) TRC_TRY(kernel_grid_cap(k.fn, k.threads, lds_cap, 2048 / k.threads, n_cu, &k.max_blocks));
+    return (cap && lds_cap == k.lds) ? TRC_OK : kernel_allow_lds(k.fn, k.lds);
+}
+
+// Chooses the kernel of every stage for this call and sets up SP0, the parameters every batch starts from: the facts are gathered,
+// trc_stream_decide (trc_forms.h) decides, each id chosen becomes a function, and each function gets its grid cap and its LDS
+static int stream_choose_forms(StreamForms &F, StreamParams &SP0, trc_scene *sc, StreamEngine &E, const StreamPlan &plan, trc_facts &f,
+                               const trc_source_desc *src_desc) {
     const int n_cu = sc->ctx->n_cu;
-    const size_t b_recs = (size_t)sc->n_surf * sc->stride * 8;
-    F.lds_exact = b_recs <= 40 * 1024 ? b_recs : 0;
-    SP0.lds_recs = F.lds_exact ? 1 : 0;
-    // (the general path never runs on tables beyond LDS: there SP.search == plan.mode)
-    F.walk = {plan.mode == 2 ? (const void *)k_s_walk<SW_THREADS, true> : (const void *)k_s_walk<SW_THREADS, false>, SW_THREADS, plan.lds_walk, 0u};
-    TRC_TRY(kernel_grid_cap(F.walk.fn, SW_THREADS, F.walk.lds, 2048 / SW_THREADS, n_cu, &F.walk.max_blocks));
+    memset(&F, 0, sizeof(F));
+    // 1. the facts the call did not have yet: the pass over the surfaces, and the footprint map of the source
+    f.scene = scene_facts(sc, true);
+    f.fp = {};
+    TRC_TRY(stream_fp_prepare(sc, E, src_desc, f.knobs, &SP0.fp, &f.fp.use));
+    if (f.fp.use) {
+        const trc_fp_host &H = *E.fp;
+        f.fp = {true, SP0.fp.n_list, H.P.M, H.P.Mc, H.P.has_generic != 0, H.P.cdf_end, H.coverage, H.ucoverage, E.d_fp_umask.get() ? (int)H.umask.size() : 0, H.Mu, H.Mv};
+    }
+    // 2. the decisions
+    trc_stream_forms &D = F.D;
+    if (!trc_stream_decide(f, plan, &D)) return trc_fail(TRC_ERR_UNSUPPORTED, "no shading kernel for device material tables beside a chart flux map");
+    SP0.search = D.search; SP0.lds_recs = D.lds_recs; SP0.P.lds_tally = D.lds_tally; SP0.lds_tables = D.lds_tables; SP0.lds_extra = D.lds_extra;
+    SP0.lds_fm_bins = D.lds_fm_bins; SP0.bg_occ_words = D.bg_occ_words; SP0.shade_term_cls = D.shade_term_cls; SP0.split_terminal = D.split_terminal;
+    SP0.hit_epoch = sc->hits.epoch;
+    SP0.chunk_hitbuf = sc->hits.chunk_size();
+    // 3. and 4. the instances, their grid caps and their LDS
+    TRC_TRY(stream_stage(F.gen0, D.gen0, n_cu, false, 0));
+    TRC_TRY(stream_stage(F.gen, D.gen, n_cu, false, 0));
+    TRC_TRY(stream_stage(F.walk, D.walk, n_cu, true, D.walk.lds));
+    TRC_TRY(stream_stage(F.exact, D.exact, n_cu, false, 0));
     F.g_wide = (unsigned)(n_cu * 8);     // 256-thread blocks: 4 waves each, <= 16384 waves in all
     F.g_gen = (unsigned)(n_cu * 8);
-    return TRC_OK;
-}
-
-static int stream_shade_grid(StreamShadeK &K, int n_cu) {
-    TRC_TRY(kernel_grid_cap(K.fn, (int)K.threads, K.lds, 2048 / (int)K.threads, n_cu, &K.max_blocks));
-    if ((unsigned long long)K.max_blocks * K.wpb > SHADE_MAX_WAVES) K.max_blocks = SHADE_MAX_WAVES / K.wpb;
-    return TRC_OK;
-}
-
-// The shading kernels: one per optics class present in the scene (trc_shade.hip), each taking its hits off the bounce's list, or one
-// for every hit (k_s_shade_x) when the rays carry more than the fast engine's record.
-// (split: some optics of the scene send two rays on from a hit -- a carry call served by k_s_shade_x<.., SPLIT>)
-static int stream_form_shade(StreamForms &F, StreamParams &SP0, const trc_scene *sc, bool carry, bool split_rays) {
-    const int n_cu = sc->ctx->n_cu;
-    const int S = sc->n_surf;
-    const long long bins = flux_map_bins(sc);
-    // k_s_shade, or k_s_shade_x for rays that carry more (the same image): tallies, records, optics parameters, flux-map tables, flags
-    // and table values in LDS -- all of them or none (its LDS instance knows the address space of every table; see the kernel) -- and
-    // the flux-map bins too while a workgroup stays within half a CU's LDS (two workgroups per CU)
-    bool shade_lds;
-    const size_t lds_shade = shade_lds_choose(sc, carry ? TRC_IMG_SHADE_X : TRC_IMG_SHADE, bins, &shade_lds, &SP0.lds_fm_bins);
-    SP0.P.lds_tally = SP0.lds_tables = SP0.lds_extra = shade_lds ? 1 : 0;
-    // scenes of flat surfaces with mirror / diffuse optics only (heliostat fields, plate cavities): the lean instance
-    bool shade_simple = true;
-    for (int i = 0; i < S && shade_simple; ++i)
-        shade_simple = trc_gm_is_flat(sc->surfs[i].gm_kind) && ((TRC_OPT_SIMPLE_MASK >> sc->surfs[i].optics_kind) & 1u);
-    // (instances built for 3 and 4 waves per SIMD -- 168 / 128 registers, 228 / 376 bytes of scratch per lane -- were slower:
-    // 3.09 and 2.70 ms per NSTTF step against 2.54; later, without anything fetched ahead and with the incidence-angle factor out
-    // of line, 192 / 336 bytes and 2.33 / 2.35 ms against 1.99.  The registers are held by the optics code as a whole -- an instance
-    // that only knows Transparent needs none of the spills -- and it does not yield to the obvious: lighter sine / cosine / tangent
-    // kernels for bounded arguments made it worse (their float64 constants live in scalar registers, which then spill into vector
-    // ones))
-    const bool spec = SP0.P.spec != nullptr;      // (a source with a spectrum: the instances that draw the wavelength at the first hit)
-    // A flux map in another chart than XY: the instances that know the charts -- of k_s_shade and of the lean kernels the ones for
-    // any geometry and any optics, which serve flat mirrors and walls with the same arithmetic.  Hits on surfaces that end every ray
-    // go to the shading kernels in such a scene (stream_form_absorb): k_s_absorb and k_s_bounce have no such instance.
-    const bool chart = scene_has_chart_map(sc);
-    if (chart) shade_simple = false;
-    const void *shade_fn = chart ? (spec ? (shade_lds ? (const void *)k_s_shade<false, 2, true, true, true> : (const void *)k_s_shade<false, 2, false, true, true>)
-                                         : (shade_lds ? (const void *)k_s_shade<false, 2, true, false, true> : (const void *)k_s_shade<false, 2, false, false, true>))
-                         : spec ? (shade_simple ? (shade_lds ? (const void *)k_s_shade<true, 2, true, true> : (const void *)k_s_shade<true, 2, false, true>)
-                                                : (shade_lds ? (const void *)k_s_shade<false, 2, true, true> : (const void *)k_s_shade<false, 2, false, true>))
-                                : shade_simple ? (shade_lds ? (const void *)k_s_shade<true, 2, true> : (const void *)k_s_shade<true, 2, false>)
-                                               : (shade_lds ? (const void *)k_s_shade<false, 2, true> : (const void *)k_s_shade<false, 2, false>);
-    int n_shk = 0;
-    int term_cls = -1;
-    const bool split = !carry;
-    bool present[TRC_CLS_COUNT] = {false, false, false};
-    if (split) {
-        // a surface that ends every ray (TRC_SURF_TERMINAL) needs no optics when a ray of energy 0 ends in the reference too
-        // (0 <= min_energy): its hits go to a class that is there anyway
-        const bool term_ok = SP0.P.min_energy >= 0.0;
-        bool any_term = false;
-        for (int i = 0; i < S; ++i) {
-            const trc_surface_desc &sd = sc->surfs[i];
-            if (term_ok && surface_ends_every_ray(sd)) any_term = true;
-            else present[trc_shade_class_of(sd)] = true;
-        }
-        if (any_term) {
-            term_cls = present[TRC_CLS_MIRROR] ? TRC_CLS_MIRROR : present[TRC_CLS_DIFFUSE] ? TRC_CLS_DIFFUSE : -1;
-            if (term_cls < 0)          // nothing lean among the others: the terminal surfaces go by their own class
-                for (int i = 0; i < S; ++i) present[trc_shade_class_of(sc->surfs[i])] = true;
-        }
-        const bool all_flat = !chart && all_surfaces_flat(sc);
-        for (int c = 0; c < TRC_CLS_GENERAL; ++c) {
-            if (!present[c]) continue;
-            StreamShadeK &K = F.shk[n_shk++];
-            K.cls = c; K.threads = SHC_THREADS; K.wpb = SHC_THREADS / 64;
-            bool in_lds;
-            K.lds = shade_lds_choose(sc, c == TRC_CLS_MIRROR ? TRC_IMG_LEAN_MIRROR : TRC_IMG_LEAN, bins, &in_lds, &K.lds_fm_bins);
-            K.lds_tables = in_lds ? 1 : 0;
-            K.fn = trc_shade_lean_kernel(c, all_flat, in_lds, spec, chart);
-            TRC_TRY(stream_shade_grid(K, n_cu));
-        }
+    for (int q = 0; q < D.n_shk; ++q) {
+        const trc_shade_stage &s = D.shk[q];
+        StreamKernel k;
+        // k_s_shade: 2 waves per SIMD, four workgroups of 256 per CU in two rounds; the others by their occupancy, within the waves
+        // that may keep a chunk of the hit buffer open
+        const bool cap = s.id.family != TRC_K_SHADE;
+        TRC_TRY(stream_stage(k, {s.id, s.threads, s.lds}, n_cu, cap, s.lds));
+        StreamShadeK &K = F.shk[q];
+        K = {s.cls, k.fn, (unsigned)s.threads, (unsigned)s.threads / 64, cap ? k.max_blocks : (unsigned)(n_cu * 4), s.lds, s.lds_tables, s.lds_fm_bins};
+        if (cap && (unsigned long long)K.max_blocks * K.wpb > SHADE_MAX_WAVES) K.max_blocks = SHADE_MAX_WAVES / K.wpb;
     }
-    if (!split || present[TRC_CLS_GENERAL]) {
-        StreamShadeK &K = F.shk[n_shk++];
-        K.cls = split ? TRC_CLS_GENERAL : -1;
-        // 2 waves per SIMD: four workgroups of 256 per CU in two rounds
-        K.fn = shade_fn; K.threads = 256; K.wpb = 4; K.max_blocks = (unsigned)(n_cu * 4); K.lds = lds_shade;
-        K.lds_tables = SP0.lds_tables; K.lds_fm_bins = SP0.lds_fm_bins;
-        if (carry) {            // sixteen waves per workgroup
-            // (CarryIn.mat_tab: the materials' tables are on the device and the call brings no rows -- the MAT instances)
-            K.fn = trc_shade_carry_kernel(shade_lds, chart, split_rays, SP0.carry.mat_tab != nullptr);
-            if (!K.fn) return trc_fail(TRC_ERR_UNSUPPORTED, "no shading kernel for device material tables beside a chart flux map");
-            K.threads = SHC_THREADS; K.wpb = SHC_THREADS / 64;
-            TRC_TRY(stream_shade_grid(K, n_cu));
-        } else
-            TRC_TRY(kernel_allow_lds(K.fn, K.lds));
-    }
-    F.n_shk = n_shk;
-    F.multi = n_shk > 1;
-    SP0.shade_term_cls = term_cls;
-    SP0.chunk_hitbuf = sc->hits.chunk_size();
-    return TRC_OK;
-}
-
-// Dynamic LDS of a search kernel from its image (trc_search_lds_layout): what a fits-in-LDS decision compares with its limit, and what
-// a launch asks for -- 16 bytes more, so that it is never 0 and a block the kernel puts behind the image can start on 16 bytes
-static size_t lds_need(const trc_lds_layout &L) { return L.end + L.slack; }
-static size_t lds_request(const trc_lds_layout &L) { return lds_need(L) + 16; }
-
-// fresh rays of a plane source with a narrow cone: footprint map, k_s_cull + k_s_fresh (trc_footprint.h)
-static int stream_form_fresh(StreamForms &F, StreamParams &SP0, trc_scene *sc, StreamEngine &E, const trc_source_desc *src_desc, const StreamKnobs &K) {
-    F.general_share = 0.0; F.listed_share = 1.0;
-    TRC_TRY(stream_fp_prepare(sc, E, src_desc, K, &SP0.fp, &F.use_fp));
-    if (!F.use_fp) return TRC_OK;
-    const int n_cu = sc->ctx->n_cu;
-    const int S = sc->n_surf;
-    const int src_kind = F.src_kind;
-    const bool buie = src_kind == TRC_SRC_BUIE_DISK || src_kind == TRC_SRC_BUIE_RECT;
-    const bool flat = all_surfaces_flat(sc);
-    const int sf_threads = SF_THREADS(flat);
-    // k_s_fresh: the tables every listed ray reads go to LDS when they all fit (one workgroup per CU)
-    bool fresh_in_lds = false;
-    // the Buie sources go through the two-phase form (k_s_fresh2): a queue of SFQ_CAP (ray, cell) pairs per wave
-    const bool fresh_two = buie;
-    // (the kernels' own description of their LDS image; the lists are 16-bit there)
-    const size_t n_list = E.fp->clist.size();
-    const int queue_waves = fresh_two ? sf_threads / 64 : 0;
-    if (n_list < 65536) fresh_in_lds = lds_need(trc_search_lds_layout(fresh_lds_parts(S, sc->stride, SP0.fp.P, (long long)n_list, buie, true, queue_waves))) <= 150 * 1024;
-    const size_t lds_fresh = lds_request(trc_search_lds_layout(fresh_lds_parts(S, sc->stride, SP0.fp.P, (long long)n_list, buie, fresh_in_lds, queue_waves)));
-#define SF_PICK(K) (flat ? (fresh_in_lds ? (const void *)k_s_fresh<K, true, true> : (const void *)k_s_fresh<K, true, false>) \
-                         : (fresh_in_lds ? (const void *)k_s_fresh<K, false, true> : (const void *)k_s_fresh<K, false, false>))
-    // (the tabulated sunshapes: the general <kind, flat, lds> form, their table read from global memory, where it stays in L2)
-    const void *fresh1_fn = src_kind == TRC_SRC_BUIE_DISK ? SF_PICK(TRC_SRC_BUIE_DISK) : src_kind == TRC_SRC_BUIE_RECT ? SF_PICK(TRC_SRC_BUIE_RECT)
-                          : src_kind == TRC_SRC_SUNSHAPE_DISK ? SF_PICK(TRC_SRC_SUNSHAPE_DISK) : src_kind == TRC_SRC_SUNSHAPE_RECT ? SF_PICK(TRC_SRC_SUNSHAPE_RECT)
-                          : src_kind == TRC_SRC_PILLBOX_DISK ? SF_PICK(TRC_SRC_PILLBOX_DISK) : SF_PICK(TRC_SRC_PILLBOX_RECT);
-#undef SF_PICK
-#define SF2_PICK(K) (flat ? (fresh_in_lds ? (const void *)k_s_fresh2<K, true, true> : (const void *)k_s_fresh2<K, true, false>) \
-                          : (fresh_in_lds ? (const void *)k_s_fresh2<K, false, true> : (const void *)k_s_fresh2<K, false, false>))
-    const void *fresh_fn = !fresh_two ? fresh1_fn : src_kind == TRC_SRC_BUIE_DISK ? SF2_PICK(TRC_SRC_BUIE_DISK) : SF2_PICK(TRC_SRC_BUIE_RECT);
-#undef SF2_PICK
-    const void *cull_fn = src_kind == TRC_SRC_BUIE_DISK ? (const void *)k_s_cull<TRC_SRC_BUIE_DISK> : src_kind == TRC_SRC_BUIE_RECT ? (const void *)k_s_cull<TRC_SRC_BUIE_RECT>
-                        : src_kind == TRC_SRC_SUNSHAPE_DISK ? (const void *)k_s_cull<TRC_SRC_SUNSHAPE_DISK>
-                        : src_kind == TRC_SRC_SUNSHAPE_RECT ? (const void *)k_s_cull<TRC_SRC_SUNSHAPE_RECT>
-                        : src_kind == TRC_SRC_PILLBOX_DISK ? (const void *)k_s_cull<TRC_SRC_PILLBOX_DISK> : (const void *)k_s_cull<TRC_SRC_PILLBOX_RECT>;
-    const size_t lds_cull = (size_t)SP0.fp.P.M * SP0.fp.P.M / 8 + (SC_GEN_CAP + 4) * 4;
-    if (lds_cull > LDS_MAX_ALLOWED || lds_fresh > LDS_MAX_ALLOWED) { F.use_fp = false; return TRC_OK; }
-    // The mask over the uniforms, for the listed rays that k_s_fresh2 takes: it finds its list cell itself.  k_s_fresh (the
-    // pillbox kinds, the tabulated sunshapes, a Buie source whose listed rays mostly hit) and the instances of k_s_fresh2 that
-    // do not derive the cell (SF2_DERIVES_CELL) are handed it by the other form.
-    F.cull_u = {nullptr, SC_THREADS, 0, 0u};
-    F.ulisted_share = 1.0;
-    memset(&F.cull_up, 0, sizeof(F.cull_up));
-    if (fresh_two && SF2_DERIVES_CELL(flat, fresh_in_lds) && K.umask && E.d_fp_umask.get()) {
-        F.cull_u.fn = src_kind == TRC_SRC_BUIE_DISK ? (const void *)k_s_ucull<TRC_SRC_BUIE_DISK> : (const void *)k_s_ucull<TRC_SRC_BUIE_RECT>;
-        F.cull_u.lds = E.fp->umask.size() * 4 + (SC_GEN_CAP + 4) * 4;      // (at most what the Cartesian mask takes: Mu Mv <= M M)
+    TRC_TRY(stream_stage(F.cull, D.cull, n_cu, true, D.cull.lds));
+    TRC_TRY(stream_stage(F.fresh, D.fresh, n_cu, true, D.fresh.lds));
+    if (trc_kid_equal(D.fresh_one.id, D.fresh.id)) F.fresh_one = {F.fresh.fn, F.fresh.threads, F.fresh.lds, 0u};
+    else TRC_TRY(stream_stage(F.fresh_one, D.fresh_one, n_cu, false, 0));
+    TRC_TRY(stream_stage(F.cull_u, D.cull_u, n_cu, true, D.cull_u.lds));
+    if (F.cull_u.fn) {
         CullParams &U = F.cull_up;
         U.mask = E.d_fp_umask.get(); U.mask_words = (int)E.fp->umask.size();
-        for (U.lu = 0; (1 << U.lu) < E.fp->Mu; ++U.lu) {}
-        for (U.lv = 0; (1 << U.lv) < E.fp->Mv; ++U.lv) {}
+        U.lu = D.cull_lu; U.lv = D.cull_lv;
         bool on;
         U.gen_thr = trc_fp_generic_threshold(SP0.fp.P, &on);
         U.gen_on = on ? 1 : 0;
-        F.ulisted_share = E.fp->ucoverage > 1.0 ? 1.0 : E.fp->ucoverage;
-        TRC_TRY(kernel_grid_cap(F.cull_u.fn, SC_THREADS, F.cull_u.lds, 2048 / SC_THREADS, n_cu, &F.cull_u.max_blocks));
     }
-    F.fresh = {fresh_fn, sf_threads, lds_fresh, 0u};
-    F.fresh_one = {fresh1_fn, sf_threads, lds_fresh, 0u};
-    F.cull = {cull_fn, SC_THREADS, lds_cull, 0u};
-    TRC_TRY(kernel_grid_cap(fresh_fn, sf_threads, lds_fresh, 2048 / sf_threads, n_cu, &F.fresh.max_blocks));
-    if (fresh1_fn != fresh_fn) TRC_TRY(kernel_allow_lds(fresh1_fn, lds_fresh));
-    TRC_TRY(kernel_grid_cap(cull_fn, SC_THREADS, lds_cull, 2048 / SC_THREADS, n_cu, &F.cull.max_blocks));
-    F.general_share = SP0.fp.P.has_generic ? (1.0 - SP0.fp.P.cdf_end) : 0.0;
-    if (F.general_share < 0.0) F.general_share = 0.0;
-    F.listed_share = E.fp->coverage * (src_kind == TRC_SRC_BUIE_DISK || src_kind == TRC_SRC_PILLBOX_DISK || src_kind == TRC_SRC_SUNSHAPE_DISK ? 4.0 / TRC_PI : 1.0);
-    if (F.listed_share > 1.0) F.listed_share = 1.0;
+    // (k_s_bounce keeps the grid cap of its LDS without k_s_absorb's tables)
+    TRC_TRY(stream_stage(F.bounce, D.bounce, n_cu, true, D.bounce.lds - D.lds_inline));
+    TRC_TRY(stream_stage(F.first, D.first, n_cu, true, D.first.lds));
+    // k_s_absorb: one workgroup of 16 waves per CU (4096 waves with open chunks of the hit buffer at most)
+    TRC_TRY(stream_stage(F.absorb, D.absorb, n_cu, false, 0));
+    if (F.absorb.fn) F.absorb.max_blocks = (unsigned)n_cu;
     return TRC_OK;
-}
-
-// Continued rays (bounces >= 1): one kernel per bounce on the grid / all-boxes forms (k_s_bounce); the Kd walk of
-// TRC_STREAM_SEARCH=1 keeps the queues.  Fresh rays outside the footprint map go through k_s_bounce<.., FRESH> instead of the
-// general path in large scenes and in small ones.
-static int stream_form_bounce(StreamForms &F, StreamParams &SP0, const trc_scene *sc, const StreamPlan &plan, const StreamKnobs &K) {
-    const int n_cu = sc->ctx->n_cu;
-    const int S = sc->n_surf;
-    const bool big = !plan.walk_ok;
-    F.use_fused = plan.mode != 1 && (K.bounce || big);
-    F.use_first = big || F.small_scene || (K.first && plan.mode != 1);
-    if (!F.use_fused && !F.use_first) return TRC_OK;
-    const int gridm = F.gridm;
-    // One decision for the instance of the continued rays and that of the fresh ones: the tables go to LDS when an image with the
-    // parts of both (the Buie table of the one, the flags of the other) fits; the fresh instance is sized by that image
-    const int g_cells = plan.mode == 2 ? (int)sc->accel.grid_off.size() - 1 : 0, g_list = (int)sc->accel.grid_list.size();
-    const bool in_lds = gridm != 2 && gridm != 3 && lds_need(trc_search_lds_layout(bounce_lds_parts(S, sc->stride, true, true, true, g_cells, g_list, 0, 0))) <= 150 * 1024;
-    SP0.bg_occ_words = 0;
-    // the large grid: k_s_bounce_coop, whose lanes share the tests of their wave's rays
-    const bool coop = F.coop = gridm == 2 && K.coop;
-    if (gridm == 2 && sc->accel.big_occ.size() * 4 <= (coop ? 80 : 96) * 1024) SP0.bg_occ_words = (int)sc->accel.big_occ.size();      // the occupancy bits of the large grid
-    const int coop_waves = coop ? SB_THREADS / 64 : 0;
-    const size_t lds_bounce = lds_request(trc_search_lds_layout(bounce_lds_parts(S, sc->stride, false, in_lds, in_lds, in_lds ? g_cells : 0, g_list, SP0.bg_occ_words, coop_waves)));
-    const size_t lds_first = lds_request(trc_search_lds_layout(bounce_lds_parts(S, sc->stride, true, in_lds, in_lds, in_lds ? g_cells : 0, g_list, SP0.bg_occ_words, coop_waves)));
-#define SB_PICK(FR, FL, SN) (gridm == 3 ? (const void *)k_s_bounce<3, false, FR, FL, SN> : gridm == 2 ? (coop ? (const void *)k_s_bounce_coop<FR, FL, SN> : (const void *)k_s_bounce<2, false, FR, FL, SN>) \
-                           : gridm == 1 ? (in_lds ? (const void *)k_s_bounce<1, true, FR, FL, SN> : (const void *)k_s_bounce<1, false, FR, FL, SN>) \
-                                        : (in_lds ? (const void *)k_s_bounce<0, true, FR, FL, SN> : (const void *)k_s_bounce<0, false, FR, FL, SN>))
-    const bool all_flat = all_surfaces_flat(sc);
-    const void *bounce_fn = all_flat ? SB_PICK(false, true, false) : SB_PICK(false, false, false);
-    // (fresh rays of a tabulated sunshape: the instances that know it)
-    const bool sun = F.src_kind == TRC_SRC_SUNSHAPE_DISK || F.src_kind == TRC_SRC_SUNSHAPE_RECT;
-    const void *first_fn = sun ? (all_flat && gridm == 2 && coop ? (const void *)k_s_bounce_coop<true, true, true> : SB_PICK(true, false, true))
-                               : (all_flat && gridm == 2 && coop ? (const void *)k_s_bounce_coop<true, true> : SB_PICK(true, false, false));
-#undef SB_PICK
-    F.bounce = {bounce_fn, SB_THREADS_OF(gridm), lds_bounce, 0u};
-    F.first = {first_fn, SB_THREADS_OF(gridm), lds_first, 0u};
-    TRC_TRY(kernel_grid_cap(bounce_fn, F.bounce.threads, lds_bounce, 2048 / F.bounce.threads, n_cu, &F.bounce.max_blocks));
-    TRC_TRY(kernel_grid_cap(first_fn, F.first.threads, lds_first, 2048 / F.first.threads, n_cu, &F.first.max_blocks));
-    return TRC_OK;
-}
-
-// Hits on surfaces that end every ray (the receiver of a field) are listed apart by k_s_bounce and finished by k_s_absorb -- when
-// the scene has such surfaces and k_s_absorb's tables (those of k_s_shade without records and optics) fit LDS -- or finished inside
-// k_s_bounce when its workgroup has the LDS for the tallies, flux-map tables and bins as well (TRC_STREAM_ABSORB=1: always behind
-// the list, by k_s_absorb).
-static int stream_form_absorb(StreamForms &F, StreamParams &SP0, const trc_scene *sc, bool carry, const StreamKnobs &K) {
-    if (!(F.use_fused && SP0.P.lds_tally && SP0.lds_tables && !carry)) return TRC_OK;
-    bool any = false;
-    for (int i = 0; i < sc->n_surf && !any; ++i) any = surface_ends_every_ray(sc->surfs[i]);
-    const long long bins = flux_map_bins(sc);
-    const size_t lds_absorb = shade_lds_need(shade_lds_parts(sc, TRC_IMG_ABSORB, true, SP0.lds_fm_bins));
-    const bool fm_ok = bins == 0 || SP0.lds_fm_bins > 0;       // (bins outside LDS would be scattered global atomics at eight waves per SIMD: not this kernel;
-                                                                // nor a map in another chart than XY: k_s_absorb and k_s_bounce bin in x, y only)
-    F.use_absorb = any && fm_ok && !scene_has_chart_map(sc) && lds_absorb <= trc_shade_lds_limit(TRC_IMG_ABSORB, true) && sc->tr_off < 0 && SP0.P.min_energy >= 0.0 && K.absorb != 0;      // (0 <= min_energy: the ray ends there in the reference too)
-    if (!F.use_absorb) return TRC_OK;
-    // one workgroup of 16 waves per CU (4096 waves with open chunks of the hit buffer at most)
-    F.absorb = {(const void *)k_s_absorb, SA_THREADS, lds_absorb, (unsigned)sc->ctx->n_cu};
-    TRC_TRY(kernel_allow_lds(F.absorb.fn, lds_absorb));
-    SP0.split_terminal = 1;
-    const size_t extra_lds = shade_lds_need(shade_lds_parts(sc, TRC_IMG_INLINE, true, SP0.lds_fm_bins));
-    if (K.absorb != 1 && !(F.gridm == 2 && F.coop) && F.bounce.lds + extra_lds <= trc_shade_lds_limit(TRC_IMG_INLINE, true)) {
-        // (k_s_bounce keeps the grid cap of its LDS without these tables)
-        F.absorb_inline = true;
-        F.bounce.lds += extra_lds;
-        TRC_TRY(kernel_allow_lds(F.bounce.fn, F.bounce.lds));
-        SP0.split_terminal = 2;
-    }
-    return TRC_OK;
-}
-
-// Chooses the kernel of every stage for this call and sets up SP0, the parameters every batch starts from
-static int stream_choose_forms(StreamForms &F, StreamParams &SP0, trc_scene *sc, StreamEngine &E, const StreamPlan &plan, bool carry, bool split_rays,
-                               const trc_source_desc *src_desc, const StreamKnobs &K) {
-    const int S = sc->n_surf;
-    memset(&F, 0, sizeof(F));
-    F.src_kind = src_desc ? src_desc->kind : -1;
-    F.gridm = plan.mode == 2 ? 1 : (plan.mode == 3 ? 2 : 0);
-    // a few surfaces: neither grid nor lists, the wave takes the surfaces one by one (k_s_bounce<3>) -- up to four surfaces (a
-    // dish and its receiver), where every lane tests every surface anyway and the form pays: 0.50 against 0.58 ms per bounce of
-    // 1e7 rays.  (Measured on the seven-wall cavity, one batch alone: 1.15 ms per bounce surface by surface against 0.96 ms lane by
-    // lane -- every wave runs all seven exact tests where its lanes needed four or five each.)
-    F.small_scene = S <= STREAM_SMALL_SURFACES && plan.mode != 1 && plan.walk_ok;
-    if (F.small_scene && S <= 4) F.gridm = 3;
-    SP0.search = plan.walk_ok ? plan.mode : 2;
-    SP0.hit_epoch = sc->hits.epoch;
-    TRC_TRY(stream_form_general(F, SP0, sc, plan));
-    TRC_TRY(stream_form_shade(F, SP0, sc, carry, split_rays));
-    TRC_TRY(stream_form_fresh(F, SP0, sc, E, src_desc, K));
-    TRC_TRY(stream_form_bounce(F, SP0, sc, plan, K));
-    return stream_form_absorb(F, SP0, sc, carry, K);
 }
 
 // workspaces of the slots for batches of `cap` rays: queues, spectra of the rays under way, the class lists of k_s_partition
@@ -2579,9 +2345,9 @@ static int stream_slots_alloc(StreamEngine &E, int n_slots, long long cap, const
             Tk.rid_len = Tk.W.room;
         }
         StreamBuffers &Wk = Tk.W;
-        if (!F.multi) continue;
+        if (!F.D.multi) continue;
         Wk.pl_room = 2 * Wk.room;
-        for (int q = 0; q < F.n_shk; ++q) {
+        for (int q = 0; q < F.D.n_shk; ++q) {
             const int c = F.shk[q].cls;
             if (Wk.pl_t[c]) continue;      // (the last of the three made: a list half made is made again)
             TRC_TRY(Wk.pl_slot[c].alloc((size_t)Wk.pl_room));
@@ -2627,10 +2393,10 @@ static void plan_bounce(const StreamCall &C, StreamSlot &T) {
         return u < floor ? floor : u;
     };
     const int sf_threads = F.fresh.threads, sb_threads = F.bounce.threads, first_threads = F.first.threads;
-    T.fresh = F.use_fp && T.b == 0;
-    T.fused = F.use_fused && T.b > 0;
-    T.first = F.use_first && T.b == 0 && (!T.fresh || F.general_share > 0.0);
-    T.general = !T.fused && !T.first && (!T.fresh || F.general_share > 0.0);
+    T.fresh = F.D.use_fp && T.b == 0;
+    T.fused = F.D.use_fused && T.b > 0;
+    T.first = F.D.use_first && T.b == 0 && (!T.fresh || F.D.general_share > 0.0);
+    T.general = !T.fused && !T.first && (!T.fresh || F.D.general_share > 0.0);
     T.gb_bounce = T.fused ? grid_for(F.bounce.max_blocks, sb_threads) : 0u;
     T.gb_cull = T.fresh ? grid_for(F.cull.max_blocks, SC_THREADS * 8) : 0u;
     T.SP.chunk_hit = T.SP.chunk_slot = T.SP.chunk_act = T.SP.chunk_first = T.SP.chunk_thit = SQ_CHUNK;
@@ -2644,22 +2410,22 @@ static void plan_bounce(const StreamCall &C, StreamSlot &T) {
         // the two-phase form pays where most listed rays miss (a field of mirrors: two of three); where most of them hit (a dish
         // under its own source: the first phase rejects nothing) the batches after the first go back to k_s_fresh, which is
         // handed its cells by k_s_cull on the Cartesian mask
-        const bool mostly_hits = E.fp_hit_rate > 0.0 && E.fp_hit_rate > 0.6 * 1.15 * F.listed_share;
+        const bool mostly_hits = E.fp_hit_rate > 0.0 && E.fp_hit_rate > 0.6 * 1.15 * F.D.listed_share;
         T.umask = F.cull_u.fn != nullptr && !mostly_hits;
         T.fresh_one = mostly_hits;
         if (T.umask) T.gb_cull = grid_for(F.cull_u.max_blocks, SC_THREADS * 8);
         // (the mask over the uniforms lists somewhat more rays than the Cartesian one: its lists and grids are sized by its own share)
-        const double listed = (T.umask ? F.ulisted_share : F.listed_share) * (double)T.nb;
+        const double listed = (T.umask ? F.D.ulisted_share : F.D.listed_share) * (double)T.nb;
         T.gb_fresh = clamp_grid(((long long)(1.2 * listed) + 4096 + sf_threads * 2 - 1) / (sf_threads * 2), F.fresh.max_blocks);
         T.cull_chunk = chunk_for(1.1 * listed, (unsigned long long)T.gb_cull * (SC_THREADS / 64));
         // general-path rays: rare -> per workgroup through LDS; a source with a strong aureole (CSR 0.3: a third of the rays) ->
         // chunks per wave like the other lists
-        if (F.general_share * (double)T.nb / (double)T.gb_cull > 0.25 * SC_GEN_CAP)
-            T.cull_gen_chunk = chunk_for(1.1 * F.general_share * (double)T.nb, (unsigned long long)T.gb_cull * (SC_THREADS / 64));
+        if (F.D.general_share * (double)T.nb / (double)T.gb_cull > 0.25 * SC_GEN_CAP)
+            T.cull_gen_chunk = chunk_for(1.1 * F.D.general_share * (double)T.nb, (unsigned long long)T.gb_cull * (SC_THREADS / 64));
         // hits of the fresh rays: measured on the batches before (E.fp_hit_rate), every listed ray to start with
-        const double hits = (E.fp_hit_rate > 0.0 ? E.fp_hit_rate : (T.umask ? F.ulisted_share : F.listed_share)) * (double)T.nb;
+        const double hits = (E.fp_hit_rate > 0.0 ? E.fp_hit_rate : (T.umask ? F.D.ulisted_share : F.D.listed_share)) * (double)T.nb;
         T.SP.chunk_hit = T.SP.chunk_slot = chunk_for(hits, (unsigned long long)T.gb_fresh * (unsigned long long)(sf_threads / 64));
-        act_expected = hits + 2.0 * F.general_share * (double)T.nb;
+        act_expected = hits + 2.0 * F.D.general_share * (double)T.nb;
     } else {
         T.gb_fresh = 0u;
         if (T.fused) {    // at most the rays that entered the bounce hit, at most those go on
@@ -2675,7 +2441,7 @@ static void plan_bounce(const StreamCall &C, StreamSlot &T) {
         }
     }
     // behind k_s_cull the general path only sees the rays left to it (the Buie aureole)
-    if (T.fresh) work = (long long)(1.5 * F.general_share * (double)T.nb) + 4096;
+    if (T.fresh) work = (long long)(1.5 * F.D.general_share * (double)T.nb) + 4096;
     if (T.first) {
         T.gb_first = grid_for(F.first.max_blocks, first_threads);
         T.SP.chunk_first = chunk_for((double)work, (unsigned long long)T.gb_first * (first_threads / 64));      // at most every ray hits
@@ -2687,10 +2453,10 @@ static void plan_bounce(const StreamCall &C, StreamSlot &T) {
         long long entries_of[TRC_CLS_COUNT] = {shade_entries, shade_entries, shade_entries};
         T.gb_part = 0u;
         for (int c = 0; c < TRC_CLS_COUNT; ++c) { T.part_start[c] = 0ull; T.SP.part_chunk[c] = SQ_CHUNK_MAX; T.SP.part_static[c] = 0; }
-        if (F.multi) {
+        if (F.D.multi) {
             T.gb_part = clamp_grid((shade_entries + 256ll * SW_ITEMS - 1) / (256ll * SW_ITEMS), F.g_wide);
             const unsigned long long pw = (unsigned long long)T.gb_part * 4ull;
-            for (int k = 0; k < F.n_shk; ++k) {
+            for (int k = 0; k < F.D.n_shk; ++k) {
                 const int c = F.shk[k].cls;
                 if (!(C.K.static_chunks && T.b < STREAM_RATE_BOUNCES && E.rate_cls[T.b][c] >= 0.0)) continue;      // share not known yet: the waves reserve as they go
                 double cc = 1.1 * E.rate_cls[T.b][c] * rays_in0 / (double)pw + 128.0;
@@ -2705,9 +2471,9 @@ static void plan_bounce(const StreamCall &C, StreamSlot &T) {
             }
         }
         unsigned long long total_waves = 0;
-        for (int k = 0; k < F.n_shk; ++k) {
+        for (int k = 0; k < F.D.n_shk; ++k) {
             const long long per = (long long)F.shk[k].threads * SW_ITEMS;
-            const long long shade_entries_k = F.multi ? entries_of[F.shk[k].cls] : shade_entries;
+            const long long shade_entries_k = F.D.multi ? entries_of[F.shk[k].cls] : shade_entries;
             T.gb_sh[k] = clamp_grid((shade_entries_k + per - 1) / per, F.shk[k].max_blocks);
             total_waves += (unsigned long long)T.gb_sh[k] * F.shk[k].wpb;
         }
@@ -2715,7 +2481,7 @@ static void plan_bounce(const StreamCall &C, StreamSlot &T) {
                             (double)(total_waves ? total_waves : 1ull);
         const double rays_in = T.b == 0 ? (double)T.nb : (double)T.n_in;
         long long base = 0;
-        for (int k = 0; k < F.n_shk; ++k) {
+        for (int k = 0; k < F.D.n_shk; ++k) {
             const unsigned long long waves = (unsigned long long)T.gb_sh[k] * F.shk[k].wpb;
             unsigned chunk = SQ_CHUNK;
             if (act_expected >= 0.0) {
@@ -2788,26 +2554,17 @@ static int launch_bounce(StreamCall &C, StreamSlot &T) {
     if (T.fused) { TRC_TRY(launch_kernel(F.bounce, T.gb_bounce, SP, T.stream.get())); C.launches += 1; }
     if (T.first) { TRC_TRY(launch_kernel(F.first, T.gb_first, SP, T.stream.get())); C.launches += 1; }
     if (T.general) {
-        const int src_kind = F.src_kind;
-        const unsigned gb_gen = T.gb_gen;
-        if (T.b == 0 && src_kind == TRC_SRC_BUIE_DISK) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_BUIE_DISK>, dim3(gb_gen), dim3(256), 0, T.stream.get(), SP);
-        else if (T.b == 0 && src_kind == TRC_SRC_BUIE_RECT) hipLaunchKernelGGL((k_s_gen<true, TRC_SRC_BUIE_RECT>), dim3(gb_gen), dim3(256), 0, T.stream.get(), SP);
-        else if (T.b == 0 && src_kind == TRC_SRC_PILLBOX_DISK) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_PILLBOX_DISK>, dim3(gb_gen), dim3(256), 0, T.stream.get(), SP);
-        else if (T.b == 0 && src_kind == TRC_SRC_PILLBOX_RECT) hipLaunchKernelGGL(k_s_gen_src<TRC_SRC_PILLBOX_RECT>, dim3(gb_gen), dim3(256), 0, T.stream.get(), SP);
-        else if (T.b == 0 && src_kind == TRC_SRC_SUNSHAPE_DISK) hipLaunchKernelGGL((k_s_gen<true, TRC_SRC_SUNSHAPE_DISK>), dim3(gb_gen), dim3(256), 0, T.stream.get(), SP);
-        else if (T.b == 0 && src_kind == TRC_SRC_SUNSHAPE_RECT) hipLaunchKernelGGL((k_s_gen<true, TRC_SRC_SUNSHAPE_RECT>), dim3(gb_gen), dim3(256), 0, T.stream.get(), SP);
-        else if (T.b == 0) hipLaunchKernelGGL(k_s_gen<true>, dim3(gb_gen), dim3(256), 0, T.stream.get(), SP);
-        else hipLaunchKernelGGL(k_s_gen<false>, dim3(gb_gen), dim3(256), 0, T.stream.get(), SP);
+        TRC_TRY(launch_kernel(T.b == 0 ? F.gen0 : F.gen, T.gb_gen, SP, T.stream.get()));
         TRC_TRY(launch_kernel(F.walk, T.gb_walk, SP, T.stream.get()));
-        hipLaunchKernelGGL(k_s_exact, dim3(T.gb_wide), dim3(256), F.lds_exact, T.stream.get(), SP);
+        TRC_TRY(launch_kernel(F.exact, T.gb_wide, SP, T.stream.get()));
         C.launches += 3;
     }
-    if (F.multi) { TRC_TRY(launch_kernel({(const void *)k_s_partition, 256, 0, F.g_wide}, T.gb_part, SP, T.stream.get())); C.launches += 1; }
-    for (int k = 0; k < F.n_shk; ++k) {
+    if (F.D.multi) { TRC_TRY(launch_kernel({(const void *)k_s_partition, 256, 0, F.g_wide}, T.gb_part, SP, T.stream.get())); C.launches += 1; }
+    for (int k = 0; k < F.D.n_shk; ++k) {
         const StreamShadeK &K = F.shk[k];
         StreamParams SK = SP;
         SK.shade_cls = K.cls;
-        if (F.multi) {
+        if (F.D.multi) {
             SK.hl_slot = SP.W.pl_slot[K.cls]; SK.hl_surf = SP.W.pl_surf[K.cls]; SK.hl_t = SP.W.pl_t[K.cls]; SK.hl_room = SP.W.pl_room; SK.hl_cn = CN(CW_CLS_LIST + K.cls);
         } else {
             SK.hl_slot = SP.W.hit_slot; SK.hl_surf = SP.W.hit_surf; SK.hl_t = SP.W.hit_t; SK.hl_room = SP.W.room; SK.hl_cn = CN(CW_HIT_LIST);
@@ -2850,7 +2607,7 @@ static int upload_counters(const StreamCall &C, StreamSlot &T) {
         up[CN(CW_HIT_LIST)] = (unsigned long long)T.SP.hit_base0 + (sg ? (unsigned long long)T.gb_wide * 4ull * SQ_CHUNK : 0ull) + first_entries;   // hit list <- k_s_fresh / k_s_bounce, k_s_exact / k_s_bounce<FRESH>
         for (int c = 0; c < TRC_CLS_COUNT; ++c) up[CN(CW_CLS_LIST + c)] = T.part_start[c];                      // class lists <- k_s_partition
         unsigned long long a = 0;                                                                      // active list <- the shading kernels
-        for (int k = 0; k < F.n_shk; ++k) a += (unsigned long long)T.gb_sh[k] * F.shk[k].wpb * T.chunk_act_sh[k];
+        for (int k = 0; k < F.D.n_shk; ++k) a += (unsigned long long)T.gb_sh[k] * F.shk[k].wpb * T.chunk_act_sh[k];
         up[CN(CW_ACT_OUT)] = a;
         up[CN(CW_SLOTS)] = (unsigned long long)T.SP.slot_base0 + ((sg && T.b == 0) ? (unsigned long long)T.gb_gen * 4ull * SQ_CHUNK : 0ull) + first_entries;   // slots <- k_s_fresh, k_s_gen<true> / k_s_bounce<FRESH>
         up[CN(CW_GEN_LIST)] = cull_waves * (unsigned long long)T.cull_gen_chunk;                                 // general-path list <- k_s_cull
@@ -3038,9 +2795,10 @@ static int advance(StreamCall &C, StreamSlot &T) {
 
 // Runs the whole call batch by batch, two batches in flight.  P is fully set up by trc_trace_fast (inputs staged, source uploaded),
 // which has planned the search (stream_plan) and read the knobs.
-static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, const StreamPlan &plan, const StreamKnobs &K, const trc_source_desc *src_desc,
+static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, const StreamPlan &plan, trc_facts &facts, const trc_source_desc *src_desc,
                         StreamEngine &E, trc_trace_stats *stats, double *seg_out, double *hit_out) {
     trc_ctx *ctx = sc->ctx;
+    const StreamKnobs &K = facts.knobs;
     // Batches: equal parts, a multiple of the number of slots (so that the slots finish together), at most 2^26 rays each
     // (14 GB of workspace per slot); calls below 2^23 rays are not split.
     const long long cap_max = 1ll << 26;
@@ -3058,13 +2816,13 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, c
     // shaded by k_s_shade_x; the spectra of the rays under way live in a table of their own beside the ray table
     // ... and so are all hits of a scene whose optics send two rays on from a hit, by its SPLIT form
     const bool split_rays = sc->splits;
-    const bool carry = sc->needs.any() || carry_in.ref_im || carry_in.mat || carry_in.spec || split_rays;
+    facts.call.carry = sc->needs.any() || carry_in.ref_im || carry_in.mat || carry_in.spec || split_rays;
     StreamForms F;
     StreamCall C{F, K, E, StreamParams(), cap, 0.0, 0.0, {0.0, 0.0, 0.0}, 0, 0, split_rays};
     memset(&C.SP0, 0, sizeof(C.SP0));
     C.SP0.P = P;
     C.SP0.carry = carry_in;
-    TRC_TRY(stream_choose_forms(F, C.SP0, sc, E, plan, carry, split_rays, src_desc, K));
+    TRC_TRY(stream_choose_forms(F, C.SP0, sc, E, plan, facts, src_desc));
     TRC_TRY(stream_slots_alloc(E, n_slots, cap, sc, carry_in, F, K, split_rays));
 
     for (int k = 0; k < STREAM_MAX_SLOTS; ++k) E.slot[k].busy = false;
