@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as N
 
 from . import _cabi
+from . import call_plan
 from .geometry_manager import NativeGeometryManager, fill_desc
 from .deferred import Delivery
 from .face_set import FaceSet, SurfaceSeq
@@ -558,8 +559,7 @@ class DeviceScene(object):
         last = None
         last_cols = None
         if keep_last:
-            # (at most one ray left per ray given, unless the optics split rays)
-            m = n if last_capacity is None else max(1, int(last_capacity) if self.compiled.splits else min(int(last_capacity), n))
+            m = n if last_capacity is None else call_plan.last_room(n, self.compiled.splits, last_capacity)
             last_cols = [N.empty(m) for _ in range(7)]
             last = _cabi.make_rays(m, *last_cols)
         status = self.lib.trc_trace_fast_x(self.handle, C.byref(rays) if rays is not None else None,

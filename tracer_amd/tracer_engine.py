@@ -26,6 +26,7 @@ import numpy as N
 
 from . import rng
 from . import _cabi
+from . import call_plan
 from .accel_tree import KdTree
 from .ray_bundle import RayBundle, concatenate_rays
 from .scene import compile_scene, DeviceScene, NotNativeError, feed_accountants, PendingHits
@@ -48,6 +49,10 @@ class TracerEngine(object):
         self._transfer_host = None      # contribution of ordered-engine runs (from the tree's parents)
         self._kd_on_device = None
         self._auto_kd = None
+        self._kd_lazy = None            # (cache key, depth, fast, keywords) of the tree that reading Kd_Tree builds: _kd_request
+        self._Kd_Tree = None
+        self._t_marks = []
+        self.tree = RayTree()
         self._ordered_pending = []      # weak references to what ordered traces still owe to accountants (ordered_levels.PendingLevels)
         self._transfer_pending = []     # those of them that carry a contribution to the transfer matrix (kept alive until it is read)
         self.stats = {}
@@ -55,7 +60,7 @@ class TracerEngine(object):
     # -- the Kd-tree of the last accelerated call (tracer_engine.py:171-185) -------------------------------
     @property
     def Kd_Tree(self):
-        lazy = getattr(self, '_kd_lazy', None)
+        lazy = self._kd_lazy
         if lazy is not None:
             key, max_depth, fast, kw = lazy
             if self._auto_kd is not None and self._auto_kd[0] == key:
@@ -69,7 +74,7 @@ class TracerEngine(object):
                     self._auto_kd = (key, tree)
                 self._Kd_Tree = tree
             self._kd_lazy = None
-        return getattr(self, '_Kd_Tree', None)
+        return self._Kd_Tree
 
     @Kd_Tree.setter
     def Kd_Tree(self, value):
@@ -113,6 +118,9 @@ class TracerEngine(object):
         new = compiled.frames12()
         return all(N.array_equal(self._dev_frames[si], new[si]) for si in self._fluxmap_requests)
 
+    def _surface_index(self, surface):
+        return surface if isinstance(surface, int) else self._asm.get_surfaces().index(surface)
+
     def set_fluxmap(self, surface, u_edges, v_edges, chart='xy', swap_xy=False):
         """
         Ask the device to bin the energy absorbed by `surface` (a Surface of the assembly, or its
@@ -125,7 +133,7 @@ class TracerEngine(object):
         """
         if chart not in _cabi.FM_CHARTS:
             raise ValueError("unknown flux-map chart %r (one of %s)" % (chart, sorted(_cabi.FM_CHARTS)))
-        si = surface if isinstance(surface, int) else self._asm.get_surfaces().index(surface)
+        si = self._surface_index(surface)
         self._fluxmap_requests[si] = (N.asarray(u_edges, dtype=float), N.asarray(v_edges, dtype=float), chart, bool(swap_xy))
         self._fluxmap_areas.pop(si, None)
         if self._dev is not None:
@@ -138,18 +146,18 @@ class TracerEngine(object):
         get_fluxmap(.., resolution) (fluxmap_grid).  Read it with get_surface_flux().  A geometry without such a grid
         raises NotImplementedError.
         """
-        surfs = self._asm.get_surfaces()
-        si = surface if isinstance(surface, int) else surfs.index(surface)
-        grid = getattr(surfs[si].get_geometry_manager(), 'fluxmap_grid', None)
+        si = self._surface_index(surface)
+        gm = self._asm.get_surfaces()[si].get_geometry_manager()
+        grid = getattr(gm, 'fluxmap_grid', None)
         if grid is None:
-            raise NotImplementedError("%s has no flux-map grid" % type(surfs[si].get_geometry_manager()).__name__)
+            raise NotImplementedError("%s has no flux-map grid" % type(gm).__name__)
         chart, swap_xy, u_edges, v_edges, areas = grid(resolution)
         self.set_fluxmap(si, u_edges, v_edges, chart=chart, swap_xy=swap_xy)
         self._fluxmap_areas[si] = N.asarray(areas, dtype=float)
 
     def get_surface_flux(self, surface):
         """energy per area of the bins of a map set by set_surface_fluxmap: the array the geometry's get_fluxmap returns"""
-        si = surface if isinstance(surface, int) else self._asm.get_surfaces().index(surface)
+        si = self._surface_index(surface)
         if si not in self._fluxmap_areas:
             raise ValueError("surface %d has no flux map set by set_surface_fluxmap (a map set by set_fluxmap has no bin areas: "
                              "read it with get_fluxmap)" % si)
@@ -158,7 +166,7 @@ class TracerEngine(object):
         return N.hstack(self._dev.get_fluxmap(si) / self._fluxmap_areas[si])
 
     def get_fluxmap(self, surface):
-        si = surface if isinstance(surface, int) else self._asm.get_surfaces().index(surface)
+        si = self._surface_index(surface)
         return self._dev.get_fluxmap(si)
 
     def get_tallies(self):
@@ -253,102 +261,65 @@ class TracerEngine(object):
             logging.log(self.loglevel, 'protocol engine: %s' % err)
             return self._trace_protocol(bundle, reps, min_energy, tree)
 
+        rays = call_plan.ray_facts(bundle)
+        scene = call_plan.scene_facts(dev, rays)
         if engine == 'auto':
-            # Complex refractive indices, materials evaluated at the rays' wavelengths and spectra travel with the rays of the
-            # ordered engine and of the streaming form of the fast engine (64 rays or more of a given bundle; k_s_shade_x).  A
-            # captured hit of a polychromatic ray keeps its sample wavelengths and its spectrum before and after the surface (what
-            # PolychromaticAccountant collects).
-            carries = dev.compiled.carries or (not _pending(bundle) and (bundle.is_polychromatic() or bundle.has_complex_index()))
-            # A source with a spectrum stays pending on a scene whose materials' tables are on the device (TabulatedMaterial(...,
-            # device=True)): the kernels evaluate m(lambda) per ray and draw the wavelengths themselves.
-            dev_mats = getattr(dev.compiled, 'material_tables', None) is not None and _pending(bundle) and \
-                bundle.source_spectrum() is not None and dev.materials_on_device()
-            if carries:
-                carries = (_pending(bundle) and not dev_mats) or bundle.get_num_rays() < 64
-            # Optics that send two rays on from a hit (single_ray=False) are traced by the streaming form too (k_s_shade_x<.., SPLIT>,
-            # DESIGN.md section 14.11): 64 rays or more, no source spectrum.  The ray tree, smaller calls and sources with a
-            # spectrum stay with the ordered engine.
-            splits = dev.compiled.splits and not (self.SPLIT_ON_FAST and bundle.get_num_rays() >= 64 and
-                                                  not (_pending(bundle) and bundle.source_spectrum() is not None and not dev_mats))
-            engine = 'ordered' if (tree or splits or carries) else 'fast'
-        if accel and Kd_Tree is None and (engine == 'fast' or (engine == 'ordered' and (dev.n_surf > self.KD_BUILD_MAX or (
-                dev.n_surf <= 65535 and bundle.get_num_rays() * dev.n_surf <= self.KD_WORTH_IT)))):
-            # The fast engine does not walk the reference's Kd-tree: large calls search the library's own uniform grid over the same
-            # geometry boxes (csrc/trc_bounds.h), small ones test the boxes themselves.  Building the tree -- the reference's SAH
-            # build, Python: 38 ms for the 219 surfaces of the NSTTF field, minutes for a mesh of 1e5 faces -- before every trace
-            # of a scene that moves (a day of sun positions) cost more than the traces.  engine.Kd_Tree builds it when it is read.
-            # The ordered engine walks it, but below KD_WORTH_IT box tests per bounce (rays x surfaces: a millisecond of the GPU)
-            # testing every surface's box costs less than the build: 1e5 rays on the NSTTF field took 30 ms with the tree, 3 without.
-            # Beyond KD_BUILD_MAX surfaces (a mesh) the tree is never built for a trace: the scene stands on the library's large grid,
-            # which the ordered engine walks too (trc_nearest_grid32).
-            num_surfs = dev.n_surf
-            kw = dict(kwargs)
-            kw.setdefault('min_leaf', 1)
-            unknown = [k for k in kw if k not in self.KD_KEYWORDS]       # (the tree is built later, if at all: complain now)
+            engine = call_plan.choose_engine(self, rays, scene, tree)
+        kd = call_plan.kd_action(self, rays, scene, engine, accel, Kd_Tree)
+        if kd in ('defer', 'never'):
+            lazy = self._kd_request(dev, accel, kwargs)
+            unknown = [k for k in lazy[3] if k not in self.KD_KEYWORDS]  # (the tree is built later, if at all: complain now)
             if unknown:
                 raise TypeError("ray_tracer() got unexpected keyword argument(s) %s" % ', '.join(repr(k) for k in unknown))
             self._Kd_Tree = None
-            self._kd_lazy = None if num_surfs > self.KD_BUILD_MAX else \
-                ((self._dev_sig, accel == 'fast', tuple(sorted(kw.items()))), 8 + 1.3 * N.log(num_surfs), accel == 'fast', kw)
+            self._kd_lazy = lazy if kd == 'defer' else None
             if self._kd_on_device is not None:
                 dev.set_kdtree(None)
                 self._kd_on_device = None
-        elif accel:
-            if Kd_Tree is None:
-                num_surfs = dev.n_surf
-                max_depth = 8 + 1.3 * N.log(num_surfs)
+        elif kd in ('build', 'given'):
+            if kd == 'build':
+                key, max_depth, fast, kw = self._kd_request(dev, accel, kwargs)
                 logging.log(self.loglevel, 'Maximum Kd tree depth %i' % max_depth)
-                kw = dict(kwargs)
-                kw.setdefault('min_leaf', 1)
-                # the tree only depends on the scene and on these arguments: repeated calls (Monte-Carlo loops) reuse it
-                key = (self._dev_sig, accel == 'fast', tuple(sorted(kw.items())))
                 if self._auto_kd is None or self._auto_kd[0] != key:
-                    self._auto_kd = (key, KdTree(self._asm, max_depth, loglevel=self.loglevel, fast=(accel == 'fast'), **kw))
-                self.Kd_Tree = self._auto_kd[1]
-            else:
-                self.Kd_Tree = Kd_Tree
-            if self._kd_on_device is not self.Kd_Tree:
-                dev.set_kdtree(self.Kd_Tree)
-                self._kd_on_device = self.Kd_Tree
+                    self._auto_kd = (key, KdTree(self._asm, max_depth, loglevel=self.loglevel, fast=fast, **kw))
+                Kd_Tree = self._auto_kd[1]
+            self.Kd_Tree = Kd_Tree
+            if self._kd_on_device is not Kd_Tree:
+                dev.set_kdtree(Kd_Tree)
+                self._kd_on_device = Kd_Tree
 
         if engine == 'fast':
-            return self._trace_fast(dev, bundle, reps, min_energy, seed, bool(accel), hit_capacity, fast_kernel, feed, last_capacity)
+            return self._trace_fast(dev, bundle, reps, min_energy, seed, bool(accel), hit_capacity, fast_kernel, feed, last_capacity,
+                                    (rays, scene))
         if engine == 'ordered':
             # (no tree on the device: the call was too small for one to pay, every surface's box is tested)
-            return self._trace_ordered(dev, bundle, reps, min_energy, seed, bool(accel) and self._kd_on_device is not None, tree)
+            return self._trace_ordered(dev, bundle, reps, min_energy, seed, bool(accel) and self._kd_on_device is not None, tree,
+                                       (rays, scene))
         raise ValueError("unknown engine %r" % (engine,))
 
+    def _kd_request(self, dev, accel, kwargs):
+        """(cache key, depth, fast, keywords) of the reference's Kd-tree that an accel=... call asks for"""
+        kw = dict(kwargs)
+        kw.setdefault('min_leaf', 1)
+        # the tree only depends on the scene and on these arguments: repeated calls (Monte-Carlo loops) reuse it
+        key = (self._dev_sig, accel == 'fast', tuple(sorted(kw.items())))
+        return key, 8 + 1.3 * N.log(dev.n_surf), accel == 'fast', kw
+
     # -- fast engine --------------------------------------------------------------------------------
-    def _trace_fast(self, dev, bundle, reps, min_energy, seed, accel, hit_capacity, fast_kernel='auto', feed=True, last_capacity=None):
-        n = bundle.get_num_rays()
-        capture = any(dev.compiled.capture)
-        split = bool(dev.compiled.splits)       # optics that send two rays on from a hit: the streaming form alone (k_s_shade_x<.., SPLIT>)
+    def _trace_fast(self, dev, bundle, reps, min_energy, seed, accel, hit_capacity, fast_kernel='auto', feed=True, last_capacity=None,
+                    facts=None):
+        rays, scene = facts or (call_plan.ray_facts(bundle), call_plan.scene_facts(dev))      # (ray_tracer has gathered them)
+        n, capture, split = rays.n, scene.capture, scene.splits
         accs = []
         pend = None
         if capture:
-            # The hits stay in the device's buffer until an accountant is read (scene.PendingHits).  A call that finds the hits
-            # of the calls before still unread there -- every accountant concerned still holds its mark -- goes on filling the
-            # same buffer, grown if need be; otherwise what it holds is delivered (or dropped, when nobody waits for it any more)
-            # and the buffer emptied.  An explicit hit_capacity is taken literally: an empty buffer of that size.
-            # Room for the hits of this call: two per ray unless the caller says otherwise -- or, once the scene in its present
-            # poses has been traced, four times the share of captured hits per ray seen so far (a field sends 6 % of its rays to
-            # the receiver: successive calls then fit the buffer of the first many times over before it has to grow).
-            need = int(hit_capacity) if hit_capacity is not None else 2 * n + 1024
-            if hit_capacity is None and dev.capture_rate is not None:
-                need = min(need, int(4. * dev.capture_rate * n) + 65536)
+            need = call_plan.hit_room(n, hit_capacity, dev.capture_rate)
             accs = [a for opt in dev.compiled.capturing_optics for a in opt.accountants]
             pend = dev.pending_hits
-            keep = bool(feed and hit_capacity is None and pend is not None and pend.wanted() and accs and all(pend.holds_mark(a) for a in accs))
-            if keep and ((not _pending(bundle) and bundle.is_polychromatic()) or dev.hit_spectral_columns()):
-                keep = False        # (all hits in the buffer have the same spectral columns: hits waiting there with spectra, or
-                                    # before a call that brings spectra, are delivered first)
-            if keep and split:
-                keep = False        # (a call whose hits do not fit is made again on an empty buffer: see below)
-            used = 0
-            if keep:
-                used = dev.hits_reserved()[0]
-                keep = used + need <= self.HITS_RESIDENT_MAX
-            if keep:
+            held = pend is not None and pend.wanted() and accs and all(pend.holds_mark(a) for a in accs)
+            keep = call_plan.may_keep_hits(rays, scene, feed, hit_capacity, held) and not dev.hit_spectral_columns()
+            used = dev.hits_reserved()[0] if keep else 0
+            if keep and used + need <= self.HITS_RESIDENT_MAX:
                 dev.reserve_hits(used + need)
             else:
                 pend = None
@@ -359,47 +330,21 @@ class TracerEngine(object):
                     dev.set_hit_capacity(need)
                 dev.lib.trc_scene_clear_hits(dev.handle)
         t0 = time.time()
-        stream = {'auto': None, 'stream': True, 'megakernel': False}[fast_kernel]
-        if stream is None and split:
-            stream = True       # (fast_kernel='megakernel' is refused by the library, which names trc_trace_ordered)
-        if stream is None and accel and dev.n_surf > self.KD_BUILD_MAX:
-            stream = True       # the streaming form has the grid for large scenes; the megakernel would test every box
-        # Large calls go to the streaming form.  On a scene where it turns out slow -- every segment a hit on overlapping curved
-        # shapes, several bounces deep: below SLOW_STREAM segments per ms, a fortieth of its rate on a heliostat field -- the next
-        # large call tries the megakernel, whose rays stay in registers, and the faster of the two serves the scene from then on.
-        # Both forms end every ray alike (test_forms_of_the_fast_engine_end_every_ray_alike).
-        tuned = stream is None and n >= self.TUNE_MIN_RAYS and dev.n_surf <= self.TUNE_MAX_SURFACES
-        if tuned:
-            rate = dev.form_rate
-            if 'stream' in rate and rate['stream'] < self.SLOW_STREAM:
-                stream = False if ('megakernel' not in rate or rate['megakernel'] > rate['stream']) else True
-        # Rays still alive after `reps` interactions come back as the call's result (tracer_engine.py:293-295).  Bundles beyond
-        # 2^24 rays get room for 2^22 of them unless the caller says otherwise (last_capacity=...): 1e8 rays would cost 5.6 GB
-        # of host arrays per call for a result that is empty in most scenes.  More rays left than room is an error of the
-        # call (status ERR_CAPACITY), raised after the trace: tallies and flux maps of the scene then hold it, the accountants do not.
-        cap = last_capacity if last_capacity is not None else (n if n <= (1 << 24) else (1 << 22))
-        if split and last_capacity is None and n <= (1 << 24):
-            cap = 2 * n + 1024      # (two rays may leave a hit: room as for the hits; beyond it the call is made again, below)
+        stream, tuned = call_plan.fast_form(self, rays, scene, fast_kernel, accel, dev.form_rate)
+        cap = call_plan.last_room(n, split, last_capacity)
         over_capacity = 0
         if not split:
             stats, last = dev.trace_fast(bundle, reps, min_energy, seed, accel=accel, keep_last=True, stream=stream, last_capacity=cap)
         else:
-            # A scene that splits rays can capture more hits than the default room of two per ray, and leave more rays than it was
-            # given; the ordered engine has neither limit, and nothing grows in the middle of a call.  So before a call that
-            # captures the packed tally buffer (tallies, flux maps, transfer matrix) is kept aside, and a call that dropped hits
-            # or had no room for its last rays is undone -- hit buffer emptied, tallies put back -- and made once more, with the
-            # same seed, with room for every hit it counted (captured or not: an upper bound; the library adds what the buffer's
-            # open chunks can leave unused) and every ray it left.  A scene that captures nothing pays for no snapshot: there
-            # only the last rays can lack room, the tallies of such a call are complete, and they are put back behind the
-            # second call.  Room the caller set (hit_capacity, last_capacity) is taken literally.
             saved = dev.export_tallies() if capture else None
             literal = capture and hit_capacity is not None
             hits_before = dev.get_tallies()[2] if literal else None
             stats, last = dev.trace_fast(bundle, reps, min_energy, seed, accel=accel, keep_last=True, stream=stream, last_capacity=cap,
                                          short_last_ok=last_capacity is None)
-            if (stats.hits_dropped and capture and hit_capacity is None) or last is None:
+            again, grow = call_plan.split_retry(scene, hit_capacity, stats.hits_dropped, last is None)
+            if again:
                 if capture:
-                    if stats.hits_dropped and hit_capacity is None:
+                    if grow:
                         dev.set_hit_capacity(int(stats.hits))
                     dev.lib.trc_scene_clear_hits(dev.handle)
                     dev.import_tallies(saved)
@@ -422,11 +367,10 @@ class TracerEngine(object):
         if tuned and stats.kernel_ms > 0:
             dev.form_rate[self.stats['form']] = stats.segments / stats.kernel_ms
         if stats.hits_dropped:
-            raise RuntimeError("%d hits were not captured: the hit buffer holds %d; pass hit_capacity=..."
-                               % (stats.hits_dropped, dev.hit_capacity))
+            raise _not_captured(stats.hits_dropped, dev.hit_capacity)
         if over_capacity > 0:
             dev.lib.trc_scene_clear_hits(dev.handle)
-            raise RuntimeError("%d hits were not captured: the hit buffer holds %d; pass hit_capacity=..." % (over_capacity, int(hit_capacity)))
+            raise _not_captured(over_capacity, int(hit_capacity))
         if capture and n > 0 and not split:      # (a split call's room is found by the call itself)
             rate = max(dev.hits_reserved()[0] - used, 0) / float(n)
             dev.capture_rate = rate if dev.capture_rate is None else max(dev.capture_rate, rate)
@@ -443,15 +387,16 @@ class TracerEngine(object):
         return vertices, directions
 
     # -- ordered engine -----------------------------------------------------------------------------
-    def _trace_ordered(self, dev, bundle, reps, min_energy, seed, accel, tree):
-        has_ref = bundle._has_column('ref_index') if not _pending(bundle) else False
-        has_wl = bundle._has_column('wavelengths') if not _pending(bundle) else False
-        if _pending(bundle) and bundle.source_spectrum() is not None:
+    def _trace_ordered(self, dev, bundle, reps, min_energy, seed, accel, tree, facts=None):
+        rays, scene = facts or (call_plan.ray_facts(bundle), call_plan.scene_facts(dev))
+        has_ref = not rays.pending and bundle._has_column('ref_index')
+        has_wl = not rays.pending and bundle._has_column('wavelengths')
+        if rays.spectrum is not None:
             # (a source with a spectrum: level 0 carries the wavelengths drawn on the device, and the index the spectrum gives)
-            has_ref = 'ref_index' in bundle.spectral_columns()
-            has_wl = 'wavelengths' in bundle.spectral_columns()
-        n_spec = bundle.get_spectra().shape[0] if (not _pending(bundle) and bundle.is_polychromatic()) else 0
-        cplx = bool(dev.compiled.materials) or (not _pending(bundle) and bundle.has_complex_index())
+            has_ref = 'ref_index' in rays.columns
+            has_wl = 'wavelengths' in rays.columns
+        n_spec = bundle.get_spectra().shape[0] if rays.polychromatic else 0
+        cplx = scene.materials or rays.complex_index
         if n_spec:
             has_wl = False          # `wavelengths` is the (W, N) grid of the spectra
         self._trim_resident_levels()
@@ -583,23 +528,23 @@ class TracerEngine(object):
     def _set_stats(self, stats, wall, engine):
         self.stats = dict(engine=engine, segments=stats.segments, hits=stats.hits, rays_left=stats.rays_left,
                           energy_left=stats.energy_left, kernel_ms=stats.kernel_ms, bounces=stats.bounces,
-                          launches=stats.launches, wall_s=wall, host_s=dict(getattr(self, '_t_marks', [])))
+                          launches=stats.launches, wall_s=wall, host_s=dict(self._t_marks))
         logging.log(self.loglevel, 'trace time %s s' % wall)
 
     def _warn_left(self, rays_left, energy_left, bundle):
         if rays_left:
             logging.warning('%d rays left at the end of the simulation' % rays_left)
             try:
-                tot = N.sum(bundle.get_energy()) if not _pending(bundle) else bundle.source_args()[0].energy * bundle.get_num_rays()
+                pending = call_plan.ray_facts(bundle).pending
+                tot = N.sum(bundle.get_energy()) if not pending else bundle.source_args()[0].energy * bundle.get_num_rays()
                 logging.warning('Remaining energy in last bundle: %s%%' % (energy_left / tot * 100.))
             except Exception:
                 pass
 
 
-def _pending(bundle):
-    return hasattr(bundle, 'is_pending') and bundle.is_pending()
+def _not_captured(count, room):
+    return RuntimeError("%d hits were not captured: the hit buffer holds %d; pass hit_capacity=..." % (count, room))
 
 
 def _has_refractive(dev):
-    from . import _cabi
     return any(d.optics_kind == _cabi.OPT_REFRACTIVE_HOMOGENOUS for d in dev.compiled.descs)
