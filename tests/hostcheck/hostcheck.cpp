@@ -115,6 +115,9 @@ long hc_sizeof(int which) {
     }
 }
 
+// parameters of a geometry kind in a surface record (tests/geometry_cases.py restates the table); -1: no such kind
+int hc_gm_nparams(int kind) { return trc_gm_nparams(kind); }
+
 int hc_shade(const trc_surface_desc *s, const double *extra, long n, const double *dx, const double *dy, const double *dz,
              const double *e, const double *ref, const double *wl, const double *nx, const double *ny, const double *nz,
              const uint64_t *rid, uint64_t seed, int event, double *odx, double *ody, double *odz, double *oe, double *oref,

@@ -226,9 +226,7 @@ class Hand(object):
         self.map_surf, self.full_surf, self.twin, self.terminal = map_surf, full_surf, twin, terminal
         self.edges = {map_surf: edges}
         self.captured = [i for i in range(Sn) if self.cs.capture[i]]
-        gm = sc._names('GM_')
-        nparams = dict(sc.GM_NPARAMS, GM_FLAT_INF=0)            # trc_gm_nparams (csrc/trc_core.h)
-        self.stride = (sc.REC_HDR + max(nparams[gm[self.cs.descs[i].gm_kind]] for i in range(Sn))) | 1
+        self.stride = sc.record_stride(self.cs)
         # the boxes of the plates, from their corners in global coordinates; a plane has none
         c = N.array([[sx, sy, 0., 1.] for sx in (-1, 1) for sy in (-1, 1)]).T
         self.bounded = N.array([h is not None for gm, o, tr, h in parts])

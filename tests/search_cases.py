@@ -705,17 +705,20 @@ def kd_depth(kd):
 def predict(call):
     """{search-stage kernel as a kernel trace names it: launches} of a call (a second call: of the two), from forms(), the per-bounce
     choice of plan_bounce / launch_bounce, and the reference's rays alive at every bounce"""
-    f = forms(facts(call))
-    o = reference(call)
+    return launches(forms(facts(call)), reference(call)['levels'], N_RAYS, REPS, call.second)
+
+
+def launches(f, levels, n_rays, reps, second=False):
+    """predict() for the decisions `f` of forms() and the levels of a reference of n_rays rays traced for reps interactions"""
     # bounces run: b = 0, then one more while rays are alive and b + 1 < reps (advance)
     n_bounces = 1
-    for L in o['levels'][1:]:
-        if L['n_live'] == 0 or n_bounces >= REPS:
+    for L in levels[1:]:
+        if L['n_live'] == 0 or n_bounces >= reps:
             break
         n_bounces += 1
     out = collections.Counter()
     hit_rate = 0.
-    for turn in range(2 if call.second else 1):
+    for turn in range(2 if second else 1):
         for b in range(n_bounces):
             fresh = f['use_fp'] and b == 0
             fused = f['use_fused'] and b > 0
@@ -733,7 +736,7 @@ def predict(call):
                 for stage in ('gen0' if b == 0 else 'gen', 'walk', 'exact'):
                     out[f[stage][0]] += 1
         if f['use_fp']:         # advance: what the next call on the scene expects of the listed rays
-            hit_rate = 1.15 * len(o['levels'][1]['surf']) / float(N_RAYS) + 256. / N_RAYS
+            hit_rate = 1.15 * len(levels[1]['surf']) / float(n_rays) + 256. / n_rays
     return dict(out)
 
 

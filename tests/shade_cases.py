@@ -44,8 +44,8 @@ KiB = 1024
 LIMIT_LEAN, LIMIT_LEAN_BINS = 120 * KiB, 150 * KiB          # trc_stream_form_shade: `need <= 120 * 1024`, `K.lds + bins * 8 + 16 <= 150 * 1024`
 LIMIT_SHADE, LIMIT_SHADE_BINS = 72 * KiB, 78 * KiB          # ... `all <= 72 * 1024`, `lds_shade + bins * 8 + 16 <= 78 * 1024`
 
-# trc_gm_nparams (csrc/trc_core.h) of the geometry kinds the room uses, by _cabi.GM_* name
-GM_NPARAMS = {'GM_RECT': 2, 'GM_ROUND': 2, 'GM_TRIANGLE': 6, 'GM_POLYGON': 6, 'GM_SPHERE': 1, 'GM_CYL_FINITE': 4, 'GM_PARAB_DISH': 3}
+# (trc_gm_nparams of the geometry kinds, by _cabi.GM_* name: geometry_cases.NPARAMS, all 30 of them, held to the library by
+# test_geometry_cases_host.py; record_stride reads it there)
 REC_HDR = 14                # TRC_REC_HDR
 SIZEOF_FLUXMAPDEV = 4 * 4 + 3 * 8 + 12 * 8          # struct FluxMapDev (csrc/trc_device.h)
 FLAT_KINDS = ('GM_FLAT_INF', 'GM_RECT', 'GM_RECT_EXTRUDED', 'GM_RECT_PERFORATED', 'GM_ROUND', 'GM_ROUND_CUT', 'GM_TRIANGLE', 'GM_POLYGON')
@@ -75,8 +75,9 @@ def _names(prefix):
 # -- the sums of trc_stream_form_shade ------------------------------------------------------------------------------------------------
 def record_stride(cs):
     """doubles per surface record (trc_scene_create): TRC_REC_HDR + the parameters of the widest geometry kind, made odd"""
+    from geometry_cases import NPARAMS         # (that module imports this one)
     gm = _names('GM_')
-    return (REC_HDR + max(GM_NPARAMS[gm[cs.descs[i].gm_kind]] for i in range(cs.n_surf))) | 1
+    return (REC_HDR + max(NPARAMS[gm[cs.descs[i].gm_kind]] for i in range(cs.n_surf))) | 1
 
 
 def shade_class_of(desc):

@@ -353,10 +353,13 @@ def _kd_desc(asm, n_surf):
 def test_nearest_hit_searches_on_random_scenes(hc):
     """
     Every candidate search of the engines -- the float64 Kd walk, the single-precision walk with and without the tree, the uniform
-    grid with its DDA -- against brute force on scenes of 120 plates, discs, spheres, hemispheres, cylinders and dishes thrown
-    into a cube: once turned at random, once on integer positions with quarter turns (coincident planes, faces in cell and split
-    planes), with axis-parallel rays and rays that start on those planes; then again for rays that leave the points just hit.
+    grid with its DDA -- against brute force on scenes of 120 surfaces thrown into a cube -- plates, discs, spheres, hemispheres,
+    cylinders and dishes of random size, and every maker of the kind table of geometry_cases.py, the unbounded kinds among them
+    (no box: always relevant) -- once turned at random, once on integer positions with quarter turns (coincident planes, faces in
+    cell and split planes), with axis-parallel rays and rays that start on those planes; then again for rays that leave the points
+    just hit.
     """
+    import geometry_cases as G
     from tracer_amd.scene import compile_scene
     from tracer_amd.assembly import Assembly
     from tracer_amd.object import AssembledObject
@@ -372,8 +375,12 @@ def test_nearest_hit_searches_on_random_scenes(hc):
     def scene(rng, aligned):
         objs = []
         for _ in range(120):
-            kind, s = rng.randint(0, 6), rng.uniform(0.2, 1.5)
-            if kind == 0:
+            kind, s = rng.randint(0, 6 + len(G.MAKERS)), rng.uniform(0.2, 1.5)
+            if kind >= 6:
+                maker = list(G.MAKERS)[kind - 6]
+                gm, r = G.make(maker), G.MAKERS[maker][5]
+                lo, hi = (None, None) if r is None else ([-r, -r, -r], [r, r, r])
+            elif kind == 0:
                 gm, lo, hi = RectPlateGM(2 * s, s), [-s, -s / 2, 0], [s, s / 2, 0]
             elif kind == 1:
                 gm, lo, hi = RoundPlateGM(s), [-s, -s, 0], [s, s, 0]
@@ -386,7 +393,7 @@ def test_nearest_hit_searches_on_random_scenes(hc):
             else:
                 f = rng.uniform(0.5, 2.)
                 gm, lo, hi = ParabolicDishGM(2 * s, f), [-s, -s, 0], [s, s, s * s / (4 * f)]
-            o = AssembledObject(Surface(gm, Reflective(0.1)), bounds=BoundaryBox([lo, hi]))
+            o = AssembledObject(Surface(gm, Reflective(0.1)), bounds=BoundaryBox([lo, hi]) if lo is not None else None)
             loc = rng.uniform(-6., 6., 3)
             if aligned:
                 o.set_transform(generate_transform(N.r_[1., 0, 0], rng.choice([0., N.pi / 2, N.pi]), N.round(loc)[:, None]))
@@ -482,8 +489,10 @@ def test_footprint_map_is_conservative(hc):
     assert rc == 0 and o[4] == 0 and o[3] > 50000, (why, o)
     rng = N.random.RandomState(5)
     objs = []
-    for k in range(14):
-        gm = [RectPlateGM(1.2, 0.7), RoundPlateGM(0.6), ParabolicDishGM(1.4, 1.1), HemisphereGM(0.5), FiniteCylinder(0.8, 1.1)][k % 5]
+    import geometry_cases as G
+    for k in range(14 + len(G.BOUNDED)):       # ... and every bounded maker of the kind table
+        gm = [RectPlateGM(1.2, 0.7), RoundPlateGM(0.6), ParabolicDishGM(1.4, 1.1), HemisphereGM(0.5), FiniteCylinder(0.8, 1.1)][k % 5] if k < 14 else \
+            G.make(G.BOUNDED[k - 14])
         tr = N.dot(translate(*rng.uniform(-4, 4, 3)), N.dot(rotx(rng.uniform(0, 6.3)), N.dot(roty(rng.uniform(0, 6.3)), rotz(rng.uniform(0, 6.3)))))
         objs.append(AssembledObject(surfs=[Surface(gm, opt.Reflective(0.1))], transform=tr))
     mixed = compile_scene(Assembly(objects=objs))
