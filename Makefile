@@ -102,6 +102,15 @@ splitcheck: $(SPLITCHECK_EXE)
 $(SPLITCHECK_EXE): $(SPLITCHECK_SRC) $(HDR)
 	$(CXX) -O1 -g -std=c++17 $(FPFLAGS) $(SPLIT_SAN) -o $@ $(SPLITCHECK_SRC)
 
+# what k_s_shade_p rests on -- trc_interp2_at against trc_interp2 bit for bit, the ids and the LDS decision of its family
+# (trc_forms.h) -- as a program of its own, built with the sanitizers and run by tests/test_poly_source_host.py
+POLYCHECK_EXE := $(ROOT)tests/polycheck/poly_check
+POLYCHECK_SRC := $(ROOT)tests/polycheck/poly_check.cpp
+polycheck: $(POLYCHECK_EXE)
+
+$(POLYCHECK_EXE): $(POLYCHECK_SRC) $(HDR)
+	$(CXX) -O1 -g -std=c++17 $(FPFLAGS) $(SPLIT_SAN) -o $@ $(POLYCHECK_SRC)
+
 # assembly listings with the registers, scratch and occupancy of every kernel (build/*.s, build/*.resources.txt)
 asm: $(SRCS) $(HDR)
 	mkdir -p $(ROOT)build
@@ -118,4 +127,4 @@ asm-shade: $(CSRC)/trc_shade.hip $(HDR)
 clean:
 	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK)
 
-.PHONY: all hostcheck umaskcheck umaskcheck-exe splitcheck asm asm-shade clean
+.PHONY: all hostcheck umaskcheck umaskcheck-exe splitcheck polycheck asm asm-shade clean

@@ -239,12 +239,15 @@ typedef struct trc_sunshape trc_sunshape;
  * CONSTANT: every ray has `wavelength`.  TABLE: a piecewise-linear spectral density (the inverse CDF of the reference's
  * ray_trace_utils/sampling.py:35-52, PW_linear_distribution), n points (2..4096) of strictly increasing wavelengths `wl` and
  * finite, non-negative densities `value` with a positive integral.  The rays start in a medium of index `ref_index`.
+ * CARRIED: the same table (the fields of TABLE), but no wavelength is drawn: every source ray is polychromatic and carries all n
+ * points as its sample wavelengths, with the spectrum energy_of_ray * value[w] / integral (whose trapezoid integral is the ray's
+ * energy).  Its scalar wavelength is 0.
  */
-typedef enum trc_spectrum_kind { TRC_SPECTRUM_NONE = 0, TRC_SPECTRUM_CONSTANT = 1, TRC_SPECTRUM_TABLE = 2 } trc_spectrum_kind;
+typedef enum trc_spectrum_kind { TRC_SPECTRUM_NONE = 0, TRC_SPECTRUM_CONSTANT = 1, TRC_SPECTRUM_TABLE = 2, TRC_SPECTRUM_CARRIED = 3 } trc_spectrum_kind;
 #define TRC_SPECTRUM_MAX_POINTS 4096
 typedef struct trc_source_spectrum {
     int32_t kind;
-    int32_t n;              /* TABLE: points, 2..4096 */
+    int32_t n;              /* TABLE, CARRIED: points, 2..4096 */
     double wavelength;      /* CONSTANT */
     double ref_index;       /* index of the medium the rays start in (1.0 = the value without a spectrum) */
     const double *wl;       /* TABLE: n strictly increasing wavelengths */
@@ -450,7 +453,12 @@ int trc_trace_fast(trc_scene *scene, const trc_rays *in, const trc_source_desc *
                    int32_t flags, trc_rays *last, trc_trace_stats *stats);
 /* The same with the spectrum of `src` (NULL: trc_trace_fast).  A spectrum with a given bundle `in` is TRC_ERR_INVALID; a spectrum
    on a scene whose optics send two rays on from a hit is TRC_ERR_UNSUPPORTED (use trc_trace_ordered_x) unless the scene's
-   tabulated materials are on the device (above). */
+   tabulated materials are on the device (above).
+   A CARRIED spectrum is traced by the streaming form alone (64 rays or more; k_s_shade_p, which stages the sample grid and the birth
+   spectrum per workgroup and uploads nothing per ray): TRC_TRACE_MEGAKERNEL or fewer rays are TRC_ERR_UNSUPPORTED (use
+   trc_trace_ordered_x), and so is a scene between tabulated materials.  Scenes whose optics split rays, flux maps in any chart and
+   captured hits (3 n spectral columns each) are served.  With TRC_TRACE_KEEP_LAST, a non-NULL last->spectra and last->n_spec == n, the
+   rays left bring their spectra back (last->spectra[w * capacity + q]; last->spec_wl, when non-NULL, is filled with the grid). */
 int trc_trace_fast_x(trc_scene *scene, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
                      int64_t n, int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset,
                      int32_t flags, trc_rays *last, trc_trace_stats *stats);
@@ -464,7 +472,9 @@ int trc_trace_fast_x(trc_scene *scene, const trc_rays *in, const trc_source_desc
 int trc_trace_ordered(trc_scene *scene, const trc_rays *in, const trc_source_desc *src, int64_t n,
                       int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset,
                       int32_t flags, trc_result **out, trc_trace_stats *stats);
-/* The same with the spectrum of `src` (NULL: trc_trace_ordered): level 0 carries the drawn wavelengths and ref_index. */
+/* The same with the spectrum of `src` (NULL: trc_trace_ordered): level 0 carries the drawn wavelengths and ref_index; under a
+   CARRIED spectrum it carries the (n_spec, n) sample wavelengths and spectra, written on the device, and is traced as a given
+   polychromatic bundle is. */
 int trc_trace_ordered_x(trc_scene *scene, const trc_rays *in, const trc_source_desc *src, const trc_source_spectrum *spec,
                         int64_t n, int32_t reps, double min_energy, uint64_t seed, uint64_t ray_offset,
                         int32_t flags, trc_result **out, trc_trace_stats *stats);
@@ -482,7 +492,9 @@ int trc_result_destroy(trc_result *res);
 /* sources.*_bundle(...) materialised as a bundle (sources.py:175-515) */
 int trc_source_generate(trc_ctx *ctx, const trc_source_desc *src, int64_t n, uint64_t seed,
                         uint64_t ray_offset, trc_rays *out);
-/* The same with a spectrum (NULL: trc_source_generate); out->wavelength and out->ref_index are filled when non-NULL. */
+/* The same with a spectrum (NULL: trc_source_generate); out->wavelength and out->ref_index are filled when non-NULL.  A CARRIED
+   spectrum of n points fills out->spec_wl and out->spectra (rows out->n apart), which must be given with out->n_spec == n
+   (TRC_ERR_INVALID otherwise); out->wavelength is 0. */
 int trc_source_generate_x(trc_ctx *ctx, const trc_source_desc *src, const trc_source_spectrum *spec, int64_t n, uint64_t seed,
                           uint64_t ray_offset, trc_rays *out);
 

@@ -83,7 +83,7 @@ class SourceDesc(C.Structure):
 
 
 # enum trc_spectrum_kind
-SPECTRUM_NONE, SPECTRUM_CONSTANT, SPECTRUM_TABLE = range(3)
+SPECTRUM_NONE, SPECTRUM_CONSTANT, SPECTRUM_TABLE, SPECTRUM_CARRIED = range(4)
 SPECTRUM_MAX_POINTS = 4096
 
 

@@ -11,6 +11,8 @@ tests/test_call_plan_host.py holds the decisions to account through TracerEngine
 from collections import namedtuple
 
 # columns: those a pending source's spectrum fills when the bundle is made ('wavelengths', 'ref_index')
+# A pending source whose spectrum is carried (SourceSpectrum.polychromatic) is pending AND polychromatic: every ray brings the whole
+# table, and the device makes the (W, n) columns where an engine needs them (carried()).
 Rays = namedtuple('Rays', 'n pending polychromatic complex_index spectrum columns')
 # splits: optics that send two rays on from a hit: the streaming form alone (k_s_shade_x<.., SPLIT>)
 # materials_on_device: the device evaluates the scene's materials for this call's source (asked for a source with a spectrum only)
@@ -20,8 +22,14 @@ Scene = namedtuple('Scene', 'n_surf carries splits capture materials materials_o
 def ray_facts(bundle):
     if hasattr(bundle, 'is_pending') and bundle.is_pending():
         spectrum = bundle.source_spectrum()
-        return Rays(bundle.get_num_rays(), True, False, False, spectrum, bundle.spectral_columns() if spectrum is not None else ())
+        poly = bool(getattr(spectrum, 'is_carried', lambda: False)())       # (SourceSpectrum.polychromatic: the rays carry the table)
+        return Rays(bundle.get_num_rays(), True, poly, False, spectrum, bundle.spectral_columns() if spectrum is not None else ())
     return Rays(bundle.get_num_rays(), False, bool(bundle.is_polychromatic()), bool(bundle.has_complex_index()), None, ())
+
+
+def carried(rays):
+    """the rays are those of a pending source that carries its spectrum"""
+    return bool(rays.pending and rays.polychromatic)
 
 
 def scene_facts(dev, rays=None):
@@ -39,14 +47,16 @@ def choose_engine(lim, rays, scene, tree):
     # ordered engine and of the streaming form of the fast engine (64 rays or more of a given bundle; k_s_shade_x).  A
     # captured hit of a polychromatic ray keeps its sample wavelengths and its spectrum before and after the surface (what
     # PolychromaticAccountant collects).
+    # A pending source that carries its spectrum goes the same way without ever being made on the host (k_s_shade_p, DESIGN.md
+    # section 14.13): the streaming form from 64 rays on, scenes that split rays included, the ordered engine otherwise.
     carries = scene.carries or rays.polychromatic or rays.complex_index
     if carries:
-        carries = (rays.pending and not scene.materials_on_device) or rays.n < 64
+        carries = (rays.pending and not scene.materials_on_device and not carried(rays)) or rays.n < 64
     # Optics that send two rays on from a hit (single_ray=False) are traced by the streaming form too (k_s_shade_x<.., SPLIT>,
     # DESIGN.md section 14.11): 64 rays or more, no source spectrum.  The ray tree, smaller calls and sources with a
     # spectrum stay with the ordered engine.
     splits = scene.splits and not (lim.SPLIT_ON_FAST and rays.n >= 64 and
-                                   not (rays.spectrum is not None and not scene.materials_on_device))
+                                   not (rays.spectrum is not None and not scene.materials_on_device and not carried(rays)))
     return 'ordered' if (tree or splits or carries) else 'fast'
 
 
@@ -101,7 +111,7 @@ def may_keep_hits(rays, scene, feed, hit_capacity, marks_held):
 def fast_form(lim, rays, scene, fast_kernel, accel, form_rate):
     """(the `stream` argument of the fast engine: True, False or None for the library's choice; whether the call is tuned)"""
     stream = {'auto': None, 'stream': True, 'megakernel': False}[fast_kernel]
-    if stream is None and scene.splits:
+    if stream is None and (scene.splits or carried(rays)):
         stream = True       # (fast_kernel='megakernel' is refused by the library, which names trc_trace_ordered)
     if stream is None and accel and scene.n_surf > lim.KD_BUILD_MAX:
         stream = True       # the streaming form has the grid for large scenes; the megakernel would test every box

@@ -1192,13 +1192,20 @@ TRC_HD int trc_grid_cell(const double *xs, int n, double x, double *w) {
     *w = (x - xs[lo]) / (xs[lo + 1] - xs[lo]);
     return lo;
 }
-TRC_HD double trc_interp2(const double *tab, double th, double lam) {
+// ... the blend of cell (it, il) with the weights trc_grid_cell gave: what trc_interp2 returns, for a caller that keeps the cells
+// (k_s_shade_p: the lambda cell of a sample is the same for every ray of a call)
+TRC_HD double trc_interp2_at(const double *tab, int it, double wt, int il, double wlam) {
     int nt = (int)tab[0], nl = (int)tab[1];
-    const double *ts = tab + 2, *ls = ts + nt, *v = ls + nl;
-    double wt, wlam;
-    int it = trc_grid_cell(ts, nt, th, &wt), il = trc_grid_cell(ls, nl, lam, &wlam);
+    const double *v = tab + 2 + nt + nl;
     double v00 = v[it * nl + il], v01 = v[it * nl + il + 1], v10 = v[(it + 1) * nl + il], v11 = v[(it + 1) * nl + il + 1];
     return (1.0 - wt) * ((1.0 - wlam) * v00 + wlam * v01) + wt * ((1.0 - wlam) * v10 + wlam * v11);
+}
+TRC_HD double trc_interp2(const double *tab, double th, double lam) {
+    int nt = (int)tab[0], nl = (int)tab[1];
+    const double *ts = tab + 2, *ls = ts + nt;
+    double wt, wlam;
+    int it = trc_grid_cell(ts, nt, th, &wt), il = trc_grid_cell(ls, nl, lam, &wlam);
+    return trc_interp2_at(tab, it, wt, il, wlam);
 }
 
 // interface between a perfect dielectric and an absorbing medium, optics.py:63-81 (fresnel_to_attenuating):

@@ -324,6 +324,12 @@ struct CarryIn {
     // the scene's tabulated materials (trc_material_index's packed table, trc_scene_set_materials) for a call that brings no rows
     // of them: read by the MAT instances of k_s_shade_x alone, null for every other call.  The very last word, for the same reason.
     const double *mat_tab;
+    // a source that carries its spectrum (TRC_SPECTRUM_CARRIED): read by k_s_shade_p alone, zero for every other call, and behind
+    // everything else for the same reason.  spec_wl and spec above are null then (grid and values come from FastParams.spec) and
+    // n_spec is the table's W.  last_spec / last_wl: spectra and sample wavelengths of the rays left, sample w of ray q at
+    // [w * last_cap + q] (null: not asked for).  poly_cells: the polychromatic walls whose lambda cells the LDS instances stage (0: none)
+    double *last_spec, *last_wl;
+    int poly_cells;
 };
 
 struct FastParams {
@@ -659,6 +665,7 @@ __device__ __forceinline__ void tally_by_wave(double *tl, int Sn, int ts, double
 const void *trc_shade_carry_kernel(bool lds, bool chart = false, bool split = false, bool mat = false);      // k_s_shade_x (trc_shade.hip): every optics kind, with what the rays carry;
                                                                                             // split: its form for scenes whose optics send two rays on from a hit
 const void *trc_shade_lean_kernel(int cls, bool flat, bool lds, bool spec = false, bool chart = false);
+const void *trc_shade_poly_kernel(bool lds, bool chart, bool split);        // k_s_shade_p (trc_shade.hip): k_s_shade_x for a source that carries its spectrum
 
 __device__ __forceinline__ trc_accel_view stream_accel_global(const DScene &sc, int mode) {
     const bool kd32 = mode == 1;

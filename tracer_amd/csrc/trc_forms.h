@@ -203,6 +203,8 @@ struct trc_call_facts {
     bool carry;                 // the rays carry more than the fast engine's record (complex indices, materials, spectra)
     bool mat_dev;               // the materials' tables are on the device and the call brings no rows of them
     bool term_ok;               // 0 <= min_energy: a ray of energy 0 ends in the reference too
+    int poly_src;               // the source carries its spectrum (TRC_SPECTRUM_CARRIED): the points W of its table, 0: it does not
+    int poly_walls;             // ... and the polychromatic walls of the scene, whose lambda cells k_s_shade_p may stage
 };
 // the footprint map of the call's source, after stream_fp_prepare
 struct trc_fp_facts {
@@ -261,6 +263,7 @@ enum trc_kernel_family {
     TRC_K_ABSORB,               // k_s_absorb
     TRC_K_TRACE_COOP, TRC_K_TRACE_FAST,         // k_trace_coop<THREADS, SPEC, SUN, CHART>, k_trace_fast<THREADS, SPEC, SUN, CHART>
     TRC_K_ORD_BOUNCE,           // k_ord_bounce<MODE, CHART, MAT>
+    TRC_K_SHADE_P,              // k_s_shade_p<LDS, CHART, SPLIT>
     TRC_K_FAMILIES
 };
 struct trc_kernel_id { int family; int a[5]; };     // the template arguments in their order, bool as 0 / 1; unused: 0
@@ -274,7 +277,8 @@ static inline const char *trc_kernel_family_name(int family, const char **args) 
     static const char *const names[TRC_K_FAMILIES][2] = {
         {"", ""}, {"k_s_cull", "i"}, {"k_s_ucull", "i"}, {"k_s_fresh", "ibb"}, {"k_s_fresh2", "ibb"}, {"k_s_bounce", "ibbbb"}, {"k_s_bounce_coop", "bbb"},
         {"k_s_walk", "ib"}, {"k_s_gen", "bi"}, {"k_s_gen_src", "i"}, {"k_s_exact", ""}, {"k_s_shade", "bibbb"}, {"k_s_shade_c", "ibbbb"},
-        {"k_s_shade_x", "bbbb"}, {"k_s_absorb", ""}, {"k_trace_coop", "ibbb"}, {"k_trace_fast", "ibbb"}, {"k_ord_bounce", "ibb"}};
+        {"k_s_shade_x", "bbbb"}, {"k_s_absorb", ""}, {"k_trace_coop", "ibbb"}, {"k_trace_fast", "ibbb"}, {"k_ord_bounce", "ibb"},
+        {"k_s_shade_p", "bbb"}};
     if (family < 0 || family >= TRC_K_FAMILIES) family = TRC_K_NONE;
     if (args) *args = names[family][1];
     return names[family][0];
@@ -329,6 +333,7 @@ static inline bool trc_kernel_id_valid(const trc_kernel_id &id) {
     case TRC_K_TRACE_COOP: return a[0] == 512 || a[0] == 256;
     case TRC_K_TRACE_FAST: return a[0] == 256;
     case TRC_K_ORD_BOUNCE: return a[0] >= 0 && a[0] <= 2 && !(a[1] && a[2]);
+    case TRC_K_SHADE_P: return true;                                // (every LDS x CHART x SPLIT)
     default: return false;
     }
 }
@@ -375,6 +380,30 @@ struct trc_stage { trc_kernel_id id; int threads; size_t lds; };
 // ... of a shading kernel: the class it serves (-1: the only shading kernel, every kind) and the tables it stages
 struct trc_shade_stage { trc_kernel_id id; int threads; size_t lds; int cls, lds_tables, lds_fm_bins; };
 
+// k_s_shade_p's image: that of TRC_IMG_SHADE_X with the sample grid and the birth vector (W doubles each) behind it.  They belong to
+// the tables -- all in LDS or none, so that every access has a known address space: the LDS instance serves a call whose image fits
+// the kernel's limit WITH them, and a long optics table or a long grid sends the tables, the grid and the birth vector to global
+// memory together.  The lambda cells of the polychromatic walls (per wall and sample a weight and a cell, and a word per surface)
+// follow when they fit the same limit too: *cells = the walls staged, all of them or 0 (then every hit searches).
+static inline size_t trc_poly_grid_bytes(int W) { return (size_t)16 * (size_t)W; }
+static inline size_t trc_poly_cells_bytes(int W, int walls, int n_surf) {
+    return (size_t)walls * W * 8 + (((size_t)walls * W + 1) / 2) * 8 + (((size_t)n_surf + 1) / 2) * 8;
+}
+static inline size_t trc_shade_p_choose(const trc_scene_facts &sc, int W, int walls, bool *in_lds, int *lds_fm_bins, int *cells) {
+    const int img = TRC_IMG_SHADE_X;
+    auto need = [&](bool lds, int bins) {
+        const trc_shade_layout L = trc_shade_lds_layout(trc_shade_lds_parts(img, lds, sc.n_surf, sc.stride, sc.n_fm_edges, sc.fms_bytes, sc.n_extra, bins));
+        return L.end + L.slack + (lds ? trc_poly_grid_bytes(W) : 0);
+    };
+    *in_lds = need(true, 0) <= trc_shade_lds_limit(img, false);
+    *lds_fm_bins = (sc.fm_bins > 0 && *in_lds && need(true, (int)sc.fm_bins) <= trc_shade_lds_limit(img, true)) ? (int)sc.fm_bins : 0;
+    size_t lds = need(*in_lds, *lds_fm_bins);
+    const size_t b_cells = trc_poly_cells_bytes(W, walls, sc.n_surf);
+    *cells = (*in_lds && walls > 0 && lds + b_cells <= trc_shade_lds_limit(img, *lds_fm_bins > 0)) ? walls : 0;
+    if (*cells) lds += b_cells;
+    return lds;
+}
+
 // The kernels a streaming call runs and the per-call decisions its bounces are planned by
 struct trc_stream_forms {
     int src_kind;
@@ -396,6 +425,7 @@ struct trc_stream_forms {
     double listed_share;         // ... and lists for k_s_fresh (an estimate for its grid: the covered part of the source)
     // what the choice sets in StreamParams
     int search, lds_recs, lds_tally, lds_tables, lds_extra, lds_fm_bins, bg_occ_words, shade_term_cls, split_terminal;
+    int poly_cells;              // CarryIn.poly_cells: the polychromatic walls whose lambda cells k_s_shade_p stages (0 for every other call)
 };
 
 static inline trc_lds_parts trc_fresh_parts(const trc_facts &f, bool buie, bool lds, int queue_waves) {
@@ -422,7 +452,8 @@ static inline void trc_stream_form_general(trc_stream_forms &F, const trc_facts 
 
 // The shading kernels: one per optics class present in the scene (trc_shade.hip), each taking its hits off the bounce's list, or one
 // for every hit (k_s_shade_x) when the rays carry more than the fast engine's record (carry), among them the calls on a scene whose
-// optics send two rays on from a hit (its SPLIT form).  false: no instance (device material tables beside a chart flux map).
+// optics send two rays on from a hit (its SPLIT form) -- k_s_shade_p in its place when the source carries its spectrum (poly_src).
+// false: no instance (device material tables beside a chart flux map, or beside a carried spectrum).
 static inline bool trc_stream_form_shade(trc_stream_forms &F, const trc_facts &f) {
     const trc_scene_facts &sc = f.scene;
     const bool carry = f.call.carry, spec = f.call.spec, chart = sc.chart;
@@ -432,8 +463,12 @@ static inline bool trc_stream_form_shade(trc_stream_forms &F, const trc_facts &f
     // k_s_shade, or k_s_shade_x for rays that carry more (the same image): tallies, records, optics parameters, flux-map tables, flags
     // and table values in LDS -- all of them or none (its LDS instance knows the address space of every table; see the kernel) -- and
     // the flux-map bins too while a workgroup stays within half a CU's LDS (two workgroups per CU)
+    // (k_s_shade_p, for a source that carries its spectrum: the same image with grid, birth vector and cells, trc_shade_p_choose)
+    const bool poly = carry && f.call.poly_src > 0;
     bool shade_lds;
-    const size_t lds_shade = choose(carry ? TRC_IMG_SHADE_X : TRC_IMG_SHADE, &shade_lds, &F.lds_fm_bins);
+    F.poly_cells = 0;
+    const size_t lds_shade = poly ? trc_shade_p_choose(sc, f.call.poly_src, f.call.poly_walls, &shade_lds, &F.lds_fm_bins, &F.poly_cells)
+                                  : choose(carry ? TRC_IMG_SHADE_X : TRC_IMG_SHADE, &shade_lds, &F.lds_fm_bins);
     F.lds_tally = F.lds_tables = F.lds_extra = shade_lds ? 1 : 0;
     // A flux map in another chart than XY: the instances that know the charts -- of k_s_shade and of the lean kernels the ones for
     // any geometry and any optics, which serve flat mirrors and walls with the same arithmetic.  Hits on surfaces that end every ray
@@ -471,8 +506,8 @@ static inline bool trc_stream_form_shade(trc_stream_forms &F, const trc_facts &f
         K.cls = carry ? -1 : TRC_CLS_GENERAL;
         K.lds = lds_shade; K.lds_tables = F.lds_tables; K.lds_fm_bins = F.lds_fm_bins;
         if (carry) {            // sixteen waves per workgroup; the MAT instances read the materials' tables on the device
-            if (f.call.mat_dev && chart) return false;
-            K.id = trc_kid(TRC_K_SHADE_X, shade_lds, chart, sc.splits, f.call.mat_dev);
+            if (f.call.mat_dev && (chart || poly)) return false;       // (nor a MAT instance of k_s_shade_p)
+            K.id = poly ? trc_kid(TRC_K_SHADE_P, shade_lds, chart, sc.splits) : trc_kid(TRC_K_SHADE_X, shade_lds, chart, sc.splits, f.call.mat_dev);
             K.threads = SHC_THREADS;
         } else {                // 2 waves per SIMD: four workgroups of 256 per CU in two rounds; scenes of flat surfaces with mirror /
                                 // diffuse optics only (heliostat fields, plate cavities): the SIMPLE instance

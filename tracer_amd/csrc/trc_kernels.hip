@@ -499,6 +499,8 @@ struct trc_scene {
     bool src_host_ok;
     DevBuf<double> d_last[7];         // device side of trc_trace_fast's `last` bundle, kept between calls (seven hipMalloc / hipFree per
     int64_t d_last_cap;               // call were a millisecond of a Monte-Carlo loop's 1e6-ray calls)
+    DevBuf<double> d_last_x;          // ... and the spectra of the rays a source that carries its spectrum leaves (W rows, d_last_x_len doubles)
+    size_t d_last_x_len = 0;
     HitBuffer hits;
 };
 
@@ -2670,12 +2672,24 @@ __global__ __launch_bounds__(256) void k_source_spectrum(const double *tab, int 
     }
 }
 
+// A carried spectrum (TRC_SPECTRUM_CARRIED): every ray i brings all n_tab points -- sample w at [w * stride + i]: the grid's
+// wavelength, and e[i] * val[w], whose trapezoid integral is the ray's energy (tab = wl | val | cdf)
+__global__ __launch_bounds__(256) void k_source_carried(const double *tab, int n_tab, long long n, long long stride, const double *e,
+                                                        double *spec_wl, double *spectra) {
+    const long long total = (long long)n_tab * n;
+    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < total; k += (long long)gridDim.x * blockDim.x) {
+        const long long w = k / n, i = k - w * n;
+        if (spec_wl) spec_wl[w * stride + i] = tab[w];
+        if (spectra) spectra[w * stride + i] = e[i] * tab[n_tab + w];
+    }
+}
+
 // A spectrum checked and packed for the device: wl | density normalised to a unit trapezoid integral | its running integral
 // (float64 on the host; the last entry of the CDF is 1 exactly, so every u in [0, 1) finds an interval of positive mass).
 static int spectrum_pack(const trc_source_spectrum *sp, const char *who, std::vector<double> &tab) {
     tab.clear();
-    if (sp->kind != TRC_SPECTRUM_CONSTANT && sp->kind != TRC_SPECTRUM_TABLE)
-        return trc_fail(TRC_ERR_INVALID, "%s: spectrum kind %d is neither CONSTANT nor TABLE", who, sp->kind);
+    if (sp->kind != TRC_SPECTRUM_CONSTANT && sp->kind != TRC_SPECTRUM_TABLE && sp->kind != TRC_SPECTRUM_CARRIED)
+        return trc_fail(TRC_ERR_INVALID, "%s: spectrum kind %d is neither CONSTANT nor TABLE nor CARRIED", who, sp->kind);
     if (!std::isfinite(sp->ref_index) || !(sp->ref_index > 0.0))
         return trc_fail(TRC_ERR_INVALID, "%s: spectrum ref_index must be finite and positive", who);
     if (sp->kind == TRC_SPECTRUM_CONSTANT) {
@@ -2707,6 +2721,7 @@ static int spectrum_pack(const trc_source_spectrum *sp, const char *who, std::ve
 }
 
 static bool spectrum_given(const trc_source_spectrum *sp) { return sp && sp->kind != TRC_SPECTRUM_NONE; }
+static bool spectrum_carried(const trc_source_spectrum *sp) { return sp && sp->kind == TRC_SPECTRUM_CARRIED; }
 
 // wl / ref (device columns, either may be NULL) of source rays offset .. offset+n-1 on the context's stream
 static int spectrum_fill(trc_ctx *ctx, const trc_source_spectrum *sp, const std::vector<double> &tab, int64_t n, uint64_t seed,
@@ -2717,10 +2732,26 @@ static int spectrum_fill(trc_ctx *ctx, const trc_source_spectrum *sp, const std:
     if (n_tab) TRC_TRY(dev_upload(d_tab, tab.data(), tab.size(), "spectrum upload failed"));
     long long grid = (n + 255) / 256;
     if (grid > 8192) grid = 8192;
+    // (a carried spectrum: no wavelength is drawn, the rays' scalar wavelength is 0 as for a given polychromatic bundle)
     hipLaunchKernelGGL(k_source_spectrum, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const double *)d_tab.get(), n_tab, sp->kind,
-                       sp->wavelength, sp->ref_index, (long long)n, (unsigned long long)seed, (unsigned long long)ray_offset, wl, ref);
+                       spectrum_carried(sp) ? 0.0 : sp->wavelength, sp->ref_index, (long long)n, (unsigned long long)seed, (unsigned long long)ray_offset, wl, ref);
     hipError_t se = hipStreamSynchronize(ctx->stream);
     if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_source_spectrum failed: %s", hipGetErrorString(se));
+    return TRC_OK;
+}
+
+// spec_wl / spectra (device, rows `stride` apart, either may be NULL) of n source rays of energies e (device) under a carried spectrum
+static int carried_fill(trc_ctx *ctx, const trc_source_spectrum *sp, const std::vector<double> &tab, int64_t n, int64_t stride, const double *e,
+                        double *spec_wl, double *spectra) {
+    if (n == 0 || (!spec_wl && !spectra)) return TRC_OK;
+    DevBuf<double> d_tab;
+    TRC_TRY(dev_upload(d_tab, tab.data(), tab.size(), "spectrum upload failed"));
+    long long grid = ((long long)sp->n * n + 255) / 256;
+    if (grid > 8192) grid = 8192;
+    hipLaunchKernelGGL(k_source_carried, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const double *)d_tab.get(), (int)sp->n, (long long)n,
+                       (long long)stride, e, spec_wl, spectra);
+    hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_source_carried failed: %s", hipGetErrorString(se));
     return TRC_OK;
 }
 
@@ -2730,7 +2761,22 @@ extern "C" int trc_source_generate_x(trc_ctx *ctx, const trc_source_desc *src, c
     if (!ctx || !src || n < 0) return trc_fail(TRC_ERR_INVALID, "trc_source_generate_x: bad arguments");
     std::vector<double> tab;
     TRC_TRY(spectrum_pack(spec, "trc_source_generate_x", tab));
+    if (spectrum_carried(spec) && (!out || !out->spec_wl || !out->spectra || out->n_spec != spec->n))
+        return trc_fail(TRC_ERR_INVALID, "trc_source_generate_x: a carried spectrum of %d points fills out->spec_wl and out->spectra, which need n_spec == %d",
+                        spec->n, spec->n);
     TRC_TRY(trc_source_generate(ctx, src, n, seed, ray_offset, out));
+    if (spectrum_carried(spec) && n > 0) {
+        if (out->on_device) TRC_TRY(carried_fill(ctx, spec, tab, n, out->n, out->e, out->spec_wl, out->spectra));
+        else {
+            DevBuf<double> d_e, d_x[2];
+            TRC_TRY(dev_upload(d_e, out->e, (size_t)n, "energy upload failed"));
+            for (auto &b : d_x) TRC_TRY(b.alloc((size_t)spec->n * (size_t)n));
+            TRC_TRY(carried_fill(ctx, spec, tab, n, n, d_e.get(), d_x[0].get(), d_x[1].get()));
+            double *host[2] = {out->spec_wl, out->spectra};
+            for (int i = 0; i < 2; ++i)
+                HIP_TRY(hipMemcpy2D(host[i], (size_t)out->n * 8, d_x[i].get(), (size_t)n * 8, (size_t)n * 8, (size_t)spec->n, hipMemcpyDeviceToHost));
+        }
+    }
     if (n == 0 || (!out->wavelength && !out->ref_index)) return TRC_OK;
     if (out->on_device) return spectrum_fill(ctx, spec, tab, n, seed, ray_offset, out->wavelength, out->ref_index);
     DevBuf<double> d[2];
@@ -2748,6 +2794,7 @@ extern "C" int trc_source_generate_x(trc_ctx *ctx, const trc_source_desc *src, c
 struct SourceSpectrum {
     const trc_source_spectrum *desc = nullptr;
     std::vector<double> tab;
+    int carried() const { return spectrum_carried(desc) ? desc->n : 0; }      // the samples W every ray carries (TRC_SPECTRUM_CARRIED), else 0
 };
 
 // ... made by the _x entry points (`who`) from their arguments; a spectrum belongs to a source descriptor
@@ -2764,7 +2811,7 @@ static int source_spectrum_make(const trc_source_spectrum *spec, const trc_rays 
 // table), in a buffer kept on the scene between calls.  The SPEC instances of the kernels draw the wavelength where a source ray
 // first needs one.
 static int scene_stage_spectrum(trc_scene *sc, const SourceSpectrum &sp, const double **d_spec) {
-    const int n_tab = sp.desc->kind == TRC_SPECTRUM_TABLE ? sp.desc->n : 0;
+    const int n_tab = sp.desc->kind != TRC_SPECTRUM_CONSTANT ? sp.desc->n : 0;
     std::vector<double> packed((size_t)3 + sp.tab.size());
     packed[0] = (double)n_tab; packed[1] = sp.desc->wavelength; packed[2] = sp.desc->ref_index;
     std::copy(sp.tab.begin(), sp.tab.end(), packed.begin() + 3);
@@ -2804,11 +2851,14 @@ static bool scene_mat_route(const trc_scene *sc, const trc_rays *in) {
 // What the bundle `in` (NULL: a source descriptor, whose rays carry nothing but what its spectrum gives them: has_spec) brings
 // beyond the nine columns, against what the scene's optics read: lay->n_mat and lay->W.  has_im is the ordered engine's to set.
 // *mat_dev: scene_mat_route -- the materials' indices come from the scene's tables, lay->n_mat is 0.
-static int check_carried(const trc_scene *sc, const trc_rays *in, bool has_spec, const char *who, PayLayout *lay, bool *mat_dev) {
+// carried_W: the source carries its spectrum (TRC_SPECTRUM_CARRIED) -- its rays bring W samples each, and no wavelength of their own.
+static int check_carried(const trc_scene *sc, const trc_rays *in, bool has_spec, int carried_W, const char *who, PayLayout *lay, bool *mat_dev) {
     const CarryNeeds &needs = sc->needs;
     lay->n_mat = (in && in->mat) ? (int)in->n_mat : 0;
-    lay->W = (in && in->spectra && in->spec_wl) ? in->n_spec : 0;
+    lay->W = (in && in->spectra && in->spec_wl) ? in->n_spec : (!in ? carried_W : 0);
     *mat_dev = scene_mat_route(sc, in);
+    if (!in && carried_W > 0 && needs.max_mat >= 0)
+        return trc_fail(TRC_ERR_UNSUPPORTED, "%s: the scene refracts between tabulated materials, and a ray that carries the source's spectrum has no single wavelength to evaluate them at", who);
     if (lay->W < 0 || lay->W > 4096 || lay->n_mat < 0 || lay->n_mat > 64) return trc_fail(TRC_ERR_INVALID, "%s: n_spec or n_mat out of range", who);
     if (needs.max_mat >= 0 && *mat_dev) {
         if (in && !in->wavelength)
@@ -2863,9 +2913,12 @@ struct FastCall {
     DevBuf<double> carry_own[4];
     const trc_source_desc *d_src;
     const double *d_spec;
-    // fast_stage_last
+    // fast_stage_last (d_last_x: spectra of the rays left, for a source that carries its spectrum, kept on the scene as d_last is;
+    // last_wl: their sample wavelengths, for a caller that wants the grid tiled)
     double *d_last[7];
     int64_t last_cap;
+    double *d_last_x;
+    DevBuf<double> last_wl;
     // fast_begin
     CounterValues before;
     int64_t dirty_before;
@@ -2887,14 +2940,16 @@ static int fast_check_args(FastCall &C) {
     // more are: not by the megakernel, not in calls too small for that form, and not under a source with a spectrum -- unless the
     // scene's materials are on the device: the MAT instances of k_s_shade_x are the ones that draw wavelengths.
     const bool mat_dev = scene_mat_route(sc, C.in);
-    if (sc->splits && ((C.flags & TRC_TRACE_MEGAKERNEL) || C.n < 64 || (C.spec->desc && !mat_dev)))
+    const int carried_W = C.spec->carried();
+    if (sc->splits && ((C.flags & TRC_TRACE_MEGAKERNEL) || C.n < 64 || (C.spec->desc && !mat_dev && !carried_W)))
         return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has ray-splitting optics, which the fast engine traces in its streaming form only (64 rays or more, no source spectrum): use trc_trace_ordered");
     C.facts.knobs = stream_knobs();
     // Rays that carry the imaginary part of a complex index, materials evaluated at their wavelength or a sampled spectrum are
     // traced by the streaming form (k_s_shade_x); the megakernel knows nothing of them.
-    C.carry = sc->needs.any() || (C.in && (C.in->ref_index_im || C.in->spectra || C.in->mat));
-    if (C.carry && !C.in && !mat_dev) return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has optics that read what only the rays of a given bundle carry (materials, spectra)");
-    TRC_TRY(check_carried(sc, C.in, C.spec->desc != nullptr, "trc_trace_fast", &C.lay, &C.mat_dev));
+    // ... and so are the rays of a source that carries its spectrum (k_s_shade_p)
+    C.carry = sc->needs.any() || (C.in && (C.in->ref_index_im || C.in->spectra || C.in->mat)) || carried_W > 0;
+    if (C.carry && !C.in && !mat_dev && !carried_W) return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has optics that read what only the rays of a given bundle carry (materials, spectra)");
+    TRC_TRY(check_carried(sc, C.in, C.spec->desc != nullptr, carried_W, "trc_trace_fast", &C.lay, &C.mat_dev));
     if (C.carry && ((C.flags & TRC_TRACE_MEGAKERNEL) || C.n < 64))
         return trc_fail(TRC_ERR_UNSUPPORTED, "complex refractive indices and spectra travel with the streaming form of the fast engine (64 rays or more) and with trc_trace_ordered");
     return TRC_OK;
@@ -2936,6 +2991,18 @@ static int fast_stage_last(FastCall &C) {
         sc->d_last_cap = C.last_cap;
     }
     for (int i = 0; i < 7; ++i) C.d_last[i] = sc->d_last[i].get();
+    // the rays left by a source that carries its spectrum bring their spectra back, when the caller made room for them
+    const int W = C.spec->carried();
+    if (W > 0 && last->spectra && last->n_spec == W && C.last_cap > 0) {
+        const size_t need = (size_t)W * (size_t)C.last_cap;
+        if (sc->d_last_x_len < need) {
+            sc->d_last_x_len = 0;
+            TRC_TRY(sc->d_last_x.alloc(need));
+            sc->d_last_x_len = need;
+        }
+        C.d_last_x = sc->d_last_x.get();
+        if (last->spec_wl) TRC_TRY(C.last_wl.alloc(need));
+    }
     return TRC_OK;
 }
 
@@ -2969,12 +3036,17 @@ static void fast_params(const FastCall &C, const MegaPlan &M, FastParams *P, Car
     carry_in->ref_im = C.carry_d[0]; carry_in->mat = C.carry_d[1]; carry_in->spec_wl = C.carry_d[2]; carry_in->spec = C.carry_d[3];
     carry_in->n_mat = C.lay.n_mat; carry_in->n_spec = C.lay.W;
     carry_in->mat_tab = C.mat_dev ? C.sc->d_mat_tab.get() : nullptr;
+    carry_in->last_spec = C.d_last_x; carry_in->last_wl = C.last_wl.get();
 }
 
 // the facts of the call for the decisions of trc_forms.h (the scene's without the pass over its surfaces; the knobs are there already)
 static void fast_facts(FastCall &C) {
     C.facts.scene = scene_facts(C.sc, false);
-    C.facts.call = {C.n, C.flags, C.src ? C.src->kind : -1, C.d_spec != nullptr, C.carry, C.mat_dev && C.sc->d_mat_tab.get(), C.min_energy >= 0.0};
+    int poly_walls = 0;
+    if (C.spec->carried())
+        for (int i = 0; i < C.sc->n_surf; ++i) poly_walls += C.sc->surfs[i].optics_kind == TRC_OPT_LAMBERTIAN_POLYCHROMATIC ? 1 : 0;
+    C.facts.call = {C.n, C.flags, C.src ? C.src->kind : -1, C.d_spec != nullptr, C.carry, C.mat_dev && C.sc->d_mat_tab.get(), C.min_energy >= 0.0,
+                    C.spec->carried(), poly_walls};
 }
 
 // the megakernel's instance of an id (mega_plan, trc_forms.h); null: the library has none
@@ -3055,6 +3127,11 @@ static int fast_finish(FastCall &C) {
         if (m > C.last_cap) return trc_fail(TRC_ERR_CAPACITY, "%lld rays left but `last` holds %lld", (long long)m, (long long)C.last_cap);
         double *dst[7] = {last->x, last->y, last->z, last->dx, last->dy, last->dz, last->e};
         for (int i = 0; i < 7 && m > 0; ++i) TRC_TRY(dev_download(dst[i], C.d_last[i], (size_t)m));
+        double *dst_x[2] = {last->spectra, last->spec_wl};      // (rows last_cap apart on both sides)
+        const double *src_x[2] = {C.d_last_x, C.last_wl.get()};
+        for (int i = 0; i < 2 && m > 0; ++i)
+            if (src_x[i])
+                HIP_TRY(hipMemcpy2D(dst_x[i], (size_t)C.last_cap * 8, src_x[i], (size_t)C.last_cap * 8, (size_t)m * 8, (size_t)C.spec->carried(), hipMemcpyDeviceToHost));
         last->n = m;
     }
     return TRC_OK;
@@ -3153,6 +3230,9 @@ static int ordered_level0(OrdCall &C, const trc_rays *in, const trc_source_desc 
                            (unsigned long long)C.seed, (unsigned long long)ray_offset, B0.x, B0.y, B0.z, B0.dx, B0.dy, B0.dz, B0.e, B0.rid);
         if (spec.desc) {     // level 0 carries the wavelengths the source's spectrum gives its rays, and their index
             TRC_TRY(spectrum_fill(ctx, spec.desc, spec.tab, n, C.seed, ray_offset, B0.wl, B0.ref));
+            // ... or, under a carried spectrum, the sample wavelengths and spectra of a polychromatic bundle: the level's own rows
+            if (spec.carried() && lay.W == spec.carried())
+                TRC_TRY(carried_fill(ctx, spec.desc, spec.tab, n, n, B0.e, B0.pay + (size_t)lay.r_wl() * n, B0.pay + (size_t)lay.r_spec() * n));
         } else { fill_f64(ctx->stream, g0, B0.ref, n, 1.0); fill_f64(ctx->stream, g0, B0.wl, n, 0.0); }
         // (a scene between materials whose tables are on the device: the source's rays start with a real index)
         if (lay.has_im && n > 0 && hipMemsetAsync(B0.pay, 0, (size_t)n * 8, ctx->stream) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "level 0 setup failed");
@@ -3312,7 +3392,7 @@ static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_sourc
     // index whether the bundle brought it or not
     PayLayout lay;
     bool mat_dev = false;
-    TRC_TRY(check_carried(sc, in, spec.desc != nullptr, "trc_trace_ordered", &lay, &mat_dev));
+    TRC_TRY(check_carried(sc, in, spec.desc != nullptr, spec.carried(), "trc_trace_ordered", &lay, &mat_dev));
     lay.has_im = ((in && in->ref_index_im) || sc->needs.max_mat >= 0) ? 1 : 0;
     std::unique_ptr<trc_result> res(new (std::nothrow) trc_result());
     if (!res) return trc_fail(TRC_ERR_NOMEM, "out of host memory");

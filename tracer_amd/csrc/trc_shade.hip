@@ -216,8 +216,21 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
 //        them: a hit between materials evaluates both at the ray's wavelength (trc_shade_xt), and the ray of a source descriptor
 //        draws its wavelength from the source's spectrum at its first hit, with the spectrum's index and no imaginary part -- as
 //        the lean SPEC kernels do (k_s_shade_c).  The children of a SPLIT hit inherit the wavelength like every other ray.
-template <bool LDS, bool CHART = false, bool SPLIT = false, bool MAT = false>
-__global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
+//
+// k_s_shade_p: the same stage for a source that CARRIES its spectrum (TRC_SPECTRUM_CARRIED): every ray is born with the W points of
+// the source's table as its sample wavelengths and src->energy * val[w] as its spectrum, so neither is a per-ray column:
+//   sample wavelengths    the grid wl[W] of the call's packed spectrum (FastParams.spec), stride 1, at every bounce
+//   spectrum              at a ray's first hit the birth vector src->energy * val[w], from the second on the slot table as above
+//   index                 spec[2]; no wavelength and no Im of the index is drawn or read
+// Its LDS instances stage grid and birth vector behind the image of TRC_IMG_SHADE_X (the host counts them into the image: all tables
+// or none, trc_stream_form_shade), and -- when they fit too (CarryIn.poly_cells) -- the lambda cell and weight of every sample in
+// every polychromatic wall's table, which no ray changes; the other instances read grid and values from the packed spectrum and
+// search per hit.  At a polychromatic wall the theta cell is found once per hit and every sample is blended by trc_interp2_at, the
+// expression of trc_interp2: one evaluation per sample serves the integral and the spectrum that goes on (a captured hit, whose
+// place in the hit buffer is known only after its energy, evaluates once more for its 3 W columns and writes both then).
+// With TRC_TRACE_KEEP_LAST the rays left write their spectra too (CarryIn.last_spec).  Both families are one body: POLY.
+template <bool LDS, bool CHART, bool SPLIT, bool MAT, bool POLY>
+__device__ __forceinline__ void shade_x_body(const StreamParams &S) {
     extern __shared__ double lds[];
     const FastParams &P = S.P;
     const DScene &sc = P.sc;
@@ -253,6 +266,43 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
         for (int i = threadIdx.x; i < S.lds_fm_bins; i += blockDim.x) l_fm[i] = 0.0;
     }
     const double src_energy = P.src ? P.src->energy : 0.0;
+    const CarryIn &C = S.carry;
+    // (POLY) the sample grid and the values of the call's packed spectrum; in the LDS instances grid and birth vector as offsets into
+    // lds[], so that every access has a known address space, and behind them the walls' lambda cells (weights, cells, surface -> wall)
+    const int pW = POLY ? C.n_spec : 0;
+    const double *g_wl = POLY ? P.spec + 3 : nullptr, *g_val = POLY ? P.spec + 3 + pW : nullptr;
+    int o_wl = 0, o_birth = 0, o_cw = 0;
+    const int32_t *l_ci = nullptr, *l_wall = nullptr;
+    int n_cells = 0;
+    if constexpr (POLY && LDS) {
+        o_wl = (int)(cur - lds); o_birth = o_wl + pW; cur += 2 * pW;
+        for (int i = threadIdx.x; i < pW; i += blockDim.x) { lds[o_wl + i] = g_wl[i]; lds[o_birth + i] = src_energy * g_val[i]; }
+        n_cells = C.poly_cells;
+        if (n_cells > 0) {
+            o_cw = (int)(cur - lds); cur += (size_t)n_cells * pW;
+            int32_t *ci = (int32_t *)cur; cur += ((size_t)n_cells * pW + 1) / 2;
+            int32_t *wall = (int32_t *)cur; cur += (Sn + 1) / 2;
+            __syncthreads();            // (the records and tables the cells are made from)
+            if (threadIdx.x == 0) {
+                int k = 0;
+                for (int s = 0; s < Sn; ++s)
+                    wall[s] = (trc_rec_opt_kind(L.recs + (size_t)s * sc.stride) == TRC_OPT_LAMBERTIAN_POLYCHROMATIC && k < n_cells) ? k++ : -1;
+            }
+            __syncthreads();
+            for (int s = 0; s < Sn; ++s) {
+                const int p = wall[s];
+                if (p < 0) continue;
+                const double *tab = L.extra + trc_rec_extra_off(L.recs + (size_t)s * sc.stride);
+                const int nt = (int)tab[0], nl = (int)tab[1];
+                for (int w = threadIdx.x; w < pW; w += blockDim.x) {
+                    double wlam;
+                    ci[p * pW + w] = trc_grid_cell(tab + 2 + nt, nl, lds[o_wl + w], &wlam);
+                    lds[o_cw + p * pW + w] = wlam;
+                }
+            }
+            l_ci = ci; l_wall = wall;
+        }
+    }
     __syncthreads();
     long long nh = (long long)W.cnt[S.hl_cn];
     if (nh > S.hl_room) nh = S.hl_room;
@@ -265,8 +315,8 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
     unsigned n_hit = 0, n_alive = 0;
     const int bounce0 = S.bounce_no;
     const bool aux_in = !P.src || bounce0 > 0;
-    const CarryIn &C = S.carry;
     const int nW = C.slot_spec ? C.n_spec : 0;
+    const double ref_src = POLY ? P.spec[2] : 1.0;      // (POLY) the index of the medium the source's rays start in
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < padded; i += stride) {
         uint32_t slot = SQ_INVALID, hs = SQ_INVALID;
@@ -297,9 +347,9 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
             const bool first = bounce0 == 0;
             const int prev = first ? Sn : (int)((uint32_t)(g.tail >> 32) & ~SQ_SKIP_SELF);
             const long long ray = S.base + (long long)g.idx;            // the ray's place in the bundle's columns
-            double e = src_energy, ref = 1.0, wl = 0.0, ref_im = 0.0;
+            double e = src_energy, ref = ref_src, wl = 0.0, ref_im = 0.0;
             if (aux_in) { const SRayAux a = W.aux[slot]; e = a.e; ref = a.ref; wl = a.wl; ref_im = a.pad; }
-            if (first) ref_im = C.ref_im ? C.ref_im[ray] : 0.0;
+            if (!POLY && first) ref_im = C.ref_im ? C.ref_im[ray] : 0.0;
             const double *rec = L.recs + (size_t)s * sc.stride;
             double hx = g.px + t * g.dx, hy = g.py + t * g.dy, hz = g.pz + t * g.dz;
             double nx, ny, nz;
@@ -308,10 +358,34 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
             trc_ray_ext X;
             X.ref_im = ref_im; X.W = nW; X.n_mat = (!MAT && C.mat) ? C.n_mat : 0; X.stride = P.n;
             X.mat = (!MAT && C.mat) ? C.mat + ray : nullptr;
-            X.wl = nW ? C.spec_wl + ray : nullptr;
-            X.spec = nW ? C.spec + ray : nullptr;
+            X.wl = (!POLY && nW) ? C.spec_wl + ray : nullptr;
+            X.spec = (!POLY && nW) ? C.spec + ray : nullptr;
             long long spec_stride = P.n;                                 // ... of the spectrum as it reaches this hit
             if (nW && !first) { X.spec = C.slot_spec + slot; spec_stride = W.room; }
+            // sample wavelength w and sample w of the spectrum that arrives: the bundle's columns with their strides, or (POLY) the
+            // grid with stride 1 and, at the first hit, the birth vector
+            auto wl_of = [&](int w) -> double {
+                if constexpr (POLY) return LDS ? lds[o_wl + w] : g_wl[w];
+                else return X.wl[(long long)w * P.n];
+            };
+            auto spec_of = [&](int w) -> double {
+                if constexpr (POLY) { if (first) return LDS ? lds[o_birth + w] : src_energy * g_val[w]; }
+                return X.spec[(long long)w * spec_stride];
+            };
+            // (POLY) a polychromatic wall: the theta cell of the hit, the wall's row of staged lambda cells (-1: searched), and
+            // whether the spectrum that goes on is in the slot table already
+            int p_it = 0, p_wall = -1;
+            double p_wt = 0.0;
+            bool p_done = false;
+            auto poly_abs = [&](const double *tab, double th, int w, double xw) -> double {
+                if constexpr (POLY) {
+                    double wlam;
+                    int il;
+                    if (p_wall >= 0) { il = l_ci[p_wall * pW + w]; wlam = lds[o_cw + p_wall * pW + w]; }
+                    else il = trc_grid_cell(tab + 2 + (int)tab[0], (int)tab[1], xw, &wlam);
+                    return trc_interp2_at(tab, p_it, p_wt, il, wlam);
+                } else return trc_poly_absorptance(tab, th, xw);
+            };
             trc_ray_out out[2];
             double out_im[2], poly_th;
             unsigned long long rid = P.rid ? P.rid[ray] : (P.ray_offset + (unsigned long long)ray);
@@ -320,8 +394,8 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
             // (sample wavelengths and spectrum have different strides once the spectrum lives in the slot table: the polychromatic
             // wall reads both, so its integral is taken here with the two strides, the optics get the wavelengths' stride)
             int n_out;
-            if (nW && !first && trc_rec_opt_kind(rec) == TRC_OPT_LAMBERTIAN_POLYCHROMATIC) {
-                // trc_shade_x's branch (optics_callables.py:406-425) with the spectrum read from the slot table
+            if (nW && (POLY || !first) && trc_rec_opt_kind(rec) == TRC_OPT_LAMBERTIAN_POLYCHROMATIC) {
+                // trc_shade_x's branch (optics_callables.py:406-425) with the spectrum read from the slot table (POLY: or the birth vector)
                 out[0].blk = 0; out[1].blk = 1; out[0].back = out[1].back = 0.0; out[0].sf = out[1].sf = 1.0; out[0].shift = out[1].shift = 0.0;
                 out[0].ref = ref;
                 out_im[0] = out_im[1] = ref_im;
@@ -330,11 +404,18 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
                 const double th = acos(sqrt(wx * wx + wy * wy + wz * wz));
                 const double *tab = L.extra + trc_rec_extra_off(rec);
                 double en = 0.0, y0 = 0.0, x0 = 0.0;
+                if constexpr (POLY) {
+                    p_it = trc_grid_cell(tab + 2, (int)tab[0], th, &p_wt);
+                    if (n_cells > 0) p_wall = l_wall[s];
+                    // (a hit that is captured writes its spectrum with its 3 W columns, behind record_hit)
+                    p_done = !(P.capture && C.hit_x && (L.sflags[s] & TRC_SURF_CAPTURE_HITS));
+                }
                 for (int w = 0; w < nW; ++w) {
-                    const double xw = X.wl[(long long)w * P.n];
-                    const double yw = X.spec[(long long)w * spec_stride] * (1.0 - trc_poly_absorptance(tab, th, xw));
+                    const double xw = wl_of(w);
+                    const double yw = spec_of(w) * (1.0 - poly_abs(tab, th, w, xw));
                     if (w > 0) en += (xw - x0) * (yw + y0) / 2.0;
                     x0 = xw; y0 = yw;
+                    if (POLY && p_done) C.slot_spec[(long long)w * W.room + slot] = yw;
                 }
                 double u0, u1, ax, ay, az;
                 trc_uniform_pair(P.seed, rid, (uint32_t)(bounce0 + 1), 0, &u0, &u1);
@@ -362,12 +443,14 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
             if (nW && C.hit_x && hslot != ~0ull) {        // a captured hit of a polychromatic ray: wavelengths, spectrum in, spectrum out
                 const double *tab = L.extra + trc_rec_extra_off(rec);
                 for (int w = 0; w < nW; ++w) {
-                    const double xw = X.wl[(long long)w * P.n], yin = X.spec[(long long)w * spec_stride];
-                    const double f = poly_th >= 0.0 ? 1.0 - trc_poly_absorptance(tab, poly_th, xw) : (two ? out[0].sf + out[1].sf : out[0].sf);
+                    const double xw = wl_of(w), yin = spec_of(w);
+                    const double f = poly_th >= 0.0 ? 1.0 - poly_abs(tab, poly_th, w, xw) : (two ? out[0].sf + out[1].sf : out[0].sf);
                     C.hit_x[(long long)w * C.hit_x_cap + (long long)hslot] = xw;
                     C.hit_x[(long long)(nW + w) * C.hit_x_cap + (long long)hslot] = yin;
                     C.hit_x[(long long)(2 * nW + w) * C.hit_x_cap + (long long)hslot] = yin * f;
+                    if (POLY && poly_th >= 0.0) C.slot_spec[(long long)w * W.room + slot] = yin * f;      // (in place: sample w is not read again)
                 }
+                if (POLY && poly_th >= 0.0) p_done = true;
             }
             if constexpr (SPLIT) {
                 // the second ray, before the first goes back into the hit's slot (whose spectrum row it reads)
@@ -380,6 +463,10 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
                         if ((long long)q < P.last_cap) {
                             P.lx[q] = hx + out[1].shift * nx; P.ly[q] = hy + out[1].shift * ny; P.lz[q] = hz + out[1].shift * nz;
                             P.ldx[q] = out[1].dx; P.ldy[q] = out[1].dy; P.ldz[q] = out[1].dz; P.le[q] = out[1].e;
+                            if constexpr (POLY) {
+                                if (C.last_spec) for (int w = 0; w < nW; ++w) C.last_spec[(long long)w * P.last_cap + (long long)q] = spec_of(w) * out[1].sf;
+                                if (C.last_wl) for (int w = 0; w < nW; ++w) C.last_wl[(long long)w * P.last_cap + (long long)q] = wl_of(w);
+                            }
                         }
                     }
                 }
@@ -402,7 +489,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
                     ao.e = out[1].e; ao.ref = out[1].ref; ao.wl = wl; ao.pad = out_im[1];
                     W.aux[slot1] = ao;
                     C.slot_rid[slot1] = trc_child_rid(rid, (uint32_t)(bounce0 + 1));
-                    for (int w = 0; w < nW; ++w) C.slot_spec[(long long)w * W.room + slot1] = X.spec[(long long)w * spec_stride] * out[1].sf;
+                    for (int w = 0; w < nW; ++w) C.slot_spec[(long long)w * W.room + slot1] = spec_of(w) * out[1].sf;
                 }
             }
             const double ox = out[0].dx, oy = out[0].dy, oz = out[0].dz;
@@ -415,6 +502,16 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
                         if ((long long)q < P.last_cap) {
                             P.lx[q] = hx + out[0].shift * nx; P.ly[q] = hy + out[0].shift * ny; P.lz[q] = hz + out[0].shift * nz;
                             P.ldx[q] = ox; P.ldy[q] = oy; P.ldz[q] = oz; P.le[q] = e_out;
+                            if constexpr (POLY) {
+                                // the spectrum that leaves: at a polychromatic wall the one written above, or evaluated here
+                                const double *tab = L.extra + trc_rec_extra_off(rec);
+                                if (C.last_spec)
+                                    for (int w = 0; w < nW; ++w)
+                                        C.last_spec[(long long)w * P.last_cap + (long long)q] =
+                                            p_done ? C.slot_spec[(long long)w * W.room + slot]
+                                                   : spec_of(w) * (poly_th >= 0.0 ? 1.0 - poly_abs(tab, poly_th, w, wl_of(w)) : out[0].sf);
+                                if (C.last_wl) for (int w = 0; w < nW; ++w) C.last_wl[(long long)w * P.last_cap + (long long)q] = wl_of(w);
+                            }
                         }
                     }
                 } else {
@@ -432,11 +529,11 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
                     ao.e = e_out; ao.ref = out[0].ref; ao.wl = wl; ao.pad = out_im[0];
                     W.aux[slot] = ao;
                     if (SPLIT) C.slot_rid[slot] = rid;          // (the first ray keeps the parent's stream)
-                    if (nW) {       // the spectrum goes on with the ray (RayBundle.inherit, ray_bundle.py:117-143), the optics' changes applied
+                    if (nW && !(POLY && p_done)) {       // the spectrum goes on with the ray (RayBundle.inherit, ray_bundle.py:117-143), the optics' changes applied
                         const double *tab = L.extra + trc_rec_extra_off(rec);
                         for (int w = 0; w < nW; ++w) {
-                            const double f = poly_th >= 0.0 ? 1.0 - trc_poly_absorptance(tab, poly_th, X.wl[(long long)w * P.n]) : out[0].sf;
-                            C.slot_spec[(long long)w * W.room + slot] = X.spec[(long long)w * spec_stride] * f;
+                            const double f = poly_th >= 0.0 ? 1.0 - poly_abs(tab, poly_th, w, wl_of(w)) : out[0].sf;
+                            C.slot_spec[(long long)w * W.room + slot] = spec_of(w) * f;
                         }
                     }
                 }
@@ -456,6 +553,22 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) {
     if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
     flush_counts<true>(l_tally + (LDS ? 3 * Sn : 0), n_hit, n_alive, &W.cnt[CN(CW_HITS)], &W.cnt[CN(CW_CLS_HITS + TRC_CLS_GENERAL)], &W.cnt[CN(CW_ALIVE)]);
     flush_sums(L.tally, l_tally, LDS ? 3 * Sn : 0, l_fm, S.lds_fm_bins, Sn);
+}
+
+template <bool LDS, bool CHART = false, bool SPLIT = false, bool MAT = false>
+__global__ __launch_bounds__(SHC_THREADS) void k_s_shade_x(StreamParams S) { shade_x_body<LDS, CHART, SPLIT, MAT, false>(S); }
+
+// (no MAT x POLY instance: a carried ray has no single wavelength to evaluate m(lambda) at)
+template <bool LDS, bool CHART, bool SPLIT>
+__global__ __launch_bounds__(SHC_THREADS) void k_s_shade_p(StreamParams S) { shade_x_body<LDS, CHART, SPLIT, false, true>(S); }
+
+const void *trc_shade_poly_kernel(bool lds, bool chart, bool split) {
+    if (split) {
+        if (chart) return lds ? (const void *)k_s_shade_p<true, true, true> : (const void *)k_s_shade_p<false, true, true>;
+        return lds ? (const void *)k_s_shade_p<true, false, true> : (const void *)k_s_shade_p<false, false, true>;
+    }
+    if (chart) return lds ? (const void *)k_s_shade_p<true, true, false> : (const void *)k_s_shade_p<false, true, false>;
+    return lds ? (const void *)k_s_shade_p<true, false, false> : (const void *)k_s_shade_p<false, false, false>;
 }
 
 const void *trc_shade_carry_kernel(bool lds, bool chart, bool split, bool mat) {

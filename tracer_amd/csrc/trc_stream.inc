@@ -2229,6 +2229,7 @@ static const void *stream_kernel_fn(const trc_kernel_id &id) {
     case TRC_K_SHADE: return shade_kernel_fn(id);
     case TRC_K_SHADE_C: return trc_shade_lean_kernel(id.a[0], id.a[1] != 0, id.a[2] != 0, id.a[3] != 0, id.a[4] != 0);
     case TRC_K_SHADE_X: return trc_shade_carry_kernel(id.a[0] != 0, id.a[1] != 0, id.a[2] != 0, id.a[3] != 0);
+    case TRC_K_SHADE_P: return trc_shade_poly_kernel(id.a[0] != 0, id.a[1] != 0, id.a[2] != 0);
     default: return nullptr;
     }
 }
@@ -2284,6 +2285,7 @@ static int stream_choose_forms(StreamForms &F, StreamParams &SP0, trc_scene *sc,
     if (!trc_stream_decide(f, plan, &D)) return trc_fail(TRC_ERR_UNSUPPORTED, "no shading kernel for device material tables beside a chart flux map");
     SP0.search = D.search; SP0.lds_recs = D.lds_recs; SP0.P.lds_tally = D.lds_tally; SP0.lds_tables = D.lds_tables; SP0.lds_extra = D.lds_extra;
     SP0.lds_fm_bins = D.lds_fm_bins; SP0.bg_occ_words = D.bg_occ_words; SP0.shade_term_cls = D.shade_term_cls; SP0.split_terminal = D.split_terminal;
+    SP0.carry.poly_cells = D.poly_cells;
     SP0.hit_epoch = sc->hits.epoch;
     SP0.chunk_hitbuf = sc->hits.chunk_size();
     // 3. and 4. the instances, their grid caps and their LDS
@@ -2328,11 +2330,12 @@ static int stream_choose_forms(StreamForms &F, StreamParams &SP0, trc_scene *sc,
 
 // workspaces of the slots for batches of `cap` rays: queues, spectra of the rays under way, the class lists of k_s_partition
 static int stream_slots_alloc(StreamEngine &E, int n_slots, long long cap, const trc_scene *sc, const CarryIn &carry_in, const StreamForms &F, const StreamKnobs &K,
-                              bool split_rays) {
+                              bool split_rays, bool poly_src) {
     for (int k = 0; k < n_slots; ++k) {
         StreamSlot &Tk = E.slot[k];
         TRC_TRY(stream_ws_alloc(Tk.W, cap, (int)sc->accel.unbounded.size(), (long long)sc->tally_n, K));
-        const long long want = (carry_in.spec && carry_in.n_spec > 0) ? (long long)carry_in.n_spec * Tk.W.room : 0;
+        // (a source that carries its spectrum brings no columns, but its rays' spectra live in the slot table all the same)
+        const long long want = ((carry_in.spec || poly_src) && carry_in.n_spec > 0) ? (long long)carry_in.n_spec * Tk.W.room : 0;
         if (Tk.spec_len < want) {
             Tk.spec_len = 0;
             TRC_TRY(Tk.spec.alloc((size_t)want));
@@ -2816,14 +2819,14 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, c
     // shaded by k_s_shade_x; the spectra of the rays under way live in a table of their own beside the ray table
     // ... and so are all hits of a scene whose optics send two rays on from a hit, by its SPLIT form
     const bool split_rays = sc->splits;
-    facts.call.carry = sc->needs.any() || carry_in.ref_im || carry_in.mat || carry_in.spec || split_rays;
+    facts.call.carry = sc->needs.any() || carry_in.ref_im || carry_in.mat || carry_in.spec || split_rays || facts.call.poly_src > 0;
     StreamForms F;
     StreamCall C{F, K, E, StreamParams(), cap, 0.0, 0.0, {0.0, 0.0, 0.0}, 0, 0, split_rays};
     memset(&C.SP0, 0, sizeof(C.SP0));
     C.SP0.P = P;
     C.SP0.carry = carry_in;
     TRC_TRY(stream_choose_forms(F, C.SP0, sc, E, plan, facts, src_desc));
-    TRC_TRY(stream_slots_alloc(E, n_slots, cap, sc, carry_in, F, K, split_rays));
+    TRC_TRY(stream_slots_alloc(E, n_slots, cap, sc, carry_in, F, K, split_rays, facts.call.poly_src > 0));
 
     for (int k = 0; k < STREAM_MAX_SLOTS; ++k) E.slot[k].busy = false;
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));

@@ -561,7 +561,15 @@ class DeviceScene(object):
         if keep_last:
             m = n if last_capacity is None else call_plan.last_room(n, self.compiled.splits, last_capacity)
             last_cols = [N.empty(m) for _ in range(7)]
-            last = _cabi.make_rays(m, *last_cols)
+            carried = keep if (rays is None and keep is not None and keep.is_carried()) else None
+            if carried is not None:     # the rays a source that carries its spectrum leaves bring theirs back: (W, m) spectra and wavelengths
+                # (their sample wavelengths are the source's grid: a view of it, no column is fetched)
+                W = carried.wavelengths.size
+                last_cols += [_cabi.pinned_empty((W, m)), N.broadcast_to(carried.wavelengths[:, None], (W, m))]
+                last = _cabi.make_rays(m, *last_cols[:7])
+                last.n_spec, last.spectra = W, _cabi.ptr(last_cols[7])
+            else:
+                last = _cabi.make_rays(m, *last_cols)
         status = self.lib.trc_trace_fast_x(self.handle, C.byref(rays) if rays is not None else None,
                                            C.byref(src) if src is not None else None, C.byref(spec) if spec is not None else None,
                                            n, int(reps), float(min_energy), int(seed), int(off), flags,
@@ -571,7 +579,7 @@ class DeviceScene(object):
         _cabi.check(status)
         if keep_last:
             m = last.n
-            last_cols = [c[:m] for c in last_cols]
+            last_cols = [c[..., :m] for c in last_cols]
         return stats, last_cols
 
     def trace_ordered(self, bundle, reps, min_energy, seed, accel=False):

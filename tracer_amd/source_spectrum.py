@@ -3,6 +3,10 @@ Spectra of sources: every ray of a source descriptor gets one wavelength, drawn 
 the descriptor (include/tracer_amd.h, trc_source_spectrum; csrc/trc_core.h, trc_spectrum_draw).  The usual spectral Monte
 Carlo: a source with a spectrum stays a pending LazySourceBundle, and the engines trace it without host wavelength columns.
 
+A spectrum can also be CARRIED (SourceSpectrum.polychromatic, .as_polychromatic()): no wavelength is drawn, every source ray is
+polychromatic and carries all W points of the table as its sample wavelengths, with the spectrum energy_of_ray * table()[1] --
+one ray integrates the whole spectrum.  Such a bundle stays pending too; the device makes the (W, n) columns when they are needed.
+
 The table is a piecewise-linear spectral density, sampled by the inverse of its CDF as the reference's
 ray_trace_utils/sampling.py:35-52 (PW_linear_distribution.sample) does -- without its rounding of the abscissae to 8 decimals,
 which snaps wavelengths given in metres to 10 nm.
@@ -29,7 +33,8 @@ def planck(wl, T):
 
 class SourceSpectrum(object):
     """
-    A spectrum for a source descriptor: monochromatic (every ray has one wavelength) or tabulated (piecewise-linear density).
+    A spectrum for a source descriptor: monochromatic (every ray has one wavelength), tabulated (piecewise-linear density a
+    wavelength is drawn from per ray) or polychromatic (the same table, carried whole by every ray).
     ref_index is the index of the medium the rays start in.  Inputs are checked here (ValueError); desc() packs the
     trc_source_spectrum the C-ABI takes and keeps its arrays alive with the object.
     """
@@ -44,7 +49,7 @@ class SourceSpectrum(object):
         if kind == _cabi.SPECTRUM_CONSTANT:
             if not N.isfinite(self.wavelength):
                 raise ValueError("SourceSpectrum: the wavelength must be finite")
-        elif kind == _cabi.SPECTRUM_TABLE:
+        elif kind in (_cabi.SPECTRUM_TABLE, _cabi.SPECTRUM_CARRIED):
             wl = N.ascontiguousarray(N.ravel(N.asarray(wavelengths, dtype=float)))
             val = N.ascontiguousarray(N.ravel(N.asarray(values, dtype=float)))
             if wl.shape != val.shape:
@@ -71,6 +76,25 @@ class SourceSpectrum(object):
     def tabulated(cls, wavelengths, values, ref_index=1.):
         """spectral density `values` at `wavelengths`, linear in between, zero outside"""
         return cls(_cabi.SPECTRUM_TABLE, wavelengths=wavelengths, values=values, ref_index=ref_index)
+
+    @classmethod
+    def polychromatic(cls, wavelengths, values, ref_index=1.):
+        """the table of `tabulated`, carried: every source ray brings all W points as its sample wavelengths and the spectrum
+        energy_of_ray * table()[1] (its trapezoid integral is the ray's energy); the ray's scalar wavelength is 0"""
+        return cls(_cabi.SPECTRUM_CARRIED, wavelengths=wavelengths, values=values, ref_index=ref_index)
+
+    def as_polychromatic(self):
+        """this tabulated spectrum (planck(...), uniform(...)), carried by every ray instead of sampled"""
+        if not self.has_table():
+            raise ValueError("SourceSpectrum.as_polychromatic: a monochromatic spectrum has no table to carry")
+        return SourceSpectrum.polychromatic(self.wavelengths, self.values, self.ref_index)
+
+    def has_table(self):
+        return self.kind in (_cabi.SPECTRUM_TABLE, _cabi.SPECTRUM_CARRIED)
+
+    def is_carried(self):
+        """every ray carries the whole table (polychromatic) instead of one wavelength drawn from it"""
+        return self.kind == _cabi.SPECTRUM_CARRIED
 
     @classmethod
     def uniform(cls, lo, hi, ref_index=1.):
@@ -108,7 +132,7 @@ class SourceSpectrum(object):
     def table(self):
         """(wavelengths, density normalised to a unit trapezoid integral, its running integral): the table the device samples,
         packed as the library packs it (the running sum in order, divided by its last entry, which makes the CDF end at 1)."""
-        if self.kind != _cabi.SPECTRUM_TABLE:
+        if not self.has_table():
             raise ValueError("SourceSpectrum.table: a monochromatic spectrum has no table")
         wl, v = self.wavelengths, self.values
         cum = N.concatenate(([0.], N.cumsum((wl[1:] - wl[:-1]) * (v[1:] + v[:-1]) / 2.)))
@@ -121,7 +145,7 @@ class SourceSpectrum(object):
             d.kind = self.kind
             d.ref_index = self.ref_index
             d.wavelength = self.wavelength
-            if self.kind == _cabi.SPECTRUM_TABLE:
+            if self.has_table():
                 d.n = self.wavelengths.size
                 d.wl = self.wavelengths.ctypes.data_as(C.POINTER(C.c_double))
                 d.value = self.values.ctypes.data_as(C.POINTER(C.c_double))
@@ -131,5 +155,5 @@ class SourceSpectrum(object):
     def __repr__(self):
         if self.kind == _cabi.SPECTRUM_CONSTANT:
             return 'SourceSpectrum.monochromatic(%r, ref_index=%r)' % (self.wavelength, self.ref_index)
-        return 'SourceSpectrum.tabulated(<%d points, %g..%g>, ref_index=%r)' % (
-            self.wavelengths.size, self.wavelengths[0], self.wavelengths[-1], self.ref_index)
+        return 'SourceSpectrum.%s(<%d points, %g..%g>, ref_index=%r)' % (
+            'polychromatic' if self.is_carried() else 'tabulated', self.wavelengths.size, self.wavelengths[0], self.wavelengths[-1], self.ref_index)

@@ -27,11 +27,15 @@ class LazySourceBundle(RayBundle):
     def __init__(self, desc, n, seed, ray_offset=0, constant_columns=None, spectrum=None, spectral_columns=('wavelengths', 'ref_index'),
                  table=None):
         """spectrum: a source_spectrum.SourceSpectrum -- every ray gets a wavelength drawn on the device (the columns
-        `spectral_columns` of the materialised bundle); the bundle stays pending.  table: the SunshapeTable a tabulated
+        `spectral_columns` of the materialised bundle); the bundle stays pending.  A spectrum that is carried
+        (SourceSpectrum.polychromatic) makes the bundle polychromatic instead: materialised, it has `wavelengths` and `spectra`
+        of shape (W, n) and `ref_index`.  table: the SunshapeTable a tabulated
         sunshape's descriptor names (made on the device when the rays are first needed, kept alive with the bundle)."""
         if spectrum is not None and constant_columns:
             raise ValueError("a source bundle takes a spectrum or constant columns, not both")
         spectral_columns = tuple(spectral_columns) if spectrum is not None else ()
+        if spectrum is not None and spectrum.is_carried():
+            spectral_columns = ('wavelengths', 'spectra', 'ref_index')
         RayBundle.__init__(self, **dict((k, None) for k in tuple(constant_columns or {}) + spectral_columns))
         object.__setattr__(self, '_src_const', dict(constant_columns or {}))
         object.__setattr__(self, '_src_desc', desc)
@@ -79,9 +83,16 @@ class LazySourceBundle(RayBundle):
         d = _cabi.pinned_empty((3, n))
         e = _cabi.pinned_empty(n)
         spec = self._src_spectrum
-        wl = _cabi.pinned_empty(n) if 'wavelengths' in self._src_spec_cols else None
+        carried = spec is not None and spec.is_carried()
+        wl = _cabi.pinned_empty(n) if ('wavelengths' in self._src_spec_cols and not carried) else None
         ref = _cabi.pinned_empty(n) if 'ref_index' in self._src_spec_cols else None
-        rays = _cabi.make_rays(n, v[0], v[1], v[2], d[0], d[1], d[2], e, ref_index=ref, wavelength=wl)
+        if carried:     # every ray carries the W points of the table: `wavelengths` and `spectra` are (W, n)
+            W = spec.wavelengths.size
+            wl = _cabi.pinned_empty((W, n))
+            spectra = _cabi.pinned_empty((W, n))
+            rays = _cabi.make_rays(n, v[0], v[1], v[2], d[0], d[1], d[2], e, ref_index=ref, spec_wl=wl, spectra=spectra)
+        else:
+            rays = _cabi.make_rays(n, v[0], v[1], v[2], d[0], d[1], d[2], e, ref_index=ref, wavelength=wl)
         _cabi.check(ctx.lib.trc_source_generate_x(ctx.handle, C.byref(self._bound_desc()),
                                                   C.byref(spec.desc()) if spec is not None else None, n, self._src_seed,
                                                   self._src_offset, C.byref(rays)))
@@ -92,6 +103,8 @@ class LazySourceBundle(RayBundle):
             self._cols['wavelengths'] = wl
         if ref is not None:
             self._cols['ref_index'] = ref
+        if carried:
+            self._cols['spectra'] = spectra
         for k, val in self._src_const.items():
             self._cols[k] = N.ones(n) * val
 

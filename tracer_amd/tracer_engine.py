@@ -383,7 +383,10 @@ class TracerEngine(object):
         self._warn_left(stats.rays_left, stats.energy_left, bundle)
         vertices, directions = N.vstack(last[0:3]), N.vstack(last[3:6])
         # "otherwise only register the last bundle" (tracer_engine.py:288-291): scripts read engine.tree[-1] after tree=False
-        self.tree.append(RayBundle(vertices=vertices, directions=directions, energy=N.asarray(last[6])))
+        if len(last) > 7:       # the rays of a source that carries its spectrum come back with theirs
+            self.tree.append(RayBundle(vertices=vertices, directions=directions, energy=N.asarray(last[6]), spectra=last[7], wavelengths=last[8]))
+        else:
+            self.tree.append(RayBundle(vertices=vertices, directions=directions, energy=N.asarray(last[6])))
         return vertices, directions
 
     # -- ordered engine -----------------------------------------------------------------------------
@@ -395,7 +398,8 @@ class TracerEngine(object):
             # (a source with a spectrum: level 0 carries the wavelengths drawn on the device, and the index the spectrum gives)
             has_ref = 'ref_index' in rays.columns
             has_wl = 'wavelengths' in rays.columns
-        n_spec = bundle.get_spectra().shape[0] if rays.polychromatic else 0
+        # (a pending source that carries its spectrum is not made for this: level 0 gets its (W, n) columns on the device)
+        n_spec = (rays.spectrum.wavelengths.size if call_plan.carried(rays) else bundle.get_spectra().shape[0]) if rays.polychromatic else 0
         cplx = scene.materials or rays.complex_index
         if n_spec:
             has_wl = False          # `wavelengths` is the (W, N) grid of the spectra
