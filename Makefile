@@ -12,7 +12,7 @@ CSRC := $(ROOT)tracer_amd/csrc
 SRCS := $(CSRC)/trc_kernels.hip $(CSRC)/trc_shade.hip
 OBJDIR := $(ROOT)build/obj
 OBJS := $(OBJDIR)/trc_kernels.o $(OBJDIR)/trc_shade.o
-HDR := $(CSRC)/trc_core.h $(CSRC)/trc_bounds.h $(CSRC)/trc_footprint.h $(CSRC)/trc_forms.h $(CSRC)/trc_device.h $(CSRC)/trc_stream.inc $(ROOT)include/tracer_amd.h
+HDR := $(CSRC)/trc_core.h $(CSRC)/trc_bounds.h $(CSRC)/trc_footprint.h $(CSRC)/trc_forms.h $(CSRC)/trc_device.h $(CSRC)/trc_stream.inc $(CSRC)/trc_mega.inc $(ROOT)include/tracer_amd.h
 
 HOSTCHECK := $(ROOT)tests/hostcheck/libtrc_hostcheck.so
 HOSTCHECK_SRC := $(ROOT)tests/hostcheck/hostcheck.cpp
@@ -20,6 +20,8 @@ SPECCHECK := $(ROOT)tests/hostcheck/libtrc_spectrum_check.so
 SPECCHECK_SRC := $(ROOT)tests/hostcheck/spectrum_check.cpp
 SUNCHECK := $(ROOT)tests/hostcheck/libtrc_sunshape_check.so
 SUNCHECK_SRC := $(ROOT)tests/hostcheck/sunshape_check.cpp
+LAMPCHECK := $(ROOT)tests/hostcheck/libtrc_lamp_check.so
+LAMPCHECK_SRC := $(ROOT)tests/hostcheck/lamp_check.cpp
 FMCHECK := $(ROOT)tests/hostcheck/libtrc_fluxmap_check.so
 FMCHECK_SRC := $(ROOT)tests/hostcheck/fluxmap_check.cpp
 
@@ -60,7 +62,7 @@ $(LIB): $(OBJS)
 MATCHECK := $(ROOT)tests/hostcheck/libtrc_material_check.so
 MATCHECK_SRC := $(ROOT)tests/hostcheck/material_check.cpp
 
-hostcheck: $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK)
+hostcheck: $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK)
 
 # the tabulated materials' lookup of the per-ray core, host-compiled for its tests
 $(MATCHECK): $(MATCHECK_SRC) $(HDR)
@@ -76,6 +78,10 @@ $(SPECCHECK): $(SPECCHECK_SRC) $(HDR)
 # the tabulated-sunshape sampler and sources of the per-ray core, host-compiled for their tests
 $(SUNCHECK): $(SUNCHECK_SRC) $(HDR)
 	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(SUNCHECK_SRC)
+
+# the arc-lamp sources of the per-ray core and the decisions for their kinds, host-compiled for their tests
+$(LAMPCHECK): $(LAMPCHECK_SRC) $(HDR)
+	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(LAMPCHECK_SRC)
 
 # the flux-map charts and bin index of the per-ray core, host-compiled for their tests
 $(FMCHECK): $(FMCHECK_SRC) $(HDR)
@@ -125,6 +131,6 @@ asm-shade: $(CSRC)/trc_shade.hip $(HDR)
 		-o $(ROOT)build/trc_shade.s $(CSRC)/trc_shade.hip 2> $(ROOT)build/trc_shade.resources.txt
 
 clean:
-	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK)
+	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK)
 
 .PHONY: all hostcheck umaskcheck umaskcheck-exe splitcheck polycheck asm asm-shade clean

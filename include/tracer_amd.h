@@ -193,8 +193,25 @@ typedef enum trc_source_kind {
        the last kind rather than by a literal: the oracle's kind table, which the header's literals are checked against, has no
        model of them.) */
     TRC_SRC_SUNSHAPE_DISK = TRC_SRC_VF_FRUSTUM + 1,  /* tabulated_sunshape sources.py:386-410, :412-464  p: radius ; table */
-    TRC_SRC_SUNSHAPE_RECT = TRC_SRC_VF_FRUSTUM + 2   /* rect_tabulated_sunshape sources.py:386-410, :466-515  p: width,height ; table */
+    TRC_SRC_SUNSHAPE_RECT = TRC_SRC_VF_FRUSTUM + 2,  /* rect_tabulated_sunshape sources.py:386-410, :466-515  p: width,height ; table */
+    /* arc-lamp sources (models/solar_simulator.py): rays leave a volume, or a curved surface about its local normal.  Three local
+       coordinates, as the wall emitters.  Draws of ray i, event 0: the four uniforms of block 0 (u0..u3), and for ARC_VOLUME the
+       first uniform of block 1 (u4).
+       ARC_VOLUME (SimulatorLampBader): a point in the cylinder volume z = u0 l - l/2, phi = 2 pi u1, r = R sqrt(u2); polar angle
+         about +z from the table `table` names (trc_angle_table_create) at u3, azimuth 2 pi u4.  p: R, l ; p[TRC_SUNSHAPE_P_N] is
+         written by the library.
+       EMIT_SPHERE (sampling.sphere_sampling): phi = 2 pi u0, cos(theta) = 2 u1 - 1, the point R n; direction in the cone of half
+         angle ang_range about sign n, azimuth 2 pi u2, law TRC_EMIT_LAMBERTIAN: sin(theta) = sin(ang_range) sqrt(u3),
+         TRC_EMIT_ISOTROPIC: cos(theta) = 1 - u3 (1 - cos(ang_range)); turned from +z to the normal by the minimal rotation
+         (vector_manipulations.rotate_z_to_normal).  p: R, ang_range, law, sign (+1 outwards, -1 inwards).
+       EMIT_CYLINDER (sampling.cylinder_sampling): z = u0 h - h/2, phi = 2 pi u1, the point (R cos phi, R sin phi, z); direction
+         as EMIT_SPHERE about sign (cos phi, sin phi, 0).  p: R, h, ang_range, law, sign. */
+    TRC_SRC_ARC_VOLUME = TRC_SRC_VF_FRUSTUM + 3,
+    TRC_SRC_EMIT_SPHERE = TRC_SRC_VF_FRUSTUM + 4,
+    TRC_SRC_EMIT_CYLINDER = TRC_SRC_VF_FRUSTUM + 5
 } trc_source_kind;
+#define TRC_EMIT_LAMBERTIAN 0
+#define TRC_EMIT_ISOTROPIC 1
 
 #define TRC_BUIE_NELEM 210  /* sources.py:338 */
 
@@ -207,7 +224,7 @@ typedef enum trc_source_kind {
  */
 typedef struct trc_source_desc {
     int32_t kind;
-    int32_t table;      /* TRC_SRC_SUNSHAPE_*: the id of a live trc_sunshape (trc_sunshape_id); 0 for every other kind */
+    int32_t table;      /* TRC_SRC_SUNSHAPE_*, TRC_SRC_ARC_VOLUME: the id of a live trc_sunshape (trc_sunshape_id); 0 for every other kind */
     double center[3];
     double rot_pos[9];  /* row-major local->global for start points */
     double rot_dir[9];  /* row-major local->global for directions   */
@@ -507,6 +524,14 @@ int trc_sunshape_create(trc_ctx *ctx, int32_t n, const double *angle, const doub
 int trc_sunshape_id(trc_sunshape *table, int32_t *id);
 int trc_sunshape_get(trc_sunshape *table, int32_t *n, double *packed, double *theta_c, double *u_c);
 int trc_sunshape_destroy(trc_sunshape *table);
+/*
+ * Polar table of an arc lamp (TRC_SRC_ARC_VOLUME): n points (2..TRC_SUNSHAPE_MAX_POINTS) of strictly increasing angles within
+ * [0, pi] and finite, non-negative densities of the polar angle itself -- taken as given, without a cos sin factor -- with a positive
+ * integral.  Packed as a source spectrum's table is (angle | density normalised to a unit trapezoid integral | its running integral,
+ * ending at exactly 1); the polar angle of a uniform u is the spectrum's sampler on it.  The object is a trc_sunshape: it shares the
+ * id space, and trc_sunshape_id / _get / _destroy serve it (get: theta_c = the last angle, u_c = 1).
+ */
+int trc_angle_table_create(trc_ctx *ctx, int32_t n, const double *angle, const double *density, trc_sunshape **out);
 
 /*
  * Start points of the first n rays of a disc / rectangle source (sources.py:175-515) in the source's own plane coordinates

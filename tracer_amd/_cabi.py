@@ -55,6 +55,8 @@ SRC_SUNSHAPE_DISK, SRC_SUNSHAPE_RECT = 7, 8       # tabulated sunshapes: the des
 SUNSHAPE_MAX_POINTS = 4096
 SUNSHAPE_CORE_TAIL = 0.01
 SUNSHAPE_P_THETA_C, SUNSHAPE_P_U_C, SUNSHAPE_P_N = 5, 6, 7
+SRC_ARC_VOLUME, SRC_EMIT_SPHERE, SRC_EMIT_CYLINDER = 9, 10, 11      # arc-lamp sources; ARC_VOLUME's `table` names a polar table
+EMIT_LAMBERTIAN, EMIT_ISOTROPIC = 0, 1                              # TRC_EMIT_*: the direction law of the emitters
 
 _p_f64 = C.POINTER(C.c_double)
 _p_i64 = C.POINTER(C.c_int64)
@@ -162,6 +164,7 @@ SIGNATURES = {
     'trc_sunshape_id': (C.c_int, [_vp, _p_i32]),
     'trc_sunshape_get': (C.c_int, [_vp, _p_i32, _p_f64, _p_f64, _p_f64]),
     'trc_sunshape_destroy': (C.c_int, [_vp]),
+    'trc_angle_table_create': (C.c_int, [_vp, C.c_int32, _p_f64, _p_f64, _pvp]),
     'trc_source_start32': (C.c_int, [_vp, C.POINTER(SourceDesc), C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), _p_f64]),
     'trc_gm_find_intersections': (C.c_int, [_vp, C.POINTER(SurfaceDesc), C.c_int32, _p_f64, C.POINTER(Rays), _p_f64,

@@ -13,7 +13,7 @@ _MODULES = ['assembly', 'object', 'surface', 'has_frame', 'geometry_manager', 'f
             'spatial_geometry', 'boundary_shape', 'accel_tree', 'polygon', 'tracer_engine_mp', 'models',
             'models.one_sided_mirror', 'models.heliostat_field', 'models.homogenizer', 'models.spherical_lens',
             'models.triangulated_surface', 'models.homogenized_local_receiver', 'models.tau_minidish', 'models.PETAL_dish',
-            'models.SG4']
+            'models.SG4', 'models.solar_simulator']
 
 
 def install(force=False):
@@ -55,4 +55,6 @@ def install(force=False):
     sys.modules.setdefault('ray_trace_utils.stl_utils', rtu.stl_utils)
     rtu.estimator = importlib.import_module('tracer_amd.estimator')
     sys.modules.setdefault('ray_trace_utils.estimator', rtu.estimator)
+    rtu.sampling = importlib.import_module('tracer_amd.sampling')
+    sys.modules.setdefault('ray_trace_utils.sampling', rtu.sampling)
     return root

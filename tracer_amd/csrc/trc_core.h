@@ -1866,6 +1866,114 @@ TRC_HD const double *trc_sunshape_table(const trc_source_desc *src) {
     return (const double *)(uintptr_t)__builtin_bit_cast(uint64_t, src->buie[0]);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Arc-lamp sources (TRC_SRC_ARC_VOLUME, TRC_SRC_EMIT_SPHERE, TRC_SRC_EMIT_CYLINDER; models/solar_simulator.py): rays from a
+// volume, or from a curved surface about its local normal.
+// ---------------------------------------------------------------------------------------------
+TRC_HD bool trc_src_kind_is_lamp(int k) { return k == TRC_SRC_ARC_VOLUME || k == TRC_SRC_EMIT_SPHERE || k == TRC_SRC_EMIT_CYLINDER; }
+
+// Host: packs a checked polar table (n >= 2 strictly increasing angles, finite non-negative densities) as a source spectrum is
+// packed -- tab[3n] = angle | density / integral | running trapezoid integral / integral, the last entry 1 exactly -- with the
+// density as given (no cos sin factor: the table is the density of the polar angle itself).  false: no (or no finite) mass.
+static inline bool trc_angle_table_pack(int n, const double *angle, const double *density, double *tab) {
+    double *w = tab, *v = tab + n, *c = tab + 2 * n;
+    double cum = 0.0;
+    for (int i = 0; i < n; ++i) {
+        w[i] = angle[i];
+        if (i > 0) cum += (angle[i] - angle[i - 1]) * (density[i] + density[i - 1]) / 2.;
+        c[i] = cum;
+    }
+    if (!(cum > 0.0) || !(cum < TRC_INF)) return false;
+    for (int i = 0; i < n; ++i) { v[i] = density[i] / cum; c[i] = c[i] / cum; }
+    return true;
+}
+
+// direction in the cone of half angle ang_range about +z: azimuth 2 pi ua; polar angle from up by the Lambertian law
+// (sampling.Lambertian_directions_sampling: sin(theta) = sin(ang_range) sqrt(up)) or uniform in solid angle
+// (isotropic_directions_sampling: cos(theta) = 1 - up (1 - cos(ang_range)))
+TRC_HD void trc_emit_dir_u(int law, double ua, double up, double ang_range, double *ax, double *ay, double *az) {
+    if (law != TRC_EMIT_ISOTROPIC) { trc_pillbox_dir_u(ua, up, ang_range, ax, ay, az); return; }
+    const double c = 1.0 - up * (1.0 - cos(ang_range));
+    const double s = sqrt((1.0 - c) * (1.0 + c));
+    double sa, ca;
+    trc_sincos_2pi(ua, &sa, &ca);
+    *ax = ca * s; *ay = sa * s; *az = c;
+}
+
+// A lamp ray in the source's own frame from its uniforms: the point l, the direction a.  tab: the packed polar table of
+// ARC_VOLUME (n_tab points), unused by the emitters.  The draws in the order the host samplers make theirs (sampling.py:
+// cylinder_sampling's zs, ths, rs; PW_linear_distribution.sample; the azimuth -- sphere_sampling's phis, cosths and the
+// direction sampler's xi1, xi2).
+TRC_HD void trc_lamp_local_u(int kind, const double *p, const double *tab, int n_tab, double u0, double u1, double u2, double u3,
+                             double u4, double *lx, double *ly, double *lz, double *ax, double *ay, double *az) {
+    if (kind == TRC_SRC_ARC_VOLUME) {
+        *lz = u0 * p[1] - p[1] / 2.0;
+        double sp, cp, st, ct, sa, ca;
+        trc_sincos_2pi(u1, &sp, &cp);
+        const double r = sqrt(u2) * p[0];
+        *lx = r * cp; *ly = r * sp;
+        const double th = trc_spectrum_sample(tab, tab + n_tab, tab + 2 * n_tab, n_tab, u3);
+        trc_sincos(th, &st, &ct);
+        trc_sincos_2pi(u4, &sa, &ca);
+        *ax = st * ca; *ay = st * sa; *az = ct;
+        return;
+    }
+    double nx, ny, nz, fx, fy, fz, ang, sign;
+    int law;
+    if (kind == TRC_SRC_EMIT_SPHERE) {
+        double sp, cp;
+        trc_sincos_2pi(u0, &sp, &cp);
+        const double c = 2.0 * u1 - 1.0;
+        const double s = sqrt(1.0 - c * c);
+        nx = s * cp; ny = s * sp; nz = c;
+        *lx = p[0] * nx; *ly = p[0] * ny; *lz = p[0] * nz;
+        ang = p[1]; law = (int)p[2]; sign = p[3];
+    } else {                                // TRC_SRC_EMIT_CYLINDER
+        *lz = u0 * p[1] - p[1] / 2.0;
+        double sp, cp;
+        trc_sincos_2pi(u1, &sp, &cp);
+        nx = cp; ny = sp; nz = 0.0;
+        *lx = p[0] * cp; *ly = p[0] * sp;
+        ang = p[2]; law = (int)p[3]; sign = p[4];
+    }
+    trc_emit_dir_u(law, u2, u3, ang, &fx, &fy, &fz);
+    trc_rotate_z_to_normal(fx, fy, fz, sign * nx, sign * ny, sign * nz, ax, ay, az);
+}
+
+// local point and direction into the global frame: three local coordinates, as the wall emitters
+TRC_HD void trc_lamp_pose(const trc_source_desc *src, double lx, double ly, double lz, double ax, double ay, double az,
+                          double *px, double *py, double *pz, double *dx, double *dy, double *dz) {
+    const double *rp = src->rot_pos, *rd = src->rot_dir;
+    *px = rp[0] * lx + rp[1] * ly + rp[2] * lz + src->center[0];
+    *py = rp[3] * lx + rp[4] * ly + rp[5] * lz + src->center[1];
+    *pz = rp[6] * lx + rp[7] * ly + rp[8] * lz + src->center[2];
+    *dx = rd[0] * ax + rd[1] * ay + rd[2] * az;
+    *dy = rd[3] * ax + rd[4] * ay + rd[5] * az;
+    *dz = rd[6] * ax + rd[7] * ay + rd[8] * az;
+}
+
+// Ray `rid` of a lamp descriptor: event 0, the four uniforms of block 0 and -- ARC_VOLUME only -- the first of block 1 (no other
+// source draws from block 1: the x_cut redraws use blocks 2..4097, the spectrum block 0xFFFFFFFF).  KIND >= 0 promises
+// src->kind == KIND.
+template <int KIND>
+TRC_HD void trc_lamp_ray_t(const trc_source_desc *src, uint64_t seed, uint64_t rid, double *px, double *py, double *pz, double *dx,
+                           double *dy, double *dz) {
+    const int kind = KIND >= 0 ? KIND : src->kind;
+    double u0, u1, u2, u3, u4 = 0.0;
+    trc_uniform_quad(seed, rid, 0, 0, &u0, &u1, &u2, &u3);
+    const double *tab = nullptr;
+    int n_tab = 0;
+    if (kind == TRC_SRC_ARC_VOLUME) {
+        double v1, v2, v3;
+        trc_uniform_quad(seed, rid, 0, 1, &u4, &v1, &v2, &v3);
+        tab = trc_sunshape_table(src);
+        n_tab = (int)src->p[TRC_SUNSHAPE_P_N];
+    }
+    double lx, ly, lz, ax, ay, az;
+    trc_lamp_local_u(kind, src->p, tab, n_tab, u0, u1, u2, u3, u4, &lx, &ly, &lz, &ax, &ay, &az);
+    trc_lamp_pose(src, lx, ly, lz, ax, ay, az, px, py, pz, dx, dy, dz);
+}
+
 // buie: the table of the descriptor (or its LDS copy); aur: trc_buie_aureole_consts of it, or null; bf: the
 // trc_buie_fast form of the table when the caller has staged one (then buie and aur are not read).
 // KIND >= 0 promises src->kind == KIND (the streaming engine compiles the Buie disc on its own: 158 instead of 237
@@ -1875,6 +1983,12 @@ template <int KIND, bool SUN = false>
 TRC_HD void trc_source_ray_t(const trc_source_desc *src, const double *buie, const double *aur, uint64_t seed, uint64_t rid,
                              double *px, double *py, double *pz, double *dx, double *dy, double *dz,
                              const trc_buie_fast *bf = nullptr) {
+    // (the lamp kinds: compiled in only where the kind is promised -- the instances for any kind stay those that existed before
+    // them, and the host never hands them a lamp)
+    if constexpr (KIND == TRC_SRC_ARC_VOLUME || KIND == TRC_SRC_EMIT_SPHERE || KIND == TRC_SRC_EMIT_CYLINDER) {
+        trc_lamp_ray_t<KIND>(src, seed, rid, px, py, pz, dx, dy, dz);
+        return;
+    }
     double u0, u1, u2, u3;
     trc_uniform_quad(seed, rid, 0, 0, &u0, &u1, &u2, &u3);      // event 0 = source generation
     double lx, ly, lz = 0.0, ax, ay, az;
@@ -1991,7 +2105,8 @@ TRC_HD void trc_source_ray_t(const trc_source_desc *src, const double *buie, con
 
 TRC_HD void trc_source_ray(const trc_source_desc *src, const double *buie, const double *aur, uint64_t seed, uint64_t rid,
                            double *px, double *py, double *pz, double *dx, double *dy, double *dz) {
-    trc_source_ray_t<-1, true>(src, buie, aur, seed, rid, px, py, pz, dx, dy, dz);
+    if (trc_src_kind_is_lamp(src->kind)) trc_lamp_ray_t<-1>(src, seed, rid, px, py, pz, dx, dy, dz);
+    else trc_source_ray_t<-1, true>(src, buie, aur, seed, rid, px, py, pz, dx, dy, dz);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -48,7 +48,7 @@ class Estimator(object):
             with N.errstate(divide='ignore', invalid='ignore'):
                 half = half / self.mean
         half = N.array(half, dtype=float, ndmin=1)
-        half[N.ravel(sd) == 0.] = 0.
+        half[N.reshape(sd, half.shape) == 0.] = 0.     # (of any shape: a Target's flux map is two-dimensional)
         return half.reshape(shape) if shape else half
 
 

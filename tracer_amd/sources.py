@@ -508,13 +508,16 @@ class SunshapeTable(object):
         self._lib = None
         self._id = 0
 
+    def _create(self, ctx, handle):
+        return ctx.lib.trc_sunshape_create(ctx.handle, self.angles.size, _cabi.ptr(self.angles), _cabi.ptr(self.intensity),
+                                           C.byref(handle))
+
     def table_id(self):
         """the id a descriptor names the device table by (trc_sunshape_create on the current device on first call)"""
         if self._handle is None:
             ctx = _cabi.get_context()
             h = C.c_void_p()
-            _cabi.check(ctx.lib.trc_sunshape_create(ctx.handle, self.angles.size, _cabi.ptr(self.angles),
-                                                    _cabi.ptr(self.intensity), C.byref(h)))
+            _cabi.check(self._create(ctx, h))
             i = C.c_int32()
             _cabi.check(ctx.lib.trc_sunshape_id(h, C.byref(i)))
             self._handle, self._lib, self._id = h, ctx.lib, int(i.value)
@@ -585,6 +588,143 @@ def rect_tabulated_sunshape(num_rays, center, direction, width, height, angles, 
     desc = _fill_source(_cabi.SRC_SUNSHAPE_RECT, center, rotation_to_z(direction), rotation_to_z(rays_direction),
                         [width, height], energy)
     return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum, table=table)
+
+
+# -- arc-lamp sources (models/solar_simulator.py): rays from a volume, or from a curved surface about its local normal ------------
+from .sampling import isotropic_directions_sampling     # noqa: E402,F401  (the reference's model imports it from here)
+
+_EMIT_LAWS = {'lambertian': _cabi.EMIT_LAMBERTIAN, 'isotropic': _cabi.EMIT_ISOTROPIC}
+
+
+def check_angle_table(thetas, density):
+    """The polar table of an arc lamp as two float64 arrays; ValueError unless it has 2..4096 points, finite angles strictly
+    increasing within [0, pi], finite non-negative densities and a positive integral (the checks of trc_angle_table_create)."""
+    a = N.ascontiguousarray(N.ravel(N.asarray(thetas, dtype=float)))
+    d = N.ascontiguousarray(N.ravel(N.asarray(density, dtype=float)))
+    if a.shape != d.shape:
+        raise ValueError("angle table: %d angles but %d densities" % (a.size, d.size))
+    if not 2 <= a.size <= _cabi.SUNSHAPE_MAX_POINTS:
+        raise ValueError("angle table: 2..%d points, got %d" % (_cabi.SUNSHAPE_MAX_POINTS, a.size))
+    if not N.all(N.isfinite(a)) or not N.all(a[1:] > a[:-1]):
+        raise ValueError("angle table: the angles must be finite and strictly increasing")
+    if not (a[0] >= 0. and a[-1] <= N.pi):
+        raise ValueError("angle table: the angles must lie in [0, pi]")
+    if not N.all(N.isfinite(d)) or N.any(d < 0.):
+        raise ValueError("angle table: the densities must be finite and non-negative")
+    mass = N.sum((a[1:] - a[:-1]) * (d[1:] + d[:-1]) / 2.)
+    if not (mass > 0. and N.isfinite(mass)):
+        raise ValueError("angle table: the table has no mass")
+    return a, d
+
+
+class AngleTable(SunshapeTable):
+    """A checked polar table of an arc lamp: the density of the polar angle over [0, pi], taken as given.  On the device it is a
+    table like a sunshape's (trc_angle_table_create: the same object, the same ids), packed as a source spectrum's."""
+    def __init__(self, thetas, density):
+        self.angles, self.intensity = check_angle_table(thetas, density)
+        self._handle = None
+        self._lib = None
+        self._id = 0
+
+    def _create(self, ctx, handle):
+        return ctx.lib.trc_angle_table_create(ctx.handle, self.angles.size, _cabi.ptr(self.angles), _cabi.ptr(self.intensity),
+                                              C.byref(handle))
+
+
+_angle_tables = {}
+
+
+def angle_table(thetas, density):
+    """the AngleTable of this content (cached like sunshape_table)"""
+    a, d = check_angle_table(thetas, density)
+    key = (a.tobytes(), d.tobytes())
+    t = _angle_tables.get(key)
+    if t is None:
+        if len(_angle_tables) > 64:
+            _angle_tables.clear()
+        t = _angle_tables[key] = AngleTable(a, d)
+    return t
+
+
+def _lamp_frame(direction, rotation):
+    """the rotation a lamp source is posed by: `rotation` (3, 3) as given, else the minimal rotation that takes +z to `direction`
+    (vector_manipulations.rotate_z_to_normal, as the lamps of the model pose their rays)"""
+    if rotation is not None:
+        rot = N.asarray(rotation, dtype=float)
+        if rot.shape != (3, 3):
+            raise ValueError("rotation must be a 3 x 3 matrix")
+        return rot
+    from .vector_manipulations import rotate_z_to_normal
+    d = N.ravel(N.asarray(direction, dtype=float))
+    return rotate_z_to_normal(N.eye(3), d / N.sqrt(N.sum(d ** 2)))
+
+
+def _lamp_checks(what, num_rays, power, **lengths):
+    if int(num_rays) < 0:
+        raise ValueError("%s: num_rays must not be negative" % what)
+    for name, val in lengths.items():
+        if not (N.isfinite(val) and val > 0.):
+            raise ValueError("%s: %s must be positive and finite, got %r" % (what, name, val))
+    if not N.isfinite(power):
+        raise ValueError("%s: power must be finite" % what)
+
+
+def arc_volume_bundle(num_rays, r_c, l_c, thetas, density, center, direction, power, seed=None, ray_offset=0, spectrum=None,
+                      rotation=None):
+    """
+    The arc of a lamp as a cylinder volume of radius r_c and length l_c about `direction`, centred on `center` (a 3x1 column): start
+    points uniform in the volume, polar angles about `direction` drawn on the device from the tabulated density (thetas within
+    [0, pi], density of the polar angle itself, linear between the points), azimuths uniform.  Each ray carries power / num_rays.
+    What SimulatorLampBader.generate_rays samples on the host (solar_simulator.py:237-258), drawn per ray from its Philox stream:
+    event 0, block 0 for the height, the azimuth and the radius of the point and for the polar angle; the first uniform of block 1
+    for the azimuth of the direction.  rotation: the (3, 3) pose in place of the minimal rotation of +z to `direction`.
+    """
+    r_c, l_c = float(r_c), float(l_c)
+    _lamp_checks('arc_volume_bundle', num_rays, power, r_c=r_c, l_c=l_c)
+    table = angle_table(thetas, density)
+    rot = _lamp_frame(direction, rotation)
+    desc = _fill_source(_cabi.SRC_ARC_VOLUME, center, rot, rot, [r_c, l_c], float(power) / max(int(num_rays), 1))
+    return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum, table=table)
+
+
+def _emitter_params(what, ang_range, law, rays_in):
+    if law not in _EMIT_LAWS:
+        raise ValueError("%s: law must be 'lambertian' or 'isotropic', got %r" % (what, law))
+    ang_range = float(ang_range)
+    if not 0. <= ang_range <= N.pi / 2.:
+        raise ValueError("%s: ang_range must lie in [0, pi/2]" % what)
+    return [ang_range, float(_EMIT_LAWS[law]), -1. if rays_in else 1.]
+
+
+def sphere_emitter_bundle(num_rays, radius, center, direction, power, ang_range=N.pi / 2., law='lambertian', rays_in=False, seed=None,
+                          ray_offset=0, spectrum=None, rotation=None):
+    """
+    Rays leaving a sphere of `radius` centred on `center`, uniformly over its surface (sampling.sphere_sampling), each within
+    ang_range of the local normal -- outwards, or inwards with rays_in -- by the Lambertian law or uniformly in solid angle
+    (law='isotropic': isotropic_directions_sampling), turned from +z to the normal by the minimal rotation.  Each ray carries
+    power / num_rays.  Draws of a ray: event 0, block 0 -- azimuth and cosine of the point, azimuth and polar uniform of the direction.
+    """
+    radius = float(radius)
+    _lamp_checks('sphere_emitter_bundle', num_rays, power, radius=radius)
+    rot = _lamp_frame(direction, rotation)
+    desc = _fill_source(_cabi.SRC_EMIT_SPHERE, center, rot, rot, [radius] + _emitter_params('sphere_emitter_bundle', ang_range, law, rays_in),
+                        float(power) / max(int(num_rays), 1))
+    return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum)
+
+
+def cylinder_emitter_bundle(num_rays, radius, height, center, direction, power, ang_range=N.pi / 2., law='lambertian', rays_in=False,
+                            seed=None, ray_offset=0, spectrum=None, rotation=None):
+    """
+    Rays leaving the wall of a cylinder of `radius` and `height` about `direction`, centred on `center`, uniformly over the wall
+    (sampling.cylinder_sampling), each about the local normal as sphere_emitter_bundle's.  Draws of a ray: event 0, block 0 --
+    height and azimuth of the point, azimuth and polar uniform of the direction.
+    """
+    radius, height = float(radius), float(height)
+    _lamp_checks('cylinder_emitter_bundle', num_rays, power, radius=radius, height=height)
+    rot = _lamp_frame(direction, rotation)
+    desc = _fill_source(_cabi.SRC_EMIT_CYLINDER, center, rot, rot,
+                        [radius, height] + _emitter_params('cylinder_emitter_bundle', ang_range, law, rays_in), float(power) / max(int(num_rays), 1))
+    return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum)
 
 
 def single_ray_source(position, direction, flux=None):
