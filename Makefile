@@ -7,12 +7,13 @@ ARCH ?= gfx950
 
 LIB := $(ROOT)tracer_amd/lib/libtracer_amd.so
 CSRC := $(ROOT)tracer_amd/csrc
-# two translation units: the engines and the C-ABI (trc_kernels.hip, which includes trc_stream.inc), and the class-split shading
-# kernels of the streaming engine (trc_shade.hip).  `make -j2` compiles them side by side.
-SRCS := $(CSRC)/trc_kernels.hip $(CSRC)/trc_shade.hip
+# three translation units: the engines and the C-ABI (trc_kernels.hip, which includes trc_stream.inc), the class-split shading
+# kernels of the streaming engine (trc_shade.hip), and the histogram of captured hits (trc_hithist.hip).  `make -j2` compiles them
+# side by side.
+SRCS := $(CSRC)/trc_kernels.hip $(CSRC)/trc_shade.hip $(CSRC)/trc_hithist.hip
 OBJDIR := $(ROOT)build/obj
-OBJS := $(OBJDIR)/trc_kernels.o $(OBJDIR)/trc_shade.o
-HDR := $(CSRC)/trc_core.h $(CSRC)/trc_bounds.h $(CSRC)/trc_footprint.h $(CSRC)/trc_forms.h $(CSRC)/trc_device.h $(CSRC)/trc_stream.inc $(CSRC)/trc_mega.inc $(ROOT)include/tracer_amd.h
+OBJS := $(OBJDIR)/trc_kernels.o $(OBJDIR)/trc_shade.o $(OBJDIR)/trc_hithist.o
+HDR := $(CSRC)/trc_core.h $(CSRC)/trc_bounds.h $(CSRC)/trc_footprint.h $(CSRC)/trc_forms.h $(CSRC)/trc_device.h $(CSRC)/trc_stream.inc $(CSRC)/trc_mega.inc $(CSRC)/trc_hithist.h $(ROOT)include/tracer_amd.h
 
 HOSTCHECK := $(ROOT)tests/hostcheck/libtrc_hostcheck.so
 HOSTCHECK_SRC := $(ROOT)tests/hostcheck/hostcheck.cpp
@@ -24,6 +25,8 @@ LAMPCHECK := $(ROOT)tests/hostcheck/libtrc_lamp_check.so
 LAMPCHECK_SRC := $(ROOT)tests/hostcheck/lamp_check.cpp
 FMCHECK := $(ROOT)tests/hostcheck/libtrc_fluxmap_check.so
 FMCHECK_SRC := $(ROOT)tests/hostcheck/fluxmap_check.cpp
+HHCHECK := $(ROOT)tests/hostcheck/libtrc_hithist_check.so
+HHCHECK_SRC := $(ROOT)tests/hostcheck/hithist_check.cpp
 
 UMASKCHECK := $(ROOT)tests/umaskcheck/libtrc_umask_check.so
 UMASKCHECK_EXE := $(ROOT)tests/umaskcheck/umask_check
@@ -55,6 +58,10 @@ $(OBJDIR)/trc_kernels.o: $(CSRC)/trc_kernels.hip $(HDR)
 	mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(KERNELS_FLAGS) -c -o $@ $<
 
+$(OBJDIR)/trc_hithist.o: $(CSRC)/trc_hithist.hip $(HDR)
+	mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(KERNELS_FLAGS) -c -o $@ $<
+
 $(LIB): $(OBJS)
 	mkdir -p $(dir $(LIB))
 	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared -o $@ $(OBJS)
@@ -62,7 +69,7 @@ $(LIB): $(OBJS)
 MATCHECK := $(ROOT)tests/hostcheck/libtrc_material_check.so
 MATCHECK_SRC := $(ROOT)tests/hostcheck/material_check.cpp
 
-hostcheck: $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK)
+hostcheck: $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK) $(HHCHECK)
 
 # the tabulated materials' lookup of the per-ray core, host-compiled for its tests
 $(MATCHECK): $(MATCHECK_SRC) $(HDR)
@@ -86,6 +93,10 @@ $(LAMPCHECK): $(LAMPCHECK_SRC) $(HDR)
 # the flux-map charts and bin index of the per-ray core, host-compiled for their tests
 $(FMCHECK): $(FMCHECK_SRC) $(HDR)
 	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(FMCHECK_SRC)
+
+# the histogram of captured hits -- its per-hit function, its LDS decision and its pass as a host loop -- host-compiled for their tests
+$(HHCHECK): $(HHCHECK_SRC) $(HDR)
+	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(HHCHECK_SRC)
 
 # the footprint map's mask over the uniforms against brute force, host-compiled: a library for its test, and the same as a program
 # (umaskcheck-exe; SAN="-fsanitize=address,undefined" builds it for a sanitizer run)
@@ -120,7 +131,7 @@ $(POLYCHECK_EXE): $(POLYCHECK_SRC) $(HDR)
 # assembly listings with the registers, scratch and occupancy of every kernel (build/*.s, build/*.resources.txt)
 asm: $(SRCS) $(HDR)
 	mkdir -p $(ROOT)build
-	for f in trc_kernels trc_shade; do \
+	for f in trc_kernels trc_shade trc_hithist; do \
 		fl="$(KERNELS_FLAGS)"; [ $$f = trc_shade ] && fl="$(SHADE_FLAGS)"; \
 		$(HIPCC) $(HIPFLAGS) $$fl -S --cuda-device-only -Rpass-analysis=kernel-resource-usage \
 			-o $(ROOT)build/$$f.s $(CSRC)/$$f.hip 2> $(ROOT)build/$$f.resources.txt || exit 1; done
@@ -131,6 +142,6 @@ asm-shade: $(CSRC)/trc_shade.hip $(HDR)
 		-o $(ROOT)build/trc_shade.s $(CSRC)/trc_shade.hip 2> $(ROOT)build/trc_shade.resources.txt
 
 clean:
-	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK)
+	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK) $(HHCHECK)
 
 .PHONY: all hostcheck umaskcheck umaskcheck-exe splitcheck polycheck asm asm-shade clean

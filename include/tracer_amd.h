@@ -417,6 +417,34 @@ int trc_scene_eval_materials(trc_scene *scene, int64_t n, const double *wl, doub
 #define TRC_BIN_RADIUS_HALF_OPEN 0x10
 int trc_scene_bin_hits(trc_scene *scene, int32_t n_bins, const int32_t *surf_lo, const int32_t *surf_hi,
                        const double *ranges6, const int32_t *mode, double *out);
+/* A 2-D histogram of the captured hits where they lie, in one pass over the hit buffer (k_hist_hits): numpy.histogram2d of what
+   trc_scene_get_hits would return now, for the hits of the surfaces surf_lo..surf_hi (inclusive; they share proj12: the faces of a
+   mesh binned in the frame of their object), without the transfer of the hits.  chart: the coordinates (u, v) of a hit --
+     0..3  the charts of trc_fluxmap_chart, of the hit point taken through proj12
+     TRC_HH_DIR_COSINES (4)  u = dxl, v = dyl of the incident direction dl = rows 0..2 of proj12 applied to d (no translation)
+     TRC_HH_DIR_ANGLES (5)   u = arccos(|dzl| / |dl|), the angle to the local z axis in [0, pi/2]; v = arctan2(-dyl, -dxl), 2 pi added
+                             where it is negative: the azimuth the ray comes from
+   weight: the absorbed energy, the incident energy or 1 per hit.  u_edges[nu + 1], v_edges[nv + 1]: numpy's edges (the last bin closed
+   on the right, a NaN coordinate outside), finite and strictly increasing.  sum[nu * nv] (row-major u) takes the weights, sum_sq the
+   squared weights and count the hits of every bin; outside[2] the weight and the number of selected hits in no bin; sum_sq, count
+   and outside may be NULL.  The outputs are overwritten (an empty buffer gives zeros); the hit buffer, the tallies and the scene
+   stay as they are, and no flux map need be set.  TRC_ERR_INVALID: an unknown chart or weight, fewer than one bin either way,
+   bad edges, a range outside the scene or without a capturing surface, and a direction chart or the incident weight on a range
+   that holds a surface captured lean (TRC_SURF_CAPTURE_LEAN: neither was written). */
+typedef enum trc_hit_hist_chart { TRC_HH_DIR_COSINES = 4, TRC_HH_DIR_ANGLES = 5 } trc_hit_hist_chart;
+typedef enum trc_hit_hist_weight { TRC_HH_ABSORBED = 0, TRC_HH_INCIDENT = 1, TRC_HH_COUNT = 2 } trc_hit_hist_weight;
+typedef struct trc_hit_hist_desc {
+    int32_t surf_lo, surf_hi;
+    int32_t chart, weight;
+    int32_t nu, nv;
+    const double *u_edges, *v_edges;
+    const double *proj12;
+} trc_hit_hist_desc;
+int trc_scene_histogram_hits(trc_scene *scene, const trc_hit_hist_desc *desc, double *sum, double *sum_sq, int64_t *count,
+                             double *outside);
+/* milliseconds the kernel of the scene's last trc_scene_histogram_hits took on the device, between two events (0: it had no entry
+   to pass over) */
+int trc_scene_histogram_hits_ms(trc_scene *scene, double *ms);
 /* Surface-to-surface energy transfer of the fast engine: T[from][to] = energy carried by the segments that leave
    surface `from` (row n_surf = the source) and land on surface `to`, (n_surf+1) x n_surf, row-major.  It replaces
    the blocking / shading post-process of examples/Sandia_NSTTF_field example.py:229-290, which recovers the parent

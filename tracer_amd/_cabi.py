@@ -48,6 +48,11 @@ LEVEL_VOLUME = 0x40000000        # TRC_LEVEL_VOLUME: bit of a level's surf[] ent
 # enum trc_fluxmap_chart: the coordinates a flux map bins in (trc_scene_set_fluxmap_chart)
 FM_XY, FM_CYLINDER, FM_POLAR, FM_SPHERE = range(4)
 FM_CHARTS = {'xy': FM_XY, 'cylinder': FM_CYLINDER, 'polar': FM_POLAR, 'sphere': FM_SPHERE}
+# trc_scene_histogram_hits: those charts of the hit point and enum trc_hit_hist_chart, of the incident direction; enum trc_hit_hist_weight
+HH_DIR_COSINES, HH_DIR_ANGLES = 4, 5
+HH_CHARTS = dict(FM_CHARTS, dir_cosines=HH_DIR_COSINES, dir_angles=HH_DIR_ANGLES)
+HH_ABSORBED, HH_INCIDENT, HH_COUNT = range(3)
+HH_WEIGHTS = {'absorbed': HH_ABSORBED, 'incident': HH_INCIDENT, 'count': HH_COUNT}
 
 # enum trc_source_kind
 SRC_PILLBOX_DISK, SRC_PILLBOX_RECT, SRC_BUIE_DISK, SRC_BUIE_RECT, SRC_PILLBOX_TRIANGLE, SRC_VF_CYLINDER, SRC_VF_FRUSTUM = range(7)
@@ -102,6 +107,12 @@ class KdTreeDesc(C.Structure):
                 ('always_relevant', _p_i32), ('bounds', C.c_double * 6)]
 
 
+class HitHistDesc(C.Structure):
+    """trc_hit_hist_desc (filled by DeviceScene.histogram_hits, which keeps its arrays alive)"""
+    _fields_ = [('surf_lo', C.c_int32), ('surf_hi', C.c_int32), ('chart', C.c_int32), ('weight', C.c_int32),
+                ('nu', C.c_int32), ('nv', C.c_int32), ('u_edges', _p_f64), ('v_edges', _p_f64), ('proj12', _p_f64)]
+
+
 class TraceStats(C.Structure):
     _fields_ = [('segments', C.c_int64), ('hits', C.c_int64), ('rays_left', C.c_int64),
                 ('hits_dropped', C.c_int64), ('energy_left', C.c_double), ('kernel_ms', C.c_double),
@@ -139,6 +150,8 @@ SIGNATURES = {
     'trc_scene_set_materials': (C.c_int, [_vp, C.c_int32, _p_i32, _p_f64]),
     'trc_scene_eval_materials': (C.c_int, [_vp, C.c_int64, _p_f64, _p_f64]),
     'trc_scene_bin_hits': (C.c_int, [_vp, C.c_int32, _p_i32, _p_i32, _p_f64, _p_i32, _p_f64]),
+    'trc_scene_histogram_hits': (C.c_int, [_vp, C.POINTER(HitHistDesc), _p_f64, _p_f64, _p_i64, _p_f64]),
+    'trc_scene_histogram_hits_ms': (C.c_int, [_vp, _p_f64]),
     'trc_scene_enable_transfer': (C.c_int, [_vp, C.c_int32]),
     'trc_scene_get_transfer': (C.c_int, [_vp, _p_f64]),
     'trc_scene_tally_size': (C.c_int, [_vp, _p_i64]),

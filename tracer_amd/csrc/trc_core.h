@@ -2191,4 +2191,26 @@ TRC_HD void trc_fluxmap_uv(int chart, const double *proj, double hx, double hy, 
     else *u = acos(zl / sqrt((xl * xl + yl * yl) + zl * zl));
 }
 
+// The coordinates a histogram of captured hits bins a hit in (trc_scene_histogram_hits): charts 0..3 are the flux maps' of the hit
+// point p; the other two are of the incident direction d in the surface's frame, dl = the three rows of proj applied to d without
+// the translation column.
+//   TRC_HH_DIR_COSINES  (dxl, dyl)
+//   TRC_HH_DIR_ANGLES   (the angle to the local z axis in [0, pi/2], whichever side the ray comes from; the azimuth it comes from,
+//                       atan2(-dyl, -dxl), 2.*pi added where it is negative)
+// Products and sums in the written order here too.  A direction along the axis has the azimuth atan2(-+0, -+0): +-0 or pi.
+#define TRC_HH_CHARTS 6     /* the four flux-map charts and trc_hit_hist_chart (tracer_amd.h) */
+#define TRC_HH_IS_DIR(chart) ((chart) >= TRC_HH_DIR_COSINES)
+TRC_HD void trc_hit_hist_uv(int chart, const double *proj, double px, double py, double pz, double dx, double dy, double dz, double *u,
+                            double *v) {
+    if (!TRC_HH_IS_DIR(chart)) { trc_fluxmap_uv(chart, proj, px, py, pz, u, v); return; }
+    const double dxl = proj[0] * dx + proj[1] * dy + proj[2] * dz;
+    const double dyl = proj[4] * dx + proj[5] * dy + proj[6] * dz;
+    if (chart == TRC_HH_DIR_COSINES) { *u = dxl; *v = dyl; return; }
+    const double dzl = proj[8] * dx + proj[9] * dy + proj[10] * dz;
+    double phi = atan2(-dyl, -dxl);
+    if (phi < 0.0) phi += TRC_TWO_PI;
+    *u = acos(fabs(dzl) / sqrt((dxl * dxl + dyl * dyl) + dzl * dzl));
+    *v = phi;
+}
+
 #endif  // TRC_CORE_H

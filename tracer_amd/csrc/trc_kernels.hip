@@ -35,6 +35,7 @@
 #include "trc_bounds.h"
 #include "trc_footprint.h"
 #include "trc_device.h"
+#include "trc_hithist.h"
 
 // ================================================================================================
 // error handling
@@ -502,6 +503,7 @@ struct trc_scene {
     DevBuf<double> d_last_x;          // ... and the spectra of the rays a source that carries its spectrum leaves (W rows, d_last_x_len doubles)
     size_t d_last_x_len = 0;
     HitBuffer hits;
+    double hist_ms = 0.0;             // device time of the last k_hist_hits (trc_scene_histogram_hits_ms)
 };
 
 // what rays of the ordered engine carry beyond the nine columns: rows of one matrix `pay` (row r of ray i at pay[r * n + i]):
@@ -2031,7 +2033,95 @@ extern "C" int trc_scene_bin_hits(trc_scene *sc, int32_t n_bins, const int32_t *
     return st;
 }
 
-#define TRC_TRANSFER_MAX_SURF 1024      /* (S+1) x S doubles, kept in every private copy of the tally buffer too */
+// The captured hits binned where they lie (k_hist_hits, trc_hithist.hip): edges up, one pass over the reserved entries, planes down.
+#define TRC_HH_MAX_BINS (1ll << 27)      /* bins of a plane: 1 GiB of float64 */
+extern "C" int trc_scene_histogram_hits(trc_scene *sc, const trc_hit_hist_desc *d, double *sum, double *sum_sq, int64_t *count, double *outside) {
+    if (!sc || !d || !sum || !d->u_edges || !d->v_edges || !d->proj12) return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: bad arguments");
+    if (d->chart < 0 || d->chart >= TRC_HH_CHARTS) return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: unknown chart %d", d->chart);
+    if (d->weight != TRC_HH_ABSORBED && d->weight != TRC_HH_INCIDENT && d->weight != TRC_HH_COUNT)
+        return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: unknown weight %d", d->weight);
+    if (d->nu < 1 || d->nv < 1) return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: a histogram has at least one bin either way (%d x %d)", d->nu, d->nv);
+    if ((long long)d->nu * d->nv > TRC_HH_MAX_BINS)
+        return trc_fail(TRC_ERR_CAPACITY, "trc_scene_histogram_hits: %d x %d bins (at most %lld)", d->nu, d->nv, (long long)TRC_HH_MAX_BINS);
+    for (int ax = 0; ax < 2; ++ax) {
+        const double *e = ax ? d->v_edges : d->u_edges;
+        const int n = ax ? d->nv : d->nu;
+        for (int k = 0; k <= n; ++k)
+            if (!std::isfinite(e[k]) || (k > 0 && !(e[k] > e[k - 1])))
+                return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: the %s edges must be finite and increase strictly", ax ? "v" : "u");
+    }
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(d->proj12[k])) return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: proj12 holds a value that is not finite");
+    if (d->surf_lo < 0 || d->surf_hi >= sc->n_surf || d->surf_lo > d->surf_hi)
+        return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: surfaces %d..%d are not a range of the scene's %d", d->surf_lo, d->surf_hi, sc->n_surf);
+    const bool full = TRC_HH_IS_DIR(d->chart) || d->weight == TRC_HH_INCIDENT;
+    bool captures = false;
+    for (int s = d->surf_lo; s <= d->surf_hi; ++s) {
+        const int32_t fl = sc->surfs[s].flags;
+        if (!(fl & TRC_SURF_CAPTURE_HITS)) continue;
+        captures = true;
+        if (full && (fl & TRC_SURF_CAPTURE_LEAN))
+            return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: surface %d is captured lean (TRC_SURF_CAPTURE_LEAN): the direction and the "
+                            "incident energy of its hits were not written", s);
+    }
+    if (!captures) return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: none of the surfaces %d..%d captures its hits", d->surf_lo, d->surf_hi);
+
+    trc_ctx *ctx = sc->ctx;
+    unsigned long long cursor;
+    TRC_TRY(scene_hit_cursor(sc, &cursor));
+    const HitBuffer &hb = sc->hits;
+    const size_t nb = (size_t)d->nu * d->nv, ne = (size_t)d->nu + d->nv + 2;
+    for (size_t k = 0; k < nb; ++k) { sum[k] = 0.0; if (sum_sq) sum_sq[k] = 0.0; if (count) count[k] = 0; }
+    if (outside) outside[0] = outside[1] = 0.0;
+    sc->hist_ms = 0.0;
+    trc_hit_hist_args A;
+    memset(&A, 0, sizeof(A));
+    A.n = hb.used(cursor);
+    if (A.n == 0) return TRC_OK;
+    A.planes = (sum_sq ? TRC_HH_PLANE_SUM_SQ : 0) | (count ? TRC_HH_PLANE_COUNT : 0);
+    // one block: [edges] [sum] [sum_sq] [count] [outside]
+    const size_t np = (size_t)trc_hit_hist_n_planes(A.planes), words = ne + nb * np + 2;
+    DevBuf<double> d_buf;
+    TRC_TRY(d_buf.alloc(words));
+    std::vector<double> edges(ne);
+    std::copy(d->u_edges, d->u_edges + d->nu + 1, edges.begin());
+    std::copy(d->v_edges, d->v_edges + d->nv + 1, edges.begin() + d->nu + 1);
+    A.surf = hb.surf.get();
+    A.e_abs = hb.col[0].get(); A.e_in = hb.col[1].get(); A.px = hb.col[2].get(); A.py = hb.col[3].get(); A.pz = hb.col[4].get();
+    A.dx = hb.col[5].get(); A.dy = hb.col[6].get(); A.dz = hb.col[7].get();
+    A.surf_lo = d->surf_lo; A.surf_hi = d->surf_hi; A.chart = d->chart; A.weight = d->weight; A.nu = d->nu; A.nv = d->nv;
+    for (int k = 0; k < 12; ++k) A.proj[k] = d->proj12[k];
+    A.edges = d_buf.get();
+    A.sum = d_buf.get() + ne;
+    A.sum_sq = sum_sq ? A.sum + nb : nullptr;
+    A.count = count ? (unsigned long long *)(A.sum + nb * (sum_sq ? 2 : 1)) : nullptr;
+    A.outside = A.sum + nb * np;
+    std::vector<double> back(nb * np + 2);
+    hipError_t e = hipMemcpyAsync(d_buf.get(), edges.data(), ne * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(A.sum, 0, (nb * np + 2) * 8, ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
+    if (e == hipSuccess) e = trc_hit_hist_launch(ctx->stream, ctx->n_cu, A);
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(back.data(), A.sum, back.size() * 8, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t se = hipStreamSynchronize(ctx->stream);      // (always: nothing queued may outlive the buffers it uses)
+    if (e == hipSuccess) e = se;
+    if (e != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "trc_scene_histogram_hits: %s", hipGetErrorString(e));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) sc->hist_ms = ms;
+    memcpy(sum, back.data(), nb * 8);
+    if (sum_sq) memcpy(sum_sq, back.data() + nb, nb * 8);
+    if (count) memcpy(count, back.data() + nb * (sum_sq ? 2 : 1), nb * 8);
+    if (outside) { outside[0] = back[nb * np]; outside[1] = back[nb * np + 1]; }
+    return TRC_OK;
+}
+
+extern "C" int trc_scene_histogram_hits_ms(trc_scene *sc, double *ms) {
+    if (!sc || !ms) return trc_fail(TRC_ERR_INVALID, "bad arguments");
+    *ms = sc->hist_ms;
+    return TRC_OK;
+}
+
+#define TRC_TRANSFER_MAX_SURF 1024     /* (S+1) x S doubles, kept in every private copy of the tally buffer too */
 extern "C" int trc_scene_enable_transfer(trc_scene *sc, int32_t on) {
     if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
     if (on && sc->n_surf > TRC_TRANSFER_MAX_SURF)

@@ -48,12 +48,19 @@ class HomogenizedLocalReceiver(Assembly):
     def get_main_reflector(self):
         return self._mr
 
-    def histogram_hits(self, bins=50):
+    def histogram_hits(self, bins=50, engine=None):
         """
         Energy absorbed on the plate during the traces run so far, binned over the plate: (H, x edges, y edges) in the
         convention of numpy.histogram2d, x along the first axis of H, `bins` cells each way.
+
+        engine: the TracerEngine that traced this assembly with tree=False.  The same triple then comes from the hits its
+        device still holds (TracerEngine.histogram_hits: the calls since its hit buffer was last emptied), binned where
+        they lie: the plate's accountants are not read and no hit is fetched.
         """
         plate, = self._rec.get_surfaces()
+        if engine is not None:
+            edges = [N.linspace(-side / 2., side / 2., bins + 1) for side in self._sides]        # (histogram2d's own for a range)
+            return engine.histogram_hits(plate, edges[0], edges[1]), edges[0], edges[1]
         absorbed, where = plate.get_optics_manager().get_all_hits()[:2]
         local = plate.global_to_local(where)
         extent = [(-side / 2., side / 2.) for side in self._sides]

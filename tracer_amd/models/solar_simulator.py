@@ -11,7 +11,9 @@ with tree=False; tallies and flux maps accumulate on the device, and each Target
 Where the reference's text cannot run as written it is built as it documents itself: the `homegenizer`
 argument is `homogenizer`; the Zhu lamp takes the normals of its surfaces (the text unpacks them from calls made without
 normals=True) and directions from isotropic_directions_sampling's law; Estimator.update gets the batch's ray count; a lamp's
-theta_CDF is a path or an (N, 2) array; a Target ends the rays it maps, since a device flux map bins absorbed energy.
+theta_CDF is a path or an (N, 2) array; a Target ends the rays it maps, since a device flux map bins absorbed energy -- unless it
+is made with transmitting=True, the reference's TransparentTransmitter plate, whose map per batch is TracerEngine.histogram_hits of
+the incident energy (section 14.15).
 """
 import os
 from copy import copy
@@ -42,17 +44,20 @@ def rotation_z_to(normal):
 
 
 class Target(AssembledObject):
-    def __init__(self, width, height, location, normal, binx, biny):
+    def __init__(self, width, height, location, normal, binx, biny, transmitting=False):
         """
         A plate for flux mapping whose map is an Estimator: a running mean over the batches with a confidence interval per bin.
         location, normal: position and surface normal of the plate; binx, biny: the bin edges of its local x and y (numpy
         histogram edges), which also size the plate, as in the reference (width and height are kept for the signature).
-        The plate absorbs what it maps.
+        The plate absorbs what it maps; with transmitting=True it is the reference's TransparentTransmitter: a virtual plane
+        whose map is of the energy that arrives, and the rays go on behind it (an aperture plane, a target in front of a
+        homogenizer).
         """
         binx, biny = N.asarray(binx, dtype=float), N.asarray(biny, dtype=float)
         geom = RectPlateGM(binx[-1] - binx[0], biny[-1] - biny[0])
-        AssembledObject.__init__(self, surfs=[Surface(geometry=geom, optics=Reflective(1.))], location=location,
-                                 rotation=rotation_z_to(normal))
+        self.transmitting = bool(transmitting)
+        AssembledObject.__init__(self, surfs=[Surface(geometry=geom, optics=TransparentTransmitter() if self.transmitting else Reflective(1.))],
+                                 location=location, rotation=rotation_z_to(normal))
         self.binx, self.biny = binx, biny
         self.areas = N.vstack(binx[1:] - binx[:-1]) * (biny[1:] - biny[:-1])
         self.fluxmap = Estimator()
@@ -60,6 +65,14 @@ class Target(AssembledObject):
 
     def evaluate_fluxmap(self, engine, num_samples):
         """the power the plate took since the last call, per bin area, into the estimator (weight: the batch's ray count)"""
+        if self.transmitting:
+            # nothing is absorbed, so no device flux map: the incident energy of the batch's hits, binned where they lie on the
+            # device; the optics are reset as the reference's evaluate_fluxmap resets them, and the next batch starts an empty buffer
+            surf = self.get_surfaces()[0]
+            batch = engine.histogram_hits(surf, self.binx, self.biny, weight='incident')
+            surf.get_optics_manager().reset()
+            self.fluxmap.update(batch / self.areas, num_samples=num_samples)
+            return self.fluxmap
         total = N.asarray(engine.get_fluxmap(self.get_surfaces()[0]), dtype=float)
         batch = total if self._powermap is None else total - self._powermap
         self._powermap = total
@@ -229,7 +242,10 @@ class SolarSimulator(Assembly):
         engine = self.engine = TracerEngine(self)
         for t in self.targets:
             t._powermap = None
-            engine.set_fluxmap(t.get_surfaces()[0], t.binx, t.biny)
+            if t.transmitting:      # (its batch map comes from the hits themselves: Target.evaluate_fluxmap)
+                t.get_surfaces()[0].get_optics_manager().reset()
+            else:
+                engine.set_fluxmap(t.get_surfaces()[0], t.binx, t.biny)
         call = 0
         for i in range(int(nrays / ray_batch)):
             for m in self.modules:

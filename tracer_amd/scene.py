@@ -251,6 +251,13 @@ def compile_scene(assembly_or_surfaces):
     return CompiledScene(surfaces)
 
 
+class HitHistogram(object):
+    """What histogram_hits(moments=True) returns: per bin the sum of the weights, of their squares and the number of hits, (nu, nv)
+    each, and `outside` = (weight, number) of the selected hits in no bin."""
+    def __init__(self, total, sum_sq, count, outside):
+        self.sum, self.sum_sq, self.count, self.outside = total, sum_sq, count, outside
+
+
 class DeviceScene(object):
     """trc_scene handle."""
     def __init__(self, compiled, ctx=None):
@@ -484,6 +491,51 @@ class DeviceScene(object):
         _cabi.check(self.lib.trc_scene_bin_hits(self.handle, n, lo.ctypes.data_as(i32), hi.ctypes.data_as(i32), _cabi.ptr(rng),
                                                 md.ctypes.data_as(i32), _cabi.ptr(out)))
         return out
+
+    def histogram_hits(self, surf_lo, surf_hi, u_edges, v_edges, proj=None, chart='xy', weight='absorbed', moments=False):
+        """
+        numpy.histogram2d of what get_hits() would return now, for the hits of the surfaces surf_lo..surf_hi (inclusive), binned
+        on the device where they lie (trc_scene_histogram_hits): no hit crosses the link, the buffer stays as it is and no flux
+        map need be set.  chart: 'xy', 'cylinder', 'polar', 'sphere' of the hit point as in set_fluxmap, 'dir_cosines' (the local
+        x and y of the incident direction) or 'dir_angles' (its angle to the local z axis in [0, pi/2], and the azimuth it comes
+        from, arctan2(-dy, -dx) in [0, 2 pi]), or a number (_cabi.HH_CHARTS).  weight: 'absorbed', 'incident' or 'count'.  proj
+        defaults to round(inv(frame), 9) of surface surf_lo.  Returns the (nu, nv) array, or with moments a HitHistogram (sum,
+        sum_sq, count, outside = weight and number of the selected hits in no bin).  A surface captured lean has neither
+        directions nor incident energies: ValueError.
+        """
+        u = _cabi.f64(u_edges)
+        v = _cabi.f64(v_edges)
+        if u.ndim != 1 or v.ndim != 1 or len(u) < 2 or len(v) < 2:
+            raise ValueError("histogram_hits: at least two edges either way")
+        if isinstance(chart, str):
+            if chart not in _cabi.HH_CHARTS:
+                raise ValueError("unknown histogram chart %r (one of %s)" % (chart, sorted(_cabi.HH_CHARTS)))
+            chart = _cabi.HH_CHARTS[chart]
+        if isinstance(weight, str):
+            if weight not in _cabi.HH_WEIGHTS:
+                raise ValueError("unknown histogram weight %r (one of %s)" % (weight, sorted(_cabi.HH_WEIGHTS)))
+            weight = _cabi.HH_WEIGHTS[weight]
+        surf_lo, surf_hi = int(surf_lo), int(surf_hi)
+        if proj is None:
+            if not 0 <= surf_lo < self.n_surf:
+                raise ValueError("histogram_hits: surface %d is not one of the scene's %d" % (surf_lo, self.n_surf))
+            proj = N.round(N.linalg.inv(self.compiled.surfaces[surf_lo]._temp_frame), decimals=9)
+        p = _cabi.f64(N.asarray(proj)[:3].ravel())
+        d = _cabi.HitHistDesc(surf_lo, surf_hi, int(chart), int(weight), len(u) - 1, len(v) - 1, _cabi.ptr(u), _cabi.ptr(v), _cabi.ptr(p))
+        shape = (len(u) - 1, len(v) - 1)
+        total = N.empty(shape)
+        sq = N.empty(shape) if moments else None
+        cnt = N.empty(shape, dtype=N.int64) if moments else None
+        outside = N.empty(2) if moments else None
+        _cabi.check(self.lib.trc_scene_histogram_hits(self.handle, C.byref(d), _cabi.ptr(total), _cabi.ptr(sq),
+                                                      _cabi.ptr(cnt, C.POINTER(C.c_int64)), _cabi.ptr(outside)))
+        return HitHistogram(total, sq, cnt, outside) if moments else total
+
+    def histogram_hits_ms(self):
+        """milliseconds the kernel of the last histogram_hits took on the device"""
+        ms = C.c_double(0.)
+        _cabi.check(self.lib.trc_scene_histogram_hits_ms(self.handle, C.byref(ms)))
+        return ms.value
 
     def enable_transfer(self, on=True):
         """keep (or drop) the surface-to-surface transfer matrix of the fast engine; resets the tallies"""

@@ -178,6 +178,37 @@ class TracerEngine(object):
         binned on the device (DeviceScene.bin_hits; the view-factor allocation of emissive_losses)"""
         return self._dev.bin_hits(surf_lo, surf_hi, ranges, mode)
 
+    def histogram_hits(self, surface, u_edges, v_edges, chart='xy', weight='absorbed', swap_xy=False, moments=False):
+        """
+        A histogram of the captured hits of `surface`, binned on the device after the trace: the result is numpy.histogram2d of
+        what DeviceScene.get_hits() would return at this moment -- the hits captured by fast-engine calls (ray_tracer(tree=False))
+        and not yet cleared, those of several calls when the buffer kept them -- taken to the chart's coordinates through
+        round(inv(frame), 9) of the surface.  Nothing has to be declared before the trace, no hit crosses the link, and the hits,
+        the tallies and the flux maps stay as they are: any number of maps of the same hits may be asked for.
+
+        surface: a Surface of the assembly, its index, or an (lo, hi) pair of indices -- the hits of surfaces lo..hi binned together
+        in the frame of surface lo (the faces of a mesh in the frame of their object).
+        chart: 'xy', 'cylinder', 'polar' or 'sphere' of the hit point, as in set_fluxmap; 'dir_cosines' -- the local x and y
+        components of the incident direction; 'dir_angles' -- its angle to the local z axis in [0, pi/2] and the azimuth it
+        comes from, arctan2(-dy, -dx) in [0, 2 pi].  swap_xy: the local x and y exchanged first, as in set_fluxmap.
+        weight: 'absorbed' or 'incident' energy, or 'count'.  A surface whose accountants keep only absorbed energies and hit
+        points (the Receiver family) has neither directions nor incident energies on the device: ValueError.
+
+        Returns the (nu, nv) array; with moments=True an object with sum, sum_sq, count (per bin) and outside = (weight, number)
+        of the hits of the surface in no bin.  Raises ValueError when no device scene exists yet (nothing was traced).
+        """
+        if self._dev is None or self._dev.handle is None:
+            raise ValueError("histogram_hits: no device scene yet -- trace with ray_tracer(tree=False) first")
+        index = lambda s: int(s) if isinstance(s, (int, N.integer)) else self._surface_index(s)
+        if isinstance(surface, (tuple, list)):
+            lo, hi = [index(s) for s in surface]
+        else:
+            lo = hi = index(surface)
+        proj = None
+        if swap_xy:
+            proj = N.round(N.linalg.inv(self._dev.compiled.surfaces[lo]._temp_frame), decimals=9)[[1, 0, 2, 3]]
+        return self._dev.histogram_hits(lo, hi, u_edges, v_edges, proj=proj, chart=chart, weight=weight, moments=moments)
+
     def enable_transfer_matrix(self, on=True):
         """
         Keep the surface-to-surface energy transfer of the following traces: get_transfer_matrix()[i, j] is the energy
