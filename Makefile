@@ -1,5 +1,7 @@
 # Build recipe for the native pieces.  `make` builds the product library (HIP, gfx950).
 # `make hostcheck` builds the CPU debug harness of the per-ray core used by tests only.
+# `make poolcheck poolcheck-tsan` build the host check of the block cache (trc_pool.h: one cache, under one policy for device memory
+# and another for pinned host memory) with the address / undefined-behaviour sanitizers and with the thread sanitizer.
 ROOT := $(dir $(abspath $(lastword $(MAKEFILE_LIST))))
 HIPCC ?= hipcc
 CXX ?= g++
@@ -13,7 +15,7 @@ CSRC := $(ROOT)tracer_amd/csrc
 SRCS := $(CSRC)/trc_kernels.hip $(CSRC)/trc_shade.hip $(CSRC)/trc_hithist.hip
 OBJDIR := $(ROOT)build/obj
 OBJS := $(OBJDIR)/trc_kernels.o $(OBJDIR)/trc_shade.o $(OBJDIR)/trc_hithist.o
-HDR := $(CSRC)/trc_core.h $(CSRC)/trc_bounds.h $(CSRC)/trc_footprint.h $(CSRC)/trc_forms.h $(CSRC)/trc_device.h $(CSRC)/trc_stream.inc $(CSRC)/trc_mega.inc $(CSRC)/trc_hithist.h $(ROOT)include/tracer_amd.h
+HDR := $(CSRC)/trc_core.h $(CSRC)/trc_bounds.h $(CSRC)/trc_footprint.h $(CSRC)/trc_forms.h $(CSRC)/trc_device.h $(CSRC)/trc_stream.inc $(CSRC)/trc_mega.inc $(CSRC)/trc_hithist.h $(CSRC)/trc_pool.h $(ROOT)include/tracer_amd.h
 
 HOSTCHECK := $(ROOT)tests/hostcheck/libtrc_hostcheck.so
 HOSTCHECK_SRC := $(ROOT)tests/hostcheck/hostcheck.cpp
@@ -128,6 +130,20 @@ polycheck: $(POLYCHECK_EXE)
 $(POLYCHECK_EXE): $(POLYCHECK_SRC) $(HDR)
 	$(CXX) -O1 -g -std=c++17 $(FPFLAGS) $(SPLIT_SAN) -o $@ $(POLYCHECK_SRC)
 
+# the block cache behind device and pinned memory (trc_pool.h) through a fake backend: its classes, caps, eviction order, retry and
+# device key, and its books after eight threads have used it.  Two programs of their own, run by tests/test_pool_host.py
+POOLCHECK_EXE := $(ROOT)tests/poolcheck/pool_check
+POOLCHECK_TSAN_EXE := $(ROOT)tests/poolcheck/pool_check_tsan
+POOLCHECK_SRC := $(ROOT)tests/poolcheck/pool_check.cpp
+poolcheck: $(POOLCHECK_EXE)
+poolcheck-tsan: $(POOLCHECK_TSAN_EXE)
+
+$(POOLCHECK_EXE): $(POOLCHECK_SRC) $(CSRC)/trc_pool.h
+	$(CXX) -O1 -g -std=c++17 $(SPLIT_SAN) -pthread -o $@ $(POOLCHECK_SRC)
+
+$(POOLCHECK_TSAN_EXE): $(POOLCHECK_SRC) $(CSRC)/trc_pool.h
+	$(CXX) -O1 -g -std=c++17 -fsanitize=thread -pthread -o $@ $(POOLCHECK_SRC)
+
 # assembly listings with the registers, scratch and occupancy of every kernel (build/*.s, build/*.resources.txt)
 asm: $(SRCS) $(HDR)
 	mkdir -p $(ROOT)build
@@ -144,4 +160,4 @@ asm-shade: $(CSRC)/trc_shade.hip $(HDR)
 clean:
 	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK) $(HHCHECK)
 
-.PHONY: all hostcheck umaskcheck umaskcheck-exe splitcheck polycheck asm asm-shade clean
+.PHONY: all hostcheck umaskcheck umaskcheck-exe splitcheck polycheck poolcheck poolcheck-tsan asm asm-shade clean

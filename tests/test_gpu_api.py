@@ -420,6 +420,98 @@ def test_without_the_device_pool():
     assert out.returncode == 0 and out.stdout.strip().endswith('ok'), out.stderr[-2000:]
 
 
+def _child(code, **env):
+    """`code` in a python of its own, where the library's block caches start empty: what it printed last, as JSON"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, '-c', code], env=dict(os.environ, PYTHONPATH=root, **env), capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    print(out.stdout)
+    return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+def test_pinned_blocks_are_kept_by_class_and_foreign_pointers_refused():
+    """trc_host_alloc / trc_host_free through the C ABI: a freed block is the next one of its size class (3 MiB + 1 and 3 MiB + 5 share
+    one), a live block is nobody else's, zero bytes give a block, NULL is freed in peace, a pointer that is not a block of the
+    library's is refused by name, and a negative size is invalid"""
+    r = _child(
+        "import ctypes as C, json\n"
+        "from tracer_amd import _cabi\n"
+        "lib = _cabi.load_library()\n"
+        "def alloc(n):\n"
+        "    p = C.c_void_p()\n"
+        "    return lib.trc_host_alloc(n, C.byref(p)), p.value\n"
+        "r = {}\n"
+        "M = 3 << 20\n"
+        "r['first'] = alloc(M + 1)\n"
+        "r['freed'] = lib.trc_host_free(C.c_void_p(r['first'][1]))\n"
+        "r['again'] = alloc(M + 5)\n"
+        "r['other'] = alloc(M + 5)\n"
+        "r['zero'] = alloc(0)\n"
+        "r['null'] = lib.trc_host_free(None)\n"
+        "buf = C.create_string_buffer(64)\n"
+        "r['foreign'] = lib.trc_host_free(C.c_void_p(C.addressof(buf)))\n"
+        "r['foreign_msg'] = lib.trc_last_error().decode()\n"
+        "r['negative'] = alloc(-1)\n"
+        "r['cleanup'] = [lib.trc_host_free(C.c_void_p(r[k][1])) for k in ('again', 'other', 'zero')]\n"
+        "print(json.dumps(r))\n")
+    ok, invalid = 0, -1
+    assert r['first'][0] == ok and r['first'][1] and r['freed'] == ok
+    assert r['again'] == [ok, r['first'][1]]
+    assert r['other'][0] == ok and r['other'][1] and r['other'][1] != r['first'][1]
+    assert r['zero'][0] == ok and r['zero'][1]
+    assert r['null'] == ok
+    assert r['foreign'] == invalid and 'trc_host_free' in r['foreign_msg']
+    assert r['negative'][0] == invalid
+    assert r['cleanup'] == [ok, ok, ok]
+
+
+_KEPT_THEN_TRIMMED = (
+    "import ctypes as C, json\n"
+    "from tracer_amd import _cabi\n"
+    "lib = _cabi.load_library()\n"
+    "hip = C.CDLL('libamdhip64.so')\n"
+    "def free_bytes():\n"
+    "    free, total = C.c_size_t(0), C.c_size_t(0)\n"
+    "    assert hip.hipMemGetInfo(C.byref(free), C.byref(total)) == 0\n"
+    "    return free.value\n"
+    "ctx, sc = C.c_void_p(), C.c_void_p()\n"
+    "_cabi.check(lib.trc_ctx_create(0, C.byref(ctx)))\n"
+    "d = _cabi.SurfaceDesc()\n"
+    "d.gm_kind, d.optics_kind, d.extra_off = _cabi.GM_RECT, _cabi.OPT_REFLECTIVE, -1\n"
+    "d.frame[0] = d.frame[5] = d.frame[10] = 1.\n"
+    "d.gm[0] = d.gm[1] = 2.\n"
+    "d.opt[0] = 0.1\n"
+    "_cabi.check(lib.trc_scene_create(ctx, 1, C.byref(d), 0, None, C.byref(sc)))\n"
+    "r = {'f0': free_bytes()}\n"
+    "_cabi.check(lib.trc_scene_set_hit_capacity(sc, 4000000))\n"
+    "r['f1'] = free_bytes()\n"
+    "_cabi.check(lib.trc_scene_destroy(sc))\n"
+    "r['scene_gone'] = free_bytes()\n"
+    "_cabi.check(lib.trc_ctx_destroy(ctx))\n"
+    "r['ctx_gone'] = free_bytes()\n"
+    "print(json.dumps(r))\n")
+
+
+def test_device_blocks_wait_in_the_cache_until_the_context_goes():
+    """a hit buffer of 4e6 entries (columns of 32 MB, classed blocks) by the driver's count of free memory: what it took stays
+    taken when the scene is destroyed -- the blocks wait in the library's cache -- and comes back with the context, which trims the
+    cache; with TRC_DEV_POOL=0 it comes back with the scene.  (The quarters allow for the driver's own granularity.)"""
+    r = _child(_KEPT_THEN_TRIMMED)
+    A = r['f0'] - r['f1']
+    print('cache on: took %d, back after the scene %d, after the context %d' % (A, r['scene_gone'] - r['f1'], r['ctx_gone'] - r['f1']))
+    assert A >= 128 << 20
+    assert r['scene_gone'] - r['f1'] < A / 4
+    assert r['ctx_gone'] - r['f1'] > 3 * A / 4
+    r = _child(_KEPT_THEN_TRIMMED, TRC_DEV_POOL='0')
+    A = r['f0'] - r['f1']
+    print('cache off: took %d, back after the scene %d, after the context %d' % (A, r['scene_gone'] - r['f1'], r['ctx_gone'] - r['f1']))
+    assert A >= 128 << 20
+    assert r['scene_gone'] - r['f1'] > 3 * A / 4
+
+
 def test_sg4_zones_and_petal_under_a_parallel_beam():
     """models/SG4.py:14-61 (two nested zones, the inner one met first) and models/PETAL_dish.py:12-50 (hexagonal aperture)
     under 2e5 axial rays: which zone a ray meets, the absorbed share, the perfect focus of the zone without slope error"""

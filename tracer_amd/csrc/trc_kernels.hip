@@ -18,8 +18,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -35,6 +33,7 @@
 #include "trc_bounds.h"
 #include "trc_footprint.h"
 #include "trc_device.h"
+#include "trc_pool.h"
 #include "trc_hithist.h"
 
 // ================================================================================================
@@ -69,161 +68,40 @@ static int trc_fail(int code, const char *fmt, ...) {
 extern "C" const char *trc_last_error(void) { return g_last_error.c_str(); }
 extern "C" int trc_abi_version(void) { return TRC_ABI_VERSION; }
 
-// Device memory.  A freed block of up to POOL_BLOCK_MAX bytes is kept for the next request of its size class instead of going back
-// to the driver: scripts build an engine per run, and an ordered trace of 1e5 rays spent 3 of its 10 ms in hipMalloc / hipFree (a
-// block of a few MB costs ~0.3 ms to map and as much to release).  Size classes are an eighth of an octave apart (at most 12.5 %
-// over the request); at most POOL_KEEP bytes wait idle, and a failed hipMalloc empties the pool and tries again.  Larger requests
-// (the hit buffers and ray tables of 1e7-ray runs and beyond) go to hipMalloc as they are and come straight back: their cost is
-// nothing next to the run, and hipMalloc of a *rounded* large size was seen to stall for 1.2 s.  Keeping a block waits for the
-// device as hipFree would have.  TRC_DEV_POOL=0 turns the pool off.
-struct DevPool {
-    std::mutex mu;
-    std::unordered_map<void *, std::pair<size_t, int>> live;      // block handed out -> (bytes allocated, device)
-    std::multimap<std::pair<int, size_t>, void *> idle;           // (device, bytes) -> block waiting
-    size_t idle_bytes = 0;
-    size_t idle_large = 0;          // bytes of idle blocks beyond POOL_BLOCK_MAX (kept by exact size)
-    std::deque<void *> large_order; // ... in the order they became idle
-    int enabled = -1;
+// Device memory goes through a block cache (trc_pool.h: the policy and its reasons): a freed block of up to 128 MiB waits for the
+// next request of its size class, a larger one for the next request of exactly its size, 2 GiB of each at most.  Keeping a block
+// waits for the device as hipFree would have -- for the *current* device, as it always did, which need not be the block's own.
+// TRC_DEV_POOL=0, read when the first block is asked for, turns the cache off.
+struct DevBackend {
+    static inline thread_local hipError_t err = hipSuccess;       // why this thread's last alloc() gave nothing
+    void *alloc(size_t bytes) {
+        void *p = nullptr;
+        err = hipMalloc(&p, bytes);
+        if (err == hipSuccess) return p;
+        (void)hipGetLastError();      // (the failure is reported by err: it is not left for the next kernel launch to find)
+        return nullptr;
+    }
+    void release(void *p) { (void)hipFree(p); }
+    void quiesce() { (void)hipDeviceSynchronize(); }      // nothing in flight may still use the block when the next owner gets it
+    int device() { int d = 0; (void)hipGetDevice(&d); return d; }
 };
-static DevPool g_pool;
-static const size_t POOL_KEEP = (size_t)2 << 30;
-static const size_t POOL_BLOCK_MAX = (size_t)128 << 20;
-static const size_t POOL_KEEP_LARGE = (size_t)2 << 30;       // idle bytes of blocks beyond POOL_BLOCK_MAX (the oldest make room for a new one)
-
-static bool pool_enabled() {
-    if (g_pool.enabled < 0) {
-        const char *e = getenv("TRC_DEV_POOL");
-        g_pool.enabled = (e && e[0] == '0') ? 0 : 1;
-    }
-    return g_pool.enabled == 1;
-}
-
-static size_t pool_class(size_t bytes) {
-    if (bytes <= 256) return 256;
-    const int k = 63 - __builtin_clzll((unsigned long long)bytes);      // 2^k <= bytes
-    const size_t step = (size_t)1 << (k - 3);
-    return (bytes + step - 1) & ~(step - 1);
-}
-
-static void pool_trim() {
-    std::vector<void *> gone;
-    {
-        std::lock_guard<std::mutex> g(g_pool.mu);
-        for (auto &kv : g_pool.idle) gone.push_back(kv.second);
-        g_pool.idle.clear();
-        g_pool.large_order.clear();
-        g_pool.idle_bytes = 0;
-        g_pool.idle_large = 0;
-    }
-    for (void *p : gone) (void)hipFree(p);
-}
-
-static hipError_t pool_alloc(void **out, size_t bytes) {
-    *out = nullptr;
-    // large requests are not rounded -- hipMalloc of a rounded size (2 GiB, 4 GiB, 7 x 256 MiB ...) was seen to take 1.2 s where
-    // the exact size takes milliseconds -- but a freed large block waits for the next request of exactly its size: a Monte-Carlo
-    // loop asks for the same 0.9 GB level of 1e7 source rays call after call, and mapping it anew was 10 ms of each
-    if (!pool_enabled()) return hipMalloc(out, bytes);
-    if (bytes > POOL_BLOCK_MAX) {
-        int dev_l = 0;
-        (void)hipGetDevice(&dev_l);
-        {
-            std::lock_guard<std::mutex> g(g_pool.mu);
-            auto it = g_pool.idle.find(std::make_pair(dev_l, bytes));
-            if (it != g_pool.idle.end()) {
-                *out = it->second;
-                g_pool.idle.erase(it);
-                g_pool.idle_large -= bytes;
-                for (auto q = g_pool.large_order.begin(); q != g_pool.large_order.end(); ++q)
-                    if (*q == *out) { g_pool.large_order.erase(q); break; }
-                g_pool.live[*out] = std::make_pair(bytes, dev_l);
-                return hipSuccess;
-            }
-        }
-        hipError_t el = hipMalloc(out, bytes);
-        if (el != hipSuccess) {
-            (void)hipGetLastError();
-            pool_trim();
-            el = hipMalloc(out, bytes);
-            if (el != hipSuccess) return el;
-        }
-        std::lock_guard<std::mutex> g(g_pool.mu);
-        g_pool.live[*out] = std::make_pair(bytes, dev_l);
-        return hipSuccess;
-    }
-    const size_t cls = pool_class(bytes);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    {
-        std::lock_guard<std::mutex> g(g_pool.mu);
-        auto it = g_pool.idle.find(std::make_pair(dev, cls));
-        if (it != g_pool.idle.end()) {
-            *out = it->second;
-            g_pool.idle.erase(it);
-            g_pool.idle_bytes -= cls;
-            g_pool.live[*out] = std::make_pair(cls, dev);
-            return hipSuccess;
-        }
-    }
-    hipError_t e = hipMalloc(out, cls);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        pool_trim();
-        e = hipMalloc(out, cls);
-        if (e != hipSuccess) return e;
-    }
-    std::lock_guard<std::mutex> g(g_pool.mu);
-    g_pool.live[*out] = std::make_pair(cls, dev);
-    return hipSuccess;
-}
-
-static void pool_free(void *p) {
-    size_t cls = 0;
-    int dev = 0;
-    bool keep = false;
-    {
-        std::lock_guard<std::mutex> g(g_pool.mu);
-        auto it = g_pool.live.find(p);
-        if (it != g_pool.live.end()) {
-            cls = it->second.first;
-            dev = it->second.second;
-            g_pool.live.erase(it);
-            keep = pool_enabled() && (cls <= POOL_BLOCK_MAX ? g_pool.idle_bytes + cls <= POOL_KEEP : cls <= POOL_KEEP_LARGE);
-        }
-    }
-    if (!keep) { (void)hipFree(p); return; }
-    (void)hipDeviceSynchronize();        // nothing in flight may still use the block when the next owner gets it
-    std::vector<void *> evict;
-    {
-        std::lock_guard<std::mutex> g(g_pool.mu);
-        if (cls > POOL_BLOCK_MAX) {
-            // large blocks wait by exact size; the oldest of them make room
-            while (g_pool.idle_large + cls > POOL_KEEP_LARGE && !g_pool.large_order.empty()) {
-                void *old = g_pool.large_order.front();
-                g_pool.large_order.pop_front();
-                for (auto it = g_pool.idle.begin(); it != g_pool.idle.end(); ++it)
-                    if (it->second == old) { g_pool.idle_large -= it->first.second; g_pool.idle.erase(it); evict.push_back(old); break; }
-            }
-            g_pool.large_order.push_back(p);
-            g_pool.idle_large += cls;
-        } else g_pool.idle_bytes += cls;
-        g_pool.idle.insert(std::make_pair(std::make_pair(dev, cls), p));
-    }
-    for (void *q : evict) (void)hipFree(q);
+static trc_block_cache<DevBackend> &dev_cache() {
+    static const char *const e = getenv("TRC_DEV_POOL");
+    static trc_block_cache<DevBackend> cache({(size_t)128 << 20, (size_t)2 << 30, (size_t)2 << 30, true, true}, !(e && e[0] == '0'));
+    return cache;
 }
 
 template <class T>
 static int dev_alloc(T **p, size_t n) {
     *p = nullptr;
     if (n == 0) n = 1;
-    hipError_t e = pool_alloc((void **)p, n * sizeof(T));
-    if (e != hipSuccess)
-        return trc_fail(TRC_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", n * sizeof(T), hipGetErrorString(e));
+    *p = (T *)dev_cache().alloc(n * sizeof(T));
+    if (!*p) return trc_fail(TRC_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", n * sizeof(T), hipGetErrorString(DevBackend::err));
     return TRC_OK;
 }
 template <class T>
 static void dev_free(T *&p) {
-    if (p) pool_free((void *)p);
+    if (p) (void)dev_cache().free((void *)p);
     p = nullptr;
 }
 
@@ -245,6 +123,25 @@ public:
     void reset() { dev_free(p_); }
     T *get() const { return p_; }
     explicit operator bool() const { return p_ != nullptr; }
+};
+
+// A DevBuf kept between calls that only grows.  reserve(n) leaves a buffer of n elements or more alone; a smaller one is replaced
+// by a new one of n, contents not kept.  A reserve that fails leaves size() 0, so a buffer half grown claims nothing.
+template <class T>
+class GrowBuf {
+    DevBuf<T> b_;
+    size_t n_ = 0;
+public:
+    int reserve(size_t n) {
+        if (n <= n_) return TRC_OK;
+        n_ = 0;
+        TRC_TRY(b_.alloc(n));
+        n_ = n;
+        return TRC_OK;
+    }
+    void reset() { b_.reset(); n_ = 0; }
+    T *get() const { return b_.get(); }
+    size_t size() const { return n_; }
 };
 
 // a new block of n elements for `b`, and the n elements of host `src` copied into it (nothing is copied for n == 0 or no src);
@@ -494,14 +391,12 @@ struct trc_scene {
     DevBuf<double> d_fm_edges;
     CounterBlock counters;
     DevBuf<trc_source_desc> d_src_buf; // device copy of the source descriptor of the call in progress (kept between calls)
-    DevBuf<double> d_spec_buf;         // device copy of the packed source spectrum of the call in progress (FastParams.spec), and its room
-    size_t spec_cap;
+    GrowBuf<double> d_spec_buf;        // device copy of the packed source spectrum of the call in progress (FastParams.spec)
     trc_source_desc src_host;   // ... and what it holds (src_host_ok): a Monte-Carlo loop hands over the same descriptor every call
     bool src_host_ok;
-    DevBuf<double> d_last[7];         // device side of trc_trace_fast's `last` bundle, kept between calls (seven hipMalloc / hipFree per
-    int64_t d_last_cap;               // call were a millisecond of a Monte-Carlo loop's 1e6-ray calls)
-    DevBuf<double> d_last_x;          // ... and the spectra of the rays a source that carries its spectrum leaves (W rows, d_last_x_len doubles)
-    size_t d_last_x_len = 0;
+    GrowBuf<double> d_last[7];        // device side of trc_trace_fast's `last` bundle, kept between calls (seven hipMalloc / hipFree per
+                                      // call were a millisecond of a Monte-Carlo loop's 1e6-ray calls)
+    GrowBuf<double> d_last_x;         // ... and the spectra of the rays a source that carries its spectrum leaves (W rows)
     HitBuffer hits;
     double hist_ms = 0.0;             // device time of the last k_hist_hits (trc_scene_histogram_hits_ms)
 };
@@ -536,8 +431,8 @@ struct OrdScratch {
     DevBuf<uint32_t> key, ckey, cslot, skey, sslot;
     DevBuf<unsigned> blk_cnt, blk_cul;
     DevBuf<unsigned long long> blk_off, totals;
-    DevBuf<char> sort_tmp;
-    size_t cap_slots = 0, sort_bytes = 0;
+    GrowBuf<char> sort_tmp;
+    size_t cap_slots = 0;
     int cap_pay = 0;
     int ensure(size_t slots, int n_pay) {
         if (slots <= cap_slots && n_pay <= cap_pay) return TRC_OK;
@@ -554,13 +449,6 @@ struct OrdScratch {
         TRC_TRY(blk_cnt.alloc(nblk)); TRC_TRY(blk_cul.alloc(nblk)); TRC_TRY(blk_off.alloc(nblk));
         TRC_TRY(totals.alloc(2));
         cap_slots = slots;
-        return TRC_OK;
-    }
-    int ensure_sort(size_t bytes) {
-        if (bytes <= sort_bytes && sort_tmp) return TRC_OK;
-        sort_bytes = 0;
-        TRC_TRY(sort_tmp.alloc(bytes));
-        sort_bytes = bytes;
         return TRC_OK;
     }
 };
@@ -1256,7 +1144,7 @@ extern "C" int trc_ctx_destroy(trc_ctx *ctx) {
     (void)hipEventDestroy(ctx->ev1);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
-    pool_trim();          // blocks kept for reuse go back to the driver with the context
+    dev_cache().trim();   // blocks kept for reuse go back to the driver with the context
     return TRC_OK;
 }
 
@@ -1410,7 +1298,6 @@ extern "C" int trc_scene_create(trc_ctx *ctx, int32_t n_surf, const trc_surface_
     if (!sc) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
     sc->ctx = ctx;
     sc->src_host_ok = false;
-    sc->d_last_cap = 0;
     sc->n_surf = n_surf;
     sc->stride = TRC_REC_HDR + max_np;
     if ((sc->stride & 1) == 0) sc->stride += 1;  // odd number of doubles: spreads records over LDS banks
@@ -1625,65 +1512,32 @@ extern "C" int trc_scene_hits_reserved(trc_scene *sc, int64_t *reserved, int64_t
 }
 
 // Page-locked host memory for large results (hit lists, levels of the ray tree): a device-to-host copy into pageable memory is
-// staged through the driver's own bounce buffers at a third of the rate.  Blocks are kept by size class when they are freed
-// (page-locking 250 MB takes longer than copying them): at most HOST_KEEP bytes wait idle.
-struct HostPool {
-    std::mutex mu;
-    std::unordered_map<void *, size_t> live;
-    std::multimap<size_t, void *> idle;
-    size_t idle_bytes = 0;
+// staged through the driver's own bounce buffers at a third of the rate.  The same block cache as device memory, under a policy of
+// its own: every block classed, at most 4 GiB idle, nothing to wait for, and a pointer that is not one of its blocks refused.
+struct HostBackend {
+    static inline thread_local hipError_t err = hipSuccess;
+    void *alloc(size_t bytes) {
+        void *p = nullptr;
+        err = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+        if (err == hipSuccess) return p;
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    void release(void *p) { (void)hipHostFree(p); }
+    void quiesce() {}
+    int device() { return 0; }
 };
-static HostPool g_host_pool;
-static const size_t HOST_KEEP = (size_t)4 << 30;
+static trc_block_cache<HostBackend> g_host_cache({SIZE_MAX, (size_t)4 << 30, 0, false, false}, true);
 
 extern "C" int trc_host_alloc(int64_t bytes, void **out) {
     if (!out || bytes < 0) return trc_fail(TRC_ERR_INVALID, "bad arguments");
-    *out = nullptr;
-    const size_t cls = pool_class((size_t)(bytes > 0 ? bytes : 1));
-    {
-        std::lock_guard<std::mutex> g(g_host_pool.mu);
-        auto it = g_host_pool.idle.find(cls);
-        if (it != g_host_pool.idle.end()) {
-            *out = it->second;
-            g_host_pool.idle.erase(it);
-            g_host_pool.idle_bytes -= cls;
-            g_host_pool.live[*out] = cls;
-            return TRC_OK;
-        }
-    }
-    hipError_t e = hipHostMalloc(out, cls, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        std::vector<void *> gone;
-        {
-            std::lock_guard<std::mutex> g(g_host_pool.mu);
-            for (auto &kv : g_host_pool.idle) gone.push_back(kv.second);
-            g_host_pool.idle.clear();
-            g_host_pool.idle_bytes = 0;
-        }
-        for (void *p : gone) (void)hipHostFree(p);
-        e = hipHostMalloc(out, cls, hipHostMallocDefault);
-        if (e != hipSuccess) return trc_fail(TRC_ERR_NOMEM, "hipHostMalloc(%zu bytes) failed: %s", cls, hipGetErrorString(e));
-    }
-    std::lock_guard<std::mutex> g(g_host_pool.mu);
-    g_host_pool.live[*out] = cls;
+    *out = g_host_cache.alloc((size_t)bytes);
+    if (!*out) return trc_fail(TRC_ERR_NOMEM, "hipHostMalloc(%zu bytes) failed: %s", trc_pool_class((size_t)bytes), hipGetErrorString(HostBackend::err));
     return TRC_OK;
 }
 
 extern "C" int trc_host_free(void *p) {
-    if (!p) return TRC_OK;
-    size_t cls = 0;
-    bool keep = false;
-    {
-        std::lock_guard<std::mutex> g(g_host_pool.mu);
-        auto it = g_host_pool.live.find(p);
-        if (it == g_host_pool.live.end()) return trc_fail(TRC_ERR_INVALID, "trc_host_free: not a block of trc_host_alloc");
-        cls = it->second;
-        g_host_pool.live.erase(it);
-        keep = g_host_pool.idle_bytes + cls <= HOST_KEEP;
-        if (keep) { g_host_pool.idle.insert(std::make_pair(cls, p)); g_host_pool.idle_bytes += cls; }
-    }
-    if (!keep) (void)hipHostFree(p);
+    if (p && g_host_cache.free(p) == TRC_POOL_UNKNOWN) return trc_fail(TRC_ERR_INVALID, "trc_host_free: not a block of trc_host_alloc");
     return TRC_OK;
 }
 
@@ -2619,11 +2473,7 @@ static int scene_stage_spectrum(trc_scene *sc, const SourceSpectrum &sp, const d
     std::vector<double> packed((size_t)3 + sp.tab.size());
     packed[0] = (double)n_tab; packed[1] = sp.desc->wavelength; packed[2] = sp.desc->ref_index;
     std::copy(sp.tab.begin(), sp.tab.end(), packed.begin() + 3);
-    if (sc->spec_cap < packed.size()) {
-        sc->spec_cap = 0;
-        TRC_TRY(sc->d_spec_buf.alloc((size_t)3 + 3 * TRC_SPECTRUM_MAX_POINTS));     // (room for any table: allocated once)
-        sc->spec_cap = (size_t)3 + 3 * TRC_SPECTRUM_MAX_POINTS;
-    }
+    TRC_TRY(sc->d_spec_buf.reserve((size_t)3 + 3 * TRC_SPECTRUM_MAX_POINTS));     // (room for any table: allocated once)
     // (the stream is idle between calls: every call ends with a synchronous read of its counters)
     HIP_TRY(hipMemcpy(sc->d_spec_buf.get(), packed.data(), packed.size() * 8, hipMemcpyHostToDevice));
     *d_spec = sc->d_spec_buf.get();
@@ -2787,23 +2637,15 @@ static int fast_stage_last(FastCall &C) {
     if (!last || !last->x || !last->y || !last->z || !last->dx || !last->dy || !last->dz || !last->e || last->on_device)
         return trc_fail(TRC_ERR_INVALID, "TRC_TRACE_KEEP_LAST needs a host `last` bundle with x..e");
     C.last_cap = last->n;
-    if (sc->d_last_cap < C.last_cap) {
-        for (auto &col : sc->d_last) col.reset();
-        sc->d_last_cap = 0;
-        for (auto &col : sc->d_last)
-            if (int e = col.alloc((size_t)C.last_cap)) { for (auto &c : sc->d_last) c.reset(); return e; }
-        sc->d_last_cap = C.last_cap;
+    for (int i = 0; i < 7; ++i) {
+        if (C.last_cap > 0) TRC_TRY(sc->d_last[i].reserve((size_t)C.last_cap));
+        C.d_last[i] = sc->d_last[i].get();
     }
-    for (int i = 0; i < 7; ++i) C.d_last[i] = sc->d_last[i].get();
     // the rays left by a source that carries its spectrum bring their spectra back, when the caller made room for them
     const int W = C.spec->carried();
     if (W > 0 && last->spectra && last->n_spec == W && C.last_cap > 0) {
         const size_t need = (size_t)W * (size_t)C.last_cap;
-        if (sc->d_last_x_len < need) {
-            sc->d_last_x_len = 0;
-            TRC_TRY(sc->d_last_x.alloc(need));
-            sc->d_last_x_len = need;
-        }
+        TRC_TRY(sc->d_last_x.reserve(need));
         C.d_last_x = sc->d_last_x.get();
         if (last->spec_wl) TRC_TRY(C.last_wl.alloc(need));
     }
@@ -3145,7 +2987,7 @@ static int ordered_next_level(OrdCall &C, int it, int64_t n_cur, int64_t m, int6
     size_t tmp_bytes = 0;
     hipError_t re = rocprim::radix_sort_pairs(nullptr, tmp_bytes, sx.ckey.get(), sx.skey.get(), sx.cslot.get(), sx.sslot.get(), (size_t)m, 0, 31, ctx->stream);
     if (re != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "radix_sort_pairs(size query) failed: %s", hipGetErrorString(re));
-    TRC_TRY(sx.ensure_sort(tmp_bytes));
+    TRC_TRY(sx.sort_tmp.reserve(std::max(tmp_bytes, (size_t)1)));
     re = rocprim::radix_sort_pairs(sx.sort_tmp.get(), tmp_bytes, sx.ckey.get(), sx.skey.get(), sx.cslot.get(), sx.sslot.get(), (size_t)m, 0, 31, ctx->stream);
     if (re != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "radix_sort_pairs failed: %s", hipGetErrorString(re));
     Level next;
