@@ -2,6 +2,7 @@
 # `make hostcheck` builds the CPU debug harness of the per-ray core used by tests only.
 # `make poolcheck poolcheck-tsan` build the host check of the block cache (trc_pool.h: one cache, under one policy for device memory
 # and another for pinned host memory) with the address / undefined-behaviour sanitizers and with the thread sanitizer.
+# `make scenecheck` builds the host check of a scene's host arithmetic (trc_scene_host.h) with the same sanitizers.
 ROOT := $(dir $(abspath $(lastword $(MAKEFILE_LIST))))
 HIPCC ?= hipcc
 CXX ?= g++
@@ -15,7 +16,7 @@ CSRC := $(ROOT)tracer_amd/csrc
 SRCS := $(CSRC)/trc_kernels.hip $(CSRC)/trc_shade.hip $(CSRC)/trc_hithist.hip
 OBJDIR := $(ROOT)build/obj
 OBJS := $(OBJDIR)/trc_kernels.o $(OBJDIR)/trc_shade.o $(OBJDIR)/trc_hithist.o
-HDR := $(CSRC)/trc_core.h $(CSRC)/trc_bounds.h $(CSRC)/trc_footprint.h $(CSRC)/trc_forms.h $(CSRC)/trc_device.h $(CSRC)/trc_stream.inc $(CSRC)/trc_mega.inc $(CSRC)/trc_hithist.h $(CSRC)/trc_pool.h $(ROOT)include/tracer_amd.h
+HDR := $(CSRC)/trc_core.h $(CSRC)/trc_bounds.h $(CSRC)/trc_footprint.h $(CSRC)/trc_forms.h $(CSRC)/trc_device.h $(CSRC)/trc_stream.inc $(CSRC)/trc_mega.inc $(CSRC)/trc_hithist.h $(CSRC)/trc_pool.h $(CSRC)/trc_scene_host.h $(ROOT)include/tracer_amd.h
 
 HOSTCHECK := $(ROOT)tests/hostcheck/libtrc_hostcheck.so
 HOSTCHECK_SRC := $(ROOT)tests/hostcheck/hostcheck.cpp
@@ -144,6 +145,15 @@ $(POOLCHECK_EXE): $(POOLCHECK_SRC) $(CSRC)/trc_pool.h
 $(POOLCHECK_TSAN_EXE): $(POOLCHECK_SRC) $(CSRC)/trc_pool.h
 	$(CXX) -O1 -g -std=c++17 -fsanitize=thread -pthread -o $@ $(POOLCHECK_SRC)
 
+# the host side of a scene (trc_scene_host.h): the Kd-tree validation on malformed trees, its packing, the tally layout and the build
+# order of the search tables.  A program of its own, built with the sanitizers and run by tests/test_scene_host.py
+SCENECHECK_EXE := $(ROOT)tests/scenecheck/scene_check
+SCENECHECK_SRC := $(ROOT)tests/scenecheck/scene_check.cpp
+scenecheck: $(SCENECHECK_EXE)
+
+$(SCENECHECK_EXE): $(SCENECHECK_SRC) $(HDR)
+	$(CXX) -O1 -g -std=c++17 $(FPFLAGS) $(SPLIT_SAN) -o $@ $(SCENECHECK_SRC)
+
 # assembly listings with the registers, scratch and occupancy of every kernel (build/*.s, build/*.resources.txt)
 asm: $(SRCS) $(HDR)
 	mkdir -p $(ROOT)build
@@ -160,4 +170,4 @@ asm-shade: $(CSRC)/trc_shade.hip $(HDR)
 clean:
 	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK) $(HHCHECK)
 
-.PHONY: all hostcheck umaskcheck umaskcheck-exe splitcheck polycheck poolcheck poolcheck-tsan asm asm-shade clean
+.PHONY: all hostcheck umaskcheck umaskcheck-exe splitcheck polycheck poolcheck poolcheck-tsan scenecheck asm asm-shade clean

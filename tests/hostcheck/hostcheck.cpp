@@ -11,6 +11,7 @@
 #include "../../tracer_amd/csrc/trc_bounds.h"
 #include "../../tracer_amd/csrc/trc_footprint.h"
 #include "../../tracer_amd/csrc/trc_forms.h"
+#include "../../tracer_amd/csrc/trc_scene_host.h"
 
 static void pack_record(const trc_surface_desc &s, double *rec, int stride) {
     for (int i = 0; i < stride; ++i) rec[i] = 0.0;
@@ -622,17 +623,12 @@ int hc_forms_decide(long n, const double *facts, double *out) {
 int hc_scene_facts(int n_surf, const trc_surface_desc *surfs, const trc_kdtree_desc *kd, const trc_source_desc *src, int M, int force32, double *v) {
     trc_accel_host H;
     H.kd_depth = 0;
-    trc_accel_build_surfaces(surfs, n_surf, H);
-    trc_accel_build_grid(H, n_surf);
-    if (force32) H.grid_ok = false;
-    if (!H.grid_ok) trc_accel_build_grid32(surfs, n_surf, H);       // (the large grid: of the scenes the LDS-sized one cannot hold)
+    trc_search_tables_build(surfs, n_surf, force32 != 0, H);
     trc_scene_facts s = {};
     s.accel_ok = true;
     if (kd) { s.has_kd = true; s.kd_nodes = kd->n_nodes; s.kd_nleaf = kd->n_leaf_surfs; s.kd_nalways = kd->n_always; s.accel_kd_ok = trc_accel_build_kd(kd, H); }
     trc_scene_facts_fill(surfs, n_surf, H, true, &s);
-    int max_np = 0;
-    for (int i = 0; i < n_surf; ++i) { int np = trc_gm_nparams(surfs[i].gm_kind); if (np > max_np) max_np = np; }
-    s.stride = (TRC_REC_HDR + max_np) | 1;
+    s.stride = trc_scene_stride(surfs, n_surf);
     const double sv[16] = {(double)s.n_surf, (double)s.stride, (double)s.accel_ok, (double)s.accel_kd_ok, (double)s.has_kd, (double)s.kd_nodes, (double)s.kd_nleaf,
                            (double)s.kd_nalways, (double)s.kd_depth, (double)s.grid_ok, (double)s.big_ok, (double)s.grid_cells, (double)s.grid_list,
                            (double)s.brute_list, (double)s.n_unbounded, (double)s.big_occ_words};

@@ -375,3 +375,78 @@ def test_five_plates_two_maps_and_an_optics_table(ctx, plates, form):
     assert h0.sum() > 20000 and (h0 > 500).all()
     assert N.array_equal(h, h0) and N.allclose(a, a0, rtol=1e-9, atol=0.) and N.allclose(r, r0, rtol=1e-9, atol=0.)
     dev.close()
+
+
+def test_tally_layout_follows_the_transfer_matrix(ctx, plates):
+    """The packed tally buffer of the five plates is [3 S + 2 | the 12 + 10 bins of the two maps], and (S + 1) S more while the
+    transfer matrix is kept; every toggle gives a zeroed buffer with the maps at the same places.  With the matrix on, a trace's
+    maps equal the host histogram of its hits, the matrix's columns sum to what the surfaces received and its last row (from the
+    source) is what they receive in a trace of one bounce."""
+    cs, frames, rays, _ = plates[False]
+    S = cs.n_surf
+    T = 3 * S + 2 + sum((len(u) - 1) * (len(v) - 1) for u, v in fs.PLATES_EDGES.values())
+    assert T == 39
+    dev = _device(ctx, cs, fs.PLATES_EDGES, _capacity(20000))
+    assert dev.tally_size() == T
+    for on, size in ((True, T + (S + 1) * S), (False, T), (True, T + (S + 1) * S)):
+        dev.trace_fast(rays, 3, EMIN, 51, accel=True, stream=True)
+        assert all(dev.get_fluxmap(s).any() for s in fs.PLATES_EDGES)
+        dev.enable_transfer(on)
+        assert dev.tally_size() == size
+        assert all(dev.get_fluxmap(s).shape == (len(u) - 1, len(v) - 1) and not dev.get_fluxmap(s).any() for s, (u, v) in fs.PLATES_EDGES.items())
+        assert not dev.export_tallies().any()
+    dev.lib.trc_scene_clear_hits(dev.handle)
+    st, _ = dev.trace_fast(rays, 3, EMIN, 51, accel=True, stream=True)
+    assert st.hits_dropped == 0
+    ref = _captured(dev, frames, fs.PLATES_EDGES)
+    fs.check_inputs(ref, fs.PLATES_EDGES)
+    _check(dev, ref, fs.PLATES_EDGES, 'matrix on')
+    a, r, h = dev.get_tallies()
+    M = dev.get_transfer()
+    dev.close()
+    one = _device(ctx, cs, fs.PLATES_EDGES, _capacity(20000))
+    one.trace_fast(rays, 1, EMIN, 51, accel=True, stream=True)
+    r1 = one.get_tallies()[1]
+    one.close()
+    print('matrix: from the source %s, first bounce received %s' % (M[-1], r1))
+    assert r1.sum() > 0.5 * N.asarray(rays.get_energy()).sum()
+    assert N.allclose(M.sum(axis=0), r, rtol=1e-9, atol=0.)
+    assert N.allclose(M[-1], r1, rtol=1e-9, atol=0.) and N.isclose(M[-1].sum(), r1.sum(), rtol=1e-9, atol=0.)
+
+
+def _plates_turned(turn):
+    """the five plates with the mirror wall -y turned about its own x axis; the mapped surfaces stay"""
+    from tracer_amd.scene import compile_scene
+    from tracer_amd.spatial_geometry import rotx
+    asm, T = fs.plates(False)
+    wall = asm.get_objects()[4]
+    wall.set_transform(N.dot(wall.get_transform(), rotx(turn)))
+    cs = compile_scene(asm)
+    return cs, [N.array(s._temp_frame) for s in cs.surfaces]
+
+
+def test_update_frames_twice_then_a_trace(ctx, plates):
+    """Two trc_scene_update_frames in a row (the search tables are rebuilt twice), then a trace: the maps equal the host histogram
+    of that call's hits in the final poses, and tallies and maps are those of a scene compiled fresh in the final poses."""
+    cs, frames, rays, (a0, r0, h0) = plates[False]
+    (cs1, frames1), (cs2, frames2) = _plates_turned(0.25), _plates_turned(-0.15)
+    assert all(N.array_equal(frames[s], frames2[s]) for s in fs.PLATES_EDGES)
+    assert not N.array_equal(frames[4], frames1[4]) and not N.array_equal(frames1[4], frames2[4]) and not N.array_equal(frames[4], frames2[4])
+    out = []
+    for updates in (True, False):
+        dev = _device(ctx, cs if updates else cs2, fs.PLATES_EDGES, _capacity(20000))
+        if updates:
+            dev.update_frames(cs1)
+            dev.update_frames(cs2)
+        st, _ = dev.trace_fast(rays, 3, EMIN, 51, accel=True, stream=True)
+        assert st.hits_dropped == 0
+        ref = _captured(dev, frames2, fs.PLATES_EDGES)
+        fs.check_inputs(ref, fs.PLATES_EDGES)
+        _check(dev, ref, fs.PLATES_EDGES, 'updated twice' if updates else 'compiled fresh')
+        out.append((dev.get_tallies(), dict((s, dev.get_fluxmap(s)) for s in fs.PLATES_EDGES)))
+        dev.close()
+    ((a, r, h), maps), ((af, rf, hf), maps_f) = out
+    assert not N.array_equal(h, h0)         # (the turned wall sends its rays elsewhere)
+    assert N.array_equal(h, hf) and N.allclose(a, af, rtol=1e-9, atol=0.) and N.allclose(r, rf, rtol=1e-9, atol=0.)
+    for s in fs.PLATES_EDGES:
+        assert N.allclose(maps[s], maps_f[s], rtol=1e-9, atol=1e-9 * maps_f[s].max()), s

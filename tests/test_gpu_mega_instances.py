@@ -96,3 +96,59 @@ def test_ordered_engine_on_the_chains(ctx, depth, chart, kernel):
         Hc, e_out, n_out, n_hits, n_edge = fc.host_maps(o['hit_list'], s.frames, {s.terminal: ('polar', False, N.linspace(0., 1.8, 7), N.linspace(0., 2. * N.pi, 9))})[s.terminal]
         assert n_hits == h[s.terminal] and n_edge == 0 and Hc.max() > 0.
         assert N.allclose(fm, Hc, rtol=1e-9, atol=1e-9 * Hc.max())
+
+
+def test_kd_tree_set_replaced_dropped_and_refused(ctx):
+    """The row with 2e4 rays through the ordered engine, the megakernel and the streaming form in five states of the scene's
+    Kd-tree: chain(24) set; chain(5), of other leaves, in its place; set_kdtree(None); update_frames with the same poses, which
+    drops a tree set before it; the refused chain(33) after a tree.  A tree changes no ray: every state gives every engine the
+    per-surface hit counts of the first and its energies to 1e-9.  Without a tree the ordered engine refuses accel=True (it is
+    then traced without); the fast engine's forms search all boxes or their own grid."""
+    from tracer_amd import _cabi
+    from tracer_amd.ray_bundle import RayBundle
+    from tracer_amd.scene import DeviceScene
+    c, s, n = M.CASE['row/boxes'], M.scene('row'), 20000
+    rng = N.random.RandomState(M.SEED)
+    up = N.arange(n) % 2 == 0
+    rad, ph = M.ROW_BEAM * N.sqrt(rng.uniform(size=n)), rng.uniform(0., 2. * N.pi, n)
+    v, d, e, _ = s.to_global(N.vstack((N.where(up, -0.5, M.ROW_PLATES * M.ROW_PITCH + 0.5), rad * N.cos(ph), rad * N.sin(ph))),
+                             N.vstack((N.where(up, 1., -1.), 0.025 * rng.uniform(-1., 1., n), 0.025 * rng.uniform(-1., 1., n))))
+    dev = DeviceScene(c.cs, ctx)
+    dev.set_hit_capacity(n * (c.reps + 1))
+
+    def trace(has_tree):
+        out = {}
+        for form in ('ordered', 'megakernel', 'stream'):
+            dev.reset_tallies()
+            b = RayBundle(vertices=v.copy(), directions=d.copy(), energy=e.copy())
+            if form == 'ordered':
+                if not has_tree:
+                    with pytest.raises(_cabi.TracerAmdError) as err:
+                        dev.trace_ordered(b, c.reps, c.min_energy, M.SEED, accel=True)
+                    assert err.value.status == _cabi.ERR_INVALID
+                res, st = dev.trace_ordered(b, c.reps, c.min_energy, M.SEED, accel=has_tree)
+                res.close()
+            else:
+                dev.trace_fast(b, c.reps, c.min_energy, M.SEED, accel=True, stream=form == 'stream')
+            out[form] = [N.array(x) for x in dev.get_tallies()]
+        return out
+
+    def refused():
+        dev.set_kdtree(s.chain(7))
+        with pytest.raises(_cabi.TracerAmdError) as err:
+            dev.set_kdtree(s.chain(M.REFUSED_DEPTH))
+        assert err.value.status == _cabi.ERR_UNSUPPORTED
+
+    states = [('chain(24)', lambda: dev.set_kdtree(s.chain(M.COOP_MAX_DEPTH)), True), ('chain(5)', lambda: dev.set_kdtree(s.chain(5)), True),
+              ('no tree', lambda: dev.set_kdtree(None), False), ('update_frames', lambda: (dev.set_kdtree(s.chain(9)), dev.update_frames(c.cs)), False),
+              ('refused', refused, False)]
+    first = None
+    for name, enter, has_tree in states:
+        enter()
+        got = trace(has_tree)
+        first = first or got
+        for form, (a, r, h) in got.items():
+            a0, r0, h0 = first[form]
+            assert h0.sum() > n and N.array_equal(h, h0), (name, form)
+            assert N.allclose(a, a0, rtol=1e-9, atol=1e-12) and N.allclose(r, r0, rtol=1e-9, atol=1e-12), (name, form)
+    dev.close()

@@ -34,6 +34,7 @@
 #include "trc_footprint.h"
 #include "trc_device.h"
 #include "trc_pool.h"
+#include "trc_scene_host.h"
 #include "trc_hithist.h"
 
 // ================================================================================================
@@ -301,6 +302,7 @@ class CounterBlock {
 public:
     int alloc() { TRC_TRY(d_.alloc(CNT_WORDS)); return zero(); }
     unsigned long long *device() const { return d_.get(); }
+    void fill(DScene &d) const { d.counters = d_.get(); d.energy_left = (double *)(d.counters + CNT_ENERGY_LEFT); }     // one 64-byte block: one read-back gets both
     // the block as a call finds it (read from the device only when the mirror is stale); the mirror is stale from here on
     int snapshot(CounterValues *v) {
         if (!mirror_ok_) TRC_TRY(fetch());
@@ -335,71 +337,307 @@ public:
     }
 };
 
-// what the scene's optics read that rays carry beyond the nine columns: the highest material row named by a surface between
-// tabulated materials (-1: none) and whether some wall is polychromatic.  Found once: optics do not change after creation.
-struct CarryNeeds {
-    int max_mat = -1;
-    bool poly = false;
-    bool any() const { return max_mat >= 0 || poly; }
+// The parts of a scene, one owner each.  A part keeps its device buffers to itself and is present whole or absent whole: a method
+// that changes one builds the new state beside the old -- host tables in copies, device buffers in locals -- and moves it in when
+// all of it is there, so a call that fails half way (out of memory) leaves the part as it was or empty, never new counts beside old
+// pointers.  fill() writes the part's slice of DScene and nothing else, facts() its slice of the facts trc_forms.h decides on; the
+// arithmetic they share with the host checks is trc_scene_host.h.
+
+// The surfaces as the caller described them, and their records, optics and flags on the device.
+class SceneSurfaces {
+    std::vector<trc_surface_desc> surfs_;
+    std::vector<double> extra_h_;
+    int32_t stride_ = 0, n_extra_ = 0;
+    bool splits_ = false;   // some optics can emit two rays per hit
+    CarryNeeds needs_;      // needs.any(): some optics read what only rays of a given bundle carry (complex indices, spectra)
+    DevBuf<double> d_recs_, d_opt_, d_extra_;
+    DevBuf<int32_t> d_sflags_;
+public:
+    int create(const trc_surface_desc *surfs, int32_t n, int32_t n_extra, const double *extra);
+    int upload();           // the records, optics and flags of the present poses
+    void set_frames(const double *frames12) {
+        for (size_t i = 0; i < surfs_.size(); ++i) memcpy(surfs_[i].frame, frames12 + 12 * i, 12 * sizeof(double));
+    }
+    const std::vector<trc_surface_desc> &all() const { return surfs_; }
+    const trc_surface_desc *data() const { return surfs_.data(); }
+    const trc_surface_desc &operator[](int i) const { return surfs_[i]; }
+    bool splits() const { return splits_; }
+    const CarryNeeds &needs() const { return needs_; }
+    void fill(DScene &d) const {
+        d.recs = d_recs_.get(); d.opt = d_opt_.get(); d.sflags = d_sflags_.get(); d.extra = d_extra_.get();
+        d.stride = stride_; d.n_surf = (int32_t)surfs_.size(); d.n_extra = n_extra_;
+    }
+    void facts(trc_scene_facts &s) const { s.stride = stride_; s.n_extra = n_extra_; s.splits = splits_; }
+};
+
+// The single-precision search tables of the fast engine (trc_bounds.h) on the host and on the device, and the caller's Kd-tree packed
+// beside them.  Absent (after a rebuild that failed): ok() false, every pointer null, and trc_forms.h decides for a scene without.
+class SearchTables {
+    trc_accel_host accel_{};
+    bool ok_ = false, kd_ok_ = false;
+    uint64_t geom_version_ = 0;     // bumped whenever the tables are rebuilt: what others derived from the old poses is stale
+    DevBuf<float> d_sbox_, d_obb_, d_bg_ent_;
+    DevBuf<uint32_t> d_nodes_, d_bg_off_, d_bg_occ_;
+    DevBuf<uint16_t> d_leaf_, d_bleaf_, d_goff_, d_glist_;
+    DevBuf<int32_t> d_unbounded_, d_gapart_, d_bg_apart_;
+    int build(const trc_surface_desc *surfs, int n);
+public:
+    // the tables of the surfaces' present poses; the packed Kd-tree described the old ones and goes
+    int rebuild(const trc_surface_desc *surfs, int n) {
+        const uint64_t version = geom_version_ + 1;
+        SearchTables t;
+        const int st = t.build(surfs, n);
+        *this = st == TRC_OK ? std::move(t) : SearchTables();
+        geom_version_ = version;
+        return st;
+    }
+    // the packed form of a tree trc_kd_check accepted, where it has one (else the float64 tree alone serves)
+    int pack_kd(const trc_kdtree_desc *kd) {
+        drop_kd();
+        if (!ok_ || !trc_accel_build_kd(kd, accel_)) return TRC_OK;
+        DevBuf<uint32_t> nodes;
+        DevBuf<uint16_t> leaf;
+        TRC_TRY(dev_upload(nodes, accel_.nodes.data(), accel_.nodes.size()));
+        TRC_TRY(dev_upload(leaf, accel_.leaf_surfs.data(), accel_.leaf_surfs.size()));
+        d_nodes_ = std::move(nodes); d_leaf_ = std::move(leaf);
+        kd_ok_ = true;
+        return TRC_OK;
+    }
+    void drop_kd() { d_nodes_.reset(); d_leaf_.reset(); kd_ok_ = false; }
+    const trc_accel_host &host() const { return accel_; }
+    uint64_t geom_version() const { return geom_version_; }
+    void fill(DScene &d) const;
+    void facts(trc_scene_facts &s) const { s.accel_ok = ok_; s.accel_kd_ok = kd_ok_; }
+};
+
+int SearchTables::build(const trc_surface_desc *surfs, int n) {
+    const char *ev = getenv("TRC_GRID_FORCE32");      // (measurements: the large grid for a scene the LDS-sized one holds)
+    trc_accel_host &A = accel_;
+    trc_search_tables_build(surfs, n, ev && atoi(ev), A);
+    // conservative single-precision boxes of the bounded surfaces
+    TRC_TRY(dev_upload(d_obb_, A.obb.data(), A.obb.size()));
+    TRC_TRY(dev_upload(d_bleaf_, A.brute_leaf.data(), A.brute_leaf.size()));
+    TRC_TRY(dev_upload(d_sbox_, A.sbox.data(), A.sbox.size()));
+    TRC_TRY(dev_upload(d_unbounded_, A.unbounded.data(), A.unbounded.size()));
+    if (A.grid_ok) {
+        TRC_TRY(dev_upload(d_gapart_, A.grid_apart.data(), A.grid_apart.size()));
+        TRC_TRY(dev_upload(d_goff_, A.grid_off.data(), A.grid_off.size()));
+        TRC_TRY(dev_upload(d_glist_, A.grid_list.data(), A.grid_list.size()));
+    } else if (A.big_ok) {      // a scene the LDS-sized grid cannot hold: the 32-bit grid in global memory
+        TRC_TRY(dev_upload(d_bg_off_, A.big_off.data(), A.big_off.size()));
+        TRC_TRY(dev_upload(d_bg_ent_, A.big_ent.data(), A.big_ent.size()));
+        TRC_TRY(dev_upload(d_bg_occ_, A.big_occ.data(), A.big_occ.size()));
+        std::vector<float>().swap(A.big_ent);       // (the host keeps the list itself, not its 48-byte entries)
+        TRC_TRY(d_bg_apart_.alloc(A.big_apart.size() + 1));
+        if (!A.big_apart.empty())
+            HIP_TRY(hipMemcpy(d_bg_apart_.get(), A.big_apart.data(), A.big_apart.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    ok_ = true;
+    return TRC_OK;
+}
+
+void SearchTables::fill(DScene &d) const {
+    if (!ok_) return;
+    const trc_accel_host &A = accel_;
+    d.a_sbox = d_sbox_.get(); d.a_obb = d_obb_.get(); d.a_nodes = d_nodes_.get(); d.a_leaf = d_leaf_.get(); d.a_unbounded = d_unbounded_.get();
+    d.a_n_unbounded = (int32_t)A.unbounded.size(); d.a_kd_depth = A.kd_depth;
+    d.a_bleaf = d_bleaf_.get(); d.a_n_bleaf = (int32_t)A.brute_leaf.size();
+    d.a_bnodes[0] = A.brute_nodes[0]; d.a_bnodes[1] = A.brute_nodes[1];
+    d.a_ok = 1; d.a_kd_ok = kd_ok_ ? 1 : 0;
+    d.a_delta = A.delta;
+    d.a_goff = d_goff_.get(); d.a_glist = d_glist_.get(); d.a_gapart = d_gapart_.get();
+    d.a_bg_off = d_bg_off_.get(); d.a_bg_occ = d_bg_occ_.get(); d.a_bg_ent = d_bg_ent_.get(); d.a_bg_ok = A.big_ok ? 1 : 0;
+    d.a_bg_apart = d_bg_apart_.get(); d.a_bg_napart = A.big_ok ? (int32_t)A.big_apart.size() : 0;
+    d.a_g_napart = A.grid_ok ? (int32_t)A.grid_apart.size() : 0;
+    d.a_g_ok = A.grid_ok ? 1 : 0;
+    d.a_g_ncell = A.grid_ok ? (int32_t)A.grid_off.size() - 1 : 0;
+    d.a_g_nlist = A.grid_ok ? (int32_t)A.grid_list.size() : 0;
+    for (int i = 0; i < 3; ++i) {
+        d.a_bg_dim[i] = A.big_ok ? A.big_dim[i] : 1;
+        d.a_bg_lo[i] = A.big_lo[i]; d.a_bg_cs[i] = A.big_cs[i]; d.a_bg_inv[i] = A.big_inv[i];
+        d.a_gdim[i] = A.grid_ok ? A.grid_dim[i] : 1;
+        d.a_glo[i] = A.grid_lo[i]; d.a_gcs[i] = A.grid_cs[i]; d.a_ginv[i] = A.grid_inv[i];
+        d.a_cen[i] = A.cen[i]; d.a_slo[i] = A.slo[i]; d.a_shi[i] = A.shi[i];
+    }
+    for (int i = 0; i < 6; ++i) {
+        d.a_broot[i] = A.brute_root[i]; d.a_root[i] = A.root[i];
+        d.a_bg_root[i] = A.big_ok ? A.big_root[i] : 0.0f; d.a_groot[i] = A.grid_ok ? A.grid_root[i] : 0.0f;
+    }
+}
+
+// The caller's Kd-tree as the float64 walks read it (k_trace_fast, k_ord_bounce): set() takes a tree trc_kd_check accepted.
+class KdTables {
+    DevBuf<int32_t> d_a_, d_b_, d_leaf_, d_always_;
+    DevBuf<double> d_split_;
+    int32_t nodes_ = 0, nleaf_ = 0, nalways_ = 0;
+    double bounds_[6] = {};
+    bool has_ = false;
+public:
+    int set(const trc_kdtree_desc *kd) {
+        std::vector<int32_t> a, b;
+        trc_kd_pack(kd, a, b);
+        KdTables t;
+        TRC_TRY(dev_upload(t.d_a_, a.data(), a.size()));
+        TRC_TRY(dev_upload(t.d_b_, b.data(), b.size()));
+        TRC_TRY(dev_upload(t.d_split_, kd->split, (size_t)kd->n_nodes));
+        TRC_TRY(dev_upload(t.d_leaf_, kd->leaf_surfs, (size_t)kd->n_leaf_surfs));
+        TRC_TRY(dev_upload(t.d_always_, kd->always_relevant, (size_t)kd->n_always));
+        t.nodes_ = kd->n_nodes; t.nleaf_ = kd->n_leaf_surfs; t.nalways_ = kd->n_always;
+        memcpy(t.bounds_, kd->bounds, sizeof(t.bounds_));
+        t.has_ = true;
+        *this = std::move(t);
+        return TRC_OK;
+    }
+    void clear() { *this = KdTables(); }
+    bool has() const { return has_; }
+    void fill(DScene &d) const {
+        d.has_kd = has_ ? 1 : 0;
+        d.kd_a = d_a_.get(); d.kd_b = d_b_.get(); d.kd_leaf = d_leaf_.get(); d.kd_always = d_always_.get();
+        d.kd_split = d_split_.get();
+        d.kd_nodes = nodes_; d.kd_nleaf = nleaf_; d.kd_nalways = nalways_;
+        for (int i = 0; i < 3; ++i) { d.kd_bmin[i] = bounds_[i]; d.kd_bmax[i] = bounds_[3 + i]; }
+    }
+    void facts(trc_scene_facts &s) const { s.has_kd = has_; s.kd_nodes = nodes_; s.kd_nleaf = nleaf_; s.kd_nalways = nalways_; }
+};
+
+// The tallies and the flux maps binned into them: the buffer (trc_tally_layout), the maps' descriptors, edges and surfaces on the
+// host and on the device.  add_map and set_transfer give a new buffer, zeroed; when they fail everything is as it was.
+class TallyBuffer {
+    DevBuf<double> d_tally_, d_fm_edges_;
+    int64_t n_ = 0, tr_off_ = -1;
+    std::vector<FluxMapDev> fms_h_;
+    std::vector<double> fm_edges_h_;
+    std::vector<int32_t> fm_of_surf_h_;
+    DevBuf<int32_t> d_fm_of_surf_;
+    DevBuf<FluxMapDev> d_fms_;
+    // these maps and this choice for the matrix: laid out, brought to the device, then taken
+    int commit(std::vector<FluxMapDev> fms, std::vector<double> edges, std::vector<int32_t> of_surf, bool transfer) {
+        const trc_tally_plan L = trc_tally_layout((int)of_surf.size(), fms.data(), fms.size(), transfer);
+        for (size_t k = 0; k < fms.size(); ++k) fms[k].bins = L.bins[k];
+        DevBuf<double> tally, d_edges;
+        DevBuf<int32_t> d_of;
+        DevBuf<FluxMapDev> d_fms;
+        TRC_TRY(tally.alloc((size_t)L.total));
+        HIP_TRY(hipMemset(tally.get(), 0, (size_t)L.total * sizeof(double)));
+        if (!fms.empty()) {
+            TRC_TRY(dev_upload(d_fms, fms.data(), fms.size()));
+            TRC_TRY(dev_upload(d_edges, edges.data(), edges.size()));
+        }
+        TRC_TRY(dev_upload(d_of, of_surf.data(), of_surf.size(), "upload failed"));
+        d_tally_ = std::move(tally); d_fm_edges_ = std::move(d_edges); d_fm_of_surf_ = std::move(d_of); d_fms_ = std::move(d_fms);
+        fms_h_.swap(fms); fm_edges_h_.swap(edges); fm_of_surf_h_.swap(of_surf);
+        n_ = L.total; tr_off_ = L.tr_off;
+        return TRC_OK;
+    }
+public:
+    int create(int32_t n_surf) { return commit({}, {}, std::vector<int32_t>((size_t)n_surf, -1), false); }
+    int add_map(int32_t surf, int32_t chart, int32_t nu, int32_t nv, const double *u_edges, const double *v_edges, const double *proj12) {
+        if (fm_of_surf_h_[surf] >= 0) return trc_fail(TRC_ERR_INVALID, "surface %d already has a flux map", surf);
+        std::vector<FluxMapDev> fms = fms_h_;
+        std::vector<double> edges = fm_edges_h_;
+        std::vector<int32_t> of_surf = fm_of_surf_h_;
+        FluxMapDev m;
+        m.surf = surf; m.nu = nu; m.nv = nv; m.chart = chart;
+        m.edges_u = (int64_t)edges.size();
+        edges.insert(edges.end(), u_edges, u_edges + nu + 1);
+        m.edges_v = (int64_t)edges.size();
+        edges.insert(edges.end(), v_edges, v_edges + nv + 1);
+        memcpy(m.proj, proj12, sizeof(m.proj));
+        m.bins = 0;
+        of_surf[surf] = (int32_t)fms.size();
+        fms.push_back(m);
+        return commit(std::move(fms), std::move(edges), std::move(of_surf), tr_off_ >= 0);
+    }
+    // flux-map bins keep their offsets (the matrix comes last)
+    int set_transfer(bool on) { return on == (tr_off_ >= 0) ? TRC_OK : commit(fms_h_, fm_edges_h_, fm_of_surf_h_, on); }
+    int zero() { HIP_TRY(hipMemset(d_tally_.get(), 0, (size_t)n_ * sizeof(double))); return TRC_OK; }
+    double *device() const { return d_tally_.get(); }
+    int64_t size() const { return n_; }
+    int64_t transfer_offset() const { return tr_off_; }     // -1: the matrix is not kept
+    const FluxMapDev *map_of(int32_t surf) const { return fm_of_surf_h_[surf] >= 0 ? &fms_h_[fm_of_surf_h_[surf]] : nullptr; }
+    // some flux map bins in another chart than XY: the call runs the CHART instances of the kernels that finish hits
+    bool has_chart() const { return std::any_of(fms_h_.begin(), fms_h_.end(), [](const FluxMapDev &m) { return m.chart != TRC_FM_XY; }); }
+    void fill(DScene &d) const {
+        d.tally = d_tally_.get();
+        d.fm_of_surf = d_fm_of_surf_.get(); d.fms = d_fms_.get(); d.fm_edges = d_fm_edges_.get();
+        d.tr_off = tr_off_;
+        d.n_fm = (int32_t)fms_h_.size(); d.n_fm_edges = (int32_t)fm_edges_h_.size();
+    }
+    void facts(trc_scene_facts &s) const {
+        s.n_fm_edges = (int)fm_edges_h_.size(); s.fms_bytes = (int)(fms_h_.size() * sizeof(FluxMapDev));
+        for (auto &m : fms_h_) s.fm_bins += (long long)m.nu * m.nv;
+        s.chart = has_chart();
+        s.transfer = tr_off_ >= 0;
+    }
+};
+
+// The source of the call in progress on the device, kept between calls: the descriptor with what the copy holds -- a Monte-Carlo
+// loop hands over the same descriptor every call (hipMalloc / hipFree per call cost more than the upload) -- and the packed
+// spectrum (FastParams.spec).
+class StagedSource {
+    DevBuf<trc_source_desc> d_src_;
+    trc_source_desc host_;
+    bool host_ok_ = false;
+    GrowBuf<double> d_spec_;
+public:
+    int source(const trc_source_desc *src, const trc_source_desc **d_src) {
+        if (!d_src_) { host_ok_ = false; TRC_TRY(d_src_.alloc(1)); }
+        if (!(host_ok_ && memcmp(&host_, src, sizeof(trc_source_desc)) == 0)) {
+            host_ok_ = false;
+            if (hipMemcpy(d_src_.get(), src, sizeof(trc_source_desc), hipMemcpyHostToDevice) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "source upload failed");
+            memcpy(&host_, src, sizeof(trc_source_desc));
+            host_ok_ = true;
+        }
+        *d_src = d_src_.get();
+        return TRC_OK;
+    }
+    int spectrum(const std::vector<double> &packed, const double **d_spec) {
+        TRC_TRY(d_spec_.reserve((size_t)3 + 3 * TRC_SPECTRUM_MAX_POINTS));     // (room for any table: allocated once)
+        // (the stream is idle between calls: every call ends with a synchronous read of its counters)
+        HIP_TRY(hipMemcpy(d_spec_.get(), packed.data(), packed.size() * 8, hipMemcpyHostToDevice));
+        *d_spec = d_spec_.get();
+        return TRC_OK;
+    }
 };
 
 struct trc_scene {
     trc_ctx *ctx;
-    int32_t n_surf, stride, n_extra;
-    std::vector<trc_surface_desc> surfs;
-    std::vector<double> extra_h;
-    bool splits;  // some optics can emit two rays per hit
-    CarryNeeds needs;   // needs.any(): some optics read what only rays of a given bundle carry (complex indices, spectra)
+    int32_t n_surf;
+    SceneSurfaces surfaces;
+    SearchTables search;
+    KdTables kd;
+    TallyBuffer tally;
+    StagedSource staged;
     // the tabulated materials of the scene's optics on the device (trc_scene_set_materials; trc_material_index's packed table, in
     // global memory: part of no LDS image), mat_tab_n of them (0: none).  A call that brings no trc_rays.mat reads them.
     DevBuf<double> d_mat_tab;
     int32_t mat_tab_n = 0;
-    bool mat_tab_serves() const { return needs.max_mat >= 0 && mat_tab_n > needs.max_mat; }
-    // device buffers
-    DevBuf<double> d_recs, d_opt, d_extra;
-    DevBuf<int32_t> d_sflags;
-    DevBuf<int32_t> d_kd_a, d_kd_b, d_kd_leaf, d_kd_always;
-    DevBuf<double> d_kd_split;
-    int32_t kd_nodes, kd_nleaf, kd_nalways;
-    double kd_bounds[6];
-    bool has_kd;
-    trc_accel_host accel;
-    bool accel_ok, accel_kd_ok;
-    DevBuf<float> d_a_sbox;
-    DevBuf<float> d_a_obb;
-    uint64_t geom_version;     // bumped whenever the surfaces are (re)uploaded: tables derived from their poses are stale
-    DevBuf<uint32_t> d_a_nodes;
-    DevBuf<uint16_t> d_a_leaf;
-    DevBuf<int32_t> d_a_unbounded;
-    DevBuf<uint16_t> d_a_bleaf;
-    DevBuf<uint16_t> d_a_goff, d_a_glist;
-    DevBuf<uint32_t> d_a_bg_off, d_a_bg_occ;
-    DevBuf<float> d_a_bg_ent;
-    DevBuf<int32_t> d_a_bg_apart;
-    DevBuf<int32_t> d_a_gapart;
+    bool mat_tab_serves() const { return surfaces.needs().max_mat >= 0 && mat_tab_n > surfaces.needs().max_mat; }
     std::unique_ptr<struct StreamEngine> stream_eng;   // slots of the streaming fast engine (trc_stream.inc), allocated on first use
     std::unique_ptr<struct OrdScratch> ord_scratch;    // scratch of the ordered engine's bounce loop, kept between calls
-    DevBuf<double> d_tally;
-    int64_t tally_n;
-    bool transfer_on;          // keep the transfer matrix (trc_scene_enable_transfer)
-    int64_t tr_off;
-    std::vector<FluxMapDev> fms_h;
-    std::vector<double> fm_edges_h;
-    std::vector<int32_t> fm_of_surf_h;
-    DevBuf<int32_t> d_fm_of_surf;
-    DevBuf<FluxMapDev> d_fms;
-    DevBuf<double> d_fm_edges;
     CounterBlock counters;
-    DevBuf<trc_source_desc> d_src_buf; // device copy of the source descriptor of the call in progress (kept between calls)
-    GrowBuf<double> d_spec_buf;        // device copy of the packed source spectrum of the call in progress (FastParams.spec)
-    trc_source_desc src_host;   // ... and what it holds (src_host_ok): a Monte-Carlo loop hands over the same descriptor every call
-    bool src_host_ok;
     GrowBuf<double> d_last[7];        // device side of trc_trace_fast's `last` bundle, kept between calls (seven hipMalloc / hipFree per
                                       // call were a millisecond of a Monte-Carlo loop's 1e6-ray calls)
     GrowBuf<double> d_last_x;         // ... and the spectra of the rays a source that carries its spectrum leaves (W rows)
     HitBuffer hits;
     double hist_ms = 0.0;             // device time of the last k_hist_hits (trc_scene_histogram_hits_ms)
 };
+
+// the device of the scene's context current and its stream idle: what every entry point that touches the scene's buffers from the
+// host begins with
+static int scene_quiet(const trc_scene *sc) {
+    HIP_TRY(hipSetDevice(sc->ctx->device));
+    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
+    return TRC_OK;
+}
+
+// the device view of the scene: every part writes its own slice
+static DScene make_dscene(const trc_scene *sc) {
+    DScene d;
+    memset(&d, 0, sizeof(d));
+    sc->surfaces.fill(d); sc->kd.fill(d); sc->search.fill(d); sc->tally.fill(d); sc->counters.fill(d); sc->hits.fill(d);
+    return d;
+}
 
 // what rays of the ordered engine carry beyond the nine columns: rows of one matrix `pay` (row r of ray i at pay[r * n + i]):
 // [Im of the refractive index] [Re, Im of each material at the ray's wavelength] [wavelengths of the spectrum] [spectrum]
@@ -667,24 +905,11 @@ __device__ __forceinline__ void fast_new_ray(const FastParams &P, const double *
 #undef MEGA_SUN
 #undef MEGA_LAMP
 
-// Some flux map of the scene bins in another chart than XY: the call runs the CHART instances of the kernels that finish hits
-static bool scene_has_chart_map(const trc_scene *sc) {
-    for (auto &m : sc->fms_h) if (m.chart != TRC_FM_XY) return true;
-    return false;
-}
-
 // What the decisions of trc_forms.h read of the scene.  walk: with the pass over the surfaces, which the streaming engine alone needs.
 static trc_scene_facts scene_facts(const trc_scene *sc, bool walk) {
     trc_scene_facts s = {};
-    trc_scene_facts_fill(sc->surfs.data(), sc->n_surf, sc->accel, walk, &s);
-    s.stride = sc->stride;
-    s.accel_ok = sc->accel_ok; s.accel_kd_ok = sc->accel_kd_ok; s.has_kd = sc->has_kd;
-    s.kd_nodes = sc->kd_nodes; s.kd_nleaf = sc->kd_nleaf; s.kd_nalways = sc->kd_nalways;
-    s.n_fm_edges = (int)sc->fm_edges_h.size(); s.fms_bytes = (int)(sc->fms_h.size() * sizeof(FluxMapDev)); s.n_extra = sc->n_extra;
-    for (auto &m : sc->fms_h) s.fm_bins += (long long)m.nu * m.nv;
-    s.chart = scene_has_chart_map(sc);
-    s.transfer = sc->tr_off >= 0;
-    s.splits = sc->splits;
+    trc_scene_facts_fill(sc->surfaces.data(), sc->n_surf, sc->search.host(), walk, &s);
+    sc->surfaces.facts(s); sc->search.facts(s); sc->kd.facts(s); sc->tally.facts(s);
     return s;
 }
 
@@ -1167,112 +1392,40 @@ extern "C" int trc_ctx_device_name(trc_ctx *ctx, char *buf, int buflen) {
 // C-ABI: scene
 // ================================================================================================
 static int validate_surface(const trc_surface_desc &s, int idx, int n_extra) {
-    if (s.gm_kind < 0 || s.gm_kind >= TRC_GM_KIND_COUNT)
-        return trc_fail(TRC_ERR_UNSUPPORTED, "surface %d: geometry kind %d is not in the native table", idx, s.gm_kind);
-    if (s.optics_kind < 0 || s.optics_kind >= TRC_OPT_KIND_COUNT)
-        return trc_fail(TRC_ERR_UNSUPPORTED, "surface %d: optics kind %d is not in the native table", idx, s.optics_kind);
-    if (s.optics_kind == TRC_OPT_REFRACTIVE_SCATTERING) {
-        if (s.opt[2] == 0.0) return trc_fail(TRC_ERR_UNSUPPORTED, "surface %d: scattering optics emit one ray per interaction (single_ray)", idx);
-        if (s.extra_off < 0 || s.extra_len < 4 || s.extra_off + s.extra_len > n_extra)
-            return trc_fail(TRC_ERR_INVALID, "surface %d: scattering optics need s_c1, s_c2, g1, g2 in the extra values", idx);
-        if (s.gm_kind == TRC_GM_RECT_PERFORATED || s.gm_kind == TRC_GM_POLYGON)
-            return trc_fail(TRC_ERR_UNSUPPORTED, "surface %d: scattering optics share the extra range with the geometry", idx);
-    }
-    bool opt_table = s.optics_kind == TRC_OPT_REFLECTIVE_SPECTRAL || s.optics_kind == TRC_OPT_LAMBERTIAN_DIRECTIONAL ||
-                     s.optics_kind == TRC_OPT_LAMBERTIAN_DIRECTIONAL_SPECTRAL || s.optics_kind == TRC_OPT_FRESNEL_CONDUCTOR ||
-                     s.optics_kind == TRC_OPT_LAMBERTIAN_POLYCHROMATIC;
-    if (s.optics_kind == TRC_OPT_REFRACTIVE_MATERIAL && (s.opt[4] < 0 || s.opt[5] < 0 || s.opt[4] >= 64 || s.opt[5] >= 64))
-        return trc_fail(TRC_ERR_INVALID, "surface %d: material rows out of range", idx);
-    bool needs_extra = s.gm_kind == TRC_GM_RECT_PERFORATED || opt_table;
-    if (needs_extra && (s.extra_off < 0 || s.extra_len <= 0 || s.extra_off + s.extra_len > n_extra))
-        return trc_fail(TRC_ERR_INVALID, "surface %d: extra range [%d,+%d) outside the %d extra values", idx,
-                        s.extra_off, s.extra_len, n_extra);
-    if (s.gm_kind == TRC_GM_RECT_PERFORATED && opt_table)
-        return trc_fail(TRC_ERR_UNSUPPORTED, "surface %d: perforated plate with spectral optics shares one extra range", idx);
-    // reference argument checks (flat_surface.py:192-195, :470-480; sphere_surface.py:31-32; cone.py:82-83)
-    const double *g = s.gm;
-    switch (s.gm_kind) {
-    case TRC_GM_RECT: case TRC_GM_RECT_EXTRUDED: case TRC_GM_RECT_PERFORATED:
-        if (!(g[0] > 0) || !(g[1] > 0)) return trc_fail(TRC_ERR_INVALID, "surface %d: width and height must be positive", idx);
-        break;
-    case TRC_GM_ROUND: case TRC_GM_ROUND_CUT:
-        if (!(g[0] > 0)) return trc_fail(TRC_ERR_INVALID, "surface %d: radius must be positive", idx);
-        if (g[1] >= 0 && !(g[1] < g[0])) return trc_fail(TRC_ERR_INVALID, "surface %d: inner radius must be lower than the outer one", idx);
-        break;
-    case TRC_GM_SPHERE: case TRC_GM_HEMISPHERE: case TRC_GM_SPHERE_RECT: case TRC_GM_SPHERE_CUT:
-        if (!(g[0] > 0)) return trc_fail(TRC_ERR_INVALID, "surface %d: radius must be positive", idx);
-        break;
-    default: break;
-    }
-    return TRC_OK;
+    char why[512];
+    const int st = trc_surface_check(s, idx, n_extra, why, sizeof(why));
+    return st == TRC_OK ? TRC_OK : trc_fail(st, "%s", why);
 }
 
-static void pack_record(const trc_surface_desc &s, double *rec, int stride) {
-    for (int i = 0; i < stride; ++i) rec[i] = 0.0;
-    for (int r = 0; r < 3; ++r) {
-        for (int k = 0; k < 3; ++k) rec[3 * r + k] = s.frame[4 * r + k];
-        rec[9 + r] = s.frame[4 * r + 3];
-    }
-    int32_t *h = (int32_t *)(rec + 12);
-    h[0] = s.gm_kind; h[1] = s.optics_kind; h[2] = s.extra_off; h[3] = s.extra_len;
-    int np = trc_gm_nparams(s.gm_kind);
-    for (int i = 0; i < np; ++i) rec[TRC_REC_HDR + i] = s.gm[i];
+int SceneSurfaces::create(const trc_surface_desc *surfs, int32_t n, int32_t n_extra, const double *extra) {
+    stride_ = trc_scene_stride(surfs, n);
+    trc_scene_scan(surfs, n, &splits_, &needs_);
+    n_extra_ = n_extra;
+    surfs_.assign(surfs, surfs + n);
+    if (n_extra > 0 && extra) extra_h_.assign(extra, extra + n_extra);
+    TRC_TRY(d_recs_.alloc((size_t)n * stride_));
+    TRC_TRY(d_opt_.alloc((size_t)n * 8));
+    TRC_TRY(d_sflags_.alloc((size_t)n));
+    TRC_TRY(d_extra_.alloc((size_t)n_extra));
+    if (n_extra > 0 && hipMemcpy(d_extra_.get(), extra_h_.data(), (size_t)n_extra * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return trc_fail(TRC_ERR_DEVICE, "extra upload failed");
+    return upload();
 }
 
-static int scene_upload_surfaces(trc_scene *sc) {
-    std::vector<double> recs((size_t)sc->n_surf * sc->stride), opt((size_t)sc->n_surf * 8);
-    std::vector<int32_t> flags(sc->n_surf);
-    for (int i = 0; i < sc->n_surf; ++i) {
-        pack_record(sc->surfs[i], recs.data() + (size_t)i * sc->stride, sc->stride);
-        for (int k = 0; k < 8; ++k) opt[(size_t)i * 8 + k] = sc->surfs[i].opt[k];
-        flags[i] = sc->surfs[i].flags & 0xFFFF;
-        if (surface_ends_every_ray(sc->surfs[i])) flags[i] |= TRC_SURF_TERMINAL;
-        flags[i] |= trc_shade_class_of(sc->surfs[i]) << TRC_SURF_CLS_SHIFT;      // which shading kernel of the streaming engine serves the surface
+int SceneSurfaces::upload() {
+    const size_t n = surfs_.size();
+    std::vector<double> recs(n * stride_), opt(n * 8);
+    std::vector<int32_t> flags(n);
+    for (size_t i = 0; i < n; ++i) {
+        trc_pack_record(surfs_[i], recs.data() + i * stride_, stride_);
+        for (int k = 0; k < 8; ++k) opt[i * 8 + k] = surfs_[i].opt[k];
+        flags[i] = surfs_[i].flags & 0xFFFF;
+        if (surface_ends_every_ray(surfs_[i])) flags[i] |= TRC_SURF_TERMINAL;
+        flags[i] |= trc_shade_class_of(surfs_[i]) << TRC_SURF_CLS_SHIFT;      // which shading kernel of the streaming engine serves the surface
     }
-    HIP_TRY(hipMemcpy(sc->d_recs.get(), recs.data(), recs.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(sc->d_opt.get(), opt.data(), opt.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(sc->d_sflags.get(), flags.data(), flags.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    // conservative single-precision boxes of the bounded surfaces (fast engine)
-    trc_accel_build_surfaces(sc->surfs.data(), sc->n_surf, sc->accel);
-    sc->geom_version += 1;
-    TRC_TRY(dev_upload(sc->d_a_obb, sc->accel.obb.data(), sc->accel.obb.size()));
-    TRC_TRY(dev_upload(sc->d_a_bleaf, sc->accel.brute_leaf.data(), sc->accel.brute_leaf.size()));
-    TRC_TRY(dev_upload(sc->d_a_sbox, sc->accel.sbox.data(), sc->accel.sbox.size()));
-    TRC_TRY(dev_upload(sc->d_a_unbounded, sc->accel.unbounded.data(), sc->accel.unbounded.size()));
-    trc_accel_build_grid(sc->accel, sc->n_surf);
-    { const char *ev = getenv("TRC_GRID_FORCE32"); if (ev && atoi(ev)) sc->accel.grid_ok = false; }      // (measurements: the large grid for a scene the LDS-sized one holds)
-    sc->d_a_goff.reset(); sc->d_a_glist.reset(); sc->d_a_gapart.reset();
-    if (sc->accel.grid_ok) {
-        TRC_TRY(dev_upload(sc->d_a_gapart, sc->accel.grid_apart.data(), sc->accel.grid_apart.size()));
-        TRC_TRY(dev_upload(sc->d_a_goff, sc->accel.grid_off.data(), sc->accel.grid_off.size()));
-        TRC_TRY(dev_upload(sc->d_a_glist, sc->accel.grid_list.data(), sc->accel.grid_list.size()));
-    }
-    sc->d_a_bg_off.reset(); sc->d_a_bg_occ.reset(); sc->d_a_bg_ent.reset(); sc->d_a_bg_apart.reset();
-    if (!sc->accel.grid_ok) {      // a scene the LDS-sized grid cannot hold: the 32-bit grid in global memory
-        trc_accel_build_grid32(sc->surfs.data(), sc->n_surf, sc->accel);
-        if (sc->accel.big_ok) {
-            TRC_TRY(dev_upload(sc->d_a_bg_off, sc->accel.big_off.data(), sc->accel.big_off.size()));
-            TRC_TRY(dev_upload(sc->d_a_bg_ent, sc->accel.big_ent.data(), sc->accel.big_ent.size()));
-            TRC_TRY(dev_upload(sc->d_a_bg_occ, sc->accel.big_occ.data(), sc->accel.big_occ.size()));
-            std::vector<float>().swap(sc->accel.big_ent);       // (the host keeps the list itself, not its 48-byte entries)
-            TRC_TRY(sc->d_a_bg_apart.alloc(sc->accel.big_apart.size() + 1));
-            if (!sc->accel.big_apart.empty())
-                HIP_TRY(hipMemcpy(sc->d_a_bg_apart.get(), sc->accel.big_apart.data(), sc->accel.big_apart.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-    }
-    sc->accel_ok = true;
-    sc->accel_kd_ok = false;   // packed Kd nodes are relative to the scene centre: rebuilt by trc_scene_set_kdtree
-    return TRC_OK;
-}
-
-static int scene_alloc_tally(trc_scene *sc) {
-    int64_t n = 3 * (int64_t)sc->n_surf + 2;
-    for (auto &m : sc->fms_h) { m.bins = n; n += (int64_t)m.nu * m.nv; }
-    sc->tr_off = -1;
-    if (sc->transfer_on) { sc->tr_off = n; n += ((int64_t)sc->n_surf + 1) * sc->n_surf; }
-    sc->tally_n = n;
-    TRC_TRY(sc->d_tally.alloc((size_t)n));
-    HIP_TRY(hipMemset(sc->d_tally.get(), 0, (size_t)n * sizeof(double)));
+    HIP_TRY(hipMemcpy(d_recs_.get(), recs.data(), recs.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_opt_.get(), opt.data(), opt.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_sflags_.get(), flags.data(), flags.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     return TRC_OK;
 }
 
@@ -1282,44 +1435,15 @@ extern "C" int trc_scene_create(trc_ctx *ctx, int32_t n_surf, const trc_surface_
     if (n_surf >= (1 << 28)) return trc_fail(TRC_ERR_INVALID, "too many surfaces");
     *out = nullptr;
     HIP_TRY(hipSetDevice(ctx->device));
-    int max_np = 0;
-    bool splits = false;
-    CarryNeeds needs;
-    for (int i = 0; i < n_surf; ++i) {
-        TRC_TRY(validate_surface(surfs[i], i, n_extra));
-        int np = trc_gm_nparams(surfs[i].gm_kind);
-        if (np > max_np) max_np = np;
-        if (surfs[i].optics_kind == TRC_OPT_REFRACTIVE_HOMOGENOUS && surfs[i].opt[2] == 0.0) splits = true;
-        if (surfs[i].optics_kind == TRC_OPT_REFRACTIVE_MATERIAL && surfs[i].opt[0] == 0.0) splits = true;
-        if (surfs[i].optics_kind == TRC_OPT_REFRACTIVE_MATERIAL) needs.max_mat = std::max(needs.max_mat, std::max((int)surfs[i].opt[4], (int)surfs[i].opt[5]));
-        if (surfs[i].optics_kind == TRC_OPT_LAMBERTIAN_POLYCHROMATIC) needs.poly = true;
-    }
+    for (int i = 0; i < n_surf; ++i) TRC_TRY(validate_surface(surfs[i], i, n_extra));
     std::unique_ptr<trc_scene> sc(new (std::nothrow) trc_scene());
     if (!sc) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
     sc->ctx = ctx;
-    sc->src_host_ok = false;
     sc->n_surf = n_surf;
-    sc->stride = TRC_REC_HDR + max_np;
-    if ((sc->stride & 1) == 0) sc->stride += 1;  // odd number of doubles: spreads records over LDS banks
-    sc->n_extra = n_extra;
-    sc->surfs.assign(surfs, surfs + n_surf);
-    if (n_extra > 0 && extra) sc->extra_h.assign(extra, extra + n_extra);
-    sc->splits = splits;
-    sc->needs = needs;
-    sc->has_kd = false;
-    sc->fm_of_surf_h.assign(n_surf, -1);
-    TRC_TRY(sc->d_recs.alloc((size_t)n_surf * sc->stride));
-    TRC_TRY(sc->d_opt.alloc((size_t)n_surf * 8));
-    TRC_TRY(sc->d_sflags.alloc((size_t)n_surf));
-    TRC_TRY(sc->d_extra.alloc((size_t)n_extra));
-    TRC_TRY(sc->d_fm_of_surf.alloc((size_t)n_surf));
     TRC_TRY(sc->counters.alloc());
-    TRC_TRY(scene_upload_surfaces(sc.get()));
-    if (n_extra > 0 && hipMemcpy(sc->d_extra.get(), sc->extra_h.data(), (size_t)n_extra * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-        return trc_fail(TRC_ERR_DEVICE, "extra upload failed");
-    if (hipMemcpy(sc->d_fm_of_surf.get(), sc->fm_of_surf_h.data(), (size_t)n_surf * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
-        return trc_fail(TRC_ERR_DEVICE, "upload failed");
-    TRC_TRY(scene_alloc_tally(sc.get()));
+    TRC_TRY(sc->surfaces.create(surfs, n_surf, n_extra, extra));
+    TRC_TRY(sc->search.rebuild(surfs, n_surf));
+    TRC_TRY(sc->tally.create(n_surf));
     *out = sc.release();
     return TRC_OK;
 }
@@ -1334,66 +1458,26 @@ extern "C" int trc_scene_destroy(trc_scene *sc) {
 
 extern "C" int trc_scene_update_frames(trc_scene *sc, int32_t n_surf, const double *frames12) {
     if (!sc || !frames12 || n_surf != sc->n_surf) return trc_fail(TRC_ERR_INVALID, "trc_scene_update_frames: bad arguments");
-    HIP_TRY(hipSetDevice(sc->ctx->device));
-    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    for (int i = 0; i < n_surf; ++i) memcpy(sc->surfs[i].frame, frames12 + 12 * (size_t)i, 12 * sizeof(double));
-    sc->has_kd = false;        // a Kd-tree set before described the old poses: the caller sets a new one (or does without)
-    return scene_upload_surfaces(sc);
+    TRC_TRY(scene_quiet(sc));
+    sc->surfaces.set_frames(frames12);
+    sc->kd.clear();            // a Kd-tree set before described the old poses: the caller sets a new one (or does without)
+    TRC_TRY(sc->surfaces.upload());
+    return sc->search.rebuild(sc->surfaces.data(), n_surf);
 }
 
 extern "C" int trc_scene_set_kdtree(trc_scene *sc, const trc_kdtree_desc *kd) {
     if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
-    HIP_TRY(hipSetDevice(sc->ctx->device));
-    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    sc->d_kd_a.reset(); sc->d_kd_b.reset(); sc->d_kd_leaf.reset(); sc->d_kd_always.reset(); sc->d_kd_split.reset();
-    sc->has_kd = false;
-    sc->accel_kd_ok = false;
+    TRC_TRY(scene_quiet(sc));
+    sc->kd.clear();
+    sc->search.drop_kd();
     if (!kd) return TRC_OK;
-    if (kd->n_nodes <= 0 || !kd->flag || !kd->split || !kd->child || !kd->leaf_off || !kd->leaf_cnt)
-        return trc_fail(TRC_ERR_INVALID, "trc_scene_set_kdtree: incomplete tree");
-    if (kd->n_nodes >= (1 << 29) || kd->n_leaf_surfs >= (1 << 29)) return trc_fail(TRC_ERR_INVALID, "tree too large");
-    std::vector<int32_t> a(kd->n_nodes), b(kd->n_nodes);
-    // validate and measure depth (the traversal stack is TRC_KD_STACK deep)
-    std::vector<int32_t> depth(kd->n_nodes, 0);
-    int max_depth = 0;
-    for (int i = 0; i < kd->n_nodes; ++i) {
-        int f = kd->flag[i];
-        if (f < 0 || f > 3) return trc_fail(TRC_ERR_INVALID, "node %d: flag %d", i, f);
-        if (f == 3) {
-            int off = kd->leaf_off[i], cnt = kd->leaf_cnt[i];
-            if (off < 0 || cnt < 0 || off + cnt > kd->n_leaf_surfs) return trc_fail(TRC_ERR_INVALID, "node %d: leaf range", i);
-            for (int k = 0; k < cnt; ++k) {
-                int s = kd->leaf_surfs[off + k];
-                if (s < 0 || s >= sc->n_surf) return trc_fail(TRC_ERR_INVALID, "node %d: surface %d out of range", i, s);
-            }
-            a[i] = (off << 2) | 3; b[i] = cnt;
-        } else {
-            int c = kd->child[i];
-            if (c <= i || c + 1 >= kd->n_nodes) return trc_fail(TRC_ERR_INVALID, "node %d: child %d out of range", i, c);
-            a[i] = (c << 2) | f; b[i] = 0;
-            depth[c] = depth[c + 1] = depth[i] + 1;
-            if (depth[c] > max_depth) max_depth = depth[c];
-        }
-    }
-    if (max_depth > TRC_KD_STACK) return trc_fail(TRC_ERR_UNSUPPORTED, "Kd-tree depth %d exceeds the traversal stack (%d)", max_depth, TRC_KD_STACK);
-    for (int k = 0; k < kd->n_always; ++k)
-        if (kd->always_relevant[k] < 0 || kd->always_relevant[k] >= sc->n_surf) return trc_fail(TRC_ERR_INVALID, "always_relevant out of range");
-    TRC_TRY(dev_upload(sc->d_kd_a, a.data(), a.size()));
-    TRC_TRY(dev_upload(sc->d_kd_b, b.data(), b.size()));
-    TRC_TRY(dev_upload(sc->d_kd_split, kd->split, (size_t)kd->n_nodes));
-    TRC_TRY(dev_upload(sc->d_kd_leaf, kd->leaf_surfs, (size_t)kd->n_leaf_surfs));
-    TRC_TRY(dev_upload(sc->d_kd_always, kd->always_relevant, (size_t)kd->n_always));
-    sc->kd_nodes = kd->n_nodes; sc->kd_nleaf = kd->n_leaf_surfs; sc->kd_nalways = kd->n_always;
-    memcpy(sc->kd_bounds, kd->bounds, sizeof(sc->kd_bounds));
-    sc->has_kd = true;
-    sc->d_a_nodes.reset(); sc->d_a_leaf.reset();
-    sc->accel_kd_ok = false;
-    if (sc->accel_ok && trc_accel_build_kd(kd, sc->accel)) {
-        TRC_TRY(dev_upload(sc->d_a_nodes, sc->accel.nodes.data(), sc->accel.nodes.size()));
-        TRC_TRY(dev_upload(sc->d_a_leaf, sc->accel.leaf_surfs.data(), sc->accel.leaf_surfs.size()));
-        sc->accel_kd_ok = true;
-    }
-    return TRC_OK;
+    char why[160] = "";
+    int depth = 0;
+    const int st = trc_kd_check(kd, sc->n_surf, &depth, why, sizeof(why));
+    if (st != TRC_OK) return trc_fail(st, "trc_scene_set_kdtree: %s", why);
+    if (depth > TRC_KD_STACK) return trc_fail(TRC_ERR_UNSUPPORTED, "Kd-tree depth %d exceeds the traversal stack (%d)", depth, TRC_KD_STACK);
+    TRC_TRY(sc->kd.set(kd));
+    return sc->search.pack_kd(kd);
 }
 
 extern "C" int trc_scene_set_fluxmap(trc_scene *sc, int32_t surf, int32_t nu, int32_t nv, const double *u_edges,
@@ -1406,39 +1490,21 @@ extern "C" int trc_scene_set_fluxmap_chart(trc_scene *sc, int32_t surf, int32_t 
     if (!sc || surf < 0 || surf >= sc->n_surf || nu <= 0 || nv <= 0 || !u_edges || !v_edges || !proj12)
         return trc_fail(TRC_ERR_INVALID, "trc_scene_set_fluxmap_chart: bad arguments");
     if (chart < 0 || chart >= TRC_FM_CHARTS) return trc_fail(TRC_ERR_INVALID, "trc_scene_set_fluxmap_chart: unknown chart %d", chart);
-    HIP_TRY(hipSetDevice(sc->ctx->device));
-    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
+    TRC_TRY(scene_quiet(sc));
     for (int i = 0; i < nu; ++i) if (!(u_edges[i + 1] > u_edges[i])) return trc_fail(TRC_ERR_INVALID, "u edges must increase");
     for (int i = 0; i < nv; ++i) if (!(v_edges[i + 1] > v_edges[i])) return trc_fail(TRC_ERR_INVALID, "v edges must increase");
-    if (sc->fm_of_surf_h[surf] >= 0) return trc_fail(TRC_ERR_INVALID, "surface %d already has a flux map", surf);
-    FluxMapDev m;
-    m.surf = surf; m.nu = nu; m.nv = nv; m.chart = chart;
-    m.edges_u = (int64_t)sc->fm_edges_h.size();
-    sc->fm_edges_h.insert(sc->fm_edges_h.end(), u_edges, u_edges + nu + 1);
-    m.edges_v = (int64_t)sc->fm_edges_h.size();
-    sc->fm_edges_h.insert(sc->fm_edges_h.end(), v_edges, v_edges + nv + 1);
-    memcpy(m.proj, proj12, sizeof(m.proj));
-    m.bins = 0;
-    sc->fm_of_surf_h[surf] = (int32_t)sc->fms_h.size();
-    sc->fms_h.push_back(m);
-    TRC_TRY(scene_alloc_tally(sc));  // resets the tallies
-    TRC_TRY(dev_upload(sc->d_fms, sc->fms_h.data(), sc->fms_h.size()));
-    TRC_TRY(dev_upload(sc->d_fm_edges, sc->fm_edges_h.data(), sc->fm_edges_h.size()));
-    HIP_TRY(hipMemcpy(sc->d_fm_of_surf.get(), sc->fm_of_surf_h.data(), (size_t)sc->n_surf * sizeof(int32_t), hipMemcpyHostToDevice));
-    return TRC_OK;
+    return sc->tally.add_map(surf, chart, nu, nv, u_edges, v_edges, proj12);     // resets the tallies
 }
 
 // the cursor of the hit buffer once the context's stream has finished, for what goes on to work on the buffer
 static int scene_hit_cursor(trc_scene *sc, unsigned long long *cursor) {
-    HIP_TRY(hipSetDevice(sc->ctx->device));
-    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
+    TRC_TRY(scene_quiet(sc));
     return sc->counters.hit_cursor(cursor);
 }
 
 extern "C" int trc_scene_set_hit_capacity(trc_scene *sc, int64_t capacity) {
     if (!sc || capacity < 0) return trc_fail(TRC_ERR_INVALID, "bad arguments");
-    HIP_TRY(hipSetDevice(sc->ctx->device));
-    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
+    TRC_TRY(scene_quiet(sc));
     TRC_TRY(sc->counters.restart_hits());
     return sc->hits.set_capacity(capacity);
 }
@@ -1548,20 +1614,18 @@ extern "C" int trc_scene_clear_hits(trc_scene *sc) {
 
 extern "C" int trc_scene_reset_tallies(trc_scene *sc) {
     if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
-    HIP_TRY(hipSetDevice(sc->ctx->device));
-    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    HIP_TRY(hipMemset(sc->d_tally.get(), 0, (size_t)sc->tally_n * sizeof(double)));
+    TRC_TRY(scene_quiet(sc));
+    TRC_TRY(sc->tally.zero());
     TRC_TRY(sc->counters.zero());
     return sc->hits.reset();
 }
 
 extern "C" int trc_scene_get_tallies(trc_scene *sc, double *absorbed, double *received, int64_t *hits) {
     if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
-    HIP_TRY(hipSetDevice(sc->ctx->device));
-    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
+    TRC_TRY(scene_quiet(sc));
     const int S = sc->n_surf;
     std::vector<double> t((size_t)3 * S);
-    HIP_TRY(hipMemcpy(t.data(), sc->d_tally.get(), t.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(t.data(), sc->tally.device(), t.size() * sizeof(double), hipMemcpyDeviceToHost));
     for (int i = 0; i < S; ++i) {
         if (absorbed) absorbed[i] = t[i];
         if (received) received[i] = t[S + i];
@@ -1572,12 +1636,10 @@ extern "C" int trc_scene_get_tallies(trc_scene *sc, double *absorbed, double *re
 
 extern "C" int trc_scene_get_fluxmap(trc_scene *sc, int32_t surf, double *out) {
     if (!sc || surf < 0 || surf >= sc->n_surf || !out) return trc_fail(TRC_ERR_INVALID, "bad arguments");
-    int fm = sc->fm_of_surf_h[surf];
-    if (fm < 0) return trc_fail(TRC_ERR_INVALID, "surface %d has no flux map", surf);
-    HIP_TRY(hipSetDevice(sc->ctx->device));
-    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    const FluxMapDev &m = sc->fms_h[fm];
-    HIP_TRY(hipMemcpy(out, sc->d_tally.get() + m.bins, (size_t)m.nu * m.nv * sizeof(double), hipMemcpyDeviceToHost));
+    const FluxMapDev *m = sc->tally.map_of(surf);
+    if (!m) return trc_fail(TRC_ERR_INVALID, "surface %d has no flux map", surf);
+    TRC_TRY(scene_quiet(sc));
+    HIP_TRY(hipMemcpy(out, sc->tally.device() + m->bins, (size_t)m->nu * m->nv * sizeof(double), hipMemcpyDeviceToHost));
     return TRC_OK;
 }
 
@@ -1647,7 +1709,7 @@ static int scene_get_hits(trc_scene *sc, int64_t *n, int32_t *surf, double *e_ab
     unsigned long long cursor;
     TRC_TRY(scene_hit_cursor(sc, &cursor));
     double *const dst[8] = {e_abs, e_in, px, py, pz, dx, dy, dz};
-    return sc->hits.read(sc->ctx->stream, sc->surfs, sc->d_sflags.get(), cursor, n, surf, dst, n_x, x_out);
+    return sc->hits.read(sc->ctx->stream, sc->surfaces.all(), make_dscene(sc).sflags, cursor, n, surf, dst, n_x, x_out);
 }
 
 // the written entries of [0, cursor): n of them, and the columns whose destinations are given
@@ -1767,8 +1829,7 @@ __global__ __launch_bounds__(256) void k_material_eval(const double *tab, int n_
 extern "C" int trc_scene_set_materials(trc_scene *sc, int32_t n_mat, const int32_t *n_points, const double *packed) {
     if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
     if (n_mat < 0 || n_mat > TRC_MATERIAL_MAX) return trc_fail(TRC_ERR_INVALID, "trc_scene_set_materials: between 0 and %d materials", TRC_MATERIAL_MAX);
-    HIP_TRY(hipSetDevice(sc->ctx->device));
-    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
+    TRC_TRY(scene_quiet(sc));
     if (n_mat == 0) { sc->mat_tab_n = 0; sc->d_mat_tab.reset(); return TRC_OK; }
     if (!n_points || !packed) return trc_fail(TRC_ERR_INVALID, "trc_scene_set_materials: n_points and packed are required");
     // the caller's wl[n] | re[n] | im[n] per material, one after the other -> trc_material_index's table
@@ -1911,7 +1972,7 @@ extern "C" int trc_scene_histogram_hits(trc_scene *sc, const trc_hit_hist_desc *
     const bool full = TRC_HH_IS_DIR(d->chart) || d->weight == TRC_HH_INCIDENT;
     bool captures = false;
     for (int s = d->surf_lo; s <= d->surf_hi; ++s) {
-        const int32_t fl = sc->surfs[s].flags;
+        const int32_t fl = sc->surfaces[s].flags;
         if (!(fl & TRC_SURF_CAPTURE_HITS)) continue;
         captures = true;
         if (full && (fl & TRC_SURF_CAPTURE_LEAN))
@@ -1980,90 +2041,38 @@ extern "C" int trc_scene_enable_transfer(trc_scene *sc, int32_t on) {
     if (!sc) return trc_fail(TRC_ERR_INVALID, "scene is NULL");
     if (on && sc->n_surf > TRC_TRANSFER_MAX_SURF)
         return trc_fail(TRC_ERR_CAPACITY, "the transfer matrix is offered up to %d surfaces (scene has %d)", TRC_TRANSFER_MAX_SURF, sc->n_surf);
-    HIP_TRY(hipSetDevice(sc->ctx->device));
-    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    if ((on != 0) == sc->transfer_on) return TRC_OK;
-    sc->transfer_on = on != 0;
-    TRC_TRY(scene_alloc_tally(sc));      // resets the tallies; flux-map bins keep their offsets (the matrix comes last)
-    if (!sc->fms_h.empty()) HIP_TRY(hipMemcpy(sc->d_fms.get(), sc->fms_h.data(), sc->fms_h.size() * sizeof(FluxMapDev), hipMemcpyHostToDevice));
-    return TRC_OK;
+    TRC_TRY(scene_quiet(sc));
+    return sc->tally.set_transfer(on != 0);       // (a change resets the tallies)
 }
 
 extern "C" int trc_scene_get_transfer(trc_scene *sc, double *out) {
     if (!sc || !out) return trc_fail(TRC_ERR_INVALID, "bad arguments");
-    if (!sc->transfer_on) return trc_fail(TRC_ERR_INVALID, "the transfer matrix is not enabled (trc_scene_enable_transfer)");
-    HIP_TRY(hipSetDevice(sc->ctx->device));
-    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    HIP_TRY(hipMemcpy(out, sc->d_tally.get() + sc->tr_off, (size_t)(sc->n_surf + 1) * sc->n_surf * sizeof(double), hipMemcpyDeviceToHost));
+    if (sc->tally.transfer_offset() < 0) return trc_fail(TRC_ERR_INVALID, "the transfer matrix is not enabled (trc_scene_enable_transfer)");
+    TRC_TRY(scene_quiet(sc));
+    HIP_TRY(hipMemcpy(out, sc->tally.device() + sc->tally.transfer_offset(), (size_t)(sc->n_surf + 1) * sc->n_surf * sizeof(double), hipMemcpyDeviceToHost));
     return TRC_OK;
 }
 
 extern "C" int trc_scene_tally_size(trc_scene *sc, int64_t *n_doubles) {
     if (!sc || !n_doubles) return trc_fail(TRC_ERR_INVALID, "bad arguments");
-    *n_doubles = sc->tally_n;
+    *n_doubles = sc->tally.size();
     return TRC_OK;
 }
 
 extern "C" int trc_scene_export_tallies(trc_scene *sc, double *dst, int32_t on_device) {
     if (!sc || !dst) return trc_fail(TRC_ERR_INVALID, "bad arguments");
-    HIP_TRY(hipSetDevice(sc->ctx->device));
-    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    HIP_TRY(hipMemcpy(dst, sc->d_tally.get(), (size_t)sc->tally_n * sizeof(double),
+    TRC_TRY(scene_quiet(sc));
+    HIP_TRY(hipMemcpy(dst, sc->tally.device(), (size_t)sc->tally.size() * sizeof(double),
                       on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
     return TRC_OK;
 }
 
 extern "C" int trc_scene_import_tallies(trc_scene *sc, const double *src, int32_t on_device) {
     if (!sc || !src) return trc_fail(TRC_ERR_INVALID, "bad arguments");
-    HIP_TRY(hipSetDevice(sc->ctx->device));
-    HIP_TRY(hipStreamSynchronize(sc->ctx->stream));
-    HIP_TRY(hipMemcpy(sc->d_tally.get(), src, (size_t)sc->tally_n * sizeof(double),
+    TRC_TRY(scene_quiet(sc));
+    HIP_TRY(hipMemcpy(sc->tally.device(), src, (size_t)sc->tally.size() * sizeof(double),
                       on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     return TRC_OK;
-}
-
-static DScene make_dscene(trc_scene *sc) {
-    DScene d;
-    memset(&d, 0, sizeof(d));
-    d.recs = sc->d_recs.get(); d.opt = sc->d_opt.get(); d.sflags = sc->d_sflags.get(); d.extra = sc->d_extra.get();
-    d.stride = sc->stride; d.n_surf = sc->n_surf; d.n_extra = sc->n_extra; d.has_kd = sc->has_kd ? 1 : 0;
-    d.kd_a = sc->d_kd_a.get(); d.kd_b = sc->d_kd_b.get(); d.kd_leaf = sc->d_kd_leaf.get(); d.kd_always = sc->d_kd_always.get();
-    d.kd_split = sc->d_kd_split.get();
-    d.kd_nodes = sc->kd_nodes; d.kd_nleaf = sc->kd_nleaf; d.kd_nalways = sc->kd_nalways;
-    for (int i = 0; i < 3; ++i) { d.kd_bmin[i] = sc->kd_bounds[i]; d.kd_bmax[i] = sc->kd_bounds[3 + i]; }
-    d.a_sbox = sc->d_a_sbox.get(); d.a_obb = sc->d_a_obb.get(); d.a_nodes = sc->d_a_nodes.get(); d.a_leaf = sc->d_a_leaf.get(); d.a_unbounded = sc->d_a_unbounded.get();
-    d.a_n_unbounded = (int32_t)sc->accel.unbounded.size(); d.a_kd_depth = sc->accel.kd_depth;
-    d.a_bleaf = sc->d_a_bleaf.get(); d.a_n_bleaf = (int32_t)sc->accel.brute_leaf.size();
-    d.a_bnodes[0] = sc->accel.brute_nodes[0]; d.a_bnodes[1] = sc->accel.brute_nodes[1];
-    for (int i = 0; i < 6; ++i) d.a_broot[i] = sc->accel.brute_root[i];
-    d.a_ok = sc->accel_ok ? 1 : 0; d.a_kd_ok = sc->accel_kd_ok ? 1 : 0;
-    for (int i = 0; i < 6; ++i) d.a_root[i] = sc->accel.root[i];
-    d.a_delta = sc->accel.delta;
-    d.a_goff = sc->d_a_goff.get(); d.a_glist = sc->d_a_glist.get(); d.a_gapart = sc->d_a_gapart.get();
-    d.a_bg_off = sc->d_a_bg_off.get(); d.a_bg_occ = sc->d_a_bg_occ.get(); d.a_bg_ent = sc->d_a_bg_ent.get(); d.a_bg_ok = sc->accel.big_ok ? 1 : 0;
-    d.a_bg_apart = sc->d_a_bg_apart.get(); d.a_bg_napart = sc->accel.big_ok ? (int32_t)sc->accel.big_apart.size() : 0;
-    for (int i = 0; i < 3; ++i) {
-        d.a_bg_dim[i] = sc->accel.big_ok ? sc->accel.big_dim[i] : 1;
-        d.a_bg_lo[i] = sc->accel.big_lo[i]; d.a_bg_cs[i] = sc->accel.big_cs[i]; d.a_bg_inv[i] = sc->accel.big_inv[i];
-    }
-    for (int i = 0; i < 6; ++i) d.a_bg_root[i] = sc->accel.big_ok ? sc->accel.big_root[i] : 0.0f;
-    d.a_g_napart = sc->accel.grid_ok ? (int32_t)sc->accel.grid_apart.size() : 0;
-    for (int i = 0; i < 6; ++i) d.a_groot[i] = sc->accel.grid_ok ? sc->accel.grid_root[i] : 0.0f;
-    d.a_g_ok = sc->accel.grid_ok ? 1 : 0;
-    d.a_g_ncell = sc->accel.grid_ok ? (int32_t)sc->accel.grid_off.size() - 1 : 0;
-    d.a_g_nlist = sc->accel.grid_ok ? (int32_t)sc->accel.grid_list.size() : 0;
-    for (int i = 0; i < 3; ++i) {
-        d.a_gdim[i] = sc->accel.grid_ok ? sc->accel.grid_dim[i] : 1;
-        d.a_glo[i] = sc->accel.grid_lo[i]; d.a_gcs[i] = sc->accel.grid_cs[i]; d.a_ginv[i] = sc->accel.grid_inv[i];
-    }
-    for (int i = 0; i < 3; ++i) { d.a_cen[i] = sc->accel.cen[i]; d.a_slo[i] = sc->accel.slo[i]; d.a_shi[i] = sc->accel.shi[i]; }
-    d.tally = sc->d_tally.get();
-    d.fm_of_surf = sc->d_fm_of_surf.get(); d.fms = sc->d_fms.get(); d.fm_edges = sc->d_fm_edges.get();
-    d.tr_off = sc->tr_off;
-    d.n_fm = (int32_t)sc->fms_h.size(); d.n_fm_edges = (int32_t)sc->fm_edges_h.size();
-    d.counters = sc->counters.device(); d.energy_left = (double *)(d.counters + CNT_ENERGY_LEFT);      // one 64-byte block: one read-back gets both
-    sc->hits.fill(d);
-    return d;
 }
 
 // ================================================================================================
@@ -2473,33 +2482,14 @@ static int scene_stage_spectrum(trc_scene *sc, const SourceSpectrum &sp, const d
     std::vector<double> packed((size_t)3 + sp.tab.size());
     packed[0] = (double)n_tab; packed[1] = sp.desc->wavelength; packed[2] = sp.desc->ref_index;
     std::copy(sp.tab.begin(), sp.tab.end(), packed.begin() + 3);
-    TRC_TRY(sc->d_spec_buf.reserve((size_t)3 + 3 * TRC_SPECTRUM_MAX_POINTS));     // (room for any table: allocated once)
-    // (the stream is idle between calls: every call ends with a synchronous read of its counters)
-    HIP_TRY(hipMemcpy(sc->d_spec_buf.get(), packed.data(), packed.size() * 8, hipMemcpyHostToDevice));
-    *d_spec = sc->d_spec_buf.get();
-    return TRC_OK;
-}
-
-// The device copy of the source descriptor of the call in progress, kept on the scene with what it holds: a Monte-Carlo loop hands
-// over the same descriptor every call (hipMalloc / hipFree per call cost more than the upload).
-static int scene_stage_source(trc_scene *sc, const trc_source_desc *src, const trc_source_desc **d_src) {
-    TRC_TRY(source_kind_check(src));
-    if (!sc->d_src_buf) { TRC_TRY(sc->d_src_buf.alloc(1)); sc->src_host_ok = false; }
-    if (!(sc->src_host_ok && memcmp(&sc->src_host, src, sizeof(trc_source_desc)) == 0)) {
-        sc->src_host_ok = false;
-        if (hipMemcpy(sc->d_src_buf.get(), src, sizeof(trc_source_desc), hipMemcpyHostToDevice) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "source upload failed");
-        memcpy(&sc->src_host, src, sizeof(trc_source_desc));
-        sc->src_host_ok = true;
-    }
-    *d_src = sc->d_src_buf.get();
-    return TRC_OK;
+    return sc->staged.spectrum(packed, d_spec);
 }
 
 // The scene's tabulated materials are evaluated on the device for this call: it has a table for every material its optics name
 // (trc_scene_set_materials), the bundle brings no rows of its own (trc_rays.mat: those are traced as they are), and no flux map
 // bins in a chart other than XY (there is no CHART x MAT kernel instance)
 static bool scene_mat_route(const trc_scene *sc, const trc_rays *in) {
-    return sc->mat_tab_serves() && !(in && in->mat) && !scene_has_chart_map(sc);
+    return sc->mat_tab_serves() && !(in && in->mat) && !sc->tally.has_chart();
 }
 
 // What the bundle `in` (NULL: a source descriptor, whose rays carry nothing but what its spectrum gives them: has_spec) brings
@@ -2507,7 +2497,7 @@ static bool scene_mat_route(const trc_scene *sc, const trc_rays *in) {
 // *mat_dev: scene_mat_route -- the materials' indices come from the scene's tables, lay->n_mat is 0.
 // carried_W: the source carries its spectrum (TRC_SPECTRUM_CARRIED) -- its rays bring W samples each, and no wavelength of their own.
 static int check_carried(const trc_scene *sc, const trc_rays *in, bool has_spec, int carried_W, const char *who, PayLayout *lay, bool *mat_dev) {
-    const CarryNeeds &needs = sc->needs;
+    const CarryNeeds &needs = sc->surfaces.needs();
     lay->n_mat = (in && in->mat) ? (int)in->n_mat : 0;
     lay->W = (in && in->spectra && in->spec_wl) ? in->n_spec : (!in ? carried_W : 0);
     *mat_dev = scene_mat_route(sc, in);
@@ -2595,13 +2585,13 @@ static int fast_check_args(FastCall &C) {
     // scene's materials are on the device: the MAT instances of k_s_shade_x are the ones that draw wavelengths.
     const bool mat_dev = scene_mat_route(sc, C.in);
     const int carried_W = C.spec->carried();
-    if (sc->splits && ((C.flags & TRC_TRACE_MEGAKERNEL) || C.n < 64 || (C.spec->desc && !mat_dev && !carried_W)))
+    if (sc->surfaces.splits() && ((C.flags & TRC_TRACE_MEGAKERNEL) || C.n < 64 || (C.spec->desc && !mat_dev && !carried_W)))
         return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has ray-splitting optics, which the fast engine traces in its streaming form only (64 rays or more, no source spectrum): use trc_trace_ordered");
     C.facts.knobs = stream_knobs();
     // Rays that carry the imaginary part of a complex index, materials evaluated at their wavelength or a sampled spectrum are
     // traced by the streaming form (k_s_shade_x); the megakernel knows nothing of them.
     // ... and so are the rays of a source that carries its spectrum (k_s_shade_p)
-    C.carry = sc->needs.any() || (C.in && (C.in->ref_index_im || C.in->spectra || C.in->mat)) || carried_W > 0;
+    C.carry = sc->surfaces.needs().any() || (C.in && (C.in->ref_index_im || C.in->spectra || C.in->mat)) || carried_W > 0;
     if (C.carry && !C.in && !mat_dev && !carried_W) return trc_fail(TRC_ERR_UNSUPPORTED, "the scene has optics that read what only the rays of a given bundle carry (materials, spectra)");
     TRC_TRY(check_carried(sc, C.in, C.spec->desc != nullptr, carried_W, "trc_trace_fast", &C.lay, &C.mat_dev));
     if (C.carry && ((C.flags & TRC_TRACE_MEGAKERNEL) || C.n < 64))
@@ -2612,7 +2602,8 @@ static int fast_check_args(FastCall &C) {
 static int fast_stage_inputs(FastCall &C) {
     if (!C.in) {
         if (C.spec->desc) TRC_TRY(scene_stage_spectrum(C.sc, *C.spec, &C.d_spec));
-        return scene_stage_source(C.sc, C.src, &C.d_src);
+        TRC_TRY(source_kind_check(C.src));
+        return C.sc->staged.source(C.src, &C.d_src);
     }
     TRC_TRY(check_rays(C.in, C.n, "trc_trace_fast"));
     TRC_TRY(stage_rays(C.in, C.n, true, &C.dr));
@@ -2659,7 +2650,7 @@ static int fast_begin(FastCall &C) {
     trc_scene *sc = C.sc;
     TRC_TRY(sc->counters.snapshot(&C.before));
     if (sc->hits.cap > 0)
-        for (int i = 0; i < sc->n_surf && !C.captures; ++i) C.captures = (sc->surfs[i].flags & TRC_SURF_CAPTURE_HITS) != 0;
+        for (int i = 0; i < sc->n_surf && !C.captures; ++i) C.captures = (sc->surfaces[i].flags & TRC_SURF_CAPTURE_HITS) != 0;
     if (C.captures) TRC_TRY(sc->hits.spectra_for(3 * C.lay.W, C.before.hit_cursor, &C.hit_x));
     C.dirty_before = sc->hits.begin_call();      // (fast_finish says how far the hit buffer was used)
     return sc->counters.restart_last(C.before);
@@ -2690,7 +2681,7 @@ static void fast_facts(FastCall &C) {
     C.facts.scene = scene_facts(C.sc, false);
     int poly_walls = 0;
     if (C.spec->carried())
-        for (int i = 0; i < C.sc->n_surf; ++i) poly_walls += C.sc->surfs[i].optics_kind == TRC_OPT_LAMBERTIAN_POLYCHROMATIC ? 1 : 0;
+        for (int i = 0; i < C.sc->n_surf; ++i) poly_walls += C.sc->surfaces[i].optics_kind == TRC_OPT_LAMBERTIAN_POLYCHROMATIC ? 1 : 0;
     C.facts.call = {C.n, C.flags, C.src ? C.src->kind : -1, C.d_spec != nullptr, C.carry, C.mat_dev && C.sc->d_mat_tab.get(), C.min_energy >= 0.0,
                     C.spec->carried(), poly_walls};
 }
@@ -2731,7 +2722,7 @@ static int mega_launch(FastCall &C, const MegaPlan &M, const FastParams &P) {
     trc_scene *sc = C.sc;
     trc_ctx *ctx = sc->ctx;
     (void)hipStreamSynchronize(ctx->stream);       // (the sums of an earlier streaming call may still be on their way into the buffer)
-    if (hipMemcpy(C.tally_before, sc->d_tally.get() + 3 * sc->n_surf, sizeof(C.tally_before), hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(C.tally_before, sc->tally.device() + 3 * sc->n_surf, sizeof(C.tally_before), hipMemcpyDeviceToHost) != hipSuccess)
         return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
     void (*kern)(FastParams) = (void (*)(FastParams))mega_kernel_fn(M.id);
     if (!kern) return trc_fail(TRC_ERR_UNSUPPORTED, "the library holds no megakernel instance for this call");
@@ -2769,7 +2760,7 @@ static int fast_finish(FastCall &C) {
         s.hits = (int64_t)(C.stream_hits + 0.5);
     } else {
         double tally_after[2];
-        if (hipMemcpy(tally_after, sc->d_tally.get() + 3 * sc->n_surf, sizeof(tally_after), hipMemcpyDeviceToHost) != hipSuccess)
+        if (hipMemcpy(tally_after, sc->tally.device() + 3 * sc->n_surf, sizeof(tally_after), hipMemcpyDeviceToHost) != hipSuccess)
             return trc_fail(TRC_ERR_DEVICE, "counter readback failed");
         s.segments = (int64_t)(tally_after[0] - C.tally_before[0] + 0.5);
         s.hits = (int64_t)(tally_after[1] - C.tally_before[1] + 0.5);
@@ -3001,7 +2992,7 @@ static int ordered_next_level(OrdCall &C, int it, int64_t n_cur, int64_t m, int6
     G.m = m; G.n_parent = n_cur;
     G.x = Ln.x; G.y = Ln.y; G.z = Ln.z; G.dx = Ln.dx; G.dy = Ln.dy; G.dz = Ln.dz; G.e = Ln.e; G.ref = Ln.ref;
     G.wl = Ln.wl; G.rid = Ln.rid; G.parent = Ln.parent; G.surf = Ln.surf;
-    G.recs = sc->d_recs.get(); G.stride = sc->stride;
+    { const DScene d = make_dscene(sc); G.recs = d.recs; G.stride = d.stride; }
     G.opay = sx.opay.get(); G.pay = Ln.pay; G.n_pay = C.lay.rows();
     hipLaunchKernelGGL(k_ord_gather, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, G);
     const hipError_t se = hipStreamSynchronize(ctx->stream);
@@ -3042,7 +3033,7 @@ static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_sourc
     trc_source_desc src_res;
     TRC_TRY(source_resolve(sc->ctx, src, src_res, "trc_trace_ordered"));
     if (2 * n >= (int64_t)0xFFFFFFFFll) return trc_fail(TRC_ERR_UNSUPPORTED, "ordered engine handles fewer than 2^31 rays per call");
-    if ((flags & TRC_TRACE_ACCEL) && !sc->has_kd) return trc_fail(TRC_ERR_INVALID, "TRC_TRACE_ACCEL without a Kd-tree on the scene");
+    if ((flags & TRC_TRACE_ACCEL) && !sc->kd.has()) return trc_fail(TRC_ERR_INVALID, "TRC_TRACE_ACCEL without a Kd-tree on the scene");
     if (sc->n_surf >= (1 << 28)) return trc_fail(TRC_ERR_UNSUPPORTED, "too many surfaces for the ordering key");
     HIP_TRY(hipSetDevice(sc->ctx->device));
     // what the rays carry beyond the nine columns (complex indices, material rows, spectra); rays between materials carry Im of the
@@ -3050,7 +3041,7 @@ static int trace_ordered_impl(trc_scene *sc, const trc_rays *in, const trc_sourc
     PayLayout lay;
     bool mat_dev = false;
     TRC_TRY(check_carried(sc, in, spec.desc != nullptr, spec.carried(), "trc_trace_ordered", &lay, &mat_dev));
-    lay.has_im = ((in && in->ref_index_im) || sc->needs.max_mat >= 0) ? 1 : 0;
+    lay.has_im = ((in && in->ref_index_im) || sc->surfaces.needs().max_mat >= 0) ? 1 : 0;
     std::unique_ptr<trc_result> res(new (std::nothrow) trc_result());
     if (!res) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
     res->ctx = sc->ctx;
@@ -3214,18 +3205,10 @@ extern "C" int trc_kdtree_traversal(trc_ctx *ctx, const trc_kdtree_desc *kd, int
     if (!ctx || !kd || !relevancy || n_surf <= 0 || n < 0) return trc_fail(TRC_ERR_INVALID, "trc_kdtree_traversal: bad arguments");
     TRC_TRY(check_rays(rays, n, "trc_kdtree_traversal"));
     if (rays->on_device) return trc_fail(TRC_ERR_INVALID, "trc_kdtree_traversal: host bundle expected");
-    if (kd->n_nodes <= 0 || !kd->flag || !kd->split || !kd->child || !kd->leaf_off || !kd->leaf_cnt || (kd->n_leaf_surfs > 0 && !kd->leaf_surfs))
-        return trc_fail(TRC_ERR_INVALID, "trc_kdtree_traversal: incomplete tree");
-    for (int i = 0; i < kd->n_nodes; ++i) {
-        if (kd->flag[i] < 0 || kd->flag[i] > 3) return trc_fail(TRC_ERR_INVALID, "node %d: flag %d", i, kd->flag[i]);
-        if (kd->flag[i] != 3 && (kd->child[i] <= i || kd->child[i] + 1 >= kd->n_nodes)) return trc_fail(TRC_ERR_INVALID, "node %d: children out of range", i);
-        if (kd->flag[i] == 3 && (kd->leaf_off[i] < 0 || kd->leaf_cnt[i] < 0 || kd->leaf_off[i] + kd->leaf_cnt[i] > kd->n_leaf_surfs))
-            return trc_fail(TRC_ERR_INVALID, "node %d: leaf list out of range", i);
-    }
-    for (int i = 0; i < kd->n_leaf_surfs; ++i)
-        if (kd->leaf_surfs[i] < 0 || kd->leaf_surfs[i] >= n_surf) return trc_fail(TRC_ERR_INVALID, "leaf surface %d out of range", kd->leaf_surfs[i]);
-    for (int i = 0; i < kd->n_always; ++i)
-        if (kd->always_relevant[i] < 0 || kd->always_relevant[i] >= n_surf) return trc_fail(TRC_ERR_INVALID, "always-relevant surface out of range");
+    char why[160];
+    int depth = 0;      // (not refused here: a ray that runs out of stack raises the kernel's flag)
+    const int st = trc_kd_check(kd, n_surf, &depth, why, sizeof(why));
+    if (st != TRC_OK) return trc_fail(st, "trc_kdtree_traversal: %s", why);
     HIP_TRY(hipSetDevice(ctx->device));
     DevBuf<int32_t> d_i32[5];
     DevBuf<double> d_split, d_r[6];
@@ -3275,7 +3258,7 @@ static int upload_record(const trc_surface_desc *surf, int32_t n_extra, const do
     TRC_TRY(validate_surface(*surf, 0, n_extra));
     int stride = TRC_REC_HDR + 16;
     std::vector<double> rec(stride);
-    pack_record(*surf, rec.data(), stride);
+    trc_pack_record(*surf, rec.data(), stride);
     TRC_TRY(dev_upload(d_rec, rec.data(), (size_t)stride));
     if (d_opt) TRC_TRY(dev_upload(*d_opt, surf->opt, 8));
     TRC_TRY(d_extra.alloc((size_t)(n_extra > 0 ? n_extra : 1)));

@@ -2095,7 +2095,7 @@ static int stream_fp_prepare(trc_scene *sc, StreamEngine &E, const trc_source_de
     const bool buie = src->kind == TRC_SRC_BUIE_DISK || src->kind == TRC_SRC_BUIE_RECT;
     const double cdf_end = buie ? src->buie[2 * (TRC_BUIE_NELEM + 1) + TRC_BUIE_NELEM] : 0.0;
     if (!E.fp) { E.fp.reset(new (std::nothrow) trc_fp_host()); if (!E.fp) return trc_fail(TRC_ERR_NOMEM, "out of host memory"); E.fp_valid = false; }
-    if (!(E.fp_valid && E.fp_geom_version == sc->geom_version && memcmp(key, E.fp_key, sizeof(key)) == 0 && (!buie || E.fp->P.cdf_end == cdf_end))) {
+    if (!(E.fp_valid && E.fp_geom_version == sc->search.geom_version() && memcmp(key, E.fp_key, sizeof(key)) == 0 && (!buie || E.fp->P.cdf_end == cdf_end))) {
         int M = sc->n_surf > 4096 ? 1024 : 512;       // (a mesh of small faces: finer cells, fewer faces listed per cell; the mask still fits k_s_cull's LDS)
         const bool forced = K.fp_cells > 0;
         const bool um = buie;      // the mask over the uniforms: for the sources whose listed rays go to k_s_fresh2 (trc_stream_form_fresh)
@@ -2105,14 +2105,14 @@ static int stream_fp_prepare(trc_scene *sc, StreamEngine &E, const trc_source_de
             // A large mesh that fills the source's view: nearly every ray starts over a face, the map culls nothing, and building
             // it at full resolution takes seconds (1e5 faces: 2.5 s).  A coarse map first (1/16 of the work): covered more than
             // 80 % -> no map for this scene and source, every fresh ray is searched on the grid (k_s_bounce<.., FRESH>).
-            trc_fp_build(sc->surfs.data(), sc->n_surf, sc->accel, *src, *E.fp, 256, false);
+            trc_fp_build(sc->surfaces.data(), sc->n_surf, sc->search.host(), *src, *E.fp, 256, false);
             const bool disc = src->kind == TRC_SRC_BUIE_DISK || src->kind == TRC_SRC_PILLBOX_DISK || src->kind == TRC_SRC_SUNSHAPE_DISK;      // (the mask is a square around the disc)
             if (E.fp->ok && E.fp->coverage * (disc ? 4.0 / TRC_PI : 1.0) > 0.8) E.fp->ok = false;
-            else trc_fp_build(sc->surfs.data(), sc->n_surf, sc->accel, *src, *E.fp, M, um);
+            else trc_fp_build(sc->surfaces.data(), sc->n_surf, sc->search.host(), *src, *E.fp, M, um);
         } else
-        trc_fp_build(sc->surfs.data(), sc->n_surf, sc->accel, *src, *E.fp, M, um);
+        trc_fp_build(sc->surfaces.data(), sc->n_surf, sc->search.host(), *src, *E.fp, M, um);
         memcpy(E.fp_key, key, sizeof(key));
-        E.fp_geom_version = sc->geom_version;
+        E.fp_geom_version = sc->search.geom_version();
         E.fp_valid = true;
         E.fp_hit_rate = 0.0;
         E.d_fp_mask.reset(); E.d_fp_coff.reset(); E.d_fp_clist.reset(); E.d_fp_umask.reset();
@@ -2344,7 +2344,7 @@ static int stream_slots_alloc(StreamEngine &E, int n_slots, long long cap, const
                               bool split_rays, bool poly_src) {
     for (int k = 0; k < n_slots; ++k) {
         StreamSlot &Tk = E.slot[k];
-        TRC_TRY(stream_ws_alloc(Tk.W, cap, (int)sc->accel.unbounded.size(), (long long)sc->tally_n, K));
+        TRC_TRY(stream_ws_alloc(Tk.W, cap, (int)sc->search.host().unbounded.size(), (long long)sc->tally.size(), K));
         // (a source that carries its spectrum brings no columns, but its rays' spectra live in the slot table all the same)
         const long long want = ((carry_in.spec || poly_src) && carry_in.n_spec > 0) ? (long long)carry_in.n_spec * Tk.W.room : 0;
         if (Tk.spec_len < want) {
@@ -2822,15 +2822,15 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, c
     cap = (cap + 63) & ~63ll;
     if (cap < 64) cap = 64;
     TRC_TRY(stream_engine_init(&E, ctx));
-    if (E.rate_geom_version != sc->geom_version) {       // another pose of the scene: measured again
+    if (E.rate_geom_version != sc->search.geom_version()) {       // another pose of the scene: measured again
         E.forget_rates();
-        E.rate_geom_version = sc->geom_version;
+        E.rate_geom_version = sc->search.geom_version();
     }
     // rays that carry more than the fast engine's record -- Im of a complex index, materials at their wavelength, a spectrum -- are
     // shaded by k_s_shade_x; the spectra of the rays under way live in a table of their own beside the ray table
     // ... and so are all hits of a scene whose optics send two rays on from a hit, by its SPLIT form
-    const bool split_rays = sc->splits;
-    facts.call.carry = sc->needs.any() || carry_in.ref_im || carry_in.mat || carry_in.spec || split_rays || facts.call.poly_src > 0;
+    const bool split_rays = sc->surfaces.splits();
+    facts.call.carry = sc->surfaces.needs().any() || carry_in.ref_im || carry_in.mat || carry_in.spec || split_rays || facts.call.poly_src > 0;
     StreamForms F;
     StreamCall C{F, K, E, StreamParams(), cap, 0.0, 0.0, {0.0, 0.0, 0.0}, 0, 0, split_rays};
     memset(&C.SP0, 0, sizeof(C.SP0));
@@ -2880,8 +2880,8 @@ static int stream_trace(trc_scene *sc, FastParams &P, const CarryIn &carry_in, c
     float total_ms = 0;
     (void)hipEventElapsedTime(&total_ms, ctx->ev0, ctx->ev1);
     for (int k = 0; k < n_slots; ++k)
-        hipLaunchKernelGGL(k_s_merge_tallies, dim3((unsigned)((sc->tally_n + 255) / 256)), dim3(256), 0, ctx->stream, sc->d_tally.get(), E.slot[k].W.tally_part.get(), (long long)sc->tally_n);
-    hipLaunchKernelGGL(k_s_add2, dim3(1), dim3(64), 0, ctx->stream, sc->d_tally.get() + 3 * sc->n_surf, C.seg, C.hits);
+        hipLaunchKernelGGL(k_s_merge_tallies, dim3((unsigned)((sc->tally.size() + 255) / 256)), dim3(256), 0, ctx->stream, sc->tally.device(), E.slot[k].W.tally_part.get(), (long long)sc->tally.size());
+    hipLaunchKernelGGL(k_s_add2, dim3(1), dim3(64), 0, ctx->stream, sc->tally.device() + 3 * sc->n_surf, C.seg, C.hits);
     // (not waited for: whatever reads or resets the tallies synchronises the context's stream first, and the next call's kernels
     // are ordered behind these by ev0)
     stats->kernel_ms = total_ms;
