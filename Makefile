@@ -30,6 +30,9 @@ FMCHECK := $(ROOT)tests/hostcheck/libtrc_fluxmap_check.so
 FMCHECK_SRC := $(ROOT)tests/hostcheck/fluxmap_check.cpp
 HHCHECK := $(ROOT)tests/hostcheck/libtrc_hithist_check.so
 HHCHECK_SRC := $(ROOT)tests/hostcheck/hithist_check.cpp
+THERMCHECK := $(ROOT)tests/hostcheck/libtrc_thermal_check.so
+THERMCHECK_EXE := $(ROOT)tests/hostcheck/thermal_check
+THERMCHECK_SRC := $(ROOT)tests/hostcheck/thermal_check.cpp
 
 UMASKCHECK := $(ROOT)tests/umaskcheck/libtrc_umask_check.so
 UMASKCHECK_EXE := $(ROOT)tests/umaskcheck/umask_check
@@ -72,7 +75,7 @@ $(LIB): $(OBJS)
 MATCHECK := $(ROOT)tests/hostcheck/libtrc_material_check.so
 MATCHECK_SRC := $(ROOT)tests/hostcheck/material_check.cpp
 
-hostcheck: $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK) $(HHCHECK)
+hostcheck: $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK) $(HHCHECK) $(THERMCHECK)
 
 # the tabulated materials' lookup of the per-ray core, host-compiled for its tests
 $(MATCHECK): $(MATCHECK_SRC) $(HDR)
@@ -92,6 +95,17 @@ $(SUNCHECK): $(SUNCHECK_SRC) $(HDR)
 # the arc-lamp sources of the per-ray core and the decisions for their kinds, host-compiled for their tests
 $(LAMPCHECK): $(LAMPCHECK_SRC) $(HDR)
 	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(LAMPCHECK_SRC)
+
+# the thermal emitters of the per-ray core -- the emittance table's packing, its exact sampler, the shapes -- host-compiled for their
+# tests; and the same source as a program of its own (thermalcheck), built with the sanitizers, that runs the sampler over a grid of
+# uniforms and is run by tests/test_thermal_sources_host.py
+$(THERMCHECK): $(THERMCHECK_SRC) $(HDR)
+	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(THERMCHECK_SRC)
+
+thermalcheck: $(THERMCHECK_EXE)
+
+$(THERMCHECK_EXE): $(THERMCHECK_SRC) $(HDR)
+	$(CXX) -O1 -g -std=c++17 $(FPFLAGS) $(SPLIT_SAN) -DTHERMAL_CHECK_MAIN -o $@ $(THERMCHECK_SRC)
 
 # the flux-map charts and bin index of the per-ray core, host-compiled for their tests
 $(FMCHECK): $(FMCHECK_SRC) $(HDR)
@@ -168,6 +182,6 @@ asm-shade: $(CSRC)/trc_shade.hip $(HDR)
 		-o $(ROOT)build/trc_shade.s $(CSRC)/trc_shade.hip 2> $(ROOT)build/trc_shade.resources.txt
 
 clean:
-	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK) $(HHCHECK)
+	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK) $(HHCHECK) $(THERMCHECK) $(THERMCHECK_EXE)
 
-.PHONY: all hostcheck umaskcheck umaskcheck-exe splitcheck polycheck poolcheck poolcheck-tsan scenecheck asm asm-shade clean
+.PHONY: all hostcheck thermalcheck umaskcheck umaskcheck-exe splitcheck polycheck poolcheck poolcheck-tsan scenecheck asm asm-shade clean

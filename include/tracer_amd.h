@@ -208,10 +208,34 @@ typedef enum trc_source_kind {
          as EMIT_SPHERE about sign (cos phi, sin phi, 0).  p: R, h, ang_range, law, sign. */
     TRC_SRC_ARC_VOLUME = TRC_SRC_VF_FRUSTUM + 3,
     TRC_SRC_EMIT_SPHERE = TRC_SRC_VF_FRUSTUM + 4,
-    TRC_SRC_EMIT_CYLINDER = TRC_SRC_VF_FRUSTUM + 5
+    TRC_SRC_EMIT_CYLINDER = TRC_SRC_VF_FRUSTUM + 5,
+    /* thermal emitter (spectral_band_axisymmetrical_thermal_emission_source sources.py:771-813, gray_source :44-66): rays leave a
+       surface about its local normal with the polar density eps(theta) cos(theta) sin(theta), eps the directional band emittance
+       that the table `table` names (trc_emittance_table_create) interpolates linearly.  The density is sampled exactly -- the
+       analytic CDF is inverted per ray -- so every ray carries `energy`.  Draws of ray i, event 0, block 0: (u0, u1) the point, u2
+       the polar angle, u3 the azimuth 2 pi u3; the direction is turned from +z to sign * normal by the minimal rotation
+       (vector_manipulations.rotate_z_to_normal).  Point and direction go to the global frame through rot_pos / center and rot_dir.
+       p[0]: the shape (TRC_THERMAL_*), p[1..5]: its parameters, p[6]: sign (+1 along the shape's normal, -1 against it),
+       p[TRC_SUNSHAPE_P_N]: written by the library.  Shapes in the source's own frame, points and normals as the reference's
+       ray_trace_utils/sampling.py *_sampling(normals=True) functions give them, u0 their first draw and u1 their second:
+         DISK      phi = 2 pi u0, r = R sqrt(u1), z = 0; normal +z.  p: R
+         RECT      (X (u0 - 1/2), Y (u1 - 1/2), 0); normal +z.  p: X, Y
+         TRIANGLE  sqrt(u0) (1 - u1) AB + u1 sqrt(u0) AC in the local xy-plane, A = center; normal +z.  p: ABx, ABy, ACx, ACy
+         CYLINDER  z = u0 h - h/2, phi = 2 pi u1, (R cos phi, R sin phi, z); normal (cos phi, sin phi, 0).  p: R, h
+         FRUSTUM   phi = s0 + (s1 - s0) u1, r = sqrt((r1^2 - r0^2) u0 + r0^2), z = (r - r0) / c, c = (r1 - r0) / depth; normal
+                   -(cos phi sin ts, sin phi sin ts, cos ts), ts = atan(c) - pi/2 (frustum_sampling's with normal_in=False).
+                   p: r0, r1 (!= r0), depth, s0, s1
+         SPHERE    phi = 2 pi u0, cos = 2 u1 - 1, R n; normal n.  p: R */
+    TRC_SRC_EMIT_THERMAL = TRC_SRC_VF_FRUSTUM + 6
 } trc_source_kind;
 #define TRC_EMIT_LAMBERTIAN 0
 #define TRC_EMIT_ISOTROPIC 1
+#define TRC_THERMAL_DISK 0
+#define TRC_THERMAL_RECT 1
+#define TRC_THERMAL_TRIANGLE 2
+#define TRC_THERMAL_CYLINDER 3
+#define TRC_THERMAL_FRUSTUM 4
+#define TRC_THERMAL_SPHERE 5
 
 #define TRC_BUIE_NELEM 210  /* sources.py:338 */
 
@@ -224,7 +248,7 @@ typedef enum trc_source_kind {
  */
 typedef struct trc_source_desc {
     int32_t kind;
-    int32_t table;      /* TRC_SRC_SUNSHAPE_*, TRC_SRC_ARC_VOLUME: the id of a live trc_sunshape (trc_sunshape_id); 0 for every other kind */
+    int32_t table;      /* TRC_SRC_SUNSHAPE_*, TRC_SRC_ARC_VOLUME, TRC_SRC_EMIT_THERMAL: the id of a live trc_sunshape (trc_sunshape_id); 0 for every other kind */
     double center[3];
     double rot_pos[9];  /* row-major local->global for start points */
     double rot_dir[9];  /* row-major local->global for directions   */
@@ -560,6 +584,17 @@ int trc_sunshape_destroy(trc_sunshape *table);
  * id space, and trc_sunshape_id / _get / _destroy serve it (get: theta_c = the last angle, u_c = 1).
  */
 int trc_angle_table_create(trc_ctx *ctx, int32_t n, const double *angle, const double *density, trc_sunshape **out);
+/*
+ * Emittance table of a thermal emitter (TRC_SRC_EMIT_THERMAL): n points (2..TRC_SUNSHAPE_MAX_POINTS) of strictly increasing polar
+ * angles within [0, pi/2] (an angle within 5e-9 beyond pi/2 is taken: a table written to 8 decimals states pi/2 as 1.57079633)
+ * and finite, non-negative directional emittances eps, linear between the points, with a positive mass
+ * M = integral of eps(theta) cos(theta) sin(theta).  Packed as theta | eps / M | cdf: cdf the running analytic integral of the
+ * density over M -- each interval with its own slope at both its ends -- ending at exactly 1.  The polar angle of a uniform u is
+ * the exact solution of cdf(theta) = u (trc_emittance_theta, csrc/trc_core.h).  The object is a trc_sunshape: it shares the id
+ * space, and trc_sunshape_id / _get / _destroy serve it (get: theta_c = the last angle, u_c = M).  Every table remembers which of
+ * the three packings it holds; a TRC_SRC_EMIT_THERMAL descriptor that names a table of another packing is TRC_ERR_INVALID.
+ */
+int trc_emittance_table_create(trc_ctx *ctx, int32_t n, const double *theta, const double *eps, trc_sunshape **out);
 
 /*
  * Start points of the first n rays of a disc / rectangle source (sources.py:175-515) in the source's own plane coordinates

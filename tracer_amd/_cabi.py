@@ -62,6 +62,9 @@ SUNSHAPE_CORE_TAIL = 0.01
 SUNSHAPE_P_THETA_C, SUNSHAPE_P_U_C, SUNSHAPE_P_N = 5, 6, 7
 SRC_ARC_VOLUME, SRC_EMIT_SPHERE, SRC_EMIT_CYLINDER = 9, 10, 11      # arc-lamp sources; ARC_VOLUME's `table` names a polar table
 EMIT_LAMBERTIAN, EMIT_ISOTROPIC = 0, 1                              # TRC_EMIT_*: the direction law of the emitters
+SRC_EMIT_THERMAL = 12                                               # thermal emitter; `table` names an emittance table
+THERMAL_DISK, THERMAL_RECT, THERMAL_TRIANGLE, THERMAL_CYLINDER, THERMAL_FRUSTUM, THERMAL_SPHERE = 0, 1, 2, 3, 4, 5     # TRC_THERMAL_*
+EMITTANCE_THETA_MAX = 1.5707963267948966 + 5e-9                     # TRC_EMITTANCE_THETA_MAX: a last angle up to here is read as pi/2
 
 _p_f64 = C.POINTER(C.c_double)
 _p_i64 = C.POINTER(C.c_int64)
@@ -178,6 +181,7 @@ SIGNATURES = {
     'trc_sunshape_get': (C.c_int, [_vp, _p_i32, _p_f64, _p_f64, _p_f64]),
     'trc_sunshape_destroy': (C.c_int, [_vp]),
     'trc_angle_table_create': (C.c_int, [_vp, C.c_int32, _p_f64, _p_f64, _pvp]),
+    'trc_emittance_table_create': (C.c_int, [_vp, C.c_int32, _p_f64, _p_f64, _pvp]),
     'trc_source_start32': (C.c_int, [_vp, C.POINTER(SourceDesc), C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_float),
                                      C.POINTER(C.c_float), _p_f64]),
     'trc_gm_find_intersections': (C.c_int, [_vp, C.POINTER(SurfaceDesc), C.c_int32, _p_f64, C.POINTER(Rays), _p_f64,

@@ -1952,13 +1952,226 @@ TRC_HD void trc_lamp_pose(const trc_source_desc *src, double lx, double ly, doub
     *dz = rd[6] * ax + rd[7] * ay + rd[8] * az;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Thermal emitters (TRC_SRC_EMIT_THERMAL; sources.py:771-813, :44-66): rays from a surface whose directional band emittance
+// eps(theta) is a table, linear between its points.  The polar angle about the local normal has the density eps(theta) cos(theta)
+// sin(theta); it is sampled exactly -- the analytic CDF inverted per ray -- so that every ray carries the same energy.
+// ---------------------------------------------------------------------------------------------
+TRC_HD bool trc_src_kind_is_emitter(int k) { return trc_src_kind_is_lamp(k) || k == TRC_SRC_EMIT_THERMAL; }
+
+// a table written to 8 decimals states pi/2 as 1.57079633: a last angle up to this bound is read as pi/2 (trc_emittance_angle), so
+// that no density is negative and the CDF increases throughout
+#define TRC_EMITTANCE_THETA_MAX (TRC_PI / 2.0 + 5e-9)
+static inline double trc_emittance_angle(double theta) { return theta > TRC_PI / 2.0 ? TRC_PI / 2.0 : theta; }
+#define TRC_EMITTANCE_MAX_ITER 64
+
+// G(theta) = H(theta) - H(x0), H the antiderivative of (e0 + a (t - x0)) cos(t) sin(t) with the interval's own slope a: the
+// integral over [x0, theta], written in d = theta - x0 so that no two large terms cancel --
+//     G = e0/2 sin(d) sin(theta + x0) + a/4 (cos(2 theta) (sin(d) cos(d) - d) + sin^2(d) sin(2 theta)),
+// H(theta) - H(x0) with the sums of angles taken apart.  As a difference of two values of H, rounding is 1e-16 of a theta / 4, and
+// a = the step of eps over the interval's width is without bound on a narrow, steep interval; here it is 1e-16 of the interval's own
+// mass and of eps.  s0, c0: sin and cos of x0; s, c: of theta.  sin(d) cos(d) - d = (sin(2 d) - 2 d) / 2 by its series below
+// d = 1/16 (the term after x^11 / 11! is 1e-18 of the first there).
+TRC_HD double trc_emittance_G(double a, double e0, double s0, double c0, double d, double s, double c) {
+    const double sd = s * c0 - c * s0, cd = c * c0 + s * s0;            // sin and cos of d
+    const double s_sum = s * c0 + c * s0;                                // sin(theta + x0)
+    double w;                                                            // sin(d) cos(d) - d
+    if (d < 0.0625) {
+        const double x = 2.0 * d, x2 = x * x;
+        w = 0.5 * x * x2 * (-1.0 / 6.0 + x2 * (1.0 / 120.0 + x2 * (-1.0 / 5040.0 + x2 * (1.0 / 362880.0 - x2 * (1.0 / 39916800.0)))));
+    } else w = sd * cd - d;
+    const double sd_acc = d < 0.0625 ? d * (1.0 + d * d * (-1.0 / 6.0 + d * d * (1.0 / 120.0 + d * d * (-1.0 / 5040.0 + d * d * (1.0 / 362880.0))))) : sd;
+    return e0 / 2.0 * sd_acc * s_sum + a / 4.0 * ((c - s) * (c + s) * w + sd_acc * sd_acc * (2.0 * s * c));
+}
+
+// Host: what is wrong with an emittance table (trc_emittance_table_create's errors but the one of a table without mass, which the
+// packing finds), or null: 2..TRC_SUNSHAPE_MAX_POINTS points, finite angles within [0, pi/2] that still increase strictly once the
+// last is read as pi/2, finite non-negative emittances
+static inline const char *trc_emittance_table_fault(int n, const double *theta, const double *eps) {
+    if (n < 2 || n > TRC_SUNSHAPE_MAX_POINTS) return "the table must have 2..4096 points";
+    if (!theta || !eps) return "angles or emittances missing";
+    for (int i = 0; i < n; ++i) {
+        if (!(theta[i] - theta[i] == 0.0)) return "an angle is not finite";
+        if (i > 0 && !(trc_emittance_angle(theta[i]) > theta[i - 1])) return "the angles are not strictly increasing";
+        if (!(eps[i] - eps[i] == 0.0) || eps[i] < 0.0) return "an emittance is negative or not finite";
+    }
+    if (!(theta[0] >= 0.0) || !(theta[n - 1] <= TRC_EMITTANCE_THETA_MAX)) return "the angles must lie in [0, pi/2]";
+    return nullptr;
+}
+
+// Host: packs a checked table (trc_emittance_table_fault) into tab[3n] = theta | eps / M | cdf: M the mass sum_i (H_i(theta_i+1) -
+// H_i(theta_i)), every interval with its own slope at both its ends, cdf the running sum over M, its last entry exactly 1.
+// *mass = M.  false: no (or no finite) mass.
+static inline bool trc_emittance_pack(int n, const double *theta, const double *eps, double *tab, double *mass) {
+    double *th = tab, *e = tab + n, *c = tab + 2 * n;
+    double cum = 0.0;
+    c[0] = 0.0;
+    for (int i = 0; i < n; ++i) th[i] = trc_emittance_angle(theta[i]);
+    for (int i = 0; i + 1 < n; ++i) {
+        const double a = (eps[i + 1] - eps[i]) / (th[i + 1] - th[i]);
+        double m = trc_emittance_G(a, eps[i], sin(th[i]), cos(th[i]), th[i + 1] - th[i], sin(th[i + 1]), cos(th[i + 1]));
+        if (!(m > 0.0)) m = 0.0;                    // (an interval of zero emittance, up to rounding)
+        cum += m;
+        c[i + 1] = cum;
+    }
+    if (!(cum > 0.0) || !(cum < TRC_INF)) return false;
+    for (int i = 0; i < n; ++i) { e[i] = eps[i] / cum; c[i] /= cum; }
+    c[n - 1] = 1.0;
+    if (mass) *mass = cum;
+    return true;
+}
+
+// The polar angle of uniform u in [0, 1) from a packed emittance table: F(theta) = u solved exactly.  The interval as
+// trc_spectrum_sample finds its own (a stretch without mass is never chosen); inside it G(theta) = H(theta) - H(theta_i) = t =
+// u - cdf_i.  A flat interval (a == 0) has the closed form of the Lambertian law, sin^2 = sin^2(theta_i) + 2 t / b -- taken from
+// the nearer end of the interval (cos^2 = cos^2(theta_i+1) + 2 (cdf_i+1 - u) / b beyond half its mass), so that the angle is as
+// exact next to pi/2, where cos^2 is the small quantity, as next to 0.  Otherwise Newton's iteration from the chord point inside a
+// bracket that is kept at all times: a step that is not finite or leaves the open bracket is replaced by the bisection step.  It
+// ends when |G - t| <= 2^-50 (in units of the normalised CDF), when the bracket is two neighbouring doubles, or after
+// TRC_EMITTANCE_MAX_ITER iterations.  *iters (if given): the iterations taken.
+TRC_HD double trc_emittance_theta(const double *tab, int n, double u, int *iters = nullptr) {
+    const double *th = tab, *ev = tab + n, *cdf = tab + 2 * n;
+    int lo = 0, hi = n - 1;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (cdf[mid] <= u) lo = mid; else hi = mid;
+    }
+    if (iters) *iters = 0;
+    const double x0 = th[lo], x1 = th[lo + 1];
+    const double e0 = ev[lo], a = (ev[lo + 1] - e0) / (x1 - x0);
+    const double t = u - cdf[lo];
+    if (!(t > 0.0)) return x0;
+    if (a == 0.0) {
+        double s2, c2;
+        const double t1 = cdf[lo + 1] - u;
+        if (t <= t1) {
+            double s, c;
+            trc_sincos(x0, &s, &c);
+            s2 = s * s + 2.0 * t / e0;
+            c2 = 1.0 - s2;
+        } else {
+            double s, c;
+            trc_sincos(x1, &s, &c);
+            c2 = c * c + 2.0 * t1 / e0;
+            s2 = 1.0 - c2;
+        }
+        double r = atan2(sqrt(fmax(s2, 0.0)), sqrt(fmax(c2, 0.0)));
+        if (r < x0) r = x0;
+        if (r > x1) r = x1;
+        return r;
+    }
+    double s, c, s0, c0;
+    trc_sincos(x0, &s0, &c0);
+    double bl = x0, bh = x1;                        // G(bl) <= t < G(bh)
+    double x = x0 + (x1 - x0) * (t / (cdf[lo + 1] - cdf[lo]));
+    if (!(x > bl) || !(x < bh)) x = 0.5 * (bl + bh);
+    const double tol = 1.0 / 1125899906842624.0;    // 2^-50
+    int it = 0;
+    for (; it < TRC_EMITTANCE_MAX_ITER; ++it) {
+        trc_sincos(x, &s, &c);
+        const double F = trc_emittance_G(a, e0, s0, c0, x - x0, s, c) - t;
+        if (fabs(F) <= tol) break;
+        if (F > 0.0) bh = x; else bl = x;
+        const double mid = 0.5 * (bl + bh);
+        if (!(mid > bl) || !(mid < bh)) break;      // the bracket is two neighbouring doubles
+        const double xn = x - F / ((e0 + a * (x - x0)) * s * c);
+        x = (xn > bl && xn < bh) ? xn : mid;        // (a step that is not finite fails both comparisons)
+    }
+    if (iters) *iters = it;
+    return x;
+}
+
+// A point of a thermal emitter's shape (p[0]: TRC_THERMAL_*, p[1..5]: its parameters) in the source's own frame and the shape's
+// normal there, from (u0, u1) in the order the reference's *_sampling(normals=True) functions draw theirs.
+TRC_HD void trc_thermal_point_u(const double *p, double u0, double u1, double *lx, double *ly, double *lz, double *nx, double *ny,
+                                double *nz) {
+    *nx = 0.0; *ny = 0.0; *nz = 1.0;
+    *lz = 0.0;
+    switch ((int)p[0]) {
+    case TRC_THERMAL_DISK: {                // disk_sampling: ths, rs
+        double sp, cp;
+        trc_sincos_2pi(u0, &sp, &cp);
+        const double r = sqrt(u1) * p[1];
+        *lx = r * cp; *ly = r * sp;
+        break;
+    }
+    case TRC_THERMAL_RECT:                  // rectangle_sampling as intended: uniform over X by Y about the centre
+        *lx = p[1] * (u0 - 0.5); *ly = p[2] * (u1 - 0.5);
+        break;
+    case TRC_THERMAL_TRIANGLE: {            // triangle_sampling: r1, r2; A is the descriptor's center, AB = p[1..2], AC = p[3..4]
+        const double sq = sqrt(u0), wb = sq * (1.0 - u1), wc = u1 * sq;
+        *lx = wb * p[1] + wc * p[3]; *ly = wb * p[2] + wc * p[4];
+        break;
+    }
+    case TRC_THERMAL_CYLINDER: {            // cylinder_sampling: zs, ths
+        *lz = u0 * p[2] - p[2] / 2.0;
+        double sp, cp;
+        trc_sincos_2pi(u1, &sp, &cp);
+        *nx = cp; *ny = sp; *nz = 0.0;
+        *lx = p[1] * cp; *ly = p[1] * sp;
+        break;
+    }
+    case TRC_THERMAL_FRUSTUM: {             // frustum_sampling(z0 = 0, z1 = depth): R, phi; the normal of normal_in=False
+        const double r0 = p[1], r1 = p[2];
+        const double cs = (r1 - r0) / p[3];
+        const double rs = sqrt((r1 * r1 - r0 * r0) * u0 + r0 * r0);
+        const double phi = p[4] + (p[5] - p[4]) * u1;
+        double sp, cp, st, ct;
+        trc_sincos(phi, &sp, &cp);
+        *lx = rs * cp; *ly = rs * sp; *lz = (rs - r0) / cs;
+        trc_sincos(atan(cs) - TRC_PI / 2.0, &st, &ct);
+        *nx = -(cp * st); *ny = -(sp * st); *nz = -ct;
+        break;
+    }
+    default: {                              // TRC_THERMAL_SPHERE, sphere_sampling: phis, cosths
+        double sp, cp;
+        trc_sincos_2pi(u0, &sp, &cp);
+        const double cc = 2.0 * u1 - 1.0;
+        const double ss = sqrt(1.0 - cc * cc);
+        *nx = ss * cp; *ny = ss * sp; *nz = cc;
+        *lx = p[1] * *nx; *ly = p[1] * *ny; *lz = p[1] * *nz;
+        break;
+    }
+    }
+}
+
+// The direction of a thermal ray about the unit vector n (sign * the shape's normal): polar angle theta, azimuth 2 pi u3, turned from
+// +z by the minimal rotation (rotate_z_to_normal(directions, normals), sources.py:802)
+TRC_HD void trc_thermal_dir(double theta, double u3, double nx, double ny, double nz, double *ax, double *ay, double *az) {
+    double st, ct, sx, cx;
+    trc_sincos(theta, &st, &ct);
+    trc_sincos_2pi(u3, &sx, &cx);
+    trc_rotate_z_to_normal(st * cx, st * sx, ct, nx, ny, nz, ax, ay, az);
+}
+
+// A thermal ray in the source's own frame from its uniforms: the point l, the direction a.  tab: the packed emittance table.
+TRC_HD void trc_thermal_local_u(const double *p, const double *tab, int n_tab, double u0, double u1, double u2, double u3,
+                                double *lx, double *ly, double *lz, double *ax, double *ay, double *az) {
+    double nx, ny, nz;
+    trc_thermal_point_u(p, u0, u1, lx, ly, lz, &nx, &ny, &nz);
+    const double sign = p[6];
+    trc_thermal_dir(trc_emittance_theta(tab, n_tab, u2), u3, sign * nx, sign * ny, sign * nz, ax, ay, az);
+}
+
+// Ray `rid` of a thermal descriptor: event 0, the four uniforms of block 0
+TRC_HD void trc_thermal_ray(const trc_source_desc *src, uint64_t seed, uint64_t rid, double *px, double *py, double *pz, double *dx,
+                            double *dy, double *dz) {
+    double u0, u1, u2, u3, lx, ly, lz, ax, ay, az;
+    trc_uniform_quad(seed, rid, 0, 0, &u0, &u1, &u2, &u3);
+    trc_thermal_local_u(src->p, trc_sunshape_table(src), (int)src->p[TRC_SUNSHAPE_P_N], u0, u1, u2, u3, &lx, &ly, &lz, &ax, &ay, &az);
+    trc_lamp_pose(src, lx, ly, lz, ax, ay, az, px, py, pz, dx, dy, dz);
+}
+
 // Ray `rid` of a lamp descriptor: event 0, the four uniforms of block 0 and -- ARC_VOLUME only -- the first of block 1 (no other
 // source draws from block 1: the x_cut redraws use blocks 2..4097, the spectrum block 0xFFFFFFFF).  KIND >= 0 promises
-// src->kind == KIND.
-template <int KIND>
+// src->kind == KIND; KIND < 0 reads the kind from the descriptor, and -- THERMAL -- knows the thermal emitters too.
+template <int KIND, bool THERMAL = (KIND < 0)>
 TRC_HD void trc_lamp_ray_t(const trc_source_desc *src, uint64_t seed, uint64_t rid, double *px, double *py, double *pz, double *dx,
                            double *dy, double *dz) {
     const int kind = KIND >= 0 ? KIND : src->kind;
+    if constexpr ((KIND < 0 && THERMAL) || KIND == TRC_SRC_EMIT_THERMAL) {
+        if (kind == TRC_SRC_EMIT_THERMAL) { trc_thermal_ray(src, seed, rid, px, py, pz, dx, dy, dz); return; }
+    }
     double u0, u1, u2, u3, u4 = 0.0;
     trc_uniform_quad(seed, rid, 0, 0, &u0, &u1, &u2, &u3);
     const double *tab = nullptr;
@@ -1985,7 +2198,7 @@ TRC_HD void trc_source_ray_t(const trc_source_desc *src, const double *buie, con
                              const trc_buie_fast *bf = nullptr) {
     // (the lamp kinds: compiled in only where the kind is promised -- the instances for any kind stay those that existed before
     // them, and the host never hands them a lamp)
-    if constexpr (KIND == TRC_SRC_ARC_VOLUME || KIND == TRC_SRC_EMIT_SPHERE || KIND == TRC_SRC_EMIT_CYLINDER) {
+    if constexpr (KIND == TRC_SRC_ARC_VOLUME || KIND == TRC_SRC_EMIT_SPHERE || KIND == TRC_SRC_EMIT_CYLINDER || KIND == TRC_SRC_EMIT_THERMAL) {
         trc_lamp_ray_t<KIND>(src, seed, rid, px, py, pz, dx, dy, dz);
         return;
     }
@@ -2103,9 +2316,13 @@ TRC_HD void trc_source_ray_t(const trc_source_desc *src, const double *buie, con
     *dz = rd[6] * ax + rd[7] * ay + rd[8] * az;
 }
 
+// Ray `rid` of a descriptor of any kind.  THERMAL = false: of any kind but the thermal emitter (the generation kernel of the other
+// kinds stays the code it was; the emitter has an instance of its own).
+template <bool THERMAL = true>
 TRC_HD void trc_source_ray(const trc_source_desc *src, const double *buie, const double *aur, uint64_t seed, uint64_t rid,
                            double *px, double *py, double *pz, double *dx, double *dy, double *dz) {
-    if (trc_src_kind_is_lamp(src->kind)) trc_lamp_ray_t<-1>(src, seed, rid, px, py, pz, dx, dy, dz);
+    if (THERMAL ? trc_src_kind_is_emitter(src->kind) : trc_src_kind_is_lamp(src->kind))
+        trc_lamp_ray_t<-1, THERMAL>(src, seed, rid, px, py, pz, dx, dy, dz);
     else trc_source_ray_t<-1, true>(src, buie, aur, seed, rid, px, py, pz, dx, dy, dz);
 }
 

@@ -268,6 +268,9 @@ enum trc_kernel_family {
     // names, their template arguments, their code -- stays what it was before these sources
     TRC_K_GEN_LAMP,             // k_s_gen_lamp<KIND>: k_s_gen<true, KIND>'s body for a lamp kind
     TRC_K_LAMP_COOP, TRC_K_LAMP_FAST,           // k_lamp_coop<THREADS, SPEC, CHART>, k_lamp_fast<THREADS, SPEC, CHART>: the megakernel's text (trc_mega.inc)
+    // the thermal emitters (TRC_SRC_EMIT_THERMAL; with the lamps: trc_src_kind_is_emitter): a generation kernel of its own name;
+    // the megakernel's instances are the lamps', whose trc_lamp_ray_t<-1> knows the kind
+    TRC_K_GEN_EMIT,             // k_s_gen_emit: k_s_gen<true, TRC_SRC_EMIT_THERMAL>'s body
     TRC_K_FAMILIES
 };
 struct trc_kernel_id { int family; int a[5]; };     // the template arguments in their order, bool as 0 / 1; unused: 0
@@ -282,7 +285,7 @@ static inline const char *trc_kernel_family_name(int family, const char **args) 
         {"", ""}, {"k_s_cull", "i"}, {"k_s_ucull", "i"}, {"k_s_fresh", "ibb"}, {"k_s_fresh2", "ibb"}, {"k_s_bounce", "ibbbb"}, {"k_s_bounce_coop", "bbb"},
         {"k_s_walk", "ib"}, {"k_s_gen", "bi"}, {"k_s_gen_src", "i"}, {"k_s_exact", ""}, {"k_s_shade", "bibbb"}, {"k_s_shade_c", "ibbbb"},
         {"k_s_shade_x", "bbbb"}, {"k_s_absorb", ""}, {"k_trace_coop", "ibbb"}, {"k_trace_fast", "ibbb"}, {"k_ord_bounce", "ibb"},
-        {"k_s_shade_p", "bbb"}, {"k_s_gen_lamp", "i"}, {"k_lamp_coop", "ibb"}, {"k_lamp_fast", "ibb"}};
+        {"k_s_shade_p", "bbb"}, {"k_s_gen_lamp", "i"}, {"k_lamp_coop", "ibb"}, {"k_lamp_fast", "ibb"}, {"k_s_gen_emit", ""}};
     if (family < 0 || family >= TRC_K_FAMILIES) family = TRC_K_NONE;
     if (args) *args = names[family][1];
     return names[family][0];
@@ -341,6 +344,7 @@ static inline bool trc_kernel_id_valid(const trc_kernel_id &id) {
     case TRC_K_GEN_LAMP: return trc_src_kind_is_lamp(a[0]);
     case TRC_K_LAMP_COOP: return a[0] == 512 || a[0] == 256;
     case TRC_K_LAMP_FAST: return a[0] == 256;
+    case TRC_K_GEN_EMIT: return true;
     default: return false;
     }
 }
@@ -449,7 +453,9 @@ static inline void trc_stream_form_general(trc_stream_forms &F, const trc_facts 
     const int k = F.src_kind;
     // fresh rays: the kinds with a generation kernel of their own, the others through k_s_gen<true, KIND>, given rays through <true, -1>
     // (the lamp kinds have no source plane, hence no footprint map: every fresh ray of theirs comes this way, through k_s_gen_lamp<KIND>)
+    // (the thermal emitters likewise, through k_s_gen_emit)
     const trc_kernel_id gen0 = trc_src_kind_is_lamp(k) ? trc_kid(TRC_K_GEN_LAMP, k)
+                             : k == TRC_SRC_EMIT_THERMAL ? trc_kid(TRC_K_GEN_EMIT)
                              : (k == TRC_SRC_BUIE_DISK || k == TRC_SRC_PILLBOX_DISK || k == TRC_SRC_PILLBOX_RECT) ? trc_kid(TRC_K_GEN_SRC, k)
                              : trc_kid(TRC_K_GEN, 1, (k == TRC_SRC_BUIE_RECT || trc_src_kind_is_sunshape(k)) ? k : -1);
     F.gen0 = {gen0, 256, 0};
@@ -576,7 +582,7 @@ static inline void trc_stream_form_bounce(trc_stream_forms &F, const trc_facts &
     F.use_fused = plan.mode != 1 && (f.knobs.bounce || big);
     // (k_s_bounce<.., FRESH> does not know the lamp kinds: their fresh rays take the general path, and trc_fast_choose_engine gives a
     // scene without one to the megakernel)
-    F.use_first = !trc_src_kind_is_lamp(F.src_kind) && (big || F.small_scene || (f.knobs.first && plan.mode != 1));
+    F.use_first = !trc_src_kind_is_emitter(F.src_kind) && (big || F.small_scene || (f.knobs.first && plan.mode != 1));
     if (!F.use_fused && !F.use_first) return;
     const int gridm = F.gridm;
     // One decision for the instance of the continued rays and that of the fresh ones: the tables go to LDS when an image with the
@@ -683,7 +689,7 @@ static inline MegaPlan mega_plan(const trc_scene_facts &sc, const trc_call_facts
         M.lds_scene = (M.lds + b_scene <= LDS_MAX_PLAIN) ? 1 : 0;
         if (M.lds_scene) M.lds += b_scene;
     }
-    if (trc_src_kind_is_lamp(c.src_kind)) M.id = trc_kid(M.m32 ? TRC_K_LAMP_COOP : TRC_K_LAMP_FAST, M.threads, c.spec, sc.chart);
+    if (trc_src_kind_is_emitter(c.src_kind)) M.id = trc_kid(M.m32 ? TRC_K_LAMP_COOP : TRC_K_LAMP_FAST, M.threads, c.spec, sc.chart);
     else M.id = trc_kid(M.m32 ? TRC_K_TRACE_COOP : TRC_K_TRACE_FAST, M.threads, c.spec, trc_src_kind_is_sunshape(c.src_kind), sc.chart);
     return M;
 }
@@ -696,7 +702,7 @@ static inline trc_engine_choice trc_fast_choose_engine(const trc_scene_facts &sc
     trc_engine_choice E = {{0, 0, true}, false, false};
     bool stream_ok = c.n >= TRC_STREAM_FEWEST_RAYS && stream_plan(sc, (c.flags & TRC_TRACE_ACCEL) != 0, K, &E.plan);
     // (a lamp's fresh rays need the general path, which a scene whose search tables do not fit LDS has not)
-    if (trc_src_kind_is_lamp(c.src_kind) && !E.plan.walk_ok) stream_ok = false;
+    if (trc_src_kind_is_emitter(c.src_kind) && !E.plan.walk_ok) stream_ok = false;
     // (rays that carry more, and optics that send two rays on from a hit, are the streaming form's alone: k_s_shade_x)
     const bool stream_only = c.carry || sc.splits;
     const bool force_stream = (c.flags & TRC_TRACE_STREAM) || stream_only;

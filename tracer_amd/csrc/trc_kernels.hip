@@ -936,11 +936,10 @@ static int kernel_grid_cap(const void *fn, int threads, size_t lds, int max_bpc,
 // ================================================================================================
 // source generation as a bundle (sources.*_bundle)
 // ================================================================================================
-__global__ __launch_bounds__(256) void k_source_generate(const trc_source_desc *src, long long n,
-                                                         unsigned long long seed, unsigned long long offset,
-                                                         double *x, double *y, double *z, double *dx, double *dy,
-                                                         double *dz, double *e, uint64_t *rid) {
-    __shared__ double l_buie[TRC_BUIE_STAGED];
+template <bool THERMAL>
+__device__ __forceinline__ void source_generate_body(const trc_source_desc *src, long long n, unsigned long long seed, unsigned long long offset,
+                                                     double *x, double *y, double *z, double *dx, double *dy, double *dz, double *e,
+                                                     uint64_t *rid, double *l_buie) {
     for (int i = threadIdx.x; i < TRC_BUIE_TABLE; i += blockDim.x) l_buie[i] = src->buie[i];
     if (threadIdx.x == 0 && (src->kind == TRC_SRC_BUIE_DISK || src->kind == TRC_SRC_BUIE_RECT)) trc_buie_aureole_consts(src->buie, l_buie + TRC_BUIE_TABLE);
     __syncthreads();
@@ -948,12 +947,35 @@ __global__ __launch_bounds__(256) void k_source_generate(const trc_source_desc *
          i += (long long)gridDim.x * blockDim.x) {
         unsigned long long r = offset + (unsigned long long)i;
         double px, py, pz, qx, qy, qz;
-        trc_source_ray(src, l_buie, l_buie + TRC_BUIE_TABLE, seed, r, &px, &py, &pz, &qx, &qy, &qz);
+        trc_source_ray<THERMAL>(src, l_buie, l_buie + TRC_BUIE_TABLE, seed, r, &px, &py, &pz, &qx, &qy, &qz);
         x[i] = px; y[i] = py; z[i] = pz;
         dx[i] = qx; dy[i] = qy; dz[i] = qz;
         e[i] = src->energy;
         if (rid) rid[i] = r;
     }
+}
+
+// every kind but the thermal emitter ...
+__global__ __launch_bounds__(256) void k_source_generate(const trc_source_desc *src, long long n,
+                                                         unsigned long long seed, unsigned long long offset,
+                                                         double *x, double *y, double *z, double *dx, double *dy,
+                                                         double *dz, double *e, uint64_t *rid) {
+    __shared__ double l_buie[TRC_BUIE_STAGED];
+    source_generate_body<false>(src, n, seed, offset, x, y, z, dx, dy, dz, e, rid, l_buie);
+}
+
+// ... and the thermal emitter (TRC_SRC_EMIT_THERMAL), whose sampler would cost the kernel above two waves of occupancy
+__global__ __launch_bounds__(256) void k_source_generate_emit(const trc_source_desc *src, long long n,
+                                                              unsigned long long seed, unsigned long long offset,
+                                                              double *x, double *y, double *z, double *dx, double *dy,
+                                                              double *dz, double *e, uint64_t *rid) {
+    __shared__ double l_buie[TRC_BUIE_STAGED];
+    source_generate_body<true>(src, n, seed, offset, x, y, z, dx, dy, dz, e, rid, l_buie);
+}
+
+// the generation kernel of a descriptor's kind (host: src is the caller's copy)
+static auto source_generate_kernel(const trc_source_desc *src) -> decltype(&k_source_generate) {
+    return src->kind == TRC_SRC_EMIT_THERMAL ? k_source_generate_emit : k_source_generate;
 }
 
 // float32 start points as k_s_cull evaluates them (trc_source_start32)
@@ -2124,6 +2146,7 @@ struct trc_sunshape {
     int32_t id, n;
     std::vector<double> tab;        // theta | g | cdf (trc_sunshape_theta layout)
     double theta_c, u_c;
+    int packing = 0;                // which create function packed it: 0 trc_sunshape_create, 1 trc_angle_table_create, 2 trc_emittance_table_create
     DevBuf<double> d_tab;
 };
 
@@ -2217,6 +2240,7 @@ extern "C" int trc_angle_table_create(trc_ctx *ctx, int32_t n, const double *ang
     if (!trc_angle_table_pack(n, angle, density, t->tab.data())) return trc_fail(TRC_ERR_INVALID, "trc_angle_table_create: the table has no mass");
     t->device = ctx->device; t->n = n;
     t->theta_c = angle[n - 1]; t->u_c = 1.0;
+    t->packing = 1;
     HIP_TRY(hipSetDevice(ctx->device));
     TRC_TRY(dev_upload(t->d_tab, t->tab.data(), t->tab.size(), "angle table upload failed"));
     std::lock_guard<std::mutex> lk(g_sun_mu);
@@ -2227,8 +2251,34 @@ extern "C" int trc_angle_table_create(trc_ctx *ctx, int32_t n, const double *ang
     return TRC_OK;
 }
 
-// the kinds whose descriptor names a table: the tabulated sunshapes, and the arc volume with its polar table
-static bool source_is_sunshape(int kind) { return kind == TRC_SRC_SUNSHAPE_DISK || kind == TRC_SRC_SUNSHAPE_RECT || kind == TRC_SRC_ARC_VOLUME; }
+// the emittance table of a thermal emitter (TRC_SRC_EMIT_THERMAL): a trc_sunshape packed by trc_emittance_pack
+extern "C" int trc_emittance_table_create(trc_ctx *ctx, int32_t n, const double *theta, const double *eps, trc_sunshape **out) {
+    if (!ctx || !out) return trc_fail(TRC_ERR_INVALID, "trc_emittance_table_create: bad arguments");
+    *out = nullptr;
+    if (const char *fault = trc_emittance_table_fault(n, theta, eps)) return trc_fail(TRC_ERR_INVALID, "trc_emittance_table_create: %s", fault);
+    std::unique_ptr<trc_sunshape> t(new (std::nothrow) trc_sunshape());
+    if (!t) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
+    t->tab.assign((size_t)3 * n, 0.0);
+    double mass = 0.0;
+    if (!trc_emittance_pack(n, theta, eps, t->tab.data(), &mass)) return trc_fail(TRC_ERR_INVALID, "trc_emittance_table_create: the table has no mass");
+    t->device = ctx->device; t->n = n;
+    t->theta_c = t->tab[n - 1]; t->u_c = mass;
+    t->packing = 2;
+    HIP_TRY(hipSetDevice(ctx->device));
+    TRC_TRY(dev_upload(t->d_tab, t->tab.data(), t->tab.size(), "emittance table upload failed"));
+    std::lock_guard<std::mutex> lk(g_sun_mu);
+    if (g_sun_next == INT32_MAX) return trc_fail(TRC_ERR_CAPACITY, "trc_emittance_table_create: table ids exhausted");
+    t->id = g_sun_next++;
+    g_sun[t->id] = t.get();
+    *out = t.release();
+    return TRC_OK;
+}
+
+// the kinds whose descriptor names a table: the tabulated sunshapes, the arc volume with its polar table and the thermal emitter with
+// its emittance table
+static bool source_is_sunshape(int kind) {
+    return kind == TRC_SRC_SUNSHAPE_DISK || kind == TRC_SRC_SUNSHAPE_RECT || kind == TRC_SRC_ARC_VOLUME || kind == TRC_SRC_EMIT_THERMAL;
+}
 
 // A sunshape descriptor as the kernels read it: `tmp` = *src with theta_c, u_c, n in p[] and the table's device address in
 // buie[0]; `src` then points to it.  Other kinds are left as they are.  A host-side lookup: no device traffic.
@@ -2239,9 +2289,20 @@ static int source_resolve(trc_ctx *ctx, const trc_source_desc *&src, trc_source_
     if (it == g_sun.end()) return trc_fail(TRC_ERR_INVALID, "%s: the source names sunshape table %d, which does not exist (destroyed?)", who, src->table);
     const trc_sunshape *t = it->second;
     if (ctx && t->device != ctx->device) return trc_fail(TRC_ERR_INVALID, "%s: sunshape table %d lives on another device", who, src->table);
+    if (src->kind == TRC_SRC_EMIT_THERMAL) {       // (the one kind that checks the packing: its sampler solves another equation)
+        if (t->packing != 2)
+            return trc_fail(TRC_ERR_INVALID, "%s: table %d is not an emittance table (trc_emittance_table_create)", who, src->table);
+        const int shape = (int)src->p[0];
+        if (!(src->p[0] >= TRC_THERMAL_DISK && src->p[0] <= TRC_THERMAL_SPHERE) || (double)shape != src->p[0])
+            return trc_fail(TRC_ERR_INVALID, "%s: a thermal emitter has no shape %g", who, src->p[0]);
+        if (shape == TRC_THERMAL_FRUSTUM && src->p[1] == src->p[2])
+            return trc_fail(TRC_ERR_INVALID, "%s: a thermal frustum needs r0 != r1 (use the cylinder)", who);
+    }
     tmp = *src;
-    tmp.p[TRC_SUNSHAPE_P_THETA_C] = t->theta_c;
-    tmp.p[TRC_SUNSHAPE_P_U_C] = t->u_c;
+    if (src->kind != TRC_SRC_EMIT_THERMAL) {        // (a thermal emitter keeps its shape parameters and its sign there)
+        tmp.p[TRC_SUNSHAPE_P_THETA_C] = t->theta_c;
+        tmp.p[TRC_SUNSHAPE_P_U_C] = t->u_c;
+    }
     tmp.p[TRC_SUNSHAPE_P_N] = (double)t->n;
     memset(tmp.buie, 0, sizeof(tmp.buie));
     tmp.buie[0] = __builtin_bit_cast(double, (uint64_t)(uintptr_t)t->d_tab.get());
@@ -2250,7 +2311,7 @@ static int source_resolve(trc_ctx *ctx, const trc_source_desc *&src, trc_source_
 }
 
 static int source_kind_check(const trc_source_desc *src) {
-    if (src->kind < TRC_SRC_PILLBOX_DISK || src->kind > TRC_SRC_EMIT_CYLINDER)
+    if (src->kind < TRC_SRC_PILLBOX_DISK || src->kind > TRC_SRC_EMIT_THERMAL)
         return trc_fail(TRC_ERR_UNSUPPORTED, "source kind %d is not in the native table", src->kind);
     return TRC_OK;
 }
@@ -2313,7 +2374,7 @@ extern "C" int trc_source_generate(trc_ctx *ctx, const trc_source_desc *src, int
     }
     long long grid = (n + 255) / 256;
     if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(k_source_generate, dim3((unsigned)grid), dim3(256), 0, ctx->stream, d_src.get(), (long long)n,
+    hipLaunchKernelGGL(source_generate_kernel(src), dim3((unsigned)grid), dim3(256), 0, ctx->stream, d_src.get(), (long long)n,
                        (unsigned long long)seed, (unsigned long long)ray_offset, d[0], d[1], d[2], d[3], d[4], d[5],
                        d[6], d_rid);
     hipError_t se = hipStreamSynchronize(ctx->stream);
@@ -2874,7 +2935,7 @@ static int ordered_level0(OrdCall &C, const trc_rays *in, const trc_source_desc 
     DevBuf<trc_source_desc> d_src;
     if (src) {
         TRC_TRY(upload_source(src, d_src));
-        hipLaunchKernelGGL(k_source_generate, dim3((unsigned)g0), dim3(256), 0, ctx->stream, d_src.get(), (long long)n,
+        hipLaunchKernelGGL(source_generate_kernel(src), dim3((unsigned)g0), dim3(256), 0, ctx->stream, d_src.get(), (long long)n,
                            (unsigned long long)C.seed, (unsigned long long)ray_offset, B0.x, B0.y, B0.z, B0.dx, B0.dy, B0.dz, B0.e, B0.rid);
         if (spec.desc) {     // level 0 carries the wavelengths the source's spectrum gives its rays, and their index
             TRC_TRY(spectrum_fill(ctx, spec.desc, spec.tab, n, C.seed, ray_offset, B0.wl, B0.ref));

@@ -160,6 +160,12 @@ __global__ __launch_bounds__(256) void k_s_gen_lamp(StreamParams S) {
     s_gen_body<true, KIND>(S, l_bf);
 }
 
+// the thermal emitter compiled in (trc_thermal_ray): k_s_gen<true, TRC_SRC_EMIT_THERMAL>'s body under a name of its own, as the lamps'
+__global__ __launch_bounds__(256) void k_s_gen_emit(StreamParams S) {
+    __shared__ trc_buie_fast l_bf;
+    s_gen_body<true, TRC_SRC_EMIT_THERMAL>(S, l_bf);
+}
+
 // one source kind compiled in (Buie disc, pillbox disc / rectangle -- the Buie rectangle would spill): fits 128 registers, and
 // four waves per SIMD instead of three are worth 6 % of the kernel
 template <int KIND>
@@ -2182,6 +2188,7 @@ static const void *source_kernel_fn(const trc_kernel_id &id) {
 // ... k_s_gen, k_s_gen_src
 static const void *gen_kernel_fn(const trc_kernel_id &id) {
     const int kind = id.family == TRC_K_GEN ? id.a[1] : id.a[0];
+    if (id.family == TRC_K_GEN_EMIT) return (const void *)k_s_gen_emit;
     if (id.family == TRC_K_GEN_LAMP)
         return kind == TRC_SRC_ARC_VOLUME ? (const void *)k_s_gen_lamp<TRC_SRC_ARC_VOLUME> : kind == TRC_SRC_EMIT_SPHERE ? (const void *)k_s_gen_lamp<TRC_SRC_EMIT_SPHERE>
              : kind == TRC_SRC_EMIT_CYLINDER ? (const void *)k_s_gen_lamp<TRC_SRC_EMIT_CYLINDER> : nullptr;
@@ -2232,7 +2239,7 @@ static const void *shade_kernel_fn(const trc_kernel_id &id) {
 static const void *stream_kernel_fn(const trc_kernel_id &id) {
     switch (id.family) {
     case TRC_K_CULL: case TRC_K_UCULL: case TRC_K_FRESH: case TRC_K_FRESH2: return source_kernel_fn(id);
-    case TRC_K_GEN: case TRC_K_GEN_SRC: case TRC_K_GEN_LAMP: return gen_kernel_fn(id);
+    case TRC_K_GEN: case TRC_K_GEN_SRC: case TRC_K_GEN_LAMP: case TRC_K_GEN_EMIT: return gen_kernel_fn(id);
     case TRC_K_BOUNCE: case TRC_K_BOUNCE_COOP: return bounce_kernel_fn(id);
     case TRC_K_WALK: return id.a[0] != SW_THREADS ? nullptr : id.a[1] ? (const void *)k_s_walk<SW_THREADS, true> : (const void *)k_s_walk<SW_THREADS, false>;
     case TRC_K_EXACT: return (const void *)k_s_exact;

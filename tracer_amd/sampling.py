@@ -3,7 +3,9 @@ Host samplers with the names, arguments and return values of the reference's ray
 (models/solar_simulator.py) and scene scripts import: PW_linear_distribution (:6-52), disk_sampling (:286-295), cylinder_sampling
 (:365-382), sphere_sampling (:426-444, the surface only), Lambertian_directions_sampling (:446-459) -- and
 isotropic_directions_sampling, which the model calls and the reference defines nowhere (defined here by its name: uniform in solid
-angle over the cone).
+angle over the cone).  For the thermal emitters (sources.spectral_band_axisymmetrical_thermal_emission_source): PW_lincos_distribution
+(:99-122), PW_lincossin_distribution (:124-148), triangle_sampling (:308-331), frustum_sampling (:384-400, the surface only) and
+rectangle_sampling (:297-306) as it is meant -- the reference's raises NameError.
 
 Functions of numpy's global generator that draw what the reference draws, in its order, so that under the same numpy.random.seed
 they return its arrays.  The device sources (sources.arc_volume_bundle, sphere_emitter_bundle, cylinder_emitter_bundle) sample the
@@ -67,6 +69,69 @@ class PW_linear_distribution(object):
         return x_samples, N.ones(len(R))
 
 
+class PW_lincos_distribution(PW_linear_distribution):
+    """
+    The density ys(x) cos(x), ys linear between the points, sampled as the reference samples it: x from the piecewise-linear
+    interpolation of the nodes' ys cos(xs), each sample weighted by the true density over that proposal, the weights rescaled to
+    the sum ns.
+    """
+    def __init__(self, xs, ys):
+        xs, ys = N.asarray(xs, dtype=float), N.asarray(ys, dtype=float)
+        PW_linear_distribution.__init__(self, xs, ys * N.cos(xs))
+        self.a_cos = (ys[1:] - ys[:-1]) / (xs[1:] - xs[:-1])
+        self.b_cos = ys[:-1] - self.a_cos * xs[:-1]
+        self.integ_cos = ys[1:] * N.sin(xs[1:]) - ys[:-1] * N.sin(xs[:-1]) + self.a_cos * (N.cos(xs[1:]) - N.cos(xs[:-1]))
+        self.tot_integ_cos = N.sum(self.integ_cos)
+
+    def f(self, x):
+        loc = self.find_slice(x)
+        return (self.a_cos[loc] * x + self.b_cos[loc]) * N.cos(x)
+
+    def PDF_cos(self, x):
+        return self.f(x) / self.tot_integ_cos
+
+    def sample(self, ns):
+        x_s, weights_s = PW_linear_distribution.sample(self, ns)
+        weights = weights_s * self.PDF_cos(x_s) / self.PDF(x_s)
+        weights *= ns / N.sum(weights)
+        return x_s, weights
+
+
+class PW_lincossin_distribution(PW_linear_distribution):
+    """
+    The density ys(x) cos(x) sin(x) -- the polar angle of a surface of directional emittance ys -- sampled as the reference samples
+    it: x from the piecewise-linear interpolation of the nodes' ys cos sin, weighted by the true density over that proposal, the
+    weights rescaled to the sum ns.
+
+    tot_integ_cossin is kept as the reference computes it: the antiderivative at every node with the slope of the interval to the
+    node's right (the last node: to its left), for both ends of an interval.  Where the slope changes between intervals this is not
+    the integral (0.9690 for a table whose integral is 0.3504).  It only scales weights that sample() renormalises,
+    so the samples and weights are the reference's; nothing here takes it for the mass -- sources.EmittanceTable.mass is that.
+    """
+    def __init__(self, xs, ys):
+        xs, ys = N.asarray(xs, dtype=float), N.asarray(ys, dtype=float)
+        PW_linear_distribution.__init__(self, xs, ys * N.cos(xs) * N.sin(xs))
+        self.a_cossin = (ys[1:] - ys[:-1]) / (xs[1:] - xs[:-1])
+        self.b_cossin = ys[:-1] - self.a_cossin * xs[:-1]
+        slope_at_node = N.hstack([self.a_cossin, self.a_cossin[-1]])
+        integral = ys / 2. * N.sin(xs) ** 2. - slope_at_node / 4. * (xs - N.sin(xs) * N.cos(xs))
+        self.integ_cossin = integral[1:] - integral[:-1]
+        self.tot_integ_cossin = N.sum(self.integ_cossin)
+
+    def f(self, x):
+        loc = self.find_slice(x)
+        return (self.a_cossin[loc] * x + self.b_cossin[loc]) * N.cos(x) * N.sin(x)
+
+    def PDF_cossin(self, x):
+        return self.f(x) / self.tot_integ_cossin
+
+    def sample(self, ns):
+        x_s, weights_s = PW_linear_distribution.sample(self, ns)
+        weights = weights_s * self.PDF_cossin(x_s) / self.PDF(x_s)
+        weights *= ns / N.sum(weights)
+        return x_s, weights
+
+
 def _flat_normals(ns, normal_up):
     normals = N.vstack([N.zeros(ns), N.zeros(ns), N.ones(ns)])
     return normals if normal_up else -normals
@@ -80,6 +145,51 @@ def disk_sampling(r_ext, ns, normals=False, normal_up=True):
     positions = N.vstack([rs * N.cos(ths), rs * N.sin(ths), N.zeros(ns)])
     if normals:
         return positions, _flat_normals(ns, normal_up)
+    return positions
+
+
+def rectangle_sampling(x, y, ns, normals=False, normal_up=True):
+    """(3, ns) points uniform on the rectangle of x by y about the origin in the plane z = 0 (draws: xs over [-x/2, x/2], then ys over
+    [-y/2, y/2]; the points are (xs, ys, 0), as the device's rectangle, TRC_THERMAL_RECT, has them); with normals=True also their
+    normals.  The reference's function names variables it does not have and raises NameError, so it has no behaviour to keep: this
+    is what its arguments say."""
+    xs = N.random.uniform(low=-x / 2., high=x / 2., size=ns)
+    ys = N.random.uniform(low=-y / 2., high=y / 2., size=ns)
+    positions = N.vstack((xs, ys, N.zeros(ns)))
+    if normals:
+        return positions, _flat_normals(ns, normal_up)
+    return positions
+
+
+def triangle_sampling(A, B, C, ns, normals=False, normal_up=True):
+    """(3, ns) points uniform on the triangle A, B, C (draws: r1, then r2; the point A + sqrt(r1) (1 - r2) AB + r2 sqrt(r1) AC);
+    with normals=True also the normals, which are +z or -z whatever the triangle: it is meant to lie in a plane of constant z."""
+    A, B, C = (N.asarray(v, dtype=float) for v in (A, B, C))
+    r1 = N.vstack(N.random.uniform(size=ns))
+    r2 = N.vstack(N.random.uniform(size=ns))
+    sqrtr1 = N.sqrt(r1)
+    positions = (A + sqrtr1 * (1. - r2) * (B - A) + r2 * sqrtr1 * (C - A)).T
+    if normals:
+        return positions, _flat_normals(ns, normal_up)
+    return positions
+
+
+def frustum_sampling(r0, r1, z0, z1, ns, normals=False, normal_in=False, volume=False, angular_span=[0., 2. * N.pi]):
+    """(3, ns) points uniform on the wall of the frustum of radius r0 at height 0 and r1 at height z1 - z0 about z, within the
+    angular span (draws: R, then the azimuths): r = sqrt((r1^2 - r0^2) R + r0^2), z = (r - r0) / c with c = (r1 - r0) / (z1 - z0).
+    With normals=True also the wall's normals, as the reference gives them: (cos phi sin ts, sin phi sin ts, cos ts) with ts =
+    arctan(c) - pi/2 for normal_in, its opposite otherwise.  The volume form does not run in the reference and is not offered."""
+    if volume:
+        raise NotImplementedError("frustum_sampling(volume=True) does not run in the reference (undefined names); not offered")
+    c = (r1 - r0) / (z1 - z0)
+    R = N.random.uniform(size=ns)
+    phi = N.random.uniform(low=angular_span[0], high=angular_span[1], size=ns)
+    rs = N.sqrt((r1 ** 2. - r0 ** 2.) * R + r0 ** 2.)
+    positions = N.array([rs * N.cos(phi), rs * N.sin(phi), (rs - r0) / c])
+    if normals:
+        theta_s = N.arctan(c) - N.pi / 2.
+        norms = N.array([N.cos(phi) * N.sin(theta_s), N.sin(phi) * N.sin(theta_s), N.ones(ns) * N.cos(theta_s)])
+        return positions, (norms if normal_in else -norms)
     return positions
 
 

@@ -727,6 +727,310 @@ def cylinder_emitter_bundle(num_rays, radius, height, center, direction, power, 
     return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum)
 
 
+# -- thermal emitters: rays from a surface with a tabulated directional band emittance --------------------------------------------
+def _trapezoid(y, x):
+    return N.sum((x[1:] - x[:-1]) * (y[1:] + y[:-1]) / 2.)
+
+
+def _emittance_G(a, e0, x0, th):
+    """the integral of (e0 + a (t - x0)) cos(t) sin(t) over [x0, th], written in d = th - x0 so that no two large terms cancel
+    (trc_emittance_G, csrc/trc_core.h: the same expression)"""
+    d = th - x0
+    s0, c0, s, c = N.sin(x0), N.cos(x0), N.sin(th), N.cos(th)
+    x = 2. * d
+    x2 = x * x
+    small = d < 0.0625
+    w = N.where(small, 0.5 * x * x2 * (-1. / 6. + x2 * (1. / 120. + x2 * (-1. / 5040. + x2 * (1. / 362880. - x2 * (1. / 39916800.))))),
+                N.sin(d) * N.cos(d) - d)                                      # sin(d) cos(d) - d
+    sd = N.where(small, d * (1. + d * d * (-1. / 6. + d * d * (1. / 120. + d * d * (-1. / 5040. + d * d * (1. / 362880.))))), s * c0 - c * s0)
+    return e0 / 2. * sd * (s * c0 + c * s0) + a / 4. * ((c - s) * (c + s) * w + sd * sd * (2. * s * c))
+
+
+def check_emittance_table(thetas, emittance):
+    """The emittance table of a thermal emitter as two float64 arrays; ValueError unless it has 2..4096 points, finite angles strictly
+    increasing within [0, pi/2], finite non-negative emittances and a positive mass (the checks of trc_emittance_table_create).  A
+    last angle up to 5e-9 beyond pi/2 -- pi/2 as a table of 8 decimals states it -- is returned as pi/2, as the library reads it."""
+    a = N.ascontiguousarray(N.ravel(N.asarray(thetas, dtype=float)))
+    e = N.ascontiguousarray(N.ravel(N.asarray(emittance, dtype=float)))
+    if a.shape != e.shape:
+        raise ValueError("emittance table: %d angles but %d emittances" % (a.size, e.size))
+    if not 2 <= a.size <= _cabi.SUNSHAPE_MAX_POINTS:
+        raise ValueError("emittance table: 2..%d points, got %d" % (_cabi.SUNSHAPE_MAX_POINTS, a.size))
+    if not N.all(N.isfinite(a)):
+        raise ValueError("emittance table: the angles must be finite and strictly increasing")
+    if not (a[0] >= 0. and a[-1] <= _cabi.EMITTANCE_THETA_MAX):
+        raise ValueError("emittance table: the angles must lie in [0, pi/2]")
+    a = N.minimum(a, N.pi / 2.)
+    if not N.all(a[1:] > a[:-1]):
+        raise ValueError("emittance table: the angles must be finite and strictly increasing")
+    if not N.all(N.isfinite(e)) or N.any(e < 0.):
+        raise ValueError("emittance table: the emittances must be finite and non-negative")
+    mass = _emittance_mass(a, e)
+    if not (mass > 0. and N.isfinite(mass)):
+        raise ValueError("emittance table: the table has no mass")
+    return a, e
+
+
+def _emittance_mass(a, e):
+    """the integral of eps(theta) cos(theta) sin(theta) over the table, eps linear between the points: every interval with its own
+    slope at both its ends (trc_emittance_pack's M)"""
+    slope = (e[1:] - e[:-1]) / (a[1:] - a[:-1])
+    return N.sum(N.maximum(_emittance_G(slope, e[:-1], a[:-1], a[1:]), 0.))
+
+
+class EmittanceTable(SunshapeTable):
+    """A checked emittance table of a thermal emitter: the directional band emittance over [0, pi/2], linear between the points.  On
+    the device it is a table like a sunshape's (trc_emittance_table_create: the same object, the same ids), packed as theta | eps / M
+    | cdf with the analytic integrals of eps cos sin."""
+    def __init__(self, thetas, emittance):
+        self.angles, self.intensity = check_emittance_table(thetas, emittance)
+        self.mass = float(_emittance_mass(self.angles, self.intensity))
+        self._handle = None
+        self._lib = None
+        self._id = 0
+
+    def _create(self, ctx, handle):
+        return ctx.lib.trc_emittance_table_create(ctx.handle, self.angles.size, _cabi.ptr(self.angles), _cabi.ptr(self.intensity),
+                                                  C.byref(handle))
+
+
+_emittance_tables = {}
+
+
+def emittance_table(thetas, emittance):
+    """the EmittanceTable of this content (cached like angle_table)"""
+    a, e = check_emittance_table(thetas, emittance)
+    key = (a.tobytes(), e.tobytes())
+    t = _emittance_tables.get(key)
+    if t is None:
+        if len(_emittance_tables) > 64:
+            _emittance_tables.clear()
+        t = _emittance_tables[key] = EmittanceTable(a, e)
+    return t
+
+
+def _shape_kwargs(what, kwargs, names, flip_name):
+    """the shape's arguments by the reference samplers' names; (values, -1. if the flag that turns the normal is set else 1.)"""
+    kwargs = dict(kwargs or {})
+    flip = kwargs.pop(flip_name, flip_name == 'normal_up')
+    for k in ('ns', 'normals'):
+        kwargs.pop(k, None)
+    if kwargs.pop('volume', False):
+        raise ValueError("%s: a thermal emitter is a surface, not a volume" % what)
+    missing = [k for k in names if k not in kwargs and k != 'angular_span']
+    extra = [k for k in kwargs if k not in names]
+    if missing or extra:
+        raise ValueError("%s: the shape takes %s; missing %s, unknown %s" % (what, list(names), missing, extra))
+    turned = (not flip) if flip_name == 'normal_up' else bool(flip)
+    return kwargs, (-1. if turned else 1.)
+
+
+def _thermal_shape(what, shape):
+    """(p[0..5] of the descriptor, the area, the offset of the local origin) of gray_source's shape dictionary {'type': ..., 'kwargs':
+    {...}} -- the kwargs by the names of the reference's ray_trace_utils.sampling.<type>_sampling -- and the sign its normal flag gives"""
+    try:
+        kind, kwargs = shape['type'], shape.get('kwargs', {})
+    except (TypeError, KeyError):
+        raise ValueError("%s: shape must be a dictionary {'type': ..., 'kwargs': {...}}" % what)
+    origin = N.zeros(3)
+
+    def positive(**lengths):
+        for name, val in lengths.items():
+            if not (N.isfinite(val) and val > 0.):
+                raise ValueError("%s: %s must be positive and finite, got %r" % (what, name, val))
+
+    if kind == 'disk':
+        kw, sign = _shape_kwargs(what, kwargs, ('r_ext',), 'normal_up')
+        R = float(kw['r_ext'])
+        positive(r_ext=R)
+        p, area = [_cabi.THERMAL_DISK, R, 0., 0., 0., 0.], N.pi * R ** 2.
+    elif kind == 'rectangle':
+        kw, sign = _shape_kwargs(what, kwargs, ('x', 'y'), 'normal_up')
+        X, Y = float(kw['x']), float(kw['y'])
+        positive(x=X, y=Y)
+        p, area = [_cabi.THERMAL_RECT, X, Y, 0., 0., 0.], X * Y
+    elif kind == 'triangle':
+        kw, sign = _shape_kwargs(what, kwargs, ('A', 'B', 'C'), 'normal_up')
+        A, B, Cc = (N.ravel(N.asarray(kw[k], dtype=float)) for k in ('A', 'B', 'C'))
+        if not (A.shape == B.shape == Cc.shape == (3,)) or not N.all(N.isfinite(N.hstack((A, B, Cc)))):
+            raise ValueError("%s: A, B and C are three finite 3-vectors" % what)
+        if not (A[2] == B[2] == Cc[2]):
+            raise ValueError("%s: the triangle must lie in a plane of constant local z (its normal is +z whatever it is)" % what)
+        AB, AC = B - A, Cc - A
+        area = 0.5 * abs(AB[0] * AC[1] - AB[1] * AC[0])
+        positive(area=area)
+        p, origin = [_cabi.THERMAL_TRIANGLE, AB[0], AB[1], AC[0], AC[1], 0.], A
+    elif kind == 'cylinder':
+        kw, sign = _shape_kwargs(what, kwargs, ('r_ext', 'h'), 'normal_in')
+        R, h = float(kw['r_ext']), float(kw['h'])
+        positive(r_ext=R, h=h)
+        p, area = [_cabi.THERMAL_CYLINDER, R, h, 0., 0., 0.], 2. * N.pi * R * h
+    elif kind == 'frustum':
+        kw, sign = _shape_kwargs(what, kwargs, ('r0', 'r1', 'z0', 'z1', 'angular_span'), 'normal_in')
+        r0, r1, depth = float(kw['r0']), float(kw['r1']), float(kw['z1']) - float(kw['z0'])
+        s0, s1 = (float(v) for v in kw.get('angular_span', (0., 2. * N.pi)))
+        if not (N.isfinite(r0) and N.isfinite(r1) and r0 >= 0. and r1 >= 0.):
+            raise ValueError("%s: r0 and r1 must be finite and not negative" % what)
+        if r0 == r1:
+            raise ValueError("%s: a frustum needs r0 != r1; use the cylinder" % what)
+        positive(depth=depth, angular_span=s1 - s0)
+        p = [_cabi.THERMAL_FRUSTUM, r0, r1, depth, s0, s1]
+        area = (s1 - s0) / 2. * (r0 + r1) * N.sqrt((r1 - r0) ** 2. + depth ** 2.)
+    elif kind == 'sphere':
+        kw, sign = _shape_kwargs(what, kwargs, ('r_ext',), 'normal_in')
+        R = float(kw['r_ext'])
+        positive(r_ext=R)
+        p, area = [_cabi.THERMAL_SPHERE, R, 0., 0., 0., 0.], 4. * N.pi * R ** 2.
+    else:
+        raise ValueError("%s: shape type %r is not one of disk, rectangle, triangle, cylinder, frustum, sphere" % (what, kind))
+    return p, float(area), origin, sign
+
+
+def _thermal_desc(what, shape, table, center, rot_pos, rot_dir, energy, rays_in):
+    p, area, origin, sign = _thermal_shape(what, shape)
+    if rays_in:
+        sign = -sign
+    center = N.ravel(N.asarray(center, dtype=float))
+    if center.shape != (3,):
+        raise ValueError("%s: the location is a 3-vector" % what)
+    center = center + N.dot(rot_pos, origin)
+    return _fill_source(_cabi.SRC_EMIT_THERMAL, center, rot_pos, rot_dir, p + [sign, 0.], energy(area)), area
+
+
+def band_radiance(T, band):
+    """(L_band, wl_avg, wls) of a black body at T (K) in band = (lo, hi) (m) as the reference computes them (sources.py:788-790,
+    :808): Planck's law on linspace(lo, hi, int((hi - lo) / 1e-9)), its trapezoid integral, and the radiance-weighted mean of the
+    grid's wavelengths"""
+    from .source_spectrum import planck
+    T = float(T)
+    lo, hi = float(band[0]), float(band[1])
+    if not T > 0.:
+        raise ValueError("band_radiance: T must be positive")
+    if not (hi > lo > 0.) or int((hi - lo) / 1e-9) < 2:
+        raise ValueError("band_radiance: the band must be 0 < lo < hi, at least 2e-9 m wide")
+    wls = N.linspace(lo, hi, int((hi - lo) / 1e-9))
+    B = planck(wls, T)
+    return _trapezoid(B, wls), N.sum(wls * B) / N.sum(B), wls
+
+
+def thermal_emitter_bundle(num_rays, shape, thetas, band_emittance, T, band, center, direction, ref_index=1., rays_in=False,
+                           spectrum='band_average', quadrature='trapezoid', seed=None, ray_offset=0, rotation=None):
+    """
+    Thermal emission of a wall at temperature T (K) with the directional band emittance eps(theta) in the spectral band (lo, hi) (m),
+    into the medium of index ref_index: what the reference's spectral_band_axisymmetrical_thermal_emission_source (sources.py:771-813)
+    models, with the points, normals and directions of every ray drawn on the device from its Philox stream -- the bundle stays
+    pending.  shape: gray_source's dictionary {'type': 'disk' | 'rectangle' | 'triangle' | 'cylinder' | 'frustum' | 'sphere',
+    'kwargs': {...}}, the kwargs by the names of ray_trace_utils.sampling.<type>_sampling; the shape is posed at `center` by the
+    minimal rotation of +z to `direction`, or by `rotation` (3, 3).  Rays leave along the shape's normal, against it with rays_in.
+
+    thetas, band_emittance: the table, eps linear between its points; a scalar band_emittance is a constant table over thetas.  The
+    polar angle about the normal has the density eps(theta) cos(theta) sin(theta).  The reference draws it from a piecewise-linear
+    proposal and weights the rays; here the analytic CDF is inverted per ray, so every ray carries the same energy:
+    exitance * area / num_rays, exitance = 2 pi L_band * integral of eps cos sin, L_band the reference's (band_radiance).
+    quadrature='trapezoid' takes the integral as the reference does (:798, the trapezoid rule over the nodes -- the default, for
+    parity), 'exact' the analytic integral of the table.  A table whose node trapezoid is not positive (two points over [0, pi/2])
+    is a ValueError under 'trapezoid'.
+
+    spectrum: 'band_average' -- every ray has the reference's wl_avg (:808); 'planck' -- one wavelength per ray drawn from Planck's law
+    in the band (SourceSpectrum.planck); a SourceSpectrum or None is taken as given.
+    Draws of ray i (event 0, block 0): u0, u1 the point in the sampler's draw order, u2 the polar angle, u3 the azimuth.
+    """
+    what = 'thermal_emitter_bundle'
+    if int(num_rays) < 0:
+        raise ValueError("%s: num_rays must not be negative" % what)
+    thetas = N.ravel(N.asarray(thetas, dtype=float))
+    eps = N.asarray(band_emittance, dtype=float)
+    eps = N.full(thetas.shape, float(eps)) if eps.ndim == 0 else N.ravel(eps)
+    table = emittance_table(thetas, eps)
+    L_band, wl_avg, _ = band_radiance(T, band)
+    if quadrature == 'trapezoid':
+        integral = _trapezoid(eps * N.cos(thetas) * N.sin(thetas), thetas)
+    elif quadrature == 'exact':
+        integral = table.mass
+    else:
+        raise ValueError("%s: quadrature must be 'trapezoid' or 'exact', got %r" % (what, quadrature))
+    if not integral > 0.:       # (two points over [0, pi/2]: both nodes of the trapezoid are 0 -- or below, pi/2 written to 8 decimals)
+        raise ValueError("%s: the node trapezoid of eps cos sin over this table is %g: no power to emit; quadrature='exact' "
+                         "integrates the table" % (what, integral))
+    exitance = 2. * N.pi * L_band * integral
+    if isinstance(spectrum, str):
+        from .source_spectrum import SourceSpectrum
+        if spectrum == 'band_average':
+            spectrum = SourceSpectrum.monochromatic(wl_avg, ref_index)
+        elif spectrum == 'planck':
+            spectrum = SourceSpectrum.planck(T, band, ref_index=ref_index)
+        else:
+            raise ValueError("%s: spectrum must be 'band_average', 'planck', a SourceSpectrum or None, got %r" % (what, spectrum))
+    rot = _lamp_frame(direction, rotation)
+    desc, _ = _thermal_desc(what, shape, table, center, rot, rot, lambda area: exitance * area / max(int(num_rays), 1), rays_in)
+    return _new_bundle(desc, num_rays, seed, ray_offset, spectrum=spectrum, table=table)
+
+
+def spectral_band_axisymmetrical_thermal_emission_source(positions, normals, area, thetas, band_emittance, T, nrays, band, ref_index):
+    """
+    The reference's function of this name (sources.py:771-813) on host-given points: a materialised bundle of nrays rays leaving
+    `positions` (3, nrays) about `normals` (3, nrays), drawn from numpy's global generator as the reference draws them -- the polar
+    angles by its weighted sampler (sampling.PW_lincossin_distribution), then the azimuths -- with its energies (the weights over
+    their sum, times exitance times area), its wl_avg and ref_index columns.  thermal_emitter_bundle is the device form.
+    """
+    from .sampling import PW_lincossin_distribution
+    from .vector_manipulations import rotate_z_to_normal
+    thetas = N.asarray(thetas, dtype=float)
+    L_band, wl_avg, _ = band_radiance(T, band)
+    source_radiance = N.asarray(band_emittance, dtype=float) * L_band
+    thetas_rays, weights = PW_lincossin_distribution(thetas, source_radiance).sample(nrays)
+    source_exitance = _trapezoid(source_radiance * N.cos(thetas) * N.sin(thetas), thetas) * 2. * N.pi
+    phis_rays = N.random.uniform(size=nrays) * 2. * N.pi
+    directions = N.array([N.sin(thetas_rays) * N.cos(phis_rays), N.sin(thetas_rays) * N.sin(phis_rays), N.cos(thetas_rays)])
+    directions = rotate_z_to_normal(directions, normals)
+    energy = weights / N.sum(weights) * source_exitance * area
+    rayb = RayBundle(vertices=positions, directions=directions, energy=energy)
+    rayb._create_property('wavelengths', N.ones(nrays) * wl_avg)
+    rayb._create_property('ref_index', N.ones(nrays) * ref_index)
+    return rayb
+
+
+def gray_source(shape, location, direction, num_rays, directions_distribution, energy, rays_direction=None, seed=None, ray_offset=0):
+    """
+    The reference's general gray source (sources.py:44-66) -- a shape sampler composed with a direction law, of which it has the
+    Lambertian one -- as a pending bundle: a thermal descriptor with the constant emittance table over [0, ang_range], which the
+    device samples by the closed form of the Lambertian law.  shape: {'type': ..., 'kwargs': {...}} as thermal_emitter_bundle's;
+    directions_distribution: {'type': 'Lambertian', 'kwargs': {'ang_range': ...}}.  The points are posed by the minimal rotation of
+    +z to `direction` and moved to `location`, the directions by that of +z to rays_direction (direction when None).  Each ray carries
+    energy / num_rays -- times cos(dot(rays_direction, direction)) when rays_direction is given: the reference's expression at :63
+    as written (the cosine of the scalar product, not the scalar product), kept for parity.
+    """
+    what = 'gray_source'
+    try:
+        law, law_kwargs = directions_distribution['type'], dict(directions_distribution.get('kwargs', {}))
+    except (TypeError, KeyError):
+        raise ValueError("%s: directions_distribution must be a dictionary {'type': ..., 'kwargs': {...}}" % what)
+    if law != 'Lambertian':
+        raise ValueError("%s: the directions distribution %r is not offered (the reference has Lambertian alone)" % (what, law))
+    for k in ('ns', 'normals'):
+        law_kwargs.pop(k, None)
+    if sorted(law_kwargs) != ['ang_range']:
+        raise ValueError("%s: the Lambertian law takes ang_range" % what)
+    ang_range = float(law_kwargs['ang_range'])
+    if ang_range == 0.:
+        raise ValueError("%s: ang_range == 0 has no table (every ray along the normal): not offered" % what)
+    if not 0. < ang_range <= N.pi / 2.:
+        raise ValueError("%s: ang_range must lie in (0, pi/2]" % what)
+    if int(num_rays) < 0:
+        raise ValueError("%s: num_rays must not be negative" % what)
+    table = emittance_table([0., ang_range], [1., 1.])
+    direction = N.ravel(N.asarray(direction, dtype=float))
+    per_ray = float(energy) / max(int(num_rays), 1)
+    if rays_direction is None:
+        rays_direction = direction
+    else:
+        rays_direction = N.ravel(N.asarray(rays_direction, dtype=float))
+        per_ray *= N.cos(N.dot(rays_direction, direction))      # (sources.py:63, as written)
+    desc, _ = _thermal_desc(what, shape, table, location, _lamp_frame(direction, None), _lamp_frame(rays_direction, None),
+                            lambda area: per_ray, False)
+    return _new_bundle(desc, num_rays, seed, ray_offset, table=table)
+
+
 def single_ray_source(position, direction, flux=None):
     """One ray (sources.py:68-86)."""
     d = N.array(direction, dtype=float).reshape(3, 1)
