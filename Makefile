@@ -126,6 +126,19 @@ $(UMASKCHECK): $(UMASKCHECK_SRC) $(HDR)
 $(UMASKCHECK_EXE): $(UMASKCHECK_SRC) $(HDR)
 	$(CXX) -O2 -g -std=c++17 $(FPFLAGS) $(SAN) -DUMASK_CHECK_MAIN -o $@ $(UMASKCHECK_SRC)
 
+# the clear cones of the LDS-sized grid (trc_clear_build: trc_bounds.h) against brute force over the boxes, host-compiled: a library
+# for tests/test_clear_cones_host.py, and the same as a program of its own, built with the sanitizers, that the test runs as a child
+CLEARCHECK := $(ROOT)tests/clearcheck/libtrc_clear_check.so
+CLEARCHECK_EXE := $(ROOT)tests/clearcheck/clear_check
+CLEARCHECK_SRC := $(ROOT)tests/clearcheck/clear_check.cpp
+clearcheck: $(CLEARCHECK) $(CLEARCHECK_EXE)
+
+$(CLEARCHECK): $(CLEARCHECK_SRC) $(HDR)
+	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(CLEARCHECK_SRC)
+
+$(CLEARCHECK_EXE): $(CLEARCHECK_SRC) $(HDR)
+	$(CXX) -O1 -g -std=c++17 $(FPFLAGS) $(SPLIT_SAN) -DCLEAR_CHECK_MAIN -o $@ $(CLEARCHECK_SRC)
+
 # the room of a streaming call whose optics split rays (trc_split_room_need, trc_split_grow: trc_bounds.h) on a grid of inputs: a
 # program of its own, built with the sanitizers and run by tests/test_split_cases_host.py
 SPLITCHECK_EXE := $(ROOT)tests/splitcheck/split_check
@@ -184,4 +197,4 @@ asm-shade: $(CSRC)/trc_shade.hip $(HDR)
 clean:
 	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK) $(HHCHECK) $(THERMCHECK) $(THERMCHECK_EXE)
 
-.PHONY: all hostcheck thermalcheck umaskcheck umaskcheck-exe splitcheck polycheck poolcheck poolcheck-tsan scenecheck asm asm-shade clean
+.PHONY: all hostcheck thermalcheck umaskcheck umaskcheck-exe clearcheck splitcheck polycheck poolcheck poolcheck-tsan scenecheck asm asm-shade clean

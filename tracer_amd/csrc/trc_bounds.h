@@ -5,6 +5,7 @@
 #ifndef TRC_BOUNDS_H
 #define TRC_BOUNDS_H
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -284,6 +285,10 @@ struct trc_accel_host {
     std::vector<uint16_t> grid_list;
     std::vector<int32_t> grid_apart;   // bounded surfaces kept out of the grid: their boxes are tested for every ray
     float grid_root[6];                // box of the surfaces in the grid, relative, rounded outwards
+    // clear cones of the surfaces listed in that grid (trc_clear_build): per surface clear_T x clear_T tiles of four floats, the
+    // unit axis and tan^2 of the half-angle (0: no cone); clear_cones: tiles that have one (0: the table is not uploaded)
+    std::vector<float> clear;
+    int32_t clear_T = 0, clear_cones = 0;
     // the same kind of grid without the limits of LDS, for scenes the one above cannot hold (trc_accel_build_grid32):
     // 32-bit offsets and lists in global memory; big_apart: the few surfaces kept out of it (as grid_apart)
     bool big_ok;
@@ -484,6 +489,231 @@ static inline void trc_accel_build_grid(trc_accel_host &A, int n_surf) {
         for (int k = 0; k < 3; ++k) { A.grid_dim[k] = dim[k]; A.grid_lo[k] = (float)lo[k]; A.grid_cs[k] = cs[k]; A.grid_inv[k] = inv[k]; }
         A.grid_ok = true;
         return;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Clear cones (trc_clear_tile / trc_clear_inside in trc_core.h; call after trc_accel_build_grid).  The rays a heliostat sends on
+// were aimed: they leave plate h within a few mrad of the line from h to the receiver, and for most plates nothing stands near
+// that line.  Every tile of every plate gets a cone -- the axis a from the plate's centre to the mean centre of the surfaces set
+// apart from the grid, and a half-angle -- inside which a ray that starts on the tile can meet the oriented box of no surface
+// listed in the grid.  k_s_bounce then leaves the walk out for such a ray; the surfaces set apart and the unbounded ones are
+// tested before the walk whatever happens.
+//
+// The bound, per tile box B (the tile in h's oriented-box frame, as thick as that box, neighbours overlapping by 2 delta on
+// every side) and per other listed surface g (its oriented box G as stored in A.obb, whatever its kind):
+//   s_max = max_{q in G} a.q - min_{p in B} a.p    (<= 0: g lies behind, ignored)
+//   D     = distance of the two boxes' projections onto the plane normal to a (0 when they overlap or touch)
+//   tan(alpha_hg) = D / s_max.
+// A ray from p in B at angle theta < pi/2 to a has, at axial distance s from p, the perpendicular offset s tan(theta) exactly.
+// To reach q it needs |q_perp - p_perp| = s_q tan(theta) with 0 < s_q <= s_max, and |q_perp - p_perp| >= D: theta >= alpha_hg.
+// alpha = min over g, capped at TRC_CLEAR_CAP (a wider cone serves nobody, and the cap lets bounding spheres sort out the pairs);
+// stored is k = tan^2(alpha (1 - 1e-3) - 1e-4) rounded down -- the margin stands for the single-precision direction and test of
+// the kernel and for the tolerance of the box tests a walking ray is given (trc_box_hit32, trc_obb_hit32).
+// h qualifies when it is flat with its plate in the plane z = 0 of its frame (a ray that leaves it carries SQ_SKIP_SELF and
+// starts on that plane), bounded and listed in the grid, and the scene has a surface set apart.  Everything else gets k = 0.
+// ---------------------------------------------------------------------------------------------
+#define TRC_CLEAR_CAP 0.2      /* rad */
+
+struct trc_clear_box { double c[8][3]; double cen[3], rad; };
+
+static inline void trc_clear_box_finish(trc_clear_box &b) {
+    for (int i = 0; i < 3; ++i) { b.cen[i] = 0.0; for (int c = 0; c < 8; ++c) b.cen[i] += 0.125 * b.c[c][i]; }
+    b.rad = 0.0;
+    for (int c = 0; c < 8; ++c) {
+        double r2 = 0.0;
+        for (int i = 0; i < 3; ++i) r2 += (b.c[c][i] - b.cen[i]) * (b.c[c][i] - b.cen[i]);
+        b.rad = std::fmax(b.rad, std::sqrt(r2));
+    }
+}
+// the box [l, h] of the oriented-box record B in coordinates relative to the scene centre
+static inline void trc_clear_box_of(const float *B, const double l[3], const double h[3], trc_clear_box &b) {
+    for (int c = 0; c < 8; ++c) {
+        const double p[3] = {(c & 1) ? h[0] : l[0], (c & 2) ? h[1] : l[1], (c & 4) ? h[2] : l[2]};
+        for (int i = 0; i < 3; ++i) b.c[c][i] = (double)B[4 * i + 3] + (double)B[i] * p[0] + (double)B[4 + i] * p[1] + (double)B[8 + i] * p[2];
+    }
+    trc_clear_box_finish(b);
+}
+// tan(alpha_hg) of the tile box P and the box Q about the unit axis a with the basis (e1, e2) of its normal plane; INFINITY: Q lies
+// behind.  The widest gap along a separating edge normal is a lower bound of the distance: where it already gives `bound` or more, it is
+// returned in place of the exact value (*exact = false) -- the caller asks for a minimum, and for who stays below the cap.
+static inline double trc_clear_tan(const trc_clear_box &P, const trc_clear_box &Q, const double a[3], const double e1[3], const double e2[3],
+                                   double bound, bool *exact) {
+    double p2[8][2], q2[8][2], pmin = INFINITY, qmax = -INFINITY;
+    *exact = true;
+    for (int c = 0; c < 8; ++c) {
+        pmin = std::fmin(pmin, a[0] * P.c[c][0] + a[1] * P.c[c][1] + a[2] * P.c[c][2]);
+        qmax = std::fmax(qmax, a[0] * Q.c[c][0] + a[1] * Q.c[c][1] + a[2] * Q.c[c][2]);
+        for (int k = 0; k < 2; ++k) {
+            const double *e = k ? e2 : e1;
+            p2[c][k] = e[0] * P.c[c][0] + e[1] * P.c[c][1] + e[2] * P.c[c][2];
+            q2[c][k] = e[0] * Q.c[c][0] + e[1] * Q.c[c][1] + e[2] * Q.c[c][2];
+        }
+    }
+    const double smax = qmax - pmin;
+    if (!(smax > 0.0)) return INFINITY;
+    // The projection of a box is the zonotope of its three projected edges: two of them overlap unless one of the six edge normals
+    // separates them.
+    double gap = 0.0;
+    for (int w = 0; w < 2; ++w)
+        for (int bit = 1; bit < 8; bit <<= 1) {
+            const double (*z)[2] = w ? q2 : p2;
+            const double nx = -(z[bit][1] - z[0][1]), ny = z[bit][0] - z[0][0], nn = nx * nx + ny * ny;
+            if (!(nn > 0.0)) continue;
+            double p0 = INFINITY, p1 = -INFINITY, q0 = INFINITY, q1 = -INFINITY;
+            for (int c = 0; c < 8; ++c) {
+                const double pp = nx * p2[c][0] + ny * p2[c][1], qq = nx * q2[c][0] + ny * q2[c][1];
+                p0 = std::fmin(p0, pp); p1 = std::fmax(p1, pp); q0 = std::fmin(q0, qq); q1 = std::fmax(q1, qq);
+            }
+            const double g = std::fmax(q0 - p1, p0 - q1);
+            if (g > 0.0) gap = std::fmax(gap, g / std::sqrt(nn));
+        }
+    if (!(gap > 0.0)) return 0.0;
+    if (gap * (1.0 - 1e-12) / smax >= bound) { *exact = false; return gap * (1.0 - 1e-12) / smax; }
+    // apart: the distance is that of a corner of one to an edge of the other (every edge of a hull is a projected box edge, and the
+    // projected edges inside a hull are no nearer than the hull)
+    double d2 = INFINITY;
+    for (int w = 0; w < 2; ++w) {
+        const double (*z)[2] = w ? q2 : p2, (*o)[2] = w ? p2 : q2;       // edges of z, corners of o
+        for (int c = 0; c < 8; ++c)
+            for (int bit = 1; bit < 8; bit <<= 1) {
+                if (c & bit) continue;
+                const double ex = z[c | bit][0] - z[c][0], ey = z[c | bit][1] - z[c][1], ee = ex * ex + ey * ey, ie = ee > 0.0 ? 1.0 / ee : 0.0;
+                for (int v = 0; v < 8; ++v) {
+                    const double wx = o[v][0] - z[c][0], wy = o[v][1] - z[c][1];
+                    double t = (wx * ex + wy * ey) * ie;
+                    t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+                    const double rx = wx - t * ex, ry = wy - t * ey;
+                    d2 = std::fmin(d2, rx * rx + ry * ry);
+                }
+            }
+    }
+    return std::sqrt(d2) * (1.0 - 1e-12) / smax;
+}
+
+// T: tiles per side (the library: TRC_CLEAR_T).  surfs: the surfaces the tables of A were built from.
+static inline void trc_clear_build(const trc_surface_desc *surfs, int n_surf, int T, trc_accel_host &A) {
+    A.clear.clear();
+    A.clear_T = T;
+    A.clear_cones = 0;
+    if (!A.grid_ok || A.grid_apart.empty() || T < 1) return;
+    A.clear.assign((size_t)n_surf * T * T * 4, 0.0f);
+    const double delta = (double)A.delta, tcap = std::tan(TRC_CLEAR_CAP);
+    // the surfaces listed in the grid, with their oriented boxes
+    std::vector<char> listed((size_t)n_surf, 0);
+    for (size_t k = 0; k < (size_t)A.grid_off.back() && k < A.grid_list.size(); ++k) listed[A.grid_list[k]] = 1;
+    std::vector<int> ids;
+    std::vector<trc_clear_box> boxes;
+    for (int g = 0; g < n_surf; ++g) {
+        if (!listed[g]) continue;
+        const float *B = &A.obb[(size_t)TRC_OBB_STRIDE * g];
+        const double l[3] = {B[12], B[13], B[14]}, h[3] = {B[15], B[16], B[17]};
+        trc_clear_box b;
+        trc_clear_box_of(B, l, h, b);
+        ids.push_back(g);
+        boxes.push_back(b);
+    }
+    double target[3] = {0.0, 0.0, 0.0};
+    for (int32_t s : A.grid_apart) {
+        const float *B = &A.obb[(size_t)TRC_OBB_STRIDE * s];
+        const double l[3] = {B[12], B[13], B[14]}, h[3] = {B[15], B[16], B[17]};
+        trc_clear_box b;
+        trc_clear_box_of(B, l, h, b);
+        for (int i = 0; i < 3; ++i) target[i] += b.cen[i] / (double)A.grid_apart.size();
+    }
+    std::vector<int> near, keep;
+    std::vector<std::vector<int>> lists, below;
+    for (size_t hi = 0; hi < ids.size(); ++hi) {
+        const int hs = ids[hi];
+        const int kind = surfs[hs].gm_kind;
+        const float *B = &A.obb[(size_t)TRC_OBB_STRIDE * hs];
+        if (!trc_gm_is_flat(kind) || kind == TRC_GM_TRIANGLE || !(B[14] < 0.0f && B[17] > 0.0f && B[14] == -B[17])) continue;
+        const trc_clear_box &H = boxes[hi];
+        double a[3] = {target[0] - H.cen[0], target[1] - H.cen[1], target[2] - H.cen[2]};
+        const double an = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+        if (!(an > 0.0)) continue;
+        for (int i = 0; i < 3; ++i) a[i] /= an;
+        // what the kernel reads: the axis in single precision, made a unit vector again in double for the bound
+        const float af[3] = {(float)a[0], (float)a[1], (float)a[2]};
+        const double fn = std::sqrt((double)af[0] * af[0] + (double)af[1] * af[1] + (double)af[2] * af[2]);
+        for (int i = 0; i < 3; ++i) a[i] = (double)af[i] / fn;
+        const int m = std::fabs(a[0]) < std::fabs(a[1]) ? (std::fabs(a[0]) < std::fabs(a[2]) ? 0 : 2) : (std::fabs(a[1]) < std::fabs(a[2]) ? 1 : 2);
+        double e1[3] = {0.0, 0.0, 0.0}, e2[3];
+        e1[m] = 1.0;
+        const double d1 = a[m];
+        double n1 = 0.0;
+        for (int i = 0; i < 3; ++i) { e1[i] -= d1 * a[i]; n1 += e1[i] * e1[i]; }
+        n1 = std::sqrt(n1);
+        for (int i = 0; i < 3; ++i) e1[i] /= n1;
+        e2[0] = a[1] * e1[2] - a[2] * e1[1]; e2[1] = a[2] * e1[0] - a[0] * e1[2]; e2[2] = a[0] * e1[1] - a[1] * e1[0];
+        // the surfaces whose bounding sphere comes within the widest cone of the whole plate's, the nearest along the axis first (what
+        // blocks a tile is found early, and what is found early bounds the rest)
+        // (by the spheres: does Q leave the cone of tangent t about P free?  D >= the gap of the spheres, s_max <= s + R)
+        auto outside = [&](const trc_clear_box &P, const trc_clear_box &Q, double t) {
+            const double v[3] = {Q.cen[0] - P.cen[0], Q.cen[1] - P.cen[1], Q.cen[2] - P.cen[2]};
+            const double s = a[0] * v[0] + a[1] * v[1] + a[2] * v[2], R = P.rad + Q.rad;
+            if (s + R <= 0.0) return true;
+            const double w2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2] - s * s, reach = t * (s + R) + R;
+            return w2 >= reach * reach;
+        };
+        near.clear();
+        for (size_t gi = 0; gi < ids.size(); ++gi) if (gi != hi && !outside(H, boxes[gi], tcap)) near.push_back((int)gi);
+        std::sort(near.begin(), near.end(), [&](int x, int y) {
+            const double sx = a[0] * boxes[(size_t)x].cen[0] + a[1] * boxes[(size_t)x].cen[1] + a[2] * boxes[(size_t)x].cen[2];
+            const double sy = a[0] * boxes[(size_t)y].cen[0] + a[1] * boxes[(size_t)y].cen[1] + a[2] * boxes[(size_t)y].cen[2];
+            return sx < sy || (sx == sy && x < y);
+        });
+        // From the whole plate down to its T x T tiles, halving: a tile lies inside the tile it came from, so a surface that leaves the
+        // widest cone of a tile free leaves it free for the four below -- they inherit the list of those that do not.  (T that is no
+        // power of two: the tiles at once.)
+        const double lo[2] = {B[12], B[13]}, up[2] = {B[15], B[16]};
+        lists.assign(1, near);
+        for (int L = (T & (T - 1)) ? T : 1; L <= T; L *= 2) {
+            const bool last = L == T;
+            if (!last) below.assign((size_t)4 * L * L, std::vector<int>());
+            for (int tv = 0; tv < L; ++tv)
+                for (int tu = 0; tu < L; ++tu) {
+                    const std::vector<int> &list = lists[lists.size() == 1 ? 0 : (size_t)tv * L + tu];
+                    const int t2[2] = {tu, tv};
+                    double l[3], h[3];
+                    for (int k = 0; k < 2; ++k) {
+                        const double w = (up[k] - lo[k]) / L;
+                        l[k] = std::fmax(lo[k], lo[k] + t2[k] * w - 2.0 * delta);
+                        h[k] = std::fmin(up[k], lo[k] + (t2[k] + 1) * w + 2.0 * delta);
+                    }
+                    l[2] = B[14]; h[2] = B[17];
+                    trc_clear_box P;
+                    trc_clear_box_of(B, l, h, P);
+                    double tmin = tcap;
+                    keep.clear();
+                    for (size_t j = 0; j < list.size(); ++j) {
+                        if (!(tmin > 0.0)) {        // blocked: nothing left to find for this tile; those below look again at the rest
+                            if (last) break;
+                            keep.push_back(list[j]);
+                            continue;
+                        }
+                        const trc_clear_box &Q = boxes[(size_t)list[j]];
+                        if (outside(P, Q, tcap)) continue;
+                        if (tmin < tcap && outside(P, Q, tmin)) { keep.push_back(list[j]); continue; }      // (cannot lower the minimum)
+                        bool exact;
+                        const double t = trc_clear_tan(P, Q, a, e1, e2, tmin, &exact);
+                        if (t >= tcap) continue;
+                        keep.push_back(list[j]);
+                        if (exact) tmin = std::fmin(tmin, t);
+                    }
+                    if (!last) {
+                        for (int c = 0; c < 4; ++c) below[(size_t)(2 * tv + (c >> 1)) * (2 * L) + (2 * tu + (c & 1))] = keep;
+                        continue;
+                    }
+                    const double alpha = std::fmax(std::atan(tmin) * (1.0 - 1e-3) - 1e-4, 0.0), tk = std::tan(alpha);
+                    float k = trc_f32_down(tk * tk);
+                    if (!(k > 0.0f)) k = 0.0f;
+                    float *o = &A.clear[((size_t)hs * T * T + (size_t)tv * T + tu) * 4];
+                    o[0] = af[0]; o[1] = af[1]; o[2] = af[2]; o[3] = k;
+                    if (k > 0.0f) A.clear_cones += 1;
+                }
+            if (!last) lists.swap(below);
+        }
     }
 }
 

@@ -745,6 +745,34 @@ TRC_HD bool trc_obb_hit32(const float *B, float ox, float oy, float oz, float dx
     return hi * 1.0001f + 1e-6f >= lo;       // NaNs (0 * inf) are ignored by fminf/fmaxf: conservative, as in trc_box_hit32
 }
 
+// Clear cones (built by trc_clear_build, trc_bounds.h; read by k_s_bounce on the LDS-sized grid): a table of TRC_CLEAR_T x TRC_CLEAR_T
+// tiles per surface over the plate's two local axes, four floats each -- a unit axis and k = tan^2 of a half-angle.  A ray that
+// starts on the tile and runs inside the cone meets the oriented box of no surface listed in the grid: it need not walk the grid.
+// trc_clear_tile: the tile of a start point (relative to the scene centre, as trc_ray32's origin) from the plate's oriented box B;
+// neighbouring tiles overlap in the builder by far more than this rounds.  trc_clear_inside: is the direction d inside the cone?
+// With c = d . a and x = d x a the angle's tangent is |x| / c; the cross product is taken directly, since 1 - c^2 has lost the
+// angles that matter (1e-3 rad) to rounding.  k = 0: no cone, never inside.
+#ifndef TRC_CLEAR_T
+#define TRC_CLEAR_T 8
+#endif
+TRC_HD int trc_clear_tile(const float *B, int T, float ox, float oy, float oz) {
+    const float rx = ox - B[3], ry = oy - B[7], rz = oz - B[11];
+    const float lu = B[0] * rx + B[1] * ry + B[2] * rz, lv = B[4] * rx + B[5] * ry + B[6] * rz;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float su = (float)T * __builtin_amdgcn_rcpf(B[15] - B[12]), sv = (float)T * __builtin_amdgcn_rcpf(B[16] - B[13]);
+#else
+    const float su = (float)T / (B[15] - B[12]), sv = (float)T / (B[16] - B[13]);
+#endif
+    const int tu = (int)fminf(fmaxf((lu - B[12]) * su, 0.0f), (float)(T - 1));
+    const int tv = (int)fminf(fmaxf((lv - B[13]) * sv, 0.0f), (float)(T - 1));
+    return tv * T + tu;
+}
+TRC_HD bool trc_clear_inside(float ax, float ay, float az, float k, float dx, float dy, float dz) {
+    const float c = dx * ax + dy * ay + dz * az;
+    const float xx = dy * az - dz * ay, xy = dz * ax - dx * az, xz = dx * ay - dy * ax;
+    return c > 0.0f && xx * xx + xy * xy + xz * xz < k * (c * c);
+}
+
 // The same question for a triangular face (triangular_face.py:59-72) from its corner and two edges in single precision
 // (relative to the scene centre like the ray's origin): can the exact test succeed?  With T = o - v0, the scaled barycentric
 // coordinates are u = T . (d x e2), v = d . (T x e1) over det = e1 . (d x e2); the point is inside when u, v >= 0 and u + v <= det

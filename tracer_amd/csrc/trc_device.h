@@ -553,6 +553,9 @@ struct StreamParams {
     unsigned part_chunk[3];
     int part_static[3];
     CarryIn carry;      // (last: see CarryIn)
+    // the clear cones of the scene (trc_clear_tile, trc_core.h): read by k_s_bounce for the continued rays on the LDS-sized grid alone,
+    // null for a scene without them and with TRC_STREAM_CLEAR=0.  Behind everything else, for the reason given at CarryIn.
+    const float *clear_tab;
 };
 
 // The kernel's argument block read again where it stands in the kernel-argument segment.  What a kernel reads from its by-value

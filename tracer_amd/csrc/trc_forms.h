@@ -170,6 +170,7 @@ struct StreamKnobs {
     int fp_cells;           // TRC_STREAM_FP_CELLS: cells per side of the footprint map (>= 32; 0: by the scene)
     bool umask;             // TRC_STREAM_UMASK=0: k_s_cull on the Cartesian mask for every source (the form that packs the cell)
     int slots;              // TRC_STREAM_SLOTS: batches in flight, 1 .. STREAM_MAX_SLOTS (default 2)
+    bool clear = true;      // TRC_STREAM_CLEAR=0: k_s_bounce gets no table of clear cones, every continued ray walks the grid
 };
 
 // What the decisions read of a scene.  Two parts: the sizes, which cost nothing to gather, and what only a pass over the surfaces

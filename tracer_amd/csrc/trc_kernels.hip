@@ -376,7 +376,7 @@ class SearchTables {
     trc_accel_host accel_{};
     bool ok_ = false, kd_ok_ = false;
     uint64_t geom_version_ = 0;     // bumped whenever the tables are rebuilt: what others derived from the old poses is stale
-    DevBuf<float> d_sbox_, d_obb_, d_bg_ent_;
+    DevBuf<float> d_sbox_, d_obb_, d_bg_ent_, d_clear_;
     DevBuf<uint32_t> d_nodes_, d_bg_off_, d_bg_occ_;
     DevBuf<uint16_t> d_leaf_, d_bleaf_, d_goff_, d_glist_;
     DevBuf<int32_t> d_unbounded_, d_gapart_, d_bg_apart_;
@@ -406,6 +406,8 @@ public:
     void drop_kd() { d_nodes_.reset(); d_leaf_.reset(); kd_ok_ = false; }
     const trc_accel_host &host() const { return accel_; }
     uint64_t geom_version() const { return geom_version_; }
+    // the clear cones of the present poses (trc_clear_build), TRC_CLEAR_T x TRC_CLEAR_T tiles per surface; null: no surface has one
+    const float *clear_cones() const { return ok_ && accel_.clear_cones > 0 ? d_clear_.get() : nullptr; }
     void fill(DScene &d) const;
     void facts(trc_scene_facts &s) const { s.accel_ok = ok_; s.accel_kd_ok = kd_ok_; }
 };
@@ -423,6 +425,7 @@ int SearchTables::build(const trc_surface_desc *surfs, int n) {
         TRC_TRY(dev_upload(d_gapart_, A.grid_apart.data(), A.grid_apart.size()));
         TRC_TRY(dev_upload(d_goff_, A.grid_off.data(), A.grid_off.size()));
         TRC_TRY(dev_upload(d_glist_, A.grid_list.data(), A.grid_list.size()));
+        if (A.clear_cones > 0) TRC_TRY(dev_upload(d_clear_, A.clear.data(), A.clear.size()));
     } else if (A.big_ok) {      // a scene the LDS-sized grid cannot hold: the 32-bit grid in global memory
         TRC_TRY(dev_upload(d_bg_off_, A.big_off.data(), A.big_off.size()));
         TRC_TRY(dev_upload(d_bg_ent_, A.big_ent.data(), A.big_ent.size()));

@@ -103,12 +103,13 @@ static inline void trc_scene_scan(const trc_surface_desc *surfs, int n, bool *sp
     }
 }
 
-// The search tables of a scene, in the order every scene gets them: the boxes, the LDS-sized grid, and the 32-bit grid for a scene
-// the LDS-sized one cannot hold.  force32 (TRC_GRID_FORCE32, for measurements): the large grid for a scene the small one holds.
+// The search tables of a scene, in the order every scene gets them: the boxes, the LDS-sized grid with the clear cones of the surfaces
+// listed in it, and the 32-bit grid for a scene the LDS-sized one cannot hold.  force32 (TRC_GRID_FORCE32, for measurements): the large grid for a scene the small one holds.
 static inline void trc_search_tables_build(const trc_surface_desc *surfs, int n, bool force32, trc_accel_host &A) {
     trc_accel_build_surfaces(surfs, n, A);
     trc_accel_build_grid(A, n);
     if (force32) A.grid_ok = false;
+    trc_clear_build(surfs, n, TRC_CLEAR_T, A);      // (the clear cones belong to the LDS-sized grid: none without it)
     if (!A.grid_ok) trc_accel_build_grid32(surfs, n, A);
 }
 
