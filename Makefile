@@ -3,6 +3,7 @@
 # `make poolcheck poolcheck-tsan` build the host check of the block cache (trc_pool.h: one cache, under one policy for device memory
 # and another for pinned host memory) with the address / undefined-behaviour sanitizers and with the thread sanitizer.
 # `make scenecheck` builds the host check of a scene's host arithmetic (trc_scene_host.h) with the same sanitizers.
+# `make sourcecheck sourcecheck-tsan` build the host check of the tabulated sources' host side (trc_source_host.h) with both.
 ROOT := $(dir $(abspath $(lastword $(MAKEFILE_LIST))))
 HIPCC ?= hipcc
 CXX ?= g++
@@ -10,13 +11,13 @@ ARCH ?= gfx950
 
 LIB := $(ROOT)tracer_amd/lib/libtracer_amd.so
 CSRC := $(ROOT)tracer_amd/csrc
-# three translation units: the engines and the C-ABI (trc_kernels.hip, which includes trc_stream.inc), the class-split shading
-# kernels of the streaming engine (trc_shade.hip), and the histogram of captured hits (trc_hithist.hip).  `make -j2` compiles them
-# side by side.
-SRCS := $(CSRC)/trc_kernels.hip $(CSRC)/trc_shade.hip $(CSRC)/trc_hithist.hip
+# four translation units: the engines and the scene's part of the C-ABI (trc_kernels.hip, which includes trc_stream.inc), the
+# class-split shading kernels of the streaming engine (trc_shade.hip), the histogram of captured hits (trc_hithist.hip), and the
+# entry points that take no scene with their kernels (trc_protocol.hip).  `make -j2` compiles them side by side.
+SRCS := $(CSRC)/trc_kernels.hip $(CSRC)/trc_shade.hip $(CSRC)/trc_hithist.hip $(CSRC)/trc_protocol.hip
 OBJDIR := $(ROOT)build/obj
-OBJS := $(OBJDIR)/trc_kernels.o $(OBJDIR)/trc_shade.o $(OBJDIR)/trc_hithist.o
-HDR := $(CSRC)/trc_core.h $(CSRC)/trc_bounds.h $(CSRC)/trc_footprint.h $(CSRC)/trc_forms.h $(CSRC)/trc_device.h $(CSRC)/trc_stream.inc $(CSRC)/trc_mega.inc $(CSRC)/trc_hithist.h $(CSRC)/trc_pool.h $(CSRC)/trc_scene_host.h $(ROOT)include/tracer_amd.h
+OBJS := $(OBJDIR)/trc_kernels.o $(OBJDIR)/trc_shade.o $(OBJDIR)/trc_hithist.o $(OBJDIR)/trc_protocol.o
+HDR := $(CSRC)/trc_host.h $(CSRC)/trc_source_host.h $(CSRC)/trc_core.h $(CSRC)/trc_bounds.h $(CSRC)/trc_footprint.h $(CSRC)/trc_forms.h $(CSRC)/trc_device.h $(CSRC)/trc_stream.inc $(CSRC)/trc_mega.inc $(CSRC)/trc_hithist.h $(CSRC)/trc_pool.h $(CSRC)/trc_scene_host.h $(ROOT)include/tracer_amd.h
 
 HOSTCHECK := $(ROOT)tests/hostcheck/libtrc_hostcheck.so
 HOSTCHECK_SRC := $(ROOT)tests/hostcheck/hostcheck.cpp
@@ -65,6 +66,10 @@ $(OBJDIR)/trc_kernels.o: $(CSRC)/trc_kernels.hip $(HDR)
 	$(HIPCC) $(HIPFLAGS) $(KERNELS_FLAGS) -c -o $@ $<
 
 $(OBJDIR)/trc_hithist.o: $(CSRC)/trc_hithist.hip $(HDR)
+	mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(KERNELS_FLAGS) -c -o $@ $<
+
+$(OBJDIR)/trc_protocol.o: $(CSRC)/trc_protocol.hip $(HDR)
 	mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(KERNELS_FLAGS) -c -o $@ $<
 
@@ -181,10 +186,30 @@ scenecheck: $(SCENECHECK_EXE)
 $(SCENECHECK_EXE): $(SCENECHECK_SRC) $(HDR)
 	$(CXX) -O1 -g -std=c++17 $(FPFLAGS) $(SPLIT_SAN) -o $@ $(SCENECHECK_SRC)
 
+# the host side of the tabulated sources (trc_source_host.h): the one table check on bad tables by status and message, the packing
+# bit for bit, the id registry (in order, to exhaustion, under eight threads) and the descriptor arithmetic.  Two programs of their
+# own, run by tests/test_source_tables_host.py, and the check-and-pack functions as a library for the same test.  (The library is
+# built by `sourcecheck`, not by `hostcheck`: what `hostcheck` builds needs nothing outside tests/hostcheck.)
+SOURCECHECK_EXE := $(ROOT)tests/sourcecheck/source_check
+SOURCECHECK_TSAN_EXE := $(ROOT)tests/sourcecheck/source_check_tsan
+SOURCECHECK_LIB := $(ROOT)tests/sourcecheck/libtrc_source_check.so
+SOURCECHECK_SRC := $(ROOT)tests/sourcecheck/source_check.cpp
+sourcecheck: $(SOURCECHECK_EXE) $(SOURCECHECK_LIB)
+sourcecheck-tsan: $(SOURCECHECK_TSAN_EXE)
+
+$(SOURCECHECK_EXE): $(SOURCECHECK_SRC) $(HDR)
+	$(CXX) -O1 -g -std=c++17 $(FPFLAGS) $(SPLIT_SAN) -pthread -DSOURCE_CHECK_MAIN -o $@ $(SOURCECHECK_SRC)
+
+$(SOURCECHECK_TSAN_EXE): $(SOURCECHECK_SRC) $(HDR)
+	$(CXX) -O1 -g -std=c++17 $(FPFLAGS) -fsanitize=thread -pthread -DSOURCE_CHECK_MAIN -o $@ $(SOURCECHECK_SRC)
+
+$(SOURCECHECK_LIB): $(SOURCECHECK_SRC) $(HDR)
+	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(SOURCECHECK_SRC)
+
 # assembly listings with the registers, scratch and occupancy of every kernel (build/*.s, build/*.resources.txt)
 asm: $(SRCS) $(HDR)
 	mkdir -p $(ROOT)build
-	for f in trc_kernels trc_shade trc_hithist; do \
+	for f in trc_kernels trc_shade trc_hithist trc_protocol; do \
 		fl="$(KERNELS_FLAGS)"; [ $$f = trc_shade ] && fl="$(SHADE_FLAGS)"; \
 		$(HIPCC) $(HIPFLAGS) $$fl -S --cuda-device-only -Rpass-analysis=kernel-resource-usage \
 			-o $(ROOT)build/$$f.s $(CSRC)/$$f.hip 2> $(ROOT)build/$$f.resources.txt || exit 1; done
@@ -195,6 +220,6 @@ asm-shade: $(CSRC)/trc_shade.hip $(HDR)
 		-o $(ROOT)build/trc_shade.s $(CSRC)/trc_shade.hip 2> $(ROOT)build/trc_shade.resources.txt
 
 clean:
-	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK) $(HHCHECK) $(THERMCHECK) $(THERMCHECK_EXE)
+	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK) $(HHCHECK) $(THERMCHECK) $(THERMCHECK_EXE) $(SOURCECHECK_LIB)
 
-.PHONY: all hostcheck thermalcheck umaskcheck umaskcheck-exe clearcheck splitcheck polycheck poolcheck poolcheck-tsan scenecheck asm asm-shade clean
+.PHONY: all hostcheck thermalcheck umaskcheck umaskcheck-exe clearcheck splitcheck polycheck poolcheck poolcheck-tsan scenecheck sourcecheck sourcecheck-tsan asm asm-shade clean

@@ -82,6 +82,20 @@ def test_no_gpu_means_loud_failure(lib_path):
     assert 'no CPU path' in str(e.value) or 'HIP' in str(e.value) or 'hip' in str(e.value)
 
 
+def test_the_units_of_the_library_share_one_error_string(lib_path):
+    """trc_last_error reads what the last refusal on this thread wrote, whichever translation unit of the library refused: the
+    per-object protocol and the source tables (trc_protocol.hip), then the scene (trc_kernels.hip).  Null arguments: no device call."""
+    lib = ctypes.CDLL(lib_path)
+    lib.trc_last_error.restype = ctypes.c_char_p
+    invalid = -1
+    assert lib.trc_gm_find_intersections(None, None, 0, None, None, None, None, None, None) == invalid
+    assert lib.trc_last_error() == b'trc_gm_find_intersections: bad arguments'
+    assert lib.trc_sunshape_create(None, 0, None, None, None) == invalid
+    assert lib.trc_last_error() == b'trc_sunshape_create: bad arguments'
+    assert lib.trc_scene_get_hits(None, None, None, None, None, None, None, None, None, None, None) == invalid
+    assert lib.trc_last_error() == b'bad arguments'
+
+
 def test_product_never_imports_the_oracle():
     for dirpath, _, files in os.walk(os.path.join(ROOT, 'tracer_amd')):
         for f in files:

@@ -1,4 +1,7 @@
-// trc_kernels.hip -- CDNA4 (gfx950) kernels and the C-ABI of include/tracer_amd.h.
+// trc_kernels.hip -- CDNA4 (gfx950) kernels of the engines and the scene's part of the C-ABI of include/tracer_amd.h: the context,
+// the scene and its owners (surfaces, search tables, Kd-tree, tallies, hit buffer, materials, histograms), the trace entry points
+// and their results.  The entry points that take a context and no scene -- source tables, source generation, the per-object
+// protocol -- are trc_protocol.hip; the host plumbing both units share is trc_host.h.
 //
 // Two engines over the same per-ray core (trc_core.h):
 //   * fast engine  (k_trace_fast): persistent wavefronts.  A lane carries one ray through all of its
@@ -35,165 +38,15 @@
 #include "trc_device.h"
 #include "trc_pool.h"
 #include "trc_scene_host.h"
+#include "trc_host.h"
 #include "trc_hithist.h"
-
-// ================================================================================================
-// error handling
-// ================================================================================================
-static thread_local std::string g_last_error;
-
-static int trc_fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess)                                                                           \
-            return trc_fail(TRC_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e),      \
-                            __FILE__, __LINE__);                                                        \
-    } while (0)
-
-#define TRC_TRY(expr)                   \
-    do {                                \
-        int _s = (expr);                \
-        if (_s != TRC_OK) return _s;    \
-    } while (0)
 
 extern "C" const char *trc_last_error(void) { return g_last_error.c_str(); }
 extern "C" int trc_abi_version(void) { return TRC_ABI_VERSION; }
 
-// Device memory goes through a block cache (trc_pool.h: the policy and its reasons): a freed block of up to 128 MiB waits for the
-// next request of its size class, a larger one for the next request of exactly its size, 2 GiB of each at most.  Keeping a block
-// waits for the device as hipFree would have -- for the *current* device, as it always did, which need not be the block's own.
-// TRC_DEV_POOL=0, read when the first block is asked for, turns the cache off.
-struct DevBackend {
-    static inline thread_local hipError_t err = hipSuccess;       // why this thread's last alloc() gave nothing
-    void *alloc(size_t bytes) {
-        void *p = nullptr;
-        err = hipMalloc(&p, bytes);
-        if (err == hipSuccess) return p;
-        (void)hipGetLastError();      // (the failure is reported by err: it is not left for the next kernel launch to find)
-        return nullptr;
-    }
-    void release(void *p) { (void)hipFree(p); }
-    void quiesce() { (void)hipDeviceSynchronize(); }      // nothing in flight may still use the block when the next owner gets it
-    int device() { int d = 0; (void)hipGetDevice(&d); return d; }
-};
-static trc_block_cache<DevBackend> &dev_cache() {
-    static const char *const e = getenv("TRC_DEV_POOL");
-    static trc_block_cache<DevBackend> cache({(size_t)128 << 20, (size_t)2 << 30, (size_t)2 << 30, true, true}, !(e && e[0] == '0'));
-    return cache;
-}
-
-template <class T>
-static int dev_alloc(T **p, size_t n) {
-    *p = nullptr;
-    if (n == 0) n = 1;
-    *p = (T *)dev_cache().alloc(n * sizeof(T));
-    if (!*p) return trc_fail(TRC_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", n * sizeof(T), hipGetErrorString(DevBackend::err));
-    return TRC_OK;
-}
-template <class T>
-static void dev_free(T *&p) {
-    if (p) (void)dev_cache().free((void *)p);
-    p = nullptr;
-}
-
-// Owner of one block of dev_alloc: freed when it is reset, replaced or goes out of scope.  Kernel parameter structs take get().
-template <class T>
-class DevBuf {
-    T *p_ = nullptr;
-public:
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    DevBuf(DevBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
-    DevBuf &operator=(DevBuf &&o) noexcept {
-        if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
-        return *this;
-    }
-    ~DevBuf() { reset(); }
-    int alloc(size_t n) { reset(); return dev_alloc(&p_, n); }
-    void reset() { dev_free(p_); }
-    T *get() const { return p_; }
-    explicit operator bool() const { return p_ != nullptr; }
-};
-
-// A DevBuf kept between calls that only grows.  reserve(n) leaves a buffer of n elements or more alone; a smaller one is replaced
-// by a new one of n, contents not kept.  A reserve that fails leaves size() 0, so a buffer half grown claims nothing.
-template <class T>
-class GrowBuf {
-    DevBuf<T> b_;
-    size_t n_ = 0;
-public:
-    int reserve(size_t n) {
-        if (n <= n_) return TRC_OK;
-        n_ = 0;
-        TRC_TRY(b_.alloc(n));
-        n_ = n;
-        return TRC_OK;
-    }
-    void reset() { b_.reset(); n_ = 0; }
-    T *get() const { return b_.get(); }
-    size_t size() const { return n_; }
-};
-
-// a new block of n elements for `b`, and the n elements of host `src` copied into it (nothing is copied for n == 0 or no src);
-// a failed copy reports `fail` when given
-template <class T>
-static int dev_upload(DevBuf<T> &b, const T *src, size_t n, const char *fail = nullptr) {
-    TRC_TRY(b.alloc(n));
-    if (n == 0 || !src) return TRC_OK;
-    if (fail) {
-        if (hipMemcpy(b.get(), src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "%s", fail);
-    } else HIP_TRY(hipMemcpy(b.get(), src, n * sizeof(T), hipMemcpyHostToDevice));
-    return TRC_OK;
-}
-
-// n elements of device `src` to host `dst`
-template <class T>
-static int dev_download(T *dst, const T *src, size_t n) {
-    if (hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
-    return TRC_OK;
-}
-
-// Owner of a HIP handle that FREE releases -- a stream, an event, a pinned host block -- in the style of DevBuf.  own() takes a
-// handle this object made and releases with FREE; borrow() takes somebody else's, which is only forgotten.
-template <class H, auto FREE>
-class HipHandle {
-    H h_ = nullptr;
-    bool owned_ = false;
-public:
-    HipHandle() = default;
-    HipHandle(const HipHandle &) = delete;
-    HipHandle &operator=(const HipHandle &) = delete;
-    ~HipHandle() { reset(); }
-    void reset() { if (h_ && owned_) (void)FREE(h_); h_ = nullptr; owned_ = false; }
-    void own(H h) { reset(); h_ = h; owned_ = true; }
-    void borrow(H h) { reset(); h_ = h; }
-    H get() const { return h_; }
-};
-using StreamHandle = HipHandle<hipStream_t, hipStreamDestroy>;
-using EventHandle = HipHandle<hipEvent_t, hipEventDestroy>;
-using PinnedWords = HipHandle<unsigned long long *, hipHostFree>;
-
 // ================================================================================================
 // host-side objects
 // ================================================================================================
-struct trc_ctx {
-    int device;
-    hipStream_t stream;
-    hipEvent_t ev0, ev1;
-    int n_cu;
-};
-
 // The fast engine's hit buffer, where the hits on capturing surfaces wait until a script reads them: eight columns (absorbed and
 // incident energy, hit point, direction) and the surface of every entry, -1 for an entry not written.  Hits of polychromatic rays
 // bring 3 W spectral columns more: per hit the W sample wavelengths, the W samples of the spectrum that arrived and the W that left
@@ -937,64 +790,6 @@ static int kernel_grid_cap(const void *fn, int threads, size_t lds, int max_bpc,
 #include "trc_stream.inc"
 
 // ================================================================================================
-// source generation as a bundle (sources.*_bundle)
-// ================================================================================================
-template <bool THERMAL>
-__device__ __forceinline__ void source_generate_body(const trc_source_desc *src, long long n, unsigned long long seed, unsigned long long offset,
-                                                     double *x, double *y, double *z, double *dx, double *dy, double *dz, double *e,
-                                                     uint64_t *rid, double *l_buie) {
-    for (int i = threadIdx.x; i < TRC_BUIE_TABLE; i += blockDim.x) l_buie[i] = src->buie[i];
-    if (threadIdx.x == 0 && (src->kind == TRC_SRC_BUIE_DISK || src->kind == TRC_SRC_BUIE_RECT)) trc_buie_aureole_consts(src->buie, l_buie + TRC_BUIE_TABLE);
-    __syncthreads();
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (long long)gridDim.x * blockDim.x) {
-        unsigned long long r = offset + (unsigned long long)i;
-        double px, py, pz, qx, qy, qz;
-        trc_source_ray<THERMAL>(src, l_buie, l_buie + TRC_BUIE_TABLE, seed, r, &px, &py, &pz, &qx, &qy, &qz);
-        x[i] = px; y[i] = py; z[i] = pz;
-        dx[i] = qx; dy[i] = qy; dz[i] = qz;
-        e[i] = src->energy;
-        if (rid) rid[i] = r;
-    }
-}
-
-// every kind but the thermal emitter ...
-__global__ __launch_bounds__(256) void k_source_generate(const trc_source_desc *src, long long n,
-                                                         unsigned long long seed, unsigned long long offset,
-                                                         double *x, double *y, double *z, double *dx, double *dy,
-                                                         double *dz, double *e, uint64_t *rid) {
-    __shared__ double l_buie[TRC_BUIE_STAGED];
-    source_generate_body<false>(src, n, seed, offset, x, y, z, dx, dy, dz, e, rid, l_buie);
-}
-
-// ... and the thermal emitter (TRC_SRC_EMIT_THERMAL), whose sampler would cost the kernel above two waves of occupancy
-__global__ __launch_bounds__(256) void k_source_generate_emit(const trc_source_desc *src, long long n,
-                                                              unsigned long long seed, unsigned long long offset,
-                                                              double *x, double *y, double *z, double *dx, double *dy,
-                                                              double *dz, double *e, uint64_t *rid) {
-    __shared__ double l_buie[TRC_BUIE_STAGED];
-    source_generate_body<true>(src, n, seed, offset, x, y, z, dx, dy, dz, e, rid, l_buie);
-}
-
-// the generation kernel of a descriptor's kind (host: src is the caller's copy)
-static auto source_generate_kernel(const trc_source_desc *src) -> decltype(&k_source_generate) {
-    return src->kind == TRC_SRC_EMIT_THERMAL ? k_source_generate_emit : k_source_generate;
-}
-
-// float32 start points as k_s_cull evaluates them (trc_source_start32)
-__global__ __launch_bounds__(256) void k_source_start32(trc_fp_params F, long long n, unsigned long long seed, unsigned long long offset,
-                                                        float *lx, float *ly) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const unsigned long long rid = offset + (unsigned long long)i;
-        uint32_t o[4];
-        trc_philox4x32_10((uint32_t)rid, (uint32_t)(rid >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), o);
-        float x, y;
-        trc_fp_position32(F, o, &x, &y);
-        lx[i] = x; ly[i] = y;
-    }
-}
-
-// ================================================================================================
 // ordered engine
 // ================================================================================================
 struct OrdParams {
@@ -1276,90 +1071,6 @@ __global__ void k_fill_rid(uint64_t *p, long long n, unsigned long long offset) 
 }
 
 // ================================================================================================
-// per-surface protocol kernels
-// ================================================================================================
-__global__ __launch_bounds__(256) void k_gm_intersect(const double *rec, const double *extra, long long n,
-                                                      const double *x, const double *y, const double *z,
-                                                      const double *dx, const double *dy, const double *dz,
-                                                      double *t_out, double *hx, double *hy, double *hz) {
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double t = trc_intersect(rec, extra, x[i], y[i], z[i], dx[i], dy[i], dz[i]);
-    t_out[i] = t;
-    if (hx) {
-        // FiniteFlatGM / QuadricGM keep v + t*d for every ray (flat_surface.py:156, quadric.py:101)
-        hx[i] = x[i] + t * dx[i]; hy[i] = y[i] + t * dy[i]; hz[i] = z[i] + t * dz[i];
-    }
-}
-
-__global__ __launch_bounds__(256) void k_gm_normals(const double *rec, long long n, const double *hx,
-                                                    const double *hy, const double *hz, const double *dx,
-                                                    const double *dy, const double *dz, double *nx, double *ny,
-                                                    double *nz) {
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double a, b, c;
-    trc_normal(rec, hx[i], hy[i], hz[i], dx[i], dy[i], dz[i], &a, &b, &c);
-    nx[i] = a; ny[i] = b; nz[i] = c;
-}
-
-struct OpticsParams {
-    const double *rec, *opt, *extra;
-    long long n;
-    const double *dx, *dy, *dz, *e, *ref, *wl;
-    const uint64_t *rid;
-    unsigned long long ray_offset;
-    const double *path;             // distance from the ray origin to the hit (null: 0)
-    const double *nx, *ny, *nz;
-    unsigned long long seed;
-    int event;
-    double *odx, *ody, *odz, *oe, *oref;
-    int32_t *oblk;  // 2n: -1 empty, else block id
-    // complex indices, material rows, spectra (trc_shade_x): inputs with rows n apart, outputs 2n apart
-    const double *ref_im, *mat, *spec_wl, *spec;
-    int n_mat, W;
-    double *o_im, *o_spec;
-    double *oshift;     // 2n: how far along the oriented normal the outgoing ray starts from the hit point (PeriodicBoundary)
-};
-
-__global__ __launch_bounds__(256) void k_optics_apply(OpticsParams P) {
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= P.n) return;
-    trc_ray_out out[2];
-    unsigned long long rid = P.rid ? P.rid[i] : (P.ray_offset + (unsigned long long)i);
-    const double path = P.path ? P.path[i] : 0.0;
-    trc_ray_ext X;
-    X.ref_im = P.ref_im ? P.ref_im[i] : 0.0;
-    X.W = P.W; X.n_mat = P.n_mat; X.stride = P.n;
-    X.mat = P.mat ? P.mat + i : nullptr;
-    X.wl = P.spec_wl ? P.spec_wl + i : nullptr;
-    X.spec = P.spec ? P.spec + i : nullptr;
-    double out_im[2], poly_th;
-    int n_out = trc_shade_x(trc_rec_opt_kind(P.rec), P.opt, P.extra, trc_rec_extra_off(P.rec),
-                            trc_rec_extra_len(P.rec), P.rec[2], P.rec[5], P.rec[8], P.dx[i], P.dy[i], P.dz[i],
-                            P.e[i], P.ref ? P.ref[i] : 1.0, P.wl ? P.wl[i] : 0.0, path, P.nx[i], P.ny[i], P.nz[i], P.seed,
-                            rid, (uint32_t)P.event, X, out, out_im, &poly_th);
-    for (int c = 0; c < 2; ++c) {
-        long long slot = c == 0 ? i : P.n + i;
-        if (c < n_out) {
-            P.odx[slot] = out[c].dx; P.ody[slot] = out[c].dy; P.odz[slot] = out[c].dz;
-            P.oe[slot] = out[c].e; P.oref[slot] = out[c].ref; P.oblk[slot] = out[c].blk;
-            P.oshift[slot] = out[c].shift;
-            if (P.o_im) P.o_im[slot] = out_im[c];
-            if (P.o_spec) {
-                const double *tab = P.extra + trc_rec_extra_off(P.rec);
-                for (int w = 0; w < P.W; ++w) {
-                    const double f = poly_th >= 0.0 ? 1.0 - trc_poly_absorptance(tab, poly_th, X.wl[(size_t)w * P.n]) : out[c].sf;
-                    P.o_spec[(size_t)w * 2 * P.n + slot] = X.spec[(size_t)w * P.n] * f;
-                }
-            }
-        } else {
-            P.oblk[slot] = -1;
-        }
-    }
-}
-
-// ================================================================================================
 // C-ABI: context
 // ================================================================================================
 extern "C" int trc_ctx_create(int device_id, trc_ctx **out) {
@@ -1416,12 +1127,6 @@ extern "C" int trc_ctx_device_name(trc_ctx *ctx, char *buf, int buflen) {
 // ================================================================================================
 // C-ABI: scene
 // ================================================================================================
-static int validate_surface(const trc_surface_desc &s, int idx, int n_extra) {
-    char why[512];
-    const int st = trc_surface_check(s, idx, n_extra, why, sizeof(why));
-    return st == TRC_OK ? TRC_OK : trc_fail(st, "%s", why);
-}
-
 int SceneSurfaces::create(const trc_surface_desc *surfs, int32_t n, int32_t n_extra, const double *extra) {
     stride_ = trc_scene_stride(surfs, n);
     trc_scene_scan(surfs, n, &splits_, &needs_);
@@ -1890,10 +1595,7 @@ extern "C" int trc_scene_eval_materials(trc_scene *sc, int64_t n, const double *
     TRC_TRY(d_wl.alloc((size_t)n));
     TRC_TRY(d_out.alloc((size_t)n * 2 * (size_t)sc->mat_tab_n));
     HIP_TRY(hipMemcpy(d_wl.get(), wl, (size_t)n * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_material_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sc->ctx->stream, (const double *)sc->d_mat_tab.get(),
-                       (int)sc->mat_tab_n, (const double *)d_wl.get(), (long long)n, d_out.get());
-    const hipError_t se = hipStreamSynchronize(sc->ctx->stream);
-    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_material_eval failed: %s", hipGetErrorString(se));
+    TRC_TRY(launch_wait(sc->ctx, "k_material_eval", k_material_eval, n, 0, sc->d_mat_tab.get(), sc->mat_tab_n, d_wl.get(), n, d_out.get()));
     HIP_TRY(hipMemcpy(out, d_out.get(), (size_t)n * 2 * (size_t)sc->mat_tab_n * 8, hipMemcpyDeviceToHost));
     return TRC_OK;
 }
@@ -2101,443 +1803,8 @@ extern "C" int trc_scene_import_tallies(trc_scene *sc, const double *src, int32_
 }
 
 // ================================================================================================
-// ray staging helpers
-// ================================================================================================
-// the columns of a bundle as the kernels read them: the caller's own when they are on the device, else copies held in `own`
-struct DevRays {
-    double *x = nullptr, *y = nullptr, *z = nullptr, *dx = nullptr, *dy = nullptr, *dz = nullptr, *e = nullptr;
-    double *ref = nullptr, *wl = nullptr;
-    uint64_t *rid = nullptr;
-    DevBuf<double> own[9];
-    DevBuf<uint64_t> own_rid;
-};
-
-static int check_rays(const trc_rays *r, int64_t n, const char *who) {
-    if (!r) return trc_fail(TRC_ERR_INVALID, "%s: rays is NULL", who);
-    if (r->n < n) return trc_fail(TRC_ERR_INVALID, "%s: bundle holds %lld rays, %lld requested", who, (long long)r->n, (long long)n);
-    if (n > 0 && (!r->x || !r->y || !r->z || !r->dx || !r->dy || !r->dz))
-        return trc_fail(TRC_ERR_INVALID, "%s: vertices and directions are required", who);
-    return TRC_OK;
-}
-
-// bring the required columns of a bundle to the device (no copy when already there)
-static int stage_rays(const trc_rays *r, int64_t n, bool need_energy, DevRays *d) {
-    const double *src[9] = {r->x, r->y, r->z, r->dx, r->dy, r->dz, r->e, r->ref_index, r->wavelength};
-    double **dst[9] = {&d->x, &d->y, &d->z, &d->dx, &d->dy, &d->dz, &d->e, &d->ref, &d->wl};
-    if (need_energy && !r->e) return trc_fail(TRC_ERR_INVALID, "ray energies are required");
-    for (int i = 0; i < 9; ++i) {
-        if (!src[i]) continue;
-        if (r->on_device) { *dst[i] = (double *)src[i]; continue; }
-        TRC_TRY(dev_upload(d->own[i], src[i], (size_t)n));
-        *dst[i] = d->own[i].get();
-    }
-    if (r->rid) {
-        if (r->on_device) d->rid = r->rid;
-        else {
-            TRC_TRY(dev_upload(d->own_rid, r->rid, (size_t)n));
-            d->rid = d->own_rid.get();
-        }
-    }
-    return TRC_OK;
-}
-
-// ================================================================================================
-// tabulated sunshapes (trc_sunshape): tables packed and uploaded once, named by descriptors through their id
-// ================================================================================================
-struct trc_sunshape {
-    int device;                     // the GPU of the context it was made on
-    int32_t id, n;
-    std::vector<double> tab;        // theta | g | cdf (trc_sunshape_theta layout)
-    double theta_c, u_c;
-    int packing = 0;                // which create function packed it: 0 trc_sunshape_create, 1 trc_angle_table_create, 2 trc_emittance_table_create
-    DevBuf<double> d_tab;
-};
-
-// every live table by id; ids count up and are never reused, so that a descriptor (and the footprint map cached from it) always
-// means the same table
-static std::mutex g_sun_mu;
-static std::unordered_map<int32_t, trc_sunshape *> g_sun;
-static int32_t g_sun_next = 1;
-
-// checks a table (trc_sunshape_create's errors) and packs it (trc_sunshape_pack)
-static int sunshape_pack(int32_t n, const double *angle, const double *intensity, std::vector<double> &tab, double *theta_c, double *u_c) {
-    if (n < 2 || n > TRC_SUNSHAPE_MAX_POINTS)
-        return trc_fail(TRC_ERR_INVALID, "trc_sunshape_create: the table has %d points, 2..%d allowed", n, TRC_SUNSHAPE_MAX_POINTS);
-    if (!angle || !intensity) return trc_fail(TRC_ERR_INVALID, "trc_sunshape_create: angles or intensities missing");
-    for (int i = 0; i < n; ++i) {
-        if (!std::isfinite(angle[i])) return trc_fail(TRC_ERR_INVALID, "trc_sunshape_create: angle %d is not finite", i);
-        if (i > 0 && !(angle[i] > angle[i - 1]))
-            return trc_fail(TRC_ERR_INVALID, "trc_sunshape_create: angles are not strictly increasing (point %d)", i);
-        if (!std::isfinite(intensity[i]) || intensity[i] < 0.0)
-            return trc_fail(TRC_ERR_INVALID, "trc_sunshape_create: intensity %d is negative or not finite", i);
-    }
-    if (!(angle[0] >= 0.0) || !(angle[n - 1] < TRC_PI / 2.0))
-        return trc_fail(TRC_ERR_INVALID, "trc_sunshape_create: angles must lie in [0, pi/2)");
-    tab.assign((size_t)3 * n, 0.0);
-    if (!trc_sunshape_pack(n, angle, intensity, tab.data(), theta_c, u_c))
-        return trc_fail(TRC_ERR_INVALID, "trc_sunshape_create: the table has no mass");
-    return TRC_OK;
-}
-
-extern "C" int trc_sunshape_create(trc_ctx *ctx, int32_t n, const double *angle, const double *intensity, trc_sunshape **out) {
-    if (!ctx || !out) return trc_fail(TRC_ERR_INVALID, "trc_sunshape_create: bad arguments");
-    *out = nullptr;
-    std::unique_ptr<trc_sunshape> t(new (std::nothrow) trc_sunshape());
-    if (!t) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
-    TRC_TRY(sunshape_pack(n, angle, intensity, t->tab, &t->theta_c, &t->u_c));
-    t->device = ctx->device; t->n = n;
-    HIP_TRY(hipSetDevice(ctx->device));
-    TRC_TRY(dev_upload(t->d_tab, t->tab.data(), t->tab.size(), "sunshape upload failed"));
-    std::lock_guard<std::mutex> lk(g_sun_mu);
-    if (g_sun_next == INT32_MAX) return trc_fail(TRC_ERR_CAPACITY, "trc_sunshape_create: table ids exhausted");
-    t->id = g_sun_next++;
-    g_sun[t->id] = t.get();
-    *out = t.release();
-    return TRC_OK;
-}
-
-extern "C" int trc_sunshape_id(trc_sunshape *t, int32_t *id) {
-    if (!t || !id) return trc_fail(TRC_ERR_INVALID, "trc_sunshape_id: bad arguments");
-    *id = t->id;
-    return TRC_OK;
-}
-
-extern "C" int trc_sunshape_get(trc_sunshape *t, int32_t *n, double *packed, double *theta_c, double *u_c) {
-    if (!t) return trc_fail(TRC_ERR_INVALID, "trc_sunshape_get: table is NULL");
-    if (n) *n = t->n;
-    if (packed) memcpy(packed, t->tab.data(), t->tab.size() * sizeof(double));
-    if (theta_c) *theta_c = t->theta_c;
-    if (u_c) *u_c = t->u_c;
-    return TRC_OK;
-}
-
-extern "C" int trc_sunshape_destroy(trc_sunshape *t) {
-    if (!t) return TRC_OK;
-    {
-        std::lock_guard<std::mutex> lk(g_sun_mu);
-        g_sun.erase(t->id);
-    }
-    HIP_TRY(hipSetDevice(t->device));
-    delete t;
-    return TRC_OK;
-}
-
-// the polar table of an arc lamp (TRC_SRC_ARC_VOLUME): a trc_sunshape packed as a source spectrum's table (trc_angle_table_pack)
-extern "C" int trc_angle_table_create(trc_ctx *ctx, int32_t n, const double *angle, const double *density, trc_sunshape **out) {
-    if (!ctx || !out) return trc_fail(TRC_ERR_INVALID, "trc_angle_table_create: bad arguments");
-    *out = nullptr;
-    if (n < 2 || n > TRC_SUNSHAPE_MAX_POINTS)
-        return trc_fail(TRC_ERR_INVALID, "trc_angle_table_create: the table has %d points, 2..%d allowed", n, TRC_SUNSHAPE_MAX_POINTS);
-    if (!angle || !density) return trc_fail(TRC_ERR_INVALID, "trc_angle_table_create: angles or densities missing");
-    for (int i = 0; i < n; ++i) {
-        if (!std::isfinite(angle[i])) return trc_fail(TRC_ERR_INVALID, "trc_angle_table_create: angle %d is not finite", i);
-        if (i > 0 && !(angle[i] > angle[i - 1]))
-            return trc_fail(TRC_ERR_INVALID, "trc_angle_table_create: angles are not strictly increasing (point %d)", i);
-        if (!std::isfinite(density[i]) || density[i] < 0.0)
-            return trc_fail(TRC_ERR_INVALID, "trc_angle_table_create: density %d is negative or not finite", i);
-    }
-    if (!(angle[0] >= 0.0) || !(angle[n - 1] <= TRC_PI)) return trc_fail(TRC_ERR_INVALID, "trc_angle_table_create: angles must lie in [0, pi]");
-    std::unique_ptr<trc_sunshape> t(new (std::nothrow) trc_sunshape());
-    if (!t) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
-    t->tab.assign((size_t)3 * n, 0.0);
-    if (!trc_angle_table_pack(n, angle, density, t->tab.data())) return trc_fail(TRC_ERR_INVALID, "trc_angle_table_create: the table has no mass");
-    t->device = ctx->device; t->n = n;
-    t->theta_c = angle[n - 1]; t->u_c = 1.0;
-    t->packing = 1;
-    HIP_TRY(hipSetDevice(ctx->device));
-    TRC_TRY(dev_upload(t->d_tab, t->tab.data(), t->tab.size(), "angle table upload failed"));
-    std::lock_guard<std::mutex> lk(g_sun_mu);
-    if (g_sun_next == INT32_MAX) return trc_fail(TRC_ERR_CAPACITY, "trc_angle_table_create: table ids exhausted");
-    t->id = g_sun_next++;
-    g_sun[t->id] = t.get();
-    *out = t.release();
-    return TRC_OK;
-}
-
-// the emittance table of a thermal emitter (TRC_SRC_EMIT_THERMAL): a trc_sunshape packed by trc_emittance_pack
-extern "C" int trc_emittance_table_create(trc_ctx *ctx, int32_t n, const double *theta, const double *eps, trc_sunshape **out) {
-    if (!ctx || !out) return trc_fail(TRC_ERR_INVALID, "trc_emittance_table_create: bad arguments");
-    *out = nullptr;
-    if (const char *fault = trc_emittance_table_fault(n, theta, eps)) return trc_fail(TRC_ERR_INVALID, "trc_emittance_table_create: %s", fault);
-    std::unique_ptr<trc_sunshape> t(new (std::nothrow) trc_sunshape());
-    if (!t) return trc_fail(TRC_ERR_NOMEM, "out of host memory");
-    t->tab.assign((size_t)3 * n, 0.0);
-    double mass = 0.0;
-    if (!trc_emittance_pack(n, theta, eps, t->tab.data(), &mass)) return trc_fail(TRC_ERR_INVALID, "trc_emittance_table_create: the table has no mass");
-    t->device = ctx->device; t->n = n;
-    t->theta_c = t->tab[n - 1]; t->u_c = mass;
-    t->packing = 2;
-    HIP_TRY(hipSetDevice(ctx->device));
-    TRC_TRY(dev_upload(t->d_tab, t->tab.data(), t->tab.size(), "emittance table upload failed"));
-    std::lock_guard<std::mutex> lk(g_sun_mu);
-    if (g_sun_next == INT32_MAX) return trc_fail(TRC_ERR_CAPACITY, "trc_emittance_table_create: table ids exhausted");
-    t->id = g_sun_next++;
-    g_sun[t->id] = t.get();
-    *out = t.release();
-    return TRC_OK;
-}
-
-// the kinds whose descriptor names a table: the tabulated sunshapes, the arc volume with its polar table and the thermal emitter with
-// its emittance table
-static bool source_is_sunshape(int kind) {
-    return kind == TRC_SRC_SUNSHAPE_DISK || kind == TRC_SRC_SUNSHAPE_RECT || kind == TRC_SRC_ARC_VOLUME || kind == TRC_SRC_EMIT_THERMAL;
-}
-
-// A sunshape descriptor as the kernels read it: `tmp` = *src with theta_c, u_c, n in p[] and the table's device address in
-// buie[0]; `src` then points to it.  Other kinds are left as they are.  A host-side lookup: no device traffic.
-static int source_resolve(trc_ctx *ctx, const trc_source_desc *&src, trc_source_desc &tmp, const char *who) {
-    if (!src || !source_is_sunshape(src->kind)) return TRC_OK;
-    std::lock_guard<std::mutex> lk(g_sun_mu);
-    auto it = g_sun.find(src->table);
-    if (it == g_sun.end()) return trc_fail(TRC_ERR_INVALID, "%s: the source names sunshape table %d, which does not exist (destroyed?)", who, src->table);
-    const trc_sunshape *t = it->second;
-    if (ctx && t->device != ctx->device) return trc_fail(TRC_ERR_INVALID, "%s: sunshape table %d lives on another device", who, src->table);
-    if (src->kind == TRC_SRC_EMIT_THERMAL) {       // (the one kind that checks the packing: its sampler solves another equation)
-        if (t->packing != 2)
-            return trc_fail(TRC_ERR_INVALID, "%s: table %d is not an emittance table (trc_emittance_table_create)", who, src->table);
-        const int shape = (int)src->p[0];
-        if (!(src->p[0] >= TRC_THERMAL_DISK && src->p[0] <= TRC_THERMAL_SPHERE) || (double)shape != src->p[0])
-            return trc_fail(TRC_ERR_INVALID, "%s: a thermal emitter has no shape %g", who, src->p[0]);
-        if (shape == TRC_THERMAL_FRUSTUM && src->p[1] == src->p[2])
-            return trc_fail(TRC_ERR_INVALID, "%s: a thermal frustum needs r0 != r1 (use the cylinder)", who);
-    }
-    tmp = *src;
-    if (src->kind != TRC_SRC_EMIT_THERMAL) {        // (a thermal emitter keeps its shape parameters and its sign there)
-        tmp.p[TRC_SUNSHAPE_P_THETA_C] = t->theta_c;
-        tmp.p[TRC_SUNSHAPE_P_U_C] = t->u_c;
-    }
-    tmp.p[TRC_SUNSHAPE_P_N] = (double)t->n;
-    memset(tmp.buie, 0, sizeof(tmp.buie));
-    tmp.buie[0] = __builtin_bit_cast(double, (uint64_t)(uintptr_t)t->d_tab.get());
-    src = &tmp;
-    return TRC_OK;
-}
-
-static int source_kind_check(const trc_source_desc *src) {
-    if (src->kind < TRC_SRC_PILLBOX_DISK || src->kind > TRC_SRC_EMIT_THERMAL)
-        return trc_fail(TRC_ERR_UNSUPPORTED, "source kind %d is not in the native table", src->kind);
-    return TRC_OK;
-}
-
-static int upload_source(const trc_source_desc *src, DevBuf<trc_source_desc> &d_src) {
-    TRC_TRY(source_kind_check(src));
-    return dev_upload(d_src, src, 1);
-}
-
-// ================================================================================================
-// C-ABI: source generation
-// ================================================================================================
-extern "C" int trc_source_start32(trc_ctx *ctx, const trc_source_desc *src, int64_t n, uint64_t seed, uint64_t ray_offset,
-                                  float *lx, float *ly, double *eps) {
-    if (!ctx || !src || n < 0 || !lx || !ly) return trc_fail(TRC_ERR_INVALID, "trc_source_start32: bad arguments");
-    trc_source_desc src_res;
-    TRC_TRY(source_resolve(ctx, src, src_res, "trc_source_start32"));
-    HIP_TRY(hipSetDevice(ctx->device));
-    trc_fp_params F;
-    double half = 0.0, theta_c = 0.0;
-    const char *why = "";
-    if (!trc_fp_source(*src, F, &half, &theta_c, &why)) return trc_fail(TRC_ERR_UNSUPPORTED, "no footprint map for this source: %s", why);
-    if (eps) *eps = TRC_FP_EPS_REL * half;
-    if (n == 0) return TRC_OK;
-    DevBuf<float> d[2];
-    TRC_TRY(d[0].alloc((size_t)n));
-    TRC_TRY(d[1].alloc((size_t)n));
-    long long grid = (n + 255) / 256;
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(k_source_start32, dim3((unsigned)grid), dim3(256), 0, ctx->stream, F, (long long)n, (unsigned long long)seed,
-                       (unsigned long long)ray_offset, d[0].get(), d[1].get());
-    hipError_t se = hipStreamSynchronize(ctx->stream);
-    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_source_start32 failed: %s", hipGetErrorString(se));
-    TRC_TRY(dev_download(lx, d[0].get(), (size_t)n));
-    return dev_download(ly, d[1].get(), (size_t)n);
-}
-
-extern "C" int trc_source_generate(trc_ctx *ctx, const trc_source_desc *src, int64_t n, uint64_t seed,
-                                   uint64_t ray_offset, trc_rays *out) {
-    if (!ctx || !src || n < 0) return trc_fail(TRC_ERR_INVALID, "trc_source_generate: bad arguments");
-    trc_source_desc src_res;
-    TRC_TRY(source_resolve(ctx, src, src_res, "trc_source_generate"));
-    TRC_TRY(check_rays(out, n, "trc_source_generate"));
-    if (!out->e) return trc_fail(TRC_ERR_INVALID, "trc_source_generate: energy column required");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (n == 0) return TRC_OK;
-    DevBuf<trc_source_desc> d_src;
-    TRC_TRY(upload_source(src, d_src));
-    // the kernel writes the caller's columns when they are on the device, else copies held in `own`
-    double *host[7] = {out->x, out->y, out->z, out->dx, out->dy, out->dz, out->e};
-    double *d[7];
-    uint64_t *d_rid = out->rid;
-    DevBuf<double> own[7];
-    DevBuf<uint64_t> own_rid;
-    for (int i = 0; i < 7; ++i) d[i] = host[i];
-    if (!out->on_device) {
-        for (int i = 0; i < 7; ++i) { TRC_TRY(own[i].alloc((size_t)n)); d[i] = own[i].get(); }
-        if (out->rid) TRC_TRY(own_rid.alloc((size_t)n));
-        d_rid = own_rid.get();
-    }
-    long long grid = (n + 255) / 256;
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(source_generate_kernel(src), dim3((unsigned)grid), dim3(256), 0, ctx->stream, d_src.get(), (long long)n,
-                       (unsigned long long)seed, (unsigned long long)ray_offset, d[0], d[1], d[2], d[3], d[4], d[5],
-                       d[6], d_rid);
-    hipError_t se = hipStreamSynchronize(ctx->stream);
-    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_source_generate failed: %s", hipGetErrorString(se));
-    if (!out->on_device) {
-        for (int i = 0; i < 7; ++i) TRC_TRY(dev_download(host[i], d[i], (size_t)n));
-        if (out->rid) TRC_TRY(dev_download(out->rid, d_rid, (size_t)n));
-    }
-    return TRC_OK;
-}
-
-// ================================================================================================
-// source spectra (trc_source_spectrum): one wavelength per source ray, drawn from (seed, stream id)
-// ================================================================================================
-// wl[i], ref[i] of source rays offset + i: CONSTANT writes the constant, TABLE draws (trc_spectrum_draw; tab = wl | val | cdf)
-__global__ __launch_bounds__(256) void k_source_spectrum(const double *tab, int n_tab, int kind, double wl_const, double ref_index,
-                                                         long long n, unsigned long long seed, unsigned long long offset,
-                                                         double *wl, double *ref) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        if (wl) wl[i] = kind == TRC_SPECTRUM_TABLE ? trc_spectrum_draw(tab, tab + n_tab, tab + 2 * n_tab, n_tab, seed, offset + (unsigned long long)i)
-                                                   : wl_const;
-        if (ref) ref[i] = ref_index;
-    }
-}
-
-// A carried spectrum (TRC_SPECTRUM_CARRIED): every ray i brings all n_tab points -- sample w at [w * stride + i]: the grid's
-// wavelength, and e[i] * val[w], whose trapezoid integral is the ray's energy (tab = wl | val | cdf)
-__global__ __launch_bounds__(256) void k_source_carried(const double *tab, int n_tab, long long n, long long stride, const double *e,
-                                                        double *spec_wl, double *spectra) {
-    const long long total = (long long)n_tab * n;
-    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < total; k += (long long)gridDim.x * blockDim.x) {
-        const long long w = k / n, i = k - w * n;
-        if (spec_wl) spec_wl[w * stride + i] = tab[w];
-        if (spectra) spectra[w * stride + i] = e[i] * tab[n_tab + w];
-    }
-}
-
-// A spectrum checked and packed for the device: wl | density normalised to a unit trapezoid integral | its running integral
-// (float64 on the host; the last entry of the CDF is 1 exactly, so every u in [0, 1) finds an interval of positive mass).
-static int spectrum_pack(const trc_source_spectrum *sp, const char *who, std::vector<double> &tab) {
-    tab.clear();
-    if (sp->kind != TRC_SPECTRUM_CONSTANT && sp->kind != TRC_SPECTRUM_TABLE && sp->kind != TRC_SPECTRUM_CARRIED)
-        return trc_fail(TRC_ERR_INVALID, "%s: spectrum kind %d is neither CONSTANT nor TABLE nor CARRIED", who, sp->kind);
-    if (!std::isfinite(sp->ref_index) || !(sp->ref_index > 0.0))
-        return trc_fail(TRC_ERR_INVALID, "%s: spectrum ref_index must be finite and positive", who);
-    if (sp->kind == TRC_SPECTRUM_CONSTANT) {
-        if (!std::isfinite(sp->wavelength)) return trc_fail(TRC_ERR_INVALID, "%s: spectrum wavelength is not finite", who);
-        return TRC_OK;
-    }
-    const int n = sp->n;
-    if (n < 2 || n > TRC_SPECTRUM_MAX_POINTS)
-        return trc_fail(TRC_ERR_INVALID, "%s: spectrum table has %d points, 2..%d allowed", who, n, TRC_SPECTRUM_MAX_POINTS);
-    if (!sp->wl || !sp->value) return trc_fail(TRC_ERR_INVALID, "%s: spectrum table without wavelengths or values", who);
-    for (int i = 0; i < n; ++i) {
-        if (!std::isfinite(sp->wl[i])) return trc_fail(TRC_ERR_INVALID, "%s: spectrum wavelength %d is not finite", who, i);
-        if (i > 0 && !(sp->wl[i] > sp->wl[i - 1]))
-            return trc_fail(TRC_ERR_INVALID, "%s: spectrum wavelengths are not strictly increasing (point %d)", who, i);
-        if (!std::isfinite(sp->value[i]) || sp->value[i] < 0.0)
-            return trc_fail(TRC_ERR_INVALID, "%s: spectrum value %d is negative or not finite", who, i);
-    }
-    tab.assign((size_t)3 * n, 0.0);
-    double *w = tab.data(), *v = w + n, *c = v + n;
-    double cum = 0.0;
-    for (int i = 0; i < n; ++i) {
-        w[i] = sp->wl[i];
-        if (i > 0) cum += (sp->wl[i] - sp->wl[i - 1]) * (sp->value[i] + sp->value[i - 1]) / 2.;
-        c[i] = cum;
-    }
-    if (!(cum > 0.0) || !std::isfinite(cum)) return trc_fail(TRC_ERR_INVALID, "%s: spectrum table has a zero (or non-finite) integral", who);
-    for (int i = 0; i < n; ++i) { v[i] = sp->value[i] / cum; c[i] = c[i] / cum; }
-    return TRC_OK;
-}
-
-static bool spectrum_given(const trc_source_spectrum *sp) { return sp && sp->kind != TRC_SPECTRUM_NONE; }
-static bool spectrum_carried(const trc_source_spectrum *sp) { return sp && sp->kind == TRC_SPECTRUM_CARRIED; }
-
-// wl / ref (device columns, either may be NULL) of source rays offset .. offset+n-1 on the context's stream
-static int spectrum_fill(trc_ctx *ctx, const trc_source_spectrum *sp, const std::vector<double> &tab, int64_t n, uint64_t seed,
-                         uint64_t ray_offset, double *wl, double *ref) {
-    if (n == 0 || (!wl && !ref)) return TRC_OK;
-    DevBuf<double> d_tab;
-    const int n_tab = sp->kind == TRC_SPECTRUM_TABLE ? sp->n : 0;
-    if (n_tab) TRC_TRY(dev_upload(d_tab, tab.data(), tab.size(), "spectrum upload failed"));
-    long long grid = (n + 255) / 256;
-    if (grid > 8192) grid = 8192;
-    // (a carried spectrum: no wavelength is drawn, the rays' scalar wavelength is 0 as for a given polychromatic bundle)
-    hipLaunchKernelGGL(k_source_spectrum, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const double *)d_tab.get(), n_tab, sp->kind,
-                       spectrum_carried(sp) ? 0.0 : sp->wavelength, sp->ref_index, (long long)n, (unsigned long long)seed, (unsigned long long)ray_offset, wl, ref);
-    hipError_t se = hipStreamSynchronize(ctx->stream);
-    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_source_spectrum failed: %s", hipGetErrorString(se));
-    return TRC_OK;
-}
-
-// spec_wl / spectra (device, rows `stride` apart, either may be NULL) of n source rays of energies e (device) under a carried spectrum
-static int carried_fill(trc_ctx *ctx, const trc_source_spectrum *sp, const std::vector<double> &tab, int64_t n, int64_t stride, const double *e,
-                        double *spec_wl, double *spectra) {
-    if (n == 0 || (!spec_wl && !spectra)) return TRC_OK;
-    DevBuf<double> d_tab;
-    TRC_TRY(dev_upload(d_tab, tab.data(), tab.size(), "spectrum upload failed"));
-    long long grid = ((long long)sp->n * n + 255) / 256;
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(k_source_carried, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const double *)d_tab.get(), (int)sp->n, (long long)n,
-                       (long long)stride, e, spec_wl, spectra);
-    hipError_t se = hipStreamSynchronize(ctx->stream);
-    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_source_carried failed: %s", hipGetErrorString(se));
-    return TRC_OK;
-}
-
-extern "C" int trc_source_generate_x(trc_ctx *ctx, const trc_source_desc *src, const trc_source_spectrum *spec, int64_t n,
-                                     uint64_t seed, uint64_t ray_offset, trc_rays *out) {
-    if (!spectrum_given(spec)) return trc_source_generate(ctx, src, n, seed, ray_offset, out);
-    if (!ctx || !src || n < 0) return trc_fail(TRC_ERR_INVALID, "trc_source_generate_x: bad arguments");
-    std::vector<double> tab;
-    TRC_TRY(spectrum_pack(spec, "trc_source_generate_x", tab));
-    if (spectrum_carried(spec) && (!out || !out->spec_wl || !out->spectra || out->n_spec != spec->n))
-        return trc_fail(TRC_ERR_INVALID, "trc_source_generate_x: a carried spectrum of %d points fills out->spec_wl and out->spectra, which need n_spec == %d",
-                        spec->n, spec->n);
-    TRC_TRY(trc_source_generate(ctx, src, n, seed, ray_offset, out));
-    if (spectrum_carried(spec) && n > 0) {
-        if (out->on_device) TRC_TRY(carried_fill(ctx, spec, tab, n, out->n, out->e, out->spec_wl, out->spectra));
-        else {
-            DevBuf<double> d_e, d_x[2];
-            TRC_TRY(dev_upload(d_e, out->e, (size_t)n, "energy upload failed"));
-            for (auto &b : d_x) TRC_TRY(b.alloc((size_t)spec->n * (size_t)n));
-            TRC_TRY(carried_fill(ctx, spec, tab, n, n, d_e.get(), d_x[0].get(), d_x[1].get()));
-            double *host[2] = {out->spec_wl, out->spectra};
-            for (int i = 0; i < 2; ++i)
-                HIP_TRY(hipMemcpy2D(host[i], (size_t)out->n * 8, d_x[i].get(), (size_t)n * 8, (size_t)n * 8, (size_t)spec->n, hipMemcpyDeviceToHost));
-        }
-    }
-    if (n == 0 || (!out->wavelength && !out->ref_index)) return TRC_OK;
-    if (out->on_device) return spectrum_fill(ctx, spec, tab, n, seed, ray_offset, out->wavelength, out->ref_index);
-    DevBuf<double> d[2];
-    double *host[2] = {out->wavelength, out->ref_index};
-    for (int i = 0; i < 2; ++i) if (host[i]) TRC_TRY(d[i].alloc((size_t)n));
-    TRC_TRY(spectrum_fill(ctx, spec, tab, n, seed, ray_offset, d[0].get(), d[1].get()));
-    for (int i = 0; i < 2; ++i) if (host[i]) TRC_TRY(dev_download(host[i], d[i].get(), (size_t)n));
-    return TRC_OK;
-}
-
-// ================================================================================================
 // what a call brings: the source's spectrum, the columns rays carry beyond the nine (both engines)
 // ================================================================================================
-// The spectrum of a source descriptor as the engines take it: checked, its table packed (spectrum_pack).  desc NULL: none.
-struct SourceSpectrum {
-    const trc_source_spectrum *desc = nullptr;
-    std::vector<double> tab;
-    int carried() const { return spectrum_carried(desc) ? desc->n : 0; }      // the samples W every ray carries (TRC_SPECTRUM_CARRIED), else 0
-};
-
-// ... made by the _x entry points (`who`) from their arguments; a spectrum belongs to a source descriptor
-static int source_spectrum_make(const trc_source_spectrum *spec, const trc_rays *in, const trc_source_desc *src, const char *who, SourceSpectrum *out) {
-    if (!spectrum_given(spec)) return TRC_OK;
-    if (in) return trc_fail(TRC_ERR_INVALID, "%s: a spectrum belongs to a source descriptor, not to a given bundle", who);
-    if (!src) return trc_fail(TRC_ERR_INVALID, "%s: a spectrum needs a source descriptor", who);
-    TRC_TRY(spectrum_pack(spec, who, out->tab));
-    out->desc = spec;
-    return TRC_OK;
-}
-
 // The spectrum travels to the fast engine as FastParams.spec (trc_spectrum_of layout: n, constant wavelength, index, then the
 // table), in a buffer kept on the scene between calls.  The SPEC instances of the kernels draw the wavelength where a source ray
 // first needs one.
@@ -2937,9 +2204,8 @@ static int ordered_level0(OrdCall &C, const trc_rays *in, const trc_source_desc 
     long long g0 = (n + 255) / 256; if (g0 > 8192) g0 = 8192; if (g0 < 1) g0 = 1;
     DevBuf<trc_source_desc> d_src;
     if (src) {
-        TRC_TRY(upload_source(src, d_src));
-        hipLaunchKernelGGL(source_generate_kernel(src), dim3((unsigned)g0), dim3(256), 0, ctx->stream, d_src.get(), (long long)n,
-                           (unsigned long long)C.seed, (unsigned long long)ray_offset, B0.x, B0.y, B0.z, B0.dx, B0.dy, B0.dz, B0.e, B0.rid);
+        double *const col[7] = {B0.x, B0.y, B0.z, B0.dx, B0.dy, B0.dz, B0.e};
+        TRC_TRY(source_generate_start(ctx, src, d_src, n, C.seed, ray_offset, col, B0.rid));
         if (spec.desc) {     // level 0 carries the wavelengths the source's spectrum gives its rays, and their index
             TRC_TRY(spectrum_fill(ctx, spec.desc, spec.tab, n, C.seed, ray_offset, B0.wl, B0.ref));
             // ... or, under a carried spectrum, the sample wavelengths and spectra of a polychromatic bundle: the level's own rows
@@ -3195,329 +2461,5 @@ extern "C" int trc_result_level_get(trc_result *res, int32_t level, trc_rays *ou
         if (out->spec_wl && lay.W) HIP_TRY(hipMemcpy2D(out->spec_wl, (size_t)cap * 8, L.pay + (size_t)lay.r_wl() * n, n * 8, n * 8, (size_t)lay.W, hipMemcpyDeviceToHost));
         if (out->spectra && lay.W) HIP_TRY(hipMemcpy2D(out->spectra, (size_t)cap * 8, L.pay + (size_t)lay.r_spec() * n, n * 8, n * 8, (size_t)lay.W, hipMemcpyDeviceToHost));
     }
-    return TRC_OK;
-}
-
-// ================================================================================================
-// C-ABI: KdTree.traversal on its own (accel_tree.py:213-312)
-// ================================================================================================
-struct KdTravParams {
-    const int32_t *flag, *child, *leaf_off, *leaf_cnt, *leaf_surfs;
-    const double *split;
-    double lo[3], hi[3];
-    const double *x, *y, *z, *dx, *dy, *dz;
-    long long n;
-    uint8_t *rel;       // n_surf rows of n bytes
-    int *flags;         // [0]: some ray meets the root box; [1]: a ray needed more than KD_TRAV_STACK pending nodes
-};
-
-#define KD_TRAV_STACK 64
-
-// numpy's maximum / minimum hand a nan on (intersect_bounds :325-326)
-__device__ inline double np_maximum(double a, double b) { return (a != a || b != b) ? NAN : (a > b ? a : b); }
-__device__ inline double np_minimum(double a, double b) { return (a != a || b != b) ? NAN : (a < b ? a : b); }
-
-__global__ __launch_bounds__(256) void k_kd_traversal(KdTravParams P) {
-    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= P.n) return;
-    const double pos[3] = {P.x[r], P.y[r], P.z[r]}, dir[3] = {P.dx[r], P.dy[r], P.dz[r]};
-    const double inv[3] = {1.0 / dir[0], 1.0 / dir[1], 1.0 / dir[2]};     // :224
-    double t_lo = 0.0, t_hi = INFINITY;                                     // intersect_bounds :314-330
-    for (int i = 0; i < 3; ++i) {
-        const bool neg = dir[i] < 0.0;
-        double a = ((neg ? P.hi[i] : P.lo[i]) - pos[i]) * inv[i];
-        double b = ((neg ? P.lo[i] : P.hi[i]) - pos[i]) * inv[i];
-        if (a > b) { const double t = a; a = b; b = t; }
-        t_lo = np_maximum(t_lo, a);
-        t_hi = np_minimum(t_hi, b);
-    }
-    if (!(t_hi > 0.0) || (t_lo > t_hi)) return;
-    P.flags[0] = 1;
-    int node = 0, top = 0;
-    int st_node[KD_TRAV_STACK];
-    double st_min[KD_TRAV_STACK], st_max[KD_TRAV_STACK];
-    double t_min = t_lo, t_max = t_hi;
-    while (true) {
-        if (t_hi < t_min) break;                                            // :243 (the root's exit against the current entry)
-        const int f = P.flag[node];
-        if (f != 3) {
-            const double sp = P.split[node];
-            const double t_plane = (sp - pos[f]) * inv[f];                  // :249
-            int c1 = P.child[node], c2 = c1 + 1;
-            const bool below_first = (pos[f] < sp) || (pos[f] == sp && dir[f] <= 0.0);
-            if (!below_first) { const int t = c1; c1 = c2; c2 = t; }
-            if (t_plane > t_max || t_plane <= 0.0) node = c1;               // :258-259
-            else if (t_plane < t_min) node = c2;
-            else {
-                if (top >= KD_TRAV_STACK) { P.flags[1] = 1; return; }
-                st_node[top] = c2; st_min[top] = t_plane; st_max[top] = t_max;
-                ++top;
-                node = c1;
-                t_max = t_plane;
-            }
-        } else {
-            const int off = P.leaf_off[node], cnt = P.leaf_cnt[node];
-            for (int k = 0; k < cnt; ++k) P.rel[(size_t)P.leaf_surfs[off + k] * P.n + r] = 1;       // :288
-            if (top > 0) { --top; node = st_node[top]; t_min = st_min[top]; t_max = st_max[top]; }
-            else break;
-        }
-    }
-}
-
-extern "C" int trc_kdtree_traversal(trc_ctx *ctx, const trc_kdtree_desc *kd, int32_t n_surf, const trc_rays *rays, int64_t n,
-                                    uint8_t *relevancy, int32_t *any_inter) {
-    if (!ctx || !kd || !relevancy || n_surf <= 0 || n < 0) return trc_fail(TRC_ERR_INVALID, "trc_kdtree_traversal: bad arguments");
-    TRC_TRY(check_rays(rays, n, "trc_kdtree_traversal"));
-    if (rays->on_device) return trc_fail(TRC_ERR_INVALID, "trc_kdtree_traversal: host bundle expected");
-    char why[160];
-    int depth = 0;      // (not refused here: a ray that runs out of stack raises the kernel's flag)
-    const int st = trc_kd_check(kd, n_surf, &depth, why, sizeof(why));
-    if (st != TRC_OK) return trc_fail(st, "trc_kdtree_traversal: %s", why);
-    HIP_TRY(hipSetDevice(ctx->device));
-    DevBuf<int32_t> d_i32[5];
-    DevBuf<double> d_split, d_r[6];
-    DevBuf<uint8_t> d_rel;
-    DevBuf<int> d_flags;
-    int any = 0;
-    const int32_t *hs[5] = {kd->flag, kd->child, kd->leaf_off, kd->leaf_cnt, kd->leaf_surfs};
-    const size_t cnt[5] = {(size_t)kd->n_nodes, (size_t)kd->n_nodes, (size_t)kd->n_nodes, (size_t)kd->n_nodes, (size_t)kd->n_leaf_surfs};
-    for (int i = 0; i < 5; ++i) TRC_TRY(dev_upload(d_i32[i], hs[i], cnt[i], "memcpy failed"));
-    TRC_TRY(dev_upload(d_split, kd->split, (size_t)kd->n_nodes, "memcpy failed"));
-    TRC_TRY(d_flags.alloc(2));
-    (void)hipMemset(d_flags.get(), 0, 8);
-    const size_t nn = (size_t)std::max<int64_t>(n, 1);
-    TRC_TRY(d_rel.alloc((size_t)n_surf * nn));
-    (void)hipMemset(d_rel.get(), 0, (size_t)n_surf * nn);
-    for (int i = 0; i < kd->n_always; ++i) (void)hipMemset(d_rel.get() + (size_t)kd->always_relevant[i] * nn, 1, nn);        // :236
-    if (n > 0) {
-        const double *src[6] = {rays->x, rays->y, rays->z, rays->dx, rays->dy, rays->dz};
-        for (int i = 0; i < 6; ++i) TRC_TRY(dev_upload(d_r[i], src[i], (size_t)n, "memcpy failed"));
-        KdTravParams P;
-        P.flag = d_i32[0].get(); P.child = d_i32[1].get(); P.leaf_off = d_i32[2].get(); P.leaf_cnt = d_i32[3].get(); P.leaf_surfs = d_i32[4].get();
-        P.split = d_split.get();
-        for (int i = 0; i < 3; ++i) { P.lo[i] = kd->bounds[i]; P.hi[i] = kd->bounds[3 + i]; }
-        P.x = d_r[0].get(); P.y = d_r[1].get(); P.z = d_r[2].get(); P.dx = d_r[3].get(); P.dy = d_r[4].get(); P.dz = d_r[5].get();
-        P.n = n; P.rel = d_rel.get(); P.flags = d_flags.get();
-        hipLaunchKernelGGL(k_kd_traversal, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, P);
-        hipError_t se = hipStreamSynchronize(ctx->stream);
-        if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_kd_traversal failed: %s", hipGetErrorString(se));
-        int fl[2] = {0, 0};
-        TRC_TRY(dev_download(fl, d_flags.get(), 2));
-        if (fl[1]) return trc_fail(TRC_ERR_CAPACITY, "a ray had more than %d pending nodes: the tree is deeper than the traversal's stack", KD_TRAV_STACK);
-        any = fl[0];
-        TRC_TRY(dev_download(relevancy, d_rel.get(), (size_t)n_surf * (size_t)n));
-    }
-    // `if inters.any() or self.always_relevant.any()` (:238): any() of the array of surface indices -- a non-zero index
-    for (int i = 0; i < kd->n_always; ++i) if (kd->always_relevant[i] != 0) any = 1;
-    if (any_inter) *any_inter = any;
-    return TRC_OK;
-}
-
-// ================================================================================================
-// C-ABI: per-surface protocol
-// ================================================================================================
-// one surface on the device: its record, its optics parameters (unless d_opt is NULL) and its extra values
-static int upload_record(const trc_surface_desc *surf, int32_t n_extra, const double *extra, DevBuf<double> &d_rec, DevBuf<double> *d_opt,
-                         DevBuf<double> &d_extra) {
-    TRC_TRY(validate_surface(*surf, 0, n_extra));
-    int stride = TRC_REC_HDR + 16;
-    std::vector<double> rec(stride);
-    trc_pack_record(*surf, rec.data(), stride);
-    TRC_TRY(dev_upload(d_rec, rec.data(), (size_t)stride));
-    if (d_opt) TRC_TRY(dev_upload(*d_opt, surf->opt, 8));
-    TRC_TRY(d_extra.alloc((size_t)(n_extra > 0 ? n_extra : 1)));
-    if (n_extra > 0 && extra) HIP_TRY(hipMemcpy(d_extra.get(), extra, (size_t)n_extra * sizeof(double), hipMemcpyHostToDevice));
-    return TRC_OK;
-}
-
-extern "C" int trc_gm_find_intersections(trc_ctx *ctx, const trc_surface_desc *surf, int32_t n_extra, const double *extra,
-                                         const trc_rays *rays, double *t_out, double *hx, double *hy, double *hz) {
-    if (!ctx || !surf || !rays || !t_out) return trc_fail(TRC_ERR_INVALID, "trc_gm_find_intersections: bad arguments");
-    if (rays->on_device) return trc_fail(TRC_ERR_INVALID, "host bundle expected");
-    const int64_t n = rays->n;
-    TRC_TRY(check_rays(rays, n, "trc_gm_find_intersections"));
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (n == 0) return TRC_OK;
-    DevBuf<double> d_rec, d_extra, d_t, d_h[3];
-    DevRays dr;
-    TRC_TRY(upload_record(surf, n_extra, extra, d_rec, nullptr, d_extra));
-    TRC_TRY(stage_rays(rays, n, false, &dr));
-    TRC_TRY(d_t.alloc((size_t)n));
-    const bool want_h = hx && hy && hz;
-    if (want_h) for (auto &col : d_h) TRC_TRY(col.alloc((size_t)n));
-    hipLaunchKernelGGL(k_gm_intersect, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_rec.get(), d_extra.get(),
-                       (long long)n, dr.x, dr.y, dr.z, dr.dx, dr.dy, dr.dz, d_t.get(), d_h[0].get(), d_h[1].get(), d_h[2].get());
-    hipError_t se = hipStreamSynchronize(ctx->stream);
-    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_gm_intersect failed: %s", hipGetErrorString(se));
-    TRC_TRY(dev_download(t_out, d_t.get(), (size_t)n));
-    if (want_h) {
-        double *dst[3] = {hx, hy, hz};
-        for (int i = 0; i < 3; ++i) TRC_TRY(dev_download(dst[i], d_h[i].get(), (size_t)n));
-    }
-    return TRC_OK;
-}
-
-extern "C" int trc_gm_get_normals(trc_ctx *ctx, const trc_surface_desc *surf, int64_t n, const double *hx, const double *hy,
-                                  const double *hz, const double *dx, const double *dy, const double *dz, double *nx,
-                                  double *ny, double *nz) {
-    if (!ctx || !surf || n < 0) return trc_fail(TRC_ERR_INVALID, "trc_gm_get_normals: bad arguments");
-    if (n == 0) return TRC_OK;
-    if (!hx || !hy || !hz || !dx || !dy || !dz || !nx || !ny || !nz) return trc_fail(TRC_ERR_INVALID, "trc_gm_get_normals: NULL array");
-    HIP_TRY(hipSetDevice(ctx->device));
-    DevBuf<double> d_rec, d_extra, d[9];
-    const double *src[6] = {hx, hy, hz, dx, dy, dz};
-    trc_surface_desc tmp = *surf;
-    tmp.optics_kind = TRC_OPT_TRANSPARENT;   // normals do not depend on the optics
-    if (tmp.gm_kind == TRC_GM_RECT_PERFORATED) { tmp.gm_kind = TRC_GM_RECT; }
-    TRC_TRY(upload_record(&tmp, 0, nullptr, d_rec, nullptr, d_extra));
-    for (auto &col : d) TRC_TRY(col.alloc((size_t)n));
-    for (int i = 0; i < 6; ++i)
-        if (hipMemcpy(d[i].get(), src[i], (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
-    hipLaunchKernelGGL(k_gm_normals, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_rec.get(), (long long)n, d[0].get(),
-                       d[1].get(), d[2].get(), d[3].get(), d[4].get(), d[5].get(), d[6].get(), d[7].get(), d[8].get());
-    hipError_t se = hipStreamSynchronize(ctx->stream);
-    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_gm_normals failed: %s", hipGetErrorString(se));
-    double *dst[3] = {nx, ny, nz};
-    for (int i = 0; i < 3; ++i) TRC_TRY(dev_download(dst[i], d[6 + i].get(), (size_t)n));
-    return TRC_OK;
-}
-
-__global__ __launch_bounds__(256) void k_fresnel_attenuating(long long n, double n1, const double *m_re, const double *m_im,
-                                                             const double *th, double *rp, double *rs, double *t2) {
-    long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) trc_fresnel_attenuating(th[i], n1, m_re[i], m_im[i], &rp[i], &rs[i], &t2[i]);
-}
-
-extern "C" int trc_optics_fresnel_attenuating(trc_ctx *ctx, int64_t n, double n1, const double *m_re, const double *m_im,
-                                              const double *theta1, double *r_p, double *r_s, double *theta2) {
-    if (!ctx || n < 0 || (n > 0 && (!m_re || !m_im || !theta1 || !r_p || !r_s || !theta2)))
-        return trc_fail(TRC_ERR_INVALID, "trc_optics_fresnel_attenuating: bad arguments");
-    if (n == 0) return TRC_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    DevBuf<double> d[6];
-    const double *src[3] = {m_re, m_im, theta1};
-    double *dst[3] = {r_p, r_s, theta2};
-    for (auto &col : d) TRC_TRY(col.alloc((size_t)n));
-    for (int i = 0; i < 3; ++i)
-        if (hipMemcpy(d[i].get(), src[i], (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
-    hipLaunchKernelGGL(k_fresnel_attenuating, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (long long)n, n1,
-                       d[0].get(), d[1].get(), d[2].get(), d[3].get(), d[4].get(), d[5].get());
-    hipError_t se = hipStreamSynchronize(ctx->stream);
-    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_fresnel_attenuating failed: %s", hipGetErrorString(se));
-    for (int i = 0; i < 3; ++i) TRC_TRY(dev_download(dst[i], d[3 + i].get(), (size_t)n));
-    return TRC_OK;
-}
-
-extern "C" int trc_optics_apply(trc_ctx *ctx, const trc_surface_desc *surf, int32_t n_extra, const double *extra,
-                                const trc_rays *in, const double *hx, const double *hy, const double *hz, const double *nx,
-                                const double *ny, const double *nz, uint64_t seed, int32_t bounce, trc_rays *out) {
-    if (!ctx || !surf || !in || !out) return trc_fail(TRC_ERR_INVALID, "trc_optics_apply: bad arguments");
-    if (in->on_device || out->on_device) return trc_fail(TRC_ERR_INVALID, "host bundles expected");
-    const int64_t n = in->n;
-    if (out->n < 2 * n) return trc_fail(TRC_ERR_CAPACITY, "output bundle must hold 2n rays");
-    if (n == 0) { out->n = 0; return TRC_OK; }
-    if (!in->dx || !in->dy || !in->dz || !in->e || !hx || !hy || !hz || !nx || !ny || !nz)
-        return trc_fail(TRC_ERR_INVALID, "trc_optics_apply: directions, energies, hit points and normals are required");
-    if (!out->x || !out->y || !out->z || !out->dx || !out->dy || !out->dz || !out->e || !out->parent)
-        return trc_fail(TRC_ERR_INVALID, "trc_optics_apply: output needs x..e and parent");
-    HIP_TRY(hipSetDevice(ctx->device));
-    DevBuf<double> d_rec, d_opt, d_extra;
-    DevBuf<double> d_in[9];      // dx dy dz e ref wl nx ny nz
-    DevBuf<uint64_t> d_rid;
-    DevBuf<double> d_path;
-    DevBuf<double> d_out[5];
-    DevBuf<int32_t> d_blk;
-    DevBuf<double> d_shift;
-    // complex indices, material rows, spectra
-    const int W = (in->spectra && in->spec_wl) ? in->n_spec : 0;
-    const int n_mat = in->mat ? (int)in->n_mat : 0;
-    if (W < 0 || W > 4096 || n_mat < 0 || n_mat > 64) return trc_fail(TRC_ERR_INVALID, "trc_optics_apply: n_spec or n_mat out of range");
-    if (surf->optics_kind == TRC_OPT_LAMBERTIAN_POLYCHROMATIC && (W < 2 || !out->spectra))
-        return trc_fail(TRC_ERR_INVALID, "polychromatic optics: the bundles need spectra (trc_rays.spectra, spec_wl)");
-    if (surf->optics_kind == TRC_OPT_REFRACTIVE_MATERIAL && (!in->wavelength || n_mat <= std::max((int)surf->opt[4], (int)surf->opt[5]) || !out->ref_index_im))
-        return trc_fail(TRC_ERR_INVALID, "refraction between tabulated materials: the bundle needs wavelengths and the materials' indices at them (trc_rays.mat), the output ref_index_im");
-    if (W > 0 && out->spectra && out->n_spec != W) return trc_fail(TRC_ERR_INVALID, "trc_optics_apply: the output's n_spec differs from the input's");
-    const int64_t out_cap = out->n;
-    DevBuf<double> d_im, d_mat, d_swl, d_spec, d_oim, d_ospec;
-    TRC_TRY(upload_record(surf, n_extra, extra, d_rec, &d_opt, d_extra));
-    if (in->ref_index_im) TRC_TRY(dev_upload(d_im, in->ref_index_im, (size_t)n, "memcpy failed"));
-    struct { const double *src; int rows; DevBuf<double> &dst; } blk2[3] = {{in->mat, 2 * n_mat, d_mat}, {in->spec_wl, W, d_swl}, {in->spectra, W, d_spec}};
-    for (auto &b : blk2) {
-        if (b.rows <= 0) continue;
-        TRC_TRY(b.dst.alloc((size_t)n * b.rows));
-        if (hipMemcpy2D(b.dst.get(), (size_t)n * 8, b.src, (size_t)in->n * 8, (size_t)n * 8, (size_t)b.rows, hipMemcpyHostToDevice) != hipSuccess)
-            return trc_fail(TRC_ERR_DEVICE, "memcpy failed");
-    }
-    if (out->ref_index_im) TRC_TRY(d_oim.alloc((size_t)(2 * n)));
-    if (W > 0 && out->spectra) TRC_TRY(d_ospec.alloc((size_t)(2 * n) * W));
-    const double *src[9] = {in->dx, in->dy, in->dz, in->e, in->ref_index, in->wavelength, nx, ny, nz};
-    for (int i = 0; i < 9; ++i)
-        if (src[i]) TRC_TRY(dev_upload(d_in[i], src[i], (size_t)n, "memcpy failed"));
-    if (in->x && in->y && in->z) {      // path lengths for the attenuating optics (Absorbant.attenuate, :874-877)
-        std::vector<double> path((size_t)n);
-        for (int64_t i = 0; i < n; ++i) {
-            double ax = hx[i] - in->x[i], ay = hy[i] - in->y[i], az = hz[i] - in->z[i];
-            path[(size_t)i] = std::sqrt(ax * ax + ay * ay + az * az);
-        }
-        TRC_TRY(dev_upload(d_path, path.data(), (size_t)n, "memcpy failed"));
-    }
-    if (in->rid) TRC_TRY(dev_upload(d_rid, in->rid, (size_t)n, "memcpy failed"));
-    for (auto &col : d_out) TRC_TRY(col.alloc((size_t)(2 * n)));
-    TRC_TRY(d_blk.alloc((size_t)(2 * n)));
-    TRC_TRY(d_shift.alloc((size_t)(2 * n)));
-    OpticsParams P;
-    memset(&P, 0, sizeof(P));
-    P.rec = d_rec.get(); P.opt = d_opt.get(); P.extra = d_extra.get(); P.n = n;
-    P.dx = d_in[0].get(); P.dy = d_in[1].get(); P.dz = d_in[2].get(); P.e = d_in[3].get(); P.ref = d_in[4].get(); P.wl = d_in[5].get();
-    P.rid = d_rid.get(); P.ray_offset = 0;
-    P.nx = d_in[6].get(); P.ny = d_in[7].get(); P.nz = d_in[8].get(); P.path = d_path.get();
-    P.seed = seed; P.event = bounce;
-    P.odx = d_out[0].get(); P.ody = d_out[1].get(); P.odz = d_out[2].get(); P.oe = d_out[3].get(); P.oref = d_out[4].get();
-    P.oblk = d_blk.get(); P.oshift = d_shift.get();
-    P.ref_im = d_im.get(); P.mat = d_mat.get(); P.spec_wl = d_swl.get(); P.spec = d_spec.get(); P.n_mat = n_mat; P.W = W;
-    P.o_im = d_oim.get(); P.o_spec = d_ospec.get();
-    hipLaunchKernelGGL(k_optics_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, P);
-    hipError_t se = hipStreamSynchronize(ctx->stream);
-    if (se != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "k_optics_apply failed: %s", hipGetErrorString(se));
-    std::vector<double> h[5];
-    std::vector<int32_t> blk((size_t)(2 * n));
-    for (int i = 0; i < 5; ++i) {
-        h[i].resize((size_t)(2 * n));
-        TRC_TRY(dev_download(h[i].data(), d_out[i].get(), (size_t)(2 * n)));
-    }
-    TRC_TRY(dev_download(blk.data(), d_blk.get(), (size_t)(2 * n)));
-    std::vector<double> h_shift((size_t)(2 * n));
-    TRC_TRY(dev_download(h_shift.data(), d_shift.get(), (size_t)(2 * n)));
-    std::vector<double> h_im, h_spec;
-    if (d_oim) {
-        h_im.resize((size_t)(2 * n));
-        TRC_TRY(dev_download(h_im.data(), d_oim.get(), (size_t)(2 * n)));
-    }
-    if (d_ospec) {
-        h_spec.resize((size_t)(2 * n) * W);
-        TRC_TRY(dev_download(h_spec.data(), d_ospec.get(), h_spec.size()));
-    }
-    // reflected block first, then refracted block, each in selector order (optics_callables.py:852-857)
-    int64_t m = 0;
-    for (int b = 0; b < 2; ++b)
-        for (int64_t slot = 0; slot < 2 * n; ++slot) {
-            if (blk[(size_t)slot] != b) continue;
-            int64_t i = slot < n ? slot : slot - n;
-            const double sh = h_shift[(size_t)slot];        // (0 but for a periodic boundary: the ray goes on one period along the normal)
-            out->x[m] = hx[i] + sh * nx[i]; out->y[m] = hy[i] + sh * ny[i]; out->z[m] = hz[i] + sh * nz[i];
-            out->dx[m] = h[0][(size_t)slot]; out->dy[m] = h[1][(size_t)slot]; out->dz[m] = h[2][(size_t)slot];
-            out->e[m] = h[3][(size_t)slot];
-            if (out->ref_index) out->ref_index[m] = h[4][(size_t)slot];
-            if (out->wavelength) out->wavelength[m] = in->wavelength ? in->wavelength[i] : 0.0;
-            if (out->ref_index_im) out->ref_index_im[m] = h_im[(size_t)slot];
-            if (d_ospec)
-                for (int w = 0; w < W; ++w) {
-                    out->spectra[(size_t)w * out_cap + m] = h_spec[(size_t)w * 2 * n + slot];
-                    if (out->spec_wl) out->spec_wl[(size_t)w * out_cap + m] = in->spec_wl[(size_t)w * in->n + i];
-                }
-            out->parent[m] = i;
-            ++m;
-        }
-    out->n = m;
     return TRC_OK;
 }
