@@ -144,6 +144,15 @@ $(CLEARCHECK): $(CLEARCHECK_SRC) $(HDR)
 $(CLEARCHECK_EXE): $(CLEARCHECK_SRC) $(HDR)
 	$(CXX) -O1 -g -std=c++17 $(FPFLAGS) $(SPLIT_SAN) -DCLEAR_CHECK_MAIN -o $@ $(CLEARCHECK_SRC)
 
+# whether the shading kernels finish the next segment of the rays inside their clear cones (trc_stream_form_ahead: trc_forms.h), on the
+# fact blocks of the host check: a library for tests/test_finish_ahead_host.py
+AHEADCHECK := $(ROOT)tests/aheadcheck/libtrc_ahead_check.so
+AHEADCHECK_SRC := $(ROOT)tests/aheadcheck/ahead_check.cpp
+aheadcheck: $(AHEADCHECK)
+
+$(AHEADCHECK): $(AHEADCHECK_SRC) $(HOSTCHECK_SRC) $(HDR)
+	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(AHEADCHECK_SRC)
+
 # the room of a streaming call whose optics split rays (trc_split_room_need, trc_split_grow: trc_bounds.h) on a grid of inputs: a
 # program of its own, built with the sanitizers and run by tests/test_split_cases_host.py
 SPLITCHECK_EXE := $(ROOT)tests/splitcheck/split_check
@@ -222,4 +231,4 @@ asm-shade: $(CSRC)/trc_shade.hip $(HDR)
 clean:
 	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK) $(HHCHECK) $(THERMCHECK) $(THERMCHECK_EXE) $(SOURCECHECK_LIB)
 
-.PHONY: all hostcheck thermalcheck umaskcheck umaskcheck-exe clearcheck splitcheck polycheck poolcheck poolcheck-tsan scenecheck sourcecheck sourcecheck-tsan asm asm-shade clean
+.PHONY: all hostcheck thermalcheck umaskcheck umaskcheck-exe clearcheck aheadcheck splitcheck polycheck poolcheck poolcheck-tsan scenecheck sourcecheck sourcecheck-tsan asm asm-shade clean

@@ -457,7 +457,9 @@ enum StreamCounter {
     CW_TERM_HITS = 12,    // ... and their real count
     CW_CLS_HITS = 13,     // + class: hits shaded per class (TRC_CLS_COUNT words)
     CW_STATS = 16,        // first of the seven words of SW_STATS
-    CW_CLS_LIST = 24      // + class: entries of the class lists of k_s_partition (TRC_CLS_COUNT words)
+    CW_AHEAD = 23,        // continued rays whose next segment k_s_shade_c finished itself (StreamParams::ahead): they are not in CW_ALIVE
+    CW_CLS_LIST = 24,     // + class: entries of the class lists of k_s_partition (TRC_CLS_COUNT words)
+    CW_AHEAD_HITS = 27    // ... and those of them that hit (the others left the scene): counted in CW_HITS and CW_TERM_HITS too
 };
 enum StreamOverflow : unsigned long long {
     CW_OVF_RETRY = 1,     // the candidate queue was too small: nothing of the bounce is committed, the host doubles it and runs the bounce again
@@ -556,6 +558,9 @@ struct StreamParams {
     // the clear cones of the scene (trc_clear_tile, trc_core.h): read by k_s_bounce for the continued rays on the LDS-sized grid alone,
     // null for a scene without them and with TRC_STREAM_CLEAR=0.  Behind everything else, for the reason given at CarryIn.
     const float *clear_tab;
+    // k_s_shade_c<MIRROR, flat, LDS> finishes the next segment of a continued ray inside its clear cone itself (trc_stream_form_ahead,
+    // trc_forms.h): only with split_terminal == 2 and clear_tab.  Behind everything else, for the same reason.
+    int ahead;
 };
 
 // The kernel's argument block read again where it stands in the kernel-argument segment.  What a kernel reads from its by-value

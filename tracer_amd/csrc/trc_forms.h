@@ -171,6 +171,7 @@ struct StreamKnobs {
     bool umask;             // TRC_STREAM_UMASK=0: k_s_cull on the Cartesian mask for every source (the form that packs the cell)
     int slots;              // TRC_STREAM_SLOTS: batches in flight, 1 .. STREAM_MAX_SLOTS (default 2)
     bool clear = true;      // TRC_STREAM_CLEAR=0: k_s_bounce gets no table of clear cones, every continued ray walks the grid
+    bool ahead = true;      // TRC_STREAM_AHEAD=0: k_s_shade_c finishes no ray's next segment, every continued ray goes to k_s_bounce
 };
 
 // What the decisions read of a scene.  Two parts: the sizes, which cost nothing to gather, and what only a pass over the surfaces
@@ -194,6 +195,8 @@ struct trc_scene_facts {
     bool simple;                                // ... and every optics kind one of TRC_OPT_SIMPLE_MASK
     unsigned cls_moving, cls_all;               // bit c: class c is present among the surfaces that do not end every ray / among all
     bool any_term;                              // some surface ends every ray
+    // (not part of the pass) the search tables hold clear cones (trc_clear_build); false wherever nobody says so
+    bool clear_cones;
 };
 // what a call brings
 struct trc_call_facts {
@@ -229,6 +232,7 @@ static inline void trc_scene_facts_fill(const trc_surface_desc *surfs, int n_sur
     s->brute_list = (int)A.brute_leaf.size();
     s->n_unbounded = (int)A.unbounded.size();
     s->big_occ_words = (int)A.big_occ.size();
+    s->clear_cones = A.clear_cones > 0;
     s->walked = walk;
     if (!walk) return;
     s->all_flat = s->simple = true;
@@ -438,6 +442,7 @@ struct trc_stream_forms {
     // what the choice sets in StreamParams
     int search, lds_recs, lds_tally, lds_tables, lds_extra, lds_fm_bins, bg_occ_words, shade_term_cls, split_terminal;
     int poly_cells;              // CarryIn.poly_cells: the polychromatic walls whose lambda cells k_s_shade_p stages (0 for every other call)
+    bool ahead;                  // StreamParams.ahead: k_s_shade_c finishes the next segment of the rays inside their clear cones (trc_stream_form_ahead)
 };
 
 static inline trc_lds_parts trc_fresh_parts(const trc_facts &f, bool buie, bool lds, int queue_waves) {
@@ -628,6 +633,25 @@ static inline void trc_stream_form_absorb(trc_stream_forms &F, const trc_facts &
     }
 }
 
+// The shading instances that can finish a continued ray's next segment themselves (k_s_shade_c's AHEAD, trc_shade.hip): the mirror
+// class with flat normals and its tables in LDS, without a spectrum to draw and without flux-map charts
+static inline bool trc_shade_finishes_ahead(const trc_kernel_id &id) {
+    return id.family == TRC_K_SHADE_C && id.a[0] == TRC_CLS_MIRROR && id.a[1] == 1 && id.a[2] == 1 && id.a[3] == 0 && id.a[4] == 0;
+}
+
+// A mirror's ray inside the clear cone of the tile it leaves does not walk the grid in k_s_bounce<1, .., FRESH = false>: that kernel
+// tests the surfaces set apart for it and, with split_terminal == 2, finishes a hit on one that ends every ray in place.  The
+// shading kernel that reflects the ray does the same while it has the ray in registers, and the ray's record, its energy and its
+// entry of the active list are never written (k_s_shade_c, AHEAD).  On for a call when the next bounce's search is that kernel with
+// the clear cones and finishes terminal hits itself, no surface is without a box (those k_s_bounce tests for every ray), and an
+// instance that knows the path shades; TRC_STREAM_AHEAD=0 leaves every continued ray to k_s_bounce.
+static inline void trc_stream_form_ahead(trc_stream_forms &F, const trc_facts &f) {
+    F.ahead = false;
+    if (!(F.use_fused && F.gridm == 1 && F.bounce.id.family == TRC_K_BOUNCE && F.bounce.id.a[0] == 1 && F.bounce.id.a[2] == 0)) return;
+    if (F.split_terminal != 2 || !f.scene.clear_cones || !f.knobs.clear || f.scene.n_unbounded != 0 || !f.knobs.ahead) return;
+    for (int k = 0; k < F.n_shk; ++k) F.ahead = F.ahead || trc_shade_finishes_ahead(F.shk[k].id);
+}
+
 // Chooses the kernel of every stage of a streaming call (f.scene walked, f.fp as stream_fp_prepare left it, f.call.carry with the
 // calls on a scene whose optics split rays).  false: no shading kernel for this call (trc_stream_form_shade).
 static inline bool trc_stream_decide(const trc_facts &f, const StreamPlan &plan, trc_stream_forms *out) {
@@ -648,6 +672,7 @@ static inline bool trc_stream_decide(const trc_facts &f, const StreamPlan &plan,
     trc_stream_form_fresh(F, f);
     trc_stream_form_bounce(F, f, plan);
     trc_stream_form_absorb(F, f);
+    trc_stream_form_ahead(F, f);
     return true;
 }
 

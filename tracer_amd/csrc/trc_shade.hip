@@ -76,6 +76,12 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
     WaveChunk hc = chunk_init(S.chunk_hitbuf);
     if (P.capture && wave_g < SHADE_MAX_WAVES) hit_chunk_resume(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
     unsigned n_hit = 0, n_alive = 0;
+    // AHEAD: the instance can finish the next segment of a continued ray itself (S.ahead, set by trc_stream_form_ahead: the next
+    // bounce is k_s_bounce<1, .., FRESH = false> with split_terminal == 2 and the scene's clear cones).  A mirror's ray inside the
+    // clear cone of the tile it leaves meets no surface the grid lists, so k_s_bounce would only test the surfaces set apart and
+    // finish a hit on one that ends every ray in place: neither needs a ray record in memory, and the ray is in registers here.
+    constexpr bool AHEAD = CLS == TRC_CLS_MIRROR && FLATN && LDS && !SPEC && !CHART;
+    unsigned n_ahead = 0, n_ahead_hit = 0;
     const int bounce0 = S.bounce_no;          // every ray of a launch is at the same bounce
     const bool aux_in = !P.src || bounce0 > 0;     // fresh rays of a source carry (energy, 1, 0): nothing was written for them
     const long long stride = (long long)gridDim.x * blockDim.x;
@@ -85,6 +91,8 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
         SRayGeo g;
         g.px = g.py = g.pz = g.dx = g.dy = 0.0; g.dz = 1.0; g.head = SQ_INVALID; g.idx = 0u; g.tail = 0ull;
         bool have = false;
+        int as = -1;                         // (AHEAD) the surface this lane's ray hit on the segment finished here, with its energy
+        double ae = 0.0;
         if (i < nh) { slot = S.hl_slot[i]; hs = S.hl_surf[i]; t = S.hl_t[i]; }
         bool mine = false;
         int s = 0, fl = 0;
@@ -147,6 +155,47 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
                         }
                     }
                 } else {
+                    bool ahead = false;             // (AHEAD) the ray's next segment is finished here: it does not go to k_s_bounce
+                    if constexpr (AHEAD) {
+                        // What k_s_bounce<1, .., FRESH = false> (trc_stream.inc) does for a ray that does not walk, in its words and
+                        // on the same values: the float32 ray, the root box, the clear cone of the tile left, then the surfaces set
+                        // apart in ascending order -- box, oriented box, exact test, nearest with the lowest index on equal t.
+                        // Whoever changes one of the two changes the other.
+                        if (S.ahead && S.clear_tab && leaves_flat(rec, hx, hy, hz, ox, oy, oz)) {
+                            trc_ray32 r;
+                            double t0 = 0.0;
+                            bool clear = trc_ray32_prepare(sc.a_slo, sc.a_shi, sc.a_cen, hx, hy, hz, ox, oy, oz, &r, &t0) && t0 == 0.0;
+                            float tmin = 1.0f, tmax = 0.0f;
+                            if (clear && trc_kd32_root(sc.a_groot, r, &tmin, &tmax)) {
+                                // (the oriented box of the surface hit: a read from global memory per lane, the table stays in L2)
+                                const int tile = trc_clear_tile(sc.a_obb + (size_t)TRC_OBB_STRIDE * s, TRC_CLEAR_T, r.ox, r.oy, r.oz);
+                                const float4 cone = ((const float4 *)S.clear_tab)[(size_t)s * (TRC_CLEAR_T * TRC_CLEAR_T) + tile];
+                                clear = trc_clear_inside(cone.x, cone.y, cone.z, cone.w, r.dx, r.dy, r.dz);
+                            }
+                            if (clear) {
+                                double tb = TRC_INF;
+                                int sb = 0x7FFFFFFF;
+                                for (int k = 0; k < sc.a_g_napart; ++k) {        // (uniform indices: boxes and records of the same surfaces for every lane)
+                                    const int sidx = sc.a_gapart[k];
+                                    const float *b = sc.a_sbox + 6 * (size_t)sidx;
+                                    if ((b[3] == TRC_INF && b[0] == -TRC_INF) || sidx == s) continue;
+                                    if (!(trc_box_hit32(b, r) && trc_obb_hit32(sc.a_obb + (size_t)TRC_OBB_STRIDE * sidx, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz))) continue;
+                                    const double *rec2 = L.recs + (size_t)sidx * sc.stride;
+                                    const double t2 = trc_intersect_flat(trc_rec_gm_kind(rec2), rec2, sc.extra, hx, hy, hz, ox, oy, oz);
+                                    if (t2 > 0.0 && t2 < TRC_INF && (t2 < tb || (t2 == tb && sidx < sb))) { tb = t2; sb = sidx; }
+                                }
+                                if (sb == 0x7FFFFFFF) ahead = true;                     // nothing is hit: the ray leaves the scene
+                                else if (L.sflags[sb] & TRC_SURF_TERMINAL) {            // ... or ends on a surface that ends every ray
+                                    ahead = true;
+                                    as = sb; ae = e_out;
+                                    n_ahead_hit += 1;
+                                    record_hit<LDS, CHART>(L, l_tally, sb, e_out, e_out, hx + tb * ox, hy + tb * oy, hz + tb * oz, ox, oy, oz, P.capture != 0, s, &hc, l_fm, false, true);
+                                }
+                            }
+                            if (ahead) n_ahead += 1;
+                        }
+                    }
+                    if (!ahead) {
                     alive = true;
                     SRayGeo go;
                     go.px = hx; go.py = hy; go.pz = hz; go.dx = ox; go.dy = oy; go.dz = oz;
@@ -158,6 +207,7 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
                     W.geo[slot] = go;
                     if (aux_in) W.aux[slot].e = e_out;        // (index and wavelength stay as they are: no optics of these classes changes them)
                     else { SRayAux ao; ao.e = e_out; ao.ref = SPEC ? ref0 : 1.0; ao.wl = SPEC ? wl : 0.0; ao.pad = 0.0; W.aux[slot] = ao; }
+                    }
                 }
             }
         }
@@ -182,13 +232,48 @@ __global__ __launch_bounds__(SHC_THREADS) void k_s_shade_c(StreamParams S) {
             }
             if (ts >= 0) { atomicAdd(&tl[ts], tea); atomicAdd(&tl[Sn + ts], tei); atomicAdd(&tl[2 * Sn + ts], 1.0); }
         }
-        if (P.capture) chunk_rebroadcast(hc, __ffsll((long long)my_lanes) - 1);   // hc was advanced by the lanes with a hit only
+        // hc was advanced by the lanes with a hit only -- and once more by those whose ray hit on the segment finished here (AHEAD):
+        // theirs is the newest state
+        unsigned long long hc_lanes = my_lanes;
+        if constexpr (AHEAD) { const unsigned long long al = __ballot(as >= 0); if (al) hc_lanes = al; }
+        if (P.capture) chunk_rebroadcast(hc, __ffsll((long long)hc_lanes) - 1);
+        if constexpr (AHEAD) {
+            // the hits of the segments finished here: a tally round of their own, the form k_s_bounce has for the hits it finishes
+            // (the lanes on the first lane's surface -- the receiver -- are summed in registers and added once)
+            const unsigned long long tl = __ballot(as >= 0);
+            if (tl) {
+                const int s0 = __shfl(as, __ffsll((long long)tl) - 1, 64);
+                const bool in = as == s0;
+                const double cnt = (double)__popcll(__ballot(in));
+                const double es = wave_sum(in ? ae : 0.0);
+                if (lane_id() == 0) { atomicAdd(&l_tally[s0], es); atomicAdd(&l_tally[Sn + s0], es); atomicAdd(&l_tally[2 * Sn + s0], cnt); }
+                if (as >= 0 && !in) { atomicAdd(&l_tally[as], ae); atomicAdd(&l_tally[Sn + as], ae); atomicAdd(&l_tally[2 * Sn + as], 1.0); }
+            }
+        }
         const unsigned long long q = chunk_append(&W.cnt[CN(CW_ACT_OUT)], ca, alive, S.act_out, W.act_room);
         if (alive) { if ((long long)q < W.act_room) S.act_out[q] = slot; else W.cnt[CN(CW_OVERFLOW)] = CW_OVF_FAIL; n_alive += 1; }
     }
     chunk_close(ca, S.act_out, W.act_room);
     if (P.capture && wave_g < SHADE_MAX_WAVES && lane_id() == 0) hit_chunk_suspend(hc, W.hit_state + 2 * wave_g, S.hit_epoch);
     flush_counts<true>(l_tally + (LDS ? 3 * Sn : 0), n_hit, n_alive, &W.cnt[CN(CW_HITS)], &W.cnt[CN(CW_CLS_HITS + CLS)], &W.cnt[CN(CW_ALIVE)]);
+    if constexpr (AHEAD) {
+        // the rays finished ahead and their hits, through the same two spare words once thread 0 has taken the counts above out of them:
+        // the hits are k_s_bounce's (CW_HITS, CW_TERM_HITS, no class word), the rays are missing from CW_ALIVE
+        if (S.ahead) {          // (the same for every thread of the launch)
+            double *spare = l_tally + 3 * Sn;
+            __syncthreads();
+            if (threadIdx.x == 0) spare[0] = spare[1] = 0.0;
+            __syncthreads();
+            const double a = wave_sum((double)n_ahead), h = wave_sum((double)n_ahead_hit);
+            if (lane_id() == 0 && a > 0.0) { atomicAdd(&spare[0], a); atomicAdd(&spare[1], h); }
+            __syncthreads();
+            if (threadIdx.x == 0 && spare[0] > 0.0) {
+                const unsigned long long hh = (unsigned long long)(spare[1] + 0.5);
+                atomicAdd(&W.cnt[CN(CW_AHEAD)], (unsigned long long)(spare[0] + 0.5));
+                if (hh) { atomicAdd(&W.cnt[CN(CW_AHEAD_HITS)], hh); atomicAdd(&W.cnt[CN(CW_HITS)], hh); atomicAdd(&W.cnt[CN(CW_TERM_HITS)], hh); }
+            }
+        }
+    }
     flush_sums(L.tally, l_tally, LDS ? 3 * Sn : 0, l_fm, S.lds_fm_bins, Sn);
 }
 

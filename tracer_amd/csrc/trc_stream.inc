@@ -1012,6 +1012,8 @@ __global__ __launch_bounds__(SB_THREADS_OF(GRIDM)) void k_s_bounce(StreamParams 
                 walk = trc_kd32_root(A.root, r, &tmin, &tmax);
                 // A continued ray inside the clear cone of the tile it left (trc_clear_build) can meet the box of no surface the grid
                 // lists: it does not walk.  The heliostats' rays to the receiver: all but one in 180 on NSTTF.
+                // (k_s_shade_c's AHEAD, trc_shade.hip, restates this test, the tests of the surfaces set apart above and the terminal
+                // hits finished below for the rays it finishes itself: whoever changes one of the two changes the other)
                 if constexpr (GRIDM == 1 && !FRESH) {
                     if (walk && skip >= 0 && S.clear_tab && t0 == 0.0) {
                         const int tile = trc_clear_tile(obb + (size_t)(LDS ? TRC_OBB_LSTRIDE : TRC_OBB_STRIDE) * skip, TRC_CLEAR_T, r.ox, r.oy, r.oz);
@@ -1975,6 +1977,7 @@ static StreamKnobs stream_knobs() {
     K.slots = (ev = getenv("TRC_STREAM_SLOTS")) ? atoi(ev) : 2;
     if (K.slots < 1 || K.slots > STREAM_MAX_SLOTS) K.slots = 2;
     K.clear = !((ev = getenv("TRC_STREAM_CLEAR")) && !atoi(ev));
+    K.ahead = !((ev = getenv("TRC_STREAM_AHEAD")) && !atoi(ev));
     return K;
 }
 
@@ -2082,12 +2085,15 @@ struct StreamEngine {
 #define STREAM_RATE_BOUNCES 8
     double rate_term[STREAM_RATE_BOUNCES], rate_other[STREAM_RATE_BOUNCES];
     double rate_cls[STREAM_RATE_BOUNCES][TRC_CLS_COUNT];   // hits per ray entering bounce b that each shading class took (< 0: not yet)
+    // rays per ray entering bounce b that its shading left on the active list, measured on the batches whose shading finished the
+    // others' next segment itself (StreamParams.ahead; < 0: not yet): sizes the chunks of that list, and with them the next bounce
+    double rate_left[STREAM_RATE_BOUNCES];
     uint64_t rate_geom_version = 0;      // the pose the rates were measured on
     DevBuf<uint32_t> d_fp_mask, d_fp_coff, d_fp_umask;     // (d_fp_umask: empty where the source's kernels do not use the mask over the uniforms)
     DevBuf<uint32_t> d_fp_clist;
 
     void forget_rates() {      // not measured yet
-        for (int b = 0; b < STREAM_RATE_BOUNCES; ++b) { rate_term[b] = rate_other[b] = -1.0; for (int c = 0; c < TRC_CLS_COUNT; ++c) rate_cls[b][c] = -1.0; }
+        for (int b = 0; b < STREAM_RATE_BOUNCES; ++b) { rate_term[b] = rate_other[b] = rate_left[b] = -1.0; for (int c = 0; c < TRC_CLS_COUNT; ++c) rate_cls[b][c] = -1.0; }
     }
 };
 
@@ -2315,6 +2321,7 @@ static int stream_choose_forms(StreamForms &F, StreamParams &SP0, trc_scene *sc,
     SP0.lds_fm_bins = D.lds_fm_bins; SP0.bg_occ_words = D.bg_occ_words; SP0.shade_term_cls = D.shade_term_cls; SP0.split_terminal = D.split_terminal;
     SP0.carry.poly_cells = D.poly_cells;
     SP0.clear_tab = f.knobs.clear ? sc->search.clear_cones() : nullptr;
+    SP0.ahead = (D.ahead && SP0.clear_tab) ? 1 : 0;
     SP0.hit_epoch = sc->hits.epoch;
     SP0.chunk_hitbuf = sc->hits.chunk_size();
     // 3. and 4. the instances, their grid caps and their LDS
@@ -2512,6 +2519,9 @@ static void plan_bounce(const StreamCall &C, StreamSlot &T) {
         const double most = (double)(C.K.room_set ? (long long)(0.9 * (double)T.W.act_room) : STREAM_ACT_STATIC(T.W.cap) - 64 * (long long)total_waves) /
                             (double)(total_waves ? total_waves : 1ull);
         const double rays_in = T.b == 0 ? (double)T.nb : (double)T.n_in;
+        // the shading finishes most rays' next segment itself: the list is sized for the rays measured to be left, in short chunks --
+        // k_s_bounce walks every entry reserved, used or not
+        const bool few_left = C.SP0.ahead && T.b < STREAM_RATE_BOUNCES && E.rate_left[T.b] >= 0.0;
         long long base = 0;
         for (int k = 0; k < F.D.n_shk; ++k) {
             const unsigned long long waves = (unsigned long long)T.gb_sh[k] * F.shk[k].wpb;
@@ -2520,11 +2530,12 @@ static void plan_bounce(const StreamCall &C, StreamSlot &T) {
                 double ex = act_expected;
                 const int c = F.shk[k].cls;
                 if (c >= 0 && T.b < STREAM_RATE_BOUNCES && E.rate_cls[T.b][c] >= 0.0 && E.rate_cls[T.b][c] * rays_in < ex) ex = E.rate_cls[T.b][c] * rays_in;
+                if (few_left && E.rate_left[T.b] * rays_in < ex) ex = E.rate_left[T.b] * rays_in;
                 if (C.split_rays) ex *= 2.0;        // (two entries per hit)
-                double cc = 1.1 * ex / (double)waves + 128.0;
+                double cc = 1.1 * ex / (double)waves + (few_left ? 48.0 : 128.0);
                 if (cc > most) cc = most;
                 chunk = ((unsigned)cc + 63u) & ~63u;
-                if (chunk < SQ_CHUNK) chunk = SQ_CHUNK;
+                if (chunk < (few_left ? 64u : (unsigned)SQ_CHUNK)) chunk = few_left ? 64u : (unsigned)SQ_CHUNK;
             }
             T.chunk_act_sh[k] = chunk;
             T.act_base_sh[k] = base;
@@ -2790,15 +2801,19 @@ static int advance(StreamCall &C, StreamSlot &T) {
     }
     T.attempt = 0;
     if (C.split_rays) T.slots_used = c[CN(CW_SLOTS)];       // (reserved: the unused tails of the waves' chunks stay unused)
-    C.seg += (double)T.n_in;
+    // The rays whose next segment this bounce's shading finished itself (StreamParams.ahead): a segment each of the bounce they were
+    // finished for, which then has run as far as they are concerned; their hits are in CW_HITS and CW_TERM_HITS, which the rates
+    // below -- what the kernels of THIS bounce found -- leave out.  They are in neither CW_ALIVE nor CW_ACT_OUT.
+    const unsigned long long n_ahead = c[CN(CW_AHEAD)], ahead_hits = c[CN(CW_AHEAD_HITS)];
+    C.seg += (double)T.n_in + (double)n_ahead;
     C.hits += (double)c[CN(CW_HITS)];
     if (T.fresh && T.nb > 0) {       // what the next batches can expect (with a margin; a low guess only costs atomics)
-        const double rate = 1.15 * (double)c[CN(CW_HITS)] / (double)T.nb + 256.0 / (double)T.nb;
+        const double rate = 1.15 * (double)(c[CN(CW_HITS)] - ahead_hits) / (double)T.nb + 256.0 / (double)T.nb;
         if (rate > E.fp_hit_rate || E.fp_hit_rate > 2.0 * rate) E.fp_hit_rate = rate;
     }
     if (T.fused && T.b < STREAM_RATE_BOUNCES && T.n_in > 0) {       // (without the split CN(CW_TERM_HITS) stays 0: every hit is on the one list)
         const double nin = (double)T.n_in, pad = 512.0 / nin;
-        const double rt = 1.15 * (double)c[CN(CW_TERM_HITS)] / nin + pad, ro = 1.15 * (double)(c[CN(CW_HITS)] - c[CN(CW_TERM_HITS)]) / nin + pad;
+        const double rt = 1.15 * (double)(c[CN(CW_TERM_HITS)] - ahead_hits) / nin + pad, ro = 1.15 * (double)(c[CN(CW_HITS)] - c[CN(CW_TERM_HITS)]) / nin + pad;
         if (E.rate_term[T.b] < 0.0 || rt > E.rate_term[T.b] || E.rate_term[T.b] > 2.0 * rt) E.rate_term[T.b] = rt > 1.0 ? 1.0 : rt;
         if (E.rate_other[T.b] < 0.0 || ro > E.rate_other[T.b] || E.rate_other[T.b] > 2.0 * ro) E.rate_other[T.b] = ro > 1.0 ? 1.0 : ro;
     }
@@ -2812,7 +2827,16 @@ static int advance(StreamCall &C, StreamSlot &T) {
                 C.cls_hits[cl] += (double)c[CN(CW_CLS_HITS + cl)];
             }
     }
+    if (C.SP0.ahead && T.b < STREAM_RATE_BOUNCES) {
+        const double rin = T.b == 0 ? (double)T.nb : (double)T.n_in;
+        if (rin > 0.0) {
+            const double r = 1.15 * (double)c[CN(CW_ALIVE)] / rin + 512.0 / rin;
+            double &R = E.rate_left[T.b];
+            if (R < 0.0 || r > R || R > 2.0 * r) R = r;
+        }
+    }
     if (T.b + 1 > C.max_bounces) C.max_bounces = T.b + 1;
+    if (n_ahead && T.b + 2 > C.max_bounces) C.max_bounces = T.b + 2;
     if (c[CN(CW_ALIVE)] == 0 || T.b + 1 >= C.SP0.P.reps) { T.busy = false; return TRC_OK; }
     // next bounce: the rays just shaded are the active list
     T.n_act = c[CN(CW_ACT_OUT)];                                       // its reserved entries (the tail of the last chunks is invalid)
