@@ -31,6 +31,8 @@ FMCHECK := $(ROOT)tests/hostcheck/libtrc_fluxmap_check.so
 FMCHECK_SRC := $(ROOT)tests/hostcheck/fluxmap_check.cpp
 HHCHECK := $(ROOT)tests/hostcheck/libtrc_hithist_check.so
 HHCHECK_SRC := $(ROOT)tests/hostcheck/hithist_check.cpp
+HHXCHECK := $(ROOT)tests/hostcheck/libtrc_hithist_x_check.so
+HHXCHECK_SRC := $(ROOT)tests/hostcheck/hithist_x_check.cpp
 THERMCHECK := $(ROOT)tests/hostcheck/libtrc_thermal_check.so
 THERMCHECK_EXE := $(ROOT)tests/hostcheck/thermal_check
 THERMCHECK_SRC := $(ROOT)tests/hostcheck/thermal_check.cpp
@@ -80,7 +82,7 @@ $(LIB): $(OBJS)
 MATCHECK := $(ROOT)tests/hostcheck/libtrc_material_check.so
 MATCHECK_SRC := $(ROOT)tests/hostcheck/material_check.cpp
 
-hostcheck: $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK) $(HHCHECK) $(THERMCHECK)
+hostcheck: $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK) $(HHCHECK) $(HHXCHECK) $(THERMCHECK)
 
 # the tabulated materials' lookup of the per-ray core, host-compiled for its tests
 $(MATCHECK): $(MATCHECK_SRC) $(HDR)
@@ -119,6 +121,11 @@ $(FMCHECK): $(FMCHECK_SRC) $(HDR)
 # the histogram of captured hits -- its per-hit function, its LDS decision and its pass as a host loop -- host-compiled for their tests
 $(HHCHECK): $(HHCHECK_SRC) $(HDR)
 	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(HHCHECK_SRC)
+
+# the spectral histogram of captured hits -- where its kernel keeps its bins, and its pass as a host loop, slice by slice -- host-compiled
+# for their tests
+$(HHXCHECK): $(HHXCHECK_SRC) $(HDR)
+	$(CXX) -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -o $@ $(HHXCHECK_SRC)
 
 # the footprint map's mask over the uniforms against brute force, host-compiled: a library for its test, and the same as a program
 # (umaskcheck-exe; SAN="-fsanitize=address,undefined" builds it for a sanitizer run)
@@ -229,6 +236,6 @@ asm-shade: $(CSRC)/trc_shade.hip $(HDR)
 		-o $(ROOT)build/trc_shade.s $(CSRC)/trc_shade.hip 2> $(ROOT)build/trc_shade.resources.txt
 
 clean:
-	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK) $(HHCHECK) $(THERMCHECK) $(THERMCHECK_EXE) $(SOURCECHECK_LIB)
+	rm -f $(LIB) $(HOSTCHECK) $(SPECCHECK) $(SUNCHECK) $(FMCHECK) $(MATCHECK) $(LAMPCHECK) $(HHCHECK) $(HHXCHECK) $(THERMCHECK) $(THERMCHECK_EXE) $(SOURCECHECK_LIB)
 
 .PHONY: all hostcheck thermalcheck umaskcheck umaskcheck-exe clearcheck aheadcheck splitcheck polycheck poolcheck poolcheck-tsan scenecheck sourcecheck sourcecheck-tsan asm asm-shade clean

@@ -466,8 +466,29 @@ typedef struct trc_hit_hist_desc {
 } trc_hit_hist_desc;
 int trc_scene_histogram_hits(trc_scene *scene, const trc_hit_hist_desc *desc, double *sum, double *sum_sq, int64_t *count,
                              double *outside);
-/* milliseconds the kernel of the scene's last trc_scene_histogram_hits took on the device, between two events (0: it had no entry
-   to pass over) */
+/* The spectra of the captured hits binned the same way, in one pass (k_hist_hits_x): what numpy computes from the spectral columns
+   trc_scene_get_hits_x would return now -- the reference's PolychromaticAccountant result, oldspectra - new_bundle.get_spectra(), per
+   bin.  All pending hits carry n_samples = trc_scene_hit_spectral_columns / 3 samples.  base: range, chart, bins, edges and proj12 as
+   above; weight TRC_HH_ABSORBED (arrived - left, per sample) or TRC_HH_INCIDENT (arrived).  by_surface != 0: the bin of a hit is its
+   surface less surf_lo -- surf_hi - surf_lo + 1 bins -- and chart, nu, nv, the edges and proj12 are not looked at.
+   sum[n_bins * n_samples] (bin-major: sample k of bin b at b * n_samples + k); count[n_bins] the hits of every bin; outside[n_samples
+   + 1] the weight per sample of the selected hits in no bin, then their number; count, outside and off_grid may be NULL.
+   wl[n_samples], when given: a sample of a hit is added only where the hit's own sample wavelength k equals wl[k] (a bundle may
+   carry another grid per ray), and *off_grid counts the (hit, sample) pairs left out; the result is that of the grid exactly when it
+   is 0.  wl NULL: the wavelength columns are neither read nor checked.  The outputs are overwritten (an empty buffer gives zeros); the
+   hit buffer, the tallies and the scene stay as they are; trc_scene_histogram_hits_ms reports this pass too.  TRC_ERR_INVALID: what
+   trc_scene_histogram_hits refuses, the weight TRC_HH_COUNT, hits without spectral columns, another n_samples than the buffer's, a
+   wl that is not finite.  TRC_ERR_CAPACITY: more than 2^27 sums. */
+typedef struct trc_hit_hist_x_desc {
+    trc_hit_hist_desc base;
+    int32_t n_samples;
+    int32_t by_surface;
+    const double *wl;
+} trc_hit_hist_x_desc;
+int trc_scene_histogram_hits_x(trc_scene *scene, const trc_hit_hist_x_desc *desc, double *sum, int64_t *count, double *outside,
+                               int64_t *off_grid);
+/* milliseconds the kernel of the scene's last trc_scene_histogram_hits or trc_scene_histogram_hits_x took on the device, between two
+   events (0: it had no entry to pass over) */
 int trc_scene_histogram_hits_ms(trc_scene *scene, double *ms);
 /* Surface-to-surface energy transfer of the fast engine: T[from][to] = energy carried by the segments that leave
    surface `from` (row n_surf = the source) and land on surface `to`, (n_surf+1) x n_surf, row-major.  It replaces

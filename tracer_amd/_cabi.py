@@ -116,6 +116,11 @@ class HitHistDesc(C.Structure):
                 ('nu', C.c_int32), ('nv', C.c_int32), ('u_edges', _p_f64), ('v_edges', _p_f64), ('proj12', _p_f64)]
 
 
+class HitHistXDesc(C.Structure):
+    """trc_hit_hist_x_desc (filled by DeviceScene.histogram_spectra and surface_spectra, which keep its arrays alive)"""
+    _fields_ = [('base', HitHistDesc), ('n_samples', C.c_int32), ('by_surface', C.c_int32), ('wl', _p_f64)]
+
+
 class TraceStats(C.Structure):
     _fields_ = [('segments', C.c_int64), ('hits', C.c_int64), ('rays_left', C.c_int64),
                 ('hits_dropped', C.c_int64), ('energy_left', C.c_double), ('kernel_ms', C.c_double),
@@ -154,6 +159,7 @@ SIGNATURES = {
     'trc_scene_eval_materials': (C.c_int, [_vp, C.c_int64, _p_f64, _p_f64]),
     'trc_scene_bin_hits': (C.c_int, [_vp, C.c_int32, _p_i32, _p_i32, _p_f64, _p_i32, _p_f64]),
     'trc_scene_histogram_hits': (C.c_int, [_vp, C.POINTER(HitHistDesc), _p_f64, _p_f64, _p_i64, _p_f64]),
+    'trc_scene_histogram_hits_x': (C.c_int, [_vp, C.POINTER(HitHistXDesc), _p_f64, _p_i64, _p_f64, _p_i64]),
     'trc_scene_histogram_hits_ms': (C.c_int, [_vp, _p_f64]),
     'trc_scene_enable_transfer': (C.c_int, [_vp, C.c_int32]),
     'trc_scene_get_transfer': (C.c_int, [_vp, _p_f64]),

@@ -1677,36 +1677,46 @@ extern "C" int trc_scene_bin_hits(trc_scene *sc, int32_t n_bins, const int32_t *
 
 // The captured hits binned where they lie (k_hist_hits, trc_hithist.hip): edges up, one pass over the reserved entries, planes down.
 #define TRC_HH_MAX_BINS (1ll << 27)      /* bins of a plane: 1 GiB of float64 */
-extern "C" int trc_scene_histogram_hits(trc_scene *sc, const trc_hit_hist_desc *d, double *sum, double *sum_sq, int64_t *count, double *outside) {
-    if (!sc || !d || !sum || !d->u_edges || !d->v_edges || !d->proj12) return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: bad arguments");
-    if (d->chart < 0 || d->chart >= TRC_HH_CHARTS) return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: unknown chart %d", d->chart);
+// what both histograms refuse, `fn` in front of the message; charted: the chart, the bins, their edges and proj12 are used (the spectra
+// by surface use none of them)
+static int hit_hist_check(const char *fn, const trc_scene *sc, const trc_hit_hist_desc *d, bool charted) {
     if (d->weight != TRC_HH_ABSORBED && d->weight != TRC_HH_INCIDENT && d->weight != TRC_HH_COUNT)
-        return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: unknown weight %d", d->weight);
-    if (d->nu < 1 || d->nv < 1) return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: a histogram has at least one bin either way (%d x %d)", d->nu, d->nv);
-    if ((long long)d->nu * d->nv > TRC_HH_MAX_BINS)
-        return trc_fail(TRC_ERR_CAPACITY, "trc_scene_histogram_hits: %d x %d bins (at most %lld)", d->nu, d->nv, (long long)TRC_HH_MAX_BINS);
-    for (int ax = 0; ax < 2; ++ax) {
-        const double *e = ax ? d->v_edges : d->u_edges;
-        const int n = ax ? d->nv : d->nu;
-        for (int k = 0; k <= n; ++k)
-            if (!std::isfinite(e[k]) || (k > 0 && !(e[k] > e[k - 1])))
-                return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: the %s edges must be finite and increase strictly", ax ? "v" : "u");
+        return trc_fail(TRC_ERR_INVALID, "%s: unknown weight %d", fn, d->weight);
+    if (charted) {
+        if (!d->u_edges || !d->v_edges || !d->proj12) return trc_fail(TRC_ERR_INVALID, "%s: bad arguments", fn);
+        if (d->chart < 0 || d->chart >= TRC_HH_CHARTS) return trc_fail(TRC_ERR_INVALID, "%s: unknown chart %d", fn, d->chart);
+        if (d->nu < 1 || d->nv < 1) return trc_fail(TRC_ERR_INVALID, "%s: a histogram has at least one bin either way (%d x %d)", fn, d->nu, d->nv);
+        if ((long long)d->nu * d->nv > TRC_HH_MAX_BINS)
+            return trc_fail(TRC_ERR_CAPACITY, "%s: %d x %d bins (at most %lld)", fn, d->nu, d->nv, (long long)TRC_HH_MAX_BINS);
+        for (int ax = 0; ax < 2; ++ax) {
+            const double *e = ax ? d->v_edges : d->u_edges;
+            const int n = ax ? d->nv : d->nu;
+            for (int k = 0; k <= n; ++k)
+                if (!std::isfinite(e[k]) || (k > 0 && !(e[k] > e[k - 1])))
+                    return trc_fail(TRC_ERR_INVALID, "%s: the %s edges must be finite and increase strictly", fn, ax ? "v" : "u");
+        }
+        for (int k = 0; k < 12; ++k)
+            if (!std::isfinite(d->proj12[k])) return trc_fail(TRC_ERR_INVALID, "%s: proj12 holds a value that is not finite", fn);
     }
-    for (int k = 0; k < 12; ++k)
-        if (!std::isfinite(d->proj12[k])) return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: proj12 holds a value that is not finite");
     if (d->surf_lo < 0 || d->surf_hi >= sc->n_surf || d->surf_lo > d->surf_hi)
-        return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: surfaces %d..%d are not a range of the scene's %d", d->surf_lo, d->surf_hi, sc->n_surf);
-    const bool full = TRC_HH_IS_DIR(d->chart) || d->weight == TRC_HH_INCIDENT;
+        return trc_fail(TRC_ERR_INVALID, "%s: surfaces %d..%d are not a range of the scene's %d", fn, d->surf_lo, d->surf_hi, sc->n_surf);
+    const bool full = (charted && TRC_HH_IS_DIR(d->chart)) || d->weight == TRC_HH_INCIDENT;
     bool captures = false;
     for (int s = d->surf_lo; s <= d->surf_hi; ++s) {
         const int32_t fl = sc->surfaces[s].flags;
         if (!(fl & TRC_SURF_CAPTURE_HITS)) continue;
         captures = true;
         if (full && (fl & TRC_SURF_CAPTURE_LEAN))
-            return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: surface %d is captured lean (TRC_SURF_CAPTURE_LEAN): the direction and the "
-                            "incident energy of its hits were not written", s);
+            return trc_fail(TRC_ERR_INVALID, "%s: surface %d is captured lean (TRC_SURF_CAPTURE_LEAN): the direction and the "
+                            "incident energy of its hits were not written", fn, s);
     }
-    if (!captures) return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: none of the surfaces %d..%d captures its hits", d->surf_lo, d->surf_hi);
+    if (!captures) return trc_fail(TRC_ERR_INVALID, "%s: none of the surfaces %d..%d captures its hits", fn, d->surf_lo, d->surf_hi);
+    return TRC_OK;
+}
+
+extern "C" int trc_scene_histogram_hits(trc_scene *sc, const trc_hit_hist_desc *d, double *sum, double *sum_sq, int64_t *count, double *outside) {
+    if (!sc || !d || !sum) return trc_fail(TRC_ERR_INVALID, "trc_scene_histogram_hits: bad arguments");
+    TRC_TRY(hit_hist_check("trc_scene_histogram_hits", sc, d, true));
 
     trc_ctx *ctx = sc->ctx;
     unsigned long long cursor;
@@ -1754,6 +1764,90 @@ extern "C" int trc_scene_histogram_hits(trc_scene *sc, const trc_hit_hist_desc *
     if (sum_sq) memcpy(sum_sq, back.data() + nb, nb * 8);
     if (count) memcpy(count, back.data() + nb * (sum_sq ? 2 : 1), nb * 8);
     if (outside) { outside[0] = back[nb * np]; outside[1] = back[nb * np + 1]; }
+    return TRC_OK;
+}
+
+// The spectra of the captured hits binned where they lie (k_hist_hits_x): per bin of the chart, or per surface, and per sample.
+extern "C" int trc_scene_histogram_hits_x(trc_scene *sc, const trc_hit_hist_x_desc *dx, double *sum, int64_t *count, double *outside,
+                                          int64_t *off_grid) {
+    static const char *fn = "trc_scene_histogram_hits_x";
+    if (!sc || !dx || !sum) return trc_fail(TRC_ERR_INVALID, "%s: bad arguments", fn);
+    const trc_hit_hist_desc *d = &dx->base;
+    const bool by_surface = dx->by_surface != 0;
+    TRC_TRY(hit_hist_check(fn, sc, d, !by_surface));
+    if (d->weight == TRC_HH_COUNT)
+        return trc_fail(TRC_ERR_INVALID, "%s: the weight is the absorbed or the incident spectrum (the count is the `count` plane)", fn);
+    const int W = dx->n_samples, nu = by_surface ? d->surf_hi - d->surf_lo + 1 : d->nu, nv = by_surface ? 1 : d->nv;
+    if (W < 1) return trc_fail(TRC_ERR_INVALID, "%s: %d samples", fn, W);
+    for (int k = 0; dx->wl && k < W; ++k)
+        if (!std::isfinite(dx->wl[k])) return trc_fail(TRC_ERR_INVALID, "%s: wl holds a value that is not finite", fn);
+    const size_t nb = (size_t)nu * nv, ne = (size_t)nu + nv + 2;
+    if ((long long)nb * W > TRC_HH_MAX_BINS)
+        return trc_fail(TRC_ERR_CAPACITY, "%s: %d x %d bins of %d samples (at most %lld in all)", fn, nu, nv, W, (long long)TRC_HH_MAX_BINS);
+
+    trc_ctx *ctx = sc->ctx;
+    unsigned long long cursor;
+    TRC_TRY(scene_hit_cursor(sc, &cursor));
+    const HitBuffer &hb = sc->hits;
+    const long long n = hb.used(cursor);
+    if (n > 0 && hb.x_cols == 0) return trc_fail(TRC_ERR_INVALID, "%s: the hit buffer holds no spectral columns: its hits are not those of polychromatic rays", fn);
+    if (hb.x_cols != 0 && hb.x_cols != 3 * W)
+        return trc_fail(TRC_ERR_INVALID, "%s: the hit buffer holds %d spectral columns, 3 x %d samples, not 3 x %d", fn, hb.x_cols, hb.x_cols / 3, W);
+    for (size_t k = 0; k < nb * W; ++k) sum[k] = 0.0;
+    for (size_t k = 0; count && k < nb; ++k) count[k] = 0;
+    for (int k = 0; outside && k <= W; ++k) outside[k] = 0.0;
+    if (off_grid) *off_grid = 0;
+    sc->hist_ms = 0.0;
+    if (n == 0) return TRC_OK;
+    // one block: [edges] [sum] [count] [outside: W, and the number] [off grid]
+    const size_t tail = nb * W + (count ? nb : 0) + W + 2, words = ne + tail;
+    DevBuf<double> d_buf;
+    TRC_TRY(d_buf.alloc(words));
+    trc_hit_hist_x_args X;
+    memset(&X, 0, sizeof(X));
+    trc_hit_hist_args &A = X.h;
+    A.n = n;
+    A.planes = count ? TRC_HH_PLANE_COUNT : 0;
+    A.surf = hb.surf.get();
+    A.px = hb.col[2].get(); A.py = hb.col[3].get(); A.pz = hb.col[4].get();
+    A.dx = hb.col[5].get(); A.dy = hb.col[6].get(); A.dz = hb.col[7].get();
+    A.surf_lo = d->surf_lo; A.surf_hi = d->surf_hi; A.chart = by_surface ? 0 : d->chart; A.weight = d->weight; A.nu = nu; A.nv = nv;
+    A.edges = d_buf.get();
+    A.sum = d_buf.get() + ne;
+    A.count = count ? (unsigned long long *)(A.sum + nb * W) : nullptr;
+    A.outside = A.sum + nb * W + (count ? nb : 0);
+    X.off_grid = (unsigned long long *)(A.outside + W + 1);
+    X.x = hb.x.get(); X.cap = hb.cap; X.W = W; X.by_surface = by_surface ? 1 : 0;
+    // the edges up, and in a block of their own the wavelengths the hits are held to
+    DevBuf<double> d_wl;
+    if (dx->wl) TRC_TRY(d_wl.alloc((size_t)W));
+    std::vector<double> edges(ne, 0.0), back(tail);
+    hipError_t e = hipSuccess;
+    if (!by_surface) {
+        for (int k = 0; k < 12; ++k) A.proj[k] = d->proj12[k];
+        std::copy(d->u_edges, d->u_edges + nu + 1, edges.begin());
+        std::copy(d->v_edges, d->v_edges + nv + 1, edges.begin() + nu + 1);
+        e = hipMemcpyAsync(d_buf.get(), edges.data(), ne * 8, hipMemcpyHostToDevice, ctx->stream);
+    }
+    if (dx->wl) {
+        X.wl = d_wl.get();
+        if (e == hipSuccess) e = hipMemcpyAsync(d_wl.get(), dx->wl, (size_t)W * 8, hipMemcpyHostToDevice, ctx->stream);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(A.sum, 0, tail * 8, ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
+    if (e == hipSuccess) e = trc_hit_hist_x_launch(ctx->stream, ctx->n_cu, X);
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(back.data(), A.sum, tail * 8, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t se = hipStreamSynchronize(ctx->stream);      // (always: nothing queued may outlive the buffers it uses)
+    if (e == hipSuccess) e = se;
+    if (e != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) sc->hist_ms = ms;
+    const double *b_out = back.data() + nb * W + (count ? nb : 0);
+    memcpy(sum, back.data(), nb * W * 8);
+    if (count) memcpy(count, back.data() + nb * W, nb * 8);
+    if (outside) memcpy(outside, b_out, (size_t)(W + 1) * 8);
+    if (off_grid) memcpy(off_grid, b_out + W + 1, 8);
     return TRC_OK;
 }
 

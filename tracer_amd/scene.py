@@ -258,6 +258,25 @@ class HitHistogram(object):
         self.sum, self.sum_sq, self.count, self.outside = total, sum_sq, count, outside
 
 
+class SpectralHistogram(object):
+    """What histogram_spectra and surface_spectra return: `sum` (nu, nv, W) -- or (surfaces, W) -- the spectrum of every bin on the W
+    sample wavelengths; `count` the hits of every bin (None where it was not asked for); `outside` (W,) and `outside_n`, the spectrum
+    and the number of the selected hits in no bin; `off_grid`, the (hit, sample) pairs left out because the hit's own wavelength is
+    not that of `wavelengths` (the sums are those of the grid exactly when it is 0); `wavelengths` (W,), or None if none were given."""
+    def __init__(self, wavelengths, total, count, outside, outside_n, off_grid):
+        self.wavelengths, self.sum, self.count = wavelengths, total, count
+        self.outside, self.outside_n, self.off_grid = outside, outside_n, off_grid
+
+    def integrate(self):
+        """the energy of every bin: the trapezoid rule over the wavelengths, as the sources normalise their spectra"""
+        if self.wavelengths is None:
+            raise ValueError("integrate: the histogram was made without wavelengths")
+        return _trapz(self.sum, self.wavelengths, axis=-1)
+
+
+_trapz = getattr(N, 'trapezoid', None) or N.trapz        # (numpy.trapz is numpy.trapezoid since NumPy 2)
+
+
 class DeviceScene(object):
     """trc_scene handle."""
     def __init__(self, compiled, ctx=None):
@@ -531,8 +550,67 @@ class DeviceScene(object):
                                                       _cabi.ptr(cnt, C.POINTER(C.c_int64)), _cabi.ptr(outside)))
         return HitHistogram(total, sq, cnt, outside) if moments else total
 
+    def _spectra(self, base, by_surface, shape, weight, wavelengths, counts):
+        """trc_scene_histogram_hits_x over the bins of `shape` (the caller keeps the arrays `base` points to)"""
+        if isinstance(weight, str):
+            if weight not in _cabi.HH_WEIGHTS:
+                raise ValueError("unknown histogram weight %r (one of %s)" % (weight, sorted(_cabi.HH_WEIGHTS)))
+            weight = _cabi.HH_WEIGHTS[weight]
+        base.weight = int(weight)
+        wl = None if wavelengths is None else _cabi.f64(wavelengths)
+        if wl is not None and wl.ndim != 1:
+            raise ValueError("the wavelengths are one row of samples")
+        # (an empty buffer has no columns yet: the samples are those of the wavelengths, or one)
+        W = self.hit_spectral_columns() // 3 or (len(wl) if wl is not None else 1)
+        if wl is not None and len(wl) != W:
+            raise ValueError("%d wavelengths for hits of %d samples" % (len(wl), W))
+        d = _cabi.HitHistXDesc(base, W, 1 if by_surface else 0, _cabi.ptr(wl))
+        total = N.empty(shape + (W,))
+        cnt = N.empty(shape, dtype=N.int64) if counts else None
+        outside, off = N.empty(W + 1), C.c_int64(0)
+        _cabi.check(self.lib.trc_scene_histogram_hits_x(self.handle, C.byref(d), _cabi.ptr(total), _cabi.ptr(cnt, C.POINTER(C.c_int64)),
+                                                        _cabi.ptr(outside), C.byref(off)))
+        return SpectralHistogram(wl, total, cnt, outside[:W], int(outside[W]), off.value)
+
+    def histogram_spectra(self, surf_lo, surf_hi, u_edges, v_edges, proj=None, chart='xy', weight='absorbed', wavelengths=None, counts=False):
+        """
+        The spectra of the captured hits of polychromatic rays per bin of a map, binned on the device where they lie
+        (trc_scene_histogram_hits_x): per sample k, numpy.histogram2d of what get_hits() would return now with the weights
+        spectra[0][k] - spectra[1][k] ('absorbed': the reference's PolychromaticAccountant result) or spectra[0][k] ('incident').
+        Surfaces, edges, proj and chart as in histogram_hits.  wavelengths: the (W,) grid every hit is held to -- a sample whose own
+        wavelength differs is left out and counted in `off_grid`; None: the wavelength columns are not read.  Returns a
+        SpectralHistogram with sum (nu, nv, W), and count (nu, nv) when counts is set.  The buffer stays as it is.
+        """
+        u = _cabi.f64(u_edges)
+        v = _cabi.f64(v_edges)
+        if u.ndim != 1 or v.ndim != 1 or len(u) < 2 or len(v) < 2:
+            raise ValueError("histogram_spectra: at least two edges either way")
+        if isinstance(chart, str):
+            if chart not in _cabi.HH_CHARTS:
+                raise ValueError("unknown histogram chart %r (one of %s)" % (chart, sorted(_cabi.HH_CHARTS)))
+            chart = _cabi.HH_CHARTS[chart]
+        surf_lo, surf_hi = int(surf_lo), int(surf_hi)
+        if proj is None:
+            if not 0 <= surf_lo < self.n_surf:
+                raise ValueError("histogram_spectra: surface %d is not one of the scene's %d" % (surf_lo, self.n_surf))
+            proj = N.round(N.linalg.inv(self.compiled.surfaces[surf_lo]._temp_frame), decimals=9)
+        p = _cabi.f64(N.asarray(proj)[:3].ravel())
+        base = _cabi.HitHistDesc(surf_lo, surf_hi, int(chart), 0, len(u) - 1, len(v) - 1, _cabi.ptr(u), _cabi.ptr(v), _cabi.ptr(p))
+        return self._spectra(base, False, (len(u) - 1, len(v) - 1), weight, wavelengths, counts)
+
+    def surface_spectra(self, surf_lo, surf_hi, weight='absorbed', wavelengths=None):
+        """
+        The spectrum every surface of surf_lo..surf_hi (inclusive) absorbed, or received, from the captured hits of polychromatic
+        rays: row s - surf_lo of `sum` (surfaces, W) is the sum over the hits of surface s, `count` their number -- the absorbed
+        spectrum of every wall element of a cavity in one pass.  Surfaces that capture nothing have zero rows; the range must hold
+        one that captures.  weight, wavelengths and the result as in histogram_spectra; nothing can be outside.
+        """
+        surf_lo, surf_hi = int(surf_lo), int(surf_hi)
+        base = _cabi.HitHistDesc(surf_lo, surf_hi, 0, 0, 0, 0, None, None, None)
+        return self._spectra(base, True, (max(surf_hi - surf_lo + 1, 0),), weight, wavelengths, True)
+
     def histogram_hits_ms(self):
-        """milliseconds the kernel of the last histogram_hits took on the device"""
+        """milliseconds the kernel of the last histogram_hits, histogram_spectra or surface_spectra took on the device"""
         ms = C.c_double(0.)
         _cabi.check(self.lib.trc_scene_histogram_hits_ms(self.handle, C.byref(ms)))
         return ms.value

@@ -56,6 +56,7 @@ class TracerEngine(object):
         self._ordered_pending = []      # weak references to what ordered traces still owe to accountants (ordered_levels.PendingLevels)
         self._transfer_pending = []     # those of them that carry a contribution to the transfer matrix (kept alive until it is read)
         self.stats = {}
+        self._last_spectrum = None      # the carried SourceSpectrum of the last ray_tracer call (histogram_spectra's grid), if it had one
 
     # -- the Kd-tree of the last accelerated call (tracer_engine.py:171-185) -------------------------------
     @property
@@ -209,6 +210,61 @@ class TracerEngine(object):
             proj = N.round(N.linalg.inv(self._dev.compiled.surfaces[lo]._temp_frame), decimals=9)[[1, 0, 2, 3]]
         return self._dev.histogram_hits(lo, hi, u_edges, v_edges, proj=proj, chart=chart, weight=weight, moments=moments)
 
+    def _spectra_grid(self, what, wavelengths):
+        """the grid the captured spectra are held to: the caller's, else that of the carried spectrum of the last ray_tracer call"""
+        if self._dev is None or self._dev.handle is None:
+            raise ValueError("%s: no device scene yet -- trace with ray_tracer(tree=False) first" % what)
+        if wavelengths is not None:
+            return wavelengths
+        if self._last_spectrum is None:
+            raise ValueError("%s: the last ray_tracer call had no source that carries its spectrum (SourceSpectrum.polychromatic): "
+                             "give the wavelengths of the samples" % what)
+        return self._last_spectrum.table()[0]
+
+    @staticmethod
+    def _on_grid(what, H):
+        if H.off_grid:
+            raise ValueError("%s: %d samples of the captured hits lie on other wavelengths than the grid (off_grid); the buffer holds "
+                             "hits of another sample grid" % (what, H.off_grid))
+        return H
+
+    def histogram_spectra(self, surface, u_edges, v_edges, chart='xy', weight='absorbed', swap_xy=False, wavelengths=None, counts=False):
+        """
+        A spectral flux map of `surface` from the captured hits of polychromatic rays, binned on the device after the trace: per
+        sample wavelength what histogram_hits gives for energies -- the spectrum absorbed ('absorbed': what the reference's
+        PolychromaticAccountant keeps per hit, summed per bin) or received ('incident') in every bin.  surface, chart, swap_xy as in
+        histogram_hits.  wavelengths: the (W,) sample grid; None: that of the carried spectrum of the last ray_tracer call.  A hit
+        whose own sample wavelengths differ from the grid is a ValueError that states how many samples do.  Returns a
+        SpectralHistogram: wavelengths, sum (nu, nv, W), count (with counts=True), outside (W,), outside_n, off_grid, integrate().
+        """
+        wl = self._spectra_grid('histogram_spectra', wavelengths)
+        index = lambda s: int(s) if isinstance(s, (int, N.integer)) else self._surface_index(s)
+        if isinstance(surface, (tuple, list)):
+            lo, hi = [index(s) for s in surface]
+        else:
+            lo = hi = index(surface)
+        proj = None
+        if swap_xy:
+            proj = N.round(N.linalg.inv(self._dev.compiled.surfaces[lo]._temp_frame), decimals=9)[[1, 0, 2, 3]]
+        return self._on_grid('histogram_spectra', self._dev.histogram_spectra(lo, hi, u_edges, v_edges, proj=proj, chart=chart, weight=weight,
+                                                                              wavelengths=wl, counts=counts))
+
+    def surface_spectra(self, surfaces=None, weight='absorbed', wavelengths=None):
+        """
+        The spectrum every surface absorbed (or received) from the captured hits of polychromatic rays, summed on the device: row i
+        of the result's `sum` (surfaces, W) belongs to surface lo + i.  surfaces: a Surface, an index, an (lo, hi) pair, or None for
+        the whole scene; surfaces that capture nothing have zero rows.  wavelengths and errors as in histogram_spectra.
+        """
+        wl = self._spectra_grid('surface_spectra', wavelengths)
+        index = lambda s: int(s) if isinstance(s, (int, N.integer)) else self._surface_index(s)
+        if surfaces is None:
+            lo, hi = 0, self._dev.n_surf - 1
+        elif isinstance(surfaces, (tuple, list)):
+            lo, hi = [index(s) for s in surfaces]
+        else:
+            lo = hi = index(surfaces)
+        return self._on_grid('surface_spectra', self._dev.surface_spectra(lo, hi, weight=weight, wavelengths=wl))
+
     def enable_transfer_matrix(self, on=True):
         """
         Keep the surface-to-surface energy transfer of the following traces: get_transfer_matrix()[i, j] is the energy
@@ -279,6 +335,7 @@ class TracerEngine(object):
         t_call = time.time()
         self.tree = RayTree()           # (the tree of the call before goes: levels nobody can read any more leave the device here)
         self._t_marks = [('old tree released', time.time() - t_call)]
+        self._last_spectrum = None
 
         if engine == 'protocol':
             return self._trace_protocol(bundle, reps, min_energy, tree)
@@ -293,6 +350,7 @@ class TracerEngine(object):
             return self._trace_protocol(bundle, reps, min_energy, tree)
 
         rays = call_plan.ray_facts(bundle)
+        self._last_spectrum = rays.spectrum if call_plan.carried(rays) else None
         scene = call_plan.scene_facts(dev, rays)
         if engine == 'auto':
             engine = call_plan.choose_engine(self, rays, scene, tree)
