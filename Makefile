@@ -11,13 +11,15 @@ ARCH ?= gfx950
 
 LIB := $(ROOT)tracer_amd/lib/libtracer_amd.so
 CSRC := $(ROOT)tracer_amd/csrc
-# four translation units: the engines and the scene's part of the C-ABI (trc_kernels.hip, which includes trc_stream.inc), the
-# class-split shading kernels of the streaming engine (trc_shade.hip), the histogram of captured hits (trc_hithist.hip), and the
-# entry points that take no scene with their kernels (trc_protocol.hip).  `make -j2` compiles them side by side.
-SRCS := $(CSRC)/trc_kernels.hip $(CSRC)/trc_shade.hip $(CSRC)/trc_hithist.hip $(CSRC)/trc_protocol.hip
+# five translation units: the engines (trc_kernels.hip, which includes trc_stream.inc), the class-split shading kernels of the
+# streaming engine (trc_shade.hip), the scene's part of the C-ABI (trc_scene.hip), the histograms of captured hits with their entry
+# points (trc_hithist.hip), and the entry points that take no scene with their kernels (trc_protocol.hip).  `make -j4` compiles
+# them side by side.
+UNITS := trc_kernels trc_shade trc_scene trc_hithist trc_protocol
+SRCS := $(UNITS:%=$(CSRC)/%.hip)
 OBJDIR := $(ROOT)build/obj
-OBJS := $(OBJDIR)/trc_kernels.o $(OBJDIR)/trc_shade.o $(OBJDIR)/trc_hithist.o $(OBJDIR)/trc_protocol.o
-HDR := $(CSRC)/trc_host.h $(CSRC)/trc_source_host.h $(CSRC)/trc_core.h $(CSRC)/trc_bounds.h $(CSRC)/trc_footprint.h $(CSRC)/trc_forms.h $(CSRC)/trc_device.h $(CSRC)/trc_stream.inc $(CSRC)/trc_mega.inc $(CSRC)/trc_hithist.h $(CSRC)/trc_pool.h $(CSRC)/trc_scene_host.h $(ROOT)include/tracer_amd.h
+OBJS := $(UNITS:%=$(OBJDIR)/%.o)
+HDR := $(CSRC)/trc_host.h $(CSRC)/trc_scene.h $(CSRC)/trc_source_host.h $(CSRC)/trc_core.h $(CSRC)/trc_bounds.h $(CSRC)/trc_footprint.h $(CSRC)/trc_forms.h $(CSRC)/trc_device.h $(CSRC)/trc_stream.inc $(CSRC)/trc_mega.inc $(CSRC)/trc_hithist.h $(CSRC)/trc_pool.h $(CSRC)/trc_scene_host.h $(ROOT)include/tracer_amd.h
 
 HOSTCHECK := $(ROOT)tests/hostcheck/libtrc_hostcheck.so
 HOSTCHECK_SRC := $(ROOT)tests/hostcheck/hostcheck.cpp
@@ -56,24 +58,15 @@ HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -munsafe-fp-atomics $(FPFLAGS)
 # kernels 170 / 241 registers with it, 94 / 116 without; k_s_shade 243 -> 131, k_s_fresh 168 -> 95, k_s_bounce 128 + 180 bytes of
 # scratch -> 119, k_trace_coop 256 + 408 bytes -> 165, k_ord_bounce 166 -> 121 (build/*.resources.txt, `make asm`).
 # Measured (profiles/README.md): NSTTF +3 %, dish +4 %, cavity +9 %, the megakernel on the dish +17 %.
-SHADE_FLAGS := -mllvm -disable-machine-licm
+# One rule for every unit, under UNIT_FLAGS; SHADE_FLAGS is what trc_shade.hip alone is compiled under (the same today).
 KERNELS_FLAGS := -mllvm -disable-machine-licm
+SHADE_FLAGS := $(KERNELS_FLAGS)
+UNIT_FLAGS = $(KERNELS_FLAGS)
+$(OBJDIR)/trc_shade.o: UNIT_FLAGS = $(SHADE_FLAGS)
 
-$(OBJDIR)/trc_shade.o: $(CSRC)/trc_shade.hip $(HDR)
+$(OBJDIR)/%.o: $(CSRC)/%.hip $(HDR)
 	mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(SHADE_FLAGS) -c -o $@ $<
-
-$(OBJDIR)/trc_kernels.o: $(CSRC)/trc_kernels.hip $(HDR)
-	mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(KERNELS_FLAGS) -c -o $@ $<
-
-$(OBJDIR)/trc_hithist.o: $(CSRC)/trc_hithist.hip $(HDR)
-	mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(KERNELS_FLAGS) -c -o $@ $<
-
-$(OBJDIR)/trc_protocol.o: $(CSRC)/trc_protocol.hip $(HDR)
-	mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(KERNELS_FLAGS) -c -o $@ $<
+	$(HIPCC) $(HIPFLAGS) $(UNIT_FLAGS) -c -o $@ $<
 
 $(LIB): $(OBJS)
 	mkdir -p $(dir $(LIB))
@@ -225,7 +218,7 @@ $(SOURCECHECK_LIB): $(SOURCECHECK_SRC) $(HDR)
 # assembly listings with the registers, scratch and occupancy of every kernel (build/*.s, build/*.resources.txt)
 asm: $(SRCS) $(HDR)
 	mkdir -p $(ROOT)build
-	for f in trc_kernels trc_shade trc_hithist trc_protocol; do \
+	for f in $(UNITS); do \
 		fl="$(KERNELS_FLAGS)"; [ $$f = trc_shade ] && fl="$(SHADE_FLAGS)"; \
 		$(HIPCC) $(HIPFLAGS) $$fl -S --cuda-device-only -Rpass-analysis=kernel-resource-usage \
 			-o $(ROOT)build/$$f.s $(CSRC)/$$f.hip 2> $(ROOT)build/$$f.resources.txt || exit 1; done

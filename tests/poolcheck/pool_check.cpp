@@ -62,7 +62,7 @@ struct FakeBackend {
 };
 typedef trc_block_cache<FakeBackend> Cache;
 
-// the policies of trc_kernels.hip
+// the policies of the library: dev_cache (trc_host.h) and g_host_cache (trc_scene.hip)
 static const trc_pool_policy DEVICE = {128 * MiB, 2 * GiB, 2 * GiB, true, true};
 static const trc_pool_policy HOST = {SIZE_MAX, 4 * GiB, 0, false, false};
 

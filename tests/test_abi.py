@@ -84,7 +84,9 @@ def test_no_gpu_means_loud_failure(lib_path):
 
 def test_the_units_of_the_library_share_one_error_string(lib_path):
     """trc_last_error reads what the last refusal on this thread wrote, whichever translation unit of the library refused: the
-    per-object protocol and the source tables (trc_protocol.hip), then the scene (trc_kernels.hip).  Null arguments: no device call."""
+    per-object protocol and the source tables (trc_protocol.hip), then the scene (trc_scene.hip, where trc_last_error itself
+    lives), the histograms of the captured hits (trc_hithist.hip) and the engines (trc_kernels.hip) -- every unit with an entry point:
+    the fifth, trc_shade.hip, holds kernels alone.  Null arguments: each call returns before any device call."""
     lib = ctypes.CDLL(lib_path)
     lib.trc_last_error.restype = ctypes.c_char_p
     invalid = -1
@@ -94,6 +96,15 @@ def test_the_units_of_the_library_share_one_error_string(lib_path):
     assert lib.trc_last_error() == b'trc_sunshape_create: bad arguments'
     assert lib.trc_scene_get_hits(None, None, None, None, None, None, None, None, None, None, None) == invalid
     assert lib.trc_last_error() == b'bad arguments'
+    assert lib.trc_scene_histogram_hits(None, None, None, None, None, None) == invalid
+    assert lib.trc_last_error() == b'trc_scene_histogram_hits: bad arguments'
+    p, i32, i64, u64, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double
+    lib.trc_trace_ordered.argtypes = [p, p, p, i64, i32, f64, u64, u64, i32, p, p]
+    assert lib.trc_trace_ordered(None, None, None, 0, 0, 0.0, 0, 0, 0, None, None) == invalid
+    assert lib.trc_last_error() == b'trc_trace_ordered: bad arguments'
+    # ... and the string is the last refusal's, not the last unit's
+    assert lib.trc_sunshape_create(None, 0, None, None, None) == invalid
+    assert lib.trc_last_error() == b'trc_sunshape_create: bad arguments'
 
 
 def test_product_never_imports_the_oracle():

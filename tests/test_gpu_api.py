@@ -1095,3 +1095,114 @@ def test_failed_fast_call_still_reports_its_stats():
     want = _fast_call(ref, src, n, 12, 1, None)
     ref.close()
     assert again[:2] == want[:2] and again[3] - held == want[3] and again[2] == pytest.approx(want[2], rel=1e-12), (again, held, want)
+
+
+def _plates_device(ctx):
+    """a mirror plate (0), face down at z = 2, over an absorber plate (1) in the plane z = 0 of an identity frame that captures
+    its hits in full and carries a 4 x 4 flux map clipped to a part of what is hit; and the scene's assembly"""
+    from tracer_amd.scene import DeviceScene, compile_scene
+    asm = Assembly(objects=[AssembledObject(surfs=[Surface(RectPlateGM(4., 4.), opt.Reflective(0.1))], transform=N.dot(translate(0., 0., 2.), rotx(N.pi))),
+                            AssembledObject(surfs=[Surface(RectPlateGM(6., 6.), opt.ReflectiveDetector(0.9))], transform=N.eye(4))])
+    dev = DeviceScene(compile_scene(asm), ctx)
+    dev.set_fluxmap(1, _PLATES_EDGES, _PLATES_EDGES)
+    dev.set_hit_capacity(4 * 4096)
+    return dev, asm
+
+
+_PLATES_EDGES = N.linspace(-2.5, 2.5, 5)
+
+
+def _plates_rays(seed=7, n=4096):
+    """given rays between the plates, going up at a tilt: some miss the mirror, some of the reflected ones the absorber or its map"""
+    rng = N.random.RandomState(seed)
+    v = N.vstack([rng.uniform(-1.5, 1.5, (2, n)), N.ones(n)])
+    d = N.vstack([rng.uniform(-0.6, 0.6, (2, n)), N.ones(n)])
+    return RayBundle(vertices=v, directions=d / N.sqrt((d * d).sum(axis=0)), energy=rng.uniform(0.5, 1.5, n), ref_index=N.ones(n))
+
+
+def _sorted_rows(rows):
+    return rows[N.lexsort(rows.T[::-1])]
+
+
+def _hit_rows(h):
+    """the hit list as rows (surface, absorbed, incident, point, direction) in an order of their own: the order hits arrive in is the device's"""
+    return _sorted_rows(N.vstack([N.asarray(h['surf'], dtype=float), h['e_abs'], h['e_in'], h['points'], h['directions']]).T.reshape(-1, 9))
+
+
+def _plates_state(dev):
+    a, r, h = dev.get_tallies()
+    return dict(tallies=N.concatenate([a, r]), counts=h.copy(), fluxmap=dev.get_fluxmap(1).copy(), hits=_hit_rows(dev.get_hits()))
+
+
+def _plates_call(dev, kind):
+    """one call of `kind` on `dev`; the levels of an ordered call, read and destroyed, else None"""
+    if kind == 'ordered':
+        res, _ = dev.trace_ordered(_plates_rays(), 3, 1e-10, 7)
+        levels = [res.level(k) for k in range(res.num_levels())]
+        res.close()
+        return levels
+    dev.trace_fast(_plates_rays(), 3, 1e-10, 7, stream=(kind == 'stream'))
+    return None
+
+
+def test_a_scene_serves_every_engine_and_reader_in_turn_as_fresh_scenes_do():
+    """
+    The parts of a scene live in one unit of the library, the engines and what they keep on the scene between calls in another, the
+    histograms in a third.  (a) A scene that is created, asked for its hits and destroyed without a trace: what the engines keep
+    was never made.  (b) One scene, in order: a streaming fast call, a megakernel fast call, an ordered call whose result is read
+    and destroyed, get_hits, histogram_hits, update_frames to the same poses, a second streaming call, destroy.  After each call
+    the tallies, the flux map, the per-surface hit counts and the captured hits are those of the calls so far, each made alone on
+    a fresh scene: counts and hit columns exactly (the hits as a set: the order they arrive in is the device's), tallies and
+    flux-map bins to 1e-9 (atomic float64 sums, whose last bits depend on the order of the addends).
+    """
+    from tracer_amd import _cabi
+    from tracer_amd.scene import compile_scene
+    ctx = _cabi.get_context(0)
+    dev, _ = _plates_device(ctx)
+    assert len(dev.get_hits()['surf']) == 0 and dev.hits_reserved() == (0, 4 * 4096)
+    dev.close()
+
+    alone = {}
+    for kind in ('stream', 'mega', 'ordered'):
+        ref, _ = _plates_device(ctx)
+        levels = _plates_call(ref, kind)
+        alone[kind] = dict(_plates_state(ref), levels=levels)
+        ref.close()
+    assert len(alone['stream']['hits']) > 1000 and (alone['stream']['counts'] > 1000).all()          # (the calls do reach both plates)
+    assert 0 < alone['stream']['fluxmap'].sum() < alone['stream']['tallies'][1]                      # (... and the map is clipped)
+    assert len(alone['ordered']['hits']) == 0 and len(alone['ordered']['levels']) == 4               # (the ordered engine captures nothing)
+
+    dev, asm = _plates_device(ctx)
+    want = dict(tallies=0., counts=0, fluxmap=0., hits=N.zeros((0, 9)))
+
+    def check(what):
+        got = _plates_state(dev)
+        assert (got['counts'] == want['counts']).all(), what
+        assert got['hits'].shape == want['hits'].shape and (got['hits'] == want['hits']).all(), what
+        assert got['tallies'] == pytest.approx(want['tallies'], rel=1e-9, abs=0.), what
+        assert got['fluxmap'] == pytest.approx(want['fluxmap'], rel=1e-9, abs=0.), what
+
+    def call(kind, what):
+        levels = _plates_call(dev, kind)
+        for k in ('tallies', 'counts', 'fluxmap'):
+            want[k] = want[k] + alone[kind][k]
+        want['hits'] = _sorted_rows(N.vstack([want['hits'], alone[kind]['hits']]))
+        check(what)
+        return levels
+
+    call('stream', 'streaming call')
+    call('mega', 'megakernel call')
+    levels = call('ordered', 'ordered call')
+    for got, ref in zip(levels, alone['ordered']['levels']):
+        for k in ('vertices', 'directions', 'energy', 'parents', 'surf'):
+            assert (got[k] == ref[k]).all(), k
+    # the histogram of the captured hits on the map's grid: numpy's of the hits the two fast calls captured (u = x, v = y: the
+    # absorber's frame is the identity)
+    rows = want['hits'][want['hits'][:, 0] == 1]
+    H = dev.histogram_hits(1, 1, _PLATES_EDGES, _PLATES_EDGES)
+    assert H == pytest.approx(N.histogram2d(rows[:, 3], rows[:, 4], bins=[_PLATES_EDGES, _PLATES_EDGES], weights=rows[:, 1])[0], rel=1e-9, abs=0.)
+    check('after get_hits and histogram_hits')
+    dev.update_frames(compile_scene(asm))
+    check('after update_frames')
+    call('stream', 'second streaming call')
+    dev.close()

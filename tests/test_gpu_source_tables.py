@@ -2,7 +2,7 @@
 The table path of the library against its host header, and the one device block cache behind both units of the library.
   * trc_sunshape_create, trc_angle_table_create and trc_emittance_table_create refuse a bad table with the status and the words of
     csrc/trc_source_host.h (through the host check library of tests/sourcecheck), and give their tables ids from one sequence;
-  * device blocks taken by trc_source_generate (trc_protocol.hip) wait in the cache that trc_ctx_destroy (trc_kernels.hip) trims.
+  * device blocks taken by trc_source_generate (trc_protocol.hip) wait in the cache that trc_ctx_destroy (trc_scene.hip) trims.
 """
 import ctypes as C
 

@@ -1,4 +1,4 @@
-// trc_device.h -- device-side types and helpers shared by the translation units of the library (trc_kernels.hip, trc_shade.hip):
+// trc_device.h -- device-side types and helpers shared by the translation units of the library (trc_kernels.hip, trc_shade.hip; trc_scene.h):
 // the device view of a scene, the parameter blocks of the fast engine and of its streaming form, the chunked list appends and the
 // per-hit bookkeeping.  Moved here unchanged from trc_kernels.hip / trc_stream.inc when the class-split shading kernels got a
 // translation unit of their own (round 3).

@@ -178,11 +178,4 @@ static inline void trc_hit_hist_x_host(const trc_hit_hist_x_args &X, int k0, int
     *X.off_grid += off;
 }
 
-#ifdef __HIPCC__
-// k_hist_hits over A on `stream` (trc_hithist.hip): the planes and `outside` on the device are added to.  The grid is k_bin_hits'.
-hipError_t trc_hit_hist_launch(hipStream_t stream, int n_cu, const trc_hit_hist_args &A);
-// k_hist_hits_x over X (trc_hithist.hip), sliced as trc_hit_hist_x_plan_for says: X.Ks is set here
-hipError_t trc_hit_hist_x_launch(hipStream_t stream, int n_cu, trc_hit_hist_x_args X);
-#endif
-
 #endif  // TRC_HITHIST_H

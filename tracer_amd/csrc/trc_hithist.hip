@@ -1,12 +1,20 @@
 // trc_hithist.hip -- k_hist_hits: the captured hits binned where they lie, in any chart of the hit point or of the incident direction
 // (trc_scene_histogram_hits), and k_hist_hits_x: the spectra of those hits binned the same way or per surface
-// (trc_scene_histogram_hits_x).  A translation unit of its own: the kernels of the engines are compiled as they were.
+// (trc_scene_histogram_hits_x), with their entry points below them.  A translation unit of its own: the kernels of the engines are
+// compiled as they were.
 //
 // One grid-stride pass over the reserved entries of the hit buffer.  A thread reads the surface of its entry first -- 4 bytes, which
 // for the entries of other surfaces and for the unwritten ends of the streaming engine's open chunks are all it reads -- then the
 // three columns of the chart and the one of the weight, each a coalesced 8-byte load of consecutive entries by consecutive lanes, all
 // four in flight before the first is used.  The bin comes from trc_hit_hist_entry (trc_hithist.h), the host loop's own.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
 #include <hip/hip_runtime.h>
+
+#include "trc_scene.h"
 #include "trc_hithist.h"
 
 #define HH_THREADS 256
@@ -110,7 +118,8 @@ __global__ __launch_bounds__(HH_THREADS) void k_hist_hits_x(trc_hit_hist_x_args 
     }
 }
 
-hipError_t trc_hit_hist_x_launch(hipStream_t stream, int n_cu, trc_hit_hist_x_args X) {
+// k_hist_hits_x over X on `stream`, sliced as trc_hit_hist_x_plan_for says: X.Ks is set here
+static hipError_t trc_hit_hist_x_launch(hipStream_t stream, int n_cu, trc_hit_hist_x_args X) {
     if (X.h.n <= 0) return hipSuccess;
     const trc_hit_hist_x_plan p = trc_hit_hist_x_plan_for(X.h.nu, X.h.nv, X.W, (X.h.planes & TRC_HH_PLANE_COUNT) != 0);
     X.Ks = p.Ks;
@@ -122,7 +131,8 @@ hipError_t trc_hit_hist_x_launch(hipStream_t stream, int n_cu, trc_hit_hist_x_ar
     return hipGetLastError();
 }
 
-hipError_t trc_hit_hist_launch(hipStream_t stream, int n_cu, const trc_hit_hist_args &A) {
+// k_hist_hits over A on `stream`: the planes and `outside` on the device are added to.  The grid is k_bin_hits'.
+static hipError_t trc_hit_hist_launch(hipStream_t stream, int n_cu, const trc_hit_hist_args &A) {
     if (A.n <= 0) return hipSuccess;
     const long long blocks = (A.n + HH_THREADS - 1) / HH_THREADS;
     const unsigned grid = (unsigned)(blocks < (long long)n_cu * 8 ? blocks : (long long)n_cu * 8);
@@ -131,4 +141,192 @@ hipError_t trc_hit_hist_launch(hipStream_t stream, int n_cu, const trc_hit_hist_
     else
         hipLaunchKernelGGL(k_hist_hits<false>, dim3(grid), dim3(HH_THREADS), 16, stream, A);
     return hipGetLastError();
+}
+
+// ================================================================================================
+// C-ABI: the histograms of the captured hits
+// ================================================================================================
+// Edges up, one pass over the reserved entries, planes down.
+#define TRC_HH_MAX_BINS (1ll << 27)      /* bins of a plane: 1 GiB of float64 */
+// what both histograms refuse, `fn` in front of the message; charted: the chart, the bins, their edges and proj12 are used (the spectra
+// by surface use none of them)
+static int hit_hist_check(const char *fn, const trc_scene *sc, const trc_hit_hist_desc *d, bool charted) {
+    if (d->weight != TRC_HH_ABSORBED && d->weight != TRC_HH_INCIDENT && d->weight != TRC_HH_COUNT)
+        return trc_fail(TRC_ERR_INVALID, "%s: unknown weight %d", fn, d->weight);
+    if (charted) {
+        if (!d->u_edges || !d->v_edges || !d->proj12) return trc_fail(TRC_ERR_INVALID, "%s: bad arguments", fn);
+        if (d->chart < 0 || d->chart >= TRC_HH_CHARTS) return trc_fail(TRC_ERR_INVALID, "%s: unknown chart %d", fn, d->chart);
+        if (d->nu < 1 || d->nv < 1) return trc_fail(TRC_ERR_INVALID, "%s: a histogram has at least one bin either way (%d x %d)", fn, d->nu, d->nv);
+        if ((long long)d->nu * d->nv > TRC_HH_MAX_BINS)
+            return trc_fail(TRC_ERR_CAPACITY, "%s: %d x %d bins (at most %lld)", fn, d->nu, d->nv, (long long)TRC_HH_MAX_BINS);
+        for (int ax = 0; ax < 2; ++ax) {
+            const double *e = ax ? d->v_edges : d->u_edges;
+            const int n = ax ? d->nv : d->nu;
+            for (int k = 0; k <= n; ++k)
+                if (!std::isfinite(e[k]) || (k > 0 && !(e[k] > e[k - 1])))
+                    return trc_fail(TRC_ERR_INVALID, "%s: the %s edges must be finite and increase strictly", fn, ax ? "v" : "u");
+        }
+        for (int k = 0; k < 12; ++k)
+            if (!std::isfinite(d->proj12[k])) return trc_fail(TRC_ERR_INVALID, "%s: proj12 holds a value that is not finite", fn);
+    }
+    if (d->surf_lo < 0 || d->surf_hi >= sc->n_surf || d->surf_lo > d->surf_hi)
+        return trc_fail(TRC_ERR_INVALID, "%s: surfaces %d..%d are not a range of the scene's %d", fn, d->surf_lo, d->surf_hi, sc->n_surf);
+    const bool full = (charted && TRC_HH_IS_DIR(d->chart)) || d->weight == TRC_HH_INCIDENT;
+    bool captures = false;
+    for (int s = d->surf_lo; s <= d->surf_hi; ++s) {
+        const int32_t fl = sc->surfaces[s].flags;
+        if (!(fl & TRC_SURF_CAPTURE_HITS)) continue;
+        captures = true;
+        if (full && (fl & TRC_SURF_CAPTURE_LEAN))
+            return trc_fail(TRC_ERR_INVALID, "%s: surface %d is captured lean (TRC_SURF_CAPTURE_LEAN): the direction and the "
+                            "incident energy of its hits were not written", fn, s);
+    }
+    if (!captures) return trc_fail(TRC_ERR_INVALID, "%s: none of the surfaces %d..%d captures its hits", fn, d->surf_lo, d->surf_hi);
+    return TRC_OK;
+}
+
+// What both histograms end with, `e` being what queuing their uploads gave: the launch between the context's two events, the words
+// from d_back on down into `back`, the wait -- always: nothing queued may outlive the buffers it uses -- and the device time of the
+// kernel into hist_ms.
+template <class Launch>
+static int hit_hist_run(const char *fn, trc_scene *sc, hipError_t e, Launch launch, const double *d_back, std::vector<double> &back) {
+    trc_ctx *ctx = sc->ctx;
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
+    if (e == hipSuccess) e = launch();
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(back.data(), d_back, back.size() * 8, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = se;
+    if (e != hipSuccess) return trc_fail(TRC_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) sc->hist_ms = ms;
+    return TRC_OK;
+}
+
+extern "C" int trc_scene_histogram_hits(trc_scene *sc, const trc_hit_hist_desc *d, double *sum, double *sum_sq, int64_t *count, double *outside) {
+    static const char *fn = "trc_scene_histogram_hits";
+    if (!sc || !d || !sum) return trc_fail(TRC_ERR_INVALID, "%s: bad arguments", fn);
+    TRC_TRY(hit_hist_check(fn, sc, d, true));
+
+    trc_ctx *ctx = sc->ctx;
+    unsigned long long cursor;
+    TRC_TRY(scene_hit_cursor(sc, &cursor));
+    const HitBuffer &hb = sc->hits;
+    const size_t nb = (size_t)d->nu * d->nv, ne = (size_t)d->nu + d->nv + 2;
+    for (size_t k = 0; k < nb; ++k) { sum[k] = 0.0; if (sum_sq) sum_sq[k] = 0.0; if (count) count[k] = 0; }
+    if (outside) outside[0] = outside[1] = 0.0;
+    sc->hist_ms = 0.0;
+    trc_hit_hist_args A;
+    memset(&A, 0, sizeof(A));
+    A.n = hb.used(cursor);
+    if (A.n == 0) return TRC_OK;
+    A.planes = (sum_sq ? TRC_HH_PLANE_SUM_SQ : 0) | (count ? TRC_HH_PLANE_COUNT : 0);
+    // one block: [edges] [sum] [sum_sq] [count] [outside]
+    const size_t np = (size_t)trc_hit_hist_n_planes(A.planes), words = ne + nb * np + 2;
+    DevBuf<double> d_buf;
+    TRC_TRY(d_buf.alloc(words));
+    std::vector<double> edges(ne);
+    std::copy(d->u_edges, d->u_edges + d->nu + 1, edges.begin());
+    std::copy(d->v_edges, d->v_edges + d->nv + 1, edges.begin() + d->nu + 1);
+    A.surf = hb.surf.get();
+    A.e_abs = hb.col[0].get(); A.e_in = hb.col[1].get(); A.px = hb.col[2].get(); A.py = hb.col[3].get(); A.pz = hb.col[4].get();
+    A.dx = hb.col[5].get(); A.dy = hb.col[6].get(); A.dz = hb.col[7].get();
+    A.surf_lo = d->surf_lo; A.surf_hi = d->surf_hi; A.chart = d->chart; A.weight = d->weight; A.nu = d->nu; A.nv = d->nv;
+    for (int k = 0; k < 12; ++k) A.proj[k] = d->proj12[k];
+    A.edges = d_buf.get();
+    A.sum = d_buf.get() + ne;
+    A.sum_sq = sum_sq ? A.sum + nb : nullptr;
+    A.count = count ? (unsigned long long *)(A.sum + nb * (sum_sq ? 2 : 1)) : nullptr;
+    A.outside = A.sum + nb * np;
+    std::vector<double> back(nb * np + 2);
+    hipError_t e = hipMemcpyAsync(d_buf.get(), edges.data(), ne * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(A.sum, 0, (nb * np + 2) * 8, ctx->stream);
+    TRC_TRY(hit_hist_run(fn, sc, e, [&] { return trc_hit_hist_launch(ctx->stream, ctx->n_cu, A); }, A.sum, back));
+    memcpy(sum, back.data(), nb * 8);
+    if (sum_sq) memcpy(sum_sq, back.data() + nb, nb * 8);
+    if (count) memcpy(count, back.data() + nb * (sum_sq ? 2 : 1), nb * 8);
+    if (outside) { outside[0] = back[nb * np]; outside[1] = back[nb * np + 1]; }
+    return TRC_OK;
+}
+
+// The spectra of the captured hits binned where they lie (k_hist_hits_x): per bin of the chart, or per surface, and per sample.
+extern "C" int trc_scene_histogram_hits_x(trc_scene *sc, const trc_hit_hist_x_desc *dx, double *sum, int64_t *count, double *outside,
+                                          int64_t *off_grid) {
+    static const char *fn = "trc_scene_histogram_hits_x";
+    if (!sc || !dx || !sum) return trc_fail(TRC_ERR_INVALID, "%s: bad arguments", fn);
+    const trc_hit_hist_desc *d = &dx->base;
+    const bool by_surface = dx->by_surface != 0;
+    TRC_TRY(hit_hist_check(fn, sc, d, !by_surface));
+    if (d->weight == TRC_HH_COUNT)
+        return trc_fail(TRC_ERR_INVALID, "%s: the weight is the absorbed or the incident spectrum (the count is the `count` plane)", fn);
+    const int W = dx->n_samples, nu = by_surface ? d->surf_hi - d->surf_lo + 1 : d->nu, nv = by_surface ? 1 : d->nv;
+    if (W < 1) return trc_fail(TRC_ERR_INVALID, "%s: %d samples", fn, W);
+    for (int k = 0; dx->wl && k < W; ++k)
+        if (!std::isfinite(dx->wl[k])) return trc_fail(TRC_ERR_INVALID, "%s: wl holds a value that is not finite", fn);
+    const size_t nb = (size_t)nu * nv, ne = (size_t)nu + nv + 2;
+    if ((long long)nb * W > TRC_HH_MAX_BINS)
+        return trc_fail(TRC_ERR_CAPACITY, "%s: %d x %d bins of %d samples (at most %lld in all)", fn, nu, nv, W, (long long)TRC_HH_MAX_BINS);
+
+    trc_ctx *ctx = sc->ctx;
+    unsigned long long cursor;
+    TRC_TRY(scene_hit_cursor(sc, &cursor));
+    const HitBuffer &hb = sc->hits;
+    const long long n = hb.used(cursor);
+    if (n > 0 && hb.x_cols == 0) return trc_fail(TRC_ERR_INVALID, "%s: the hit buffer holds no spectral columns: its hits are not those of polychromatic rays", fn);
+    if (hb.x_cols != 0 && hb.x_cols != 3 * W)
+        return trc_fail(TRC_ERR_INVALID, "%s: the hit buffer holds %d spectral columns, 3 x %d samples, not 3 x %d", fn, hb.x_cols, hb.x_cols / 3, W);
+    for (size_t k = 0; k < nb * W; ++k) sum[k] = 0.0;
+    for (size_t k = 0; count && k < nb; ++k) count[k] = 0;
+    for (int k = 0; outside && k <= W; ++k) outside[k] = 0.0;
+    if (off_grid) *off_grid = 0;
+    sc->hist_ms = 0.0;
+    if (n == 0) return TRC_OK;
+    // one block: [edges] [sum] [count] [outside: W, and the number] [off grid]
+    const size_t tail = nb * W + (count ? nb : 0) + W + 2, words = ne + tail;
+    DevBuf<double> d_buf;
+    TRC_TRY(d_buf.alloc(words));
+    trc_hit_hist_x_args X;
+    memset(&X, 0, sizeof(X));
+    trc_hit_hist_args &A = X.h;
+    A.n = n;
+    A.planes = count ? TRC_HH_PLANE_COUNT : 0;
+    A.surf = hb.surf.get();
+    A.px = hb.col[2].get(); A.py = hb.col[3].get(); A.pz = hb.col[4].get();
+    A.dx = hb.col[5].get(); A.dy = hb.col[6].get(); A.dz = hb.col[7].get();
+    A.surf_lo = d->surf_lo; A.surf_hi = d->surf_hi; A.chart = by_surface ? 0 : d->chart; A.weight = d->weight; A.nu = nu; A.nv = nv;
+    A.edges = d_buf.get();
+    A.sum = d_buf.get() + ne;
+    A.count = count ? (unsigned long long *)(A.sum + nb * W) : nullptr;
+    A.outside = A.sum + nb * W + (count ? nb : 0);
+    X.off_grid = (unsigned long long *)(A.outside + W + 1);
+    X.x = hb.x.get(); X.cap = hb.cap; X.W = W; X.by_surface = by_surface ? 1 : 0;
+    // the edges up, and in a block of their own the wavelengths the hits are held to
+    DevBuf<double> d_wl;
+    if (dx->wl) TRC_TRY(d_wl.alloc((size_t)W));
+    std::vector<double> edges(ne, 0.0), back(tail);
+    hipError_t e = hipSuccess;
+    if (!by_surface) {
+        for (int k = 0; k < 12; ++k) A.proj[k] = d->proj12[k];
+        std::copy(d->u_edges, d->u_edges + nu + 1, edges.begin());
+        std::copy(d->v_edges, d->v_edges + nv + 1, edges.begin() + nu + 1);
+        e = hipMemcpyAsync(d_buf.get(), edges.data(), ne * 8, hipMemcpyHostToDevice, ctx->stream);
+    }
+    if (dx->wl) {
+        X.wl = d_wl.get();
+        if (e == hipSuccess) e = hipMemcpyAsync(d_wl.get(), dx->wl, (size_t)W * 8, hipMemcpyHostToDevice, ctx->stream);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(A.sum, 0, tail * 8, ctx->stream);
+    TRC_TRY(hit_hist_run(fn, sc, e, [&] { return trc_hit_hist_x_launch(ctx->stream, ctx->n_cu, X); }, A.sum, back));
+    const double *b_out = back.data() + nb * W + (count ? nb : 0);
+    memcpy(sum, back.data(), nb * W * 8);
+    if (count) memcpy(count, back.data() + nb * W, nb * 8);
+    if (outside) memcpy(outside, b_out, (size_t)(W + 1) * 8);
+    if (off_grid) memcpy(off_grid, b_out + W + 1, 8);
+    return TRC_OK;
+}
+
+extern "C" int trc_scene_histogram_hits_ms(trc_scene *sc, double *ms) {
+    if (!sc || !ms) return trc_fail(TRC_ERR_INVALID, "bad arguments");
+    *ms = sc->hist_ms;
+    return TRC_OK;
 }

@@ -1,7 +1,7 @@
 // trc_host.h -- the host plumbing the library's units share: the thread's error string and the macros that fill it, device memory
 // behind the block cache and its owners, the context, a bundle's columns staged on the device, and the few functions of the
-// scene-free unit (trc_protocol.hip) that the engines (trc_kernels.hip) call.  The error string and the device block cache are one
-// object each in the built library, whichever unit reaches them.
+// scene-free unit (trc_protocol.hip) that the engines (trc_kernels.hip) call.  The scene itself is trc_scene.h, on top of this
+// header.  The error string and the device block cache are one object each in the built library, whichever unit reaches them.
 #ifndef TRC_HOST_H
 #define TRC_HOST_H
 
@@ -231,6 +231,18 @@ static int stage_rays(const trc_rays *r, int64_t n, bool need_energy, DevRays *d
     }
     return TRC_OK;
 }
+
+// ================================================================================================
+// rocprim's device-wide scan and sort over 32-bit words, instantiated once for the library
+// ================================================================================================
+// Defined in the engines' unit (trc_kernels.hip), where the ordered engine sorts its slots with the same instantiation as the hit
+// buffer's reader (trc_scene.hip): the library holds rocprim's kernels once, and the engines' unit the same ones as ever -- the
+// compiler specialises the HIP headers' shuffle functions for the callers it sees in a module, so the listings of the engine kernels
+// that reduce over a wave depend on them (profiles/scene_unit.txt).  tmp null: the size query, as in rocprim.
+hipError_t dev_exclusive_scan_u32(void *tmp, size_t &tmp_bytes, uint32_t *in, uint32_t *out, size_t n, hipStream_t stream);
+// stable, by bits [0, end_bit) of the keys
+hipError_t dev_sort_pairs_u32(void *tmp, size_t &tmp_bytes, uint32_t *key_in, uint32_t *key_out, uint32_t *val_in, uint32_t *val_out, size_t n,
+                              unsigned end_bit, hipStream_t stream);
 
 // ================================================================================================
 // what the engines call of the scene-free unit (trc_protocol.hip)

@@ -13,8 +13,8 @@
 //     void release(void *p)          a block of alloc() back to where it came from
 //     void quiesce()                 returns when nothing in flight can still use a block freed before the call
 //     int device()                   the device a block allocated now would belong to
-// trc_kernels.hip has the two real ones; tests/poolcheck drives the cache through a fake one under the sanitizers.  Nothing here
-// includes a HIP header.
+// trc_host.h (device memory) and trc_scene.hip (pinned host memory) have the two real ones; tests/poolcheck drives the cache
+// through a fake one under the sanitizers.  Nothing here includes a HIP header.
 #ifndef TRC_POOL_H
 #define TRC_POOL_H
 

@@ -1,7 +1,7 @@
 // trc_scene_host.h -- the arithmetic of a scene's host side, free of HIP: the record stride and what the optics ask of the rays, the
 // order in which the search tables are built, the one validation of a caller's Kd-tree with its packing, and the layout of the
-// tally buffer.  The library (trc_kernels.hip: the owners inside trc_scene) and the host checks (tests/hostcheck, tests/scenecheck)
-// read the same functions.
+// tally buffer.  The library (trc_scene.h: the owners inside trc_scene, which hold device memory and so need HIP) and the host
+// checks (tests/hostcheck, tests/scenecheck) read the same functions.
 #ifndef TRC_SCENE_HOST_H
 #define TRC_SCENE_HOST_H
 
