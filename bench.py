@@ -2,8 +2,8 @@
 """
 bench.py -- the headline benchmark of BASELINE.json: Mray-bounces/s on the Sandia NSTTF heliostat field.
 
-    python bench.py --gpus N --steps K --warmup W
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input: `--rays` source rays (default 1e8 =
 configs[2], "Sandia NSTTF field, 1e8 rays, 1xMI355X") generated on the device from the Buie-sunshape source
@@ -16,10 +16,14 @@ exchange is ONE all-reduce (RCCL) of the packed tally buffer at the end of the j
 float64: the per-surface tallies, the receiver's flux map, the segment count and a fixed, seeded sample of the receiver's hit
 list (dump_outputs).  The inputs of a step depend only on the arguments, so two builds can be compared output for output.
 
-Prints ONE JSON line on rank 0: metric/value/unit per BASELINE.json, plus
+Prints ONE JSON line on rank 0: metric/value/unit per BASELINE.json, ms_per_step, the workload (`config`), and
   roofline      algorithmic HBM bytes of the fast engine (112 B per ray segment) over the time of its
-                kernels for one step, measured with HIP events on the launch stream, against the 8 TB/s HBM peak;
-                `traffic` = HBM bytes per step from the rocprofv3 PMC passes kept in profiles/traffic.json
+                kernels for one step, measured with HIP events on the launch stream of the timed steps themselves, against
+                the 8 TB/s HBM peak
+A plain run does only that: set-up, warm-up, the timed steps, the dump if asked for, the line.  Everything else the
+benchmark measures or checks takes time of its own and waits behind --full, which adds to the line
+  roofline      `traffic` = HBM bytes per step from the rocprofv3 PMC passes kept in profiles/traffic.json, the measured
+                fractions that follow from it, and `kernels`, the per-kernel SQ counter ratios of profiles/sq_counters.json
   api_level     the same step through the public entry point, TracerEngine.ray_tracer(tree=False, accel=True): scene
                 signature check, hit buffer sized by the engine; the receiver's hits stay on the device until its
                 accountants are read -- timed without and with that read after every call
@@ -32,6 +36,7 @@ Prints ONE JSON line on rank 0: metric/value/unit per BASELINE.json, plus
   cpu_baseline  the oracle (NumPy restatement of the reference's algorithm = the reference's own CPU path, which
                 is NumPy too) timed on this host's cores (one process per core, independent batches) on a bounded
                 sample of the same workload, rank 0 at N=1 only, before the GPU part starts.
+(--cpu-rays 0, --api-steps 0 and --no-extras leave single legs out of a --full run; without --full they have nothing to do.)
 """
 import argparse
 import json
@@ -225,12 +230,116 @@ def dump_outputs(out_dir, tallies, fluxmap, hits, segments, seed=2024):
     return sorted(arrays)
 
 
+def full_report(out, args, dev, ctx, cpu, w):
+    """
+    --full, rank 0, after the timed steps: what the headline does not need, added to the line `out` -- the counter figures of the
+    roofline, `check`, `api_level`, `cpu_baseline` (timed before the GPU part, handed in as `cpu`) and `other_configs`.
+    `w` describes the run: the plant and its source, the receiver's flux-map edges, the rays of this rank's step and of the whole
+    step, accel, the kernel time of the timed steps, the job's segments and the number of independent bundles it traced.
+    Returns (whether the check passed, the scene if it is still open or None).
+    """
+    import numpy as N
+    import torch
+    from tracer_amd import scenes
+    world = int(os.environ.get('WORLD_SIZE', '1'))
+    plant, src, (ue, ve), n, n_total, accel, kms = w['plant'], w['src'], w['fluxmap_edges'], w['rays'], w['rays_of_a_step'], w['accel'], w['kernel_ms']
+    total_segments, n_bundles = w['total_segments'], w['independent_bundles']
+    a, r, h = dev.get_tallies()
+    fm = dev.get_fluxmap(218)
+    api = None
+    if world == 1 and args.api_steps > 0 and args.kernel == 'auto':
+        # the public entry point on the same workload (a scene of its own: the engine compiles the assembly itself)
+        dev.close()
+        dev = None
+        from tracer_amd.tracer_engine import TracerEngine
+        eng = TracerEngine(plant)
+        eng.set_fluxmap(218, ue, ve)
+        mk = lambda k: scenes.nsttf_source(n, src, seed=2024, ray_offset=(args.steps + args.warmup + 1 + k) * n)
+        rec_opt = plant.get_surfaces()[218].get_optics_manager()
+        eng.ray_tracer(mk(0), reps=100, min_energy=1e-10, tree=False, accel=accel, seed=2024)       # warm-up: allocations
+        rec_opt.get_all_hits()                                                                      # ... and the page-locked blocks
+        plant.reset_all_optics()
+        torch.cuda.synchronize()
+
+        def api_loop(read):
+            t1 = time.time()
+            aseg, got = 0, 0
+            for k in range(args.api_steps):
+                eng.ray_tracer(mk(1 + k), reps=100, min_energy=1e-10, tree=False, accel=accel, seed=2024)
+                aseg += eng.stats['segments']
+                if read:
+                    got += len(rec_opt.get_all_hits()[0])     # absorbed energies and hit points of the step, on the host
+                    plant.reset_all_optics()
+            torch.cuda.synchronize()
+            adt = time.time() - t1
+            plant.reset_all_optics()
+            return adt / args.api_steps * 1e3, aseg / adt / 1e6, got
+        ms_unread, v_unread, _ = api_loop(False)
+        ms_read, v_read, got = api_loop(True)
+        api = {'entry': 'TracerEngine.ray_tracer(bundle, reps=100, min_energy=1e-10, tree=False, accel=%r)' % accel,
+               'steps': args.api_steps, 'ms_per_step': ms_unread, 'value': v_unread, 'unit': 'Mray-bounces/s',
+               'ms_per_step_hits_read': ms_read, 'value_hits_read': v_read, 'hits_read_per_step': got // max(args.api_steps, 1),
+               'includes': 'scene signature check, hit buffer kept or grown (the hits of successive calls stay on the device until an '
+                           'accountant is read), trc_trace_fast, marks handed to the receiver\'s accountants; hits_read: plus '
+                           'get_all_hits() of the receiver after every call -- the step\'s receiver hits (absorbed energy + hit point, '
+                           '36 B each) packed on the device and copied into page-locked host arrays -- and reset_all_optics()'}
+    total_rays = float(n_total) * n_bundles
+    e_ray = 1000. * N.pi * src['radius'] ** 2 / n_total  # energy per ray of ONE step's bundle
+    receiver_kw = a[218] / n_bundles / 1e3                # mean over the independent batches
+    traffic, traffic_raw = traffic_for(n, accel)
+    out['roofline'].update({
+        'traffic': traffic, 'traffic_fetch_as_counted': traffic_raw,
+        # what the counters say moves through HBM, over the same kernel time: the fraction of the 8 TB/s actually used
+        # (`frac` prices every segment at 112 B, and 94 % of the segments end in registers)
+        'hbm_measured_frac': (traffic / (kms / args.steps * 1e-3) / (HBM_PEAK_GBS * 1e9)) if (traffic and kms > 0) else None,
+        'hbm_measured_frac_fetch_as_counted': (traffic_raw / (kms / args.steps * 1e-3) / (HBM_PEAK_GBS * 1e9)) if (traffic_raw and kms > 0) else None,
+        # what binds each kernel: vector instructions issued per resident wave cycle and the share of those cycles spent
+        # waiting, from the single-batch PMC passes kept in profiles/sq_counters.json (tools/pmc_kernels.py)
+        'kernels': sq_counters_for(n)})
+    out['check'] = {'receiver_kW': receiver_kw, 'receiver_hits': int(h[218]), 'heliostat_hits': int(h[:218].sum()),
+                    'segments_total': int(round(total_segments)), 'receiver_hits_per_ray': h[218] / total_rays,
+                    'heliostat_hits_per_ray': float(h[:218].sum()) / total_rays,
+                    'fluxmap_sum_kW': float(fm.sum()) / n_bundles / 1e3, 'energy_per_ray_W': e_ray}
+    out['api_level'] = api
+    out['cpu_baseline'] = cpu
+    if world == 1 and not args.no_extras and args.kernel == 'auto' and n >= 10 ** 7:
+        try:
+            if dev is not None:
+                dev.close()
+                dev = None
+            out['other_configs'] = other_configs(ctx, log)
+        except Exception as err:        # (for the record only: the headline stands without them)
+            log('other_configs skipped: %r' % (err,))
+            out['other_configs'] = None
+    # the reference's own Monte-Carlo mean of the receiver power (10 runs of 1e5 rays): 5 sigma of both estimates
+    ok = True
+    try:
+        mc = N.load(os.path.join(ROOT, 'tests', 'golden', 'mc_reference.npz'))
+        p_ref, se_ref = float(mc['nsttf_receiver_mean']) / 1e3, float(mc['nsttf_receiver_se']) / 1e3
+        se_gpu = e_ray * N.sqrt(max(h[218], 1.)) / n_bundles / 1e3
+        sig = float(N.sqrt(se_ref ** 2 + se_gpu ** 2))
+        out['check']['reference_receiver_kW'] = p_ref
+        out['check']['sigma_kW'] = sig
+        out['check']['deviation_sigma'] = abs(receiver_kw - p_ref) / sig
+        ok = abs(receiver_kw - p_ref) <= 5. * sig and abs(float(fm.sum()) / n_bundles / 1e3 - receiver_kw) <= 1e-6 * receiver_kw
+        out['check']['ok'] = bool(ok)
+    except Exception as err:        # no fixture: nothing to compare with
+        out['check']['ok'] = None
+        log('check skipped: %s' % err)
+    if not ok:
+        log('CHECK FAILED: receiver power %.1f kW vs reference %.1f kW' % (receiver_kw, out['check'].get('reference_receiver_kW', float('nan'))))
+    return ok, dev
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--rays', type=float, default=1e8, help='source rays per step per GPU')
+    ap.add_argument('--full', action='store_true',
+                    help='also what the headline does not need: CPU baseline, the check against the reference, the public entry point, '
+                         'the other configurations, the counter figures of the roofline (the options below that name them trim such a run)')
     ap.add_argument('--cpu-rays', type=int, default=250000, help='source rays per bundle of a CPU baseline worker (0 = skip)')
     ap.add_argument('--cpu-batches', type=int, default=6, help='bundles traced by every CPU baseline worker')
     ap.add_argument('--cpu-workers', type=int, default=0, help='CPU baseline processes (0 = one per core, at most 16)')
@@ -263,7 +372,7 @@ def main():
         ap.error('--dump-outputs needs a single process')
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_rays > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_rays > 0:
         # before anything initialises the GPU in this process (the workers are separate programs)
         workers = args.cpu_workers or min(os.cpu_count() or 1, 16)
         log('timing the CPU baseline (oracle, %d processes x %d x %d rays) ...' % (workers, args.cpu_batches, args.cpu_rays))
@@ -365,52 +474,8 @@ def main():
         dev.import_tallies(carried + last)
         log('outputs of the last timed step written to %s: %s' % (args.dump_outputs, ', '.join(names)))
 
-    api = None
     if rank == 0:
-        a, r, h = dev.get_tallies()
-        fm = dev.get_fluxmap(218)
-        if world == 1 and args.api_steps > 0 and args.kernel == 'auto':
-            # the public entry point on the same workload (a scene of its own: the engine compiles the assembly itself)
-            dev.close()
-            dev = None
-            from tracer_amd.tracer_engine import TracerEngine
-            eng = TracerEngine(plant)
-            eng.set_fluxmap(218, ue, ve)
-            mk = lambda k: scenes.nsttf_source(n, src, seed=2024, ray_offset=(args.steps + args.warmup + 1 + k) * n)
-            rec_opt = plant.get_surfaces()[218].get_optics_manager()
-            eng.ray_tracer(mk(0), reps=100, min_energy=1e-10, tree=False, accel=accel, seed=2024)       # warm-up: allocations
-            rec_opt.get_all_hits()                                                                      # ... and the page-locked blocks
-            plant.reset_all_optics()
-            torch.cuda.synchronize()
-
-            def api_loop(read):
-                t1 = time.time()
-                aseg, got = 0, 0
-                for k in range(args.api_steps):
-                    eng.ray_tracer(mk(1 + k), reps=100, min_energy=1e-10, tree=False, accel=accel, seed=2024)
-                    aseg += eng.stats['segments']
-                    if read:
-                        got += len(rec_opt.get_all_hits()[0])     # absorbed energies and hit points of the step, on the host
-                        plant.reset_all_optics()
-                torch.cuda.synchronize()
-                adt = time.time() - t1
-                plant.reset_all_optics()
-                return adt / args.api_steps * 1e3, aseg / adt / 1e6, got
-            ms_unread, v_unread, _ = api_loop(False)
-            ms_read, v_read, got = api_loop(True)
-            api = {'entry': 'TracerEngine.ray_tracer(bundle, reps=100, min_energy=1e-10, tree=False, accel=%r)' % accel,
-                   'steps': args.api_steps, 'ms_per_step': ms_unread, 'value': v_unread, 'unit': 'Mray-bounces/s',
-                   'ms_per_step_hits_read': ms_read, 'value_hits_read': v_read, 'hits_read_per_step': got // max(args.api_steps, 1),
-                   'includes': 'scene signature check, hit buffer kept or grown (the hits of successive calls stay on the device until an '
-                               'accountant is read), trc_trace_fast, marks handed to the receiver\'s accountants; hits_read: plus '
-                               'get_all_hits() of the receiver after every call -- the step\'s receiver hits (absorbed energy + hit point, '
-                               '36 B each) packed on the device and copied into page-locked host arrays -- and reset_all_optics()'}
-        total_rays = float(n_total) * args.steps * (1 if strong else world)
-        e_ray = 1000. * N.pi * src['radius'] ** 2 / n_total  # energy per ray of ONE step's bundle
-        n_bundles = args.steps * (1 if strong else world)     # independent bundles of n_total rays the job traced
-        receiver_kw = a[218] / n_bundles / 1e3                # mean over the independent batches
         ach = (seg * B_SEG / 1e9) / (kms / 1e3) if kms > 0 else 0.0     # GB/s, this rank's launches
-        traffic, traffic_raw = traffic_for(n, accel)
         out = {
             'metric': 'Mray-bounces/s on Sandia NSTTF field',
             'value': total_segments / dt_max / 1e6,
@@ -418,7 +483,7 @@ def main():
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': dt_max / args.steps * 1e3,
             'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None,
-            'dtype': 'f64', 'data': 'synthetic',
+            'dtype': 'f64', 'data': 'synthetic', 'full': bool(args.full),
             'config': {'workload': 'Sandia NSTTF heliostat field: 218 heliostats + receiver, Buie sunshape CSR 0.01, '
                                    '%.0e source rays per step per GPU, %s, reps=100, min_energy=1e-10; tallies + 50x50 '
                                    'flux map + receiver hit list on device'
@@ -426,56 +491,22 @@ def main():
                                          'uniform grid over the same geometry boxes)' if accel else 'brute force'),
                        'rays_per_step_per_gpu': n, 'segments_per_step_per_gpu': seg / args.steps, 'accel': accel,
                        'parallelism': 'rays sharded by stream id over %d GPU(s) (%s), one all-reduce of tallies at the end' % (world, 'the ranks share the rays of a step' if strong else 'every rank its own rays per step')},
+            # (from the HIP events of the timed steps themselves: no run of its own)
             'roofline': {'bound': 'hbm', 'achieved': ach, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': ach / HBM_PEAK_GBS,
-                         'traffic': traffic, 'traffic_fetch_as_counted': traffic_raw,
                          'kernel': 'k_trace_coop<512>' if launches == 1 else
                                    'fast engine, streaming form: k_s_cull + k_s_fresh2 (+ the general path for the aureole) + k_s_shade_c<mirror>, '
                                    'then k_s_bounce (the hits on the receiver finished inside) + k_s_shade_c<mirror> per bounce '
                                    '(%d launches per step)' % launches,
                          'kernel_ms_per_launch': kms / args.steps,
-                         'algorithmic_bytes_per_launch': seg / args.steps * B_SEG,
-                         # what the counters say moves through HBM, over the same kernel time: the fraction of the 8 TB/s actually used
-                         # (`frac` above prices every segment at 112 B, and 94 % of the segments end in registers)
-                         'hbm_measured_frac': (traffic / (kms / args.steps * 1e-3) / (HBM_PEAK_GBS * 1e9)) if (traffic and kms > 0) else None,
-                         'hbm_measured_frac_fetch_as_counted': (traffic_raw / (kms / args.steps * 1e-3) / (HBM_PEAK_GBS * 1e9)) if (traffic_raw and kms > 0) else None,
-                         # what binds each kernel: vector instructions issued per resident wave cycle and the share of those cycles spent
-                         # waiting, from the single-batch PMC passes kept in profiles/sq_counters.json (tools/pmc_kernels.py)
-                         'kernels': sq_counters_for(n)},
-            'check': {'receiver_kW': receiver_kw, 'receiver_hits': int(h[218]), 'heliostat_hits': int(h[:218].sum()),
-                      'segments_total': int(round(total_segments)), 'receiver_hits_per_ray': h[218] / total_rays,
-                      'heliostat_hits_per_ray': float(h[:218].sum()) / total_rays,
-                      'fluxmap_sum_kW': float(fm.sum()) / n_bundles / 1e3, 'energy_per_ray_W': e_ray},
+                         'algorithmic_bytes_per_launch': seg / args.steps * B_SEG},
         }
-        out['api_level'] = api
-        out['cpu_baseline'] = cpu
-        if world == 1 and not args.no_extras and args.kernel == 'auto' and n >= 10 ** 7:
-            try:
-                if dev is not None:
-                    dev.close()
-                    dev = None
-                out['other_configs'] = other_configs(ctx, log)
-            except Exception as err:        # (for the record only: the headline stands without them)
-                log('other_configs skipped: %r' % (err,))
-                out['other_configs'] = None
-        # the reference's own Monte-Carlo mean of the receiver power (10 runs of 1e5 rays): 5 sigma of both estimates
-        ok = True
-        try:
-            mc = N.load(os.path.join(ROOT, 'tests', 'golden', 'mc_reference.npz'))
-            p_ref, se_ref = float(mc['nsttf_receiver_mean']) / 1e3, float(mc['nsttf_receiver_se']) / 1e3
-            se_gpu = e_ray * N.sqrt(max(h[218], 1.)) / n_bundles / 1e3
-            sig = float(N.sqrt(se_ref ** 2 + se_gpu ** 2))
-            out['check']['reference_receiver_kW'] = p_ref
-            out['check']['sigma_kW'] = sig
-            out['check']['deviation_sigma'] = abs(receiver_kw - p_ref) / sig
-            ok = abs(receiver_kw - p_ref) <= 5. * sig and abs(float(fm.sum()) / n_bundles / 1e3 - receiver_kw) <= 1e-6 * receiver_kw
-            out['check']['ok'] = bool(ok)
-        except Exception as err:        # no fixture: nothing to compare with
-            out['check']['ok'] = None
-            log('check skipped: %s' % err)
+        if args.full:
+            ok, dev = full_report(out, args, dev, ctx, cpu, dict(
+                plant=plant, src=src, fluxmap_edges=(ue, ve), rays=n, rays_of_a_step=n_total, accel=accel, kernel_ms=kms,
+                total_segments=total_segments, independent_bundles=args.steps * (1 if strong else world)))
+            if not ok:
+                exit_code = 3
         print(json.dumps(out), flush=True)
-        if not ok:
-            log('CHECK FAILED: receiver power %.1f kW vs reference %.1f kW' % (receiver_kw, out['check'].get('reference_receiver_kW', float('nan'))))
-            exit_code = 3
     if dev is not None:
         dev.close()
     if world > 1:

@@ -602,7 +602,7 @@ def test_bench_as_two_ranks_on_one_gpu(ctx, world):
     port = 29600 + os.getpid() % 300 + world
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(world), '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', str(world), '--steps', str(steps), '--warmup', str(warmup),
-           '--rays', str(n), '--cpu-rays', '0', '--api-steps', '0']
+           '--rays', str(n), '--full', '--cpu-rays', '0', '--api-steps', '0']      # (--full: the line's `check` is read below)
     envv = dict(os.environ, TRC_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     p = subprocess.run(cmd, cwd=root, env=envv, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
@@ -640,7 +640,7 @@ def test_bench_strong_scaling_gives_the_same_tallies_for_every_world_size(ctx):
     for world in (1, 2, 4):
         port = 29900 + os.getpid() % 300 + world
         tail = [os.path.join(root, 'bench.py'), '--gpus', str(world), '--steps', str(steps), '--warmup', str(warmup), '--rays', str(n),
-                '--cpu-rays', '0', '--api-steps', '0', '--scaling', 'strong']
+                '--full', '--cpu-rays', '0', '--api-steps', '0', '--scaling', 'strong']      # (--full: the lines' `check` is compared)
         cmd = [sys.executable] + tail if world == 1 else \
             [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(world), '--master-addr', '127.0.0.1',
              '--master-port', str(port)] + tail
@@ -655,6 +655,32 @@ def test_bench_strong_scaling_gives_the_same_tallies_for_every_world_size(ctx):
         for key in ('receiver_hits', 'heliostat_hits', 'segments_total'):
             assert c[key] == c1[key], (world, key)
         assert N.isclose(c['receiver_kW'], c1['receiver_kW'], rtol=1e-12) and N.isclose(c['fluxmap_sum_kW'], c1['fluxmap_sum_kW'], rtol=1e-12)
+
+
+def test_bench_plain_run_prints_the_headline_alone(ctx):
+    """
+    bench.py without --full: set-up, warm-up, the timed steps and the line -- `value` is the steps' segments over their time, and
+    none of the legs that take time of their own (CPU baseline, check against the reference, public entry point, other
+    configurations, counter figures) is in the line, whatever the options that trim them say.
+    """
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, steps, warmup = 3000000, 2, 1
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', str(warmup), '--rays', str(n)]
+    p = subprocess.run(cmd, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert out['full'] is False and out['n_gpus'] == 1 and out['steps'] == steps and out['warmup'] == warmup
+    assert out['metric'] == 'Mray-bounces/s on Sandia NSTTF field' and out['unit'] == 'Mray-bounces/s' and out['dtype'] == 'f64'
+    assert out['higher_is_better'] is True and out['value'] > 0. and out['ms_per_step'] > 0.
+    for leg in ('cpu_baseline', 'check', 'api_level', 'other_configs'):
+        assert leg not in out, leg
+    assert not {'traffic', 'kernels', 'hbm_measured_frac'} & set(out['roofline'])
+    seg = out['config']['segments_per_step_per_gpu'] * steps
+    assert n * steps <= seg and N.isclose(out['value'], seg / (out['ms_per_step'] * 1e-3 * steps) / 1e6, rtol=1e-6)
+    assert 'CPU baseline' not in p.stderr.decode()
 
 
 def test_forms_of_the_fast_engine_end_every_ray_alike(ctx):

@@ -7,7 +7,7 @@ V=${1:-v1}
 O=$GRAFT_REPO_ROOT/gpurun_out/r3ev_$V
 mkdir -p $O
 R=$GRAFT_REPO_ROOT
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
 python -c "import json; d=json.load(open('$O/bench.json')); print('bench', round(d['value']), round(d['ms_per_step'],3), round(d['roofline']['kernel_ms_per_launch'],3), round(d['roofline']['frac'],3))"
 (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 4 --warmup 2 --cpu-rays 0 --api-steps 0 --no-extras > $O/stats.log 2>&1)
 python3 tools/ktrace_span.py $O/stats > $O/span.txt 2>&1 || true
